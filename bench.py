@@ -15,8 +15,16 @@ SURVEY.md 8(d) protocol runs: 50 warm-up steps, 1000 timed steps, 5 repeats, the
 episode boundaries at 150 steps).
 
 Prints ONE JSON line (rank 0) with `roofline` (HBM, algorithmic bytes/env-step from SURVEY.md 8(d) x
-envs per launch / mean kernel time from hipEvents on the launch stream) and `cpu_baseline` (the C
-oracle, float32, OpenMP over envs, bounded sample, on this box's host cores).
+envs per launch / mean kernel time from hipEvents on the launch stream; null when the timed steps carried no live events).
+
+A plain run does only what the headline figure needs: set up, warm up, time the steps, print the line.  `--full` adds what
+takes runs of its own: `cpu_baseline` (the C oracle, float32, OpenMP over envs, bounded sample, on the host cores), config 2's
+`ms_per_step_one_launch_per_step`, and the host-issued passes that time the step kernel with HIP events when the timed steps
+were graph replays.
+
+`--dump-outputs DIR` writes what the timed path computed in its last step (rank 0's shard) as DIR/<name>.npy, float32 or
+float64, at most 64 MB (a fixed, seeded sample of envs beyond that): the wrapped env state for configs 1 and 2, the physics
+state for config 5, the trained network and normaliser for config 3.  Inputs are seeded, so equal arguments give equal inputs.
 """
 import argparse
 import json
@@ -125,6 +133,64 @@ def cpu_baseline(n_envs=512, steps=100, solver="cg", iterations=(8, 8)):
             "sample": f"{n_envs} envs x {steps} env-steps (10 substeps each), C oracle float32, OpenMP over envs, {dt:.1f} s"}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def state_arrays(state):
+    """The arrays a caller of the wrapped step receives (env.State), copied to the host: observation, reward, done, the physics state,
+    the metrics and the wrappers' per-env counters.  The AutoReset wrapper's stored first states repeat the reset and are left out."""
+    out = {"obs": state.obs, "reward": state.reward, "done": state.done}
+    for k in ("qpos", "qvel", "act", "qacc_warmstart"):
+        out[k] = getattr(state.pipeline_state, k)
+    for k, v in state.metrics.items():
+        if torch.is_tensor(v):
+            out["metrics." + k] = v
+    for k, v in state.info.items():
+        if torch.is_tensor(v) and not k.startswith("first_"):
+            out["info." + k] = v
+    return {k: v.detach().cpu().numpy() for k, v in out.items() if v is not None}
+
+
+def params_arrays(params):
+    """(normaliser, policy network) as ppo.train returns them: every tensor leaf, copied to the host."""
+    out = {}
+
+    def walk(prefix, x):
+        if torch.is_tensor(x):
+            out[prefix] = x.detach().cpu().numpy()
+        elif isinstance(x, torch.nn.Module):
+            for k, v in x.state_dict().items():
+                walk(f"{prefix}.{k}", v)
+        elif isinstance(x, dict):
+            for k, v in x.items():
+                walk(f"{prefix}.{k}", v)
+        elif isinstance(x, (list, tuple)):
+            for i, v in enumerate(x):
+                walk(f"{prefix}.{getattr(x, '_fields', range(len(x)))[i]}", v)
+        elif hasattr(x, "__dataclass_fields__"):
+            for k in x.__dataclass_fields__:
+                walk(f"{prefix}.{k}", getattr(x, k))
+    walk("normalizer", params[0])
+    walk("policy", params[1])
+    return out
+
+
+def write_outputs(out_dir, arrays, n_envs):
+    """DIR/<name>.npy in float32 (float64 stays float64; integer and boolean arrays become float64, exactly).  Beyond 64 MB in all,
+    every array whose leading axis is the env axis keeps the same fixed, seeded sample of envs (ascending)."""
+    arrays = {k: np.asarray(v, np.float64 if v.dtype == np.float64 or v.dtype.kind in "iub" else np.float32) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    per_env = sum(v.nbytes for v in arrays.values() if v.ndim and v.shape[0] == n_envs) / n_envs
+    if total > DUMP_LIMIT_BYTES and per_env:
+        fixed = total - per_env * n_envs
+        keep = max(1, int((DUMP_LIMIT_BYTES - fixed) // per_env))
+        rows = np.sort(np.random.default_rng(0).choice(n_envs, keep, replace=False))
+        arrays = {k: (v[rows] if v.ndim and v.shape[0] == n_envs else v) for k, v in arrays.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+
+
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -143,6 +209,10 @@ def parse():
     ap.add_argument("--solver", default="cg", choices=("cg", "newton"), help="config 2 only; the headline configuration is cg 8/8")
     ap.add_argument("--iterations", type=int, default=8)
     ap.add_argument("--ls-iterations", type=int, default=8)
+    ap.add_argument("--full", action="store_true", help="also measure what the headline figure does not need: the CPU baseline, "
+                    "config 2's one-launch-per-step figure, host-issued kernel-timing passes")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the timed path computed in its last step to "
+                    "DIR/<name>.npy (float32 / float64, at most 64 MB)")
     args = ap.parse_args()
     args.protocol = "driver" if (args.steps is not None or args.warmup is not None) else "survey-8d"
     if args.config == 3:
@@ -289,6 +359,7 @@ def main():
     gen = torch.Generator(device=dev)
     gen.manual_seed(1234 + rank)
     extra = {}
+    outputs = None            # --dump-outputs: host copies of what the last timed step computed
     if args.config == 3:
         # ---- the full PPO loop: a "step" is one TRAINING step = 64 unrolls x 10 env steps x N envs + 512 minibatch updates
         from rodent_amd.training.agents.ppo import train as ppo
@@ -297,11 +368,13 @@ def main():
         env._batch.set_timing(True)
         times = []
         fence()
-        ppo.train(environment=env, num_timesteps=500_000_000, num_evals=100, reward_scaling=1, episode_length=150,
-                  normalize_observations=True, action_repeat=1, unroll_length=10, num_minibatches=64, num_updates_per_batch=8,
-                  discounting=0.97, learning_rate=5e-5, entropy_cost=1e-3, num_envs=N * world, batch_size=N * world, seed=0,
-                  num_eval_envs=0, max_training_steps=args.warmup + args.steps, timing_fn=times.append)
+        _, params, _ = ppo.train(environment=env, num_timesteps=500_000_000, num_evals=100, reward_scaling=1, episode_length=150,
+                                 normalize_observations=True, action_repeat=1, unroll_length=10, num_minibatches=64, num_updates_per_batch=8,
+                                 discounting=0.97, learning_rate=5e-5, entropy_cost=1e-3, num_envs=N * world, batch_size=N * world, seed=0,
+                                 num_eval_envs=0, max_training_steps=args.warmup + args.steps, timing_fn=times.append)
         fence()
+        if args.dump_outputs and rank == 0:
+            outputs = params_arrays(params)
         timed = times[args.warmup:]
         elapsed = max_over_ranks(sum(t["rollout_s"] + t["learner_s"] for t in timed))
         env_steps_per_step = timed[0]["env_steps"]            # global (all ranks)
@@ -319,7 +392,7 @@ def main():
         batch = env._batch
         repeats_ms = [elapsed / len(timed) * 1e3]
         extra["step_kernel_time_source"] = "hip events around the rollout's launches"
-        if batch.kernel_time()[1] == 0:
+        if batch.kernel_time()[1] == 0 and args.full:
             # the rollouts ran as sub-batches replayed from HIP graphs (acting.SubBatchRollout): events cannot be read back from a replayed
             # graph, so the step kernel is timed on a short host-issued pass of the same env batch (random actions)
             st_ = env.reset(0)
@@ -349,6 +422,8 @@ def main():
             fence()
             repeats_ms.append(max_over_ranks(time.perf_counter() - t0) / args.steps * 1e3)
         assert torch.isfinite(state.obs).all(), "non-finite state in the rollout"
+        if args.dump_outputs and rank == 0:
+            outputs = state_arrays(state)
         total_env_steps = N * world * args.steps
         elapsed = float(np.median(repeats_ms)) * args.steps * 1e-3
     else:
@@ -440,9 +515,13 @@ def main():
                 for sub in subs:
                     sub["state"] = sub["graph"].state
             assert all(torch.isfinite(sub["state"].obs).all() for sub in subs), "non-finite state in the rollout"
-            # kernel durations by HIP events on each sub-batch's stream: a host-issued pass over the same states (events cannot be
-            # read back from inside a replayed graph); rocprofv3's kernel trace of this command shows the replayed launches themselves
-            if UT_ == 1:
+            if args.dump_outputs and rank == 0:
+                torch.cuda.synchronize(dev)
+                parts = [state_arrays(sub["state"]) for sub in subs]
+                outputs = {k: np.concatenate([p[k] for p in parts]) if parts[0][k].ndim else parts[0][k] for k in parts[0]}
+            # kernel durations by HIP events on each sub-batch's stream (--full): a host-issued pass over the same states (events cannot
+            # be read back from inside a replayed graph); rocprofv3's kernel trace of this command shows the replayed launches themselves
+            if UT_ == 1 and args.full:
                 for sub in subs:
                     sub["env"]._batch.set_timing(True)
                 eager_steps(args.steps if args.no_graph else min(args.steps, 100))
@@ -453,7 +532,7 @@ def main():
             total_env_steps = N * world * args.steps
             elapsed = float(np.median(repeats_ms)) * args.steps * 1e-3
             extra = {"substreams": S_, "steps_per_graph_replay": None if args.no_graph else R_, "env_steps_per_launch": UT_}
-            if UT_ > 1:      # for the record, outside the timed region: the same rollout as one synchronised launch per step (Rodent.step per call)
+            if UT_ > 1 and args.full:      # for the record, outside the timed region: the same rollout as one synchronised launch per step
                 for sub in subs:
                     sub["env"]._batch.set_timing(False)
                 torch.cuda.synchronize(dev)
@@ -497,6 +576,8 @@ def main():
                 fence()
                 repeats_ms.append(max_over_ranks(time.perf_counter() - t0) / args.steps * 1e3)
             assert torch.isfinite(state["qpos"]).all(), "non-finite state in the rollout"
+            if args.dump_outputs and rank == 0:
+                outputs = {k: v.cpu().numpy() for k, v in state.items()}
             total_env_steps = N * world * args.steps
             elapsed = float(np.median(repeats_ms)) * args.steps * 1e-3
     if args.config != 2:
@@ -514,7 +595,7 @@ def main():
         per_launch = extra.get("env_steps_per_launch", 1)          # env steps of every env inside one launch
         if args.config == 3 and launches and extra.get("step_kernel_time_source", "").startswith("hip events"):
             per_launch = max(1.0, extra["rollout_steps_per_env"] / launches)
-        achieved = bytes_per_env_step * (N // concurrent) * per_launch * concurrent / avg_kernel_s / 1e9
+        achieved = bytes_per_env_step * (N // concurrent) * per_launch * concurrent / avg_kernel_s / 1e9 if launches else 0.0
         traffic, traffic_src = pmc_traffic(int(per_launch)) if args.config == 2 else (None, None)
         roof = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                 "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
@@ -530,6 +611,8 @@ def main():
                 "limiter": "VALU issue + dependent LDS/L2 latency, not HBM (SURVEY.md 8(d)); see valu_busy_frac"}
         if args.config == 2:
             roof.update(sq_counters(int(per_launch), N))
+        if not launches:          # graph-replayed steps carry no HIP events; the host-issued timing pass runs with --full
+            roof = None
         out = {
             "metric": "env-steps/sec (whole node), rodent 2048 envs/GPU", "value": value, "unit": "env-steps/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
@@ -541,8 +624,10 @@ def main():
             "roofline": roof,
             "cpu_baseline": None,
         }
-        if world == 1 and not args.no_cpu_baseline and args.config == 2:
+        if world == 1 and not args.no_cpu_baseline and args.config == 2 and args.full:
             out["cpu_baseline"] = cpu_baseline(solver=args.solver, iterations=(args.iterations, args.ls_iterations))
+        if args.dump_outputs:
+            write_outputs(args.dump_outputs, outputs, N)
         print(json.dumps(out))
     if dist is not None:
         dist.barrier()

@@ -1,8 +1,8 @@
 """Compiled model blobs shipped with the package.
 
-The reference's MJCF files live only in /root/reference (absent on the GPU box), so the models are
-compiled once where the XML is available (`build_assets`, called by __graft_entry__.build()) and the
-resulting numeric tables (assets/*.rrm) are what the package loads at run time.
+The reference's MJCF files are not part of the repository, so the models are compiled once where the
+XML is available (`build_assets`, run by hand) and the resulting numeric tables (assets/*.rrm, committed)
+are what the package loads at run time.
 """
 from __future__ import annotations
 
