@@ -269,7 +269,7 @@ struct rr_batch {
   const int32_t* env_map = nullptr;     // rr_batch_set_schedule
   uint32_t* cost = nullptr;
   bool counted = false;                 // this batch is in m->live_batches
-  unsigned* dyn_overflow = nullptr;     // DYN models: launches x envs in which more pairs penetrated than the wave has contact slots (rr_batch_contact_overflow)
+  unsigned* dyn_overflow = nullptr;     // DYN models: (env, env step) events in which more pairs penetrated than the wave has contact slots (rr_batch_contact_overflow)
   unsigned* progress = nullptr;         // pacing counter of multi-step launches (RRIO::progress); RR_PACE=0 turns pacing off
 };
 
@@ -338,8 +338,11 @@ static kern_t pick_kernel(const rr_model* m, bool prof = false, bool dbg = false
   return nullptr;
 }
 
+// Multi-step instances: the single-rodent floor-contact models (fixed-dimension or generic) and the candidate-pair models (DYN, generic
+// dimensions), CG only.  None for the Newton solver, the two-wave pair instance and other slot counts.
 static kern_t pick_unroll_kernel(const rr_model* m, bool actor = false) {
-  if (m->solver == 2 || m->dyn || !(m->NBS == 2 && m->NVS == 2 && m->NCS == 1)) return nullptr;
+  if (m->solver == 2 || !(m->NBS == 2 && m->NVS == 2 && m->NCS == 1)) return nullptr;
+  if (m->dyn) return actor ? rr_step_kernel<2, 2, 1, false, false, RRDims, false, true, true, false, true> : rr_step_kernel<2, 2, 1, false, false, RRDims, false, true, false, false, true>;
   if (actor) return RRDimsRodent::matches(m->kd) ? rr_step_kernel<2, 2, 1, false, false, RRDimsRodent, false, true, true>
                     : (RRDimsRodentNew::matches(m->kd) ? rr_step_kernel<2, 2, 1, false, false, RRDimsRodentNew, false, true, true> : rr_step_kernel<2, 2, 1, false, false, RRDims, false, true, true>);
   return RRDimsRodent::matches(m->kd) ? rr_step_kernel<2, 2, 1, false, false, RRDimsRodent, false, true>
@@ -414,9 +417,11 @@ extern "C" int rr_batch_create(const rr_model* m, int32_t num_envs, int32_t devi
   }
   if (m->dyn) {
     void* p = nullptr;
-    HIPCHK(hipMalloc(&p, 64));
-    HIPCHK(hipMemset(p, 0, 64));
+    hipError_t e = hipMalloc(&p, 64);
+    if (e != hipSuccess) { rr_batch_destroy(b); return fail(RR_EHIP, std::string("rr_batch_create: hipMalloc: ") + hipGetErrorString(e)); }
     b->dev_allocs.push_back(p);
+    e = hipMemset(p, 0, 64);
+    if (e != hipSuccess) { rr_batch_destroy(b); return fail(RR_EHIP, std::string("rr_batch_create: hipMemset: ") + hipGetErrorString(e)); }
     b->dyn_overflow = (unsigned*)p;
   }
   {
@@ -501,6 +506,7 @@ static int launch(rr_batch* b, const rr_state* st, const float* ctrl, int n_fram
     if (ac) {
       if (b->m->dims.obs_dim > 1280) return fail(RR_EUNSUPPORTED, "rr_env_unroll_policy: observation wider than 1280");
       if (ac->nhidden < 1 || ac->nhidden > 5) return fail(RR_EUNSUPPORTED, "rr_env_unroll_policy: 1 .. 5 hidden layers");
+      if (b->m->dims.nu > 64) return fail(RR_EUNSUPPORTED, "rr_env_unroll_policy: more than 64 actions (the in-kernel actor's head is at most 2 x 64 logits)");
       io.a_obs_in = ac->obs_in; io.a_mean = ac->mean; io.a_std = ac->std; io.a_W0 = ac->w0; io.a_b0 = ac->b0;
       for (int l = 1; l < ac->nhidden; ++l) { io.a_Wt[l - 1] = ac->hidden_wt[l - 1]; io.a_b[l - 1] = ac->hidden_b[l - 1]; }
       io.a_Wth = ac->head_wt; io.a_bh = ac->head_b; io.a_noise = ac->noise; io.a_actions = ac->actions_out; io.ctrl = ac->actions_out;

@@ -173,7 +173,7 @@ struct RRIO {
   const float *a_mean, *a_std;                    // nullable: observation normaliser
   const float *a_W0, *a_b0;                       // first layer [32][obs] (torch layout), [32]
   const float *a_Wt[4], *a_b[4];                  // hidden layers l = 1 .. a_nh-1: TRANSPOSED [32 in][32 out], [32]
-  const float *a_Wth, *a_bh;                      // head TRANSPOSED and padded [32 in][64], [64]
+  const float *a_Wth, *a_bh;                      // head TRANSPOSED and zero-padded: [32 in][64], [64] for A <= 32; [32 in][128], [128] for 32 < A <= 64
   const float *a_noise;                           // [T][N][A] standard normal draws
   float *a_actions;                               // [T][N][nu] out: the actions taken (also what the step reads as ctrl)
   float *t_obs, *t_raw, *t_logp, *t_reward, *t_discount, *t_trunc;     // [N][T+1][obs], [N][T][A], [N][T] x 4
@@ -185,7 +185,8 @@ struct RRIO {
   // its wave priority (Wave::env_prio): the launch ends when its SLOWEST environment does, and a wave that outranks its SIMD partner
   // runs at close to single-wave speed while the partner, which is ahead, has slack.  Timing only -- results are unaffected.
   unsigned* progress;
-  unsigned* dyn_overflow;            // DYN instances (nullable): counts (env, substep) events with more pairs in penetration than contact slots
+  unsigned* dyn_overflow;            // DYN instances (nullable): counts (env, env step) events -- an env step in one of whose substeps more pairs were in
+                                     // penetration than the wave has contact slots; a multi-step launch adds one per such step, as its single launches would
   float pace_t1, pace_t2, pace_t3;   // env steps behind the average for priority levels 1, 2, 3
   int pace_mode;                     // bits 0-1: 0 max(weight level, lag level), 1 lag level only, 2 sum capped at 3; bit 2 (4): progress counted
                                      // per SUBSTEP (ten times finer); bit 3 (8): the factor-phase priority is 3 for laggards, 2 otherwise
@@ -417,7 +418,8 @@ typedef float rr_f2 __attribute__((ext_vector_type(2)));
 // substep the wave scans it, keeps the pairs in penetration in its 64 * NCS contact slots (in list order, by ballot), and works on those:
 // J = jac(body2) - jac(body1) through SIGNED dof chains (the dofs on exactly one of the two ancestor chains; J x) and a two-interval
 // membership test (J' f); contacts of condim 1 carry one row (rows 1..3 of the slot get D = 0); transmissions with several joints (fixed
-// tendons) go through per-actuator sums.  Production physics + env epilogue only.
+// tendons) go through per-actuator sums.  Production physics + env epilogue only: single-step, multi-step (UNROLL) and multi-step with the
+// actor inside (UNROLL + ACTOR); everything DYN-specific is re-derived per substep, so the multi-step loop carries nothing extra for it.
 template <int NBS, int NVS, int NCS, class DT, bool NEWTON = false, bool PAIR = false, bool DYN = false>
 struct Wave {
   const DT& D;
@@ -455,7 +457,7 @@ struct Wave {
   int con_leaf1[NCS];     // DYN: last dof of body1's chain (-1: world)
   int con_pid[NCS];       // DYN: candidate pair held by this slot
   int con_nrow[NCS];      // DYN: rows of the slot's contact (4 = pyramid, 1 = frictionless)
-  int dyn_overflow = 0;   // DYN: pairs in penetration beyond the slots (dropped; reported through RRIO::cost bit 31)
+  int dyn_overflow = 0;   // DYN: pairs in penetration beyond the slots in a substep of this env step (dropped; counted per env step, RRIO::cost bit 31)
   int jP, jLp, jnact;     // wave-uniform: lanes per contact (4 / 2 / 1), ids per piece (12 / 20 / 36), contacts in penetration
   // per-dof registers (slot s -> dof lane + 64 s)
   float dinv[NVS], dinvB[NVS];   // 1/D of M's factor, and of the eulerdamp matrix M + dt*diag(damping)
@@ -2109,7 +2111,9 @@ static __device__ __forceinline__ RRIO load_io() {
 
 // The actor of a multi-step rollout, one wave = one env: policy MLP (obs -> 32 x a_nh -> 2A, SiLU) on the observation of step `ut`,
 // tanh-normal sample with the given noise, action into a_actions (where the step reads its ctrl), raw action and log-prob into the
-// trajectory buffers.  First layer: lane l holds the normalised observation entries l, l+64, ..; for each of the 32 units the 64
+// trajectory buffers.  Head: lane = logit.  A <= 32: one pass over the 64 padded columns, lane a fetches its scale logit from lane A + a.
+// 32 < A <= 64 (rodent_cpu.xml: 38 actuators, 76 logits): two passes over 128 padded columns, location logit a and scale logit A + a both
+// formed by lane a.  The choice is wave-uniform (A is a model dimension).  First layer: lane l holds the normalised observation entries l, l+64, ..; for each of the 32 units the 64
 // partial dot products are summed over the wave (four units per DPP reduction).  Later layers: lane n = unit n, the activation
 // vector handed around by shuffles, weights transposed so that the lanes read consecutive floats.
 // trajectory addressing: step s of the launch is step t = s % L of segment u = s / L; rows [u][env][t]
@@ -2164,10 +2168,22 @@ __device__ __forceinline__ void rr_actor_step(const RRIO& io, const DT& D, int l
       h = acc / (1.0f + expf(-acc));
     }
   }
-  float o = io.a_bh[lane];
+  float o, s_raw;
+  if (A <= 32) {
+    o = io.a_bh[lane];
 #pragma unroll
-  for (int k = 0; k < 32; ++k) o = fmaf(__shfl(h, k, RR_LANES), io.a_Wth[k * 64 + lane], o);
-  const float s_raw = __shfl(o, (A + lane) & 63, RR_LANES);      // lane a: logits[A + a]
+    for (int k = 0; k < 32; ++k) o = fmaf(__shfl(h, k, RR_LANES), io.a_Wth[k * 64 + lane], o);
+    s_raw = __shfl(o, (A + lane) & 63, RR_LANES);      // lane a: logits[A + a]
+  } else {             // host check: A <= 64, so column A + lane <= 127 lies inside the 128 padded columns for every lane
+    o = io.a_bh[lane];
+    s_raw = io.a_bh[A + lane];
+#pragma unroll
+    for (int k = 0; k < 32; ++k) {
+      const float hk = __shfl(h, k, RR_LANES);
+      o = fmaf(hk, io.a_Wth[k * 128 + lane], o);
+      s_raw = fmaf(hk, io.a_Wth[k * 128 + A + lane], s_raw);
+    }
+  }
   float lp = 0.0f;
   if (lane < A) {
     const float HALF_LOG_2PI = 0.91893853320467274178f, LOG2 = 0.69314718055994530942f;
@@ -2193,7 +2209,8 @@ template <int NBS, int NVS, int NCS, bool PROF, bool DBG, class DT, bool NEWTON 
 __global__ __launch_bounds__((PAIR ? 2 : 1) * RR_LANES, (NVS >= 3 ? 1 : 2)) void rr_step_kernel(const RRDims Dk, const RRTables T, const RRIO io_kernarg, const int num_envs,
                                                            const int n_frames) {
   static_assert(!PAIR || (!PROF && !DBG && !NEWTON && !UNROLL && !ACTOR), "PAIR: production physics instance only");
-  static_assert(!DYN || (!PROF && !DBG && !NEWTON && !UNROLL && !ACTOR && !PAIR), "DYN: production instance only");
+  static_assert(!DYN || (!PROF && !DBG && !NEWTON && !PAIR), "DYN: production instances only (single-step, multi-step, multi-step with the actor)");
+  static_assert(!ACTOR || UNROLL, "the actor lives in the multi-step instances");
   extern __shared__ __attribute__((aligned(16))) float lds[];
   int env = blockIdx.x;
   if (env >= num_envs) return;
@@ -2226,6 +2243,7 @@ __global__ __launch_bounds__((PAIR ? 2 : 1) * RR_LANES, (NVS >= 3 ? 1 : 2)) void
   float u_steps = 0.0f, u_prev_done = 0.0f;
   int u_frame = 0;
   unsigned u_work = 0;
+  int u_overflow = 0;            // DYN: some step of this launch dropped pairs (RRIO::cost bit 31 of a multi-step launch)
   if (UNROLL) {
     u_steps = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(io.steps_in[env])));
     u_prev_done = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(io.prev_done[env])));
@@ -2270,6 +2288,7 @@ __global__ __launch_bounds__((PAIR ? 2 : 1) * RR_LANES, (NVS >= 3 ? 1 : 2)) void
     w.qacc[s] = w.Ma[s] = w.grad[s] = w.Mgrad[s] = w.search[s] = w.mv[s] = w.qfrc_con[s] = 0.0f;
   }
   w.work = 0;
+  if (UNROLL && DYN) w.dyn_overflow = 0;       // per env step: the counter below then counts what the single-step launches would count
   for (int i = lane; i < D.nv; i += RR_LANES) w.s_arm[i] = T.dof_f[16 * i];
   if (NEWTON) for (int i = lane; i < (D.nM + 3) / 4; i += RR_LANES) ((int*)w.s_anc)[i] = T.anc4[i];
   if (lane < 6) w.s_cdof[6 * D.nv + lane] = 0.0f;
@@ -2455,7 +2474,8 @@ __global__ __launch_bounds__((PAIR ? 2 : 1) * RR_LANES, (NVS >= 3 ? 1 : 2)) void
   io = load_io();
   if (PROF && io.prof && lane == 0) for (int i = 0; i < RR_NPH; ++i) io.prof[(size_t)env * RR_NPH + i] = w.pt[i];
   if (UNROLL) u_work += (unsigned)w.work;        // a multi-step launch reports the work of all its steps
-  if (io.cost && lane == 0 && wrep == 0) io.cost[env] = (UNROLL ? u_work : (unsigned)w.work) | (DYN && w.dyn_overflow ? 0x80000000u : 0u);
+  if (UNROLL && DYN) u_overflow |= w.dyn_overflow;
+  if (io.cost && lane == 0 && wrep == 0) io.cost[env] = (UNROLL ? u_work : (unsigned)w.work) | (DYN && (UNROLL ? u_overflow : w.dyn_overflow) ? 0x80000000u : 0u);
   if (DYN && w.dyn_overflow && io.dyn_overflow && lane == 0) __hip_atomic_fetch_add(io.dyn_overflow, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   // ---- write back state (a multi-step rollout writes it once, after the wrappers of its last step: see below)
   if (!UNROLL) {

@@ -8,6 +8,7 @@ from __future__ import annotations
 import dataclasses
 from typing import Any, Dict, Optional
 
+import numpy as np
 import torch
 
 from .. import assets, hip
@@ -97,6 +98,9 @@ class System:
         self.dt = float(d.timestep)
         self.qpos0 = self.tables["qpos0"]
         self.ncon = d.ncon
+        # the contact list is a list of CANDIDATE pairs of two moving geoms (rodent_cpu.xml): pairs in penetration beyond the kernel's
+        # contact slots are dropped and counted (`Rodent.contact_overflow`)
+        self.candidate_contacts = bool(int(np.asarray(self.tables.get("k_dyn", 0)).reshape(-1)[0]))
         # integer ids as the LOADED model holds them (C ABI rr_model_table): Contact.geom1 / geom2 and brax's link_idx
         # (= geom_bodyid[g] - 1) [NB mjcf.ipynb:917-921]
         self.contact_geom1 = self.model.table("con_geom1")

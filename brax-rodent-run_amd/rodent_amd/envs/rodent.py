@@ -75,6 +75,12 @@ class Rodent(PipelineEnv):
         """A sibling env with another batch size (ppo.train builds its per-rank and eval envs this way)."""
         return Rodent(num_envs=num_envs, device=device or self.device, **self._ctor)
 
+    def contact_overflow(self) -> int:
+        """(env, env step) events so far in which more sphere / capsule pairs were in penetration than the kernel's 64 contact slots;
+        the surplus pairs were DROPPED for that substep (models with candidate-pair contacts, e.g. rodent_cpu.xml; always 0 for the
+        floor-contact models).  Reads a device counter: synchronises the env's stream."""
+        return self._batch.contact_overflow()
+
     def _env_io(self, cur_frame, obs, reward=None, done=None, metrics=None):
         return dict(track_pos=self._track_pos, cur_frame=cur_frame, obs=obs, reward=reward, done=done, metrics=metrics,
                     healthy_reward=self._healthy_reward, ctrl_cost_weight=self._ctrl_cost_weight,

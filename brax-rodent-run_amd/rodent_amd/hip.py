@@ -290,7 +290,8 @@ class Batch:
                                     _ptr(cur_frame_in, torch.int32, self.N), C.byref(o) if o else None))
 
     def contact_overflow(self) -> int:
-        """(launch, env) events with more pairs in penetration than contact slots (candidate-pair models; synchronises the stream)."""
+        """(env, env step) events with more pairs in penetration than contact slots -- a multi-step launch counts each of its steps
+        (candidate-pair models; 0 for the others; synchronises the stream)."""
         n = C.c_int64()
         _check(lib().rr_batch_contact_overflow(self.h, C.byref(n)))
         return int(n.value)
@@ -313,7 +314,8 @@ class Batch:
     def env_unroll_policy(self, st_in, st_out, T: int, n_frames: int, env, cur_frame_in, first, first_obs, prev_done, steps_in, steps_out,
                           truncation_out, episode_length: float, actor: dict, noise, actions_out, traj: dict, obs_in, segment: int = 0):
         """T x [policy -> sample -> wrapped env step] with the transitions recorded, one launch (C ABI `rr_env_unroll_policy`).
-        actor: mean, std (or None), w0, b0, hidden_wt / hidden_b (lists, transposed weights), head_wt, head_b (padded), min_std;
+        actor: mean, std (or None), w0, b0, hidden_wt / hidden_b (lists, transposed weights), head_wt, head_b (padded to 64 columns for
+        up to 32 actions, to 128 for 33 .. 64), min_std;
         traj: obs [N, T+1, K], raw_action [N, T, A], log_prob / reward / discount / truncation [N, T] (contiguous views); with
         `segment` = L < T: U = T / L such blocks ([U, N, L+1, K], ...), a whole rollout phase of U unrolls."""
         for t in (first_obs, prev_done, steps_in, steps_out, truncation_out, noise, actions_out, obs_in, actor["w0"], actor["b0"],
@@ -324,9 +326,10 @@ class Batch:
         L_ = segment or T
         if T % L_:
             raise ValueError("rr_env_unroll_policy: the number of steps must be a multiple of the segment length")
+        HW = 64 if A_ <= 32 else 128                   # head layout: [32][64] up to 32 actions, [32][128] for 33 .. 64
         if (noise.numel() != T * self.N * A_ or actions_out.numel() != T * self.N * A_ or traj["obs"].numel() != (T // L_) * self.N * (L_ + 1) * K
                 or traj["raw_action"].numel() != self.N * T * A_ or any(traj[k].numel() != self.N * T for k in ("log_prob", "reward", "discount", "truncation"))
-                or actor["w0"].shape != (32, K) or actor["head_wt"].shape != (32, 64) or actor["head_b"].numel() != 64):
+                or actor["w0"].shape != (32, K) or actor["head_wt"].shape != (32, HW) or actor["head_b"].numel() != HW):
             raise ValueError("rr_env_unroll_policy: inconsistent shapes")
         w = RRUnrollIO(self._state(first), first_obs.data_ptr(), prev_done.data_ptr(), steps_in.data_ptr(), steps_out.data_ptr(),
                        truncation_out.data_ptr(), float(episode_length))

@@ -48,15 +48,22 @@ def generate_unroll(env, state, policy: Callable, buf: UnrollBuffer, u: int, gen
     return state
 
 
+ACTOR_MAX_ACTIONS = 64      # the in-kernel actor: lane = action, so at most one wave of actions (head <= 128 logits, two passes)
+
+
 def actor_params(policy_net, normalizer_params, min_std: float) -> dict:
     """The policy's parameters in the layout of the in-kernel actor (`rr_env_unroll_policy`): first layer as torch holds it, hidden
-    weights transposed, head transposed and zero-padded to 64 outputs.  Copies: call again after the parameters change."""
+    weights transposed, head transposed and zero-padded to 64 outputs (heads of up to 64 logits: one pass of the wave) or to 128
+    outputs (65 .. 128 logits, i.e. 33 .. 64 actions: two passes).  Copies: call again after the parameters change."""
     layers = list(policy_net.layers)
     dev = layers[0].weight.device
     P = layers[-1].out_features
-    head_wt = torch.zeros(32, 64, device=dev)
+    if P > 2 * ACTOR_MAX_ACTIONS:
+        raise ValueError(f"actor_params: a head of {P} outputs exceeds the in-kernel actor's {2 * ACTOR_MAX_ACTIONS}")
+    W = 64 if P <= 64 else 128
+    head_wt = torch.zeros(32, W, device=dev)
     head_wt[:, :P] = layers[-1].weight.detach().t()
-    head_b = torch.zeros(64, device=dev)
+    head_b = torch.zeros(W, device=dev)
     head_b[:P] = layers[-1].bias.detach()
     out = dict(w0=layers[0].weight.detach().contiguous(), b0=layers[0].bias.detach().contiguous(),
                hidden_wt=[l.weight.detach().t().contiguous() for l in layers[1:-1]], hidden_b=[l.bias.detach().contiguous() for l in layers[1:-1]],
@@ -66,15 +73,23 @@ def actor_params(policy_net, normalizer_params, min_std: float) -> dict:
     return out
 
 
-def fused_unroll_supported(wenv, policy_net, dist) -> bool:
-    """The one-launch unroll needs the fused wrapper of a HIP rodent env (rollout configuration) and the default policy shape."""
-    from .. import hip
+def actor_shape_supported(policy_net, action_size: int) -> bool:
+    """The policy shapes the in-kernel actor evaluates: 1 .. 4 hidden layers of 32 units, float32, a head of 2 x action_size
+    logits with action_size <= 64.  (The LEARNER's kernels have their own, narrower head limit -- `fused_mlp.fusable(.., 64)` in
+    `ppo.train` -- which decides the learner's path only.)"""
     from . import fused_mlp
+    ls = list(policy_net.layers)
+    return (2 <= len(ls) <= 5 and all(l.out_features == fused_mlp.POLICY_HIDDEN for l in ls[:-1]) and ls[0].weight.dtype == torch.float32
+            and ls[-1].out_features == 2 * action_size and 1 <= action_size <= ACTOR_MAX_ACTIONS)
+
+
+def fused_unroll_supported(wenv, policy_net, dist) -> bool:
+    """The one-launch unroll needs the fused wrapper of a HIP rodent env (rollout configuration) whose model has a multi-step kernel
+    instance, and a policy the in-kernel actor evaluates (`actor_shape_supported`)."""
     base = wenv.unwrapped if hasattr(wenv, "unwrapped") else wenv
     return (isinstance(wenv, wrappers.FusedEpisodeAutoResetWrapper) and hasattr(base, "unroll_policy_wrapped") and base.device.type == "cuda"
             and not base._pipeline_outputs and not base._contact_outputs and getattr(getattr(base, "sys", None), "solver", "cg") == "cg"
-            and fused_mlp.fusable(policy_net, fused_mlp.POLICY_HIDDEN, 64) and 2 <= len(policy_net.layers) <= 5
-            and policy_net.layers[-1].out_features == 2 * dist.event_size and dist.event_size == base.action_size <= 32
+            and policy_net.layers[0].weight.is_cuda and dist.event_size == base.action_size and actor_shape_supported(policy_net, base.action_size)
             and base.observation_size <= 1280 and base._batch.unroll_supported(with_actor=True))
 
 

@@ -14,6 +14,7 @@ import math
 import logging
 import os
 import time
+import warnings
 from typing import Callable, Optional, Tuple
 
 import numpy as np
@@ -267,6 +268,14 @@ def train(
 
     D.time_collectives(timing_fn is not None)
 
+    # Models with candidate-pair contacts (rodent_cpu.xml) drop the pairs in penetration beyond the kernel's contact slots and count the
+    # (env, env step) events: reported as training/contact_overflow (events since the previous report), with one warning.  The counter is
+    # read after the training step's closing synchronisation, never inside the rollout.
+    overflow_envs = []
+    if getattr(getattr(env, "sys", None), "candidate_contacts", False) and hasattr(env, "contact_overflow"):
+        overflow_envs = [sub["env"] for sub in sub_rollout.subs] if sub_rollout is not None else [env]
+    overflow = {"total": 0, "reported": 0, "warned": False}
+
     def training_step():
         nonlocal env_state, normalizer_params
         t0 = time.time()
@@ -314,7 +323,15 @@ def train(
             # (0 on one rank); SURVEY.md 8(d): rollout / learner / all-reduce
             timing_fn({"rollout_s": t1 - t0, "learner_s": t2 - t1, "allreduce_s": D.pop_collective_seconds(),
                        "env_steps": env_step_per_training_step})
-        return {f"training/{k}": float(v) for k, v in metrics.items()}
+        out = {f"training/{k}": float(v) for k, v in metrics.items()}
+        if overflow_envs:
+            overflow["total"] = sum(e.contact_overflow() for e in overflow_envs)
+            out["training/contact_overflow"] = float(overflow["total"] - overflow["reported"])
+            if overflow["total"] and not overflow["warned"]:
+                overflow["warned"] = True
+                warnings.warn(f"ppo.train: {overflow['total']} (env, step) events so far with more than 64 contact pairs in penetration; the "
+                              "surplus pairs were dropped for those substeps (training/contact_overflow counts them)", RuntimeWarning, stacklevel=2)
+        return out
 
     metrics = {}
     if process_id == 0 and evaluator is not None and num_evals > 1:
@@ -355,6 +372,7 @@ def train(
             else:
                 metrics = dict(training_metrics)
             progress_fn(current_step, metrics)
+            overflow["reported"] = overflow["total"]
             # callbacks get a SNAPSHOT (the live network keeps training)
             policy_params_fn(current_step, make_policy, params_tuple(normalizer_params.clone(), copy.deepcopy(policy_net).requires_grad_(False),
                                                                      normalize_observations))

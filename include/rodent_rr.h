@@ -135,11 +135,16 @@ int rr_env_step_to(rr_batch* b, const rr_state* in, const rr_state* out_state, c
  * bit.  `in` / `out_state` / `env` / `cur_frame_in` as rr_env_step_to (obs, reward, done, metrics, cur_frame of the LAST step are
  * written); `wrap`: the stored first state and first observation (restored where an episode ends), the wrappers' state before the
  * launch (prev_done, steps_in [N]) and after it (steps_out, truncation_out [N]; the final done goes to env->done).
- * Production instance only (no rr_outputs); RR_EUNSUPPORTED for models without a multi-step instance and for the Newton solver. */
+ * Production instance only (no rr_outputs).  Models with a multi-step instance (CG solver): the single-rodent floor-contact models
+ * (rodent_optimized / rodent_new and any model of their slot counts) and the candidate-pair models (rodent_cpu.xml:
+ * self-collisions, tendon transmissions).  RR_EUNSUPPORTED for the Newton solver and for models of other slot counts (rodent_pair.xml);
+ * rr_batch_unroll_supported tells. */
 /* Models whose contact list is a list of candidate pairs (contacts between two moving bodies, e.g. rodent_cpu.xml [REF models/rodent_cpu.xml]):
  * the kernel keeps the pairs in penetration in 64 contact slots per environment; pairs beyond that are DROPPED for that substep.  *events = the
- * number of (launch, environment) events in which that happened since the batch was created (synchronises the batch's stream); always 0 for
- * the floor-contact models, whose every contact has its own slot. */
+ * number of (environment, step) events in which that happened since the batch was created, a step being one launch of rr_pipeline_step /
+ * rr_env_step (all its n_frames substeps) or ONE of the num_steps env steps of rr_env_unroll / rr_env_unroll_policy: a multi-step launch
+ * adds exactly what the same steps as single launches add.  Synchronises the batch's stream.  Always 0 for the floor-contact models,
+ * whose every contact has its own slot. */
 int rr_batch_contact_overflow(rr_batch* b, int64_t* events);
 
 /* 1 when this batch's model / solver has a multi-step kernel instance (with_actor != 0: the one with the actor inside), else 0. */
@@ -164,8 +169,12 @@ int rr_env_unroll(rr_batch* b, const rr_state* in, const rr_state* out_state, co
  * traj_log_prob / traj_reward / traj_discount (= 1 - done) / traj_truncation [N][T] (with segment_length L < T: U = T / L such
  * blocks one after the other -- a whole rollout phase of U unrolls in one launch); actions_out [T][N][A] receives tanh(raw).
  * Weights: w0 [32][obs] and b0 [32] as torch holds them; hidden_wt[l-1] (l = 1 .. nhidden-1) TRANSPOSED [32 in][32 out];
- * head_wt TRANSPOSED and zero-padded to [32][64], head_b padded to [64]; noise [T][N][A] standard normal draws.
- * The final observation is traj_obs[:, T] (env->obs is not written).  Instances for the single-rodent models (rr_batch_unroll_supported). */
+ * head_wt TRANSPOSED (column j = logit j: columns 0 .. A-1 the location logits, A .. 2A-1 the scale logits) and zero-padded, head_b
+ * padded alike, in one of TWO layouts chosen by the model's action count A = nu: A <= 32: head_wt [32][64], head_b [64] (one pass of
+ * the wave over the head); 32 < A <= 64: head_wt [32][128], head_b [128] (two passes; rodent_cpu.xml, A = 38).  The kernel reads the
+ * whole padded width, so the arrays must have it.  A > 64: RR_EUNSUPPORTED.  noise [T][N][A] standard normal draws.
+ * The final observation is traj_obs[:, T] (env->obs is not written).  Instances for the models rr_env_unroll serves
+ * (rr_batch_unroll_supported(b, 1)). */
 typedef struct rr_actor_io {
   const float* obs_in; const float* mean; const float* std;
   const float* w0; const float* b0;
