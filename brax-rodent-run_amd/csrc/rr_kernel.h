@@ -142,6 +142,24 @@ struct RRTables {
   rr_gi act_i, act_m_i;      // transmission (DYN instances): per actuator (first moment entry, count); per entry (dof, qpos address)
   rr_gf act_m_f;             // ... coefficient per entry
 };
+// The tables the solver's loops read (level schedules, solve jobs, contact chains): the only table pointers a wave keeps in scalar
+// registers.  Every other table is read through load_tables() at the head of the phase that uses it (see RRKArgs).
+struct RRLoopTables { rr_gi factor3, linv, coljob, rowjob, jobown, con_chain_rows; };
+static __device__ __forceinline__ RRTables load_tables();      // defined with RRKArgs below
+static __device__ __forceinline__ RRDims load_dims();
+// A table row as (wave-uniform base, unsigned 32-bit byte offset of the row, element offset inside it): the address the device's
+// global_load takes as SGPR pair + 32-bit VGPR + immediate.  Indexing a table pointer with an `int` instead makes every lane carry a
+// 64-bit address built by sign extension, a 64-bit multiply-add and register-pair copies (3-5 vector instructions per row).
+// Row and element indices are non-negative by construction (ids of bodies / dofs / joints / contacts / actuators).
+typedef const char __attribute__((address_space(1)))* rr_gc;
+template <class E>
+struct rr_row {
+  rr_gc base; unsigned off; int k0;
+  __device__ __forceinline__ E operator[](int k) const { return *(const E __attribute__((address_space(1)))*)(base + (size_t)off + (ptrdiff_t)sizeof(E) * (k0 + k)); }
+  __device__ __forceinline__ rr_row operator+(int k) const { return rr_row{base, off, k0 + k}; }
+};
+__device__ __forceinline__ rr_row<int> row_at(rr_gi t, int stride, int idx) { return rr_row<int>{(rr_gc)t, (unsigned)idx * (4u * (unsigned)stride), 0}; }
+__device__ __forceinline__ rr_row<float> row_at(rr_gf t, int stride, int idx) { return rr_row<float>{(rr_gc)t, (unsigned)idx * (4u * (unsigned)stride), 0}; }
 
 struct RRIO {
   float *qpos, *qvel, *act, *warm;                         // state written by the launch
@@ -199,6 +217,7 @@ struct v3 { float x, y, z; };
 __device__ __forceinline__ v3 mk3(float x, float y, float z) { v3 r; r.x = x; r.y = y; r.z = z; return r; }
 __device__ __forceinline__ v3 ld3(const float* p) { return mk3(p[0], p[1], p[2]); }
 __device__ __forceinline__ v3 ld3(const float __attribute__((address_space(1)))* p) { return mk3(p[0], p[1], p[2]); }
+__device__ __forceinline__ v3 ld3(const rr_row<float>& p) { return mk3(p[0], p[1], p[2]); }
 __device__ __forceinline__ void st3(float* p, v3 a) { p[0] = a.x; p[1] = a.y; p[2] = a.z; }
 __device__ __forceinline__ v3 operator+(v3 a, v3 b) { return mk3(a.x + b.x, a.y + b.y, a.z + b.z); }
 __device__ __forceinline__ v3 operator-(v3 a, v3 b) { return mk3(a.x - b.x, a.y - b.y, a.z - b.z); }
@@ -355,6 +374,7 @@ __device__ __forceinline__ float div_nr(float a, float b) { float r = __builtin_
 // Table loads in the hot loops must be GLOBAL loads: when the optimiser loses the address space of a table pointer it
 // emits flat_load, which also counts on lgkmcnt -- every LDS wait would then drain the table prefetch as well.
 __device__ __forceinline__ int g_int(const int __attribute__((address_space(1)))* base, int idx) { return base[idx]; }
+__device__ __forceinline__ int g_int32(rr_gi base, int idx) { return row_at(base, 1, idx)[0]; }      // ... through a 32-bit offset (idx >= 0)
 
 // Identity the optimiser cannot see through: stops loop-invariant code motion from unpacking every packed index
 // table entry once, ahead of the solver loops, and keeping hundreds of unpacked indices / addresses alive in
@@ -371,8 +391,8 @@ struct BodyC {
 __device__ __forceinline__ BodyC load_bodyc(const RRTables& T, int b, int nbody) {
   BodyC c;
   const bool ok = b >= 1 && b < nbody;
-  auto bi = T.body_i + RR_BODYI * (ok ? b : 0);
-  auto bf = T.body_f + 18 * (ok ? b : 0);
+  auto bi = row_at(T.body_i, RR_BODYI, ok ? b : 0);
+  auto bf = row_at(T.body_f, 18, ok ? b : 0);
   c.parent = bi[0]; c.jadr = bi[1]; c.jn = ok ? bi[2] : 0; c.dofadr = bi[3]; c.dofnum = bi[4];
   c.depth = ok ? bi[8] : -1; c.sib = bi[9];
 #pragma unroll
@@ -380,8 +400,8 @@ __device__ __forceinline__ BodyC load_bodyc(const RRTables& T, int b, int nbody)
 #pragma unroll
   for (int k = 0; k < 4; ++k) c.quat[k] = bf[3 + k];
   const int j = c.jn > 0 ? c.jadr : 0;
-  auto ji = T.jnt_i + 4 * j;
-  auto jf = T.jnt_f + 8 * j;
+  auto ji = row_at(T.jnt_i, 4, j);
+  auto jf = row_at(T.jnt_f, 8, j);
   c.jtype0 = c.jn > 0 ? ji[0] : 3; c.jqa0 = ji[1]; c.jda0 = ji[2];
 #pragma unroll
   for (int k = 0; k < 3; ++k) { c.jpos0[k] = jf[k]; c.jaxis0[k] = jf[3 + k]; }
@@ -410,6 +430,8 @@ __device__ __forceinline__ BodyC load_bodyc(const RRTables& T, int b, int nbody)
 #define RR_REP_KIN 0
 #endif
 typedef float rr_f2 __attribute__((ext_vector_type(2)));
+template <class A, class B> struct rr_same { static constexpr bool value = false; };
+template <class A> struct rr_same<A, A> { static constexpr bool value = true; };
 // PAIR: the model is two identical trees that share no constraint (rodent_pair.xml: M block-diagonal, floor contacts only); the
 // workgroup is TWO wavefronts, wave r steps replica r on the tables of one replica in its own LDS region, and the only coupling is the
 // CG solver's scalars (cost, gradient norm, line-search sums, Polak-Ribiere beta): every such wave sum is followed by an exchange
@@ -423,7 +445,7 @@ typedef float rr_f2 __attribute__((ext_vector_type(2)));
 template <int NBS, int NVS, int NCS, class DT, bool NEWTON = false, bool PAIR = false, bool DYN = false>
 struct Wave {
   const DT& D;
-  const RRTables& T;
+  RRLoopTables TL;
   int lane;               // re-derived (opaquely) at the head of every substep: see RR_FRAME_LOCAL in the kernel
   float* const lds;
   int rep = 0;            // PAIR: this wave's replica (wave-uniform)
@@ -475,14 +497,24 @@ struct Wave {
   int con_nanc[NCS];
   float com0[3], com1[3];
   float gauss, cost, prev_cost;
+  // solver options, read from the kernel arguments at the head of solve() and held in scalar registers through its loops only
+  float so_tolerance, so_ls_tolerance, so_meaninertia;
+  int so_iterations, so_ls_iterations, so_nv_scale;
   int work;               // wave-uniform count of line-search point evaluations, weighted by row blocks: the scheduling cost estimate (rr_batch_set_schedule)
   unsigned long long pt_last, pt[RR_NPH];
   template <bool PROF> __device__ __forceinline__ void stamp(int i) {
     if (PROF) { const unsigned long long t = __builtin_readcyclecounter(); pt[i] += t - pt_last; pt_last = t; }
   }
 
+  // Run-time dimensions for one phase.  The fixed-dimension instances read the few scalars a phase needs (dt, gravity, schedule
+  // lengths) from the kernel arguments at its head, so none of them is held -- or spilled -- across the substep; the generic
+  // instances index by dozens of run-time dimensions in every phase and keep the resident copy.
+  __device__ __forceinline__ DT phase_dims() const {
+    if constexpr (rr_same<DT, RRDims>::value) return D;
+    else return DT(load_dims());
+  }
   __device__ Wave(const DT& d, const RRTables& t, float* l)
-      : D(d), T(t), lane(threadIdx.x & (RR_LANES - 1)), lds(l) {
+      : D(d), TL{t.factor3, t.linv, t.coljob, t.rowjob, t.jobown, t.con_chain_rows}, lane(threadIdx.x & (RR_LANES - 1)), lds(l) {
     s_qpos = l + d.o_qpos; s_qvel = l + d.o_qvel; s_act = l + d.o_act; s_ctrl = l + d.o_ctrl;
     s_xpos = l + d.o_xpos; s_xquat = l + d.o_xquat; s_cinert = l + d.o_cinert; s_crb = s_cinert;
     s_cdof = l + d.o_cdof; s_cvel = l + d.o_cvel; s_qLD = l + d.o_qLD;
@@ -490,6 +522,9 @@ struct Wave {
     s_vec = l + d.o_vec; s_x = l + d.o_x; s_arm = l + d.o_arm; s_warm = l + d.o_warm; s_qact = l + d.o_qact;
     s_jlist = (int*)(l + d.o_jlist);
     s_H = l + d.o_H; s_Mp = l + d.o_Mp; s_anc = (unsigned char*)(l + d.o_anc);
+    // plain values from here on: as loads from the argument block the allocator re-issues them (a scalar load and its wait) inside the
+    // solver's loops instead of keeping them
+    asm("" : "+s"(TL.coljob), "+s"(TL.rowjob), "+s"(TL.jobown));
   }
 
   // One wavefront owns the environment: its LDS instructions execute in program order, so a cross-lane hand-off through LDS
@@ -558,17 +593,18 @@ struct Wave {
   // T[b] <- T[anc_k(b)] o T[b], anc_{k+1} = anc_k o anc_k (ancestor tables in registers), all bodies busy every
   // round, instead of one serial step per tree level (38-39 of them, a handful of active lanes each).
   // Joint anchors / axes are kept in the parent frame (raw, in the cdof cells) and mapped to the world in com_pos.
-  __device__ __forceinline__ BodyC bodyc(int s) const { return s == 0 ? bc0 : (s == 1 ? bc1 : load_bodyc(T, lane + RR_LANES * s, D.nbody)); }
+  __device__ __forceinline__ BodyC bodyc(const RRTables& T, int s) const { return s == 0 ? bc0 : (s == 1 ? bc1 : load_bodyc(T, lane + RR_LANES * s, D.nbody)); }
   // k is a run-time round counter: select the word instead of indexing the register array (a dynamic index would
   // push the whole object into scratch memory)
   __device__ __forceinline__ int anc_at(int s, int k) const { const int wd = k < 4 ? banc[s][0] : banc[s][1]; return (wd >> (8 * (k & 3))) & 255; }
 
   __device__ __forceinline__ void kinematics() {
+    const RRTables T = load_tables();
 #pragma unroll
     for (int s = 0; s < NBS; ++s) {
       const int b = lane + RR_LANES * s;
       if (s > 0 && !__any(b < D.nbody)) continue;
-      const BodyC c = bodyc(s);
+      const BodyC c = bodyc(T, s);
       if (b >= 1 && b < D.nbody) {
         float quat[4], mat[9];
         v3 pos = mk3(c.pos[0], c.pos[1], c.pos[2]);
@@ -584,8 +620,8 @@ struct Wave {
             jt = c.jtype0; qa = c.jqa0; da = c.jda0; q0 = c.jq00;
             jp = mk3(c.jpos0[0], c.jpos0[1], c.jpos0[2]); ja = mk3(c.jaxis0[0], c.jaxis0[1], c.jaxis0[2]);
           } else {   // 2nd / 3rd joint of a multi-joint body: parameters from the tables
-            auto ji = T.jnt_i + 4 * (c.jadr + jj);
-            auto jf = T.jnt_f + 8 * (c.jadr + jj);
+            auto ji = row_at(T.jnt_i, 4, c.jadr + jj);
+            auto jf = row_at(T.jnt_f, 8, c.jadr + jj);
             jt = ji[0]; qa = ji[1]; da = ji[2]; q0 = jf[6];
             jp = ld3(jf); ja = ld3(jf + 3);
           }
@@ -664,6 +700,7 @@ struct Wave {
 
   // ---------------------------------------------------------------- A-2 com_pos: subtree COM per root, cinert, cdof
   __device__ __forceinline__ void com_pos() {
+    const RRTables T = load_tables();
     float acc[2][3] = {{0, 0, 0}, {0, 0, 0}};
     float xip[NBS][3];
 #pragma unroll
@@ -671,7 +708,7 @@ struct Wave {
       const int b = lane + RR_LANES * s;
       xip[s][0] = xip[s][1] = xip[s][2] = 0;
       if (b >= 1 && b < D.nbody) {
-        auto bf = T.body_f + 18 * b;
+        auto bf = row_at(T.body_f, 18, b);
         float bq[4], R[9];
 #pragma unroll
         for (int k = 0; k < 4; ++k) bq[k] = s_xquat[4 * b + k];
@@ -679,7 +716,7 @@ struct Wave {
         v3 xi = ld3(s_xpos + 3 * b) + mat_vec(R, ld3(bf + 7));
         xip[s][0] = xi.x; xip[s][1] = xi.y; xip[s][2] = xi.z;
         const float mass = bf[14];
-        if (T.body_i[RR_BODYI * b + 5] == 0) { acc[0][0] += mass * xi.x; acc[0][1] += mass * xi.y; acc[0][2] += mass * xi.z; }
+        if (row_at(T.body_i, RR_BODYI, b)[5] == 0) { acc[0][0] += mass * xi.x; acc[0][1] += mass * xi.y; acc[0][2] += mass * xi.z; }
         else                { acc[1][0] += mass * xi.x; acc[1][1] += mass * xi.y; acc[1][2] += mass * xi.z; }
       }
     }
@@ -692,7 +729,7 @@ struct Wave {
     for (int s = 0; s < NBS; ++s) {
       const int b = lane + RR_LANES * s;
       if (b >= 1 && b < D.nbody) {
-        auto bf = T.body_f + 18 * b;
+        auto bf = row_at(T.body_f, 18, b);
         float q[4], bq[4], iq[4], R[9];
 #pragma unroll
         for (int k = 0; k < 4; ++k) { bq[k] = s_xquat[4 * b + k]; iq[k] = bf[10 + k]; }
@@ -700,7 +737,7 @@ struct Wave {
         quat_to_mat(R, q);
         const float mass = bf[14];
         const float I0 = bf[15], I1 = bf[16], I2 = bf[17];
-        const v3 cm = get_com(T.body_i[RR_BODYI * b + 5]);
+        const v3 cm = get_com(row_at(T.body_i, RR_BODYI, b)[5]);
         const float d0 = xip[s][0] - cm.x, d1 = xip[s][1] - cm.y, d2 = xip[s][2] - cm.z;
         float t[9];
 #pragma unroll
@@ -780,12 +817,14 @@ struct Wave {
   }
 
   __device__ __forceinline__ void velocity_sweep() {
+    const RRTables T = load_tables();
+    const DT D = phase_dims();   // the run-time scalars this phase reads (dt, gravity, schedule lengths): local to it, like T
     // own contribution of every body
 #pragma unroll
     for (int s = 0; s < NBS; ++s) {
       const int b = lane + RR_LANES * s;
       if (s > 0 && !__any(b < D.nbody)) continue;
-      const BodyC c = bodyc(s);
+      const BodyC c = bodyc(T, s);
       if (b >= 1 && b < D.nbody) {
         float v[6] = {0, 0, 0, 0, 0, 0};
         for (int k = 0; k < c.dofnum; ++k) {
@@ -804,7 +843,7 @@ struct Wave {
     for (int s = 0; s < NBS; ++s) {
       const int b = lane + RR_LANES * s;
       if (s > 0 && !__any(b < D.nbody)) continue;
-      const BodyC c = bodyc(s);
+      const BodyC c = bodyc(T, s);
       if (b >= 1 && b < D.nbody) {
         const int p = c.parent, da = c.dofadr, dn = c.dofnum;
         float v[6], a[6] = {0, 0, 0, 0, 0, 0};
@@ -925,9 +964,10 @@ struct Wave {
 
   static constexpr int NME = NVS == 1 ? 10 : (NVS == 2 ? 18 : 35);   // sparse-M entries per lane (nM <= 64*NME)
   __device__ __forceinline__ void load_ment(int* ment) {
+    const RRTables T = load_tables();
     const int ol = opaque(lane);
 #pragma unroll
-    for (int it = 0; it < NME; ++it) ment[it] = g_int(T.M_ij_k, ol + RR_LANES * it);
+    for (int it = 0; it < NME; ++it) ment[it] = g_int32(T.M_ij_k, ol + RR_LANES * it);
   }
   // ---------------------------------------------------------------- A-3 qM (sparse) from crb and cdof
   __device__ __forceinline__ void mass_matrix() {
@@ -1073,15 +1113,17 @@ struct Wave {
   __device__ __forceinline__ void factor() {
     int ment[NME];          // for the row scaling at the end; requested now, local to this call (not held across the solver)
     load_ment(ment);
+    const RRTables T = load_tables();
+    const DT D = phase_dims();   // the run-time scalars this phase reads (dt, gravity, schedule lengths): local to it, like T
     if (lane < 8) s_qLD[2 * D.nM + lane] = (lane >> 1) == 1 ? 1.0f : ((lane >> 1) == 3 ? -1.0f : 0.0f);     // cells ZERO, ONE, TRASH, MINUS_ONE of the row schedules
     for (int c = lane; c < 2 * D.nalias; c += RR_LANES) s_buf[c] = 0.0f;      // alias copies of the hot rows (levelsched.py): pose cells, dead from here to the row scaling
 #pragma unroll
     for (int s = 0; s < NVS; ++s) {
       const int d = lane + RR_LANES * s;
-      if (d < D.nv) s_qLD[2 * (opaque(dofc1[s]) & 0xFFFF) + 1] += D.dt * T.dof_f[16 * d + 1];
+      if (d < D.nv) s_qLD[2 * (opaque(dofc1[s]) & 0xFFFF) + 1] += D.dt * row_at(T.dof_f, 16, d)[1];
     }
     sync();
-    run_levels<true>(PAIR ? T.factor3 + rep * D.fac_stride : T.factor3, D.nfac);
+    run_levels<true>(PAIR ? TL.factor3 + rep * D.fac_stride : TL.factor3, D.nfac);
     sync();
 #pragma unroll
     for (int s = 0; s < NVS; ++s) {
@@ -1108,7 +1150,10 @@ struct Wave {
   // of them per factorisation; with W they become two independent sparse products (ldl_solve).  Gauss-Jordan, shallow dofs
   // first (k_linv, a row program like the factorisation's): for dof k every descendant row i does W_ia -= W_ik W_ka over the
   // strict ancestors a of k; W_ik must still hold L_ik (deeper dofs overwrite it later) and row k must be final.
-  __device__ __forceinline__ void invert() { run_levels<false>(PAIR ? T.linv + rep * D.inv_stride : T.linv, D.ninv); }
+  __device__ __forceinline__ void invert() {
+    const DT D = phase_dims();   // the run-time scalars this phase reads (dt, gravity, schedule lengths): local to it, like T
+    run_levels<false>(PAIR ? TL.linv + rep * D.inv_stride : TL.linv, D.ninv);
+  }
 
   // x <- (L' D L)^-1 x = U D^-1 U' x  [MuJoCo mj_solveLD] with the explicit inverse factor U = I - W (see invert): no
   // dependent chain, no atomics.  U' b sums column j over its descendants i (a contiguous DFS range, entry (i, j) at
@@ -1125,17 +1170,18 @@ struct Wave {
   __device__ __forceinline__ void load_jobs(Jobs& j) {
     constexpr int WJ = NJS * RR_LANES;
     const int ol = opaque(lane);
+    const rr_row<int> cj = row_at(TL.coljob, 1, ol), rj = row_at(TL.rowjob, 1, ol), jo = row_at(TL.jobown, 1, ol);   // one 32-bit lane offset, the rest immediates
 #pragma unroll
     for (int s = 0; s < NJS; ++s) {
 #pragma unroll
-      for (int k = 0; k < 8; ++k) j.cw[s][k] = 2 * k < D.lmax ? g_int(T.coljob, k * WJ + s * RR_LANES + ol) : 0;
-      j.ci0[s] = g_int(T.coljob, 8 * WJ + s * RR_LANES + ol);
+      for (int k = 0; k < 8; ++k) j.cw[s][k] = 2 * k < D.lmax ? cj[k * WJ + s * RR_LANES] : 0;
+      j.ci0[s] = cj[8 * WJ + s * RR_LANES];
 #pragma unroll
-      for (int k = 0; k < 4; ++k) j.rb[s][k] = 4 * k < D.lmax ? g_int(T.rowjob, k * WJ + s * RR_LANES + ol) : 0;
-      j.ra[s] = g_int(T.rowjob, 4 * WJ + s * RR_LANES + ol);
+      for (int k = 0; k < 4; ++k) j.rb[s][k] = 4 * k < D.lmax ? rj[k * WJ + s * RR_LANES] : 0;
+      j.ra[s] = rj[4 * WJ + s * RR_LANES];
     }
 #pragma unroll
-    for (int s = 0; s < NVS; ++s) j.own[s] = ol + RR_LANES * s < D.nv ? g_int(T.jobown, ol + RR_LANES * s) : 0;
+    for (int s = 0; s < NVS; ++s) j.own[s] = ol + RR_LANES * s < D.nv ? jo[RR_LANES * s] : 0;
   }
   // column piece: sum_t mat[cw_t] * vec[i0 + t];  row piece: sum_t mat[ra + t] * vec[rb_t]   (mat = one half of the pair array)
   __device__ __forceinline__ float col_piece(const Jobs& j, int s, const float* mat, const float* vec) const {
@@ -1235,6 +1281,7 @@ struct Wave {
 
   // ---------------------------------------------------------------- passive + actuation + qfrc_smooth (per dof)
   __device__ __forceinline__ void smooth_forces(float* bias_out, float* passive_out) {
+    const RRTables T = load_tables();
     if (DYN) {      // transmission with several joints per actuator (fixed tendons [REF models/rodent_cpu.xml:505-560]; UP mjx smooth.transmission):
                     // lane = actuator: length = sum coef qpos, velocity = sum coef qvel, force -> the (dead) pose cells, read per dof below
       if (lane < D.nu) {
@@ -1245,7 +1292,7 @@ struct Wave {
           len += c * s_qpos[T.act_m_i[2 * (e0 + e) + 1]];
           vel += c * s_qvel[T.act_m_i[2 * (e0 + e)]];
         }
-        auto af = T.act_f + 8 * u;
+        auto af = row_at(T.act_f, 8, u);
         s_buf[u] = af[0] * s_act[u] + af[1] + af[2] * len + af[3] * vel;
       }
       sync();
@@ -1256,8 +1303,8 @@ struct Wave {
       qfrc_smooth[s] = 0.0f;
       bias_out[s] = passive_out[s] = 0.0f;
       if (d < D.nv) {
-        auto di = T.dof_i + RR_DOFI * d;
-        auto df = T.dof_f + 16 * d;
+        auto di = row_at(T.dof_i, RR_DOFI, d);
+        auto df = row_at(T.dof_f, 16, d);
         const float qv = s_qvel[d];
         float passive = -df[1] * qv;
         if (di[2] == 6) passive -= df[2] * (s_qpos[di[6]] - df[3]);
@@ -1268,7 +1315,7 @@ struct Wave {
           if (DYN) {
             actf = df[14] * s_buf[u];          // moment coefficient of this dof x the actuator's force
           } else {
-            auto af = T.act_f + 8 * u;
+            auto af = row_at(T.act_f, 8, u);
             const float a = s_act[u];
             actf = af[0] * a + af[1] + af[2] * s_qpos[di[6]] + af[3] * qv;
           }
@@ -1285,6 +1332,8 @@ struct Wave {
   // Runs right after com_pos while xpos / xquat are still live; the Jacobian is never materialised: a contact keeps
   // its offset from the tree COM and its frame, and J x / J' f are evaluated on the fly from cdof (J-free products).
   __device__ __forceinline__ void contact_geometry(float* dbg, float* o_dist = nullptr, float* o_pos = nullptr, float* o_frame = nullptr) {
+    const RRTables T = load_tables();
+    const DT D = phase_dims();   // the run-time scalars this phase reads (dt, gravity, schedule lengths): local to it, like T
 #pragma unroll
     for (int cs = 0; cs < NCS; ++cs) {
       const int c = lane + RR_LANES * cs;
@@ -1296,8 +1345,8 @@ struct Wave {
 #pragma unroll
       for (int k = 0; k < 9; ++k) con_fr[cs][k] = 0;
       if (c < D.ncon) {
-        auto ci = T.con_i + 8 * c;
-        auto cf = T.con_f + 26 * c;
+        auto ci = row_at(T.con_i, 8, c);
+        auto cf = row_at(T.con_f, 26, c);
         const int kind = ci[0], b = ci[1], r = ci[2];
         float gq[4], bq[4], q[4], gm[9], xm[9];
 #pragma unroll
@@ -1391,9 +1440,9 @@ struct Wave {
     if (dot(e1, e1) < dot(e2, e2)) pa = na; else pb = nb;
   }
   // pair p: signed distance, contact point, normal (geom1 -> geom2); kinds 4 sphere-sphere, 5 sphere-capsule, 6 capsule-capsule
-  __device__ __forceinline__ float pair_geometry(int p, v3& pos, v3& n) const {
-    auto ci = T.con_i + 8 * p;
-    auto cf = T.con_f + 32 * p;
+  __device__ __forceinline__ float pair_geometry(const RRTables& T, int p, v3& pos, v3& n) const {
+    auto ci = row_at(T.con_i, 8, p);
+    auto cf = row_at(T.con_f, 32, p);
     const int kind = ci[0], b1 = ci[1], b2 = ci[2];
     v3 c[2], ax[2];
     float rad[2], hl[2];
@@ -1421,11 +1470,13 @@ struct Wave {
     return dist;
   }
   __device__ __forceinline__ void contact_geometry_dyn() {
+    const RRTables T = load_tables();
+    const DT D = phase_dims();   // the run-time scalars this phase reads (dt, gravity, schedule lengths): local to it, like T
     int count = 0;
     for (int p0 = 0; p0 < D.ncon; p0 += RR_LANES) {          // scan: which candidate pairs are in penetration
       const int p = p0 + lane;
       bool pen = false;
-      if (p < D.ncon) { v3 pos_, n_; pen = pair_geometry(p, pos_, n_) < 0.0f; }
+      if (p < D.ncon) { v3 pos_, n_; pen = pair_geometry(T, p, pos_, n_) < 0.0f; }
       const unsigned long long mk = __ballot(pen);
       if (pen) {
         const int slot = count + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mk >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mk, 0u));
@@ -1449,10 +1500,10 @@ struct Wave {
       for (int k = 0; k < 9; ++k) con_fr[cs][k] = 0;
       if (slot < count) {
         const int p = s_jlist[slot];
-        auto ci = T.con_i + 8 * p;
-        auto cf = T.con_f + 32 * p;
+        auto ci = row_at(T.con_i, 8, p);
+        auto cf = row_at(T.con_f, 32, p);
         v3 pos, n;
-        const float dist = pair_geometry(p, pos, n);
+        const float dist = pair_geometry(T, p, pos, n);
         const v3 yb = (n.y > -0.5f && n.y < 0.5f) ? mk3(0, 1, 0) : mk3(0, 0, 1);       // make_frame(n)
         v3 fb = yb - n * dot(n, yb);
         fb = fb * (1.0f / sqrtf(dot(fb, fb)));
@@ -1476,14 +1527,16 @@ struct Wave {
 
   // ---------------------------------------------------------------- A-5 constraint rows (limits; contact aref)
   __device__ __forceinline__ void constraint_rows(float* dbg) {
+    const RRTables T = load_tables();
+    const DT D = phase_dims();   // the run-time scalars this phase reads (dt, gravity, schedule lengths): local to it, like T
 #pragma unroll
     for (int s = 0; s < NVS; ++s) {
       const int d = lane + RR_LANES * s;
       lim_act[s] = false; lim_sign[s] = 0; lim_D[s] = 0; lim_aref[s] = 0; lim_jar[s] = 0; lim_jv[s] = 0;
       if (d < D.nv) {
-        auto di = T.dof_i + RR_DOFI * d;
+        auto di = row_at(T.dof_i, RR_DOFI, d);
         if (di[8]) {
-          auto df = T.dof_f + 16 * d;
+          auto df = row_at(T.dof_f, 16, d);
           const float q = s_qpos[di[6]];
           const float dmin_ = q - df[4], dmax_ = df[5] - q;
           const float pos = fminf(dmin_, dmax_);
@@ -1521,6 +1574,7 @@ struct Wave {
   // per substep the chains of the contacts in penetration are cut into pieces of 12 / 20 / 36 dofs, 4 / 2 / 1 lanes per
   // contact (as many as fit 64 * NCS lanes), the lanes of a contact adjacent so that a quad DPP add joins the pieces.
   __device__ __forceinline__ void contact_jobs() {
+    const RRTables T = load_tables();
     int n_act = 0;
 #pragma unroll
     for (int cs = 0; cs < NCS; ++cs) {
@@ -1537,7 +1591,7 @@ struct Wave {
       const int c = lane + RR_LANES * cs;
       if (DYN) continue;           // DYN: the slots ARE the contacts in penetration (rank = slot) and s_jlist already holds their pair ids
       if (con_act[cs]) s_jlist[con_rank[cs]] = c;
-      con_leaf[cs] = c < D.ncon ? (g_int(T.con_chain_rows, 9 * c) & 255) : 0;
+      con_leaf[cs] = c < D.ncon ? (g_int32(TL.con_chain_rows, 9 * c) & 255) : 0;
     }
     sync();
 #pragma unroll
@@ -1548,12 +1602,13 @@ struct Wave {
       for (int k = 0; k < JW; ++k) jch[js][k] = pad;
       if (r < n_act) {
         const int c = s_jlist[r], start = p * jLp;
-        const int left = g_int(T.con_i, 8 * c + 4) - start;
+        const int left = row_at(T.con_i, 8, c)[4] - start;
         const int n = left < 0 ? 0 : (left > jLp ? jLp : left);
+        const rr_row<int> chain = row_at(TL.con_chain_rows, 1, JW * c + (start >> 2));
 #pragma unroll
         for (int k = 0; k < JW; ++k) {
           if (4 * k < jLp) {
-            const int v = g_int(T.con_chain_rows, JW * c + (start >> 2) + k);   // the table has a slack row
+            const int v = chain[k];   // the table has a slack row
             const int keep = n - 4 * k;                                          // ids of this int that belong to the piece
             const unsigned msk = keep >= 4 ? 0xFFFFFFFFu : (keep <= 0 ? 0u : (1u << (8 * keep)) - 1u);
             jch[js][k] = (v & msk) | (pad & ~msk);
@@ -1568,19 +1623,27 @@ struct Wave {
   // contact's lane through the dead pose cells), taken at the contact point and projected on the frame
   __device__ __forceinline__ void jac_mul(float (*out)[4], const float* vec) {
     const int sh = jP == 4 ? 2 : (jP == 2 ? 1 : 0);
+    // LDS byte address of cdof as ONE scalar the optimiser cannot split: a motion vector's address is then a single multiply-add
+    // (24 * id + base) and its three 8-byte reads differ by immediates.  Left to itself the optimiser shares 4 * id with the vector
+    // read and rebuilds 24 * id + base from it in three instructions per id (shift-add, multiply-add, add of the region offset).
+    int cdof8 = (int)(unsigned)(size_t)(rr_lf)s_cdof;
+    asm("" : "+s"(cdof8));
 #pragma unroll
     for (int js = 0; js < NCS; ++js) {
       float w[6] = {0, 0, 0, 0, 0, 0};
 #pragma unroll
       for (int t0 = 0; t0 < 4 * JW; t0 += 4) {
         if (t0 < jLp) {     // wave-uniform; no per-lane predicate: ids beyond the piece are nv (zero vector)
+          const int ids = opaque(jch[js][t0 >> 2]);     // one opaque copy per register of four ids
 #pragma unroll
           for (int u = 0; u < 4; ++u) {
-            const int id = (opaque(jch[js][t0 >> 2]) >> (8 * u)) & 255;
+            const int id = (ids >> (8 * u)) & 255;
             const int dd = DYN ? (id & 127) : id;
             float xv = vec[dd];
             if (DYN && (id & 128)) xv = -xv;           // a dof of body1's chain: J = jac(body2) - jac(body1)
-            const float* cd = s_cdof + 6 * dd;
+            const int ca = cdof8 + 24 * dd;            // rows of cdof are 24 bytes from a 16-byte aligned base: 8-byte reads
+            const rr_f2 c01 = lds_ld2(ca), c23 = lds_ld2(ca + 8), c45 = lds_ld2(ca + 16);
+            const float cd[6] = {c01.x, c01.y, c23.x, c23.y, c45.x, c45.y};
 #pragma unroll
             for (int i = 0; i < 6; ++i) w[i] += cd[i] * xv;
           }
@@ -1777,7 +1840,7 @@ struct Wave {
     load_ment(ment);
     if (lane < 8) s_H[2 * D.nM + lane] = (lane >> 1) == 1 ? 1.0f : 0.0f;     // cells ZERO, ONE, TRASH (+ pad)
     sync();
-    run_levels<true, true>(T.factor3, D.nfac, delta);
+    run_levels<true, true>(TL.factor3, D.nfac, delta);
     sync();
 #pragma unroll
     for (int s = 0; s < NVS; ++s) {
@@ -1795,7 +1858,7 @@ struct Wave {
       }
     }
     sync();
-    run_levels<false, true>(T.linv, D.ninv, delta);
+    run_levels<false, true>(TL.linv, D.ninv, delta);
     sync();
   }
 
@@ -1921,8 +1984,8 @@ struct Wave {
       }
     }
     solver_sum_n<4>(red);
-    const float smag = sqrtf(red[0]) * D.meaninertia * (float)D.nv_scale;
-    const float gtol = D.tolerance * D.ls_tolerance * smag;
+    const float smag = sqrtf(red[0]) * so_meaninertia * (float)so_nv_scale;
+    const float gtol = so_tolerance * so_ls_tolerance * smag;
     const float qg[3] = {gauss, red[1] - red[2], 0.5f * red[3]};
     stamp<PROF>(17);
     LSPoint p0, lo, hi, tmp3[3];
@@ -1934,7 +1997,7 @@ struct Wave {
     stamp<PROF>(18);
     bool swap = true;
     work += 4 * (1 + (R > RR_LANES ? 1 : 0));          // the four evaluations outside the bracketing loop
-    for (int it = 0; it < D.ls_iterations; ++it) {
+    for (int it = 0; it < so_ls_iterations; ++it) {
       work += 3 * (1 + (R > RR_LANES ? 1 : 0));        // the bracketing loop is what separates slow from fast environments
       bool done = !swap;
       done |= (lo.d0 < 0) && (lo.d0 > -gtol);
@@ -1975,7 +2038,12 @@ struct Wave {
   // [UP mjx solver.solve] primal CG with warm start; returns the iteration count
   template <bool PROF>
   __device__ __forceinline__ int solve() {
-    const float scale = 1.0f / (D.meaninertia * (float)D.nv_scale);
+    {
+      const DT Dl = phase_dims();
+      so_tolerance = Dl.tolerance; so_ls_tolerance = Dl.ls_tolerance; so_meaninertia = Dl.meaninertia;
+      so_iterations = Dl.iterations; so_ls_iterations = Dl.ls_iterations; so_nv_scale = Dl.nv_scale;
+    }
+    const float scale = 1.0f / (so_meaninertia * (float)so_nv_scale);
     // warm start [UP mjx solver.solve]: cost at qacc_smooth, cost at qacc_warmstart, then the full context at the cheaper
     // of the two.  One copy of the evaluation code, driven by a wave-uniform phase counter.
     float cost_smooth = 0.0f;
@@ -2002,9 +2070,9 @@ struct Wave {
 #pragma unroll
       for (int s = 0; s < NVS; ++s) g2 += grad[s] * grad[s];
       const float gradient = sqrtf(solver_sum(g2)) * scale;
-      bool done = niter >= D.iterations;
-      done |= improvement < D.tolerance;
-      done |= gradient < D.tolerance;
+      bool done = niter >= so_iterations;
+      done |= improvement < so_tolerance;
+      done |= gradient < so_tolerance;
       if (uni(done)) break;
       stamp<PROF>(12);
       for (int rep = 0; rep < RR_REP_LS; ++rep) linesearch<false>();
@@ -2038,13 +2106,15 @@ struct Wave {
 #pragma unroll
     for (int s = 0; s < NVS; ++s) qa[s] = qfrc_smooth[s] + qfrc_con[s];
     ldl_solve<true>(qa);
+    const RRTables T = load_tables();
+    const DT D = phase_dims();   // the run-time scalars this phase reads (dt, gravity, schedule lengths): local to it, like T
 #pragma unroll
     for (int s = 0; s < NVS; ++s) {
       const int d = lane + RR_LANES * s;
       if (d < D.nv) {
-        const int u = DYN ? -1 : T.dof_i[RR_DOFI * d + 7];      // DYN: an actuator may drive several dofs -- integrated per actuator below
+        const int u = DYN ? -1 : row_at(T.dof_i, RR_DOFI, d)[7];      // DYN: an actuator may drive several dofs -- integrated per actuator below
         if (u >= 0) {   // filter activation dynamics: act_dot = (clamp(ctrl) - act) / tau
-          auto af = T.act_f + 8 * u;
+          auto af = row_at(T.act_f, 8, u);
           const float c = fminf(fmaxf(s_ctrl[u], af[5]), af[6]);
           s_act[u] += D.dt * ((c - s_act[u]) / fmaxf(af[4], RR_MINVAL));
         }
@@ -2052,7 +2122,7 @@ struct Wave {
       }
     }
     if (DYN && lane < D.nu) {
-      auto af = T.act_f + 8 * lane;
+      auto af = row_at(T.act_f, 8, lane);
       const float c = fminf(fmaxf(s_ctrl[lane], af[5]), af[6]);
       s_act[lane] += D.dt * ((c - s_act[lane]) / fmaxf(af[4], RR_MINVAL));
     }
@@ -2061,7 +2131,7 @@ struct Wave {
     for (int s = 0; s < NVS; ++s) {
       const int d = lane + RR_LANES * s;
       if (d < D.nv) {
-        const int kind = T.dof_i[RR_DOFI * d + 2], qadr = T.dof_i[RR_DOFI * d + 6];
+        const int kind = row_at(T.dof_i, RR_DOFI, d)[2], qadr = row_at(T.dof_i, RR_DOFI, d)[6];
         if (kind == 6 || kind < 3) {
           s_qpos[qadr] += D.dt * s_qvel[d];
         } else if (kind == 3) {  // quaternion of the free joint: q <- normalize(q * exp(dt*w/2)), w in the body frame
@@ -2099,6 +2169,27 @@ static_assert(alignof(RRDims) == 4 && alignof(RRTables) == 8 && alignof(RRIO) ==
 static_assert(offsetof(RRKArgs, T) == rr_align_up(sizeof(RRDims), alignof(RRTables)), "RRTables follows RRDims at its natural alignment");
 static_assert(offsetof(RRKArgs, io) == rr_align_up(offsetof(RRKArgs, T) + sizeof(RRTables), alignof(RRIO)), "RRIO follows RRTables at its natural alignment");
 static_assert(offsetof(RRKArgs, num_envs) == offsetof(RRKArgs, io) + sizeof(RRIO) && sizeof(RRIO) % 8 == 0, "scalars follow RRIO without padding");
+// ... and so are the model tables outside the solver's loops: RRTables is re-read at the head of each phase that indexes a table
+// (narrow scalar loads next to an existing hand-off; the unused members' loads are dead), so no table pointer is held across the
+// substep.  The loops' own tables are the exception (RRLoopTables, taken once from the parameter).
+static __device__ __forceinline__ RRTables load_tables() {
+#if defined(__HIP_DEVICE_COMPILE__)
+  const char __attribute__((address_space(4)))* p = (const char __attribute__((address_space(4)))*)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(p));
+  return *(const RRTables __attribute__((address_space(4)))*)(p + offsetof(RRKArgs, T));
+#else
+  return RRTables{};
+#endif
+}
+static __device__ __forceinline__ RRDims load_dims() {
+#if defined(__HIP_DEVICE_COMPILE__)
+  const char __attribute__((address_space(4)))* p = (const char __attribute__((address_space(4)))*)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(p));
+  return *(const RRDims __attribute__((address_space(4)))*)(p + offsetof(RRKArgs, D));
+#else
+  return RRDims{};
+#endif
+}
 static __device__ __forceinline__ RRIO load_io() {
 #if defined(__HIP_DEVICE_COMPILE__)
   const char __attribute__((address_space(4)))* p = (const char __attribute__((address_space(4)))*)__builtin_amdgcn_kernarg_segment_ptr();
@@ -2206,7 +2297,7 @@ __device__ __forceinline__ void rr_actor_step(const RRIO& io, const DT& D, int l
 // dof count), the state arrays are the model's ([N][2 nq] ...: replica r of environment e is row 2 e + r of an [2 N][nq] array).
 // Physics only (pipeline_init / pipeline_step: no env epilogue, no optional outputs, no debug dump).
 template <int NBS, int NVS, int NCS, bool PROF, bool DBG, class DT, bool NEWTON = false, bool UNROLL = false, bool ACTOR = false, bool PAIR = false, bool DYN = false>
-__global__ __launch_bounds__((PAIR ? 2 : 1) * RR_LANES, (NVS >= 3 ? 1 : 2)) void rr_step_kernel(const RRDims Dk, const RRTables T, const RRIO io_kernarg, const int num_envs,
+__global__ __launch_bounds__((PAIR ? 2 : 1) * RR_LANES, (NVS >= 3 ? 1 : 2)) void rr_step_kernel(const RRDims Dk, const RRTables Tk, const RRIO io_kernarg, const int num_envs,
                                                            const int n_frames) {
   static_assert(!PAIR || (!PROF && !DBG && !NEWTON && !UNROLL && !ACTOR), "PAIR: production physics instance only");
   static_assert(!DYN || (!PROF && !DBG && !NEWTON && !PAIR), "DYN: production instances only (single-step, multi-step, multi-step with the actor)");
@@ -2218,7 +2309,7 @@ __global__ __launch_bounds__((PAIR ? 2 : 1) * RR_LANES, (NVS >= 3 ? 1 : 2)) void
   // LDS -- checked on the HOST for every instance a batch may launch (rr_batch_create: hipFuncGetAttributes().sharedSizeBytes == 0)
   const DT D(Dk);
   const int wrep = PAIR ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0;
-  Wave<NBS, NVS, NCS, DT, NEWTON, PAIR, DYN> w(D, T, PAIR ? lds + wrep * (D.lds_bytes_rep >> 2) : lds);
+  Wave<NBS, NVS, NCS, DT, NEWTON, PAIR, DYN> w(D, Tk, PAIR ? lds + wrep * (D.lds_bytes_rep >> 2) : lds);
   int lane = threadIdx.x & (RR_LANES - 1);
   if (PAIR) { w.rep = wrep; w.s_xc = lds + 2 * (D.lds_bytes_rep >> 2); }
   RRIO io = load_io();
@@ -2226,7 +2317,6 @@ __global__ __launch_bounds__((PAIR ? 2 : 1) * RR_LANES, (NVS >= 3 ? 1 : 2)) void
     env = __builtin_amdgcn_readfirstlane(io.env_map[env]);   // only decides which two of them share a SIMD
     if ((unsigned)env >= (unsigned)num_envs) return;
   }
-  const int senv = PAIR ? 2 * env + wrep : env;      // row of this wave's replica in the state arrays
   if (DBG) {   // the re-read block must be the real parameter, word for word; on a mismatch say so in the dump and touch nothing else
     const RRIO ref_io = io_kernarg;
     bool same = true;
@@ -2253,6 +2343,8 @@ __global__ __launch_bounds__((PAIR ? 2 : 1) * RR_LANES, (NVS >= 3 ? 1 : 2)) void
   float xq1[4] = {1, 0, 0, 0};   // xquat of body 1 at the last forward pass (obs: xmat[1])
  for (int ut = 0; ut < nsteps; ++ut) {
   if (UNROLL) { lane = opaque(lane); w.lane = lane; asm volatile("" : "+s"(env)); io = load_io(); }
+  const RRTables T = load_tables();
+  const int senv = PAIR ? 2 * env + wrep : env;      // row of this wave's replica in the state arrays (from the step's own copy of env: see RR_FRAME_LOCAL)
   const size_t ctrl_at = UNROLL ? ((size_t)ut * num_envs + env) * D.nu : (size_t)senv * D.nu;
   if (ACTOR) {
     if (ut == 0) {       // the observation the rollout starts from is row 0 of the env's trajectory
@@ -2278,8 +2370,8 @@ __global__ __launch_bounds__((PAIR ? 2 : 1) * RR_LANES, (NVS >= 3 ? 1 : 2)) void
     const int d = lane + RR_LANES * s;
     if ((!UNROLL || ut == 0) && d < D.nv) w.s_warm[d] = io.warm_in[(size_t)senv * D.nv + d];
     if (d < D.nv) {
-      auto di = T.dof_i + RR_DOFI * d;
-      w.dofc0[s] = (di[3] & 255) | ((di[2] & 15) << 8) | ((di[9] & 15) << 12) | ((di[0] & 255) << 16) | ((T.body_i[RR_BODYI * di[0]] & 255) << 24);
+      auto di = row_at(T.dof_i, RR_DOFI, d);
+      w.dofc0[s] = (di[3] & 255) | ((di[2] & 15) << 8) | ((di[9] & 15) << 12) | ((di[0] & 255) << 16) | ((row_at(T.body_i, RR_BODYI, di[0])[0] & 255) << 24);
       w.dofc1[s] = (di[4] & 0xFFFF) | (di[10] << 16);
     } else {
       w.dofc0[s] = 255 | (6 << 8);
@@ -2289,7 +2381,7 @@ __global__ __launch_bounds__((PAIR ? 2 : 1) * RR_LANES, (NVS >= 3 ? 1 : 2)) void
   }
   w.work = 0;
   if (UNROLL && DYN) w.dyn_overflow = 0;       // per env step: the counter below then counts what the single-step launches would count
-  for (int i = lane; i < D.nv; i += RR_LANES) w.s_arm[i] = T.dof_f[16 * i];
+  for (int i = lane; i < D.nv; i += RR_LANES) w.s_arm[i] = row_at(T.dof_f, 16, i)[0];
   if (NEWTON) for (int i = lane; i < (D.nM + 3) / 4; i += RR_LANES) ((int*)w.s_anc)[i] = T.anc4[i];
   if (lane < 6) w.s_cdof[6 * D.nv + lane] = 0.0f;
   if (lane == 0) w.s_qvel[D.nv] = 0.0f;
@@ -2315,6 +2407,7 @@ __global__ __launch_bounds__((PAIR ? 2 : 1) * RR_LANES, (NVS >= 3 ? 1 : 2)) void
     // the solver made the allocator spill them to scratch (HBM-side write traffic ~80x the algorithmic bytes); a plain
     // reload costs the same read and no write.  `opaque` keeps the loads inside the substep loop.
     {
+      const RRTables T = load_tables();
       const int ol = opaque(lane);
       w.bc0 = load_bodyc(T, ol, D.nbody);
       if (NBS > 1) w.bc1 = load_bodyc(T, ol + RR_LANES, D.nbody);
@@ -2322,9 +2415,9 @@ __global__ __launch_bounds__((PAIR ? 2 : 1) * RR_LANES, (NVS >= 3 ? 1 : 2)) void
       for (int s = 0; s < NBS; ++s) {
         const int b = ol + RR_LANES * s;
         const bool ok = b >= 1 && b < D.nbody;
-        w.banc[s][0] = ok ? T.body_anc[2 * b] : 0;
-        w.banc[s][1] = ok ? T.body_anc[2 * b + 1] : 0;
-        w.blast[s] = ok ? T.body_i[RR_BODYI * b + 10] : 0;
+        w.banc[s][0] = ok ? row_at(T.body_anc, 2, b)[0] : 0;
+        w.banc[s][1] = ok ? row_at(T.body_anc, 2, b)[1] : 0;
+        w.blast[s] = ok ? row_at(T.body_i, RR_BODYI, b)[10] : 0;
       }
     }
     if (lane == 0) {  // world body entries (their LDS cells are reused by later phases of every substep)
