@@ -271,6 +271,8 @@ struct rr_batch {
   bool counted = false;                 // this batch is in m->live_batches
   unsigned* dyn_overflow = nullptr;     // DYN models: (env, env step) events in which more pairs penetrated than the wave has contact slots (rr_batch_contact_overflow)
   unsigned* progress = nullptr;         // pacing counter of multi-step launches (RRIO::progress); RR_PACE=0 turns pacing off
+  float *env_dof_f = nullptr, *env_act_f = nullptr, *env_con_f = nullptr;     // per-env parameter rows, owned (rr_batch_set_env_params)
+  bool has_env_params() const { return env_dof_f || env_act_f || env_con_f; }
 };
 
 template <typename Ptr>
@@ -354,6 +356,26 @@ static kern_t pick_pair_kernel(const rr_model* m) {
   return RRDimsRodentNew::matches(m->kd_rep) ? rr_step_kernel<2, 2, 1, false, false, RRDimsRodentNew, false, false, false, true> : nullptr;
 }
 
+// Per-environment parameters (RAND instances of rr_kernel.h: rr_rand_kernel): the production CG instances of the single-rodent floor-contact
+// models -- fixed-dimension or generic (2,2,1) -- as single-step, multi-step and multi-step with the actor.  `why`: the reason when none exists.
+static bool rand_model_ok(const rr_model* m, const char** why = nullptr) {
+  const char* w = nullptr;
+  if (m->dyn) w = "models with candidate-pair contacts (DYN instances) have none";
+  else if (m->pair_ok) w = "two-tree models served by the two-wave pair instance have none";
+  else if (m->solver == 2) w = "the Newton solver's instances have none";
+  else if (!(m->NBS == 2 && m->NVS == 2 && m->NCS == 1)) w = "only the (2,2,1) slot counts have instances with per-env parameters";
+  if (why) *why = w;
+  return w == nullptr;
+}
+static kern_t pick_rand_kernel(const rr_model* m, bool unroll = false, bool actor = false) {
+  if (!rand_model_ok(m)) return nullptr;
+  const int form = actor ? 2 : (unroll ? 1 : 0);
+  if (RRDimsRodent::matches(m->kd)) { kern_t k[3] = {rr_rand_kernel<RRDimsRodent>, rr_rand_kernel<RRDimsRodent, true>, rr_rand_kernel<RRDimsRodent, true, true>}; return k[form]; }
+  if (RRDimsRodentNew::matches(m->kd)) { kern_t k[3] = {rr_rand_kernel<RRDimsRodentNew>, rr_rand_kernel<RRDimsRodentNew, true>, rr_rand_kernel<RRDimsRodentNew, true, true>}; return k[form]; }
+  kern_t k[3] = {rr_rand_kernel<RRDims>, rr_rand_kernel<RRDims, true>, rr_rand_kernel<RRDims, true, true>};
+  return k[form];
+}
+
 extern "C" int rr_batch_create(const rr_model* m, int32_t num_envs, int32_t device, void* stream, rr_batch** out) {
   if (!m || !out || num_envs <= 0) return fail(RR_EINVAL, "rr_batch_create: bad argument");
   if (!pick_kernel(m)) return fail(RR_EUNSUPPORTED, "rr_batch_create: no kernel instance for this model's slot counts");
@@ -405,7 +427,8 @@ extern "C" int rr_batch_create(const rr_model* m, int32_t num_envs, int32_t devi
   if (!m->stage_ok) { rr_batch_destroy(b); return fail(RR_EUNSUPPORTED, "rr_batch_create: 4*ncon + nv exceeds the line-search staging cells (6*nbody)"); }
   if (m->dims.lds_bytes > 64 * 1024) { rr_batch_destroy(b); return fail(RR_EUNSUPPORTED, "rr_batch_create: per-env working set exceeds the 64 KiB of LDS one workgroup may address"); }
   kern_t pair_kern = m->pair_ok ? pick_pair_kernel(m) : nullptr;
-  for (kern_t kk : {kern, pick_kernel(m, false, true), pick_unroll_kernel(m), pick_unroll_kernel(m, true), pick_kernel(m, true), pair_kern}) {   // every instance a launch may pick
+  for (kern_t kk : {kern, pick_kernel(m, false, true), pick_unroll_kernel(m), pick_unroll_kernel(m, true), pick_kernel(m, true), pair_kern,
+                    pick_rand_kernel(m), pick_rand_kernel(m, true), pick_rand_kernel(m, true, true)}) {   // every instance a launch may pick
     if (!kk) continue;
     hipError_t e = hipFuncSetAttribute((const void*)kk, hipFuncAttributeMaxDynamicSharedMemorySize, kk == pair_kern ? 2 * m->kd_rep.lds_bytes_rep + 128 : m->dims.lds_bytes);
     if (e != hipSuccess) { rr_batch_destroy(b); return fail(RR_EHIP, std::string("hipFuncSetAttribute: ") + hipGetErrorString(e)); }
@@ -443,6 +466,7 @@ extern "C" void rr_batch_destroy(rr_batch* b) {
   if (!b) return;
   if (b->counted) b->m->live_batches.fetch_sub(1);
   for (void* p : b->dev_allocs) (void)hipFree(p);
+  for (float* p : {b->env_dof_f, b->env_act_f, b->env_con_f}) if (p) (void)hipFree(p);
   for (hipEvent_t e : b->ev0) (void)hipEventDestroy(e);
   for (hipEvent_t e : b->ev1) (void)hipEventDestroy(e);
   delete b;
@@ -532,13 +556,21 @@ static int launch(rr_batch* b, const rr_state* st, const float* ctrl, int n_fram
     }
   }
   if (!kern) return fail(RR_EUNSUPPORTED, "launch: no diagnostic kernel instance for this model");
+  if (b->has_env_params()) {      // per-env parameters: the RAND instance of the same launch form; production instances only
+    if (io.dbg) return fail(RR_EUNSUPPORTED, "launch: no debug dump on a batch with per-env parameters (the debug instance reads the model's shared tables)");
+    if (io.o_cdist || io.o_cpos || io.o_cframe) return fail(RR_EUNSUPPORTED, "launch: no contact-geometry outputs on a batch with per-env parameters (they are served by the debug instance)");
+    if (b->prof) return fail(RR_EUNSUPPORTED, "launch: no profile build on a batch with per-env parameters");
+    kern = pick_rand_kernel(b->m, un != nullptr, ac != nullptr);
+    if (!kern) return fail(RR_EUNSUPPORTED, "launch: no kernel instance with per-env parameters for this model / solver");
+    io.env_dof_f = b->env_dof_f; io.env_act_f = b->env_act_f; io.env_con_f = b->env_con_f;
+  }
   io.prof = b->prof;
   io.env_map = b->env_map; io.cost = b->cost;
   io.dyn_overflow = b->dyn_overflow;
   RRDims kd = b->kd;
   kd.iterations = b->m->kd.iterations; kd.ls_iterations = b->m->kd.ls_iterations;
   // two-tree model, physics only, no diagnostics: one wavefront per replica (rr_kernel.h PAIR)
-  const bool pair = b->m->pair_ok && !env && !out && !un && !b->prof && !b->env_map && !b->cost && b->m->solver != 2;
+  const bool pair = b->m->pair_ok && !env && !out && !un && !b->prof && !b->env_map && !b->cost && b->m->solver != 2 && !b->has_env_params();
   if (pair) {
     kern = pick_pair_kernel(b->m);
     kd = b->m->kd_rep;
@@ -1105,10 +1137,45 @@ extern "C" int rr_batch_set_profile(rr_batch* b, uint64_t* dev_cycles) {
   if (dev_cycles) {
     kern_t kern = pick_kernel(b->m, true);
     if (!kern) return fail(RR_EUNSUPPORTED, "rr_batch_set_profile: no diagnostic kernel instance for this model");
+    if (b->has_env_params()) return fail(RR_EUNSUPPORTED, "rr_batch_set_profile: no profile build on a batch with per-env parameters");
     hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, b->m->dims.lds_bytes);
     if (e != hipSuccess) return fail(RR_EHIP, std::string("hipFuncSetAttribute: ") + hipGetErrorString(e));
   }
   b->prof = (unsigned long long*)dev_cycles;
+  return RR_OK;
+}
+
+extern "C" int rr_batch_env_params_supported(const rr_batch* b) {
+  if (!b) return fail(RR_EINVAL, "rr_batch_env_params_supported: null batch");
+  return rand_model_ok(b->m) ? 1 : 0;
+}
+extern "C" int rr_batch_set_env_params(rr_batch* b, const rr_env_params* p) {
+  if (!b) return fail(RR_EINVAL, "rr_batch_set_env_params: null batch");
+  const rr_dims& d = b->m->dims;
+  const bool any = p && (p->dof_f || p->act_f || p->con_f);
+  if (any) {
+    const char* why = nullptr;
+    if (!rand_model_ok(b->m, &why)) return fail(RR_EUNSUPPORTED, std::string("rr_batch_set_env_params: no kernel instance with per-env parameters: ") + why);
+    if (b->prof) return fail(RR_EUNSUPPORTED, "rr_batch_set_env_params: no profile build on a batch with per-env parameters (rr_batch_set_profile is on)");
+    if (p->num_envs != b->N) return fail(RR_EINVAL, "rr_batch_set_env_params: num_envs differs from the batch's");
+    if ((p->dof_f && p->dof_rows != d.nv) || (p->act_f && p->act_rows != d.nu) || (p->con_f && p->con_rows != d.ncon))
+      return fail(RR_EINVAL, "rr_batch_set_env_params: row counts must be the model's nv (dof_f), nu (act_f), ncon (con_f)");
+  }
+  HIPCHK(hipSetDevice(b->device));
+  HIPCHK(hipStreamSynchronize(b->stream));       // launches in flight read the copy that is about to be freed
+  float** own[3] = {&b->env_dof_f, &b->env_act_f, &b->env_con_f};
+  for (float** o : own) { if (*o) { HIPCHK(hipFree(*o)); *o = nullptr; } }
+  if (!any) return RR_OK;
+  const float* src[3] = {p->dof_f, p->act_f, p->con_f};
+  const size_t bytes[3] = {(size_t)b->N * d.nv * 16 * 4, (size_t)b->N * d.nu * 8 * 4, (size_t)b->N * d.ncon * 26 * 4};
+  for (int i = 0; i < 3; ++i) {
+    if (!src[i] || !bytes[i]) continue;
+    void* q = nullptr;
+    HIPCHK(hipMalloc(&q, bytes[i]));
+    *own[i] = (float*)q;
+    HIPCHK(hipMemcpyAsync(q, src[i], bytes[i], hipMemcpyDeviceToDevice, b->stream));
+  }
+  HIPCHK(hipStreamSynchronize(b->stream));       // the caller's buffers are free again on return
   return RR_OK;
 }
 

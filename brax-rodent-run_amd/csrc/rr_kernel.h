@@ -147,6 +147,7 @@ struct RRTables {
 struct RRLoopTables { rr_gi factor3, linv, coljob, rowjob, jobown, con_chain_rows; };
 static __device__ __forceinline__ RRTables load_tables();      // defined with RRKArgs below
 static __device__ __forceinline__ RRDims load_dims();
+static __device__ __forceinline__ RRTables load_env_tables(int env, int nv, int nu, int ncon);      // RAND instances (per-environment parameter rows)
 // A table row as (wave-uniform base, unsigned 32-bit byte offset of the row, element offset inside it): the address the device's
 // global_load takes as SGPR pair + 32-bit VGPR + immediate.  Indexing a table pointer with an `int` instead makes every lane carry a
 // 64-bit address built by sign extension, a 64-bit multiply-add and register-pair copies (3-5 vector instructions per row).
@@ -208,6 +209,12 @@ struct RRIO {
   float pace_t1, pace_t2, pace_t3;   // env steps behind the average for priority levels 1, 2, 3
   int pace_mode;                     // bits 0-1: 0 max(weight level, lag level), 1 lag level only, 2 sum capped at 3; bit 2 (4): progress counted
                                      // per SUBSTEP (ten times finer); bit 3 (8): the factor-phase priority is 3 for laggards, 2 otherwise
+  // DOMAIN RANDOMISATION (RAND instances, rr_batch_set_env_params): per-environment copies of the three float tables that hold the
+  // randomisable cells (friction mu / invweight; damping, armature; actuator gain and bias).  Each nullable: a null pointer leaves the
+  // model's shared table in place.  Environment e reads rows [e][..]; everything else of the model stays shared.
+  const float* env_dof_f;            // [N][nv][16]
+  const float* env_act_f;            // [N][nu][8]
+  const float* env_con_f;            // [N][ncon][26]
   int mode;  // 0 = forward only (pipeline_init), 1 = step; bit 1 (2) = env epilogue as reset (obs only)
   int pad_;
 };
@@ -442,10 +449,11 @@ template <class A> struct rr_same<A, A> { static constexpr bool value = true; };
 // membership test (J' f); contacts of condim 1 carry one row (rows 1..3 of the slot get D = 0); transmissions with several joints (fixed
 // tendons) go through per-actuator sums.  Production physics + env epilogue only: single-step, multi-step (UNROLL) and multi-step with the
 // actor inside (UNROLL + ACTOR); everything DYN-specific is re-derived per substep, so the multi-step loop carries nothing extra for it.
-template <int NBS, int NVS, int NCS, class DT, bool NEWTON = false, bool PAIR = false, bool DYN = false>
+template <int NBS, int NVS, int NCS, class DT, bool NEWTON = false, bool PAIR = false, bool DYN = false, bool RAND = false>
 struct Wave {
   const DT& D;
   RRLoopTables TL;
+  int renv = 0;           // RAND: the environment whose parameter rows this wave reads (wave-uniform; re-derived with `lane`)
   int lane;               // re-derived (opaquely) at the head of every substep: see RR_FRAME_LOCAL in the kernel
   float* const lds;
   int rep = 0;            // PAIR: this wave's replica (wave-uniform)
@@ -512,6 +520,12 @@ struct Wave {
   __device__ __forceinline__ DT phase_dims() const {
     if constexpr (rr_same<DT, RRDims>::value) return D;
     else return DT(load_dims());
+  }
+  // The model tables for one phase.  RAND instances: dof_f / act_f / con_f advanced to this environment's rows (scalar arithmetic on the
+  // wave-uniform id, once per phase), so that every row_at() below stays SGPR base + 32-bit offset + immediate.
+  __device__ __forceinline__ RRTables tables() const {
+    if constexpr (RAND) return load_env_tables(renv, D.nv, D.nu, D.ncon);
+    else return load_tables();
   }
   __device__ Wave(const DT& d, const RRTables& t, float* l)
       : D(d), TL{t.factor3, t.linv, t.coljob, t.rowjob, t.jobown, t.con_chain_rows}, lane(threadIdx.x & (RR_LANES - 1)), lds(l) {
@@ -599,7 +613,7 @@ struct Wave {
   __device__ __forceinline__ int anc_at(int s, int k) const { const int wd = k < 4 ? banc[s][0] : banc[s][1]; return (wd >> (8 * (k & 3))) & 255; }
 
   __device__ __forceinline__ void kinematics() {
-    const RRTables T = load_tables();
+    const RRTables T = tables();
 #pragma unroll
     for (int s = 0; s < NBS; ++s) {
       const int b = lane + RR_LANES * s;
@@ -700,7 +714,7 @@ struct Wave {
 
   // ---------------------------------------------------------------- A-2 com_pos: subtree COM per root, cinert, cdof
   __device__ __forceinline__ void com_pos() {
-    const RRTables T = load_tables();
+    const RRTables T = tables();
     float acc[2][3] = {{0, 0, 0}, {0, 0, 0}};
     float xip[NBS][3];
 #pragma unroll
@@ -817,7 +831,7 @@ struct Wave {
   }
 
   __device__ __forceinline__ void velocity_sweep() {
-    const RRTables T = load_tables();
+    const RRTables T = tables();
     const DT D = phase_dims();   // the run-time scalars this phase reads (dt, gravity, schedule lengths): local to it, like T
     // own contribution of every body
 #pragma unroll
@@ -964,7 +978,7 @@ struct Wave {
 
   static constexpr int NME = NVS == 1 ? 10 : (NVS == 2 ? 18 : 35);   // sparse-M entries per lane (nM <= 64*NME)
   __device__ __forceinline__ void load_ment(int* ment) {
-    const RRTables T = load_tables();
+    const RRTables T = tables();
     const int ol = opaque(lane);
 #pragma unroll
     for (int it = 0; it < NME; ++it) ment[it] = g_int32(T.M_ij_k, ol + RR_LANES * it);
@@ -1113,7 +1127,7 @@ struct Wave {
   __device__ __forceinline__ void factor() {
     int ment[NME];          // for the row scaling at the end; requested now, local to this call (not held across the solver)
     load_ment(ment);
-    const RRTables T = load_tables();
+    const RRTables T = tables();
     const DT D = phase_dims();   // the run-time scalars this phase reads (dt, gravity, schedule lengths): local to it, like T
     if (lane < 8) s_qLD[2 * D.nM + lane] = (lane >> 1) == 1 ? 1.0f : ((lane >> 1) == 3 ? -1.0f : 0.0f);     // cells ZERO, ONE, TRASH, MINUS_ONE of the row schedules
     for (int c = lane; c < 2 * D.nalias; c += RR_LANES) s_buf[c] = 0.0f;      // alias copies of the hot rows (levelsched.py): pose cells, dead from here to the row scaling
@@ -1281,7 +1295,7 @@ struct Wave {
 
   // ---------------------------------------------------------------- passive + actuation + qfrc_smooth (per dof)
   __device__ __forceinline__ void smooth_forces(float* bias_out, float* passive_out) {
-    const RRTables T = load_tables();
+    const RRTables T = tables();
     if (DYN) {      // transmission with several joints per actuator (fixed tendons [REF models/rodent_cpu.xml:505-560]; UP mjx smooth.transmission):
                     // lane = actuator: length = sum coef qpos, velocity = sum coef qvel, force -> the (dead) pose cells, read per dof below
       if (lane < D.nu) {
@@ -1332,7 +1346,7 @@ struct Wave {
   // Runs right after com_pos while xpos / xquat are still live; the Jacobian is never materialised: a contact keeps
   // its offset from the tree COM and its frame, and J x / J' f are evaluated on the fly from cdof (J-free products).
   __device__ __forceinline__ void contact_geometry(float* dbg, float* o_dist = nullptr, float* o_pos = nullptr, float* o_frame = nullptr) {
-    const RRTables T = load_tables();
+    const RRTables T = tables();
     const DT D = phase_dims();   // the run-time scalars this phase reads (dt, gravity, schedule lengths): local to it, like T
 #pragma unroll
     for (int cs = 0; cs < NCS; ++cs) {
@@ -1470,7 +1484,7 @@ struct Wave {
     return dist;
   }
   __device__ __forceinline__ void contact_geometry_dyn() {
-    const RRTables T = load_tables();
+    const RRTables T = tables();
     const DT D = phase_dims();   // the run-time scalars this phase reads (dt, gravity, schedule lengths): local to it, like T
     int count = 0;
     for (int p0 = 0; p0 < D.ncon; p0 += RR_LANES) {          // scan: which candidate pairs are in penetration
@@ -1527,7 +1541,7 @@ struct Wave {
 
   // ---------------------------------------------------------------- A-5 constraint rows (limits; contact aref)
   __device__ __forceinline__ void constraint_rows(float* dbg) {
-    const RRTables T = load_tables();
+    const RRTables T = tables();
     const DT D = phase_dims();   // the run-time scalars this phase reads (dt, gravity, schedule lengths): local to it, like T
 #pragma unroll
     for (int s = 0; s < NVS; ++s) {
@@ -1574,7 +1588,7 @@ struct Wave {
   // per substep the chains of the contacts in penetration are cut into pieces of 12 / 20 / 36 dofs, 4 / 2 / 1 lanes per
   // contact (as many as fit 64 * NCS lanes), the lanes of a contact adjacent so that a quad DPP add joins the pieces.
   __device__ __forceinline__ void contact_jobs() {
-    const RRTables T = load_tables();
+    const RRTables T = tables();
     int n_act = 0;
 #pragma unroll
     for (int cs = 0; cs < NCS; ++cs) {
@@ -2106,7 +2120,7 @@ struct Wave {
 #pragma unroll
     for (int s = 0; s < NVS; ++s) qa[s] = qfrc_smooth[s] + qfrc_con[s];
     ldl_solve<true>(qa);
-    const RRTables T = load_tables();
+    const RRTables T = tables();
     const DT D = phase_dims();   // the run-time scalars this phase reads (dt, gravity, schedule lengths): local to it, like T
 #pragma unroll
     for (int s = 0; s < NVS; ++s) {
@@ -2198,6 +2212,25 @@ static __device__ __forceinline__ RRIO load_io() {
 #else
   return RRIO{};
 #endif
+}
+
+// RAND instances: the tables with the three randomisable ones advanced to environment `env`'s rows.  `env` is wave-uniform, the
+// pointers come from the argument block, so the address arithmetic is scalar (a 64-bit multiply-add per table).
+static __device__ __forceinline__ RRTables load_env_tables(int env, int nv, int nu, int ncon) {
+  RRTables T = load_tables();
+#if defined(__HIP_DEVICE_COMPILE__)
+  const char __attribute__((address_space(4)))* p = (const char __attribute__((address_space(4)))*)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(p));
+  typedef const char* const __attribute__((address_space(4)))* slot_t;
+  const char* const df = *(slot_t)(p + offsetof(RRKArgs, io) + offsetof(RRIO, env_dof_f));
+  const char* const af = *(slot_t)(p + offsetof(RRKArgs, io) + offsetof(RRIO, env_act_f));
+  const char* const cf = *(slot_t)(p + offsetof(RRKArgs, io) + offsetof(RRIO, env_con_f));
+  const size_t e = (size_t)(unsigned)env;
+  if (df) T.dof_f = (rr_gf)(df + e * ((size_t)nv * 16 * sizeof(float)));
+  if (af) T.act_f = (rr_gf)(af + e * ((size_t)nu * 8 * sizeof(float)));
+  if (cf) T.con_f = (rr_gf)(cf + e * ((size_t)ncon * 26 * sizeof(float)));
+#endif
+  return T;
 }
 
 // The actor of a multi-step rollout, one wave = one env: policy MLP (obs -> 32 x a_nh -> 2A, SiLU) on the observation of step `ut`,
@@ -2296,393 +2329,24 @@ __device__ __forceinline__ void rr_actor_step(const RRIO& io, const DT& D, int l
 // PAIR (see Wave): 128 threads = one wavefront per replica of a two-tree model; Dk / T describe ONE replica (nv_scale = the model's
 // dof count), the state arrays are the model's ([N][2 nq] ...: replica r of environment e is row 2 e + r of an [2 N][nq] array).
 // Physics only (pipeline_init / pipeline_step: no env epilogue, no optional outputs, no debug dump).
+// RAND (rr_rand_kernel below): the environments of the launch carry their own parameter rows (RRIO::env_dof_f / env_act_f / env_con_f).
+// The arithmetic is the same; only the base of three tables depends on the environment (Wave::tables).
+// The body is shared between the two entries as TEXT (rr_step_body.inc).  As a __device__ __forceinline__ function template it is optimised
+// once on its own and a second time after it has been inlined into the entry, and that moved the register allocation of every existing
+// instance (SGPR spills 67 / 83 / 158 -> 63 / 77 / 147 in the fixed-dimension ones, 68 bytes of scratch in the (2,2,1) debug and the (3,3,2)
+// production instance; profiles/r05_a_kernel_meta_function_form.txt).  Included as text, rr_step_kernel compiles the token stream it always
+// had, and its instances keep their code (profiles/r05_a_kernel_meta_parent.txt against r05_a_kernel_meta_rand.txt).
 template <int NBS, int NVS, int NCS, bool PROF, bool DBG, class DT, bool NEWTON = false, bool UNROLL = false, bool ACTOR = false, bool PAIR = false, bool DYN = false>
 __global__ __launch_bounds__((PAIR ? 2 : 1) * RR_LANES, (NVS >= 3 ? 1 : 2)) void rr_step_kernel(const RRDims Dk, const RRTables Tk, const RRIO io_kernarg, const int num_envs,
                                                            const int n_frames) {
-  static_assert(!PAIR || (!PROF && !DBG && !NEWTON && !UNROLL && !ACTOR), "PAIR: production physics instance only");
-  static_assert(!DYN || (!PROF && !DBG && !NEWTON && !PAIR), "DYN: production instances only (single-step, multi-step, multi-step with the actor)");
-  static_assert(!ACTOR || UNROLL, "the actor lives in the multi-step instances");
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  int env = blockIdx.x;
-  if (env >= num_envs) return;
-  // the level schedules address LDS by absolute byte address: the dynamic segment must start at 0, i.e. the kernel has no static
-  // LDS -- checked on the HOST for every instance a batch may launch (rr_batch_create: hipFuncGetAttributes().sharedSizeBytes == 0)
-  const DT D(Dk);
-  const int wrep = PAIR ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0;
-  Wave<NBS, NVS, NCS, DT, NEWTON, PAIR, DYN> w(D, Tk, PAIR ? lds + wrep * (D.lds_bytes_rep >> 2) : lds);
-  int lane = threadIdx.x & (RR_LANES - 1);
-  if (PAIR) { w.rep = wrep; w.s_xc = lds + 2 * (D.lds_bytes_rep >> 2); }
-  RRIO io = load_io();
-  if (io.env_map) {          // a permutation of 0 .. num_envs-1 (host-checked length); environments are independent, so the mapping
-    env = __builtin_amdgcn_readfirstlane(io.env_map[env]);   // only decides which two of them share a SIMD
-    if ((unsigned)env >= (unsigned)num_envs) return;
-  }
-  if (DBG) {   // the re-read block must be the real parameter, word for word; on a mismatch say so in the dump and touch nothing else
-    const RRIO ref_io = io_kernarg;
-    bool same = true;
-    for (unsigned i = 0; i < sizeof(RRIO) / sizeof(int); ++i) same &= ((const int*)&io)[i] == ((const int*)&ref_io)[i];
-    if (ref_io.dbg && lane == 0) ref_io.dbg[(size_t)env * D.dbg_floats + D.g_kaok] = same ? 1.0f : 0.0f;
-    if (!same) return;
-  }
-  const int mode = io.mode;
-  // the debug dump (parity tests) is a separate instance: its paths keep dozens of values alive across the solver
-  float* dbg = (DBG && io.dbg) ? io.dbg + (size_t)env * D.dbg_floats : nullptr;     // DBG instance without a dump buffer: contact outputs only
-
-  // wrapper state of a multi-step rollout, wave-uniform
-  const int nsteps = UNROLL ? io.unroll_T : 1;
-  float u_steps = 0.0f, u_prev_done = 0.0f;
-  int u_frame = 0;
-  unsigned u_work = 0;
-  int u_overflow = 0;            // DYN: some step of this launch dropped pairs (RRIO::cost bit 31 of a multi-step launch)
-  if (UNROLL) {
-    u_steps = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(io.steps_in[env])));
-    u_prev_done = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(io.prev_done[env])));
-    u_frame = __builtin_amdgcn_readfirstlane(io.cur_frame_in[env]);
-  }
-  int niter = 0;
-  float xq1[4] = {1, 0, 0, 0};   // xquat of body 1 at the last forward pass (obs: xmat[1])
- for (int ut = 0; ut < nsteps; ++ut) {
-  if (UNROLL) { lane = opaque(lane); w.lane = lane; asm volatile("" : "+s"(env)); io = load_io(); }
-  const RRTables T = load_tables();
-  const int senv = PAIR ? 2 * env + wrep : env;      // row of this wave's replica in the state arrays (from the step's own copy of env: see RR_FRAME_LOCAL)
-  const size_t ctrl_at = UNROLL ? ((size_t)ut * num_envs + env) * D.nu : (size_t)senv * D.nu;
-  if (ACTOR) {
-    if (ut == 0) {       // the observation the rollout starts from is row 0 of the env's trajectory
-      for (int i = lane; i < D.obs_dim; i += RR_LANES) io.t_obs[rr_traj_obs(io, num_envs, env, 0, 0) * D.obs_dim + i] = io.a_obs_in[(size_t)env * D.obs_dim + i];
-    }
-    // ORDERING through global memory inside one wave: the observation row the actor reads was written by OTHER lanes of this wave (the
-    // previous step's epilogue / the copy above), and the action it writes (lanes < A) is read back as ctrl by all lanes below.  Same-wave
-    // vector memory operations complete in order, but the compiler must not move them across each other either: a wavefront-scope fence on
-    // both sides states the dependency (guarded by tests/test_gpu_ppo.py::test_one_launch_unroll_with_the_actor_inside, bitwise).
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    rr_actor_step(io, D, lane, env, ut, num_envs);
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  }
-  // ---- load state (a multi-step rollout keeps it in LDS after its first step)
-  if (!UNROLL || ut == 0) {
-    for (int i = lane; i < D.nq; i += RR_LANES) w.s_qpos[i] = io.qpos_in[(size_t)senv * D.nq + i];
-    for (int i = lane; i < D.nv; i += RR_LANES) w.s_qvel[i] = io.qvel_in[(size_t)senv * D.nv + i];
-    for (int i = lane; i < D.nu; i += RR_LANES) w.s_act[i] = io.act_in[(size_t)senv * D.nu + i];
-  }
-  for (int i = lane; i < D.nu; i += RR_LANES) w.s_ctrl[i] = io.ctrl ? io.ctrl[ctrl_at + i] : 0.0f;
-#pragma unroll
-  for (int s = 0; s < NVS; ++s) {
-    const int d = lane + RR_LANES * s;
-    if ((!UNROLL || ut == 0) && d < D.nv) w.s_warm[d] = io.warm_in[(size_t)senv * D.nv + d];
-    if (d < D.nv) {
-      auto di = row_at(T.dof_i, RR_DOFI, d);
-      w.dofc0[s] = (di[3] & 255) | ((di[2] & 15) << 8) | ((di[9] & 15) << 12) | ((di[0] & 255) << 16) | ((row_at(T.body_i, RR_BODYI, di[0])[0] & 255) << 24);
-      w.dofc1[s] = (di[4] & 0xFFFF) | (di[10] << 16);
-    } else {
-      w.dofc0[s] = 255 | (6 << 8);
-      w.dofc1[s] = 0;
-    }
-    w.qacc[s] = w.Ma[s] = w.grad[s] = w.Mgrad[s] = w.search[s] = w.mv[s] = w.qfrc_con[s] = 0.0f;
-  }
-  w.work = 0;
-  if (UNROLL && DYN) w.dyn_overflow = 0;       // per env step: the counter below then counts what the single-step launches would count
-  for (int i = lane; i < D.nv; i += RR_LANES) w.s_arm[i] = row_at(T.dof_f, 16, i)[0];
-  if (NEWTON) for (int i = lane; i < (D.nM + 3) / 4; i += RR_LANES) ((int*)w.s_anc)[i] = T.anc4[i];
-  if (lane < 6) w.s_cdof[6 * D.nv + lane] = 0.0f;
-  if (lane == 0) w.s_qvel[D.nv] = 0.0f;
-  if (lane < 40) w.s_qLD[2 * D.nM + lane] = 0.0f;        // cells ZERO .. pad, and the 16 zero cells behind them (pairs)
-  if (lane < 16) { w.s_vec[D.nv + lane] = 0.0f; w.s_x[D.nv + lane] = 0.0f; }   // zero cells the job descriptors pad with / padded steps read
-  w.sync();
-
-  if (PROF) { for (int i = 0; i < RR_NPH; ++i) w.pt[i] = 0; w.pt_last = __builtin_readcyclecounter(); }
-  const int frames = (mode & 1) ? n_frames : 1;
-  for (int f = 0; f < frames; ++f) {
-    // RR_FRAME_LOCAL: everything derived from the lane id / env id (per-lane table addresses, output offsets) is loop-invariant,
-    // so the optimiser hoists it out of the substep loop and -- with 256 registers taken -- spills it to scratch at the loop head
-    // (45 dwords per lane in round 1's build, reloaded one by one inside every substep).  Re-deriving the two ids through an
-    // opaque copy per substep keeps those values local to their phase.
-    lane = opaque(lane); w.lane = lane;
-    asm volatile("" : "+s"(env));
-    const bool last = f == frames - 1;
-    if (last) io = load_io();
-    float* dg = last ? dbg : nullptr;
-    float bias[NVS], passive[NVS];
-    w.template stamp<PROF>(15);
-    // ---- per-substep (re)load of the model constants from the L2-resident tables.  Holding them in registers across
-    // the solver made the allocator spill them to scratch (HBM-side write traffic ~80x the algorithmic bytes); a plain
-    // reload costs the same read and no write.  `opaque` keeps the loads inside the substep loop.
-    {
-      const RRTables T = load_tables();
-      const int ol = opaque(lane);
-      w.bc0 = load_bodyc(T, ol, D.nbody);
-      if (NBS > 1) w.bc1 = load_bodyc(T, ol + RR_LANES, D.nbody);
-#pragma unroll
-      for (int s = 0; s < NBS; ++s) {
-        const int b = ol + RR_LANES * s;
-        const bool ok = b >= 1 && b < D.nbody;
-        w.banc[s][0] = ok ? row_at(T.body_anc, 2, b)[0] : 0;
-        w.banc[s][1] = ok ? row_at(T.body_anc, 2, b)[1] : 0;
-        w.blast[s] = ok ? row_at(T.body_i, RR_BODYI, b)[10] : 0;
-      }
-    }
-    if (lane == 0) {  // world body entries (their LDS cells are reused by later phases of every substep)
-      for (int k = 0; k < 6; ++k) w.s_cvel[k] = 0.0f;
-      for (int k = 0; k < 10; ++k) w.s_cinert[k] = 0.0f;
-      for (int k = 0; k < 3; ++k) w.s_xpos[k] = 0.0f;
-      w.s_xquat[0] = 1.0f; w.s_xquat[1] = w.s_xquat[2] = w.s_xquat[3] = 0.0f;
-    }
-    for (int rep = 0; rep < RR_REP_KIN; ++rep) w.kinematics();
-    w.kinematics();
-    w.template stamp<PROF>(0);
-    w.com_pos();
-    w.template stamp<PROF>(1);
-    if (last) {   // pose outputs of the last forward pass, before the pose cells are recycled
-#pragma unroll
-      for (int k = 0; k < 4; ++k) xq1[k] = w.s_xquat[4 + k];
-      if (io.o_xpos) for (int e = lane; e < 3 * D.nbody; e += RR_LANES) io.o_xpos[(size_t)env * 3 * D.nbody + e] = w.s_xpos[e];
-      if (io.o_xmat || dg) {
-        for (int b = lane; b < D.nbody; b += RR_LANES) {
-          float q[4], mm[9];
-          for (int k = 0; k < 4; ++k) q[k] = w.s_xquat[4 * b + k];
-          quat_to_mat(mm, q);
-          for (int k = 0; k < 9; ++k) {
-            if (io.o_xmat) io.o_xmat[(size_t)env * 9 * D.nbody + 9 * b + k] = mm[k];
-            if (dg) dg[D.g_xmat + 9 * b + k] = mm[k];
-          }
-        }
-      }
-      if (io.o_com && lane == 0) for (int k = 0; k < 3; ++k) io.o_com[(size_t)env * 3 + k] = w.com0[k];
-      if (dg) {
-        for (int e = lane; e < 3 * D.nbody; e += RR_LANES) dg[D.g_xpos + e] = w.s_xpos[e];
-        for (int e = lane; e < 4 * D.nbody; e += RR_LANES) dg[D.g_xquat + e] = w.s_xquat[e];
-        for (int e = lane; e < 10 * D.nbody; e += RR_LANES) dg[D.g_cinert + e] = w.s_cinert[e];
-        for (int e = lane; e < 6 * D.nv; e += RR_LANES) dg[D.g_cdof + e] = w.s_cdof[e];
-        if (lane == 0) { for (int k = 0; k < 3; ++k) { dg[D.g_com + k] = w.com0[k]; dg[D.g_com + 3 + k] = w.com1[k]; } }
-      }
-    }
-    {   // contact geometry outputs (on request only) are served by the debug-dump instance: the production instances carry no code for them
-      float *od = nullptr, *op = nullptr, *of = nullptr;
-      if (DBG && last) {
-        od = io.o_cdist ? io.o_cdist + (size_t)env * D.ncon : nullptr;
-        op = io.o_cpos ? io.o_cpos + (size_t)env * 3 * D.ncon : nullptr;
-        of = io.o_cframe ? io.o_cframe + (size_t)env * 9 * D.ncon : nullptr;
-      }
-      if (DYN) w.contact_geometry_dyn();
-      else w.contact_geometry(dg, od, op, of);
-    }
-    w.velocity_sweep();
-    w.template stamp<PROF>(2);
-    if (last) {   // cinert / cvel of the last forward pass go out now: cinert's cells become the composite inertia next
-      if (io.o_cinert) for (int e = lane; e < 10 * D.nbody; e += RR_LANES) io.o_cinert[(size_t)env * 10 * D.nbody + e] = w.s_cinert[e];
-      if (io.o_cvel) for (int e = lane; e < 6 * D.nbody; e += RR_LANES) io.o_cvel[(size_t)env * 6 * D.nbody + e] = w.s_cvel[e];
-      if (io.obs) {
-        float* ob = (ACTOR ? io.t_obs + rr_traj_obs(io, num_envs, env, rr_traj(io, ut).u, rr_traj(io, ut).t + 1) * D.obs_dim : io.obs + (size_t)env * D.obs_dim) + D.nq + D.nv;
-        for (int i = lane; i < 10 * (D.nbody - 1); i += RR_LANES) ob[i] = w.s_cinert[10 + i];
-        ob += 10 * (D.nbody - 1);
-        for (int i = lane; i < 6 * (D.nbody - 1); i += RR_LANES) ob[i] = w.s_cvel[6 + i];
-      }
-      if (dg) for (int e = lane; e < 6 * D.nbody; e += RR_LANES) dg[D.g_cvel + e] = w.s_cvel[e];
-    }
-    w.backward_sweep();
-    w.template stamp<PROF>(3);
-    w.smooth_forces(bias, passive);     // needs cfrc, whose cells the factorisation overwrites
-    if (dg) {
-      for (int e = lane; e < 10 * D.nbody; e += RR_LANES) dg[D.g_crb + e] = w.s_crb[e];
-      for (int e = lane; e < 6 * D.nbody; e += RR_LANES) dg[D.g_cfrc + e] = w.s_cfrc[e];
-    }
-    w.contact_jobs();     // J*x jobs of the contacts in penetration: needed from here to the end of the substep
-    // WAVE PRIORITY.  2048 environments are exactly one resident round, so a launch lasts as long as its slowest environment,
-    // and an environment is slow when many contacts carry force (more J'f terms, more line-search rows).  The heavier of the two
-    // waves that share a SIMD issues first; the lighter one has slack.  Four graded levels (0 / 2+ / 6+ / 12+ contacts in
-    // penetration): -4.6 % launch time, bit-identical results (tools/variant_bench.py; a two-level split gave -3.1 %).
-    w.env_prio();
-    w.sync();
-    for (int rep = 0; rep < RR_REP_MM; ++rep) w.mass_matrix();
-    w.mass_matrix();
-    w.template stamp<PROF>(4);
-    if (dg) for (int e = lane; e < D.nM; e += RR_LANES) dg[D.g_qM + e] = w.s_qLD[2 * e];
-    if (NEWTON) {      // M itself is needed all through the Newton iterations (M * search, H = M + ...): keep a copy of the pair array
-      for (int e = lane; e < D.nM + 20; e += RR_LANES) *(rr_f2*)(w.s_Mp + 2 * e) = *(const rr_f2*)(w.s_qLD + 2 * e);
-      w.sync();
-    }
-    {   // the substep's only product with M itself: M * qacc_warmstart, for the solver's warm-start context
-      float wv[NVS];
-#pragma unroll
-      for (int s = 0; s < NVS; ++s) { const int d = lane + RR_LANES * s; wv[s] = d < D.nv ? w.s_warm[d] : 0.0f; }
-      w.put_vec(wv);
-      w.mul_m(w.Ma_warm);
-    }
-    // ... and by phase: the two level schedules are one long dependent chain of LDS round trips that issues little; at top priority
-    // its instructions go out the moment they are ready (-1.2 ... -1.6 % launch time; the same for the solves, the line-search
-    // iterations or the tree sweeps measured +0.3 ... +0.6 % each and +3 % together)
-#if RR_FACTOR_PRIO
-    if ((w.lag_mode & 8) && w.lag_prio == 0) __builtin_amdgcn_s_setprio(2);
-    else __builtin_amdgcn_s_setprio(3);
-#endif
-    w.factor();
-    if (dg) for (int e = lane; e < D.nM; e += RR_LANES) dg[D.g_qLD + e] = w.s_qLD[2 * e];
-    w.invert();
-    w.env_prio();
-    w.template stamp<PROF>(5);
-#pragma unroll
-    for (int s = 0; s < NVS; ++s) w.qacc_smooth[s] = w.qfrc_smooth[s];
-    w.ldl_solve(w.qacc_smooth);
-    w.template stamp<PROF>(6);
-    if (dg) {
-#pragma unroll
-      for (int s = 0; s < NVS; ++s) {
-        const int d = lane + RR_LANES * s;
-        if (d < D.nv) {
-          dg[D.g_dinv + d] = w.dinv[s]; dg[D.g_bias + d] = bias[s]; dg[D.g_passive + d] = passive[s];
-          dg[D.g_actuator + d] = w.s_qact[d]; dg[D.g_smooth + d] = w.qfrc_smooth[s];
-          dg[D.g_qacc_smooth + d] = w.qacc_smooth[s];
-        }
-      }
-    }
-    w.constraint_rows(dg);
-    w.template stamp<PROF>(7);
-    niter = w.template solve<PROF>();
-    w.template stamp<PROF>(12);
-    if (dg) {
-#pragma unroll
-      for (int s = 0; s < NVS; ++s) {
-        const int d = lane + RR_LANES * s;
-        if (d < D.nv) { dg[D.g_qacc + d] = w.qacc[s]; dg[D.g_qfrc_constraint + d] = w.qfrc_con[s]; }
-      }
-      if (lane == 0) { dg[D.g_misc] = (float)niter; dg[D.g_misc + 1] = w.cost; }
-    }
-    if (mode & 1) w.euler();
-    w.template stamp<PROF>(13);
-    if (UNROLL && !last) {       // pacing at substep granularity (RRIO::pace_mode bit 2)
-      const RRIO iop = load_io();
-      if (iop.progress && (iop.pace_mode & 4)) {
-        unsigned seen = 0;
-        if (lane == 0) seen = __hip_atomic_fetch_add(iop.progress, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u;
-        seen = (unsigned)__builtin_amdgcn_readfirstlane((int)seen);
-        const float behind = ((float)seen / (float)num_envs - (float)(ut * frames + f + 1)) / (float)frames;      // in env steps
-        w.lag_prio = behind > iop.pace_t3 ? 3 : (behind > iop.pace_t2 ? 2 : (behind > iop.pace_t1 ? 1 : 0));
-        w.lag_mode = iop.pace_mode;
-      }
-    }
-  }
-
-  w.template stamp<PROF>(14);
-  lane = opaque(lane); w.lane = lane;
-  asm volatile("" : "+s"(env));
-  io = load_io();
-  if (PROF && io.prof && lane == 0) for (int i = 0; i < RR_NPH; ++i) io.prof[(size_t)env * RR_NPH + i] = w.pt[i];
-  if (UNROLL) u_work += (unsigned)w.work;        // a multi-step launch reports the work of all its steps
-  if (UNROLL && DYN) u_overflow |= w.dyn_overflow;
-  if (io.cost && lane == 0 && wrep == 0) io.cost[env] = (UNROLL ? u_work : (unsigned)w.work) | (DYN && (UNROLL ? u_overflow : w.dyn_overflow) ? 0x80000000u : 0u);
-  if (DYN && w.dyn_overflow && io.dyn_overflow && lane == 0) __hip_atomic_fetch_add(io.dyn_overflow, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  // ---- write back state (a multi-step rollout writes it once, after the wrappers of its last step: see below)
-  if (!UNROLL) {
-    for (int i = lane; i < D.nq; i += RR_LANES) io.qpos[(size_t)senv * D.nq + i] = w.s_qpos[i];
-    for (int i = lane; i < D.nv; i += RR_LANES) io.qvel[(size_t)senv * D.nv + i] = w.s_qvel[i];
-    for (int i = lane; i < D.nu; i += RR_LANES) io.act[(size_t)senv * D.nu + i] = w.s_act[i];
-#pragma unroll
-    for (int s = 0; s < NVS; ++s) {
-      const int d = lane + RR_LANES * s;
-      if (d < D.nv) {
-        io.warm[(size_t)senv * D.nv + d] = w.s_warm[d];
-        if (io.o_qfrc_actuator) io.o_qfrc_actuator[(size_t)senv * D.nv + d] = w.s_qact[d];
-      }
-    }
-  }
-
-  // ---- reference env epilogue [REF Rodent_Env_Brax.py:103-158]
-  if (io.obs) {
-    const bool is_reset = (mode & 2) != 0;
-    const int old_frame = UNROLL ? u_frame : io.cur_frame_in[env];
-    const int new_frame = is_reset ? old_frame : old_frame + 1;
-    float* ob = ACTOR ? io.t_obs + rr_traj_obs(io, num_envs, env, rr_traj(io, ut).u, rr_traj(io, ut).t + 1) * D.obs_dim : io.obs + (size_t)env * D.obs_dim;
-    int o = 0;
-    for (int i = lane; i < D.nq; i += RR_LANES) ob[o + i] = w.s_qpos[i];
-    o += D.nq;
-    for (int i = lane; i < D.nv; i += RR_LANES) ob[o + i] = w.s_qvel[i];
-    o += D.nv;
-    o += 16 * (D.nbody - 1);   // cinert[1:], cvel[1:] were written right after the last forward pass
-#pragma unroll
-    for (int s = 0; s < NVS; ++s) {
-      const int d = lane + RR_LANES * s;
-      if (d < D.nv) ob[o + d] = w.s_qact[d];
-    }
-    o += D.nv;
-    if (lane < 3) {  // xmat[1] @ (track_pos[frame + 1] - qpos[:3]); JAX clamps the gather index
-      int fi = new_frame + 1;
-      fi = fi < 0 ? 0 : (fi > io.track_len - 1 ? io.track_len - 1 : fi);
-      const v3 v = ld3(io.track_pos + 3 * fi) - ld3(w.s_qpos);
-      float m1[9];
-      quat_to_mat(m1, xq1);
-      // row `lane` of xmat[1] by selects (indexing a register array by the lane id would put it into scratch memory)
-      const float r0 = m1[0] * v.x + m1[1] * v.y + m1[2] * v.z, r1 = m1[3] * v.x + m1[4] * v.y + m1[5] * v.z, r2 = m1[6] * v.x + m1[7] * v.y + m1[8] * v.z;
-      ob[o + lane] = lane == 0 ? r0 : (lane == 1 ? r1 : r2);
-    }
-    if (!is_reset) {
-      float a2 = 0.0f;
-      for (int i = lane; i < D.nu; i += RR_LANES) { const float a = io.ctrl[ctrl_at + i]; a2 += a * a; }
-      a2 = wave_sum(a2);
-      if (lane == 0) {
-        int fi = old_frame < 0 ? 0 : (old_frame > io.track_len - 1 ? io.track_len - 1 : old_frame);
-        const v3 dx = ld3(w.s_qpos) - ld3(io.track_pos + 3 * fi);
-        // explicit roundings (no fused multiply-add left to the optimiser), so that the instances of the kernel form the reward from the
-        // same operations: single-step and multi-step instances agree bit for bit (tests/test_gpu_env.py); the actor-inside instance to
-        // ONE ulp -- `expf` below is expanded inline per instance and its expansion there rounds differently
-        // (tests/test_gpu_ppo.py::test_one_launch_unroll_with_the_actor_inside allows exactly that)
-        const float d2 = __fadd_rn(__fadd_rn(__fmul_rn(dx.x, dx.x), __fmul_rn(dx.y, dx.y)), __fmul_rn(dx.z, dx.z));
-        const float pos_reward = expf(__fmul_rn(-100.0f, sqrtf(d2)));
-        const float z = w.s_qpos[2];
-        float healthy = z < io.z_min ? 0.0f : 1.0f;
-        if (z > io.z_max) healthy = 0.0f;
-        const float hr = io.terminate_when_unhealthy ? io.healthy_reward : __fmul_rn(io.healthy_reward, healthy);
-        const float cc = __fmul_rn(io.ctrl_cost_weight, a2);     // explicit roundings: every instance of the kernel forms the reward identically
-        const float rew = __fsub_rn(__fadd_rn(pos_reward, hr), cc);   // (left to the optimiser, one instance fused the product into the sum: 1 ulp)
-        io.reward[env] = rew;
-        if (ACTOR) io.t_reward[rr_traj_at(io, num_envs, env, ut)] = rew;
-        io.done[env] = io.terminate_when_unhealthy ? 1.0f - healthy : 0.0f;
-        io.metrics[3 * env] = pos_reward; io.metrics[3 * env + 1] = -cc; io.metrics[3 * env + 2] = hr;
-        io.cur_frame[env] = new_frame;
-      }
-    }
-    if (UNROLL) {
-      // EpisodeWrapper + AutoResetWrapper on the step just made (action_repeat 1), as rr_wrap_kernel applies them:
-      // steps' = (prev_done ? 0 : steps) + 1; over = steps' >= episode_length; done <- over ? 1 : done; truncation = over ? 1 - done_env : 0;
-      // where done, the stored first state and first observation come back (info -- cur_frame, steps -- is not restored)
-      const float z = w.s_qpos[2];
-      const float healthy = (z < io.z_min || z > io.z_max) ? 0.0f : 1.0f;
-      const float done_env = io.terminate_when_unhealthy ? 1.0f - healthy : 0.0f;
-      u_steps = (u_prev_done != 0.0f ? 0.0f : u_steps) + 1.0f;
-      const bool over = u_steps >= io.episode_length;
-      const float done2 = over ? 1.0f : done_env, trunc = over ? 1.0f - done_env : 0.0f;
-      u_prev_done = done2;
-      u_frame = new_frame;
-      if (ACTOR && lane == 0) { const size_t at = rr_traj_at(io, num_envs, env, ut); io.t_discount[at] = 1.0f - done2; io.t_trunc[at] = trunc; }
-      if (__builtin_amdgcn_readfirstlane(__float_as_int(done2)) != 0) {
-        w.sync();
-        for (int i = lane; i < D.nq; i += RR_LANES) w.s_qpos[i] = io.first_qpos[(size_t)env * D.nq + i];
-        for (int i = lane; i < D.nv; i += RR_LANES) { w.s_qvel[i] = io.first_qvel[(size_t)env * D.nv + i]; w.s_warm[i] = io.first_warm[(size_t)env * D.nv + i]; }
-        for (int i = lane; i < D.nu; i += RR_LANES) w.s_act[i] = io.first_act[(size_t)env * D.nu + i];
-        for (int i = lane; i < D.obs_dim; i += RR_LANES) ob[i] = io.first_obs[(size_t)env * D.obs_dim + i];
-        w.sync();
-      }
-      if (ACTOR) {      // the last observation of a segment is also the first of the next one (the learner's trajectories overlap by one row)
-        const RRTraj tr = rr_traj(io, ut);
-        if (tr.t + 1 == io.a_seg && ut + 1 < nsteps) {
-          float* nx = io.t_obs + rr_traj_obs(io, num_envs, env, tr.u + 1, 0) * D.obs_dim;
-          for (int i = lane; i < D.obs_dim; i += RR_LANES) nx[i] = ob[i];
-        }
-      }
-      if (io.progress && ut + 1 < nsteps) {
-        unsigned seen = 0;
-        if (lane == 0) seen = __hip_atomic_fetch_add(io.progress, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u;
-        seen = (unsigned)__builtin_amdgcn_readfirstlane((int)seen);
-        const float per_step = (io.pace_mode & 4) ? (float)frames : 1.0f;          // the counter's units per env step
-        const float behind = ((float)seen / (float)num_envs) / per_step - (float)(ut + 1);      // env steps behind the average environment
-        w.lag_prio = behind > io.pace_t3 ? 3 : (behind > io.pace_t2 ? 2 : (behind > io.pace_t1 ? 1 : 0));
-        w.lag_mode = io.pace_mode;
-      }
-      if (ut == nsteps - 1) {
-        if (lane == 0) { io.done[env] = done2; io.steps_out[env] = u_steps; io.trunc_out[env] = trunc; }
-        for (int i = lane; i < D.nq; i += RR_LANES) io.qpos[(size_t)env * D.nq + i] = w.s_qpos[i];
-        for (int i = lane; i < D.nv; i += RR_LANES) { io.qvel[(size_t)env * D.nv + i] = w.s_qvel[i]; io.warm[(size_t)env * D.nv + i] = w.s_warm[i]; }
-        for (int i = lane; i < D.nu; i += RR_LANES) io.act[(size_t)env * D.nu + i] = w.s_act[i];
-      }
-    }
-  }
- }     // ut
+  constexpr bool RAND = false;
+#include "rr_step_body.inc"
+}
+// Per-environment parameters: the same argument list (load_io / load_tables / load_dims find the block at the same offsets), production
+// CG instances of the (2,2,1) slot counts only -- single-step, multi-step, multi-step with the actor.
+template <class DT, bool UNROLL = false, bool ACTOR = false>
+__global__ __launch_bounds__(RR_LANES, 2) void rr_rand_kernel(const RRDims Dk, const RRTables Tk, const RRIO io_kernarg, const int num_envs, const int n_frames) {
+  constexpr int NBS = 2, NVS = 2, NCS = 1;
+  constexpr bool PROF = false, DBG = false, NEWTON = false, PAIR = false, DYN = false, RAND = true;
+#include "rr_step_body.inc"
 }

@@ -84,7 +84,12 @@ class State:
 
 
 class System:
-    """The few `sys.*` attributes the reference env touches [REF Rodent_Env_Brax.py:82-89]."""
+    """The few `sys.*` attributes the reference env touches [REF Rodent_Env_Brax.py:82-89], and the model parameters a
+    `randomization_fn` may replace (brax: `sys.tree_replace({'geom_friction': ...})`): numpy arrays under MuJoCo's names,
+    `geom_friction` [ngeom, 3], `dof_damping` [nv], `dof_armature` [nv], `actuator_gainprm` [nu, 10] (column 0: the gain),
+    `actuator_biasprm` [nu, 10] (columns 0..2).  Any other table of the blob reads as `sys.<name>` too."""
+
+    PARAM_FIELDS = ("geom_friction", "dof_damping", "dof_armature", "actuator_gainprm", "actuator_biasprm")
 
     def __init__(self, blob_path: str, iterations: int, ls_iterations: int, solver: str = "cg"):
         from .. import mjcf
@@ -107,6 +112,37 @@ class System:
         self.contact_geom2 = self.model.table("con_geom2")
         self.geom_bodyid = self.model.table("geom_bodyid")
         self.contact_link_idx = (self.geom_bodyid[self.contact_geom1] - 1, self.geom_bodyid[self.contact_geom2] - 1)
+        t = self.tables
+        self.geom_friction = t["geom_friction"].copy()
+        self.dof_damping = t["dof_damping"].copy()
+        self.dof_armature = t["dof_armature"].copy()
+        self.actuator_gainprm = np.zeros((self.nu, 10), np.float32)
+        self.actuator_gainprm[:, 0] = t["actuator_gainprm0"]
+        self.actuator_biasprm = np.zeros((self.nu, 10), np.float32)
+        self.actuator_biasprm[:, :3] = t["actuator_biasprm"]
+
+    def __getattr__(self, name):           # (only reached for names not set above) any other table of the blob, read-only use
+        tables = self.__dict__.get("tables")
+        if tables is not None and name in tables:
+            return tables[name]
+        raise AttributeError(name)
+
+    def replace(self, **kw) -> "System":
+        """A copy with the given attributes replaced (brax `sys.replace`); the original is left as it is."""
+        import copy
+        new = copy.copy(self)
+        for k, v in kw.items():
+            if not hasattr(self, k):
+                raise AttributeError(f"System has no field '{k}'")
+            setattr(new, k, v)
+        return new
+
+    def tree_replace(self, params: Dict[str, Any]) -> "System":
+        """brax `sys.tree_replace({'geom_friction': x, ...})`; nested (dotted) names are not part of this System."""
+        for k in params:
+            if "." in k:
+                raise ValueError(f"System.tree_replace: nested field '{k}' is not supported")
+        return self.replace(**params)
 
 
 class PipelineEnv:
@@ -138,6 +174,58 @@ class PipelineEnv:
             self._env_map = torch.arange(self.num_envs, dtype=torch.int32, device=self.device)
             self._cost = torch.zeros(self.num_envs, dtype=torch.int32, device=self.device)
             self._batch.set_schedule(self._env_map, self._cost)
+
+    # -- domain randomisation
+    def randomize(self, randomization_fn):
+        """Per-environment model parameters, as `brax.envs.wrappers.training.DomainRandomizationVmapWrapper` takes them:
+        `randomization_fn(sys)` -- keys already bound, e.g. `functools.partial(fn, rng=keys[N, 2])` -- returns `(sys_v, in_axes)`, a
+        System whose randomised fields carry a leading env axis [N, ...] and, per field, 0 (batched) or None; `in_axes` may be a dict
+        {field: 0 | None}, an object with such attributes, or None (then the fields whose arrays gained a leading axis are the batched
+        ones).  Supported fields: System.PARAM_FIELDS.  The kernel rows are rebuilt per env (`ktables.env_param_tables`) and uploaded;
+        the parameters stay fixed per env until the next call (brax does not re-draw them at reset either)."""
+        from .. import ktables
+        if not self._batch.env_params_supported():
+            self._batch.set_env_params(*(torch.zeros(self.num_envs, r, w, device=self.device) for r, w in
+                                         ((self.sys.nv, 16), (self.sys.nu, 8), (self.sys.ncon, 26))))      # raises with the library's reason
+        sys_v, in_axes = randomization_fn(self.sys)
+        axis = (lambda k: None) if in_axes is None else ((lambda k: in_axes.get(k)) if isinstance(in_axes, dict) else (lambda k: getattr(in_axes, k, None)))
+        names = set(System.PARAM_FIELDS) | (set(in_axes) if isinstance(in_axes, dict) else set())
+        names |= {k for k, v in vars(sys_v).items() if isinstance(v, (np.ndarray, torch.Tensor)) and v is not getattr(self.sys, k, None)}
+        batched = {}
+        for k in sorted(names):
+            new, old = getattr(sys_v, k, None), getattr(self.sys, k, None)
+            if new is None or (new is old and axis(k) is None):
+                continue
+            new = new.detach().cpu().numpy() if torch.is_tensor(new) else np.asarray(new)
+            is_b = axis(k) == 0 if in_axes is not None else (old is not None and new.ndim == np.ndim(old) + 1)
+            if axis(k) not in (None, 0):
+                raise ValueError(f"randomize: in_axes['{k}'] must be 0 or None")
+            if not is_b:
+                if old is not None and new.shape == np.shape(old) and np.array_equal(new, old):
+                    continue
+                if k not in System.PARAM_FIELDS or old is None or new.shape != np.shape(old):
+                    raise ValueError(f"randomize: field '{k}' was replaced but is not marked batched with a leading env axis; the supported "
+                                     f"fields are {', '.join(System.PARAM_FIELDS)}")
+                new = np.broadcast_to(new, (self.num_envs,) + new.shape)     # one new value for all envs
+            elif new.ndim < 1 or new.shape[0] != self.num_envs:
+                raise ValueError(f"randomize: batched field '{k}' has shape {new.shape}, expected a leading axis of {self.num_envs} envs")
+            batched[k] = new
+        dof_f, act_f, con_f = ktables.env_param_tables(self.sys.tables, batched)
+        up = lambda a: torch.from_numpy(a).to(self.device)
+        self.set_env_params(dof_f=up(dof_f) if {"dof_damping", "dof_armature"} & set(batched) else None,
+                            act_f=up(act_f) if {"actuator_gainprm", "actuator_biasprm"} & set(batched) else None,
+                            con_f=up(con_f) if "geom_friction" in batched else None)
+        return sys_v
+
+    def set_env_params(self, dof_f=None, act_f=None, con_f=None):
+        """Upload per-env kernel rows (float32 device tensors as `ktables.env_param_tables` builds them; None = the model's shared table;
+        all None clears them)."""
+        self._batch.set_env_params(dof_f, act_f, con_f)
+        self._env_params = None if dof_f is None and act_f is None and con_f is None else dict(dof_f=dof_f, act_f=act_f, con_f=con_f)
+
+    def env_params(self):
+        """The per-env rows in force: {'dof_f', 'act_f', 'con_f'} (device tensors or None per table), or None without randomisation."""
+        return getattr(self, "_env_params", None)
 
     def _rebalance(self):
         """Call before a step launch: every `rebalance_every` launches, pair heavy with light environments."""

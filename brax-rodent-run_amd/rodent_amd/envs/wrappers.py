@@ -183,11 +183,17 @@ class FusedEpisodeAutoResetWrapper(Wrapper):
         return base.unroll_policy_wrapped(state, self.episode_length, actor, noise, traj, segment)
 
 
-def wrap(env, episode_length: int = 1000, action_repeat: int = 1):
+def wrap(env, episode_length: int = 1000, action_repeat: int = 1, randomization_fn=None):
     """brax.envs.wrappers.training.wrap: Vmap -> Episode -> AutoReset (one fused wrapper for a HIP env with
-    action_repeat 1; RR_FUSED_WRAPPERS=0 selects the composition)."""
+    action_repeat 1; RR_FUSED_WRAPPERS=0 selects the composition).  `randomization_fn(sys) -> (sys_v, in_axes)` (keys already bound):
+    brax puts a DomainRandomizationVmapWrapper in place of the VmapWrapper; here the env's batch takes the per-env parameters
+    (`PipelineEnv.randomize`) and every later step of it, wrapped or not, runs on them."""
     import os
     base = env.unwrapped if hasattr(env, "unwrapped") else env
+    if randomization_fn is not None:
+        if not hasattr(base, "randomize"):
+            raise ValueError("wrap: this environment does not take a randomization_fn")
+        base.randomize(randomization_fn)
     if action_repeat == 1 and hasattr(base, "_batch") and os.environ.get("RR_FUSED_WRAPPERS", "1") == "1":
         return FusedEpisodeAutoResetWrapper(VmapWrapper(env), episode_length)
     env = VmapWrapper(env)

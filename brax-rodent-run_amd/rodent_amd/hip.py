@@ -53,6 +53,11 @@ class RRActorIO(C.Structure):
                                    "traj_discount", "traj_truncation")] + [("min_std", C.c_float), ("nhidden", C.c_int32), ("segment_length", C.c_int32)]
 
 
+class RREnvParams(C.Structure):
+    _fields_ = [("dof_f", C.c_void_p), ("act_f", C.c_void_p), ("con_f", C.c_void_p), ("dof_rows", C.c_int32), ("act_rows", C.c_int32),
+                ("con_rows", C.c_int32), ("num_envs", C.c_int32)]
+
+
 class RRDwItem(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("delta", "act", "act_rows", "mean", "std", "delta_colsum")] + \
         [("M", C.c_int32), ("O", C.c_int32), ("I", C.c_int32), ("grad", C.c_void_p)]
@@ -65,7 +70,7 @@ class RRPpoCfg(C.Structure):
 
 EXPORTS = ["rr_model_load", "rr_model_dims", "rr_model_set_solver", "rr_model_set_solver_type", "rr_model_destroy", "rr_model_table", "rr_kernarg_layout", "rr_batch_create",
            "rr_batch_destroy", "rr_pipeline_init", "rr_pipeline_step", "rr_env_step", "rr_env_reset", "rr_pipeline_step_to", "rr_env_step_to", "rr_batch_contact_overflow", "rr_batch_unroll_supported", "rr_env_unroll", "rr_env_unroll_policy",
-           "rr_compute_gae", "rr_mlp_forward", "rr_ppo_loss_workspace_bytes", "rr_ppo_loss", "rr_policy_act_workspace_bytes", "rr_policy_act", "rr_policy_sample", "rr_policy_backward_workspace_bytes", "rr_policy_backward", "rr_mlp_silu_backward_workspace_bytes", "rr_mlp_silu_backward", "rr_mlp_value_backward_workspace_bytes", "rr_mlp_value_backward", "rr_mlp_weight_grad_workspace_bytes", "rr_mlp_weight_grad", "rr_mlp_weight_grad_batch_workspace_bytes", "rr_mlp_weight_grad_batch", "rr_obs_moments_workspace_bytes", "rr_obs_moments", "rr_wrap_episode_autoreset", "rr_debug_layout", "rr_batch_set_schedule", "rr_batch_set_profile", "rr_batch_set_timing", "rr_batch_kernel_time", "rr_last_error"]
+           "rr_compute_gae", "rr_mlp_forward", "rr_ppo_loss_workspace_bytes", "rr_ppo_loss", "rr_policy_act_workspace_bytes", "rr_policy_act", "rr_policy_sample", "rr_policy_backward_workspace_bytes", "rr_policy_backward", "rr_mlp_silu_backward_workspace_bytes", "rr_mlp_silu_backward", "rr_mlp_value_backward_workspace_bytes", "rr_mlp_value_backward", "rr_mlp_weight_grad_workspace_bytes", "rr_mlp_weight_grad", "rr_mlp_weight_grad_batch_workspace_bytes", "rr_mlp_weight_grad_batch", "rr_obs_moments_workspace_bytes", "rr_obs_moments", "rr_wrap_episode_autoreset", "rr_debug_layout", "rr_batch_set_schedule", "rr_batch_set_env_params", "rr_batch_env_params_supported", "rr_batch_set_profile", "rr_batch_set_timing", "rr_batch_kernel_time", "rr_last_error"]
 
 _lib = None
 
@@ -140,6 +145,8 @@ def lib():
         L.rr_obs_moments.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         L.rr_batch_set_profile.argtypes = [C.c_void_p, C.c_void_p]
         L.rr_batch_set_schedule.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rr_batch_set_env_params.argtypes = [C.c_void_p, C.POINTER(RREnvParams)]
+        L.rr_batch_env_params_supported.argtypes = [C.c_void_p]
         L.rr_batch_set_timing.argtypes = [C.c_void_p, C.c_int32]
         L.rr_batch_kernel_time.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
         _lib = L
@@ -362,6 +369,21 @@ class Batch:
         self._sched = (env_map, cost)
         _check(lib().rr_batch_set_schedule(self.h, _ptr(env_map, torch.int32, self.N) if env_map is not None else None,
                                            _ptr(cost, torch.int32, self.N) if cost is not None else None))
+
+    def env_params_supported(self) -> bool:
+        """Whether this batch's model / solver has kernel instances with per-env parameters (C ABI `rr_batch_env_params_supported`)."""
+        return _check(lib().rr_batch_env_params_supported(self.h)) == 1
+
+    def set_env_params(self, dof_f: Optional[torch.Tensor] = None, act_f: Optional[torch.Tensor] = None, con_f: Optional[torch.Tensor] = None):
+        """Per-environment parameter rows (C ABI `rr_batch_set_env_params`): float32 device tensors dof_f [N, nv, 16], act_f [N, nu, 8],
+        con_f [N, ncon, 26] as `ktables.env_param_tables` builds them; None leaves that table the model's shared one, all None clears
+        the parameters.  The batch keeps its own copy."""
+        d, N = self.dims, self.N
+        for name, t, shape in (("dof_f", dof_f, (N, d.nv, 16)), ("act_f", act_f, (N, d.nu, 8)), ("con_f", con_f, (N, d.ncon, 26))):
+            if t is not None and tuple(t.shape) != shape:
+                raise ValueError(f"set_env_params: {name} has shape {tuple(t.shape)}, expected {shape}")
+        p = RREnvParams(_ptr(dof_f), _ptr(act_f), _ptr(con_f), d.nv, d.nu, d.ncon, N)
+        _check(lib().rr_batch_set_env_params(self.h, C.byref(p)))
 
     def set_timing(self, enable: bool):
         _check(lib().rr_batch_set_timing(self.h, int(enable)))

@@ -434,3 +434,128 @@ def _pair_tables(m, k, anc, anc_adr, ddepth, last_desc):
         packed[:, j // 4] |= rows10[:, j] << (8 * (j % 4))
     k["k_con_chain_rows"] = (packed & 0xFFFFFFFF).astype(np.uint32).view(np.int32).reshape(-1)
     k["k_con_chain_packed"] = np.zeros((9, LANES), np.int32)        # (static-slot table of the floor-contact instances: unused)
+
+
+# ----------------------------------------------------------------------------------------- domain randomisation
+# The model fields (MuJoCo's names) whose values may differ per environment, and what the step kernel derives from them:
+#   geom_friction    -> con_friction (max over the pair, or the geom of higher priority) -> k_con_f cell 16 (mu), 17 (effective invweight)
+#   dof_damping      -> k_dof_f cell 1          dof_armature -> k_dof_f cell 0
+#   actuator_gainprm -> k_act_f cell 0 (column 0: the gain)       actuator_biasprm -> k_act_f cells 1..3 (columns 0..2)
+# Constants that MJX does not recompute under a vmapped `sys` either -- dof_invweight0, body_invweight0 (hence con_invweight),
+# stat_meaninertia -- stay as compiled.  Masses, inertias and geometry would need those recomputed and are not supported.
+ENV_PARAM_FIELDS = ("geom_friction", "dof_damping", "dof_armature", "actuator_gainprm", "actuator_biasprm")
+_CON_MU, _CON_INVW = 16, 17          # cells of a k_con_f row (floor-contact models, 26 floats)
+
+
+def _check_param_model(m):
+    if int(np.asarray(m.get("k_dyn", 0)).reshape(-1)[0]):
+        raise ValueError("per-env parameters: models with candidate-pair contacts (k_dyn) are not supported")
+    if "h_dims" in m:
+        raise ValueError("per-env parameters: two-tree models with replica tables (h_*) are not supported")
+    for k in ("k_dof_f", "k_act_f", "k_con_f", "con_geom1", "con_geom2", "geom_priority", "geom_friction", "con_invweight", "opt_impratio"):
+        if k not in m:
+            raise ValueError(f"per-env parameters: the model lacks '{k}'")
+
+
+def _field_shape(m, name):
+    nv, nu, ng = int(m["nv"]), int(m["nu"]), int(m["ngeom"])
+    return {"geom_friction": (ng, 3), "dof_damping": (nv,), "dof_armature": (nv,), "actuator_gainprm": (nu, None),
+            "actuator_biasprm": (nu, None)}[name]
+
+
+def _batched_fields(m, fields, lead):
+    """Validate `fields` (name -> array with leading shape `lead`) and return them as float32-valued float64 arrays (the values the
+    blob stores, the arithmetic of the compiler).  actuator_gainprm / actuator_biasprm take MuJoCo's [nu, 10] rows or any prefix of at
+    least 1 / 3 columns."""
+    out = {}
+    for name, v in fields.items():
+        if name not in ENV_PARAM_FIELDS:
+            raise ValueError(f"per-env parameters: field '{name}' is not supported; the supported fields are {', '.join(ENV_PARAM_FIELDS)}")
+        a = np.asarray(v)
+        want = _field_shape(m, name)
+        ok = a.ndim == len(lead) + len(want) and tuple(a.shape[:len(lead)]) == tuple(lead)
+        if ok:
+            tail = a.shape[len(lead):]
+            need = {"actuator_gainprm": 1, "actuator_biasprm": 3}.get(name)
+            ok = all(w is None or w == t for w, t in zip(want, tail)) and (need is None or tail[-1] >= need)
+        if not ok or not np.issubdtype(a.dtype, np.number):
+            shp = tuple(lead) + tuple("k" if w is None else w for w in want)
+            raise ValueError(f"per-env parameters: field '{name}' has shape {a.shape}, expected {shp}")
+        out[name] = a.astype(np.float32).astype(np.float64)
+    return out
+
+
+def _derive_param_tables(m, f, lead):
+    """con_friction [lead, ncon, 5] (or None) and the three float32 kernel tables [lead, rows, width] for validated fields `f`."""
+    f32 = lambda x: np.asarray(x, np.float32)
+    tile = lambda t: np.broadcast_to(f32(t), tuple(lead) + np.shape(t)).copy()
+    kd, ka, kc = tile(m["k_dof_f"]), tile(m["k_act_f"]), tile(m["k_con_f"])
+    if "dof_armature" in f:
+        kd[..., 0] = f["dof_armature"]
+    if "dof_damping" in f:
+        kd[..., 1] = f["dof_damping"]
+    if "actuator_gainprm" in f:
+        ka[..., 0] = f["actuator_gainprm"][..., 0]
+    if "actuator_biasprm" in f:
+        ka[..., 1:4] = f["actuator_biasprm"][..., :3]
+    cf = None
+    if "geom_friction" in f:
+        gf = f["geom_friction"]
+        g1, g2 = np.asarray(m["con_geom1"]), np.asarray(m["con_geom2"])
+        p1, p2 = np.asarray(m["geom_priority"])[g1], np.asarray(m["geom_priority"])[g2]
+        f1, f2 = gf[..., g1, :], gf[..., g2, :]
+        fr = np.where((p1 == p2)[:, None], np.maximum(f1, f2), np.where((p1 > p2)[:, None], f1, f2))      # as mjcf._collision_tables mixes them
+        cf = np.stack([fr[..., 0], fr[..., 0], fr[..., 1], fr[..., 2], fr[..., 2]], axis=-1)
+        mu = cf[..., 0]
+        ciw = np.asarray(m["con_invweight"], np.float64)
+        invw = (ciw + mu * mu * ciw) * 2 * mu * mu / float(np.asarray(m["opt_impratio"]).reshape(-1)[0])
+        # a contact whose mu is the model's keeps the compiled cell (the compiler formed it from float64 inputs the blob no longer holds):
+        # the identity draw reproduces the shipped rows bit for bit
+        same = f32(mu) == f32(m["k_con_f"])[:, _CON_MU]
+        kc[..., _CON_MU] = mu
+        kc[..., _CON_INVW] = np.where(same, kc[..., _CON_INVW], f32(invw))
+    return cf, kd, ka, kc
+
+
+def with_parameters(m, **fields):
+    """A copy of the model tables `m` (mjcf.load_blob / compile_mjcf) with the given fields replaced -- any of ENV_PARAM_FIELDS, shaped as
+    in MuJoCo -- and everything that depends on them re-derived: con_friction, and the kernel rows k_dof_f / k_act_f / k_con_f.
+    `mjcf.save_blob(with_parameters(m, ...), path)` is a model the oracle and the env load like any other."""
+    _check_param_model(m)
+    f = _batched_fields(m, fields, ())
+    cf, kd, ka, kc = _derive_param_tables(m, f, ())
+    out = dict(m)
+    like = lambda name, v: np.asarray(v).astype(np.asarray(m[name]).dtype)
+    for name in ("geom_friction", "dof_damping", "dof_armature"):
+        if name in f:
+            out[name] = like(name, f[name])
+    if "actuator_gainprm" in f:
+        out["actuator_gainprm0"] = like("actuator_gainprm0", f["actuator_gainprm"][:, 0])
+    if "actuator_biasprm" in f:
+        out["actuator_biasprm"] = like("actuator_biasprm", f["actuator_biasprm"][:, :3])
+    if cf is not None:
+        out["con_friction"] = like("con_friction", cf)
+    out["k_dof_f"], out["k_act_f"], out["k_con_f"] = like("k_dof_f", kd), like("k_act_f", ka), like("k_con_f", kc)
+    return out
+
+
+def env_param_tables(m, fields_batched):
+    """Per-environment kernel rows for `fields_batched` (name -> [N, ...] array, any of ENV_PARAM_FIELDS): float32 arrays
+    (dof_f [N, nv, 16], act_f [N, nu, 8], con_f [N, ncon, 26]) as rr_batch_set_env_params takes them.  Row e equals what
+    `with_parameters(m, field=value[e], ...)` builds, cell for cell."""
+    _check_param_model(m)
+    if not fields_batched:
+        raise ValueError(f"per-env parameters: no batched field given; the supported fields are {', '.join(ENV_PARAM_FIELDS)}")
+    ns = set()
+    for name, v in fields_batched.items():
+        if name not in ENV_PARAM_FIELDS:
+            raise ValueError(f"per-env parameters: field '{name}' is not supported; the supported fields are {', '.join(ENV_PARAM_FIELDS)}")
+        if np.ndim(v) < 1:
+            raise ValueError(f"per-env parameters: field '{name}' has no leading environment axis")
+        ns.add(int(np.shape(v)[0]))
+    if len(ns) != 1:
+        raise ValueError(f"per-env parameters: the fields {sorted(fields_batched)} disagree on the number of environments {sorted(ns)}")
+    N = ns.pop()
+    f = _batched_fields(m, fields_batched, (N,))
+    _, kd, ka, kc = _derive_param_tables(m, f, (N,))
+    return np.ascontiguousarray(kd), np.ascontiguousarray(ka), np.ascontiguousarray(kc)

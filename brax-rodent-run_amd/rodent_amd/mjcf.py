@@ -900,3 +900,10 @@ def load_blob(path: str) -> Dict[str, np.ndarray]:
         arr = np.frombuffer(raw, dtype=dtype, count=nbytes // 4, offset=off).reshape([d0, d1, d2, d3][:nd])
         out[name.rstrip(b"\0").decode()] = arr.copy()
     return out
+
+
+def with_parameters(m: Dict[str, np.ndarray], **fields) -> Dict[str, np.ndarray]:
+    """The model tables with some parameters replaced (geom_friction, dof_damping, dof_armature, actuator_gainprm, actuator_biasprm)
+    and everything derived from them rebuilt: see `ktables.with_parameters`."""
+    from .ktables import with_parameters as impl
+    return impl(m, **fields)

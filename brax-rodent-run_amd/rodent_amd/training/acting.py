@@ -139,6 +139,9 @@ class SubBatchRollout:
             st = torch.cuda.Stream(device)
             with torch.cuda.stream(st):                                  # the batch binds the stream it is created on
                 env = environment.with_num_envs(self.n, device)
+                params = environment.env_params() if hasattr(environment, "env_params") else None
+                if params is not None:                                   # domain randomisation: this sub-batch's slice of the draws
+                    env.set_env_params(**{k: (v[si * self.n:(si + 1) * self.n].contiguous() if v is not None else None) for k, v in params.items()})
                 wenv = wrappers.wrap(env, episode_length=episode_length, action_repeat=action_repeat)
                 gen = torch.Generator(device=device)
                 gen.manual_seed(seed * 1009 + si)

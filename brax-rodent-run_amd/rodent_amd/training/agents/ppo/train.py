@@ -35,6 +35,16 @@ def _local_env(environment, local_num_envs: int, device):
     raise ValueError(f"environment has {getattr(environment, 'num_envs', '?')} envs, need {local_num_envs} per rank")
 
 
+def randomization_keys(seed: int, process_id: int, local_num_envs: int, num_eval_envs: int):
+    """The keys `train` binds to `randomization_fn` on rank `process_id` [UP ppo.train]: `local_num_envs` keys split from the rank's
+    env key for the training env, `num_eval_envs` keys split from its eval key for the eval env (uint32 [n, 2] each).  The rank's key
+    is folded from its process id, so two ranks draw different parameters."""
+    _, local_key = jax_random.split(jax_random.PRNGKey(seed))
+    local_key = jax_random.fold_in(local_key, process_id)
+    _, key_env, eval_key = jax_random.split(local_key, 3)
+    return jax_random.split(key_env, local_num_envs), jax_random.split(eval_key, num_eval_envs)
+
+
 def train(
     environment,
     num_timesteps: int,
@@ -78,8 +88,6 @@ def train(
     3-float all-reduce {n, sum a, sum a^2} per minibatch (the north star's "advantage-normalisation all-reduce").
     """
     assert batch_size * num_minibatches % num_envs == 0
-    if randomization_fn is not None:
-        raise NotImplementedError("domain randomisation is not used by the reference launcher")
     xt = time.time()
     process_count, process_id = D.world_size(), D.rank()
     device_count = process_count                         # one device per process
@@ -93,7 +101,14 @@ def train(
 
     env = _local_env(environment, local_num_envs, getattr(environment, "device", None))
     device = env.device
-    wenv = wrappers.wrap(env, episode_length=episode_length, action_repeat=action_repeat)
+    # domain randomisation: `randomization_fn(sys, rng)` with the rank's keys bound, one key per env; the parameters stay with the env
+    rand_fn = eval_rand_fn = None
+    if randomization_fn is not None:
+        import functools
+        rand_keys, eval_rand_keys = randomization_keys(seed, process_id, local_num_envs, num_eval_envs)
+        rand_fn = functools.partial(randomization_fn, rng=rand_keys)
+        eval_rand_fn = functools.partial(randomization_fn, rng=eval_rand_keys)
+    wenv = wrappers.wrap(env, episode_length=episode_length, action_repeat=action_repeat, randomization_fn=rand_fn)
 
     # ---- keys [UP ppo.train]: reset keys follow the jax key tree so initial states match the reference
     key = jax_random.PRNGKey(seed)
@@ -155,9 +170,11 @@ def train(
     if eval_env is None and num_evals > 0 and num_eval_envs > 0:
         eval_env = _local_env(environment, num_eval_envs, device) if hasattr(environment, "with_num_envs") or \
             getattr(environment, "num_envs", None) == num_eval_envs else None
+    if eval_rand_fn is not None and eval_env is env and hasattr(environment, "with_num_envs"):
+        eval_env = environment.with_num_envs(num_eval_envs, device)     # its own batch: the eval env carries its own draws
     evaluator = None
     if eval_env is not None:
-        weval = wrappers.wrap(eval_env, episode_length=episode_length, action_repeat=action_repeat)
+        weval = wrappers.wrap(eval_env, episode_length=episode_length, action_repeat=action_repeat, randomization_fn=eval_rand_fn)
         evaluator = acting.Evaluator(weval, lambda p: make_policy(p, deterministic=deterministic_eval), num_eval_envs,
                                      episode_length, action_repeat, eval_key)
 

@@ -22,9 +22,24 @@ sys.path.insert(0, os.path.join(ROOT, "brax-rodent-run_amd"))
 import numpy as np
 import torch
 
-from rodent_amd import envs, preprocessing, rollout
+from rodent_amd import envs, jax_random, preprocessing, rollout
 from rodent_amd.io import model
 from rodent_amd.training.agents.ppo import train as ppo
+
+
+def domain_randomize(sys, rng):
+    """Example `randomization_fn` (--randomize), shaped like brax's: one key per env in `rng` [N, 2]; per env a friction scale in
+    [0.6, 1.4] and an actuator gain scale in [0.8, 1.2] (a position actuator's bias term -kp scales with its gain)."""
+    n = len(rng)
+    friction = np.repeat(sys.geom_friction[None], n, axis=0)
+    friction[:, :, 0] *= jax_random.uniform(jax_random.split(rng, 2)[:, 0], 1, 0.6, 1.4)
+    scale = jax_random.uniform(jax_random.split(rng, 2)[:, 1], 1, 0.8, 1.2)[:, :, None]
+    gain = np.repeat(sys.actuator_gainprm[None], n, axis=0)
+    bias = np.repeat(sys.actuator_biasprm[None], n, axis=0)
+    gain[:, :, 0:1] *= scale
+    bias[:, :, 1:2] *= scale
+    in_axes = {"geom_friction": 0, "actuator_gainprm": 0, "actuator_biasprm": 0}
+    return sys.tree_replace({"geom_friction": friction, "actuator_gainprm": gain, "actuator_biasprm": bias}), in_axes
 
 
 def main():
@@ -37,6 +52,7 @@ def main():
                     "--clip-name) or .npy with the root positions [T,3]; a synthetic line if absent")
     ap.add_argument("--clip-name", default="84")
     ap.add_argument("--max-training-steps", type=int, default=None)
+    ap.add_argument("--randomize", action="store_true", help="domain randomisation: per-env friction and actuator gain (domain_randomize)")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -70,7 +86,8 @@ def main():
         reward_scaling=1, episode_length=config["episode_length"], normalize_observations=True, action_repeat=1,
         unroll_length=10, num_minibatches=64, num_updates_per_batch=8, discounting=0.97,
         learning_rate=config["learning_rate"], entropy_cost=1e-3, num_envs=config["num_envs"],
-        batch_size=config["batch_size"], seed=0, max_training_steps=args.max_training_steps)
+        batch_size=config["batch_size"], seed=0, max_training_steps=args.max_training_steps,
+        randomization_fn=domain_randomize if args.randomize else None)
 
     run_id = uuid.uuid4()
     model_path = f"./model_checkpoints/{run_id}"

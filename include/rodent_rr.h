@@ -346,6 +346,26 @@ int rr_wrap_episode_autoreset(int32_t num_envs, int32_t narr, const float* const
  * it (rodent_amd/envs/base.py: PipelineEnv._rebalance).  Both pointers are read at every later launch of this batch. */
 int rr_batch_set_schedule(rr_batch* b, const int32_t* env_map, uint32_t* cost_cycles);
 
+/* Domain randomisation: per-environment model parameters.  Three float tables of the kernel hold the cells people randomise first --
+ * `dof_f` [N][nv][16] (cell 0 armature, 1 damping), `act_f` [N][nu][8] (cell 0 gain, 1..3 bias), `con_f` [N][ncon][26] (cell 16
+ * friction mu, 17 the contact's effective inverse weight) -- laid out like the model's k_dof_f / k_act_f / k_con_f with a leading
+ * environment axis (rodent_amd/ktables.py env_param_tables builds them).  Each pointer is nullable: a null table stays the
+ * model's shared one.  The batch copies the data (device memory) into allocations it owns, on its stream, and frees a previous copy;
+ * a NULL `p`, or three null pointers, clears the parameters.  From then on every launch of the batch runs the instance that reads
+ * environment e's rows [e] (same arithmetic; rr_kernel.h rr_rand_kernel); such a batch refuses the debug dump, the contact-geometry
+ * outputs and the profile build.  RR_EUNSUPPORTED (rr_last_error says why) for models with candidate-pair contacts, two-tree
+ * models on the two-wave instance, the Newton solver and slot counts other than (2,2,1).  Synchronises the batch's stream. */
+typedef struct rr_env_params {
+  const float* dof_f;     /* nullable */
+  const float* act_f;     /* nullable */
+  const float* con_f;     /* nullable */
+  int32_t dof_rows, act_rows, con_rows;   /* rows per environment: the model's nv, nu, ncon */
+  int32_t num_envs;                       /* the batch's */
+} rr_env_params;
+int rr_batch_set_env_params(rr_batch* b, const rr_env_params* p);
+/* 1 when rr_batch_set_env_params can serve this batch's model / solver, 0 otherwise */
+int rr_batch_env_params_supported(const rr_batch* b);
+
 /* Debug dump layout: names[i] begins at float offsets[i] of each env's debug row; returns the field count. */
 int rr_debug_layout(const rr_batch* b, const char*** names, const int32_t** offsets, const int32_t** sizes);
 

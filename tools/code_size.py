@@ -16,10 +16,12 @@ def owner(line):
     for s, n in funcs:
         if s <= line: o = n
     return o
-fid = None
+fid = body_fid = None     # the kernel's body lives in rr_step_body.inc (included by both __global__ entries)
 for l in asm:
     m = re.match(r'\s*\.file\s+(\d+) "[^"]*" "rr_kernel.h"', l)
     if m: fid = m.group(1)
+    m = re.match(r'\s*\.file\s+(\d+) "[^"]*" "rr_step_body.inc"', l)
+    if m: body_fid = m.group(1)
 start = next(i for i, l in enumerate(asm) if l.startswith("_Z14rr_step_kernel" + sym))
 cnt, lines = collections.Counter(), collections.Counter()
 cur = "?"; curline = 0; total = 0
@@ -28,6 +30,7 @@ for l in asm[start:]:
     m = re.match(r"\s*\.loc\s+(\d+) (\d+)", l)
     if m:
         if m.group(1) == fid: curline = int(m.group(2)); cur = owner(curline)
+        elif m.group(1) == body_fid: curline = 0; cur = "kernel_body"
         else: cur = "<hip headers>"
         continue
     if re.match(r"\t[a-z]\w+", l) and not l.startswith("\t."):
