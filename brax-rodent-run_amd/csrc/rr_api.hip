@@ -272,6 +272,7 @@ struct rr_batch {
   unsigned* dyn_overflow = nullptr;     // DYN models: (env, env step) events in which more pairs penetrated than the wave has contact slots (rr_batch_contact_overflow)
   unsigned* progress = nullptr;         // pacing counter of multi-step launches (RRIO::progress); RR_PACE=0 turns pacing off
   float *env_dof_f = nullptr, *env_act_f = nullptr, *env_con_f = nullptr;     // per-env parameter rows, owned (rr_batch_set_env_params)
+  float* eval_actions = nullptr;        // [N][nu]: where an evaluation launch without actions_out keeps the current action (rr_env_unroll_eval)
   bool has_env_params() const { return env_dof_f || env_act_f || env_con_f; }
 };
 
@@ -376,6 +377,19 @@ static kern_t pick_rand_kernel(const rr_model* m, bool unroll = false, bool acto
   return k[form];
 }
 
+// Evaluation instances (rr_eval_kernel): the production CG multi-step form with the actor of the (2,2,1) slot counts, fixed-dimension,
+// generic or generic with candidate-pair contacts.  `why`: the reason when the model / solver has none.
+static kern_t pick_eval_kernel(const rr_model* m, const char** why = nullptr) {
+  const char* w = nullptr;
+  if (m->solver == 2) w = "the Newton solver has no multi-step instance";
+  else if (m->pair_ok) w = "two-tree models served by the two-wave pair instance have no multi-step instance";
+  else if (!(m->NBS == 2 && m->NVS == 2 && m->NCS == 1)) w = "only the (2,2,1) slot counts have an evaluation instance";
+  if (why) *why = w;
+  if (w) return nullptr;
+  if (m->dyn) return rr_eval_kernel<RRDims, true>;
+  return RRDimsRodent::matches(m->kd) ? rr_eval_kernel<RRDimsRodent> : (RRDimsRodentNew::matches(m->kd) ? rr_eval_kernel<RRDimsRodentNew> : rr_eval_kernel<RRDims>);
+}
+
 extern "C" int rr_batch_create(const rr_model* m, int32_t num_envs, int32_t device, void* stream, rr_batch** out) {
   if (!m || !out || num_envs <= 0) return fail(RR_EINVAL, "rr_batch_create: bad argument");
   if (!pick_kernel(m)) return fail(RR_EUNSUPPORTED, "rr_batch_create: no kernel instance for this model's slot counts");
@@ -428,7 +442,7 @@ extern "C" int rr_batch_create(const rr_model* m, int32_t num_envs, int32_t devi
   if (m->dims.lds_bytes > 64 * 1024) { rr_batch_destroy(b); return fail(RR_EUNSUPPORTED, "rr_batch_create: per-env working set exceeds the 64 KiB of LDS one workgroup may address"); }
   kern_t pair_kern = m->pair_ok ? pick_pair_kernel(m) : nullptr;
   for (kern_t kk : {kern, pick_kernel(m, false, true), pick_unroll_kernel(m), pick_unroll_kernel(m, true), pick_kernel(m, true), pair_kern,
-                    pick_rand_kernel(m), pick_rand_kernel(m, true), pick_rand_kernel(m, true, true)}) {   // every instance a launch may pick
+                    pick_rand_kernel(m), pick_rand_kernel(m, true), pick_rand_kernel(m, true, true), pick_eval_kernel(m)}) {   // every instance a launch may pick
     if (!kk) continue;
     hipError_t e = hipFuncSetAttribute((const void*)kk, hipFuncAttributeMaxDynamicSharedMemorySize, kk == pair_kern ? 2 * m->kd_rep.lds_bytes_rep + 128 : m->dims.lds_bytes);
     if (e != hipSuccess) { rr_batch_destroy(b); return fail(RR_EHIP, std::string("hipFuncSetAttribute: ") + hipGetErrorString(e)); }
@@ -466,7 +480,7 @@ extern "C" void rr_batch_destroy(rr_batch* b) {
   if (!b) return;
   if (b->counted) b->m->live_batches.fetch_sub(1);
   for (void* p : b->dev_allocs) (void)hipFree(p);
-  for (float* p : {b->env_dof_f, b->env_act_f, b->env_con_f}) if (p) (void)hipFree(p);
+  for (float* p : {b->env_dof_f, b->env_act_f, b->env_con_f, b->eval_actions}) if (p) (void)hipFree(p);
   for (hipEvent_t e : b->ev0) (void)hipEventDestroy(e);
   for (hipEvent_t e : b->ev1) (void)hipEventDestroy(e);
   delete b;
@@ -497,10 +511,10 @@ static int collect_timing(rr_batch* b, bool all = true) {
 
 static int launch(rr_batch* b, const rr_state* st, const float* ctrl, int n_frames, const rr_env_io* env, const rr_outputs* out, int mode,
                   const rr_state* st_in = nullptr, const int32_t* cur_frame_in = nullptr, const rr_unroll_io* un = nullptr, int unroll_T = 0,
-                  const rr_actor_io* ac = nullptr) {
+                  const rr_actor_io* ac = nullptr, const rr_eval_io* ev = nullptr) {
   if (!b || !st || !st->qpos || !st->qvel || !st->act || !st->qacc_warmstart) return fail(RR_EINVAL, "launch: null state pointer");
   if (st_in && (!st_in->qpos || !st_in->qvel || !st_in->act || !st_in->qacc_warmstart)) return fail(RR_EINVAL, "launch: null input state pointer");
-  if ((mode & 1) && (!ctrl || n_frames <= 0)) return fail(RR_EINVAL, "launch: step needs ctrl and n_frames > 0");
+  if ((mode & 1) && ((!ctrl && !ev) || n_frames <= 0)) return fail(RR_EINVAL, "launch: step needs ctrl and n_frames > 0");      // ev: the batch's own action rows
   RRIO io;
   memset(&io, 0, sizeof(io));
   io.qpos = st->qpos; io.qvel = st->qvel; io.act = st->act; io.warm = st->qacc_warmstart; io.ctrl = ctrl;
@@ -525,7 +539,12 @@ static int launch(rr_batch* b, const rr_state* st, const float* ctrl, int n_fram
   kern_t kern = pick_kernel(b->m, b->prof != nullptr, io.dbg != nullptr || io.o_cdist || io.o_cpos || io.o_cframe);
   if (un) {      // multi-step rollout: the UNROLL instance, no diagnostics
     if (b->prof || io.dbg || io.o_cdist || io.o_cpos || io.o_cframe || out) return fail(RR_EUNSUPPORTED, "rr_env_unroll: no diagnostic outputs in a multi-step rollout");
-    kern = pick_unroll_kernel(b->m, ac != nullptr);
+    if (ev) {      // evaluation form: its own entry, shared tables only
+      const char* why = nullptr;
+      kern = pick_eval_kernel(b->m, &why);
+      if (!kern) return fail(RR_EUNSUPPORTED, std::string("rr_env_unroll_eval: ") + why);
+      if (b->has_env_params()) return fail(RR_EUNSUPPORTED, "rr_env_unroll_eval: no evaluation instance reads per-env parameters (this batch carries some)");
+    } else kern = pick_unroll_kernel(b->m, ac != nullptr);
     if (!kern) return fail(RR_EUNSUPPORTED, "rr_env_unroll: no multi-step kernel instance for this model / solver");
     if (ac) {
       if (b->m->dims.obs_dim > 1280) return fail(RR_EUNSUPPORTED, "rr_env_unroll_policy: observation wider than 1280");
@@ -539,6 +558,14 @@ static int launch(rr_batch* b, const rr_state* st, const float* ctrl, int n_fram
       io.a_seg = ac->segment_length > 0 ? ac->segment_length : unroll_T;
       if (unroll_T % io.a_seg) return fail(RR_EINVAL, "rr_env_unroll_policy: num_steps must be a multiple of segment_length");
       io.obs = ac->traj_obs;
+      if (ev) {
+        io.t_obs = io.obs = ev->obs_ring; io.e_metrics = ev->eval_metrics; io.e_qpos_out = ev->qpos_out; io.a_seg = unroll_T;
+        io.a_pad = (ev->raw_env ? RR_EVAL_RAW : 0) | (ac->actions_out ? RR_EVAL_ACTIONS : 0);
+        if (!ac->actions_out) {
+          if (!b->eval_actions) HIPCHK(hipMalloc((void**)&b->eval_actions, (size_t)b->N * b->m->dims.nu * sizeof(float)));
+          io.a_actions = b->eval_actions; io.ctrl = b->eval_actions;
+        }
+      }
     }
     io.first_qpos = un->first.qpos; io.first_qvel = un->first.qvel; io.first_act = un->first.act; io.first_warm = un->first.qacc_warmstart;
     io.first_obs = un->first_obs; io.prev_done = un->prev_done; io.steps_in = un->steps_in; io.steps_out = un->steps_out;
@@ -638,6 +665,27 @@ extern "C" int rr_env_unroll_policy(rr_batch* b, const rr_state* in, const rr_st
   rr_env_io e = *env;
   e.obs = actor->traj_obs;                   // the observations of the launch go to the trajectory
   return launch(b, outst, actor->actions_out, n_frames, &e, nullptr, 1, in, cur_frame_in, wrap, num_steps, actor);
+}
+extern "C" int rr_batch_eval_supported(const rr_batch* b) {
+  if (!b) return fail(RR_EINVAL, "rr_batch_eval_supported: null batch");
+  return (pick_eval_kernel(b->m) && !b->has_env_params() && !b->prof && b->m->dims.obs_dim <= 1280 && b->m->dims.nu <= 64) ? 1 : 0;
+}
+extern "C" int rr_env_unroll_eval(rr_batch* b, const rr_state* in, const rr_state* outst, int32_t num_steps, int32_t n_frames, const rr_env_io* env,
+                                  const int32_t* cur_frame_in, const rr_unroll_io* wrap, const rr_actor_io* actor, const rr_eval_io* ev) {
+  if (!env || !in || !cur_frame_in || !actor || !ev || num_steps <= 0) return fail(RR_EINVAL, "rr_env_unroll_eval: bad argument");
+  if (!ev->obs_ring) return fail(RR_EINVAL, "rr_env_unroll_eval: null observation ring");
+  if (!ev->raw_env && (!wrap || !wrap->first.qpos || !wrap->first.qvel || !wrap->first.act || !wrap->first.qacc_warmstart || !wrap->first_obs || !wrap->prev_done ||
+                       !wrap->steps_in || !wrap->steps_out || !wrap->truncation_out))
+    return fail(RR_EINVAL, "rr_env_unroll_eval: null wrapper pointer (only the raw form runs without the wrappers' state)");
+  if (!actor->obs_in || !actor->w0 || !actor->b0 || !actor->head_wt || !actor->head_b || (actor->mean == nullptr) != (actor->std == nullptr))
+    return fail(RR_EINVAL, "rr_env_unroll_eval: null actor pointer");
+  for (int l = 1; l < actor->nhidden && l < 5; ++l)
+    if (!actor->hidden_wt[l - 1] || !actor->hidden_b[l - 1]) return fail(RR_EINVAL, "rr_env_unroll_eval: null hidden layer");
+  rr_unroll_io none;
+  memset(&none, 0, sizeof(none));
+  rr_env_io e = *env;
+  e.obs = ev->obs_ring;                      // the observations of the launch live in the ring
+  return launch(b, outst, actor->actions_out, n_frames, &e, nullptr, 1, in, cur_frame_in, ev->raw_env ? &none : wrap, num_steps, actor, ev);
 }
 extern "C" int rr_pipeline_init(rr_batch* b, const rr_state* st, const rr_outputs* out) { return launch(b, st, nullptr, 1, nullptr, out, 0); }
 extern "C" int rr_pipeline_step(rr_batch* b, const rr_state* st, const float* ctrl, int32_t n_frames, const rr_outputs* out) {

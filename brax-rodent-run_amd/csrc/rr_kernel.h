@@ -162,6 +162,8 @@ struct rr_row {
 __device__ __forceinline__ rr_row<int> row_at(rr_gi t, int stride, int idx) { return rr_row<int>{(rr_gc)t, (unsigned)idx * (4u * (unsigned)stride), 0}; }
 __device__ __forceinline__ rr_row<float> row_at(rr_gf t, int stride, int idx) { return rr_row<float>{(rr_gc)t, (unsigned)idx * (4u * (unsigned)stride), 0}; }
 
+#define RR_EVAL_RAW 1
+#define RR_EVAL_ACTIONS 2
 struct RRIO {
   float *qpos, *qvel, *act, *warm;                         // state written by the launch
   const float *qpos_in, *qvel_in, *act_in, *warm_in;       // state read (== the above for an in-place step)
@@ -199,6 +201,8 @@ struct RRIO {
   float a_min_std;
   int a_nh;
   int a_seg, a_pad;                               // trajectory segment length L (unroll_T = U * L): the buffers are [U][N][L(+1)][...]
+                                                  // a_pad: EVAL instances only -- bit 0 (RR_EVAL_RAW): no Episode / AutoReset wrappers between the steps;
+                                                  // bit 1 (RR_EVAL_ACTIONS): a_actions is [unroll_T][N][nu] (else one row set [N][nu], reused by every step)
   // PACING of a multi-step launch (nullable): one counter per launch, zeroed by the host; every environment adds 1 per finished env
   // step, so counter / num_envs is the launch's average progress.  An environment behind it by more than a fraction of a step raises
   // its wave priority (Wave::env_prio): the launch ends when its SLOWEST environment does, and a wave that outranks its SIMD partner
@@ -215,6 +219,12 @@ struct RRIO {
   const float* env_dof_f;            // [N][nv][16]
   const float* env_act_f;            // [N][nu][8]
   const float* env_con_f;            // [N][ncon][26]
+  // EVALUATION (EVAL instances, rr_env_unroll_eval: rr_eval_kernel): the multi-step form with the actor inside, without the trajectory.
+  // t_obs is then a ring of two observation rows per environment, [N][2][obs] (step t reads row t & 1 and writes row (t + 1) & 1), the
+  // other t_* arrays are not touched, a_noise may be null (the deterministic policy) and a_pad carries the flags below.
+  float* e_metrics;                  // nullable [N][6], read and written: episode_steps, active_episodes, then the sums of pos_reward, reward_quadctrl,
+                                     // reward_alive, reward over the env's active steps (brax EvalWrapper's eval_metrics)
+  float* e_qpos_out;                 // nullable [unroll_T + 1][N][nq]: row 0 the incoming qpos, row t + 1 the qpos after step t (before a restore)
   int mode;  // 0 = forward only (pipeline_init), 1 = step; bit 1 (2) = env epilogue as reset (obs only)
   int pad_;
 };
@@ -2246,12 +2256,15 @@ static __device__ __forceinline__ RRTraj rr_traj(const RRIO& io, int s) { RRTraj
 static __device__ __forceinline__ size_t rr_traj_obs(const RRIO& io, int N, int env, int u, int t) { return ((size_t)u * N + env) * (io.a_seg + 1) + t; }   // row index
 static __device__ __forceinline__ size_t rr_traj_at(const RRIO& io, int N, int env, int s) { const RRTraj r = rr_traj(io, s); return ((size_t)r.u * N + env) * io.a_seg + r.t; }
 static __device__ __forceinline__ float rr_softplus_k(float x) { return fmaxf(x, 0.0f) + log1pf(expf(-fabsf(x))); }
-template <class DT>
+// EVAL (rr_eval_kernel): the observation comes from the env's two-row ring, a null noise pointer is the deterministic policy (raw = loc,
+// formed as loc + scale * 0 so that it equals the sampled form under all-zero noise bit for bit), and nothing but the action is recorded.
+template <bool EVAL = false, class DT>
 __device__ __forceinline__ void rr_actor_step(const RRIO& io, const DT& D, int lane, int env, int ut, int num_envs) {
   constexpr int JM = 20;                      // observation entries per lane (host check: obs_dim <= 1280)
   const int K = D.obs_dim, A = D.nu;
-  const RRTraj tr = rr_traj(io, ut);
-  const float* ob = io.t_obs + rr_traj_obs(io, num_envs, env, tr.u, tr.t) * K;
+  const float* ob;
+  if constexpr (EVAL) ob = io.t_obs + ((size_t)env * 2 + (ut & 1)) * K;
+  else { const RRTraj tr = rr_traj(io, ut); ob = io.t_obs + rr_traj_obs(io, num_envs, env, tr.u, tr.t) * K; }
   float x[JM];
 #pragma unroll
   for (int j = 0; j < JM; ++j) {
@@ -2308,6 +2321,15 @@ __device__ __forceinline__ void rr_actor_step(const RRIO& io, const DT& D, int l
       s_raw = fmaf(hk, io.a_Wth[k * 128 + A + lane], s_raw);
     }
   }
+  if constexpr (EVAL) {
+    if (lane < A) {
+      const float scale = rr_softplus_k(s_raw) + io.a_min_std;
+      const float nz = io.a_noise ? io.a_noise[((size_t)ut * num_envs + env) * A + lane] : 0.0f;
+      const float raw = o + scale * nz;
+      io.a_actions[((size_t)((io.a_pad & RR_EVAL_ACTIONS) ? ut : 0) * num_envs + env) * A + lane] = tanhf(raw);
+    }
+    return;
+  }
   float lp = 0.0f;
   if (lane < A) {
     const float HALF_LOG_2PI = 0.91893853320467274178f, LOG2 = 0.69314718055994530942f;
@@ -2339,7 +2361,7 @@ __device__ __forceinline__ void rr_actor_step(const RRIO& io, const DT& D, int l
 template <int NBS, int NVS, int NCS, bool PROF, bool DBG, class DT, bool NEWTON = false, bool UNROLL = false, bool ACTOR = false, bool PAIR = false, bool DYN = false>
 __global__ __launch_bounds__((PAIR ? 2 : 1) * RR_LANES, (NVS >= 3 ? 1 : 2)) void rr_step_kernel(const RRDims Dk, const RRTables Tk, const RRIO io_kernarg, const int num_envs,
                                                            const int n_frames) {
-  constexpr bool RAND = false;
+  constexpr bool RAND = false, EVAL = false;
 #include "rr_step_body.inc"
 }
 // Per-environment parameters: the same argument list (load_io / load_tables / load_dims find the block at the same offsets), production
@@ -2347,6 +2369,17 @@ __global__ __launch_bounds__((PAIR ? 2 : 1) * RR_LANES, (NVS >= 3 ? 1 : 2)) void
 template <class DT, bool UNROLL = false, bool ACTOR = false>
 __global__ __launch_bounds__(RR_LANES, 2) void rr_rand_kernel(const RRDims Dk, const RRTables Tk, const RRIO io_kernarg, const int num_envs, const int n_frames) {
   constexpr int NBS = 2, NVS = 2, NCS = 1;
-  constexpr bool PROF = false, DBG = false, NEWTON = false, PAIR = false, DYN = false, RAND = true;
+  constexpr bool PROF = false, DBG = false, NEWTON = false, PAIR = false, DYN = false, RAND = true, EVAL = false;
+#include "rr_step_body.inc"
+}
+// Evaluation (rr_env_unroll_eval): the multi-step form with the actor inside as brax's Evaluator and the launcher's evaluation rollout
+// use it -- EvalWrapper's sums kept in place, the policy deterministic on request, no trajectory (a two-row observation ring), optionally
+// without the Episode / AutoReset wrappers, optionally with the qpos of every step (RRIO::e_*).  A third entry for the same reason
+// rr_rand_kernel is one: the instances of the other two keep their token stream, every `if (EVAL)` in the body folds away there.
+// Production CG instances of the (2,2,1) slot counts: fixed-dimension, generic, generic with candidate-pair contacts (DYN).
+template <class DT, bool DYN = false>
+__global__ __launch_bounds__(RR_LANES, 2) void rr_eval_kernel(const RRDims Dk, const RRTables Tk, const RRIO io_kernarg, const int num_envs, const int n_frames) {
+  constexpr int NBS = 2, NVS = 2, NCS = 1;
+  constexpr bool PROF = false, DBG = false, NEWTON = false, PAIR = false, RAND = false, UNROLL = true, ACTOR = true, EVAL = true;
 #include "rr_step_body.inc"
 }

@@ -1,10 +1,11 @@
 // rr_step_body.inc -- the body of the step kernel, included by each of its __global__ entries in rr_kernel.h (rr_step_kernel,
-// rr_rand_kernel).  In scope where it is included: the kernel's five arguments (Dk, Tk, io_kernarg, num_envs, n_frames) and the
-// compile-time switches NBS, NVS, NCS, PROF, DBG, DT, NEWTON, UNROLL, ACTOR, PAIR, DYN, RAND.
+// rr_rand_kernel, rr_eval_kernel).  In scope where it is included: the kernel's five arguments (Dk, Tk, io_kernarg, num_envs, n_frames) and the
+// compile-time switches NBS, NVS, NCS, PROF, DBG, DT, NEWTON, UNROLL, ACTOR, PAIR, DYN, RAND, EVAL.
 // Why text and not a function: see the note above rr_step_kernel.
   static_assert(!PAIR || (!PROF && !DBG && !NEWTON && !UNROLL && !ACTOR), "PAIR: production physics instance only");
   static_assert(!DYN || (!PROF && !DBG && !NEWTON && !PAIR), "DYN: production instances only (single-step, multi-step, multi-step with the actor)");
   static_assert(!ACTOR || UNROLL, "the actor lives in the multi-step instances");
+  static_assert(!EVAL || (ACTOR && !RAND && !PROF && !DBG && !NEWTON && !PAIR), "EVAL: a form of the production multi-step instance with the actor");
   extern __shared__ __attribute__((aligned(16))) float lds[];
   int env = blockIdx.x;
   if (env >= num_envs) return;
@@ -39,8 +40,10 @@
   unsigned u_work = 0;
   int u_overflow = 0;            // DYN: some step of this launch dropped pairs (RRIO::cost bit 31 of a multi-step launch)
   if (UNROLL) {
+    if (!EVAL || !(io.a_pad & RR_EVAL_RAW)) {      // EVAL without the wrappers: no wrapper state (the pointers may be null)
     u_steps = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(io.steps_in[env])));
     u_prev_done = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(io.prev_done[env])));
+    }
     u_frame = __builtin_amdgcn_readfirstlane(io.cur_frame_in[env]);
   }
   int niter = 0;
@@ -49,17 +52,18 @@
   if (UNROLL) { lane = opaque(lane); w.lane = lane; asm volatile("" : "+s"(env)); if (RAND) w.renv = env; io = load_io(); }
   const RRTables T = w.tables();
   const int senv = PAIR ? 2 * env + wrep : env;      // row of this wave's replica in the state arrays (from the step's own copy of env: see RR_FRAME_LOCAL)
-  const size_t ctrl_at = UNROLL ? ((size_t)ut * num_envs + env) * D.nu : (size_t)senv * D.nu;
+  const size_t ctrl_at = UNROLL ? ((size_t)((EVAL && !(io.a_pad & RR_EVAL_ACTIONS)) ? 0 : ut) * num_envs + env) * D.nu : (size_t)senv * D.nu;
   if (ACTOR) {
-    if (ut == 0) {       // the observation the rollout starts from is row 0 of the env's trajectory
-      for (int i = lane; i < D.obs_dim; i += RR_LANES) io.t_obs[rr_traj_obs(io, num_envs, env, 0, 0) * D.obs_dim + i] = io.a_obs_in[(size_t)env * D.obs_dim + i];
+    if (ut == 0) {       // the observation the rollout starts from is row 0 of the env's trajectory (EVAL: of its two-row ring)
+      for (int i = lane; i < D.obs_dim; i += RR_LANES) io.t_obs[(EVAL ? (size_t)env * 2 : rr_traj_obs(io, num_envs, env, 0, 0)) * D.obs_dim + i] = io.a_obs_in[(size_t)env * D.obs_dim + i];
+      if (EVAL && io.e_qpos_out) for (int i = lane; i < D.nq; i += RR_LANES) io.e_qpos_out[(size_t)env * D.nq + i] = io.qpos_in[(size_t)env * D.nq + i];
     }
     // ORDERING through global memory inside one wave: the observation row the actor reads was written by OTHER lanes of this wave (the
     // previous step's epilogue / the copy above), and the action it writes (lanes < A) is read back as ctrl by all lanes below.  Same-wave
     // vector memory operations complete in order, but the compiler must not move them across each other either: a wavefront-scope fence on
     // both sides states the dependency (guarded by tests/test_gpu_ppo.py::test_one_launch_unroll_with_the_actor_inside, bitwise).
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    rr_actor_step(io, D, lane, env, ut, num_envs);
+    rr_actor_step<EVAL>(io, D, lane, env, ut, num_envs);
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
   }
   // ---- load state (a multi-step rollout keeps it in LDS after its first step)
@@ -176,7 +180,7 @@
       if (io.o_cinert) for (int e = lane; e < 10 * D.nbody; e += RR_LANES) io.o_cinert[(size_t)env * 10 * D.nbody + e] = w.s_cinert[e];
       if (io.o_cvel) for (int e = lane; e < 6 * D.nbody; e += RR_LANES) io.o_cvel[(size_t)env * 6 * D.nbody + e] = w.s_cvel[e];
       if (io.obs) {
-        float* ob = (ACTOR ? io.t_obs + rr_traj_obs(io, num_envs, env, rr_traj(io, ut).u, rr_traj(io, ut).t + 1) * D.obs_dim : io.obs + (size_t)env * D.obs_dim) + D.nq + D.nv;
+        float* ob = (EVAL ? io.t_obs + ((size_t)env * 2 + ((ut + 1) & 1)) * D.obs_dim : ACTOR ? io.t_obs + rr_traj_obs(io, num_envs, env, rr_traj(io, ut).u, rr_traj(io, ut).t + 1) * D.obs_dim : io.obs + (size_t)env * D.obs_dim) + D.nq + D.nv;
         for (int i = lane; i < 10 * (D.nbody - 1); i += RR_LANES) ob[i] = w.s_cinert[10 + i];
         ob += 10 * (D.nbody - 1);
         for (int i = lane; i < 6 * (D.nbody - 1); i += RR_LANES) ob[i] = w.s_cvel[6 + i];
@@ -296,7 +300,7 @@
     const bool is_reset = (mode & 2) != 0;
     const int old_frame = UNROLL ? u_frame : io.cur_frame_in[env];
     const int new_frame = is_reset ? old_frame : old_frame + 1;
-    float* ob = ACTOR ? io.t_obs + rr_traj_obs(io, num_envs, env, rr_traj(io, ut).u, rr_traj(io, ut).t + 1) * D.obs_dim : io.obs + (size_t)env * D.obs_dim;
+    float* ob = EVAL ? io.t_obs + ((size_t)env * 2 + ((ut + 1) & 1)) * D.obs_dim : ACTOR ? io.t_obs + rr_traj_obs(io, num_envs, env, rr_traj(io, ut).u, rr_traj(io, ut).t + 1) * D.obs_dim : io.obs + (size_t)env * D.obs_dim;
     int o = 0;
     for (int i = lane; i < D.nq; i += RR_LANES) ob[o + i] = w.s_qpos[i];
     o += D.nq;
@@ -339,7 +343,7 @@
         const float cc = __fmul_rn(io.ctrl_cost_weight, a2);     // explicit roundings: every instance of the kernel forms the reward identically
         const float rew = __fsub_rn(__fadd_rn(pos_reward, hr), cc);   // (left to the optimiser, one instance fused the product into the sum: 1 ulp)
         io.reward[env] = rew;
-        if (ACTOR) io.t_reward[rr_traj_at(io, num_envs, env, ut)] = rew;
+        if (ACTOR && !EVAL) io.t_reward[rr_traj_at(io, num_envs, env, ut)] = rew;
         io.done[env] = io.terminate_when_unhealthy ? 1.0f - healthy : 0.0f;
         io.metrics[3 * env] = pos_reward; io.metrics[3 * env + 1] = -cc; io.metrics[3 * env + 2] = hr;
         io.cur_frame[env] = new_frame;
@@ -352,13 +356,30 @@
       const float z = w.s_qpos[2];
       const float healthy = (z < io.z_min || z > io.z_max) ? 0.0f : 1.0f;
       const float done_env = io.terminate_when_unhealthy ? 1.0f - healthy : 0.0f;
-      u_steps = (u_prev_done != 0.0f ? 0.0f : u_steps) + 1.0f;
-      const bool over = u_steps >= io.episode_length;
+      const bool wrapped = !EVAL || !(io.a_pad & RR_EVAL_RAW);      // EVAL without the wrappers: the env's own done, no step count, no restore
+      if (wrapped) u_steps = (u_prev_done != 0.0f ? 0.0f : u_steps) + 1.0f;
+      const bool over = wrapped && u_steps >= io.episode_length;
       const float done2 = over ? 1.0f : done_env, trunc = over ? 1.0f - done_env : 0.0f;
       u_prev_done = done2;
       u_frame = new_frame;
-      if (ACTOR && lane == 0) { const size_t at = rr_traj_at(io, num_envs, env, ut); io.t_discount[at] = 1.0f - done2; io.t_trunc[at] = trunc; }
-      if (__builtin_amdgcn_readfirstlane(__float_as_int(done2)) != 0) {
+      if (ACTOR && !EVAL && lane == 0) { const size_t at = rr_traj_at(io, num_envs, env, ut); io.t_discount[at] = 1.0f - done2; io.t_trunc[at] = trunc; }
+      if (EVAL) {
+        // brax EvalWrapper on the step just made, in place: episode_steps += active; sums += metric * active; active *= 1 - done (the
+        // wrapped done).  Lane 0 reads the step's metrics back from where it has just stored them and updates the env's six cells in
+        // memory: nothing of this lives across the solver.  Products and sums rounded one by one -- the operations torch performs.
+        if (io.e_metrics && lane == 0) {
+          float* em = io.e_metrics + (size_t)env * 6;
+          const float active = em[1];
+          em[0] = __fadd_rn(em[0], active);
+          em[2] = __fadd_rn(em[2], __fmul_rn(io.metrics[3 * env], active));
+          em[3] = __fadd_rn(em[3], __fmul_rn(io.metrics[3 * env + 1], active));
+          em[4] = __fadd_rn(em[4], __fmul_rn(io.metrics[3 * env + 2], active));
+          em[5] = __fadd_rn(em[5], __fmul_rn(io.reward[env], active));
+          em[1] = __fmul_rn(active, __fsub_rn(1.0f, done2));
+        }
+        if (io.e_qpos_out) for (int i = lane; i < D.nq; i += RR_LANES) io.e_qpos_out[((size_t)(ut + 1) * num_envs + env) * D.nq + i] = w.s_qpos[i];
+      }
+      if (wrapped && __builtin_amdgcn_readfirstlane(__float_as_int(done2)) != 0) {
         w.sync();
         for (int i = lane; i < D.nq; i += RR_LANES) w.s_qpos[i] = io.first_qpos[(size_t)env * D.nq + i];
         for (int i = lane; i < D.nv; i += RR_LANES) { w.s_qvel[i] = io.first_qvel[(size_t)env * D.nv + i]; w.s_warm[i] = io.first_warm[(size_t)env * D.nv + i]; }
@@ -366,7 +387,7 @@
         for (int i = lane; i < D.obs_dim; i += RR_LANES) ob[i] = io.first_obs[(size_t)env * D.obs_dim + i];
         w.sync();
       }
-      if (ACTOR) {      // the last observation of a segment is also the first of the next one (the learner's trajectories overlap by one row)
+      if (ACTOR && !EVAL) {      // the last observation of a segment is also the first of the next one (the learner's trajectories overlap by one row)
         const RRTraj tr = rr_traj(io, ut);
         if (tr.t + 1 == io.a_seg && ut + 1 < nsteps) {
           float* nx = io.t_obs + rr_traj_obs(io, num_envs, env, tr.u + 1, 0) * D.obs_dim;
@@ -383,7 +404,7 @@
         w.lag_mode = io.pace_mode;
       }
       if (ut == nsteps - 1) {
-        if (lane == 0) { io.done[env] = done2; io.steps_out[env] = u_steps; io.trunc_out[env] = trunc; }
+        if (lane == 0) { io.done[env] = done2; if (wrapped) { io.steps_out[env] = u_steps; io.trunc_out[env] = trunc; } }
         for (int i = lane; i < D.nq; i += RR_LANES) io.qpos[(size_t)env * D.nq + i] = w.s_qpos[i];
         for (int i = lane; i < D.nv; i += RR_LANES) { io.qvel[(size_t)env * D.nv + i] = w.s_qvel[i]; io.warm[(size_t)env * D.nv + i] = w.s_warm[i]; }
         for (int i = lane; i < D.nu; i += RR_LANES) io.act[(size_t)env * D.nu + i] = w.s_act[i];

@@ -168,6 +168,47 @@ class Rodent(PipelineEnv):
         obs = traj["obs"].reshape(T // L_, N, L_ + 1, -1)[-1, :, L_].contiguous()
         return state.replace(pipeline_state=PipelineState(**st), obs=obs, reward=reward, done=done, metrics=m, info=ninfo), actions
 
+    def eval_supported(self) -> bool:
+        """Whether `unroll_eval` serves this env: a batch with an evaluation instance (CG solver, a model with a multi-step instance, no
+        per-env parameters) and no pipeline / contact outputs."""
+        return (self.device.type == "cuda" and not self._pipeline_outputs and not self._contact_outputs and self._batch.eval_supported())
+
+    def unroll_eval(self, state: State, T: int, actor: dict, noise: Optional[torch.Tensor] = None, episode_length: Optional[float] = None,
+                    eval_metrics: Optional[torch.Tensor] = None, actions_out: Optional[torch.Tensor] = None, qpos_out: Optional[torch.Tensor] = None) -> State:
+        """T x [policy(obs) -> action -> step] in ONE launch without a trajectory (`rr_env_unroll_eval`): what an evaluation needs.
+        `episode_length` given: `state` is a state of the wrapped env and `EpisodeWrapper(episode_length)` + `AutoResetWrapper` act between
+        the steps, with brax's EvalWrapper bookkeeping on `eval_metrics` [N, 6] = (episode_steps, active_episodes, sums of pos_reward,
+        reward_quadctrl, reward_alive, reward), updated in place.  `episode_length` None: the unwrapped env, stepping on past `done`.
+        `actor`: `acting.actor_params`; `noise` [T, N, A] standard normal draws, None = the deterministic policy.  Optional records:
+        `actions_out` [T, N, A], `qpos_out` [T + 1, N, nq] (row 0 the incoming qpos; wrapped: taken before a restore).  Returns the state
+        after the last step, as T calls of `step` on the same actions leave it.  A batch without an evaluation instance (`eval_supported`)
+        refuses with the reason (RuntimeError)."""
+        if self._pipeline_outputs or self._contact_outputs:
+            raise ValueError("an evaluation launch returns no pipeline / contact outputs: build the env without them")
+        N, dev, s = self.num_envs, self.device, self.sys
+        ps, info = state.pipeline_state, state.info
+        st_in = dict(qpos=ps.qpos, qvel=ps.qvel, act=ps.act, qacc_warmstart=ps.qacc_warmstart)
+        st = {k: torch.empty_like(v) for k, v in st_in.items()}
+        cur_frame = torch.empty_like(info["cur_frame"])
+        reward, done = torch.empty(N, device=dev), torch.empty(N, device=dev)
+        metrics = torch.empty(N, 3, device=dev)
+        ring = torch.empty(N, 2, s.obs_dim, device=dev)
+        obs_in = state.obs.contiguous()
+        wrap = None
+        ninfo = dict(info)
+        if episode_length is not None:
+            fps = info["first_pipeline_state"]
+            steps, trunc = torch.empty(N, device=dev), torch.empty(N, device=dev)
+            wrap = dict(first=dict(qpos=fps.qpos, qvel=fps.qvel, act=fps.act, qacc_warmstart=fps.qacc_warmstart), first_obs=info["first_obs"],
+                        prev_done=state.done, steps_in=info["steps"], steps_out=steps, truncation_out=trunc, episode_length=episode_length)
+            ninfo.update(steps=steps, truncation=trunc)
+        self._batch.env_unroll_eval(st_in, st, int(T), self._n_frames, self._env_io(cur_frame, obs_in, reward, done, metrics), info["cur_frame"], actor,
+                                    obs_in, ring, noise, actions_out, eval_metrics, qpos_out, wrap)
+        ninfo.update(cur_frame=cur_frame)
+        m = dict(state.metrics)
+        m.update(pos_reward=metrics[:, 0], reward_quadctrl=metrics[:, 1], reward_alive=metrics[:, 2])
+        return state.replace(pipeline_state=PipelineState(**st), obs=ring[:, int(T) & 1].contiguous(), reward=reward, done=done, metrics=m, info=ninfo)
+
     def step(self, state: State, action: torch.Tensor) -> State:
         """Runs one timestep of the environment's dynamics."""
         N, dev, s = self.num_envs, self.device, self.sys

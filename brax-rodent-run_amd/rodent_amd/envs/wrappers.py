@@ -135,6 +135,32 @@ class EvalWrapper(Wrapper):
         return nstate
 
 
+    EVAL_KEYS = ("pos_reward", "reward_quadctrl", "reward_alive", "reward")      # the order of the kernel's sums (rr_env_unroll_eval)
+
+    def unroll_supported(self) -> bool:
+        """`unroll_policy` needs this wrapper directly on the fused Episode + AutoReset wrapper of a HIP env with an evaluation instance."""
+        base = self.env.unwrapped if hasattr(self.env, "unwrapped") else self.env
+        return isinstance(self.env, FusedEpisodeAutoResetWrapper) and hasattr(base, "eval_supported") and base.eval_supported()
+
+    def unroll_policy(self, state, actor, noise, T: int, actions_out=None, qpos_out=None):
+        """T x [policy -> action -> `step`] in one launch (`Rodent.unroll_eval` / C ABI `rr_env_unroll_eval`): the state T calls of `step`
+        on the same actions give, `info["eval_metrics"]` included.  `actor`: `acting.actor_params`; `noise` [T, N, A] or None (the
+        deterministic policy); `actions_out` [T, N, A] / `qpos_out` [T + 1, N, nq] (optional) receive the actions taken / the qpos of every step."""
+        if not self.unroll_supported():
+            raise ValueError("EvalWrapper.unroll_policy: not directly on the fused wrapper of a HIP env with an evaluation instance")
+        em = state.info["eval_metrics"]
+        if set(em["episode_metrics"]) != set(self.EVAL_KEYS):
+            raise ValueError(f"EvalWrapper.unroll_policy: the kernel sums exactly {self.EVAL_KEYS}")
+        packed = torch.stack([em["episode_steps"], em["active_episodes"]] + [em["episode_metrics"][k] for k in self.EVAL_KEYS], dim=1).contiguous()
+        base = self.env.unwrapped
+        nstate = base.unroll_eval(state, T, actor, noise, episode_length=self.env.episode_length, eval_metrics=packed, actions_out=actions_out,
+                                  qpos_out=qpos_out)
+        nstate.metrics["reward"] = nstate.reward
+        nstate.info["eval_metrics"] = dict(episode_metrics={k: packed[:, 2 + self.EVAL_KEYS.index(k)] for k in em["episode_metrics"]},
+                                           active_episodes=packed[:, 1], episode_steps=packed[:, 0])
+        return nstate
+
+
 class FusedEpisodeAutoResetWrapper(Wrapper):
     """EpisodeWrapper + AutoResetWrapper of a HIP env with action_repeat 1: the same values, but the ~15 elementwise
     launches of the composed wrappers (step count, truncation, done, ten `where(done, first, current)` selects) are one

@@ -53,6 +53,10 @@ class RRActorIO(C.Structure):
                                    "traj_discount", "traj_truncation")] + [("min_std", C.c_float), ("nhidden", C.c_int32), ("segment_length", C.c_int32)]
 
 
+class RREvalIO(C.Structure):
+    _fields_ = [("eval_metrics", C.c_void_p), ("obs_ring", C.c_void_p), ("qpos_out", C.c_void_p), ("raw_env", C.c_int32)]
+
+
 class RREnvParams(C.Structure):
     _fields_ = [("dof_f", C.c_void_p), ("act_f", C.c_void_p), ("con_f", C.c_void_p), ("dof_rows", C.c_int32), ("act_rows", C.c_int32),
                 ("con_rows", C.c_int32), ("num_envs", C.c_int32)]
@@ -69,7 +73,7 @@ class RRPpoCfg(C.Structure):
 
 
 EXPORTS = ["rr_model_load", "rr_model_dims", "rr_model_set_solver", "rr_model_set_solver_type", "rr_model_destroy", "rr_model_table", "rr_kernarg_layout", "rr_batch_create",
-           "rr_batch_destroy", "rr_pipeline_init", "rr_pipeline_step", "rr_env_step", "rr_env_reset", "rr_pipeline_step_to", "rr_env_step_to", "rr_batch_contact_overflow", "rr_batch_unroll_supported", "rr_env_unroll", "rr_env_unroll_policy",
+           "rr_batch_destroy", "rr_pipeline_init", "rr_pipeline_step", "rr_env_step", "rr_env_reset", "rr_pipeline_step_to", "rr_env_step_to", "rr_batch_contact_overflow", "rr_batch_unroll_supported", "rr_env_unroll", "rr_env_unroll_policy", "rr_batch_eval_supported", "rr_env_unroll_eval",
            "rr_compute_gae", "rr_mlp_forward", "rr_ppo_loss_workspace_bytes", "rr_ppo_loss", "rr_policy_act_workspace_bytes", "rr_policy_act", "rr_policy_sample", "rr_policy_backward_workspace_bytes", "rr_policy_backward", "rr_mlp_silu_backward_workspace_bytes", "rr_mlp_silu_backward", "rr_mlp_value_backward_workspace_bytes", "rr_mlp_value_backward", "rr_mlp_weight_grad_workspace_bytes", "rr_mlp_weight_grad", "rr_mlp_weight_grad_batch_workspace_bytes", "rr_mlp_weight_grad_batch", "rr_obs_moments_workspace_bytes", "rr_obs_moments", "rr_wrap_episode_autoreset", "rr_debug_layout", "rr_batch_set_schedule", "rr_batch_set_env_params", "rr_batch_env_params_supported", "rr_batch_set_profile", "rr_batch_set_timing", "rr_batch_kernel_time", "rr_last_error"]
 
 _lib = None
@@ -107,6 +111,9 @@ def lib():
                                     C.c_void_p, C.POINTER(RRUnrollIO)]
         L.rr_env_unroll_policy.argtypes = [C.c_void_p, C.POINTER(RRState), C.POINTER(RRState), C.c_int32, C.c_int32, C.POINTER(RREnvIO), C.c_void_p,
                                            C.POINTER(RRUnrollIO), C.POINTER(RRActorIO)]
+        L.rr_batch_eval_supported.argtypes = [C.c_void_p]
+        L.rr_env_unroll_eval.argtypes = [C.c_void_p, C.POINTER(RRState), C.POINTER(RRState), C.c_int32, C.c_int32, C.POINTER(RREnvIO), C.c_void_p,
+                                         C.POINTER(RRUnrollIO), C.POINTER(RRActorIO), C.POINTER(RREvalIO)]
         L.rr_env_reset.argtypes = [C.c_void_p, C.POINTER(RRState), C.POINTER(RREnvIO), C.POINTER(RROutputs)]
         L.rr_debug_layout.argtypes = [C.c_void_p, C.POINTER(C.POINTER(C.c_char_p)), C.POINTER(C.POINTER(C.c_int32)),
                                       C.POINTER(C.POINTER(C.c_int32))]
@@ -349,6 +356,47 @@ class Batch:
                       traj["truncation"].data_ptr(), float(actor["min_std"]), nh, int(L_))
         _check(lib().rr_env_unroll_policy(self.h, C.byref(self._state(st_in)), C.byref(self._state(st_out)), int(T), int(n_frames),
                                           C.byref(self._env(env)), _ptr(cur_frame_in, torch.int32, self.N), C.byref(w), C.byref(a)))
+
+    def eval_supported(self) -> bool:
+        """Whether this batch evaluates in one launch (C ABI `rr_batch_eval_supported`): CG solver, a model with a multi-step instance,
+        no per-env parameters."""
+        return _check(lib().rr_batch_eval_supported(self.h)) == 1
+
+    def env_unroll_eval(self, st_in, st_out, T: int, n_frames: int, env, cur_frame_in, actor: dict, obs_in, obs_ring, noise=None, actions_out=None,
+                        eval_metrics=None, qpos_out=None, wrap: Optional[dict] = None):
+        """T x [policy -> action -> env step] without a trajectory, one launch (C ABI `rr_env_unroll_eval`).  `wrap` = dict(first, first_obs,
+        prev_done, steps_in, steps_out, truncation_out, episode_length): the Episode + AutoReset wrappers between the steps and brax's
+        EvalWrapper on `eval_metrics` [N, 6] (in place); None: the unwrapped env.  noise [T, N, A] or None (deterministic policy);
+        actions_out [T, N, A] and qpos_out [T + 1, N, nq] optional; obs_ring [N, 2, K] (final observation: obs_ring[:, T & 1])."""
+        d, N = self.dims, self.N
+        A_, K = d.nu, d.obs_dim
+        nh = len(actor["hidden_wt"]) + 1
+        HW = 64 if A_ <= 32 else 128
+        if actor["w0"].shape != (32, K) or actor["head_wt"].shape != (32, HW) or actor["head_b"].numel() != HW or actor["b0"].numel() != 32:
+            raise ValueError("rr_env_unroll_eval: inconsistent actor shapes")
+        for t in (actor["w0"], actor["b0"], actor["head_wt"], actor["head_b"], *actor["hidden_wt"], *actor["hidden_b"]):
+            _ptr(t)
+        for w_, b_ in zip(actor["hidden_wt"], actor["hidden_b"]):
+            if w_.numel() != 1024 or b_.numel() != 32:
+                raise ValueError("rr_env_unroll_eval: hidden layers are 32 x 32")
+        p = lambda t: t.data_ptr() if t is not None else None
+        a = RRActorIO(_ptr(obs_in, numel=N * K), _ptr(actor.get("mean"), numel=K) if actor.get("mean") is not None else None,
+                      _ptr(actor.get("std"), numel=K) if actor.get("std") is not None else None, actor["w0"].data_ptr(), actor["b0"].data_ptr(),
+                      (C.c_void_p * 4)(*([t.data_ptr() for t in actor["hidden_wt"]] + [None] * (4 - nh + 1))),
+                      (C.c_void_p * 4)(*([t.data_ptr() for t in actor["hidden_b"]] + [None] * (4 - nh + 1))),
+                      actor["head_wt"].data_ptr(), actor["head_b"].data_ptr(), _ptr(noise, numel=T * N * A_) if noise is not None else None,
+                      _ptr(actions_out, numel=T * N * A_) if actions_out is not None else None, None, None, None, None, None, None,
+                      float(actor["min_std"]), nh, 0)
+        e = RREvalIO(_ptr(eval_metrics, numel=N * 6) if eval_metrics is not None else None, _ptr(obs_ring, numel=N * 2 * K),
+                     _ptr(qpos_out, numel=(T + 1) * N * d.nq) if qpos_out is not None else None, 0 if wrap is not None else 1)
+        w = None
+        if wrap is not None:
+            for k in ("first_obs", "prev_done", "steps_in", "steps_out", "truncation_out"):
+                _ptr(wrap[k], numel=N * K if k == "first_obs" else N)
+            w = RRUnrollIO(self._state(wrap["first"]), wrap["first_obs"].data_ptr(), wrap["prev_done"].data_ptr(), wrap["steps_in"].data_ptr(),
+                           wrap["steps_out"].data_ptr(), wrap["truncation_out"].data_ptr(), float(wrap["episode_length"]))
+        _check(lib().rr_env_unroll_eval(self.h, C.byref(self._state(st_in)), C.byref(self._state(st_out)), int(T), int(n_frames), C.byref(self._env(env)),
+                                        _ptr(cur_frame_in, torch.int32, N), C.byref(w) if w is not None else None, C.byref(a), C.byref(e)))
 
     def env_reset(self, st, env, out=None):
         o = self._outputs(out)

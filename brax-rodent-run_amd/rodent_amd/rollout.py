@@ -6,6 +6,7 @@ are returned / saved as .npz; `pair_poses` runs the pair model's forward pass on
 """
 from __future__ import annotations
 
+import os
 from typing import Optional
 
 import numpy as np
@@ -15,10 +16,13 @@ from . import jax_random
 
 
 @torch.no_grad()
-def eval_rollout(env, make_policy, params, steps: int = 500, seed: int = 0, record: Optional[list] = None) -> np.ndarray:
+def eval_rollout(env, make_policy, params, steps: int = 500, seed: int = 0, record: Optional[list] = None, actor: Optional[dict] = None) -> np.ndarray:
     """`env`: a `Rodent` with num_envs = 1 (the reference's jit_reset / jit_step pair).  Key handling as the launcher:
     `key = PRNGKey(seed); _, key = split(key); reset_rng, act_rng = split(key)`; the policy is deterministic.
-    Returns the rollout's qpos [steps + 1, nq] (float32).  `record` (tests): a list that receives (state, action, next_state) per step."""
+    Returns the rollout's qpos [steps + 1, nq] (float32).  `record` (tests): a list that receives (state, action, next_state) per step.
+    `actor`: the same policy as `acting.actor_params` lays it out; with it (and no `record`) the whole rollout is one launch of the
+    unwrapped env (`Rodent.unroll_eval`) where the env has an evaluation instance and RR_FUSED_EVAL=1.  The per-step loop is the default:
+    with one env the launch measured 7 % slower than the loop."""
     if env.num_envs != 1:
         raise ValueError("the evaluation rollout steps a single env (use env.with_num_envs(1))")
     key = jax_random.PRNGKey(seed)
@@ -26,6 +30,11 @@ def eval_rollout(env, make_policy, params, steps: int = 500, seed: int = 0, reco
     reset_rng, act_rng = jax_random.split(key)
     policy = make_policy(params, deterministic=True)
     state = env.reset(reset_rng[None])
+    if (record is None and actor is not None and os.environ.get("RR_FUSED_EVAL", "0") == "1" and hasattr(env, "eval_supported")
+            and env.eval_supported()):
+        qpos_out = torch.empty(steps + 1, 1, state.pipeline_state.qpos.shape[1], device=state.obs.device)
+        env.unroll_eval(state, steps, actor, None, qpos_out=qpos_out)
+        return qpos_out[:, 0].cpu().numpy()
     qposes = [state.pipeline_state.qpos[0].clone()]
     for _ in range(steps):
         _, act_rng = jax_random.split(act_rng)

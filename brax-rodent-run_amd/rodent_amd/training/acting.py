@@ -3,8 +3,9 @@
 the upstream Transition keeps both, 13.6 GB per training step at 2048 envs)."""
 from __future__ import annotations
 
+import os
 import time
-from typing import Callable, Dict
+from typing import Callable, Dict, Optional
 
 import torch
 
@@ -183,13 +184,27 @@ class SubBatchRollout:
 class Evaluator:
     """`brax.training.acting.Evaluator`: episode_length steps of a freshly reset eval env, episode metric sums."""
 
-    def __init__(self, eval_env, eval_policy_fn: Callable, num_eval_envs: int, episode_length: int, action_repeat: int, key):
+    def __init__(self, eval_env, eval_policy_fn: Callable, num_eval_envs: int, episode_length: int, action_repeat: int, key,
+                 actor_fn: Optional[Callable] = None, deterministic: bool = False):
+        """`actor_fn(policy_params)` -> the policy in the layout of the in-kernel actor (`actor_params`), `deterministic`: whether
+        `eval_policy_fn` builds the deterministic policy.  With them and RR_FUSED_EVAL=1 the evaluation is ONE launch
+        (`EvalWrapper.unroll_policy`) where the env has an evaluation instance (the fused wrapper of a HIP env, action_repeat 1);
+        everything else runs the per-step loop.  The loop is the default: at 128 envs x 150 steps both paths wait for the same chain of
+        dependent env steps and the one launch measured no faster (tools/bench_eval.py)."""
         self._key = key
+        self._actor_fn = actor_fn
+        self._deterministic = deterministic
+        self._action_repeat = action_repeat
         self._eval_walltime = 0.0
         self._env = wrappers.EvalWrapper(eval_env)
         self._policy_fn = eval_policy_fn
         self._steps_per_unroll = episode_length * num_eval_envs
         self._unroll_length = episode_length // action_repeat
+
+    def one_launch(self) -> bool:
+        """Whether `run_evaluation` takes the one-launch path now (per-env parameters set on the env later turn it off)."""
+        return (self._actor_fn is not None and self._action_repeat == 1 and os.environ.get("RR_FUSED_EVAL", "0") == "1"
+                and self._env.unroll_supported())
 
     @torch.no_grad()
     def run_evaluation(self, policy_params, training_metrics: Dict, aggregate_episodes: bool = True) -> Dict:
@@ -198,9 +213,14 @@ class Evaluator:
         t = time.time()
         policy = self._policy_fn(policy_params)
         state = self._env.reset(jax_random.split(unroll_key, self._env.num_envs))
-        for _ in range(self._unroll_length):
-            action, _ = policy(state.obs, None)
-            state = self._env.step(state, action)
+        if self.one_launch():
+            T, N = self._unroll_length, self._env.num_envs
+            noise = None if self._deterministic else torch.randn(T, N, self._env.action_size, device=state.obs.device)
+            state = self._env.unroll_policy(state, self._actor_fn(policy_params), noise, T)
+        else:
+            for _ in range(self._unroll_length):
+                action, _ = policy(state.obs, None)
+                state = self._env.step(state, action)
         if state.obs.is_cuda:
             torch.cuda.synchronize(state.obs.device)
         em = state.info["eval_metrics"]

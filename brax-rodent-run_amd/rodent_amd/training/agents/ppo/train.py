@@ -175,8 +175,13 @@ def train(
     evaluator = None
     if eval_env is not None:
         weval = wrappers.wrap(eval_env, episode_length=episode_length, action_repeat=action_repeat, randomization_fn=eval_rand_fn)
+        # evaluation as one launch (rr_env_unroll_eval, RR_FUSED_EVAL=1) under the conditions of the one-launch rollout; the Evaluator
+        # itself checks the env.  Off by default: it measured no faster than the per-step loop
+        actor_fn = None
+        if action_repeat == 1 and acting.fused_unroll_supported(weval, policy_net, dist):
+            actor_fn = lambda p: acting.actor_params(p[1], p[0], dist.min_std)
         evaluator = acting.Evaluator(weval, lambda p: make_policy(p, deterministic=deterministic_eval), num_eval_envs,
-                                     episode_length, action_repeat, eval_key)
+                                     episode_length, action_repeat, eval_key, actor_fn=actor_fn, deterministic=deterministic_eval)
 
     U = batch_size * num_minibatches // num_envs
     N, T = local_num_envs, unroll_length

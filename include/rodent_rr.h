@@ -191,6 +191,32 @@ typedef struct rr_actor_io {
 int rr_env_unroll_policy(rr_batch* b, const rr_state* in, const rr_state* out_state, int32_t num_steps, int32_t n_frames, const rr_env_io* env,
                          const int32_t* cur_frame_in, const rr_unroll_io* wrap, const rr_actor_io* actor);
 
+/* Evaluation in ONE launch: rr_env_unroll_policy without the trajectory, in the two forms a training run evaluates in.
+ * WRAPPED (raw_env = 0) is brax.training.acting.Evaluator's unroll -- num_steps x [policy(obs) -> action -> Rodent.step -> EpisodeWrapper
+ * + AutoResetWrapper -> EvalWrapper]: per env step, after the wrappers and before the restore of a finished episode,
+ *   episode_steps += active;  sum_k += metric_k * active for k = pos_reward, reward_quadctrl, reward_alive, reward;  active *= 1 - done
+ * on eval_metrics [N][6] = (episode_steps, active_episodes, the four sums), read and written in place, so launches chain (nullable:
+ * no bookkeeping).  RAW (raw_env = 1) is the launcher's evaluation rollout [REF brax_rodent_run_ppo.py:141-151], a loop over the
+ * unwrapped env.step: no step count, no truncation, no restore -- the env keeps stepping past `done`; `wrap` may then be NULL.
+ * `actor` as for rr_env_unroll_policy, except: noise may be NULL (the deterministic policy, action = tanh(loc); equal bit for bit to an
+ * all-zero noise array), actions_out [num_steps][N][A] may be NULL (not recorded) and the traj_* members and segment_length are ignored.
+ * obs_ring [N][2][obs]: the only observation storage of the launch -- step t reads row t & 1 and writes row (t + 1) & 1, so the final
+ * observation of env e is obs_ring[e][num_steps & 1] (env->obs is not written).  qpos_out (nullable) [num_steps + 1][N][nq]: row 0 the
+ * incoming qpos, row t + 1 the qpos after step t (wrapped form: before a restore).  Everything else (final state, reward / done /
+ * metrics / cur_frame of the last step, steps_out / truncation_out in the wrapped form) as rr_env_unroll.
+ * Instances: the models rr_env_unroll_policy serves, CG solver.  RR_EUNSUPPORTED (rr_last_error says why) for the Newton solver, two-tree
+ * models served by the two-wave pair instance, other slot counts, batches that carry per-env parameters (rr_batch_set_env_params),
+ * observations wider than 1280, more than 64 actions and diagnostic batches; those evaluate step by step.  rr_batch_eval_supported: 1 / 0. */
+typedef struct rr_eval_io {
+  float* eval_metrics;
+  float* obs_ring;
+  float* qpos_out;
+  int32_t raw_env;
+} rr_eval_io;
+int rr_batch_eval_supported(const rr_batch* b);
+int rr_env_unroll_eval(rr_batch* b, const rr_state* in, const rr_state* out_state, int32_t num_steps, int32_t n_frames, const rr_env_io* env,
+                       const int32_t* cur_frame_in, const rr_unroll_io* wrap, const rr_actor_io* actor, const rr_eval_io* eval);
+
 /* obs of Rodent.reset: after rr_pipeline_init, obs = _get_obs(data, 0, cur_frame) [REF :89];
  * implemented as rr_pipeline_init + obs epilogue in one launch. Only env->obs/track_pos/cur_frame are used. */
 int rr_env_reset(rr_batch* b, const rr_state* st, const rr_env_io* env, const rr_outputs* out);
