@@ -795,7 +795,8 @@ extern "C" int rr_policy_backward(const float* grad_logits, const float* head_we
                                   size_t workspace_bytes, void* stream) {
   if (!grad_logits || !head_weight || !hidden_weights || !pre_act || !delta || !bias_grads || !workspace || M <= 0 || pre_act_rows < M)
     return fail(RR_EINVAL, "rr_policy_backward: bad argument");
-  if (nhidden < 1 || nhidden > RR_POL_MAXL || P < 1 || P > 64) return fail(RR_EUNSUPPORTED, "rr_policy_backward: unsupported network shape");
+  if (nhidden < 1 || nhidden > RR_POL_MAXL) return fail(RR_EUNSUPPORTED, "rr_policy_backward: 1 .. 8 hidden layers");
+  if (P < 1 || P > 128) return fail(RR_EUNSUPPORTED, "rr_policy_backward: a head of " + std::to_string(P) + " logits (1 .. 128 are supported)");
   if (workspace_bytes < rr_policy_backward_workspace_bytes(M, nhidden)) return fail(RR_EINVAL, "rr_policy_backward: workspace too small");
   RRPolBwdArgs A;
   memset(&A, 0, sizeof(A));
@@ -806,7 +807,7 @@ extern "C" int rr_policy_backward(const float* grad_logits, const float* head_we
     A.bgrad[j] = bias_grads[j];
     A.W[j] = j > 0 ? hidden_weights[j] : nullptr;
   }
-  const size_t lds = ((size_t)P * 32 + (size_t)(nhidden - 1) * 1024) * sizeof(float);
+  const size_t lds = ((size_t)P * 32 + (size_t)(nhidden - 1) * 1024) * sizeof(float);      // head [P][32] (16 KB at P = 128) + hidden layers
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(rr_policy_backward_kernel, dim3(A.nblk), dim3(256), lds, st, A);
   hipLaunchKernelGGL(rr_policy_colsum_kernel, dim3(nhidden), dim3(1024), 0, st, A);
@@ -840,17 +841,18 @@ extern "C" int rr_mlp_silu_backward(const float* g, const float* z, int32_t M, i
 }
 
 // ------------------------------------------------------------------------------------------ PPO: fused MLP forward (MFMA f32)
-static int mlp_net(const rr_mlp_net* n, int K, int hidden, bool is_value, RRMlpNet* out, const char* who) {
+static int mlp_net(const rr_mlp_net* n, int K, int hidden, bool is_value, RRMlpNet* out, const char* who, const char* fn = "rr_mlp_forward") {
   memset(out, 0, sizeof(*out));
   if (!n) return RR_OK;
-  if (!n->weights || !n->biases || !n->sizes || n->nlayers < 2 || n->nlayers > RR_MLP_MAXL) return fail(RR_EINVAL, std::string("rr_mlp_forward: bad ") + who + " network description");
-  if (n->sizes[0] != K) return fail(RR_EINVAL, std::string("rr_mlp_forward: ") + who + " input width differs from the observation width");
+  if (!n->weights || !n->biases || !n->sizes || n->nlayers < 2 || n->nlayers > RR_MLP_MAXL) return fail(RR_EINVAL, std::string(fn) + ": bad " + who + " network description");
+  if (n->sizes[0] != K) return fail(RR_EINVAL, std::string(fn) + ": " + who + " input width differs from the observation width");
   for (int l = 1; l < n->nlayers; ++l)
-    if (n->sizes[l] != hidden) return fail(RR_EUNSUPPORTED, std::string("rr_mlp_forward: ") + who + " hidden width must be " + std::to_string(hidden));
+    if (n->sizes[l] != hidden) return fail(RR_EUNSUPPORTED, std::string(fn) + ": " + who + " hidden width must be " + std::to_string(hidden));
   const int od = n->sizes[n->nlayers];
-  if (is_value ? od != 1 : (od < 1 || od > 64)) return fail(RR_EUNSUPPORTED, std::string("rr_mlp_forward: unsupported ") + who + " output width");
+  if (is_value ? od != 1 : (od < 1 || od > 128))
+    return fail(RR_EUNSUPPORTED, std::string(fn) + ": unsupported " + who + " output width " + std::to_string(od) + (is_value ? " (the value head is 1 wide)" : " (1 .. 128 logits are supported)"));
   for (int l = 0; l < n->nlayers; ++l) {
-    if (!n->weights[l] || !n->biases[l]) return fail(RR_EINVAL, std::string("rr_mlp_forward: null ") + who + " parameter");
+    if (!n->weights[l] || !n->biases[l]) return fail(RR_EINVAL, std::string(fn) + ": null " + who + " parameter");
     out->W[l] = n->weights[l]; out->b[l] = n->biases[l];
   }
   out->nlayers = n->nlayers; out->out_dim = od;
@@ -918,10 +920,11 @@ extern "C" int rr_policy_act(const float* obs, const int64_t* obs_rows, int32_t 
   if (!obs || !policy || !action || !workspace || M <= 0 || K <= 0) return fail(RR_EINVAL, "rr_policy_act: bad argument");
   if ((mean == nullptr) != (std_ == nullptr)) return fail(RR_EINVAL, "rr_policy_act: mean and std must be given together");
   RRMlpNet net;
-  int rc = mlp_net(policy, K, RR_MLP_PH, false, &net, "policy");
+  int rc = mlp_net(policy, K, RR_MLP_PH, false, &net, "policy", "rr_policy_act");
   if (rc) return rc;
   const int nh = net.nlayers - 1, P = net.out_dim, A_ = P / 2;
-  if ((P & 1) || A_ > 32 || nh > RR_POL_MAXL - 1) return fail(RR_EUNSUPPORTED, "rr_policy_act: the head must be 2 x action_size <= 64 wide");
+  if ((P & 1) || A_ > 64 || nh > RR_POL_MAXL - 1)
+    return fail(RR_EUNSUPPORTED, "rr_policy_act: a head of " + std::to_string(P) + " logits (it must be 2 x action_size <= 128 wide, at most 7 hidden layers)");
   if (workspace_bytes < rr_policy_act_workspace_bytes(M)) return fail(RR_EINVAL, "rr_policy_act: workspace too small");
   hipStream_t st = (hipStream_t)stream;
   RRPolL1Args L;
@@ -937,8 +940,11 @@ extern "C" int rr_policy_act(const float* obs, const int64_t* obs_rows, int32_t 
   T.action = action; T.raw = raw_action; T.logp = log_prob; T.logits = logits;
   for (int l = 1; l <= nh; ++l) T.W[l] = net.W[l];
   for (int l = 0; l <= nh; ++l) T.b[l] = net.b[l];
-  const size_t lds = ((size_t)(nh - 1) * 1024 + 2048 + (size_t)nh * 32 + 64) * sizeof(float);
-  hipLaunchKernelGGL(rr_policy_tail_kernel, dim3(std::max(1, std::min(256, (M + 7) / 8))), dim3(256), lds, st, T);
+  const int HW = P <= 64 ? 64 : 128;           // head columns in LDS (rr_policy_tail_kernel)
+  const size_t lds = ((size_t)(nh - 1) * 1024 + (size_t)32 * HW + (size_t)nh * 32 + HW) * sizeof(float);
+  const dim3 grid(std::max(1, std::min(256, (M + 7) / 8)));
+  if (HW == 64) hipLaunchKernelGGL(rr_policy_tail_kernel<64>, grid, dim3(256), lds, st, T);
+  else hipLaunchKernelGGL(rr_policy_tail_kernel<128>, grid, dim3(256), lds, st, T);
   HIPCHK(hipGetLastError());
   return RR_OK;
 }

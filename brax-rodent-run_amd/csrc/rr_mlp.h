@@ -31,7 +31,7 @@ struct RRMlpNet {
   const float* W[RR_MLP_MAXL];   // [out][in] row-major (torch.nn.Linear.weight)
   const float* b[RR_MLP_MAXL];   // [out]
   int nlayers;                   // hidden layers + 1
-  int out_dim;                   // width of the last layer (policy: 2*action_size <= 64; value: 1)
+  int out_dim;                   // width of the last layer (policy: 2*action_size <= 128; value: 1)
 };
 struct RRMlpArgs {
   const float* obs; int M, K;
@@ -72,8 +72,8 @@ constexpr int RR_SP = RR_MLP_PH + 2;        // policy activation stride (34)
 // resident round; at two per CU the second round was 37 % full).  Two regions, reused by phase:
 //   A [32][258]  layer 1: observation chunk [32][18] + weight chunk [288][18] (value rows 0..255, policy 256..287);
 //                afterwards the value activations (written by layer 1's epilogue, when every wave is done with the stage)
-//   B [256][18]  policy layers 2..head (run right after layer 1): their whole weight matrix [2 x 64][18] at the bottom, the policy
-//                activations [32][34] above it; then, the policy being finished, the weight chunks of the value hidden layers
+//   B [256][18]  policy layers 2..head (run right after layer 1): their weight matrix [2 x 64][18] at the bottom (a head of more than 64
+//                logits: 64 rows at a time), the policy activations [32][34] above it; then, the policy being finished, the weight chunks of the value hidden layers
 constexpr int RR_MLP_LDS_A = RR_MLP_BM * RR_SV, RR_MLP_LDS_B = RR_MLP_VH * RR_SX;
 constexpr int RR_MLP_ACTP_AT = 3072;        // actP inside B (above the 2304 floats of the policy weights)
 constexpr int RR_MLP_LDS_FLOATS = RR_MLP_LDS_A + RR_MLP_LDS_B;
@@ -326,39 +326,46 @@ __global__ __launch_bounds__(256, RR_MLP_FWD_WGS) void rr_mlp_forward_kernel(con
   for (int l = 1; has_pol && l < A.pol.nlayers; ++l) {
     const bool head = l == A.pol.nlayers - 1;
     const int nout = head ? A.pol.out_dim : RR_MLP_PH;
-    __syncthreads();
-    // the whole weight matrix [nout <= 64][32] as two k-chunks side by side: chunk c of row n at sW[(64 c + n) * 18 ..]
-    for (int e = threadIdx.x; e < 64 * RR_MLP_PH; e += 256) {
-      const int n = e / RR_MLP_PH, k = e % RR_MLP_PH;
-      sB[(64 * (k / RR_MLP_KC) + n) * RR_SX + (k % RR_MLP_KC)] = n < nout ? A.pol.W[l][n * RR_MLP_PH + k] : 0.0f;
-    }
-    __syncthreads();
-    if (!head) {
-      rr_f16 d0 = {0}, d1 = {0};
-      rr_f4 ap = {0, 0, 0, 0};
-      rr_mlp_chunk<false, true>(actP, RR_SP, 0, sB, 0, d0, d1, ap, lane, wv);
-      rr_mlp_chunk<false, true>(actP, RR_SP, RR_MLP_KC, sB, 64, d0, d1, ap, lane, wv);
+    // a head of 65 .. 128 logits runs as two passes over column halves of 64, each staged into the same 2304 floats (a full [128][32]
+    // head does not fit below actP); the columns are independent, so a pass computes its columns exactly as a 64-logit head would
+    const int npass = head ? (nout + 63) >> 6 : 1;
+#pragma unroll 1
+    for (int half = 0; half < npass; ++half) {
+      const int n0 = 64 * half;
       __syncthreads();
-      rr_mlp_store_pol(actP, ap, A.pol.b[l], lane, wv, A.pol_act ? A.pol_act + (size_t)l * M * RR_MLP_PH : nullptr, row0, M);
-    } else {
-      // [32 x 64] output = 2 x 4 tiles of 16x16: wave wv takes n-tile wv for both m-tiles
-#pragma unroll
-      for (int mt = 0; mt < 2; ++mt) {
+      // rows n0 .. n0+63 of the weight matrix [nout][32] as two k-chunks side by side: chunk c of row n0 + n at sW[(64 c + n) * 18 ..]
+      for (int e = threadIdx.x; e < 64 * RR_MLP_PH; e += 256) {
+        const int n = e / RR_MLP_PH, k = e % RR_MLP_PH;
+        sB[(64 * (k / RR_MLP_KC) + n) * RR_SX + (k % RR_MLP_KC)] = n0 + n < nout ? A.pol.W[l][(n0 + n) * RR_MLP_PH + k] : 0.0f;
+      }
+      __syncthreads();
+      if (!head) {
+        rr_f16 d0 = {0}, d1 = {0};
         rr_f4 ap = {0, 0, 0, 0};
+        rr_mlp_chunk<false, true>(actP, RR_SP, 0, sB, 0, d0, d1, ap, lane, wv);
+        rr_mlp_chunk<false, true>(actP, RR_SP, RR_MLP_KC, sB, 64, d0, d1, ap, lane, wv);
+        __syncthreads();
+        rr_mlp_store_pol(actP, ap, A.pol.b[l], lane, wv, A.pol_act ? A.pol_act + (size_t)l * M * RR_MLP_PH : nullptr, row0, M);
+      } else {
+        // [32 x 64] output = 2 x 4 tiles of 16x16: wave wv takes n-tile wv for both m-tiles
 #pragma unroll
-        for (int c = 0; c < 2; ++c) {
-          const float* xr = actP + (16 * mt + (lane & 15)) * RR_SP + c * RR_MLP_KC + (lane >> 4);
-          const float* w0 = sB + (64 * c + 16 * wv + (lane & 15)) * RR_SX + (lane >> 4);
+        for (int mt = 0; mt < 2; ++mt) {
+          rr_f4 ap = {0, 0, 0, 0};
 #pragma unroll
-          for (int kk = 0; kk < RR_MLP_KC; kk += 4) ap = __builtin_amdgcn_mfma_f32_16x16x4f32(xr[kk], w0[kk], ap, 0, 0, 0);
-        }
-        const int n = 16 * wv + (lane & 15);
-        if (n < nout) {
-          const float bn = A.pol.b[l][n];
+          for (int c = 0; c < 2; ++c) {
+            const float* xr = actP + (16 * mt + (lane & 15)) * RR_SP + c * RR_MLP_KC + (lane >> 4);
+            const float* w0 = sB + (64 * c + 16 * wv + (lane & 15)) * RR_SX + (lane >> 4);
 #pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int m = 16 * mt + 4 * (lane >> 4) + r;
-            if (row0 + m < M) A.pol_out[(size_t)(row0 + m) * nout + n] = ap[r] + bn;
+            for (int kk = 0; kk < RR_MLP_KC; kk += 4) ap = __builtin_amdgcn_mfma_f32_16x16x4f32(xr[kk], w0[kk], ap, 0, 0, 0);
+          }
+          const int n = n0 + 16 * wv + (lane & 15);
+          if (n < nout) {
+            const float bn = A.pol.b[l][n];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const int m = 16 * mt + 4 * (lane >> 4) + r;
+              if (row0 + m < M) A.pol_out[(size_t)(row0 + m) * nout + n] = ap[r] + bn;
+            }
           }
         }
       }

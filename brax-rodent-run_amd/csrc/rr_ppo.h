@@ -259,7 +259,7 @@ __global__ __launch_bounds__(256) void rr_policy_sample_kernel(const float* __re
 // delta_j (= db_j; fixed-order reduction by rr_policy_colsum_kernel).
 #define RR_POL_MAXL 8
 struct RRPolBwdArgs {
-  const float* g;                 // [M][P]  d loss / d logits
+  const float* g;                 // [M][P]  d loss / d logits, P <= 128
   const float* w_head;            // [P][32]
   const float* W[RR_POL_MAXL];    // W[j], j = 1 .. nh-1: [32 out][32 in] (torch layout)
   float* z;                       // [nh][zrows][32]  pre-activations in, silu(z) out (rows 0 .. M-1 of each layer)
@@ -281,9 +281,16 @@ __global__ __launch_bounds__(256) void rr_policy_backward_kernel(const RRPolBwdA
   for (int j = 0; j < RR_POL_MAXL; ++j) cs[j] = 0.0f;
   for (int row = blockIdx.x * 8 + rg; row < A.M; row += gridDim.x * 8) {
     const float* gr = A.g + (size_t)row * A.P;
+    // the row's output gradient in four registers (logits lane, lane + 32, lane + 64, lane + 96: P <= 128), summed in the order o = 0 .. P-1
     const float g0 = lane < A.P ? gr[lane] : 0.0f, g1 = lane + 32 < A.P ? gr[lane + 32] : 0.0f;
+    const float g2 = lane + 64 < A.P ? gr[lane + 64] : 0.0f, g3 = lane + 96 < A.P ? gr[lane + 96] : 0.0f;
     float acc = 0.0f;
-    for (int o = 0; o < A.P; ++o) acc = fmaf(o < 32 ? __shfl(g0, o, 32) : __shfl(g1, o - 32, 32), sw[o * 32 + lane], acc);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const float gq = q == 0 ? g0 : (q == 1 ? g1 : (q == 2 ? g2 : g3));
+      const int nq = min(32, A.P - 32 * q);
+      for (int o = 0; o < nq; ++o) acc = fmaf(__shfl(gq, o, 32), sw[(32 * q + o) * 32 + lane], acc);
+    }
 #pragma unroll
     for (int jj = 0; jj < RR_POL_MAXL; ++jj) {
       const int j = A.nh - 1 - jj;             // nh-1 .. 0
@@ -338,22 +345,25 @@ __global__ __launch_bounds__(1024) void rr_policy_colsum_kernel(const RRPolBwdAr
 //   noise given: raw = loc + (softplus(s) + min_std) eps, action = tanh(raw), log_prob as rr_policy_sample_kernel; noise NULL: tanh(loc).
 struct RRPolTailArgs {
   const float* part; int nslice;
-  const float* W[RR_POL_MAXL];    // W[l], l = 1 .. nh-1: [32][32];  W[nh]: head [P][32]
+  const float* W[RR_POL_MAXL];    // W[l], l = 1 .. nh-1: [32][32];  W[nh]: head [P][32], P = 2 A <= 128
   const float* b[RR_POL_MAXL + 1];// b[0 .. nh-1]: [32]; b[nh]: [P]
   int M, P, A, nh;
   const float* noise; float min_std;
   float* action; float* raw; float* logp; float* logits;     // raw / logp / logits nullable
 };
+// W: head columns in LDS, 64 for P <= 64 and 128 above (the rule of acting.actor_params).  A template constant, so that the instance for
+// up to 32 actions is the kernel it was before the wide head existed, instruction for instruction.
+template <int W>
 __global__ __launch_bounds__(256) void rr_policy_tail_kernel(const RRPolTailArgs T) {
-  extern __shared__ float sw[];                      // (nh - 1) x [32 k][32 n], then head [32 k][64 n], then biases nh x 32 + 64
+  extern __shared__ float sw[];                      // (nh - 1) x [32 k][32 n], then head [32 k][W n], then biases nh x 32 + W
   const int lane = threadIdx.x & 31, rg = threadIdx.x >> 5;
   float* swh = sw + (T.nh - 1) * 1024;
-  float* sb = swh + 2048;
+  float* sb = swh + 32 * W;
   for (int l = 1; l < T.nh; ++l)
     for (int e = threadIdx.x; e < 1024; e += 256) sw[(l - 1) * 1024 + (e & 31) * 32 + (e >> 5)] = T.W[l][e];      // [n][k] -> [k][n]
-  for (int e = threadIdx.x; e < 2048; e += 256) { const int n = e >> 5, k = e & 31; swh[k * 64 + n] = n < T.P ? T.W[T.nh][n * 32 + k] : 0.0f; }
+  for (int e = threadIdx.x; e < 32 * W; e += 256) { const int n = e >> 5, k = e & 31; swh[k * W + n] = n < T.P ? T.W[T.nh][n * 32 + k] : 0.0f; }
   for (int e = threadIdx.x; e < T.nh * 32; e += 256) sb[e] = T.b[e >> 5][e & 31];
-  for (int e = threadIdx.x; e < 64; e += 256) sb[T.nh * 32 + e] = e < T.P ? T.b[T.nh][e] : 0.0f;
+  for (int e = threadIdx.x; e < W; e += 256) sb[T.nh * 32 + e] = e < T.P ? T.b[T.nh][e] : 0.0f;
   __syncthreads();
   const float HALF_LOG_2PI = 0.91893853320467274178f, LOG2 = 0.69314718055994530942f;
   for (int row = blockIdx.x * 8 + rg; row < T.M; row += gridDim.x * 8) {
@@ -367,34 +377,80 @@ __global__ __launch_bounds__(256) void rr_policy_tail_kernel(const RRPolTailArgs
       for (int k = 0; k < 32; ++k) acc = fmaf(__shfl(h, k, 32), w[k * 32 + lane], acc);
       h = acc / (1.0f + expf(-acc));
     }
-    float o0 = sb[T.nh * 32 + lane], o1 = sb[T.nh * 32 + 32 + lane];
+    if constexpr (W == 64) {
+      float o0 = sb[T.nh * 32 + lane], o1 = sb[T.nh * 32 + 32 + lane];
 #pragma unroll
-    for (int k = 0; k < 32; ++k) { const float hk = __shfl(h, k, 32); o0 = fmaf(hk, swh[k * 64 + lane], o0); o1 = fmaf(hk, swh[k * 64 + 32 + lane], o1); }
-    if (T.logits) {
-      if (lane < T.P) T.logits[(size_t)row * T.P + lane] = o0;
-      if (lane + 32 < T.P) T.logits[(size_t)row * T.P + 32 + lane] = o1;
-    }
-    // lane a needs logits[a] (its own o0) and logits[A + a]: o0 of lane A + a, or o1 of lane A + a - 32
-    const float s_lo = __shfl(o0, (T.A + lane) & 31, 32), s_hi = __shfl(o1, (T.A + lane - 32) & 31, 32);
-    const float sraw = T.A + lane < 32 ? s_lo : s_hi;
-    float lp = 0.0f;
-    if (lane < T.A) {
-      const float loc = o0;
-      if (T.noise) {
-        const float scale = rr_softplus(sraw) + T.min_std;
-        const float eps = T.noise[(size_t)row * T.A + lane], raw = loc + scale * eps;
-        const float zz = (raw - loc) / scale;
-        lp = -0.5f * zz * zz - logf(scale) - HALF_LOG_2PI - 2.0f * (LOG2 - raw - rr_softplus(-2.0f * raw));
-        if (T.raw) T.raw[(size_t)row * T.A + lane] = raw;
-        T.action[(size_t)row * T.A + lane] = tanhf(raw);
-      } else {
-        T.action[(size_t)row * T.A + lane] = tanhf(loc);
+      for (int k = 0; k < 32; ++k) { const float hk = __shfl(h, k, 32); o0 = fmaf(hk, swh[k * 64 + lane], o0); o1 = fmaf(hk, swh[k * 64 + 32 + lane], o1); }
+      if (T.logits) {
+        if (lane < T.P) T.logits[(size_t)row * T.P + lane] = o0;
+        if (lane + 32 < T.P) T.logits[(size_t)row * T.P + 32 + lane] = o1;
       }
-    }
-    if (T.noise && T.logp) {
+      // lane a needs logits[a] (its own o0) and logits[A + a]: o0 of lane A + a, or o1 of lane A + a - 32
+      const float s_lo = __shfl(o0, (T.A + lane) & 31, 32), s_hi = __shfl(o1, (T.A + lane - 32) & 31, 32);
+      const float sraw = T.A + lane < 32 ? s_lo : s_hi;
+      float lp = 0.0f;
+      if (lane < T.A) {
+        const float loc = o0;
+        if (T.noise) {
+          const float scale = rr_softplus(sraw) + T.min_std;
+          const float eps = T.noise[(size_t)row * T.A + lane], raw = loc + scale * eps;
+          const float zz = (raw - loc) / scale;
+          lp = -0.5f * zz * zz - logf(scale) - HALF_LOG_2PI - 2.0f * (LOG2 - raw - rr_softplus(-2.0f * raw));
+          if (T.raw) T.raw[(size_t)row * T.A + lane] = raw;
+          T.action[(size_t)row * T.A + lane] = tanhf(raw);
+        } else {
+          T.action[(size_t)row * T.A + lane] = tanhf(loc);
+        }
+      }
+      if (T.noise && T.logp) {
 #pragma unroll
-      for (int o = 16; o > 0; o >>= 1) lp += __shfl_xor(lp, o, 32);
-      if (lane == 0) T.logp[row] = lp;
+        for (int o = 16; o > 0; o >>= 1) lp += __shfl_xor(lp, o, 32);
+        if (lane == 0) T.logp[row] = lp;
+      }
+    } else {
+      // 33 .. 64 actions: a lane forms the four logits lane + 32 q and owns the action dimensions a = lane and a = lane + 32
+      float o[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) o[q] = sb[T.nh * 32 + 32 * q + lane];
+#pragma unroll
+      for (int k = 0; k < 32; ++k) {
+        const float hk = __shfl(h, k, 32);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) o[q] = fmaf(hk, swh[k * 128 + 32 * q + lane], o[q]);
+      }
+      if (T.logits) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+          if (32 * q + lane < T.P) T.logits[(size_t)row * T.P + 32 * q + lane] = o[q];
+      }
+      // the scale logit of dimension a is logit A + a, 33 <= A <= 64: for a = lane it sits in o[1] or o[2] of lane (A + a) & 31, for
+      // a = lane + 32 one register further up in the same lane
+      const int src = (T.A + lane) & 31;
+      const float t1 = __shfl(o[1], src, 32), t2 = __shfl(o[2], src, 32), t3 = __shfl(o[3], src, 32);
+      const bool up = T.A + lane >= 64;
+      float lp = 0.0f;
+#pragma unroll
+      for (int d = 0; d < 2; ++d) {
+        const int a = lane + 32 * d;
+        const float loc = d ? o[1] : o[0], sraw = d ? (up ? t3 : t2) : (up ? t2 : t1);
+        if (a < T.A) {
+          if (T.noise) {
+            const float scale = rr_softplus(sraw) + T.min_std;
+            const float eps = T.noise[(size_t)row * T.A + a], raw = loc + scale * eps;
+            const float zz = (raw - loc) / scale;
+            lp += -0.5f * zz * zz - logf(scale) - HALF_LOG_2PI - 2.0f * (LOG2 - raw - rr_softplus(-2.0f * raw));
+            if (T.raw) T.raw[(size_t)row * T.A + a] = raw;
+            T.action[(size_t)row * T.A + a] = tanhf(raw);
+          } else {
+            T.action[(size_t)row * T.A + a] = tanhf(loc);
+          }
+        }
+      }
+      if (T.noise && T.logp) {
+#pragma unroll
+        for (int o_ = 16; o_ > 0; o_ >>= 1) lp += __shfl_xor(lp, o_, 32);
+        if (lane == 0) T.logp[row] = lp;
+      }
     }
   }
 }

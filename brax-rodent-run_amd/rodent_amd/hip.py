@@ -492,7 +492,7 @@ def mlp_forward(obs, mean=None, std=None, policy=None, value=None, want_pre=Fals
     """Fused normalise + policy MLP + value MLP forward on the f32 matrix cores (C ABI `rr_mlp_forward`).
 
     obs [M, K] float32 device; policy / value: (weights, biases) lists in nn.Linear layout or None.  Returns
-    (policy_out [M, P] | None, value_out [M] | None, policy_pre [L-1, M, 32] | None, value_pre [L-1, M, 256] | None).
+    (policy_out [M, P] | None, value_out [M] | None, policy_pre [L-1, M, 32] | None, value_pre [L-1, M, 256] | None); P <= 128.
     rows (int64 [M], optional): sample m is row rows[m] of obs (the minibatch addressed in place)."""
     M, K = obs.shape
     _ptr(obs)
@@ -659,7 +659,7 @@ def policy_sample(logits, noise, min_std: float):
 def policy_backward(grad_logits, head_weight, hidden_weights, pre_act, bias_grads, bufs=None):
     """Delta chain of the policy network's 32-wide hidden stack in one launch (C ABI `rr_policy_backward`).
 
-    grad_logits [M, P]; head_weight [P, 32]; hidden_weights: list, entry j >= 1 = W_j [32, 32] (entry 0 ignored); pre_act
+    grad_logits [M, P], P <= 128; head_weight [P, 32]; hidden_weights: list, entry j >= 1 = W_j [32, 32] (entry 0 ignored); pre_act
     [nh, >= M, 32] (rr_mlp_forward's policy_pre; the first M rows of each layer are overwritten by silu(z)); bias_grads: list of
     nh [32] tensors.  Returns (delta [nh, M, 32], h = pre_act)."""
     nh = pre_act.shape[0]
@@ -688,7 +688,7 @@ _pa_ws = {}
 
 def policy_act(obs, mean, std, policy, noise, min_std: float, want_logits: bool = False, rows=None):
     """The rollout's actor step in two launches (C ABI `rr_policy_act`): obs [M, K] (or obs[rows]) -> normalise -> policy MLP ->
-    tanh-normal head.  noise [M, A] or None (deterministic: action = tanh(loc)).  Returns (action, raw_action | None,
+    tanh-normal head (A <= 64).  noise [M, A] or None (deterministic: action = tanh(loc)).  Returns (action, raw_action | None,
     log_prob | None, logits | None)."""
     M, K = obs.shape
     _ptr(obs)

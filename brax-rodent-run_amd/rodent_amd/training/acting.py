@@ -76,8 +76,8 @@ def actor_params(policy_net, normalizer_params, min_std: float) -> dict:
 
 def actor_shape_supported(policy_net, action_size: int) -> bool:
     """The policy shapes the in-kernel actor evaluates: 1 .. 4 hidden layers of 32 units, float32, a head of 2 x action_size
-    logits with action_size <= 64.  (The LEARNER's kernels have their own, narrower head limit -- `fused_mlp.fusable(.., 64)` in
-    `ppo.train` -- which decides the learner's path only.)"""
+    logits with action_size <= 64.  (The LEARNER's kernels take the same widths, but `ppo.train` hands them a head of more than 64
+    logits only with RR_FUSED_WIDE_HEAD=1 -- `fused_mlp.max_policy_head()` -- which decides the learner's path only.)"""
     from . import fused_mlp
     ls = list(policy_net.layers)
     return (2 <= len(ls) <= 5 and all(l.out_features == fused_mlp.POLICY_HIDDEN for l in ls[:-1]) and ls[0].weight.dtype == torch.float32

@@ -11,6 +11,7 @@ in afterwards, so the normalised copy of the minibatch is never written.
 """
 from __future__ import annotations
 
+import os
 from typing import Optional, Sequence
 
 import torch
@@ -18,6 +19,13 @@ import torch
 from .. import hip
 
 POLICY_HIDDEN, VALUE_HIDDEN = 32, 256
+
+
+def max_policy_head() -> int:
+    """Widest policy head (in logits) that `ppo.train` and `make_inference_fn` hand to the hand-written learner / actor kernels: 64, or
+    128 with RR_FUSED_WIDE_HEAD=1.  The kernels themselves take up to 128 (two passes over column halves of 64); the switch is
+    opt-in until the wide path has been measured against the autograd path it replaces."""
+    return 128 if os.environ.get("RR_FUSED_WIDE_HEAD", "0") == "1" else 64
 
 
 def net_params(mlp):

@@ -231,7 +231,8 @@ int rr_compute_gae(const float* truncation, const float* termination, const floa
 /* Fused actor / critic MLP forward on the f32 matrix cores (v_mfma_f32_32x32x2_f32 / 16x16x4_f32; csrc/rr_mlp.h): what
  * `ppo.networks.make_inference_fn` (normalise, policy MLP) and the forward half of `ppo.losses.compute_ppo_loss` (policy and
  * value MLP on the same observations) compute [UP brax.training; REF brax_rodent_run_ppo.py:97-114], for
- * the `make_ppo_networks` default shapes: policy obs -> 32 x (nlayers-1) -> out (<= 64), value obs -> 256 x (nlayers-1) -> 1,
+ * the `make_ppo_networks` default shapes: policy obs -> 32 x (nlayers-1) -> out (<= 128; more than 64
+ * logits run as two passes over column halves of 64), value obs -> 256 x (nlayers-1) -> 1,
  * SiLU on hidden layers, float32 throughout.  A network is described by HOST arrays of DEVICE pointers: weights[l] is
  * [sizes[l+1]][sizes[l]] row-major (torch.nn.Linear.weight), biases[l] is [sizes[l+1]]; sizes has nlayers + 1 entries.
  * Either network may be NULL (skipped).  obs_rows (device int64 [M], nullable): sample m is row obs_rows[m] of `obs` (a minibatch
@@ -271,7 +272,7 @@ int rr_ppo_loss(const float* policy_logits, const float* values, const float* ra
 
 /* The rollout's actor step, acting.actor_step -> make_inference_fn [UP; SURVEY.md a22], in two launches: observations (optionally
  * through obs_rows, optionally normalised by mean / std) -> policy network (as rr_mlp_forward takes it: 32-wide hidden layers,
- * head 2 x action_size <= 64) -> tanh-normal head.  noise [M][A] standard normal draws: raw_action = loc + (softplus(scale) + min_std)
+ * head 2 x action_size <= 128; an odd or wider head: RR_EUNSUPPORTED) -> tanh-normal head.  noise [M][A] standard normal draws: raw_action = loc + (softplus(scale) + min_std)
  * * noise, action = tanh(raw_action), log_prob [M]; noise NULL: the deterministic policy, action = tanh(loc).  raw_action, log_prob,
  * logits [M][2A] are optional outputs (NULL = not written).  The first layer is split over the observation width across
  * workgroups (the batch alone is 64 row tiles for 256 CUs).  workspace: rr_policy_act_workspace_bytes(M) bytes of device memory. */
@@ -288,7 +289,7 @@ int rr_policy_sample(const float* logits, const float* noise, int32_t N, int32_t
                      float* log_prob, void* stream);
 
 /* Backward pass of the policy network's hidden stack (32-wide SiLU layers) in one launch: delta_{nh-1} = (g W_head) *
- * silu'(z_{nh-1}), delta_{j-1} = (delta_j W_j) * silu'(z_{j-1}).  grad_logits [M][P] (P <= 64) = d loss / d logits; head_weight
+ * silu'(z_{nh-1}), delta_{j-1} = (delta_j W_j) * silu'(z_{j-1}).  grad_logits [M][P] (P <= 128; wider: RR_EUNSUPPORTED) = d loss / d logits; head_weight
  * [P][32]; hidden_weights: HOST array of nhidden device pointers, entry j (1 <= j < nhidden) = W_j [32 out][32 in]
  * (torch.nn.Linear.weight), entry 0 unused; pre_act [nhidden][pre_act_rows >= M][32] = rr_mlp_forward's policy_pre, rows 0..M-1 of
  * each layer overwritten by silu(z) (a minibatch may carry bootstrap rows, which have no policy gradient, behind the M used ones);
