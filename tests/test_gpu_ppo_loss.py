@@ -4,47 +4,11 @@ import numpy as np
 import pytest
 import torch
 
+from tests import ppo_batches
+from tests.ppo_batches import CFG, _batch, _reference
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-CFG = dict(entropy_cost=1e-3, discounting=0.97, reward_scaling=1.0, gae_lambda=0.95, clipping_epsilon=0.3)
-
-
-def _fixed_noise_dist(A, noise):
-    from rodent_amd.training.networks import NormalTanhDistribution
-
-    class FixedNoise(NormalTanhDistribution):
-        def sample_no_postprocessing(self, logits, generator=None):
-            loc, scale = self._params(logits)
-            return loc + scale * noise.to(loc.dtype).to(loc.device).reshape(loc.shape)
-    return FixedNoise(A)
-
-
-def _batch(T, B, R, A, seed):
-    g = torch.Generator().manual_seed(seed)
-    data = dict(raw_action=torch.randn(R, T, A, generator=g) * 0.8, log_prob=torch.randn(R, T, generator=g) * 2 - 25,
-                reward=torch.rand(R, T, generator=g), truncation=(torch.rand(R, T, generator=g) < 0.05).float())
-    data["discount"] = 1 - (torch.rand(R, T, generator=g) < 0.1).float()
-    logits = torch.randn((T + 1) * B, 2 * A, generator=g) * 0.7
-    values = torch.randn((T + 1) * B, generator=g) * 3
-    noise = torch.randn(T * B, A, generator=g)
-    idx = torch.randperm(R, generator=g)[:B]
-    return data, logits, values, noise, idx
-
-
-def _reference(data, logits, values, noise, idx, T, B, A, dtype, device, normalize_advantage=True):
-    """compute_ppo_loss + autograd in `dtype`; returns (metrics, d loss / d logits, d loss / d values)."""
-    from rodent_amd.training.agents.ppo import losses
-    c = lambda x: x.to(dtype).to(device)
-    lg = c(logits).clone().requires_grad_(True)
-    vl = c(values).clone().requires_grad_(True)
-    rows = idx if idx is not None else torch.arange(B)
-    mbd = {k: c(data[k][rows]).transpose(0, 1) for k in ("raw_action", "log_prob", "reward", "discount", "truncation")}
-    v = vl.reshape(T + 1, B)
-    loss, m = losses.compute_ppo_loss(lg[:T * B].reshape(T, B, 2 * A), v[:T], v[T], mbd, _fixed_noise_dist(A, noise),
-                                      normalize_advantage=normalize_advantage, **CFG)
-    loss.backward()
-    return torch.stack([m[k] for k in ("total_loss", "policy_loss", "v_loss", "entropy_loss")]).double().cpu(), \
-        lg.grad.double().cpu(), vl.grad.double().cpu()
 
 
 @pytest.mark.parametrize("T,B,R,A,use_idx,norm", [(10, 256, 700, 30, True, True), (10, 2048, 2048, 30, True, True), (5, 77, 77, 30, False, True),
@@ -70,6 +34,46 @@ def test_fused_loss_and_output_gradients(T, B, R, A, use_idx, norm):
         assert err <= 3 * err32 + 2e-6, (name, float(err), float(err32))        # in the float32 class of the path it replaces
     # every sample is either inside the clip range (tie of the two surrogates) or outside: both branches are exercised
     assert (gl64[:T * B].abs().sum(1) > 0).all()
+
+
+def _hip_sampler(logits, eps):
+    """The actor's head on the GPU: (raw_action, log_prob) of `hip.policy_sample` at the CURRENT logits."""
+    from rodent_amd import hip
+    _, raw, lp = hip.policy_sample(logits.to(DEV).contiguous(), eps.to(DEV).contiguous(), 0.001)
+    return raw, lp
+
+
+ONPOLICY = [(T, B, R, A, u, True, 0.3) for (T, B, R, u) in ((7, 130, 200, True), (5, 77, 77, False), (3, 8, 8, False)) for A in (2, 30, 32, 33, 38, 64)]
+ONPOLICY += [(7, 130, 200, 30, True, False, 0.3),         # advantages as they come
+             (7, 130, 200, 38, True, True, 0.05)]         # narrow clip range: more than half of the rows are clipped
+
+
+@pytest.mark.parametrize("T,B,R,A,use_idx,norm,eps_clip", ONPOLICY)
+def test_loss_kernel_on_on_policy_batches(T, B, R, A, use_idx, norm, eps_clip):
+    """rr_ppo_loss where rho ~ 1 (tests/ppo_batches.py): all six classes {adv > 0, adv < 0} x {rho < lo, in range, rho > hi} populated, the
+    t == 0 rows sampled by `rr_policy_sample` itself (rho = 1: the two kernels agree on the log-prob), d loss / d logits compared PER ROW
+    against float64 with torch's float32 autograd as the yardstick.  A = 33 puts one lane into the second trip of the `a += 32` loops, 32
+    and 64 are whole trips.  tests/test_ppo_loss_criteria_cpu.py holds the criterion itself: five seeded kernel errors fail it."""
+    from rodent_amd import hip
+    cfg = dict(CFG, clipping_epsilon=eps_clip)
+    label = f"T={T} B={B} A={A} norm={norm} eps={eps_clip}"
+    data, logits, values, noise, idx = batch = ppo_batches.onpolicy_batch(T, B, R, A, seed=T * 1000 + B + A, use_idx=use_idx, sampler=_hip_sampler)
+    rho, adv = ppo_batches.rho_and_advantage64(data, logits, values, idx, T, B, A, norm, cfg)
+    kept = ppo_batches.assert_coverage(rho, adv, eps_clip, T, B, A, label)
+    ppo_batches.assert_t0_rows_on_policy(rho, eps_clip, B)
+    m64, gl64, gv64 = _reference(*batch, T, B, A, torch.float64, "cpu", norm, cfg)
+    m32, gl32, gv32 = _reference(*batch, T, B, A, torch.float32, DEV, norm, cfg)
+    dd = {k: v.to(DEV).contiguous() for k, v in data.items()}
+    gl, gv, m = hip.ppo_loss(logits.to(DEV), values.to(DEV), dd, idx.to(DEV) if idx is not None else None, noise.to(DEV), T,
+                             normalize_advantage=norm, **cfg)
+    torch.cuda.synchronize()
+    gl, gv, m = gl.double().cpu(), gv.double().cpu(), m.double().cpu()
+    assert torch.isfinite(gl).all() and torch.isfinite(gv).all() and torch.isfinite(m).all()
+    assert (gl[T * B:] == 0).all() and (gv[T * B:] == 0).all()                 # bootstrap rows
+    assert float(m64[1].abs()) > 1e-3                                          # policy_loss is O(1): the metrics check below means something
+    ppo_batches.assert_rowrel_criterion(gl, gl32, gl64, kept, label)
+    ppo_batches.assert_global_criterion("values", gv, gv32, gv64, label)
+    ppo_batches.assert_global_criterion("metrics", m, m32, m64, label)
 
 
 def test_fused_update_equals_the_autograd_path():
@@ -112,6 +116,69 @@ def test_fused_update_equals_the_autograd_path():
         assert (a - b).abs().max() <= 2e-4 * b.abs().max() + 1e-9, (tuple(p.shape), float((a - b).abs().max()), float(b.abs().max()))
     for k in m_f:
         assert abs(m_f[k] - float(m[k])) <= 1e-5 * max(1.0, abs(float(m[k]))), (k, m_f[k], float(m[k]))
+
+
+def fused_update_on_an_on_policy_batch(A):
+    """FusedUpdate against compute_ppo_loss + backward on the same fused forward, as test_fused_update_equals_the_autograd_path, on a
+    batch whose behaviour actions and log-probs are samples of a policy near the network's own (tests/ppo_batches.py; the t == 0 rows
+    from `rr_policy_sample` at the network's logits), and the check that what is compared is the policy term: the head weight's gradient
+    is at least 100 x what the entropy term alone leaves when the reference is rerun with the advantages zeroed."""
+    from rodent_amd import hip
+    from rodent_amd.training import distributed as D, fused_mlp, networks
+    from rodent_amd.training.agents.ppo import fused_update, losses
+    torch.manual_seed(0)
+    T, B, R, K = 6, 96, 300, 211
+    nets = networks.make_ppo_networks(K, A, device=DEV)
+    pnet, vnet, dist = nets.policy_network, nets.value_network, nets.parametric_action_distribution
+    params = list(pnet.parameters()) + list(vnet.parameters())
+    flat = D.FlatGrads(params)
+    g = torch.Generator(device=DEV).manual_seed(1)
+    idx = _batch(T, B, R, A, seed=9)[4].to(DEV)
+    obs = torch.randn(R, T + 1, K, device=DEV, generator=g) * 2 + 0.5
+    mean, std = torch.randn(K, device=DEV, generator=g) * 0.3, torch.rand(K, device=DEV, generator=g) + 0.5
+    # the network's outputs on the minibatch, by the forward FusedUpdate itself runs (time-major rows t * B + b)
+    rows = (idx.unsqueeze(0) * (T + 1) + torch.arange(T + 1, device=DEV).unsqueeze(1)).reshape(-1)
+    with torch.no_grad():
+        cur, val = hip.mlp_forward(obs.reshape(-1, K), mean, std, fused_mlp.net_params(pnet), fused_mlp.net_params(vnet), rows=rows)[:2]
+    data, cur, _, _, _ = ppo_batches.onpolicy_batch(T, B, R, A, seed=9, sampler=_hip_sampler, logits=cur)
+    rho, adv = ppo_batches.rho_and_advantage64(data, cur, val.cpu(), idx.cpu(), T, B, A, True, CFG)
+    ppo_batches.assert_coverage(rho, adv, CFG["clipping_epsilon"], T, B, A, f"FusedUpdate A={A}")
+    data = {k: v.to(DEV).contiguous() for k, v in data.items()}
+    data["obs"] = obs
+    fu = fused_update.FusedUpdate(pnet, vnet, dist, T, normalize_advantage=True, **CFG)
+    gen = torch.Generator(device=DEV).manual_seed(77)
+    m_f = fu(data, idx, mean, std, gen)
+    got = flat.flat.clone()
+    m_f = {k: float(v) for k, v in m_f.items()}
+
+    def autograd_path(advantage_stats_fn=None):            # the path it replaces, same noise stream
+        gen = torch.Generator(device=DEV).manual_seed(77)
+        mbd = {k: data[k][idx].transpose(0, 1) for k in ("raw_action", "log_prob", "reward", "discount", "truncation")}
+        raw = data["obs"][idx].transpose(0, 1)
+        logits_all, values_all = fused_mlp.actor_critic(raw.reshape((T + 1) * B, -1), mean, std, pnet, vnet)
+        values = values_all.reshape(T + 1, B)
+        loss, m = losses.compute_ppo_loss(logits_all[:T * B].reshape(T, B, -1), values[:T], values[T], mbd, dist, normalize_advantage=True,
+                                          generator=gen, advantage_stats_fn=advantage_stats_fn, **CFG)
+        flat.zero_()
+        loss.backward()
+        return flat.flat.clone(), m, float(pnet.layers[-1].weight.grad.abs().max())
+    want, m, head = autograd_path()
+    o = 0
+    for p in params:                                           # per tensor: the scales differ by orders of magnitude
+        a, b = got[o:o + p.numel()], want[o:o + p.numel()]
+        o += p.numel()
+        assert torch.isfinite(a).all()
+        assert (a - b).abs().max() <= 2e-4 * b.abs().max() + 1e-9, (tuple(p.shape), float((a - b).abs().max()), float(b.abs().max()))
+    for k in m_f:
+        assert abs(m_f[k] - float(m[k])) <= 1e-5 * max(1.0, abs(float(m[k]))), (k, m_f[k], float(m[k]))
+    # (adv - mean) / (inf + 1e-8): every advantage is zero, the policy term vanishes, the entropy term stays
+    _, _, head_entropy_only = autograd_path(lambda adv: (adv.mean(), torch.full((), float("inf"), device=adv.device)))
+    print(f"A={A}: policy_loss {m_f['policy_loss']:.3f}; max |d loss / d head weight| {head:.3e}, with zero advantages {head_entropy_only:.3e}")
+    assert head_entropy_only > 0 and head >= 100 * head_entropy_only
+
+
+def test_fused_update_equals_the_autograd_path_on_policy():
+    fused_update_on_an_on_policy_batch(30)
 
 
 @pytest.mark.parametrize("M,H", [(22528, 256), (20480, 32), (100, 64), (7, 256), (513, 128)])

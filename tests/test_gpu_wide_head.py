@@ -10,7 +10,7 @@ import pytest
 import torch
 
 from tests import util
-from tests.test_gpu_ppo_loss import CFG, _batch, _reference
+from tests.test_gpu_ppo_loss import CFG, _batch, _reference, fused_update_on_an_on_policy_batch
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -288,6 +288,13 @@ def test_fused_update_equals_the_autograd_path_at_38_actions():
         assert (a - b).abs().max() <= 2e-4 * b.abs().max() + 1e-9, (tuple(p.shape), float((a - b).abs().max()), float(b.abs().max()))
     for k in m_f:
         assert abs(m_f[k] - float(m[k])) <= 1e-5 * max(1.0, abs(float(m[k]))), (k, m_f[k], float(m[k]))
+
+
+def test_fused_update_equals_the_autograd_path_at_38_actions_on_policy(monkeypatch):
+    """The same on a 76-logit policy with the switch that sends `ppo.train`'s learner this way, on a batch with rho ~ 1: the policy term,
+    not the entropy term alone, goes through the two-pass head forward and the four-segment `rr_policy_backward`."""
+    monkeypatch.setenv("RR_FUSED_WIDE_HEAD", "1")
+    fused_update_on_an_on_policy_batch(38)
 
 
 MODEL = "rodent_cpu.xml"
