@@ -11,7 +11,9 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 static thread_local std::string g_err;
@@ -51,23 +53,97 @@ struct rr_model {
   float fscalar(const char* n, int i = 0) const { const Entry* x = find(n); return x ? ((const float*)x->data)[i] : 0.f; }
 };
 
+// ------------------------------------------------------------------------------------------ kernel instances
+// One function maps (model, launch form, variant) to the kernel instance that serves it, or to the reason there is none: launch(),
+// the support queries and the attribute loop of rr_batch_create all ask it, so none of them can disagree about what exists.
+enum Form { F_STEP, F_UNROLL, F_ACTOR, F_EVAL, N_FORMS };                        // single step | multi-step | ... with the actor | evaluation
+enum Variant { V_PROD, V_DEBUG, V_PROFILE, V_RAND, V_PAIR, N_VARIANTS };         // production | debug dump | cycle-stamp profile | per-env parameters | two-wave pair
+struct Instance { kern_t kern; const char* why = nullptr; bool fixed = false; };      // why: the reason when kern is null (multi-step forms: with the entry point that reports it); fixed: compiled for the model's dimensions
+
+static Instance select(const rr_model* m, Form form, Variant v) {
+  const bool s111 = m->NBS == 1 && m->NVS == 1 && m->NCS == 1, s221 = m->NBS == 2 && m->NVS == 2 && m->NCS == 1, s332 = m->NBS == 3 && m->NVS == 3 && m->NCS == 2;
+  const bool newton = m->solver == 2, eval = form == F_EVAL, unroll = form != F_STEP, actor = form == F_ACTOR;
+  const char *no_diag = "no diagnostic kernel instance for this model", *no_slots = "no kernel instance for this model's slot counts";
+  auto no = [](const char* why) { return Instance{nullptr, why}; };
+  // rr_step_kernel<NBS, NVS, NCS, PROF, DBG, dims, NEWTON, UNROLL, ACTOR, PAIR, DYN>, rr_rand_kernel<dims, UNROLL, ACTOR>, rr_eval_kernel<dims, DYN>
+  if (v == V_PAIR && (unroll || newton || !RRDimsRodentNew::matches(m->kd_rep))) return no("no two-wave pair instance for this model / launch form");
+  if (v == V_PAIR) return {rr_step_kernel<2, 2, 1, false, false, RRDimsRodentNew, false, false, false, true>, nullptr, true};      // one replica = the rodent_new dims
+  // Eligibility first.  Multi-step instances: the single-rodent floor-contact models (fixed-dimension or generic) and the candidate-pair models
+  // (DYN, generic dimensions), CG only, no diagnostics.  None for the Newton solver, the two-wave pair instance and other slot counts.
+  if (unroll && (v == V_DEBUG || v == V_PROFILE)) return no("rr_env_unroll: no diagnostic outputs in a multi-step rollout");
+  if (eval) {
+    // Evaluation instances (rr_eval_kernel): the production CG multi-step form with the actor of the (2,2,1) slot counts, fixed-dimension,
+    // generic or generic with candidate-pair contacts; shared tables only
+    if (newton) return no("rr_env_unroll_eval: the Newton solver has no multi-step instance");
+    if (m->pair_ok) return no("rr_env_unroll_eval: two-tree models served by the two-wave pair instance have no multi-step instance");
+    if (!s221) return no("rr_env_unroll_eval: only the (2,2,1) slot counts have an evaluation instance");
+    if (v == V_RAND) return no("rr_env_unroll_eval: no evaluation instance reads per-env parameters (this batch carries some)");
+  } else if (v == V_RAND) {
+    // Per-environment parameters (rr_rand_kernel): the production CG instances of the single-rodent floor-contact models -- fixed-dimension
+    // or generic (2,2,1) -- as single-step, multi-step and multi-step with the actor
+    if (m->dyn) return no("models with candidate-pair contacts (DYN instances) have none");
+    if (m->pair_ok) return no("two-tree models served by the two-wave pair instance have none");
+    if (newton) return no("the Newton solver's instances have none");
+    if (!s221) return no("only the (2,2,1) slot counts have instances with per-env parameters");
+  } else if (unroll && (newton || !s221))
+    return no("rr_env_unroll: no multi-step kernel instance for this model / solver");
+  if (m->dyn) {      // candidate-pair contacts: the production instances (generic dimensions); no debug dump, no profile build
+    if (v != V_PROD) return no(no_diag);
+    if (newton || !s221) return no(no_slots);
+    if (eval) return Instance{rr_eval_kernel<RRDims, true>};
+    return Instance{actor ? rr_step_kernel<2, 2, 1, false, false, RRDims, false, true, true, false, true>
+                    : (unroll ? rr_step_kernel<2, 2, 1, false, false, RRDims, false, true, false, false, true> : rr_step_kernel<2, 2, 1, false, false, RRDims, false, false, false, false, true>)};
+  }
+  // Single step besides production: debug dump (generic dims; selected per launch when rr_outputs.debug is given), cycle-stamp profile
+  // (diagnostic, rodent dims or generic 2,2,1)
+  if (v == V_PROFILE && (newton || !s221)) return no(no_diag);
+  if (v == V_PROFILE) return RRDimsRodent::matches(m->kd) ? Instance{rr_step_kernel<2, 2, 1, true, false, RRDimsRodent>, nullptr, true} : Instance{rr_step_kernel<2, 2, 1, true, false, RRDims>};
+  if (newton)     // Newton: the (2,2,1) generic instances only (rr_model_set_solver_type checks)
+    return Instance{v == V_DEBUG ? rr_step_kernel<2, 2, 1, false, true, RRDims, true> : rr_step_kernel<2, 2, 1, false, false, RRDims, true>};
+  if (v == V_DEBUG)
+    return s111 ? Instance{rr_step_kernel<1, 1, 1, false, true, RRDims>} : (s221 ? Instance{rr_step_kernel<2, 2, 1, false, true, RRDims>} : (s332 ? Instance{rr_step_kernel<3, 3, 2, false, true, RRDims>} : no(no_diag)));
+  if (!s221) return s111 ? Instance{rr_step_kernel<1, 1, 1, false, false, RRDims>} : (s332 ? Instance{rr_step_kernel<3, 3, 2, false, false, RRDims>} : no(no_slots));
+  auto family = [&](auto* t) -> kern_t {      // the (2,2,1) CG production family: one set per dims type
+    typedef typename std::remove_pointer<decltype(t)>::type DT;      // t: a null pointer that names the dims type
+    if (eval) return rr_eval_kernel<DT>;
+    if (v == V_RAND) return actor ? rr_rand_kernel<DT, true, true> : (unroll ? rr_rand_kernel<DT, true> : rr_rand_kernel<DT>);
+    return actor ? rr_step_kernel<2, 2, 1, false, false, DT, false, true, true> : (unroll ? rr_step_kernel<2, 2, 1, false, false, DT, false, true> : rr_step_kernel<2, 2, 1, false, false, DT>);
+  };
+  if (RRDimsRodent::matches(m->kd)) return {family((RRDimsRodent*)nullptr), nullptr, true};      // fixed-dimension instances (rr_kernel.h RRDimsFixed)
+  if (RRDimsRodentNew::matches(m->kd)) return {family((RRDimsRodentNew*)nullptr), nullptr, true};
+  return Instance{family((RRDims*)nullptr)};
+}
+
+static void set_layout(RRDims& k, const RRLayout& L) {
+  k.o_qpos = L.o_qpos; k.o_qvel = L.o_qvel; k.o_act = L.o_act; k.o_ctrl = L.o_ctrl; k.o_xpos = L.o_xpos; k.o_xquat = L.o_xquat;
+  k.o_cinert = L.o_cinert; k.o_cdof = L.o_cdof; k.o_cvel = L.o_cvel; k.o_qLD = L.o_qLD; k.o_vec = L.o_vec; k.o_x = L.o_x;
+  k.o_arm = L.o_arm; k.o_warm = L.o_warm; k.o_qact = L.o_qact; k.o_jlist = L.o_jlist; k.lds_floats = L.lds_floats;
+  k.o_H = L.o_H; k.o_Mp = L.o_Mp; k.o_anc = L.o_anc;      // 0 unless Newton
+}
+// staging of the line search's compacted rows: cinert | cvel | pose regions each hold 4*ncon + nv floats; the alias cells share the pose cells
+static bool stage_fits(int nbody, int nv, int con_slots, int nalias) {
+  const int pose = std::max(7 * nbody + 4, 6 * nv);
+  return 2 * (nalias + 4) <= pose && 2 * (nbody + 8) <= pose && 6 * con_slots <= pose && 4 * con_slots + nv <= std::min(std::min(10 * nbody, 6 * nbody), pose);
+}
+// the solve job tables `prefix`k_coljob / k_rowjob against the job slots and loop bounds of the kernel instance
+static bool solve_jobs_fit(const rr_model* m, const char* prefix, int njs, const RRDims& k) {
+  return (int)m->find((std::string(prefix) + "k_coljob").c_str())->count == 9 * njs && (int)m->find((std::string(prefix) + "k_rowjob").c_str())->count == 5 * njs &&
+         k.lmax <= 16 && k.lmax >= 1 && k.cmax <= 8 && k.rmax <= 8 && k.cmax >= 1;
+}
+
 static void layout(rr_model* m) {
   RRDims& k = m->kd;
   const rr_dims& d = m->dims;
   const int con_slots = m->dyn ? m->NCS * RR_LANES : d.ncon;      // DYN: the wave holds the pairs in penetration in its contact slots
   const RRLayout L = rr_layout(d.nq, d.nv, d.nu, d.nbody, d.nM, con_slots, m->solver == 2);
-  k.o_H = L.o_H; k.o_Mp = L.o_Mp; k.o_anc = L.o_anc; k.solver = m->solver;
+  set_layout(k, L);
+  k.solver = m->solver;
   // factorisation schedule: with alias copies of the hot rows in the pose cells (levelsched.py); the Newton instances reuse the schedule
   // on the Hessian's array through an address shift, which the alias cells would not follow, so they run the alias-free one
   k.nfac = m->iscalar(m->solver == 2 ? "k_factor3p_rows" : "k_factor3_rows");
   k.nalias = m->solver == 2 ? 0 : m->iscalar("k_nalias");
   m->dbg_names.clear(); m->dbg_off.clear(); m->dbg_size.clear(); m->dbg_cnames.clear();      // layout() may run again (rr_model_set_solver_type)
-  k.o_qpos = L.o_qpos; k.o_qvel = L.o_qvel; k.o_act = L.o_act; k.o_ctrl = L.o_ctrl; k.o_xpos = L.o_xpos; k.o_xquat = L.o_xquat;
-  k.o_cinert = L.o_cinert; k.o_cdof = L.o_cdof; k.o_cvel = L.o_cvel; k.o_qLD = L.o_qLD; k.o_vec = L.o_vec; k.o_x = L.o_x;
-  k.o_arm = L.o_arm; k.o_warm = L.o_warm; k.o_qact = L.o_qact; k.o_jlist = L.o_jlist; k.lds_floats = L.lds_floats;
-  const int o = L.lds_floats;
-  // staging of the line search's compacted rows: cinert | cvel | pose regions each hold 4*ncon + nv floats
-  m->stage_ok = 2 * (k.nalias + 4) <= std::max(7 * d.nbody + 4, 6 * d.nv) && 2 * (d.nbody + 8) <= std::max(7 * d.nbody + 4, 6 * d.nv) && 6 * con_slots <= std::max(7 * d.nbody + 4, 6 * d.nv) && 4 * con_slots + d.nv <= std::min(std::min(10 * d.nbody, 6 * d.nbody), std::max(7 * d.nbody + 4, 6 * d.nv));
+  m->stage_ok = stage_fits(d.nbody, d.nv, con_slots, k.nalias);
   if (m->dyn && d.nu > std::max(7 * d.nbody + 4, 6 * d.nv)) m->stage_ok = false;      // actuator forces go through the pose cells
   // debug dump
   int g = 0;
@@ -84,16 +160,15 @@ static void layout(rr_model* m) {
   k.g_kaok = dbg("kernarg_ok", 1);
   k.dbg_floats = g;
   for (auto& s : m->dbg_names) m->dbg_cnames.push_back(s.c_str());
-  m->dims.lds_bytes = o * (int)sizeof(float);
+  m->dims.lds_bytes = L.lds_floats * (int)sizeof(float);
   m->dims.dbg_floats = g;
   m->dims.solver = m->solver;
   // 1: the production launches of this model run an instance compiled for its dimensions (rr_kernel.h RRDimsFixed); 0: the generic
   // instance (same results, ~10 % slower).  The constants cover the schedule-table parameters, so a compiler change that moves
   // them shows up here (tests/test_abi_and_oracle.py) instead of as a silent slowdown.
-  m->dims.fixed_instance = (m->solver != 2 && !m->dyn && m->NBS == 2 && m->NVS == 2 && m->NCS == 1 && (RRDimsRodent::matches(k) || RRDimsRodentNew::matches(k))) ? 1 : 0;
+  m->dims.fixed_instance = select(m, F_STEP, V_PROD).fixed ? 1 : 0;
 }
 
-static kern_t pick_pair_kernel(const rr_model* m);
 // Two-wave (PAIR) instance: dims of one replica from the blob's h_* tables (rodent_amd/ktables.py replica_model).  RR_PAIR_WAVES=0
 // keeps such models on the generic one-wave instance (A/B runs).
 static void setup_replica(rr_model* m) {
@@ -115,21 +190,16 @@ static void setup_replica(rr_model* m) {
   k.lmax = m->iscalar("h_k_solve_lmax"); k.cmax = m->iscalar("h_k_solve_cmax"); k.rmax = m->iscalar("h_k_solve_rmax");
   k.obs_dim = k.nq + k.nv + 16 * (k.nbody - 1) + k.nv + 3;
   const RRLayout L = rr_layout(k.nq, k.nv, k.nu, k.nbody, k.nM, k.ncon, false);
-  k.o_qpos = L.o_qpos; k.o_qvel = L.o_qvel; k.o_act = L.o_act; k.o_ctrl = L.o_ctrl; k.o_xpos = L.o_xpos; k.o_xquat = L.o_xquat;
-  k.o_cinert = L.o_cinert; k.o_cdof = L.o_cdof; k.o_cvel = L.o_cvel; k.o_qLD = L.o_qLD; k.o_vec = L.o_vec; k.o_x = L.o_x;
-  k.o_arm = L.o_arm; k.o_warm = L.o_warm; k.o_qact = L.o_qact; k.o_jlist = L.o_jlist; k.lds_floats = L.lds_floats;
-  k.o_H = k.o_Mp = k.o_anc = 0; k.solver = 1;
+  set_layout(k, L);
+  k.solver = 1;
   k.nv_scale = m->dims.nv;                          // the solver's tolerances scale with the MODEL's dof count
   k.lds_bytes_rep = L.lds_floats * 4;
   k.fac_stride = (int)m->find("h_k_factor3")->count; k.inv_stride = (int)m->find("h_k_linv")->count;
-  const int njs = 2 * RR_LANES;
-  if ((int)m->find("h_k_coljob")->count != 9 * njs || (int)m->find("h_k_rowjob")->count != 5 * njs || k.lmax > 16 || k.lmax < 1 || k.cmax > 8 || k.rmax > 8 || k.cmax < 1) return;
+  if (!solve_jobs_fit(m, "h_", 2 * RR_LANES, k)) return;
   if (k.nM > RR_LANES * 18 || k.nroot != 1) return;
-  const bool stage_ok = 2 * (k.nbody + 8) <= std::max(7 * k.nbody + 4, 6 * k.nv) && 6 * k.ncon <= std::max(7 * k.nbody + 4, 6 * k.nv) &&
-                        4 * k.ncon + k.nv <= std::min(std::min(10 * k.nbody, 6 * k.nbody), std::max(7 * k.nbody + 4, 6 * k.nv));
-  if (!stage_ok || 2 * (k.nalias + 4) > std::max(7 * k.nbody + 4, 6 * k.nv) || 2 * k.lds_bytes_rep + 128 > 64 * 1024) return;
+  if (!stage_fits(k.nbody, k.nv, k.ncon, k.nalias) || 2 * k.lds_bytes_rep + 128 > 64 * 1024) return;
   m->kd_rep = k;
-  m->pair_ok = pick_pair_kernel(m) != nullptr;
+  m->pair_ok = select(m, F_STEP, V_PAIR).kern != nullptr;
 }
 
 extern "C" int rr_model_load(const char* path, rr_model** out) {
@@ -191,10 +261,9 @@ extern "C" int rr_model_load(const char* path, rr_model** out) {
   k.nround = m->iscalar("k_nround");
   k.ninv = m->iscalar("k_linv_rows");
   if (d.nM > RR_LANES * (m->NVS == 1 ? 10 : (m->NVS == 2 ? 18 : 35))) { delete m; return fail(RR_EUNSUPPORTED, "rr_model_load: more mass-matrix entries than the kernel's register table"); }
-  { const int njs = (m->NVS >= 3 ? m->NVS + 1 : m->NVS) * RR_LANES;     // Wave::NJS job slots
-    k.lmax = m->iscalar("k_solve_lmax"); k.cmax = m->iscalar("k_solve_cmax"); k.rmax = m->iscalar("k_solve_rmax");
-    if ((int)m->find("k_coljob")->count != 9 * njs || (int)m->find("k_rowjob")->count != 5 * njs || k.lmax > 16 || k.lmax < 1 || k.cmax > 8 || k.rmax > 8 || k.cmax < 1) {
-      delete m; return fail(RR_EIO, "rr_model_load: solve job tables do not match the kernel instance (stale blob)"); } }
+  k.lmax = m->iscalar("k_solve_lmax"); k.cmax = m->iscalar("k_solve_cmax"); k.rmax = m->iscalar("k_solve_rmax");
+  if (!solve_jobs_fit(m, "", (m->NVS >= 3 ? m->NVS + 1 : m->NVS) * RR_LANES, k)) {     // Wave::NJS job slots
+    delete m; return fail(RR_EIO, "rr_model_load: solve job tables do not match the kernel instance (stale blob)"); }
   k.obs_dim = d.obs_dim; k.iterations = d.iterations; k.ls_iterations = d.ls_iterations;
   k.dt = d.timestep; k.gx = m->fscalar("opt_gravity", 0); k.gy = m->fscalar("opt_gravity", 1); k.gz = m->fscalar("opt_gravity", 2);
   k.tolerance = m->fscalar("opt_tolerance"); k.ls_tolerance = m->fscalar("opt_ls_tolerance");
@@ -276,16 +345,20 @@ struct rr_batch {
   bool has_env_params() const { return env_dof_f || env_act_f || env_con_f; }
 };
 
+// hipMalloc recorded in the batch (rr_batch_destroy frees it), filled from `host` when given
+template <typename Ptr>
+static int dev_alloc(rr_batch* b, size_t bytes, Ptr* dst, const void* host = nullptr, size_t host_bytes = 0) {
+  void* p = nullptr;
+  HIPCHK(hipMalloc(&p, bytes));
+  b->dev_allocs.push_back(p);
+  if (host_bytes) HIPCHK(hipMemcpy(p, host, host_bytes, hipMemcpyHostToDevice));
+  *dst = (Ptr)p;
+  return RR_OK;
+}
 template <typename Ptr>
 static int upload(rr_batch* b, const char* name, Ptr* dst) {
   const Entry* e = b->m->find(name);
-  void* p = nullptr;
-  size_t bytes = std::max<size_t>(e->count, 1) * 4;
-  HIPCHK(hipMalloc(&p, bytes));
-  b->dev_allocs.push_back(p);
-  if (e->count) HIPCHK(hipMemcpy(p, e->data, e->count * 4, hipMemcpyHostToDevice));
-  *dst = (Ptr)p;
-  return RR_OK;
+  return dev_alloc(b, std::max<size_t>(e->count, 1) * 4, dst, e->data, e->count * 4);
 }
 
 // Row schedules (k_factor3, k_linv): element indices -> LDS byte addresses (rr_kernel.h run_levels).  Indices below nM + 4 are cells of
@@ -310,117 +383,40 @@ static int upload_levels(rr_batch* b, const char* name, rr_gi* dst, uint32_t bas
       tc[i + 3] = q * 8u;
     }
   }
-  void* p = nullptr;
-  HIPCHK(hipMalloc(&p, t.size() * 4));
-  b->dev_allocs.push_back(p);
-  HIPCHK(hipMemcpy(p, t.data(), t.size() * 4, hipMemcpyHostToDevice));
-  *dst = (rr_gi)p;
-  return RR_OK;
+  return dev_alloc(b, t.size() * 4, dst, t.data(), t.size() * 4);
 }
 
-// Instances: production (no debug dump; fixed-dimension variant for the rodent dims), debug dump (generic dims; selected per
-// launch when rr_outputs.debug is given), cycle-stamp profile (diagnostic, rodent dims or generic 2,2,1).
-static kern_t pick_kernel(const rr_model* m, bool prof = false, bool dbg = false) {
-  const int nbs = m->NBS, nvs = m->NVS, ncs = m->NCS;
-  if (m->dyn)        // candidate-pair contacts: one production instance (generic dimensions); no debug dump, no profile build
-    return (!prof && !dbg && m->solver != 2 && nbs == 2 && nvs == 2 && ncs == 1) ? rr_step_kernel<2, 2, 1, false, false, RRDims, false, false, false, false, true> : nullptr;
-  if (prof && m->solver != 2) return (nbs == 2 && nvs == 2 && ncs == 1) ? (RRDimsRodent::matches(m->kd) ? rr_step_kernel<2, 2, 1, true, false, RRDimsRodent> : rr_step_kernel<2, 2, 1, true, false, RRDims>) : nullptr;
-  if (m->solver == 2)     // Newton: the (2,2,1) generic instances only (rr_model_set_solver_type checks)
-    return prof ? nullptr : (dbg ? rr_step_kernel<2, 2, 1, false, true, RRDims, true> : rr_step_kernel<2, 2, 1, false, false, RRDims, true>);
-  if (dbg) {
-    if (nbs == 1 && nvs == 1 && ncs == 1) return rr_step_kernel<1, 1, 1, false, true, RRDims>;
-    if (nbs == 2 && nvs == 2 && ncs == 1) return rr_step_kernel<2, 2, 1, false, true, RRDims>;
-    if (nbs == 3 && nvs == 3 && ncs == 2) return rr_step_kernel<3, 3, 2, false, true, RRDims>;
-    return nullptr;
-  }
-  if (nbs == 2 && nvs == 2 && ncs == 1 && RRDimsRodent::matches(m->kd)) return rr_step_kernel<2, 2, 1, false, false, RRDimsRodent>;   // fixed-dimension instances
-  if (nbs == 2 && nvs == 2 && ncs == 1 && RRDimsRodentNew::matches(m->kd)) return rr_step_kernel<2, 2, 1, false, false, RRDimsRodentNew>;
-  if (nbs == 1 && nvs == 1 && ncs == 1) return rr_step_kernel<1, 1, 1, false, false, RRDims>;
-  if (nbs == 2 && nvs == 2 && ncs == 1) return rr_step_kernel<2, 2, 1, false, false, RRDims>;
-  if (nbs == 3 && nvs == 3 && ncs == 2) return rr_step_kernel<3, 3, 2, false, false, RRDims>;
-  return nullptr;
-}
-
-// Multi-step instances: the single-rodent floor-contact models (fixed-dimension or generic) and the candidate-pair models (DYN, generic
-// dimensions), CG only.  None for the Newton solver, the two-wave pair instance and other slot counts.
-static kern_t pick_unroll_kernel(const rr_model* m, bool actor = false) {
-  if (m->solver == 2 || !(m->NBS == 2 && m->NVS == 2 && m->NCS == 1)) return nullptr;
-  if (m->dyn) return actor ? rr_step_kernel<2, 2, 1, false, false, RRDims, false, true, true, false, true> : rr_step_kernel<2, 2, 1, false, false, RRDims, false, true, false, false, true>;
-  if (actor) return RRDimsRodent::matches(m->kd) ? rr_step_kernel<2, 2, 1, false, false, RRDimsRodent, false, true, true>
-                    : (RRDimsRodentNew::matches(m->kd) ? rr_step_kernel<2, 2, 1, false, false, RRDimsRodentNew, false, true, true> : rr_step_kernel<2, 2, 1, false, false, RRDims, false, true, true>);
-  return RRDimsRodent::matches(m->kd) ? rr_step_kernel<2, 2, 1, false, false, RRDimsRodent, false, true>
-         : (RRDimsRodentNew::matches(m->kd) ? rr_step_kernel<2, 2, 1, false, false, RRDimsRodentNew, false, true> : rr_step_kernel<2, 2, 1, false, false, RRDims, false, true>);
-}
-// the two-wave instance of a two-tree model (one replica = the rodent_new dims); nullptr: no such instance -> generic one-wave kernel
-static kern_t pick_pair_kernel(const rr_model* m) {
-  if (m->solver == 2) return nullptr;
-  return RRDimsRodentNew::matches(m->kd_rep) ? rr_step_kernel<2, 2, 1, false, false, RRDimsRodentNew, false, false, false, true> : nullptr;
-}
-
-// Per-environment parameters (RAND instances of rr_kernel.h: rr_rand_kernel): the production CG instances of the single-rodent floor-contact
-// models -- fixed-dimension or generic (2,2,1) -- as single-step, multi-step and multi-step with the actor.  `why`: the reason when none exists.
-static bool rand_model_ok(const rr_model* m, const char** why = nullptr) {
-  const char* w = nullptr;
-  if (m->dyn) w = "models with candidate-pair contacts (DYN instances) have none";
-  else if (m->pair_ok) w = "two-tree models served by the two-wave pair instance have none";
-  else if (m->solver == 2) w = "the Newton solver's instances have none";
-  else if (!(m->NBS == 2 && m->NVS == 2 && m->NCS == 1)) w = "only the (2,2,1) slot counts have instances with per-env parameters";
-  if (why) *why = w;
-  return w == nullptr;
-}
-static kern_t pick_rand_kernel(const rr_model* m, bool unroll = false, bool actor = false) {
-  if (!rand_model_ok(m)) return nullptr;
-  const int form = actor ? 2 : (unroll ? 1 : 0);
-  if (RRDimsRodent::matches(m->kd)) { kern_t k[3] = {rr_rand_kernel<RRDimsRodent>, rr_rand_kernel<RRDimsRodent, true>, rr_rand_kernel<RRDimsRodent, true, true>}; return k[form]; }
-  if (RRDimsRodentNew::matches(m->kd)) { kern_t k[3] = {rr_rand_kernel<RRDimsRodentNew>, rr_rand_kernel<RRDimsRodentNew, true>, rr_rand_kernel<RRDimsRodentNew, true, true>}; return k[form]; }
-  kern_t k[3] = {rr_rand_kernel<RRDims>, rr_rand_kernel<RRDims, true>, rr_rand_kernel<RRDims, true, true>};
-  return k[form];
-}
-
-// Evaluation instances (rr_eval_kernel): the production CG multi-step form with the actor of the (2,2,1) slot counts, fixed-dimension,
-// generic or generic with candidate-pair contacts.  `why`: the reason when the model / solver has none.
-static kern_t pick_eval_kernel(const rr_model* m, const char** why = nullptr) {
-  const char* w = nullptr;
-  if (m->solver == 2) w = "the Newton solver has no multi-step instance";
-  else if (m->pair_ok) w = "two-tree models served by the two-wave pair instance have no multi-step instance";
-  else if (!(m->NBS == 2 && m->NVS == 2 && m->NCS == 1)) w = "only the (2,2,1) slot counts have an evaluation instance";
-  if (why) *why = w;
-  if (w) return nullptr;
-  if (m->dyn) return rr_eval_kernel<RRDims, true>;
-  return RRDimsRodent::matches(m->kd) ? rr_eval_kernel<RRDimsRodent> : (RRDimsRodentNew::matches(m->kd) ? rr_eval_kernel<RRDimsRodentNew> : rr_eval_kernel<RRDims>);
-}
+static int lds_bytes(const rr_model* m, Variant v) { return v == V_PAIR ? 2 * m->kd_rep.lds_bytes_rep + 128 : m->dims.lds_bytes; }      // of a launch of select(m, form, v)
 
 extern "C" int rr_batch_create(const rr_model* m, int32_t num_envs, int32_t device, void* stream, rr_batch** out) {
   if (!m || !out || num_envs <= 0) return fail(RR_EINVAL, "rr_batch_create: bad argument");
-  if (!pick_kernel(m)) return fail(RR_EUNSUPPORTED, "rr_batch_create: no kernel instance for this model's slot counts");
+  const Instance prod = select(m, F_STEP, V_PROD);
+  if (!prod.kern) return fail(RR_EUNSUPPORTED, std::string("rr_batch_create: ") + prod.why);
   HIPCHK(hipSetDevice(device));
-  rr_batch* b = new rr_batch();
+  std::unique_ptr<rr_batch, void (*)(rr_batch*)> guard(new rr_batch(), rr_batch_destroy);      // every early return below destroys the batch
+  rr_batch* b = guard.get();
   b->m = m; b->N = num_envs; b->device = device; b->stream = (hipStream_t)stream; b->kd = m->kd;
   int rc = 0;
-#define UP(field, name) if ((rc = upload(b, name, &b->T.field))) { rr_batch_destroy(b); return rc; }
-  UP(body_i, "k_body_i") UP(jnt_i, "k_jnt_i") UP(dof_i, "k_dof_i") UP(M_ij_k, "k_M_ij_k")
-  UP(body_anc, "k_body_anc") UP(con_chain_rows, "k_con_chain_rows") UP(coljob, "k_coljob") UP(rowjob, "k_rowjob") UP(jobown, "k_jobown") UP(con_i, "k_con_i")
-  UP(body_f, "k_body_f") UP(jnt_f, "k_jnt_f") UP(dof_f, "k_dof_f")
-  UP(act_f, "k_act_f") UP(con_f, "k_con_f") UP(root_mass, "k_root_mass")
-  UP(act_i, "k_act_i") UP(act_m_i, "k_act_m_i") UP(act_m_f, "k_act_m_f")
-#undef UP
-  {
-    const uint32_t qb = (uint32_t)m->kd.o_qLD * 4u, ab = (uint32_t)m->kd.o_xpos * 4u, nM = (uint32_t)m->dims.nM;
-    if ((rc = upload_levels(b, m->solver == 2 ? "k_factor3p" : "k_factor3", &b->T.factor3, qb, ab, nM)) || (rc = upload_levels(b, "k_linv", &b->T.linv, qb, ab, nM))) { rr_batch_destroy(b); return rc; }
-  }
+  // the model's tables; T_rep: those of one replica (blob prefix h_) -- all but the transmission tables, which only DYN instances read
+#define UP(T, prefix, field) if ((rc = upload(b, prefix "k_" #field, &T.field))) return rc;
+#define UP_REPLICA_TABLES(T, prefix)                                                                                                \
+  UP(T, prefix, body_i) UP(T, prefix, jnt_i) UP(T, prefix, dof_i) UP(T, prefix, M_ij_k) UP(T, prefix, body_anc)                     \
+  UP(T, prefix, con_chain_rows) UP(T, prefix, coljob) UP(T, prefix, rowjob) UP(T, prefix, jobown) UP(T, prefix, con_i)              \
+  UP(T, prefix, body_f) UP(T, prefix, jnt_f) UP(T, prefix, dof_f) UP(T, prefix, act_f) UP(T, prefix, con_f) UP(T, prefix, root_mass)
+  UP_REPLICA_TABLES(b->T, "")
+  UP(b->T, "", act_i) UP(b->T, "", act_m_i) UP(b->T, "", act_m_f)
+  const uint32_t qb = (uint32_t)m->kd.o_qLD * 4u, ab = (uint32_t)m->kd.o_xpos * 4u, nM = (uint32_t)m->dims.nM;
+  if ((rc = upload_levels(b, m->solver == 2 ? "k_factor3p" : "k_factor3", &b->T.factor3, qb, ab, nM)) || (rc = upload_levels(b, "k_linv", &b->T.linv, qb, ab, nM))) return rc;
   memset(&b->T_rep, 0, sizeof(b->T_rep));
   if (m->pair_ok) {      // tables of one replica; the level schedules twice (second copy addressed into the second wavefront's region)
-#define UPH(field, name) if ((rc = upload(b, "h_" name, &b->T_rep.field))) { rr_batch_destroy(b); return rc; }
-    UPH(body_i, "k_body_i") UPH(jnt_i, "k_jnt_i") UPH(dof_i, "k_dof_i") UPH(M_ij_k, "k_M_ij_k")
-    UPH(body_anc, "k_body_anc") UPH(con_chain_rows, "k_con_chain_rows") UPH(coljob, "k_coljob") UPH(rowjob, "k_rowjob") UPH(jobown, "k_jobown") UPH(con_i, "k_con_i")
-    UPH(body_f, "k_body_f") UPH(jnt_f, "k_jnt_f") UPH(dof_f, "k_dof_f")
-    UPH(act_f, "k_act_f") UPH(con_f, "k_con_f") UPH(root_mass, "k_root_mass")
-#undef UPH
+    UP_REPLICA_TABLES(b->T_rep, "h_")
     const uint32_t base = (uint32_t)m->kd_rep.o_qLD * 4u, rb = (uint32_t)m->kd_rep.lds_bytes_rep;
     const uint32_t abase = (uint32_t)m->kd_rep.o_xpos * 4u, hnM = (uint32_t)m->kd_rep.nM;
-    if ((rc = upload_levels(b, "h_k_factor3", &b->T_rep.factor3, base, abase, hnM, 2, rb)) || (rc = upload_levels(b, "h_k_linv", &b->T_rep.linv, base, abase, hnM, 2, rb))) { rr_batch_destroy(b); return rc; }
+    if ((rc = upload_levels(b, "h_k_factor3", &b->T_rep.factor3, base, abase, hnM, 2, rb)) || (rc = upload_levels(b, "h_k_linv", &b->T_rep.linv, base, abase, hnM, 2, rb))) return rc;
     b->T_rep.anc4 = b->T_rep.M_ij_k;     // unused (Newton only); a valid pointer
   }
+#undef UP_REPLICA_TABLES
+#undef UP
   {   // ancestor ids along the rows of M (Newton): byte Madr[i] + p = the p-th ancestor of dof i (p = 0: i itself)
     const Entry *an = m->find("dof_anc"), *ad = m->find("dof_ancadr"), *ma = m->find("dof_Madr");
     std::vector<unsigned char> bytes(((size_t)m->dims.nM + 3) / 4 * 4 + 4, 0);
@@ -430,49 +426,28 @@ extern "C" int rr_batch_create(const rr_model* m, int32_t num_envs, int32_t devi
         const int n = adr[i + 1] - adr[i];                 // chain root .. self
         for (int p = 0; p < n; ++p) bytes[madr[i] + p] = (unsigned char)anc[adr[i] + n - 1 - p];
       }
-    } else if (m->solver == 2) { rr_batch_destroy(b); return fail(RR_EIO, "rr_batch_create: blob lacks the ancestor tables the Newton solver needs"); }
-    void* p = nullptr;
-    HIPCHK(hipMalloc(&p, bytes.size()));
-    b->dev_allocs.push_back(p);
-    HIPCHK(hipMemcpy(p, bytes.data(), bytes.size(), hipMemcpyHostToDevice));
-    b->T.anc4 = (rr_gi)p;
+    } else if (m->solver == 2) return fail(RR_EIO, "rr_batch_create: blob lacks the ancestor tables the Newton solver needs");
+    if ((rc = dev_alloc(b, bytes.size(), &b->T.anc4, bytes.data(), bytes.size()))) return rc;
   }
-  kern_t kern = pick_kernel(m);
-  if (!m->stage_ok) { rr_batch_destroy(b); return fail(RR_EUNSUPPORTED, "rr_batch_create: 4*ncon + nv exceeds the line-search staging cells (6*nbody)"); }
-  if (m->dims.lds_bytes > 64 * 1024) { rr_batch_destroy(b); return fail(RR_EUNSUPPORTED, "rr_batch_create: per-env working set exceeds the 64 KiB of LDS one workgroup may address"); }
-  kern_t pair_kern = m->pair_ok ? pick_pair_kernel(m) : nullptr;
-  for (kern_t kk : {kern, pick_kernel(m, false, true), pick_unroll_kernel(m), pick_unroll_kernel(m, true), pick_kernel(m, true), pair_kern,
-                    pick_rand_kernel(m), pick_rand_kernel(m, true), pick_rand_kernel(m, true, true), pick_eval_kernel(m)}) {   // every instance a launch may pick
-    if (!kk) continue;
-    hipError_t e = hipFuncSetAttribute((const void*)kk, hipFuncAttributeMaxDynamicSharedMemorySize, kk == pair_kern ? 2 * m->kd_rep.lds_bytes_rep + 128 : m->dims.lds_bytes);
-    if (e != hipSuccess) { rr_batch_destroy(b); return fail(RR_EHIP, std::string("hipFuncSetAttribute: ") + hipGetErrorString(e)); }
-    // the level schedules address LDS by absolute byte address, so the dynamic segment must begin at LDS address 0: no static LDS
-    hipFuncAttributes fa;
-    e = hipFuncGetAttributes(&fa, (const void*)kk);
-    if (e != hipSuccess) { rr_batch_destroy(b); return fail(RR_EHIP, std::string("hipFuncGetAttributes: ") + hipGetErrorString(e)); }
-    if (fa.sharedSizeBytes != 0) { rr_batch_destroy(b); return fail(RR_EUNSUPPORTED, "rr_batch_create: a step-kernel instance has static LDS (the level schedules need the dynamic segment at address 0)"); }
-  }
-  if (m->dyn) {
-    void* p = nullptr;
-    hipError_t e = hipMalloc(&p, 64);
-    if (e != hipSuccess) { rr_batch_destroy(b); return fail(RR_EHIP, std::string("rr_batch_create: hipMalloc: ") + hipGetErrorString(e)); }
-    b->dev_allocs.push_back(p);
-    e = hipMemset(p, 0, 64);
-    if (e != hipSuccess) { rr_batch_destroy(b); return fail(RR_EHIP, std::string("rr_batch_create: hipMemset: ") + hipGetErrorString(e)); }
-    b->dyn_overflow = (unsigned*)p;
-  }
-  {
-    const char* pace = getenv("RR_PACE");
-    if (!(pace && pace[0] == '0')) {
-      void* p = nullptr;
-      HIPCHK(hipMalloc(&p, 64));
-      b->dev_allocs.push_back(p);
-      b->progress = (unsigned*)p;
+  if (!m->stage_ok) return fail(RR_EUNSUPPORTED, "rr_batch_create: 4*ncon + nv exceeds the line-search staging cells (6*nbody)");
+  if (m->dims.lds_bytes > 64 * 1024) return fail(RR_EUNSUPPORTED, "rr_batch_create: per-env working set exceeds the 64 KiB of LDS one workgroup may address");
+  for (int f = 0; f < N_FORMS; ++f)
+    for (int v = 0; v < N_VARIANTS; ++v) {      // every instance a launch may pick
+      const kern_t kk = select(m, (Form)f, (Variant)v).kern;
+      if (!kk) continue;
+      HIPCHK(hipFuncSetAttribute((const void*)kk, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes(m, (Variant)v)));
+      // the level schedules address LDS by absolute byte address, so the dynamic segment must begin at LDS address 0: no static LDS
+      hipFuncAttributes fa;
+      HIPCHK(hipFuncGetAttributes(&fa, (const void*)kk));
+      if (fa.sharedSizeBytes != 0) return fail(RR_EUNSUPPORTED, "rr_batch_create: a step-kernel instance has static LDS (the level schedules need the dynamic segment at address 0)");
     }
-  }
+  if (m->dyn && (rc = dev_alloc(b, 64, &b->dyn_overflow))) return rc;
+  if (m->dyn) HIPCHK(hipMemset(b->dyn_overflow, 0, 64));
+  const char* pace = getenv("RR_PACE");
+  if (!(pace && pace[0] == '0') && (rc = dev_alloc(b, 64, &b->progress))) return rc;
   m->live_batches.fetch_add(1);
   b->counted = true;
-  *out = b;
+  *out = guard.release();
   return RR_OK;
 }
 
@@ -509,106 +484,140 @@ static int collect_timing(rr_batch* b, bool all = true) {
   return RR_OK;
 }
 
-static int launch(rr_batch* b, const rr_state* st, const float* ctrl, int n_frames, const rr_env_io* env, const rr_outputs* out, int mode,
-                  const rr_state* st_in = nullptr, const int32_t* cur_frame_in = nullptr, const rr_unroll_io* un = nullptr, int unroll_T = 0,
-                  const rr_actor_io* ac = nullptr, const rr_eval_io* ev = nullptr) {
-  if (!b || !st || !st->qpos || !st->qvel || !st->act || !st->qacc_warmstart) return fail(RR_EINVAL, "launch: null state pointer");
+// One launch of the step kernel as an ABI entry point describes it (fields named at the call: designated initialisers, in this order).
+struct Launch {
+  int mode = 1;                                     // 0 = forward pass only, 1 = step, 2 = reset
+  const rr_state *st = nullptr, *st_in = nullptr;   // the state written; the one read (null: st)
+  const float* ctrl = nullptr;
+  int n_frames = 1;
+  const rr_env_io* env = nullptr;
+  const int32_t* cur_frame_in = nullptr;            // null: env->cur_frame is read and written
+  const rr_outputs* out = nullptr;
+  const rr_unroll_io* un = nullptr;                 // multi-step forms: the wrappers' state, unroll_T steps
+  int unroll_T = 0;
+  const rr_actor_io* ac = nullptr;                  // ... with the actor
+  const rr_eval_io* ev = nullptr;                   // ... as an evaluation
+};
+static int check_wrap(const char* who, const rr_unroll_io* w, const char* note = "") {
+  if (!w || !w->first.qpos || !w->first.qvel || !w->first.act || !w->first.qacc_warmstart || !w->first_obs || !w->prev_done || !w->steps_in ||
+      !w->steps_out || !w->truncation_out)
+    return fail(RR_EINVAL, std::string(who) + ": null wrapper pointer" + note);
+  return RR_OK;
+}
+// traj: the form that samples and records transitions (noise, actions and the trajectory arrays are required)
+static int check_actor(const char* who, const rr_actor_io* a, bool traj) {
+  if (!a->obs_in || !a->w0 || !a->b0 || !a->head_wt || !a->head_b || (a->mean == nullptr) != (a->std == nullptr) ||
+      (traj && (!a->noise || !a->actions_out || !a->traj_obs || !a->traj_raw_action || !a->traj_log_prob || !a->traj_reward || !a->traj_discount ||
+                !a->traj_truncation)))
+    return fail(RR_EINVAL, std::string(who) + ": null actor pointer");
+  for (int l = 1; l < a->nhidden && l < 5; ++l)
+    if (!a->hidden_wt[l - 1] || !a->hidden_b[l - 1]) return fail(RR_EINVAL, std::string(who) + ": null hidden layer");
+  return RR_OK;
+}
+// What the in-kernel actor cannot serve, or null.  ac null: the limits on the model alone (rr_batch_eval_supported)
+static const char* actor_limit(const rr_model* m, const rr_actor_io* ac) {
+  if (m->dims.obs_dim > 1280) return "rr_env_unroll_policy: observation wider than 1280";
+  if (ac && (ac->nhidden < 1 || ac->nhidden > 5)) return "rr_env_unroll_policy: 1 .. 5 hidden layers";
+  if (m->dims.nu > 64) return "rr_env_unroll_policy: more than 64 actions (the in-kernel actor's head is at most 2 x 64 logits)";
+  return nullptr;
+}
+
+// launch() step 1: RRIO from the state, the env io and the outputs
+static int fill_io(const Launch& L, RRIO& io) {
+  const rr_state *st = L.st, *st_in = L.st_in;
+  if (!st || !st->qpos || !st->qvel || !st->act || !st->qacc_warmstart) return fail(RR_EINVAL, "launch: null state pointer");
   if (st_in && (!st_in->qpos || !st_in->qvel || !st_in->act || !st_in->qacc_warmstart)) return fail(RR_EINVAL, "launch: null input state pointer");
-  if ((mode & 1) && ((!ctrl && !ev) || n_frames <= 0)) return fail(RR_EINVAL, "launch: step needs ctrl and n_frames > 0");      // ev: the batch's own action rows
-  RRIO io;
+  if ((L.mode & 1) && ((!L.ctrl && !L.ev) || L.n_frames <= 0)) return fail(RR_EINVAL, "launch: step needs ctrl and n_frames > 0");      // ev: the batch's own action rows
   memset(&io, 0, sizeof(io));
-  io.qpos = st->qpos; io.qvel = st->qvel; io.act = st->act; io.warm = st->qacc_warmstart; io.ctrl = ctrl;
+  io.qpos = st->qpos; io.qvel = st->qvel; io.act = st->act; io.warm = st->qacc_warmstart; io.ctrl = L.ctrl;
   const rr_state* si = st_in ? st_in : st;
   io.qpos_in = si->qpos; io.qvel_in = si->qvel; io.act_in = si->act; io.warm_in = si->qacc_warmstart;
-  if (out) {
+  if (const rr_outputs* out = L.out) {
     io.o_cinert = out->cinert; io.o_cvel = out->cvel; io.o_qfrc_actuator = out->qfrc_actuator; io.o_xpos = out->xpos;
     io.o_xmat = out->xmat; io.o_com = out->subtree_com; io.dbg = out->debug;
     io.o_cdist = out->contact_dist; io.o_cpos = out->contact_pos; io.o_cframe = out->contact_frame;
   }
-  if (env) {
+  if (const rr_env_io* env = L.env) {
     if (!env->obs || !env->track_pos || !env->cur_frame || env->track_len <= 0) return fail(RR_EINVAL, "launch: env io needs obs, track_pos, cur_frame");
-    if ((mode & 1) && (!env->reward || !env->done || !env->metrics)) return fail(RR_EINVAL, "launch: env step needs reward, done, metrics");
+    if ((L.mode & 1) && (!env->reward || !env->done || !env->metrics)) return fail(RR_EINVAL, "launch: env step needs reward, done, metrics");
     io.track_pos = env->track_pos; io.track_len = env->track_len; io.cur_frame = env->cur_frame; io.obs = env->obs;
-    io.cur_frame_in = cur_frame_in ? cur_frame_in : env->cur_frame;
+    io.cur_frame_in = L.cur_frame_in ? L.cur_frame_in : env->cur_frame;
     io.reward = env->reward; io.done = env->done; io.metrics = env->metrics;
     io.healthy_reward = env->healthy_reward; io.ctrl_cost_weight = env->ctrl_cost_weight; io.z_min = env->healthy_z_min;
     io.z_max = env->healthy_z_max; io.terminate_when_unhealthy = env->terminate_when_unhealthy;
   }
-  io.mode = mode;
-  HIPCHK(hipSetDevice(b->device));
-  kern_t kern = pick_kernel(b->m, b->prof != nullptr, io.dbg != nullptr || io.o_cdist || io.o_cpos || io.o_cframe);
-  if (un) {      // multi-step rollout: the UNROLL instance, no diagnostics
-    if (b->prof || io.dbg || io.o_cdist || io.o_cpos || io.o_cframe || out) return fail(RR_EUNSUPPORTED, "rr_env_unroll: no diagnostic outputs in a multi-step rollout");
-    if (ev) {      // evaluation form: its own entry, shared tables only
-      const char* why = nullptr;
-      kern = pick_eval_kernel(b->m, &why);
-      if (!kern) return fail(RR_EUNSUPPORTED, std::string("rr_env_unroll_eval: ") + why);
-      if (b->has_env_params()) return fail(RR_EUNSUPPORTED, "rr_env_unroll_eval: no evaluation instance reads per-env parameters (this batch carries some)");
-    } else kern = pick_unroll_kernel(b->m, ac != nullptr);
-    if (!kern) return fail(RR_EUNSUPPORTED, "rr_env_unroll: no multi-step kernel instance for this model / solver");
-    if (ac) {
-      if (b->m->dims.obs_dim > 1280) return fail(RR_EUNSUPPORTED, "rr_env_unroll_policy: observation wider than 1280");
-      if (ac->nhidden < 1 || ac->nhidden > 5) return fail(RR_EUNSUPPORTED, "rr_env_unroll_policy: 1 .. 5 hidden layers");
-      if (b->m->dims.nu > 64) return fail(RR_EUNSUPPORTED, "rr_env_unroll_policy: more than 64 actions (the in-kernel actor's head is at most 2 x 64 logits)");
-      io.a_obs_in = ac->obs_in; io.a_mean = ac->mean; io.a_std = ac->std; io.a_W0 = ac->w0; io.a_b0 = ac->b0;
-      for (int l = 1; l < ac->nhidden; ++l) { io.a_Wt[l - 1] = ac->hidden_wt[l - 1]; io.a_b[l - 1] = ac->hidden_b[l - 1]; }
-      io.a_Wth = ac->head_wt; io.a_bh = ac->head_b; io.a_noise = ac->noise; io.a_actions = ac->actions_out; io.ctrl = ac->actions_out;
-      io.t_obs = ac->traj_obs; io.t_raw = ac->traj_raw_action; io.t_logp = ac->traj_log_prob; io.t_reward = ac->traj_reward;
-      io.t_discount = ac->traj_discount; io.t_trunc = ac->traj_truncation; io.a_min_std = ac->min_std; io.a_nh = ac->nhidden;
-      io.a_seg = ac->segment_length > 0 ? ac->segment_length : unroll_T;
-      if (unroll_T % io.a_seg) return fail(RR_EINVAL, "rr_env_unroll_policy: num_steps must be a multiple of segment_length");
-      io.obs = ac->traj_obs;
-      if (ev) {
-        io.t_obs = io.obs = ev->obs_ring; io.e_metrics = ev->eval_metrics; io.e_qpos_out = ev->qpos_out; io.a_seg = unroll_T;
-        io.a_pad = (ev->raw_env ? RR_EVAL_RAW : 0) | (ac->actions_out ? RR_EVAL_ACTIONS : 0);
-        if (!ac->actions_out) {
-          if (!b->eval_actions) HIPCHK(hipMalloc((void**)&b->eval_actions, (size_t)b->N * b->m->dims.nu * sizeof(float)));
-          io.a_actions = b->eval_actions; io.ctrl = b->eval_actions;
-        }
+  io.mode = L.mode;
+  return RR_OK;
+}
+
+// launch() step 3: the fields of the multi-step forms -- wrappers' state, actor, evaluation, pacing
+static int fill_unroll(rr_batch* b, const Launch& L, RRIO& io) {
+  if (const rr_actor_io* ac = L.ac) {
+    if (const char* limit = actor_limit(b->m, ac)) return fail(RR_EUNSUPPORTED, limit);
+    io.a_obs_in = ac->obs_in; io.a_mean = ac->mean; io.a_std = ac->std; io.a_W0 = ac->w0; io.a_b0 = ac->b0;
+    for (int l = 1; l < ac->nhidden; ++l) { io.a_Wt[l - 1] = ac->hidden_wt[l - 1]; io.a_b[l - 1] = ac->hidden_b[l - 1]; }
+    io.a_Wth = ac->head_wt; io.a_bh = ac->head_b; io.a_noise = ac->noise; io.a_actions = ac->actions_out; io.ctrl = ac->actions_out;
+    io.t_obs = ac->traj_obs; io.t_raw = ac->traj_raw_action; io.t_logp = ac->traj_log_prob; io.t_reward = ac->traj_reward;
+    io.t_discount = ac->traj_discount; io.t_trunc = ac->traj_truncation; io.a_min_std = ac->min_std; io.a_nh = ac->nhidden;
+    io.a_seg = ac->segment_length > 0 ? ac->segment_length : L.unroll_T;
+    if (L.unroll_T % io.a_seg) return fail(RR_EINVAL, "rr_env_unroll_policy: num_steps must be a multiple of segment_length");
+    io.obs = ac->traj_obs;
+    if (const rr_eval_io* ev = L.ev) {
+      io.t_obs = io.obs = ev->obs_ring; io.e_metrics = ev->eval_metrics; io.e_qpos_out = ev->qpos_out; io.a_seg = L.unroll_T;
+      io.a_pad = (ev->raw_env ? RR_EVAL_RAW : 0) | (ac->actions_out ? RR_EVAL_ACTIONS : 0);
+      if (!ac->actions_out) {
+        if (!b->eval_actions) HIPCHK(hipMalloc((void**)&b->eval_actions, (size_t)b->N * b->m->dims.nu * sizeof(float)));
+        io.a_actions = b->eval_actions; io.ctrl = b->eval_actions;
       }
     }
-    io.first_qpos = un->first.qpos; io.first_qvel = un->first.qvel; io.first_act = un->first.act; io.first_warm = un->first.qacc_warmstart;
-    io.first_obs = un->first_obs; io.prev_done = un->prev_done; io.steps_in = un->steps_in; io.steps_out = un->steps_out;
-    io.trunc_out = un->truncation_out; io.episode_length = un->episode_length; io.unroll_T = unroll_T;
-    if (b->progress && unroll_T > 1) {
-      HIPCHK(hipMemsetAsync(b->progress, 0, 4, b->stream));
-      io.progress = b->progress;
-      static const struct Pace { float t[3]; int mode; } pace = [] {        // RR_PACE_T="t1,t2,t3", RR_PACE_MODE: tuning switches (tools/)
-        Pace p = {{0.3f, 0.6f, 1.0f}, 0};
-        if (const char* e = getenv("RR_PACE_T")) sscanf(e, "%f,%f,%f", &p.t[0], &p.t[1], &p.t[2]);
-        if (const char* e = getenv("RR_PACE_MODE")) p.mode = atoi(e);
-        return p;
-      }();
-      io.pace_t1 = pace.t[0]; io.pace_t2 = pace.t[1]; io.pace_t3 = pace.t[2]; io.pace_mode = pace.mode;
-    }
   }
-  if (!kern) return fail(RR_EUNSUPPORTED, "launch: no diagnostic kernel instance for this model");
-  if (b->has_env_params()) {      // per-env parameters: the RAND instance of the same launch form; production instances only
-    if (io.dbg) return fail(RR_EUNSUPPORTED, "launch: no debug dump on a batch with per-env parameters (the debug instance reads the model's shared tables)");
-    if (io.o_cdist || io.o_cpos || io.o_cframe) return fail(RR_EUNSUPPORTED, "launch: no contact-geometry outputs on a batch with per-env parameters (they are served by the debug instance)");
-    if (b->prof) return fail(RR_EUNSUPPORTED, "launch: no profile build on a batch with per-env parameters");
-    kern = pick_rand_kernel(b->m, un != nullptr, ac != nullptr);
-    if (!kern) return fail(RR_EUNSUPPORTED, "launch: no kernel instance with per-env parameters for this model / solver");
-    io.env_dof_f = b->env_dof_f; io.env_act_f = b->env_act_f; io.env_con_f = b->env_con_f;
+  io.first_qpos = L.un->first.qpos; io.first_qvel = L.un->first.qvel; io.first_act = L.un->first.act; io.first_warm = L.un->first.qacc_warmstart;
+  io.first_obs = L.un->first_obs; io.prev_done = L.un->prev_done; io.steps_in = L.un->steps_in; io.steps_out = L.un->steps_out;
+  io.trunc_out = L.un->truncation_out; io.episode_length = L.un->episode_length; io.unroll_T = L.unroll_T;
+  if (b->progress && L.unroll_T > 1) {
+    HIPCHK(hipMemsetAsync(b->progress, 0, 4, b->stream));
+    io.progress = b->progress;
+    static const struct Pace { float t[3]; int mode; } pace = [] {        // RR_PACE_T="t1,t2,t3", RR_PACE_MODE: tuning switches (tools/)
+      Pace p = {{0.3f, 0.6f, 1.0f}, 0};
+      if (const char* e = getenv("RR_PACE_T")) sscanf(e, "%f,%f,%f", &p.t[0], &p.t[1], &p.t[2]);
+      if (const char* e = getenv("RR_PACE_MODE")) p.mode = atoi(e);
+      return p;
+    }();
+    io.pace_t1 = pace.t[0]; io.pace_t2 = pace.t[1]; io.pace_t3 = pace.t[2]; io.pace_mode = pace.mode;
   }
-  io.prof = b->prof;
-  io.env_map = b->env_map; io.cost = b->cost;
-  io.dyn_overflow = b->dyn_overflow;
-  RRDims kd = b->kd;
-  kd.iterations = b->m->kd.iterations; kd.ls_iterations = b->m->kd.ls_iterations;
+  return RR_OK;
+}
+
+static int launch(rr_batch* b, const Launch& L) {
+  if (!b) return fail(RR_EINVAL, "launch: null state pointer");
+  RRIO io;
+  int rc = fill_io(L, io);
+  if (rc) return rc;
+  HIPCHK(hipSetDevice(b->device));
+  // step 2: the instance that serves the launch on this batch, or the refusal
+  const rr_model* m = b->m;
+  const bool geom = io.o_cdist || io.o_cpos || io.o_cframe, params = b->has_env_params();
+  // per-env parameters: the RAND instance of the same launch form; production instances only (a batch takes them only where those exist)
+  if (params && io.dbg) return fail(RR_EUNSUPPORTED, "launch: no debug dump on a batch with per-env parameters (the debug instance reads the model's shared tables)");
+  if (params && geom) return fail(RR_EUNSUPPORTED, "launch: no contact-geometry outputs on a batch with per-env parameters (they are served by the debug instance)");
+  if (params && b->prof) return fail(RR_EUNSUPPORTED, "launch: no profile build on a batch with per-env parameters");
+  Variant v = b->prof ? V_PROFILE : ((io.dbg || geom) ? V_DEBUG : (params ? V_RAND : V_PROD));
   // two-tree model, physics only, no diagnostics: one wavefront per replica (rr_kernel.h PAIR)
-  const bool pair = b->m->pair_ok && !env && !out && !un && !b->prof && !b->env_map && !b->cost && b->m->solver != 2 && !b->has_env_params();
-  if (pair) {
-    kern = pick_pair_kernel(b->m);
-    kd = b->m->kd_rep;
-    kd.iterations = b->m->kd.iterations; kd.ls_iterations = b->m->kd.ls_iterations;
-  }
+  const bool pair = m->pair_ok && v == V_PROD && !L.env && !L.out && !L.un && !b->env_map && !b->cost && m->solver != 2;
+  if (pair) v = V_PAIR;
+  const Instance in = select(m, L.ev ? F_EVAL : (L.ac ? F_ACTOR : (L.un ? F_UNROLL : F_STEP)), v);
+  if (!in.kern) return fail(RR_EUNSUPPORTED, std::string(L.un ? "" : "launch: ") + in.why);
+  if (L.un && (rc = fill_unroll(b, L, io))) return rc;
+  io.env_dof_f = b->env_dof_f; io.env_act_f = b->env_act_f; io.env_con_f = b->env_con_f;      // null without per-env parameters
+  io.prof = b->prof; io.env_map = b->env_map; io.cost = b->cost; io.dyn_overflow = b->dyn_overflow;
+  // step 4: the launch itself, between the event pair of the timing ring
+  RRDims kd = pair ? m->kd_rep : b->kd;
+  kd.iterations = m->kd.iterations; kd.ls_iterations = m->kd.ls_iterations;
   if (b->timing) {
-    if (b->npending == RR_TIMING_RING) { int rc = collect_timing(b, false); if (rc) return rc; }
+    if (b->npending == RR_TIMING_RING && (rc = collect_timing(b, false))) return rc;
     HIPCHK(hipEventRecord(b->ev0[(b->ring_head + b->npending) % RR_TIMING_RING], b->stream));
   }
-  if (pair) hipLaunchKernelGGL(kern, dim3(b->N), dim3(2 * RR_LANES), (size_t)(2 * kd.lds_bytes_rep + 128), b->stream, kd, b->T_rep, io, b->N, n_frames);
-  else hipLaunchKernelGGL(kern, dim3(b->N), dim3(RR_LANES), (size_t)b->m->dims.lds_bytes, b->stream, kd, b->T, io, b->N, n_frames);
+  hipLaunchKernelGGL(in.kern, dim3(b->N), dim3((pair ? 2 : 1) * RR_LANES), (size_t)lds_bytes(m, v), b->stream, kd, pair ? b->T_rep : b->T, io, b->N, L.n_frames);
   HIPCHK(hipGetLastError());
   if (b->timing) {
     HIPCHK(hipEventRecord(b->ev1[(b->ring_head + b->npending) % RR_TIMING_RING], b->stream));
@@ -619,13 +628,13 @@ static int launch(rr_batch* b, const rr_state* st, const float* ctrl, int n_fram
 
 extern "C" int rr_pipeline_step_to(rr_batch* b, const rr_state* in, const rr_state* outst, const float* ctrl, int32_t n_frames, const rr_outputs* out) {
   if (!in) return fail(RR_EINVAL, "rr_pipeline_step_to: null input state");
-  return launch(b, outst, ctrl, n_frames, nullptr, out, 1, in);
+  return launch(b, {.st = outst, .st_in = in, .ctrl = ctrl, .n_frames = n_frames, .out = out});
 }
 extern "C" int rr_env_step_to(rr_batch* b, const rr_state* in, const rr_state* outst, const float* action, int32_t n_frames, const rr_env_io* env,
                               const int32_t* cur_frame_in, const rr_outputs* out) {
   if (!env) return fail(RR_EINVAL, "rr_env_step_to: env io required");
   if (!in || !cur_frame_in) return fail(RR_EINVAL, "rr_env_step_to: null input state");
-  return launch(b, outst, action, n_frames, env, out, 1, in, cur_frame_in);
+  return launch(b, {.st = outst, .st_in = in, .ctrl = action, .n_frames = n_frames, .env = env, .cur_frame_in = cur_frame_in, .out = out});
 }
 extern "C" int rr_batch_contact_overflow(rr_batch* b, int64_t* events) {
   if (!b || !events) return fail(RR_EINVAL, "rr_batch_contact_overflow: null argument");
@@ -640,64 +649,53 @@ extern "C" int rr_batch_contact_overflow(rr_batch* b, int64_t* events) {
 }
 extern "C" int rr_batch_unroll_supported(const rr_batch* b, int32_t with_actor) {
   if (!b) return fail(RR_EINVAL, "rr_batch_unroll_supported: null batch");
-  return pick_unroll_kernel(b->m, with_actor != 0) ? 1 : 0;
+  return select(b->m, with_actor ? F_ACTOR : F_UNROLL, V_PROD).kern ? 1 : 0;
 }
 extern "C" int rr_env_unroll(rr_batch* b, const rr_state* in, const rr_state* outst, const float* actions, int32_t num_steps, int32_t n_frames,
                              const rr_env_io* env, const int32_t* cur_frame_in, const rr_unroll_io* wrap) {
   if (!env || !in || !cur_frame_in || !wrap || !actions || num_steps <= 0) return fail(RR_EINVAL, "rr_env_unroll: bad argument");
-  if (!wrap->first.qpos || !wrap->first.qvel || !wrap->first.act || !wrap->first.qacc_warmstart || !wrap->first_obs || !wrap->prev_done ||
-      !wrap->steps_in || !wrap->steps_out || !wrap->truncation_out)
-    return fail(RR_EINVAL, "rr_env_unroll: null wrapper pointer");
-  return launch(b, outst, actions, n_frames, env, nullptr, 1, in, cur_frame_in, wrap, num_steps);
+  if (int rc = check_wrap("rr_env_unroll", wrap)) return rc;
+  return launch(b, {.st = outst, .st_in = in, .ctrl = actions, .n_frames = n_frames, .env = env, .cur_frame_in = cur_frame_in, .un = wrap, .unroll_T = num_steps});
 }
 extern "C" int rr_env_unroll_policy(rr_batch* b, const rr_state* in, const rr_state* outst, int32_t num_steps, int32_t n_frames, const rr_env_io* env,
                                     const int32_t* cur_frame_in, const rr_unroll_io* wrap, const rr_actor_io* actor) {
   if (!env || !in || !cur_frame_in || !wrap || !actor || num_steps <= 0) return fail(RR_EINVAL, "rr_env_unroll_policy: bad argument");
-  if (!wrap->first.qpos || !wrap->first.qvel || !wrap->first.act || !wrap->first.qacc_warmstart || !wrap->first_obs || !wrap->prev_done ||
-      !wrap->steps_in || !wrap->steps_out || !wrap->truncation_out)
-    return fail(RR_EINVAL, "rr_env_unroll_policy: null wrapper pointer");
-  if (!actor->obs_in || !actor->w0 || !actor->b0 || !actor->head_wt || !actor->head_b || !actor->noise || !actor->actions_out || !actor->traj_obs ||
-      !actor->traj_raw_action || !actor->traj_log_prob || !actor->traj_reward || !actor->traj_discount || !actor->traj_truncation ||
-      (actor->mean == nullptr) != (actor->std == nullptr))
-    return fail(RR_EINVAL, "rr_env_unroll_policy: null actor pointer");
-  for (int l = 1; l < actor->nhidden && l < 5; ++l)
-    if (!actor->hidden_wt[l - 1] || !actor->hidden_b[l - 1]) return fail(RR_EINVAL, "rr_env_unroll_policy: null hidden layer");
+  int rc = check_wrap("rr_env_unroll_policy", wrap);
+  if (rc || (rc = check_actor("rr_env_unroll_policy", actor, true))) return rc;
   rr_env_io e = *env;
   e.obs = actor->traj_obs;                   // the observations of the launch go to the trajectory
-  return launch(b, outst, actor->actions_out, n_frames, &e, nullptr, 1, in, cur_frame_in, wrap, num_steps, actor);
+  return launch(b, {.st = outst, .st_in = in, .ctrl = actor->actions_out, .n_frames = n_frames, .env = &e, .cur_frame_in = cur_frame_in, .un = wrap,
+                    .unroll_T = num_steps, .ac = actor});
 }
 extern "C" int rr_batch_eval_supported(const rr_batch* b) {
   if (!b) return fail(RR_EINVAL, "rr_batch_eval_supported: null batch");
-  return (pick_eval_kernel(b->m) && !b->has_env_params() && !b->prof && b->m->dims.obs_dim <= 1280 && b->m->dims.nu <= 64) ? 1 : 0;
+  const Variant v = b->prof ? V_PROFILE : (b->has_env_params() ? V_RAND : V_PROD);
+  return (select(b->m, F_EVAL, v).kern && !actor_limit(b->m, nullptr)) ? 1 : 0;
 }
 extern "C" int rr_env_unroll_eval(rr_batch* b, const rr_state* in, const rr_state* outst, int32_t num_steps, int32_t n_frames, const rr_env_io* env,
                                   const int32_t* cur_frame_in, const rr_unroll_io* wrap, const rr_actor_io* actor, const rr_eval_io* ev) {
   if (!env || !in || !cur_frame_in || !actor || !ev || num_steps <= 0) return fail(RR_EINVAL, "rr_env_unroll_eval: bad argument");
   if (!ev->obs_ring) return fail(RR_EINVAL, "rr_env_unroll_eval: null observation ring");
-  if (!ev->raw_env && (!wrap || !wrap->first.qpos || !wrap->first.qvel || !wrap->first.act || !wrap->first.qacc_warmstart || !wrap->first_obs || !wrap->prev_done ||
-                       !wrap->steps_in || !wrap->steps_out || !wrap->truncation_out))
-    return fail(RR_EINVAL, "rr_env_unroll_eval: null wrapper pointer (only the raw form runs without the wrappers' state)");
-  if (!actor->obs_in || !actor->w0 || !actor->b0 || !actor->head_wt || !actor->head_b || (actor->mean == nullptr) != (actor->std == nullptr))
-    return fail(RR_EINVAL, "rr_env_unroll_eval: null actor pointer");
-  for (int l = 1; l < actor->nhidden && l < 5; ++l)
-    if (!actor->hidden_wt[l - 1] || !actor->hidden_b[l - 1]) return fail(RR_EINVAL, "rr_env_unroll_eval: null hidden layer");
+  int rc = ev->raw_env ? RR_OK : check_wrap("rr_env_unroll_eval", wrap, " (only the raw form runs without the wrappers' state)");
+  if (rc || (rc = check_actor("rr_env_unroll_eval", actor, false))) return rc;
   rr_unroll_io none;
   memset(&none, 0, sizeof(none));
   rr_env_io e = *env;
   e.obs = ev->obs_ring;                      // the observations of the launch live in the ring
-  return launch(b, outst, actor->actions_out, n_frames, &e, nullptr, 1, in, cur_frame_in, ev->raw_env ? &none : wrap, num_steps, actor, ev);
+  return launch(b, {.st = outst, .st_in = in, .ctrl = actor->actions_out, .n_frames = n_frames, .env = &e, .cur_frame_in = cur_frame_in,
+                    .un = ev->raw_env ? &none : wrap, .unroll_T = num_steps, .ac = actor, .ev = ev});
 }
-extern "C" int rr_pipeline_init(rr_batch* b, const rr_state* st, const rr_outputs* out) { return launch(b, st, nullptr, 1, nullptr, out, 0); }
+extern "C" int rr_pipeline_init(rr_batch* b, const rr_state* st, const rr_outputs* out) { return launch(b, {.mode = 0, .st = st, .out = out}); }
 extern "C" int rr_pipeline_step(rr_batch* b, const rr_state* st, const float* ctrl, int32_t n_frames, const rr_outputs* out) {
-  return launch(b, st, ctrl, n_frames, nullptr, out, 1);
+  return launch(b, {.st = st, .ctrl = ctrl, .n_frames = n_frames, .out = out});
 }
 extern "C" int rr_env_step(rr_batch* b, const rr_state* st, const float* action, int32_t n_frames, const rr_env_io* env, const rr_outputs* out) {
   if (!env) return fail(RR_EINVAL, "rr_env_step: env io required");
-  return launch(b, st, action, n_frames, env, out, 1);
+  return launch(b, {.st = st, .ctrl = action, .n_frames = n_frames, .env = env, .out = out});
 }
 extern "C" int rr_env_reset(rr_batch* b, const rr_state* st, const rr_env_io* env, const rr_outputs* out) {
   if (!env) return fail(RR_EINVAL, "rr_env_reset: env io required");
-  return launch(b, st, nullptr, 1, env, out, 2);
+  return launch(b, {.mode = 2, .st = st, .env = env, .out = out});
 }
 
 // ------------------------------------------------------------------------------------------ PPO: GAE
@@ -1126,6 +1124,7 @@ extern "C" int rr_obs_moments(const float* obs, int64_t nseq, int32_t Tp1, int32
   mom_plan(A.nrows, &A.rows_per_block, &A.nblk);
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(rr_obs_moments_kernel, dim3(A.nblk), dim3(256), 0, st, A);
+  HIPCHK(hipGetLastError());
   hipLaunchKernelGGL(rr_obs_moments_reduce_kernel, dim3((2 * K + 255) / 256), dim3(256), 0, st, A);
   HIPCHK(hipGetLastError());
   return RR_OK;
@@ -1189,11 +1188,9 @@ extern "C" int rr_debug_layout(const rr_batch* b, const char*** names, const int
 extern "C" int rr_batch_set_profile(rr_batch* b, uint64_t* dev_cycles) {
   if (!b) return fail(RR_EINVAL, "rr_batch_set_profile: null batch");
   if (dev_cycles) {
-    kern_t kern = pick_kernel(b->m, true);
-    if (!kern) return fail(RR_EUNSUPPORTED, "rr_batch_set_profile: no diagnostic kernel instance for this model");
+    const Instance in = select(b->m, F_STEP, V_PROFILE);      // rr_batch_create has set its LDS attribute
+    if (!in.kern) return fail(RR_EUNSUPPORTED, std::string("rr_batch_set_profile: ") + in.why);
     if (b->has_env_params()) return fail(RR_EUNSUPPORTED, "rr_batch_set_profile: no profile build on a batch with per-env parameters");
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, b->m->dims.lds_bytes);
-    if (e != hipSuccess) return fail(RR_EHIP, std::string("hipFuncSetAttribute: ") + hipGetErrorString(e));
   }
   b->prof = (unsigned long long*)dev_cycles;
   return RR_OK;
@@ -1201,15 +1198,15 @@ extern "C" int rr_batch_set_profile(rr_batch* b, uint64_t* dev_cycles) {
 
 extern "C" int rr_batch_env_params_supported(const rr_batch* b) {
   if (!b) return fail(RR_EINVAL, "rr_batch_env_params_supported: null batch");
-  return rand_model_ok(b->m) ? 1 : 0;
+  return select(b->m, F_STEP, V_RAND).kern ? 1 : 0;
 }
 extern "C" int rr_batch_set_env_params(rr_batch* b, const rr_env_params* p) {
   if (!b) return fail(RR_EINVAL, "rr_batch_set_env_params: null batch");
   const rr_dims& d = b->m->dims;
   const bool any = p && (p->dof_f || p->act_f || p->con_f);
   if (any) {
-    const char* why = nullptr;
-    if (!rand_model_ok(b->m, &why)) return fail(RR_EUNSUPPORTED, std::string("rr_batch_set_env_params: no kernel instance with per-env parameters: ") + why);
+    const Instance in = select(b->m, F_STEP, V_RAND);
+    if (!in.kern) return fail(RR_EUNSUPPORTED, std::string("rr_batch_set_env_params: no kernel instance with per-env parameters: ") + in.why);
     if (b->prof) return fail(RR_EUNSUPPORTED, "rr_batch_set_env_params: no profile build on a batch with per-env parameters (rr_batch_set_profile is on)");
     if (p->num_envs != b->N) return fail(RR_EINVAL, "rr_batch_set_env_params: num_envs differs from the batch's");
     if ((p->dof_f && p->dof_rows != d.nv) || (p->act_f && p->act_rows != d.nu) || (p->con_f && p->con_rows != d.ncon))

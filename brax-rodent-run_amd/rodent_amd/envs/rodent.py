@@ -112,6 +112,33 @@ class Rodent(PipelineEnv):
         metrics = {"pos_reward": zero, "reward_quadctrl": zero.clone(), "reward_alive": zero.clone()}
         return State(PipelineState(**st, **out), obs, zero.clone(), zero.clone(), metrics, {"cur_frame": cur_frame})
 
+    def _launch_buffers(self, state: State, episode_length: Optional[float] = None):
+        """What a step launch reads and writes: (st_in, st_out, env-io outputs dict(cur_frame, reward, done, metrics), wrap) -- `wrap` the
+        Episode + AutoReset wrappers' state of a multi-step launch (`hip.Batch._unroll_io`), None without `episode_length`.  The previous
+        state is left untouched (no copies)."""
+        N, dev = self.num_envs, self.device
+        ps, info = state.pipeline_state, state.info
+        fields = lambda p: dict(qpos=p.qpos, qvel=p.qvel, act=p.act, qacc_warmstart=p.qacc_warmstart)
+        st_in = fields(ps)
+        st = {k: torch.empty_like(v) for k, v in st_in.items()}
+        io = dict(cur_frame=torch.empty_like(info["cur_frame"]), reward=torch.empty(N, device=dev), done=torch.empty(N, device=dev),
+                  metrics=torch.empty(N, 3, device=dev))
+        wrap = None
+        if episode_length is not None:
+            wrap = dict(first=fields(info["first_pipeline_state"]), first_obs=info["first_obs"], prev_done=state.done, steps_in=info["steps"],
+                        steps_out=torch.empty(N, device=dev), truncation_out=torch.empty(N, device=dev), episode_length=episode_length)
+        return st_in, st, io, wrap
+
+    def _next_state(self, state: State, st, io, obs, wrap=None, out=None) -> State:
+        """The State a launch on `_launch_buffers` left."""
+        info = dict(state.info)
+        info["cur_frame"] = io["cur_frame"]
+        if wrap is not None:
+            info.update(steps=wrap["steps_out"], truncation=wrap["truncation_out"])
+        m = dict(state.metrics)
+        m.update(pos_reward=io["metrics"][:, 0], reward_quadctrl=io["metrics"][:, 1], reward_alive=io["metrics"][:, 2])
+        return state.replace(pipeline_state=PipelineState(**st, **(out or {})), obs=obs, reward=io["reward"], done=io["done"], metrics=m, info=info)
+
     def unroll_wrapped(self, state: State, actions: torch.Tensor, episode_length: float) -> State:
         """`actions.shape[0]` steps with `EpisodeWrapper(episode_length)` + `AutoResetWrapper` (action_repeat 1) in ONE launch
         (`rr_env_unroll`): what `lax.scan` over the wrapped `step` is to the reference.  `state` is a state of the wrapped env
@@ -119,25 +146,12 @@ class Rodent(PipelineEnv):
         the per-step calls give.  Intermediate observations / rewards are not returned (a random-action rollout needs none)."""
         if self._pipeline_outputs or self._contact_outputs:
             raise ValueError("a multi-step rollout returns no pipeline / contact outputs: build the env without them")
-        N, dev, s = self.num_envs, self.device, self.sys
-        ps, info = state.pipeline_state, state.info
-        fps = info["first_pipeline_state"]
-        st_in = dict(qpos=ps.qpos, qvel=ps.qvel, act=ps.act, qacc_warmstart=ps.qacc_warmstart)
-        first = dict(qpos=fps.qpos, qvel=fps.qvel, act=fps.act, qacc_warmstart=fps.qacc_warmstart)
-        st = {k: torch.empty_like(v) for k, v in st_in.items()}
-        cur_frame = torch.empty_like(info["cur_frame"])
-        obs = torch.empty(N, s.obs_dim, device=dev)
-        reward, done, steps, trunc = (torch.empty(N, device=dev) for _ in range(4))
-        metrics = torch.empty(N, 3, device=dev)
-        actions = actions.to(dev, torch.float32).contiguous()
+        st_in, st, io, wrap = self._launch_buffers(state, episode_length)
+        obs = torch.empty(self.num_envs, self.sys.obs_dim, device=self.device)
+        actions = actions.to(self.device, torch.float32).contiguous()
         self._rebalance()
-        self._batch.env_unroll(st_in, st, actions, self._n_frames, self._env_io(cur_frame, obs, reward, done, metrics), info["cur_frame"],
-                               first, info["first_obs"], state.done, info["steps"], steps, trunc, episode_length)
-        ninfo = dict(info)
-        ninfo.update(cur_frame=cur_frame, steps=steps, truncation=trunc)
-        m = dict(state.metrics)
-        m.update(pos_reward=metrics[:, 0], reward_quadctrl=metrics[:, 1], reward_alive=metrics[:, 2])
-        return state.replace(pipeline_state=PipelineState(**st), obs=obs, reward=reward, done=done, metrics=m, info=ninfo)
+        self._batch.env_unroll(st_in, st, actions, self._n_frames, self._env_io(obs=obs, **io), state.info["cur_frame"], wrap)
+        return self._next_state(state, st, io, obs, wrap)
 
     def unroll_policy_wrapped(self, state: State, episode_length: float, actor: dict, noise: torch.Tensor, traj: dict, segment: int = 0) -> State:
         """`generate_unroll` in one launch (`rr_env_unroll_policy`): T = noise.shape[0] x [policy(obs) -> tanh-normal sample -> step ->
@@ -146,27 +160,15 @@ class Rodent(PipelineEnv):
         T / L trajectories ([U, N, L(+1), ...] buffers) -- a whole rollout phase in one launch.  Returns the state after the last step."""
         if self._pipeline_outputs or self._contact_outputs:
             raise ValueError("a multi-step rollout returns no pipeline / contact outputs: build the env without them")
-        N, dev, T = self.num_envs, self.device, noise.shape[0]
-        ps, info = state.pipeline_state, state.info
-        fps = info["first_pipeline_state"]
-        st_in = dict(qpos=ps.qpos, qvel=ps.qvel, act=ps.act, qacc_warmstart=ps.qacc_warmstart)
-        first = dict(qpos=fps.qpos, qvel=fps.qvel, act=fps.act, qacc_warmstart=fps.qacc_warmstart)
-        st = {k: torch.empty_like(v) for k, v in st_in.items()}
-        cur_frame = torch.empty_like(info["cur_frame"])
-        reward, done, steps, trunc = (torch.empty(N, device=dev) for _ in range(4))
-        metrics = torch.empty(N, 3, device=dev)
-        actions = torch.empty(T, N, self.action_size, device=dev)
+        N, T = self.num_envs, noise.shape[0]
+        st_in, st, io, wrap = self._launch_buffers(state, episode_length)
+        actions = torch.empty(T, N, self.action_size, device=self.device)
         obs_in = state.obs.contiguous()            # (also fills the env io's obs slot, which this entry point does not write)
-        self._batch.env_unroll_policy(st_in, st, T, self._n_frames, self._env_io(cur_frame, obs_in, reward, done, metrics), info["cur_frame"],
-                                      first, info["first_obs"], state.done, info["steps"], steps, trunc, episode_length, actor, noise, actions,
-                                      traj, obs_in, segment)
-        ninfo = dict(info)
-        ninfo.update(cur_frame=cur_frame, steps=steps, truncation=trunc)
-        m = dict(state.metrics)
-        m.update(pos_reward=metrics[:, 0], reward_quadctrl=metrics[:, 1], reward_alive=metrics[:, 2])
+        self._batch.env_unroll_policy(st_in, st, T, self._n_frames, self._env_io(obs=obs_in, **io), state.info["cur_frame"], wrap, actor, noise,
+                                      actions, traj, obs_in, segment)
         L_ = segment or T
         obs = traj["obs"].reshape(T // L_, N, L_ + 1, -1)[-1, :, L_].contiguous()
-        return state.replace(pipeline_state=PipelineState(**st), obs=obs, reward=reward, done=done, metrics=m, info=ninfo), actions
+        return self._next_state(state, st, io, obs, wrap), actions
 
     def eval_supported(self) -> bool:
         """Whether `unroll_eval` serves this env: a batch with an evaluation instance (CG solver, a model with a multi-step instance, no
@@ -185,47 +187,19 @@ class Rodent(PipelineEnv):
         refuses with the reason (RuntimeError)."""
         if self._pipeline_outputs or self._contact_outputs:
             raise ValueError("an evaluation launch returns no pipeline / contact outputs: build the env without them")
-        N, dev, s = self.num_envs, self.device, self.sys
-        ps, info = state.pipeline_state, state.info
-        st_in = dict(qpos=ps.qpos, qvel=ps.qvel, act=ps.act, qacc_warmstart=ps.qacc_warmstart)
-        st = {k: torch.empty_like(v) for k, v in st_in.items()}
-        cur_frame = torch.empty_like(info["cur_frame"])
-        reward, done = torch.empty(N, device=dev), torch.empty(N, device=dev)
-        metrics = torch.empty(N, 3, device=dev)
-        ring = torch.empty(N, 2, s.obs_dim, device=dev)
+        st_in, st, io, wrap = self._launch_buffers(state, episode_length)
+        ring = torch.empty(self.num_envs, 2, self.sys.obs_dim, device=self.device)
         obs_in = state.obs.contiguous()
-        wrap = None
-        ninfo = dict(info)
-        if episode_length is not None:
-            fps = info["first_pipeline_state"]
-            steps, trunc = torch.empty(N, device=dev), torch.empty(N, device=dev)
-            wrap = dict(first=dict(qpos=fps.qpos, qvel=fps.qvel, act=fps.act, qacc_warmstart=fps.qacc_warmstart), first_obs=info["first_obs"],
-                        prev_done=state.done, steps_in=info["steps"], steps_out=steps, truncation_out=trunc, episode_length=episode_length)
-            ninfo.update(steps=steps, truncation=trunc)
-        self._batch.env_unroll_eval(st_in, st, int(T), self._n_frames, self._env_io(cur_frame, obs_in, reward, done, metrics), info["cur_frame"], actor,
+        self._batch.env_unroll_eval(st_in, st, int(T), self._n_frames, self._env_io(obs=obs_in, **io), state.info["cur_frame"], actor,
                                     obs_in, ring, noise, actions_out, eval_metrics, qpos_out, wrap)
-        ninfo.update(cur_frame=cur_frame)
-        m = dict(state.metrics)
-        m.update(pos_reward=metrics[:, 0], reward_quadctrl=metrics[:, 1], reward_alive=metrics[:, 2])
-        return state.replace(pipeline_state=PipelineState(**st), obs=ring[:, int(T) & 1].contiguous(), reward=reward, done=done, metrics=m, info=ninfo)
+        return self._next_state(state, st, io, ring[:, int(T) & 1].contiguous(), wrap)
 
     def step(self, state: State, action: torch.Tensor) -> State:
         """Runs one timestep of the environment's dynamics."""
-        N, dev, s = self.num_envs, self.device, self.sys
-        ps = state.pipeline_state
-        st_in = dict(qpos=ps.qpos, qvel=ps.qvel, act=ps.act, qacc_warmstart=ps.qacc_warmstart)
-        st = {k: torch.empty_like(v) for k, v in st_in.items()}      # the previous state is left untouched (no copies)
+        st_in, st, io, _ = self._launch_buffers(state)
         out = self._alloc_outputs(full=False)
-        cur_frame = torch.empty_like(state.info["cur_frame"])
-        obs = torch.empty(N, s.obs_dim, device=dev)
-        reward, done = torch.empty(N, device=dev), torch.empty(N, device=dev)
-        metrics = torch.empty(N, 3, device=dev)
-        action = action.to(dev, torch.float32).contiguous()
+        obs = torch.empty(self.num_envs, self.sys.obs_dim, device=self.device)
+        action = action.to(self.device, torch.float32).contiguous()
         self._rebalance()
-        self._batch.env_step_to(st_in, st, action, self._n_frames, self._env_io(cur_frame, obs, reward, done, metrics),
-                                state.info["cur_frame"], out)
-        info = dict(state.info)
-        info["cur_frame"] = cur_frame
-        m = dict(state.metrics)
-        m.update(pos_reward=metrics[:, 0], reward_quadctrl=metrics[:, 1], reward_alive=metrics[:, 2])
-        return state.replace(pipeline_state=PipelineState(**st, **out), obs=obs, reward=reward, done=done, metrics=m, info=info)
+        self._batch.env_step_to(st_in, st, action, self._n_frames, self._env_io(obs=obs, **io), state.info["cur_frame"], out)
+        return self._next_state(state, st, io, obs, out=out)

@@ -313,49 +313,52 @@ class Batch:
     def unroll_supported(self, with_actor: bool = False) -> bool:
         return _check(lib().rr_batch_unroll_supported(self.h, int(with_actor))) == 1
 
-    def env_unroll(self, st_in, st_out, actions, n_frames: int, env, cur_frame_in, first, first_obs, prev_done, steps_in, steps_out,
-                   truncation_out, episode_length: float):
-        """`actions.shape[0]` env steps with the Episode + AutoReset wrappers in one launch (C ABI `rr_env_unroll`)."""
+    def _unroll_io(self, wrap) -> RRUnrollIO:
+        """`wrap` = dict(first, first_obs, prev_done, steps_in, steps_out, truncation_out, episode_length): the state of the Episode +
+        AutoReset wrappers that a multi-step launch reads and writes."""
+        N, K = self.N, self.dims.obs_dim
+        return RRUnrollIO(self._state(wrap["first"]), _ptr(wrap["first_obs"], numel=N * K), *(_ptr(wrap[k], numel=N) for k in
+                          ("prev_done", "steps_in", "steps_out", "truncation_out")), float(wrap["episode_length"]))
+
+    def _actor_io(self, who: str, actor: dict, obs_in, T: int, noise=None, actions_out=None, traj: Optional[dict] = None, segment: int = 0) -> RRActorIO:
+        """The in-kernel actor's block.  actor (`acting.actor_params`): mean, std (or None), w0, b0, hidden_wt / hidden_b (lists, transposed
+        32 x 32 weights), head_wt, head_b (padded to 64 columns for up to 32 actions, to 128 for 33 .. 64), min_std;  traj (the recording
+        form): obs [N, T+1, K], raw_action [N, T, A], log_prob / reward / discount / truncation [N, T] (contiguous views); with `segment`
+        = L < T: U = T / L such blocks ([U, N, L+1, K], ...), a whole rollout phase of U unrolls."""
+        N, A_, K = self.N, self.dims.nu, self.dims.obs_dim
+        HW = 64 if A_ <= 32 else 128                   # head layout: [32][64] up to 32 actions, [32][128] for 33 .. 64
+        bad = f"{who}: inconsistent shapes" if traj is not None else f"{who}: inconsistent actor shapes"
+        if actor["w0"].shape != (32, K) or actor["head_wt"].shape != (32, HW) or actor["head_b"].numel() != HW or actor["b0"].numel() != 32:
+            raise ValueError(bad)
+        if any(w.numel() != 1024 or b.numel() != 32 for w, b in zip(actor["hidden_wt"], actor["hidden_b"])):
+            raise ValueError(f"{who}: hidden layers are 32 x 32")
+        L_ = segment or T
+        if traj is not None and (noise.numel() != T * N * A_ or actions_out.numel() != T * N * A_ or traj["obs"].numel() != (T // L_) * N * (L_ + 1) * K
+                                 or traj["raw_action"].numel() != N * T * A_ or any(traj[k].numel() != N * T for k in ("log_prob", "reward", "discount", "truncation"))):
+            raise ValueError(bad)
+        hidden = lambda ts: (C.c_void_p * 4)(*([_ptr(t) for t in ts] + [None] * (4 - len(ts))))
+        names = ("obs", "raw_action", "log_prob", "reward", "discount", "truncation")
+        return RRActorIO(_ptr(obs_in, numel=N * K), _ptr(actor.get("mean"), numel=K), _ptr(actor.get("std"), numel=K), _ptr(actor["w0"]), _ptr(actor["b0"]),
+                         hidden(actor["hidden_wt"]), hidden(actor["hidden_b"]), _ptr(actor["head_wt"]), _ptr(actor["head_b"]), _ptr(noise, numel=T * N * A_),
+                         _ptr(actions_out, numel=T * N * A_), *(_ptr(traj[k]) if traj is not None else None for k in names), float(actor["min_std"]),
+                         len(actor["hidden_wt"]) + 1, int(segment))
+
+    def env_unroll(self, st_in, st_out, actions, n_frames: int, env, cur_frame_in, wrap: dict):
+        """`actions.shape[0]` env steps with the Episode + AutoReset wrappers (`wrap`: see `_unroll_io`) in one launch (C ABI `rr_env_unroll`)."""
         T = actions.shape[0]
-        for t in (first_obs, prev_done, steps_in, steps_out, truncation_out):
-            _ptr(t)
-        w = RRUnrollIO(self._state(first), first_obs.data_ptr(), prev_done.data_ptr(), steps_in.data_ptr(), steps_out.data_ptr(),
-                       truncation_out.data_ptr(), float(episode_length))
         _check(lib().rr_env_unroll(self.h, C.byref(self._state(st_in)), C.byref(self._state(st_out)),
                                    _ptr(actions, numel=T * self.N * self.dims.nu), T, int(n_frames), C.byref(self._env(env)),
-                                   _ptr(cur_frame_in, torch.int32, self.N), C.byref(w)))
+                                   _ptr(cur_frame_in, torch.int32, self.N), C.byref(self._unroll_io(wrap))))
 
-    def env_unroll_policy(self, st_in, st_out, T: int, n_frames: int, env, cur_frame_in, first, first_obs, prev_done, steps_in, steps_out,
-                          truncation_out, episode_length: float, actor: dict, noise, actions_out, traj: dict, obs_in, segment: int = 0):
-        """T x [policy -> sample -> wrapped env step] with the transitions recorded, one launch (C ABI `rr_env_unroll_policy`).
-        actor: mean, std (or None), w0, b0, hidden_wt / hidden_b (lists, transposed weights), head_wt, head_b (padded to 64 columns for
-        up to 32 actions, to 128 for 33 .. 64), min_std;
-        traj: obs [N, T+1, K], raw_action [N, T, A], log_prob / reward / discount / truncation [N, T] (contiguous views); with
-        `segment` = L < T: U = T / L such blocks ([U, N, L+1, K], ...), a whole rollout phase of U unrolls."""
-        for t in (first_obs, prev_done, steps_in, steps_out, truncation_out, noise, actions_out, obs_in, actor["w0"], actor["b0"],
-                  actor["head_wt"], actor["head_b"], *actor["hidden_wt"], *actor["hidden_b"], *traj.values()):
-            _ptr(t)
-        nh = len(actor["hidden_wt"]) + 1
-        A_, K = self.dims.nu, self.dims.obs_dim
-        L_ = segment or T
-        if T % L_:
+    def env_unroll_policy(self, st_in, st_out, T: int, n_frames: int, env, cur_frame_in, wrap: dict, actor: dict, noise, actions_out, traj: dict,
+                          obs_in, segment: int = 0):
+        """T x [policy -> sample -> wrapped env step] with the transitions recorded in `traj`, one launch (C ABI `rr_env_unroll_policy`);
+        `wrap`, `actor`, `traj`, `segment`: see `_unroll_io` / `_actor_io`."""
+        if T % (segment or T):
             raise ValueError("rr_env_unroll_policy: the number of steps must be a multiple of the segment length")
-        HW = 64 if A_ <= 32 else 128                   # head layout: [32][64] up to 32 actions, [32][128] for 33 .. 64
-        if (noise.numel() != T * self.N * A_ or actions_out.numel() != T * self.N * A_ or traj["obs"].numel() != (T // L_) * self.N * (L_ + 1) * K
-                or traj["raw_action"].numel() != self.N * T * A_ or any(traj[k].numel() != self.N * T for k in ("log_prob", "reward", "discount", "truncation"))
-                or actor["w0"].shape != (32, K) or actor["head_wt"].shape != (32, HW) or actor["head_b"].numel() != HW):
-            raise ValueError("rr_env_unroll_policy: inconsistent shapes")
-        w = RRUnrollIO(self._state(first), first_obs.data_ptr(), prev_done.data_ptr(), steps_in.data_ptr(), steps_out.data_ptr(),
-                       truncation_out.data_ptr(), float(episode_length))
-        p = lambda t: t.data_ptr() if t is not None else None
-        a = RRActorIO(obs_in.data_ptr(), p(actor.get("mean")), p(actor.get("std")), actor["w0"].data_ptr(), actor["b0"].data_ptr(),
-                      (C.c_void_p * 4)(*([t.data_ptr() for t in actor["hidden_wt"]] + [None] * (4 - nh + 1))),
-                      (C.c_void_p * 4)(*([t.data_ptr() for t in actor["hidden_b"]] + [None] * (4 - nh + 1))),
-                      actor["head_wt"].data_ptr(), actor["head_b"].data_ptr(), noise.data_ptr(), actions_out.data_ptr(), traj["obs"].data_ptr(),
-                      traj["raw_action"].data_ptr(), traj["log_prob"].data_ptr(), traj["reward"].data_ptr(), traj["discount"].data_ptr(),
-                      traj["truncation"].data_ptr(), float(actor["min_std"]), nh, int(L_))
+        a = self._actor_io("rr_env_unroll_policy", actor, obs_in, T, noise, actions_out, traj, segment or T)
         _check(lib().rr_env_unroll_policy(self.h, C.byref(self._state(st_in)), C.byref(self._state(st_out)), int(T), int(n_frames),
-                                          C.byref(self._env(env)), _ptr(cur_frame_in, torch.int32, self.N), C.byref(w), C.byref(a)))
+                                          C.byref(self._env(env)), _ptr(cur_frame_in, torch.int32, self.N), C.byref(self._unroll_io(wrap)), C.byref(a)))
 
     def eval_supported(self) -> bool:
         """Whether this batch evaluates in one launch (C ABI `rr_batch_eval_supported`): CG solver, a model with a multi-step instance,
@@ -364,37 +367,15 @@ class Batch:
 
     def env_unroll_eval(self, st_in, st_out, T: int, n_frames: int, env, cur_frame_in, actor: dict, obs_in, obs_ring, noise=None, actions_out=None,
                         eval_metrics=None, qpos_out=None, wrap: Optional[dict] = None):
-        """T x [policy -> action -> env step] without a trajectory, one launch (C ABI `rr_env_unroll_eval`).  `wrap` = dict(first, first_obs,
-        prev_done, steps_in, steps_out, truncation_out, episode_length): the Episode + AutoReset wrappers between the steps and brax's
-        EvalWrapper on `eval_metrics` [N, 6] (in place); None: the unwrapped env.  noise [T, N, A] or None (deterministic policy);
-        actions_out [T, N, A] and qpos_out [T + 1, N, nq] optional; obs_ring [N, 2, K] (final observation: obs_ring[:, T & 1])."""
+        """T x [policy -> action -> env step] without a trajectory, one launch (C ABI `rr_env_unroll_eval`).  `wrap` (see `_unroll_io`): the
+        Episode + AutoReset wrappers between the steps and brax's EvalWrapper on `eval_metrics` [N, 6] (in place); None: the unwrapped env.
+        noise [T, N, A] or None (deterministic policy); actions_out [T, N, A] and qpos_out [T + 1, N, nq] optional; obs_ring [N, 2, K]
+        (final observation: obs_ring[:, T & 1])."""
         d, N = self.dims, self.N
-        A_, K = d.nu, d.obs_dim
-        nh = len(actor["hidden_wt"]) + 1
-        HW = 64 if A_ <= 32 else 128
-        if actor["w0"].shape != (32, K) or actor["head_wt"].shape != (32, HW) or actor["head_b"].numel() != HW or actor["b0"].numel() != 32:
-            raise ValueError("rr_env_unroll_eval: inconsistent actor shapes")
-        for t in (actor["w0"], actor["b0"], actor["head_wt"], actor["head_b"], *actor["hidden_wt"], *actor["hidden_b"]):
-            _ptr(t)
-        for w_, b_ in zip(actor["hidden_wt"], actor["hidden_b"]):
-            if w_.numel() != 1024 or b_.numel() != 32:
-                raise ValueError("rr_env_unroll_eval: hidden layers are 32 x 32")
-        p = lambda t: t.data_ptr() if t is not None else None
-        a = RRActorIO(_ptr(obs_in, numel=N * K), _ptr(actor.get("mean"), numel=K) if actor.get("mean") is not None else None,
-                      _ptr(actor.get("std"), numel=K) if actor.get("std") is not None else None, actor["w0"].data_ptr(), actor["b0"].data_ptr(),
-                      (C.c_void_p * 4)(*([t.data_ptr() for t in actor["hidden_wt"]] + [None] * (4 - nh + 1))),
-                      (C.c_void_p * 4)(*([t.data_ptr() for t in actor["hidden_b"]] + [None] * (4 - nh + 1))),
-                      actor["head_wt"].data_ptr(), actor["head_b"].data_ptr(), _ptr(noise, numel=T * N * A_) if noise is not None else None,
-                      _ptr(actions_out, numel=T * N * A_) if actions_out is not None else None, None, None, None, None, None, None,
-                      float(actor["min_std"]), nh, 0)
-        e = RREvalIO(_ptr(eval_metrics, numel=N * 6) if eval_metrics is not None else None, _ptr(obs_ring, numel=N * 2 * K),
+        a = self._actor_io("rr_env_unroll_eval", actor, obs_in, T, noise, actions_out)
+        e = RREvalIO(_ptr(eval_metrics, numel=N * 6) if eval_metrics is not None else None, _ptr(obs_ring, numel=N * 2 * d.obs_dim),
                      _ptr(qpos_out, numel=(T + 1) * N * d.nq) if qpos_out is not None else None, 0 if wrap is not None else 1)
-        w = None
-        if wrap is not None:
-            for k in ("first_obs", "prev_done", "steps_in", "steps_out", "truncation_out"):
-                _ptr(wrap[k], numel=N * K if k == "first_obs" else N)
-            w = RRUnrollIO(self._state(wrap["first"]), wrap["first_obs"].data_ptr(), wrap["prev_done"].data_ptr(), wrap["steps_in"].data_ptr(),
-                           wrap["steps_out"].data_ptr(), wrap["truncation_out"].data_ptr(), float(wrap["episode_length"]))
+        w = self._unroll_io(wrap) if wrap is not None else None
         _check(lib().rr_env_unroll_eval(self.h, C.byref(self._state(st_in)), C.byref(self._state(st_out)), int(T), int(n_frames), C.byref(self._env(env)),
                                         _ptr(cur_frame_in, torch.int32, N), C.byref(w) if w is not None else None, C.byref(a), C.byref(e)))
 

@@ -197,3 +197,96 @@ def test_env_contact_and_pipeline_outputs():
     # contact outputs are served by the debug-dump instance, the lean env by the production one: equal to rounding, which one
     # forward pass (reset) shows; ten substeps amplify it (tests/parity.py)
     assert torch.equal(r2.pipeline_state.qpos, r.pipeline_state.qpos) and torch.allclose(r2.obs, r.obs, atol=1e-5, rtol=1e-5)
+
+
+# Which launch forms each shipped blob serves (the table of DESIGN.md section 4h): None = served, a string = the fragment of the
+# refusal's message, SKIP = a cell another test pins -- the evaluation refusals of Newton on rodent_optimized and of rodent_pair in
+# test_gpu_eval_unroll.py::test_refusals, the per-env parameter refusals of rodent_cpu, rodent_pair and Newton on rodent_optimized in
+# test_gpu_randomisation.py::test_refusals, the multi-step refusal of Newton on rodent_optimized in test_gpu_env.py.
+SKIP = "(pinned elsewhere)"
+NO_DIAG = "no diagnostic kernel instance"
+_ALL = dict(debug=None, profile=None, unroll=None, eval=None, params=None)
+_NEWTON = dict(debug=None, profile=NO_DIAG, unroll="multi-step", eval="Newton", params="Newton")
+LAUNCH_FORMS = {
+    ("rodent_0", "cg"): _ALL,                     # (2,2,1) slot counts, generic dimensions
+    ("rodent_new", "cg"): _ALL,                   # fixed-dimension instances
+    ("rodent_optimized", "cg"): _ALL,
+    ("rodent_cpu", "cg"): dict(debug=NO_DIAG, profile=NO_DIAG, unroll=None, eval=None, params=SKIP),          # candidate-pair contacts
+    ("rodent_pair", "cg"): dict(debug=None, profile=NO_DIAG, unroll="multi-step", eval=SKIP, params=SKIP),    # (3,3,2) + the two-wave pair instance
+    ("rodent_0", "newton"): _NEWTON,
+    ("rodent_new", "newton"): _NEWTON,
+    ("rodent_optimized", "newton"): dict(_NEWTON, unroll=SKIP, eval=SKIP, params=SKIP),
+}
+
+
+@pytest.mark.parametrize("model,solver", list(LAUNCH_FORMS), ids=["-".join(k) for k in LAUNCH_FORMS])
+def test_launch_forms_of_the_shipped_models(model, solver):
+    """Every launch form a shipped blob serves runs once and leaves a finite state; every form it does not serve is refused with
+    the reason (4 envs, n_frames = 1, 2 steps per multi-step launch, 2 solver iterations)."""
+    from rodent_amd import assets, envs, hip, jax_random
+    from rodent_amd.envs import wrappers
+    from rodent_amd.training import acting, networks
+    from tests import randomisation_sets as rs
+    want = LAUNCH_FORMS[(model, solver)]
+    n, T = 4, 2
+    if model in ("rodent_cpu", "rodent_pair"):
+        with pytest.raises(RuntimeError, match="Newton instance"):
+            hip.Model(assets.asset_path(model), 2, 2, solver="newton")
+    env = envs.get_environment("rodent", track_pos=util.synthetic_track(), num_envs=n, xml_path=model + ".xml", solver=solver, iterations=2,
+                               ls_iterations=2, n_frames=1, device=DEV, healthy_z_range=(-0.3, 0.5))
+    b, nu = env._batch, env.action_size
+    finite = lambda s: all(bool(torch.isfinite(getattr(s.pipeline_state, k)).all()) for k in ("qpos", "qvel", "act", "qacc_warmstart"))
+
+    def attempt(form, fn):
+        """fn() launches and returns the state(s) it left; the table says whether it runs or which refusal it meets."""
+        if want[form] is None:
+            assert all(finite(s) for s in fn()), form
+        elif want[form] is not SKIP:
+            with pytest.raises(RuntimeError, match=want[form]):
+                fn()
+
+    def physics(out=None):
+        st = b.zeros_state()
+        st["qpos"][:] = torch.from_numpy(env.sys.qpos0).to(DEV)
+        b.pipeline_step(st, torch.zeros(n, nu, device=DEV), 1, out=out)
+        return [envs.State(envs.PipelineState(**st), None, None, None)]
+
+    def profiled():
+        b.set_profile(torch.zeros(n, 16, dtype=torch.int64, device=DEV))
+        try:
+            return physics()
+        finally:
+            b.set_profile(None)
+
+    keys = jax_random.split(jax_random.PRNGKey(5), n)
+    torch.manual_seed(5)
+    actor = acting.actor_params(networks.make_ppo_networks(env.observation_size, nu, device=DEV).policy_network, None, 0.001)
+    wenv = wrappers.wrap(env, episode_length=5, action_repeat=1)
+    assert isinstance(wenv, wrappers.FusedEpisodeAutoResetWrapper)
+
+    def unrolled(with_actor):
+        if not with_actor:
+            return [wenv.unroll(wenv.reset(keys), torch.zeros(T, n, nu, device=DEV))]
+        K = env.observation_size
+        traj = dict(obs=torch.empty(n, T + 1, K, device=DEV), raw_action=torch.empty(n, T, nu, device=DEV),
+                    **{k: torch.empty(n, T, device=DEV) for k in ("log_prob", "reward", "discount", "truncation")})
+        return [wenv.unroll_policy(wenv.reset(keys), actor, torch.randn(T, n, nu, device=DEV), traj)[0]]
+
+    assert finite(env.step(env.reset(keys), torch.zeros(n, nu, device=DEV)))                 # single step, production instance
+    assert all(finite(s) for s in physics())                                                   # physics only (rodent_pair: the two-wave instance)
+    attempt("debug", lambda: physics(dict(debug=torch.zeros(n, b.dims.dbg_floats, device=DEV))))
+    attempt("profile", profiled)
+    served = want["unroll"] is None
+    assert b.unroll_supported(False) == served and b.unroll_supported(True) == served
+    attempt("unroll", lambda: unrolled(False))
+    attempt("unroll", lambda: unrolled(True))
+    assert env.eval_supported() == (want["eval"] is None)
+    attempt("eval", lambda: [env.unroll_eval(env.reset(keys), T, actor)])
+    assert b.env_params_supported() == (want["params"] is None)
+    fn = rs.system_fn(rs.mixed_fields)
+
+    def randomised():
+        env.randomize(lambda sys: fn(sys, n))
+        return [env.step(env.reset(keys), torch.zeros(n, nu, device=DEV))]
+    attempt("params", randomised)
+    torch.cuda.synchronize()
