@@ -339,6 +339,7 @@ struct rr_batch {
   uint32_t* cost = nullptr;
   bool counted = false;                 // this batch is in m->live_batches
   unsigned* dyn_overflow = nullptr;     // DYN models: (env, env step) events in which more pairs penetrated than the wave has contact slots (rr_batch_contact_overflow)
+  unsigned* bad_states = nullptr;       // (env, env step) events of the bad-state check (rr_env_io::bad_state_max; rr_batch_bad_states)
   unsigned* progress = nullptr;         // pacing counter of multi-step launches (RRIO::progress); RR_PACE=0 turns pacing off
   float *env_dof_f = nullptr, *env_act_f = nullptr, *env_con_f = nullptr;     // per-env parameter rows, owned (rr_batch_set_env_params)
   float* eval_actions = nullptr;        // [N][nu]: where an evaluation launch without actions_out keeps the current action (rr_env_unroll_eval)
@@ -443,6 +444,8 @@ extern "C" int rr_batch_create(const rr_model* m, int32_t num_envs, int32_t devi
     }
   if (m->dyn && (rc = dev_alloc(b, 64, &b->dyn_overflow))) return rc;
   if (m->dyn) HIPCHK(hipMemset(b->dyn_overflow, 0, 64));
+  if ((rc = dev_alloc(b, 64, &b->bad_states))) return rc;
+  HIPCHK(hipMemset(b->bad_states, 0, 64));
   const char* pace = getenv("RR_PACE");
   if (!(pace && pace[0] == '0') && (rc = dev_alloc(b, 64, &b->progress))) return rc;
   m->live_batches.fetch_add(1);
@@ -545,6 +548,8 @@ static int fill_io(const Launch& L, RRIO& io) {
     io.reward = env->reward; io.done = env->done; io.metrics = env->metrics;
     io.healthy_reward = env->healthy_reward; io.ctrl_cost_weight = env->ctrl_cost_weight; io.z_min = env->healthy_z_min;
     io.z_max = env->healthy_z_max; io.terminate_when_unhealthy = env->terminate_when_unhealthy;
+    if (!(env->bad_state_max >= 0.0f)) return fail(RR_EINVAL, "launch: env io bad_state_max must be >= 0 (0 = no bad-state check)");
+    io.bad_state_max = env->bad_state_max;
   }
   io.mode = L.mode;
   return RR_OK;
@@ -609,7 +614,7 @@ static int launch(rr_batch* b, const Launch& L) {
   if (!in.kern) return fail(RR_EUNSUPPORTED, std::string(L.un ? "" : "launch: ") + in.why);
   if (L.un && (rc = fill_unroll(b, L, io))) return rc;
   io.env_dof_f = b->env_dof_f; io.env_act_f = b->env_act_f; io.env_con_f = b->env_con_f;      // null without per-env parameters
-  io.prof = b->prof; io.env_map = b->env_map; io.cost = b->cost; io.dyn_overflow = b->dyn_overflow;
+  io.prof = b->prof; io.env_map = b->env_map; io.cost = b->cost; io.dyn_overflow = b->dyn_overflow; io.bad_states = b->bad_states;
   // step 4: the launch itself, between the event pair of the timing ring
   RRDims kd = pair ? m->kd_rep : b->kd;
   kd.iterations = m->kd.iterations; kd.ls_iterations = m->kd.ls_iterations;
@@ -644,6 +649,16 @@ extern "C" int rr_batch_contact_overflow(rr_batch* b, int64_t* events) {
   HIPCHK(hipStreamSynchronize(b->stream));
   unsigned v = 0;
   HIPCHK(hipMemcpy(&v, b->dyn_overflow, sizeof(v), hipMemcpyDeviceToHost));
+  *events = (int64_t)v;
+  return RR_OK;
+}
+extern "C" int rr_batch_bad_states(rr_batch* b, int64_t* events) {
+  if (!b || !events) return fail(RR_EINVAL, "rr_batch_bad_states: null argument");
+  *events = 0;
+  HIPCHK(hipSetDevice(b->device));
+  HIPCHK(hipStreamSynchronize(b->stream));
+  unsigned v = 0;
+  HIPCHK(hipMemcpy(&v, b->bad_states, sizeof(v), hipMemcpyDeviceToHost));
   *events = (int64_t)v;
   return RR_OK;
 }

@@ -210,6 +210,7 @@ struct RRIO {
   unsigned* progress;
   unsigned* dyn_overflow;            // DYN instances (nullable): counts (env, env step) events -- an env step in one of whose substeps more pairs were in
                                      // penetration than the wave has contact slots; a multi-step launch adds one per such step, as its single launches would
+  unsigned* bad_states;              // counts (env, env step) events of the bad-state check below, with the same semantics; read only where the check is on
   float pace_t1, pace_t2, pace_t3;   // env steps behind the average for priority levels 1, 2, 3
   int pace_mode;                     // bits 0-1: 0 max(weight level, lag level), 1 lag level only, 2 sum capped at 3; bit 2 (4): progress counted
                                      // per SUBSTEP (ten times finer); bit 3 (8): the factor-phase priority is 3 for laggards, 2 otherwise
@@ -226,7 +227,11 @@ struct RRIO {
                                      // reward_alive, reward over the env's active steps (brax EvalWrapper's eval_metrics)
   float* e_qpos_out;                 // nullable [unroll_T + 1][N][nq]: row 0 the incoming qpos, row t + 1 the qpos after step t (before a restore)
   int mode;  // 0 = forward only (pipeline_init), 1 = step; bit 1 (2) = env epilogue as reset (obs only)
-  int pad_;
+  // BAD-STATE CHECK of the env epilogue (rr_step_body.inc), 0 = off: after an env step the env is bad when some element x of its qpos / qvel
+  // fails |x| <= bad_state_max (so NaN and +-inf are bad).  Then done = 1, reward = 0, the metrics = 0 (actor instances: traj_reward = 0)
+  // and bad_states += 1; the wrapped forms restore the first state as for any finished episode.  State and observation of the bad step are
+  // NOT sanitised: the bare step and the raw evaluation form return them, flagged by done.
+  float bad_state_max;
 };
 
 // ------------------------------------------------------------------------------------------ small math
@@ -2221,6 +2226,18 @@ static __device__ __forceinline__ RRIO load_io() {
   return *(const RRIO __attribute__((address_space(4)))*)(p + offsetof(RRKArgs, io));
 #else
   return RRIO{};
+#endif
+}
+
+// One member of the I/O block, read where it is used (a narrow scalar load with a short live range; `load_io` fetches the whole block)
+template <class T>
+static __device__ __forceinline__ T load_io_member(size_t member_offset) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  const char __attribute__((address_space(4)))* p = (const char __attribute__((address_space(4)))*)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(p));
+  return *(const T __attribute__((address_space(4)))*)(p + offsetof(RRKArgs, io) + member_offset);
+#else
+  return T{};
 #endif
 }
 

@@ -29,7 +29,7 @@
     if (ref_io.dbg && lane == 0) ref_io.dbg[(size_t)env * D.dbg_floats + D.g_kaok] = same ? 1.0f : 0.0f;
     if (!same) return;
   }
-  const int mode = io.mode;
+  int mode = io.mode;            // bits 0-1: RRIO::mode; bit 2 (4): the bad-state flag of the env step being finished (set and cleared below)
   // the debug dump (parity tests) is a separate instance: its paths keep dozens of values alive across the solver
   float* dbg = (DBG && io.dbg) ? io.dbg + (size_t)env * D.dbg_floats : nullptr;     // DBG instance without a dump buffer: contact outputs only
 
@@ -274,6 +274,26 @@
   lane = opaque(lane); w.lane = lane;
   asm volatile("" : "+s"(env));
   if (RAND) w.renv = env;
+  // ---- BAD-STATE CHECK (RRIO::bad_state_max > 0; MuJoCo's mj_checkPos / mj_checkVel): once per env step, on the state after the last
+  // substep, never at reset.  The env is bad when some element x of its qpos / qvel fails |x| <= bad_state_max -- written that way round,
+  // so NaN and +-inf are bad.  One pass of the lanes over the two LDS vectors and one ballot; the flag is wave-uniform and travels in
+  // bit 2 of `mode`, a register that is live anyway, up to the two places below that form `done`.  It stands HERE, before the epilogue
+  // re-reads the I/O block, and takes its two members by narrow loads: formed in the observation loops below with the members read from
+  // `io`, the flag met the epilogue's register peak and the fixed-dimension multi-step instances went from 83 / 158 to 105 / 172 spilled
+  // SGPRs (DESIGN.md section 4i).  Physics-only launches carry no threshold (the host sets it with the env io only).
+  if (!PAIR) {
+    const float bad_max = load_io_member<float>(offsetof(RRIO, bad_state_max));
+    mode &= 3;
+    if (bad_max > 0.0f && !(mode & 2)) {
+      bool b = false;
+      for (int i = lane; i < D.nq; i += RR_LANES) b |= !(fabsf(w.s_qpos[i]) <= bad_max);
+      for (int i = lane; i < D.nv; i += RR_LANES) b |= !(fabsf(w.s_qvel[i]) <= bad_max);
+      if (__builtin_amdgcn_ballot_w64(b) != 0) {
+        mode |= 4;
+        if (lane == 0) __hip_atomic_fetch_add(load_io_member<unsigned*>(offsetof(RRIO, bad_states)), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+    }
+  }
   io = load_io();
   if (PROF && io.prof && lane == 0) for (int i = 0; i < RR_NPH; ++i) io.prof[(size_t)env * RR_NPH + i] = w.pt[i];
   if (UNROLL) u_work += (unsigned)w.work;        // a multi-step launch reports the work of all its steps
@@ -347,6 +367,14 @@
         io.done[env] = io.terminate_when_unhealthy ? 1.0f - healthy : 0.0f;
         io.metrics[3 * env] = pos_reward; io.metrics[3 * env + 1] = -cc; io.metrics[3 * env + 2] = hr;
         io.cur_frame[env] = new_frame;
+        // a bad state ends the episode with reward 0 and metrics 0, whatever terminate_when_unhealthy is (state and observation stay as they
+        // are).  Written OVER the step's values by a branch of its own: the arithmetic above keeps the code it had without the check
+        if (mode & 4) {
+          io.reward[env] = 0.0f;
+          if (ACTOR && !EVAL) io.t_reward[rr_traj_at(io, num_envs, env, ut)] = 0.0f;
+          io.done[env] = 1.0f;
+          io.metrics[3 * env] = 0.0f; io.metrics[3 * env + 1] = 0.0f; io.metrics[3 * env + 2] = 0.0f;
+        }
       }
     }
     if (UNROLL) {
@@ -355,7 +383,7 @@
       // where done, the stored first state and first observation come back (info -- cur_frame, steps -- is not restored)
       const float z = w.s_qpos[2];
       const float healthy = (z < io.z_min || z > io.z_max) ? 0.0f : 1.0f;
-      const float done_env = io.terminate_when_unhealthy ? 1.0f - healthy : 0.0f;
+      const float done_env = (mode & 4) ? 1.0f : (io.terminate_when_unhealthy ? 1.0f - healthy : 0.0f);
       const bool wrapped = !EVAL || !(io.a_pad & RR_EVAL_RAW);      // EVAL without the wrappers: the env's own done, no step count, no restore
       if (wrapped) u_steps = (u_prev_done != 0.0f ? 0.0f : u_steps) + 1.0f;
       const bool over = wrapped && u_steps >= io.episode_length;

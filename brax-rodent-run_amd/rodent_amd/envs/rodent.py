@@ -20,6 +20,15 @@ from .base import PipelineEnv, PipelineState, State, System
 _XML_PATH = "./models/rodent_new.xml"   # [REF Rodent_Env_Brax.py:16]
 
 
+def bad_state_mask(qpos: torch.Tensor, qvel: torch.Tensor, bad_state_max: float) -> torch.Tensor:
+    """The bad-state rule of the step kernel's epilogue in plain torch: env e is bad iff some element x of qpos[e] or qvel[e] fails
+    |x| <= bad_state_max (float32) -- written that way round, so NaN and +-inf are bad.  bool [N].  For tests and for users who compose the
+    env step by step themselves (MuJoCo's mj_checkPos / mj_checkVel with mjMAXVAL = 1e10)."""
+    lim = torch.tensor(float(bad_state_max), dtype=torch.float32, device=qpos.device)
+    ok = lambda x: (x.to(torch.float32).abs() <= lim).flatten(1).all(dim=1)
+    return ~(ok(qpos) & ok(qvel))
+
+
 class Rodent(PipelineEnv):
 
     def __init__(
@@ -38,8 +47,20 @@ class Rodent(PipelineEnv):
         num_envs: int = 1,
         xml_path: str = _XML_PATH,
         device=None,
+        bad_state_max: Optional[float] = None,
         **kwargs,
     ):
+        """`bad_state_max` (None = off, the default): the bad-state check of MuJoCo (`mj_checkPos` / `mj_checkVel`, there with
+        mjMAXVAL = 1e10).  After an env step an env is bad when some element x of its qpos or qvel fails |x| <= bad_state_max (NaN and
+        +-inf included); that step then has done = 1 (whatever `terminate_when_unhealthy` is), reward 0 and metrics 0, and is counted
+        (`bad_states()`).  Under `AutoResetWrapper` -- composed or in the one-launch rollouts -- the first state comes back as for any
+        finished episode, with no bootstrap from the bad step.  The bare `step` does NOT sanitise: it returns the bad state and its
+        observation as they are, flagged by `done`; so does the raw evaluation form (`unroll_eval` without `episode_length`)."""
+        if bad_state_max is not None:
+            with np.errstate(over="ignore", under="ignore"):
+                thr32 = np.float32(bad_state_max)        # what the kernel gets: 1e-50 would arrive as 0 (= off), 1e39 as inf
+            if not (np.isfinite(thr32) and thr32 > 0):
+                raise ValueError(f"bad_state_max must be finite and > 0 as a float32 (or None: no check), got {bad_state_max!r}")
         if solver.lower() not in ("cg", "newton"):       # [REF Rodent_Env_Brax.py:42-45]
             raise ValueError(f"solver must be 'cg' or 'newton', got {solver!r}")
         if vision:
@@ -63,13 +84,14 @@ class Rodent(PipelineEnv):
         self._healthy_z_range = healthy_z_range
         self._reset_noise_scale = reset_noise_scale
         self._vision = vision
+        self._bad_state_max = None if bad_state_max is None else float(bad_state_max)
         self._ctor = dict(track_pos=track_pos, forward_reward_weight=forward_reward_weight, ctrl_cost_weight=ctrl_cost_weight,
                           healthy_reward=healthy_reward, terminate_when_unhealthy=terminate_when_unhealthy,
                           healthy_z_range=healthy_z_range, reset_noise_scale=reset_noise_scale, solver=solver,
                           iterations=iterations, ls_iterations=ls_iterations, vision=vision, xml_path=xml_path,
                           n_frames=kwargs["n_frames"], pipeline_outputs=kwargs.get("pipeline_outputs", False),
                           contact_outputs=kwargs.get("contact_outputs", False), balance=kwargs.get("balance"),
-                          rebalance_every=kwargs.get("rebalance_every", 4))
+                          rebalance_every=kwargs.get("rebalance_every", 4), bad_state_max=bad_state_max)
 
     def with_num_envs(self, num_envs: int, device=None):
         """A sibling env with another batch size (ppo.train builds its per-rank and eval envs this way)."""
@@ -81,10 +103,21 @@ class Rodent(PipelineEnv):
         floor-contact models).  Reads a device counter: synchronises the env's stream."""
         return self._batch.contact_overflow()
 
+    @property
+    def bad_state_max(self) -> Optional[float]:
+        """The threshold of the bad-state check, None when it is off."""
+        return self._bad_state_max
+
+    def bad_states(self) -> int:
+        """(env, env step) events so far in which the bad-state check ended an episode (`bad_state_max`; always 0 while it is off).  A
+        multi-step launch counts each of its steps.  Reads a device counter: synchronises the env's stream."""
+        return self._batch.bad_states()
+
     def _env_io(self, cur_frame, obs, reward=None, done=None, metrics=None):
         return dict(track_pos=self._track_pos, cur_frame=cur_frame, obs=obs, reward=reward, done=done, metrics=metrics,
                     healthy_reward=self._healthy_reward, ctrl_cost_weight=self._ctrl_cost_weight,
-                    healthy_z_range=self._healthy_z_range, terminate_when_unhealthy=self._terminate_when_unhealthy)
+                    healthy_z_range=self._healthy_z_range, terminate_when_unhealthy=self._terminate_when_unhealthy,
+                    bad_state_max=self._bad_state_max)
 
     def reset(self, rng) -> State:
         """Resets the environment to an initial state.  `rng`: uint32 keys [N, 2] (one jax-style
@@ -195,7 +228,8 @@ class Rodent(PipelineEnv):
         return self._next_state(state, st, io, ring[:, int(T) & 1].contiguous(), wrap)
 
     def step(self, state: State, action: torch.Tensor) -> State:
-        """Runs one timestep of the environment's dynamics."""
+        """Runs one timestep of the environment's dynamics.  With `bad_state_max` set, a bad env comes back with done = 1, reward 0 and
+        metrics 0, but its state and observation are returned as they are (possibly non-finite): restoring is AutoReset's part."""
         st_in, st, io, _ = self._launch_buffers(state)
         out = self._alloc_outputs(full=False)
         obs = torch.empty(self.num_envs, self.sys.obs_dim, device=self.device)

@@ -39,7 +39,7 @@ class RREnvIO(C.Structure):
     _fields_ = [("track_pos", C.c_void_p), ("track_len", C.c_int32), ("cur_frame", C.c_void_p), ("obs", C.c_void_p),
                 ("reward", C.c_void_p), ("done", C.c_void_p), ("metrics", C.c_void_p), ("healthy_reward", C.c_float),
                 ("ctrl_cost_weight", C.c_float), ("healthy_z_min", C.c_float), ("healthy_z_max", C.c_float),
-                ("terminate_when_unhealthy", C.c_int32)]
+                ("terminate_when_unhealthy", C.c_int32), ("bad_state_max", C.c_float)]
 
 
 class RRUnrollIO(C.Structure):
@@ -73,7 +73,7 @@ class RRPpoCfg(C.Structure):
 
 
 EXPORTS = ["rr_model_load", "rr_model_dims", "rr_model_set_solver", "rr_model_set_solver_type", "rr_model_destroy", "rr_model_table", "rr_kernarg_layout", "rr_batch_create",
-           "rr_batch_destroy", "rr_pipeline_init", "rr_pipeline_step", "rr_env_step", "rr_env_reset", "rr_pipeline_step_to", "rr_env_step_to", "rr_batch_contact_overflow", "rr_batch_unroll_supported", "rr_env_unroll", "rr_env_unroll_policy", "rr_batch_eval_supported", "rr_env_unroll_eval",
+           "rr_batch_destroy", "rr_pipeline_init", "rr_pipeline_step", "rr_env_step", "rr_env_reset", "rr_pipeline_step_to", "rr_env_step_to", "rr_batch_contact_overflow", "rr_batch_bad_states", "rr_batch_unroll_supported", "rr_env_unroll", "rr_env_unroll_policy", "rr_batch_eval_supported", "rr_env_unroll_eval",
            "rr_compute_gae", "rr_mlp_forward", "rr_ppo_loss_workspace_bytes", "rr_ppo_loss", "rr_policy_act_workspace_bytes", "rr_policy_act", "rr_policy_sample", "rr_policy_backward_workspace_bytes", "rr_policy_backward", "rr_mlp_silu_backward_workspace_bytes", "rr_mlp_silu_backward", "rr_mlp_value_backward_workspace_bytes", "rr_mlp_value_backward", "rr_mlp_weight_grad_workspace_bytes", "rr_mlp_weight_grad", "rr_mlp_weight_grad_batch_workspace_bytes", "rr_mlp_weight_grad_batch", "rr_obs_moments_workspace_bytes", "rr_obs_moments", "rr_wrap_episode_autoreset", "rr_debug_layout", "rr_batch_set_schedule", "rr_batch_set_env_params", "rr_batch_env_params_supported", "rr_batch_set_profile", "rr_batch_set_timing", "rr_batch_kernel_time", "rr_last_error"]
 
 _lib = None
@@ -107,6 +107,7 @@ def lib():
                                      C.c_void_p, C.POINTER(RROutputs)]
         L.rr_batch_unroll_supported.argtypes = [C.c_void_p, C.c_int32]
         L.rr_batch_contact_overflow.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+        L.rr_batch_bad_states.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
         L.rr_env_unroll.argtypes = [C.c_void_p, C.POINTER(RRState), C.POINTER(RRState), C.c_void_p, C.c_int32, C.c_int32, C.POINTER(RREnvIO),
                                     C.c_void_p, C.POINTER(RRUnrollIO)]
         L.rr_env_unroll_policy.argtypes = [C.c_void_p, C.POINTER(RRState), C.POINTER(RRState), C.c_int32, C.c_int32, C.POINTER(RREnvIO), C.c_void_p,
@@ -274,6 +275,7 @@ class Batch:
         e.ctrl_cost_weight = env.get("ctrl_cost_weight", 0.1)
         e.healthy_z_min, e.healthy_z_max = env.get("healthy_z_range", (0.03, 0.5))
         e.terminate_when_unhealthy = int(env.get("terminate_when_unhealthy", True))
+        e.bad_state_max = float(env.get("bad_state_max") or 0.0)      # 0 = no bad-state check
         return e
 
     # ------------------------------------------------------------------ C-ABI calls
@@ -308,6 +310,13 @@ class Batch:
         (candidate-pair models; 0 for the others; synchronises the stream)."""
         n = C.c_int64()
         _check(lib().rr_batch_contact_overflow(self.h, C.byref(n)))
+        return int(n.value)
+
+    def bad_states(self) -> int:
+        """(env, env step) events in which the bad-state check (env io `bad_state_max` > 0) found a non-finite or out-of-range qpos /
+        qvel -- a multi-step launch counts each of its steps (0 while the check is off; synchronises the stream)."""
+        n = C.c_int64()
+        _check(lib().rr_batch_bad_states(self.h, C.byref(n)))
         return int(n.value)
 
     def unroll_supported(self, with_actor: bool = False) -> bool:

@@ -298,6 +298,13 @@ def train(
     if getattr(getattr(env, "sys", None), "candidate_contacts", False) and hasattr(env, "contact_overflow"):
         overflow_envs = [sub["env"] for sub in sub_rollout.subs] if sub_rollout is not None else [env]
     overflow = {"total": 0, "reported": 0, "warned": False}
+    # Envs built with the bad-state check (Rodent(bad_state_max=...)) end and restore an episode whose qpos / qvel is non-finite or beyond the
+    # threshold, and count the (env, env step) events: reported as training/bad_state_resets (events since the previous report), with one
+    # warning.  Read next to the counter above, after the closing synchronisation.  The env carries the setting; off: no metric.
+    bad_envs = []
+    if getattr(env, "bad_state_max", None) and hasattr(env, "bad_states"):
+        bad_envs = [sub["env"] for sub in sub_rollout.subs] if sub_rollout is not None else [env]
+    bad = {"total": 0, "reported": 0, "warned": False}
 
     def training_step():
         nonlocal env_state, normalizer_params
@@ -354,6 +361,14 @@ def train(
                 overflow["warned"] = True
                 warnings.warn(f"ppo.train: {overflow['total']} (env, step) events so far with more than 64 contact pairs in penetration; the "
                               "surplus pairs were dropped for those substeps (training/contact_overflow counts them)", RuntimeWarning, stacklevel=2)
+        if bad_envs:
+            bad["total"] = sum(e.bad_states() for e in bad_envs)
+            out["training/bad_state_resets"] = float(bad["total"] - bad["reported"])
+            if bad["total"] and not bad["warned"]:
+                bad["warned"] = True
+                warnings.warn(f"ppo.train: {bad['total']} (env, step) events so far in which an env's qpos / qvel was non-finite or beyond "
+                              f"bad_state_max = {env.bad_state_max:g}; those episodes were ended and restored "
+                              "(training/bad_state_resets counts them)", RuntimeWarning, stacklevel=2)
         return out
 
     metrics = {}
@@ -396,6 +411,7 @@ def train(
                 metrics = dict(training_metrics)
             progress_fn(current_step, metrics)
             overflow["reported"] = overflow["total"]
+            bad["reported"] = bad["total"]
             # callbacks get a SNAPSHOT (the live network keeps training)
             policy_params_fn(current_step, make_policy, params_tuple(normalizer_params.clone(), copy.deepcopy(policy_net).requires_grad_(False),
                                                                      normalize_observations))

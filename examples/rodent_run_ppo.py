@@ -54,6 +54,8 @@ def main():
     ap.add_argument("--clip-name", default="84")
     ap.add_argument("--max-training-steps", type=int, default=None)
     ap.add_argument("--randomize", action="store_true", help="domain randomisation: per-env friction and actuator gain (domain_randomize)")
+    ap.add_argument("--bad-state-max", type=float, default=None, help="end and restore episodes whose qpos / qvel is non-finite or exceeds this "
+                    "magnitude (MuJoCo's mjMAXVAL is 1e10); off by default")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -80,7 +82,8 @@ def main():
     env = envs.get_environment(
         config["env_name"], track_pos=track_pos, terminate_when_unhealthy=config["terminate_when_unhealthy"],
         solver=config["solver"], iterations=config["iterations"], ls_iterations=config["ls_iterations"],
-        vision=config["vision"], num_envs=args.envs_per_gpu, xml_path=args.xml, device=f"cuda:{local_rank}")
+        vision=config["vision"], num_envs=args.envs_per_gpu, xml_path=args.xml, device=f"cuda:{local_rank}",
+        bad_state_max=args.bad_state_max)
 
     train_fn = functools.partial(
         ppo.train, num_timesteps=config["num_timesteps"], num_evals=int(config["num_timesteps"] / config["eval_every"]),

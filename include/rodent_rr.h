@@ -80,6 +80,12 @@ typedef struct rr_env_io {
   float* metrics;         /* [N][3] out: pos_reward, reward_quadctrl, reward_alive */
   float healthy_reward, ctrl_cost_weight, healthy_z_min, healthy_z_max;
   int32_t terminate_when_unhealthy;
+  /* Bad-state check (MuJoCo's mj_checkPos / mj_checkVel; mjMAXVAL = 1e10), 0 = off (a zero-initialised struct keeps the unchecked
+   * behaviour); negative or NaN: RR_EINVAL.  After an env step -- once per step, on the state after the last substep, never at reset and
+   * never in rr_pipeline_step -- env e is BAD iff some element x of its qpos or qvel fails fabsf(x) <= bad_state_max, so NaN and +-inf
+   * are bad.  That step then writes done = 1 (whatever terminate_when_unhealthy is), reward = 0 and the three metrics = 0, and adds 1
+   * to the batch's counter (rr_batch_bad_states).  The state and the observation of the bad step are NOT sanitised. */
+  float bad_state_max;
 } rr_env_io;
 
 /* -- model ------------------------------------------------------------------------------------- */
@@ -119,6 +125,8 @@ int rr_pipeline_step(rr_batch* b, const rr_state* st, const float* ctrl, int32_t
 int rr_env_step(rr_batch* b, const rr_state* st, const float* action, int32_t n_frames, const rr_env_io* env,
                 const rr_outputs* out);
 
+/* With env->bad_state_max > 0 a bad env (see rr_env_io) leaves rr_env_step / rr_env_step_to flagged by done = 1 with reward and metrics 0,
+ * but its qpos / qvel / obs are returned as they are (possibly non-finite): the caller -- AutoReset, rr_wrap_episode_autoreset -- restores. */
 /* Out-of-place variants: read the state from `in` (and info['cur_frame'] from `cur_frame_in`), write the stepped state to
  * `out_state` (and env->cur_frame).  brax states are immutable values [REF Rodent_Env_Brax.py:98-136 returns a new State]:
  * a caller that keeps the previous state (rollout buffers, AutoReset's first state) needs no copies.  `in` and
@@ -138,7 +146,9 @@ int rr_env_step_to(rr_batch* b, const rr_state* in, const rr_state* out_state, c
  * Production instance only (no rr_outputs).  Models with a multi-step instance (CG solver): the single-rodent floor-contact models
  * (rodent_optimized / rodent_new and any model of their slot counts) and the candidate-pair models (rodent_cpu.xml:
  * self-collisions, tendon transmissions).  RR_EUNSUPPORTED for the Newton solver and for models of other slot counts (rodent_pair.xml);
- * rr_batch_unroll_supported tells. */
+ * rr_batch_unroll_supported tells.
+ * Bad-state check (env->bad_state_max > 0): a bad step counts as a finished episode with done_env = 1 -- truncation 0, and the stored first
+ * state and first observation come back, so nothing non-finite survives the step; cur_frame and steps behave as at any other done. */
 /* Models whose contact list is a list of candidate pairs (contacts between two moving bodies, e.g. rodent_cpu.xml [REF models/rodent_cpu.xml]):
  * the kernel keeps the pairs in penetration in 64 contact slots per environment; pairs beyond that are DROPPED for that substep.  *events = the
  * number of (environment, step) events in which that happened since the batch was created, a step being one launch of rr_pipeline_step /
@@ -146,6 +156,10 @@ int rr_env_step_to(rr_batch* b, const rr_state* in, const rr_state* out_state, c
  * adds exactly what the same steps as single launches add.  Synchronises the batch's stream.  Always 0 for the floor-contact models,
  * whose every contact has its own slot. */
 int rr_batch_contact_overflow(rr_batch* b, int64_t* events);
+/* *events = the number of (environment, env step) events in which the bad-state check (rr_env_io::bad_state_max) found a bad env since the
+ * batch was created, counted like the events above: one launch of rr_env_step is one step, a multi-step launch adds exactly what the same
+ * steps as single launches add.  The counter is owned by the batch.  Always 0 while the check is off.  Synchronises the batch's stream. */
+int rr_batch_bad_states(rr_batch* b, int64_t* events);
 
 /* 1 when this batch's model / solver has a multi-step kernel instance (with_actor != 0: the one with the actor inside), else 0. */
 int rr_batch_unroll_supported(const rr_batch* b, int32_t with_actor);
@@ -174,7 +188,9 @@ int rr_env_unroll(rr_batch* b, const rr_state* in, const rr_state* out_state, co
  * the wave over the head); 32 < A <= 64: head_wt [32][128], head_b [128] (two passes; rodent_cpu.xml, A = 38).  The kernel reads the
  * whole padded width, so the arrays must have it.  A > 64: RR_EUNSUPPORTED.  noise [T][N][A] standard normal draws.
  * The final observation is traj_obs[:, T] (env->obs is not written).  Instances for the models rr_env_unroll serves
- * (rr_batch_unroll_supported(b, 1)). */
+ * (rr_batch_unroll_supported(b, 1)).
+ * Bad-state check: at a bad transition traj_reward = 0, traj_discount = 0 (no bootstrap from the bad step), traj_truncation = 0, and the next
+ * observation row is the stored first observation. */
 typedef struct rr_actor_io {
   const float* obs_in; const float* mean; const float* std;
   const float* w0; const float* b0;
@@ -206,7 +222,9 @@ int rr_env_unroll_policy(rr_batch* b, const rr_state* in, const rr_state* out_st
  * metrics / cur_frame of the last step, steps_out / truncation_out in the wrapped form) as rr_env_unroll.
  * Instances: the models rr_env_unroll_policy serves, CG solver.  RR_EUNSUPPORTED (rr_last_error says why) for the Newton solver, two-tree
  * models served by the two-wave pair instance, other slot counts, batches that carry per-env parameters (rr_batch_set_env_params),
- * observations wider than 1280, more than 64 actions and diagnostic batches; those evaluate step by step.  rr_batch_eval_supported: 1 / 0. */
+ * observations wider than 1280, more than 64 actions and diagnostic batches; those evaluate step by step.  rr_batch_eval_supported: 1 / 0.
+ * Bad-state check: a bad step adds zeros to the sums and ends the episode (active *= 0).  The WRAPPED form restores the first state; the
+ * RAW form has no restore, so it flags the env by done = 1, counts the event and goes on stepping the bad state as it is. */
 typedef struct rr_eval_io {
   float* eval_metrics;
   float* obs_ring;
