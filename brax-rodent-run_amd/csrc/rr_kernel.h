@@ -43,6 +43,9 @@
 #ifndef RR_DPP_BLOCK
 #define RR_DPP_BLOCK 1     // one s_nop per row-broadcast stage instead of one per value (-0.6 % launch time, bit-identical)
 #endif
+#ifndef RR_LS_REPEAT_EXIT
+#define RR_LS_REPEAT_EXIT 1   // the line search leaves its bracketing loop after an iteration that changed nothing (Wave::linesearch; bit-identical results)
+#endif
 #define RR_MINVAL 1e-15f
 #define RR_MINIMP 0.0001f
 #define RR_MAXIMP 0.9999f
@@ -64,7 +67,7 @@ struct RRDims {
   // debug dump offsets (floats)
   int g_xpos, g_xquat, g_xmat, g_com, g_cinert, g_crb, g_cdof, g_cvel, g_cfrc, g_qM, g_qLD, g_dinv, g_bias, g_passive,
       g_actuator, g_smooth, g_qacc_smooth, g_con_dist, g_con_pos, g_con_frame, g_con_D, g_con_aref, g_lim, g_qacc,
-      g_qfrc_constraint, g_misc, g_kaok, dbg_floats;
+      g_qfrc_constraint, g_misc, g_ls_iters, g_kaok, dbg_floats;
 };
 
 // LDS layout of one environment (float offsets).  One constexpr function serves the host (rr_api.hip layout) and the
@@ -232,6 +235,10 @@ struct RRIO {
   // and bad_states += 1; the wrapped forms restore the first state as for any finished episode.  State and observation of the bad step are
   // NOT sanitised: the bare step and the raw evaluation form return them, flagged by done.
   float bad_state_max;
+  // debug-dump instance only (rr_batch_set_ls_repeat_exit): 1 = the line search runs its repeated bracketing iterations instead of leaving
+  // the loop (RR_LS_REPEAT_EXIT) -- the A side of the bitwise test of that exit.  No other instance reads it.
+  int ls_run_repeats;
+  int pad_end;                 // sizeof(RRIO) stays a multiple of 8 (RRKArgs)
 };
 
 // ------------------------------------------------------------------------------------------ small math
@@ -523,6 +530,7 @@ struct Wave {
   // solver options, read from the kernel arguments at the head of solve() and held in scalar registers through its loops only
   float so_tolerance, so_ls_tolerance, so_meaninertia;
   int so_iterations, so_ls_iterations, so_nv_scale;
+  int dbg_ls_run_repeats = 0, dbg_ls_ran = 0, dbg_ls_left = 0;      // debug-dump instance only: RRIO::ls_run_repeats; bracketing iterations executed / left out in this substep
   int work;               // wave-uniform count of line-search point evaluations, weighted by row blocks: the scheduling cost estimate (rr_batch_set_schedule)
   unsigned long long pt_last, pt[RR_NPH];
   template <bool PROF> __device__ __forceinline__ void stamp(int i) {
@@ -1965,7 +1973,7 @@ struct Wave {
   // (Jaref, Jv, D) triples are compacted once per line search through LDS (positions by ballot / mbcnt; the staging cells
   // are the dead cinert / cvel / pose regions), so that every evaluation of the up to 2 + 3*ls_iterations points costs one
   // row per lane instead of 4*NCS + NVS.
-  template <bool PROF>
+  template <bool PROF, bool DBG = false>
   __device__ __forceinline__ void linesearch() {
     float red[4] = {0, 0, 0, 0};
     put_vec(search);   // CG: mv = M search is carried by the caller's recurrence; Newton: an explicit product with the copy of M
@@ -2026,12 +2034,28 @@ struct Wave {
     stamp<PROF>(18);
     bool swap = true;
     work += 4 * (1 + (R > RR_LANES ? 1 : 0));          // the four evaluations outside the bracketing loop
-    for (int it = 0; it < so_ls_iterations; ++it) {
+    // REPEAT EXIT (RR_LS_REPEAT_EXIT).  One iteration is a function of (lo, hi) and of values the loop does not change (the compacted rows,
+    // qg, gtol), and every iteration runs this one machine-code body (hence nounroll).  An iteration that leaves lo and hi bitwise what they
+    // were at its head -- alpha, d0 and d1 of both -- is therefore followed by identical ones: with `swap` false the next loop head ends
+    // the loop anyway, with `swap` true nothing changes up to the cap.  In float32 with contracted FMAs that second case is the common
+    // one: both ends on one side of the root keep swap_lo_next / swap_hi_next true although the Newton step no longer moves alpha, and gtol
+    // lies far below one ulp of d0.  Leaving at once gives the same lo, hi, final costs and alpha.  `work` counts the loop heads the full loop
+    // would have visited (after the loop, from `it`: an addition inside the loop costs the single-step instance an SGPR spill).  PAIR: both
+    // waves compare the same totals, so they leave in the same iteration and their barriers still match.
+    int it = 0, ls_ran = 0, ls_left = 0;               // DBG / PROF: bracketing iterations executed / left out by the exit
+#pragma nounroll
+    for (; it < so_ls_iterations; ++it) {
+#if !RR_LS_REPEAT_EXIT
       work += 3 * (1 + (R > RR_LANES ? 1 : 0));        // the bracketing loop is what separates slow from fast environments
+#endif
       bool done = !swap;
       done |= (lo.d0 < 0) && (lo.d0 > -gtol);
       done |= (hi.d0 > 0) && (hi.d0 < gtol);
       if (uni(done)) break;
+      if constexpr (PROF || DBG) ++ls_ran;
+#if RR_LS_REPEAT_EXIT
+      const LSPoint lo_head = lo, hi_head = hi;
+#endif
       const float a3[3] = {lo.alpha - div_nr(lo.d0, lo.d1), hi.alpha - div_nr(hi.d0, hi.d1), 0.5f * (lo.alpha + hi.alpha)};
       ls_eval<3, false>(a3, qg, tmp3, R, rjr, rjv, rD);
       const LSPoint lo_next = tmp3[0], hi_next = tmp3[1], mid = tmp3[2];
@@ -2044,7 +2068,23 @@ struct Wave {
       const bool swap_hi_mid = (mid.d0 > 0) && (hi.d0 > mid.d0);
       if (swap_hi_mid) hi = mid;
       swap = swap_lo_next || swap_lo_mid || swap_hi_next || swap_hi_mid;
+#if RR_LS_REPEAT_EXIT
+      bool same = swap;        // without a swap the next loop head leaves (and counts itself in `work`)
+      same &= __float_as_int(lo.alpha) == __float_as_int(lo_head.alpha) && __float_as_int(lo.d0) == __float_as_int(lo_head.d0) && __float_as_int(lo.d1) == __float_as_int(lo_head.d1);
+      same &= __float_as_int(hi.alpha) == __float_as_int(hi_head.alpha) && __float_as_int(hi.d0) == __float_as_int(hi_head.d0) && __float_as_int(hi.d1) == __float_as_int(hi_head.d1);
+      if constexpr (DBG) same &= dbg_ls_run_repeats == 0;      // debug-dump instance: run the repeats anyway (rr_batch_set_ls_repeat_exit)
+      if (uni(same)) {
+        if constexpr (PROF || DBG) ls_left = so_ls_iterations - 1 - it;
+        it = so_ls_iterations;
+        break;
+      }
+#endif
     }
+#if RR_LS_REPEAT_EXIT
+    work += 3 * (1 + (R > RR_LANES ? 1 : 0)) * (it < so_ls_iterations ? it + 1 : it);      // the bracketing loop is what separates slow from fast environments
+#endif
+    if constexpr (PROF) { pt[20] += (unsigned)ls_ran; pt[21] += (unsigned)ls_left; }
+    if constexpr (DBG) { dbg_ls_ran += ls_ran; dbg_ls_left += ls_left; }
     {   // costs of the bracket's end points
       const float a2[2] = {lo.alpha, hi.alpha};
       LSPoint f2[2];
@@ -2065,7 +2105,7 @@ struct Wave {
   }
 
   // [UP mjx solver.solve] primal CG with warm start; returns the iteration count
-  template <bool PROF>
+  template <bool PROF, bool DBG = false>
   __device__ __forceinline__ int solve() {
     {
       const DT Dl = phase_dims();
@@ -2105,7 +2145,7 @@ struct Wave {
       if (uni(done)) break;
       stamp<PROF>(12);
       for (int rep = 0; rep < RR_REP_LS; ++rep) linesearch<false>();
-      linesearch<PROF>();
+      linesearch<PROF, DBG>();
       stamp<PROF>(9);
       float pm[NVS], gg = 0.0f;
 #pragma unroll

@@ -245,7 +245,8 @@
     }
     w.constraint_rows(dg);
     w.template stamp<PROF>(7);
-    niter = w.template solve<PROF>();
+    if (DBG) { w.dbg_ls_run_repeats = io.ls_run_repeats; w.dbg_ls_ran = w.dbg_ls_left = 0; }
+    niter = w.template solve<PROF, DBG>();
     w.template stamp<PROF>(12);
     if (dg) {
 #pragma unroll
@@ -253,7 +254,7 @@
         const int d = lane + RR_LANES * s;
         if (d < D.nv) { dg[D.g_qacc + d] = w.qacc[s]; dg[D.g_qfrc_constraint + d] = w.qfrc_con[s]; }
       }
-      if (lane == 0) { dg[D.g_misc] = (float)niter; dg[D.g_misc + 1] = w.cost; }
+      if (lane == 0) { dg[D.g_misc] = (float)niter; dg[D.g_misc + 1] = w.cost; dg[D.g_ls_iters] = (float)w.dbg_ls_ran; dg[D.g_ls_iters + 1] = (float)w.dbg_ls_left; }
     }
     if (mode & 1) w.euler();
     w.template stamp<PROF>(13);

@@ -414,13 +414,21 @@ int rr_batch_env_params_supported(const rr_batch* b);
 /* Debug dump layout: names[i] begins at float offsets[i] of each env's debug row; returns the field count. */
 int rr_debug_layout(const rr_batch* b, const char*** names, const int32_t** offsets, const int32_t** sizes);
 
+/* Diagnostic, debug-dump launches only (rr_outputs.debug or the contact-geometry outputs): the line search leaves its bracketing loop
+ * after an iteration that left the bracket bitwise unchanged, because every later one would repeat it (rr_kernel.h RR_LS_REPEAT_EXIT).
+ * enable = 0 makes the debug-dump instance run those iterations anyway, so that a test can compare the two bit for bit; the dump
+ * field `ls_iters` holds the bracketing iterations the last substep executed and those the exit left out.  Default 1.  Every other
+ * instance always takes the exit and carries no code for this switch. */
+int rr_batch_set_ls_repeat_exit(rr_batch* b, int32_t enable);
+
 /* ms of the most recent step-kernel launches on this batch measured with hipEvents on its stream
  * (enable with rr_batch_set_timing(b,1); each launch is then bracketed by events) */
 int rr_batch_set_timing(rr_batch* b, int32_t enable);
 int rr_batch_kernel_time(rr_batch* b, double* total_ms, int64_t* launches);
 
 /* Diagnostic only (never in a timed run): route launches to the s_memtime-instrumented build of the kernel, which
- * writes per-phase cycle sums of each env into dev_cycles [N][16] (uint64, device).  NULL switches back. */
+ * writes per-phase cycle sums of each env into dev_cycles [N][24] (uint64, device; RR_NPH slots).  Slots 20 and 21 are counts, not cycles:
+ * the bracketing iterations the env's line searches executed, and those the repeat exit left out.  NULL switches back. */
 int rr_batch_set_profile(rr_batch* b, uint64_t* dev_cycles);
 
 /* Build-consistency probe (tests): byte offset and size of the I/O block inside the step kernel's argument segment as the
