@@ -12,6 +12,7 @@
 #include <cstring>
 #include <map>
 #include <memory>
+#include <mutex>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -509,6 +510,9 @@ static int check_wrap(const char* who, const rr_unroll_io* w, const char* note =
     return fail(RR_EINVAL, std::string(who) + ": null wrapper pointer" + note);
   return RR_OK;
 }
+// Columns the actor's head is padded to, in the kernel arguments (rr_actor_step) and in LDS (rr_policy_tail_kernel): 64 up to 64 logits,
+// 128 above.  A head fits when P <= head_cols(P).
+static int head_cols(int P) { return P <= 64 ? 64 : 128; }
 // traj: the form that samples and records transitions (noise, actions and the trajectory arrays are required)
 static int check_actor(const char* who, const rr_actor_io* a, bool traj) {
   if (!a->obs_in || !a->w0 || !a->b0 || !a->head_wt || !a->head_b || (a->mean == nullptr) != (a->std == nullptr) ||
@@ -523,7 +527,7 @@ static int check_actor(const char* who, const rr_actor_io* a, bool traj) {
 static const char* actor_limit(const rr_model* m, const rr_actor_io* ac) {
   if (m->dims.obs_dim > 1280) return "rr_env_unroll_policy: observation wider than 1280";
   if (ac && (ac->nhidden < 1 || ac->nhidden > 5)) return "rr_env_unroll_policy: 1 .. 5 hidden layers";
-  if (m->dims.nu > 64) return "rr_env_unroll_policy: more than 64 actions (the in-kernel actor's head is at most 2 x 64 logits)";
+  if (2 * m->dims.nu > head_cols(2 * m->dims.nu)) return "rr_env_unroll_policy: more than 64 actions (the in-kernel actor's head is at most 2 x 64 logits)";
   return nullptr;
 }
 
@@ -857,6 +861,21 @@ extern "C" int rr_mlp_silu_backward(const float* g, const float* z, int32_t M, i
 }
 
 // ------------------------------------------------------------------------------------------ PPO: fused MLP forward (MFMA f32)
+// A launch with `bytes` of dynamic LDS needs the kernel's limit raised first.  The attribute belongs to the (kernel, device) pair, so
+// that is what is remembered (rr_batch_create does the same for the step-kernel instances of its batch's device).
+static int dyn_lds(const void* kernel, size_t bytes) {
+  static std::mutex mu;
+  static std::map<std::pair<const void*, int>, size_t> set_to;
+  int dev = 0;
+  HIPCHK(hipGetDevice(&dev));
+  std::lock_guard<std::mutex> lock(mu);
+  size_t& have = set_to[{kernel, dev}];
+  if (have < bytes) {
+    HIPCHK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    have = bytes;
+  }
+  return RR_OK;
+}
 static int mlp_net(const rr_mlp_net* n, int K, int hidden, bool is_value, RRMlpNet* out, const char* who, const char* fn = "rr_mlp_forward") {
   memset(out, 0, sizeof(*out));
   if (!n) return RR_OK;
@@ -889,12 +908,7 @@ extern "C" int rr_mlp_forward(const float* obs, const int64_t* obs_rows, int32_t
   const size_t lds = RR_MLP_LDS_FLOATS * sizeof(float);
   typedef void (*fwd_t)(const RRMlpArgs);
   const fwd_t kern = policy && value ? (fwd_t)rr_mlp_forward_kernel<true, true> : (value ? (fwd_t)rr_mlp_forward_kernel<true, false> : (fwd_t)rr_mlp_forward_kernel<false, true>);
-  static bool attr_set = false;
-  if (!attr_set) {
-    for (fwd_t k_ : {(fwd_t)rr_mlp_forward_kernel<true, true>, (fwd_t)rr_mlp_forward_kernel<true, false>, (fwd_t)rr_mlp_forward_kernel<false, true>})
-      HIPCHK(hipFuncSetAttribute((const void*)k_, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr_set = true;
-  }
+  if ((rc = dyn_lds((const void*)kern, lds))) return rc;
   // diagnostic (RR_MLP_PROF=<file>, eager calls only): shader-clock stamps per phase and workgroup, summarised into the file after every call
   static const char* prof_path = getenv("RR_MLP_PROF");
   static unsigned long long* prof_dev = nullptr;
@@ -939,7 +953,7 @@ extern "C" int rr_policy_act(const float* obs, const int64_t* obs_rows, int32_t 
   int rc = mlp_net(policy, K, RR_MLP_PH, false, &net, "policy", "rr_policy_act");
   if (rc) return rc;
   const int nh = net.nlayers - 1, P = net.out_dim, A_ = P / 2;
-  if ((P & 1) || A_ > 64 || nh > RR_POL_MAXL - 1)
+  if ((P & 1) || P > head_cols(P) || nh > RR_POL_MAXL - 1)
     return fail(RR_EUNSUPPORTED, "rr_policy_act: a head of " + std::to_string(P) + " logits (it must be 2 x action_size <= 128 wide, at most 7 hidden layers)");
   if (workspace_bytes < rr_policy_act_workspace_bytes(M)) return fail(RR_EINVAL, "rr_policy_act: workspace too small");
   hipStream_t st = (hipStream_t)stream;
@@ -956,7 +970,7 @@ extern "C" int rr_policy_act(const float* obs, const int64_t* obs_rows, int32_t 
   T.action = action; T.raw = raw_action; T.logp = log_prob; T.logits = logits;
   for (int l = 1; l <= nh; ++l) T.W[l] = net.W[l];
   for (int l = 0; l <= nh; ++l) T.b[l] = net.b[l];
-  const int HW = P <= 64 ? 64 : 128;           // head columns in LDS (rr_policy_tail_kernel)
+  const int HW = head_cols(P);
   const size_t lds = ((size_t)(nh - 1) * 1024 + (size_t)32 * HW + (size_t)nh * 32 + HW) * sizeof(float);
   const dim3 grid(std::max(1, std::min(256, (M + 7) / 8)));
   if (HW == 64) hipLaunchKernelGGL(rr_policy_tail_kernel<64>, grid, dim3(256), lds, st, T);
@@ -987,11 +1001,7 @@ extern "C" int rr_mlp_value_backward(const float* grad_value, const float* head_
     A.Wt[j] = j > 0 ? hidden_weights_t[j] : nullptr;
   }
   const size_t lds = RR_MLP_BWD_LDS_FLOATS * sizeof(float);
-  static bool attr_set = false;
-  if (!attr_set) {
-    HIPCHK(hipFuncSetAttribute((const void*)rr_mlp_value_backward_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr_set = true;
-  }
+  if (const int rc = dyn_lds((const void*)rr_mlp_value_backward_kernel, lds)) return rc;
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(rr_mlp_value_backward_kernel, dim3(A.nblk), dim3(256), lds, st, A);
   hipLaunchKernelGGL(rr_mlp_colsum_kernel, dim3(RR_MLP_VH / 16, nhidden), dim3(256), 0, st, A);
@@ -1033,11 +1043,7 @@ template <int GO, int GI, int WO, int WI, int KC>
 static int dw_launch(const RRDwBatch& B, dim3 grid, hipStream_t st) {
   constexpr int TO = GO * WO * 32, TI = GI * WI * 32;
   constexpr size_t lds = (size_t)KC * ((TO + (TO % 64 == 0 ? 32 : 0)) + (TI + (TI % 64 == 0 ? 32 : 0))) * sizeof(float);
-  static bool attr_set = false;
-  if (!attr_set) {
-    HIPCHK(hipFuncSetAttribute((const void*)rr_mlp_dw_kernel<GO, GI, WO, WI, KC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr_set = true;
-  }
+  if (const int rc = dyn_lds((const void*)rr_mlp_dw_kernel<GO, GI, WO, WI, KC>, lds)) return rc;
   hipLaunchKernelGGL((rr_mlp_dw_kernel<GO, GI, WO, WI, KC>), grid, dim3(256), lds, st, B);
   return RR_OK;
 }

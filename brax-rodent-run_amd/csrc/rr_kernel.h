@@ -16,6 +16,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "rr_tanh_normal.h"
 
 #define RR_LANES 64
 #define RR_DOFI 12   // ints per dof in k_dof_i
@@ -2312,7 +2313,6 @@ struct RRTraj { int u, t; };
 static __device__ __forceinline__ RRTraj rr_traj(const RRIO& io, int s) { RRTraj r; r.u = s / io.a_seg; r.t = s - r.u * io.a_seg; return r; }
 static __device__ __forceinline__ size_t rr_traj_obs(const RRIO& io, int N, int env, int u, int t) { return ((size_t)u * N + env) * (io.a_seg + 1) + t; }   // row index
 static __device__ __forceinline__ size_t rr_traj_at(const RRIO& io, int N, int env, int s) { const RRTraj r = rr_traj(io, s); return ((size_t)r.u * N + env) * io.a_seg + r.t; }
-static __device__ __forceinline__ float rr_softplus_k(float x) { return fmaxf(x, 0.0f) + log1pf(expf(-fabsf(x))); }
 // EVAL (rr_eval_kernel): the observation comes from the env's two-row ring, a null noise pointer is the deterministic policy (raw = loc,
 // formed as loc + scale * 0 so that it equals the sampled form under all-zero noise bit for bit), and nothing but the action is recorded.
 template <bool EVAL = false, class DT>
@@ -2380,20 +2380,18 @@ __device__ __forceinline__ void rr_actor_step(const RRIO& io, const DT& D, int l
   }
   if constexpr (EVAL) {
     if (lane < A) {
-      const float scale = rr_softplus_k(s_raw) + io.a_min_std;
+      const float scale = rr_tn_scale(s_raw, io.a_min_std);
       const float nz = io.a_noise ? io.a_noise[((size_t)ut * num_envs + env) * A + lane] : 0.0f;
-      const float raw = o + scale * nz;
+      const float raw = rr_tn_raw(o, scale, nz);
       io.a_actions[((size_t)((io.a_pad & RR_EVAL_ACTIONS) ? ut : 0) * num_envs + env) * A + lane] = tanhf(raw);
     }
     return;
   }
   float lp = 0.0f;
   if (lane < A) {
-    const float HALF_LOG_2PI = 0.91893853320467274178f, LOG2 = 0.69314718055994530942f;
-    const float scale = rr_softplus_k(s_raw) + io.a_min_std;
-    const float raw = o + scale * io.a_noise[((size_t)ut * num_envs + env) * A + lane];
-    const float zz = (raw - o) / scale;
-    lp = -0.5f * zz * zz - logf(scale) - HALF_LOG_2PI - 2.0f * (LOG2 - raw - rr_softplus_k(-2.0f * raw));
+    const float scale = rr_tn_scale(s_raw, io.a_min_std);
+    const float raw = rr_tn_raw(o, scale, io.a_noise[((size_t)ut * num_envs + env) * A + lane]);
+    lp = rr_tn_logp(o, scale, raw);
     io.a_actions[((size_t)ut * num_envs + env) * A + lane] = tanhf(raw);
     io.t_raw[rr_traj_at(io, num_envs, env, ut) * A + lane] = raw;
   }

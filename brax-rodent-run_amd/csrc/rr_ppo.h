@@ -15,6 +15,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "rr_tanh_normal.h"
 
 struct RRPpoArgs {
   // network outputs on the gathered minibatch, time-major: logits [(T+1)*B][2A] (row t*B + b; the last B rows are the bootstrap
@@ -84,8 +85,6 @@ __global__ __launch_bounds__(256) void rr_ppo_gae_kernel(const RRPpoArgs P) {
   rr_block_sum<2>(s, sh, P.part_adv + blockIdx.x, P.nblk1);
 }
 
-static __device__ __forceinline__ float rr_softplus(float x) { return fmaxf(x, 0.0f) + log1pf(expf(-fabsf(x))); }
-
 __global__ __launch_bounds__(256) void rr_ppo_loss_kernel(const RRPpoArgs P) {
   __shared__ double sh[12];
   __shared__ float s_stat[2];
@@ -107,7 +106,6 @@ __global__ __launch_bounds__(256) void rr_ppo_loss_kernel(const RRPpoArgs P) {
   const int lane = threadIdx.x & 31;
   const int P2 = 2 * A;
   const float invn = 1.0f / (float)n;
-  const float HALF_LOG_2PI = 0.91893853320467274178f, LOG2 = 0.69314718055994530942f;
   double acc[3] = {0.0, 0.0, 0.0};
   // bootstrap rows: no gradient
   for (int i = blockIdx.x * 256 + threadIdx.x; i < B * P2; i += gridDim.x * 256) P.grad_logits[(size_t)n * P2 + i] = 0.0f;
@@ -120,11 +118,9 @@ __global__ __launch_bounds__(256) void rr_ppo_loss_kernel(const RRPpoArgs P) {
     float lp = 0.0f, ent = 0.0f;
     // pass 1: log-prob of the behaviour action under the current policy, entropy estimate (sums over the action dimensions)
     for (int a = lane; a < A; a += 32) {
-      const float loc = lg[a], sr = lg[A + a], scale = rr_softplus(sr) + P.min_std;
-      const float raw = P.raw_action[row * A + a], z = (raw - loc) / scale, ls = logf(scale);
-      lp += -0.5f * z * z - ls - HALF_LOG_2PI - 2.0f * (LOG2 - raw - rr_softplus(-2.0f * raw));
-      const float x = loc + scale * P.noise[(size_t)smp * A + a];
-      ent += 0.5f + HALF_LOG_2PI + ls + 2.0f * (LOG2 - x - rr_softplus(-2.0f * x));
+      const float loc = lg[a], scale = rr_tn_scale(lg[A + a], P.min_std);
+      lp += rr_tn_logp(loc, scale, P.raw_action[row * A + a]);
+      ent += rr_tn_entropy(scale, rr_tn_raw(loc, scale, P.noise[(size_t)smp * A + a]));
     }
 #pragma unroll
     for (int o = 16; o > 0; o >>= 1) { lp += __shfl_xor(lp, o, 32); ent += __shfl_xor(ent, o, 32); }
@@ -144,9 +140,9 @@ __global__ __launch_bounds__(256) void rr_ppo_loss_kernel(const RRPpoArgs P) {
     }
     // pass 2: gradient rows
     for (int a = lane; a < A; a += 32) {
-      const float loc = lg[a], sr = lg[A + a], scale = rr_softplus(sr) + P.min_std, is = 1.0f / scale;
+      const float loc = lg[a], sr = lg[A + a], scale = rr_tn_scale(sr, P.min_std), is = 1.0f / scale;
       const float raw = P.raw_action[row * A + a], z = (raw - loc) * is;
-      const float eps = P.noise[(size_t)smp * A + a], th = tanhf(loc + scale * eps);
+      const float eps = P.noise[(size_t)smp * A + a], th = tanhf(rr_tn_raw(loc, scale, eps));
       const float dloc = g_lp * z * is + g_h * (-2.0f * th);
       const float dscale = g_lp * (z * z - 1.0f) * is + g_h * (is - 2.0f * th * eps);
       const float sig = 1.0f / (1.0f + expf(-sr));         // softplus'
@@ -234,14 +230,12 @@ __global__ __launch_bounds__(256) void rr_policy_sample_kernel(const float* __re
   const int lane = threadIdx.x & 31;
   const int n = blockIdx.x * 8 + (threadIdx.x >> 5);
   if (n >= N) return;
-  const float HALF_LOG_2PI = 0.91893853320467274178f, LOG2 = 0.69314718055994530942f;
   const float* lg = logits + (size_t)n * 2 * A;
   float lp = 0.0f;
   for (int a = lane; a < A; a += 32) {
-    const float loc = lg[a], scale = rr_softplus(lg[A + a]) + min_std;
-    const float raw = loc + scale * noise[(size_t)n * A + a];
-    const float z = (raw - loc) / scale;
-    lp += -0.5f * z * z - logf(scale) - HALF_LOG_2PI - 2.0f * (LOG2 - raw - rr_softplus(-2.0f * raw));
+    const float loc = lg[a], scale = rr_tn_scale(lg[A + a], min_std);
+    const float raw = rr_tn_raw(loc, scale, noise[(size_t)n * A + a]);
+    lp += rr_tn_logp(loc, scale, raw);
     raw_out[(size_t)n * A + a] = raw;
     action[(size_t)n * A + a] = tanhf(raw);
   }
@@ -351,8 +345,8 @@ struct RRPolTailArgs {
   const float* noise; float min_std;
   float* action; float* raw; float* logp; float* logits;     // raw / logp / logits nullable
 };
-// W: head columns in LDS, 64 for P <= 64 and 128 above (the rule of acting.actor_params).  A template constant, so that the instance for
-// up to 32 actions is the kernel it was before the wide head existed, instruction for instruction.
+// W: head columns in LDS, 64 for P <= 64 and 128 above (head_cols, csrc/rr_api.hip).  A template constant: the head's loops over a lane's
+// W / 32 logits and W / 64 action dimensions unroll into registers.
 template <int W>
 __global__ __launch_bounds__(256) void rr_policy_tail_kernel(const RRPolTailArgs T) {
   extern __shared__ float sw[];                      // (nh - 1) x [32 k][32 n], then head [32 k][W n], then biases nh x 32 + W
@@ -365,7 +359,6 @@ __global__ __launch_bounds__(256) void rr_policy_tail_kernel(const RRPolTailArgs
   for (int e = threadIdx.x; e < T.nh * 32; e += 256) sb[e] = T.b[e >> 5][e & 31];
   for (int e = threadIdx.x; e < W; e += 256) sb[T.nh * 32 + e] = e < T.P ? T.b[T.nh][e] : 0.0f;
   __syncthreads();
-  const float HALF_LOG_2PI = 0.91893853320467274178f, LOG2 = 0.69314718055994530942f;
   for (int row = blockIdx.x * 8 + rg; row < T.M; row += gridDim.x * 8) {
     float z = sb[lane];
     for (int s = 0; s < T.nslice; ++s) z += T.part[((size_t)s * T.M + row) * 32 + lane];
@@ -377,80 +370,49 @@ __global__ __launch_bounds__(256) void rr_policy_tail_kernel(const RRPolTailArgs
       for (int k = 0; k < 32; ++k) acc = fmaf(__shfl(h, k, 32), w[k * 32 + lane], acc);
       h = acc / (1.0f + expf(-acc));
     }
-    if constexpr (W == 64) {
-      float o0 = sb[T.nh * 32 + lane], o1 = sb[T.nh * 32 + 32 + lane];
+    // the head: a lane forms the Q logits lane + 32 q and owns the D action dimensions a = lane + 32 d
+    constexpr int Q = W / 32, D = W / 64;
+    float o[Q], t[Q];
 #pragma unroll
-      for (int k = 0; k < 32; ++k) { const float hk = __shfl(h, k, 32); o0 = fmaf(hk, swh[k * 64 + lane], o0); o1 = fmaf(hk, swh[k * 64 + 32 + lane], o1); }
-      if (T.logits) {
-        if (lane < T.P) T.logits[(size_t)row * T.P + lane] = o0;
-        if (lane + 32 < T.P) T.logits[(size_t)row * T.P + 32 + lane] = o1;
-      }
-      // lane a needs logits[a] (its own o0) and logits[A + a]: o0 of lane A + a, or o1 of lane A + a - 32
-      const float s_lo = __shfl(o0, (T.A + lane) & 31, 32), s_hi = __shfl(o1, (T.A + lane - 32) & 31, 32);
-      const float sraw = T.A + lane < 32 ? s_lo : s_hi;
-      float lp = 0.0f;
-      if (lane < T.A) {
-        const float loc = o0;
+    for (int q = 0; q < Q; ++q) o[q] = sb[T.nh * 32 + 32 * q + lane];
+#pragma unroll
+    for (int k = 0; k < 32; ++k) {
+      const float hk = __shfl(h, k, 32);
+#pragma unroll
+      for (int q = 0; q < Q; ++q) o[q] = fmaf(hk, swh[k * W + 32 * q + lane], o[q]);
+    }
+    if (T.logits) {
+#pragma unroll
+      for (int q = 0; q < Q; ++q)
+        if (32 * q + lane < T.P) T.logits[(size_t)row * T.P + 32 * q + lane] = o[q];
+    }
+    // the scale logit of dimension a is column A + a: register (A + a) >> 5 of lane (A + a) & 31 (the same lane for every d)
+#pragma unroll
+    for (int q = 0; q < Q; ++q) t[q] = __shfl(o[q], (T.A + lane) & 31, 32);
+    float lp = 0.0f;
+#pragma unroll
+    for (int d = 0; d < D; ++d) {
+      const int a = lane + 32 * d, r = (T.A + a) >> 5;
+      const float loc = o[d];
+      float sraw = t[Q - 1];
+#pragma unroll
+      for (int q = Q - 2; q >= 0; --q) sraw = r == q ? t[q] : sraw;
+      if (a < T.A) {
         if (T.noise) {
-          const float scale = rr_softplus(sraw) + T.min_std;
-          const float eps = T.noise[(size_t)row * T.A + lane], raw = loc + scale * eps;
-          const float zz = (raw - loc) / scale;
-          lp = -0.5f * zz * zz - logf(scale) - HALF_LOG_2PI - 2.0f * (LOG2 - raw - rr_softplus(-2.0f * raw));
-          if (T.raw) T.raw[(size_t)row * T.A + lane] = raw;
-          T.action[(size_t)row * T.A + lane] = tanhf(raw);
+          const float scale = rr_tn_scale(sraw, T.min_std);
+          const float raw = rr_tn_raw(loc, scale, T.noise[(size_t)row * T.A + a]);
+          lp += rr_tn_logp(loc, scale, raw);
+          if (T.raw) T.raw[(size_t)row * T.A + a] = raw;
+          T.action[(size_t)row * T.A + a] = tanhf(raw);
         } else {
-          T.action[(size_t)row * T.A + lane] = tanhf(loc);
+          T.action[(size_t)row * T.A + a] = tanhf(loc);
         }
       }
-      if (T.noise && T.logp) {
+    }
+    if (T.noise && T.logp) {
 #pragma unroll
-        for (int o = 16; o > 0; o >>= 1) lp += __shfl_xor(lp, o, 32);
-        if (lane == 0) T.logp[row] = lp;
-      }
-    } else {
-      // 33 .. 64 actions: a lane forms the four logits lane + 32 q and owns the action dimensions a = lane and a = lane + 32
-      float o[4];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) o[q] = sb[T.nh * 32 + 32 * q + lane];
-#pragma unroll
-      for (int k = 0; k < 32; ++k) {
-        const float hk = __shfl(h, k, 32);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) o[q] = fmaf(hk, swh[k * 128 + 32 * q + lane], o[q]);
-      }
-      if (T.logits) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-          if (32 * q + lane < T.P) T.logits[(size_t)row * T.P + 32 * q + lane] = o[q];
-      }
-      // the scale logit of dimension a is logit A + a, 33 <= A <= 64: for a = lane it sits in o[1] or o[2] of lane (A + a) & 31, for
-      // a = lane + 32 one register further up in the same lane
-      const int src = (T.A + lane) & 31;
-      const float t1 = __shfl(o[1], src, 32), t2 = __shfl(o[2], src, 32), t3 = __shfl(o[3], src, 32);
-      const bool up = T.A + lane >= 64;
-      float lp = 0.0f;
-#pragma unroll
-      for (int d = 0; d < 2; ++d) {
-        const int a = lane + 32 * d;
-        const float loc = d ? o[1] : o[0], sraw = d ? (up ? t3 : t2) : (up ? t2 : t1);
-        if (a < T.A) {
-          if (T.noise) {
-            const float scale = rr_softplus(sraw) + T.min_std;
-            const float eps = T.noise[(size_t)row * T.A + a], raw = loc + scale * eps;
-            const float zz = (raw - loc) / scale;
-            lp += -0.5f * zz * zz - logf(scale) - HALF_LOG_2PI - 2.0f * (LOG2 - raw - rr_softplus(-2.0f * raw));
-            if (T.raw) T.raw[(size_t)row * T.A + a] = raw;
-            T.action[(size_t)row * T.A + a] = tanhf(raw);
-          } else {
-            T.action[(size_t)row * T.A + a] = tanhf(loc);
-          }
-        }
-      }
-      if (T.noise && T.logp) {
-#pragma unroll
-        for (int o_ = 16; o_ > 0; o_ >>= 1) lp += __shfl_xor(lp, o_, 32);
-        if (lane == 0) T.logp[row] = lp;
-      }
+      for (int x = 16; x > 0; x >>= 1) lp += __shfl_xor(lp, x, 32);
+      if (lane == 0) T.logp[row] = lp;
     }
   }
 }

@@ -178,6 +178,31 @@ def _ptr(t: Optional[torch.Tensor], dtype=torch.float32, numel: Optional[int] = 
     return t.data_ptr()
 
 
+def _dp(t: Optional[torch.Tensor]):
+    """data_ptr() of a tensor that has been checked already, None for None."""
+    return t.data_ptr() if t is not None else None
+
+
+def head_columns(P: int) -> int:
+    """Columns the in-kernel actor's head of P logits is padded to (`head_cols` in csrc/rr_api.hip): 64 up to 64 logits, 128 above."""
+    return 64 if P <= 64 else 128
+
+
+_scratch: dict = {}
+
+
+def _ws(bufs: Optional[dict], call: str, dev, shape_key, nbytes: int, dtype=torch.float32, shape=None) -> torch.Tensor:
+    """Device buffer of at least `nbytes` (or of `shape`) for `call`, one per (call, device, stream, shape key): scratch of a launch
+    must not be shared between streams or devices.  It lives in `bufs` when the caller keeps one (so a captured HIP graph sees the same
+    addresses for the life of that object), else in the module's dict, and is never replaced: the address is stable per key."""
+    store = _scratch if bufs is None else bufs
+    key = (call, dev, torch.cuda.current_stream(dev).cuda_stream, shape_key)
+    if key not in store:
+        item = dtype.itemsize
+        store[key] = torch.empty(shape if shape is not None else ((nbytes + item - 1) // item,), dtype=dtype, device=dev)
+    return store[key]
+
+
 class Model:
     """A compiled model loaded from an RRM1 blob (host side)."""
 
@@ -258,7 +283,7 @@ class Batch:
             raise ValueError(f"unknown rr_outputs field(s): {sorted(unknown)}")
         o = RROutputs()
         for k, w in sizes.items():
-            setattr(o, k, _ptr(out.get(k), numel=N * w) if out.get(k) is not None else None)
+            setattr(o, k, _ptr(out.get(k), numel=N * w))
         return o
 
     def _env(self, env) -> RREnvIO:
@@ -269,9 +294,9 @@ class Batch:
         e.track_len = tp.shape[0]
         e.cur_frame = _ptr(env["cur_frame"], torch.int32, N)
         e.obs = _ptr(env["obs"], numel=N * d.obs_dim)
-        e.reward = _ptr(env.get("reward"), numel=N) if env.get("reward") is not None else None
-        e.done = _ptr(env.get("done"), numel=N) if env.get("done") is not None else None
-        e.metrics = _ptr(env.get("metrics"), numel=3 * N) if env.get("metrics") is not None else None
+        e.reward = _ptr(env.get("reward"), numel=N)
+        e.done = _ptr(env.get("done"), numel=N)
+        e.metrics = _ptr(env.get("metrics"), numel=3 * N)
         e.healthy_reward = env.get("healthy_reward", 1.0)
         e.ctrl_cost_weight = env.get("ctrl_cost_weight", 0.1)
         e.healthy_z_min, e.healthy_z_max = env.get("healthy_z_range", (0.03, 0.5))
@@ -336,7 +361,7 @@ class Batch:
         form): obs [N, T+1, K], raw_action [N, T, A], log_prob / reward / discount / truncation [N, T] (contiguous views); with `segment`
         = L < T: U = T / L such blocks ([U, N, L+1, K], ...), a whole rollout phase of U unrolls."""
         N, A_, K = self.N, self.dims.nu, self.dims.obs_dim
-        HW = 64 if A_ <= 32 else 128                   # head layout: [32][64] up to 32 actions, [32][128] for 33 .. 64
+        HW = head_columns(2 * A_)
         bad = f"{who}: inconsistent shapes" if traj is not None else f"{who}: inconsistent actor shapes"
         if actor["w0"].shape != (32, K) or actor["head_wt"].shape != (32, HW) or actor["head_b"].numel() != HW or actor["b0"].numel() != 32:
             raise ValueError(bad)
@@ -383,8 +408,8 @@ class Batch:
         (final observation: obs_ring[:, T & 1])."""
         d, N = self.dims, self.N
         a = self._actor_io("rr_env_unroll_eval", actor, obs_in, T, noise, actions_out)
-        e = RREvalIO(_ptr(eval_metrics, numel=N * 6) if eval_metrics is not None else None, _ptr(obs_ring, numel=N * 2 * d.obs_dim),
-                     _ptr(qpos_out, numel=(T + 1) * N * d.nq) if qpos_out is not None else None, 0 if wrap is not None else 1)
+        e = RREvalIO(_ptr(eval_metrics, numel=N * 6), _ptr(obs_ring, numel=N * 2 * d.obs_dim), _ptr(qpos_out, numel=(T + 1) * N * d.nq),
+                     0 if wrap is not None else 1)
         w = self._unroll_io(wrap) if wrap is not None else None
         _check(lib().rr_env_unroll_eval(self.h, C.byref(self._state(st_in)), C.byref(self._state(st_out)), int(T), int(n_frames), C.byref(self._env(env)),
                                         _ptr(cur_frame_in, torch.int32, N), C.byref(w) if w is not None else None, C.byref(a), C.byref(e)))
@@ -401,14 +426,13 @@ class Batch:
     def set_profile(self, buf: Optional[torch.Tensor]):
         """Diagnostic: int64 device tensor [N,24] receiving per-phase cycle sums (None = off); slots 20 / 21 count the line searches'
         bracketing iterations executed / left out by the repeat exit."""
-        _check(lib().rr_batch_set_profile(self.h, buf.data_ptr() if buf is not None else None))
+        _check(lib().rr_batch_set_profile(self.h, _dp(buf)))
 
     def set_schedule(self, env_map: Optional[torch.Tensor], cost: Optional[torch.Tensor]):
         """workgroup -> environment map (int32 [N] device, a permutation) and per-env cycle output (int32 [N] device); None = off.
         The tensors must stay alive while the batch launches (C ABI `rr_batch_set_schedule`)."""
         self._sched = (env_map, cost)
-        _check(lib().rr_batch_set_schedule(self.h, _ptr(env_map, torch.int32, self.N) if env_map is not None else None,
-                                           _ptr(cost, torch.int32, self.N) if cost is not None else None))
+        _check(lib().rr_batch_set_schedule(self.h, _ptr(env_map, torch.int32, self.N), _ptr(cost, torch.int32, self.N)))
 
     def env_params_supported(self) -> bool:
         """Whether this batch's model / solver has kernel instances with per-env parameters (C ABI `rr_batch_env_params_supported`)."""
@@ -511,10 +535,8 @@ def mlp_forward(obs, mean=None, std=None, policy=None, value=None, want_pre=Fals
         if want_pre:
             val_pre = torch.empty(len(value[0]) - 1, M, 256, device=dev)
     stream = torch.cuda.current_stream(dev).cuda_stream
-    p = lambda t: t.data_ptr() if t is not None else None
-    _check(lib().rr_mlp_forward(obs.data_ptr(), rows.data_ptr() if rows is not None else None, M, K, _ptr(mean, numel=K) if mean is not None else None,
-                                _ptr(std, numel=K) if std is not None else None, C.byref(pn) if pn is not None else None,
-                                C.byref(vn) if vn is not None else None, p(pol_out), p(val_out), p(pol_pre), p(val_pre), C.c_void_p(stream)))
+    _check(lib().rr_mlp_forward(obs.data_ptr(), _dp(rows), M, K, _ptr(mean, numel=K), _ptr(std, numel=K), C.byref(pn) if pn is not None else None,
+                                C.byref(vn) if vn is not None else None, _dp(pol_out), _dp(val_out), _dp(pol_pre), _dp(val_pre), C.c_void_p(stream)))
     return pol_out, val_out, pol_pre, val_pre
 
 
@@ -549,13 +571,10 @@ def ppo_loss(policy_logits, values, data, idx, noise, T: int, *, entropy_cost, d
     stream = torch.cuda.current_stream(dev).cuda_stream
     _check(lib().rr_ppo_loss(policy_logits.data_ptr(), values.data_ptr(), data["raw_action"].data_ptr(), data["log_prob"].data_ptr(),
                              data["reward"].data_ptr(), data["discount"].data_ptr(), data["truncation"].data_ptr(),
-                             idx.data_ptr() if idx is not None else None, noise.data_ptr(), T, B, A, C.byref(cfg),
+                             _dp(idx), noise.data_ptr(), T, B, A, C.byref(cfg),
                              out["grad_logits"].data_ptr(), out["grad_values"].data_ptr(), out["metrics"].data_ptr(),
                              out["workspace"].data_ptr(), out["workspace"].numel() * 8, C.c_void_p(stream)))
     return out["grad_logits"], out["grad_values"], out["metrics"]
-
-
-_silu_ws = {}
 
 
 def mlp_silu_backward(g, z, bias_grad):
@@ -563,11 +582,7 @@ def mlp_silu_backward(g, z, bias_grad):
     `rr_mlp_silu_backward`).  g, z: [M, H] contiguous float32 device tensors.  Returns (delta, h) = (g, z)."""
     M, H = g.shape
     _ptr(g); _ptr(z, numel=M * H); _ptr(bias_grad, numel=H)
-    wb = lib().rr_mlp_silu_backward_workspace_bytes(M, H)
-    key = (g.device, M, H, torch.cuda.current_stream(g.device).cuda_stream)      # per stream: the workspace is scratch of the launch
-    if key not in _silu_ws:
-        _silu_ws[key] = torch.empty((wb + 3) // 4, device=g.device)
-    ws = _silu_ws[key]
+    ws = _ws(None, "silu_bwd", g.device, (M, H), lib().rr_mlp_silu_backward_workspace_bytes(M, H))
     _check(lib().rr_mlp_silu_backward(g.data_ptr(), z.data_ptr(), M, H, g.data_ptr(), z.data_ptr(), bias_grad.data_ptr(), ws.data_ptr(), ws.numel() * 4,
                                       C.c_void_p(torch.cuda.current_stream(g.device).cuda_stream)))
     return g, z
@@ -587,20 +602,14 @@ def mlp_value_backward(grad_value, head_weight, hidden_weights_t, pre_act, bias_
         _ptr(bias_grads[j], numel=256)
         if j > 0:
             _ptr(hidden_weights_t[j], numel=256 * 256)
-    bufs = bufs if bufs is not None else {}
-    wb = lib().rr_mlp_value_backward_workspace_bytes(M, nh)
-    if bufs.get("vb_key") != (M, nh):
-        bufs["vb_ws"] = torch.empty((wb + 3) // 4, device=pre_act.device)
-        bufs["vb_delta"] = torch.empty_like(pre_act)
-        bufs["vb_key"] = (M, nh)
+    dev, bufs = pre_act.device, {} if bufs is None else bufs      # no `bufs`: a fresh delta per call (it is an output)
+    ws = _ws(bufs, "value_bwd", dev, (M, nh), lib().rr_mlp_value_backward_workspace_bytes(M, nh))
+    delta = _ws(bufs, "value_bwd_delta", dev, (M, nh), 0, shape=pre_act.shape)
     wt = (C.c_void_p * nh)(*[hidden_weights_t[j].data_ptr() if j > 0 else None for j in range(nh)])
     bg = (C.c_void_p * nh)(*[b.data_ptr() for b in bias_grads])
-    _check(lib().rr_mlp_value_backward(grad_value.data_ptr(), head_weight.data_ptr(), wt, nh, M, pre_act.data_ptr(), bufs["vb_delta"].data_ptr(), bg,
-                                       bufs["vb_ws"].data_ptr(), bufs["vb_ws"].numel() * 4, C.c_void_p(torch.cuda.current_stream(pre_act.device).cuda_stream)))
-    return bufs["vb_delta"], pre_act
-
-
-_dw_ws = {}
+    _check(lib().rr_mlp_value_backward(grad_value.data_ptr(), head_weight.data_ptr(), wt, nh, M, pre_act.data_ptr(), delta.data_ptr(), bg,
+                                       ws.data_ptr(), ws.numel() * 4, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    return delta, pre_act
 
 
 def mlp_weight_grad(delta, act, out, rows=None, mean=None, std=None, delta_colsum=None):
@@ -614,13 +623,10 @@ def mlp_weight_grad(delta, act, out, rows=None, mean=None, std=None, delta_colsu
         _ptr(rows, torch.int64, M)
     elif act.shape[0] < M:
         raise ValueError("rr_mlp_weight_grad: fewer activation rows than delta rows")
-    key = (delta.device, M, O, I, torch.cuda.current_stream(delta.device).cuda_stream)      # per stream (scratch of the launch)
-    if key not in _dw_ws:
-        _dw_ws[key] = torch.empty((lib().rr_mlp_weight_grad_workspace_bytes(M, O, I) + 3) // 4, device=delta.device)
-    ws = _dw_ws[key]
-    _check(lib().rr_mlp_weight_grad(delta.data_ptr(), act.data_ptr(), rows.data_ptr() if rows is not None else None,
-                                    _ptr(mean, numel=I) if mean is not None else None, _ptr(std, numel=I) if std is not None else None,
-                                    _ptr(delta_colsum, numel=O) if mean is not None else None, M, O, I, out.data_ptr(), ws.data_ptr(), ws.numel() * 4, C.c_void_p(torch.cuda.current_stream(delta.device).cuda_stream)))
+    ws = _ws(None, "weight_grad", delta.device, (M, O, I), lib().rr_mlp_weight_grad_workspace_bytes(M, O, I))
+    _check(lib().rr_mlp_weight_grad(delta.data_ptr(), act.data_ptr(), _dp(rows), _ptr(mean, numel=I), _ptr(std, numel=I),
+                                    _ptr(delta_colsum, numel=O) if mean is not None else None, M, O, I, out.data_ptr(), ws.data_ptr(), ws.numel() * 4,
+                                    C.c_void_p(torch.cuda.current_stream(delta.device).cuda_stream)))
     return out
 
 
@@ -630,11 +636,7 @@ def obs_moments(obs, T: int, mean, bufs=None):
     K, Tp1 = obs.shape[-1], obs.shape[-2]
     nseq = obs.numel() // (Tp1 * K)
     _ptr(obs); _ptr(mean, numel=K)
-    nb = lib().rr_obs_moments_workspace_bytes(nseq, T, K)
-    bufs = {} if bufs is None else bufs
-    ws = bufs.get("mom_ws")
-    if ws is None or ws.numel() * 8 < nb or ws.device != obs.device:
-        ws = bufs["mom_ws"] = torch.empty((nb + 7) // 8, dtype=torch.float64, device=obs.device)
+    ws = _ws(bufs, "obs_moments", obs.device, (nseq, T, K), lib().rr_obs_moments_workspace_bytes(nseq, T, K), torch.float64)
     sums = torch.empty(2, K, dtype=torch.float64, device=obs.device)
     _check(lib().rr_obs_moments(obs.data_ptr(), nseq, Tp1, T, K, mean.data_ptr(), sums.data_ptr(), ws.data_ptr(), ws.numel() * 8,
                                 C.c_void_p(torch.cuda.current_stream(obs.device).cuda_stream)))
@@ -668,19 +670,14 @@ def policy_backward(grad_logits, head_weight, hidden_weights, pre_act, bias_grad
         _ptr(bias_grads[j], numel=32)
         if j > 0:
             _ptr(hidden_weights[j], numel=1024)
-    bufs = bufs if bufs is not None else {}
-    if bufs.get("pb_key") != (M, nh):
-        bufs["pb_ws"] = torch.empty((lib().rr_policy_backward_workspace_bytes(M, nh) + 3) // 4, device=pre_act.device)
-        bufs["pb_delta"] = torch.empty(nh, M, 32, device=pre_act.device)
-        bufs["pb_key"] = (M, nh)
+    dev, bufs = pre_act.device, {} if bufs is None else bufs      # no `bufs`: a fresh delta per call (it is an output)
+    ws = _ws(bufs, "policy_bwd", dev, (M, nh), lib().rr_policy_backward_workspace_bytes(M, nh))
+    delta = _ws(bufs, "policy_bwd_delta", dev, (M, nh), 0, shape=(nh, M, 32))
     wt = (C.c_void_p * nh)(*[hidden_weights[j].data_ptr() if j > 0 else None for j in range(nh)])
     bg = (C.c_void_p * nh)(*[b.data_ptr() for b in bias_grads])
-    _check(lib().rr_policy_backward(grad_logits.data_ptr(), head_weight.data_ptr(), wt, nh, M, P, pre_act.data_ptr(), pre_act.shape[1], bufs["pb_delta"].data_ptr(), bg,
-                                    bufs["pb_ws"].data_ptr(), bufs["pb_ws"].numel() * 4, C.c_void_p(torch.cuda.current_stream(pre_act.device).cuda_stream)))
-    return bufs["pb_delta"], pre_act
-
-
-_pa_ws = {}
+    _check(lib().rr_policy_backward(grad_logits.data_ptr(), head_weight.data_ptr(), wt, nh, M, P, pre_act.data_ptr(), pre_act.shape[1], delta.data_ptr(), bg,
+                                    ws.data_ptr(), ws.numel() * 4, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    return delta, pre_act
 
 
 def policy_act(obs, mean, std, policy, noise, min_std: float, want_logits: bool = False, rows=None):
@@ -703,18 +700,10 @@ def policy_act(obs, mean, std, policy, noise, min_std: float, want_logits: bool 
     if want_logits:
         logits = torch.empty(M, 2 * A, device=dev)
     stream = torch.cuda.current_stream(dev).cuda_stream
-    key = (dev, M, stream)                 # per stream: sub-batches on several streams run this concurrently
-    if key not in _pa_ws:
-        _pa_ws[key] = torch.empty((lib().rr_policy_act_workspace_bytes(M) + 3) // 4, device=dev)
-    ws = _pa_ws[key]
-    p = lambda t: t.data_ptr() if t is not None else None
-    _check(lib().rr_policy_act(obs.data_ptr(), p(rows), M, K, _ptr(mean, numel=K) if mean is not None else None,
-                               _ptr(std, numel=K) if std is not None else None, C.byref(pn), p(noise), min_std, action.data_ptr(), p(raw), p(lp),
-                               p(logits), ws.data_ptr(), ws.numel() * 4, C.c_void_p(stream)))
+    ws = _ws(None, "policy_act", dev, M, lib().rr_policy_act_workspace_bytes(M))      # per stream: sub-batches on several streams run this concurrently
+    _check(lib().rr_policy_act(obs.data_ptr(), _dp(rows), M, K, _ptr(mean, numel=K), _ptr(std, numel=K), C.byref(pn), _dp(noise), min_std, action.data_ptr(),
+                               _dp(raw), _dp(lp), _dp(logits), ws.data_ptr(), ws.numel() * 4, C.c_void_p(stream)))
     return action, raw, lp, logits
-
-
-_dwb_ws = {}
 
 
 def mlp_weight_grad_batch(items):
@@ -735,13 +724,8 @@ def mlp_weight_grad_batch(items):
             _ptr(rows, torch.int64, M)
         elif act.shape[0] < M:
             raise ValueError("rr_mlp_weight_grad_batch: fewer activation rows than delta rows")
-        p = lambda t: t.data_ptr() if t is not None else None
-        arr[i] = RRDwItem(delta.data_ptr(), act.data_ptr(), p(rows), _ptr(mean, numel=I) if mean is not None else None,
-                          _ptr(std, numel=I) if std is not None else None, _ptr(cs, numel=O) if mean is not None else None, M, O, I, out.data_ptr())
+        arr[i] = RRDwItem(delta.data_ptr(), act.data_ptr(), _dp(rows), _ptr(mean, numel=I), _ptr(std, numel=I),
+                          _ptr(cs, numel=O) if mean is not None else None, M, O, I, out.data_ptr())
         shape_key.append((M, O, I))
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    key = (dev, tuple(shape_key), stream)
-    if key not in _dwb_ws:
-        _dwb_ws[key] = torch.empty((lib().rr_mlp_weight_grad_batch_workspace_bytes(arr, n) + 3) // 4, device=dev)
-    ws = _dwb_ws[key]
-    _check(lib().rr_mlp_weight_grad_batch(arr, n, ws.data_ptr(), ws.numel() * 4, C.c_void_p(stream)))
+    ws = _ws(None, "weight_grad_batch", dev, tuple(shape_key), lib().rr_mlp_weight_grad_batch_workspace_bytes(arr, n))
+    _check(lib().rr_mlp_weight_grad_batch(arr, n, ws.data_ptr(), ws.numel() * 4, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))

@@ -9,6 +9,7 @@ from typing import Callable, Dict, Optional
 
 import torch
 
+from .. import hip
 from ..envs import wrappers
 
 
@@ -61,7 +62,7 @@ def actor_params(policy_net, normalizer_params, min_std: float) -> dict:
     P = layers[-1].out_features
     if P > 2 * ACTOR_MAX_ACTIONS:
         raise ValueError(f"actor_params: a head of {P} outputs exceeds the in-kernel actor's {2 * ACTOR_MAX_ACTIONS}")
-    W = 64 if P <= 64 else 128
+    W = hip.head_columns(P)
     head_wt = torch.zeros(32, W, device=dev)
     head_wt[:, :P] = layers[-1].weight.detach().t()
     head_b = torch.zeros(W, device=dev)

@@ -4,10 +4,17 @@ backward pass, as one `torch.autograd.Function`.
 Replaces, for the `make_ppo_networks` default shapes (policy obs -> 32 x4 -> 2*action_size, value obs -> 256 x5 -> 1, SiLU),
 the ~40 library launches of `normalize -> policy_net -> value_net` in `ppo.losses.compute_ppo_loss`'s forward
 [UP brax.training.agents.ppo.losses; SURVEY.md a22 / a25] by ONE launch that reads the observation tile once for both
-networks.  The kernel also writes the hidden pre-activations, from which `backward` forms the parameter gradients with plain
-matrix products (rocBLAS/hipBLASLt): dW_l = delta_l' h_{l-1},
-delta_{l-1} = silu_backward(delta_l W_l, z_{l-1}); the first layer's dW uses the raw observations and folds the normaliser
-in afterwards, so the normalised copy of the minibatch is never written.
+networks.  The kernel also writes the hidden pre-activations.  Two backward passes read them:
+
+* the learner's default on a GPU, `agents/ppo/fused_update.FusedUpdate`, takes no autograd graph at all: `hip.mlp_forward` with the
+  minibatch addressed in place, `rr_ppo_loss`, then the delta chains (`rr_mlp_value_backward` on the matrix cores, `rr_policy_backward`)
+  and every dW = delta' h as a split-row matrix-core product (`rr_mlp_weight_grad_batch`), all hand-written kernels;
+* `_ActorCritic.backward` below, the path under `compute_ppo_loss` + `loss.backward()` (`RR_FUSED_LOSS=0`, and what the tests hold
+  `FusedUpdate` against), forms the same gradients with library matrix products (rocBLAS / hipBLASLt) and `silu_backward`:
+  dW_l = delta_l' h_{l-1}, delta_{l-1} = silu_backward(delta_l W_l, z_{l-1}).
+
+In both, the first layer's dW uses the raw observations and folds the normaliser in afterwards, so the normalised copy of the
+minibatch is never written.
 """
 from __future__ import annotations
 
