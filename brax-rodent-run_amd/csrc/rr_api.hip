@@ -876,13 +876,14 @@ static int dyn_lds(const void* kernel, size_t bytes) {
   }
   return RR_OK;
 }
-static int mlp_net(const rr_mlp_net* n, int K, int hidden, bool is_value, RRMlpNet* out, const char* who, const char* fn = "rr_mlp_forward") {
+static int mlp_net(const rr_mlp_net* n, int K, int hidden, bool is_value, RRMlpNet* out, const char* who, const char* fn = "rr_mlp_forward",
+                   const char* widths = nullptr) {
   memset(out, 0, sizeof(*out));
   if (!n) return RR_OK;
   if (!n->weights || !n->biases || !n->sizes || n->nlayers < 2 || n->nlayers > RR_MLP_MAXL) return fail(RR_EINVAL, std::string(fn) + ": bad " + who + " network description");
   if (n->sizes[0] != K) return fail(RR_EINVAL, std::string(fn) + ": " + who + " input width differs from the observation width");
   for (int l = 1; l < n->nlayers; ++l)
-    if (n->sizes[l] != hidden) return fail(RR_EUNSUPPORTED, std::string(fn) + ": " + who + " hidden width must be " + std::to_string(hidden));
+    if (n->sizes[l] != hidden) return fail(RR_EUNSUPPORTED, std::string(fn) + ": " + who + " hidden width must be " + (widths ? std::string(widths) : std::to_string(hidden)));
   const int od = n->sizes[n->nlayers];
   if (is_value ? od != 1 : (od < 1 || od > 128))
     return fail(RR_EUNSUPPORTED, std::string(fn) + ": unsupported " + who + " output width " + std::to_string(od) + (is_value ? " (the value head is 1 wide)" : " (1 .. 128 logits are supported)"));
@@ -902,10 +903,26 @@ extern "C" int rr_mlp_forward(const float* obs, const int64_t* obs_rows, int32_t
   RRMlpArgs A;
   memset(&A, 0, sizeof(A));
   int rc;
-  if ((rc = mlp_net(policy, K, RR_MLP_PH, false, &A.pol, "policy")) || (rc = mlp_net(value, K, RR_MLP_VH, true, &A.val, "value"))) return rc;
+  // a policy whose first hidden layer is 256 wide is held to 256 in every hidden layer and runs as a launch of its own
+  // (rr_mlp_policy256_forward_kernel) next to the value network's; any other policy is held to 32 and shares the value network's launch
+  const bool wide = policy && policy->sizes && policy->nlayers >= 2 && policy->sizes[1] == RR_MLP_VH;
+  if ((rc = mlp_net(policy, K, wide ? RR_MLP_VH : RR_MLP_PH, false, &A.pol, "policy", "rr_mlp_forward", "32 or 256, the same in every hidden layer")) ||
+      (rc = mlp_net(value, K, RR_MLP_VH, true, &A.val, "value"))) return rc;
   A.obs = obs; A.rows = obs_rows; A.M = M; A.K = K; A.mean = mean; A.std_ = std_;
   A.pol_out = policy_out; A.val_out = value_out; A.pol_act = policy ? policy_pre : nullptr; A.val_act = value ? value_pre : nullptr;
   const size_t lds = RR_MLP_LDS_FLOATS * sizeof(float);
+  if (wide) {
+    RRMlpArgs W = A;
+    memset(&W.val, 0, sizeof(W.val));
+    W.val_out = W.val_act = nullptr;
+    if ((rc = dyn_lds((const void*)rr_mlp_policy256_forward_kernel, lds))) return rc;
+    hipLaunchKernelGGL(rr_mlp_policy256_forward_kernel, dim3((M + RR_MLP_BM - 1) / RR_MLP_BM), dim3(256), lds, (hipStream_t)stream, W);
+    HIPCHK(hipGetLastError());
+    if (!value) return RR_OK;
+    memset(&A.pol, 0, sizeof(A.pol));           // the value network: the launch a value-only call makes
+    A.pol_out = A.pol_act = nullptr;
+    policy = nullptr;
+  }
   typedef void (*fwd_t)(const RRMlpArgs);
   const fwd_t kern = policy && value ? (fwd_t)rr_mlp_forward_kernel<true, true> : (value ? (fwd_t)rr_mlp_forward_kernel<true, false> : (fwd_t)rr_mlp_forward_kernel<false, true>);
   if ((rc = dyn_lds((const void*)kern, lds))) return rc;
@@ -1005,6 +1022,38 @@ extern "C" int rr_mlp_value_backward(const float* grad_value, const float* head_
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(rr_mlp_value_backward_kernel, dim3(A.nblk), dim3(256), lds, st, A);
   hipLaunchKernelGGL(rr_mlp_colsum_kernel, dim3(RR_MLP_VH / 16, nhidden), dim3(256), 0, st, A);
+  HIPCHK(hipGetLastError());
+  return RR_OK;
+}
+
+// 256-wide policy network backward: the value chain with a [n x P] . [P x 256] product at the head (csrc/rr_mlp.h)
+extern "C" size_t rr_mlp_policy_backward_workspace_bytes(int32_t n, int32_t nhidden) { return rr_mlp_value_backward_workspace_bytes(n, nhidden); }
+extern "C" int rr_mlp_policy_backward(const float* grad_logits, const float* head_weight_t, const float* const* hidden_weights_t, int32_t nhidden,
+                                      int32_t n, int32_t M, int32_t P, float* pre_act, float* delta, float* const* bias_grads, void* workspace,
+                                      size_t workspace_bytes, void* stream) {
+  if (!grad_logits || !head_weight_t || !hidden_weights_t || !pre_act || !delta || !bias_grads || !workspace || n <= 0 || M < n)
+    return fail(RR_EINVAL, "rr_mlp_policy_backward: bad argument");
+  if (P < 1 || P > 128) return fail(RR_EUNSUPPORTED, "rr_mlp_policy_backward: a head of " + std::to_string(P) + " logits (1 .. 128 are supported)");
+  if (nhidden < 1 || nhidden > RR_MLP_MAXL - 1)
+    return fail(RR_EUNSUPPORTED, "rr_mlp_policy_backward: " + std::to_string(nhidden) + " hidden layers (1 .. 7 are supported)");
+  if (workspace_bytes < rr_mlp_policy_backward_workspace_bytes(n, nhidden)) return fail(RR_EINVAL, "rr_mlp_policy_backward: workspace too small");
+  RRPol256BwdArgs A;
+  RRMlpBwdArgs S;                                // what rr_mlp_colsum_kernel reads: part, nblk, bgrad
+  memset(&A, 0, sizeof(A));
+  memset(&S, 0, sizeof(S));
+  A.g = grad_logits; A.wt_head = head_weight_t; A.z = pre_act; A.delta = delta; A.part = (float*)workspace; A.n = n; A.M = M; A.P = P; A.nh = nhidden;
+  A.nblk = (n + RR_MLP_BM - 1) / RR_MLP_BM;
+  S.part = A.part; S.nblk = A.nblk; S.M = n; S.nh = nhidden;
+  for (int j = 0; j < nhidden; ++j) {
+    if (!bias_grads[j] || (j > 0 && !hidden_weights_t[j])) return fail(RR_EINVAL, "rr_mlp_policy_backward: null layer pointer");
+    S.bgrad[j] = bias_grads[j];
+    A.Wt[j] = j > 0 ? hidden_weights_t[j] : nullptr;
+  }
+  const size_t lds = RR_MLP_BWD_LDS_FLOATS * sizeof(float);
+  if (const int rc = dyn_lds((const void*)rr_mlp_policy256_backward_kernel, lds)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(rr_mlp_policy256_backward_kernel, dim3(A.nblk), dim3(256), lds, st, A);
+  hipLaunchKernelGGL(rr_mlp_colsum_kernel, dim3(RR_MLP_VH / 16, nhidden), dim3(256), 0, st, S);
   HIPCHK(hipGetLastError());
   return RR_OK;
 }

@@ -40,7 +40,7 @@ struct RRMlpArgs {
   RRMlpNet pol, val;                         // nlayers == 0: that network is skipped
   float* pol_out;                            // [M][pol.out_dim]
   float* val_out;                            // [M]
-  float* pol_act;                            // nullable: [pol.nlayers-1][M][32]   hidden PRE-activations z = h W' + b (for a backward pass)
+  float* pol_act;                            // nullable: [pol.nlayers-1][M][32]   hidden PRE-activations z = h W' + b (for a backward pass); rr_mlp_policy256_forward_kernel: [..][M][256]
   float* val_act;                            // nullable: [val.nlayers-1][M][256]
   unsigned long long* prof;                  // nullable, diagnostic (RR_MLP_PROF): [workgroups][16] shader-clock stamps per phase
 };
@@ -753,5 +753,195 @@ __global__ __launch_bounds__(256) void rr_policy_l1_kernel(const RRPolL1Args A) 
   for (int r = 0; r < 4; ++r) {
     const int m = row0 + 16 * mt + 4 * (lane >> 4) + r;
     if (m < M) dst[(size_t)m * RR_MLP_PH + n] = ap[r];
+  }
+}
+
+// ------------------------------------------------------------------------------------------ a policy network with 256-wide hidden layers
+// A policy obs -> 256 x (1 .. 7) -> P logits (P <= 128) is the value network's shape with a head that is a [256 x P] product instead of a
+// dot product, so both directions reuse the value path's pieces: rr_mlp_chunk<true, false>, rr_mlp_hidden_layer, rr_mlp_store_val forward;
+// rr_mlp_bwd_epilogue<false>, rr_mlp_colsum_kernel backward.  Forward and backward therefore share rr_sigmoid_val with the value network.
+// No in-kernel actor evaluates this shape: the rollout's actor step and the learner's forward are this one kernel, so the same observation
+// row gives the same logits in both, whatever the row count of the call (a row's result depends on no other row of its tile).
+//
+// Forward.  Layer 1 is the value path's k-loop (observation chunk normalised when it is committed, `rows` indirection, rows clamped into
+// the batch, partial last chunk).  The head runs on v_mfma_f32_32x32x2_f32 with the fragment layout of the hidden layers (conflict-free
+// reads of the [32][258] tile): the 128 head columns are four 32-column tiles, wave wv owns columns [32 wv, 32 wv + 32) and leaves at once
+// when they lie past P, so a head of up to 64 logits is half the matrix work of one of 65 .. 128 and neither takes a second pass over the
+// activations.  The head's weight rows [P][256] are staged 128 at a time, clamped to row P - 1 (the duplicates feed columns never stored).
+__global__ __launch_bounds__(256, RR_MLP_FWD_WGS) void rr_mlp_policy256_forward_kernel(const RRMlpArgs A) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  float* actV = lds;                                 // region A: [32][258] activations ...
+  float* sX = lds;                                   //   ... during layer 1: [32][18] normalised observation chunk
+  float* sW = sX + RR_MLP_BM * RR_SX;                //   ... and [256][18] weight chunk
+  float* sB = lds + RR_MLP_LDS_A;                    // region B: [256][18] weight chunks of the hidden layers, [128][18] of the head
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int row0 = blockIdx.x * RR_MLP_BM;
+  const int M = A.M, K = A.K;
+  rr_f16 a0 = {0}, a1 = {0};
+  rr_f4 ap = {0, 0, 0, 0};
+  // ------------------------------------------------------------------ layer 1: K -> 256
+  {
+    typedef RRStage<RR_MLP_BM> Sx;
+    Sx gx;
+    RRStage<RR_MLP_VH> gw;
+    rr_f4 mu[Sx::PER], sd[Sx::PER];
+    const int nchunk = (K + RR_MLP_KC - 1) / RR_MLP_KC;
+    long long xoff[Sx::PER];
+#pragma unroll
+    for (int i = 0; i < Sx::PER; ++i) {
+      const int v = min((int)threadIdx.x + 256 * i, Sx::NV - 1), m = min(row0 + (v >> 2), M - 1);   // clamped: see RRStage
+      xoff[i] = (long long)(A.rows ? A.rows[m] : m) * K;
+    }
+    auto fetch_t = [&](int c, auto full) {
+      constexpr bool FULL = decltype(full)::value;
+      const int k0 = c * RR_MLP_KC;
+      gx.template fetch_at<FULL>(A.obs, xoff, k0, K);
+      if (A.mean) {                        // applied at commit time (see rr_mlp_forward_kernel)
+#pragma unroll
+        for (int i = 0; i < Sx::PER; ++i) {
+          const int k = k0 + 4 * ((threadIdx.x + 256 * i) & 3);
+          mu[i] = Sx::template load4<FULL>(A.mean, k, K);
+          sd[i] = Sx::template load4<FULL>(A.std_, k, K);
+          if (!FULL) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) sd[i][j] = k + j < K ? sd[i][j] : 1.0f;
+          }
+        }
+      }
+      gw.template fetch<FULL>(A.pol.W[0], K, 0, RR_MLP_VH, k0, K);
+    };
+    auto fetch = [&](int c) {              // uniform branch: only the last chunk can be partial
+      if ((c + 1) * RR_MLP_KC <= K) fetch_t(c, std::true_type{});
+      else fetch_t(c, std::false_type{});
+    };
+    fetch(0);
+    for (int c = 0; c < nchunk; ++c) {
+      if (A.mean) {
+#pragma unroll
+        for (int i = 0; i < Sx::PER; ++i)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) gx.r[i][j] = (gx.r[i][j] - mu[i][j]) / sd[i][j];
+      }
+      gx.commit(sX);
+      gw.commit(sW);
+      __syncthreads();
+      if (c + 1 < nchunk) fetch(c + 1);
+      rr_mlp_chunk<true, false>(sX, RR_SX, 0, sW, 0, a0, a1, ap, lane, wv);
+      __syncthreads();
+    }
+    rr_mlp_store_val(actV, a0, a1, A.pol.b[0], lane, wv, A.pol_act, row0, M);
+    __syncthreads();
+  }
+  // ------------------------------------------------------------------ hidden layers 256 -> 256
+  for (int l = 1; l < A.pol.nlayers - 1; ++l) {
+    a0 = rr_f16{0}; a1 = rr_f16{0};
+    rr_mlp_hidden_layer(A.pol.W[l], actV, sB, a0, a1, ap, lane, wv);
+    rr_mlp_store_val(actV, a0, a1, A.pol.b[l], lane, wv, A.pol_act ? A.pol_act + (size_t)l * M * RR_MLP_VH : nullptr, row0, M);
+    __syncthreads();
+  }
+  // ------------------------------------------------------------------ head 256 -> P
+  {
+    const int l = A.pol.nlayers - 1, P = A.pol.out_dim;
+    constexpr int HR = 128, nchunk = RR_MLP_VH / RR_MLP_KC;
+    const bool mine = 32 * wv < P;                   // wave-uniform
+    RRStage<HR> g;
+    rr_f16 acc = {0};
+    g.fetch<true>(A.pol.W[l], RR_MLP_VH, 0, P, 0, RR_MLP_VH);
+#pragma unroll 1
+    for (int c = 0; c < nchunk; ++c) {
+      g.commit(sB);
+      __syncthreads();
+      if (c + 1 < nchunk) g.fetch<true>(A.pol.W[l], RR_MLP_VH, 0, P, (c + 1) * RR_MLP_KC, RR_MLP_VH);
+      if (mine) {
+        const float* xr = actV + (lane & 31) * RR_SV + c * RR_MLP_KC + (lane >> 5);
+        const float* w0 = sB + (32 * wv + (lane & 31)) * RR_SX + (lane >> 5);
+#pragma unroll
+        for (int kk = 0; kk < RR_MLP_KC; kk += 2) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(xr[kk], w0[kk], acc, 0, 0, 0);
+      }
+      __syncthreads();
+    }
+    const int n = 32 * wv + (lane & 31);
+    if (n < P) {
+      const float bn = A.pol.b[l][n];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int m = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        if (row0 + m < M) A.pol_out[(size_t)(row0 + m) * P + n] = acc[r] + bn;
+      }
+    }
+  }
+}
+
+// Backward: the value network's delta chain with the head step a product, delta_{nh-1} = (G W_head) * silu'(z_{nh-1}), G [n][P].  The G
+// tile [32][P rounded up to 16] sits in the cells of the delta tile during that product (the last chunk ends with a barrier before the
+// epilogue overwrites them); the B operand is W_head transposed, [256][P] row-major, so k = P: the last chunk is partial when P % 16 != 0
+// and the chunk count may be odd.  g covers the first n <= M rows of the forward's dump [nh][M][256]: rows n .. M - 1 (a minibatch's
+// bootstrap rows) carry no policy gradient and are neither read nor written.
+struct RRPol256BwdArgs {
+  const float* g;                    // [n][P]  d loss / d logits
+  const float* wt_head;              // [256][P]  the head's weight transposed
+  const float* Wt[RR_MLP_MAXL];      // Wt[j], j = 1 .. nh-1: W_j transposed, [256 in][256 out]
+  float* z;                          // [nh][M][256]  pre-activations in, silu(z) out (rows < n)
+  float* delta;                      // [nh][n][256]  out
+  float* part;                       // [nh][gridDim.x][256]
+  int n, M, P, nh, nblk;
+};
+// Two workgroups per CU: rr_mlp_hidden_layer + rr_mlp_bwd_epilogue alone need ~175 VGPRs, so at the value kernel's three per CU (a cap of 168)
+// this kernel spills 6 VGPRs to scratch (the value kernel: 4); at two it takes 194 and touches no scratch.
+#ifndef RR_MLP_P256_BWD_WGS
+#define RR_MLP_P256_BWD_WGS 2
+#endif
+__global__ __launch_bounds__(256, RR_MLP_P256_BWD_WGS) void rr_mlp_policy256_backward_kernel(const RRPol256BwdArgs A) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  float* sW = lds;                                   // [256][18]  chunk of a transposed weight matrix
+  float* actV = sW + RR_MLP_VH * RR_SX;              // [32][258]  G tile, then the delta tile
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int row0 = blockIdx.x * RR_MLP_BM;
+  const int P = A.P, nchunk = (P + RR_MLP_KC - 1) / RR_MLP_KC, PW = nchunk * RR_MLP_KC;
+  // the epilogue's view of layer j: it strides both z and delta by its row count, here n, while the dump's layers are M rows apart
+  auto layer = [&](int j) {
+    RRMlpBwdArgs B = {};
+    B.z = A.z + (size_t)j * (A.M - A.n) * RR_MLP_VH;
+    B.delta = A.delta; B.part = A.part; B.M = A.n; B.nblk = A.nblk;
+    return B;
+  };
+  for (int e = threadIdx.x; e < RR_MLP_BM * PW; e += 256) {
+    const int m = e / PW, k = e - m * PW;
+    actV[m * RR_SV + k] = row0 + m < A.n && k < P ? A.g[(size_t)(row0 + m) * P + k] : 0.0f;     // columns past P meet zero weights
+  }
+  {
+    rr_f16 a0 = {0}, a1 = {0};
+    rr_f4 ap = {0, 0, 0, 0};
+    RRStage<RR_MLP_VH> g0, g1;
+    auto fetch = [&](RRStage<RR_MLP_VH>& s, int c) {      // uniform branch: only the last chunk can be partial
+      if ((c + 1) * RR_MLP_KC <= P) s.fetch<true>(A.wt_head, P, 0, RR_MLP_VH, c * RR_MLP_KC, P);
+      else s.fetch<false>(A.wt_head, P, 0, RR_MLP_VH, c * RR_MLP_KC, P);
+    };
+    fetch(g0, 0);
+    if (nchunk > 1) fetch(g1, 1);
+#pragma unroll 1
+    for (int c = 0; c < nchunk; c += 2) {
+      g0.commit(sW);
+      __syncthreads();                               // also: the G tile is complete
+      if (c + 2 < nchunk) fetch(g0, c + 2);
+      rr_mlp_chunk<true, false>(actV, RR_SV, c * RR_MLP_KC, sW, 0, a0, a1, ap, lane, wv);
+      __syncthreads();
+      if (c + 1 < nchunk) {
+        g1.commit(sW);
+        __syncthreads();
+        if (c + 3 < nchunk) fetch(g1, c + 3);
+        rr_mlp_chunk<true, false>(actV, RR_SV, (c + 1) * RR_MLP_KC, sW, 0, a0, a1, ap, lane, wv);
+        __syncthreads();
+      }
+    }
+    rr_mlp_bwd_epilogue<false>(layer(A.nh - 1), A.nh - 1, actV, a0, a1, nullptr, lane, wv, row0);
+    __syncthreads();
+  }
+  for (int j = A.nh - 1; j >= 1; --j) {
+    rr_f16 a0 = {0}, a1 = {0};
+    rr_f4 ap = {0, 0, 0, 0};
+    rr_mlp_hidden_layer(A.Wt[j], actV, sW, a0, a1, ap, lane, wv);
+    rr_mlp_bwd_epilogue<false>(layer(j - 1), j - 1, actV, a0, a1, nullptr, lane, wv, row0);
+    __syncthreads();
   }
 }

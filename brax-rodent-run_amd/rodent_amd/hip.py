@@ -74,7 +74,7 @@ class RRPpoCfg(C.Structure):
 
 EXPORTS = ["rr_model_load", "rr_model_dims", "rr_model_set_solver", "rr_model_set_solver_type", "rr_model_destroy", "rr_model_table", "rr_kernarg_layout", "rr_batch_create",
            "rr_batch_destroy", "rr_pipeline_init", "rr_pipeline_step", "rr_env_step", "rr_env_reset", "rr_pipeline_step_to", "rr_env_step_to", "rr_batch_contact_overflow", "rr_batch_bad_states", "rr_batch_unroll_supported", "rr_env_unroll", "rr_env_unroll_policy", "rr_batch_eval_supported", "rr_env_unroll_eval",
-           "rr_compute_gae", "rr_mlp_forward", "rr_ppo_loss_workspace_bytes", "rr_ppo_loss", "rr_policy_act_workspace_bytes", "rr_policy_act", "rr_policy_sample", "rr_policy_backward_workspace_bytes", "rr_policy_backward", "rr_mlp_silu_backward_workspace_bytes", "rr_mlp_silu_backward", "rr_mlp_value_backward_workspace_bytes", "rr_mlp_value_backward", "rr_mlp_weight_grad_workspace_bytes", "rr_mlp_weight_grad", "rr_mlp_weight_grad_batch_workspace_bytes", "rr_mlp_weight_grad_batch", "rr_obs_moments_workspace_bytes", "rr_obs_moments", "rr_wrap_episode_autoreset", "rr_debug_layout", "rr_batch_set_schedule", "rr_batch_set_env_params", "rr_batch_env_params_supported", "rr_batch_set_profile", "rr_batch_set_ls_repeat_exit", "rr_batch_set_timing", "rr_batch_kernel_time", "rr_last_error"]
+           "rr_compute_gae", "rr_mlp_forward", "rr_ppo_loss_workspace_bytes", "rr_ppo_loss", "rr_policy_act_workspace_bytes", "rr_policy_act", "rr_policy_sample", "rr_policy_backward_workspace_bytes", "rr_policy_backward", "rr_mlp_silu_backward_workspace_bytes", "rr_mlp_silu_backward", "rr_mlp_value_backward_workspace_bytes", "rr_mlp_policy_backward", "rr_mlp_policy_backward_workspace_bytes", "rr_mlp_value_backward", "rr_mlp_weight_grad_workspace_bytes", "rr_mlp_weight_grad", "rr_mlp_weight_grad_batch_workspace_bytes", "rr_mlp_weight_grad_batch", "rr_obs_moments_workspace_bytes", "rr_obs_moments", "rr_wrap_episode_autoreset", "rr_debug_layout", "rr_batch_set_schedule", "rr_batch_set_env_params", "rr_batch_env_params_supported", "rr_batch_set_profile", "rr_batch_set_ls_repeat_exit", "rr_batch_set_timing", "rr_batch_kernel_time", "rr_last_error"]
 
 _lib = None
 
@@ -140,6 +140,10 @@ def lib():
         L.rr_mlp_value_backward_workspace_bytes.restype = C.c_size_t
         L.rr_mlp_value_backward.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                             C.POINTER(C.c_void_p), C.c_void_p, C.c_size_t, C.c_void_p]
+        L.rr_mlp_policy_backward_workspace_bytes.argtypes = [C.c_int32, C.c_int32]
+        L.rr_mlp_policy_backward_workspace_bytes.restype = C.c_size_t
+        L.rr_mlp_policy_backward.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                             C.POINTER(C.c_void_p), C.c_void_p, C.c_size_t, C.c_void_p]
         L.rr_mlp_weight_grad_workspace_bytes.argtypes = [C.c_int32] * 3
         L.rr_mlp_weight_grad_workspace_bytes.restype = C.c_size_t
         L.rr_mlp_weight_grad.argtypes = [C.c_void_p] * 6 + [C.c_int32] * 3 + [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
@@ -514,6 +518,7 @@ def mlp_forward(obs, mean=None, std=None, policy=None, value=None, want_pre=Fals
 
     obs [M, K] float32 device; policy / value: (weights, biases) lists in nn.Linear layout or None.  Returns
     (policy_out [M, P] | None, value_out [M] | None, policy_pre [L-1, M, 32] | None, value_pre [L-1, M, 256] | None); P <= 128.
+    A policy whose hidden layers are all 256 wide runs as a launch of its own (policy_pre [L-1, M, 256]); widths other than 32 / 256: refused.
     rows (int64 [M], optional): sample m is row rows[m] of obs (the minibatch addressed in place)."""
     M, K = obs.shape
     _ptr(obs)
@@ -528,7 +533,7 @@ def mlp_forward(obs, mean=None, std=None, policy=None, value=None, want_pre=Fals
         pn, k = _mlp_net(*policy, in_dim=K); keep.append((k, policy))
         pol_out = torch.empty(M, policy[0][-1].shape[0], device=dev)
         if want_pre:
-            pol_pre = torch.empty(len(policy[0]) - 1, M, 32, device=dev)
+            pol_pre = torch.empty(len(policy[0]) - 1, M, policy[0][0].shape[0], device=dev)      # the policy's hidden width: 32 or 256
     if value is not None:
         vn, k = _mlp_net(*value, in_dim=K); keep.append((k, value))
         val_out = torch.empty(M, device=dev)
@@ -610,6 +615,35 @@ def mlp_value_backward(grad_value, head_weight, hidden_weights_t, pre_act, bias_
     _check(lib().rr_mlp_value_backward(grad_value.data_ptr(), head_weight.data_ptr(), wt, nh, M, pre_act.data_ptr(), delta.data_ptr(), bg,
                                        ws.data_ptr(), ws.numel() * 4, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
     return delta, pre_act
+
+
+def mlp_policy_backward(grad_logits, head_weight_t, hidden_weights_t, pre_act, bias_grads, bufs=None):
+    """Delta chain of a 256-wide policy network's hidden stack on the matrix cores (C ABI `rr_mlp_policy_backward`).
+
+    grad_logits [n, P], P <= 128; head_weight_t [256, P] = W_head.t().contiguous(); hidden_weights_t: list, entry j >= 1 =
+    W_j.t().contiguous() (entry 0 ignored); pre_act [nh, M >= n, 256] (rr_mlp_forward's policy_pre; the first n rows of each layer are
+    overwritten by silu(z), the rows behind them -- a minibatch's bootstrap rows -- are left alone); bias_grads: list of nh [256] tensors
+    (written).  Returns (delta [nh, n, 256], h = pre_act).  `bufs`: persistent buffers (a captured HIP graph sees the same addresses)."""
+    nh, M, H = pre_act.shape
+    n, P = grad_logits.shape
+    if H != 256 or M < n or len(bias_grads) != nh or len(hidden_weights_t) != nh or head_weight_t.shape != (256, P):
+        raise ValueError("rr_mlp_policy_backward: inconsistent shapes")
+    _ptr(grad_logits); _ptr(head_weight_t); _ptr(pre_act)
+    for j in range(nh):
+        _ptr(bias_grads[j], numel=256)
+        if j > 0:
+            _ptr(hidden_weights_t[j], numel=256 * 256)
+    dev, bufs = pre_act.device, {} if bufs is None else bufs      # no `bufs`: a fresh delta per call (it is an output)
+    ws = _ws(bufs, "policy256_bwd", dev, (n, nh), lib().rr_mlp_policy_backward_workspace_bytes(n, nh))
+    delta = _ws(bufs, "policy256_bwd_delta", dev, (n, nh), 0, shape=(nh, n, 256))
+    wt = (C.c_void_p * nh)(*[hidden_weights_t[j].data_ptr() if j > 0 else None for j in range(nh)])
+    bg = (C.c_void_p * nh)(*[b.data_ptr() for b in bias_grads])
+    _check(lib().rr_mlp_policy_backward(grad_logits.data_ptr(), head_weight_t.data_ptr(), wt, nh, n, M, P, pre_act.data_ptr(), delta.data_ptr(), bg,
+                                        ws.data_ptr(), ws.numel() * 4, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    return delta, pre_act
+
+
+DW_MAX_ITEMS = 12      # RR_DW_MAXB in csrc/rr_mlp.h: products per `rr_mlp_weight_grad_batch` call
 
 
 def mlp_weight_grad(delta, act, out, rows=None, mean=None, std=None, delta_colsum=None):

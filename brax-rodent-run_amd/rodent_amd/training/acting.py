@@ -62,6 +62,9 @@ def actor_params(policy_net, normalizer_params, min_std: float) -> dict:
     P = layers[-1].out_features
     if P > 2 * ACTOR_MAX_ACTIONS:
         raise ValueError(f"actor_params: a head of {P} outputs exceeds the in-kernel actor's {2 * ACTOR_MAX_ACTIONS}")
+    widths = sorted({l.out_features for l in layers[:-1]})
+    if widths != [32]:      # a 256-wide policy (served by rr_mlp_forward / rr_mlp_policy_backward) has no in-kernel actor
+        raise ValueError(f"actor_params: the in-kernel actor takes hidden layers of 32 units, got {widths}")
     W = hip.head_columns(P)
     head_wt = torch.zeros(32, W, device=dev)
     head_wt[:, :P] = layers[-1].weight.detach().t()

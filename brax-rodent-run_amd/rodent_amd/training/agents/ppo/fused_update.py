@@ -37,14 +37,20 @@ class FusedUpdate:
                 p.grad = torch.zeros_like(p)
 
     def _policy_backward(self, pre, g, obs, rows, mean, std):
-        """Policy network: the delta chain of the 32-wide stack is one launch (`rr_policy_backward`: delta_j, h_j = silu(z_j) over the
-        forward's dump, bias gradients).  g [n, P] covers the first n rows of the minibatch (the bootstrap rows behind them carry no
-        policy gradient).  Returns the weight-gradient products to be taken (`rr_mlp_weight_grad_batch` items)."""
+        """Policy network: the delta chain of the stack is one launch (32-wide: `rr_policy_backward`; 256-wide: `rr_mlp_policy_backward`;
+        both: delta_j, h_j = silu(z_j) over the forward's dump, bias gradients).  g [n, P] covers the first n rows of the minibatch (the
+        bootstrap rows behind them carry no policy gradient).  Returns the weight-gradient products to be taken (`rr_mlp_weight_grad_batch` items)."""
         layers = self.policy_net.layers
         nh = len(layers) - 1
         n = g.shape[0]
-        delta, h = hip.policy_backward(g, layers[nh].weight, [None] + [layers[j].weight for j in range(1, nh)], pre,
-                                       [layers[j].bias.grad for j in range(nh)], self.bufs)
+        if fused_mlp.policy_width(self.policy_net) == fused_mlp.WIDE_POLICY_HIDDEN:
+            # 256-wide stack: the value network's chain with a product at the head (`rr_mlp_policy_backward`, on the matrix cores); it reads
+            # the head and the hidden weights transposed.  delta [nh, n, 256]; h = the dump, its first n rows per layer now silu(z)
+            wt = [None] + [layers[j].weight.t().contiguous() for j in range(1, nh)]
+            delta, h = hip.mlp_policy_backward(g, layers[nh].weight.t().contiguous(), wt, pre, [layers[j].bias.grad for j in range(nh)], self.bufs)
+        else:
+            delta, h = hip.policy_backward(g, layers[nh].weight, [None] + [layers[j].weight for j in range(1, nh)], pre,
+                                           [layers[j].bias.grad for j in range(nh)], self.bufs)
         torch.sum(g, 0, out=layers[nh].bias.grad)
         items = [dict(delta=g, act=h[nh - 1, :n], out=layers[nh].weight.grad)]
         items += [dict(delta=delta[j], act=h[j - 1, :n], out=layers[j].weight.grad) for j in range(nh - 1, 0, -1)]
@@ -81,7 +87,12 @@ class FusedUpdate:
         n = T * B                                                                           # the bootstrap rows carry no policy gradient
         if self.side is None:
             items = self._policy_backward(ppre, g_pol[:n], obs, rows[:n], mean, std) + self._value_backward(vpre, g_val, obs, rows, mean, std)
-            hip.mlp_weight_grad_batch(items)        # all eleven dW = delta' h: one launch per tile shape + one reduction launch
+            if len(items) <= hip.DW_MAX_ITEMS:
+                hip.mlp_weight_grad_batch(items)    # all eleven dW = delta' h: one launch per tile shape + one reduction launch
+            else:                                   # deep networks (e.g. 7 + 5 hidden layers = 14 products): one call per network, each <= 8 items
+                npol = len(self.policy_net.layers)
+                hip.mlp_weight_grad_batch(items[:npol])
+                hip.mlp_weight_grad_batch(items[npol:])
         else:
             cur = torch.cuda.current_stream(obs.device)
             self.side.wait_stream(cur)              # fork: the policy branch needs the forward's dumps and the loss gradients

@@ -208,8 +208,10 @@ def train(
     # forward of both networks on the hand-written f32-MFMA kernel (one launch, observation tile read once for both nets,
     # normalisation fused) with an explicit backward; nn.Linear path for other shapes / CPU (RR_FUSED_MLP=0 forces it).  Policy heads of
     # 65 .. 128 logits (rodent_cpu.xml: 76) take this path only with RR_FUSED_WIDE_HEAD=1 (`fused_mlp.max_policy_head`)
+    # A policy with 256-wide hidden layers (`fused_mlp.policy_width`) takes it too (RR_FUSED_POLICY256=0 keeps it off); its rollouts stay
+    # per-step launches (`generate_unroll`: one forward launch + one sampling launch for all envs), the in-kernel actor is 32-wide only
     use_fused = (device.type == "cuda" and os.environ.get("RR_FUSED_MLP", "1") == "1"
-                 and fused_mlp.fusable(policy_net, fused_mlp.POLICY_HIDDEN, fused_mlp.max_policy_head()) and fused_mlp.fusable(value_net, fused_mlp.VALUE_HIDDEN, 1))
+                 and fused_mlp.fusable_policy(policy_net) and fused_mlp.fusable(value_net, fused_mlp.VALUE_HIDDEN, 1))
 
     # ... and the loss half + backward without an autograd graph (`fused_update`: rr_ppo_loss, gradients written straight into the
     # flat buffer).  RR_FUSED_LOSS=0 keeps compute_ppo_loss + loss.backward() on the fused forward.

@@ -15,6 +15,10 @@ networks.  The kernel also writes the hidden pre-activations.  Two backward pass
 
 In both, the first layer's dW uses the raw observations and folds the normaliser in afterwards, so the normalised copy of the
 minibatch is never written.
+
+A policy whose hidden layers are all 256 wide (`policy_width`) is served as well: `rr_mlp_forward` runs it as a launch of its own
+(rr_mlp_policy256_forward_kernel, the value path's pieces with a [256 x P] product as the head) and `FusedUpdate` takes its delta chain
+from `rr_mlp_policy_backward`; `_ActorCritic.backward` is width-agnostic.
 """
 from __future__ import annotations
 
@@ -26,6 +30,7 @@ import torch
 from .. import hip
 
 POLICY_HIDDEN, VALUE_HIDDEN = 32, 256
+WIDE_POLICY_HIDDEN = 256      # the second policy width the kernels serve: the value network's (rr_mlp_policy256_* in csrc/rr_mlp.h)
 
 
 def max_policy_head() -> int:
@@ -33,6 +38,12 @@ def max_policy_head() -> int:
     128 with RR_FUSED_WIDE_HEAD=1.  The kernels themselves take up to 128 (two passes over column halves of 64); the switch is
     opt-in until the wide path has been measured against the autograd path it replaces."""
     return 128 if os.environ.get("RR_FUSED_WIDE_HEAD", "0") == "1" else 64
+
+
+def wide_policy_enabled() -> bool:
+    """`ppo.train` and `make_inference_fn` hand a 256-wide policy to the hand-written kernels (RR_FUSED_POLICY256, default 1: the fused
+    learner's median time was below the autograd path's minimum); 0 keeps that shape on the nn.Linear path."""
+    return os.environ.get("RR_FUSED_POLICY256", "1") == "1"
 
 
 def net_params(mlp):
@@ -44,6 +55,27 @@ def fusable(mlp, hidden: int, max_out: int) -> bool:
     ls = list(mlp.layers)
     return (2 <= len(ls) <= 8 and all(l.out_features == hidden for l in ls[:-1]) and ls[-1].out_features <= max_out
             and ls[0].weight.is_cuda and ls[0].weight.dtype == torch.float32)
+
+
+def policy_width(mlp):
+    """Hidden width of a policy `MLP` the hand-written kernels serve -- 32 (`POLICY_HIDDEN`) or 256 (`WIDE_POLICY_HIDDEN`), the same in
+    every hidden layer, 1 .. 7 of them -- or None for any other shape.  Says nothing about the head or the device: `fusable_policy`."""
+    ls = list(mlp.layers)
+    if not 2 <= len(ls) <= 8:
+        return None
+    widths = {l.out_features for l in ls[:-1]}
+    if len(widths) == 1 and next(iter(widths)) in (POLICY_HIDDEN, WIDE_POLICY_HIDDEN):
+        return next(iter(widths))
+    return None
+
+
+def fusable_policy(mlp) -> bool:
+    """The policy network goes to the hand-written forward / learner kernels: a served width (`policy_width`), a head of at most
+    `max_policy_head()` logits, float32 parameters on a GPU, and for the 256-wide shape the switch of `wide_policy_enabled`."""
+    w = policy_width(mlp)
+    if w is None or (w == WIDE_POLICY_HIDDEN and not wide_policy_enabled()):
+        return False
+    return fusable(mlp, w, max_policy_head())
 
 
 class _ActorCritic(torch.autograd.Function):

@@ -2,8 +2,8 @@
 obs -> 32 x4 -> 2*action_size, value MLP obs -> 256 x5 -> 1, swish on hidden layers,
 lecun_uniform kernels, zero biases; `NormalTanhDistribution(min_std=1e-3)`.
 On a GPU with these default shapes the forward passes run on the hand-written f32-MFMA kernel (`fused_mlp`, C ABI
-`rr_mlp_forward`; heads of more than 64 logits only with RR_FUSED_WIDE_HEAD=1, `fused_mlp.max_policy_head`); other shapes / CPU
-tensors use the nn.Linear path (rocBLAS/hipBLASLt)."""
+`rr_mlp_forward`; heads of more than 64 logits only with RR_FUSED_WIDE_HEAD=1, `fused_mlp.max_policy_head`), and so does a policy
+whose hidden layers are all 256 wide (`fused_mlp.policy_width`); other shapes / CPU tensors use the nn.Linear path (rocBLAS/hipBLASLt)."""
 from __future__ import annotations
 
 import math
@@ -106,10 +106,11 @@ def make_inference_fn(ppo_networks: PPONetworks):
         elif policy_params is not None:
             raise TypeError(f"policy params must be an nn.Module or a state dict, got {type(policy_params).__name__}")
         dist = ppo_networks.parametric_action_distribution
-        fused = os.environ.get("RR_FUSED_MLP", "1") == "1" and fused_mlp.fusable(net, fused_mlp.POLICY_HIDDEN, fused_mlp.max_policy_head())
+        fused = os.environ.get("RR_FUSED_MLP", "1") == "1" and fused_mlp.fusable_policy(net)
 
         # rr_policy_act takes 2 x action_size <= 128 logits; `fused` has already held the head to max_policy_head() (64 unless RR_FUSED_WIDE_HEAD=1)
-        two_launch = (fused and isinstance(dist, NormalTanhDistribution) and type(dist) is NormalTanhDistribution and dist.event_size <= 64
+        # (32-wide policies only: a 256-wide one takes `policy_logits` + `policy_sample` below, also two launches per actor step)
+        two_launch = (fused and fused_mlp.policy_width(net) == fused_mlp.POLICY_HIDDEN and isinstance(dist, NormalTanhDistribution) and type(dist) is NormalTanhDistribution and dist.event_size <= 64
                       and os.environ.get("RR_POLICY_ACT", "1") == "1")
 
         @torch.no_grad()

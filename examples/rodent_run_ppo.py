@@ -24,7 +24,7 @@ import torch
 
 from rodent_amd import envs, jax_random, preprocessing, rollout
 from rodent_amd.io import model
-from rodent_amd.training import acting
+from rodent_amd.training import acting, networks
 from rodent_amd.training.agents.ppo import train as ppo
 
 
@@ -56,6 +56,10 @@ def main():
     ap.add_argument("--randomize", action="store_true", help="domain randomisation: per-env friction and actuator gain (domain_randomize)")
     ap.add_argument("--bad-state-max", type=float, default=None, help="end and restore episodes whose qpos / qvel is non-finite or exceeds this "
                     "magnitude (MuJoCo's mjMAXVAL is 1e10); off by default")
+    ap.add_argument("--policy-width", type=int, choices=(32, 256), default=32, help="units per hidden layer of the policy network; both "
+                    "widths run on the hand-written learner kernels (256: per-step rollouts, the in-kernel actor is 32-wide)")
+    ap.add_argument("--policy-depth", type=int, default=4, help="hidden layers of the policy network (1 .. 7 for the hand-written kernels; "
+                    "the one-launch rollout of the 32-wide policy takes 1 .. 4)")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -91,7 +95,8 @@ def main():
         unroll_length=10, num_minibatches=64, num_updates_per_batch=8, discounting=0.97,
         learning_rate=config["learning_rate"], entropy_cost=1e-3, num_envs=config["num_envs"],
         batch_size=config["batch_size"], seed=0, max_training_steps=args.max_training_steps,
-        randomization_fn=domain_randomize if args.randomize else None)
+        randomization_fn=domain_randomize if args.randomize else None,
+        network_factory=functools.partial(networks.make_ppo_networks, policy_hidden_layer_sizes=(args.policy_width,) * args.policy_depth))
 
     run_id = uuid.uuid4()
     model_path = f"./model_checkpoints/{run_id}"

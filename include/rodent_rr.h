@@ -257,7 +257,11 @@ int rr_compute_gae(const float* truncation, const float* termination, const floa
  * addressed inside the unroll buffer, no gathered copy).  mean / std (device, [K]) may both be NULL (no normalisation), else
  * x <- (x - mean) / std.  Outputs: policy_out [M][sizes[nlayers]], value_out [M]; optional PRE-activation dumps of the
  * hidden layers (for a backward pass): policy_pre [nlayers-1][M][32], value_pre [nlayers-1][M][256] (NULL = not written).
- * RR_EUNSUPPORTED for other shapes. */
+ * A policy whose hidden layers are ALL 256 wide (1 .. 7 of them, head 1 .. 128 logits) is taken too: it runs as a launch of its own
+ * next to the value network's (the same launch whether or not `value` is given, so a row's logits do not depend on the call's other
+ * arguments or row count), policy_pre is then [nlayers-1][M][256], and its backward pass is rr_mlp_policy_backward.  rr_policy_act,
+ * rr_policy_backward and the in-kernel actor of rr_env_unroll_policy stay 32-wide only.
+ * RR_EUNSUPPORTED for other shapes (mixed hidden widths or widths other than 32 / 256 included). */
 typedef struct rr_mlp_net {
   const float* const* weights;
   const float* const* biases;
@@ -338,6 +342,19 @@ size_t rr_mlp_value_backward_workspace_bytes(int32_t M, int32_t nhidden);
 int rr_mlp_value_backward(const float* grad_value, const float* head_weight, const float* const* hidden_weights_t, int32_t nhidden,
                           int32_t M, float* pre_act, float* delta, float* const* bias_grads, void* workspace, size_t workspace_bytes,
                           void* stream);
+
+/* Backward pass of a 256-wide policy network's hidden stack (as rr_mlp_forward takes it), the value network's chain with a product at
+ * the head: delta_{nh-1} = (G W_head) * silu'(z_{nh-1}), delta_{j-1} = (delta_j W_j) * silu'(z_{j-1}).  grad_logits [n][P] (1 <= P <= 128;
+ * else RR_EUNSUPPORTED) = d loss / d logits of the first n <= M rows; head_weight_t [256][P] = the head's weight TRANSPOSED;
+ * hidden_weights_t as for rr_mlp_value_backward; nhidden 1 .. 7 (else RR_EUNSUPPORTED); pre_act [nhidden][M][256] = rr_mlp_forward's
+ * policy_pre, rows 0 .. n-1 of each layer overwritten by silu(z), rows n .. M-1 (a minibatch's bootstrap rows, which carry no policy
+ * gradient) neither read nor written; delta [nhidden][n][256] out; bias_grads: HOST array of nhidden device pointers, db_j [256]
+ * (fixed-order sums).  The weight gradients (rr_mlp_weight_grad_batch on these outputs; dW_head = grad_logits' h_{nh-1}) stay with the
+ * caller.  workspace: rr_mlp_policy_backward_workspace_bytes(n, nhidden) bytes of device memory. */
+size_t rr_mlp_policy_backward_workspace_bytes(int32_t n, int32_t nhidden);
+int rr_mlp_policy_backward(const float* grad_logits, const float* head_weight_t, const float* const* hidden_weights_t, int32_t nhidden,
+                           int32_t n, int32_t M, int32_t P, float* pre_act, float* delta, float* const* bias_grads, void* workspace,
+                           size_t workspace_bytes, void* stream);
 
 /* Weight gradient of one layer, grad[o][i] = sum_m delta[m][o] * x[m][i], on the f32 matrix cores with the row range split
  * over workgroups (the output is small, the reduction ~2e4 rows long) and a fixed-order sum of the partial tiles.  delta
