@@ -556,6 +556,8 @@ static int fill_io(const Launch& L, RRIO& io) {
     io.z_max = env->healthy_z_max; io.terminate_when_unhealthy = env->terminate_when_unhealthy;
     if (!(env->bad_state_max >= 0.0f)) return fail(RR_EINVAL, "launch: env io bad_state_max must be >= 0 (0 = no bad-state check)");
     io.bad_state_max = env->bad_state_max;
+    if (env->clip && env->num_clips < 1) return fail(RR_EINVAL, "launch: env io clip needs num_clips >= 1");
+    io.clip = env->clip; io.num_clips = env->num_clips;
   }
   io.mode = L.mode;
   return RR_OK;

@@ -239,7 +239,10 @@ struct RRIO {
   // debug-dump instance only (rr_batch_set_ls_repeat_exit): 1 = the line search runs its repeated bracketing iterations instead of leaving
   // the loop (RR_LS_REPEAT_EXIT) -- the A side of the bitwise test of that exit.  No other instance reads it.
   int ls_run_repeats;
-  int pad_end;                 // sizeof(RRIO) stays a multiple of 8 (RRKArgs)
+  // MULTI-CLIP TRACKING (env epilogue): with `clip` set, track_pos is [num_clips][track_len][3] and environment e tracks clip clip[e]
+  // (clamped into [0, num_clips - 1]); the frame clamp stays per clip.  A null `clip` is the single-clip path: track_pos [track_len][3].
+  int num_clips;               // (also keeps sizeof(RRIO) a multiple of 8, RRKArgs)
+  const int* clip;             // nullable [N]
 };
 
 // ------------------------------------------------------------------------------------------ small math
@@ -2239,6 +2242,7 @@ static_assert(alignof(RRDims) == 4 && alignof(RRTables) == 8 && alignof(RRIO) ==
 static_assert(offsetof(RRKArgs, T) == rr_align_up(sizeof(RRDims), alignof(RRTables)), "RRTables follows RRDims at its natural alignment");
 static_assert(offsetof(RRKArgs, io) == rr_align_up(offsetof(RRKArgs, T) + sizeof(RRTables), alignof(RRIO)), "RRIO follows RRTables at its natural alignment");
 static_assert(offsetof(RRKArgs, num_envs) == offsetof(RRKArgs, io) + sizeof(RRIO) && sizeof(RRIO) % 8 == 0, "scalars follow RRIO without padding");
+static_assert(offsetof(RRIO, clip) % 8 == 0 && offsetof(RRIO, clip) + sizeof(const int*) == sizeof(RRIO), "the clip ids close RRIO without padding");
 // ... and so are the model tables outside the solver's loops: RRTables is re-read at the head of each phase that indexes a table
 // (narrow scalar loads next to an existing hand-off; the unused members' loads are dead), so no table pointer is held across the
 // substep.  The loops' own tables are the exception (RRLoopTables, taken once from the parameter).

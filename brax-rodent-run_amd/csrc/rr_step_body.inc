@@ -321,6 +321,15 @@
     const bool is_reset = (mode & 2) != 0;
     const int old_frame = UNROLL ? u_frame : io.cur_frame_in[env];
     const int new_frame = is_reset ? old_frame : old_frame + 1;
+    // multi-clip tracking: the env's clip as the base of both track reads below.  clip[env] is wave-uniform: one load per env step next
+    // to cur_frame_in's, the clamp and the offset on the scalar unit, re-read in each epilogue (nothing lives across the solver).  The id
+    // is clamped, so none addresses outside the array; the frame clamp below stays per clip.  Null clip: io.track_pos as it is.
+    const float* track = io.track_pos;
+    if (io.clip) {
+      int c = io.clip[env];
+      c = c < 0 ? 0 : (c > io.num_clips - 1 ? io.num_clips - 1 : c);
+      track += (size_t)3 * (size_t)io.track_len * (size_t)c;
+    }
     float* ob = EVAL ? io.t_obs + ((size_t)env * 2 + ((ut + 1) & 1)) * D.obs_dim : ACTOR ? io.t_obs + rr_traj_obs(io, num_envs, env, rr_traj(io, ut).u, rr_traj(io, ut).t + 1) * D.obs_dim : io.obs + (size_t)env * D.obs_dim;
     int o = 0;
     for (int i = lane; i < D.nq; i += RR_LANES) ob[o + i] = w.s_qpos[i];
@@ -337,7 +346,7 @@
     if (lane < 3) {  // xmat[1] @ (track_pos[frame + 1] - qpos[:3]); JAX clamps the gather index
       int fi = new_frame + 1;
       fi = fi < 0 ? 0 : (fi > io.track_len - 1 ? io.track_len - 1 : fi);
-      const v3 v = ld3(io.track_pos + 3 * fi) - ld3(w.s_qpos);
+      const v3 v = ld3(track + 3 * fi) - ld3(w.s_qpos);
       float m1[9];
       quat_to_mat(m1, xq1);
       // row `lane` of xmat[1] by selects (indexing a register array by the lane id would put it into scratch memory)
@@ -350,7 +359,7 @@
       a2 = wave_sum(a2);
       if (lane == 0) {
         int fi = old_frame < 0 ? 0 : (old_frame > io.track_len - 1 ? io.track_len - 1 : old_frame);
-        const v3 dx = ld3(w.s_qpos) - ld3(io.track_pos + 3 * fi);
+        const v3 dx = ld3(w.s_qpos) - ld3(track + 3 * fi);
         // explicit roundings (no fused multiply-add left to the optimiser), so that the instances of the kernel form the reward from the
         // same operations: single-step and multi-step instances agree bit for bit (tests/test_gpu_env.py); the actor-inside instance to
         // ONE ulp -- `expf` below is expanded inline per instance and its expansion there rounds differently

@@ -29,6 +29,46 @@ def bad_state_mask(qpos: torch.Tensor, qvel: torch.Tensor, bad_state_max: float)
     return ~(ok(qpos) & ok(qvel))
 
 
+def reset_draws(keys, nq: int, nv: int, reset_noise_scale: float, num_clips: Optional[int] = None):
+    """The host draws of `Rodent.reset`, without a device: `keys` uint32 [N, 2] -> (start_frame int32 [N], qpos noise float32 [N, nq],
+    qvel float32 [N, nv], clip int32 [N] or None).  The key chain is the reference's, `rng, rng1, rng2, rng_pos = split(rng, 4)`
+    [REF Rodent_Env_Brax.py:98-113]: start_frame from rng, the qpos noise from rng1, qvel from rng2.  The reference splits off rng_pos and
+    never uses it; with `num_clips` given (an env with a [C, T, 3] track) the clip id is `randint(rng_pos, 0, num_clips)`, so no other draw
+    moves whether there are clips or not."""
+    keys = np.asarray(keys, dtype=np.uint32).reshape(-1, 2)
+    ks = jax_random.split(keys, 4)                       # rng, rng1, rng2, rng_pos
+    start_frame = jax_random.randint(ks[:, 0], 0, 100)   # [N] int32
+    low, hi = -reset_noise_scale, reset_noise_scale
+    qpos_noise = jax_random.uniform(ks[:, 1], nq, low, hi)
+    qvel = jax_random.uniform(ks[:, 2], nv, low, hi)
+    clip = None if num_clips is None else jax_random.randint(ks[:, 3], 0, int(num_clips)).astype(np.int32)
+    return start_frame, qpos_noise, qvel, clip
+
+
+def _check_track(track_pos) -> np.ndarray:
+    """track_pos as float32 [T, 3] or [C, T, 3] (C >= 1, T >= 1), ValueError otherwise."""
+    t = track_pos.detach().cpu().numpy() if torch.is_tensor(track_pos) else np.asarray(track_pos)
+    if t.ndim not in (2, 3) or t.shape[-1] != 3 or 0 in t.shape:
+        raise ValueError(f"track_pos must be [T, 3] (one clip) or [C, T, 3] (C >= 1 clips of equal length), got shape {tuple(t.shape)}")
+    return np.ascontiguousarray(t, dtype=np.float32)
+
+
+def _check_clip(clip, num_clips: Optional[int], num_envs: int) -> np.ndarray:
+    """Explicit clip ids of `Rodent.reset` as int32 [N]; ValueError for an env without a clip axis, a wrong shape or an id outside [0, C)."""
+    if num_clips is None:
+        raise ValueError("reset(clip=...) needs an env built with a [C, T, 3] track_pos; this one has a single [T, 3] track")
+    c = clip.detach().cpu().numpy() if torch.is_tensor(clip) else np.asarray(clip)
+    if c.dtype.kind not in "iu":
+        raise ValueError(f"clip ids must be integers, got dtype {c.dtype}")
+    if c.ndim == 0:
+        c = np.full(num_envs, c)
+    if c.shape != (num_envs,):
+        raise ValueError(f"clip must be an int or have shape ({num_envs},), got {tuple(c.shape)}")
+    if c.size and (c.min() < 0 or c.max() >= num_clips):
+        raise ValueError(f"clip ids must lie in [0, {num_clips}), got {int(c.min())} .. {int(c.max())}")
+    return c.astype(np.int32)
+
+
 class Rodent(PipelineEnv):
 
     def __init__(
@@ -50,7 +90,12 @@ class Rodent(PipelineEnv):
         bad_state_max: Optional[float] = None,
         **kwargs,
     ):
-        """`bad_state_max` (None = off, the default): the bad-state check of MuJoCo (`mj_checkPos` / `mj_checkVel`, there with
+        """`track_pos`: the reference positions to track, float [T, 3] -- one clip, followed by every env -- or [C, T, 3], C >= 1 clips of
+        equal length (what `preprocessing.load_reference_clip` returns for a list of clip names).  With the clip axis each env follows ONE
+        clip, drawn at `reset` (or given there) and kept in `info['clip']`: its reward reads `track_pos[clip, cur_frame]`, its observation
+        `track_pos[clip, cur_frame + 1]`, frames clamped within the clip.  Any other rank raises ValueError.  `num_clips` is C, or 1.
+
+        `bad_state_max` (None = off, the default): the bad-state check of MuJoCo (`mj_checkPos` / `mj_checkVel`, there with
         mjMAXVAL = 1e10).  After an env step an env is bad when some element x of its qpos or qvel fails |x| <= bad_state_max (NaN and
         +-inf included); that step then has done = 1 (whatever `terminate_when_unhealthy` is), reward 0 and metrics 0, and is counted
         (`bad_states()`).  Under `AutoResetWrapper` -- composed or in the one-launch rollouts -- the first state comes back as for any
@@ -61,6 +106,7 @@ class Rodent(PipelineEnv):
                 thr32 = np.float32(bad_state_max)        # what the kernel gets: 1e-50 would arrive as 0 (= off), 1e39 as inf
             if not (np.isfinite(thr32) and thr32 > 0):
                 raise ValueError(f"bad_state_max must be finite and > 0 as a float32 (or None: no check), got {bad_state_max!r}")
+        track_np = _check_track(track_pos)
         if solver.lower() not in ("cg", "newton"):       # [REF Rodent_Env_Brax.py:42-45]
             raise ValueError(f"solver must be 'cg' or 'newton', got {solver!r}")
         if vision:
@@ -76,7 +122,9 @@ class Rodent(PipelineEnv):
         kwargs["n_frames"] = kwargs.get("n_frames", physics_steps_per_control_step)
         kwargs["backend"] = "hip"
         super().__init__(sys, num_envs=num_envs, device=device, **kwargs)
-        self._track_pos = torch.as_tensor(np.asarray(track_pos), dtype=torch.float32).to(self.device).contiguous()
+        self._track_pos = torch.from_numpy(track_np).to(self.device).contiguous()
+        self._track_host = track_np
+        self._num_clips = track_np.shape[0] if track_np.ndim == 3 else None      # None: no clip axis (the single-clip path, no ids anywhere)
         self._forward_reward_weight = forward_reward_weight
         self._ctrl_cost_weight = ctrl_cost_weight
         self._healthy_reward = healthy_reward
@@ -97,6 +145,11 @@ class Rodent(PipelineEnv):
         """A sibling env with another batch size (ppo.train builds its per-rank and eval envs this way)."""
         return Rodent(num_envs=num_envs, device=device or self.device, **self._ctor)
 
+    @property
+    def num_clips(self) -> int:
+        """Clips in `track_pos`: C of a [C, T, 3] track, 1 for a [T, 3] one."""
+        return 1 if self._num_clips is None else self._num_clips
+
     def contact_overflow(self) -> int:
         """(env, env step) events so far in which more sphere / capsule pairs were in penetration than the kernel's 64 contact slots;
         the surplus pairs were DROPPED for that substep (models with candidate-pair contacts, e.g. rodent_cpu.xml; always 0 for the
@@ -113,37 +166,47 @@ class Rodent(PipelineEnv):
         multi-step launch counts each of its steps.  Reads a device counter: synchronises the env's stream."""
         return self._batch.bad_states()
 
-    def _env_io(self, cur_frame, obs, reward=None, done=None, metrics=None):
-        return dict(track_pos=self._track_pos, cur_frame=cur_frame, obs=obs, reward=reward, done=done, metrics=metrics,
+    def _env_io(self, cur_frame, obs, reward=None, done=None, metrics=None, clip=None):
+        return dict(track_pos=self._track_pos, cur_frame=cur_frame, obs=obs, reward=reward, done=done, metrics=metrics, clip=clip,
                     healthy_reward=self._healthy_reward, ctrl_cost_weight=self._ctrl_cost_weight,
                     healthy_z_range=self._healthy_z_range, terminate_when_unhealthy=self._terminate_when_unhealthy,
                     bad_state_max=self._bad_state_max)
 
-    def reset(self, rng) -> State:
+    def reset(self, rng, clip=None) -> State:
         """Resets the environment to an initial state.  `rng`: uint32 keys [N, 2] (one jax-style
-        PRNG key per env, as `jax.vmap(env.reset)(split(key, N))` passes) or an int seed."""
+        PRNG key per env, as `jax.vmap(env.reset)(split(key, N))` passes) or an int seed.
+
+        An env with a [C, T, 3] track gives each env a clip: `randint(rng_pos, 0, C)` from the fourth key of the reference's split (which
+        the reference never uses, so start frame, qpos noise and qvel are what a single-clip env draws from the same key), or `clip`, an
+        int or integer ids [N] in [0, C) (ValueError outside, and for an env without a clip axis).  The ids live in `info['clip']` (int32
+        [N], device) and stay for the life of the state: like `cur_frame` they are not restored by AutoReset, and never re-drawn."""
         N, dev, s = self.num_envs, self.device, self.sys
+        if clip is not None:
+            clip = _check_clip(clip, self._num_clips, N)
         if isinstance(rng, (int, np.integer)):
             rng = jax_random.split(jax_random.PRNGKey(int(rng)), N)
         keys = np.asarray(rng, dtype=np.uint32).reshape(N, 2)
-        ks = jax_random.split(keys, 4)                       # rng, rng1, rng2, rng_pos
-        start_frame = jax_random.randint(ks[:, 0], 0, 100)   # [N] int32
-        low, hi = -self._reset_noise_scale, self._reset_noise_scale
-        track = self._track_pos.cpu().numpy()
+        start_frame, qpos_noise, qvel, drawn = reset_draws(keys, s.nq, s.nv, self._reset_noise_scale, self._num_clips)
+        if clip is None:
+            clip = drawn
+        track = self._track_host                             # float32 [T, 3] or [C, T, 3], what the device holds
         qpos = np.tile(np.asarray(s.qpos0, dtype=np.float32), (N, 1))
-        qpos[:, :3] = track[np.clip(start_frame, 0, len(track) - 1)]
-        qpos = qpos + jax_random.uniform(ks[:, 1], s.nq, low, hi)
-        qvel = jax_random.uniform(ks[:, 2], s.nv, low, hi)
+        fi = np.clip(start_frame, 0, track.shape[-2] - 1)
+        qpos[:, :3] = track[fi] if clip is None else track[clip, fi]
+        qpos = qpos + qpos_noise
 
         st = dict(qpos=torch.from_numpy(qpos).to(dev), qvel=torch.from_numpy(qvel).to(dev),
                   act=torch.zeros(N, s.na, device=dev), qacc_warmstart=torch.zeros(N, s.nv, device=dev))
         out = self._alloc_outputs(full=False)
         cur_frame = torch.from_numpy(start_frame.astype(np.int32)).to(dev)
+        info = {"cur_frame": cur_frame}
+        if clip is not None:
+            info["clip"] = torch.from_numpy(np.ascontiguousarray(clip, dtype=np.int32)).to(dev)
         obs = torch.empty(N, s.obs_dim, device=dev)
-        self._batch.env_reset(st, self._env_io(cur_frame, obs), out)
+        self._batch.env_reset(st, self._env_io(cur_frame, obs, clip=info.get("clip")), out)
         zero = torch.zeros(N, device=dev)
         metrics = {"pos_reward": zero, "reward_quadctrl": zero.clone(), "reward_alive": zero.clone()}
-        return State(PipelineState(**st, **out), obs, zero.clone(), zero.clone(), metrics, {"cur_frame": cur_frame})
+        return State(PipelineState(**st, **out), obs, zero.clone(), zero.clone(), metrics, info)
 
     def _launch_buffers(self, state: State, episode_length: Optional[float] = None):
         """What a step launch reads and writes: (st_in, st_out, env-io outputs dict(cur_frame, reward, done, metrics), wrap) -- `wrap` the
@@ -155,7 +218,7 @@ class Rodent(PipelineEnv):
         st_in = fields(ps)
         st = {k: torch.empty_like(v) for k, v in st_in.items()}
         io = dict(cur_frame=torch.empty_like(info["cur_frame"]), reward=torch.empty(N, device=dev), done=torch.empty(N, device=dev),
-                  metrics=torch.empty(N, 3, device=dev))
+                  metrics=torch.empty(N, 3, device=dev), clip=info.get("clip"))      # clip: read only (None without a clip axis)
         wrap = None
         if episode_length is not None:
             wrap = dict(first=fields(info["first_pipeline_state"]), first_obs=info["first_obs"], prev_done=state.done, steps_in=info["steps"],

@@ -3,7 +3,8 @@
 The env is batched by construction, so `VmapWrapper` only validates shapes.  `EpisodeWrapper`
 maintains `info['steps']` / `info['truncation']`; `AutoResetWrapper` selects the stored first
 state back on `done` -- no re-randomisation and `info` (hence `cur_frame`) is NOT restored, exactly
-as upstream.
+as upstream.  The same holds for `info['clip']` of a multi-clip env: an env keeps
+its clip across restores.  `reset(rng, **kw)` hands keyword arguments (`clip=`) down to the env.
 """
 from __future__ import annotations
 
@@ -36,8 +37,8 @@ class Wrapper:
             raise AttributeError(name)
         return getattr(self.env, name)
 
-    def reset(self, rng):
-        return self.env.reset(rng)
+    def reset(self, rng, **kw):
+        return self.env.reset(rng, **kw)
 
     def step(self, state, action):
         return self.env.step(state, action)
@@ -64,8 +65,8 @@ class EpisodeWrapper(Wrapper):
         self.episode_length = episode_length
         self.action_repeat = action_repeat
 
-    def reset(self, rng):
-        state = self.env.reset(rng)
+    def reset(self, rng, **kw):
+        state = self.env.reset(rng, **kw)
         state.info["steps"] = torch.zeros_like(state.reward)
         state.info["truncation"] = torch.zeros_like(state.reward)
         return state
@@ -89,8 +90,8 @@ class EpisodeWrapper(Wrapper):
 class AutoResetWrapper(Wrapper):
     """Automatically resets Brax envs that are done (to the FIRST state of the batch member)."""
 
-    def reset(self, rng):
-        state = self.env.reset(rng)
+    def reset(self, rng, **kw):
+        state = self.env.reset(rng, **kw)
         state.info["first_pipeline_state"] = state.pipeline_state
         state.info["first_obs"] = state.obs
         return state
@@ -116,8 +117,8 @@ class AutoResetWrapper(Wrapper):
 class EvalWrapper(Wrapper):
     """Accumulates episode metrics for evaluation (brax EvalWrapper)."""
 
-    def reset(self, rng):
-        rs = self.env.reset(rng)
+    def reset(self, rng, **kw):
+        rs = self.env.reset(rng, **kw)
         rs.metrics["reward"] = rs.reward
         z = torch.zeros_like(rs.reward)
         rs.info["eval_metrics"] = dict(episode_metrics={k: torch.zeros_like(v) for k, v in rs.metrics.items()},
@@ -172,8 +173,8 @@ class FusedEpisodeAutoResetWrapper(Wrapper):
         self.episode_length = episode_length
         self.action_repeat = 1
 
-    def reset(self, rng):
-        state = self.env.reset(rng)
+    def reset(self, rng, **kw):
+        state = self.env.reset(rng, **kw)
         state.info["steps"] = torch.zeros_like(state.reward)
         state.info["truncation"] = torch.zeros_like(state.reward)
         state.info["first_pipeline_state"] = state.pipeline_state

@@ -42,6 +42,12 @@ class RREnvIO(C.Structure):
                 ("terminate_when_unhealthy", C.c_int32), ("bad_state_max", C.c_float)]
 
 
+class RREnvIOClips(C.Structure):
+    """The whole `rr_env_io`, and what every env call passes: the 80 bytes of `RREnvIO` (the single-clip members, kept as they were) followed
+    by the two multi-clip members.  All zero behind `bad_state_max` is the single-clip path."""
+    _fields_ = RREnvIO._fields_ + [("clip", C.c_void_p), ("num_clips", C.c_int32)]
+
+
 class RRUnrollIO(C.Structure):
     _fields_ = [("first", RRState), ("first_obs", C.c_void_p), ("prev_done", C.c_void_p), ("steps_in", C.c_void_p), ("steps_out", C.c_void_p),
                 ("truncation_out", C.c_void_p), ("episode_length", C.c_float)]
@@ -100,22 +106,22 @@ def lib():
         L.rr_batch_destroy.restype = None
         L.rr_pipeline_init.argtypes = [C.c_void_p, C.POINTER(RRState), C.POINTER(RROutputs)]
         L.rr_pipeline_step.argtypes = [C.c_void_p, C.POINTER(RRState), C.c_void_p, C.c_int32, C.POINTER(RROutputs)]
-        L.rr_env_step.argtypes = [C.c_void_p, C.POINTER(RRState), C.c_void_p, C.c_int32, C.POINTER(RREnvIO),
+        L.rr_env_step.argtypes = [C.c_void_p, C.POINTER(RRState), C.c_void_p, C.c_int32, C.POINTER(RREnvIOClips),
                                   C.POINTER(RROutputs)]
         L.rr_pipeline_step_to.argtypes = [C.c_void_p, C.POINTER(RRState), C.POINTER(RRState), C.c_void_p, C.c_int32, C.POINTER(RROutputs)]
-        L.rr_env_step_to.argtypes = [C.c_void_p, C.POINTER(RRState), C.POINTER(RRState), C.c_void_p, C.c_int32, C.POINTER(RREnvIO),
+        L.rr_env_step_to.argtypes = [C.c_void_p, C.POINTER(RRState), C.POINTER(RRState), C.c_void_p, C.c_int32, C.POINTER(RREnvIOClips),
                                      C.c_void_p, C.POINTER(RROutputs)]
         L.rr_batch_unroll_supported.argtypes = [C.c_void_p, C.c_int32]
         L.rr_batch_contact_overflow.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
         L.rr_batch_bad_states.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
-        L.rr_env_unroll.argtypes = [C.c_void_p, C.POINTER(RRState), C.POINTER(RRState), C.c_void_p, C.c_int32, C.c_int32, C.POINTER(RREnvIO),
+        L.rr_env_unroll.argtypes = [C.c_void_p, C.POINTER(RRState), C.POINTER(RRState), C.c_void_p, C.c_int32, C.c_int32, C.POINTER(RREnvIOClips),
                                     C.c_void_p, C.POINTER(RRUnrollIO)]
-        L.rr_env_unroll_policy.argtypes = [C.c_void_p, C.POINTER(RRState), C.POINTER(RRState), C.c_int32, C.c_int32, C.POINTER(RREnvIO), C.c_void_p,
+        L.rr_env_unroll_policy.argtypes = [C.c_void_p, C.POINTER(RRState), C.POINTER(RRState), C.c_int32, C.c_int32, C.POINTER(RREnvIOClips), C.c_void_p,
                                            C.POINTER(RRUnrollIO), C.POINTER(RRActorIO)]
         L.rr_batch_eval_supported.argtypes = [C.c_void_p]
-        L.rr_env_unroll_eval.argtypes = [C.c_void_p, C.POINTER(RRState), C.POINTER(RRState), C.c_int32, C.c_int32, C.POINTER(RREnvIO), C.c_void_p,
+        L.rr_env_unroll_eval.argtypes = [C.c_void_p, C.POINTER(RRState), C.POINTER(RRState), C.c_int32, C.c_int32, C.POINTER(RREnvIOClips), C.c_void_p,
                                          C.POINTER(RRUnrollIO), C.POINTER(RRActorIO), C.POINTER(RREvalIO)]
-        L.rr_env_reset.argtypes = [C.c_void_p, C.POINTER(RRState), C.POINTER(RREnvIO), C.POINTER(RROutputs)]
+        L.rr_env_reset.argtypes = [C.c_void_p, C.POINTER(RRState), C.POINTER(RREnvIOClips), C.POINTER(RROutputs)]
         L.rr_debug_layout.argtypes = [C.c_void_p, C.POINTER(C.POINTER(C.c_char_p)), C.POINTER(C.POINTER(C.c_int32)),
                                       C.POINTER(C.POINTER(C.c_int32))]
         L.rr_compute_gae.argtypes = [C.c_void_p] * 5 + [C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -290,12 +296,18 @@ class Batch:
             setattr(o, k, _ptr(out.get(k), numel=N * w))
         return o
 
-    def _env(self, env) -> RREnvIO:
+    def _env(self, env) -> RREnvIOClips:
         d, N = self.dims, self.N
         tp = env["track_pos"]
-        e = RREnvIO()
+        clip = env.get("clip")
+        if (clip is not None) != (tp.dim() == 3):
+            raise ValueError("env io: `clip` goes with a [C, T, 3] track_pos, and only with one")
+        e = RREnvIOClips()
         e.track_pos = _ptr(tp)
-        e.track_len = tp.shape[0]
+        e.track_len = tp.shape[-2]
+        if clip is not None:        # multi-clip tracking: env e follows track_pos[clip[e]]
+            e.clip = _ptr(clip, torch.int32, N)
+            e.num_clips = tp.shape[0]
         e.cur_frame = _ptr(env["cur_frame"], torch.int32, N)
         e.obs = _ptr(env["obs"], numel=N * d.obs_dim)
         e.reward = _ptr(env.get("reward"), numel=N)

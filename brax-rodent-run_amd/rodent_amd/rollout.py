@@ -16,20 +16,25 @@ from . import jax_random
 
 
 @torch.no_grad()
-def eval_rollout(env, make_policy, params, steps: int = 500, seed: int = 0, record: Optional[list] = None, actor: Optional[dict] = None) -> np.ndarray:
+def eval_rollout(env, make_policy, params, steps: int = 500, seed: int = 0, record: Optional[list] = None, actor: Optional[dict] = None,
+                 clip: int = 0) -> np.ndarray:
     """`env`: a `Rodent` with num_envs = 1 (the reference's jit_reset / jit_step pair).  Key handling as the launcher:
     `key = PRNGKey(seed); _, key = split(key); reset_rng, act_rng = split(key)`; the policy is deterministic.
     Returns the rollout's qpos [steps + 1, nq] (float32).  `record` (tests): a list that receives (state, action, next_state) per step.
     `actor`: the same policy as `acting.actor_params` lays it out; with it (and no `record`) the whole rollout is one launch of the
     unwrapped env (`Rodent.unroll_eval`) where the env has an evaluation instance and RR_FUSED_EVAL=1.  The per-step loop is the default:
-    with one env the launch measured 7 % slower than the loop."""
+    with one env the launch measured 7 % slower than the loop.
+    `clip`: the clip the rollout follows where the env has several (`env.num_clips > 1`); a single-clip env takes only 0."""
     if env.num_envs != 1:
         raise ValueError("the evaluation rollout steps a single env (use env.with_num_envs(1))")
+    multi = getattr(env, "num_clips", 1) > 1                      # several clips: the env takes an explicit id (one clip: it can only be 0)
+    if not multi and clip != 0:
+        raise ValueError(f"eval_rollout(clip={clip}): the env has a single clip")
     key = jax_random.PRNGKey(seed)
     _, key = jax_random.split(key)
     reset_rng, act_rng = jax_random.split(key)
     policy = make_policy(params, deterministic=True)
-    state = env.reset(reset_rng[None])
+    state = env.reset(reset_rng[None], clip=int(clip)) if multi else env.reset(reset_rng[None])
     if (record is None and actor is not None and os.environ.get("RR_FUSED_EVAL", "0") == "1" and hasattr(env, "eval_supported")
             and env.eval_supported()):
         qpos_out = torch.empty(steps + 1, 1, state.pipeline_state.qpos.shape[1], device=state.obs.device)

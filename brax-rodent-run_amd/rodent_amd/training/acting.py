@@ -232,6 +232,12 @@ class Evaluator:
         metrics = {}
         for name, value in em["episode_metrics"].items():
             metrics[f"eval/episode_{name}"] = float(value.mean()) if aggregate_episodes else value.cpu().numpy()
+        # multi-clip eval env: the episode reward per clip, over the eval envs that follow it (a clip no eval env drew has no key)
+        clip = state.info.get("clip")
+        if clip is not None and getattr(self._env, "num_clips", 1) > 1 and aggregate_episodes:
+            reward, ids = em["episode_metrics"]["reward"].cpu(), clip.cpu()
+            for c in torch.unique(ids).tolist():
+                metrics[f"eval/episode_reward_clip{c}"] = float(reward[ids == c].mean())
         metrics["eval/avg_episode_length"] = float(em["episode_steps"].mean())
         metrics["eval/epoch_eval_time"] = epoch_eval_time
         metrics["eval/sps"] = self._steps_per_unroll / epoch_eval_time

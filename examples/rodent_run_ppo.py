@@ -51,7 +51,9 @@ def main():
     ap.add_argument("--xml", default="./models/rodent_new.xml")        # [REF Rodent_Env_Brax.py:16]
     ap.add_argument("--clip", default=None, help="reference clip: .npz / .h5 written by preprocessing.save_reference_clip (clip name "
                     "--clip-name) or .npy with the root positions [T,3]; a synthetic line if absent")
-    ap.add_argument("--clip-name", default="84")
+    ap.add_argument("--clip-name", nargs="+", default=["84"], help="one or more clip names of --clip; with several, each env follows one of "
+                    "them (drawn at reset) and the evaluation reports eval/episode_reward_clip{c} per clip")
+    ap.add_argument("--synthetic-clips", type=int, default=1, help="without a clip file: K synthetic lines of different heading (1: one line along x)")
     ap.add_argument("--max-training-steps", type=int, default=None)
     ap.add_argument("--randomize", action="store_true", help="domain randomisation: per-env friction and actuator gain (domain_randomize)")
     ap.add_argument("--bad-state-max", type=float, default=None, help="end and restore episodes whose qpos / qvel is non-finite or exceeds this "
@@ -75,12 +77,16 @@ def main():
         "solver": "cg", "iterations": 8, "ls_iterations": 8, "vision": False,
     }
     if args.clip and os.path.exists(args.clip) and not args.clip.endswith(".npy"):
-        track_pos = np.asarray(preprocessing.load_reference_clip(args.clip, args.clip_name).position[0])     # reference_clip.position [REF :84]
+        position = np.asarray(preprocessing.load_reference_clip(args.clip, args.clip_name).position)         # reference_clip.position [REF :84], [C, T, 3]
+        track_pos = position[0] if len(args.clip_name) == 1 else position
     elif args.clip and os.path.exists(args.clip):
         track_pos = np.load(args.clip)
     else:   # the reference clip (clips/84.p) is not distributed: straight line at 0.2 m/s, torso rest height
         t = np.arange(250)
         track_pos = np.stack([0.004 * t, np.zeros(250), np.full(250, 0.0681)], axis=1)
+        if args.synthetic_clips > 1:    # K lines from the same start, headings spread over +-45 degrees
+            heading = np.linspace(-np.pi / 4, np.pi / 4, args.synthetic_clips)
+            track_pos = np.stack([np.stack([0.004 * t * np.cos(h), 0.004 * t * np.sin(h), np.full(250, 0.0681)], axis=1) for h in heading])
 
     envs.register_environment("rodent", envs.Rodent)
     env = envs.get_environment(
@@ -106,8 +112,9 @@ def main():
         print(json.dumps({k: (float(v) if np.isscalar(v) else v) for k, v in metrics.items()}), flush=True)
 
     eval_env = env.with_num_envs(1)                  # the launcher's un-vmapped jit_reset / jit_step pair [REF :93-94]
-    ref_clip = preprocessing.ReferenceClip(position=track_pos, quaternion=np.tile([1.0, 0, 0, 0], (len(track_pos), 1)),
-                                           joints=np.zeros((len(track_pos), env.sys.nq - 7)))
+    track0 = track_pos if track_pos.ndim == 2 else track_pos[0]       # the evaluation rollout follows clip 0
+    ref_clip = preprocessing.ReferenceClip(position=track0, quaternion=np.tile([1.0, 0, 0, 0], (len(track0), 1)),
+                                           joints=np.zeros((len(track0), env.sys.nq - 7)))
 
     def policy_params_fn(num_steps, make_policy, params, model_path=model_path):
         """Checkpoint + the 500-step evaluation rollout paired with the reference clip [REF brax_rodent_run_ppo.py:135-191];
@@ -116,7 +123,7 @@ def main():
         model.save_params(f"{model_path}/{num_steps}", params)
         net = params[1]                                  # the snapshot network in the in-kernel actor's layout: RR_FUSED_EVAL=1 makes the rollout one launch
         actor = acting.actor_params(net, params[0], 0.001) if isinstance(net, torch.nn.Module) and acting.actor_shape_supported(net, eval_env.action_size) else None
-        qposes = rollout.eval_rollout(eval_env, make_policy, params, steps=500, seed=0, actor=actor)
+        qposes = rollout.eval_rollout(eval_env, make_policy, params, steps=500, seed=0, actor=actor, clip=0)
         rollout.save_rollout(f"{model_path}/{num_steps}_rollout.npz", rollout.qpos_pairs(ref_clip, qposes), eval_env.dt, qposes)
 
     make_inference_fn, params, _ = train_fn(environment=env, progress_fn=progress, policy_params_fn=policy_params_fn)

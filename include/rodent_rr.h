@@ -71,7 +71,7 @@ typedef struct rr_outputs {
 
 /* reference-env epilogue fused into the step kernel [REF Rodent_Env_Brax.py:98-136]; all NULL = physics only */
 typedef struct rr_env_io {
-  const float* track_pos; /* [T][3] device */
+  const float* track_pos; /* [T][3] device; with `clip` set: [num_clips][T][3] */
   int32_t track_len;      /* T */
   int32_t* cur_frame;     /* [N] in/out: info['cur_frame'] */
   float* obs;             /* [N][obs_dim] out */
@@ -86,6 +86,13 @@ typedef struct rr_env_io {
    * are bad.  That step then writes done = 1 (whatever terminate_when_unhealthy is), reward = 0 and the three metrics = 0, and adds 1
    * to the batch's counter (rr_batch_bad_states).  The state and the observation of the bad step are NOT sanitised. */
   float bad_state_max;
+  /* Multi-clip tracking, NULL = one clip (a zero-initialised struct keeps the single-clip behaviour and num_clips is not read).  With
+   * `clip` set, track_pos is [num_clips][track_len][3] and env e tracks clip clip[e]: its reward reads track_pos[clip[e]][old_frame], its
+   * observation track_pos[clip[e]][new_frame + 1], both frames clamped into [0, track_len - 1] WITHIN the clip.  The kernel clamps
+   * clip[e] into [0, num_clips - 1]; num_clips < 1 with clip set: RR_EINVAL.  Every launch form and rr_env_reset honour it; the ids are
+   * only read (a wrapped form's restore leaves them alone, as it leaves cur_frame). */
+  const int32_t* clip;    /* [N] device, nullable */
+  int32_t num_clips;      /* C */
 } rr_env_io;
 
 /* -- model ------------------------------------------------------------------------------------- */
@@ -236,7 +243,8 @@ int rr_env_unroll_eval(rr_batch* b, const rr_state* in, const rr_state* out_stat
                        const int32_t* cur_frame_in, const rr_unroll_io* wrap, const rr_actor_io* actor, const rr_eval_io* eval);
 
 /* obs of Rodent.reset: after rr_pipeline_init, obs = _get_obs(data, 0, cur_frame) [REF :89];
- * implemented as rr_pipeline_init + obs epilogue in one launch. Only env->obs/track_pos/cur_frame are used. */
+ * implemented as rr_pipeline_init + obs epilogue in one launch. Only env->obs/track_pos/cur_frame are used,
+ * and env->clip/num_clips where set (the observation holds track_pos[clip[e]][cur_frame + 1]). */
 int rr_env_reset(rr_batch* b, const rr_state* st, const rr_env_io* env, const rr_outputs* out);
 
 /* Generalised advantage estimation of one PPO minibatch, the reverse scan of brax.training.agents.ppo.losses.compute_gae
