@@ -159,6 +159,9 @@ static void layout(rr_model* m) {
   k.g_con_D = dbg("con_D", d.ncon); k.g_con_aref = dbg("con_aref", 4 * d.ncon); k.g_lim = dbg("limit_pos_D_aref", 3 * d.nv);
   k.g_qacc = dbg("qacc", d.nv); k.g_qfrc_constraint = dbg("qfrc_constraint", d.nv); k.g_misc = dbg("niter_cost", 2);
   k.g_ls_iters = dbg("ls_iters", 2);      // bracketing iterations of the last substep's line searches: executed, left out by the repeat exit
+  // the last substep's solve(): [0] 1 = the context at qacc_smooth was chosen, 0 = the one at qacc_warmstart; [1] how the loop ended, a sum of
+  // 1 = iteration cap, 2 = improvement below the tolerance, 4 = gradient below the tolerance
+  k.g_solver_end = dbg("solver_end", 2);
   k.g_kaok = dbg("kernarg_ok", 1);
   k.dbg_floats = g;
   for (auto& s : m->dbg_names) m->dbg_cnames.push_back(s.c_str());
@@ -344,7 +347,7 @@ struct rr_batch {
   unsigned* bad_states = nullptr;       // (env, env step) events of the bad-state check (rr_env_io::bad_state_max; rr_batch_bad_states)
   unsigned* progress = nullptr;         // pacing counter of multi-step launches (RRIO::progress); RR_PACE=0 turns pacing off
   float *env_dof_f = nullptr, *env_act_f = nullptr, *env_con_f = nullptr;     // per-env parameter rows, owned (rr_batch_set_env_params)
-  int ls_run_repeats = 0;               // debug-dump launches: the line search runs its repeated bracketing iterations (rr_batch_set_ls_repeat_exit(b, 0))
+  int dbg_flags = 0;                    // debug-dump launches, RRIO::dbg_flags: RR_DBG_LS_RUN_REPEATS (rr_batch_set_ls_repeat_exit(b, 0)), RR_DBG_SOLVER_UNTRIMMED (rr_batch_set_solver_trim(b, 0))
   float* eval_actions = nullptr;        // [N][nu]: where an evaluation launch without actions_out keeps the current action (rr_env_unroll_eval)
   bool has_env_params() const { return env_dof_f || env_act_f || env_con_f; }
 };
@@ -623,7 +626,7 @@ static int launch(rr_batch* b, const Launch& L) {
   if (L.un && (rc = fill_unroll(b, L, io))) return rc;
   io.env_dof_f = b->env_dof_f; io.env_act_f = b->env_act_f; io.env_con_f = b->env_con_f;      // null without per-env parameters
   io.prof = b->prof; io.env_map = b->env_map; io.cost = b->cost; io.dyn_overflow = b->dyn_overflow; io.bad_states = b->bad_states;
-  if (v == V_DEBUG) io.ls_run_repeats = b->ls_run_repeats;      // the only instance that reads it
+  if (v == V_DEBUG) io.dbg_flags = b->dbg_flags;      // the only instance that reads it
   // step 4: the launch itself, between the event pair of the timing ring
   RRDims kd = pair ? m->kd_rep : b->kd;
   kd.iterations = m->kd.iterations; kd.ls_iterations = m->kd.ls_iterations;
@@ -1313,7 +1316,13 @@ extern "C" int rr_batch_set_schedule(rr_batch* b, const int32_t* env_map, uint32
 
 extern "C" int rr_batch_set_ls_repeat_exit(rr_batch* b, int32_t enable) {
   if (!b) return fail(RR_EINVAL, "rr_batch_set_ls_repeat_exit: null batch");
-  b->ls_run_repeats = enable ? 0 : 1;
+  b->dbg_flags = enable ? (b->dbg_flags & ~RR_DBG_LS_RUN_REPEATS) : (b->dbg_flags | RR_DBG_LS_RUN_REPEATS);
+  return RR_OK;
+}
+
+extern "C" int rr_batch_set_solver_trim(rr_batch* b, int32_t enable) {
+  if (!b) return fail(RR_EINVAL, "rr_batch_set_solver_trim: null batch");
+  b->dbg_flags = enable ? (b->dbg_flags & ~RR_DBG_SOLVER_UNTRIMMED) : (b->dbg_flags | RR_DBG_SOLVER_UNTRIMMED);
   return RR_OK;
 }
 

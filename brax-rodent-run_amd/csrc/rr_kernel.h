@@ -68,7 +68,7 @@ struct RRDims {
   // debug dump offsets (floats)
   int g_xpos, g_xquat, g_xmat, g_com, g_cinert, g_crb, g_cdof, g_cvel, g_cfrc, g_qM, g_qLD, g_dinv, g_bias, g_passive,
       g_actuator, g_smooth, g_qacc_smooth, g_con_dist, g_con_pos, g_con_frame, g_con_D, g_con_aref, g_lim, g_qacc,
-      g_qfrc_constraint, g_misc, g_ls_iters, g_kaok, dbg_floats;
+      g_qfrc_constraint, g_misc, g_ls_iters, g_solver_end, g_kaok, dbg_floats;
 };
 
 // LDS layout of one environment (float offsets).  One constexpr function serves the host (rr_api.hip layout) and the
@@ -236,9 +236,13 @@ struct RRIO {
   // and bad_states += 1; the wrapped forms restore the first state as for any finished episode.  State and observation of the bad step are
   // NOT sanitised: the bare step and the raw evaluation form return them, flagged by done.
   float bad_state_max;
-  // debug-dump instance only (rr_batch_set_ls_repeat_exit): 1 = the line search runs its repeated bracketing iterations instead of leaving
-  // the loop (RR_LS_REPEAT_EXIT) -- the A side of the bitwise test of that exit.  No other instance reads it.
-  int ls_run_repeats;
+  // debug-dump instance only, a set of flags; no other instance reads it.  Each one makes that instance do work the production code leaves
+  // out because nothing reads its result -- the A side of a bitwise test.
+  //   RR_DBG_LS_RUN_REPEATS (rr_batch_set_ls_repeat_exit(b, 0)): the line search runs its repeated bracketing iterations instead of
+  //     leaving the loop (RR_LS_REPEAT_EXIT);
+  //   RR_DBG_SOLVER_UNTRIMMED (rr_batch_set_solver_trim(b, 0)): the solver solves for Mgrad and forms the next search direction BEFORE its
+  //     exit test, walks the contacts (J' f) in the cost-only context at qacc_smooth, and rebuilds that context's rows where it is chosen.
+  int dbg_flags;
   // MULTI-CLIP TRACKING (env epilogue): with `clip` set, track_pos is [num_clips][track_len][3] and environment e tracks clip clip[e]
   // (clamped into [0, num_clips - 1]); the frame clamp stays per clip.  A null `clip` is the single-clip path: track_pos [track_len][3].
   int num_clips;               // (also keeps sizeof(RRIO) a multiple of 8, RRKArgs)
@@ -246,6 +250,8 @@ struct RRIO {
 };
 
 // ------------------------------------------------------------------------------------------ small math
+#define RR_DBG_LS_RUN_REPEATS 1
+#define RR_DBG_SOLVER_UNTRIMMED 2
 struct v3 { float x, y, z; };
 __device__ __forceinline__ v3 mk3(float x, float y, float z) { v3 r; r.x = x; r.y = y; r.z = z; return r; }
 __device__ __forceinline__ v3 ld3(const float* p) { return mk3(p[0], p[1], p[2]); }
@@ -534,7 +540,8 @@ struct Wave {
   // solver options, read from the kernel arguments at the head of solve() and held in scalar registers through its loops only
   float so_tolerance, so_ls_tolerance, so_meaninertia;
   int so_iterations, so_ls_iterations, so_nv_scale;
-  int dbg_ls_run_repeats = 0, dbg_ls_ran = 0, dbg_ls_left = 0;      // debug-dump instance only: RRIO::ls_run_repeats; bracketing iterations executed / left out in this substep
+  int dbg_flags = 0, dbg_ls_ran = 0, dbg_ls_left = 0;      // debug-dump instance only: RRIO::dbg_flags; bracketing iterations executed / left out in this substep
+  int dbg_solver_end = 0;           // debug-dump instance only, this substep's solve(): bit 0 the context at qacc_smooth was chosen; how the loop ended: bit 1 cap, bit 2 improvement, bit 3 gradient
   int work;               // wave-uniform count of line-search point evaluations, weighted by row blocks: the scheduling cost estimate (rr_batch_set_schedule)
   unsigned long long pt_last, pt[RR_NPH];
   template <bool PROF> __device__ __forceinline__ void stamp(int i) {
@@ -1722,7 +1729,8 @@ struct Wave {
   }
 
   // constraint state at the current Jaref: forces, qfrc_constraint, cost  [UP mjx solver._update_constraint]
-  __device__ __forceinline__ void update_constraint() {
+  // `walk` (wave-uniform) false: cost only -- no contact is broadcast, and qfrc_con holds the limit forces alone (solve(), context at qacc_smooth)
+  __device__ __forceinline__ void update_constraint(bool walk = true) {
     float part[2] = {0.0f, 0.0f};  // [0] = sum D*Jaref^2 over active rows, [1] = gauss dot
     // J' f without a Jacobian and without atomics: a contact pushes with the spatial force (tau about the tree COM, F)
     // on every dof of its body's ancestor chain, qfrc_d += cdof_d . (tau, F).  The wave walks the contacts that carry
@@ -1749,7 +1757,7 @@ struct Wave {
         }
         const float mu = con_mu[cs];
         const float fn = f[0] + f[1] + f[2] + f[3], f1 = mu * (f[0] - f[1]), f2 = mu * (f[2] - f[3]);
-        if (fn != 0.0f) {
+        if (walk && fn != 0.0f) {
           has = true;
           const v3 F = mk3(con_fr[cs][0], con_fr[cs][1], con_fr[cs][2]) * fn + mk3(con_fr[cs][3], con_fr[cs][4], con_fr[cs][5]) * f1 +
                        mk3(con_fr[cs][6], con_fr[cs][7], con_fr[cs][8]) * f2;
@@ -1903,9 +1911,14 @@ struct Wave {
     sync();
   }
 
-  __device__ __forceinline__ void update_gradient() {
+  // [UP mjx solver._update_gradient] in two halves: the exit test of solve() needs grad alone and stands between them
+  __device__ __forceinline__ void form_gradient() {
 #pragma unroll
-    for (int s = 0; s < NVS; ++s) { grad[s] = Ma[s] - qfrc_smooth[s] - qfrc_con[s]; Mgrad[s] = grad[s]; }
+    for (int s = 0; s < NVS; ++s) grad[s] = Ma[s] - qfrc_smooth[s] - qfrc_con[s];
+  }
+  __device__ __forceinline__ void solve_gradient() {
+#pragma unroll
+    for (int s = 0; s < NVS; ++s) Mgrad[s] = grad[s];
     for (int rep = 0; rep < RR_REP_SOLVE; ++rep) { float t_[NVS]; for (int s = 0; s < NVS; ++s) t_[s] = grad[s]; ldl_solve(t_); }
     if (NEWTON) {            // Mgrad = H^-1 grad
       newton_hessian();
@@ -1916,17 +1929,36 @@ struct Wave {
     }
   }
 
+  // search direction from grad / Mgrad: steepest descent on the first pass, Polak-Ribiere after it (pm, gg: Mgrad and grad . Mgrad of the pass before)
+  __device__ __forceinline__ void direction(int niter, const float* pm, float gg) {
+    if (niter == 0) {
+#pragma unroll
+      for (int s = 0; s < NVS; ++s) { search[s] = -Mgrad[s]; mv[s] = -grad[s]; }
+    } else {
+      float bt[2] = {0.0f, gg};
+#pragma unroll
+      for (int s = 0; s < NVS; ++s) bt[0] += grad[s] * (Mgrad[s] - pm[s]);
+      solver_sum_n<2>(bt);
+      const float beta = NEWTON ? 0.0f : fmaxf(0.0f, bt[0] / fmaxf(RR_MINVAL, bt[1]));      // Newton: search = -Mgrad
+#pragma unroll
+      for (int s = 0; s < NVS; ++s) { search[s] = -Mgrad[s] + beta * search[s]; mv[s] = -grad[s] + beta * mv[s]; }
+    }
+  }
+
   // [UP mjx solver._Context.create]: Jaref, Ma, constraint state (and gradient/search) at `qacc`
   // `at_smooth`: qacc == qacc_smooth, where Ma = M qacc_smooth = qfrc_smooth by construction (no product needed)
-  __device__ __forceinline__ void ctx_create(bool at_smooth) {
-    put_vec(qacc);
-    jac_mul(con_jar, s_vec);
+  // `rows_kept`: con_jar / lim_jar already hold the rows at this qacc (solve(), ph 2); `walk`: see update_constraint.  All three wave-uniform.
+  __device__ __forceinline__ void ctx_create(bool at_smooth, bool rows_kept, bool walk) {
+    if (!rows_kept) {
+      put_vec(qacc);
+      jac_mul(con_jar, s_vec);
 #pragma unroll
-    for (int cs = 0; cs < NCS; ++cs)
+      for (int cs = 0; cs < NCS; ++cs)
 #pragma unroll
-      for (int k = 0; k < 4; ++k) con_jar[cs][k] -= con_aref[cs][k];
+        for (int k = 0; k < 4; ++k) con_jar[cs][k] -= con_aref[cs][k];
 #pragma unroll
-    for (int s = 0; s < NVS; ++s) lim_jar[s] = lim_sign[s] * qacc[s] - lim_aref[s];
+      for (int s = 0; s < NVS; ++s) lim_jar[s] = lim_sign[s] * qacc[s] - lim_aref[s];
+    }
     if (at_smooth) {
 #pragma unroll
       for (int s = 0; s < NVS; ++s) Ma[s] = qfrc_smooth[s];
@@ -1935,7 +1967,7 @@ struct Wave {
       for (int s = 0; s < NVS; ++s) Ma[s] = Ma_warm[s];     // M * qacc_warmstart (taken before the factorisations)
     }
     cost = INFINITY; prev_cost = 0.0f;
-    update_constraint();
+    update_constraint(walk);
   }
 
   // line-search point(s): cost and derivatives of the piecewise-quadratic 1-D cost at alpha, over the COMPACTED active
@@ -2076,7 +2108,7 @@ struct Wave {
       bool same = swap;        // without a swap the next loop head leaves (and counts itself in `work`)
       same &= __float_as_int(lo.alpha) == __float_as_int(lo_head.alpha) && __float_as_int(lo.d0) == __float_as_int(lo_head.d0) && __float_as_int(lo.d1) == __float_as_int(lo_head.d1);
       same &= __float_as_int(hi.alpha) == __float_as_int(hi_head.alpha) && __float_as_int(hi.d0) == __float_as_int(hi_head.d0) && __float_as_int(hi.d1) == __float_as_int(hi_head.d1);
-      if constexpr (DBG) same &= dbg_ls_run_repeats == 0;      // debug-dump instance: run the repeats anyway (rr_batch_set_ls_repeat_exit)
+      if constexpr (DBG) same &= (dbg_flags & RR_DBG_LS_RUN_REPEATS) == 0;      // debug-dump instance: run the repeats anyway (rr_batch_set_ls_repeat_exit)
       if (uni(same)) {
         if constexpr (PROF || DBG) ls_left = so_ls_iterations - 1 - it;
         it = so_ls_iterations;
@@ -2118,26 +2150,62 @@ struct Wave {
     }
     const float scale = 1.0f / (so_meaninertia * (float)so_nv_scale);
     // warm start [UP mjx solver.solve]: cost at qacc_smooth, cost at qacc_warmstart, then the full context at the cheaper
-    // of the two.  One copy of the evaluation code, driven by a wave-uniform phase counter.
+    // of the two.  One copy of the evaluation code, driven by a wave-uniform phase counter, so the two costs that are compared come from
+    // the same instructions.  Of ph 0 only the cost is ever read: its qfrc_con is overwritten by ph 1 or formed again by ph 2.  So ph 0
+    // skips the contact walk (update_constraint(false): same force and cost arithmetic, empty ballot), and its rows Jaref are kept in
+    // registers for ph 2, which would compute the same J * qacc_smooth - aref by the same code: ph 2 restores them and walks.
+    const bool untrimmed = DBG && (dbg_flags & RR_DBG_SOLVER_UNTRIMMED) != 0;      // debug-dump instance: walk in ph 0, rebuild in ph 2, solve before the exit test
     float cost_smooth = 0.0f;
     bool use_smooth = false;
+    float jar0[NCS][4], ljar0[NVS];
+#pragma unroll
+    for (int cs = 0; cs < NCS; ++cs)
+#pragma unroll
+      for (int k = 0; k < 4; ++k) jar0[cs][k] = 0.0f;
+#pragma unroll
+    for (int s = 0; s < NVS; ++s) ljar0[s] = 0.0f;
 #pragma nounroll
     for (int ph = 0; ph < 3; ++ph) {
       if (ph == 2 && !use_smooth) break;        // the context already is the one at qacc_warmstart
 #pragma unroll
       for (int s = 0; s < NVS; ++s) qacc[s] = ph != 1 ? qacc_smooth[s] : (lane + RR_LANES * s < D.nv ? s_warm[lane + RR_LANES * s] : 0.0f);
-      ctx_create(ph != 1);
-      if (ph == 0) cost_smooth = cost;
+      const bool rows_kept = ph == 2 && !untrimmed;
+      if (rows_kept) {
+#pragma unroll
+        for (int cs = 0; cs < NCS; ++cs)
+#pragma unroll
+          for (int k = 0; k < 4; ++k) con_jar[cs][k] = jar0[cs][k];
+#pragma unroll
+        for (int s = 0; s < NVS; ++s) lim_jar[s] = ljar0[s];
+      }
+      ctx_create(ph != 1, rows_kept, ph != 0 || untrimmed);
+      if (ph == 0) {
+        cost_smooth = cost;
+#pragma unroll
+        for (int cs = 0; cs < NCS; ++cs)
+#pragma unroll
+          for (int k = 0; k < 4; ++k) jar0[cs][k] = con_jar[cs][k];
+#pragma unroll
+        for (int s = 0; s < NVS; ++s) ljar0[s] = lim_jar[s];
+      }
       if (ph == 1) use_smooth = uni(!(cost < cost_smooth));
     }
-    update_gradient();
-    // search = -Mgrad, and mv = M search = -grad because Mgrad = M^-1 grad: the product the reference recomputes every
-    // iteration [UP mjx solver._linesearch: mv = M @ search] follows the search-direction recurrence exactly
-#pragma unroll
-    for (int s = 0; s < NVS; ++s) { search[s] = -Mgrad[s]; mv[s] = -grad[s]; }
-    stamp<PROF>(8);
+    if constexpr (DBG) dbg_solver_end = use_smooth ? 1 : 0;
+    // THE EXIT TEST STANDS BEFORE THE SOLVE.  The loop below is the reference's  linesearch -> update_constraint -> update_gradient ->
+    // direction -> ++niter -> test  rotated by half a turn: the test reads niter, prev_cost and cost (final after update_constraint) and
+    // |grad|, never Mgrad.  So on the pass that ends the loop -- every forward pass has one -- the solve Mgrad = M^-1 grad (Newton: Hessian,
+    // factorisation and solve), the beta sums and the new search / mv would be computed and never read: after the loop only niter, cost,
+    // qacc, qfrc_con and s_warm are.  Here grad is formed, niter counted and the test made first; the solve and the direction follow only
+    // when another line search does.  One copy of the test, of the solve and of the direction serves the first pass (niter == 0: search =
+    // -Mgrad, mv = -grad) and the later ones.  gg and pm are taken from grad / Mgrad before update_constraint, as ever.  PAIR: both waves
+    // test identical totals, so they leave together and their barriers still match.
+    form_gradient();
     int niter = 0;
+    float pm[NVS], gg = 0.0f;
+#pragma unroll
+    for (int s = 0; s < NVS; ++s) pm[s] = 0.0f;
     while (true) {
+      if (untrimmed) { solve_gradient(); direction(niter, pm, gg); }      // debug-dump instance, switch off: the reference's order
       const float improvement = (prev_cost - cost) * scale;
       float g2 = 0.0f;
 #pragma unroll
@@ -2146,26 +2214,29 @@ struct Wave {
       bool done = niter >= so_iterations;
       done |= improvement < so_tolerance;
       done |= gradient < so_tolerance;
-      if (uni(done)) break;
-      stamp<PROF>(12);
+      if (uni(done)) {
+        if constexpr (DBG) dbg_solver_end |= (niter >= so_iterations ? 2 : 0) | (uni(improvement < so_tolerance) ? 4 : 0) | (uni(gradient < so_tolerance) ? 8 : 0);
+        break;
+      }
+      if constexpr (PROF) { if (niter) stamp<PROF>(12); }       // cg_misc: grad, the test (and the direction below)
+      if (!untrimmed) {
+        solve_gradient();
+        if constexpr (PROF) { if (niter) stamp<PROF>(11); }     // update_gradient: the solve; the first one belongs to solver_init
+        // search = -Mgrad, and mv = M search = -grad because Mgrad = M^-1 grad: the product the reference recomputes every
+        // iteration [UP mjx solver._linesearch: mv = M @ search] follows the search-direction recurrence exactly
+        direction(niter, pm, gg);
+      }
+      if constexpr (PROF) { if (niter) stamp<PROF>(12); else stamp<PROF>(8); }
       for (int rep = 0; rep < RR_REP_LS; ++rep) linesearch<false>();
       linesearch<PROF, DBG>();
       stamp<PROF>(9);
-      float pm[NVS], gg = 0.0f;
+      gg = 0.0f;
 #pragma unroll
       for (int s = 0; s < NVS; ++s) { gg += grad[s] * Mgrad[s]; pm[s] = Mgrad[s]; }
       for (int rep = 0; rep < RR_REP_UC; ++rep) { const float pc = prev_cost, c0 = cost; update_constraint(); prev_cost = pc; cost = c0; }
       update_constraint();
       stamp<PROF>(10);
-      update_gradient();
-      stamp<PROF>(11);
-      float bt[2] = {0.0f, gg};
-#pragma unroll
-      for (int s = 0; s < NVS; ++s) bt[0] += grad[s] * (Mgrad[s] - pm[s]);
-      solver_sum_n<2>(bt);
-      const float beta = NEWTON ? 0.0f : fmaxf(0.0f, bt[0] / fmaxf(RR_MINVAL, bt[1]));      // Newton: search = -Mgrad
-#pragma unroll
-      for (int s = 0; s < NVS; ++s) { search[s] = -Mgrad[s] + beta * search[s]; mv[s] = -grad[s] + beta * mv[s]; }
+      form_gradient();
       ++niter;
     }
 #pragma unroll

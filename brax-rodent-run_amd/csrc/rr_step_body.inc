@@ -192,7 +192,9 @@
     w.smooth_forces(bias, passive);     // needs cfrc, whose cells the factorisation overwrites
     if (dg) {
       for (int e = lane; e < 10 * D.nbody; e += RR_LANES) dg[D.g_crb + e] = w.s_crb[e];
-      for (int e = lane; e < 6 * D.nbody; e += RR_LANES) dg[D.g_cfrc + e] = w.s_cfrc[e];
+      // the world body has no cfrc: nothing writes or reads its row, and its cells hold whatever LDS held (the previous substep's qLD, or at the
+      // first substep of a launch the previous kernel's data) -- the dump says 0, so that two launches from one state dump the same bits
+      for (int e = lane; e < 6 * D.nbody; e += RR_LANES) dg[D.g_cfrc + e] = e < 6 ? 0.0f : w.s_cfrc[e];
     }
     w.contact_jobs();     // J*x jobs of the contacts in penetration: needed from here to the end of the substep
     // WAVE PRIORITY.  2048 environments are exactly one resident round, so a launch lasts as long as its slowest environment,
@@ -245,7 +247,7 @@
     }
     w.constraint_rows(dg);
     w.template stamp<PROF>(7);
-    if (DBG) { w.dbg_ls_run_repeats = io.ls_run_repeats; w.dbg_ls_ran = w.dbg_ls_left = 0; }
+    if (DBG) { w.dbg_flags = io.dbg_flags; w.dbg_ls_ran = w.dbg_ls_left = 0; }
     niter = w.template solve<PROF, DBG>();
     w.template stamp<PROF>(12);
     if (dg) {
@@ -254,7 +256,11 @@
         const int d = lane + RR_LANES * s;
         if (d < D.nv) { dg[D.g_qacc + d] = w.qacc[s]; dg[D.g_qfrc_constraint + d] = w.qfrc_con[s]; }
       }
-      if (lane == 0) { dg[D.g_misc] = (float)niter; dg[D.g_misc + 1] = w.cost; dg[D.g_ls_iters] = (float)w.dbg_ls_ran; dg[D.g_ls_iters + 1] = (float)w.dbg_ls_left; }
+      if (lane == 0) {
+        dg[D.g_misc] = (float)niter; dg[D.g_misc + 1] = w.cost;
+        dg[D.g_ls_iters] = (float)w.dbg_ls_ran; dg[D.g_ls_iters + 1] = (float)w.dbg_ls_left;
+        dg[D.g_solver_end] = (float)(w.dbg_solver_end & 1); dg[D.g_solver_end + 1] = (float)(w.dbg_solver_end >> 1);
+      }
     }
     if (mode & 1) w.euler();
     w.template stamp<PROF>(13);

@@ -446,6 +446,15 @@ int rr_debug_layout(const rr_batch* b, const char*** names, const int32_t** offs
  * instance always takes the exit and carries no code for this switch. */
 int rr_batch_set_ls_repeat_exit(rr_batch* b, int32_t enable);
 
+/* Diagnostic, debug-dump launches only: the solver makes its exit test before it solves for Mgrad = M^-1 grad (Newton: before the Hessian,
+ * its factorisation and the solve) and forms the next search direction, evaluates the warm-start candidate at qacc_smooth for its cost
+ * alone (no J' f walk over the contacts), and reuses that candidate's constraint rows where it is chosen -- work whose results nothing
+ * reads (rr_kernel.h Wave::solve).  enable = 0 makes the debug-dump instance do all of it anyway, in the order the reference has, so that
+ * a test can compare the two bit for bit.  The dump field `solver_end` holds, for the last substep, [0] 1 where the context at qacc_smooth
+ * was chosen (0: at qacc_warmstart) and [1] how the loop ended: a sum of 1 = iteration cap, 2 = improvement below the tolerance,
+ * 4 = gradient below the tolerance.  Default 1.  Every other instance always runs trimmed and carries no code for this switch. */
+int rr_batch_set_solver_trim(rr_batch* b, int32_t enable);
+
 /* ms of the most recent step-kernel launches on this batch measured with hipEvents on its stream
  * (enable with rr_batch_set_timing(b,1); each launch is then bracketed by events) */
 int rr_batch_set_timing(rr_batch* b, int32_t enable);
