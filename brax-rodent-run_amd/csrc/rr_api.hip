@@ -347,7 +347,7 @@ struct rr_batch {
   unsigned* bad_states = nullptr;       // (env, env step) events of the bad-state check (rr_env_io::bad_state_max; rr_batch_bad_states)
   unsigned* progress = nullptr;         // pacing counter of multi-step launches (RRIO::progress); RR_PACE=0 turns pacing off
   float *env_dof_f = nullptr, *env_act_f = nullptr, *env_con_f = nullptr;     // per-env parameter rows, owned (rr_batch_set_env_params)
-  int dbg_flags = 0;                    // debug-dump launches, RRIO::dbg_flags: RR_DBG_LS_RUN_REPEATS (rr_batch_set_ls_repeat_exit(b, 0)), RR_DBG_SOLVER_UNTRIMMED (rr_batch_set_solver_trim(b, 0))
+  int dbg_flags = 0;                    // debug-dump launches, RRIO::dbg_flags: RR_DBG_LS_RUN_REPEATS (rr_batch_set_ls_repeat_exit(b, 0)), RR_DBG_SOLVER_UNTRIMMED (rr_batch_set_solver_trim(b, 0)), RR_DBG_SOLVER_UNBATCHED (rr_batch_set_solver_batch(b, 0))
   float* eval_actions = nullptr;        // [N][nu]: where an evaluation launch without actions_out keeps the current action (rr_env_unroll_eval)
   bool has_env_params() const { return env_dof_f || env_act_f || env_con_f; }
 };
@@ -1323,6 +1323,12 @@ extern "C" int rr_batch_set_ls_repeat_exit(rr_batch* b, int32_t enable) {
 extern "C" int rr_batch_set_solver_trim(rr_batch* b, int32_t enable) {
   if (!b) return fail(RR_EINVAL, "rr_batch_set_solver_trim: null batch");
   b->dbg_flags = enable ? (b->dbg_flags & ~RR_DBG_SOLVER_UNTRIMMED) : (b->dbg_flags | RR_DBG_SOLVER_UNTRIMMED);
+  return RR_OK;
+}
+
+extern "C" int rr_batch_set_solver_batch(rr_batch* b, int32_t enable) {
+  if (!b) return fail(RR_EINVAL, "rr_batch_set_solver_batch: null batch");
+  b->dbg_flags = enable ? (b->dbg_flags & ~RR_DBG_SOLVER_UNBATCHED) : (b->dbg_flags | RR_DBG_SOLVER_UNBATCHED);
   return RR_OK;
 }
 

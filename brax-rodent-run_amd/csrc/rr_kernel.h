@@ -47,6 +47,12 @@
 #ifndef RR_LS_REPEAT_EXIT
 #define RR_LS_REPEAT_EXIT 1   // the line search leaves its bracketing loop after an iteration that changed nothing (Wave::linesearch; bit-identical results)
 #endif
+#ifndef RR_JOBS_RESIDENT
+#define RR_JOBS_RESIDENT 1    // the solve-job descriptors are loaded once per substep and held in registers (Wave::jobs_res; bit-identical results)
+#endif
+#ifndef RR_LS_STAGE_ONCE
+#define RR_LS_STAGE_ONCE 1    // the line search's compacted row positions and its D values are staged once per substep (Wave::ls_stage; bit-identical results)
+#endif
 #define RR_MINVAL 1e-15f
 #define RR_MINIMP 0.0001f
 #define RR_MAXIMP 0.9999f
@@ -242,6 +248,8 @@ struct RRIO {
   //     leaving the loop (RR_LS_REPEAT_EXIT);
   //   RR_DBG_SOLVER_UNTRIMMED (rr_batch_set_solver_trim(b, 0)): the solver solves for Mgrad and forms the next search direction BEFORE its
   //     exit test, walks the contacts (J' f) in the cost-only context at qacc_smooth, and rebuilds that context's rows where it is chosen.
+  //   RR_DBG_SOLVER_UNBATCHED (rr_batch_set_solver_batch(b, 0)): the line search stages its compacted positions and D values in every
+  //     call instead of once per substep (RR_LS_STAGE_ONCE).
   int dbg_flags;
   // MULTI-CLIP TRACKING (env epilogue): with `clip` set, track_pos is [num_clips][track_len][3] and environment e tracks clip clip[e]
   // (clamped into [0, num_clips - 1]); the frame clamp stays per clip.  A null `clip` is the single-clip path: track_pos [track_len][3].
@@ -252,6 +260,7 @@ struct RRIO {
 // ------------------------------------------------------------------------------------------ small math
 #define RR_DBG_LS_RUN_REPEATS 1
 #define RR_DBG_SOLVER_UNTRIMMED 2
+#define RR_DBG_SOLVER_UNBATCHED 4
 struct v3 { float x, y, z; };
 __device__ __forceinline__ v3 mk3(float x, float y, float z) { v3 r; r.x = x; r.y = y; r.z = z; return r; }
 __device__ __forceinline__ v3 ld3(const float* p) { return mk3(p[0], p[1], p[2]); }
@@ -481,7 +490,9 @@ template <class A> struct rr_same<A, A> { static constexpr bool value = true; };
 // membership test (J' f); contacts of condim 1 carry one row (rows 1..3 of the slot get D = 0); transmissions with several joints (fixed
 // tendons) go through per-actuator sums.  Production physics + env epilogue only: single-step, multi-step (UNROLL) and multi-step with the
 // actor inside (UNROLL + ACTOR); everything DYN-specific is re-derived per substep, so the multi-step loop carries nothing extra for it.
-template <int NBS, int NVS, int NCS, class DT, bool NEWTON = false, bool PAIR = false, bool DYN = false, bool RAND = false>
+// JRES: this instance may hold the solve-job descriptors in registers for the substep (RR_JOBS_RESIDENT; not the debug-dump instances, whose
+// dump paths leave no room for them)
+template <int NBS, int NVS, int NCS, class DT, bool NEWTON = false, bool PAIR = false, bool DYN = false, bool RAND = false, bool JRES = true>
 struct Wave {
   const DT& D;
   RRLoopTables TL;
@@ -1210,15 +1221,17 @@ struct Wave {
   // D.lmax (<= 16) entries, one piece per lane and job slot (k_coljob / k_rowjob); the piece sums go through the (dead)
   // pose cells s_buf and the owner lane of the column / row adds up its pieces.  Lane d owns x_d.
   static constexpr int NJS = NVS >= 3 ? NVS + 1 : NVS;      // job slots per lane (ktables: nslot)
-  // This lane's jobs (rodent_amd/ktables.py), reloaded per call from the L2-resident tables (held across the solver they
-  // would be spilled).  PREDICATE-FREE: every job runs D.lmax steps; a column job lists the byte offsets of its matrix
+  // This lane's jobs (rodent_amd/ktables.py), loaded from the L2-resident tables (once per substep, or with RR_JOBS_RESIDENT 0
+  // per call: see jobs_res below).  PREDICATE-FREE: every job runs D.lmax steps; a column job lists the byte offsets of its matrix
   // entries (padding: the matrix array's ZERO cell) and walks the vector from i0, a row job lists its ancestor dof ids
   // (padding: vector cell nv, which always holds 0) and walks the matrix row from byte offset ra.
   struct Jobs { int cw[NJS][8], ci0[NJS], rb[NJS][4], ra[NJS], own[NVS]; };
-  __device__ __forceinline__ void load_jobs(Jobs& j) {
+  __device__ __forceinline__ void load_jobs(Jobs& j) { load_jobs(j, TL.coljob, TL.rowjob, TL.jobown); }
+  template <class P>
+  __device__ __forceinline__ void load_jobs(Jobs& j, P coljob, P rowjob, P jobown) {
     constexpr int WJ = NJS * RR_LANES;
     const int ol = opaque(lane);
-    const rr_row<int> cj = row_at(TL.coljob, 1, ol), rj = row_at(TL.rowjob, 1, ol), jo = row_at(TL.jobown, 1, ol);   // one 32-bit lane offset, the rest immediates
+    const rr_row<int> cj = row_at(coljob, 1, ol), rj = row_at(rowjob, 1, ol), jo = row_at(jobown, 1, ol);   // one 32-bit lane offset, the rest immediates
 #pragma unroll
     for (int s = 0; s < NJS; ++s) {
 #pragma unroll
@@ -1230,6 +1243,36 @@ struct Wave {
     }
 #pragma unroll
     for (int s = 0; s < NVS; ++s) j.own[s] = ol + RR_LANES * s < D.nv ? jo[RR_LANES * s] : 0;
+  }
+  // RR_JOBS_RESIDENT: the descriptors depend on the lane alone, and a substep uses them 11-12 times (M * qacc_warmstart, the solve for
+  // qacc_smooth, one solve per CG iteration, the eulerdamp solve).  Each reload is ~30 global loads whose L2 round trip the first
+  // product of the call waits for.  The instances now sit well below the register cap (the reload dates from when they sat on it), so
+  // the substep loads them once, ahead of M * qacc_warmstart (load_jobs_resident), and every solve / product up to euler() reads
+  // this copy.  The opaque lane id in load_jobs keeps the load inside the substep: nothing is carried across the tree phases.
+  // The three table pointers are then read from the kernel arguments where the load stands, once per substep, instead of living in
+  // scalar registers through the launch for the per-call reloads.  The debug-dump instances (JRES false) keep the reload: with their
+  // dump paths the resident copy does not fit their registers.
+  static constexpr bool JOBS_RES = RR_JOBS_RESIDENT != 0 && JRES;
+  Jobs jobs_res;
+  __device__ __forceinline__ void load_jobs_resident() {
+    if constexpr (JOBS_RES) { const RRTables T = load_tables(); load_jobs(jobs_res, T.coljob, T.rowjob, T.jobown); }
+  }
+  // The resident copy as values the optimiser has not seen before (in place: no instruction, no register).  Without this it takes the
+  // unpacked offsets and ids of one call for those of the next, keeps them all alive across the solver and runs out of registers.
+  // Fixed dimensions: the entries beyond lmax are constants and stay so; run-time dimensions: every entry (no branch around nothing).
+  __device__ __forceinline__ void jobs_fresh() {
+    constexpr bool ALL = rr_same<DT, RRDims>::value;
+#pragma unroll
+    for (int s = 0; s < NJS; ++s) {
+#pragma unroll
+      for (int k = 0; k < 8; ++k) if (ALL || 2 * k < D.lmax) asm volatile("" : "+v"(jobs_res.cw[s][k]));
+      asm volatile("" : "+v"(jobs_res.ci0[s]));
+#pragma unroll
+      for (int k = 0; k < 4; ++k) if (ALL || 4 * k < D.lmax) asm volatile("" : "+v"(jobs_res.rb[s][k]));
+      asm volatile("" : "+v"(jobs_res.ra[s]));
+    }
+#pragma unroll
+    for (int s = 0; s < NVS; ++s) asm volatile("" : "+v"(jobs_res.own[s]));
   }
   // column piece: sum_t mat[cw_t] * vec[i0 + t];  row piece: sum_t mat[ra + t] * vec[rb_t]   (mat = one half of the pair array)
   __device__ __forceinline__ float col_piece(const Jobs& j, int s, const float* mat, const float* vec) const {
@@ -1262,8 +1305,10 @@ struct Wave {
   // mat: one half of a pair array holding an inverse factor; di: its 1/D
   template <bool DAMPED = false>
   __device__ __forceinline__ void ldl_solve_on(float* x, const float* mat, const float* di) {
-    Jobs jb;
-    load_jobs(jb);
+    Jobs jl;
+    if constexpr (!JOBS_RES) load_jobs(jl);
+    else jobs_fresh();
+    const Jobs& jb = JOBS_RES ? jobs_res : jl;
 #pragma unroll
     for (int s = 0; s < NVS; ++s) { const int d = lane + RR_LANES * s; if (d < D.nv) s_x[d] = x[s]; }
     sync();
@@ -1295,8 +1340,10 @@ struct Wave {
   __device__ __forceinline__ void mul_m(float* y) { mul_m_on(y, s_qLD); }
   __device__ __forceinline__ void mul_m_on(float* y, const float* mp) {
     constexpr int WJ = NJS * RR_LANES;
-    Jobs jb;
-    load_jobs(jb);
+    Jobs jl;
+    if constexpr (!JOBS_RES) load_jobs(jl);
+    else jobs_fresh();
+    const Jobs& jb = JOBS_RES ? jobs_res : jl;
 #pragma unroll
     for (int s = 0; s < NJS; ++s) {
       s_buf[s * RR_LANES + lane] = col_piece(jb, s, mp, s_vec);
@@ -2009,6 +2056,46 @@ struct Wave {
   // (Jaref, Jv, D) triples are compacted once per line search through LDS (positions by ballot / mbcnt; the staging cells
   // are the dead cinert / cvel / pose regions), so that every evaluation of the up to 2 + 3*ls_iterations points costs one
   // row per lane instead of 4*NCS + NVS.
+  // RR_LS_STAGE_ONCE: which rows are active (con_act, lim_act) and their D are fixed from constraint_rows() to the end of the substep,
+  // so the compacted positions of this lane's rows, the row count R and the D column are formed ONCE, at the head of solve(): a line
+  // search then stages and reads back Jaref and Jv alone.  Same positions, same values, same evaluation code (ls_eval).
+  int ls_R = 0;                       // wave-uniform
+  int ls_cpos[NCS], ls_lpos[NVS];     // first compacted row of this lane's contact slot / its limit row
+  float ls_rD[KR];
+  __device__ __forceinline__ void ls_stage() {
+    int R = 0;
+#pragma unroll
+    for (int cs = 0; cs < NCS; ++cs) {
+      const unsigned long long m = __ballot(con_act[cs]);
+      const int pos = R + 4 * (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+      R += 4 * __popcll(m);
+      ls_cpos[cs] = pos;
+      if (con_act[cs]) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) s_buf[pos + k] = (!DYN || k < con_nrow[cs]) ? con_D[cs] : 0.0f;
+      }
+    }
+#pragma unroll
+    for (int s = 0; s < NVS; ++s) {
+      const unsigned long long m = __ballot(lim_act[s]);
+      const int pos = R + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+      R += __popcll(m);
+      ls_lpos[s] = pos;
+      if (lim_act[s]) s_buf[pos] = lim_D[s];
+    }
+    ls_R = __builtin_amdgcn_readfirstlane(R);
+    sync();
+#pragma unroll
+    for (int r = 0; r < KR; ++r) {
+      ls_rD[r] = 0.0f;
+      if (r * RR_LANES < R) {
+        const int idx = r * RR_LANES + lane;
+        if (idx < R) ls_rD[r] = s_buf[idx];
+      }
+    }
+    sync();     // the pose cells are reused (J * x hand-off)
+  }
+
   template <bool PROF, bool DBG = false>
   __device__ __forceinline__ void linesearch() {
     float red[4] = {0, 0, 0, 0};
@@ -2026,7 +2113,31 @@ struct Wave {
       red[3] += search[s] * mv[s];
     }
     int R = 0;
-    {
+    bool stage_all = !RR_LS_STAGE_ONCE;
+    if constexpr (DBG) stage_all |= (dbg_flags & RR_DBG_SOLVER_UNBATCHED) != 0;
+    if (!stage_all) {
+      float* const st_jr = s_cinert; float* const st_jv = s_cvel;
+      // the staged values as values the optimiser has not seen before (in place: no instruction): it would otherwise hoist every mask and
+      // address derived from them out of the solver loop and hold them across it
+      asm volatile("" : "+s"(ls_R));
+#pragma unroll
+      for (int cs = 0; cs < NCS; ++cs) asm volatile("" : "+v"(ls_cpos[cs]));
+#pragma unroll
+      for (int s = 0; s < NVS; ++s) asm volatile("" : "+v"(ls_lpos[s]));
+#pragma unroll
+      for (int r = 0; r < KR; ++r) asm volatile("" : "+v"(ls_rD[r]));
+      R = ls_R;
+#pragma unroll
+      for (int cs = 0; cs < NCS; ++cs) {
+        if (con_act[cs]) {
+#pragma unroll
+          for (int k = 0; k < 4; ++k) { st_jr[ls_cpos[cs] + k] = con_jar[cs][k]; st_jv[ls_cpos[cs] + k] = con_jv[cs][k]; }
+        }
+      }
+#pragma unroll
+      for (int s = 0; s < NVS; ++s)
+        if (lim_act[s]) { st_jr[ls_lpos[s]] = lim_jar[s]; st_jv[ls_lpos[s]] = lim_jv[s]; }
+    } else {
       float* const st_jr = s_cinert; float* const st_jv = s_cvel; float* const st_D = s_buf;
 #pragma unroll
       for (int cs = 0; cs < NCS; ++cs) {
@@ -2053,8 +2164,9 @@ struct Wave {
       rjr[r] = rjv[r] = rD[r] = 0.0f;
       if (r * RR_LANES < R) {
         const int idx = r * RR_LANES + lane;
-        if (idx < R) { rjr[r] = s_cinert[idx]; rjv[r] = s_cvel[idx]; rD[r] = s_buf[idx]; }
+        if (idx < R) { rjr[r] = s_cinert[idx]; rjv[r] = s_cvel[idx]; if (stage_all) rD[r] = s_buf[idx]; }
       }
+      if (!stage_all) rD[r] = ls_rD[r];
     }
     solver_sum_n<4>(red);
     const float smag = sqrtf(red[0]) * so_meaninertia * (float)so_nv_scale;
@@ -2155,6 +2267,8 @@ struct Wave {
     // skips the contact walk (update_constraint(false): same force and cost arithmetic, empty ballot), and its rows Jaref are kept in
     // registers for ph 2, which would compute the same J * qacc_smooth - aref by the same code: ph 2 restores them and walks.
     const bool untrimmed = DBG && (dbg_flags & RR_DBG_SOLVER_UNTRIMMED) != 0;      // debug-dump instance: walk in ph 0, rebuild in ph 2, solve before the exit test
+    const bool unbatched = DBG && (dbg_flags & RR_DBG_SOLVER_UNBATCHED) != 0;      // debug-dump instance: the line search stages positions and D in every call
+    if (RR_LS_STAGE_ONCE && !unbatched) ls_stage();
     float cost_smooth = 0.0f;
     bool use_smooth = false;
     float jar0[NCS][4], ljar0[NVS];

@@ -13,7 +13,7 @@
   // LDS -- checked on the HOST for every instance a batch may launch (rr_batch_create: hipFuncGetAttributes().sharedSizeBytes == 0)
   const DT D(Dk);
   const int wrep = PAIR ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0;
-  Wave<NBS, NVS, NCS, DT, NEWTON, PAIR, DYN, RAND> w(D, Tk, PAIR ? lds + wrep * (D.lds_bytes_rep >> 2) : lds);
+  Wave<NBS, NVS, NCS, DT, NEWTON, PAIR, DYN, RAND, !DBG> w(D, Tk, PAIR ? lds + wrep * (D.lds_bytes_rep >> 2) : lds);
   int lane = threadIdx.x & (RR_LANES - 1);
   if (PAIR) { w.rep = wrep; w.s_xc = lds + 2 * (D.lds_bytes_rep >> 2); }
   RRIO io = load_io();
@@ -216,6 +216,7 @@
 #pragma unroll
       for (int s = 0; s < NVS; ++s) { const int d = lane + RR_LANES * s; wv[s] = d < D.nv ? w.s_warm[d] : 0.0f; }
       w.put_vec(wv);
+      w.load_jobs_resident();     // the solve-job descriptors of this substep: read by every product / solve from here to euler()
       w.mul_m(w.Ma_warm);
     }
     // ... and by phase: the two level schedules are one long dependent chain of LDS round trips that issues little; at top priority

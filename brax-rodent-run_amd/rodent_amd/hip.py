@@ -80,7 +80,7 @@ class RRPpoCfg(C.Structure):
 
 EXPORTS = ["rr_model_load", "rr_model_dims", "rr_model_set_solver", "rr_model_set_solver_type", "rr_model_destroy", "rr_model_table", "rr_kernarg_layout", "rr_batch_create",
            "rr_batch_destroy", "rr_pipeline_init", "rr_pipeline_step", "rr_env_step", "rr_env_reset", "rr_pipeline_step_to", "rr_env_step_to", "rr_batch_contact_overflow", "rr_batch_bad_states", "rr_batch_unroll_supported", "rr_env_unroll", "rr_env_unroll_policy", "rr_batch_eval_supported", "rr_env_unroll_eval",
-           "rr_compute_gae", "rr_mlp_forward", "rr_ppo_loss_workspace_bytes", "rr_ppo_loss", "rr_policy_act_workspace_bytes", "rr_policy_act", "rr_policy_sample", "rr_policy_backward_workspace_bytes", "rr_policy_backward", "rr_mlp_silu_backward_workspace_bytes", "rr_mlp_silu_backward", "rr_mlp_value_backward_workspace_bytes", "rr_mlp_policy_backward", "rr_mlp_policy_backward_workspace_bytes", "rr_mlp_value_backward", "rr_mlp_weight_grad_workspace_bytes", "rr_mlp_weight_grad", "rr_mlp_weight_grad_batch_workspace_bytes", "rr_mlp_weight_grad_batch", "rr_obs_moments_workspace_bytes", "rr_obs_moments", "rr_wrap_episode_autoreset", "rr_debug_layout", "rr_batch_set_schedule", "rr_batch_set_env_params", "rr_batch_env_params_supported", "rr_batch_set_profile", "rr_batch_set_ls_repeat_exit", "rr_batch_set_solver_trim", "rr_batch_set_timing", "rr_batch_kernel_time", "rr_last_error"]
+           "rr_compute_gae", "rr_mlp_forward", "rr_ppo_loss_workspace_bytes", "rr_ppo_loss", "rr_policy_act_workspace_bytes", "rr_policy_act", "rr_policy_sample", "rr_policy_backward_workspace_bytes", "rr_policy_backward", "rr_mlp_silu_backward_workspace_bytes", "rr_mlp_silu_backward", "rr_mlp_value_backward_workspace_bytes", "rr_mlp_policy_backward", "rr_mlp_policy_backward_workspace_bytes", "rr_mlp_value_backward", "rr_mlp_weight_grad_workspace_bytes", "rr_mlp_weight_grad", "rr_mlp_weight_grad_batch_workspace_bytes", "rr_mlp_weight_grad_batch", "rr_obs_moments_workspace_bytes", "rr_obs_moments", "rr_wrap_episode_autoreset", "rr_debug_layout", "rr_batch_set_schedule", "rr_batch_set_env_params", "rr_batch_env_params_supported", "rr_batch_set_profile", "rr_batch_set_ls_repeat_exit", "rr_batch_set_solver_trim", "rr_batch_set_solver_batch", "rr_batch_set_timing", "rr_batch_kernel_time", "rr_last_error"]
 
 _lib = None
 
@@ -167,6 +167,7 @@ def lib():
         L.rr_batch_env_params_supported.argtypes = [C.c_void_p]
         L.rr_batch_set_ls_repeat_exit.argtypes = [C.c_void_p, C.c_int32]
         L.rr_batch_set_solver_trim.argtypes = [C.c_void_p, C.c_int32]
+        L.rr_batch_set_solver_batch.argtypes = [C.c_void_p, C.c_int32]
         L.rr_batch_set_timing.argtypes = [C.c_void_p, C.c_int32]
         L.rr_batch_kernel_time.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
         _lib = L
@@ -477,6 +478,11 @@ class Batch:
         of that context's rows where it is chosen (C ABI `rr_batch_set_solver_trim`).  The dump field `solver_end` tells which start was
         chosen and how the loop ended.  Default True."""
         _check(lib().rr_batch_set_solver_trim(self.h, int(enable)))
+
+    def set_solver_batch(self, enable: bool):
+        """Debug-dump launches only: False makes the line search form and stage its compacted row positions and D values in every call
+        instead of once per substep (C ABI `rr_batch_set_solver_batch`).  Default True."""
+        _check(lib().rr_batch_set_solver_batch(self.h, int(enable)))
 
     def set_timing(self, enable: bool):
         _check(lib().rr_batch_set_timing(self.h, int(enable)))

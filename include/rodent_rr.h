@@ -455,6 +455,13 @@ int rr_batch_set_ls_repeat_exit(rr_batch* b, int32_t enable);
  * 4 = gradient below the tolerance.  Default 1.  Every other instance always runs trimmed and carries no code for this switch. */
 int rr_batch_set_solver_trim(rr_batch* b, int32_t enable);
 
+/* Diagnostic, debug-dump launches only: the line search forms once per substep what does not change inside it -- the compacted positions
+ * of the active constraint rows, their count and their D column (rr_kernel.h RR_LS_STAGE_ONCE).  enable = 0 makes the debug-dump instance
+ * form and stage them in every line search, so that a test can compare the two bit for bit.  Default 1.  Every other instance always
+ * stages once and carries no code for this switch.  (The once-per-substep load of the solve-job descriptors, RR_JOBS_RESIDENT, has no
+ * second path to switch.) */
+int rr_batch_set_solver_batch(rr_batch* b, int32_t enable);
+
 /* ms of the most recent step-kernel launches on this batch measured with hipEvents on its stream
  * (enable with rr_batch_set_timing(b,1); each launch is then bracketed by events) */
 int rr_batch_set_timing(rr_batch* b, int32_t enable);
