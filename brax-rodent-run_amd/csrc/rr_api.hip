@@ -7,6 +7,7 @@
 
 #include <atomic>
 #include <climits>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -58,7 +59,7 @@ struct rr_model {
 // One function maps (model, launch form, variant) to the kernel instance that serves it, or to the reason there is none: launch(),
 // the support queries and the attribute loop of rr_batch_create all ask it, so none of them can disagree about what exists.
 enum Form { F_STEP, F_UNROLL, F_ACTOR, F_EVAL, N_FORMS };                        // single step | multi-step | ... with the actor | evaluation
-enum Variant { V_PROD, V_DEBUG, V_PROFILE, V_RAND, V_PAIR, N_VARIANTS };         // production | debug dump | cycle-stamp profile | per-env parameters | two-wave pair
+enum Variant { V_PROD, V_DEBUG, V_PROFILE, V_RAND, V_PAIR, V_POSE, N_VARIANTS }; // production | debug dump | cycle-stamp profile | per-env parameters | two-wave pair | pose tracking
 struct Instance { kern_t kern; const char* why = nullptr; bool fixed = false; };      // why: the reason when kern is null (multi-step forms: with the entry point that reports it); fixed: compiled for the model's dimensions
 
 static Instance select(const rr_model* m, Form form, Variant v) {
@@ -66,7 +67,8 @@ static Instance select(const rr_model* m, Form form, Variant v) {
   const bool newton = m->solver == 2, eval = form == F_EVAL, unroll = form != F_STEP, actor = form == F_ACTOR;
   const char *no_diag = "no diagnostic kernel instance for this model", *no_slots = "no kernel instance for this model's slot counts";
   auto no = [](const char* why) { return Instance{nullptr, why}; };
-  // rr_step_kernel<NBS, NVS, NCS, PROF, DBG, dims, NEWTON, UNROLL, ACTOR, PAIR, DYN>, rr_rand_kernel<dims, UNROLL, ACTOR>, rr_eval_kernel<dims, DYN>
+  // rr_step_kernel<NBS, NVS, NCS, PROF, DBG, dims, NEWTON, UNROLL, ACTOR, PAIR, DYN>, rr_rand_kernel<dims, UNROLL, ACTOR>, rr_eval_kernel<dims, DYN>,
+  // rr_pose_kernel<dims, UNROLL, ACTOR>
   if (v == V_PAIR && (unroll || newton || !RRDimsRodentNew::matches(m->kd_rep))) return no("no two-wave pair instance for this model / launch form");
   if (v == V_PAIR) return {rr_step_kernel<2, 2, 1, false, false, RRDimsRodentNew, false, false, false, true>, nullptr, true};      // one replica = the rodent_new dims
   // Eligibility first.  Multi-step instances: the single-rodent floor-contact models (fixed-dimension or generic) and the candidate-pair models
@@ -79,6 +81,13 @@ static Instance select(const rr_model* m, Form form, Variant v) {
     if (m->pair_ok) return no("rr_env_unroll_eval: two-tree models served by the two-wave pair instance have no multi-step instance");
     if (!s221) return no("rr_env_unroll_eval: only the (2,2,1) slot counts have an evaluation instance");
     if (v == V_RAND) return no("rr_env_unroll_eval: no evaluation instance reads per-env parameters (this batch carries some)");
+    if (v == V_POSE) return no("rr_env_unroll_eval: no evaluation instance rewards the pose (this env io carries track_pose); evaluate step by step");
+  } else if (v == V_POSE) {
+    // Pose tracking (rr_pose_kernel): the same models and launch forms as the per-env parameters below, shared tables
+    if (m->dyn) return no("pose tracking: models with candidate-pair contacts (DYN instances) have no pose instance");
+    if (m->pair_ok) return no("pose tracking: two-tree models served by the two-wave pair instance have no pose instance");
+    if (newton) return no("pose tracking: the Newton solver's instances have no pose instance");
+    if (!s221) return no("pose tracking: only the (2,2,1) slot counts have pose instances");
   } else if (v == V_RAND) {
     // Per-environment parameters (rr_rand_kernel): the production CG instances of the single-rodent floor-contact models -- fixed-dimension
     // or generic (2,2,1) -- as single-step, multi-step and multi-step with the actor
@@ -108,6 +117,7 @@ static Instance select(const rr_model* m, Form form, Variant v) {
     typedef typename std::remove_pointer<decltype(t)>::type DT;      // t: a null pointer that names the dims type
     if (eval) return rr_eval_kernel<DT>;
     if (v == V_RAND) return actor ? rr_rand_kernel<DT, true, true> : (unroll ? rr_rand_kernel<DT, true> : rr_rand_kernel<DT>);
+    if (v == V_POSE) return actor ? rr_pose_kernel<DT, true, true> : (unroll ? rr_pose_kernel<DT, true> : rr_pose_kernel<DT>);
     return actor ? rr_step_kernel<2, 2, 1, false, false, DT, false, true, true> : (unroll ? rr_step_kernel<2, 2, 1, false, false, DT, false, true> : rr_step_kernel<2, 2, 1, false, false, DT>);
   };
   if (RRDimsRodent::matches(m->kd)) return {family((RRDimsRodent*)nullptr), nullptr, true};      // fixed-dimension instances (rr_kernel.h RRDimsFixed)
@@ -349,6 +359,7 @@ struct rr_batch {
   float *env_dof_f = nullptr, *env_act_f = nullptr, *env_con_f = nullptr;     // per-env parameter rows, owned (rr_batch_set_env_params)
   int dbg_flags = 0;                    // debug-dump launches, RRIO::dbg_flags: RR_DBG_LS_RUN_REPEATS (rr_batch_set_ls_repeat_exit(b, 0)), RR_DBG_SOLVER_UNTRIMMED (rr_batch_set_solver_trim(b, 0)), RR_DBG_SOLVER_UNBATCHED (rr_batch_set_solver_batch(b, 0))
   float* eval_actions = nullptr;        // [N][nu]: where an evaluation launch without actions_out keeps the current action (rr_env_unroll_eval)
+  rr_pose_io pose = {};                 // pose tracking of the env steps (rr_batch_set_pose); track_pose null: off
   bool has_env_params() const { return env_dof_f || env_act_f || env_con_f; }
 };
 
@@ -617,7 +628,17 @@ static int launch(rr_batch* b, const Launch& L) {
   if (params && io.dbg) return fail(RR_EUNSUPPORTED, "launch: no debug dump on a batch with per-env parameters (the debug instance reads the model's shared tables)");
   if (params && geom) return fail(RR_EUNSUPPORTED, "launch: no contact-geometry outputs on a batch with per-env parameters (they are served by the debug instance)");
   if (params && b->prof) return fail(RR_EUNSUPPORTED, "launch: no profile build on a batch with per-env parameters");
-  Variant v = b->prof ? V_PROFILE : ((io.dbg || geom) ? V_DEBUG : (params ? V_RAND : V_PROD));
+  // pose tracking (rr_batch_set_pose): an env step's reward terms -- a reset has no reward and ignores the block -- served by the POSE
+  // instance of the same launch form; shared tables, production instances only
+  const bool pose = b->pose.track_pose && L.env && L.mode == 1;
+  if (pose) {
+    io.track_pose = b->pose.track_pose; io.pose_metrics = b->pose.pose_metrics;
+    io.pose_quat_w = b->pose.quat_reward_weight; io.pose_quat_k = b->pose.quat_reward_scale;
+    io.pose_joint_w = b->pose.joint_reward_weight; io.pose_joint_k = b->pose.joint_reward_scale;
+  }
+  if (pose && params) return fail(RR_EUNSUPPORTED, "launch: pose tracking: no pose instance reads per-env parameters (this batch carries some)");
+  if (pose && (io.dbg || geom || b->prof)) return fail(RR_EUNSUPPORTED, "launch: pose tracking: no debug dump, contact-geometry outputs or profile build with track_pose (diagnostic instances have no pose form)");
+  Variant v = b->prof ? V_PROFILE : ((io.dbg || geom) ? V_DEBUG : (params ? V_RAND : (pose ? V_POSE : V_PROD)));
   // two-tree model, physics only, no diagnostics: one wavefront per replica (rr_kernel.h PAIR)
   const bool pair = m->pair_ok && v == V_PROD && !L.env && !L.out && !L.un && !b->env_map && !b->cost && m->solver != 2;
   if (pair) v = V_PAIR;
@@ -1278,6 +1299,25 @@ extern "C" int rr_batch_env_params_supported(const rr_batch* b) {
   if (!b) return fail(RR_EINVAL, "rr_batch_env_params_supported: null batch");
   return select(b->m, F_STEP, V_RAND).kern ? 1 : 0;
 }
+extern "C" int rr_batch_pose_supported(const rr_batch* b) {
+  if (!b) return fail(RR_EINVAL, "rr_batch_pose_supported: null batch");
+  const Instance in = select(b->m, F_STEP, V_POSE);
+  const char* why = in.kern ? nullptr : in.why;
+  if (!why && b->has_env_params()) why = "pose tracking: no pose instance reads per-env parameters (this batch carries some)";
+  if (!why && b->prof) why = "pose tracking: no profile build with track_pose";
+  if (why) (void)fail(RR_EUNSUPPORTED, std::string("rr_batch_pose_supported: ") + why);
+  return why ? 0 : 1;
+}
+extern "C" int rr_batch_set_pose(rr_batch* b, const rr_pose_io* p) {
+  if (!b) return fail(RR_EINVAL, "rr_batch_set_pose: null batch");
+  if (!p || (!p->track_pose && !p->pose_metrics)) { b->pose = rr_pose_io{}; return RR_OK; }
+  if (!p->track_pose || !p->pose_metrics) return fail(RR_EINVAL, "rr_batch_set_pose: track_pose and pose_metrics go together");
+  for (float x : {p->quat_reward_weight, p->quat_reward_scale, p->joint_reward_weight, p->joint_reward_scale})
+    if (!(x >= 0.0f) || !std::isfinite(x)) return fail(RR_EINVAL, "rr_batch_set_pose: pose reward weights and scales must be finite and >= 0");
+  if (rr_batch_pose_supported(b) != 1) return RR_EUNSUPPORTED;      // the reason is in place
+  b->pose = *p;
+  return RR_OK;
+}
 extern "C" int rr_batch_set_env_params(rr_batch* b, const rr_env_params* p) {
   if (!b) return fail(RR_EINVAL, "rr_batch_set_env_params: null batch");
   const rr_dims& d = b->m->dims;
@@ -1286,6 +1326,7 @@ extern "C" int rr_batch_set_env_params(rr_batch* b, const rr_env_params* p) {
     const Instance in = select(b->m, F_STEP, V_RAND);
     if (!in.kern) return fail(RR_EUNSUPPORTED, std::string("rr_batch_set_env_params: no kernel instance with per-env parameters: ") + in.why);
     if (b->prof) return fail(RR_EUNSUPPORTED, "rr_batch_set_env_params: no profile build on a batch with per-env parameters (rr_batch_set_profile is on)");
+    if (b->pose.track_pose) return fail(RR_EUNSUPPORTED, "rr_batch_set_env_params: pose tracking: no pose instance reads per-env parameters (rr_batch_set_pose is on)");
     if (p->num_envs != b->N) return fail(RR_EINVAL, "rr_batch_set_env_params: num_envs differs from the batch's");
     if ((p->dof_f && p->dof_rows != d.nv) || (p->act_f && p->act_rows != d.nu) || (p->con_f && p->con_rows != d.ncon))
       return fail(RR_EINVAL, "rr_batch_set_env_params: row counts must be the model's nv (dof_f), nu (act_f), ncon (con_f)");

@@ -255,6 +255,16 @@ struct RRIO {
   // (clamped into [0, num_clips - 1]); the frame clamp stays per clip.  A null `clip` is the single-clip path: track_pos [track_len][3].
   int num_clips;               // (also keeps sizeof(RRIO) a multiple of 8, RRKArgs)
   const int* clip;             // nullable [N]
+  // POSE TRACKING (env epilogue of the POSE instances, rr_pose_kernel; no other instance reads these): the clip's root quaternion and
+  // joint angles next to its root position.  track_pose is [T][nq - 3] (with `clip` set [num_clips][T][nq - 3]), a row = quaternion
+  // (w, x, y, z) then the nq - 7 joints, indexed by the clip and frame the position reward reads.  With q = qpos[3:7], j = qpos[7:]:
+  //   d = conj(r_q) (x) q,  theta = 2 atan2(|d.xyz|, |d.w|)      (invariant to the sign and the scale of q, well conditioned at 0)
+  //   quat_reward = pose_quat_w exp(-pose_quat_k theta^2),  joint_reward = pose_joint_w exp(-pose_joint_k sum_i (j_i - r_j,i)^2)
+  //   reward = (plain reward + quat_reward) + joint_reward;  pose_metrics[env] = (quat_reward, joint_reward), zeroed by a bad step
+  // All six are fetched by narrow loads where they are used (load_io_member), never through load_io().
+  const float* track_pose;
+  float* pose_metrics;         // [N][2]
+  float pose_quat_w, pose_quat_k, pose_joint_w, pose_joint_k;
 };
 
 // ------------------------------------------------------------------------------------------ small math
@@ -2427,7 +2437,8 @@ static_assert(alignof(RRDims) == 4 && alignof(RRTables) == 8 && alignof(RRIO) ==
 static_assert(offsetof(RRKArgs, T) == rr_align_up(sizeof(RRDims), alignof(RRTables)), "RRTables follows RRDims at its natural alignment");
 static_assert(offsetof(RRKArgs, io) == rr_align_up(offsetof(RRKArgs, T) + sizeof(RRTables), alignof(RRIO)), "RRIO follows RRTables at its natural alignment");
 static_assert(offsetof(RRKArgs, num_envs) == offsetof(RRKArgs, io) + sizeof(RRIO) && sizeof(RRIO) % 8 == 0, "scalars follow RRIO without padding");
-static_assert(offsetof(RRIO, clip) % 8 == 0 && offsetof(RRIO, clip) + sizeof(const int*) == sizeof(RRIO), "the clip ids close RRIO without padding");
+static_assert(offsetof(RRIO, clip) % 8 == 0 && offsetof(RRIO, clip) + sizeof(const int*) == offsetof(RRIO, track_pose), "the pose members follow the clip ids without padding");
+static_assert(offsetof(RRIO, pose_joint_k) + sizeof(float) == sizeof(RRIO), "the pose members close RRIO without padding");
 // ... and so are the model tables outside the solver's loops: RRTables is re-read at the head of each phase that indexes a table
 // (narrow scalar loads next to an existing hand-off; the unused members' loads are dead), so no table pointer is held across the
 // substep.  The loops' own tables are the exception (RRLoopTables, taken once from the parameter).
@@ -2605,7 +2616,7 @@ __device__ __forceinline__ void rr_actor_step(const RRIO& io, const DT& D, int l
 template <int NBS, int NVS, int NCS, bool PROF, bool DBG, class DT, bool NEWTON = false, bool UNROLL = false, bool ACTOR = false, bool PAIR = false, bool DYN = false>
 __global__ __launch_bounds__((PAIR ? 2 : 1) * RR_LANES, (NVS >= 3 ? 1 : 2)) void rr_step_kernel(const RRDims Dk, const RRTables Tk, const RRIO io_kernarg, const int num_envs,
                                                            const int n_frames) {
-  constexpr bool RAND = false, EVAL = false;
+  constexpr bool RAND = false, EVAL = false, POSE = false;
 #include "rr_step_body.inc"
 }
 // Per-environment parameters: the same argument list (load_io / load_tables / load_dims find the block at the same offsets), production
@@ -2613,7 +2624,7 @@ __global__ __launch_bounds__((PAIR ? 2 : 1) * RR_LANES, (NVS >= 3 ? 1 : 2)) void
 template <class DT, bool UNROLL = false, bool ACTOR = false>
 __global__ __launch_bounds__(RR_LANES, 2) void rr_rand_kernel(const RRDims Dk, const RRTables Tk, const RRIO io_kernarg, const int num_envs, const int n_frames) {
   constexpr int NBS = 2, NVS = 2, NCS = 1;
-  constexpr bool PROF = false, DBG = false, NEWTON = false, PAIR = false, DYN = false, RAND = true, EVAL = false;
+  constexpr bool PROF = false, DBG = false, NEWTON = false, PAIR = false, DYN = false, RAND = true, EVAL = false, POSE = false;
 #include "rr_step_body.inc"
 }
 // Evaluation (rr_env_unroll_eval): the multi-step form with the actor inside as brax's Evaluator and the launcher's evaluation rollout
@@ -2624,6 +2635,16 @@ __global__ __launch_bounds__(RR_LANES, 2) void rr_rand_kernel(const RRDims Dk, c
 template <class DT, bool DYN = false>
 __global__ __launch_bounds__(RR_LANES, 2) void rr_eval_kernel(const RRDims Dk, const RRTables Tk, const RRIO io_kernarg, const int num_envs, const int n_frames) {
   constexpr int NBS = 2, NVS = 2, NCS = 1;
-  constexpr bool PROF = false, DBG = false, NEWTON = false, PAIR = false, RAND = false, UNROLL = true, ACTOR = true, EVAL = true;
+  constexpr bool PROF = false, DBG = false, NEWTON = false, PAIR = false, RAND = false, UNROLL = true, ACTOR = true, EVAL = true, POSE = false;
+#include "rr_step_body.inc"
+}
+// Pose tracking (rr_batch_set_pose, rr_pose_io): the env epilogue also rewards the clip's root orientation and joint angles (RRIO, POSE TRACKING).
+// A fourth entry for the reason the two above are entries of their own: the instances of the other three keep their code, every
+// `if (POSE)` in the body folds away there.  Production CG instances of the (2,2,1) slot counts, shared tables: single-step, multi-step,
+// multi-step with the actor.
+template <class DT, bool UNROLL = false, bool ACTOR = false>
+__global__ __launch_bounds__(RR_LANES, 2) void rr_pose_kernel(const RRDims Dk, const RRTables Tk, const RRIO io_kernarg, const int num_envs, const int n_frames) {
+  constexpr int NBS = 2, NVS = 2, NCS = 1;
+  constexpr bool PROF = false, DBG = false, NEWTON = false, PAIR = false, DYN = false, RAND = false, EVAL = false, POSE = true;
 #include "rr_step_body.inc"
 }

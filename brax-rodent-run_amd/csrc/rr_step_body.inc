@@ -1,10 +1,11 @@
 // rr_step_body.inc -- the body of the step kernel, included by each of its __global__ entries in rr_kernel.h (rr_step_kernel,
-// rr_rand_kernel, rr_eval_kernel).  In scope where it is included: the kernel's five arguments (Dk, Tk, io_kernarg, num_envs, n_frames) and the
-// compile-time switches NBS, NVS, NCS, PROF, DBG, DT, NEWTON, UNROLL, ACTOR, PAIR, DYN, RAND, EVAL.
+// rr_rand_kernel, rr_eval_kernel, rr_pose_kernel).  In scope where it is included: the kernel's five arguments (Dk, Tk, io_kernarg, num_envs, n_frames) and the
+// compile-time switches NBS, NVS, NCS, PROF, DBG, DT, NEWTON, UNROLL, ACTOR, PAIR, DYN, RAND, EVAL, POSE.
 // Why text and not a function: see the note above rr_step_kernel.
   static_assert(!PAIR || (!PROF && !DBG && !NEWTON && !UNROLL && !ACTOR), "PAIR: production physics instance only");
   static_assert(!DYN || (!PROF && !DBG && !NEWTON && !PAIR), "DYN: production instances only (single-step, multi-step, multi-step with the actor)");
   static_assert(!ACTOR || UNROLL, "the actor lives in the multi-step instances");
+  static_assert(!POSE || (!RAND && !EVAL && !PROF && !DBG && !NEWTON && !PAIR && !DYN), "POSE: production CG instances of the floor-contact models only");
   static_assert(!EVAL || (ACTOR && !RAND && !PROF && !DBG && !NEWTON && !PAIR), "EVAL: a form of the production multi-step instance with the actor");
   extern __shared__ __attribute__((aligned(16))) float lds[];
   int env = blockIdx.x;
@@ -364,6 +365,26 @@
       float a2 = 0.0f;
       for (int i = lane; i < D.nu; i += RR_LANES) { const float a = io.ctrl[ctrl_at + i]; a2 += a * a; }
       a2 = wave_sum(a2);
+      // ---- POSE TRACKING (POSE instances, RRIO::track_pose): the clip's row [quaternion, joints] at the clip and frame of the position
+      // reward.  The lanes read the joint part coalesced, the squared errors are rounded one by one and summed over the wave; lane 0 forms
+      // the two terms below.  The members come by narrow loads HERE, for the reason given at the bad-state check above.
+      // Roundings: the pose arithmetic stands in blocks with floating-point contraction OFF and uses the plain operators.  __fmul_rn /
+      // __fadd_rn are `x * y` / `x + y` in an inline function and carry the translation unit's contraction licence with them: the
+      // backend fused weight * exp(..) into the sum that forms the reward (one ulp off the stored metric) until the pragma stood here.
+      const float* prow = nullptr;
+      float pe2 = 0.0f;
+      if (POSE) {
+        const float* tpose = load_io_member<const float*>(offsetof(RRIO, track_pose));
+        if (tpose) {
+#pragma clang fp contract(off)
+          int pc = 0;
+          if (io.clip) { pc = io.clip[env]; pc = pc < 0 ? 0 : (pc > io.num_clips - 1 ? io.num_clips - 1 : pc); }
+          const int pf = old_frame < 0 ? 0 : (old_frame > io.track_len - 1 ? io.track_len - 1 : old_frame);
+          prow = tpose + ((size_t)pc * (size_t)io.track_len + (size_t)pf) * (size_t)(D.nq - 3);
+          for (int i = lane; i < D.nq - 7; i += RR_LANES) { const float e = w.s_qpos[7 + i] - prow[4 + i]; const float ee = e * e; pe2 = pe2 + ee; }
+          pe2 = wave_sum(pe2);
+        }
+      }
       if (lane == 0) {
         int fi = old_frame < 0 ? 0 : (old_frame > io.track_len - 1 ? io.track_len - 1 : old_frame);
         const v3 dx = ld3(w.s_qpos) - ld3(track + 3 * fi);
@@ -378,7 +399,28 @@
         if (z > io.z_max) healthy = 0.0f;
         const float hr = io.terminate_when_unhealthy ? io.healthy_reward : __fmul_rn(io.healthy_reward, healthy);
         const float cc = __fmul_rn(io.ctrl_cost_weight, a2);     // explicit roundings: every instance of the kernel forms the reward identically
-        const float rew = __fsub_rn(__fadd_rn(pos_reward, hr), cc);   // (left to the optimiser, one instance fused the product into the sum: 1 ulp)
+        const float plain_rew = __fsub_rn(__fadd_rn(pos_reward, hr), cc);   // (left to the optimiser, one instance fused the product into the sum: 1 ulp)
+        float rew = plain_rew;
+        if (POSE) {
+          if (prow) {      // d = conj(r_q) (x) q, theta = 2 atan2(|d.xyz|, |d.w|); every product and sum rounded on its own (contraction off)
+#pragma clang fp contract(off)
+            const float rw = prow[0], rx = prow[1], ry = prow[2], rz = prow[3];
+            const float qw = w.s_qpos[3], qx = w.s_qpos[4], qy = w.s_qpos[5], qz = w.s_qpos[6];
+            const float dw = ((rw * qw + rx * qx) + ry * qy) + rz * qz;
+            const float dq1 = ((rw * qx - rx * qw) - ry * qz) + rz * qy;
+            const float dq2 = ((rw * qy + rx * qz) - ry * qw) - rz * qx;
+            const float dq3 = ((rw * qz - rx * qy) + ry * qx) - rz * qw;
+            const float dv = sqrtf((dq1 * dq1 + dq2 * dq2) + dq3 * dq3);
+            const float theta = 2.0f * atan2f(dv, fabsf(dw));
+            const float xq = load_io_member<float>(offsetof(RRIO, pose_quat_k)) * (theta * theta);
+            const float quat_rew = load_io_member<float>(offsetof(RRIO, pose_quat_w)) * expf(-xq);
+            const float xj = load_io_member<float>(offsetof(RRIO, pose_joint_k)) * pe2;
+            const float joint_rew = load_io_member<float>(offsetof(RRIO, pose_joint_w)) * expf(-xj);
+            rew = (plain_rew + quat_rew) + joint_rew;
+            float* pm = load_io_member<float*>(offsetof(RRIO, pose_metrics)) + 2 * (size_t)env;
+            pm[0] = quat_rew; pm[1] = joint_rew;
+          }
+        }
         io.reward[env] = rew;
         if (ACTOR && !EVAL) io.t_reward[rr_traj_at(io, num_envs, env, ut)] = rew;
         io.done[env] = io.terminate_when_unhealthy ? 1.0f - healthy : 0.0f;
@@ -391,6 +433,9 @@
           if (ACTOR && !EVAL) io.t_reward[rr_traj_at(io, num_envs, env, ut)] = 0.0f;
           io.done[env] = 1.0f;
           io.metrics[3 * env] = 0.0f; io.metrics[3 * env + 1] = 0.0f; io.metrics[3 * env + 2] = 0.0f;
+          if (POSE) {
+            if (prow) { float* pm = load_io_member<float*>(offsetof(RRIO, pose_metrics)) + 2 * (size_t)env; pm[0] = 0.0f; pm[1] = 0.0f; }
+          }
         }
       }
     }

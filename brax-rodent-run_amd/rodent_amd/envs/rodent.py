@@ -45,6 +45,19 @@ def reset_draws(keys, nq: int, nv: int, reset_noise_scale: float, num_clips: Opt
     return start_frame, qpos_noise, qvel, clip
 
 
+def reset_qpos(qpos0, track: np.ndarray, start_frame, qpos_noise, clip=None, pose: Optional[np.ndarray] = None) -> np.ndarray:
+    """The qpos `Rodent.reset` starts from, float32 [N, nq], out of the draws of `reset_draws`: qpos0 with the root position replaced by
+    track[(clip,) start_frame] (the frame clamped within the clip), plus the noise.  `pose` (the env's [(C,) T, nq - 3] rows, given with
+    `reset_to_reference=True`): qpos[3:] starts from pose[(clip,) start_frame] instead of qpos0[3:].  The draws are not touched."""
+    N = len(start_frame)
+    qpos = np.tile(np.asarray(qpos0, dtype=np.float32), (N, 1))
+    fi = np.clip(start_frame, 0, track.shape[-2] - 1)
+    qpos[:, :3] = track[fi] if clip is None else track[clip, fi]
+    if pose is not None:
+        qpos[:, 3:] = pose[fi] if clip is None else pose[clip, fi]
+    return qpos + qpos_noise
+
+
 def _check_track(track_pos) -> np.ndarray:
     """track_pos as float32 [T, 3] or [C, T, 3] (C >= 1, T >= 1), ValueError otherwise."""
     t = track_pos.detach().cpu().numpy() if torch.is_tensor(track_pos) else np.asarray(track_pos)
@@ -69,6 +82,60 @@ def _check_clip(clip, num_clips: Optional[int], num_envs: int) -> np.ndarray:
     return c.astype(np.int32)
 
 
+def pose_rewards(qpos, ref_quat, ref_joints, weights=(1.0, 1.0), scales=(2.0, 0.5)):
+    """The two pose terms of the step kernel's epilogue (`Rodent(track_quat=..., track_joints=...)`; rr_pose_io) restated in
+    numpy float64.  `qpos` [..., nq] the stepped state, `ref_quat` [..., 4] (w, x, y, z) and `ref_joints` [..., nq - 7] the clip's row at
+    the clip and frame the position reward reads, `weights` = (quat_reward_weight, joint_reward_weight), `scales` likewise.  With
+    q = qpos[3:7], j = qpos[7:]:
+
+        d = conj(ref_quat) (x) q,   theta = 2 atan2(|d.xyz|, |d.w|)
+        quat_reward  = weights[0] * exp(-scales[0] * theta**2)
+        joint_reward = weights[1] * exp(-scales[1] * sum((j - ref_joints)**2))
+
+    theta is the rotation angle between the two orientations in [0, pi]: q and -q are the same rotation (|d.w|), the scale of either
+    quaternion cancels in the atan2, and near theta = 0 the angle comes from |d.xyz|, not from 1 - d.w**2.  Returns (quat_reward,
+    joint_reward), float64 [...]."""
+    qpos, r, rj = (np.asarray(a, dtype=np.float64) for a in (qpos, ref_quat, ref_joints))
+    q = qpos[..., 3:7]
+    rw, rx, ry, rz = (r[..., i] for i in range(4))
+    qw, qx, qy, qz = (q[..., i] for i in range(4))
+    dw = rw * qw + rx * qx + ry * qy + rz * qz
+    dx = rw * qx - rx * qw - ry * qz + rz * qy
+    dy = rw * qy + rx * qz - ry * qw - rz * qx
+    dz = rw * qz - rx * qy + ry * qx - rz * qw
+    theta = 2.0 * np.arctan2(np.sqrt(dx * dx + dy * dy + dz * dz), np.abs(dw))
+    e2 = ((qpos[..., 7:] - rj) ** 2).sum(-1)
+    return weights[0] * np.exp(-scales[0] * theta ** 2), weights[1] * np.exp(-scales[1] * e2)
+
+
+def _check_pose(track: np.ndarray, track_quat, track_joints, nq: int, weights_and_scales=()) -> Optional[np.ndarray]:
+    """The pose arguments of `Rodent` against its (checked) `track` [(C,) T, 3]: None when neither is given, else the rows the device
+    holds, float32 [(C,) T, nq - 3] = unit quaternion (normalised here, in float64) then joints.  ValueError for one without the other,
+    a shape other than track.shape[:-1] + (4,) / + (nq - 7,), a zero or non-finite quaternion, a non-finite joint angle, and a negative
+    or non-finite reward weight or scale."""
+    for x in weights_and_scales:
+        with np.errstate(over="ignore"):
+            x32 = np.float32(x)
+        if not (np.isfinite(x32) and x32 >= 0):
+            raise ValueError(f"pose reward weights and scales must be finite and >= 0 (as float32), got {x!r}")
+    if track_quat is None and track_joints is None:
+        return None
+    if track_quat is None or track_joints is None:
+        raise ValueError("track_quat and track_joints go together: pass both (pose tracking) or neither")
+    arr = lambda a: a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+    quat, joints = arr(track_quat).astype(np.float64), arr(track_joints).astype(np.float64)
+    lead = track.shape[:-1]
+    if quat.shape != lead + (4,) or joints.shape != lead + (nq - 7,):
+        raise ValueError(f"track_quat / track_joints must have shapes {lead + (4,)} / {lead + (nq - 7,)} next to a track_pos of shape "
+                         f"{track.shape} (the same clips and frames), got {quat.shape} / {joints.shape}")
+    norm = np.sqrt((quat * quat).sum(-1, keepdims=True))
+    if not np.isfinite(norm).all() or (norm == 0).any():
+        raise ValueError("track_quat holds a zero or non-finite quaternion")
+    if not np.isfinite(joints).all():
+        raise ValueError("track_joints holds a non-finite joint angle")
+    return np.ascontiguousarray(np.concatenate([quat / norm, joints], axis=-1), dtype=np.float32)
+
+
 class Rodent(PipelineEnv):
 
     def __init__(
@@ -88,6 +155,13 @@ class Rodent(PipelineEnv):
         xml_path: str = _XML_PATH,
         device=None,
         bad_state_max: Optional[float] = None,
+        track_quat=None,
+        track_joints=None,
+        quat_reward_weight: float = 1.0,
+        quat_reward_scale: float = 2.0,
+        joint_reward_weight: float = 1.0,
+        joint_reward_scale: float = 0.5,
+        reset_to_reference: bool = False,
         **kwargs,
     ):
         """`track_pos`: the reference positions to track, float [T, 3] -- one clip, followed by every env -- or [C, T, 3], C >= 1 clips of
@@ -100,7 +174,25 @@ class Rodent(PipelineEnv):
         +-inf included); that step then has done = 1 (whatever `terminate_when_unhealthy` is), reward 0 and metrics 0, and is counted
         (`bad_states()`).  Under `AutoResetWrapper` -- composed or in the one-launch rollouts -- the first state comes back as for any
         finished episode, with no bootstrap from the bad step.  The bare `step` does NOT sanitise: it returns the bad state and its
-        observation as they are, flagged by `done`; so does the raw evaluation form (`unroll_eval` without `episode_length`)."""
+        observation as they are, flagged by `done`; so does the raw evaluation form (`unroll_eval` without `episode_length`).
+
+        Pose tracking: `track_quat` [T, 4] (w, x, y, z) and `track_joints` [T, nq - 7] -- with a [C, T, 3] track_pos [C, T, 4] and
+        [C, T, nq - 7] -- are the clip's root orientation and joint angles (`preprocessing.ReferenceClip.quaternion` / `.joints`); both or
+        neither.  Quaternions are normalised here; a zero or non-finite one raises ValueError.  With them every env step (never a reset)
+        adds two terms to the reward, formed in the step kernel at the clip and frame the position reward reads (`pose_rewards` is their
+        float64 restatement):
+
+            quat_reward  = quat_reward_weight  * exp(-quat_reward_scale  * theta**2),  theta the angle between qpos[3:7] and the clip's
+            joint_reward = joint_reward_weight * exp(-joint_reward_scale * sum((qpos[7:] - joints)**2))
+            reward       = (reward without pose + quat_reward) + joint_reward
+
+        and `State.metrics` gains `quat_reward` and `joint_reward` (zeros at reset and after a bad step).  done, cur_frame, the
+        observation and the other metrics are what they are without pose; the observation does not carry the reference pose.  The four
+        defaults (1, 2, 1, 0.5) are UNTUNED choices, not values from a reference.  Served by the CG solver on the floor-contact models
+        in `step`, `unroll_wrapped` and `unroll_policy_wrapped`; a model or solver without a pose instance raises RuntimeError here with
+        the library's reason, `randomize` / `set_env_params` raise on a pose env, and `eval_supported()` is False (evaluation runs the
+        per-step loop).  `reset_to_reference=True` (pose envs only): reset starts from the clip's pose, qpos[3:] = reference[clip,
+        start_frame] + noise instead of qpos0[3:] + noise; the random draws are the same."""
         if bad_state_max is not None:
             with np.errstate(over="ignore", under="ignore"):
                 thr32 = np.float32(bad_state_max)        # what the kernel gets: 1e-50 would arrive as 0 (= off), 1e39 as inf
@@ -118,6 +210,9 @@ class Rodent(PipelineEnv):
                           "under random actions (non-finite states within a few env steps, on the CPU oracle too); use iterations >= 2",
                           RuntimeWarning, stacklevel=2)
         sys = System(assets.resolve_model(xml_path), iterations, ls_iterations, solver)
+        pose_np = _check_pose(track_np, track_quat, track_joints, sys.nq, (quat_reward_weight, quat_reward_scale, joint_reward_weight, joint_reward_scale))
+        if reset_to_reference and pose_np is None:
+            raise ValueError("reset_to_reference=True needs the reference pose: pass track_quat and track_joints")
         physics_steps_per_control_step = 10   # [REF Rodent_Env_Brax.py:53-57]
         kwargs["n_frames"] = kwargs.get("n_frames", physics_steps_per_control_step)
         kwargs["backend"] = "hip"
@@ -125,6 +220,15 @@ class Rodent(PipelineEnv):
         self._track_pos = torch.from_numpy(track_np).to(self.device).contiguous()
         self._track_host = track_np
         self._num_clips = track_np.shape[0] if track_np.ndim == 3 else None      # None: no clip axis (the single-clip path, no ids anywhere)
+        self._pose_host = pose_np                            # None: no pose tracking (the position-only reward, no pose members anywhere)
+        self._track_pose = None if pose_np is None else torch.from_numpy(pose_np).to(self.device).contiguous()
+        self._quat_reward = (float(quat_reward_weight), float(quat_reward_scale))
+        self._joint_reward = (float(joint_reward_weight), float(joint_reward_scale))
+        self._reset_to_reference = bool(reset_to_reference)
+        if pose_np is not None:
+            why = self._batch.pose_supported()
+            if why is not None:
+                raise RuntimeError(f"Rodent(track_quat=..., track_joints=...): {why}")
         self._forward_reward_weight = forward_reward_weight
         self._ctrl_cost_weight = ctrl_cost_weight
         self._healthy_reward = healthy_reward
@@ -139,7 +243,10 @@ class Rodent(PipelineEnv):
                           iterations=iterations, ls_iterations=ls_iterations, vision=vision, xml_path=xml_path,
                           n_frames=kwargs["n_frames"], pipeline_outputs=kwargs.get("pipeline_outputs", False),
                           contact_outputs=kwargs.get("contact_outputs", False), balance=kwargs.get("balance"),
-                          rebalance_every=kwargs.get("rebalance_every", 4), bad_state_max=bad_state_max)
+                          rebalance_every=kwargs.get("rebalance_every", 4), bad_state_max=bad_state_max,
+                          track_quat=track_quat, track_joints=track_joints, quat_reward_weight=quat_reward_weight,
+                          quat_reward_scale=quat_reward_scale, joint_reward_weight=joint_reward_weight,
+                          joint_reward_scale=joint_reward_scale, reset_to_reference=reset_to_reference)
 
     def with_num_envs(self, num_envs: int, device=None):
         """A sibling env with another batch size (ppo.train builds its per-rank and eval envs this way)."""
@@ -166,11 +273,29 @@ class Rodent(PipelineEnv):
         multi-step launch counts each of its steps.  Reads a device counter: synchronises the env's stream."""
         return self._batch.bad_states()
 
-    def _env_io(self, cur_frame, obs, reward=None, done=None, metrics=None, clip=None):
-        return dict(track_pos=self._track_pos, cur_frame=cur_frame, obs=obs, reward=reward, done=done, metrics=metrics, clip=clip,
-                    healthy_reward=self._healthy_reward, ctrl_cost_weight=self._ctrl_cost_weight,
-                    healthy_z_range=self._healthy_z_range, terminate_when_unhealthy=self._terminate_when_unhealthy,
-                    bad_state_max=self._bad_state_max)
+    @property
+    def pose_tracking(self) -> bool:
+        """Whether the reward has the two pose terms (`track_quat` / `track_joints` were given)."""
+        return self._pose_host is not None
+
+    def set_env_params(self, dof_f=None, act_f=None, con_f=None):
+        if self.pose_tracking and not (dof_f is None and act_f is None and con_f is None):
+            raise RuntimeError("pose tracking: no pose instance reads per-env parameters (randomize / set_env_params on a pose env)")
+        super().set_env_params(dof_f, act_f, con_f)
+
+    def randomize(self, randomization_fn):
+        if self.pose_tracking:
+            raise RuntimeError("pose tracking: no pose instance reads per-env parameters (randomize / set_env_params on a pose env)")
+        return super().randomize(randomization_fn)
+
+    def _env_io(self, cur_frame, obs, reward=None, done=None, metrics=None, clip=None, pose_metrics=None):
+        io = dict(track_pos=self._track_pos, cur_frame=cur_frame, obs=obs, reward=reward, done=done, metrics=metrics, clip=clip,
+                  healthy_reward=self._healthy_reward, ctrl_cost_weight=self._ctrl_cost_weight,
+                  healthy_z_range=self._healthy_z_range, terminate_when_unhealthy=self._terminate_when_unhealthy,
+                  bad_state_max=self._bad_state_max)
+        if pose_metrics is not None:         # a step of a pose env (a reset passes none: it has no reward)
+            io.update(track_pose=self._track_pose, pose_metrics=pose_metrics, quat_reward=self._quat_reward, joint_reward=self._joint_reward)
+        return io
 
     def reset(self, rng, clip=None) -> State:
         """Resets the environment to an initial state.  `rng`: uint32 keys [N, 2] (one jax-style
@@ -189,11 +314,8 @@ class Rodent(PipelineEnv):
         start_frame, qpos_noise, qvel, drawn = reset_draws(keys, s.nq, s.nv, self._reset_noise_scale, self._num_clips)
         if clip is None:
             clip = drawn
-        track = self._track_host                             # float32 [T, 3] or [C, T, 3], what the device holds
-        qpos = np.tile(np.asarray(s.qpos0, dtype=np.float32), (N, 1))
-        fi = np.clip(start_frame, 0, track.shape[-2] - 1)
-        qpos[:, :3] = track[fi] if clip is None else track[clip, fi]
-        qpos = qpos + qpos_noise
+        # float32 [T, 3] or [C, T, 3] (and the pose rows), what the device holds
+        qpos = reset_qpos(s.qpos0, self._track_host, start_frame, qpos_noise, clip, self._pose_host if self._reset_to_reference else None)
 
         st = dict(qpos=torch.from_numpy(qpos).to(dev), qvel=torch.from_numpy(qvel).to(dev),
                   act=torch.zeros(N, s.na, device=dev), qacc_warmstart=torch.zeros(N, s.nv, device=dev))
@@ -206,6 +328,8 @@ class Rodent(PipelineEnv):
         self._batch.env_reset(st, self._env_io(cur_frame, obs, clip=info.get("clip")), out)
         zero = torch.zeros(N, device=dev)
         metrics = {"pos_reward": zero, "reward_quadctrl": zero.clone(), "reward_alive": zero.clone()}
+        if self.pose_tracking:
+            metrics.update(quat_reward=zero.clone(), joint_reward=zero.clone())
         return State(PipelineState(**st, **out), obs, zero.clone(), zero.clone(), metrics, info)
 
     def _launch_buffers(self, state: State, episode_length: Optional[float] = None):
@@ -219,6 +343,8 @@ class Rodent(PipelineEnv):
         st = {k: torch.empty_like(v) for k, v in st_in.items()}
         io = dict(cur_frame=torch.empty_like(info["cur_frame"]), reward=torch.empty(N, device=dev), done=torch.empty(N, device=dev),
                   metrics=torch.empty(N, 3, device=dev), clip=info.get("clip"))      # clip: read only (None without a clip axis)
+        if self.pose_tracking:
+            io["pose_metrics"] = torch.empty(N, 2, device=dev)
         wrap = None
         if episode_length is not None:
             wrap = dict(first=fields(info["first_pipeline_state"]), first_obs=info["first_obs"], prev_done=state.done, steps_in=info["steps"],
@@ -233,6 +359,8 @@ class Rodent(PipelineEnv):
             info.update(steps=wrap["steps_out"], truncation=wrap["truncation_out"])
         m = dict(state.metrics)
         m.update(pos_reward=io["metrics"][:, 0], reward_quadctrl=io["metrics"][:, 1], reward_alive=io["metrics"][:, 2])
+        if self.pose_tracking:
+            m.update(quat_reward=io["pose_metrics"][:, 0], joint_reward=io["pose_metrics"][:, 1])
         return state.replace(pipeline_state=PipelineState(**st, **(out or {})), obs=obs, reward=io["reward"], done=io["done"], metrics=m, info=info)
 
     def unroll_wrapped(self, state: State, actions: torch.Tensor, episode_length: float) -> State:
@@ -268,8 +396,9 @@ class Rodent(PipelineEnv):
 
     def eval_supported(self) -> bool:
         """Whether `unroll_eval` serves this env: a batch with an evaluation instance (CG solver, a model with a multi-step instance, no
-        per-env parameters) and no pipeline / contact outputs."""
-        return (self.device.type == "cuda" and not self._pipeline_outputs and not self._contact_outputs and self._batch.eval_supported())
+        per-env parameters) and no pipeline / contact outputs.  False for a pose env: no evaluation instance rewards the pose, so
+        evaluation runs the per-step loop, whose `EvalWrapper` sums the two pose metrics like the others."""
+        return (not self.pose_tracking and self.device.type == "cuda" and not self._pipeline_outputs and not self._contact_outputs and self._batch.eval_supported())
 
     def unroll_eval(self, state: State, T: int, actor: dict, noise: Optional[torch.Tensor] = None, episode_length: Optional[float] = None,
                     eval_metrics: Optional[torch.Tensor] = None, actions_out: Optional[torch.Tensor] = None, qpos_out: Optional[torch.Tensor] = None) -> State:

@@ -48,6 +48,12 @@ class RREnvIOClips(C.Structure):
     _fields_ = RREnvIO._fields_ + [("clip", C.c_void_p), ("num_clips", C.c_int32)]
 
 
+class RRPoseIO(C.Structure):
+    """`rr_pose_io`, the pose-tracking block a batch carries (`rr_batch_set_pose`); all zero is the position-only reward."""
+    _fields_ = [("track_pose", C.c_void_p), ("pose_metrics", C.c_void_p), ("quat_reward_weight", C.c_float), ("quat_reward_scale", C.c_float),
+                ("joint_reward_weight", C.c_float), ("joint_reward_scale", C.c_float)]
+
+
 class RRUnrollIO(C.Structure):
     _fields_ = [("first", RRState), ("first_obs", C.c_void_p), ("prev_done", C.c_void_p), ("steps_in", C.c_void_p), ("steps_out", C.c_void_p),
                 ("truncation_out", C.c_void_p), ("episode_length", C.c_float)]
@@ -79,7 +85,7 @@ class RRPpoCfg(C.Structure):
 
 
 EXPORTS = ["rr_model_load", "rr_model_dims", "rr_model_set_solver", "rr_model_set_solver_type", "rr_model_destroy", "rr_model_table", "rr_kernarg_layout", "rr_batch_create",
-           "rr_batch_destroy", "rr_pipeline_init", "rr_pipeline_step", "rr_env_step", "rr_env_reset", "rr_pipeline_step_to", "rr_env_step_to", "rr_batch_contact_overflow", "rr_batch_bad_states", "rr_batch_unroll_supported", "rr_env_unroll", "rr_env_unroll_policy", "rr_batch_eval_supported", "rr_env_unroll_eval",
+           "rr_batch_destroy", "rr_pipeline_init", "rr_pipeline_step", "rr_env_step", "rr_env_reset", "rr_pipeline_step_to", "rr_env_step_to", "rr_batch_contact_overflow", "rr_batch_bad_states", "rr_batch_unroll_supported", "rr_env_unroll", "rr_env_unroll_policy", "rr_batch_eval_supported", "rr_env_unroll_eval", "rr_batch_pose_supported", "rr_batch_set_pose",
            "rr_compute_gae", "rr_mlp_forward", "rr_ppo_loss_workspace_bytes", "rr_ppo_loss", "rr_policy_act_workspace_bytes", "rr_policy_act", "rr_policy_sample", "rr_policy_backward_workspace_bytes", "rr_policy_backward", "rr_mlp_silu_backward_workspace_bytes", "rr_mlp_silu_backward", "rr_mlp_value_backward_workspace_bytes", "rr_mlp_policy_backward", "rr_mlp_policy_backward_workspace_bytes", "rr_mlp_value_backward", "rr_mlp_weight_grad_workspace_bytes", "rr_mlp_weight_grad", "rr_mlp_weight_grad_batch_workspace_bytes", "rr_mlp_weight_grad_batch", "rr_obs_moments_workspace_bytes", "rr_obs_moments", "rr_wrap_episode_autoreset", "rr_debug_layout", "rr_batch_set_schedule", "rr_batch_set_env_params", "rr_batch_env_params_supported", "rr_batch_set_profile", "rr_batch_set_ls_repeat_exit", "rr_batch_set_solver_trim", "rr_batch_set_solver_batch", "rr_batch_set_timing", "rr_batch_kernel_time", "rr_last_error"]
 
 _lib = None
@@ -165,6 +171,8 @@ def lib():
         L.rr_batch_set_schedule.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.rr_batch_set_env_params.argtypes = [C.c_void_p, C.POINTER(RREnvParams)]
         L.rr_batch_env_params_supported.argtypes = [C.c_void_p]
+        L.rr_batch_pose_supported.argtypes = [C.c_void_p]
+        L.rr_batch_set_pose.argtypes = [C.c_void_p, C.POINTER(RRPoseIO)]
         L.rr_batch_set_ls_repeat_exit.argtypes = [C.c_void_p, C.c_int32]
         L.rr_batch_set_solver_trim.argtypes = [C.c_void_p, C.c_int32]
         L.rr_batch_set_solver_batch.argtypes = [C.c_void_p, C.c_int32]
@@ -262,6 +270,7 @@ class Batch:
         self.N = int(num_envs)
         self.dims = model.dims
         self.h = C.c_void_p()
+        self._pose = None           # the tensors of the pose block in force (set_pose)
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream().cuda_stream
         _check(lib().rr_batch_create(model.h, self.N, self.device.index or 0, C.c_void_p(stream), C.byref(self.h)))
@@ -320,6 +329,14 @@ class Batch:
         e.healthy_z_min, e.healthy_z_max = env.get("healthy_z_range", (0.03, 0.5))
         e.terminate_when_unhealthy = int(env.get("terminate_when_unhealthy", True))
         e.bad_state_max = float(env.get("bad_state_max") or 0.0)      # 0 = no bad-state check
+        # pose tracking rides on the batch, not in rr_env_io: the env-io dict decides what the launch about to be issued sees
+        pose = env.get("track_pose")
+        if pose is not None:        # [T, nq - 3] rows (quaternion, joints), or [C, T, nq - 3] next to a [C, T, 3] track_pos
+            if tuple(pose.shape) != tuple(tp.shape[:-1]) + (d.nq - 3,):
+                raise ValueError(f"env io: track_pose has shape {tuple(pose.shape)}, expected {tuple(tp.shape[:-1]) + (d.nq - 3,)}")
+            self.set_pose(pose, env.get("pose_metrics"), env.get("quat_reward", (1.0, 2.0)), env.get("joint_reward", (1.0, 0.5)))
+        elif self._pose is not None:
+            self.set_pose(None)
         return e
 
     # ------------------------------------------------------------------ C-ABI calls
@@ -451,6 +468,25 @@ class Batch:
         The tensors must stay alive while the batch launches (C ABI `rr_batch_set_schedule`)."""
         self._sched = (env_map, cost)
         _check(lib().rr_batch_set_schedule(self.h, _ptr(env_map, torch.int32, self.N), _ptr(cost, torch.int32, self.N)))
+
+    def set_pose(self, track_pose: Optional[torch.Tensor], pose_metrics: Optional[torch.Tensor] = None, quat_reward=(1.0, 2.0), joint_reward=(1.0, 0.5)):
+        """The pose-tracking block of this batch's later env steps (C ABI `rr_batch_set_pose`): `track_pose` [(C,) T, nq - 3] rows of
+        quaternion then joints, `pose_metrics` [N, 2] out, `quat_reward` / `joint_reward` = (weight, scale); None clears it.  The env-io
+        dict of a launch (`track_pose`, `pose_metrics`, `quat_reward`, `joint_reward` keys) sets or clears it by itself.  The batch keeps
+        the tensors alive."""
+        if track_pose is None:
+            _check(lib().rr_batch_set_pose(self.h, None))
+            self._pose = None
+            return
+        p = RRPoseIO(_ptr(track_pose), _ptr(pose_metrics, numel=2 * self.N), *quat_reward, *joint_reward)
+        _check(lib().rr_batch_set_pose(self.h, C.byref(p)))
+        self._pose = (track_pose, pose_metrics)
+
+    def pose_supported(self) -> Optional[str]:
+        """None when this batch serves pose tracking (`set_pose`; C ABI `rr_batch_pose_supported`), else the refusal's text."""
+        if _check(lib().rr_batch_pose_supported(self.h)) == 1:
+            return None
+        return lib().rr_last_error().decode()
 
     def env_params_supported(self) -> bool:
         """Whether this batch's model / solver has kernel instances with per-env parameters (C ABI `rr_batch_env_params_supported`)."""

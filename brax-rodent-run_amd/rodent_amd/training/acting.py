@@ -206,7 +206,9 @@ class Evaluator:
         self._unroll_length = episode_length // action_repeat
 
     def one_launch(self) -> bool:
-        """Whether `run_evaluation` takes the one-launch path now (per-env parameters set on the env later turn it off)."""
+        """Whether `run_evaluation` takes the one-launch path now (per-env parameters set on the env later turn it off).  Never for a
+        pose env (`Rodent(track_quat=..., track_joints=...)`: no evaluation instance rewards the pose): the per-step loop below runs, and
+        its `EvalWrapper` sums `quat_reward` and `joint_reward` like every other metric (eval/episode_quat_reward, eval/episode_joint_reward)."""
         return (self._actor_fn is not None and self._action_repeat == 1 and os.environ.get("RR_FUSED_EVAL", "0") == "1"
                 and self._env.unroll_supported())
 

@@ -22,7 +22,7 @@ sys.path.insert(0, os.path.join(ROOT, "brax-rodent-run_amd"))
 import numpy as np
 import torch
 
-from rodent_amd import envs, jax_random, preprocessing, rollout
+from rodent_amd import assets, envs, jax_random, mjcf, preprocessing, rollout
 from rodent_amd.io import model
 from rodent_amd.training import acting, networks
 from rodent_amd.training.agents.ppo import train as ppo
@@ -58,6 +58,8 @@ def main():
     ap.add_argument("--randomize", action="store_true", help="domain randomisation: per-env friction and actuator gain (domain_randomize)")
     ap.add_argument("--bad-state-max", type=float, default=None, help="end and restore episodes whose qpos / qvel is non-finite or exceeds this "
                     "magnitude (MuJoCo's mjMAXVAL is 1e10); off by default")
+    ap.add_argument("--track-pose", action="store_true", help="reward the clip's root orientation and joint angles too (Rodent(track_quat=..., "
+                    "track_joints=...), untuned default weights); the synthetic line carries the identity quaternion and qpos0's joints.  Not with --randomize")
     ap.add_argument("--policy-width", type=int, choices=(32, 256), default=32, help="units per hidden layer of the policy network; both "
                     "widths run on the hand-written learner kernels (256: per-step rollouts, the in-kernel actor is 32-wide)")
     ap.add_argument("--policy-depth", type=int, default=4, help="hidden layers of the policy network (1 .. 7 for the hand-written kernels; "
@@ -76,8 +78,12 @@ def main():
         "batch_size": args.envs_per_gpu * n_gpus, "learning_rate": 5e-5, "terminate_when_unhealthy": True,
         "solver": "cg", "iterations": 8, "ls_iterations": 8, "vision": False,
     }
+    if args.track_pose and args.randomize:
+        ap.error("--track-pose: the step kernel's pose instances read no per-env parameters; drop --randomize")
+    clips = None                                     # the loaded ReferenceClip(s), [C, T, ...] fields; None for a .npy track or the synthetic line
     if args.clip and os.path.exists(args.clip) and not args.clip.endswith(".npy"):
-        position = np.asarray(preprocessing.load_reference_clip(args.clip, args.clip_name).position)         # reference_clip.position [REF :84], [C, T, 3]
+        clips = preprocessing.load_reference_clip(args.clip, args.clip_name)
+        position = np.asarray(clips.position)         # reference_clip.position [REF :84], [C, T, 3]
         track_pos = position[0] if len(args.clip_name) == 1 else position
     elif args.clip and os.path.exists(args.clip):
         track_pos = np.load(args.clip)
@@ -88,12 +94,22 @@ def main():
             heading = np.linspace(-np.pi / 4, np.pi / 4, args.synthetic_clips)
             track_pos = np.stack([np.stack([0.004 * t * np.cos(h), 0.004 * t * np.sin(h), np.full(250, 0.0681)], axis=1) for h in heading])
 
+    pose = {}
+    if args.track_pose:
+        if clips is not None:                        # the clip's own orientation and joint angles, the clip axis as track_pos has it
+            quat, joints = np.asarray(clips.quaternion), np.asarray(clips.joints)
+            pose = dict(track_quat=quat[0] if track_pos.ndim == 2 else quat, track_joints=joints[0] if track_pos.ndim == 2 else joints)
+        else:                                        # no pose in the file: upright, the model's rest joint angles
+            rest = np.asarray(mjcf.load_blob(assets.resolve_model(args.xml))["qpos0"], np.float64)[7:]
+            lead = track_pos.shape[:-1]
+            pose = dict(track_quat=np.broadcast_to([1.0, 0.0, 0.0, 0.0], lead + (4,)), track_joints=np.broadcast_to(rest, lead + rest.shape))
+
     envs.register_environment("rodent", envs.Rodent)
     env = envs.get_environment(
         config["env_name"], track_pos=track_pos, terminate_when_unhealthy=config["terminate_when_unhealthy"],
         solver=config["solver"], iterations=config["iterations"], ls_iterations=config["ls_iterations"],
         vision=config["vision"], num_envs=args.envs_per_gpu, xml_path=args.xml, device=f"cuda:{local_rank}",
-        bad_state_max=args.bad_state_max)
+        bad_state_max=args.bad_state_max, **pose)
 
     train_fn = functools.partial(
         ppo.train, num_timesteps=config["num_timesteps"], num_evals=int(config["num_timesteps"] / config["eval_every"]),
@@ -113,8 +129,11 @@ def main():
 
     eval_env = env.with_num_envs(1)                  # the launcher's un-vmapped jit_reset / jit_step pair [REF :93-94]
     track0 = track_pos if track_pos.ndim == 2 else track_pos[0]       # the evaluation rollout follows clip 0
-    ref_clip = preprocessing.ReferenceClip(position=track0, quaternion=np.tile([1.0, 0, 0, 0], (len(track0), 1)),
-                                           joints=np.zeros((len(track0), env.sys.nq - 7)))
+    if clips is not None:                            # the real clip: its own orientation and joints next to the rollout's
+        ref_clip = preprocessing.ReferenceClip(position=track0, quaternion=np.asarray(clips.quaternion)[0], joints=np.asarray(clips.joints)[0])
+    else:                                            # a bare track: dummies, only to pair the rollout with the positions
+        ref_clip = preprocessing.ReferenceClip(position=track0, quaternion=np.tile([1.0, 0, 0, 0], (len(track0), 1)),
+                                               joints=np.zeros((len(track0), env.sys.nq - 7)))
 
     def policy_params_fn(num_steps, make_policy, params, model_path=model_path):
         """Checkpoint + the 500-step evaluation rollout paired with the reference clip [REF brax_rodent_run_ppo.py:135-191];

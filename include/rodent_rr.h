@@ -247,6 +247,34 @@ int rr_env_unroll_eval(rr_batch* b, const rr_state* in, const rr_state* out_stat
  * and env->clip/num_clips where set (the observation holds track_pos[clip[e]][cur_frame + 1]). */
 int rr_env_reset(rr_batch* b, const rr_state* st, const rr_env_io* env, const rr_outputs* out);
 
+/* Pose tracking: the env step also rewards the clip's root orientation and joint angles.  The block is set on the BATCH (rr_env_io is
+ * closed: its layout ends with the clip members) and read by every later env step of it -- rr_env_step(_to), rr_env_unroll and
+ * rr_env_unroll_policy -- until it is replaced or cleared; a launch takes the pointers as they are when it is issued, so the caller may
+ * hand a fresh pose_metrics array before each launch.  NULL, or both pointers NULL: off, the position-only reward (a batch starts that way).
+ * track_pose is [T][nq - 3] -- with rr_env_io::clip set [num_clips][T][nq - 3] -- one row per frame: the clip's root quaternion
+ * (w, x, y, z; unit length) then its nq - 7 joint angles, with the launch's track_len / clip / num_clips, indexed like track_pos.  An env
+ * step (never a reset) reads the row of the clip and frame its position reward reads and, with q = qpos[3:7] and j = qpos[7:nq] of the
+ * stepped state, r_q and r_j the row's two parts:
+ *   d = conj(r_q) (x) q,   theta = 2 atan2(|d.xyz|, |d.w|)      (the sign and the scale of q do not matter)
+ *   quat_reward  = quat_reward_weight  * exp(-quat_reward_scale  * theta^2)
+ *   joint_reward = joint_reward_weight * exp(-joint_reward_scale * sum_i (j_i - r_j,i)^2)
+ *   reward = (reward without pose + quat_reward) + joint_reward       (float32, rounded in that order)
+ * pose_metrics[e] = (quat_reward, joint_reward); a bad step (bad_state_max) zeroes both.  done, cur_frame, obs and metrics are what they
+ * are without pose; in rr_env_unroll_policy traj_reward holds the new total.  rr_env_reset ignores the block.
+ * rr_batch_set_pose: one pointer without the other, or a negative or non-finite weight or scale: RR_EINVAL.  RR_EUNSUPPORTED with the
+ * reason where the batch has no pose instance -- there are some for the CG solver on the single-rodent floor-contact models (fixed-dimension
+ * or generic (2,2,1) slot counts) with shared tables: none for the Newton solver, models with candidate-pair contacts, two-tree models
+ * served by the two-wave pair instance and batches that carry per-env parameters (rr_batch_set_env_params refuses in turn while a pose
+ * block is set).  With a block set, rr_env_unroll_eval and launches with a debug dump, contact-geometry outputs or the profile build
+ * refuse (RR_EUNSUPPORTED).  rr_batch_pose_supported: 1 / 0, with 0 rr_last_error holds the reason. */
+typedef struct rr_pose_io {
+  const float* track_pose;
+  float* pose_metrics;    /* [N][2] out */
+  float quat_reward_weight, quat_reward_scale, joint_reward_weight, joint_reward_scale;
+} rr_pose_io;
+int rr_batch_set_pose(rr_batch* b, const rr_pose_io* pose);
+int rr_batch_pose_supported(const rr_batch* b);
+
 /* Generalised advantage estimation of one PPO minibatch, the reverse scan of brax.training.agents.ppo.losses.compute_gae
  * [UP; SURVEY.md Appendix E], one thread per trajectory.  All arrays time-major [T][B] device float32; bootstrap [B];
  * outputs vs [T][B] and advantages [T][B].  `stream` is a hipStream_t (NULL = default stream). */
