@@ -59,7 +59,7 @@ struct rr_model {
 // One function maps (model, launch form, variant) to the kernel instance that serves it, or to the reason there is none: launch(),
 // the support queries and the attribute loop of rr_batch_create all ask it, so none of them can disagree about what exists.
 enum Form { F_STEP, F_UNROLL, F_ACTOR, F_EVAL, N_FORMS };                        // single step | multi-step | ... with the actor | evaluation
-enum Variant { V_PROD, V_DEBUG, V_PROFILE, V_RAND, V_PAIR, V_POSE, N_VARIANTS }; // production | debug dump | cycle-stamp profile | per-env parameters | two-wave pair | pose tracking
+enum Variant { V_PROD, V_DEBUG, V_PROFILE, V_RAND, V_PAIR, V_POSE, V_MATLDS, N_VARIANTS }; // production | debug dump | cycle-stamp profile | per-env parameters | two-wave pair | pose tracking | production, inverse factor read from LDS
 struct Instance { kern_t kern; const char* why = nullptr; bool fixed = false; };      // why: the reason when kern is null (multi-step forms: with the entry point that reports it); fixed: compiled for the model's dimensions
 
 static Instance select(const rr_model* m, Form form, Variant v) {
@@ -68,9 +68,15 @@ static Instance select(const rr_model* m, Form form, Variant v) {
   const char *no_diag = "no diagnostic kernel instance for this model", *no_slots = "no kernel instance for this model's slot counts";
   auto no = [](const char* why) { return Instance{nullptr, why}; };
   // rr_step_kernel<NBS, NVS, NCS, PROF, DBG, dims, NEWTON, UNROLL, ACTOR, PAIR, DYN>, rr_rand_kernel<dims, UNROLL, ACTOR>, rr_eval_kernel<dims, DYN>,
-  // rr_pose_kernel<dims, UNROLL, ACTOR>
+  // rr_pose_kernel<dims, UNROLL, ACTOR>, rr_matlds_kernel<dims>
   if (v == V_PAIR && (unroll || newton || !RRDimsRodentNew::matches(m->kd_rep))) return no("no two-wave pair instance for this model / launch form");
   if (v == V_PAIR) return {rr_step_kernel<2, 2, 1, false, false, RRDimsRodentNew, false, false, false, true>, nullptr, true};      // one replica = the rodent_new dims
+  if (v == V_MATLDS) {      // rr_batch_set_solve_resident(b, 0): the production single-step instance of the benchmark model's dimensions, solves from LDS
+    if (newton || m->dyn || m->pair_ok || !s221 || !RRDimsRodent::matches(m->kd))
+      return no("rr_batch_set_solve_resident: only the fixed-dimension CG instance of the rodent_optimized dimensions has a form that solves from LDS");
+    if (unroll) return no("rr_batch_set_solve_resident(b, 0): the instance that solves from LDS is single-step; no multi-step, actor or evaluation launch on this batch");
+    return {rr_matlds_kernel<RRDimsRodent>, nullptr, true};
+  }
   // Eligibility first.  Multi-step instances: the single-rodent floor-contact models (fixed-dimension or generic) and the candidate-pair models
   // (DYN, generic dimensions), CG only, no diagnostics.  None for the Newton solver, the two-wave pair instance and other slot counts.
   if (unroll && (v == V_DEBUG || v == V_PROFILE)) return no("rr_env_unroll: no diagnostic outputs in a multi-step rollout");
@@ -360,6 +366,7 @@ struct rr_batch {
   int dbg_flags = 0;                    // debug-dump launches, RRIO::dbg_flags: RR_DBG_LS_RUN_REPEATS (rr_batch_set_ls_repeat_exit(b, 0)), RR_DBG_SOLVER_UNTRIMMED (rr_batch_set_solver_trim(b, 0)), RR_DBG_SOLVER_UNBATCHED (rr_batch_set_solver_batch(b, 0))
   float* eval_actions = nullptr;        // [N][nu]: where an evaluation launch without actions_out keeps the current action (rr_env_unroll_eval)
   rr_pose_io pose = {};                 // pose tracking of the env steps (rr_batch_set_pose); track_pose null: off
+  bool solve_lds = false;               // rr_batch_set_solve_resident(b, 0): production single-step launches run rr_matlds_kernel
   bool has_env_params() const { return env_dof_f || env_act_f || env_con_f; }
 };
 
@@ -642,6 +649,10 @@ static int launch(rr_batch* b, const Launch& L) {
   // two-tree model, physics only, no diagnostics: one wavefront per replica (rr_kernel.h PAIR)
   const bool pair = m->pair_ok && v == V_PROD && !L.env && !L.out && !L.un && !b->env_map && !b->cost && m->solver != 2;
   if (pair) v = V_PAIR;
+  if (b->solve_lds) {      // rr_batch_set_solve_resident(b, 0): production launches only, and select() refuses the multi-step forms
+    if (v != V_PROD) return fail(RR_EUNSUPPORTED, "launch: rr_batch_set_solve_resident(b, 0) serves production launches only (no debug dump, contact-geometry outputs, profile build, per-env parameters or pose tracking on this batch)");
+    v = V_MATLDS;
+  }
   const Instance in = select(m, L.ev ? F_EVAL : (L.ac ? F_ACTOR : (L.un ? F_UNROLL : F_STEP)), v);
   if (!in.kern) return fail(RR_EUNSUPPORTED, std::string(L.un ? "" : "launch: ") + in.why);
   if (L.un && (rc = fill_unroll(b, L, io))) return rc;
@@ -1370,6 +1381,21 @@ extern "C" int rr_batch_set_solver_trim(rr_batch* b, int32_t enable) {
 extern "C" int rr_batch_set_solver_batch(rr_batch* b, int32_t enable) {
   if (!b) return fail(RR_EINVAL, "rr_batch_set_solver_batch: null batch");
   b->dbg_flags = enable ? (b->dbg_flags & ~RR_DBG_SOLVER_UNBATCHED) : (b->dbg_flags | RR_DBG_SOLVER_UNBATCHED);
+  return RR_OK;
+}
+
+extern "C" int rr_model_solve_resident_switch(const rr_model* m) {
+  if (!m) return fail(RR_EINVAL, "rr_model_solve_resident_switch: null model");
+  const Instance in = select(m, F_STEP, V_MATLDS);
+  return in.kern ? RR_OK : fail(RR_EUNSUPPORTED, in.why);
+}
+extern "C" int rr_batch_set_solve_resident(rr_batch* b, int32_t enable) {
+  if (!b) return fail(RR_EINVAL, "rr_batch_set_solve_resident: null batch");
+  if (!enable) {
+    const int rc = rr_model_solve_resident_switch(b->m);
+    if (rc) return rc;
+  }
+  b->solve_lds = enable == 0;
   return RR_OK;
 }
 

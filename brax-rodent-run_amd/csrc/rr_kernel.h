@@ -50,6 +50,9 @@
 #ifndef RR_JOBS_RESIDENT
 #define RR_JOBS_RESIDENT 1    // the solve-job descriptors are loaded once per substep and held in registers (Wave::jobs_res; bit-identical results)
 #endif
+#ifndef RR_SOLVE_MAT_RESIDENT
+#define RR_SOLVE_MAT_RESIDENT 1   // the M-half inverse-factor entries of this lane's solve jobs are read once per substep and held in registers (Wave::mres_c / mres_r; bit-identical results)
+#endif
 #ifndef RR_LS_STAGE_ONCE
 #define RR_LS_STAGE_ONCE 1    // the line search's compacted row positions and its D values are staged once per substep (Wave::ls_stage; bit-identical results)
 #endif
@@ -502,7 +505,9 @@ template <class A> struct rr_same<A, A> { static constexpr bool value = true; };
 // actor inside (UNROLL + ACTOR); everything DYN-specific is re-derived per substep, so the multi-step loop carries nothing extra for it.
 // JRES: this instance may hold the solve-job descriptors in registers for the substep (RR_JOBS_RESIDENT; not the debug-dump instances, whose
 // dump paths leave no room for them)
-template <int NBS, int NVS, int NCS, class DT, bool NEWTON = false, bool PAIR = false, bool DYN = false, bool RAND = false, bool JRES = true>
+// MRES: how much of the inverse factor this instance may hold in registers next to them (RR_SOLVE_MAT_RESIDENT; Wave::MAT_RES): 0 nothing,
+// 1 the entries of its column jobs, 2 those of its column and row jobs.  Chosen per entry point by its register figures.
+template <int NBS, int NVS, int NCS, class DT, bool NEWTON = false, bool PAIR = false, bool DYN = false, bool RAND = false, bool JRES = true, int MRES = 0>
 struct Wave {
   const DT& D;
   RRLoopTables TL;
@@ -1237,7 +1242,7 @@ struct Wave {
   // (padding: vector cell nv, which always holds 0) and walks the matrix row from byte offset ra.
   struct Jobs { int cw[NJS][8], ci0[NJS], rb[NJS][4], ra[NJS], own[NVS]; };
   __device__ __forceinline__ void load_jobs(Jobs& j) { load_jobs(j, TL.coljob, TL.rowjob, TL.jobown); }
-  template <class P>
+  template <class P, bool CW = true>
   __device__ __forceinline__ void load_jobs(Jobs& j, P coljob, P rowjob, P jobown) {
     constexpr int WJ = NJS * RR_LANES;
     const int ol = opaque(lane);
@@ -1245,7 +1250,7 @@ struct Wave {
 #pragma unroll
     for (int s = 0; s < NJS; ++s) {
 #pragma unroll
-      for (int k = 0; k < 8; ++k) j.cw[s][k] = 2 * k < D.lmax ? cj[k * WJ + s * RR_LANES] : 0;
+      for (int k = 0; k < 8; ++k) if (CW) j.cw[s][k] = 2 * k < D.lmax ? cj[k * WJ + s * RR_LANES] : 0;
       j.ci0[s] = cj[8 * WJ + s * RR_LANES];
 #pragma unroll
       for (int k = 0; k < 4; ++k) j.rb[s][k] = 4 * k < D.lmax ? rj[k * WJ + s * RR_LANES] : 0;
@@ -1263,9 +1268,25 @@ struct Wave {
   // scalar registers through the launch for the per-call reloads.  The debug-dump instances (JRES false) keep the reload: with their
   // dump paths the resident copy does not fit their registers.
   static constexpr bool JOBS_RES = RR_JOBS_RESIDENT != 0 && JRES;
+  static constexpr bool MAT_RES = RR_SOLVE_MAT_RESIDENT != 0 && MRES > 0 && !NEWTON && !PAIR && JOBS_RES && !rr_same<DT, RRDims>::value;      // see below
+  static constexpr bool CW_RES = !MAT_RES;      // the column jobs' matrix offsets stay resident only where the solver still reads them
   Jobs jobs_res;
   __device__ __forceinline__ void load_jobs_resident() {
-    if constexpr (JOBS_RES) { const RRTables T = load_tables(); load_jobs(jobs_res, T.coljob, T.rowjob, T.jobown); }
+    if constexpr (JOBS_RES) { const RRTables T = load_tables(); load_jobs<rr_gi, CW_RES>(jobs_res, T.coljob, T.rowjob, T.jobown); }
+  }
+  // !CW_RES (see MAT_RES below): the column jobs' matrix offsets are not held; the three calls that still gather through them (mul_m, the
+  // loader of the resident entries, the damped solve of euler()) load them into the same members first, and they are dead in between.
+  __device__ __forceinline__ void load_cw() {
+    if constexpr (JOBS_RES && !CW_RES) {
+      constexpr int WJ = NJS * RR_LANES;
+      const RRTables T = load_tables();
+      const rr_row<int> cj = row_at(T.coljob, 1, opaque(lane));
+#pragma unroll
+      for (int s = 0; s < NJS; ++s) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) jobs_res.cw[s][k] = 2 * k < D.lmax ? cj[k * WJ + s * RR_LANES] : 0;
+      }
+    }
   }
   // The resident copy as values the optimiser has not seen before (in place: no instruction, no register).  Without this it takes the
   // unpacked offsets and ids of one call for those of the next, keeps them all alive across the solver and runs out of registers.
@@ -1275,7 +1296,7 @@ struct Wave {
 #pragma unroll
     for (int s = 0; s < NJS; ++s) {
 #pragma unroll
-      for (int k = 0; k < 8; ++k) if (ALL || 2 * k < D.lmax) asm volatile("" : "+v"(jobs_res.cw[s][k]));
+      for (int k = 0; k < 8; ++k) if (CW_RES && (ALL || 2 * k < D.lmax)) asm volatile("" : "+v"(jobs_res.cw[s][k]));
       asm volatile("" : "+v"(jobs_res.ci0[s]));
 #pragma unroll
       for (int k = 0; k < 4; ++k) if (ALL || 4 * k < D.lmax) asm volatile("" : "+v"(jobs_res.rb[s][k]));
@@ -1283,6 +1304,68 @@ struct Wave {
     }
 #pragma unroll
     for (int s = 0; s < NVS; ++s) asm volatile("" : "+v"(jobs_res.own[s]));
+  }
+  // RR_SOLVE_MAT_RESIDENT: the inverse factor W stands still from invert() to the next substep's mass_matrix(), and about nine of the
+  // substep's solves are with its M half (qacc_smooth, one per CG iteration).  Each of them gathered this lane's lmax entries per job
+  // and side from LDS again -- the costliest reads of the solve by bank conflicts (every M-half entry lies on an even dword: 16 banks),
+  // the column side with two instructions of offset arithmetic per entry on top.  The substep reads them once, after invert()
+  // (load_mat_resident: the addresses of col_piece / row_piece), and ldl_solve_on<false> multiplies from registers, in the same order
+  // from the same 0.0f.  A padded column step holds the ZERO cell's 0.0f, a padded row step whatever finite entry follows the row
+  // (its vector cell is the zero at nv), as in LDS: the loops stay predicate-free.  The damped solve of euler(), mul_m (on M, before
+  // the factorisation) and every Newton / PAIR / debug / run-time-dimension instance keep the gathers.  MRES picks the sides by the
+  // instance's registers: +12 values per side and job slot, and the solver no longer reads the column jobs' matrix offsets, so they
+  // leave the resident descriptors (CW_RES, load_cw: -12).  Timed instance: 217 -> 253 VGPRs with both sides, 229 with the column side.
+  static constexpr bool MAT_RES_ROW = MAT_RES && MRES > 1;
+  static constexpr int MRL = 12;      // == D.lmax of the fixed-dimension instances
+  float mres_c[NJS][MRL], mres_r[NJS][MRL];
+  __device__ __forceinline__ void load_mat_resident() {
+    if constexpr (MAT_RES) {
+      static_assert(DT::lmax == MRL, "resident matrix entries: one register per step of a job");
+      sync();     // the inversion's last rows were written by other lanes
+      jobs_fresh();
+      load_cw();
+#pragma unroll
+      for (int s = 0; s < NJS; ++s) {
+#pragma unroll
+        for (int t = 0; t < MRL; ++t) mres_c[s][t] = *(const float*)((const char*)s_qLD + ((jobs_res.cw[s][t >> 1] >> (16 * (t & 1))) & 0xFFFF));
+        if constexpr (MAT_RES_ROW) {
+          const float* m_ = (const float*)((const char*)s_qLD + jobs_res.ra[s]);
+#pragma unroll
+          for (int t = 0; t < MRL; ++t) mres_r[s][t] = m_[2 * t];
+        }
+      }
+    }
+  }
+  // The resident entries as values the optimiser has not seen before, like jobs_fresh(): nothing derived from them outlives a call.
+  __device__ __forceinline__ void mat_fresh() {
+#pragma unroll
+    for (int s = 0; s < NJS; ++s) {
+#pragma unroll
+      for (int t = 0; t < MRL; ++t) {
+        asm volatile("" : "+v"(mres_c[s][t]));
+        if constexpr (MAT_RES_ROW) asm volatile("" : "+v"(mres_r[s][t]));
+      }
+    }
+  }
+  __device__ __forceinline__ float col_piece_res(int s, const float* vec) const {
+    const float* v = vec + jobs_res.ci0[s];
+    float vv[MRL], acc = 0.0f;      // every read ahead of the first multiply-add: see row_piece_res
+#pragma unroll
+    for (int t = 0; t < MRL; ++t) vv[t] = v[t];
+#pragma unroll
+    for (int t = 0; t < MRL; ++t) acc += mres_c[s][t] * vv[t];
+    return acc;
+  }
+  __device__ __forceinline__ float row_piece_res(int s, const float* vec) const {
+    // With the resident values live the solver runs close to the register cap, and there the instruction scheduler leaves a region as
+    // it found it.  Written as read, multiply-add, read ... the products came out in that order, one exposed LDS round trip per pair of
+    // entries (measured: +1.8 % launch time against the gathers), so the source has the vector reads first.
+    float vv[MRL], acc = 0.0f;
+#pragma unroll
+    for (int t = 0; t < MRL; ++t) vv[t] = vec[(jobs_res.rb[s][t >> 2] >> (8 * (t & 3))) & 255];
+#pragma unroll
+    for (int t = 0; t < MRL; ++t) acc += mres_r[s][t] * vv[t];
+    return acc;
   }
   // column piece: sum_t mat[cw_t] * vec[i0 + t];  row piece: sum_t mat[ra + t] * vec[rb_t]   (mat = one half of the pair array)
   __device__ __forceinline__ float col_piece(const Jobs& j, int s, const float* mat, const float* vec) const {
@@ -1319,11 +1402,15 @@ struct Wave {
     if constexpr (!JOBS_RES) load_jobs(jl);
     else jobs_fresh();
     const Jobs& jb = JOBS_RES ? jobs_res : jl;
+    // the undamped solves of a MAT_RES instance are all with W's M half in s_qLD (its Newton instances, which solve with s_H, have none)
+    constexpr bool RES = MAT_RES && !DAMPED;
+    if constexpr (RES) mat_fresh();
+    else load_cw();
 #pragma unroll
     for (int s = 0; s < NVS; ++s) { const int d = lane + RR_LANES * s; if (d < D.nv) s_x[d] = x[s]; }
     sync();
 #pragma unroll
-    for (int s = 0; s < NJS; ++s) s_buf[s * RR_LANES + lane] = col_piece(jb, s, mat, s_x);
+    for (int s = 0; s < NJS; ++s) s_buf[s * RR_LANES + lane] = RES ? col_piece_res(s, s_x) : col_piece(jb, s, mat, s_x);
     sync();
     float y[NVS];
 #pragma unroll
@@ -1335,7 +1422,7 @@ struct Wave {
     for (int s = 0; s < NVS; ++s) { const int d = lane + RR_LANES * s; if (d < D.nv) s_x[d] = y[s]; }
     sync();
 #pragma unroll
-    for (int s = 0; s < NJS; ++s) s_buf[s * RR_LANES + lane] = row_piece(jb, s, mat, s_x);
+    for (int s = 0; s < NJS; ++s) s_buf[s * RR_LANES + lane] = (RES && MAT_RES_ROW) ? row_piece_res(s, s_x) : row_piece(jb, s, mat, s_x);
     sync();
 #pragma unroll
     for (int s = 0; s < NVS; ++s) {
@@ -1353,6 +1440,7 @@ struct Wave {
     Jobs jl;
     if constexpr (!JOBS_RES) load_jobs(jl);
     else jobs_fresh();
+    load_cw();
     const Jobs& jb = JOBS_RES ? jobs_res : jl;
 #pragma unroll
     for (int s = 0; s < NJS; ++s) {
@@ -2617,6 +2705,7 @@ template <int NBS, int NVS, int NCS, bool PROF, bool DBG, class DT, bool NEWTON 
 __global__ __launch_bounds__((PAIR ? 2 : 1) * RR_LANES, (NVS >= 3 ? 1 : 2)) void rr_step_kernel(const RRDims Dk, const RRTables Tk, const RRIO io_kernarg, const int num_envs,
                                                            const int n_frames) {
   constexpr bool RAND = false, EVAL = false, POSE = false;
+  constexpr int MRES = ACTOR ? 1 : 2;      // resident inverse-factor entries (Wave::MAT_RES): both sides at 245-253 registers (timed: -1.4 % against the column side alone); with the actor the column side (233)
 #include "rr_step_body.inc"
 }
 // Per-environment parameters: the same argument list (load_io / load_tables / load_dims find the block at the same offsets), production
@@ -2625,6 +2714,7 @@ template <class DT, bool UNROLL = false, bool ACTOR = false>
 __global__ __launch_bounds__(RR_LANES, 2) void rr_rand_kernel(const RRDims Dk, const RRTables Tk, const RRIO io_kernarg, const int num_envs, const int n_frames) {
   constexpr int NBS = 2, NVS = 2, NCS = 1;
   constexpr bool PROF = false, DBG = false, NEWTON = false, PAIR = false, DYN = false, RAND = true, EVAL = false, POSE = false;
+  constexpr int MRES = 1;      // resident inverse-factor entries (Wave::MAT_RES): the column side (229-237 registers; both sides reach the cap of 256 here)
 #include "rr_step_body.inc"
 }
 // Evaluation (rr_env_unroll_eval): the multi-step form with the actor inside as brax's Evaluator and the launcher's evaluation rollout
@@ -2636,6 +2726,7 @@ template <class DT, bool DYN = false>
 __global__ __launch_bounds__(RR_LANES, 2) void rr_eval_kernel(const RRDims Dk, const RRTables Tk, const RRIO io_kernarg, const int num_envs, const int n_frames) {
   constexpr int NBS = 2, NVS = 2, NCS = 1;
   constexpr bool PROF = false, DBG = false, NEWTON = false, PAIR = false, RAND = false, UNROLL = true, ACTOR = true, EVAL = true, POSE = false;
+  constexpr int MRES = 1;      // resident inverse-factor entries (Wave::MAT_RES): the column side (229-237 registers; both sides reach the cap of 256 here)
 #include "rr_step_body.inc"
 }
 // Pose tracking (rr_batch_set_pose, rr_pose_io): the env epilogue also rewards the clip's root orientation and joint angles (RRIO, POSE TRACKING).
@@ -2646,5 +2737,15 @@ template <class DT, bool UNROLL = false, bool ACTOR = false>
 __global__ __launch_bounds__(RR_LANES, 2) void rr_pose_kernel(const RRDims Dk, const RRTables Tk, const RRIO io_kernarg, const int num_envs, const int n_frames) {
   constexpr int NBS = 2, NVS = 2, NCS = 1;
   constexpr bool PROF = false, DBG = false, NEWTON = false, PAIR = false, DYN = false, RAND = false, EVAL = false, POSE = true;
+  constexpr int MRES = 1;      // resident inverse-factor entries (Wave::MAT_RES): the column side (229-237 registers; both sides reach the cap of 256 here)
+#include "rr_step_body.inc"
+}
+// The production single-step instance with the inverse factor's entries left in LDS (MRES 0), whatever RR_SOLVE_MAT_RESIDENT says: the other
+// arm of an exact A/B inside one library (rr_batch_set_solve_resident(b, 0); tests/test_gpu_solve_resident.py).  An entry of its own so
+// that the instances of the other four keep their code.
+template <class DT>
+__global__ __launch_bounds__(RR_LANES, 2) void rr_matlds_kernel(const RRDims Dk, const RRTables Tk, const RRIO io_kernarg, const int num_envs, const int n_frames) {
+  constexpr int NBS = 2, NVS = 2, NCS = 1, MRES = 0;
+  constexpr bool PROF = false, DBG = false, NEWTON = false, UNROLL = false, ACTOR = false, PAIR = false, DYN = false, RAND = false, EVAL = false, POSE = false;
 #include "rr_step_body.inc"
 }

@@ -1,6 +1,6 @@
 // rr_step_body.inc -- the body of the step kernel, included by each of its __global__ entries in rr_kernel.h (rr_step_kernel,
-// rr_rand_kernel, rr_eval_kernel, rr_pose_kernel).  In scope where it is included: the kernel's five arguments (Dk, Tk, io_kernarg, num_envs, n_frames) and the
-// compile-time switches NBS, NVS, NCS, PROF, DBG, DT, NEWTON, UNROLL, ACTOR, PAIR, DYN, RAND, EVAL, POSE.
+// rr_rand_kernel, rr_eval_kernel, rr_pose_kernel, rr_matlds_kernel).  In scope where it is included: the kernel's five arguments (Dk, Tk, io_kernarg, num_envs, n_frames) and the
+// compile-time switches NBS, NVS, NCS, PROF, DBG, DT, NEWTON, UNROLL, ACTOR, PAIR, DYN, RAND, EVAL, POSE, MRES.
 // Why text and not a function: see the note above rr_step_kernel.
   static_assert(!PAIR || (!PROF && !DBG && !NEWTON && !UNROLL && !ACTOR), "PAIR: production physics instance only");
   static_assert(!DYN || (!PROF && !DBG && !NEWTON && !PAIR), "DYN: production instances only (single-step, multi-step, multi-step with the actor)");
@@ -14,7 +14,7 @@
   // LDS -- checked on the HOST for every instance a batch may launch (rr_batch_create: hipFuncGetAttributes().sharedSizeBytes == 0)
   const DT D(Dk);
   const int wrep = PAIR ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0;
-  Wave<NBS, NVS, NCS, DT, NEWTON, PAIR, DYN, RAND, !DBG> w(D, Tk, PAIR ? lds + wrep * (D.lds_bytes_rep >> 2) : lds);
+  Wave<NBS, NVS, NCS, DT, NEWTON, PAIR, DYN, RAND, !DBG, MRES> w(D, Tk, PAIR ? lds + wrep * (D.lds_bytes_rep >> 2) : lds);
   int lane = threadIdx.x & (RR_LANES - 1);
   if (PAIR) { w.rep = wrep; w.s_xc = lds + 2 * (D.lds_bytes_rep >> 2); }
   RRIO io = load_io();
@@ -231,6 +231,7 @@
     if (dg) for (int e = lane; e < D.nM; e += RR_LANES) dg[D.g_qLD + e] = w.s_qLD[2 * e];
     w.invert();
     w.env_prio();
+    w.load_mat_resident();      // this lane's entries of the inverse factor's M half: read by every undamped solve of the substep
     w.template stamp<PROF>(5);
 #pragma unroll
     for (int s = 0; s < NVS; ++s) w.qacc_smooth[s] = w.qfrc_smooth[s];

@@ -490,6 +490,18 @@ int rr_batch_set_solver_trim(rr_batch* b, int32_t enable);
  * second path to switch.) */
 int rr_batch_set_solver_batch(rr_batch* b, int32_t enable);
 
+/* A/B switch of the production code, for tests: the fixed-dimension instances hold this lane's entries of the inverse factor's M half in
+ * registers from the inversion to the end of the substep, and the undamped M^-1 solves multiply from there (rr_kernel.h
+ * RR_SOLVE_MAT_RESIDENT).  enable = 0 makes the batch's production single-step launches (rr_pipeline_step, rr_env_step and their _to forms)
+ * run the same instance built with the entries left in LDS, so that a test can compare the two bit for bit.  Only for models of the
+ * rodent_optimized dimensions with the CG solver (RR_EUNSUPPORTED otherwise); while it is off, multi-step, actor and evaluation launches
+ * and every launch that needs another instance (debug dump, contact geometry, profile, per-env parameters, pose tracking) are refused.
+ * Default 1. */
+int rr_batch_set_solve_resident(rr_batch* b, int32_t enable);
+/* RR_OK where rr_batch_set_solve_resident(b, 0) would be accepted on a batch of this model, else its error code with its words in
+ * rr_last_error (needs no device). */
+int rr_model_solve_resident_switch(const rr_model* m);
+
 /* ms of the most recent step-kernel launches on this batch measured with hipEvents on its stream
  * (enable with rr_batch_set_timing(b,1); each launch is then bracketed by events) */
 int rr_batch_set_timing(rr_batch* b, int32_t enable);
