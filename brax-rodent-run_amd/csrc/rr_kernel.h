@@ -268,6 +268,17 @@ struct RRIO {
   const float* track_pose;
   float* pose_metrics;         // [N][2]
   float pose_quat_w, pose_quat_k, pose_joint_w, pose_joint_k;
+  // REFERENCE OBSERVATION (REFOBS instances, rr_refobs_kernel; no other instance reads it): the observation row carries the clip's next
+  // ref_frames = H >= 1 frames behind today's obs_dim entries, [ obs (obs_dim) | block_1 | ... | block_H ], row width obs_dim + H nq --
+  // the stride of obs, t_obs, a_obs_in and first_obs in those instances (rr_obs_width).  block_h = (p_h[3], q_h[4], j_h[nq - 7]) at frame
+  // f_h = clamp(new_frame + h, 0, track_len - 1) of the env's clip, new_frame the frame the track entry of the observation counts from:
+  //   p_h = xmat[1] @ (track_pos[f_h] - qpos[:3])            (p_1 IS the track entry, bit for bit)
+  //   q_h = s (conj(x) (x) r_q[f_h]), x = xquat[1], s = -1 where the w component is negative (q and -q are one rotation)
+  //   j_h = r_j[f_h] - qpos[7:]
+  // with r_q, r_j the parts of track_pose's row.  Written where the observation is written: at reset and after every env step.
+  // Fetched by a narrow load where it is used (load_io_member), never through load_io().
+  int ref_frames;
+  int ref_pad;                 // keeps sizeof(RRIO) a multiple of 8 (RRKArgs)
 };
 
 // ------------------------------------------------------------------------------------------ small math
@@ -2526,7 +2537,8 @@ static_assert(offsetof(RRKArgs, T) == rr_align_up(sizeof(RRDims), alignof(RRTabl
 static_assert(offsetof(RRKArgs, io) == rr_align_up(offsetof(RRKArgs, T) + sizeof(RRTables), alignof(RRIO)), "RRIO follows RRTables at its natural alignment");
 static_assert(offsetof(RRKArgs, num_envs) == offsetof(RRKArgs, io) + sizeof(RRIO) && sizeof(RRIO) % 8 == 0, "scalars follow RRIO without padding");
 static_assert(offsetof(RRIO, clip) % 8 == 0 && offsetof(RRIO, clip) + sizeof(const int*) == offsetof(RRIO, track_pose), "the pose members follow the clip ids without padding");
-static_assert(offsetof(RRIO, pose_joint_k) + sizeof(float) == sizeof(RRIO), "the pose members close RRIO without padding");
+static_assert(offsetof(RRIO, pose_joint_k) + sizeof(float) == offsetof(RRIO, ref_frames), "the reference-observation members follow the pose members without padding");
+static_assert(offsetof(RRIO, ref_pad) + sizeof(int) == sizeof(RRIO), "the reference-observation members close RRIO without padding");
 // ... and so are the model tables outside the solver's loops: RRTables is re-read at the head of each phase that indexes a table
 // (narrow scalar loads next to an existing hand-off; the unused members' loads are dead), so no table pointer is held across the
 // substep.  The loops' own tables are the exception (RRLoopTables, taken once from the parameter).
@@ -2570,6 +2582,14 @@ static __device__ __forceinline__ T load_io_member(size_t member_offset) {
 #endif
 }
 
+// Width of an observation row = the stride of obs, t_obs, a_obs_in and first_obs.  REFOBS instances (rr_refobs_kernel): the model's obs_dim
+// plus RRIO::ref_frames blocks of nq entries, the count read where the width is used; every other instance: D.obs_dim itself.
+template <bool REFOBS, class DT>
+static __device__ __forceinline__ int rr_obs_width(const DT& D) {
+  if constexpr (REFOBS) return D.obs_dim + load_io_member<int>(offsetof(RRIO, ref_frames)) * D.nq;
+  else return D.obs_dim;
+}
+
 // RAND instances: the tables with the three randomisable ones advanced to environment `env`'s rows.  `env` is wave-uniform, the
 // pointers come from the argument block, so the address arithmetic is scalar (a 64-bit multiply-add per table).
 static __device__ __forceinline__ RRTables load_env_tables(int env, int nv, int nu, int ncon) {
@@ -2603,10 +2623,14 @@ static __device__ __forceinline__ size_t rr_traj_obs(const RRIO& io, int N, int 
 static __device__ __forceinline__ size_t rr_traj_at(const RRIO& io, int N, int env, int s) { const RRTraj r = rr_traj(io, s); return ((size_t)r.u * N + env) * io.a_seg + r.t; }
 // EVAL (rr_eval_kernel): the observation comes from the env's two-row ring, a null noise pointer is the deterministic policy (raw = loc,
 // formed as loc + scale * 0 so that it equals the sampled form under all-zero noise bit for bit), and nothing but the action is recorded.
-template <bool EVAL = false, class DT>
+// JM: observation entries per lane, so the row is at most 64 JM wide (host check, actor_limit): RR_ACTOR_JM = 20 (1280) everywhere but in
+// the REFOBS instances, whose row is rr_obs_width wide and which read RR_ACTOR_JM_REFOBS = 26 per lane (1664: up to five reference
+// frames on the shipped floor-contact models, 1279 + 5 x 74 = 1649 and 1263 + 5 x 74 = 1633).
+#define RR_ACTOR_JM 20
+#define RR_ACTOR_JM_REFOBS 26
+template <bool EVAL = false, int JM = RR_ACTOR_JM, bool REFOBS = false, class DT>
 __device__ __forceinline__ void rr_actor_step(const RRIO& io, const DT& D, int lane, int env, int ut, int num_envs) {
-  constexpr int JM = 20;                      // observation entries per lane (host check: obs_dim <= 1280)
-  const int K = D.obs_dim, A = D.nu;
+  const int K = rr_obs_width<REFOBS>(D), A = D.nu;
   const float* ob;
   if constexpr (EVAL) ob = io.t_obs + ((size_t)env * 2 + (ut & 1)) * K;
   else { const RRTraj tr = rr_traj(io, ut); ob = io.t_obs + rr_traj_obs(io, num_envs, env, tr.u, tr.t) * K; }
@@ -2704,7 +2728,7 @@ __device__ __forceinline__ void rr_actor_step(const RRIO& io, const DT& D, int l
 template <int NBS, int NVS, int NCS, bool PROF, bool DBG, class DT, bool NEWTON = false, bool UNROLL = false, bool ACTOR = false, bool PAIR = false, bool DYN = false>
 __global__ __launch_bounds__((PAIR ? 2 : 1) * RR_LANES, (NVS >= 3 ? 1 : 2)) void rr_step_kernel(const RRDims Dk, const RRTables Tk, const RRIO io_kernarg, const int num_envs,
                                                            const int n_frames) {
-  constexpr bool RAND = false, EVAL = false, POSE = false;
+  constexpr bool RAND = false, EVAL = false, POSE = false, REFOBS = false;
   constexpr int MRES = ACTOR ? 1 : 2;      // resident inverse-factor entries (Wave::MAT_RES): both sides at 245-253 registers (timed: -1.4 % against the column side alone); with the actor the column side (233)
 #include "rr_step_body.inc"
 }
@@ -2713,7 +2737,7 @@ __global__ __launch_bounds__((PAIR ? 2 : 1) * RR_LANES, (NVS >= 3 ? 1 : 2)) void
 template <class DT, bool UNROLL = false, bool ACTOR = false>
 __global__ __launch_bounds__(RR_LANES, 2) void rr_rand_kernel(const RRDims Dk, const RRTables Tk, const RRIO io_kernarg, const int num_envs, const int n_frames) {
   constexpr int NBS = 2, NVS = 2, NCS = 1;
-  constexpr bool PROF = false, DBG = false, NEWTON = false, PAIR = false, DYN = false, RAND = true, EVAL = false, POSE = false;
+  constexpr bool PROF = false, DBG = false, NEWTON = false, PAIR = false, DYN = false, RAND = true, EVAL = false, POSE = false, REFOBS = false;
   constexpr int MRES = 1;      // resident inverse-factor entries (Wave::MAT_RES): the column side (229-237 registers; both sides reach the cap of 256 here)
 #include "rr_step_body.inc"
 }
@@ -2725,7 +2749,7 @@ __global__ __launch_bounds__(RR_LANES, 2) void rr_rand_kernel(const RRDims Dk, c
 template <class DT, bool DYN = false>
 __global__ __launch_bounds__(RR_LANES, 2) void rr_eval_kernel(const RRDims Dk, const RRTables Tk, const RRIO io_kernarg, const int num_envs, const int n_frames) {
   constexpr int NBS = 2, NVS = 2, NCS = 1;
-  constexpr bool PROF = false, DBG = false, NEWTON = false, PAIR = false, RAND = false, UNROLL = true, ACTOR = true, EVAL = true, POSE = false;
+  constexpr bool PROF = false, DBG = false, NEWTON = false, PAIR = false, RAND = false, UNROLL = true, ACTOR = true, EVAL = true, POSE = false, REFOBS = false;
   constexpr int MRES = 1;      // resident inverse-factor entries (Wave::MAT_RES): the column side (229-237 registers; both sides reach the cap of 256 here)
 #include "rr_step_body.inc"
 }
@@ -2736,16 +2760,27 @@ __global__ __launch_bounds__(RR_LANES, 2) void rr_eval_kernel(const RRDims Dk, c
 template <class DT, bool UNROLL = false, bool ACTOR = false>
 __global__ __launch_bounds__(RR_LANES, 2) void rr_pose_kernel(const RRDims Dk, const RRTables Tk, const RRIO io_kernarg, const int num_envs, const int n_frames) {
   constexpr int NBS = 2, NVS = 2, NCS = 1;
-  constexpr bool PROF = false, DBG = false, NEWTON = false, PAIR = false, DYN = false, RAND = false, EVAL = false, POSE = true;
+  constexpr bool PROF = false, DBG = false, NEWTON = false, PAIR = false, DYN = false, RAND = false, EVAL = false, POSE = true, REFOBS = false;
   constexpr int MRES = 1;      // resident inverse-factor entries (Wave::MAT_RES): the column side (229-237 registers; both sides reach the cap of 256 here)
+#include "rr_step_body.inc"
+}
+// Reference observation (rr_batch_set_reference_obs): the pose instances with the clip's next frames appended to every observation row
+// (RRIO, REFERENCE OBSERVATION), served to env steps AND resets of a batch that carries frames.  A fifth entry for the reason the three
+// above are entries of their own: the instances of the others keep their code, every `if (REFOBS)` in the body folds away there and
+// rr_obs_width is D.obs_dim.  The same nine forms as rr_pose_kernel; the actor inside reads RR_ACTOR_JM_REFOBS entries per lane.
+template <class DT, bool UNROLL = false, bool ACTOR = false>
+__global__ __launch_bounds__(RR_LANES, 2) void rr_refobs_kernel(const RRDims Dk, const RRTables Tk, const RRIO io_kernarg, const int num_envs, const int n_frames) {
+  constexpr int NBS = 2, NVS = 2, NCS = 1;
+  constexpr bool PROF = false, DBG = false, NEWTON = false, PAIR = false, DYN = false, RAND = false, EVAL = false, POSE = true, REFOBS = true;
+  constexpr int MRES = 1;      // resident inverse-factor entries (Wave::MAT_RES): the column side, as in rr_pose_kernel
 #include "rr_step_body.inc"
 }
 // The production single-step instance with the inverse factor's entries left in LDS (MRES 0), whatever RR_SOLVE_MAT_RESIDENT says: the other
 // arm of an exact A/B inside one library (rr_batch_set_solve_resident(b, 0); tests/test_gpu_solve_resident.py).  An entry of its own so
-// that the instances of the other four keep their code.
+// that the instances of the other five keep their code.
 template <class DT>
 __global__ __launch_bounds__(RR_LANES, 2) void rr_matlds_kernel(const RRDims Dk, const RRTables Tk, const RRIO io_kernarg, const int num_envs, const int n_frames) {
   constexpr int NBS = 2, NVS = 2, NCS = 1, MRES = 0;
-  constexpr bool PROF = false, DBG = false, NEWTON = false, UNROLL = false, ACTOR = false, PAIR = false, DYN = false, RAND = false, EVAL = false, POSE = false;
+  constexpr bool PROF = false, DBG = false, NEWTON = false, UNROLL = false, ACTOR = false, PAIR = false, DYN = false, RAND = false, EVAL = false, POSE = false, REFOBS = false;
 #include "rr_step_body.inc"
 }

@@ -1,11 +1,12 @@
 // rr_step_body.inc -- the body of the step kernel, included by each of its __global__ entries in rr_kernel.h (rr_step_kernel,
-// rr_rand_kernel, rr_eval_kernel, rr_pose_kernel, rr_matlds_kernel).  In scope where it is included: the kernel's five arguments (Dk, Tk, io_kernarg, num_envs, n_frames) and the
-// compile-time switches NBS, NVS, NCS, PROF, DBG, DT, NEWTON, UNROLL, ACTOR, PAIR, DYN, RAND, EVAL, POSE, MRES.
+// rr_rand_kernel, rr_eval_kernel, rr_pose_kernel, rr_refobs_kernel, rr_matlds_kernel).  In scope where it is included: the kernel's five arguments (Dk, Tk, io_kernarg, num_envs, n_frames) and the
+// compile-time switches NBS, NVS, NCS, PROF, DBG, DT, NEWTON, UNROLL, ACTOR, PAIR, DYN, RAND, EVAL, POSE, REFOBS, MRES.
 // Why text and not a function: see the note above rr_step_kernel.
   static_assert(!PAIR || (!PROF && !DBG && !NEWTON && !UNROLL && !ACTOR), "PAIR: production physics instance only");
   static_assert(!DYN || (!PROF && !DBG && !NEWTON && !PAIR), "DYN: production instances only (single-step, multi-step, multi-step with the actor)");
   static_assert(!ACTOR || UNROLL, "the actor lives in the multi-step instances");
   static_assert(!POSE || (!RAND && !EVAL && !PROF && !DBG && !NEWTON && !PAIR && !DYN), "POSE: production CG instances of the floor-contact models only");
+  static_assert(!REFOBS || POSE, "REFOBS: a form of the pose instances (the blocks are rows of track_pose)");
   static_assert(!EVAL || (ACTOR && !RAND && !PROF && !DBG && !NEWTON && !PAIR), "EVAL: a form of the production multi-step instance with the actor");
   extern __shared__ __attribute__((aligned(16))) float lds[];
   int env = blockIdx.x;
@@ -56,7 +57,8 @@
   const size_t ctrl_at = UNROLL ? ((size_t)((EVAL && !(io.a_pad & RR_EVAL_ACTIONS)) ? 0 : ut) * num_envs + env) * D.nu : (size_t)senv * D.nu;
   if (ACTOR) {
     if (ut == 0) {       // the observation the rollout starts from is row 0 of the env's trajectory (EVAL: of its two-row ring)
-      for (int i = lane; i < D.obs_dim; i += RR_LANES) io.t_obs[(EVAL ? (size_t)env * 2 : rr_traj_obs(io, num_envs, env, 0, 0)) * D.obs_dim + i] = io.a_obs_in[(size_t)env * D.obs_dim + i];
+      const int ow = rr_obs_width<REFOBS>(D);      // row stride (REFOBS: with the reference blocks)
+      for (int i = lane; i < ow; i += RR_LANES) io.t_obs[(EVAL ? (size_t)env * 2 : rr_traj_obs(io, num_envs, env, 0, 0)) * ow + i] = io.a_obs_in[(size_t)env * ow + i];
       if (EVAL && io.e_qpos_out) for (int i = lane; i < D.nq; i += RR_LANES) io.e_qpos_out[(size_t)env * D.nq + i] = io.qpos_in[(size_t)env * D.nq + i];
     }
     // ORDERING through global memory inside one wave: the observation row the actor reads was written by OTHER lanes of this wave (the
@@ -64,7 +66,7 @@
     // vector memory operations complete in order, but the compiler must not move them across each other either: a wavefront-scope fence on
     // both sides states the dependency (guarded by tests/test_gpu_ppo.py::test_one_launch_unroll_with_the_actor_inside, bitwise).
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    rr_actor_step<EVAL>(io, D, lane, env, ut, num_envs);
+    rr_actor_step<EVAL, REFOBS ? RR_ACTOR_JM_REFOBS : RR_ACTOR_JM, REFOBS>(io, D, lane, env, ut, num_envs);
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
   }
   // ---- load state (a multi-step rollout keeps it in LDS after its first step)
@@ -181,7 +183,8 @@
       if (io.o_cinert) for (int e = lane; e < 10 * D.nbody; e += RR_LANES) io.o_cinert[(size_t)env * 10 * D.nbody + e] = w.s_cinert[e];
       if (io.o_cvel) for (int e = lane; e < 6 * D.nbody; e += RR_LANES) io.o_cvel[(size_t)env * 6 * D.nbody + e] = w.s_cvel[e];
       if (io.obs) {
-        float* ob = (EVAL ? io.t_obs + ((size_t)env * 2 + ((ut + 1) & 1)) * D.obs_dim : ACTOR ? io.t_obs + rr_traj_obs(io, num_envs, env, rr_traj(io, ut).u, rr_traj(io, ut).t + 1) * D.obs_dim : io.obs + (size_t)env * D.obs_dim) + D.nq + D.nv;
+        const int ow = rr_obs_width<REFOBS>(D);
+        float* ob = (EVAL ? io.t_obs + ((size_t)env * 2 + ((ut + 1) & 1)) * ow : ACTOR ? io.t_obs + rr_traj_obs(io, num_envs, env, rr_traj(io, ut).u, rr_traj(io, ut).t + 1) * ow : io.obs + (size_t)env * ow) + D.nq + D.nv;
         for (int i = lane; i < 10 * (D.nbody - 1); i += RR_LANES) ob[i] = w.s_cinert[10 + i];
         ob += 10 * (D.nbody - 1);
         for (int i = lane; i < 6 * (D.nbody - 1); i += RR_LANES) ob[i] = w.s_cvel[6 + i];
@@ -339,7 +342,8 @@
       c = c < 0 ? 0 : (c > io.num_clips - 1 ? io.num_clips - 1 : c);
       track += (size_t)3 * (size_t)io.track_len * (size_t)c;
     }
-    float* ob = EVAL ? io.t_obs + ((size_t)env * 2 + ((ut + 1) & 1)) * D.obs_dim : ACTOR ? io.t_obs + rr_traj_obs(io, num_envs, env, rr_traj(io, ut).u, rr_traj(io, ut).t + 1) * D.obs_dim : io.obs + (size_t)env * D.obs_dim;
+    const int ow = rr_obs_width<REFOBS>(D);      // row stride of obs / t_obs / first_obs (REFOBS: with the reference blocks)
+    float* ob = EVAL ? io.t_obs + ((size_t)env * 2 + ((ut + 1) & 1)) * ow : ACTOR ? io.t_obs + rr_traj_obs(io, num_envs, env, rr_traj(io, ut).u, rr_traj(io, ut).t + 1) * ow : io.obs + (size_t)env * ow;
     int o = 0;
     for (int i = lane; i < D.nq; i += RR_LANES) ob[o + i] = w.s_qpos[i];
     o += D.nq;
@@ -361,6 +365,59 @@
       // row `lane` of xmat[1] by selects (indexing a register array by the lane id would put it into scratch memory)
       const float r0 = m1[0] * v.x + m1[1] * v.y + m1[2] * v.z, r1 = m1[3] * v.x + m1[4] * v.y + m1[5] * v.z, r2 = m1[6] * v.x + m1[7] * v.y + m1[8] * v.z;
       ob[o + lane] = lane == 0 ? r0 : (lane == 1 ? r1 : r2);
+    }
+    // ---- REFERENCE OBSERVATION (REFOBS instances, RRIO::ref_frames = H): H blocks of nq entries behind the obs_dim entries above, block h
+    // = (p_h[3], q_h[4], j_h[nq - 7]) from the clip's frame f_h = clamp(new_frame + h) -- at reset and after every step alike, a bad step
+    // included.  The lanes write the joint part coalesced (one subtraction each); lanes 0 .. 6 form p_h and q_h and pick their entry by
+    // selects.  p_h is the track entry's expression at frame f_h.  p_1 is not formed again: lanes 0 .. 2 read back the track entry they
+    // have just stored, so the two are the same bits whatever the optimiser contracts.  q_h stands under contraction OFF (see POSE
+    // TRACKING below): every product and sum rounded on its own.  Clip and frame are clamped before the row offset is formed, so no row
+    // lies outside track_pose; H and the table come by narrow loads here and nothing of this lives across the solver.
+    // ISOLATION: the block shares no value with the track entry above -- lane id, row pointer and quaternion pass through opaque copies.
+    // Sharing them (one rotation matrix for both, the track entry kept in a register) gave the products of the track entry further uses,
+    // and the backend then contracted it differently from every other instance: one ulp in obs[obs_dim - 3 ..], measured against the
+    // pose instances.  Apart, the track entry above compiles from the tokens and the uses it has everywhere else.
+    if (REFOBS) {
+      const int H = load_io_member<int>(offsetof(RRIO, ref_frames));
+      const float* tpose = load_io_member<const float*>(offsetof(RRIO, track_pose));
+      if (tpose) {
+        const int rl = opaque(lane);
+        float* rob = ob;
+        asm volatile("" : "+s"(rob) : : "memory");
+        int rc = 0;
+        if (io.clip) { rc = io.clip[env]; rc = rc < 0 ? 0 : (rc > io.num_clips - 1 ? io.num_clips - 1 : rc); }
+        float xo[4], m1[9];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { xo[k] = xq1[k]; asm volatile("" : "+v"(xo[k])); }
+        quat_to_mat(m1, xo);
+        const float p1 = rl < 3 ? rob[D.obs_dim - 3 + rl] : 0.0f;      // the track entry this lane stored above (same thread: program order)
+        for (int h = 1; h <= H; ++h) {
+          int fh = new_frame + h;
+          fh = fh < 0 ? 0 : (fh > io.track_len - 1 ? io.track_len - 1 : fh);
+          const float* rrow = tpose + ((size_t)rc * (size_t)io.track_len + (size_t)fh) * (size_t)(D.nq - 3);
+          float* blk = rob + D.obs_dim + (h - 1) * D.nq;
+          for (int i = rl; i < D.nq - 7; i += RR_LANES) blk[7 + i] = rrow[4 + i] - w.s_qpos[7 + i];
+          if (rl < 7) {
+            const v3 v = ld3(track + 3 * fh) - ld3(w.s_qpos);
+            const float r0 = m1[0] * v.x + m1[1] * v.y + m1[2] * v.z, r1 = m1[3] * v.x + m1[4] * v.y + m1[5] * v.z, r2 = m1[6] * v.x + m1[7] * v.y + m1[8] * v.z;
+            float qw, qx, qy, qz;
+            {
+#pragma clang fp contract(off)
+              const float xw = xo[0], xx = xo[1], xy = xo[2], xz = xo[3];
+              const float rw = rrow[0], rx = rrow[1], ry = rrow[2], rz = rrow[3];
+              const float dw = ((xw * rw + xx * rx) + xy * ry) + xz * rz;
+              const float d1 = ((xw * rx - xx * rw) - xy * rz) + xz * ry;
+              const float d2 = ((xw * ry + xx * rz) - xy * rw) - xz * rx;
+              const float d3 = ((xw * rz - xx * ry) + xy * rx) - xz * rw;
+              const float sg = dw < 0.0f ? -1.0f : 1.0f;
+              qw = sg * dw; qx = sg * d1; qy = sg * d2; qz = sg * d3;
+            }
+            const float p = h == 1 ? p1 : (rl == 0 ? r0 : (rl == 1 ? r1 : r2));
+            const float q = rl == 3 ? qw : (rl == 4 ? qx : (rl == 5 ? qy : qz));
+            blk[rl] = rl < 3 ? p : q;
+          }
+        }
+      }
     }
     if (!is_reset) {
       float a2 = 0.0f;
@@ -475,14 +532,14 @@
         for (int i = lane; i < D.nq; i += RR_LANES) w.s_qpos[i] = io.first_qpos[(size_t)env * D.nq + i];
         for (int i = lane; i < D.nv; i += RR_LANES) { w.s_qvel[i] = io.first_qvel[(size_t)env * D.nv + i]; w.s_warm[i] = io.first_warm[(size_t)env * D.nv + i]; }
         for (int i = lane; i < D.nu; i += RR_LANES) w.s_act[i] = io.first_act[(size_t)env * D.nu + i];
-        for (int i = lane; i < D.obs_dim; i += RR_LANES) ob[i] = io.first_obs[(size_t)env * D.obs_dim + i];
+        for (int i = lane; i < ow; i += RR_LANES) ob[i] = io.first_obs[(size_t)env * ow + i];
         w.sync();
       }
       if (ACTOR && !EVAL) {      // the last observation of a segment is also the first of the next one (the learner's trajectories overlap by one row)
         const RRTraj tr = rr_traj(io, ut);
         if (tr.t + 1 == io.a_seg && ut + 1 < nsteps) {
-          float* nx = io.t_obs + rr_traj_obs(io, num_envs, env, tr.u + 1, 0) * D.obs_dim;
-          for (int i = lane; i < D.obs_dim; i += RR_LANES) nx[i] = ob[i];
+          float* nx = io.t_obs + rr_traj_obs(io, num_envs, env, tr.u + 1, 0) * ow;
+          for (int i = lane; i < ow; i += RR_LANES) nx[i] = ob[i];
         }
       }
       if (io.progress && ut + 1 < nsteps) {

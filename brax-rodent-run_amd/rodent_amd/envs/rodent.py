@@ -136,6 +136,63 @@ def _check_pose(track: np.ndarray, track_quat, track_joints, nq: int, weights_an
     return np.ascontiguousarray(np.concatenate([quat / norm, joints], axis=-1), dtype=np.float32)
 
 
+def _quat_to_mat(q: np.ndarray) -> np.ndarray:
+    """Rotation matrix [..., 3, 3] of a quaternion (w, x, y, z) [..., 4], MuJoCo's mju_quat2Mat, float64."""
+    w, x, y, z = (q[..., i] for i in range(4))
+    return np.stack([np.stack([w * w + x * x - y * y - z * z, 2 * (x * y - w * z), 2 * (x * z + w * y)], -1),
+                     np.stack([2 * (x * y + w * z), w * w - x * x + y * y - z * z, 2 * (y * z - w * x)], -1),
+                     np.stack([2 * (x * z - w * y), 2 * (y * z + w * x), w * w - x * x - y * y + z * z], -1)], -2)
+
+
+def reference_obs(qpos, track_pos, track_quat, track_joints, frame, frames: int, clip=None, xquat=None, xmat=None) -> np.ndarray:
+    """The reference blocks the step kernel appends to the observation (`Rodent(reference_obs_frames=H)`; C ABI
+    `rr_batch_set_reference_obs`) restated in numpy float64: [..., frames * nq], block h = 1 .. frames = (p_h[3], q_h[4], j_h[nq - 7]).
+
+    `qpos` [N, nq] the state the observation is formed from; `track_pos` [T, 3], `track_quat` [T, 4] (w, x, y, z), `track_joints`
+    [T, nq - 7] -- with `clip` (int ids [N], clamped into [0, C)) [C, T, ...]; `frame` int [N]: the frame the observation's track entry
+    counts from (the stepped `cur_frame` after a step, the start frame at reset).  With f_h = clamp(frame + h, 0, T - 1), x the world
+    quaternion of body 1 and r_q, r_j the clip's row at f_h:
+
+        p_h = xmat[1] @ (track_pos[f_h] - qpos[:3])
+        q_h = s * (conj(x) (x) r_q),   s = -1 where that product's w is negative, else +1
+        j_h = r_j - qpos[7:]
+
+    Body 1 is the root body of the free joint, so x = qpos[3:7] and xmat[1] is its matrix; `xquat` [N, 4] / `xmat` [N, 3, 3] override
+    them (e.g. with the values of a forward pass).  r_q and -r_q give the same block; frames past the clip's end repeat its last row."""
+    qpos = np.asarray(qpos, dtype=np.float64)
+    tp, tq, tj = (np.asarray(a, dtype=np.float64) for a in (track_pos, track_quat, track_joints))
+    N, nq = qpos.shape
+    frame = np.broadcast_to(np.asarray(frame, dtype=np.int64), (N,))
+    if clip is not None:
+        c = np.clip(np.broadcast_to(np.asarray(clip, dtype=np.int64), (N,)), 0, tp.shape[0] - 1)
+    T = tp.shape[-2]
+    x = qpos[:, 3:7] if xquat is None else np.asarray(xquat, dtype=np.float64)
+    R = _quat_to_mat(x) if xmat is None else np.asarray(xmat, dtype=np.float64)
+    xw, xx, xy, xz = (x[:, i] for i in range(4))
+    out = np.empty((N, int(frames), nq))
+    for h in range(1, int(frames) + 1):
+        f = np.clip(frame + h, 0, T - 1)
+        row = (lambda a: a[f]) if clip is None else (lambda a: a[c, f])
+        out[:, h - 1, :3] = np.einsum("nij,nj->ni", R, row(tp) - qpos[:, :3])
+        rw, rx, ry, rz = (row(tq)[:, i] for i in range(4))
+        d = np.stack([xw * rw + xx * rx + xy * ry + xz * rz, xw * rx - xx * rw - xy * rz + xz * ry,
+                      xw * ry + xx * rz - xy * rw - xz * rx, xw * rz - xx * ry + xy * rx - xz * rw], -1)
+        out[:, h - 1, 3:7] = np.where(d[:, :1] < 0, -d, d)
+        out[:, h - 1, 7:] = row(tj) - qpos[:, 7:]
+    return out.reshape(N, int(frames) * nq)
+
+
+def _check_reference_frames(frames, have_pose: bool) -> int:
+    """`reference_obs_frames` of `Rodent` as an int in [0, 16]; ValueError for anything else, and for frames without the pose arguments."""
+    if isinstance(frames, (bool, np.bool_)) or not isinstance(frames, (int, np.integer)):
+        raise ValueError(f"reference_obs_frames must be an int in [0, 16], got {frames!r}")
+    if not 0 <= int(frames) <= 16:
+        raise ValueError(f"reference_obs_frames must lie in [0, 16], got {frames!r}")
+    if int(frames) > 0 and not have_pose:
+        raise ValueError("reference_obs_frames > 0 needs the reference pose: pass track_quat and track_joints")
+    return int(frames)
+
+
 class Rodent(PipelineEnv):
 
     def __init__(
@@ -162,6 +219,7 @@ class Rodent(PipelineEnv):
         joint_reward_weight: float = 1.0,
         joint_reward_scale: float = 0.5,
         reset_to_reference: bool = False,
+        reference_obs_frames: int = 0,
         **kwargs,
     ):
         """`track_pos`: the reference positions to track, float [T, 3] -- one clip, followed by every env -- or [C, T, 3], C >= 1 clips of
@@ -187,12 +245,22 @@ class Rodent(PipelineEnv):
             reward       = (reward without pose + quat_reward) + joint_reward
 
         and `State.metrics` gains `quat_reward` and `joint_reward` (zeros at reset and after a bad step).  done, cur_frame, the
-        observation and the other metrics are what they are without pose; the observation does not carry the reference pose.  The four
+        observation and the other metrics are what they are without pose (`reference_obs_frames` below adds the reference pose to the
+        observation).  The four
         defaults (1, 2, 1, 0.5) are UNTUNED choices, not values from a reference.  Served by the CG solver on the floor-contact models
         in `step`, `unroll_wrapped` and `unroll_policy_wrapped`; a model or solver without a pose instance raises RuntimeError here with
         the library's reason, `randomize` / `set_env_params` raise on a pose env, and `eval_supported()` is False (evaluation runs the
         per-step loop).  `reset_to_reference=True` (pose envs only): reset starts from the clip's pose, qpos[3:] = reference[clip,
-        start_frame] + noise instead of qpos0[3:] + noise; the random draws are the same."""
+        start_frame] + noise instead of qpos0[3:] + noise; the random draws are the same.
+
+        `reference_obs_frames` = H (pose envs only, an int in [0, 16]; 0, the default, is the observation above in every bit): the
+        observation carries what the pose reward scores.  Every row -- at reset and after every step, in `step`, `unroll_wrapped` and
+        `unroll_policy_wrapped` -- becomes [the observation above | block_1 | ... | block_H], `observation_size` = obs_dim + H * nq, with
+        block_h = (p_h[3], q_h[4], j_h[nq - 7]) read at frame clamp(cur_frame + h) of the env's clip: the next track positions in the root
+        frame (p_1 is the observation's own last three entries), the reference orientations relative to the root's with w >= 0, and the
+        reference joint angles minus the current ones (`reference_obs` restates them in float64).  AutoReset restores the stored first
+        observation at the full width.  The one-launch rollout with the actor inside serves rows up to 1664 wide (H <= 5 on the shipped
+        floor-contact models); above that `ppo.train` collects per step."""
         if bad_state_max is not None:
             with np.errstate(over="ignore", under="ignore"):
                 thr32 = np.float32(bad_state_max)        # what the kernel gets: 1e-50 would arrive as 0 (= off), 1e39 as inf
@@ -211,6 +279,7 @@ class Rodent(PipelineEnv):
                           RuntimeWarning, stacklevel=2)
         sys = System(assets.resolve_model(xml_path), iterations, ls_iterations, solver)
         pose_np = _check_pose(track_np, track_quat, track_joints, sys.nq, (quat_reward_weight, quat_reward_scale, joint_reward_weight, joint_reward_scale))
+        ref_frames = _check_reference_frames(reference_obs_frames, pose_np is not None)
         if reset_to_reference and pose_np is None:
             raise ValueError("reset_to_reference=True needs the reference pose: pass track_quat and track_joints")
         physics_steps_per_control_step = 10   # [REF Rodent_Env_Brax.py:53-57]
@@ -229,6 +298,16 @@ class Rodent(PipelineEnv):
             why = self._batch.pose_supported()
             if why is not None:
                 raise RuntimeError(f"Rodent(track_quat=..., track_joints=...): {why}")
+        self._ref_frames = ref_frames
+        if ref_frames:
+            # the batch carries the count; its rows come from the pose block, which therefore stands from here on (every launch of this
+            # env, resets included, hands the block: a reset writes no pose metrics and gets a buffer nobody reads)
+            why = self._batch.reference_obs_supported(ref_frames)
+            if why is not None:
+                raise RuntimeError(f"Rodent(reference_obs_frames={ref_frames}): {why}")
+            self._reset_pose_metrics = torch.zeros(num_envs, 2, device=self.device)
+            self._batch.set_pose(self._track_pose, self._reset_pose_metrics, self._quat_reward, self._joint_reward)
+            self._batch.set_reference_obs(ref_frames)
         self._forward_reward_weight = forward_reward_weight
         self._ctrl_cost_weight = ctrl_cost_weight
         self._healthy_reward = healthy_reward
@@ -246,7 +325,8 @@ class Rodent(PipelineEnv):
                           rebalance_every=kwargs.get("rebalance_every", 4), bad_state_max=bad_state_max,
                           track_quat=track_quat, track_joints=track_joints, quat_reward_weight=quat_reward_weight,
                           quat_reward_scale=quat_reward_scale, joint_reward_weight=joint_reward_weight,
-                          joint_reward_scale=joint_reward_scale, reset_to_reference=reset_to_reference)
+                          joint_reward_scale=joint_reward_scale, reset_to_reference=reset_to_reference,
+                          reference_obs_frames=reference_obs_frames)
 
     def with_num_envs(self, num_envs: int, device=None):
         """A sibling env with another batch size (ppo.train builds its per-rank and eval envs this way)."""
@@ -278,6 +358,16 @@ class Rodent(PipelineEnv):
         """Whether the reward has the two pose terms (`track_quat` / `track_joints` were given)."""
         return self._pose_host is not None
 
+    @property
+    def reference_obs_frames(self) -> int:
+        """Reference frames H behind every observation row (0: none)."""
+        return self._ref_frames
+
+    @property
+    def observation_size(self) -> int:
+        """Entries of an observation row: the model's obs_dim plus `reference_obs_frames` blocks of nq."""
+        return self.sys.obs_dim + self._ref_frames * self.sys.nq
+
     def set_env_params(self, dof_f=None, act_f=None, con_f=None):
         if self.pose_tracking and not (dof_f is None and act_f is None and con_f is None):
             raise RuntimeError("pose tracking: no pose instance reads per-env parameters (randomize / set_env_params on a pose env)")
@@ -293,6 +383,8 @@ class Rodent(PipelineEnv):
                   healthy_reward=self._healthy_reward, ctrl_cost_weight=self._ctrl_cost_weight,
                   healthy_z_range=self._healthy_z_range, terminate_when_unhealthy=self._terminate_when_unhealthy,
                   bad_state_max=self._bad_state_max)
+        if pose_metrics is None and self._ref_frames:      # a reset that writes the reference blocks: it reads the pose rows too
+            pose_metrics = self._reset_pose_metrics
         if pose_metrics is not None:         # a step of a pose env (a reset passes none: it has no reward)
             io.update(track_pose=self._track_pose, pose_metrics=pose_metrics, quat_reward=self._quat_reward, joint_reward=self._joint_reward)
         return io
@@ -324,7 +416,7 @@ class Rodent(PipelineEnv):
         info = {"cur_frame": cur_frame}
         if clip is not None:
             info["clip"] = torch.from_numpy(np.ascontiguousarray(clip, dtype=np.int32)).to(dev)
-        obs = torch.empty(N, s.obs_dim, device=dev)
+        obs = torch.empty(N, self.observation_size, device=dev)
         self._batch.env_reset(st, self._env_io(cur_frame, obs, clip=info.get("clip")), out)
         zero = torch.zeros(N, device=dev)
         metrics = {"pos_reward": zero, "reward_quadctrl": zero.clone(), "reward_alive": zero.clone()}
@@ -371,7 +463,7 @@ class Rodent(PipelineEnv):
         if self._pipeline_outputs or self._contact_outputs:
             raise ValueError("a multi-step rollout returns no pipeline / contact outputs: build the env without them")
         st_in, st, io, wrap = self._launch_buffers(state, episode_length)
-        obs = torch.empty(self.num_envs, self.sys.obs_dim, device=self.device)
+        obs = torch.empty(self.num_envs, self.observation_size, device=self.device)
         actions = actions.to(self.device, torch.float32).contiguous()
         self._rebalance()
         self._batch.env_unroll(st_in, st, actions, self._n_frames, self._env_io(obs=obs, **io), state.info["cur_frame"], wrap)
@@ -413,7 +505,7 @@ class Rodent(PipelineEnv):
         if self._pipeline_outputs or self._contact_outputs:
             raise ValueError("an evaluation launch returns no pipeline / contact outputs: build the env without them")
         st_in, st, io, wrap = self._launch_buffers(state, episode_length)
-        ring = torch.empty(self.num_envs, 2, self.sys.obs_dim, device=self.device)
+        ring = torch.empty(self.num_envs, 2, self.observation_size, device=self.device)
         obs_in = state.obs.contiguous()
         self._batch.env_unroll_eval(st_in, st, int(T), self._n_frames, self._env_io(obs=obs_in, **io), state.info["cur_frame"], actor,
                                     obs_in, ring, noise, actions_out, eval_metrics, qpos_out, wrap)
@@ -424,7 +516,7 @@ class Rodent(PipelineEnv):
         metrics 0, but its state and observation are returned as they are (possibly non-finite): restoring is AutoReset's part."""
         st_in, st, io, _ = self._launch_buffers(state)
         out = self._alloc_outputs(full=False)
-        obs = torch.empty(self.num_envs, self.sys.obs_dim, device=self.device)
+        obs = torch.empty(self.num_envs, self.observation_size, device=self.device)
         action = action.to(self.device, torch.float32).contiguous()
         self._rebalance()
         self._batch.env_step_to(st_in, st, action, self._n_frames, self._env_io(obs=obs, **io), state.info["cur_frame"], out)

@@ -85,7 +85,7 @@ class RRPpoCfg(C.Structure):
 
 
 EXPORTS = ["rr_model_load", "rr_model_dims", "rr_model_set_solver", "rr_model_set_solver_type", "rr_model_destroy", "rr_model_table", "rr_kernarg_layout", "rr_batch_create",
-           "rr_batch_destroy", "rr_pipeline_init", "rr_pipeline_step", "rr_env_step", "rr_env_reset", "rr_pipeline_step_to", "rr_env_step_to", "rr_batch_contact_overflow", "rr_batch_bad_states", "rr_batch_unroll_supported", "rr_env_unroll", "rr_env_unroll_policy", "rr_batch_eval_supported", "rr_env_unroll_eval", "rr_batch_pose_supported", "rr_batch_set_pose",
+           "rr_batch_destroy", "rr_pipeline_init", "rr_pipeline_step", "rr_env_step", "rr_env_reset", "rr_pipeline_step_to", "rr_env_step_to", "rr_batch_contact_overflow", "rr_batch_bad_states", "rr_batch_unroll_supported", "rr_env_unroll", "rr_env_unroll_policy", "rr_batch_eval_supported", "rr_env_unroll_eval", "rr_batch_pose_supported", "rr_batch_set_pose", "rr_batch_set_reference_obs", "rr_batch_obs_width", "rr_batch_reference_obs_supported",
            "rr_compute_gae", "rr_mlp_forward", "rr_ppo_loss_workspace_bytes", "rr_ppo_loss", "rr_policy_act_workspace_bytes", "rr_policy_act", "rr_policy_sample", "rr_policy_backward_workspace_bytes", "rr_policy_backward", "rr_mlp_silu_backward_workspace_bytes", "rr_mlp_silu_backward", "rr_mlp_value_backward_workspace_bytes", "rr_mlp_policy_backward", "rr_mlp_policy_backward_workspace_bytes", "rr_mlp_value_backward", "rr_mlp_weight_grad_workspace_bytes", "rr_mlp_weight_grad", "rr_mlp_weight_grad_batch_workspace_bytes", "rr_mlp_weight_grad_batch", "rr_obs_moments_workspace_bytes", "rr_obs_moments", "rr_wrap_episode_autoreset", "rr_debug_layout", "rr_batch_set_schedule", "rr_batch_set_env_params", "rr_batch_env_params_supported", "rr_batch_set_profile", "rr_batch_set_ls_repeat_exit", "rr_batch_set_solver_trim", "rr_batch_set_solver_batch", "rr_batch_set_solve_resident", "rr_model_solve_resident_switch", "rr_batch_set_timing", "rr_batch_kernel_time", "rr_last_error"]
 
 _lib = None
@@ -173,6 +173,10 @@ def lib():
         L.rr_batch_env_params_supported.argtypes = [C.c_void_p]
         L.rr_batch_pose_supported.argtypes = [C.c_void_p]
         L.rr_batch_set_pose.argtypes = [C.c_void_p, C.POINTER(RRPoseIO)]
+        L.rr_batch_set_reference_obs.argtypes = [C.c_void_p, C.c_int32]
+        L.rr_batch_obs_width.argtypes = [C.c_void_p]
+        L.rr_batch_obs_width.restype = C.c_int32
+        L.rr_batch_reference_obs_supported.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
         L.rr_batch_set_ls_repeat_exit.argtypes = [C.c_void_p, C.c_int32]
         L.rr_batch_set_solver_trim.argtypes = [C.c_void_p, C.c_int32]
         L.rr_batch_set_solver_batch.argtypes = [C.c_void_p, C.c_int32]
@@ -327,7 +331,7 @@ class Batch:
             e.clip = _ptr(clip, torch.int32, N)
             e.num_clips = tp.shape[0]
         e.cur_frame = _ptr(env["cur_frame"], torch.int32, N)
-        e.obs = _ptr(env["obs"], numel=N * d.obs_dim)
+        e.obs = _ptr(env["obs"], numel=N * self.obs_width())
         e.reward = _ptr(env.get("reward"), numel=N)
         e.done = _ptr(env.get("done"), numel=N)
         e.metrics = _ptr(env.get("metrics"), numel=3 * N)
@@ -342,7 +346,7 @@ class Batch:
             if tuple(pose.shape) != tuple(tp.shape[:-1]) + (d.nq - 3,):
                 raise ValueError(f"env io: track_pose has shape {tuple(pose.shape)}, expected {tuple(tp.shape[:-1]) + (d.nq - 3,)}")
             self.set_pose(pose, env.get("pose_metrics"), env.get("quat_reward", (1.0, 2.0)), env.get("joint_reward", (1.0, 0.5)))
-        elif self._pose is not None:
+        elif self._pose is not None:        # (refused while the batch carries reference frames: their launches all carry track_pose)
             self.set_pose(None)
         return e
 
@@ -393,7 +397,7 @@ class Batch:
     def _unroll_io(self, wrap) -> RRUnrollIO:
         """`wrap` = dict(first, first_obs, prev_done, steps_in, steps_out, truncation_out, episode_length): the state of the Episode +
         AutoReset wrappers that a multi-step launch reads and writes."""
-        N, K = self.N, self.dims.obs_dim
+        N, K = self.N, self.obs_width()
         return RRUnrollIO(self._state(wrap["first"]), _ptr(wrap["first_obs"], numel=N * K), *(_ptr(wrap[k], numel=N) for k in
                           ("prev_done", "steps_in", "steps_out", "truncation_out")), float(wrap["episode_length"]))
 
@@ -402,7 +406,7 @@ class Batch:
         32 x 32 weights), head_wt, head_b (padded to 64 columns for up to 32 actions, to 128 for 33 .. 64), min_std;  traj (the recording
         form): obs [N, T+1, K], raw_action [N, T, A], log_prob / reward / discount / truncation [N, T] (contiguous views); with `segment`
         = L < T: U = T / L such blocks ([U, N, L+1, K], ...), a whole rollout phase of U unrolls."""
-        N, A_, K = self.N, self.dims.nu, self.dims.obs_dim
+        N, A_, K = self.N, self.dims.nu, self.obs_width()
         HW = head_columns(2 * A_)
         bad = f"{who}: inconsistent shapes" if traj is not None else f"{who}: inconsistent actor shapes"
         if actor["w0"].shape != (32, K) or actor["head_wt"].shape != (32, HW) or actor["head_b"].numel() != HW or actor["b0"].numel() != 32:
@@ -450,7 +454,7 @@ class Batch:
         (final observation: obs_ring[:, T & 1])."""
         d, N = self.dims, self.N
         a = self._actor_io("rr_env_unroll_eval", actor, obs_in, T, noise, actions_out)
-        e = RREvalIO(_ptr(eval_metrics, numel=N * 6), _ptr(obs_ring, numel=N * 2 * d.obs_dim), _ptr(qpos_out, numel=(T + 1) * N * d.nq),
+        e = RREvalIO(_ptr(eval_metrics, numel=N * 6), _ptr(obs_ring, numel=N * 2 * self.obs_width()), _ptr(qpos_out, numel=(T + 1) * N * d.nq),
                      0 if wrap is not None else 1)
         w = self._unroll_io(wrap) if wrap is not None else None
         _check(lib().rr_env_unroll_eval(self.h, C.byref(self._state(st_in)), C.byref(self._state(st_out)), int(T), int(n_frames), C.byref(self._env(env)),
@@ -492,6 +496,22 @@ class Batch:
     def pose_supported(self) -> Optional[str]:
         """None when this batch serves pose tracking (`set_pose`; C ABI `rr_batch_pose_supported`), else the refusal's text."""
         if _check(lib().rr_batch_pose_supported(self.h)) == 1:
+            return None
+        return lib().rr_last_error().decode()
+
+    def set_reference_obs(self, frames: int):
+        """`frames` = H reference frames behind every observation row of this batch (C ABI `rr_batch_set_reference_obs`): 0 .. 16, more
+        than 0 only with the pose block set (`set_pose`).  Every buffer documented as obs wide is then `obs_width()` wide."""
+        _check(lib().rr_batch_set_reference_obs(self.h, int(frames)))
+
+    def obs_width(self) -> int:
+        """Entries of an observation row of this batch (C ABI `rr_batch_obs_width`): obs_dim + frames * nq."""
+        return _check(lib().rr_batch_obs_width(self.h))
+
+    def reference_obs_supported(self, frames: int, with_actor: bool = False) -> Optional[str]:
+        """None when this batch serves `frames` reference frames (C ABI `rr_batch_reference_obs_supported`) -- with `with_actor` also in
+        the one-launch rollout with the actor inside, whose actor reads a bounded row width -- else the refusal's text."""
+        if _check(lib().rr_batch_reference_obs_supported(self.h, int(frames), int(with_actor))) == 1:
             return None
         return lib().rr_last_error().decode()
 

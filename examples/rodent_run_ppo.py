@@ -60,6 +60,9 @@ def main():
                     "magnitude (MuJoCo's mjMAXVAL is 1e10); off by default")
     ap.add_argument("--track-pose", action="store_true", help="reward the clip's root orientation and joint angles too (Rodent(track_quat=..., "
                     "track_joints=...), untuned default weights); the synthetic line carries the identity quaternion and qpos0's joints.  Not with --randomize")
+    ap.add_argument("--reference-frames", type=int, default=0, metavar="H", help="with --track-pose: the observation also carries the clip's next "
+                    "H frames (Rodent(reference_obs_frames=H), 0 .. 16): next positions in the root frame, relative orientations, joint-angle "
+                    "differences.  Up to 5 the rollout stays one launch; above that it is collected per step")
     ap.add_argument("--policy-width", type=int, choices=(32, 256), default=32, help="units per hidden layer of the policy network; both "
                     "widths run on the hand-written learner kernels (256: per-step rollouts, the in-kernel actor is 32-wide)")
     ap.add_argument("--policy-depth", type=int, default=4, help="hidden layers of the policy network (1 .. 7 for the hand-written kernels; "
@@ -80,6 +83,10 @@ def main():
     }
     if args.track_pose and args.randomize:
         ap.error("--track-pose: the step kernel's pose instances read no per-env parameters; drop --randomize")
+    if args.reference_frames and not args.track_pose:
+        ap.error("--reference-frames: the frames are rows of the reference pose; add --track-pose")
+    if not 0 <= args.reference_frames <= 16:
+        ap.error("--reference-frames: 0 .. 16")
     clips = None                                     # the loaded ReferenceClip(s), [C, T, ...] fields; None for a .npy track or the synthetic line
     if args.clip and os.path.exists(args.clip) and not args.clip.endswith(".npy"):
         clips = preprocessing.load_reference_clip(args.clip, args.clip_name)
@@ -109,7 +116,7 @@ def main():
         config["env_name"], track_pos=track_pos, terminate_when_unhealthy=config["terminate_when_unhealthy"],
         solver=config["solver"], iterations=config["iterations"], ls_iterations=config["ls_iterations"],
         vision=config["vision"], num_envs=args.envs_per_gpu, xml_path=args.xml, device=f"cuda:{local_rank}",
-        bad_state_max=args.bad_state_max, **pose)
+        bad_state_max=args.bad_state_max, reference_obs_frames=args.reference_frames, **pose)
 
     train_fn = functools.partial(
         ppo.train, num_timesteps=config["num_timesteps"], num_evals=int(config["num_timesteps"] / config["eval_every"]),

@@ -275,6 +275,34 @@ typedef struct rr_pose_io {
 int rr_batch_set_pose(rr_batch* b, const rr_pose_io* pose);
 int rr_batch_pose_supported(const rr_batch* b);
 
+/* Reference observation: the policy sees what the pose reward scores.  rr_batch_set_reference_obs(b, H), H = 1 .. 16, on a batch whose
+ * pose block is set (rr_batch_set_pose; rr_env_io and rr_pose_io are closed, so the count rides on the batch like the block) makes every
+ * observation row of the batch
+ *   [ the model's observation (obs_dim) | block_1 | ... | block_H ],   rr_batch_obs_width(b) = obs_dim + H * nq entries,
+ * written wherever an observation is written -- by rr_env_reset, which then reads the pose block too, and by every env step of
+ * rr_env_step(_to), rr_env_unroll and rr_env_unroll_policy, a bad step included.  EVERY array this header documents as [obs] wide is
+ * rr_batch_obs_width(b) wide on such a batch: rr_env_io::obs, rr_unroll_io::first_obs, rr_actor_io::traj_obs, obs_in, mean, std and the
+ * rows of w0 (the library cannot check the callers' lengths).  H = 0 (a batch starts that way): the width is obs_dim and nothing changes.
+ * block_h = (p_h[3], q_h[4], j_h[nq - 7]) reads frame f_h = clamp(frame + h, 0, track_len - 1) of the env's clip (the id clamped as
+ * everywhere), `frame` being the frame the observation's track entry counts from: the stepped cur_frame after a step, cur_frame at a
+ * reset.  With x the world quaternion of body 1 (whose matrix is the xmat[1] of the track entry) and (r_q, r_j) track_pose's row:
+ *   p_h = xmat[1] @ (track_pos[f_h] - qpos[:3])        p_1 equals the last three entries of the model's observation bit for bit
+ *   q_h = s * (conj(x) (x) r_q),  s = -1 where that product's w is negative, else +1 (so q_h.w >= 0); float32, every product and sum
+ *         rounded on its own:  w = ((xw rw + xx rx) + xy ry) + xz rz,  x = ((xw rx - xx rw) - xy rz) + xz ry,
+ *                              y = ((xw ry + xx rz) - xy rw) - xz rx,  z = ((xw rz - xx ry) + xy rx) - xz rw
+ *   j_h = r_j - qpos[7:nq]                             one float32 subtraction per entry
+ * Under the AutoReset wrapper of the multi-step forms the stored first observation comes back verbatim at the full width.
+ * rr_batch_set_reference_obs: frames outside 0 .. 16, or frames > 0 without a pose block: RR_EINVAL; RR_EUNSUPPORTED with the reason
+ * wherever pose tracking is unsupported.  While frames > 0, rr_batch_set_pose(b, NULL) is RR_EINVAL (set the frames to 0 first) and
+ * rr_env_unroll_eval refuses (no evaluation instance writes the blocks; evaluate step by step).  The in-kernel actor of these instances
+ * reads 26 entries per lane, a row of at most 1664: rr_env_unroll_policy refuses a wider one (RR_EUNSUPPORTED) -- on the shipped
+ * floor-contact models (obs_dim 1279 / 1263, nq 74) that is H <= 5 -- while the forms without the actor serve every H.
+ * rr_batch_reference_obs_supported(b, frames, with_actor): 1 / 0 -- whether the batch serves that many frames (with_actor != 0: also in
+ * rr_env_unroll_policy); with 0 rr_last_error holds the reason.  It does not need the pose block to be set. */
+int rr_batch_set_reference_obs(rr_batch* b, int32_t frames);
+int32_t rr_batch_obs_width(const rr_batch* b);
+int rr_batch_reference_obs_supported(const rr_batch* b, int32_t frames, int32_t with_actor);
+
 /* Generalised advantage estimation of one PPO minibatch, the reverse scan of brax.training.agents.ppo.losses.compute_gae
  * [UP; SURVEY.md Appendix E], one thread per trajectory.  All arrays time-major [T][B] device float32; bootstrap [B];
  * outputs vs [T][B] and advantages [T][B].  `stream` is a hipStream_t (NULL = default stream). */
