@@ -279,6 +279,15 @@ struct RRIO {
   // Fetched by a narrow load where it is used (load_io_member), never through load_io().
   int ref_frames;
   int ref_pad;                 // keeps sizeof(RRIO) a multiple of 8 (RRKArgs)
+  // POSE TERMINATION (PTERM instances, rr_poseterm_kernel; no other instance reads it): an env step whose stepped qpos strays from the
+  // clip's row at (clip[env], old_frame) -- the row the position and pose rewards read -- ends the episode.  Lane 0 forms
+  //   e_pos = |qpos[:3] - track_pos[f]|, e_quat = theta of POSE TRACKING, e_joint = sqrt(sum (qpos[7+i] - r_j,i)^2),
+  //   code = 1 (e_pos > pose_max_pos) | 2 (e_quat > pose_max_quat) | 4 (e_joint > pose_max_joint)      (+inf: off; a NaN error: no bit)
+  // stores (float)code in pose_fail[env] and done = max(done, code != 0); a bad step stores code 0.  Never at reset.  Nothing else of the
+  // step changes.  Fetched by narrow loads where they are used (load_io_member), never through load_io().
+  float* pose_fail;            // [N]
+  float pose_max_pos, pose_max_quat, pose_max_joint;
+  int pterm_pad;               // keeps sizeof(RRIO) a multiple of 8 (RRKArgs)
 };
 
 // ------------------------------------------------------------------------------------------ small math
@@ -2538,7 +2547,9 @@ static_assert(offsetof(RRKArgs, io) == rr_align_up(offsetof(RRKArgs, T) + sizeof
 static_assert(offsetof(RRKArgs, num_envs) == offsetof(RRKArgs, io) + sizeof(RRIO) && sizeof(RRIO) % 8 == 0, "scalars follow RRIO without padding");
 static_assert(offsetof(RRIO, clip) % 8 == 0 && offsetof(RRIO, clip) + sizeof(const int*) == offsetof(RRIO, track_pose), "the pose members follow the clip ids without padding");
 static_assert(offsetof(RRIO, pose_joint_k) + sizeof(float) == offsetof(RRIO, ref_frames), "the reference-observation members follow the pose members without padding");
-static_assert(offsetof(RRIO, ref_pad) + sizeof(int) == sizeof(RRIO), "the reference-observation members close RRIO without padding");
+static_assert(offsetof(RRIO, ref_pad) + sizeof(int) == offsetof(RRIO, pose_fail) && offsetof(RRIO, pose_fail) % 8 == 0, "the pose-termination members follow the reference-observation members without padding");
+static_assert(offsetof(RRIO, pose_fail) + sizeof(float*) == offsetof(RRIO, pose_max_pos), "the thresholds follow pose_fail without padding");
+static_assert(offsetof(RRIO, pterm_pad) + sizeof(int) == sizeof(RRIO), "the pose-termination members close RRIO without padding");
 // ... and so are the model tables outside the solver's loops: RRTables is re-read at the head of each phase that indexes a table
 // (narrow scalar loads next to an existing hand-off; the unused members' loads are dead), so no table pointer is held across the
 // substep.  The loops' own tables are the exception (RRLoopTables, taken once from the parameter).
@@ -2728,7 +2739,7 @@ __device__ __forceinline__ void rr_actor_step(const RRIO& io, const DT& D, int l
 template <int NBS, int NVS, int NCS, bool PROF, bool DBG, class DT, bool NEWTON = false, bool UNROLL = false, bool ACTOR = false, bool PAIR = false, bool DYN = false>
 __global__ __launch_bounds__((PAIR ? 2 : 1) * RR_LANES, (NVS >= 3 ? 1 : 2)) void rr_step_kernel(const RRDims Dk, const RRTables Tk, const RRIO io_kernarg, const int num_envs,
                                                            const int n_frames) {
-  constexpr bool RAND = false, EVAL = false, POSE = false, REFOBS = false;
+  constexpr bool RAND = false, EVAL = false, POSE = false, REFOBS = false, PTERM = false;
   constexpr int MRES = ACTOR ? 1 : 2;      // resident inverse-factor entries (Wave::MAT_RES): both sides at 245-253 registers (timed: -1.4 % against the column side alone); with the actor the column side (233)
 #include "rr_step_body.inc"
 }
@@ -2737,7 +2748,7 @@ __global__ __launch_bounds__((PAIR ? 2 : 1) * RR_LANES, (NVS >= 3 ? 1 : 2)) void
 template <class DT, bool UNROLL = false, bool ACTOR = false>
 __global__ __launch_bounds__(RR_LANES, 2) void rr_rand_kernel(const RRDims Dk, const RRTables Tk, const RRIO io_kernarg, const int num_envs, const int n_frames) {
   constexpr int NBS = 2, NVS = 2, NCS = 1;
-  constexpr bool PROF = false, DBG = false, NEWTON = false, PAIR = false, DYN = false, RAND = true, EVAL = false, POSE = false, REFOBS = false;
+  constexpr bool PROF = false, DBG = false, NEWTON = false, PAIR = false, DYN = false, RAND = true, EVAL = false, POSE = false, REFOBS = false, PTERM = false;
   constexpr int MRES = 1;      // resident inverse-factor entries (Wave::MAT_RES): the column side (229-237 registers; both sides reach the cap of 256 here)
 #include "rr_step_body.inc"
 }
@@ -2749,7 +2760,7 @@ __global__ __launch_bounds__(RR_LANES, 2) void rr_rand_kernel(const RRDims Dk, c
 template <class DT, bool DYN = false>
 __global__ __launch_bounds__(RR_LANES, 2) void rr_eval_kernel(const RRDims Dk, const RRTables Tk, const RRIO io_kernarg, const int num_envs, const int n_frames) {
   constexpr int NBS = 2, NVS = 2, NCS = 1;
-  constexpr bool PROF = false, DBG = false, NEWTON = false, PAIR = false, RAND = false, UNROLL = true, ACTOR = true, EVAL = true, POSE = false, REFOBS = false;
+  constexpr bool PROF = false, DBG = false, NEWTON = false, PAIR = false, RAND = false, UNROLL = true, ACTOR = true, EVAL = true, POSE = false, REFOBS = false, PTERM = false;
   constexpr int MRES = 1;      // resident inverse-factor entries (Wave::MAT_RES): the column side (229-237 registers; both sides reach the cap of 256 here)
 #include "rr_step_body.inc"
 }
@@ -2760,7 +2771,7 @@ __global__ __launch_bounds__(RR_LANES, 2) void rr_eval_kernel(const RRDims Dk, c
 template <class DT, bool UNROLL = false, bool ACTOR = false>
 __global__ __launch_bounds__(RR_LANES, 2) void rr_pose_kernel(const RRDims Dk, const RRTables Tk, const RRIO io_kernarg, const int num_envs, const int n_frames) {
   constexpr int NBS = 2, NVS = 2, NCS = 1;
-  constexpr bool PROF = false, DBG = false, NEWTON = false, PAIR = false, DYN = false, RAND = false, EVAL = false, POSE = true, REFOBS = false;
+  constexpr bool PROF = false, DBG = false, NEWTON = false, PAIR = false, DYN = false, RAND = false, EVAL = false, POSE = true, REFOBS = false, PTERM = false;
   constexpr int MRES = 1;      // resident inverse-factor entries (Wave::MAT_RES): the column side (229-237 registers; both sides reach the cap of 256 here)
 #include "rr_step_body.inc"
 }
@@ -2771,16 +2782,28 @@ __global__ __launch_bounds__(RR_LANES, 2) void rr_pose_kernel(const RRDims Dk, c
 template <class DT, bool UNROLL = false, bool ACTOR = false>
 __global__ __launch_bounds__(RR_LANES, 2) void rr_refobs_kernel(const RRDims Dk, const RRTables Tk, const RRIO io_kernarg, const int num_envs, const int n_frames) {
   constexpr int NBS = 2, NVS = 2, NCS = 1;
-  constexpr bool PROF = false, DBG = false, NEWTON = false, PAIR = false, DYN = false, RAND = false, EVAL = false, POSE = true, REFOBS = true;
+  constexpr bool PROF = false, DBG = false, NEWTON = false, PAIR = false, DYN = false, RAND = false, EVAL = false, POSE = true, REFOBS = true, PTERM = false;
+  constexpr int MRES = 1;      // resident inverse-factor entries (Wave::MAT_RES): the column side, as in rr_pose_kernel
+#include "rr_step_body.inc"
+}
+// Pose termination (rr_batch_set_pose_termination): the reference-observation instances with the env step's done raised where the stepped
+// pose strays from the clip (RRIO, POSE TERMINATION), served to the env steps of a batch that carries the block; resets stay on the
+// instance they use without it.  A sixth entry for the reason the others are entries of their own: every `if (PTERM)` in the body folds
+// away in their instances.  REFOBS is on, so the row is rr_obs_width wide and ref_frames = 0 is the same code with zero blocks; the actor
+// inside reads RR_ACTOR_JM_REFOBS entries per lane whatever the frame count.  The same nine forms as rr_pose_kernel.
+template <class DT, bool UNROLL = false, bool ACTOR = false>
+__global__ __launch_bounds__(RR_LANES, 2) void rr_poseterm_kernel(const RRDims Dk, const RRTables Tk, const RRIO io_kernarg, const int num_envs, const int n_frames) {
+  constexpr int NBS = 2, NVS = 2, NCS = 1;
+  constexpr bool PROF = false, DBG = false, NEWTON = false, PAIR = false, DYN = false, RAND = false, EVAL = false, POSE = true, REFOBS = true, PTERM = true;
   constexpr int MRES = 1;      // resident inverse-factor entries (Wave::MAT_RES): the column side, as in rr_pose_kernel
 #include "rr_step_body.inc"
 }
 // The production single-step instance with the inverse factor's entries left in LDS (MRES 0), whatever RR_SOLVE_MAT_RESIDENT says: the other
 // arm of an exact A/B inside one library (rr_batch_set_solve_resident(b, 0); tests/test_gpu_solve_resident.py).  An entry of its own so
-// that the instances of the other five keep their code.
+// that the instances of the other six keep their code.
 template <class DT>
 __global__ __launch_bounds__(RR_LANES, 2) void rr_matlds_kernel(const RRDims Dk, const RRTables Tk, const RRIO io_kernarg, const int num_envs, const int n_frames) {
   constexpr int NBS = 2, NVS = 2, NCS = 1, MRES = 0;
-  constexpr bool PROF = false, DBG = false, NEWTON = false, UNROLL = false, ACTOR = false, PAIR = false, DYN = false, RAND = false, EVAL = false, POSE = false, REFOBS = false;
+  constexpr bool PROF = false, DBG = false, NEWTON = false, UNROLL = false, ACTOR = false, PAIR = false, DYN = false, RAND = false, EVAL = false, POSE = false, REFOBS = false, PTERM = false;
 #include "rr_step_body.inc"
 }

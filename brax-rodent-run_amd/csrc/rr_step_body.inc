@@ -1,12 +1,13 @@
 // rr_step_body.inc -- the body of the step kernel, included by each of its __global__ entries in rr_kernel.h (rr_step_kernel,
-// rr_rand_kernel, rr_eval_kernel, rr_pose_kernel, rr_refobs_kernel, rr_matlds_kernel).  In scope where it is included: the kernel's five arguments (Dk, Tk, io_kernarg, num_envs, n_frames) and the
-// compile-time switches NBS, NVS, NCS, PROF, DBG, DT, NEWTON, UNROLL, ACTOR, PAIR, DYN, RAND, EVAL, POSE, REFOBS, MRES.
+// rr_rand_kernel, rr_eval_kernel, rr_pose_kernel, rr_refobs_kernel, rr_poseterm_kernel, rr_matlds_kernel).  In scope where it is included: the kernel's five arguments (Dk, Tk, io_kernarg, num_envs, n_frames) and the
+// compile-time switches NBS, NVS, NCS, PROF, DBG, DT, NEWTON, UNROLL, ACTOR, PAIR, DYN, RAND, EVAL, POSE, REFOBS, PTERM, MRES.
 // Why text and not a function: see the note above rr_step_kernel.
   static_assert(!PAIR || (!PROF && !DBG && !NEWTON && !UNROLL && !ACTOR), "PAIR: production physics instance only");
   static_assert(!DYN || (!PROF && !DBG && !NEWTON && !PAIR), "DYN: production instances only (single-step, multi-step, multi-step with the actor)");
   static_assert(!ACTOR || UNROLL, "the actor lives in the multi-step instances");
   static_assert(!POSE || (!RAND && !EVAL && !PROF && !DBG && !NEWTON && !PAIR && !DYN), "POSE: production CG instances of the floor-contact models only");
   static_assert(!REFOBS || POSE, "REFOBS: a form of the pose instances (the blocks are rows of track_pose)");
+  static_assert(!PTERM || REFOBS, "PTERM: a form of the reference-observation instances (ref_frames 0: no blocks)");
   static_assert(!EVAL || (ACTOR && !RAND && !PROF && !DBG && !NEWTON && !PAIR), "EVAL: a form of the production multi-step instance with the actor");
   extern __shared__ __attribute__((aligned(16))) float lds[];
   int env = blockIdx.x;
@@ -419,6 +420,7 @@
         }
       }
     }
+    int pterm_code = 0;      // PTERM instances: the pose-termination code of this step, decided on lane 0, wave-uniform after the lane-0 block
     if (!is_reset) {
       float a2 = 0.0f;
       for (int i = lane; i < D.nu; i += RR_LANES) { const float a = io.ctrl[ctrl_at + i]; a2 += a * a; }
@@ -477,6 +479,17 @@
             rew = (plain_rew + quat_rew) + joint_rew;
             float* pm = load_io_member<float*>(offsetof(RRIO, pose_metrics)) + 2 * (size_t)env;
             pm[0] = quat_rew; pm[1] = joint_rew;
+            // ---- POSE TERMINATION (PTERM instances, RRIO::pose_fail): the three errors against the thresholds.  ISOLATION: d2, theta and
+            // pe2 pass through opaque copies, so the reward's expressions above keep the uses -- and with them the contraction -- they
+            // have in the pose and reference-observation instances; the compared values are formed again from the copies, contraction
+            // off.  `x > +inf` and `NaN > x` are false: an infinite threshold is off, a NaN error belongs to the bad-state check.
+            if (PTERM) {
+              float cd2 = d2, cth = theta, cpe = pe2;
+              asm volatile("" : "+v"(cd2), "+v"(cth), "+v"(cpe));
+              const float e_pos = sqrtf(cd2), e_joint = sqrtf(cpe);
+              pterm_code = (e_pos > load_io_member<float>(offsetof(RRIO, pose_max_pos)) ? 1 : 0) | (cth > load_io_member<float>(offsetof(RRIO, pose_max_quat)) ? 2 : 0) |
+                           (e_joint > load_io_member<float>(offsetof(RRIO, pose_max_joint)) ? 4 : 0);
+            }
           }
         }
         io.reward[env] = rew;
@@ -494,8 +507,15 @@
           if (POSE) {
             if (prow) { float* pm = load_io_member<float*>(offsetof(RRIO, pose_metrics)) + 2 * (size_t)env; pm[0] = 0.0f; pm[1] = 0.0f; }
           }
+          if (PTERM) pterm_code = 0;      // a bad step: done = 1 from the check above, code 0
+        }
+        // pose termination changes nothing but done: raised OVER the step's value, as the bad-state branch does
+        if (PTERM) {
+          if (float* pf = load_io_member<float*>(offsetof(RRIO, pose_fail))) pf[env] = (float)pterm_code;
+          if (pterm_code != 0) io.done[env] = 1.0f;
         }
       }
+      if (PTERM) pterm_code = __builtin_amdgcn_readfirstlane(pterm_code);      // lane 0's value in every lane: done_env below is formed by all of them
     }
     if (UNROLL) {
       // EpisodeWrapper + AutoResetWrapper on the step just made (action_repeat 1), as rr_wrap_kernel applies them:
@@ -503,7 +523,8 @@
       // where done, the stored first state and first observation come back (info -- cur_frame, steps -- is not restored)
       const float z = w.s_qpos[2];
       const float healthy = (z < io.z_min || z > io.z_max) ? 0.0f : 1.0f;
-      const float done_env = (mode & 4) ? 1.0f : (io.terminate_when_unhealthy ? 1.0f - healthy : 0.0f);
+      const float done_own = (mode & 4) ? 1.0f : (io.terminate_when_unhealthy ? 1.0f - healthy : 0.0f);
+      const float done_env = (PTERM && pterm_code != 0) ? 1.0f : done_own;      // PTERM: a pose failure is a termination (trunc 0, discount 0, restore)
       const bool wrapped = !EVAL || !(io.a_pad & RR_EVAL_RAW);      // EVAL without the wrappers: the env's own done, no step count, no restore
       if (wrapped) u_steps = (u_prev_done != 0.0f ? 0.0f : u_steps) + 1.0f;
       const bool over = wrapped && u_steps >= io.episode_length;

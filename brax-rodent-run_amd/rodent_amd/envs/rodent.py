@@ -7,6 +7,7 @@ substeps + reward / done / observation epilogue (C ABI `rr_env_step`).
 """
 from __future__ import annotations
 
+import math
 import os
 import warnings
 from typing import Optional
@@ -193,6 +194,61 @@ def _check_reference_frames(frames, have_pose: bool) -> int:
     return int(frames)
 
 
+def pose_errors(qpos, ref_pos, ref_quat, ref_joints):
+    """The three errors pose termination compares (`Rodent(max_pos_error=..., max_quat_error=..., max_joint_error=...)`; C ABI
+    `rr_batch_set_pose_termination`) restated in numpy float64.  `qpos` [..., nq] the stepped state; `ref_pos` [..., 3], `ref_quat`
+    [..., 4] (w, x, y, z) and `ref_joints` [..., nq - 7] the clip's row at the clip and frame the step's rewards read (`cur_frame` before
+    the step, clamped).  Returns (e_pos, e_quat, e_joint), float64 [...]:
+
+        e_pos   = |qpos[:3] - ref_pos|_2
+        e_quat  = theta of `pose_rewards` = 2 atan2(|d.xyz|, |d.w|), d = conj(ref_quat) (x) qpos[3:7]     (in [0, pi]; q and -q agree)
+        e_joint = sqrt(sum((qpos[7:] - ref_joints)**2))"""
+    qpos, rp, r, rj = (np.asarray(a, dtype=np.float64) for a in (qpos, ref_pos, ref_quat, ref_joints))
+    q = qpos[..., 3:7]
+    rw, rx, ry, rz = (r[..., i] for i in range(4))
+    qw, qx, qy, qz = (q[..., i] for i in range(4))
+    dw = rw * qw + rx * qx + ry * qy + rz * qz
+    dx = rw * qx - rx * qw - ry * qz + rz * qy
+    dy = rw * qy + rx * qz - ry * qw - rz * qx
+    dz = rw * qz - rx * qy + ry * qx - rz * qw
+    e_quat = 2.0 * np.arctan2(np.sqrt(dx * dx + dy * dy + dz * dz), np.abs(dw))
+    return np.sqrt(((qpos[..., :3] - rp) ** 2).sum(-1)), e_quat, np.sqrt(((qpos[..., 7:] - rj) ** 2).sum(-1))
+
+
+def pose_fail_code(errors, thresholds) -> np.ndarray:
+    """The pose-termination code of `errors` = (e_pos, e_quat, e_joint) (`pose_errors`) against `thresholds` = (max_pos_error,
+    max_quat_error, max_joint_error): int64 [...] = 1 (e_pos > max_pos) | 2 (e_quat > max_quat) | 4 (e_joint > max_joint).  A threshold
+    of inf (or None) never fires; a NaN error sets no bit (`x > t` is false)."""
+    code = 0
+    with np.errstate(invalid="ignore"):
+        for bit, e, t in zip((1, 2, 4), errors, thresholds):
+            code = code + bit * (np.asarray(e, dtype=np.float64) > (np.inf if t is None else float(t))).astype(np.int64)
+    return np.asarray(code, dtype=np.int64)
+
+
+def _check_pose_termination(max_pos_error, max_quat_error, max_joint_error, have_pose: bool) -> Optional[tuple]:
+    """The three thresholds of `Rodent` as floats (None -> inf), or None when all three are None or inf (no termination block).  ValueError
+    for a value that is NaN or not > 0 as a float32 (what the kernel compares with), and for any finite value without the pose
+    arguments."""
+    out = []
+    for name, x in (("max_pos_error", max_pos_error), ("max_quat_error", max_quat_error), ("max_joint_error", max_joint_error)):
+        if x is None:
+            out.append(math.inf)
+            continue
+        if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, float, np.integer, np.floating)):
+            raise ValueError(f"{name} must be a number > 0 (or None: that criterion off), got {x!r}")
+        with np.errstate(over="ignore", under="ignore"):
+            x32 = np.float32(x)
+        if not x32 > 0:       # NaN included
+            raise ValueError(f"{name} must be > 0 as a float32 and not NaN (or None: that criterion off), got {x!r}")
+        out.append(float(x32))
+    if all(math.isinf(x) for x in out):
+        return None
+    if not have_pose:
+        raise ValueError("max_pos_error / max_quat_error / max_joint_error need the reference pose: pass track_quat and track_joints")
+    return tuple(out)
+
+
 class Rodent(PipelineEnv):
 
     def __init__(
@@ -220,6 +276,9 @@ class Rodent(PipelineEnv):
         joint_reward_scale: float = 0.5,
         reset_to_reference: bool = False,
         reference_obs_frames: int = 0,
+        max_pos_error: Optional[float] = None,
+        max_quat_error: Optional[float] = None,
+        max_joint_error: Optional[float] = None,
         **kwargs,
     ):
         """`track_pos`: the reference positions to track, float [T, 3] -- one clip, followed by every env -- or [C, T, 3], C >= 1 clips of
@@ -260,7 +319,17 @@ class Rodent(PipelineEnv):
         frame (p_1 is the observation's own last three entries), the reference orientations relative to the root's with w >= 0, and the
         reference joint angles minus the current ones (`reference_obs` restates them in float64).  AutoReset restores the stored first
         observation at the full width.  The one-launch rollout with the actor inside serves rows up to 1664 wide (H <= 5 on the shipped
-        floor-contact models); above that `ppo.train` collects per step."""
+        floor-contact models); above that `ppo.train` collects per step.
+
+        Pose termination: `max_pos_error` (metres), `max_quat_error` (radians), `max_joint_error` (radians, the 2-norm over the joints)
+        -- pose envs only; None, the default, or inf: that criterion off; each > 0 and not NaN.  With any of them finite an env step
+        (never a reset) whose stepped pose has strayed from the clip's row -- the row its rewards read -- ends the episode:
+        `pose_errors` gives (e_pos, e_quat, e_joint), `pose_fail_code` the code 1 (e_pos > max_pos_error) | 2 (e_quat > max_quat_error)
+        | 4 (e_joint > max_joint_error), and done = max(done, code != 0), whatever `terminate_when_unhealthy` is.  Nothing else of the
+        step changes.  It is a termination, not a truncation: under AutoReset -- composed or in the one-launch rollouts -- the first
+        state comes back, discount 0.  `State.metrics` gains `pose_fail`, `pose_fail_pos`, `pose_fail_quat`, `pose_fail_joint` (0 / 1;
+        zeros at reset and after a bad step), so an evaluation reports `eval/episode_pose_fail`, the share of episodes ended by the
+        clip.  The thresholds have no defaults: they depend on the clips and on how far training has come."""
         if bad_state_max is not None:
             with np.errstate(over="ignore", under="ignore"):
                 thr32 = np.float32(bad_state_max)        # what the kernel gets: 1e-50 would arrive as 0 (= off), 1e39 as inf
@@ -280,6 +349,7 @@ class Rodent(PipelineEnv):
         sys = System(assets.resolve_model(xml_path), iterations, ls_iterations, solver)
         pose_np = _check_pose(track_np, track_quat, track_joints, sys.nq, (quat_reward_weight, quat_reward_scale, joint_reward_weight, joint_reward_scale))
         ref_frames = _check_reference_frames(reference_obs_frames, pose_np is not None)
+        pose_term = _check_pose_termination(max_pos_error, max_quat_error, max_joint_error, pose_np is not None)
         if reset_to_reference and pose_np is None:
             raise ValueError("reset_to_reference=True needs the reference pose: pass track_quat and track_joints")
         physics_steps_per_control_step = 10   # [REF Rodent_Env_Brax.py:53-57]
@@ -308,6 +378,11 @@ class Rodent(PipelineEnv):
             self._reset_pose_metrics = torch.zeros(num_envs, 2, device=self.device)
             self._batch.set_pose(self._track_pose, self._reset_pose_metrics, self._quat_reward, self._joint_reward)
             self._batch.set_reference_obs(ref_frames)
+        self._pose_term = pose_term       # None: no pose termination (no such members anywhere, the launches run the instances they ran)
+        if pose_term is not None:
+            why = self._batch.pose_termination_supported()
+            if why is not None:
+                raise RuntimeError(f"Rodent(max_pos_error / max_quat_error / max_joint_error): {why}")
         self._forward_reward_weight = forward_reward_weight
         self._ctrl_cost_weight = ctrl_cost_weight
         self._healthy_reward = healthy_reward
@@ -326,7 +401,8 @@ class Rodent(PipelineEnv):
                           track_quat=track_quat, track_joints=track_joints, quat_reward_weight=quat_reward_weight,
                           quat_reward_scale=quat_reward_scale, joint_reward_weight=joint_reward_weight,
                           joint_reward_scale=joint_reward_scale, reset_to_reference=reset_to_reference,
-                          reference_obs_frames=reference_obs_frames)
+                          reference_obs_frames=reference_obs_frames, max_pos_error=max_pos_error, max_quat_error=max_quat_error,
+                          max_joint_error=max_joint_error)
 
     def with_num_envs(self, num_envs: int, device=None):
         """A sibling env with another batch size (ppo.train builds its per-rank and eval envs this way)."""
@@ -359,6 +435,11 @@ class Rodent(PipelineEnv):
         return self._pose_host is not None
 
     @property
+    def pose_termination(self) -> Optional[tuple]:
+        """(max_pos_error, max_quat_error, max_joint_error) as the kernel compares them, inf = off; None without pose termination."""
+        return self._pose_term
+
+    @property
     def reference_obs_frames(self) -> int:
         """Reference frames H behind every observation row (0: none)."""
         return self._ref_frames
@@ -378,7 +459,7 @@ class Rodent(PipelineEnv):
             raise RuntimeError("pose tracking: no pose instance reads per-env parameters (randomize / set_env_params on a pose env)")
         return super().randomize(randomization_fn)
 
-    def _env_io(self, cur_frame, obs, reward=None, done=None, metrics=None, clip=None, pose_metrics=None):
+    def _env_io(self, cur_frame, obs, reward=None, done=None, metrics=None, clip=None, pose_metrics=None, pose_fail=None):
         io = dict(track_pos=self._track_pos, cur_frame=cur_frame, obs=obs, reward=reward, done=done, metrics=metrics, clip=clip,
                   healthy_reward=self._healthy_reward, ctrl_cost_weight=self._ctrl_cost_weight,
                   healthy_z_range=self._healthy_z_range, terminate_when_unhealthy=self._terminate_when_unhealthy,
@@ -387,6 +468,8 @@ class Rodent(PipelineEnv):
             pose_metrics = self._reset_pose_metrics
         if pose_metrics is not None:         # a step of a pose env (a reset passes none: it has no reward)
             io.update(track_pose=self._track_pose, pose_metrics=pose_metrics, quat_reward=self._quat_reward, joint_reward=self._joint_reward)
+        if pose_fail is not None:            # a step of an env with pose termination (a reset passes none: it has no done to raise)
+            io.update(pose_fail=pose_fail, pose_termination=self._pose_term)
         return io
 
     def reset(self, rng, clip=None) -> State:
@@ -422,6 +505,8 @@ class Rodent(PipelineEnv):
         metrics = {"pos_reward": zero, "reward_quadctrl": zero.clone(), "reward_alive": zero.clone()}
         if self.pose_tracking:
             metrics.update(quat_reward=zero.clone(), joint_reward=zero.clone())
+        if self._pose_term is not None:
+            metrics.update({k: zero.clone() for k in ("pose_fail", "pose_fail_pos", "pose_fail_quat", "pose_fail_joint")})
         return State(PipelineState(**st, **out), obs, zero.clone(), zero.clone(), metrics, info)
 
     def _launch_buffers(self, state: State, episode_length: Optional[float] = None):
@@ -437,6 +522,8 @@ class Rodent(PipelineEnv):
                   metrics=torch.empty(N, 3, device=dev), clip=info.get("clip"))      # clip: read only (None without a clip axis)
         if self.pose_tracking:
             io["pose_metrics"] = torch.empty(N, 2, device=dev)
+        if self._pose_term is not None:
+            io["pose_fail"] = torch.empty(N, device=dev)
         wrap = None
         if episode_length is not None:
             wrap = dict(first=fields(info["first_pipeline_state"]), first_obs=info["first_obs"], prev_done=state.done, steps_in=info["steps"],
@@ -453,6 +540,10 @@ class Rodent(PipelineEnv):
         m.update(pos_reward=io["metrics"][:, 0], reward_quadctrl=io["metrics"][:, 1], reward_alive=io["metrics"][:, 2])
         if self.pose_tracking:
             m.update(quat_reward=io["pose_metrics"][:, 0], joint_reward=io["pose_metrics"][:, 1])
+        if self._pose_term is not None:      # the code of the (last) step, 0 .. 7, split into its bits
+            code = io["pose_fail"].to(torch.int32)
+            m.update(pose_fail=(code != 0).float(), pose_fail_pos=(code & 1).float(), pose_fail_quat=((code >> 1) & 1).float(),
+                     pose_fail_joint=((code >> 2) & 1).float())
         return state.replace(pipeline_state=PipelineState(**st, **(out or {})), obs=obs, reward=io["reward"], done=io["done"], metrics=m, info=info)
 
     def unroll_wrapped(self, state: State, actions: torch.Tensor, episode_length: float) -> State:

@@ -7,6 +7,7 @@ fallback: if the shared library is missing or no GPU is present the calls raise.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from typing import Dict, Optional
 
@@ -54,6 +55,11 @@ class RRPoseIO(C.Structure):
                 ("joint_reward_weight", C.c_float), ("joint_reward_scale", C.c_float)]
 
 
+class RRPoseTermIO(C.Structure):
+    """`rr_pose_term_io`, the pose-termination block a batch carries next to its pose block (`rr_batch_set_pose_termination`)."""
+    _fields_ = [("fail", C.c_void_p), ("max_pos", C.c_float), ("max_quat", C.c_float), ("max_joint", C.c_float), ("pad", C.c_int32)]
+
+
 class RRUnrollIO(C.Structure):
     _fields_ = [("first", RRState), ("first_obs", C.c_void_p), ("prev_done", C.c_void_p), ("steps_in", C.c_void_p), ("steps_out", C.c_void_p),
                 ("truncation_out", C.c_void_p), ("episode_length", C.c_float)]
@@ -85,7 +91,7 @@ class RRPpoCfg(C.Structure):
 
 
 EXPORTS = ["rr_model_load", "rr_model_dims", "rr_model_set_solver", "rr_model_set_solver_type", "rr_model_destroy", "rr_model_table", "rr_kernarg_layout", "rr_batch_create",
-           "rr_batch_destroy", "rr_pipeline_init", "rr_pipeline_step", "rr_env_step", "rr_env_reset", "rr_pipeline_step_to", "rr_env_step_to", "rr_batch_contact_overflow", "rr_batch_bad_states", "rr_batch_unroll_supported", "rr_env_unroll", "rr_env_unroll_policy", "rr_batch_eval_supported", "rr_env_unroll_eval", "rr_batch_pose_supported", "rr_batch_set_pose", "rr_batch_set_reference_obs", "rr_batch_obs_width", "rr_batch_reference_obs_supported",
+           "rr_batch_destroy", "rr_pipeline_init", "rr_pipeline_step", "rr_env_step", "rr_env_reset", "rr_pipeline_step_to", "rr_env_step_to", "rr_batch_contact_overflow", "rr_batch_bad_states", "rr_batch_unroll_supported", "rr_env_unroll", "rr_env_unroll_policy", "rr_batch_eval_supported", "rr_env_unroll_eval", "rr_batch_pose_supported", "rr_batch_set_pose", "rr_batch_set_reference_obs", "rr_batch_obs_width", "rr_batch_reference_obs_supported", "rr_batch_set_pose_termination", "rr_batch_pose_termination_supported",
            "rr_compute_gae", "rr_mlp_forward", "rr_ppo_loss_workspace_bytes", "rr_ppo_loss", "rr_policy_act_workspace_bytes", "rr_policy_act", "rr_policy_sample", "rr_policy_backward_workspace_bytes", "rr_policy_backward", "rr_mlp_silu_backward_workspace_bytes", "rr_mlp_silu_backward", "rr_mlp_value_backward_workspace_bytes", "rr_mlp_policy_backward", "rr_mlp_policy_backward_workspace_bytes", "rr_mlp_value_backward", "rr_mlp_weight_grad_workspace_bytes", "rr_mlp_weight_grad", "rr_mlp_weight_grad_batch_workspace_bytes", "rr_mlp_weight_grad_batch", "rr_obs_moments_workspace_bytes", "rr_obs_moments", "rr_wrap_episode_autoreset", "rr_debug_layout", "rr_batch_set_schedule", "rr_batch_set_env_params", "rr_batch_env_params_supported", "rr_batch_set_profile", "rr_batch_set_ls_repeat_exit", "rr_batch_set_solver_trim", "rr_batch_set_solver_batch", "rr_batch_set_solve_resident", "rr_model_solve_resident_switch", "rr_batch_set_timing", "rr_batch_kernel_time", "rr_last_error"]
 
 _lib = None
@@ -177,6 +183,8 @@ def lib():
         L.rr_batch_obs_width.argtypes = [C.c_void_p]
         L.rr_batch_obs_width.restype = C.c_int32
         L.rr_batch_reference_obs_supported.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
+        L.rr_batch_set_pose_termination.argtypes = [C.c_void_p, C.POINTER(RRPoseTermIO)]
+        L.rr_batch_pose_termination_supported.argtypes = [C.c_void_p, C.c_int32]
         L.rr_batch_set_ls_repeat_exit.argtypes = [C.c_void_p, C.c_int32]
         L.rr_batch_set_solver_trim.argtypes = [C.c_void_p, C.c_int32]
         L.rr_batch_set_solver_batch.argtypes = [C.c_void_p, C.c_int32]
@@ -282,6 +290,7 @@ class Batch:
         self.dims = model.dims
         self.h = C.c_void_p()
         self._pose = None           # the tensors of the pose block in force (set_pose)
+        self._pterm = None          # the tensor of the pose-termination block in force (set_pose_termination)
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream().cuda_stream
         _check(lib().rr_batch_create(model.h, self.N, self.device.index or 0, C.c_void_p(stream), C.byref(self.h)))
@@ -341,6 +350,9 @@ class Batch:
         e.terminate_when_unhealthy = int(env.get("terminate_when_unhealthy", True))
         e.bad_state_max = float(env.get("bad_state_max") or 0.0)      # 0 = no bad-state check
         # pose tracking rides on the batch, not in rr_env_io: the env-io dict decides what the launch about to be issued sees
+        fail = env.get("pose_fail")         # pose termination rides there too: the code array [N] and `pose_termination` = the three thresholds
+        if fail is None and self._pterm is not None:        # cleared BEFORE the pose block may go: the library keeps the pose block while it stands
+            self.set_pose_termination(None)
         pose = env.get("track_pose")
         if pose is not None:        # [T, nq - 3] rows (quaternion, joints), or [C, T, nq - 3] next to a [C, T, 3] track_pos
             if tuple(pose.shape) != tuple(tp.shape[:-1]) + (d.nq - 3,):
@@ -348,6 +360,8 @@ class Batch:
             self.set_pose(pose, env.get("pose_metrics"), env.get("quat_reward", (1.0, 2.0)), env.get("joint_reward", (1.0, 0.5)))
         elif self._pose is not None:        # (refused while the batch carries reference frames: their launches all carry track_pose)
             self.set_pose(None)
+        if fail is not None:
+            self.set_pose_termination(fail, env.get("pose_termination", (math.inf, math.inf, math.inf)))
         return e
 
     # ------------------------------------------------------------------ C-ABI calls
@@ -492,6 +506,26 @@ class Batch:
         p = RRPoseIO(_ptr(track_pose), _ptr(pose_metrics, numel=2 * self.N), *quat_reward, *joint_reward)
         _check(lib().rr_batch_set_pose(self.h, C.byref(p)))
         self._pose = (track_pose, pose_metrics)
+
+    def set_pose_termination(self, fail: Optional[torch.Tensor], thresholds=(math.inf, math.inf, math.inf)):
+        """The pose-termination block of this batch's later env steps (C ABI `rr_batch_set_pose_termination`): `fail` [N] out, the code
+        of each env's step as a float 0 .. 7; `thresholds` = (max_pos, max_quat, max_joint), each > 0, inf = that criterion off; None
+        clears it.  Needs the pose block (`set_pose`).  The env-io dict of a launch (`pose_fail`, `pose_termination` keys) sets or clears
+        it by itself.  The batch keeps the tensor alive."""
+        if fail is None:
+            _check(lib().rr_batch_set_pose_termination(self.h, None))
+            self._pterm = None
+            return
+        t = RRPoseTermIO(_ptr(fail, numel=self.N), *(float(x) for x in thresholds), 0)
+        _check(lib().rr_batch_set_pose_termination(self.h, C.byref(t)))
+        self._pterm = fail
+
+    def pose_termination_supported(self, with_actor: bool = False) -> Optional[str]:
+        """None when this batch serves pose termination at its frame count (C ABI `rr_batch_pose_termination_supported`) -- with
+        `with_actor` also in the one-launch rollout with the actor inside -- else the refusal's text."""
+        if _check(lib().rr_batch_pose_termination_supported(self.h, int(with_actor))) == 1:
+            return None
+        return lib().rr_last_error().decode()
 
     def pose_supported(self) -> Optional[str]:
         """None when this batch serves pose tracking (`set_pose`; C ABI `rr_batch_pose_supported`), else the refusal's text."""

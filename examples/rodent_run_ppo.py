@@ -63,6 +63,12 @@ def main():
     ap.add_argument("--reference-frames", type=int, default=0, metavar="H", help="with --track-pose: the observation also carries the clip's next "
                     "H frames (Rodent(reference_obs_frames=H), 0 .. 16): next positions in the root frame, relative orientations, joint-angle "
                     "differences.  Up to 5 the rollout stays one launch; above that it is collected per step")
+    ap.add_argument("--max-pos-error", type=float, default=None, metavar="M", help="with --track-pose: end an episode whose root is more than M metres "
+                    "from the clip's (Rodent(max_pos_error=M)); a termination, not a truncation.  Off by default")
+    ap.add_argument("--max-quat-error", type=float, default=None, metavar="RAD", help="with --track-pose: ... whose root orientation is more than RAD "
+                    "radians from the clip's (Rodent(max_quat_error=RAD))")
+    ap.add_argument("--max-joint-error", type=float, default=None, metavar="RAD", help="with --track-pose: ... whose joint angles are more than RAD "
+                    "radians (2-norm over the joints) from the clip's (Rodent(max_joint_error=RAD))")
     ap.add_argument("--policy-width", type=int, choices=(32, 256), default=32, help="units per hidden layer of the policy network; both "
                     "widths run on the hand-written learner kernels (256: per-step rollouts, the in-kernel actor is 32-wide)")
     ap.add_argument("--policy-depth", type=int, default=4, help="hidden layers of the policy network (1 .. 7 for the hand-written kernels; "
@@ -85,6 +91,11 @@ def main():
         ap.error("--track-pose: the step kernel's pose instances read no per-env parameters; drop --randomize")
     if args.reference_frames and not args.track_pose:
         ap.error("--reference-frames: the frames are rows of the reference pose; add --track-pose")
+    for flag in ("max_pos_error", "max_quat_error", "max_joint_error"):
+        if getattr(args, flag) is not None and not args.track_pose:
+            ap.error(f"--{flag.replace('_', '-')}: the errors are taken against the reference pose; add --track-pose")
+        if getattr(args, flag) is not None and not getattr(args, flag) > 0:
+            ap.error(f"--{flag.replace('_', '-')}: must be > 0")
     if not 0 <= args.reference_frames <= 16:
         ap.error("--reference-frames: 0 .. 16")
     clips = None                                     # the loaded ReferenceClip(s), [C, T, ...] fields; None for a .npy track or the synthetic line
@@ -116,7 +127,8 @@ def main():
         config["env_name"], track_pos=track_pos, terminate_when_unhealthy=config["terminate_when_unhealthy"],
         solver=config["solver"], iterations=config["iterations"], ls_iterations=config["ls_iterations"],
         vision=config["vision"], num_envs=args.envs_per_gpu, xml_path=args.xml, device=f"cuda:{local_rank}",
-        bad_state_max=args.bad_state_max, reference_obs_frames=args.reference_frames, **pose)
+        bad_state_max=args.bad_state_max, reference_obs_frames=args.reference_frames, max_pos_error=args.max_pos_error,
+        max_quat_error=args.max_quat_error, max_joint_error=args.max_joint_error, **pose)
 
     train_fn = functools.partial(
         ppo.train, num_timesteps=config["num_timesteps"], num_evals=int(config["num_timesteps"] / config["eval_every"]),

@@ -303,6 +303,34 @@ int rr_batch_set_reference_obs(rr_batch* b, int32_t frames);
 int32_t rr_batch_obs_width(const rr_batch* b);
 int rr_batch_reference_obs_supported(const rr_batch* b, int32_t frames, int32_t with_actor);
 
+/* Pose termination: an env step whose pose has strayed from the clip ends the episode.  The block is set on the BATCH, next to the pose
+ * block it needs (rr_env_io and rr_pose_io are closed), and read by every later env step of it -- rr_env_step(_to), rr_env_unroll and
+ * rr_env_unroll_policy -- until it is replaced or cleared (NULL; a batch starts without one); a launch takes `fail` as it is when it is
+ * issued.  An env step (never a reset) compares the stepped qpos with the row of the clip and frame its position and pose rewards read:
+ *   e_pos   = |qpos[:3] - track_pos[c][f]|_2
+ *   e_quat  = theta of rr_pose_io               (2 atan2(|d.xyz|, |d.w|), d = conj(r_q) (x) q)
+ *   e_joint = sqrt(sum_i (qpos[7+i] - r_j,i)^2)
+ *   code = 1 (e_pos > max_pos) | 2 (e_quat > max_quat) | 4 (e_joint > max_joint);   fail[e] = (float)code;   done = max(done, code != 0)
+ * +INFINITY switches a criterion off (x > inf is false); a NaN error sets no bit (bad_state_max ends such a step).  The failing step
+ * changes nothing but done: reward, metrics, pose_metrics, cur_frame, obs and the state are what they are without the block, and the
+ * rule does not ask terminate_when_unhealthy.  A bad step stores code 0 next to its done = 1.  In the multi-step forms the code enters
+ * the env's done before the Episode and AutoReset wrappers: a pose failure is a termination -- truncation 0, traj_discount 0, the first
+ * state and first observation restored -- and steps_out counts from there.  rr_env_reset ignores the block.
+ * rr_batch_set_pose_termination: no pose block on the batch (rr_batch_set_pose first), a NULL fail, or a threshold that is NaN or <= 0:
+ * RR_EINVAL; RR_EUNSUPPORTED with the reason wherever pose tracking is unsupported.  While the block is set, rr_batch_set_pose(b, NULL)
+ * is RR_EINVAL (clear this block first), and what refuses a pose block refuses here: rr_env_unroll_eval, per-env parameters, the debug
+ * dump, contact-geometry outputs and the profile build.  The env steps run the reference-observation instances' code whatever the frame
+ * count (0 .. 16), so rr_env_unroll_policy serves rows of up to 1664 entries.
+ * rr_batch_pose_termination_supported(b, with_actor): 1 / 0 -- whether the batch serves the block with its current frame count
+ * (with_actor != 0: also in rr_env_unroll_policy); with 0 rr_last_error holds the reason.  It does not need the pose block to be set. */
+typedef struct rr_pose_term_io {
+  float* fail;            /* [N] out: the code as a float, 0 .. 7 */
+  float max_pos, max_quat, max_joint;
+  int32_t pad;
+} rr_pose_term_io;
+int rr_batch_set_pose_termination(rr_batch* b, const rr_pose_term_io* term);
+int rr_batch_pose_termination_supported(const rr_batch* b, int32_t with_actor);
+
 /* Generalised advantage estimation of one PPO minibatch, the reverse scan of brax.training.agents.ppo.losses.compute_gae
  * [UP; SURVEY.md Appendix E], one thread per trajectory.  All arrays time-major [T][B] device float32; bootstrap [B];
  * outputs vs [T][B] and advantages [T][B].  `stream` is a hipStream_t (NULL = default stream). */
