@@ -59,8 +59,27 @@ struct rr_model {
 // One function maps (model, launch form, variant) to the kernel instance that serves it, or to the reason there is none: launch(),
 // the support queries and the attribute loop of rr_batch_create all ask it, so none of them can disagree about what exists.
 enum Form { F_STEP, F_UNROLL, F_ACTOR, F_EVAL, N_FORMS };                        // single step | multi-step | ... with the actor | evaluation
-enum Variant { V_PROD, V_DEBUG, V_PROFILE, V_RAND, V_PAIR, V_POSE, V_MATLDS, V_REFOBS, V_POSETERM, N_VARIANTS }; // production | debug dump | cycle-stamp profile | per-env parameters | two-wave pair | pose tracking | production, inverse factor read from LDS | pose tracking with the reference observation | ... and with pose termination
+enum Variant { V_PROD, V_DEBUG, V_PROFILE, V_RAND, V_PAIR, V_POSE, V_MATLDS, V_REFOBS, V_POSETERM, V_TWOSLOT, N_VARIANTS }; // production | debug dump | cycle-stamp profile | per-env parameters | two-wave pair | pose tracking | production, inverse factor read from LDS | pose tracking with the reference observation | ... and with pose termination | production, tree phases on the plain lane <-> body map
 struct Instance { kern_t kern; const char* why = nullptr; bool fixed = false; };      // why: the reason when kern is null (multi-step forms: with the entry point that reports it); fixed: compiled for the model's dimensions
+
+// The shape the root-slot tree phases need beyond the dimensions (rr_kernel.h Wave::ROOT): one tree; body 1 is the child of the world and
+// holds the model's only free joint, on qpos[0 .. 6] and dofs 0 .. 5; its subtree is every body; at most two bodies beyond the 64 lanes.
+static bool root_slot_ok(const rr_model* m) {
+  const int nbody = m->dims.nbody, njnt = m->dims.njnt;
+  if (m->kd.nroot != 1 || nbody < 2 || nbody - RR_LANES > 2) return false;
+  const int32_t* bi = (const int32_t*)m->find("k_body_i")->data;
+  const int32_t* ji = (const int32_t*)m->find("k_jnt_i")->data;
+  if ((int)m->find("k_body_i")->count < RR_BODYI * nbody || (int)m->find("k_jnt_i")->count < 4 * njnt) return false;
+  const int32_t* r = bi + RR_BODYI;      // parent, jadr, jn, dofadr, dofnum, root, .., .., depth, sib, last
+  if (r[0] != 0 || r[2] != 1 || r[3] != 0 || r[4] != 6 || r[10] != nbody - 1 || r[1] < 0 || r[1] >= njnt) return false;
+  if (ji[4 * r[1]] != 0 || ji[4 * r[1] + 1] != 0 || ji[4 * r[1] + 2] != 0) return false;
+  for (int j = 0; j < njnt; ++j) if (j != r[1] && ji[4 * j] == 0) return false;
+  for (int b = 2; b < nbody; ++b) if (bi[RR_BODYI * b] < 1) return false;
+  return true;
+}
+// the fixed-dimension instances of the rodent_optimized dimensions serve this model: the dimensions match, and where those instances
+// run the root-slot tree phases (RR_ROOT_SLOT) the model has the shape for them; a model that has not runs the generic instances
+static bool rodent_fixed(const rr_model* m) { return RRDimsRodent::matches(m->kd) && (!rr_root_slot<RRDimsRodent>::value || root_slot_ok(m)); }
 
 static Instance select(const rr_model* m, Form form, Variant v) {
   const bool s111 = m->NBS == 1 && m->NVS == 1 && m->NCS == 1, s221 = m->NBS == 2 && m->NVS == 2 && m->NCS == 1, s332 = m->NBS == 3 && m->NVS == 3 && m->NCS == 2;
@@ -68,14 +87,20 @@ static Instance select(const rr_model* m, Form form, Variant v) {
   const char *no_diag = "no diagnostic kernel instance for this model", *no_slots = "no kernel instance for this model's slot counts";
   auto no = [](const char* why) { return Instance{nullptr, why}; };
   // rr_step_kernel<NBS, NVS, NCS, PROF, DBG, dims, NEWTON, UNROLL, ACTOR, PAIR, DYN>, rr_rand_kernel<dims, UNROLL, ACTOR>, rr_eval_kernel<dims, DYN>,
-  // rr_pose_kernel<dims, UNROLL, ACTOR>, rr_refobs_kernel<dims, UNROLL, ACTOR>, rr_poseterm_kernel<dims, UNROLL, ACTOR>, rr_matlds_kernel<dims>
+  // rr_pose_kernel<dims, UNROLL, ACTOR>, rr_refobs_kernel<dims, UNROLL, ACTOR>, rr_poseterm_kernel<dims, UNROLL, ACTOR>, rr_matlds_kernel<dims>, rr_twoslot_kernel<dims>
   if (v == V_PAIR && (unroll || newton || !RRDimsRodentNew::matches(m->kd_rep))) return no("no two-wave pair instance for this model / launch form");
   if (v == V_PAIR) return {rr_step_kernel<2, 2, 1, false, false, RRDimsRodentNew, false, false, false, true>, nullptr, true};      // one replica = the rodent_new dims
   if (v == V_MATLDS) {      // rr_batch_set_solve_resident(b, 0): the production single-step instance of the benchmark model's dimensions, solves from LDS
-    if (newton || m->dyn || m->pair_ok || !s221 || !RRDimsRodent::matches(m->kd))
+    if (newton || m->dyn || m->pair_ok || !s221 || !rodent_fixed(m))
       return no("rr_batch_set_solve_resident: only the fixed-dimension CG instance of the rodent_optimized dimensions has a form that solves from LDS");
     if (unroll) return no("rr_batch_set_solve_resident(b, 0): the instance that solves from LDS is single-step; no multi-step, actor or evaluation launch on this batch");
     return {rr_matlds_kernel<RRDimsRodent>, nullptr, true};
+  }
+  if (v == V_TWOSLOT) {      // rr_batch_set_root_slot(b, 0): the production single-step instance of the benchmark model, tree phases on the plain map
+    if (newton || m->dyn || m->pair_ok || !s221 || !rodent_fixed(m))
+      return no("rr_batch_set_root_slot: only the fixed-dimension CG instance of the rodent_optimized model runs the tree phases with the root body in a slot of its own");
+    if (unroll) return no("rr_batch_set_root_slot(b, 0): the instance with the plain lane-to-body map is single-step; no multi-step, actor or evaluation launch on this batch");
+    return {rr_twoslot_kernel<RRDimsRodent>, nullptr, true};
   }
   // Eligibility first.  Multi-step instances: the single-rodent floor-contact models (fixed-dimension or generic) and the candidate-pair models
   // (DYN, generic dimensions), CG only, no diagnostics.  None for the Newton solver, the two-wave pair instance and other slot counts.
@@ -116,7 +141,7 @@ static Instance select(const rr_model* m, Form form, Variant v) {
   // Single step besides production: debug dump (generic dims; selected per launch when rr_outputs.debug is given), cycle-stamp profile
   // (diagnostic, rodent dims or generic 2,2,1)
   if (v == V_PROFILE && (newton || !s221)) return no(no_diag);
-  if (v == V_PROFILE) return RRDimsRodent::matches(m->kd) ? Instance{rr_step_kernel<2, 2, 1, true, false, RRDimsRodent>, nullptr, true} : Instance{rr_step_kernel<2, 2, 1, true, false, RRDims>};
+  if (v == V_PROFILE) return rodent_fixed(m) ? Instance{rr_step_kernel<2, 2, 1, true, false, RRDimsRodent>, nullptr, true} : Instance{rr_step_kernel<2, 2, 1, true, false, RRDims>};
   if (newton)     // Newton: the (2,2,1) generic instances only (rr_model_set_solver_type checks)
     return Instance{v == V_DEBUG ? rr_step_kernel<2, 2, 1, false, true, RRDims, true> : rr_step_kernel<2, 2, 1, false, false, RRDims, true>};
   if (v == V_DEBUG)
@@ -131,7 +156,7 @@ static Instance select(const rr_model* m, Form form, Variant v) {
     if (v == V_POSETERM) return actor ? rr_poseterm_kernel<DT, true, true> : (unroll ? rr_poseterm_kernel<DT, true> : rr_poseterm_kernel<DT>);
     return actor ? rr_step_kernel<2, 2, 1, false, false, DT, false, true, true> : (unroll ? rr_step_kernel<2, 2, 1, false, false, DT, false, true> : rr_step_kernel<2, 2, 1, false, false, DT>);
   };
-  if (RRDimsRodent::matches(m->kd)) return {family((RRDimsRodent*)nullptr), nullptr, true};      // fixed-dimension instances (rr_kernel.h RRDimsFixed)
+  if (rodent_fixed(m)) return {family((RRDimsRodent*)nullptr), nullptr, true};      // fixed-dimension instances (rr_kernel.h RRDimsFixed)
   if (RRDimsRodentNew::matches(m->kd)) return {family((RRDimsRodentNew*)nullptr), nullptr, true};
   return Instance{family((RRDims*)nullptr)};
 }
@@ -374,6 +399,7 @@ struct rr_batch {
   int ref_frames = 0;                   // reference frames in every observation row (rr_batch_set_reference_obs); > 0 only with a pose block
   int obs_width() const { return m->dims.obs_dim + ref_frames * m->dims.nq; }      // of obs, first_obs, traj_obs, obs_in, mean, std, w0's rows
   rr_pose_term_io pterm = {};           // pose termination of the env steps (rr_batch_set_pose_termination); fail null: off; set only with a pose block
+  bool plain_slots = false;             // rr_batch_set_root_slot(b, 0): production single-step launches run rr_twoslot_kernel
   bool solve_lds = false;               // rr_batch_set_solve_resident(b, 0): production single-step launches run rr_matlds_kernel
   bool has_env_params() const { return env_dof_f || env_act_f || env_con_f; }
 };
@@ -672,6 +698,11 @@ static int launch(rr_batch* b, const Launch& L) {
   if (b->solve_lds) {      // rr_batch_set_solve_resident(b, 0): production launches only, and select() refuses the multi-step forms
     if (v != V_PROD) return fail(RR_EUNSUPPORTED, "launch: rr_batch_set_solve_resident(b, 0) serves production launches only (no debug dump, contact-geometry outputs, profile build, per-env parameters or pose tracking on this batch)");
     v = V_MATLDS;
+  }
+  if (b->plain_slots) {      // rr_batch_set_root_slot(b, 0): production launches only, and select() refuses the multi-step forms
+    if (b->solve_lds) return fail(RR_EUNSUPPORTED, "launch: rr_batch_set_root_slot(b, 0) and rr_batch_set_solve_resident(b, 0) select different comparison instances; one of the two per batch");
+    if (v != V_PROD) return fail(RR_EUNSUPPORTED, "launch: rr_batch_set_root_slot(b, 0) serves production launches only (no debug dump, contact-geometry outputs, profile build, per-env parameters or pose tracking on this batch)");
+    v = V_TWOSLOT;
   }
   const Instance in = select(m, L.ev ? F_EVAL : (L.ac ? F_ACTOR : (L.un ? F_UNROLL : F_STEP)), v);
   if (!in.kern) return fail(RR_EUNSUPPORTED, std::string(L.un ? "" : "launch: ") + in.why);
@@ -1475,6 +1506,21 @@ extern "C" int rr_batch_set_solve_resident(rr_batch* b, int32_t enable) {
     if (rc) return rc;
   }
   b->solve_lds = enable == 0;
+  return RR_OK;
+}
+
+extern "C" int rr_model_root_slot_switch(const rr_model* m) {
+  if (!m) return fail(RR_EINVAL, "rr_model_root_slot_switch: null model");
+  const Instance in = select(m, F_STEP, V_TWOSLOT);
+  return in.kern ? RR_OK : fail(RR_EUNSUPPORTED, in.why);
+}
+extern "C" int rr_batch_set_root_slot(rr_batch* b, int32_t enable) {
+  if (!b) return fail(RR_EINVAL, "rr_batch_set_root_slot: null batch");
+  if (!enable) {
+    const int rc = rr_model_root_slot_switch(b->m);
+    if (rc) return rc;
+  }
+  b->plain_slots = enable == 0;
   return RR_OK;
 }
 

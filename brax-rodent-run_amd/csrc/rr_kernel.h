@@ -53,6 +53,9 @@
 #ifndef RR_SOLVE_MAT_RESIDENT
 #define RR_SOLVE_MAT_RESIDENT 1   // the M-half inverse-factor entries of this lane's solve jobs are read once per substep and held in registers (Wave::mres_c / mres_r; bit-identical results)
 #endif
+#ifndef RR_ROOT_SLOT
+#define RR_ROOT_SLOT 1        // models of one free-jointed root and <= 66 bodies: the 64 other bodies fill body slot 0, the root stands alone in slot 1 (Wave::ROOT; bit-identical results)
+#endif
 #ifndef RR_LS_STAGE_ONCE
 #define RR_LS_STAGE_ONCE 1    // the line search's compacted row positions and its D values are staged once per substep (Wave::ls_stage; bit-identical results)
 #endif
@@ -144,6 +147,11 @@ struct RRDimsFixed : RRDims {
   }
 };
 typedef RRDimsFixed<66, 59, 1263> RRDimsRodent;       // rodent_optimized.xml (the benchmark model)
+// ROOT SLOT (RR_ROOT_SLOT; Wave::ROOT): which dims types run the tree phases with the root body alone in the second body slot.  The
+// dimensions alone do not say that a model has the shape this needs; the host checks the rest against the blob (rr_api.hip root_slot_ok)
+// before it selects an instance of such a type.
+template <class DT> struct rr_root_slot { static constexpr bool value = false; };
+template <> struct rr_root_slot<RRDimsFixed<66, 59, 1263>> { static constexpr bool value = RR_ROOT_SLOT != 0; };
 typedef RRDimsFixed<67, 57, 1279> RRDimsRodentNew;    // rodent_new.xml (the env's default model [REF Rodent_Env_Brax.py:16]) == one replica of rodent_pair.xml
 
 // Table pointers carry the global address space in their type, so every table access is a global_load (never flat).
@@ -527,8 +535,15 @@ template <class A> struct rr_same<A, A> { static constexpr bool value = true; };
 // dump paths leave no room for them)
 // MRES: how much of the inverse factor this instance may hold in registers next to them (RR_SOLVE_MAT_RESIDENT; Wave::MAT_RES): 0 nothing,
 // 1 the entries of its column jobs, 2 those of its column and row jobs.  Chosen per entry point by its register figures.
-template <int NBS, int NVS, int NCS, class DT, bool NEWTON = false, bool PAIR = false, bool DYN = false, bool RAND = false, bool JRES = true, int MRES = 0>
+// ROOT (RR_ROOT_SLOT; rr_root_slot<DT>): the lane <-> body map of the tree phases for a model of ONE tree whose root (body 1, child of the
+// world) holds the model's only free joint and that has at most 66 bodies.  Slot 0 then holds the 64 bodies that are not the root -- lanes
+// 2 .. 63 their own number, lanes 0 and 1 bodies 64 and 65 -- and slot 1 the root alone, on lane 1.  Every body stays on the lane it has
+// under the plain map b = lane + 64 s, so the per-lane partial sums of the subtree COM stand where they stood.  Slot 0's code then carries
+// no free-joint branch; slot 1's carries no hinge, no pointer-doubling round (the root has no ancestor) and no table read (its joint is
+// qpos[0 .. 6], its dofs 0 .. 5: host-checked), and its subtree sum is spread over 16 lanes (backward_sweep).
+template <int NBS, int NVS, int NCS, class DT, bool NEWTON = false, bool PAIR = false, bool DYN = false, bool RAND = false, bool JRES = true, int MRES = 0, bool ROOT = false>
 struct Wave {
+  static_assert(!ROOT || (NBS == 2 && !PAIR && !DYN), "ROOT: one-tree models of 65 or 66 bodies");
   const DT& D;
   RRLoopTables TL;
   int renv = 0;           // RAND: the environment whose parameter rows this wave reads (wave-uniform; re-derived with `lane`)
@@ -553,7 +568,7 @@ struct Wave {
   static constexpr int WC = NCS * RR_LANES;
 
   // ---- model constants held in registers for the whole launch (loaded once, reused by all substeps)
-  BodyC bc0, bc1;         // constants of bodies `lane` (slot 0) and `lane + 64` (slot 1); further slots are loaded at use
+  BodyC bc0, bc1;         // constants of bodies `lane` (slot 0) and `lane + 64` (slot 1); further slots are loaded at use (ROOT: of body_at(0); bc1 unused)
   int banc[NBS][2];       // 2^k-th ancestors of the slot's body, k = 0..7, one byte each (0 = none)
   int blast[NBS];         // last body of the subtree (bodies are in DFS order)
   int dofc0[NVS], dofc1[NVS];   // packed per-dof constants: depth | kind<<8 | root<<12 | body<<16 | parent-of-body<<24 ; Madr | last_desc<<16
@@ -687,6 +702,11 @@ struct Wave {
   // T[b] <- T[anc_k(b)] o T[b], anc_{k+1} = anc_k o anc_k (ancestor tables in registers), all bodies busy every
   // round, instead of one serial step per tree level (38-39 of them, a handful of active lanes each).
   // Joint anchors / axes are kept in the parent frame (raw, in the cdof cells) and mapped to the world in com_pos.
+  // the body of this lane in slot s (0: none)
+  __device__ __forceinline__ int body_at(int s) const {
+    if constexpr (ROOT) return s == 0 ? (lane < 2 ? lane + RR_LANES : lane) : (lane == 1 ? 1 : 0);
+    else return lane + RR_LANES * s;
+  }
   __device__ __forceinline__ BodyC bodyc(const RRTables& T, int s) const { return s == 0 ? bc0 : (s == 1 ? bc1 : load_bodyc(T, lane + RR_LANES * s, D.nbody)); }
   // k is a run-time round counter: select the word instead of indexing the register array (a dynamic index would
   // push the whole object into scratch memory)
@@ -696,7 +716,19 @@ struct Wave {
     const RRTables T = tables();
 #pragma unroll
     for (int s = 0; s < NBS; ++s) {
-      const int b = lane + RR_LANES * s;
+      const int b = body_at(s);
+      if (ROOT && s == 1) {      // the root: its pose is the free joint's coordinates, qpos[0 .. 6]
+        if (b == 1) {
+          float quat[4];
+#pragma unroll
+          for (int k = 0; k < 4; ++k) quat[k] = s_qpos[3 + k];
+          quat_normalize(quat);
+          st3(s_xpos + 3, ld3(s_qpos));
+#pragma unroll
+          for (int k = 0; k < 4; ++k) s_xquat[4 + k] = quat[k];
+        }
+        continue;
+      }
       if (s > 0 && !__any(b < D.nbody)) continue;
       const BodyC c = bodyc(T, s);
       if (b >= 1 && b < D.nbody) {
@@ -719,7 +751,7 @@ struct Wave {
             jt = ji[0]; qa = ji[1]; da = ji[2]; q0 = jf[6];
             jp = ld3(jf); ja = ld3(jf + 3);
           }
-          if (jt == 0) {  // free joint: the pose is the generalised coordinate itself (parent = world)
+          if (!ROOT && jt == 0) {  // free joint: the pose is the generalised coordinate itself (parent = world)
             pos = ld3(s_qpos + qa);
 #pragma unroll
             for (int k = 0; k < 4; ++k) quat[k] = s_qpos[qa + 3 + k];
@@ -751,8 +783,8 @@ struct Wave {
       float np[NBS][3], nq[NBS][4];
       bool upd[NBS];
 #pragma unroll
-      for (int s = 0; s < NBS; ++s) {
-        const int b = lane + RR_LANES * s;
+      for (int s = 0; s < (ROOT ? 1 : NBS); ++s) {      // ROOT: the root has no ancestor
+        const int b = body_at(s);
         const int a = anc_at(s, k);
         upd[s] = b >= 1 && b < D.nbody && a != 0;
         if (upd[s]) {
@@ -767,9 +799,9 @@ struct Wave {
       }
       sync();
 #pragma unroll
-      for (int s = 0; s < NBS; ++s) {
+      for (int s = 0; s < (ROOT ? 1 : NBS); ++s) {
         if (upd[s]) {
-          const int b = lane + RR_LANES * s;
+          const int b = body_at(s);
           st3(s_xpos + 3 * b, mk3(np[s][0], np[s][1], np[s][2]));
 #pragma unroll
           for (int i = 0; i < 4; ++i) s_xquat[4 * b + i] = nq[s][i];
@@ -779,7 +811,7 @@ struct Wave {
     }
 #pragma unroll
     for (int s = 0; s < NBS; ++s) {   // xquat is kept normalised, as the reference does per body
-      const int b = lane + RR_LANES * s;
+      const int b = body_at(s);
       if (b >= 1 && b < D.nbody) {
         float q[4];
 #pragma unroll
@@ -798,8 +830,11 @@ struct Wave {
     float acc[2][3] = {{0, 0, 0}, {0, 0, 0}};
     float xip[NBS][3];
 #pragma unroll
-    for (int s = 0; s < NBS; ++s) {
-      const int b = lane + RR_LANES * s;
+    for (int s_ = 0; s_ < NBS; ++s_) {
+      // ROOT: slot 1 first, so that lane 1 adds the root's term and then body 65's, the order of the plain map (the += is a fused
+      // multiply-add: the order of the two terms decides the rounding)
+      const int s = ROOT ? NBS - 1 - s_ : s_;
+      const int b = body_at(s);
       xip[s][0] = xip[s][1] = xip[s][2] = 0;
       if (b >= 1 && b < D.nbody) {
         auto bf = row_at(T.body_f, 18, b);
@@ -821,7 +856,7 @@ struct Wave {
     }
 #pragma unroll
     for (int s = 0; s < NBS; ++s) {
-      const int b = lane + RR_LANES * s;
+      const int b = body_at(s);
       if (b >= 1 && b < D.nbody) {
         auto bf = row_at(T.body_f, 18, b);
         float q[4], bq[4], iq[4], R[9];
@@ -888,8 +923,8 @@ struct Wave {
       float add[NBS][6];
       bool upd[NBS];
 #pragma unroll
-      for (int s = 0; s < NBS; ++s) {
-        const int b = lane + RR_LANES * s;
+      for (int s = 0; s < (ROOT ? 1 : NBS); ++s) {      // ROOT: the root has no ancestor
+        const int b = body_at(s);
         const int a = anc_at(s, k);
         upd[s] = b >= 1 && b < D.nbody && a != 0;
         if (upd[s]) {
@@ -899,9 +934,9 @@ struct Wave {
       }
       sync();
 #pragma unroll
-      for (int s = 0; s < NBS; ++s) {
+      for (int s = 0; s < (ROOT ? 1 : NBS); ++s) {
         if (upd[s]) {
-          const int b = lane + RR_LANES * s;
+          const int b = body_at(s);
 #pragma unroll
           for (int i = 0; i < 6; ++i) arr[6 * b + i] += add[s][i];
         }
@@ -916,7 +951,20 @@ struct Wave {
     // own contribution of every body
 #pragma unroll
     for (int s = 0; s < NBS; ++s) {
-      const int b = lane + RR_LANES * s;
+      const int b = body_at(s);
+      if (ROOT && s == 1) {      // the root: dofs 0 .. 5
+        if (b == 1) {
+          float v[6] = {0, 0, 0, 0, 0, 0};
+          for (int k = 0; k < 6; ++k) {
+            const float qv = s_qvel[k];
+#pragma unroll
+            for (int i = 0; i < 6; ++i) v[i] += s_cdof[6 * k + i] * qv;
+          }
+#pragma unroll
+          for (int i = 0; i < 6; ++i) s_cvel[6 + i] = v[i];
+        }
+        continue;
+      }
       if (s > 0 && !__any(b < D.nbody)) continue;
       const BodyC c = bodyc(T, s);
       if (b >= 1 && b < D.nbody) {
@@ -935,15 +983,18 @@ struct Wave {
     // cdof_dot (lane-local) -> own acceleration contribution
 #pragma unroll
     for (int s = 0; s < NBS; ++s) {
-      const int b = lane + RR_LANES * s;
-      if (s > 0 && !__any(b < D.nbody)) continue;
-      const BodyC c = bodyc(T, s);
+      const int b = body_at(s);
+      if (ROOT && s == 1 && b != 1) continue;
+      if (!ROOT && s > 0 && !__any(b < D.nbody)) continue;
+      BodyC c;
+      if (ROOT && s == 1) { c.parent = 0; c.dofadr = 0; c.dofnum = 6; c.jn = 1; c.jtype0 = 0; }      // the root: child of the world, dofs 0 .. 5
+      else c = bodyc(T, s);
       if (b >= 1 && b < D.nbody) {
         const int p = c.parent, da = c.dofadr, dn = c.dofnum;
         float v[6], a[6] = {0, 0, 0, 0, 0, 0};
 #pragma unroll
         for (int k = 0; k < 6; ++k) v[k] = s_cvel[6 * p + k];
-        const bool is_free = c.jn > 0 && c.jtype0 == 0;
+        const bool is_free = ROOT ? s == 1 : (c.jn > 0 && c.jtype0 == 0);
         if (is_free) {
           for (int k = 0; k < 3; ++k) {
             const float qv = s_qvel[da + k];
@@ -972,7 +1023,7 @@ struct Wave {
     // body forces: cfrc = I (cacc - g) + cvel x* (I cvel)
 #pragma unroll
     for (int s = 0; s < NBS; ++s) {
-      const int b = lane + RR_LANES * s;
+      const int b = body_at(s);
       if (b >= 1 && b < D.nbody) {
         float v[6], a[6], t[6], t1[6], t2[6];
 #pragma unroll
@@ -1015,8 +1066,8 @@ struct Wave {
     sync();
     float acc[NBS][16];
 #pragma unroll
-    for (int s = 0; s < NBS; ++s) {
-      const int b = lane + RR_LANES * s;
+    for (int s = 0; s < (ROOT ? 1 : NBS); ++s) {
+      const int b = body_at(s);
 #pragma unroll
       for (int k = 0; k < 16; ++k) acc[s][k] = 0.0f;
       if (b >= 1 && b < D.nbody) {
@@ -1042,16 +1093,34 @@ struct Wave {
         }
       }
     }
+    // ROOT: the root's range is the whole tree, bodies [1, nbody).  One lane would walk it in 16 steps of 16 additions, alone in its slot;
+    // lanes 0 .. 15 take one of the 16 components each and make the same additions in the same order: the head bodies up to the first
+    // block boundary, the whole blocks, the tail bodies.
+    float racc = 0.0f;
+    if constexpr (ROOT) {
+      if (lane < 16) {
+        const bool ci = lane < 10;                                    // components 0 .. 9: cinert, 10 .. 15: cfrc
+        const float* one = ci ? s_cinert + lane : s_cfrc + (lane - 10);
+        const int st = ci ? 10 : 6;
+        int d = 1;
+        for (; d < BS && d < D.nbody; ++d) racc += one[st * d];
+        for (; d + BS <= D.nbody; d += BS) racc += s_buf[2 * d + lane];
+        for (; d < D.nbody; ++d) racc += one[st * d];
+      }
+    }
     sync();
 #pragma unroll
-    for (int s = 0; s < NBS; ++s) {
-      const int b = lane + RR_LANES * s;
+    for (int s = 0; s < (ROOT ? 1 : NBS); ++s) {
+      const int b = body_at(s);
       if (b >= 1 && b < D.nbody) {
 #pragma unroll
         for (int k = 0; k < 10; ++k) s_crb[10 * b + k] = acc[s][k];
 #pragma unroll
         for (int k = 0; k < 6; ++k) s_cfrc[6 * b + k] = acc[s][10 + k];
       }
+    }
+    if constexpr (ROOT) {
+      if (lane < 16) *(lane < 10 ? s_crb + 10 + lane : s_cfrc + 6 + (lane - 10)) = racc;
     }
     sync();
   }
@@ -2740,6 +2809,7 @@ template <int NBS, int NVS, int NCS, bool PROF, bool DBG, class DT, bool NEWTON 
 __global__ __launch_bounds__((PAIR ? 2 : 1) * RR_LANES, (NVS >= 3 ? 1 : 2)) void rr_step_kernel(const RRDims Dk, const RRTables Tk, const RRIO io_kernarg, const int num_envs,
                                                            const int n_frames) {
   constexpr bool RAND = false, EVAL = false, POSE = false, REFOBS = false, PTERM = false;
+  constexpr bool ROOTSLOT = rr_root_slot<DT>::value && NBS == 2 && !NEWTON && !PAIR && !DYN;      // the root body alone in the second body slot (Wave::ROOT)
   constexpr int MRES = ACTOR ? 1 : 2;      // resident inverse-factor entries (Wave::MAT_RES): both sides at 245-253 registers (timed: -1.4 % against the column side alone); with the actor the column side (233)
 #include "rr_step_body.inc"
 }
@@ -2750,6 +2820,7 @@ __global__ __launch_bounds__(RR_LANES, 2) void rr_rand_kernel(const RRDims Dk, c
   constexpr int NBS = 2, NVS = 2, NCS = 1;
   constexpr bool PROF = false, DBG = false, NEWTON = false, PAIR = false, DYN = false, RAND = true, EVAL = false, POSE = false, REFOBS = false, PTERM = false;
   constexpr int MRES = 1;      // resident inverse-factor entries (Wave::MAT_RES): the column side (229-237 registers; both sides reach the cap of 256 here)
+  constexpr bool ROOTSLOT = rr_root_slot<DT>::value;
 #include "rr_step_body.inc"
 }
 // Evaluation (rr_env_unroll_eval): the multi-step form with the actor inside as brax's Evaluator and the launcher's evaluation rollout
@@ -2762,6 +2833,7 @@ __global__ __launch_bounds__(RR_LANES, 2) void rr_eval_kernel(const RRDims Dk, c
   constexpr int NBS = 2, NVS = 2, NCS = 1;
   constexpr bool PROF = false, DBG = false, NEWTON = false, PAIR = false, RAND = false, UNROLL = true, ACTOR = true, EVAL = true, POSE = false, REFOBS = false, PTERM = false;
   constexpr int MRES = 1;      // resident inverse-factor entries (Wave::MAT_RES): the column side (229-237 registers; both sides reach the cap of 256 here)
+  constexpr bool ROOTSLOT = rr_root_slot<DT>::value;
 #include "rr_step_body.inc"
 }
 // Pose tracking (rr_batch_set_pose, rr_pose_io): the env epilogue also rewards the clip's root orientation and joint angles (RRIO, POSE TRACKING).
@@ -2773,6 +2845,7 @@ __global__ __launch_bounds__(RR_LANES, 2) void rr_pose_kernel(const RRDims Dk, c
   constexpr int NBS = 2, NVS = 2, NCS = 1;
   constexpr bool PROF = false, DBG = false, NEWTON = false, PAIR = false, DYN = false, RAND = false, EVAL = false, POSE = true, REFOBS = false, PTERM = false;
   constexpr int MRES = 1;      // resident inverse-factor entries (Wave::MAT_RES): the column side (229-237 registers; both sides reach the cap of 256 here)
+  constexpr bool ROOTSLOT = rr_root_slot<DT>::value;
 #include "rr_step_body.inc"
 }
 // Reference observation (rr_batch_set_reference_obs): the pose instances with the clip's next frames appended to every observation row
@@ -2784,6 +2857,7 @@ __global__ __launch_bounds__(RR_LANES, 2) void rr_refobs_kernel(const RRDims Dk,
   constexpr int NBS = 2, NVS = 2, NCS = 1;
   constexpr bool PROF = false, DBG = false, NEWTON = false, PAIR = false, DYN = false, RAND = false, EVAL = false, POSE = true, REFOBS = true, PTERM = false;
   constexpr int MRES = 1;      // resident inverse-factor entries (Wave::MAT_RES): the column side, as in rr_pose_kernel
+  constexpr bool ROOTSLOT = rr_root_slot<DT>::value;
 #include "rr_step_body.inc"
 }
 // Pose termination (rr_batch_set_pose_termination): the reference-observation instances with the env step's done raised where the stepped
@@ -2796,6 +2870,7 @@ __global__ __launch_bounds__(RR_LANES, 2) void rr_poseterm_kernel(const RRDims D
   constexpr int NBS = 2, NVS = 2, NCS = 1;
   constexpr bool PROF = false, DBG = false, NEWTON = false, PAIR = false, DYN = false, RAND = false, EVAL = false, POSE = true, REFOBS = true, PTERM = true;
   constexpr int MRES = 1;      // resident inverse-factor entries (Wave::MAT_RES): the column side, as in rr_pose_kernel
+  constexpr bool ROOTSLOT = rr_root_slot<DT>::value;
 #include "rr_step_body.inc"
 }
 // The production single-step instance with the inverse factor's entries left in LDS (MRES 0), whatever RR_SOLVE_MAT_RESIDENT says: the other
@@ -2804,6 +2879,17 @@ __global__ __launch_bounds__(RR_LANES, 2) void rr_poseterm_kernel(const RRDims D
 template <class DT>
 __global__ __launch_bounds__(RR_LANES, 2) void rr_matlds_kernel(const RRDims Dk, const RRTables Tk, const RRIO io_kernarg, const int num_envs, const int n_frames) {
   constexpr int NBS = 2, NVS = 2, NCS = 1, MRES = 0;
+  constexpr bool ROOTSLOT = rr_root_slot<DT>::value;
+  constexpr bool PROF = false, DBG = false, NEWTON = false, UNROLL = false, ACTOR = false, PAIR = false, DYN = false, RAND = false, EVAL = false, POSE = false, REFOBS = false, PTERM = false;
+#include "rr_step_body.inc"
+}
+// The production single-step instance with the tree phases on the plain lane <-> body map b = lane + 64 s (Wave::ROOT off), whatever
+// RR_ROOT_SLOT says: the other arm of an exact A/B inside one library (rr_batch_set_root_slot(b, 0); tests/test_gpu_root_slot.py).  An
+// entry of its own so that the instances of the other seven keep their code.
+template <class DT>
+__global__ __launch_bounds__(RR_LANES, 2) void rr_twoslot_kernel(const RRDims Dk, const RRTables Tk, const RRIO io_kernarg, const int num_envs, const int n_frames) {
+  constexpr int NBS = 2, NVS = 2, NCS = 1, MRES = 2;
+  constexpr bool ROOTSLOT = false;
   constexpr bool PROF = false, DBG = false, NEWTON = false, UNROLL = false, ACTOR = false, PAIR = false, DYN = false, RAND = false, EVAL = false, POSE = false, REFOBS = false, PTERM = false;
 #include "rr_step_body.inc"
 }

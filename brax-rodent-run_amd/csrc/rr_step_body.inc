@@ -1,6 +1,6 @@
 // rr_step_body.inc -- the body of the step kernel, included by each of its __global__ entries in rr_kernel.h (rr_step_kernel,
-// rr_rand_kernel, rr_eval_kernel, rr_pose_kernel, rr_refobs_kernel, rr_poseterm_kernel, rr_matlds_kernel).  In scope where it is included: the kernel's five arguments (Dk, Tk, io_kernarg, num_envs, n_frames) and the
-// compile-time switches NBS, NVS, NCS, PROF, DBG, DT, NEWTON, UNROLL, ACTOR, PAIR, DYN, RAND, EVAL, POSE, REFOBS, PTERM, MRES.
+// rr_rand_kernel, rr_eval_kernel, rr_pose_kernel, rr_refobs_kernel, rr_poseterm_kernel, rr_matlds_kernel, rr_twoslot_kernel).  In scope where it is included: the kernel's five arguments (Dk, Tk, io_kernarg, num_envs, n_frames) and the
+// compile-time switches NBS, NVS, NCS, PROF, DBG, DT, NEWTON, UNROLL, ACTOR, PAIR, DYN, RAND, EVAL, POSE, REFOBS, PTERM, MRES, ROOTSLOT.
 // Why text and not a function: see the note above rr_step_kernel.
   static_assert(!PAIR || (!PROF && !DBG && !NEWTON && !UNROLL && !ACTOR), "PAIR: production physics instance only");
   static_assert(!DYN || (!PROF && !DBG && !NEWTON && !PAIR), "DYN: production instances only (single-step, multi-step, multi-step with the actor)");
@@ -16,7 +16,7 @@
   // LDS -- checked on the HOST for every instance a batch may launch (rr_batch_create: hipFuncGetAttributes().sharedSizeBytes == 0)
   const DT D(Dk);
   const int wrep = PAIR ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0;
-  Wave<NBS, NVS, NCS, DT, NEWTON, PAIR, DYN, RAND, !DBG, MRES> w(D, Tk, PAIR ? lds + wrep * (D.lds_bytes_rep >> 2) : lds);
+  Wave<NBS, NVS, NCS, DT, NEWTON, PAIR, DYN, RAND, !DBG, MRES, ROOTSLOT> w(D, Tk, PAIR ? lds + wrep * (D.lds_bytes_rep >> 2) : lds);
   int lane = threadIdx.x & (RR_LANES - 1);
   if (PAIR) { w.rep = wrep; w.s_xc = lds + 2 * (D.lds_bytes_rep >> 2); }
   RRIO io = load_io();
@@ -122,11 +122,12 @@
     {
       const RRTables T = w.tables();
       const int ol = opaque(lane);
-      w.bc0 = load_bodyc(T, ol, D.nbody);
-      if (NBS > 1) w.bc1 = load_bodyc(T, ol + RR_LANES, D.nbody);
+      // ROOTSLOT (Wave::ROOT): slot 0 holds bodies 64 and 65 on lanes 0 and 1; the root, alone in slot 1, needs none of these
+      w.bc0 = load_bodyc(T, ROOTSLOT && ol < 2 ? ol + RR_LANES : ol, D.nbody);
+      if (NBS > 1 && !ROOTSLOT) w.bc1 = load_bodyc(T, ol + RR_LANES, D.nbody);
 #pragma unroll
-      for (int s = 0; s < NBS; ++s) {
-        const int b = ol + RR_LANES * s;
+      for (int s = 0; s < (ROOTSLOT ? 1 : NBS); ++s) {
+        const int b = ROOTSLOT && ol < 2 ? ol + RR_LANES : ol + RR_LANES * s;
         const bool ok = b >= 1 && b < D.nbody;
         w.banc[s][0] = ok ? row_at(T.body_anc, 2, b)[0] : 0;
         w.banc[s][1] = ok ? row_at(T.body_anc, 2, b)[1] : 0;

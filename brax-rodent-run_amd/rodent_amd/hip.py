@@ -92,7 +92,7 @@ class RRPpoCfg(C.Structure):
 
 EXPORTS = ["rr_model_load", "rr_model_dims", "rr_model_set_solver", "rr_model_set_solver_type", "rr_model_destroy", "rr_model_table", "rr_kernarg_layout", "rr_batch_create",
            "rr_batch_destroy", "rr_pipeline_init", "rr_pipeline_step", "rr_env_step", "rr_env_reset", "rr_pipeline_step_to", "rr_env_step_to", "rr_batch_contact_overflow", "rr_batch_bad_states", "rr_batch_unroll_supported", "rr_env_unroll", "rr_env_unroll_policy", "rr_batch_eval_supported", "rr_env_unroll_eval", "rr_batch_pose_supported", "rr_batch_set_pose", "rr_batch_set_reference_obs", "rr_batch_obs_width", "rr_batch_reference_obs_supported", "rr_batch_set_pose_termination", "rr_batch_pose_termination_supported",
-           "rr_compute_gae", "rr_mlp_forward", "rr_ppo_loss_workspace_bytes", "rr_ppo_loss", "rr_policy_act_workspace_bytes", "rr_policy_act", "rr_policy_sample", "rr_policy_backward_workspace_bytes", "rr_policy_backward", "rr_mlp_silu_backward_workspace_bytes", "rr_mlp_silu_backward", "rr_mlp_value_backward_workspace_bytes", "rr_mlp_policy_backward", "rr_mlp_policy_backward_workspace_bytes", "rr_mlp_value_backward", "rr_mlp_weight_grad_workspace_bytes", "rr_mlp_weight_grad", "rr_mlp_weight_grad_batch_workspace_bytes", "rr_mlp_weight_grad_batch", "rr_obs_moments_workspace_bytes", "rr_obs_moments", "rr_wrap_episode_autoreset", "rr_debug_layout", "rr_batch_set_schedule", "rr_batch_set_env_params", "rr_batch_env_params_supported", "rr_batch_set_profile", "rr_batch_set_ls_repeat_exit", "rr_batch_set_solver_trim", "rr_batch_set_solver_batch", "rr_batch_set_solve_resident", "rr_model_solve_resident_switch", "rr_batch_set_timing", "rr_batch_kernel_time", "rr_last_error"]
+           "rr_compute_gae", "rr_mlp_forward", "rr_ppo_loss_workspace_bytes", "rr_ppo_loss", "rr_policy_act_workspace_bytes", "rr_policy_act", "rr_policy_sample", "rr_policy_backward_workspace_bytes", "rr_policy_backward", "rr_mlp_silu_backward_workspace_bytes", "rr_mlp_silu_backward", "rr_mlp_value_backward_workspace_bytes", "rr_mlp_policy_backward", "rr_mlp_policy_backward_workspace_bytes", "rr_mlp_value_backward", "rr_mlp_weight_grad_workspace_bytes", "rr_mlp_weight_grad", "rr_mlp_weight_grad_batch_workspace_bytes", "rr_mlp_weight_grad_batch", "rr_obs_moments_workspace_bytes", "rr_obs_moments", "rr_wrap_episode_autoreset", "rr_debug_layout", "rr_batch_set_schedule", "rr_batch_set_env_params", "rr_batch_env_params_supported", "rr_batch_set_profile", "rr_batch_set_ls_repeat_exit", "rr_batch_set_solver_trim", "rr_batch_set_solver_batch", "rr_batch_set_solve_resident", "rr_model_solve_resident_switch", "rr_batch_set_root_slot", "rr_model_root_slot_switch", "rr_batch_set_timing", "rr_batch_kernel_time", "rr_last_error"]
 
 _lib = None
 
@@ -190,6 +190,8 @@ def lib():
         L.rr_batch_set_solver_batch.argtypes = [C.c_void_p, C.c_int32]
         L.rr_batch_set_solve_resident.argtypes = [C.c_void_p, C.c_int32]
         L.rr_model_solve_resident_switch.argtypes = [C.c_void_p]
+        L.rr_batch_set_root_slot.argtypes = [C.c_void_p, C.c_int32]
+        L.rr_model_root_slot_switch.argtypes = [C.c_void_p]
         L.rr_batch_set_timing.argtypes = [C.c_void_p, C.c_int32]
         L.rr_batch_kernel_time.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
         _lib = L
@@ -267,6 +269,11 @@ class Model:
         """Raise, with the words `Batch.set_solve_resident(False)` would be refused with, unless this model has the instance that
         switch selects (C ABI `rr_model_solve_resident_switch`; needs no device)."""
         _check(lib().rr_model_solve_resident_switch(self.h))
+
+    def check_root_slot_switch(self):
+        """Raise, with the words `Batch.set_root_slot(False)` would be refused with, unless this model has the instance that switch
+        selects (C ABI `rr_model_root_slot_switch`; needs no device)."""
+        _check(lib().rr_model_root_slot_switch(self.h))
 
     def __del__(self):
         try:
@@ -586,6 +593,12 @@ class Batch:
         factor's entries from LDS in every solve instead of holding them in registers for the substep (C ABI
         `rr_batch_set_solve_resident`).  Same results bit for bit; rodent_optimized dimensions with the CG solver only.  Default True."""
         _check(lib().rr_batch_set_solve_resident(self.h, int(enable)))
+
+    def set_root_slot(self, enable: bool):
+        """A/B switch for tests: False makes the batch's production single-step launches run the instance whose tree phases use the plain
+        map body = lane + 64 * slot instead of the root body in a slot of its own (C ABI `rr_batch_set_root_slot`).  Same results bit
+        for bit; the rodent_optimized model with the CG solver only.  Default True."""
+        _check(lib().rr_batch_set_root_slot(self.h, int(enable)))
 
     def set_timing(self, enable: bool):
         _check(lib().rr_batch_set_timing(self.h, int(enable)))

@@ -558,6 +558,19 @@ int rr_batch_set_solve_resident(rr_batch* b, int32_t enable);
  * rr_last_error (needs no device). */
 int rr_model_solve_resident_switch(const rr_model* m);
 
+/* A/B switch of the production code, for tests: for a model of one tree whose root body holds the only free joint and that has at most
+ * two bodies beyond the 64 lanes (rodent_optimized), the fixed-dimension instances run the tree phases with the 64 other bodies in the
+ * first body slot and the root alone in the second (rr_kernel.h RR_ROOT_SLOT).  enable = 0 makes the batch's production single-step
+ * launches (rr_pipeline_step, rr_env_step and their _to forms) run the same instance built with the plain map body = lane + 64 * slot,
+ * so that a test can compare the two bit for bit.  Only for such a model with the CG solver (RR_EUNSUPPORTED otherwise); while it is
+ * off, multi-step, actor and evaluation launches and every launch that needs another instance (debug dump, contact geometry, profile,
+ * per-env parameters, pose tracking) are refused, and so is a launch with rr_batch_set_solve_resident(b, 0) on the same batch.
+ * Default 1. */
+int rr_batch_set_root_slot(rr_batch* b, int32_t enable);
+/* RR_OK where rr_batch_set_root_slot(b, 0) would be accepted on a batch of this model, else its error code with its words in
+ * rr_last_error (needs no device). */
+int rr_model_root_slot_switch(const rr_model* m);
+
 /* ms of the most recent step-kernel launches on this batch measured with hipEvents on its stream
  * (enable with rr_batch_set_timing(b,1); each launch is then bracketed by events) */
 int rr_batch_set_timing(rr_batch* b, int32_t enable);
