@@ -59,7 +59,7 @@ struct rr_model {
 // One function maps (model, launch form, variant) to the kernel instance that serves it, or to the reason there is none: launch(),
 // the support queries and the attribute loop of rr_batch_create all ask it, so none of them can disagree about what exists.
 enum Form { F_STEP, F_UNROLL, F_ACTOR, F_EVAL, N_FORMS };                        // single step | multi-step | ... with the actor | evaluation
-enum Variant { V_PROD, V_DEBUG, V_PROFILE, V_RAND, V_PAIR, V_POSE, V_MATLDS, V_REFOBS, V_POSETERM, V_TWOSLOT, N_VARIANTS }; // production | debug dump | cycle-stamp profile | per-env parameters | two-wave pair | pose tracking | production, inverse factor read from LDS | pose tracking with the reference observation | ... and with pose termination | production, tree phases on the plain lane <-> body map
+enum Variant { V_PROD, V_DEBUG, V_PROFILE, V_RAND, V_PAIR, V_POSE, V_MATLDS, V_REFOBS, V_POSETERM, V_TWOSLOT, V_BODY, N_VARIANTS }; // production | debug dump | cycle-stamp profile | per-env parameters | two-wave pair | pose tracking | production, inverse factor read from LDS | pose tracking with the reference observation | ... and with pose termination | production, tree phases on the plain lane <-> body map | pose tracking with the body-position terms (a superset of the pose-termination form)
 struct Instance { kern_t kern; const char* why = nullptr; bool fixed = false; };      // why: the reason when kern is null (multi-step forms: with the entry point that reports it); fixed: compiled for the model's dimensions
 
 // The shape the root-slot tree phases need beyond the dimensions (rr_kernel.h Wave::ROOT): one tree; body 1 is the child of the world and
@@ -87,7 +87,7 @@ static Instance select(const rr_model* m, Form form, Variant v) {
   const char *no_diag = "no diagnostic kernel instance for this model", *no_slots = "no kernel instance for this model's slot counts";
   auto no = [](const char* why) { return Instance{nullptr, why}; };
   // rr_step_kernel<NBS, NVS, NCS, PROF, DBG, dims, NEWTON, UNROLL, ACTOR, PAIR, DYN>, rr_rand_kernel<dims, UNROLL, ACTOR>, rr_eval_kernel<dims, DYN>,
-  // rr_pose_kernel<dims, UNROLL, ACTOR>, rr_refobs_kernel<dims, UNROLL, ACTOR>, rr_poseterm_kernel<dims, UNROLL, ACTOR>, rr_matlds_kernel<dims>, rr_twoslot_kernel<dims>
+  // rr_pose_kernel<dims, UNROLL, ACTOR>, rr_refobs_kernel<dims, UNROLL, ACTOR>, rr_poseterm_kernel<dims, UNROLL, ACTOR>, rr_body_kernel<dims, UNROLL, ACTOR>, rr_matlds_kernel<dims>, rr_twoslot_kernel<dims>
   if (v == V_PAIR && (unroll || newton || !RRDimsRodentNew::matches(m->kd_rep))) return no("no two-wave pair instance for this model / launch form");
   if (v == V_PAIR) return {rr_step_kernel<2, 2, 1, false, false, RRDimsRodentNew, false, false, false, true>, nullptr, true};      // one replica = the rodent_new dims
   if (v == V_MATLDS) {      // rr_batch_set_solve_resident(b, 0): the production single-step instance of the benchmark model's dimensions, solves from LDS
@@ -115,8 +115,10 @@ static Instance select(const rr_model* m, Form form, Variant v) {
     if (v == V_POSE) return no("rr_env_unroll_eval: no evaluation instance rewards the pose (this env io carries track_pose); evaluate step by step");
     if (v == V_REFOBS) return no("rr_env_unroll_eval: no evaluation instance writes the reference observation (rr_batch_set_reference_obs is on); evaluate step by step");
     if (v == V_POSETERM) return no("rr_env_unroll_eval: no evaluation instance ends episodes on the pose error (rr_batch_set_pose_termination is on); evaluate step by step");
-  } else if (v == V_POSE || v == V_REFOBS || v == V_POSETERM) {
-    // Pose tracking (rr_pose_kernel; with the reference observation rr_refobs_kernel; with pose termination rr_poseterm_kernel): the same
+    if (v == V_BODY) return no("rr_env_unroll_eval: no evaluation instance rewards the body positions (rr_batch_set_body_tracking is on); evaluate step by step");
+  } else if (v == V_POSE || v == V_REFOBS || v == V_POSETERM || v == V_BODY) {
+    // Pose tracking (rr_pose_kernel; with the reference observation rr_refobs_kernel; with pose termination rr_poseterm_kernel; with the
+    // body-position terms rr_body_kernel): the same
     // models and launch forms as the per-env parameters below, shared tables
     if (m->dyn) return no("pose tracking: models with candidate-pair contacts (DYN instances) have no pose instance");
     if (m->pair_ok) return no("pose tracking: two-tree models served by the two-wave pair instance have no pose instance");
@@ -154,6 +156,7 @@ static Instance select(const rr_model* m, Form form, Variant v) {
     if (v == V_POSE) return actor ? rr_pose_kernel<DT, true, true> : (unroll ? rr_pose_kernel<DT, true> : rr_pose_kernel<DT>);
     if (v == V_REFOBS) return actor ? rr_refobs_kernel<DT, true, true> : (unroll ? rr_refobs_kernel<DT, true> : rr_refobs_kernel<DT>);
     if (v == V_POSETERM) return actor ? rr_poseterm_kernel<DT, true, true> : (unroll ? rr_poseterm_kernel<DT, true> : rr_poseterm_kernel<DT>);
+    if (v == V_BODY) return actor ? rr_body_kernel<DT, true, true> : (unroll ? rr_body_kernel<DT, true> : rr_body_kernel<DT>);
     return actor ? rr_step_kernel<2, 2, 1, false, false, DT, false, true, true> : (unroll ? rr_step_kernel<2, 2, 1, false, false, DT, false, true> : rr_step_kernel<2, 2, 1, false, false, DT>);
   };
   if (rodent_fixed(m)) return {family((RRDimsRodent*)nullptr), nullptr, true};      // fixed-dimension instances (rr_kernel.h RRDimsFixed)
@@ -400,6 +403,7 @@ struct rr_batch {
   int obs_width() const { return m->dims.obs_dim + ref_frames * m->dims.nq; }      // of obs, first_obs, traj_obs, obs_in, mean, std, w0's rows
   rr_pose_term_io pterm = {};           // pose termination of the env steps (rr_batch_set_pose_termination); fail null: off; set only with a pose block
   bool plain_slots = false;             // rr_batch_set_root_slot(b, 0): production single-step launches run rr_twoslot_kernel
+  rr_body_io body = {};                 // body tracking of the env steps (rr_batch_set_body_tracking); track_bodies null: off; set only with a pose block
   bool solve_lds = false;               // rr_batch_set_solve_resident(b, 0): production single-step launches run rr_matlds_kernel
   bool has_env_params() const { return env_dof_f || env_act_f || env_con_f; }
 };
@@ -580,7 +584,7 @@ static int check_actor(const char* who, const rr_actor_io* a, bool traj) {
 }
 // What the in-kernel actor cannot serve, or null.  ac null: the limits on the model alone (rr_batch_eval_supported).  ref_frames: of the
 // batch; the actor of the selected instance reads 64 x JM entries of the row (rr_actor_step: 1280, REFOBS instances 1664).  wide: the
-// launch runs a REFOBS instance whatever ref_frames is (pose termination)
+// launch runs a REFOBS instance whatever ref_frames is (pose termination, body tracking)
 static const char* actor_limit(const rr_model* m, const rr_actor_io* ac, int ref_frames = 0, bool wide = false) {
   static_assert(RR_ACTOR_JM == 20 && RR_ACTOR_JM_REFOBS == 26, "the two texts below name 64 x JM");
   if ((ref_frames > 0 || wide) && m->dims.obs_dim + ref_frames * m->dims.nq > 64 * RR_ACTOR_JM_REFOBS)
@@ -626,7 +630,7 @@ static int fill_io(const Launch& L, RRIO& io) {
 // launch() step 3: the fields of the multi-step forms -- wrappers' state, actor, evaluation, pacing
 static int fill_unroll(rr_batch* b, const Launch& L, RRIO& io) {
   if (const rr_actor_io* ac = L.ac) {
-    if (const char* limit = actor_limit(b->m, ac, io.ref_frames, io.pose_fail != nullptr)) return fail(RR_EUNSUPPORTED, limit);
+    if (const char* limit = actor_limit(b->m, ac, io.ref_frames, io.pose_fail != nullptr || io.track_bodies != nullptr)) return fail(RR_EUNSUPPORTED, limit);
     io.a_obs_in = ac->obs_in; io.a_mean = ac->mean; io.a_std = ac->std; io.a_W0 = ac->w0; io.a_b0 = ac->b0;
     for (int l = 1; l < ac->nhidden; ++l) { io.a_Wt[l - 1] = ac->hidden_wt[l - 1]; io.a_b[l - 1] = ac->hidden_b[l - 1]; }
     io.a_Wth = ac->head_wt; io.a_bh = ac->head_b; io.a_noise = ac->noise; io.a_actions = ac->actions_out; io.ctrl = ac->actions_out;
@@ -682,7 +686,15 @@ static int launch(rr_batch* b, const Launch& L) {
   // pose termination (rr_batch_set_pose_termination): env steps only -- a reset has no done to raise and stays on the variant it uses
   // without the block -- served by the PTERM instance, which is a REFOBS instance for every frame count, 0 included
   const bool pterm = b->pterm.fail && b->pose.track_pose && L.env && L.mode == 1;
+  // body tracking (rr_batch_set_body_tracking): env steps only, as pose termination; served by the BODY instance, a superset of the PTERM
+  // instance: without a termination block it gets a null pose_fail and thresholds that no error exceeds
+  const bool body = b->body.track_bodies && b->pose.track_pose && L.env && L.mode == 1;
   if (refobs) io.ref_frames = b->ref_frames;
+  if (body) {
+    io.track_bodies = b->body.track_bodies; io.body_weights = b->body.body_weights; io.body_metrics = b->body.body_metrics;
+    io.body_w = b->body.body_reward_weight; io.body_k = b->body.body_reward_scale; io.endeff_w = b->body.endeff_reward_weight; io.endeff_k = b->body.endeff_reward_scale;
+    io.pose_max_pos = io.pose_max_quat = io.pose_max_joint = INFINITY;
+  }
   if (pterm) { io.pose_fail = b->pterm.fail; io.pose_max_pos = b->pterm.max_pos; io.pose_max_quat = b->pterm.max_quat; io.pose_max_joint = b->pterm.max_joint; }
   if (pose) {
     io.track_pose = b->pose.track_pose; io.pose_metrics = b->pose.pose_metrics;
@@ -691,7 +703,7 @@ static int launch(rr_batch* b, const Launch& L) {
   }
   if (pose && params) return fail(RR_EUNSUPPORTED, "launch: pose tracking: no pose instance reads per-env parameters (this batch carries some)");
   if (pose && (io.dbg || geom || b->prof)) return fail(RR_EUNSUPPORTED, "launch: pose tracking: no debug dump, contact-geometry outputs or profile build with track_pose (diagnostic instances have no pose form)");
-  Variant v = b->prof ? V_PROFILE : ((io.dbg || geom) ? V_DEBUG : (params ? V_RAND : (pterm ? V_POSETERM : (refobs ? V_REFOBS : (pose ? V_POSE : V_PROD)))));
+  Variant v = b->prof ? V_PROFILE : ((io.dbg || geom) ? V_DEBUG : (params ? V_RAND : (body ? V_BODY : (pterm ? V_POSETERM : (refobs ? V_REFOBS : (pose ? V_POSE : V_PROD))))));
   // two-tree model, physics only, no diagnostics: one wavefront per replica (rr_kernel.h PAIR)
   const bool pair = m->pair_ok && v == V_PROD && !L.env && !L.out && !L.un && !b->env_map && !b->cost && m->solver != 2;
   if (pair) v = V_PAIR;
@@ -779,7 +791,7 @@ extern "C" int rr_env_unroll_policy(rr_batch* b, const rr_state* in, const rr_st
 }
 extern "C" int rr_batch_eval_supported(const rr_batch* b) {
   if (!b) return fail(RR_EINVAL, "rr_batch_eval_supported: null batch");
-  const Variant v = b->prof ? V_PROFILE : (b->has_env_params() ? V_RAND : (b->pterm.fail ? V_POSETERM : (b->ref_frames > 0 ? V_REFOBS : V_PROD)));
+  const Variant v = b->prof ? V_PROFILE : (b->has_env_params() ? V_RAND : (b->body.track_bodies ? V_BODY : (b->pterm.fail ? V_POSETERM : (b->ref_frames > 0 ? V_REFOBS : V_PROD))));
   return (select(b->m, F_EVAL, v).kern && !actor_limit(b->m, nullptr)) ? 1 : 0;
 }
 extern "C" int rr_env_unroll_eval(rr_batch* b, const rr_state* in, const rr_state* outst, int32_t num_steps, int32_t n_frames, const rr_env_io* env,
@@ -1374,6 +1386,7 @@ extern "C" int rr_batch_set_pose(rr_batch* b, const rr_pose_io* p) {
   if (!b) return fail(RR_EINVAL, "rr_batch_set_pose: null batch");
   if (!p || (!p->track_pose && !p->pose_metrics)) {
     if (b->ref_frames > 0) return fail(RR_EINVAL, "rr_batch_set_pose: the batch carries reference frames (rr_batch_set_reference_obs), whose rows come from the pose block: set them to 0 first");
+    if (b->body.track_bodies) return fail(RR_EINVAL, "rr_batch_set_pose: the batch carries a body-tracking block (rr_batch_set_body_tracking), whose rows are indexed like the pose block's: clear it first");
     if (b->pterm.fail) return fail(RR_EINVAL, "rr_batch_set_pose: the batch carries a pose-termination block (rr_batch_set_pose_termination), whose errors come from the pose block: clear it first");
     b->pose = rr_pose_io{};
     return RR_OK;
@@ -1433,6 +1446,32 @@ extern "C" int rr_batch_set_pose_termination(rr_batch* b, const rr_pose_term_io*
   for (float x : {t->max_pos, t->max_quat, t->max_joint})
     if (!(x > 0.0f)) return fail(RR_EINVAL, "rr_batch_set_pose_termination: thresholds must be > 0 and not NaN (INFINITY switches a criterion off)");
   b->pterm = *t;
+  return RR_OK;
+}
+// Body tracking: wherever pose tracking is served, at the batch's frame count; with_actor also asks the width the actor of the
+// reference-observation instances reads
+static const char* body_limit(const rr_batch* b, bool with_actor) {
+  const Instance in = select(b->m, with_actor ? F_ACTOR : F_STEP, V_BODY);
+  if (!in.kern) return in.why;
+  if (b->has_env_params()) return "pose tracking: no pose instance reads per-env parameters (this batch carries some)";
+  if (b->prof) return "pose tracking: no profile build with track_pose";
+  return with_actor ? actor_limit(b->m, nullptr, b->ref_frames, true) : nullptr;
+}
+extern "C" int rr_batch_body_tracking_supported(const rr_batch* b, int32_t with_actor) {
+  if (!b) return fail(RR_EINVAL, "rr_batch_body_tracking_supported: null batch");
+  const char* why = body_limit(b, with_actor != 0);
+  if (why) (void)fail(RR_EUNSUPPORTED, std::string("rr_batch_body_tracking_supported: ") + why);
+  return why ? 0 : 1;
+}
+extern "C" int rr_batch_set_body_tracking(rr_batch* b, const rr_body_io* t) {
+  if (!b) return fail(RR_EINVAL, "rr_batch_set_body_tracking: null batch");
+  if (!t) { b->body = rr_body_io{}; return RR_OK; }
+  if (const char* why = body_limit(b, false)) return fail(RR_EUNSUPPORTED, std::string("rr_batch_set_body_tracking: ") + why);
+  if (!b->pose.track_pose) return fail(RR_EINVAL, "rr_batch_set_body_tracking: needs a pose block (rr_batch_set_pose) first: track_bodies is indexed like track_pose");
+  if (!t->track_bodies || !t->body_weights || !t->body_metrics) return fail(RR_EINVAL, "rr_batch_set_body_tracking: null track_bodies, body_weights or body_metrics");
+  for (float x : {t->body_reward_weight, t->body_reward_scale, t->endeff_reward_weight, t->endeff_reward_scale})
+    if (!(x >= 0.0f) || !std::isfinite(x)) return fail(RR_EINVAL, "rr_batch_set_body_tracking: weights and scales must be finite and >= 0");
+  b->body = *t;
   return RR_OK;
 }
 extern "C" int32_t rr_batch_obs_width(const rr_batch* b) {

@@ -296,6 +296,22 @@ struct RRIO {
   float* pose_fail;            // [N]
   float pose_max_pos, pose_max_quat, pose_max_joint;
   int pterm_pad;               // keeps sizeof(RRIO) a multiple of 8 (RRKArgs)
+  // BODY TRACKING (BODY instances, rr_body_kernel; no other instance reads these): the clip's global body positions next to its pose.
+  // track_bodies is [T][nbody][3] (with `clip` set [num_clips][T][nbody][3]), indexed by the clip and frame the position and pose rewards
+  // read; body_weights is [2][nbody], row 0 the 0 / 1 mask of the tracked bodies B, row 1 that of the end effectors E (entry 0, the
+  // world, is not read).  With xpos the body positions of the step's LAST FORWARD PASS (the pose before the last substep's integration,
+  // what rr_outputs.xpos holds) and r the row:
+  //   S_B = sum_{b in B} |xpos[b] - r[b]|^2,  S_E = the same over E        (every product and sum rounded on its own, ascending b per lane)
+  //   body_reward = body_w exp(-body_k S_B),  endeff_reward = endeff_w exp(-endeff_k S_E)
+  //   reward = (((plain reward + quat_reward) + joint_reward) + body_reward) + endeff_reward
+  //   body_metrics[env] = (body_reward, endeff_reward), zeroed by a bad step.  Never at reset.
+  // xpos lives in LDS only between kinematics() and the recycling of its cells in the last substep, so S_B and S_E are formed THERE and
+  // parked in body_metrics[env] by lane 0, which reads them back in the epilogue and overwrites them with the two terms: nothing lives
+  // across the solver.  All fetched by narrow loads where they are used (load_io_member), never through load_io().
+  const float* track_bodies;
+  const float* body_weights;   // [2][nbody]
+  float* body_metrics;         // [N][2]
+  float body_w, body_k, endeff_w, endeff_k;
 };
 
 // ------------------------------------------------------------------------------------------ small math
@@ -2618,7 +2634,9 @@ static_assert(offsetof(RRIO, clip) % 8 == 0 && offsetof(RRIO, clip) + sizeof(con
 static_assert(offsetof(RRIO, pose_joint_k) + sizeof(float) == offsetof(RRIO, ref_frames), "the reference-observation members follow the pose members without padding");
 static_assert(offsetof(RRIO, ref_pad) + sizeof(int) == offsetof(RRIO, pose_fail) && offsetof(RRIO, pose_fail) % 8 == 0, "the pose-termination members follow the reference-observation members without padding");
 static_assert(offsetof(RRIO, pose_fail) + sizeof(float*) == offsetof(RRIO, pose_max_pos), "the thresholds follow pose_fail without padding");
-static_assert(offsetof(RRIO, pterm_pad) + sizeof(int) == sizeof(RRIO), "the pose-termination members close RRIO without padding");
+static_assert(offsetof(RRIO, pterm_pad) + sizeof(int) == offsetof(RRIO, track_bodies) && offsetof(RRIO, track_bodies) % 8 == 0, "the body-tracking members follow the pose-termination members without padding");
+static_assert(offsetof(RRIO, track_bodies) + 3 * sizeof(float*) == offsetof(RRIO, body_w), "the weights and scales follow the three body-tracking pointers without padding");
+static_assert(offsetof(RRIO, endeff_k) + sizeof(float) == sizeof(RRIO), "the body-tracking members close RRIO without padding");
 // ... and so are the model tables outside the solver's loops: RRTables is re-read at the head of each phase that indexes a table
 // (narrow scalar loads next to an existing hand-off; the unused members' loads are dead), so no table pointer is held across the
 // substep.  The loops' own tables are the exception (RRLoopTables, taken once from the parameter).
@@ -2808,7 +2826,7 @@ __device__ __forceinline__ void rr_actor_step(const RRIO& io, const DT& D, int l
 template <int NBS, int NVS, int NCS, bool PROF, bool DBG, class DT, bool NEWTON = false, bool UNROLL = false, bool ACTOR = false, bool PAIR = false, bool DYN = false>
 __global__ __launch_bounds__((PAIR ? 2 : 1) * RR_LANES, (NVS >= 3 ? 1 : 2)) void rr_step_kernel(const RRDims Dk, const RRTables Tk, const RRIO io_kernarg, const int num_envs,
                                                            const int n_frames) {
-  constexpr bool RAND = false, EVAL = false, POSE = false, REFOBS = false, PTERM = false;
+  constexpr bool RAND = false, EVAL = false, POSE = false, REFOBS = false, PTERM = false, BODY = false;
   constexpr bool ROOTSLOT = rr_root_slot<DT>::value && NBS == 2 && !NEWTON && !PAIR && !DYN;      // the root body alone in the second body slot (Wave::ROOT)
   constexpr int MRES = ACTOR ? 1 : 2;      // resident inverse-factor entries (Wave::MAT_RES): both sides at 245-253 registers (timed: -1.4 % against the column side alone); with the actor the column side (233)
 #include "rr_step_body.inc"
@@ -2818,7 +2836,7 @@ __global__ __launch_bounds__((PAIR ? 2 : 1) * RR_LANES, (NVS >= 3 ? 1 : 2)) void
 template <class DT, bool UNROLL = false, bool ACTOR = false>
 __global__ __launch_bounds__(RR_LANES, 2) void rr_rand_kernel(const RRDims Dk, const RRTables Tk, const RRIO io_kernarg, const int num_envs, const int n_frames) {
   constexpr int NBS = 2, NVS = 2, NCS = 1;
-  constexpr bool PROF = false, DBG = false, NEWTON = false, PAIR = false, DYN = false, RAND = true, EVAL = false, POSE = false, REFOBS = false, PTERM = false;
+  constexpr bool PROF = false, DBG = false, NEWTON = false, PAIR = false, DYN = false, RAND = true, EVAL = false, POSE = false, REFOBS = false, PTERM = false, BODY = false;
   constexpr int MRES = 1;      // resident inverse-factor entries (Wave::MAT_RES): the column side (229-237 registers; both sides reach the cap of 256 here)
   constexpr bool ROOTSLOT = rr_root_slot<DT>::value;
 #include "rr_step_body.inc"
@@ -2831,7 +2849,7 @@ __global__ __launch_bounds__(RR_LANES, 2) void rr_rand_kernel(const RRDims Dk, c
 template <class DT, bool DYN = false>
 __global__ __launch_bounds__(RR_LANES, 2) void rr_eval_kernel(const RRDims Dk, const RRTables Tk, const RRIO io_kernarg, const int num_envs, const int n_frames) {
   constexpr int NBS = 2, NVS = 2, NCS = 1;
-  constexpr bool PROF = false, DBG = false, NEWTON = false, PAIR = false, RAND = false, UNROLL = true, ACTOR = true, EVAL = true, POSE = false, REFOBS = false, PTERM = false;
+  constexpr bool PROF = false, DBG = false, NEWTON = false, PAIR = false, RAND = false, UNROLL = true, ACTOR = true, EVAL = true, POSE = false, REFOBS = false, PTERM = false, BODY = false;
   constexpr int MRES = 1;      // resident inverse-factor entries (Wave::MAT_RES): the column side (229-237 registers; both sides reach the cap of 256 here)
   constexpr bool ROOTSLOT = rr_root_slot<DT>::value;
 #include "rr_step_body.inc"
@@ -2843,7 +2861,7 @@ __global__ __launch_bounds__(RR_LANES, 2) void rr_eval_kernel(const RRDims Dk, c
 template <class DT, bool UNROLL = false, bool ACTOR = false>
 __global__ __launch_bounds__(RR_LANES, 2) void rr_pose_kernel(const RRDims Dk, const RRTables Tk, const RRIO io_kernarg, const int num_envs, const int n_frames) {
   constexpr int NBS = 2, NVS = 2, NCS = 1;
-  constexpr bool PROF = false, DBG = false, NEWTON = false, PAIR = false, DYN = false, RAND = false, EVAL = false, POSE = true, REFOBS = false, PTERM = false;
+  constexpr bool PROF = false, DBG = false, NEWTON = false, PAIR = false, DYN = false, RAND = false, EVAL = false, POSE = true, REFOBS = false, PTERM = false, BODY = false;
   constexpr int MRES = 1;      // resident inverse-factor entries (Wave::MAT_RES): the column side (229-237 registers; both sides reach the cap of 256 here)
   constexpr bool ROOTSLOT = rr_root_slot<DT>::value;
 #include "rr_step_body.inc"
@@ -2855,7 +2873,7 @@ __global__ __launch_bounds__(RR_LANES, 2) void rr_pose_kernel(const RRDims Dk, c
 template <class DT, bool UNROLL = false, bool ACTOR = false>
 __global__ __launch_bounds__(RR_LANES, 2) void rr_refobs_kernel(const RRDims Dk, const RRTables Tk, const RRIO io_kernarg, const int num_envs, const int n_frames) {
   constexpr int NBS = 2, NVS = 2, NCS = 1;
-  constexpr bool PROF = false, DBG = false, NEWTON = false, PAIR = false, DYN = false, RAND = false, EVAL = false, POSE = true, REFOBS = true, PTERM = false;
+  constexpr bool PROF = false, DBG = false, NEWTON = false, PAIR = false, DYN = false, RAND = false, EVAL = false, POSE = true, REFOBS = true, PTERM = false, BODY = false;
   constexpr int MRES = 1;      // resident inverse-factor entries (Wave::MAT_RES): the column side, as in rr_pose_kernel
   constexpr bool ROOTSLOT = rr_root_slot<DT>::value;
 #include "rr_step_body.inc"
@@ -2868,28 +2886,42 @@ __global__ __launch_bounds__(RR_LANES, 2) void rr_refobs_kernel(const RRDims Dk,
 template <class DT, bool UNROLL = false, bool ACTOR = false>
 __global__ __launch_bounds__(RR_LANES, 2) void rr_poseterm_kernel(const RRDims Dk, const RRTables Tk, const RRIO io_kernarg, const int num_envs, const int n_frames) {
   constexpr int NBS = 2, NVS = 2, NCS = 1;
-  constexpr bool PROF = false, DBG = false, NEWTON = false, PAIR = false, DYN = false, RAND = false, EVAL = false, POSE = true, REFOBS = true, PTERM = true;
+  constexpr bool PROF = false, DBG = false, NEWTON = false, PAIR = false, DYN = false, RAND = false, EVAL = false, POSE = true, REFOBS = true, PTERM = true, BODY = false;
+  constexpr int MRES = 1;      // resident inverse-factor entries (Wave::MAT_RES): the column side, as in rr_pose_kernel
+  constexpr bool ROOTSLOT = rr_root_slot<DT>::value;
+#include "rr_step_body.inc"
+}
+// Body tracking (rr_batch_set_body_tracking): the pose-termination instances with the reward's body-position and end-effector terms
+// (RRIO, BODY TRACKING), served to the env steps of a batch that carries the block; resets stay on the instance they use without it.  An
+// entry of its own for the reason the others are: every `if (BODY)` in the body folds away in their instances.  POSE, REFOBS and PTERM
+// are on -- a superset instance: ref_frames = 0 is that code with zero blocks, and a batch without a termination block hands +inf
+// thresholds and a null pose_fail, which the PTERM code takes.  The same nine forms as rr_pose_kernel; the actor inside reads
+// RR_ACTOR_JM_REFOBS entries per lane whatever the frame count.
+template <class DT, bool UNROLL = false, bool ACTOR = false>
+__global__ __launch_bounds__(RR_LANES, 2) void rr_body_kernel(const RRDims Dk, const RRTables Tk, const RRIO io_kernarg, const int num_envs, const int n_frames) {
+  constexpr int NBS = 2, NVS = 2, NCS = 1;
+  constexpr bool PROF = false, DBG = false, NEWTON = false, PAIR = false, DYN = false, RAND = false, EVAL = false, POSE = true, REFOBS = true, PTERM = true, BODY = true;
   constexpr int MRES = 1;      // resident inverse-factor entries (Wave::MAT_RES): the column side, as in rr_pose_kernel
   constexpr bool ROOTSLOT = rr_root_slot<DT>::value;
 #include "rr_step_body.inc"
 }
 // The production single-step instance with the inverse factor's entries left in LDS (MRES 0), whatever RR_SOLVE_MAT_RESIDENT says: the other
 // arm of an exact A/B inside one library (rr_batch_set_solve_resident(b, 0); tests/test_gpu_solve_resident.py).  An entry of its own so
-// that the instances of the other six keep their code.
+// that the instances of the other seven keep their code.
 template <class DT>
 __global__ __launch_bounds__(RR_LANES, 2) void rr_matlds_kernel(const RRDims Dk, const RRTables Tk, const RRIO io_kernarg, const int num_envs, const int n_frames) {
   constexpr int NBS = 2, NVS = 2, NCS = 1, MRES = 0;
   constexpr bool ROOTSLOT = rr_root_slot<DT>::value;
-  constexpr bool PROF = false, DBG = false, NEWTON = false, UNROLL = false, ACTOR = false, PAIR = false, DYN = false, RAND = false, EVAL = false, POSE = false, REFOBS = false, PTERM = false;
+  constexpr bool PROF = false, DBG = false, NEWTON = false, UNROLL = false, ACTOR = false, PAIR = false, DYN = false, RAND = false, EVAL = false, POSE = false, REFOBS = false, PTERM = false, BODY = false;
 #include "rr_step_body.inc"
 }
 // The production single-step instance with the tree phases on the plain lane <-> body map b = lane + 64 s (Wave::ROOT off), whatever
 // RR_ROOT_SLOT says: the other arm of an exact A/B inside one library (rr_batch_set_root_slot(b, 0); tests/test_gpu_root_slot.py).  An
-// entry of its own so that the instances of the other seven keep their code.
+// entry of its own so that the instances of the other eight keep their code.
 template <class DT>
 __global__ __launch_bounds__(RR_LANES, 2) void rr_twoslot_kernel(const RRDims Dk, const RRTables Tk, const RRIO io_kernarg, const int num_envs, const int n_frames) {
   constexpr int NBS = 2, NVS = 2, NCS = 1, MRES = 2;
   constexpr bool ROOTSLOT = false;
-  constexpr bool PROF = false, DBG = false, NEWTON = false, UNROLL = false, ACTOR = false, PAIR = false, DYN = false, RAND = false, EVAL = false, POSE = false, REFOBS = false, PTERM = false;
+  constexpr bool PROF = false, DBG = false, NEWTON = false, UNROLL = false, ACTOR = false, PAIR = false, DYN = false, RAND = false, EVAL = false, POSE = false, REFOBS = false, PTERM = false, BODY = false;
 #include "rr_step_body.inc"
 }

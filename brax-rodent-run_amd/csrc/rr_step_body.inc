@@ -1,6 +1,6 @@
 // rr_step_body.inc -- the body of the step kernel, included by each of its __global__ entries in rr_kernel.h (rr_step_kernel,
-// rr_rand_kernel, rr_eval_kernel, rr_pose_kernel, rr_refobs_kernel, rr_poseterm_kernel, rr_matlds_kernel, rr_twoslot_kernel).  In scope where it is included: the kernel's five arguments (Dk, Tk, io_kernarg, num_envs, n_frames) and the
-// compile-time switches NBS, NVS, NCS, PROF, DBG, DT, NEWTON, UNROLL, ACTOR, PAIR, DYN, RAND, EVAL, POSE, REFOBS, PTERM, MRES, ROOTSLOT.
+// rr_rand_kernel, rr_eval_kernel, rr_pose_kernel, rr_refobs_kernel, rr_poseterm_kernel, rr_body_kernel, rr_matlds_kernel, rr_twoslot_kernel).  In scope where it is included: the kernel's five arguments (Dk, Tk, io_kernarg, num_envs, n_frames) and the
+// compile-time switches NBS, NVS, NCS, PROF, DBG, DT, NEWTON, UNROLL, ACTOR, PAIR, DYN, RAND, EVAL, POSE, REFOBS, PTERM, BODY, MRES, ROOTSLOT.
 // Why text and not a function: see the note above rr_step_kernel.
   static_assert(!PAIR || (!PROF && !DBG && !NEWTON && !UNROLL && !ACTOR), "PAIR: production physics instance only");
   static_assert(!DYN || (!PROF && !DBG && !NEWTON && !PAIR), "DYN: production instances only (single-step, multi-step, multi-step with the actor)");
@@ -8,6 +8,7 @@
   static_assert(!POSE || (!RAND && !EVAL && !PROF && !DBG && !NEWTON && !PAIR && !DYN), "POSE: production CG instances of the floor-contact models only");
   static_assert(!REFOBS || POSE, "REFOBS: a form of the pose instances (the blocks are rows of track_pose)");
   static_assert(!PTERM || REFOBS, "PTERM: a form of the reference-observation instances (ref_frames 0: no blocks)");
+  static_assert(!BODY || PTERM, "BODY: a form of the pose-termination instances (+inf thresholds and a null pose_fail: no termination)");
   static_assert(!EVAL || (ACTOR && !RAND && !PROF && !DBG && !NEWTON && !PAIR), "EVAL: a form of the production multi-step instance with the actor");
   extern __shared__ __attribute__((aligned(16))) float lds[];
   int env = blockIdx.x;
@@ -161,6 +162,43 @@
         }
       }
       if (io.o_com && lane == 0) for (int k = 0; k < 3; ++k) io.o_com[(size_t)env * 3 + k] = w.com0[k];
+      // ---- BODY TRACKING, capture (BODY instances, RRIO::track_bodies): the squared distances of the body positions to the clip's row, env
+      // steps only.  It stands HERE because s_xpos exists only up to the recycling of its cells later in this substep; the epilogue's
+      // terms need S_B and S_E alone, and those travel through body_metrics[env] -- stored by lane 0 now, read back by lane 0 in the
+      // epilogue (same thread, program order, as the REFOBS block reads back p_1) -- so nothing of this lives across the solver.  The
+      // lanes walk bodies lane, lane + 64, .. from 1 in ascending order; differences, squares, masked products and sums are rounded one by
+      // one (contraction off, see POSE TRACKING below).  Clip and frame -- the row the position and pose rewards of this step read -- are
+      // clamped before the offset is formed, so no row lies outside track_bodies.  Every member comes by a narrow load.
+      if (BODY) {
+        const float* tbod = load_io_member<const float*>(offsetof(RRIO, track_bodies));
+        if (tbod && !(mode & 2)) {
+#pragma clang fp contract(off)
+          const float* bwt = load_io_member<const float*>(offsetof(RRIO, body_weights));
+          const int blen = load_io_member<int>(offsetof(RRIO, track_len));
+          int bc = 0;
+          if (const int* bclip = load_io_member<const int*>(offsetof(RRIO, clip))) {
+            const int nc = load_io_member<int>(offsetof(RRIO, num_clips));
+            bc = bclip[env];
+            bc = bc < 0 ? 0 : (bc > nc - 1 ? nc - 1 : bc);
+          }
+          int bf = UNROLL ? u_frame : load_io_member<const int*>(offsetof(RRIO, cur_frame_in))[env];
+          bf = bf < 0 ? 0 : (bf > blen - 1 ? blen - 1 : bf);
+          const float* brow = tbod + ((size_t)bc * (size_t)blen + (size_t)bf) * (size_t)(3 * D.nbody);
+          float sb = 0.0f, se = 0.0f;
+          for (int b = lane; b < D.nbody; b += RR_LANES) {
+            if (b >= 1) {
+              const float ex = w.s_xpos[3 * b] - brow[3 * b], ey = w.s_xpos[3 * b + 1] - brow[3 * b + 1], ez = w.s_xpos[3 * b + 2] - brow[3 * b + 2];
+              const float xx = ex * ex, yy = ey * ey, zz = ez * ez;
+              const float e2 = (xx + yy) + zz;
+              const float tb = bwt[b] * e2, te = bwt[D.nbody + b] * e2;
+              sb = sb + tb; se = se + te;
+            }
+          }
+          sb = wave_sum(sb);
+          se = wave_sum(se);
+          if (lane == 0) { float* bm = load_io_member<float*>(offsetof(RRIO, body_metrics)) + 2 * (size_t)env; bm[0] = sb; bm[1] = se; }
+        }
+      }
       if (dg) {
         for (int e = lane; e < 3 * D.nbody; e += RR_LANES) dg[D.g_xpos + e] = w.s_xpos[e];
         for (int e = lane; e < 4 * D.nbody; e += RR_LANES) dg[D.g_xquat + e] = w.s_xquat[e];
@@ -493,6 +531,23 @@
             }
           }
         }
+        // ---- BODY TRACKING, terms (BODY instances): lane 0 reads back the S_B and S_E it parked in body_metrics[env] after the last
+        // forward pass and overwrites them with the two terms.  ISOLATION: the reward formed above passes through an opaque copy, so its
+        // expressions keep the uses -- and the contraction -- they have in the pose instances; the two sums stand under contraction off.
+        if (BODY) {
+          if (load_io_member<const float*>(offsetof(RRIO, track_bodies))) {
+#pragma clang fp contract(off)
+            float* bm = load_io_member<float*>(offsetof(RRIO, body_metrics)) + 2 * (size_t)env;
+            float rb = rew;
+            asm volatile("" : "+v"(rb));
+            const float xb = load_io_member<float>(offsetof(RRIO, body_k)) * bm[0];
+            const float body_rew = load_io_member<float>(offsetof(RRIO, body_w)) * expf(-xb);
+            const float xe = load_io_member<float>(offsetof(RRIO, endeff_k)) * bm[1];
+            const float endeff_rew = load_io_member<float>(offsetof(RRIO, endeff_w)) * expf(-xe);
+            rew = (rb + body_rew) + endeff_rew;
+            bm[0] = body_rew; bm[1] = endeff_rew;
+          }
+        }
         io.reward[env] = rew;
         if (ACTOR && !EVAL) io.t_reward[rr_traj_at(io, num_envs, env, ut)] = rew;
         io.done[env] = io.terminate_when_unhealthy ? 1.0f - healthy : 0.0f;
@@ -507,6 +562,9 @@
           io.metrics[3 * env] = 0.0f; io.metrics[3 * env + 1] = 0.0f; io.metrics[3 * env + 2] = 0.0f;
           if (POSE) {
             if (prow) { float* pm = load_io_member<float*>(offsetof(RRIO, pose_metrics)) + 2 * (size_t)env; pm[0] = 0.0f; pm[1] = 0.0f; }
+          }
+          if (BODY) {
+            if (load_io_member<const float*>(offsetof(RRIO, track_bodies))) { float* bm = load_io_member<float*>(offsetof(RRIO, body_metrics)) + 2 * (size_t)env; bm[0] = 0.0f; bm[1] = 0.0f; }
           }
           if (PTERM) pterm_code = 0;      // a bad step: done = 1 from the check above, code 0
         }

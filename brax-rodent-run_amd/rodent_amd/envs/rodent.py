@@ -249,6 +249,64 @@ def _check_pose_termination(max_pos_error, max_quat_error, max_joint_error, have
     return tuple(out)
 
 
+def body_rewards(xpos, ref_bodies, body_ids, end_effector_ids, weights=(1.0, 1.0), scales=(8.0, 100.0)):
+    """The two body-position terms the step kernel adds to the reward of an env with body tracking (`Rodent(track_bodies=...)`; C ABI
+    `rr_batch_set_body_tracking`) restated in numpy float64.  `xpos` [..., nbody, 3] the body positions of the step's last forward pass
+    (`State.pipeline_state.xpos`), `ref_bodies` [..., nbody, 3] the clip's row at the clip and frame the step's rewards read (`cur_frame`
+    before the step, clamped); `body_ids` / `end_effector_ids` the sets B and E of body ids (None or empty: that sum is 0).  Returns
+    (body_reward, endeff_reward), float64 [...]:
+
+        S_B = sum_{b in B} |xpos[b] - ref_bodies[b]|^2,   S_E the same over E
+        body_reward = weights[0] * exp(-scales[0] * S_B),   endeff_reward = weights[1] * exp(-scales[1] * S_E)"""
+    xpos, ref = np.asarray(xpos, dtype=np.float64), np.asarray(ref_bodies, dtype=np.float64)
+    d2 = ((xpos - ref) ** 2).sum(-1)
+    sums = [d2[..., np.asarray([] if ids is None else list(ids), dtype=np.int64)].sum(-1) for ids in (body_ids, end_effector_ids)]
+    return weights[0] * np.exp(-scales[0] * sums[0]), weights[1] * np.exp(-scales[1] * sums[1])
+
+
+def _check_body_tracking(track: np.ndarray, track_bodies, body_ids, end_effector_ids, nbody: int, weights_and_scales, have_pose: bool):
+    """The body-tracking arguments of `Rodent` against its (checked) `track` [(C,) T, 3]: None when `track_bodies` is None, else
+    (rows float32 [(C,) T, nbody, 3], masks float32 [2, nbody] -- row 0 the tracked bodies, row 1 the end effectors --, B, E as tuples).
+    ValueError for ids without `track_bodies`, `track_bodies` without the pose arguments, a shape other than track.shape[:-1] +
+    (nbody, 3), a non-finite entry, ids that are not unique ints in 1 .. nbody - 1, and a negative or non-finite weight or scale."""
+    for x in weights_and_scales:
+        if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, float, np.integer, np.floating)):
+            raise ValueError(f"body reward weights and scales must be numbers, finite and >= 0, got {x!r}")
+        with np.errstate(over="ignore"):
+            x32 = np.float32(x)
+        if not (np.isfinite(x32) and x32 >= 0):
+            raise ValueError(f"body reward weights and scales must be finite and >= 0 (as float32), got {x!r}")
+    if track_bodies is None:
+        if body_ids is not None or end_effector_ids is not None:
+            raise ValueError("body_ids / end_effector_ids need track_bodies (the clip's body positions)")
+        return None
+    if not have_pose:
+        raise ValueError("track_bodies needs the reference pose: pass track_quat and track_joints")
+    bodies = (track_bodies.detach().cpu().numpy() if torch.is_tensor(track_bodies) else np.asarray(track_bodies)).astype(np.float64)
+    want = track.shape[:-1] + (nbody, 3)
+    if bodies.shape != want:
+        raise ValueError(f"track_bodies must have shape {want} next to a track_pos of shape {track.shape} (the same clips and frames, "
+                         f"one global position per body), got {bodies.shape}")
+    if not np.isfinite(bodies).all():
+        raise ValueError("track_bodies holds a non-finite position")
+    sets = []
+    for name, ids in (("body_ids", body_ids), ("end_effector_ids", end_effector_ids)):
+        if ids is None:
+            sets.append(tuple(range(1, nbody)) if name == "body_ids" else ())
+            continue
+        ids = list(ids.tolist() if isinstance(ids, np.ndarray) else ids)
+        for b in ids:
+            if isinstance(b, (bool, np.bool_)) or not isinstance(b, (int, np.integer)) or not 1 <= int(b) <= nbody - 1:
+                raise ValueError(f"{name} must be ints in 1 .. {nbody - 1} (body 0 is the world), got {b!r}")
+        if len(set(int(b) for b in ids)) != len(ids):
+            raise ValueError(f"{name} must be unique, got {ids!r}")
+        sets.append(tuple(int(b) for b in ids))
+    masks = np.zeros((2, nbody), dtype=np.float32)
+    for row, ids in enumerate(sets):
+        masks[row, list(ids)] = 1.0
+    return np.ascontiguousarray(bodies, dtype=np.float32), masks, sets[0], sets[1]
+
+
 class Rodent(PipelineEnv):
 
     def __init__(
@@ -279,6 +337,13 @@ class Rodent(PipelineEnv):
         max_pos_error: Optional[float] = None,
         max_quat_error: Optional[float] = None,
         max_joint_error: Optional[float] = None,
+        track_bodies=None,
+        body_ids=None,
+        end_effector_ids=None,
+        body_reward_weight: float = 1.0,
+        body_reward_scale: float = 8.0,
+        endeff_reward_weight: float = 1.0,
+        endeff_reward_scale: float = 100.0,
         **kwargs,
     ):
         """`track_pos`: the reference positions to track, float [T, 3] -- one clip, followed by every env -- or [C, T, 3], C >= 1 clips of
@@ -329,7 +394,24 @@ class Rodent(PipelineEnv):
         step changes.  It is a termination, not a truncation: under AutoReset -- composed or in the one-launch rollouts -- the first
         state comes back, discount 0.  `State.metrics` gains `pose_fail`, `pose_fail_pos`, `pose_fail_quat`, `pose_fail_joint` (0 / 1;
         zeros at reset and after a bad step), so an evaluation reports `eval/episode_pose_fail`, the share of episodes ended by the
-        clip.  The thresholds have no defaults: they depend on the clips and on how far training has come."""
+        clip.  The thresholds have no defaults: they depend on the clips and on how far training has come.
+
+        Body tracking: `track_bodies` [T, nbody, 3] -- with a [C, T, 3] track_pos [C, T, nbody, 3] -- are the clip's global body positions
+        (`preprocessing.ReferenceClip.body_positions`); pose envs only, every entry finite.  `body_ids` is the set B of tracked bodies
+        (None: bodies 1 .. nbody - 1), `end_effector_ids` the set E of end effectors (None: no such term); unique ints in 1 .. nbody - 1.
+        A joint-angle reward lets errors add up along a limb; these two terms score where the bodies ARE.  Every env step (never a
+        reset) adds, at the clip and frame the other rewards read (`body_rewards` is the float64 restatement):
+
+            body_reward   = body_reward_weight   * exp(-body_reward_scale   * sum_{b in B} |xpos[b] - track_bodies[b]|**2)
+            endeff_reward = endeff_reward_weight * exp(-endeff_reward_scale * sum_{b in E} |xpos[b] - track_bodies[b]|**2)
+            reward        = (reward with the pose terms + body_reward) + endeff_reward
+
+        with xpos the body positions of the step's last forward pass -- `State.pipeline_state.xpos` with `pipeline_outputs=True`, MJX's
+        `data.xpos` after `step`: the pose before the last substep's integration, one substep behind qpos.  `State.metrics` gains
+        `body_reward` and `endeff_reward` (zeros at reset and after a bad step); everything else of the step is what it is without the
+        terms.  An empty set gives its term weight 0.  The four defaults (1, 8, 1, 100) are UNTUNED choices, not values from a reference.
+        Served where pose tracking is, in `step`, `unroll_wrapped` and `unroll_policy_wrapped`, with or without reference frames and
+        pose termination."""
         if bad_state_max is not None:
             with np.errstate(over="ignore", under="ignore"):
                 thr32 = np.float32(bad_state_max)        # what the kernel gets: 1e-50 would arrive as 0 (= off), 1e39 as inf
@@ -350,6 +432,8 @@ class Rodent(PipelineEnv):
         pose_np = _check_pose(track_np, track_quat, track_joints, sys.nq, (quat_reward_weight, quat_reward_scale, joint_reward_weight, joint_reward_scale))
         ref_frames = _check_reference_frames(reference_obs_frames, pose_np is not None)
         pose_term = _check_pose_termination(max_pos_error, max_quat_error, max_joint_error, pose_np is not None)
+        body_np = _check_body_tracking(track_np, track_bodies, body_ids, end_effector_ids, sys.nbody,
+                                       (body_reward_weight, body_reward_scale, endeff_reward_weight, endeff_reward_scale), pose_np is not None)
         if reset_to_reference and pose_np is None:
             raise ValueError("reset_to_reference=True needs the reference pose: pass track_quat and track_joints")
         physics_steps_per_control_step = 10   # [REF Rodent_Env_Brax.py:53-57]
@@ -383,6 +467,16 @@ class Rodent(PipelineEnv):
             why = self._batch.pose_termination_supported()
             if why is not None:
                 raise RuntimeError(f"Rodent(max_pos_error / max_quat_error / max_joint_error): {why}")
+        self._body = None                 # None: no body tracking (no such members anywhere, the launches run the instances they ran)
+        if body_np is not None:
+            why = self._batch.body_tracking_supported()
+            if why is not None:
+                raise RuntimeError(f"Rodent(track_bodies=...): {why}")
+            rows, masks, B, E = body_np
+            # an empty set gives its term weight 0 here, so the term is 0 whatever its (empty) sum
+            self._body = dict(track_bodies=torch.from_numpy(rows).to(self.device).contiguous(), body_weights=torch.from_numpy(masks).to(self.device).contiguous(),
+                              body_reward=(float(body_reward_weight) if B else 0.0, float(body_reward_scale)),
+                              endeff_reward=(float(endeff_reward_weight) if E else 0.0, float(endeff_reward_scale)), body_ids=B, end_effector_ids=E)
         self._forward_reward_weight = forward_reward_weight
         self._ctrl_cost_weight = ctrl_cost_weight
         self._healthy_reward = healthy_reward
@@ -402,7 +496,9 @@ class Rodent(PipelineEnv):
                           quat_reward_scale=quat_reward_scale, joint_reward_weight=joint_reward_weight,
                           joint_reward_scale=joint_reward_scale, reset_to_reference=reset_to_reference,
                           reference_obs_frames=reference_obs_frames, max_pos_error=max_pos_error, max_quat_error=max_quat_error,
-                          max_joint_error=max_joint_error)
+                          max_joint_error=max_joint_error, track_bodies=track_bodies, body_ids=body_ids, end_effector_ids=end_effector_ids,
+                          body_reward_weight=body_reward_weight, body_reward_scale=body_reward_scale,
+                          endeff_reward_weight=endeff_reward_weight, endeff_reward_scale=endeff_reward_scale)
 
     def with_num_envs(self, num_envs: int, device=None):
         """A sibling env with another batch size (ppo.train builds its per-rank and eval envs this way)."""
@@ -440,6 +536,14 @@ class Rodent(PipelineEnv):
         return self._pose_term
 
     @property
+    def body_tracking(self) -> Optional[dict]:
+        """None without body tracking, else dict(body_ids, end_effector_ids, body_reward=(weight, scale), endeff_reward=(weight, scale))
+        as the kernel uses them (an empty set has weight 0)."""
+        if self._body is None:
+            return None
+        return {k: self._body[k] for k in ("body_ids", "end_effector_ids", "body_reward", "endeff_reward")}
+
+    @property
     def reference_obs_frames(self) -> int:
         """Reference frames H behind every observation row (0: none)."""
         return self._ref_frames
@@ -459,7 +563,7 @@ class Rodent(PipelineEnv):
             raise RuntimeError("pose tracking: no pose instance reads per-env parameters (randomize / set_env_params on a pose env)")
         return super().randomize(randomization_fn)
 
-    def _env_io(self, cur_frame, obs, reward=None, done=None, metrics=None, clip=None, pose_metrics=None, pose_fail=None):
+    def _env_io(self, cur_frame, obs, reward=None, done=None, metrics=None, clip=None, pose_metrics=None, pose_fail=None, body_metrics=None):
         io = dict(track_pos=self._track_pos, cur_frame=cur_frame, obs=obs, reward=reward, done=done, metrics=metrics, clip=clip,
                   healthy_reward=self._healthy_reward, ctrl_cost_weight=self._ctrl_cost_weight,
                   healthy_z_range=self._healthy_z_range, terminate_when_unhealthy=self._terminate_when_unhealthy,
@@ -470,6 +574,9 @@ class Rodent(PipelineEnv):
             io.update(track_pose=self._track_pose, pose_metrics=pose_metrics, quat_reward=self._quat_reward, joint_reward=self._joint_reward)
         if pose_fail is not None:            # a step of an env with pose termination (a reset passes none: it has no done to raise)
             io.update(pose_fail=pose_fail, pose_termination=self._pose_term)
+        if body_metrics is not None:         # a step of an env with body tracking (a reset passes none: it has no reward)
+            io.update(track_bodies=self._body["track_bodies"], body_weights=self._body["body_weights"], body_metrics=body_metrics,
+                      body_reward=self._body["body_reward"], endeff_reward=self._body["endeff_reward"])
         return io
 
     def reset(self, rng, clip=None) -> State:
@@ -507,6 +614,8 @@ class Rodent(PipelineEnv):
             metrics.update(quat_reward=zero.clone(), joint_reward=zero.clone())
         if self._pose_term is not None:
             metrics.update({k: zero.clone() for k in ("pose_fail", "pose_fail_pos", "pose_fail_quat", "pose_fail_joint")})
+        if self._body is not None:
+            metrics.update(body_reward=zero.clone(), endeff_reward=zero.clone())
         return State(PipelineState(**st, **out), obs, zero.clone(), zero.clone(), metrics, info)
 
     def _launch_buffers(self, state: State, episode_length: Optional[float] = None):
@@ -524,6 +633,8 @@ class Rodent(PipelineEnv):
             io["pose_metrics"] = torch.empty(N, 2, device=dev)
         if self._pose_term is not None:
             io["pose_fail"] = torch.empty(N, device=dev)
+        if self._body is not None:
+            io["body_metrics"] = torch.empty(N, 2, device=dev)
         wrap = None
         if episode_length is not None:
             wrap = dict(first=fields(info["first_pipeline_state"]), first_obs=info["first_obs"], prev_done=state.done, steps_in=info["steps"],
@@ -544,6 +655,8 @@ class Rodent(PipelineEnv):
             code = io["pose_fail"].to(torch.int32)
             m.update(pose_fail=(code != 0).float(), pose_fail_pos=(code & 1).float(), pose_fail_quat=((code >> 1) & 1).float(),
                      pose_fail_joint=((code >> 2) & 1).float())
+        if self._body is not None:
+            m.update(body_reward=io["body_metrics"][:, 0], endeff_reward=io["body_metrics"][:, 1])
         return state.replace(pipeline_state=PipelineState(**st, **(out or {})), obs=obs, reward=io["reward"], done=io["done"], metrics=m, info=info)
 
     def unroll_wrapped(self, state: State, actions: torch.Tensor, episode_length: float) -> State:

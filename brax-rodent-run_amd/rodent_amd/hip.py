@@ -60,6 +60,13 @@ class RRPoseTermIO(C.Structure):
     _fields_ = [("fail", C.c_void_p), ("max_pos", C.c_float), ("max_quat", C.c_float), ("max_joint", C.c_float), ("pad", C.c_int32)]
 
 
+class RRBodyIO(C.Structure):
+    """`rr_body_io`, the body-tracking block a batch carries next to its pose block (`rr_batch_set_body_tracking`)."""
+    _fields_ = [("track_bodies", C.c_void_p), ("body_weights", C.c_void_p), ("body_metrics", C.c_void_p),
+                ("body_reward_weight", C.c_float), ("body_reward_scale", C.c_float),
+                ("endeff_reward_weight", C.c_float), ("endeff_reward_scale", C.c_float)]
+
+
 class RRUnrollIO(C.Structure):
     _fields_ = [("first", RRState), ("first_obs", C.c_void_p), ("prev_done", C.c_void_p), ("steps_in", C.c_void_p), ("steps_out", C.c_void_p),
                 ("truncation_out", C.c_void_p), ("episode_length", C.c_float)]
@@ -91,7 +98,7 @@ class RRPpoCfg(C.Structure):
 
 
 EXPORTS = ["rr_model_load", "rr_model_dims", "rr_model_set_solver", "rr_model_set_solver_type", "rr_model_destroy", "rr_model_table", "rr_kernarg_layout", "rr_batch_create",
-           "rr_batch_destroy", "rr_pipeline_init", "rr_pipeline_step", "rr_env_step", "rr_env_reset", "rr_pipeline_step_to", "rr_env_step_to", "rr_batch_contact_overflow", "rr_batch_bad_states", "rr_batch_unroll_supported", "rr_env_unroll", "rr_env_unroll_policy", "rr_batch_eval_supported", "rr_env_unroll_eval", "rr_batch_pose_supported", "rr_batch_set_pose", "rr_batch_set_reference_obs", "rr_batch_obs_width", "rr_batch_reference_obs_supported", "rr_batch_set_pose_termination", "rr_batch_pose_termination_supported",
+           "rr_batch_destroy", "rr_pipeline_init", "rr_pipeline_step", "rr_env_step", "rr_env_reset", "rr_pipeline_step_to", "rr_env_step_to", "rr_batch_contact_overflow", "rr_batch_bad_states", "rr_batch_unroll_supported", "rr_env_unroll", "rr_env_unroll_policy", "rr_batch_eval_supported", "rr_env_unroll_eval", "rr_batch_pose_supported", "rr_batch_set_pose", "rr_batch_set_reference_obs", "rr_batch_obs_width", "rr_batch_reference_obs_supported", "rr_batch_set_pose_termination", "rr_batch_pose_termination_supported", "rr_batch_set_body_tracking", "rr_batch_body_tracking_supported",
            "rr_compute_gae", "rr_mlp_forward", "rr_ppo_loss_workspace_bytes", "rr_ppo_loss", "rr_policy_act_workspace_bytes", "rr_policy_act", "rr_policy_sample", "rr_policy_backward_workspace_bytes", "rr_policy_backward", "rr_mlp_silu_backward_workspace_bytes", "rr_mlp_silu_backward", "rr_mlp_value_backward_workspace_bytes", "rr_mlp_policy_backward", "rr_mlp_policy_backward_workspace_bytes", "rr_mlp_value_backward", "rr_mlp_weight_grad_workspace_bytes", "rr_mlp_weight_grad", "rr_mlp_weight_grad_batch_workspace_bytes", "rr_mlp_weight_grad_batch", "rr_obs_moments_workspace_bytes", "rr_obs_moments", "rr_wrap_episode_autoreset", "rr_debug_layout", "rr_batch_set_schedule", "rr_batch_set_env_params", "rr_batch_env_params_supported", "rr_batch_set_profile", "rr_batch_set_ls_repeat_exit", "rr_batch_set_solver_trim", "rr_batch_set_solver_batch", "rr_batch_set_solve_resident", "rr_model_solve_resident_switch", "rr_batch_set_root_slot", "rr_model_root_slot_switch", "rr_batch_set_timing", "rr_batch_kernel_time", "rr_last_error"]
 
 _lib = None
@@ -185,6 +192,8 @@ def lib():
         L.rr_batch_reference_obs_supported.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
         L.rr_batch_set_pose_termination.argtypes = [C.c_void_p, C.POINTER(RRPoseTermIO)]
         L.rr_batch_pose_termination_supported.argtypes = [C.c_void_p, C.c_int32]
+        L.rr_batch_set_body_tracking.argtypes = [C.c_void_p, C.POINTER(RRBodyIO)]
+        L.rr_batch_body_tracking_supported.argtypes = [C.c_void_p, C.c_int32]
         L.rr_batch_set_ls_repeat_exit.argtypes = [C.c_void_p, C.c_int32]
         L.rr_batch_set_solver_trim.argtypes = [C.c_void_p, C.c_int32]
         L.rr_batch_set_solver_batch.argtypes = [C.c_void_p, C.c_int32]
@@ -298,6 +307,7 @@ class Batch:
         self.h = C.c_void_p()
         self._pose = None           # the tensors of the pose block in force (set_pose)
         self._pterm = None          # the tensor of the pose-termination block in force (set_pose_termination)
+        self._body = None           # the tensors of the body-tracking block in force (set_body_tracking)
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream().cuda_stream
         _check(lib().rr_batch_create(model.h, self.N, self.device.index or 0, C.c_void_p(stream), C.byref(self.h)))
@@ -360,6 +370,9 @@ class Batch:
         fail = env.get("pose_fail")         # pose termination rides there too: the code array [N] and `pose_termination` = the three thresholds
         if fail is None and self._pterm is not None:        # cleared BEFORE the pose block may go: the library keeps the pose block while it stands
             self.set_pose_termination(None)
+        bodies = env.get("track_bodies")    # body tracking likewise: [(C), T, nbody, 3] next to `body_weights` [2, nbody] and `body_metrics` [N, 2]
+        if bodies is None and self._body is not None:
+            self.set_body_tracking(None)
         pose = env.get("track_pose")
         if pose is not None:        # [T, nq - 3] rows (quaternion, joints), or [C, T, nq - 3] next to a [C, T, 3] track_pos
             if tuple(pose.shape) != tuple(tp.shape[:-1]) + (d.nq - 3,):
@@ -369,6 +382,11 @@ class Batch:
             self.set_pose(None)
         if fail is not None:
             self.set_pose_termination(fail, env.get("pose_termination", (math.inf, math.inf, math.inf)))
+        if bodies is not None:
+            if tuple(bodies.shape) != tuple(tp.shape[:-1]) + (d.nbody, 3):
+                raise ValueError(f"env io: track_bodies has shape {tuple(bodies.shape)}, expected {tuple(tp.shape[:-1]) + (d.nbody, 3)}")
+            self.set_body_tracking(bodies, env.get("body_weights"), env.get("body_metrics"), env.get("body_reward", (1.0, 8.0)),
+                                   env.get("endeff_reward", (1.0, 100.0)))
         return e
 
     # ------------------------------------------------------------------ C-ABI calls
@@ -526,6 +544,32 @@ class Batch:
         t = RRPoseTermIO(_ptr(fail, numel=self.N), *(float(x) for x in thresholds), 0)
         _check(lib().rr_batch_set_pose_termination(self.h, C.byref(t)))
         self._pterm = fail
+
+    def set_body_tracking(self, track_bodies: Optional[torch.Tensor], body_weights: Optional[torch.Tensor] = None,
+                          body_metrics: Optional[torch.Tensor] = None, body_reward=(1.0, 8.0), endeff_reward=(1.0, 100.0)):
+        """The body-tracking block of this batch's later env steps (C ABI `rr_batch_set_body_tracking`): `track_bodies` [(C), T, nbody, 3]
+        the clip's global body positions, `body_weights` [2, nbody] the 0 / 1 masks of the tracked bodies and of the end effectors,
+        `body_metrics` [N, 2] out (body_reward, endeff_reward); `body_reward` / `endeff_reward` = (weight, scale); None clears it.
+        Needs the pose block (`set_pose`).  The env-io dict of a launch (`track_bodies`, `body_weights`, `body_metrics`, `body_reward`,
+        `endeff_reward` keys) sets or clears it by itself.  The batch keeps the tensors alive."""
+        if track_bodies is None:
+            _check(lib().rr_batch_set_body_tracking(self.h, None))
+            self._body = None
+            return
+        nb = self.dims.nbody
+        if track_bodies.dim() < 3 or tuple(track_bodies.shape[-2:]) != (nb, 3):
+            raise ValueError(f"track_bodies has shape {tuple(track_bodies.shape)}, expected [(C), T, {nb}, 3]")
+        t = RRBodyIO(_ptr(track_bodies), _ptr(body_weights, numel=2 * nb), _ptr(body_metrics, numel=2 * self.N),
+                     float(body_reward[0]), float(body_reward[1]), float(endeff_reward[0]), float(endeff_reward[1]))
+        _check(lib().rr_batch_set_body_tracking(self.h, C.byref(t)))
+        self._body = (track_bodies, body_weights, body_metrics)
+
+    def body_tracking_supported(self, with_actor: bool = False) -> Optional[str]:
+        """None when this batch serves body tracking at its frame count (C ABI `rr_batch_body_tracking_supported`) -- with
+        `with_actor` also in the one-launch rollout with the actor inside -- else the refusal's text."""
+        if _check(lib().rr_batch_body_tracking_supported(self.h, int(with_actor))) == 1:
+            return None
+        return lib().rr_last_error().decode()
 
     def pose_termination_supported(self, with_actor: bool = False) -> Optional[str]:
         """None when this batch serves pose termination at its frame count (C ABI `rr_batch_pose_termination_supported`) -- with

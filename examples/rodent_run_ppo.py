@@ -69,6 +69,12 @@ def main():
                     "radians from the clip's (Rodent(max_quat_error=RAD))")
     ap.add_argument("--max-joint-error", type=float, default=None, metavar="RAD", help="with --track-pose: ... whose joint angles are more than RAD "
                     "radians (2-norm over the joints) from the clip's (Rodent(max_joint_error=RAD))")
+    ap.add_argument("--track-bodies", action="store_true", help="with --track-pose: reward the clip's body positions too (Rodent(track_bodies=..., "
+                    "untuned default weights): every body of the model, from the clip's body_positions; the synthetic line gets the forward "
+                    "kinematics of its own poses")
+    ap.add_argument("--end-effector-ids", type=int, nargs="+", default=None, metavar="ID", help="with --track-bodies: body ids of the end effectors, "
+                    "which get a sharper term of their own (Rodent(end_effector_ids=...)).  The model blobs hold no body names: on "
+                    "rodent_optimized / rodent_0 foot_L, foot_R, hand_L, hand_R, skull are 11 15 59 64 54, on rodent_new each is one higher")
     ap.add_argument("--policy-width", type=int, choices=(32, 256), default=32, help="units per hidden layer of the policy network; both "
                     "widths run on the hand-written learner kernels (256: per-step rollouts, the in-kernel actor is 32-wide)")
     ap.add_argument("--policy-depth", type=int, default=4, help="hidden layers of the policy network (1 .. 7 for the hand-written kernels; "
@@ -96,6 +102,10 @@ def main():
             ap.error(f"--{flag.replace('_', '-')}: the errors are taken against the reference pose; add --track-pose")
         if getattr(args, flag) is not None and not getattr(args, flag) > 0:
             ap.error(f"--{flag.replace('_', '-')}: must be > 0")
+    if args.track_bodies and not args.track_pose:
+        ap.error("--track-bodies: the body positions are indexed like the reference pose; add --track-pose")
+    if args.end_effector_ids is not None and not args.track_bodies:
+        ap.error("--end-effector-ids: the end effectors are bodies of the clip; add --track-bodies")
     if not 0 <= args.reference_frames <= 16:
         ap.error("--reference-frames: 0 .. 16")
     clips = None                                     # the loaded ReferenceClip(s), [C, T, ...] fields; None for a .npy track or the synthetic line
@@ -121,6 +131,18 @@ def main():
             rest = np.asarray(mjcf.load_blob(assets.resolve_model(args.xml))["qpos0"], np.float64)[7:]
             lead = track_pos.shape[:-1]
             pose = dict(track_quat=np.broadcast_to([1.0, 0.0, 0.0, 0.0], lead + (4,)), track_joints=np.broadcast_to(rest, lead + rest.shape))
+
+    if args.track_bodies:
+        if clips is not None:
+            bodies = np.asarray(clips.body_positions)
+            bodies = bodies[0] if track_pos.ndim == 2 else bodies
+        else:                                        # the synthetic line: forward kinematics of (track position, upright, rest joints) per frame
+            probe = envs.Rodent(track_pos=track_pos, num_envs=1, xml_path=args.xml, device=f"cuda:{local_rank}")
+            lead = track_pos.shape[:-1]
+            qpos = np.concatenate([track_pos, pose["track_quat"], pose["track_joints"]], axis=-1).reshape(-1, probe.sys.nq)
+            bodies = preprocessing.extract_features(probe, qpos).body_positions
+            bodies = bodies.reshape(lead + bodies.shape[1:])
+        pose.update(track_bodies=bodies, end_effector_ids=args.end_effector_ids)
 
     envs.register_environment("rodent", envs.Rodent)
     env = envs.get_environment(

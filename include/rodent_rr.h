@@ -331,6 +331,37 @@ typedef struct rr_pose_term_io {
 int rr_batch_set_pose_termination(rr_batch* b, const rr_pose_term_io* term);
 int rr_batch_pose_termination_supported(const rr_batch* b, int32_t with_actor);
 
+/* Body tracking: the reward also scores the clip's body positions, and a sharper term its end effectors.  The block is set on the BATCH,
+ * next to the pose block it needs (rr_env_io, rr_pose_io and rr_pose_term_io are closed), and read by every later env step of it --
+ * rr_env_step(_to), rr_env_unroll and rr_env_unroll_policy -- until it is replaced or cleared (NULL; a batch starts without one); a
+ * launch takes the pointers as they are when it is issued.  track_bodies is [T][nbody][3] (with clip ids [num_clips][T][nbody][3]),
+ * global body-frame origins, indexed like track_pose; body_weights is [2][nbody] floats, row 0 the 0 / 1 mask of the tracked bodies B,
+ * row 1 that of the end effectors E (entry 0, the world, is not read).  An env step (never a reset) forms, with xpos the body positions
+ * of its last forward pass -- what rr_outputs.xpos returns: the pose before the last substep's integration -- and r the row of the clip
+ * and frame its position and pose rewards read:
+ *   S_B = sum_{b in B} |xpos[b] - r[b]|^2,   S_E = the same over E
+ *   body_reward   = body_reward_weight   exp(-body_reward_scale   S_B)
+ *   endeff_reward = endeff_reward_weight exp(-endeff_reward_scale S_E)
+ *   reward = (((plain + quat_reward) + joint_reward) + body_reward) + endeff_reward;   body_metrics[e] = (body_reward, endeff_reward)
+ * every product and sum rounded to float32 on its own.  done, cur_frame, obs, the state, metrics, pose_metrics and pose_fail are what they
+ * are without the block; a bad step (bad_state_max) zeroes body_metrics with the others.  rr_env_reset ignores the block.
+ * rr_batch_set_body_tracking: no pose block on the batch (rr_batch_set_pose first), a NULL pointer, or a weight or scale that is negative
+ * or not finite: RR_EINVAL; RR_EUNSUPPORTED with the reason wherever pose tracking is unsupported.  While the block is set,
+ * rr_batch_set_pose(b, NULL) is RR_EINVAL (clear this block first), and what refuses a pose block refuses here: rr_env_unroll_eval,
+ * per-env parameters, the debug dump, contact-geometry outputs and the profile build.  The env steps run the reference-observation
+ * instances' code whatever the frame count (0 .. 16), so rr_env_unroll_policy serves rows of up to 1664 entries; a pose-termination
+ * block may stand next to this one or not.
+ * rr_batch_body_tracking_supported(b, with_actor): 1 / 0 -- whether the batch serves the block with its current frame count
+ * (with_actor != 0: also in rr_env_unroll_policy); with 0 rr_last_error holds the reason.  It does not need the pose block to be set. */
+typedef struct rr_body_io {
+  const float* track_bodies;   /* [(C)][T][nbody][3] */
+  const float* body_weights;   /* [2][nbody]: row 0 the mask of B, row 1 that of E */
+  float* body_metrics;         /* [N][2] out: (body_reward, endeff_reward) */
+  float body_reward_weight, body_reward_scale, endeff_reward_weight, endeff_reward_scale;
+} rr_body_io;
+int rr_batch_set_body_tracking(rr_batch* b, const rr_body_io* body);
+int rr_batch_body_tracking_supported(const rr_batch* b, int32_t with_actor);
+
 /* Generalised advantage estimation of one PPO minibatch, the reverse scan of brax.training.agents.ppo.losses.compute_gae
  * [UP; SURVEY.md Appendix E], one thread per trajectory.  All arrays time-major [T][B] device float32; bootstrap [B];
  * outputs vs [T][B] and advantages [T][B].  `stream` is a hipStream_t (NULL = default stream). */
