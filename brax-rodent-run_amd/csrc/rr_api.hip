@@ -59,7 +59,7 @@ struct rr_model {
 // One function maps (model, launch form, variant) to the kernel instance that serves it, or to the reason there is none: launch(),
 // the support queries and the attribute loop of rr_batch_create all ask it, so none of them can disagree about what exists.
 enum Form { F_STEP, F_UNROLL, F_ACTOR, F_EVAL, N_FORMS };                        // single step | multi-step | ... with the actor | evaluation
-enum Variant { V_PROD, V_DEBUG, V_PROFILE, V_RAND, V_PAIR, V_POSE, V_MATLDS, V_REFOBS, V_POSETERM, V_TWOSLOT, V_BODY, N_VARIANTS }; // production | debug dump | cycle-stamp profile | per-env parameters | two-wave pair | pose tracking | production, inverse factor read from LDS | pose tracking with the reference observation | ... and with pose termination | production, tree phases on the plain lane <-> body map | pose tracking with the body-position terms (a superset of the pose-termination form)
+enum Variant { V_PROD, V_DEBUG, V_PROFILE, V_RAND, V_PAIR, V_POSE, V_MATLDS, V_REFOBS, V_POSETERM, V_TWOSLOT, V_BODY, V_RESTART, N_VARIANTS }; // production | debug dump | cycle-stamp profile | per-env parameters | two-wave pair | pose tracking | production, inverse factor read from LDS | pose tracking with the reference observation | ... and with pose termination | production, tree phases on the plain lane <-> body map | pose tracking with the body-position terms (a superset of the pose-termination form) | ... with the restore from the bank of start states (multi-step forms only; a superset of the body-tracking form)
 struct Instance { kern_t kern; const char* why = nullptr; bool fixed = false; };      // why: the reason when kern is null (multi-step forms: with the entry point that reports it); fixed: compiled for the model's dimensions
 
 // The shape the root-slot tree phases need beyond the dimensions (rr_kernel.h Wave::ROOT): one tree; body 1 is the child of the world and
@@ -87,7 +87,7 @@ static Instance select(const rr_model* m, Form form, Variant v) {
   const char *no_diag = "no diagnostic kernel instance for this model", *no_slots = "no kernel instance for this model's slot counts";
   auto no = [](const char* why) { return Instance{nullptr, why}; };
   // rr_step_kernel<NBS, NVS, NCS, PROF, DBG, dims, NEWTON, UNROLL, ACTOR, PAIR, DYN>, rr_rand_kernel<dims, UNROLL, ACTOR>, rr_eval_kernel<dims, DYN>,
-  // rr_pose_kernel<dims, UNROLL, ACTOR>, rr_refobs_kernel<dims, UNROLL, ACTOR>, rr_poseterm_kernel<dims, UNROLL, ACTOR>, rr_body_kernel<dims, UNROLL, ACTOR>, rr_matlds_kernel<dims>, rr_twoslot_kernel<dims>
+  // rr_pose_kernel<dims, UNROLL, ACTOR>, rr_refobs_kernel<dims, UNROLL, ACTOR>, rr_poseterm_kernel<dims, UNROLL, ACTOR>, rr_body_kernel<dims, UNROLL, ACTOR>, rr_restart_kernel<dims, ACTOR>, rr_matlds_kernel<dims>, rr_twoslot_kernel<dims>
   if (v == V_PAIR && (unroll || newton || !RRDimsRodentNew::matches(m->kd_rep))) return no("no two-wave pair instance for this model / launch form");
   if (v == V_PAIR) return {rr_step_kernel<2, 2, 1, false, false, RRDimsRodentNew, false, false, false, true>, nullptr, true};      // one replica = the rodent_new dims
   if (v == V_MATLDS) {      // rr_batch_set_solve_resident(b, 0): the production single-step instance of the benchmark model's dimensions, solves from LDS
@@ -116,7 +116,8 @@ static Instance select(const rr_model* m, Form form, Variant v) {
     if (v == V_REFOBS) return no("rr_env_unroll_eval: no evaluation instance writes the reference observation (rr_batch_set_reference_obs is on); evaluate step by step");
     if (v == V_POSETERM) return no("rr_env_unroll_eval: no evaluation instance ends episodes on the pose error (rr_batch_set_pose_termination is on); evaluate step by step");
     if (v == V_BODY) return no("rr_env_unroll_eval: no evaluation instance rewards the body positions (rr_batch_set_body_tracking is on); evaluate step by step");
-  } else if (v == V_POSE || v == V_REFOBS || v == V_POSETERM || v == V_BODY) {
+    if (v == V_RESTART) return no("rr_env_unroll_eval: no evaluation instance restores from the bank of start states (rr_batch_set_clip_restarts is on); evaluate step by step");
+  } else if (v == V_POSE || v == V_REFOBS || v == V_POSETERM || v == V_BODY || v == V_RESTART) {
     // Pose tracking (rr_pose_kernel; with the reference observation rr_refobs_kernel; with pose termination rr_poseterm_kernel; with the
     // body-position terms rr_body_kernel): the same
     // models and launch forms as the per-env parameters below, shared tables
@@ -124,6 +125,7 @@ static Instance select(const rr_model* m, Form form, Variant v) {
     if (m->pair_ok) return no("pose tracking: two-tree models served by the two-wave pair instance have no pose instance");
     if (newton) return no("pose tracking: the Newton solver's instances have no pose instance");
     if (!s221) return no("pose tracking: only the (2,2,1) slot counts have pose instances");
+    if (v == V_RESTART && !unroll) return no("clip restarts: the restore lives in the multi-step instances (rr_env_unroll, rr_env_unroll_policy); a single step has none");
   } else if (v == V_RAND) {
     // Per-environment parameters (rr_rand_kernel): the production CG instances of the single-rodent floor-contact models -- fixed-dimension
     // or generic (2,2,1) -- as single-step, multi-step and multi-step with the actor
@@ -157,6 +159,7 @@ static Instance select(const rr_model* m, Form form, Variant v) {
     if (v == V_REFOBS) return actor ? rr_refobs_kernel<DT, true, true> : (unroll ? rr_refobs_kernel<DT, true> : rr_refobs_kernel<DT>);
     if (v == V_POSETERM) return actor ? rr_poseterm_kernel<DT, true, true> : (unroll ? rr_poseterm_kernel<DT, true> : rr_poseterm_kernel<DT>);
     if (v == V_BODY) return actor ? rr_body_kernel<DT, true, true> : (unroll ? rr_body_kernel<DT, true> : rr_body_kernel<DT>);
+    if (v == V_RESTART) return actor ? rr_restart_kernel<DT, true> : rr_restart_kernel<DT>;
     return actor ? rr_step_kernel<2, 2, 1, false, false, DT, false, true, true> : (unroll ? rr_step_kernel<2, 2, 1, false, false, DT, false, true> : rr_step_kernel<2, 2, 1, false, false, DT>);
   };
   if (rodent_fixed(m)) return {family((RRDimsRodent*)nullptr), nullptr, true};      // fixed-dimension instances (rr_kernel.h RRDimsFixed)
@@ -404,6 +407,7 @@ struct rr_batch {
   rr_pose_term_io pterm = {};           // pose termination of the env steps (rr_batch_set_pose_termination); fail null: off; set only with a pose block
   bool plain_slots = false;             // rr_batch_set_root_slot(b, 0): production single-step launches run rr_twoslot_kernel
   rr_body_io body = {};                 // body tracking of the env steps (rr_batch_set_body_tracking); track_bodies null: off; set only with a pose block
+  rr_clip_restart_io restart = {};      // clip restarts of the multi-step launches (rr_batch_set_clip_restarts); frames null: off; set only with a pose block
   bool solve_lds = false;               // rr_batch_set_solve_resident(b, 0): production single-step launches run rr_matlds_kernel
   bool has_env_params() const { return env_dof_f || env_act_f || env_con_f; }
 };
@@ -630,7 +634,7 @@ static int fill_io(const Launch& L, RRIO& io) {
 // launch() step 3: the fields of the multi-step forms -- wrappers' state, actor, evaluation, pacing
 static int fill_unroll(rr_batch* b, const Launch& L, RRIO& io) {
   if (const rr_actor_io* ac = L.ac) {
-    if (const char* limit = actor_limit(b->m, ac, io.ref_frames, io.pose_fail != nullptr || io.track_bodies != nullptr)) return fail(RR_EUNSUPPORTED, limit);
+    if (const char* limit = actor_limit(b->m, ac, io.ref_frames, io.pose_fail != nullptr || io.track_bodies != nullptr || io.restart_frames != nullptr)) return fail(RR_EUNSUPPORTED, limit);
     io.a_obs_in = ac->obs_in; io.a_mean = ac->mean; io.a_std = ac->std; io.a_W0 = ac->w0; io.a_b0 = ac->b0;
     for (int l = 1; l < ac->nhidden; ++l) { io.a_Wt[l - 1] = ac->hidden_wt[l - 1]; io.a_b[l - 1] = ac->hidden_b[l - 1]; }
     io.a_Wth = ac->head_wt; io.a_bh = ac->head_b; io.a_noise = ac->noise; io.a_actions = ac->actions_out; io.ctrl = ac->actions_out;
@@ -689,7 +693,16 @@ static int launch(rr_batch* b, const Launch& L) {
   // body tracking (rr_batch_set_body_tracking): env steps only, as pose termination; served by the BODY instance, a superset of the PTERM
   // instance: without a termination block it gets a null pose_fail and thresholds that no error exceeds
   const bool body = b->body.track_bodies && b->pose.track_pose && L.env && L.mode == 1;
+  // clip restarts (rr_batch_set_clip_restarts): the multi-step launches of the training wrappers only -- single steps have no restore in
+  // the kernel, the evaluation form none from a bank -- served by the RESTART instance, a superset of the BODY instance: without a
+  // body-tracking block it gets a null track_bodies, without a termination block what the BODY instance gets
+  const bool restart = b->restart.frames && b->pose.track_pose && L.env && L.mode == 1 && L.un && !L.ev;
   if (refobs) io.ref_frames = b->ref_frames;
+  if (restart) {
+    io.restart_frames = b->restart.frames; io.restart_slot_in = b->restart.slot_in; io.restart_slot_out = b->restart.slot_out;
+    io.restart_K = b->restart.num_slots; io.restart_end = b->restart.end_at_clip_end ? 1 : 0;
+    io.pose_max_pos = io.pose_max_quat = io.pose_max_joint = INFINITY;
+  }
   if (body) {
     io.track_bodies = b->body.track_bodies; io.body_weights = b->body.body_weights; io.body_metrics = b->body.body_metrics;
     io.body_w = b->body.body_reward_weight; io.body_k = b->body.body_reward_scale; io.endeff_w = b->body.endeff_reward_weight; io.endeff_k = b->body.endeff_reward_scale;
@@ -703,7 +716,7 @@ static int launch(rr_batch* b, const Launch& L) {
   }
   if (pose && params) return fail(RR_EUNSUPPORTED, "launch: pose tracking: no pose instance reads per-env parameters (this batch carries some)");
   if (pose && (io.dbg || geom || b->prof)) return fail(RR_EUNSUPPORTED, "launch: pose tracking: no debug dump, contact-geometry outputs or profile build with track_pose (diagnostic instances have no pose form)");
-  Variant v = b->prof ? V_PROFILE : ((io.dbg || geom) ? V_DEBUG : (params ? V_RAND : (body ? V_BODY : (pterm ? V_POSETERM : (refobs ? V_REFOBS : (pose ? V_POSE : V_PROD))))));
+  Variant v = b->prof ? V_PROFILE : ((io.dbg || geom) ? V_DEBUG : (params ? V_RAND : (restart ? V_RESTART : (body ? V_BODY : (pterm ? V_POSETERM : (refobs ? V_REFOBS : (pose ? V_POSE : V_PROD)))))));
   // two-tree model, physics only, no diagnostics: one wavefront per replica (rr_kernel.h PAIR)
   const bool pair = m->pair_ok && v == V_PROD && !L.env && !L.out && !L.un && !b->env_map && !b->cost && m->solver != 2;
   if (pair) v = V_PAIR;
@@ -791,7 +804,7 @@ extern "C" int rr_env_unroll_policy(rr_batch* b, const rr_state* in, const rr_st
 }
 extern "C" int rr_batch_eval_supported(const rr_batch* b) {
   if (!b) return fail(RR_EINVAL, "rr_batch_eval_supported: null batch");
-  const Variant v = b->prof ? V_PROFILE : (b->has_env_params() ? V_RAND : (b->body.track_bodies ? V_BODY : (b->pterm.fail ? V_POSETERM : (b->ref_frames > 0 ? V_REFOBS : V_PROD))));
+  const Variant v = b->prof ? V_PROFILE : (b->has_env_params() ? V_RAND : (b->restart.frames ? V_RESTART : (b->body.track_bodies ? V_BODY : (b->pterm.fail ? V_POSETERM : (b->ref_frames > 0 ? V_REFOBS : V_PROD)))));
   return (select(b->m, F_EVAL, v).kern && !actor_limit(b->m, nullptr)) ? 1 : 0;
 }
 extern "C" int rr_env_unroll_eval(rr_batch* b, const rr_state* in, const rr_state* outst, int32_t num_steps, int32_t n_frames, const rr_env_io* env,
@@ -1350,6 +1363,58 @@ extern "C" int rr_wrap_episode_autoreset(int32_t num_envs, int32_t narr, const f
   return RR_OK;
 }
 
+// The same with clip restarts (rr_clip_restart_io's rule, one env step): `first[i]` are banks [num_slots][N][widths[i]], the clip's end joins
+// `over`, and where done the next bank entry and its frame come back.  cur_frame holds the stepped frame and is finished in place.
+__global__ void rr_wrap_restart_kernel(const RRWrapArgs A, const float* __restrict__ prev_done, const float* __restrict__ prev_steps,
+                                       float* __restrict__ done, float* __restrict__ steps, float* __restrict__ truncation,
+                                       float episode_length, float action_repeat, int* __restrict__ cur_frame, const int* __restrict__ bank_frames,
+                                       const int* __restrict__ slot_in, int* __restrict__ slot_out, int num_slots, int track_len, int end_at_clip_end) {
+  const int e = blockIdx.x, N = gridDim.x;
+  const float s0 = prev_done[e] != 0.0f ? 0.0f : prev_steps[e];
+  const float s1 = s0 + action_repeat;
+  const int new_frame = cur_frame[e];
+  const bool over = s1 >= episode_length || (end_at_clip_end && new_frame >= track_len - 1);
+  const float d_env = done[e];
+  const float d_out = over ? 1.0f : d_env;
+  int slot = slot_in[e];
+  slot = slot < 0 ? 0 : (slot > num_slots - 1 ? num_slots - 1 : slot);      // clamped into the bank
+  if (d_out != 0.0f) slot = slot + 1 >= num_slots ? 0 : slot + 1;
+  const size_t row = (size_t)slot * N + e;
+  const int frame = d_out != 0.0f ? bank_frames[row] : new_frame;
+  __syncthreads();                       // every thread has read done[e] and cur_frame[e] before thread 0 rewrites them
+  if (threadIdx.x == 0) { steps[e] = s1; truncation[e] = over ? 1.0f - d_env : 0.0f; done[e] = d_out; cur_frame[e] = frame; slot_out[e] = slot; }
+  if (d_out != 0.0f) {
+    for (int a = 0; a < A.narr; ++a) {
+      const int w = A.width[a];
+      const float* src = A.first[a] + row * w;
+      float* dst = A.cur[a] + (size_t)e * w;
+      for (int i = threadIdx.x; i < w; i += blockDim.x) dst[i] = src[i];
+    }
+  }
+}
+
+extern "C" int rr_wrap_clip_restart(int32_t num_envs, int32_t narr, const float* const* first, float* const* cur, const int32_t* widths,
+                                    const float* prev_done, const float* prev_steps, float* done, float* steps, float* truncation,
+                                    float episode_length, float action_repeat, int32_t* cur_frame, const int32_t* bank_frames,
+                                    const int32_t* slot_in, int32_t* slot_out, int32_t num_slots, int32_t track_len, int32_t end_at_clip_end,
+                                    void* stream) {
+  if (num_envs <= 0 || narr < 0 || narr > RR_WRAP_MAX || !prev_done || !prev_steps || !done || !steps || !truncation || !cur_frame || !bank_frames ||
+      !slot_in || !slot_out || track_len <= 0)
+    return fail(RR_EINVAL, "rr_wrap_clip_restart: bad argument");
+  if (num_slots < 1 || num_slots > 64) return fail(RR_EINVAL, "rr_wrap_clip_restart: num_slots must lie in 1 .. 64");
+  RRWrapArgs A;
+  memset(&A, 0, sizeof(A));
+  A.narr = narr;
+  for (int i = 0; i < narr; ++i) {
+    if (!first[i] || !cur[i] || widths[i] <= 0) return fail(RR_EINVAL, "rr_wrap_clip_restart: null array");
+    A.first[i] = first[i]; A.cur[i] = cur[i]; A.width[i] = widths[i];
+  }
+  hipLaunchKernelGGL(rr_wrap_restart_kernel, dim3(num_envs), dim3(256), 0, (hipStream_t)stream, A, prev_done, prev_steps, done, steps, truncation,
+                     episode_length, action_repeat, cur_frame, bank_frames, slot_in, slot_out, num_slots, track_len, end_at_clip_end);
+  HIPCHK(hipGetLastError());
+  return RR_OK;
+}
+
 extern "C" int rr_debug_layout(const rr_batch* b, const char*** names, const int32_t** offsets, const int32_t** sizes) {
   if (!b) return fail(RR_EINVAL, "rr_debug_layout: null batch");
   if (names) *names = const_cast<const char**>(b->m->dbg_cnames.data());
@@ -1386,6 +1451,7 @@ extern "C" int rr_batch_set_pose(rr_batch* b, const rr_pose_io* p) {
   if (!b) return fail(RR_EINVAL, "rr_batch_set_pose: null batch");
   if (!p || (!p->track_pose && !p->pose_metrics)) {
     if (b->ref_frames > 0) return fail(RR_EINVAL, "rr_batch_set_pose: the batch carries reference frames (rr_batch_set_reference_obs), whose rows come from the pose block: set them to 0 first");
+    if (b->restart.frames) return fail(RR_EINVAL, "rr_batch_set_pose: the batch carries a clip-restart block (rr_batch_set_clip_restarts), which serves pose envs only: clear it first");
     if (b->body.track_bodies) return fail(RR_EINVAL, "rr_batch_set_pose: the batch carries a body-tracking block (rr_batch_set_body_tracking), whose rows are indexed like the pose block's: clear it first");
     if (b->pterm.fail) return fail(RR_EINVAL, "rr_batch_set_pose: the batch carries a pose-termination block (rr_batch_set_pose_termination), whose errors come from the pose block: clear it first");
     b->pose = rr_pose_io{};
@@ -1472,6 +1538,31 @@ extern "C" int rr_batch_set_body_tracking(rr_batch* b, const rr_body_io* t) {
   for (float x : {t->body_reward_weight, t->body_reward_scale, t->endeff_reward_weight, t->endeff_reward_scale})
     if (!(x >= 0.0f) || !std::isfinite(x)) return fail(RR_EINVAL, "rr_batch_set_body_tracking: weights and scales must be finite and >= 0");
   b->body = *t;
+  return RR_OK;
+}
+// Clip restarts: wherever pose tracking is served in the multi-step forms, at the batch's frame count; with_actor also asks the width the
+// actor of the reference-observation instances reads
+static const char* restart_limit(const rr_batch* b, bool with_actor) {
+  const Instance in = select(b->m, with_actor ? F_ACTOR : F_UNROLL, V_RESTART);
+  if (!in.kern) return in.why;
+  if (b->has_env_params()) return "pose tracking: no pose instance reads per-env parameters (this batch carries some)";
+  if (b->prof) return "pose tracking: no profile build with track_pose";
+  return with_actor ? actor_limit(b->m, nullptr, b->ref_frames, true) : nullptr;
+}
+extern "C" int rr_batch_clip_restarts_supported(const rr_batch* b, int32_t with_actor) {
+  if (!b) return fail(RR_EINVAL, "rr_batch_clip_restarts_supported: null batch");
+  const char* why = restart_limit(b, with_actor != 0);
+  if (why) (void)fail(RR_EUNSUPPORTED, std::string("rr_batch_clip_restarts_supported: ") + why);
+  return why ? 0 : 1;
+}
+extern "C" int rr_batch_set_clip_restarts(rr_batch* b, const rr_clip_restart_io* r) {
+  if (!b) return fail(RR_EINVAL, "rr_batch_set_clip_restarts: null batch");
+  if (!r) { b->restart = rr_clip_restart_io{}; return RR_OK; }
+  if (const char* why = restart_limit(b, false)) return fail(RR_EUNSUPPORTED, std::string("rr_batch_set_clip_restarts: ") + why);
+  if (!b->pose.track_pose) return fail(RR_EINVAL, "rr_batch_set_clip_restarts: needs a pose block (rr_batch_set_pose) first: clip restarts serve pose envs only");
+  if (!r->frames || !r->slot_in || !r->slot_out) return fail(RR_EINVAL, "rr_batch_set_clip_restarts: null frames, slot_in or slot_out");
+  if (r->num_slots < 1 || r->num_slots > 64) return fail(RR_EINVAL, "rr_batch_set_clip_restarts: num_slots must lie in 1 .. 64");
+  b->restart = *r;
   return RR_OK;
 }
 extern "C" int32_t rr_batch_obs_width(const rr_batch* b) {

@@ -312,6 +312,18 @@ struct RRIO {
   const float* body_weights;   // [2][nbody]
   float* body_metrics;         // [N][2]
   float body_w, body_k, endeff_w, endeff_k;
+  // CLIP RESTARTS (RESTART instances, rr_restart_kernel; no other instance reads these): a restarted episode rejoins its clip.  The
+  // first_* arrays of the launch are then a BANK of restart_K start states, [K][N][width] each, restart_frames [K][N] the frame each was
+  // formed at, and the env carries a slot (wave-uniform, next to u_steps / u_frame).  Per wrapped env step, new_frame = old_frame + 1:
+  //   over = steps' >= episode_length || (restart_end && new_frame >= track_len - 1)
+  //   done: slot' = (slot + 1) mod K, state and observation <- bank[slot'], cur_frame <- restart_frames[slot'];  else slot, new_frame
+  // The step that ends the episode is untouched (its reward, metrics and pose_fail read old_frame); cur_frame and the slot of the
+  // launch's last step go out with the final state.  Fetched by narrow loads where they are used (load_io_member).
+  const int* restart_frames;   // [K][N]
+  const int* restart_slot_in;  // [N]
+  int* restart_slot_out;       // [N]
+  int restart_K;               // 1 .. 64
+  int restart_end;             // != 0: the clip's end (no next frame left to read without clamping) truncates the episode
 };
 
 // ------------------------------------------------------------------------------------------ small math
@@ -2636,7 +2648,9 @@ static_assert(offsetof(RRIO, ref_pad) + sizeof(int) == offsetof(RRIO, pose_fail)
 static_assert(offsetof(RRIO, pose_fail) + sizeof(float*) == offsetof(RRIO, pose_max_pos), "the thresholds follow pose_fail without padding");
 static_assert(offsetof(RRIO, pterm_pad) + sizeof(int) == offsetof(RRIO, track_bodies) && offsetof(RRIO, track_bodies) % 8 == 0, "the body-tracking members follow the pose-termination members without padding");
 static_assert(offsetof(RRIO, track_bodies) + 3 * sizeof(float*) == offsetof(RRIO, body_w), "the weights and scales follow the three body-tracking pointers without padding");
-static_assert(offsetof(RRIO, endeff_k) + sizeof(float) == sizeof(RRIO), "the body-tracking members close RRIO without padding");
+static_assert(offsetof(RRIO, endeff_k) + sizeof(float) == offsetof(RRIO, restart_frames) && offsetof(RRIO, restart_frames) % 8 == 0, "the clip-restart members follow the body-tracking members without padding");
+static_assert(offsetof(RRIO, restart_frames) + 3 * sizeof(int*) == offsetof(RRIO, restart_K), "the slot count follows the three clip-restart pointers without padding");
+static_assert(offsetof(RRIO, restart_end) + sizeof(int) == sizeof(RRIO), "the clip-restart members close RRIO without padding");
 // ... and so are the model tables outside the solver's loops: RRTables is re-read at the head of each phase that indexes a table
 // (narrow scalar loads next to an existing hand-off; the unused members' loads are dead), so no table pointer is held across the
 // substep.  The loops' own tables are the exception (RRLoopTables, taken once from the parameter).
@@ -2826,7 +2840,7 @@ __device__ __forceinline__ void rr_actor_step(const RRIO& io, const DT& D, int l
 template <int NBS, int NVS, int NCS, bool PROF, bool DBG, class DT, bool NEWTON = false, bool UNROLL = false, bool ACTOR = false, bool PAIR = false, bool DYN = false>
 __global__ __launch_bounds__((PAIR ? 2 : 1) * RR_LANES, (NVS >= 3 ? 1 : 2)) void rr_step_kernel(const RRDims Dk, const RRTables Tk, const RRIO io_kernarg, const int num_envs,
                                                            const int n_frames) {
-  constexpr bool RAND = false, EVAL = false, POSE = false, REFOBS = false, PTERM = false, BODY = false;
+  constexpr bool RAND = false, EVAL = false, POSE = false, REFOBS = false, PTERM = false, BODY = false, RESTART = false;
   constexpr bool ROOTSLOT = rr_root_slot<DT>::value && NBS == 2 && !NEWTON && !PAIR && !DYN;      // the root body alone in the second body slot (Wave::ROOT)
   constexpr int MRES = ACTOR ? 1 : 2;      // resident inverse-factor entries (Wave::MAT_RES): both sides at 245-253 registers (timed: -1.4 % against the column side alone); with the actor the column side (233)
 #include "rr_step_body.inc"
@@ -2836,7 +2850,7 @@ __global__ __launch_bounds__((PAIR ? 2 : 1) * RR_LANES, (NVS >= 3 ? 1 : 2)) void
 template <class DT, bool UNROLL = false, bool ACTOR = false>
 __global__ __launch_bounds__(RR_LANES, 2) void rr_rand_kernel(const RRDims Dk, const RRTables Tk, const RRIO io_kernarg, const int num_envs, const int n_frames) {
   constexpr int NBS = 2, NVS = 2, NCS = 1;
-  constexpr bool PROF = false, DBG = false, NEWTON = false, PAIR = false, DYN = false, RAND = true, EVAL = false, POSE = false, REFOBS = false, PTERM = false, BODY = false;
+  constexpr bool PROF = false, DBG = false, NEWTON = false, PAIR = false, DYN = false, RAND = true, EVAL = false, POSE = false, REFOBS = false, PTERM = false, BODY = false, RESTART = false;
   constexpr int MRES = 1;      // resident inverse-factor entries (Wave::MAT_RES): the column side (229-237 registers; both sides reach the cap of 256 here)
   constexpr bool ROOTSLOT = rr_root_slot<DT>::value;
 #include "rr_step_body.inc"
@@ -2849,7 +2863,7 @@ __global__ __launch_bounds__(RR_LANES, 2) void rr_rand_kernel(const RRDims Dk, c
 template <class DT, bool DYN = false>
 __global__ __launch_bounds__(RR_LANES, 2) void rr_eval_kernel(const RRDims Dk, const RRTables Tk, const RRIO io_kernarg, const int num_envs, const int n_frames) {
   constexpr int NBS = 2, NVS = 2, NCS = 1;
-  constexpr bool PROF = false, DBG = false, NEWTON = false, PAIR = false, RAND = false, UNROLL = true, ACTOR = true, EVAL = true, POSE = false, REFOBS = false, PTERM = false, BODY = false;
+  constexpr bool PROF = false, DBG = false, NEWTON = false, PAIR = false, RAND = false, UNROLL = true, ACTOR = true, EVAL = true, POSE = false, REFOBS = false, PTERM = false, BODY = false, RESTART = false;
   constexpr int MRES = 1;      // resident inverse-factor entries (Wave::MAT_RES): the column side (229-237 registers; both sides reach the cap of 256 here)
   constexpr bool ROOTSLOT = rr_root_slot<DT>::value;
 #include "rr_step_body.inc"
@@ -2861,7 +2875,7 @@ __global__ __launch_bounds__(RR_LANES, 2) void rr_eval_kernel(const RRDims Dk, c
 template <class DT, bool UNROLL = false, bool ACTOR = false>
 __global__ __launch_bounds__(RR_LANES, 2) void rr_pose_kernel(const RRDims Dk, const RRTables Tk, const RRIO io_kernarg, const int num_envs, const int n_frames) {
   constexpr int NBS = 2, NVS = 2, NCS = 1;
-  constexpr bool PROF = false, DBG = false, NEWTON = false, PAIR = false, DYN = false, RAND = false, EVAL = false, POSE = true, REFOBS = false, PTERM = false, BODY = false;
+  constexpr bool PROF = false, DBG = false, NEWTON = false, PAIR = false, DYN = false, RAND = false, EVAL = false, POSE = true, REFOBS = false, PTERM = false, BODY = false, RESTART = false;
   constexpr int MRES = 1;      // resident inverse-factor entries (Wave::MAT_RES): the column side (229-237 registers; both sides reach the cap of 256 here)
   constexpr bool ROOTSLOT = rr_root_slot<DT>::value;
 #include "rr_step_body.inc"
@@ -2873,7 +2887,7 @@ __global__ __launch_bounds__(RR_LANES, 2) void rr_pose_kernel(const RRDims Dk, c
 template <class DT, bool UNROLL = false, bool ACTOR = false>
 __global__ __launch_bounds__(RR_LANES, 2) void rr_refobs_kernel(const RRDims Dk, const RRTables Tk, const RRIO io_kernarg, const int num_envs, const int n_frames) {
   constexpr int NBS = 2, NVS = 2, NCS = 1;
-  constexpr bool PROF = false, DBG = false, NEWTON = false, PAIR = false, DYN = false, RAND = false, EVAL = false, POSE = true, REFOBS = true, PTERM = false, BODY = false;
+  constexpr bool PROF = false, DBG = false, NEWTON = false, PAIR = false, DYN = false, RAND = false, EVAL = false, POSE = true, REFOBS = true, PTERM = false, BODY = false, RESTART = false;
   constexpr int MRES = 1;      // resident inverse-factor entries (Wave::MAT_RES): the column side, as in rr_pose_kernel
   constexpr bool ROOTSLOT = rr_root_slot<DT>::value;
 #include "rr_step_body.inc"
@@ -2886,7 +2900,7 @@ __global__ __launch_bounds__(RR_LANES, 2) void rr_refobs_kernel(const RRDims Dk,
 template <class DT, bool UNROLL = false, bool ACTOR = false>
 __global__ __launch_bounds__(RR_LANES, 2) void rr_poseterm_kernel(const RRDims Dk, const RRTables Tk, const RRIO io_kernarg, const int num_envs, const int n_frames) {
   constexpr int NBS = 2, NVS = 2, NCS = 1;
-  constexpr bool PROF = false, DBG = false, NEWTON = false, PAIR = false, DYN = false, RAND = false, EVAL = false, POSE = true, REFOBS = true, PTERM = true, BODY = false;
+  constexpr bool PROF = false, DBG = false, NEWTON = false, PAIR = false, DYN = false, RAND = false, EVAL = false, POSE = true, REFOBS = true, PTERM = true, BODY = false, RESTART = false;
   constexpr int MRES = 1;      // resident inverse-factor entries (Wave::MAT_RES): the column side, as in rr_pose_kernel
   constexpr bool ROOTSLOT = rr_root_slot<DT>::value;
 #include "rr_step_body.inc"
@@ -2900,7 +2914,21 @@ __global__ __launch_bounds__(RR_LANES, 2) void rr_poseterm_kernel(const RRDims D
 template <class DT, bool UNROLL = false, bool ACTOR = false>
 __global__ __launch_bounds__(RR_LANES, 2) void rr_body_kernel(const RRDims Dk, const RRTables Tk, const RRIO io_kernarg, const int num_envs, const int n_frames) {
   constexpr int NBS = 2, NVS = 2, NCS = 1;
-  constexpr bool PROF = false, DBG = false, NEWTON = false, PAIR = false, DYN = false, RAND = false, EVAL = false, POSE = true, REFOBS = true, PTERM = true, BODY = true;
+  constexpr bool PROF = false, DBG = false, NEWTON = false, PAIR = false, DYN = false, RAND = false, EVAL = false, POSE = true, REFOBS = true, PTERM = true, BODY = true, RESTART = false;
+  constexpr int MRES = 1;      // resident inverse-factor entries (Wave::MAT_RES): the column side, as in rr_pose_kernel
+  constexpr bool ROOTSLOT = rr_root_slot<DT>::value;
+#include "rr_step_body.inc"
+}
+// Clip restarts (rr_batch_set_clip_restarts): the multi-step body-tracking instances with the AutoReset restore drawn from a bank of start
+// states, the restored frame and the clip-end truncation (RRIO, CLIP RESTARTS), served to the multi-step launches of a batch that carries
+// the block.  An entry of its own for the reason the others are: every `if (RESTART)` in the body folds away in their instances.  POSE,
+// REFOBS, PTERM and BODY are on -- a superset instance: ref_frames = 0 is that code with zero blocks, no termination block is +inf
+// thresholds and a null pose_fail, no body block a null track_bodies.  Multi-step forms only (a single step has no restore in the
+// kernel): without and with the actor, which reads RR_ACTOR_JM_REFOBS entries per lane whatever the frame count.
+template <class DT, bool ACTOR = false>
+__global__ __launch_bounds__(RR_LANES, 2) void rr_restart_kernel(const RRDims Dk, const RRTables Tk, const RRIO io_kernarg, const int num_envs, const int n_frames) {
+  constexpr int NBS = 2, NVS = 2, NCS = 1;
+  constexpr bool PROF = false, DBG = false, NEWTON = false, UNROLL = true, PAIR = false, DYN = false, RAND = false, EVAL = false, POSE = true, REFOBS = true, PTERM = true, BODY = true, RESTART = true;
   constexpr int MRES = 1;      // resident inverse-factor entries (Wave::MAT_RES): the column side, as in rr_pose_kernel
   constexpr bool ROOTSLOT = rr_root_slot<DT>::value;
 #include "rr_step_body.inc"
@@ -2912,7 +2940,7 @@ template <class DT>
 __global__ __launch_bounds__(RR_LANES, 2) void rr_matlds_kernel(const RRDims Dk, const RRTables Tk, const RRIO io_kernarg, const int num_envs, const int n_frames) {
   constexpr int NBS = 2, NVS = 2, NCS = 1, MRES = 0;
   constexpr bool ROOTSLOT = rr_root_slot<DT>::value;
-  constexpr bool PROF = false, DBG = false, NEWTON = false, UNROLL = false, ACTOR = false, PAIR = false, DYN = false, RAND = false, EVAL = false, POSE = false, REFOBS = false, PTERM = false, BODY = false;
+  constexpr bool PROF = false, DBG = false, NEWTON = false, UNROLL = false, ACTOR = false, PAIR = false, DYN = false, RAND = false, EVAL = false, POSE = false, REFOBS = false, PTERM = false, BODY = false, RESTART = false;
 #include "rr_step_body.inc"
 }
 // The production single-step instance with the tree phases on the plain lane <-> body map b = lane + 64 s (Wave::ROOT off), whatever
@@ -2922,6 +2950,6 @@ template <class DT>
 __global__ __launch_bounds__(RR_LANES, 2) void rr_twoslot_kernel(const RRDims Dk, const RRTables Tk, const RRIO io_kernarg, const int num_envs, const int n_frames) {
   constexpr int NBS = 2, NVS = 2, NCS = 1, MRES = 2;
   constexpr bool ROOTSLOT = false;
-  constexpr bool PROF = false, DBG = false, NEWTON = false, UNROLL = false, ACTOR = false, PAIR = false, DYN = false, RAND = false, EVAL = false, POSE = false, REFOBS = false, PTERM = false, BODY = false;
+  constexpr bool PROF = false, DBG = false, NEWTON = false, UNROLL = false, ACTOR = false, PAIR = false, DYN = false, RAND = false, EVAL = false, POSE = false, REFOBS = false, PTERM = false, BODY = false, RESTART = false;
 #include "rr_step_body.inc"
 }

@@ -1,6 +1,6 @@
 // rr_step_body.inc -- the body of the step kernel, included by each of its __global__ entries in rr_kernel.h (rr_step_kernel,
-// rr_rand_kernel, rr_eval_kernel, rr_pose_kernel, rr_refobs_kernel, rr_poseterm_kernel, rr_body_kernel, rr_matlds_kernel, rr_twoslot_kernel).  In scope where it is included: the kernel's five arguments (Dk, Tk, io_kernarg, num_envs, n_frames) and the
-// compile-time switches NBS, NVS, NCS, PROF, DBG, DT, NEWTON, UNROLL, ACTOR, PAIR, DYN, RAND, EVAL, POSE, REFOBS, PTERM, BODY, MRES, ROOTSLOT.
+// rr_rand_kernel, rr_eval_kernel, rr_pose_kernel, rr_refobs_kernel, rr_poseterm_kernel, rr_body_kernel, rr_restart_kernel, rr_matlds_kernel, rr_twoslot_kernel).  In scope where it is included: the kernel's five arguments (Dk, Tk, io_kernarg, num_envs, n_frames) and the
+// compile-time switches NBS, NVS, NCS, PROF, DBG, DT, NEWTON, UNROLL, ACTOR, PAIR, DYN, RAND, EVAL, POSE, REFOBS, PTERM, BODY, RESTART, MRES, ROOTSLOT.
 // Why text and not a function: see the note above rr_step_kernel.
   static_assert(!PAIR || (!PROF && !DBG && !NEWTON && !UNROLL && !ACTOR), "PAIR: production physics instance only");
   static_assert(!DYN || (!PROF && !DBG && !NEWTON && !PAIR), "DYN: production instances only (single-step, multi-step, multi-step with the actor)");
@@ -9,6 +9,7 @@
   static_assert(!REFOBS || POSE, "REFOBS: a form of the pose instances (the blocks are rows of track_pose)");
   static_assert(!PTERM || REFOBS, "PTERM: a form of the reference-observation instances (ref_frames 0: no blocks)");
   static_assert(!BODY || PTERM, "BODY: a form of the pose-termination instances (+inf thresholds and a null pose_fail: no termination)");
+  static_assert(!RESTART || (BODY && UNROLL), "RESTART: a form of the multi-step body-tracking instances (a null track_bodies: no body terms)");
   static_assert(!EVAL || (ACTOR && !RAND && !PROF && !DBG && !NEWTON && !PAIR), "EVAL: a form of the production multi-step instance with the actor");
   extern __shared__ __attribute__((aligned(16))) float lds[];
   int env = blockIdx.x;
@@ -41,6 +42,7 @@
   const int nsteps = UNROLL ? io.unroll_T : 1;
   float u_steps = 0.0f, u_prev_done = 0.0f;
   int u_frame = 0;
+  int u_slot = 0;                // RESTART: the bank entry the env's next restore follows (RRIO, CLIP RESTARTS)
   unsigned u_work = 0;
   int u_overflow = 0;            // DYN: some step of this launch dropped pairs (RRIO::cost bit 31 of a multi-step launch)
   if (UNROLL) {
@@ -49,6 +51,11 @@
     u_prev_done = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(io.prev_done[env])));
     }
     u_frame = __builtin_amdgcn_readfirstlane(io.cur_frame_in[env]);
+    if (RESTART) {      // clamped into the bank, so no slot addresses outside it
+      const int rk = load_io_member<int>(offsetof(RRIO, restart_K));
+      u_slot = __builtin_amdgcn_readfirstlane(load_io_member<const int*>(offsetof(RRIO, restart_slot_in))[env]);
+      u_slot = u_slot < 0 ? 0 : (u_slot > rk - 1 ? rk - 1 : u_slot);
+    }
   }
   int niter = 0;
   float xq1[4] = {1, 0, 0, 0};   // xquat of body 1 at the last forward pass (obs: xmat[1])
@@ -580,13 +587,17 @@
       // EpisodeWrapper + AutoResetWrapper on the step just made (action_repeat 1), as rr_wrap_kernel applies them:
       // steps' = (prev_done ? 0 : steps) + 1; over = steps' >= episode_length; done <- over ? 1 : done; truncation = over ? 1 - done_env : 0;
       // where done, the stored first state and first observation come back (info -- cur_frame, steps -- is not restored)
+      // RESTART: the clip's end joins `over`, and the state, the observation AND the frame come back from the next entry of the bank
       const float z = w.s_qpos[2];
       const float healthy = (z < io.z_min || z > io.z_max) ? 0.0f : 1.0f;
       const float done_own = (mode & 4) ? 1.0f : (io.terminate_when_unhealthy ? 1.0f - healthy : 0.0f);
       const float done_env = (PTERM && pterm_code != 0) ? 1.0f : done_own;      // PTERM: a pose failure is a termination (trunc 0, discount 0, restore)
       const bool wrapped = !EVAL || !(io.a_pad & RR_EVAL_RAW);      // EVAL without the wrappers: the env's own done, no step count, no restore
       if (wrapped) u_steps = (u_prev_done != 0.0f ? 0.0f : u_steps) + 1.0f;
-      const bool over = wrapped && u_steps >= io.episode_length;
+      bool over = wrapped && u_steps >= io.episode_length;
+      if (RESTART) {      // new_frame >= T - 1: the new state's observation has no next frame left to read without clamping
+        if (load_io_member<int>(offsetof(RRIO, restart_end)) != 0 && new_frame >= io.track_len - 1) over = true;
+      }
       const float done2 = over ? 1.0f : done_env, trunc = over ? 1.0f - done_env : 0.0f;
       u_prev_done = done2;
       u_frame = new_frame;
@@ -607,7 +618,20 @@
         }
         if (io.e_qpos_out) for (int i = lane; i < D.nq; i += RR_LANES) io.e_qpos_out[((size_t)(ut + 1) * num_envs + env) * D.nq + i] = w.s_qpos[i];
       }
-      if (wrapped && __builtin_amdgcn_readfirstlane(__float_as_int(done2)) != 0) {
+      if (RESTART) {
+        if (__builtin_amdgcn_readfirstlane(__float_as_int(done2)) != 0) {
+          u_slot = u_slot + 1;
+          if (u_slot >= load_io_member<int>(offsetof(RRIO, restart_K))) u_slot = 0;
+          const size_t re = (size_t)u_slot * (size_t)num_envs + (size_t)env;      // row of the bank entry in every [K][N][width] array
+          u_frame = __builtin_amdgcn_readfirstlane(load_io_member<const int*>(offsetof(RRIO, restart_frames))[re]);
+          w.sync();
+          for (int i = lane; i < D.nq; i += RR_LANES) w.s_qpos[i] = io.first_qpos[re * D.nq + i];
+          for (int i = lane; i < D.nv; i += RR_LANES) { w.s_qvel[i] = io.first_qvel[re * D.nv + i]; w.s_warm[i] = io.first_warm[re * D.nv + i]; }
+          for (int i = lane; i < D.nu; i += RR_LANES) w.s_act[i] = io.first_act[re * D.nu + i];
+          for (int i = lane; i < ow; i += RR_LANES) ob[i] = io.first_obs[re * ow + i];
+          w.sync();
+        }
+      } else if (wrapped && __builtin_amdgcn_readfirstlane(__float_as_int(done2)) != 0) {
         w.sync();
         for (int i = lane; i < D.nq; i += RR_LANES) w.s_qpos[i] = io.first_qpos[(size_t)env * D.nq + i];
         for (int i = lane; i < D.nv; i += RR_LANES) { w.s_qvel[i] = io.first_qvel[(size_t)env * D.nv + i]; w.s_warm[i] = io.first_warm[(size_t)env * D.nv + i]; }
@@ -633,6 +657,9 @@
       }
       if (ut == nsteps - 1) {
         if (lane == 0) { io.done[env] = done2; if (wrapped) { io.steps_out[env] = u_steps; io.trunc_out[env] = trunc; } }
+        if (RESTART) {      // the frame and the slot the next launch goes on from (lane 0 stored new_frame above: program order)
+          if (lane == 0) { io.cur_frame[env] = u_frame; load_io_member<int*>(offsetof(RRIO, restart_slot_out))[env] = u_slot; }
+        }
         for (int i = lane; i < D.nq; i += RR_LANES) io.qpos[(size_t)env * D.nq + i] = w.s_qpos[i];
         for (int i = lane; i < D.nv; i += RR_LANES) { io.qvel[(size_t)env * D.nv + i] = w.s_qvel[i]; io.warm[(size_t)env * D.nv + i] = w.s_warm[i]; }
         for (int i = lane; i < D.nu; i += RR_LANES) io.act[(size_t)env * D.nu + i] = w.s_act[i];

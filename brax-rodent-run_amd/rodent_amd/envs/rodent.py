@@ -46,6 +46,53 @@ def reset_draws(keys, nq: int, nv: int, reset_noise_scale: float, num_clips: Opt
     return start_frame, qpos_noise, qvel, clip
 
 
+def restart_bank_draws(keys, num_entries: int, nq: int, nv: int, reset_noise_scale: float, frame_range=(0, 100), num_clips: Optional[int] = None):
+    """The host draws of the start bank of `Rodent(clip_restarts=K)`, without a device: `keys` uint32 [N, 2] -> (start_frame int32
+    [K, N], qpos noise float32 [K, N, nq], qvel float32 [K, N, nv], clip int32 [N] or None).  Entry 0 is `reset_draws(keys)` itself,
+    whatever K is.  Entry k = 1 .. K - 1 is `reset_draws(fold_in(keys, k))` -- qpos noise and qvel -- except its start frame, which is
+    `randint(lo, hi)` of that key's first subkey, `frame_range` = (lo, hi).  The clip is the one of `keys`: every entry follows it."""
+    keys = np.asarray(keys, dtype=np.uint32).reshape(-1, 2)
+    lo, hi = frame_range
+    frames, noises, qvels = [], [], []
+    clip = None
+    for k in range(int(num_entries)):
+        kk = keys if k == 0 else jax_random.fold_in(keys, k)
+        f, noise, qvel, drawn = reset_draws(kk, nq, nv, reset_noise_scale, num_clips)
+        if k == 0:
+            clip = drawn
+        else:
+            f = jax_random.randint(jax_random.split(kk, 4)[:, 0], int(lo), int(hi))
+        frames.append(np.asarray(f, dtype=np.int32)); noises.append(noise); qvels.append(qvel)
+    return np.stack(frames), np.stack(noises), np.stack(qvels), clip
+
+
+def _check_clip_restarts(clip_restarts, restart_frame_range, end_at_clip_end, have_pose: bool, track_len: int):
+    """`clip_restarts`, `restart_frame_range` and `end_at_clip_end` of `Rodent` as (K, (lo, hi), flag); ValueError for K outside 0 .. 64,
+    any of the three without the pose arguments, `end_at_clip_end` with K = 0, lo < 0 or hi <= lo, and -- with `end_at_clip_end` -- a
+    clip so short that some entry can start at its end (T - 1 <= the largest frame an entry can draw; 99 for entry 0): such an env would
+    truncate on every step."""
+    if isinstance(clip_restarts, (bool, np.bool_)) or not isinstance(clip_restarts, (int, np.integer)) or not 0 <= int(clip_restarts) <= 64:
+        raise ValueError(f"clip_restarts must be an int in 0 .. 64 (0: the first state comes back, the frame does not), got {clip_restarts!r}")
+    K, end = int(clip_restarts), bool(end_at_clip_end)
+    if (K > 0 or restart_frame_range is not None or end) and not have_pose:
+        raise ValueError("clip_restarts / restart_frame_range / end_at_clip_end need the reference pose: pass track_quat and track_joints")
+    if end and K == 0:
+        raise ValueError("end_at_clip_end=True needs clip_restarts >= 1: without the bank the restored state does not rejoin the clip")
+    lo, hi = (0, 100) if restart_frame_range is None else restart_frame_range
+    for x in (lo, hi):
+        if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, np.integer)):
+            raise ValueError(f"restart_frame_range must be two ints (lo, hi), got {restart_frame_range!r}")
+    lo, hi = int(lo), int(hi)
+    if lo < 0 or hi <= lo:
+        raise ValueError(f"restart_frame_range = (lo, hi) needs 0 <= lo < hi (frames are drawn in [lo, hi)), got {(lo, hi)!r}")
+    if end:
+        largest = max(99, hi - 1) if K > 1 else 99
+        if track_len - 1 <= largest:
+            raise ValueError(f"end_at_clip_end=True: the clip has {track_len} frames, but an entry of the start bank can start at frame {largest}; "
+                             f"with T - 1 <= {largest} such an env would truncate on every step (use a longer clip or a smaller restart_frame_range)")
+    return K, (lo, hi), end
+
+
 def reset_qpos(qpos0, track: np.ndarray, start_frame, qpos_noise, clip=None, pose: Optional[np.ndarray] = None) -> np.ndarray:
     """The qpos `Rodent.reset` starts from, float32 [N, nq], out of the draws of `reset_draws`: qpos0 with the root position replaced by
     track[(clip,) start_frame] (the frame clamped within the clip), plus the noise.  `pose` (the env's [(C,) T, nq - 3] rows, given with
@@ -344,6 +391,9 @@ class Rodent(PipelineEnv):
         body_reward_scale: float = 8.0,
         endeff_reward_weight: float = 1.0,
         endeff_reward_scale: float = 100.0,
+        clip_restarts: int = 0,
+        restart_frame_range=None,
+        end_at_clip_end: bool = False,
         **kwargs,
     ):
         """`track_pos`: the reference positions to track, float [T, 3] -- one clip, followed by every env -- or [C, T, 3], C >= 1 clips of
@@ -411,7 +461,23 @@ class Rodent(PipelineEnv):
         `body_reward` and `endeff_reward` (zeros at reset and after a bad step); everything else of the step is what it is without the
         terms.  An empty set gives its term weight 0.  The four defaults (1, 8, 1, 100) are UNTUNED choices, not values from a reference.
         Served where pose tracking is, in `step`, `unroll_wrapped` and `unroll_policy_wrapped`, with or without reference frames and
-        pose termination."""
+        pose termination.
+
+        Clip restarts: `clip_restarts` = K (pose envs only, an int in 0 .. 64; 0, the default, is today's behaviour in every bit).  Upstream's
+        AutoReset brings back the first state and leaves `cur_frame` alone, so a restarted tracking env is compared with frames it never
+        started at.  With K >= 1 `reset` builds a bank of K start states per env -- entry 0 the reset state itself, entry k = 1 .. K - 1
+        what `reset_draws` gives for `fold_in(key, k)` with its start frame drawn in `restart_frame_range` = (lo, hi) (None: (0, 100), the
+        reference's range); all on the env's one clip (`restart_bank_draws`) -- and keeps it in `info['restart_bank']` (dict:
+        `pipeline_state` [K, N, ...], `obs` [K, N, observation_size], `frame` int32 [K, N]) next to `info['restart_slot']` (int32 [N],
+        zeros at reset).  Bank and slot are info: never re-drawn, never restored.  Per wrapped env step (`wrappers.wrap`,
+        `unroll_wrapped`, `unroll_policy_wrapped`), with new_frame = old_frame + 1 and T the clip length:
+
+            over = steps' >= episode_length  or  (end_at_clip_end and new_frame >= T - 1);   done, truncation as ever
+            done:  slot' = (slot + 1) mod K;  state, obs <- bank[slot'];  cur_frame <- bank frame[slot'];    else slot, new_frame
+
+        The clip's end (`end_at_clip_end=True`, needs K >= 1) is a truncation like `episode_length`, so the value bootstraps; the step
+        that ends the episode is untouched.  K = 1 restores the frame with the state.  The bare `step` and the raw evaluation rollout have
+        no wrappers and do not change."""
         if bad_state_max is not None:
             with np.errstate(over="ignore", under="ignore"):
                 thr32 = np.float32(bad_state_max)        # what the kernel gets: 1e-50 would arrive as 0 (= off), 1e39 as inf
@@ -434,6 +500,7 @@ class Rodent(PipelineEnv):
         pose_term = _check_pose_termination(max_pos_error, max_quat_error, max_joint_error, pose_np is not None)
         body_np = _check_body_tracking(track_np, track_bodies, body_ids, end_effector_ids, sys.nbody,
                                        (body_reward_weight, body_reward_scale, endeff_reward_weight, endeff_reward_scale), pose_np is not None)
+        restarts = _check_clip_restarts(clip_restarts, restart_frame_range, end_at_clip_end, pose_np is not None, track_np.shape[-2])
         if reset_to_reference and pose_np is None:
             raise ValueError("reset_to_reference=True needs the reference pose: pass track_quat and track_joints")
         physics_steps_per_control_step = 10   # [REF Rodent_Env_Brax.py:53-57]
@@ -477,6 +544,11 @@ class Rodent(PipelineEnv):
             self._body = dict(track_bodies=torch.from_numpy(rows).to(self.device).contiguous(), body_weights=torch.from_numpy(masks).to(self.device).contiguous(),
                               body_reward=(float(body_reward_weight) if B else 0.0, float(body_reward_scale)),
                               endeff_reward=(float(endeff_reward_weight) if E else 0.0, float(endeff_reward_scale)), body_ids=B, end_effector_ids=E)
+        self._clip_restarts, self._restart_frame_range, self._end_at_clip_end = restarts
+        if self._clip_restarts:
+            why = self._batch.clip_restarts_supported()
+            if why is not None:
+                raise RuntimeError(f"Rodent(clip_restarts={self._clip_restarts}): {why}")
         self._forward_reward_weight = forward_reward_weight
         self._ctrl_cost_weight = ctrl_cost_weight
         self._healthy_reward = healthy_reward
@@ -498,7 +570,8 @@ class Rodent(PipelineEnv):
                           reference_obs_frames=reference_obs_frames, max_pos_error=max_pos_error, max_quat_error=max_quat_error,
                           max_joint_error=max_joint_error, track_bodies=track_bodies, body_ids=body_ids, end_effector_ids=end_effector_ids,
                           body_reward_weight=body_reward_weight, body_reward_scale=body_reward_scale,
-                          endeff_reward_weight=endeff_reward_weight, endeff_reward_scale=endeff_reward_scale)
+                          endeff_reward_weight=endeff_reward_weight, endeff_reward_scale=endeff_reward_scale,
+                          clip_restarts=clip_restarts, restart_frame_range=restart_frame_range, end_at_clip_end=end_at_clip_end)
 
     def with_num_envs(self, num_envs: int, device=None):
         """A sibling env with another batch size (ppo.train builds its per-rank and eval envs this way)."""
@@ -544,6 +617,26 @@ class Rodent(PipelineEnv):
         return {k: self._body[k] for k in ("body_ids", "end_effector_ids", "body_reward", "endeff_reward")}
 
     @property
+    def clip_restarts(self) -> int:
+        """Entries K of the start bank a restarted episode draws from (0: no bank, the first state comes back and the frame does not)."""
+        return self._clip_restarts
+
+    @property
+    def end_at_clip_end(self) -> bool:
+        """Whether the wrapped env truncates an episode whose next observation would read past the clip's last frame."""
+        return self._end_at_clip_end
+
+    @property
+    def restart_frame_range(self) -> tuple:
+        """(lo, hi): bank entries 1 .. K - 1 start at frames drawn in [lo, hi)."""
+        return self._restart_frame_range
+
+    @property
+    def track_len(self) -> int:
+        """Frames T of a clip."""
+        return int(self._track_host.shape[-2])
+
+    @property
     def reference_obs_frames(self) -> int:
         """Reference frames H behind every observation row (0: none)."""
         return self._ref_frames
@@ -563,7 +656,7 @@ class Rodent(PipelineEnv):
             raise RuntimeError("pose tracking: no pose instance reads per-env parameters (randomize / set_env_params on a pose env)")
         return super().randomize(randomization_fn)
 
-    def _env_io(self, cur_frame, obs, reward=None, done=None, metrics=None, clip=None, pose_metrics=None, pose_fail=None, body_metrics=None):
+    def _env_io(self, cur_frame, obs, reward=None, done=None, metrics=None, clip=None, pose_metrics=None, pose_fail=None, body_metrics=None, restart=None):
         io = dict(track_pos=self._track_pos, cur_frame=cur_frame, obs=obs, reward=reward, done=done, metrics=metrics, clip=clip,
                   healthy_reward=self._healthy_reward, ctrl_cost_weight=self._ctrl_cost_weight,
                   healthy_z_range=self._healthy_z_range, terminate_when_unhealthy=self._terminate_when_unhealthy,
@@ -577,6 +670,8 @@ class Rodent(PipelineEnv):
         if body_metrics is not None:         # a step of an env with body tracking (a reset passes none: it has no reward)
             io.update(track_bodies=self._body["track_bodies"], body_weights=self._body["body_weights"], body_metrics=body_metrics,
                       body_reward=self._body["body_reward"], endeff_reward=self._body["endeff_reward"])
+        if restart is not None:              # a multi-step launch of an env with clip restarts (single steps and resets pass none)
+            io["restart"] = restart
         return io
 
     def reset(self, rng, clip=None) -> State:
@@ -593,21 +688,32 @@ class Rodent(PipelineEnv):
         if isinstance(rng, (int, np.integer)):
             rng = jax_random.split(jax_random.PRNGKey(int(rng)), N)
         keys = np.asarray(rng, dtype=np.uint32).reshape(N, 2)
-        start_frame, qpos_noise, qvel, drawn = reset_draws(keys, s.nq, s.nv, self._reset_noise_scale, self._num_clips)
+        K = max(self._clip_restarts, 1)      # entry 0 of the bank is the reset state itself: the same draws, whatever K is
+        frames, noises, qvels, drawn = restart_bank_draws(keys, K, s.nq, s.nv, self._reset_noise_scale, self._restart_frame_range, self._num_clips)
         if clip is None:
             clip = drawn
-        # float32 [T, 3] or [C, T, 3] (and the pose rows), what the device holds
-        qpos = reset_qpos(s.qpos0, self._track_host, start_frame, qpos_noise, clip, self._pose_host if self._reset_to_reference else None)
-
-        st = dict(qpos=torch.from_numpy(qpos).to(dev), qvel=torch.from_numpy(qvel).to(dev),
-                  act=torch.zeros(N, s.na, device=dev), qacc_warmstart=torch.zeros(N, s.nv, device=dev))
-        out = self._alloc_outputs(full=False)
-        cur_frame = torch.from_numpy(start_frame.astype(np.int32)).to(dev)
+        clip_dev = None if clip is None else torch.from_numpy(np.ascontiguousarray(clip, dtype=np.int32)).to(dev)
+        entries = []
+        for k in range(K):
+            # float32 [T, 3] or [C, T, 3] (and the pose rows), what the device holds
+            qpos = reset_qpos(s.qpos0, self._track_host, frames[k], noises[k], clip, self._pose_host if self._reset_to_reference else None)
+            st = dict(qpos=torch.from_numpy(qpos).to(dev), qvel=torch.from_numpy(qvels[k]).to(dev),
+                      act=torch.zeros(N, s.na, device=dev), qacc_warmstart=torch.zeros(N, s.nv, device=dev))
+            out = self._alloc_outputs(full=False)
+            cur_frame = torch.from_numpy(frames[k].astype(np.int32)).to(dev)
+            obs = torch.empty(N, self.observation_size, device=dev)
+            self._batch.env_reset(st, self._env_io(cur_frame, obs, clip=clip_dev), out)
+            entries.append((st, out, cur_frame, obs))
+        st, out, cur_frame, obs = entries[0]
         info = {"cur_frame": cur_frame}
         if clip is not None:
-            info["clip"] = torch.from_numpy(np.ascontiguousarray(clip, dtype=np.int32)).to(dev)
-        obs = torch.empty(N, self.observation_size, device=dev)
-        self._batch.env_reset(st, self._env_io(cur_frame, obs, clip=info.get("clip")), out)
+            info["clip"] = clip_dev
+        if self._clip_restarts:
+            stack = lambda name, src: torch.stack([e[src][name] for e in entries]).contiguous()
+            bank_ps = PipelineState(**{n: stack(n, 0) for n in st}, **{n: (stack(n, 1) if out[n] is not None else None) for n in out})
+            info["restart_bank"] = dict(pipeline_state=bank_ps, obs=torch.stack([e[3] for e in entries]).contiguous(),
+                                        frame=torch.stack([e[2] for e in entries]).contiguous())
+            info["restart_slot"] = torch.zeros(N, dtype=torch.int32, device=dev)
         zero = torch.zeros(N, device=dev)
         metrics = {"pos_reward": zero, "reward_quadctrl": zero.clone(), "reward_alive": zero.clone()}
         if self.pose_tracking:
@@ -636,7 +742,14 @@ class Rodent(PipelineEnv):
         if self._body is not None:
             io["body_metrics"] = torch.empty(N, 2, device=dev)
         wrap = None
-        if episode_length is not None:
+        if episode_length is not None and self._clip_restarts:      # the restores draw from the bank, and frame and slot travel with the state
+            bank = info["restart_bank"]
+            wrap = dict(first=fields(bank["pipeline_state"]), first_obs=bank["obs"], prev_done=state.done, steps_in=info["steps"],
+                        steps_out=torch.empty(N, device=dev), truncation_out=torch.empty(N, device=dev), episode_length=episode_length,
+                        slots=self._clip_restarts)
+            io["restart"] = dict(frames=bank["frame"], slot_in=info["restart_slot"], slot_out=torch.empty_like(info["restart_slot"]),
+                                 end_at_clip_end=self._end_at_clip_end)
+        elif episode_length is not None:
             wrap = dict(first=fields(info["first_pipeline_state"]), first_obs=info["first_obs"], prev_done=state.done, steps_in=info["steps"],
                         steps_out=torch.empty(N, device=dev), truncation_out=torch.empty(N, device=dev), episode_length=episode_length)
         return st_in, st, io, wrap
@@ -647,6 +760,8 @@ class Rodent(PipelineEnv):
         info["cur_frame"] = io["cur_frame"]
         if wrap is not None:
             info.update(steps=wrap["steps_out"], truncation=wrap["truncation_out"])
+            if "restart" in io:
+                info["restart_slot"] = io["restart"]["slot_out"]
         m = dict(state.metrics)
         m.update(pos_reward=io["metrics"][:, 0], reward_quadctrl=io["metrics"][:, 1], reward_alive=io["metrics"][:, 2])
         if self.pose_tracking:
@@ -662,8 +777,8 @@ class Rodent(PipelineEnv):
     def unroll_wrapped(self, state: State, actions: torch.Tensor, episode_length: float) -> State:
         """`actions.shape[0]` steps with `EpisodeWrapper(episode_length)` + `AutoResetWrapper` (action_repeat 1) in ONE launch
         (`rr_env_unroll`): what `lax.scan` over the wrapped `step` is to the reference.  `state` is a state of the wrapped env
-        (info carries steps, truncation, first_pipeline_state, first_obs); returns the state after the last step, bit for bit what
-        the per-step calls give.  Intermediate observations / rewards are not returned (a random-action rollout needs none)."""
+        (info carries steps, truncation, first_pipeline_state, first_obs -- with `clip_restarts >= 1` restart_bank and restart_slot instead,
+        and the launch applies the clip-restart rule); returns the state after the last step, bit for bit what the per-step calls give.  Intermediate observations / rewards are not returned (a random-action rollout needs none)."""
         if self._pipeline_outputs or self._contact_outputs:
             raise ValueError("a multi-step rollout returns no pipeline / contact outputs: build the env without them")
         st_in, st, io, wrap = self._launch_buffers(state, episode_length)

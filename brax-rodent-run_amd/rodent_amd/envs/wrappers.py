@@ -5,6 +5,9 @@ maintains `info['steps']` / `info['truncation']`; `AutoResetWrapper` selects the
 state back on `done` -- no re-randomisation and `info` (hence `cur_frame`) is NOT restored, exactly
 as upstream.  The same holds for `info['clip']` of a multi-clip env: an env keeps
 its clip across restores.  `reset(rng, **kw)` hands keyword arguments (`clip=`) down to the env.
+
+An env with clip restarts (`Rodent(clip_restarts=K)`, K >= 1) is wrapped by `ClipEpisodeWrapper` and `ClipAutoResetWrapper` instead: the
+clip's end may truncate the episode, and a restore takes the next entry of the env's start bank -- state, observation AND frame.
 """
 from __future__ import annotations
 
@@ -114,6 +117,64 @@ class AutoResetWrapper(Wrapper):
         return state.replace(pipeline_state=new_ps, obs=obs)
 
 
+def _base(env):
+    return env.unwrapped if hasattr(env, "unwrapped") else env
+
+
+class ClipEpisodeWrapper(EpisodeWrapper):
+    """`EpisodeWrapper` of an env with clip restarts: with `end_at_clip_end` the episode also ends -- a truncation, like
+    `episode_length` -- when the stepped frame reaches the clip's last one, new_frame >= T - 1: the new state's observation has no next
+    frame left to read without clamping."""
+
+    def step(self, state, action):
+        total = None
+        nstate = state
+        for _ in range(self.action_repeat):
+            nstate = self.env.step(nstate, action)
+            total = nstate.reward if total is None else total + nstate.reward
+        state = nstate.replace(reward=total)
+        steps = state.info["steps"] + self.action_repeat
+        one, zero = torch.ones_like(state.done), torch.zeros_like(state.done)
+        over = steps >= self.episode_length
+        base = _base(self.env)
+        if base.end_at_clip_end:
+            over = over | (state.info["cur_frame"] >= base.track_len - 1)
+        done = torch.where(over, one, state.done)
+        state.info["truncation"] = torch.where(over, 1 - state.done, zero)
+        state.info["steps"] = steps
+        return state.replace(done=done)
+
+
+class ClipAutoResetWrapper(Wrapper):
+    """`AutoResetWrapper` of an env with clip restarts: where done, the env takes the NEXT entry of its start bank
+    (`info['restart_bank']`, built by the env's `reset`) -- slot' = (slot + 1) mod K; pipeline state, observation and `cur_frame` come
+    from entry slot' -- so the restarted episode rejoins its clip at the frame its state was formed at.  Bank and slot are info: never
+    re-drawn, never restored."""
+
+    def step(self, state, action):
+        if "steps" in state.info:
+            steps = state.info["steps"]
+            steps = torch.where(state.done.bool(), torch.zeros_like(steps), steps)
+            state.info.update(steps=steps)
+        state = state.replace(done=torch.zeros_like(state.done))
+        state = self.env.step(state, action)
+        done = state.done.bool()
+        bank, slot = state.info["restart_bank"], state.info["restart_slot"]
+        K = bank["frame"].shape[0]
+        nslot = torch.where(done, (slot + 1) % K, slot)
+        row, env = nslot.long(), torch.arange(done.shape[0], device=done.device)
+
+        def where_done(x, y):      # x: the bank's leaf [K, N, ...]
+            d = done.reshape((-1,) + (1,) * (y.dim() - 1))
+            return torch.where(d, x[row, env], y)
+
+        new_ps = _tree_map2(where_done, bank["pipeline_state"], state.pipeline_state)
+        obs = where_done(bank["obs"], state.obs)
+        state.info["cur_frame"] = where_done(bank["frame"], state.info["cur_frame"])
+        state.info["restart_slot"] = nslot
+        return state.replace(pipeline_state=new_ps, obs=obs)
+
+
 class EvalWrapper(Wrapper):
     """Accumulates episode metrics for evaluation (brax EvalWrapper)."""
 
@@ -177,6 +238,8 @@ class FusedEpisodeAutoResetWrapper(Wrapper):
         state = self.env.reset(rng, **kw)
         state.info["steps"] = torch.zeros_like(state.reward)
         state.info["truncation"] = torch.zeros_like(state.reward)
+        if getattr(_base(self.env), "clip_restarts", 0) >= 1:      # the restores draw from info['restart_bank'], whose entry 0 is this state
+            return state
         state.info["first_pipeline_state"] = state.pipeline_state
         state.info["first_obs"] = state.obs
         return state
@@ -184,6 +247,18 @@ class FusedEpisodeAutoResetWrapper(Wrapper):
     def step(self, state, action):
         from .. import hip
         nstate = self.env.step(state, action)              # fresh tensors: safe to finish in place
+        base = _base(self.env)
+        if getattr(base, "clip_restarts", 0) >= 1:         # clip restarts: the rule of the two Clip wrappers in one launch
+            bank, ps = nstate.info["restart_bank"], nstate.pipeline_state
+            names = [f.name for f in dataclasses.fields(ps) if torch.is_tensor(getattr(ps, f.name))]
+            first = [getattr(bank["pipeline_state"], n) for n in names] + [bank["obs"]]
+            cur = [getattr(ps, n) for n in names] + [nstate.obs]
+            steps, trunc = torch.empty_like(nstate.done), torch.empty_like(nstate.done)
+            slot = torch.empty_like(state.info["restart_slot"])
+            hip.wrap_clip_restart(first, cur, state.done, state.info["steps"], nstate.done, steps, trunc, self.episode_length, 1,
+                                  nstate.info["cur_frame"], bank["frame"], state.info["restart_slot"], slot, base.track_len, base.end_at_clip_end)
+            nstate.info.update(steps=steps, truncation=trunc, restart_slot=slot)
+            return nstate
         fps, ps = nstate.info["first_pipeline_state"], nstate.pipeline_state
         names = [f.name for f in dataclasses.fields(ps) if torch.is_tensor(getattr(ps, f.name))]
         first = [getattr(fps, n) for n in names] + [nstate.info["first_obs"]]
@@ -212,7 +287,8 @@ class FusedEpisodeAutoResetWrapper(Wrapper):
 
 def wrap(env, episode_length: int = 1000, action_repeat: int = 1, randomization_fn=None):
     """brax.envs.wrappers.training.wrap: Vmap -> Episode -> AutoReset (one fused wrapper for a HIP env with
-    action_repeat 1; RR_FUSED_WRAPPERS=0 selects the composition).  `randomization_fn(sys) -> (sys_v, in_axes)` (keys already bound):
+    action_repeat 1; RR_FUSED_WRAPPERS=0 selects the composition; an env with `clip_restarts >= 1` gets the fused wrapper too, or
+    `ClipEpisodeWrapper` -> `ClipAutoResetWrapper` as the composition).  `randomization_fn(sys) -> (sys_v, in_axes)` (keys already bound):
     brax puts a DomainRandomizationVmapWrapper in place of the VmapWrapper; here the env's batch takes the per-env parameters
     (`PipelineEnv.randomize`) and every later step of it, wrapped or not, runs on them."""
     import os
@@ -224,5 +300,7 @@ def wrap(env, episode_length: int = 1000, action_repeat: int = 1, randomization_
     if action_repeat == 1 and hasattr(base, "_batch") and os.environ.get("RR_FUSED_WRAPPERS", "1") == "1":
         return FusedEpisodeAutoResetWrapper(VmapWrapper(env), episode_length)
     env = VmapWrapper(env)
+    if getattr(base, "clip_restarts", 0) >= 1:      # an env with a start bank: the clip's end and the restored frame
+        return ClipAutoResetWrapper(ClipEpisodeWrapper(env, episode_length, action_repeat))
     env = EpisodeWrapper(env, episode_length, action_repeat)
     return AutoResetWrapper(env)

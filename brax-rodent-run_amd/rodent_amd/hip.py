@@ -67,6 +67,11 @@ class RRBodyIO(C.Structure):
                 ("endeff_reward_weight", C.c_float), ("endeff_reward_scale", C.c_float)]
 
 
+class RRClipRestartIO(C.Structure):
+    """`rr_clip_restart_io`, the clip-restart block a batch carries next to its pose block (`rr_batch_set_clip_restarts`)."""
+    _fields_ = [("frames", C.c_void_p), ("slot_in", C.c_void_p), ("slot_out", C.c_void_p), ("num_slots", C.c_int32), ("end_at_clip_end", C.c_int32)]
+
+
 class RRUnrollIO(C.Structure):
     _fields_ = [("first", RRState), ("first_obs", C.c_void_p), ("prev_done", C.c_void_p), ("steps_in", C.c_void_p), ("steps_out", C.c_void_p),
                 ("truncation_out", C.c_void_p), ("episode_length", C.c_float)]
@@ -98,7 +103,7 @@ class RRPpoCfg(C.Structure):
 
 
 EXPORTS = ["rr_model_load", "rr_model_dims", "rr_model_set_solver", "rr_model_set_solver_type", "rr_model_destroy", "rr_model_table", "rr_kernarg_layout", "rr_batch_create",
-           "rr_batch_destroy", "rr_pipeline_init", "rr_pipeline_step", "rr_env_step", "rr_env_reset", "rr_pipeline_step_to", "rr_env_step_to", "rr_batch_contact_overflow", "rr_batch_bad_states", "rr_batch_unroll_supported", "rr_env_unroll", "rr_env_unroll_policy", "rr_batch_eval_supported", "rr_env_unroll_eval", "rr_batch_pose_supported", "rr_batch_set_pose", "rr_batch_set_reference_obs", "rr_batch_obs_width", "rr_batch_reference_obs_supported", "rr_batch_set_pose_termination", "rr_batch_pose_termination_supported", "rr_batch_set_body_tracking", "rr_batch_body_tracking_supported",
+           "rr_batch_destroy", "rr_pipeline_init", "rr_pipeline_step", "rr_env_step", "rr_env_reset", "rr_pipeline_step_to", "rr_env_step_to", "rr_batch_contact_overflow", "rr_batch_bad_states", "rr_batch_unroll_supported", "rr_env_unroll", "rr_env_unroll_policy", "rr_batch_eval_supported", "rr_env_unroll_eval", "rr_batch_pose_supported", "rr_batch_set_pose", "rr_batch_set_reference_obs", "rr_batch_obs_width", "rr_batch_reference_obs_supported", "rr_batch_set_pose_termination", "rr_batch_pose_termination_supported", "rr_batch_set_body_tracking", "rr_batch_body_tracking_supported", "rr_batch_set_clip_restarts", "rr_batch_clip_restarts_supported", "rr_wrap_clip_restart",
            "rr_compute_gae", "rr_mlp_forward", "rr_ppo_loss_workspace_bytes", "rr_ppo_loss", "rr_policy_act_workspace_bytes", "rr_policy_act", "rr_policy_sample", "rr_policy_backward_workspace_bytes", "rr_policy_backward", "rr_mlp_silu_backward_workspace_bytes", "rr_mlp_silu_backward", "rr_mlp_value_backward_workspace_bytes", "rr_mlp_policy_backward", "rr_mlp_policy_backward_workspace_bytes", "rr_mlp_value_backward", "rr_mlp_weight_grad_workspace_bytes", "rr_mlp_weight_grad", "rr_mlp_weight_grad_batch_workspace_bytes", "rr_mlp_weight_grad_batch", "rr_obs_moments_workspace_bytes", "rr_obs_moments", "rr_wrap_episode_autoreset", "rr_debug_layout", "rr_batch_set_schedule", "rr_batch_set_env_params", "rr_batch_env_params_supported", "rr_batch_set_profile", "rr_batch_set_ls_repeat_exit", "rr_batch_set_solver_trim", "rr_batch_set_solver_batch", "rr_batch_set_solve_resident", "rr_model_solve_resident_switch", "rr_batch_set_root_slot", "rr_model_root_slot_switch", "rr_batch_set_timing", "rr_batch_kernel_time", "rr_last_error"]
 
 _lib = None
@@ -194,6 +199,10 @@ def lib():
         L.rr_batch_pose_termination_supported.argtypes = [C.c_void_p, C.c_int32]
         L.rr_batch_set_body_tracking.argtypes = [C.c_void_p, C.POINTER(RRBodyIO)]
         L.rr_batch_body_tracking_supported.argtypes = [C.c_void_p, C.c_int32]
+        L.rr_batch_set_clip_restarts.argtypes = [C.c_void_p, C.POINTER(RRClipRestartIO)]
+        L.rr_batch_clip_restarts_supported.argtypes = [C.c_void_p, C.c_int32]
+        L.rr_wrap_clip_restart.argtypes = [C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int32)] + \
+            [C.c_void_p] * 5 + [C.c_float, C.c_float] + [C.c_void_p] * 4 + [C.c_int32] * 3 + [C.c_void_p]
         L.rr_batch_set_ls_repeat_exit.argtypes = [C.c_void_p, C.c_int32]
         L.rr_batch_set_solver_trim.argtypes = [C.c_void_p, C.c_int32]
         L.rr_batch_set_solver_batch.argtypes = [C.c_void_p, C.c_int32]
@@ -308,6 +317,7 @@ class Batch:
         self._pose = None           # the tensors of the pose block in force (set_pose)
         self._pterm = None          # the tensor of the pose-termination block in force (set_pose_termination)
         self._body = None           # the tensors of the body-tracking block in force (set_body_tracking)
+        self._restart = None        # the tensors of the clip-restart block in force (set_clip_restarts)
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream().cuda_stream
         _check(lib().rr_batch_create(model.h, self.N, self.device.index or 0, C.c_void_p(stream), C.byref(self.h)))
@@ -370,6 +380,9 @@ class Batch:
         fail = env.get("pose_fail")         # pose termination rides there too: the code array [N] and `pose_termination` = the three thresholds
         if fail is None and self._pterm is not None:        # cleared BEFORE the pose block may go: the library keeps the pose block while it stands
             self.set_pose_termination(None)
+        restart = env.get("restart")        # clip restarts likewise: dict(frames [K, N], slot_in [N], slot_out [N], end_at_clip_end), multi-step launches only
+        if restart is None and self._restart is not None:
+            self.set_clip_restarts(None)
         bodies = env.get("track_bodies")    # body tracking likewise: [(C), T, nbody, 3] next to `body_weights` [2, nbody] and `body_metrics` [N, 2]
         if bodies is None and self._body is not None:
             self.set_body_tracking(None)
@@ -387,6 +400,8 @@ class Batch:
                 raise ValueError(f"env io: track_bodies has shape {tuple(bodies.shape)}, expected {tuple(tp.shape[:-1]) + (d.nbody, 3)}")
             self.set_body_tracking(bodies, env.get("body_weights"), env.get("body_metrics"), env.get("body_reward", (1.0, 8.0)),
                                    env.get("endeff_reward", (1.0, 100.0)))
+        if restart is not None:
+            self.set_clip_restarts(restart["frames"], restart["slot_in"], restart["slot_out"], restart.get("end_at_clip_end", False))
         return e
 
     # ------------------------------------------------------------------ C-ABI calls
@@ -435,9 +450,15 @@ class Batch:
 
     def _unroll_io(self, wrap) -> RRUnrollIO:
         """`wrap` = dict(first, first_obs, prev_done, steps_in, steps_out, truncation_out, episode_length): the state of the Episode +
-        AutoReset wrappers that a multi-step launch reads and writes."""
+        AutoReset wrappers that a multi-step launch reads and writes.  With `slots` = K (an env with clip restarts) `first` and
+        `first_obs` are the bank, [K, N, width] each."""
         N, K = self.N, self.obs_width()
-        return RRUnrollIO(self._state(wrap["first"]), _ptr(wrap["first_obs"], numel=N * K), *(_ptr(wrap[k], numel=N) for k in
+        S = int(wrap.get("slots", 1))
+        d = self.dims
+        f = wrap["first"]
+        first = RRState(_ptr(f["qpos"], numel=S * N * d.nq), _ptr(f["qvel"], numel=S * N * d.nv), _ptr(f["act"], numel=S * N * d.na),
+                        _ptr(f["qacc_warmstart"], numel=S * N * d.nv))
+        return RRUnrollIO(first, _ptr(wrap["first_obs"], numel=S * N * K), *(_ptr(wrap[k], numel=N) for k in
                           ("prev_done", "steps_in", "steps_out", "truncation_out")), float(wrap["episode_length"]))
 
     def _actor_io(self, who: str, actor: dict, obs_in, T: int, noise=None, actions_out=None, traj: Optional[dict] = None, segment: int = 0) -> RRActorIO:
@@ -564,6 +585,29 @@ class Batch:
         _check(lib().rr_batch_set_body_tracking(self.h, C.byref(t)))
         self._body = (track_bodies, body_weights, body_metrics)
 
+    def set_clip_restarts(self, frames: Optional[torch.Tensor], slot_in: Optional[torch.Tensor] = None, slot_out: Optional[torch.Tensor] = None,
+                          end_at_clip_end: bool = False):
+        """The clip-restart block of this batch's later multi-step launches (C ABI `rr_batch_set_clip_restarts`): `frames` int32 [K, N]
+        the start frame of each bank entry, `slot_in` / `slot_out` int32 [N]; None clears it.  Needs the pose block (`set_pose`).  The
+        env-io dict of a launch (`restart` key) sets or clears it by itself.  The batch keeps the tensors alive."""
+        if frames is None:
+            _check(lib().rr_batch_set_clip_restarts(self.h, None))
+            self._restart = None
+            return
+        if frames.dim() != 2 or frames.shape[1] != self.N:
+            raise ValueError(f"clip restarts: frames has shape {tuple(frames.shape)}, expected [K, {self.N}]")
+        t = RRClipRestartIO(_ptr(frames, torch.int32), _ptr(slot_in, torch.int32, self.N), _ptr(slot_out, torch.int32, self.N),
+                            int(frames.shape[0]), int(bool(end_at_clip_end)))
+        _check(lib().rr_batch_set_clip_restarts(self.h, C.byref(t)))
+        self._restart = (frames, slot_in, slot_out)
+
+    def clip_restarts_supported(self, with_actor: bool = False) -> Optional[str]:
+        """None when this batch's multi-step launches serve clip restarts at its frame count (C ABI `rr_batch_clip_restarts_supported`)
+        -- with `with_actor` the one-launch rollout with the actor inside -- else the refusal's text."""
+        if _check(lib().rr_batch_clip_restarts_supported(self.h, int(with_actor))) == 1:
+            return None
+        return lib().rr_last_error().decode()
+
     def body_tracking_supported(self, with_actor: bool = False) -> Optional[str]:
         """None when this batch serves body tracking at its frame count (C ABI `rr_batch_body_tracking_supported`) -- with
         `with_actor` also in the one-launch rollout with the actor inside -- else the refusal's text."""
@@ -683,6 +727,28 @@ def wrap_episode_autoreset(first, cur, prev_done, prev_steps, done, steps, trunc
     stream = torch.cuda.current_stream(done.device).cuda_stream
     _check(lib().rr_wrap_episode_autoreset(N, n, F, Cu, W, prev_done.data_ptr(), prev_steps.data_ptr(), done.data_ptr(), steps.data_ptr(),
                                            truncation.data_ptr(), float(episode_length), float(action_repeat), C.c_void_p(stream)))
+
+
+def wrap_clip_restart(first, cur, prev_done, prev_steps, done, steps, truncation, episode_length: float, action_repeat: float,
+                      cur_frame, bank_frames, slot_in, slot_out, track_len: int, end_at_clip_end: bool):
+    """`wrap_episode_autoreset` for an env with clip restarts (C ABI `rr_wrap_clip_restart`): `first` are banks [K, N, ...], `cur_frame`
+    int32 [N] holds the stepped frame and is finished in place, `bank_frames` int32 [K, N], `slot_in` / `slot_out` int32 [N]."""
+    n = len(cur)
+    N = done.numel()
+    K = bank_frames.shape[0]
+    for t in list(first) + list(cur) + [prev_done, prev_steps, done, steps, truncation]:
+        _ptr(t)
+    for f, c in zip(first, cur):
+        if tuple(f.shape) != (K,) + tuple(c.shape):
+            raise ValueError("bank / current state shapes differ")
+    F = (C.c_void_p * n)(*[t.data_ptr() for t in first])
+    Cu = (C.c_void_p * n)(*[t.data_ptr() for t in cur])
+    W = (C.c_int32 * n)(*[t.numel() // N for t in cur])
+    stream = torch.cuda.current_stream(done.device).cuda_stream
+    _check(lib().rr_wrap_clip_restart(N, n, F, Cu, W, prev_done.data_ptr(), prev_steps.data_ptr(), done.data_ptr(), steps.data_ptr(),
+                                      truncation.data_ptr(), float(episode_length), float(action_repeat), _ptr(cur_frame, torch.int32, N),
+                                      _ptr(bank_frames, torch.int32, K * N), _ptr(slot_in, torch.int32, N), _ptr(slot_out, torch.int32, N),
+                                      int(K), int(track_len), int(bool(end_at_clip_end)), C.c_void_p(stream)))
 
 
 def _mlp_net(weights, biases, in_dim=None):

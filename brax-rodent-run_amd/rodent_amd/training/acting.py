@@ -95,7 +95,9 @@ def fused_unroll_supported(wenv, policy_net, dist) -> bool:
     without reference frames, 1664 with them); a wider row falls back to per-step collection."""
     base = wenv.unwrapped if hasattr(wenv, "unwrapped") else wenv
     ask = getattr(getattr(base, "_batch", None), "reference_obs_supported", None)
-    if ask is not None and getattr(base, "body_tracking", None) is not None:      # its env steps run the wide actor at every frame count
+    if ask is not None and getattr(base, "clip_restarts", 0) >= 1:      # its multi-step launches run the clip-restart instances: the wide actor too
+        width_ok = base._batch.clip_restarts_supported(with_actor=True) is None
+    elif ask is not None and getattr(base, "body_tracking", None) is not None:      # its env steps run the wide actor at every frame count
         width_ok = base._batch.body_tracking_supported(with_actor=True) is None
     elif ask is not None and getattr(base, "pose_termination", None) is not None:      # likewise
         width_ok = base._batch.pose_termination_supported(with_actor=True) is None

@@ -75,6 +75,13 @@ def main():
     ap.add_argument("--end-effector-ids", type=int, nargs="+", default=None, metavar="ID", help="with --track-bodies: body ids of the end effectors, "
                     "which get a sharper term of their own (Rodent(end_effector_ids=...)).  The model blobs hold no body names: on "
                     "rodent_optimized / rodent_0 foot_L, foot_R, hand_L, hand_R, skull are 11 15 59 64 54, on rodent_new each is one higher")
+    ap.add_argument("--clip-restarts", type=int, default=0, metavar="K", help="with --track-pose: a restarted episode rejoins its clip "
+                    "(Rodent(clip_restarts=K), 1 .. 64): each env keeps K start states drawn at reset and takes the next one -- state, "
+                    "observation AND frame -- at every restart.  0, the default: the first state comes back and the frame runs on, as upstream")
+    ap.add_argument("--restart-frames", type=int, nargs=2, default=None, metavar=("LO", "HI"), help="with --clip-restarts K > 1: start frames of "
+                    "the K - 1 further start states are drawn in [LO, HI) (default 0 100, the reference's range)")
+    ap.add_argument("--end-at-clip-end", action="store_true", help="with --clip-restarts: truncate an episode at the clip's last frame instead "
+                    "of comparing it with the clamped last row (the clip must be longer than every start frame: the synthetic line has 250 frames)")
     ap.add_argument("--policy-width", type=int, choices=(32, 256), default=32, help="units per hidden layer of the policy network; both "
                     "widths run on the hand-written learner kernels (256: per-step rollouts, the in-kernel actor is 32-wide)")
     ap.add_argument("--policy-depth", type=int, default=4, help="hidden layers of the policy network (1 .. 7 for the hand-written kernels; "
@@ -106,6 +113,12 @@ def main():
         ap.error("--track-bodies: the body positions are indexed like the reference pose; add --track-pose")
     if args.end_effector_ids is not None and not args.track_bodies:
         ap.error("--end-effector-ids: the end effectors are bodies of the clip; add --track-bodies")
+    if (args.clip_restarts or args.restart_frames is not None or args.end_at_clip_end) and not args.track_pose:
+        ap.error("--clip-restarts / --restart-frames / --end-at-clip-end: the restarted env rejoins the reference pose; add --track-pose")
+    if not 0 <= args.clip_restarts <= 64:
+        ap.error("--clip-restarts: 0 .. 64")
+    if args.end_at_clip_end and args.clip_restarts < 1:
+        ap.error("--end-at-clip-end: needs --clip-restarts K >= 1")
     if not 0 <= args.reference_frames <= 16:
         ap.error("--reference-frames: 0 .. 16")
     clips = None                                     # the loaded ReferenceClip(s), [C, T, ...] fields; None for a .npy track or the synthetic line
@@ -150,7 +163,9 @@ def main():
         solver=config["solver"], iterations=config["iterations"], ls_iterations=config["ls_iterations"],
         vision=config["vision"], num_envs=args.envs_per_gpu, xml_path=args.xml, device=f"cuda:{local_rank}",
         bad_state_max=args.bad_state_max, reference_obs_frames=args.reference_frames, max_pos_error=args.max_pos_error,
-        max_quat_error=args.max_quat_error, max_joint_error=args.max_joint_error, **pose)
+        max_quat_error=args.max_quat_error, max_joint_error=args.max_joint_error, clip_restarts=args.clip_restarts,
+        restart_frame_range=None if args.restart_frames is None else tuple(args.restart_frames), end_at_clip_end=args.end_at_clip_end,
+        **pose)     # a clip too short for --end-at-clip-end is refused here with the reason (ValueError)
 
     train_fn = functools.partial(
         ppo.train, num_timesteps=config["num_timesteps"], num_evals=int(config["num_timesteps"] / config["eval_every"]),

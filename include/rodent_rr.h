@@ -362,6 +362,38 @@ typedef struct rr_body_io {
 int rr_batch_set_body_tracking(rr_batch* b, const rr_body_io* body);
 int rr_batch_body_tracking_supported(const rr_batch* b, int32_t with_actor);
 
+/* Clip restarts: a restarted episode rejoins its clip at a drawn frame.  Upstream's AutoReset brings back the first state and the first
+ * observation and leaves info -- cur_frame -- alone; a tracking env then compares the restored pose with frames it never started at.  With
+ * this block set on the BATCH (next to the pose block it needs; the structs above are closed) the multi-step launches -- rr_env_unroll and
+ * rr_env_unroll_policy; single steps have no restore in the kernel and ignore the block -- read rr_unroll_io::first and first_obs as a
+ * BANK of K = num_slots start states, [K][N][width] each ([K][N][rr_batch_obs_width] for first_obs), `frames` [K][N] the frame each entry
+ * was formed at and slot_in [N] the entry each env restored last (0 after a reset).  Per wrapped env step, with done_env the env's own done
+ * (pose failure and bad state included), new_frame = old_frame + 1 and T = rr_env_io::track_len:
+ *   steps' = (prev_done ? 0 : steps) + 1
+ *   over   = steps' >= episode_length  ||  (end_at_clip_end && new_frame >= T - 1)
+ *   done   = over ? 1 : done_env;   truncation = over ? 1 - done_env : 0
+ *   done:  slot' = (slot + 1) mod K;  state, obs <- bank[slot'];  cur_frame <- frames[slot'];     else slot' = slot, cur_frame = new_frame
+ * new_frame >= T - 1: the new state's observation has no next frame left to read without clamping; the clip's end is a truncation like
+ * episode_length.  The step that ends the episode is untouched: reward, metrics, pose_fail and the trajectory read old_frame as without the
+ * block.  env->cur_frame and slot_out [N] receive the frame and the slot after the launch's last step, so launches chain.  A launch takes
+ * the pointers as they are when it is issued.  num_slots = 1: the frame comes back with the one stored state.
+ * rr_batch_set_clip_restarts: NULL clears (a batch starts without one); num_slots outside 1 .. 64, a NULL pointer, or no pose block on the
+ * batch (rr_batch_set_pose first): RR_EINVAL; RR_EUNSUPPORTED with the reason wherever pose tracking is unsupported.  While the block is
+ * set, rr_batch_set_pose(b, NULL) is RR_EINVAL (clear this block first) and rr_env_unroll_eval refuses, as for any pose block.  The
+ * launches run the reference-observation instances' code whatever the frame count, so rr_env_unroll_policy serves rows of up to 1664
+ * entries; pose-termination and body-tracking blocks may stand next to this one or not.
+ * rr_batch_clip_restarts_supported(b, with_actor): 1 / 0 -- whether rr_env_unroll (with_actor != 0: rr_env_unroll_policy) serves the block
+ * on this batch at its current frame count; with 0 rr_last_error holds the reason.  It does not need the pose block to be set. */
+typedef struct rr_clip_restart_io {
+  const int32_t* frames;       /* [K][N]: the start frame of each bank entry */
+  const int32_t* slot_in;      /* [N] */
+  int32_t* slot_out;           /* [N] out */
+  int32_t num_slots;           /* K: 1 .. 64 */
+  int32_t end_at_clip_end;     /* != 0: the clip's end truncates the episode */
+} rr_clip_restart_io;
+int rr_batch_set_clip_restarts(rr_batch* b, const rr_clip_restart_io* restart);
+int rr_batch_clip_restarts_supported(const rr_batch* b, int32_t with_actor);
+
 /* Generalised advantage estimation of one PPO minibatch, the reverse scan of brax.training.agents.ppo.losses.compute_gae
  * [UP; SURVEY.md Appendix E], one thread per trajectory.  All arrays time-major [T][B] device float32; bootstrap [B];
  * outputs vs [T][B] and advantages [T][B].  `stream` is a hipStream_t (NULL = default stream). */
@@ -521,6 +553,14 @@ int rr_obs_moments(const float* obs, int64_t nseq, int32_t Tp1, int32_t T, int32
 int rr_wrap_episode_autoreset(int32_t num_envs, int32_t narr, const float* const* first, float* const* cur, const int32_t* widths,
                               const float* prev_done, const float* prev_steps, float* done, float* steps, float* truncation,
                               float episode_length, float action_repeat, void* stream);
+/* The same for an env with clip restarts (rr_clip_restart_io's rule on one env step; the entry above is unchanged): `first[i]` are banks
+ * [num_slots][N][widths[i]], cur_frame [N] holds the stepped frame and is finished in place (the bank entry's frame where done),
+ * bank_frames [num_slots][N], slot_in / slot_out [N] (they may alias), track_len = T, end_at_clip_end the flag. */
+int rr_wrap_clip_restart(int32_t num_envs, int32_t narr, const float* const* first, float* const* cur, const int32_t* widths,
+                         const float* prev_done, const float* prev_steps, float* done, float* steps, float* truncation,
+                         float episode_length, float action_repeat, int32_t* cur_frame, const int32_t* bank_frames,
+                         const int32_t* slot_in, int32_t* slot_out, int32_t num_slots, int32_t track_len, int32_t end_at_clip_end,
+                         void* stream);
 
 /* Scheduling of the environments on the GPU (results are unaffected: environments are independent).  `env_map` (device,
  * [N] int32, a permutation of 0..N-1, or NULL = identity): workgroup w steps environment env_map[w]; `cost_cycles` (device,
