@@ -59,7 +59,7 @@ struct rr_model {
 // One function maps (model, launch form, variant) to the kernel instance that serves it, or to the reason there is none: launch(),
 // the support queries and the attribute loop of rr_batch_create all ask it, so none of them can disagree about what exists.
 enum Form { F_STEP, F_UNROLL, F_ACTOR, F_EVAL, N_FORMS };                        // single step | multi-step | ... with the actor | evaluation
-enum Variant { V_PROD, V_DEBUG, V_PROFILE, V_RAND, V_PAIR, V_POSE, V_MATLDS, V_REFOBS, V_POSETERM, V_TWOSLOT, V_BODY, V_RESTART, N_VARIANTS }; // production | debug dump | cycle-stamp profile | per-env parameters | two-wave pair | pose tracking | production, inverse factor read from LDS | pose tracking with the reference observation | ... and with pose termination | production, tree phases on the plain lane <-> body map | pose tracking with the body-position terms (a superset of the pose-termination form) | ... with the restore from the bank of start states (multi-step forms only; a superset of the body-tracking form)
+enum Variant { V_PROD, V_DEBUG, V_PROFILE, V_RAND, V_PAIR, V_POSE, V_MATLDS, V_POSETERM, V_TWOSLOT, V_BODY, V_RESTART, N_VARIANTS }; // production | debug dump | cycle-stamp profile | per-env parameters | two-wave pair | pose tracking, the pose block alone | production, inverse factor read from LDS | pose tracking with pose termination and no body tracking (V_BODY computes the same; kept for its speed with the actor inside) | production, tree phases on the plain lane <-> body map | pose tracking with any of reference frames, pose termination and body tracking | ... with the restore from the bank of start states (multi-step forms only; a superset of V_BODY)
 struct Instance { kern_t kern; const char* why = nullptr; bool fixed = false; };      // why: the reason when kern is null (multi-step forms: with the entry point that reports it); fixed: compiled for the model's dimensions
 
 // The shape the root-slot tree phases need beyond the dimensions (rr_kernel.h Wave::ROOT): one tree; body 1 is the child of the world and
@@ -81,13 +81,18 @@ static bool root_slot_ok(const rr_model* m) {
 // run the root-slot tree phases (RR_ROOT_SLOT) the model has the shape for them; a model that has not runs the generic instances
 static bool rodent_fixed(const rr_model* m) { return RRDimsRodent::matches(m->kd) && (!rr_root_slot<RRDimsRodent>::value || root_slot_ok(m)); }
 
-static Instance select(const rr_model* m, Form form, Variant v) {
+// The sentence with which rr_env_unroll_eval refuses a pose batch, worded after the most specific block the batch carries (defined with
+// the batch's option checks below).  Null batch: the pose block alone.
+static const char* pose_eval_refusal(const rr_batch* b);
+
+// b: the batch whose blocks word the evaluation refusal of the pose variants; it decides nothing else
+static Instance select(const rr_model* m, Form form, Variant v, const rr_batch* b = nullptr) {
   const bool s111 = m->NBS == 1 && m->NVS == 1 && m->NCS == 1, s221 = m->NBS == 2 && m->NVS == 2 && m->NCS == 1, s332 = m->NBS == 3 && m->NVS == 3 && m->NCS == 2;
   const bool newton = m->solver == 2, eval = form == F_EVAL, unroll = form != F_STEP, actor = form == F_ACTOR;
   const char *no_diag = "no diagnostic kernel instance for this model", *no_slots = "no kernel instance for this model's slot counts";
   auto no = [](const char* why) { return Instance{nullptr, why}; };
   // rr_step_kernel<NBS, NVS, NCS, PROF, DBG, dims, NEWTON, UNROLL, ACTOR, PAIR, DYN>, rr_rand_kernel<dims, UNROLL, ACTOR>, rr_eval_kernel<dims, DYN>,
-  // rr_pose_kernel<dims, UNROLL, ACTOR>, rr_refobs_kernel<dims, UNROLL, ACTOR>, rr_poseterm_kernel<dims, UNROLL, ACTOR>, rr_body_kernel<dims, UNROLL, ACTOR>, rr_restart_kernel<dims, ACTOR>, rr_matlds_kernel<dims>, rr_twoslot_kernel<dims>
+  // rr_pose_kernel<dims, UNROLL, ACTOR>, rr_poseterm_kernel<dims, UNROLL, ACTOR>, rr_body_kernel<dims, UNROLL, ACTOR>, rr_restart_kernel<dims, ACTOR>, rr_matlds_kernel<dims>, rr_twoslot_kernel<dims>
   if (v == V_PAIR && (unroll || newton || !RRDimsRodentNew::matches(m->kd_rep))) return no("no two-wave pair instance for this model / launch form");
   if (v == V_PAIR) return {rr_step_kernel<2, 2, 1, false, false, RRDimsRodentNew, false, false, false, true>, nullptr, true};      // one replica = the rodent_new dims
   if (v == V_MATLDS) {      // rr_batch_set_solve_resident(b, 0): the production single-step instance of the benchmark model's dimensions, solves from LDS
@@ -112,15 +117,11 @@ static Instance select(const rr_model* m, Form form, Variant v) {
     if (m->pair_ok) return no("rr_env_unroll_eval: two-tree models served by the two-wave pair instance have no multi-step instance");
     if (!s221) return no("rr_env_unroll_eval: only the (2,2,1) slot counts have an evaluation instance");
     if (v == V_RAND) return no("rr_env_unroll_eval: no evaluation instance reads per-env parameters (this batch carries some)");
-    if (v == V_POSE) return no("rr_env_unroll_eval: no evaluation instance rewards the pose (this env io carries track_pose); evaluate step by step");
-    if (v == V_REFOBS) return no("rr_env_unroll_eval: no evaluation instance writes the reference observation (rr_batch_set_reference_obs is on); evaluate step by step");
-    if (v == V_POSETERM) return no("rr_env_unroll_eval: no evaluation instance ends episodes on the pose error (rr_batch_set_pose_termination is on); evaluate step by step");
-    if (v == V_BODY) return no("rr_env_unroll_eval: no evaluation instance rewards the body positions (rr_batch_set_body_tracking is on); evaluate step by step");
-    if (v == V_RESTART) return no("rr_env_unroll_eval: no evaluation instance restores from the bank of start states (rr_batch_set_clip_restarts is on); evaluate step by step");
-  } else if (v == V_POSE || v == V_REFOBS || v == V_POSETERM || v == V_BODY || v == V_RESTART) {
-    // Pose tracking (rr_pose_kernel; with the reference observation rr_refobs_kernel; with pose termination rr_poseterm_kernel; with the
-    // body-position terms rr_body_kernel): the same
-    // models and launch forms as the per-env parameters below, shared tables
+    if (v == V_POSE || v == V_POSETERM || v == V_BODY || v == V_RESTART) return no(pose_eval_refusal(b));
+  } else if (v == V_POSE || v == V_POSETERM || v == V_BODY || v == V_RESTART) {
+    // Pose tracking (rr_pose_kernel: the pose block alone; rr_body_kernel: with any of reference frames, pose termination and body
+    // tracking; rr_poseterm_kernel: pose termination without body tracking; rr_restart_kernel: with clip restarts): the same models and
+    // launch forms as the per-env parameters below, shared tables
     if (m->dyn) return no("pose tracking: models with candidate-pair contacts (DYN instances) have no pose instance");
     if (m->pair_ok) return no("pose tracking: two-tree models served by the two-wave pair instance have no pose instance");
     if (newton) return no("pose tracking: the Newton solver's instances have no pose instance");
@@ -156,7 +157,6 @@ static Instance select(const rr_model* m, Form form, Variant v) {
     if (eval) return rr_eval_kernel<DT>;
     if (v == V_RAND) return actor ? rr_rand_kernel<DT, true, true> : (unroll ? rr_rand_kernel<DT, true> : rr_rand_kernel<DT>);
     if (v == V_POSE) return actor ? rr_pose_kernel<DT, true, true> : (unroll ? rr_pose_kernel<DT, true> : rr_pose_kernel<DT>);
-    if (v == V_REFOBS) return actor ? rr_refobs_kernel<DT, true, true> : (unroll ? rr_refobs_kernel<DT, true> : rr_refobs_kernel<DT>);
     if (v == V_POSETERM) return actor ? rr_poseterm_kernel<DT, true, true> : (unroll ? rr_poseterm_kernel<DT, true> : rr_poseterm_kernel<DT>);
     if (v == V_BODY) return actor ? rr_body_kernel<DT, true, true> : (unroll ? rr_body_kernel<DT, true> : rr_body_kernel<DT>);
     if (v == V_RESTART) return actor ? rr_restart_kernel<DT, true> : rr_restart_kernel<DT>;
@@ -412,6 +412,14 @@ struct rr_batch {
   bool has_env_params() const { return env_dof_f || env_act_f || env_con_f; }
 };
 
+static const char* pose_eval_refusal(const rr_batch* b) {
+  if (b && b->restart.frames) return "rr_env_unroll_eval: no evaluation instance restores from the bank of start states (rr_batch_set_clip_restarts is on); evaluate step by step";
+  if (b && b->body.track_bodies) return "rr_env_unroll_eval: no evaluation instance rewards the body positions (rr_batch_set_body_tracking is on); evaluate step by step";
+  if (b && b->pterm.fail) return "rr_env_unroll_eval: no evaluation instance ends episodes on the pose error (rr_batch_set_pose_termination is on); evaluate step by step";
+  if (b && b->ref_frames > 0) return "rr_env_unroll_eval: no evaluation instance writes the reference observation (rr_batch_set_reference_obs is on); evaluate step by step";
+  return "rr_env_unroll_eval: no evaluation instance rewards the pose (this env io carries track_pose); evaluate step by step";
+}
+
 // hipMalloc recorded in the batch (rr_batch_destroy frees it), filled from `host` when given
 template <typename Ptr>
 static int dev_alloc(rr_batch* b, size_t bytes, Ptr* dst, const void* host = nullptr, size_t host_bytes = 0) {
@@ -588,7 +596,7 @@ static int check_actor(const char* who, const rr_actor_io* a, bool traj) {
 }
 // What the in-kernel actor cannot serve, or null.  ac null: the limits on the model alone (rr_batch_eval_supported).  ref_frames: of the
 // batch; the actor of the selected instance reads 64 x JM entries of the row (rr_actor_step: 1280, REFOBS instances 1664).  wide: the
-// launch runs a REFOBS instance whatever ref_frames is (pose termination, body tracking)
+// launch runs a REFOBS instance (V_POSETERM, V_BODY, V_RESTART) whatever ref_frames is
 static const char* actor_limit(const rr_model* m, const rr_actor_io* ac, int ref_frames = 0, bool wide = false) {
   static_assert(RR_ACTOR_JM == 20 && RR_ACTOR_JM_REFOBS == 26, "the two texts below name 64 x JM");
   if ((ref_frames > 0 || wide) && m->dims.obs_dim + ref_frames * m->dims.nq > 64 * RR_ACTOR_JM_REFOBS)
@@ -632,9 +640,10 @@ static int fill_io(const Launch& L, RRIO& io) {
 }
 
 // launch() step 3: the fields of the multi-step forms -- wrappers' state, actor, evaluation, pacing
-static int fill_unroll(rr_batch* b, const Launch& L, RRIO& io) {
+// wide: the launch runs V_POSETERM, V_BODY or V_RESTART, whose actor reads the wider row
+static int fill_unroll(rr_batch* b, const Launch& L, RRIO& io, bool wide) {
   if (const rr_actor_io* ac = L.ac) {
-    if (const char* limit = actor_limit(b->m, ac, io.ref_frames, io.pose_fail != nullptr || io.track_bodies != nullptr || io.restart_frames != nullptr)) return fail(RR_EUNSUPPORTED, limit);
+    if (const char* limit = actor_limit(b->m, ac, io.ref_frames, wide)) return fail(RR_EUNSUPPORTED, limit);
     io.a_obs_in = ac->obs_in; io.a_mean = ac->mean; io.a_std = ac->std; io.a_W0 = ac->w0; io.a_b0 = ac->b0;
     for (int l = 1; l < ac->nhidden; ++l) { io.a_Wt[l - 1] = ac->hidden_wt[l - 1]; io.a_b[l - 1] = ac->hidden_b[l - 1]; }
     io.a_Wth = ac->head_wt; io.a_bh = ac->head_b; io.a_noise = ac->noise; io.a_actions = ac->actions_out; io.ctrl = ac->actions_out;
@@ -683,30 +692,29 @@ static int launch(rr_batch* b, const Launch& L) {
   if (params && geom) return fail(RR_EUNSUPPORTED, "launch: no contact-geometry outputs on a batch with per-env parameters (they are served by the debug instance)");
   if (params && b->prof) return fail(RR_EUNSUPPORTED, "launch: no profile build on a batch with per-env parameters");
   // pose tracking (rr_batch_set_pose): an env step's reward terms -- a reset has no reward and ignores the block -- served by the POSE
-  // instance of the same launch form; shared tables, production instances only.  With reference frames on the batch
-  // (rr_batch_set_reference_obs) the REFOBS instance serves env steps AND resets: both write the blocks, and every row is obs_width() wide
+  // instance of the same launch form; shared tables, production instances only.  The options on top of the block:
+  //   reference frames (rr_batch_set_reference_obs): env steps AND resets write the blocks, and every row is obs_width() wide;
+  //   pose termination (rr_batch_set_pose_termination) and body tracking (rr_batch_set_body_tracking): env steps only -- a reset has
+  //   neither done nor reward and stays on the variant it uses without them;
+  //   clip restarts (rr_batch_set_clip_restarts): the multi-step launches of the training wrappers only -- single steps have no restore
+  //   in the kernel, the evaluation form none from a bank.
+  // Any of the first three selects V_BODY, clip restarts V_RESTART (rr_kernel.h rr_body_kernel: one instance for every combination);
+  // an env step with a termination block and no body block runs V_POSETERM, the same computation without the body code.  An option the
+  // batch does not carry reaches the kernel as zero frames, thresholds that no error exceeds with a null pose_fail, a null track_bodies
+  const bool pose_step = b->pose.track_pose && L.env && L.mode == 1;
   const bool refobs = b->ref_frames > 0 && b->pose.track_pose && L.env;
-  const bool pose = b->pose.track_pose && L.env && (L.mode == 1 || refobs);
-  // pose termination (rr_batch_set_pose_termination): env steps only -- a reset has no done to raise and stays on the variant it uses
-  // without the block -- served by the PTERM instance, which is a REFOBS instance for every frame count, 0 included
-  const bool pterm = b->pterm.fail && b->pose.track_pose && L.env && L.mode == 1;
-  // body tracking (rr_batch_set_body_tracking): env steps only, as pose termination; served by the BODY instance, a superset of the PTERM
-  // instance: without a termination block it gets a null pose_fail and thresholds that no error exceeds
-  const bool body = b->body.track_bodies && b->pose.track_pose && L.env && L.mode == 1;
-  // clip restarts (rr_batch_set_clip_restarts): the multi-step launches of the training wrappers only -- single steps have no restore in
-  // the kernel, the evaluation form none from a bank -- served by the RESTART instance, a superset of the BODY instance: without a
-  // body-tracking block it gets a null track_bodies, without a termination block what the BODY instance gets
-  const bool restart = b->restart.frames && b->pose.track_pose && L.env && L.mode == 1 && L.un && !L.ev;
+  const bool pose = pose_step || refobs;
+  const bool pterm = b->pterm.fail && pose_step, body = b->body.track_bodies && pose_step, restart = b->restart.frames && pose_step && L.un && !L.ev;
+  const bool options = refobs || pterm || body || restart;
+  if (options) io.pose_max_pos = io.pose_max_quat = io.pose_max_joint = INFINITY;
   if (refobs) io.ref_frames = b->ref_frames;
   if (restart) {
     io.restart_frames = b->restart.frames; io.restart_slot_in = b->restart.slot_in; io.restart_slot_out = b->restart.slot_out;
     io.restart_K = b->restart.num_slots; io.restart_end = b->restart.end_at_clip_end ? 1 : 0;
-    io.pose_max_pos = io.pose_max_quat = io.pose_max_joint = INFINITY;
   }
   if (body) {
     io.track_bodies = b->body.track_bodies; io.body_weights = b->body.body_weights; io.body_metrics = b->body.body_metrics;
     io.body_w = b->body.body_reward_weight; io.body_k = b->body.body_reward_scale; io.endeff_w = b->body.endeff_reward_weight; io.endeff_k = b->body.endeff_reward_scale;
-    io.pose_max_pos = io.pose_max_quat = io.pose_max_joint = INFINITY;
   }
   if (pterm) { io.pose_fail = b->pterm.fail; io.pose_max_pos = b->pterm.max_pos; io.pose_max_quat = b->pterm.max_quat; io.pose_max_joint = b->pterm.max_joint; }
   if (pose) {
@@ -716,7 +724,7 @@ static int launch(rr_batch* b, const Launch& L) {
   }
   if (pose && params) return fail(RR_EUNSUPPORTED, "launch: pose tracking: no pose instance reads per-env parameters (this batch carries some)");
   if (pose && (io.dbg || geom || b->prof)) return fail(RR_EUNSUPPORTED, "launch: pose tracking: no debug dump, contact-geometry outputs or profile build with track_pose (diagnostic instances have no pose form)");
-  Variant v = b->prof ? V_PROFILE : ((io.dbg || geom) ? V_DEBUG : (params ? V_RAND : (restart ? V_RESTART : (body ? V_BODY : (pterm ? V_POSETERM : (refobs ? V_REFOBS : (pose ? V_POSE : V_PROD)))))));
+  Variant v = b->prof ? V_PROFILE : ((io.dbg || geom) ? V_DEBUG : (params ? V_RAND : (restart ? V_RESTART : (pterm && !body ? V_POSETERM : (options ? V_BODY : (pose ? V_POSE : V_PROD))))));
   // two-tree model, physics only, no diagnostics: one wavefront per replica (rr_kernel.h PAIR)
   const bool pair = m->pair_ok && v == V_PROD && !L.env && !L.out && !L.un && !b->env_map && !b->cost && m->solver != 2;
   if (pair) v = V_PAIR;
@@ -729,9 +737,9 @@ static int launch(rr_batch* b, const Launch& L) {
     if (v != V_PROD) return fail(RR_EUNSUPPORTED, "launch: rr_batch_set_root_slot(b, 0) serves production launches only (no debug dump, contact-geometry outputs, profile build, per-env parameters or pose tracking on this batch)");
     v = V_TWOSLOT;
   }
-  const Instance in = select(m, L.ev ? F_EVAL : (L.ac ? F_ACTOR : (L.un ? F_UNROLL : F_STEP)), v);
+  const Instance in = select(m, L.ev ? F_EVAL : (L.ac ? F_ACTOR : (L.un ? F_UNROLL : F_STEP)), v, b);
   if (!in.kern) return fail(RR_EUNSUPPORTED, std::string(L.un ? "" : "launch: ") + in.why);
-  if (L.un && (rc = fill_unroll(b, L, io))) return rc;
+  if (L.un && (rc = fill_unroll(b, L, io, options))) return rc;
   io.env_dof_f = b->env_dof_f; io.env_act_f = b->env_act_f; io.env_con_f = b->env_con_f;      // null without per-env parameters
   io.prof = b->prof; io.env_map = b->env_map; io.cost = b->cost; io.dyn_overflow = b->dyn_overflow; io.bad_states = b->bad_states;
   if (v == V_DEBUG) io.dbg_flags = b->dbg_flags;      // the only instance that reads it
@@ -804,8 +812,9 @@ extern "C" int rr_env_unroll_policy(rr_batch* b, const rr_state* in, const rr_st
 }
 extern "C" int rr_batch_eval_supported(const rr_batch* b) {
   if (!b) return fail(RR_EINVAL, "rr_batch_eval_supported: null batch");
-  const Variant v = b->prof ? V_PROFILE : (b->has_env_params() ? V_RAND : (b->restart.frames ? V_RESTART : (b->body.track_bodies ? V_BODY : (b->pterm.fail ? V_POSETERM : (b->ref_frames > 0 ? V_REFOBS : V_PROD)))));
-  return (select(b->m, F_EVAL, v).kern && !actor_limit(b->m, nullptr)) ? 1 : 0;
+  const bool options = b->ref_frames > 0 || b->pterm.fail || b->body.track_bodies || b->restart.frames;      // of the pose family: none has an evaluation instance
+  const Variant v = b->prof ? V_PROFILE : (b->has_env_params() ? V_RAND : (options ? V_BODY : V_PROD));
+  return (select(b->m, F_EVAL, v, b).kern && !actor_limit(b->m, nullptr)) ? 1 : 0;
 }
 extern "C" int rr_env_unroll_eval(rr_batch* b, const rr_state* in, const rr_state* outst, int32_t num_steps, int32_t n_frames, const rr_env_io* env,
                                   const int32_t* cur_frame_in, const rr_unroll_io* wrap, const rr_actor_io* actor, const rr_eval_io* ev) {
@@ -1438,14 +1447,18 @@ extern "C" int rr_batch_env_params_supported(const rr_batch* b) {
   if (!b) return fail(RR_EINVAL, "rr_batch_env_params_supported: null batch");
   return select(b->m, F_STEP, V_RAND).kern ? 1 : 0;
 }
+// the answer of a rr_batch_*_supported query: 1, or 0 with `who: why` as the last error
+static int supported(const char* who, const char* why) {
+  if (why) (void)fail(RR_EUNSUPPORTED, std::string(who) + ": " + why);
+  return why ? 0 : 1;
+}
 extern "C" int rr_batch_pose_supported(const rr_batch* b) {
   if (!b) return fail(RR_EINVAL, "rr_batch_pose_supported: null batch");
   const Instance in = select(b->m, F_STEP, V_POSE);
   const char* why = in.kern ? nullptr : in.why;
   if (!why && b->has_env_params()) why = "pose tracking: no pose instance reads per-env parameters (this batch carries some)";
   if (!why && b->prof) why = "pose tracking: no profile build with track_pose";
-  if (why) (void)fail(RR_EUNSUPPORTED, std::string("rr_batch_pose_supported: ") + why);
-  return why ? 0 : 1;
+  return supported("rr_batch_pose_supported", why);
 }
 extern "C" int rr_batch_set_pose(rr_batch* b, const rr_pose_io* p) {
   if (!b) return fail(RR_EINVAL, "rr_batch_set_pose: null batch");
@@ -1464,49 +1477,39 @@ extern "C" int rr_batch_set_pose(rr_batch* b, const rr_pose_io* p) {
   b->pose = *p;
   return RR_OK;
 }
-// The reference observation: frames 0 .. 16 on a batch that serves pose tracking; with_actor also asks the in-kernel actor's width
-static const char* refobs_limit(const rr_batch* b, int frames, bool with_actor) {
-  if (frames < 0 || frames > 16) return "reference observation: frames must lie in 0 .. 16";
-  if (frames == 0) return with_actor ? actor_limit(b->m, nullptr) : nullptr;      // the model's own row in the instances the batch launches anyway
-  const Instance in = select(b->m, with_actor ? F_ACTOR : F_STEP, V_REFOBS);
+// What keeps an option of the pose family off this batch, or null.  form: F_STEP for the options that rr_body_kernel serves in every
+// launch form (reference frames, pose termination, body tracking), F_UNROLL for clip restarts (rr_restart_kernel: multi-step forms
+// only).  frames: the reference frames the batch carries or is about to, 0 .. 16; with_actor also asks the width the in-kernel actor of
+// these instances reads
+static const char* pose_option_limit(const rr_batch* b, Form form, int frames, bool with_actor) {
+  const Instance in = select(b->m, with_actor ? F_ACTOR : form, form == F_STEP ? V_BODY : V_RESTART);
   if (!in.kern) return in.why;
   if (b->has_env_params()) return "pose tracking: no pose instance reads per-env parameters (this batch carries some)";
   if (b->prof) return "pose tracking: no profile build with track_pose";
-  return with_actor ? actor_limit(b->m, nullptr, frames) : nullptr;
+  return with_actor ? actor_limit(b->m, nullptr, frames, true) : nullptr;
 }
 extern "C" int rr_batch_reference_obs_supported(const rr_batch* b, int32_t frames, int32_t with_actor) {
   if (!b) return fail(RR_EINVAL, "rr_batch_reference_obs_supported: null batch");
-  const char* why = refobs_limit(b, frames, with_actor != 0);
-  if (why) (void)fail(RR_EUNSUPPORTED, std::string("rr_batch_reference_obs_supported: ") + why);
-  return why ? 0 : 1;
+  if (frames < 0 || frames > 16) return supported("rr_batch_reference_obs_supported", "reference observation: frames must lie in 0 .. 16");
+  // no frames: the model's own row in the instances the batch launches anyway
+  return supported("rr_batch_reference_obs_supported", frames == 0 ? (with_actor ? actor_limit(b->m, nullptr) : nullptr) : pose_option_limit(b, F_STEP, frames, with_actor != 0));
 }
 extern "C" int rr_batch_set_reference_obs(rr_batch* b, int32_t frames) {
   if (!b) return fail(RR_EINVAL, "rr_batch_set_reference_obs: null batch");
   if (frames < 0 || frames > 16) return fail(RR_EINVAL, "rr_batch_set_reference_obs: frames must lie in 0 .. 16");
   if (frames > 0 && !b->pose.track_pose) return fail(RR_EINVAL, "rr_batch_set_reference_obs: frames > 0 need a pose block (rr_batch_set_pose) first: the rows come from track_pose");
-  if (const char* why = refobs_limit(b, frames, false)) return fail(RR_EUNSUPPORTED, std::string("rr_batch_set_reference_obs: ") + why);
+  if (const char* why = frames > 0 ? pose_option_limit(b, F_STEP, frames, false) : nullptr) return fail(RR_EUNSUPPORTED, std::string("rr_batch_set_reference_obs: ") + why);
   b->ref_frames = frames;
   return RR_OK;
 }
-// Pose termination: wherever pose tracking is served, at the batch's frame count; with_actor also asks the width the actor of the
-// reference-observation instances reads
-static const char* pterm_limit(const rr_batch* b, bool with_actor) {
-  const Instance in = select(b->m, with_actor ? F_ACTOR : F_STEP, V_POSETERM);
-  if (!in.kern) return in.why;
-  if (b->has_env_params()) return "pose tracking: no pose instance reads per-env parameters (this batch carries some)";
-  if (b->prof) return "pose tracking: no profile build with track_pose";
-  return with_actor ? actor_limit(b->m, nullptr, b->ref_frames, true) : nullptr;
-}
 extern "C" int rr_batch_pose_termination_supported(const rr_batch* b, int32_t with_actor) {
   if (!b) return fail(RR_EINVAL, "rr_batch_pose_termination_supported: null batch");
-  const char* why = pterm_limit(b, with_actor != 0);
-  if (why) (void)fail(RR_EUNSUPPORTED, std::string("rr_batch_pose_termination_supported: ") + why);
-  return why ? 0 : 1;
+  return supported("rr_batch_pose_termination_supported", pose_option_limit(b, F_STEP, b->ref_frames, with_actor != 0));
 }
 extern "C" int rr_batch_set_pose_termination(rr_batch* b, const rr_pose_term_io* t) {
   if (!b) return fail(RR_EINVAL, "rr_batch_set_pose_termination: null batch");
   if (!t) { b->pterm = rr_pose_term_io{}; return RR_OK; }
-  if (const char* why = pterm_limit(b, false)) return fail(RR_EUNSUPPORTED, std::string("rr_batch_set_pose_termination: ") + why);
+  if (const char* why = pose_option_limit(b, F_STEP, b->ref_frames, false)) return fail(RR_EUNSUPPORTED, std::string("rr_batch_set_pose_termination: ") + why);
   if (!b->pose.track_pose) return fail(RR_EINVAL, "rr_batch_set_pose_termination: needs a pose block (rr_batch_set_pose) first: the errors are taken against track_pose's rows");
   if (!t->fail) return fail(RR_EINVAL, "rr_batch_set_pose_termination: null fail array");
   for (float x : {t->max_pos, t->max_quat, t->max_joint})
@@ -1514,25 +1517,14 @@ extern "C" int rr_batch_set_pose_termination(rr_batch* b, const rr_pose_term_io*
   b->pterm = *t;
   return RR_OK;
 }
-// Body tracking: wherever pose tracking is served, at the batch's frame count; with_actor also asks the width the actor of the
-// reference-observation instances reads
-static const char* body_limit(const rr_batch* b, bool with_actor) {
-  const Instance in = select(b->m, with_actor ? F_ACTOR : F_STEP, V_BODY);
-  if (!in.kern) return in.why;
-  if (b->has_env_params()) return "pose tracking: no pose instance reads per-env parameters (this batch carries some)";
-  if (b->prof) return "pose tracking: no profile build with track_pose";
-  return with_actor ? actor_limit(b->m, nullptr, b->ref_frames, true) : nullptr;
-}
 extern "C" int rr_batch_body_tracking_supported(const rr_batch* b, int32_t with_actor) {
   if (!b) return fail(RR_EINVAL, "rr_batch_body_tracking_supported: null batch");
-  const char* why = body_limit(b, with_actor != 0);
-  if (why) (void)fail(RR_EUNSUPPORTED, std::string("rr_batch_body_tracking_supported: ") + why);
-  return why ? 0 : 1;
+  return supported("rr_batch_body_tracking_supported", pose_option_limit(b, F_STEP, b->ref_frames, with_actor != 0));
 }
 extern "C" int rr_batch_set_body_tracking(rr_batch* b, const rr_body_io* t) {
   if (!b) return fail(RR_EINVAL, "rr_batch_set_body_tracking: null batch");
   if (!t) { b->body = rr_body_io{}; return RR_OK; }
-  if (const char* why = body_limit(b, false)) return fail(RR_EUNSUPPORTED, std::string("rr_batch_set_body_tracking: ") + why);
+  if (const char* why = pose_option_limit(b, F_STEP, b->ref_frames, false)) return fail(RR_EUNSUPPORTED, std::string("rr_batch_set_body_tracking: ") + why);
   if (!b->pose.track_pose) return fail(RR_EINVAL, "rr_batch_set_body_tracking: needs a pose block (rr_batch_set_pose) first: track_bodies is indexed like track_pose");
   if (!t->track_bodies || !t->body_weights || !t->body_metrics) return fail(RR_EINVAL, "rr_batch_set_body_tracking: null track_bodies, body_weights or body_metrics");
   for (float x : {t->body_reward_weight, t->body_reward_scale, t->endeff_reward_weight, t->endeff_reward_scale})
@@ -1540,25 +1532,14 @@ extern "C" int rr_batch_set_body_tracking(rr_batch* b, const rr_body_io* t) {
   b->body = *t;
   return RR_OK;
 }
-// Clip restarts: wherever pose tracking is served in the multi-step forms, at the batch's frame count; with_actor also asks the width the
-// actor of the reference-observation instances reads
-static const char* restart_limit(const rr_batch* b, bool with_actor) {
-  const Instance in = select(b->m, with_actor ? F_ACTOR : F_UNROLL, V_RESTART);
-  if (!in.kern) return in.why;
-  if (b->has_env_params()) return "pose tracking: no pose instance reads per-env parameters (this batch carries some)";
-  if (b->prof) return "pose tracking: no profile build with track_pose";
-  return with_actor ? actor_limit(b->m, nullptr, b->ref_frames, true) : nullptr;
-}
 extern "C" int rr_batch_clip_restarts_supported(const rr_batch* b, int32_t with_actor) {
   if (!b) return fail(RR_EINVAL, "rr_batch_clip_restarts_supported: null batch");
-  const char* why = restart_limit(b, with_actor != 0);
-  if (why) (void)fail(RR_EUNSUPPORTED, std::string("rr_batch_clip_restarts_supported: ") + why);
-  return why ? 0 : 1;
+  return supported("rr_batch_clip_restarts_supported", pose_option_limit(b, F_UNROLL, b->ref_frames, with_actor != 0));
 }
 extern "C" int rr_batch_set_clip_restarts(rr_batch* b, const rr_clip_restart_io* r) {
   if (!b) return fail(RR_EINVAL, "rr_batch_set_clip_restarts: null batch");
   if (!r) { b->restart = rr_clip_restart_io{}; return RR_OK; }
-  if (const char* why = restart_limit(b, false)) return fail(RR_EUNSUPPORTED, std::string("rr_batch_set_clip_restarts: ") + why);
+  if (const char* why = pose_option_limit(b, F_UNROLL, b->ref_frames, false)) return fail(RR_EUNSUPPORTED, std::string("rr_batch_set_clip_restarts: ") + why);
   if (!b->pose.track_pose) return fail(RR_EINVAL, "rr_batch_set_clip_restarts: needs a pose block (rr_batch_set_pose) first: clip restarts serve pose envs only");
   if (!r->frames || !r->slot_in || !r->slot_out) return fail(RR_EINVAL, "rr_batch_set_clip_restarts: null frames, slot_in or slot_out");
   if (r->num_slots < 1 || r->num_slots > 64) return fail(RR_EINVAL, "rr_batch_set_clip_restarts: num_slots must lie in 1 .. 64");

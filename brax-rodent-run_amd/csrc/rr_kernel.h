@@ -276,7 +276,7 @@ struct RRIO {
   const float* track_pose;
   float* pose_metrics;         // [N][2]
   float pose_quat_w, pose_quat_k, pose_joint_w, pose_joint_k;
-  // REFERENCE OBSERVATION (REFOBS instances, rr_refobs_kernel; no other instance reads it): the observation row carries the clip's next
+  // REFERENCE OBSERVATION (REFOBS instances, rr_poseterm_kernel, rr_body_kernel and rr_restart_kernel; no other instance reads it): the observation row carries the clip's next
   // ref_frames = H >= 1 frames behind today's obs_dim entries, [ obs (obs_dim) | block_1 | ... | block_H ], row width obs_dim + H nq --
   // the stride of obs, t_obs, a_obs_in and first_obs in those instances (rr_obs_width).  block_h = (p_h[3], q_h[4], j_h[nq - 7]) at frame
   // f_h = clamp(new_frame + h, 0, track_len - 1) of the env's clip, new_frame the frame the track entry of the observation counts from:
@@ -287,7 +287,7 @@ struct RRIO {
   // Fetched by a narrow load where it is used (load_io_member), never through load_io().
   int ref_frames;
   int ref_pad;                 // keeps sizeof(RRIO) a multiple of 8 (RRKArgs)
-  // POSE TERMINATION (PTERM instances, rr_poseterm_kernel; no other instance reads it): an env step whose stepped qpos strays from the
+  // POSE TERMINATION (PTERM instances, rr_poseterm_kernel, rr_body_kernel and rr_restart_kernel; no other instance reads it): an env step whose stepped qpos strays from the
   // clip's row at (clip[env], old_frame) -- the row the position and pose rewards read -- ends the episode.  Lane 0 forms
   //   e_pos = |qpos[:3] - track_pos[f]|, e_quat = theta of POSE TRACKING, e_joint = sqrt(sum (qpos[7+i] - r_j,i)^2),
   //   code = 1 (e_pos > pose_max_pos) | 2 (e_quat > pose_max_quat) | 4 (e_joint > pose_max_joint)      (+inf: off; a NaN error: no bit)
@@ -296,7 +296,7 @@ struct RRIO {
   float* pose_fail;            // [N]
   float pose_max_pos, pose_max_quat, pose_max_joint;
   int pterm_pad;               // keeps sizeof(RRIO) a multiple of 8 (RRKArgs)
-  // BODY TRACKING (BODY instances, rr_body_kernel; no other instance reads these): the clip's global body positions next to its pose.
+  // BODY TRACKING (BODY instances, rr_body_kernel and rr_restart_kernel; no other instance reads these): the clip's global body positions next to its pose.
   // track_bodies is [T][nbody][3] (with `clip` set [num_clips][T][nbody][3]), indexed by the clip and frame the position and pose rewards
   // read; body_weights is [2][nbody], row 0 the 0 / 1 mask of the tracked bodies B, row 1 that of the end effectors E (entry 0, the
   // world, is not read).  With xpos the body positions of the step's LAST FORWARD PASS (the pose before the last substep's integration,
@@ -2694,7 +2694,7 @@ static __device__ __forceinline__ T load_io_member(size_t member_offset) {
 #endif
 }
 
-// Width of an observation row = the stride of obs, t_obs, a_obs_in and first_obs.  REFOBS instances (rr_refobs_kernel): the model's obs_dim
+// Width of an observation row = the stride of obs, t_obs, a_obs_in and first_obs.  REFOBS instances (rr_poseterm_kernel, rr_body_kernel, rr_restart_kernel): the model's obs_dim
 // plus RRIO::ref_frames blocks of nq entries, the count read where the width is used; every other instance: D.obs_dim itself.
 template <bool REFOBS, class DT>
 static __device__ __forceinline__ int rr_obs_width(const DT& D) {
@@ -2880,23 +2880,11 @@ __global__ __launch_bounds__(RR_LANES, 2) void rr_pose_kernel(const RRDims Dk, c
   constexpr bool ROOTSLOT = rr_root_slot<DT>::value;
 #include "rr_step_body.inc"
 }
-// Reference observation (rr_batch_set_reference_obs): the pose instances with the clip's next frames appended to every observation row
-// (RRIO, REFERENCE OBSERVATION), served to env steps AND resets of a batch that carries frames.  A fifth entry for the reason the three
-// above are entries of their own: the instances of the others keep their code, every `if (REFOBS)` in the body folds away there and
-// rr_obs_width is D.obs_dim.  The same nine forms as rr_pose_kernel; the actor inside reads RR_ACTOR_JM_REFOBS entries per lane.
-template <class DT, bool UNROLL = false, bool ACTOR = false>
-__global__ __launch_bounds__(RR_LANES, 2) void rr_refobs_kernel(const RRDims Dk, const RRTables Tk, const RRIO io_kernarg, const int num_envs, const int n_frames) {
-  constexpr int NBS = 2, NVS = 2, NCS = 1;
-  constexpr bool PROF = false, DBG = false, NEWTON = false, PAIR = false, DYN = false, RAND = false, EVAL = false, POSE = true, REFOBS = true, PTERM = false, BODY = false, RESTART = false;
-  constexpr int MRES = 1;      // resident inverse-factor entries (Wave::MAT_RES): the column side, as in rr_pose_kernel
-  constexpr bool ROOTSLOT = rr_root_slot<DT>::value;
-#include "rr_step_body.inc"
-}
-// Pose termination (rr_batch_set_pose_termination): the reference-observation instances with the env step's done raised where the stepped
-// pose strays from the clip (RRIO, POSE TERMINATION), served to the env steps of a batch that carries the block; resets stay on the
-// instance they use without it.  A sixth entry for the reason the others are entries of their own: every `if (PTERM)` in the body folds
-// away in their instances.  REFOBS is on, so the row is rr_obs_width wide and ref_frames = 0 is the same code with zero blocks; the actor
-// inside reads RR_ACTOR_JM_REFOBS entries per lane whatever the frame count.  The same nine forms as rr_pose_kernel.
+// Pose termination (rr_batch_set_pose_termination) without body tracking: the env steps of a batch that carries a termination block and
+// no body block, at any frame count -- rr_body_kernel below with BODY off.  REFOBS is on, so ref_frames = 0 is the same code with zero
+// blocks and the actor inside reads RR_ACTOR_JM_REFOBS entries per lane.  rr_body_kernel computes the same bits for these launches
+// (tests/test_gpu_pose_family.py); the entry is kept for the one-launch rollout with the actor inside, which ran 0.27 % slower on
+// rr_body_kernel in six of six pairs.  The same nine forms as rr_pose_kernel.
 template <class DT, bool UNROLL = false, bool ACTOR = false>
 __global__ __launch_bounds__(RR_LANES, 2) void rr_poseterm_kernel(const RRDims Dk, const RRTables Tk, const RRIO io_kernarg, const int num_envs, const int n_frames) {
   constexpr int NBS = 2, NVS = 2, NCS = 1;
@@ -2905,12 +2893,16 @@ __global__ __launch_bounds__(RR_LANES, 2) void rr_poseterm_kernel(const RRDims D
   constexpr bool ROOTSLOT = rr_root_slot<DT>::value;
 #include "rr_step_body.inc"
 }
-// Body tracking (rr_batch_set_body_tracking): the pose-termination instances with the reward's body-position and end-effector terms
-// (RRIO, BODY TRACKING), served to the env steps of a batch that carries the block; resets stay on the instance they use without it.  An
-// entry of its own for the reason the others are: every `if (BODY)` in the body folds away in their instances.  POSE, REFOBS and PTERM
-// are on -- a superset instance: ref_frames = 0 is that code with zero blocks, and a batch without a termination block hands +inf
-// thresholds and a null pose_fail, which the PTERM code takes.  The same nine forms as rr_pose_kernel; the actor inside reads
-// RR_ACTOR_JM_REFOBS entries per lane whatever the frame count.
+// The options of pose tracking -- reference frames (rr_batch_set_reference_obs; RRIO, REFERENCE OBSERVATION), pose termination
+// (rr_batch_set_pose_termination; POSE TERMINATION) and body tracking (rr_batch_set_body_tracking; BODY TRACKING) -- in ONE set of
+// instances: POSE, REFOBS, PTERM and BODY are all on, and this entry serves every combination of the three on a batch.  What a batch
+// does not carry reaches the kernel switched off at run time: ref_frames = 0 is the same code with zero blocks (the row is rr_obs_width =
+// obs_dim wide), no termination block is +inf thresholds and a null pose_fail, no body block a null track_bodies.  Env steps of a batch
+// with any of the three run it; the single-step form also serves the RESETS of a batch with ref_frames > 0 (they write the blocks; the
+// step-only code is not reached at reset).  A batch with the pose block alone stays on rr_pose_kernel, whose actor reads the narrower
+// row.  An entry of its own for the reason the others are: every `if (REFOBS)`, `if (PTERM)` and `if (BODY)` in the body folds away in
+// their instances.  The same nine forms as rr_pose_kernel; the actor inside reads RR_ACTOR_JM_REFOBS entries per lane whatever the frame
+// count.
 template <class DT, bool UNROLL = false, bool ACTOR = false>
 __global__ __launch_bounds__(RR_LANES, 2) void rr_body_kernel(const RRDims Dk, const RRTables Tk, const RRIO io_kernarg, const int num_envs, const int n_frames) {
   constexpr int NBS = 2, NVS = 2, NCS = 1;
@@ -2919,7 +2911,7 @@ __global__ __launch_bounds__(RR_LANES, 2) void rr_body_kernel(const RRDims Dk, c
   constexpr bool ROOTSLOT = rr_root_slot<DT>::value;
 #include "rr_step_body.inc"
 }
-// Clip restarts (rr_batch_set_clip_restarts): the multi-step body-tracking instances with the AutoReset restore drawn from a bank of start
+// Clip restarts (rr_batch_set_clip_restarts): the multi-step rr_body_kernel instances with the AutoReset restore drawn from a bank of start
 // states, the restored frame and the clip-end truncation (RRIO, CLIP RESTARTS), served to the multi-step launches of a batch that carries
 // the block.  An entry of its own for the reason the others are: every `if (RESTART)` in the body folds away in their instances.  POSE,
 // REFOBS, PTERM and BODY are on -- a superset instance: ref_frames = 0 is that code with zero blocks, no termination block is +inf

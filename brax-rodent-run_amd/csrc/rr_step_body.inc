@@ -1,5 +1,5 @@
 // rr_step_body.inc -- the body of the step kernel, included by each of its __global__ entries in rr_kernel.h (rr_step_kernel,
-// rr_rand_kernel, rr_eval_kernel, rr_pose_kernel, rr_refobs_kernel, rr_poseterm_kernel, rr_body_kernel, rr_restart_kernel, rr_matlds_kernel, rr_twoslot_kernel).  In scope where it is included: the kernel's five arguments (Dk, Tk, io_kernarg, num_envs, n_frames) and the
+// rr_rand_kernel, rr_eval_kernel, rr_pose_kernel, rr_poseterm_kernel, rr_body_kernel, rr_restart_kernel, rr_matlds_kernel, rr_twoslot_kernel).  In scope where it is included: the kernel's five arguments (Dk, Tk, io_kernarg, num_envs, n_frames) and the
 // compile-time switches NBS, NVS, NCS, PROF, DBG, DT, NEWTON, UNROLL, ACTOR, PAIR, DYN, RAND, EVAL, POSE, REFOBS, PTERM, BODY, RESTART, MRES, ROOTSLOT.
 // Why text and not a function: see the note above rr_step_kernel.
   static_assert(!PAIR || (!PROF && !DBG && !NEWTON && !UNROLL && !ACTOR), "PAIR: production physics instance only");

@@ -601,32 +601,30 @@ class Batch:
         _check(lib().rr_batch_set_clip_restarts(self.h, C.byref(t)))
         self._restart = (frames, slot_in, slot_out)
 
+    def _refusal(self, query, *args) -> Optional[str]:
+        """None when the `rr_batch_*_supported` function `query` answers 1 for this batch, else the text it left in `rr_last_error`."""
+        if _check(query(self.h, *args)) == 1:
+            return None
+        return lib().rr_last_error().decode()
+
     def clip_restarts_supported(self, with_actor: bool = False) -> Optional[str]:
         """None when this batch's multi-step launches serve clip restarts at its frame count (C ABI `rr_batch_clip_restarts_supported`)
         -- with `with_actor` the one-launch rollout with the actor inside -- else the refusal's text."""
-        if _check(lib().rr_batch_clip_restarts_supported(self.h, int(with_actor))) == 1:
-            return None
-        return lib().rr_last_error().decode()
+        return self._refusal(lib().rr_batch_clip_restarts_supported, int(with_actor))
 
     def body_tracking_supported(self, with_actor: bool = False) -> Optional[str]:
         """None when this batch serves body tracking at its frame count (C ABI `rr_batch_body_tracking_supported`) -- with
         `with_actor` also in the one-launch rollout with the actor inside -- else the refusal's text."""
-        if _check(lib().rr_batch_body_tracking_supported(self.h, int(with_actor))) == 1:
-            return None
-        return lib().rr_last_error().decode()
+        return self._refusal(lib().rr_batch_body_tracking_supported, int(with_actor))
 
     def pose_termination_supported(self, with_actor: bool = False) -> Optional[str]:
         """None when this batch serves pose termination at its frame count (C ABI `rr_batch_pose_termination_supported`) -- with
         `with_actor` also in the one-launch rollout with the actor inside -- else the refusal's text."""
-        if _check(lib().rr_batch_pose_termination_supported(self.h, int(with_actor))) == 1:
-            return None
-        return lib().rr_last_error().decode()
+        return self._refusal(lib().rr_batch_pose_termination_supported, int(with_actor))
 
     def pose_supported(self) -> Optional[str]:
         """None when this batch serves pose tracking (`set_pose`; C ABI `rr_batch_pose_supported`), else the refusal's text."""
-        if _check(lib().rr_batch_pose_supported(self.h)) == 1:
-            return None
-        return lib().rr_last_error().decode()
+        return self._refusal(lib().rr_batch_pose_supported)
 
     def set_reference_obs(self, frames: int):
         """`frames` = H reference frames behind every observation row of this batch (C ABI `rr_batch_set_reference_obs`): 0 .. 16, more
@@ -640,9 +638,7 @@ class Batch:
     def reference_obs_supported(self, frames: int, with_actor: bool = False) -> Optional[str]:
         """None when this batch serves `frames` reference frames (C ABI `rr_batch_reference_obs_supported`) -- with `with_actor` also in
         the one-launch rollout with the actor inside, whose actor reads a bounded row width -- else the refusal's text."""
-        if _check(lib().rr_batch_reference_obs_supported(self.h, int(frames), int(with_actor))) == 1:
-            return None
-        return lib().rr_last_error().decode()
+        return self._refusal(lib().rr_batch_reference_obs_supported, int(frames), int(with_actor))
 
     def env_params_supported(self) -> bool:
         """Whether this batch's model / solver has kernel instances with per-env parameters (C ABI `rr_batch_env_params_supported`)."""

@@ -1,4 +1,4 @@
-"""The reference observation on the GPU (`Rodent(reference_obs_frames=H)`; rr_batch_set_reference_obs, the rr_refobs_kernel instances):
+"""The reference observation on the GPU (`Rodent(reference_obs_frames=H)`; rr_batch_set_reference_obs, the rr_body_kernel instances):
 every observation row carries the clip's next H frames behind the model's obs_dim entries.  Held against a pose env with H = 0 of the same
 build -- bit for bit in everything but the new columns -- and against the float64 restatement `rodent.reference_obs`.
 

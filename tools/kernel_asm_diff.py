@@ -1,7 +1,8 @@
 """Compare two device-only `-S` outputs of csrc/rr_api.hip kernel by kernel: did a source change move any instruction?
 
 Each file is `hipcc <build()'s flags> --cuda-device-only -S -o x.s csrc/rr_api.hip` of one tree.  Per kernel symbol the instruction
-lines are taken (comments, directives and labels dropped, branch targets reduced to the block number) and compared:
+lines are taken (comments, directives and labels dropped, branch targets reduced to the block number, the file-wide counter of the
+long branches' `.Lpost_getpc<n>` labels dropped) and compared:
   identical            the same instructions in the same order
   reordered            the same multiset of instructions in another order
   reordered, renamed   the same multiset of opcodes: another order and another register assignment
@@ -24,7 +25,9 @@ def kernels(path):
         for line in m.group(2).split("\n"):
             line = line.split(";")[0].strip()
             if line and not line.startswith(".") and not line.endswith(":"):
-                ins.append(re.sub(r"\.LBB\d+_", ".LBB_", re.sub(r"\s+", " ", line)))
+                # labels numbered over the whole file, not per kernel: the function number in .LBB<f>_<block>, and the count of long
+                # branches in .Lpost_getpc<n> -- both move when a kernel before this one is added or removed
+                ins.append(re.sub(r"\.Lpost_getpc\d+", ".Lpost_getpc", re.sub(r"\.LBB\d+_", ".LBB_", re.sub(r"\s+", " ", line))))
         out[m.group(1)] = [ins, {}]
     for m in re.finditer(r"^  - \.agpr_count:.*?(?=^  - \.agpr_count:|^amdhsa\.target)", text, re.M | re.S):      # one metadata entry per kernel
         f = lambda k: int(re.search(r"^\s+\.%s:\s+(\d+)" % k, m.group(0), re.M).group(1))
