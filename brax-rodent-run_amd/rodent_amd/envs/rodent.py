@@ -7,10 +7,11 @@ substeps + reward / done / observation epilogue (C ABI `rr_env_step`).
 """
 from __future__ import annotations
 
+import inspect
 import math
 import os
 import warnings
-from typing import Optional
+from typing import Callable, NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -354,6 +355,26 @@ def _check_body_tracking(track: np.ndarray, track_bodies, body_ids, end_effector
     return np.ascontiguousarray(bodies, dtype=np.float32), masks, sets[0], sets[1]
 
 
+class _StepOption(NamedTuple):
+    """One option of the env step as `Rodent` hands it to its batch and reads it back: the output buffer a step launch gets under the
+    env-io key `key` (float32 [N] + `shape`), the `static` env-io entries that go with it (the option's tensors and scalar tuples), the
+    `metrics` it adds to `State.metrics`, and `read`: buffer -> those metrics, in that order."""
+    key: str
+    shape: tuple
+    static: dict
+    metrics: tuple
+    read: Callable
+
+
+_columns = lambda buf: (buf[:, 0], buf[:, 1])      # the two columns of an [N, 2] metrics buffer, as views
+
+
+def _code_bits(buf):
+    """The pose-termination code of the (last) step, 0 .. 7 as a float [N], split: (any, bit 0, bit 1, bit 2) as floats 0 / 1."""
+    code = buf.to(torch.int32)
+    return (code != 0).float(), (code & 1).float(), ((code >> 1) & 1).float(), ((code >> 2) & 1).float()
+
+
 class Rodent(PipelineEnv):
 
     def __init__(
@@ -478,6 +499,7 @@ class Rodent(PipelineEnv):
         The clip's end (`end_at_clip_end=True`, needs K >= 1) is a truncation like `episode_length`, so the value bootstraps; the step
         that ends the episode is untouched.  K = 1 restores the frame with the state.  The bare `step` and the raw evaluation rollout have
         no wrappers and do not change."""
+        given = locals()                  # the arguments as they came (first statement: nothing else is a local yet): `_ctor` below
         if bad_state_max is not None:
             with np.errstate(over="ignore", under="ignore"):
                 thr32 = np.float32(bad_state_max)        # what the kernel gets: 1e-50 would arrive as 0 (= off), 1e39 as inf
@@ -515,40 +537,45 @@ class Rodent(PipelineEnv):
         self._quat_reward = (float(quat_reward_weight), float(quat_reward_scale))
         self._joint_reward = (float(joint_reward_weight), float(joint_reward_scale))
         self._reset_to_reference = bool(reset_to_reference)
-        if pose_np is not None:
-            why = self._batch.pose_supported()
-            if why is not None:
-                raise RuntimeError(f"Rodent(track_quat=..., track_joints=...): {why}")
         self._ref_frames = ref_frames
-        if ref_frames:
+        self._pose_term = pose_term       # None: no pose termination (no such members anywhere, the launches run the instances they ran)
+        self._clip_restarts, self._restart_frame_range, self._end_at_clip_end = restarts
+        batch = self._batch
+
+        def reference_frames_supported():
             # the batch carries the count; its rows come from the pose block, which therefore stands from here on (every launch of this
             # env, resets included, hands the block: a reset writes no pose metrics and gets a buffer nobody reads)
-            why = self._batch.reference_obs_supported(ref_frames)
+            why = batch.reference_obs_supported(ref_frames)
+            if why is None:
+                self._reset_pose_metrics = torch.zeros(num_envs, 2, device=self.device)
+                batch.set_pose(self._track_pose, self._reset_pose_metrics, self._quat_reward, self._joint_reward)
+                batch.set_reference_obs(ref_frames)
+            return why
+        probes = ((pose_np is not None, "track_quat=..., track_joints=...", batch.pose_supported),
+                  (ref_frames > 0, f"reference_obs_frames={ref_frames}", reference_frames_supported),
+                  (pose_term is not None, "max_pos_error / max_quat_error / max_joint_error", batch.pose_termination_supported),
+                  (body_np is not None, "track_bodies=...", batch.body_tracking_supported),
+                  (self._clip_restarts > 0, f"clip_restarts={self._clip_restarts}", batch.clip_restarts_supported))
+        for wanted, label, query in probes:       # a model, solver or frame count without the option's instance: the library's reason
+            why = query() if wanted else None
             if why is not None:
-                raise RuntimeError(f"Rodent(reference_obs_frames={ref_frames}): {why}")
-            self._reset_pose_metrics = torch.zeros(num_envs, 2, device=self.device)
-            self._batch.set_pose(self._track_pose, self._reset_pose_metrics, self._quat_reward, self._joint_reward)
-            self._batch.set_reference_obs(ref_frames)
-        self._pose_term = pose_term       # None: no pose termination (no such members anywhere, the launches run the instances they ran)
-        if pose_term is not None:
-            why = self._batch.pose_termination_supported()
-            if why is not None:
-                raise RuntimeError(f"Rodent(max_pos_error / max_quat_error / max_joint_error): {why}")
+                raise RuntimeError(f"Rodent({label}): {why}")
         self._body = None                 # None: no body tracking (no such members anywhere, the launches run the instances they ran)
         if body_np is not None:
-            why = self._batch.body_tracking_supported()
-            if why is not None:
-                raise RuntimeError(f"Rodent(track_bodies=...): {why}")
             rows, masks, B, E = body_np
             # an empty set gives its term weight 0 here, so the term is 0 whatever its (empty) sum
             self._body = dict(track_bodies=torch.from_numpy(rows).to(self.device).contiguous(), body_weights=torch.from_numpy(masks).to(self.device).contiguous(),
                               body_reward=(float(body_reward_weight) if B else 0.0, float(body_reward_scale)),
                               endeff_reward=(float(endeff_reward_weight) if E else 0.0, float(endeff_reward_scale)), body_ids=B, end_effector_ids=E)
-        self._clip_restarts, self._restart_frame_range, self._end_at_clip_end = restarts
-        if self._clip_restarts:
-            why = self._batch.clip_restarts_supported()
-            if why is not None:
-                raise RuntimeError(f"Rodent(clip_restarts={self._clip_restarts}): {why}")
+        # the step options in force, in the order their metrics follow the three old ones; a reset hands none of them (it has no reward
+        # and no done to raise) -- but see `_env_io` for an env with reference frames
+        self._options = tuple(o for o in (
+            pose_np is not None and _StepOption("pose_metrics", (2,), dict(track_pose=self._track_pose, quat_reward=self._quat_reward, joint_reward=self._joint_reward),
+                                                ("quat_reward", "joint_reward"), _columns),
+            pose_term is not None and _StepOption("pose_fail", (), dict(pose_termination=pose_term),
+                                                  ("pose_fail", "pose_fail_pos", "pose_fail_quat", "pose_fail_joint"), _code_bits),
+            body_np is not None and _StepOption("body_metrics", (2,), {k: self._body[k] for k in ("track_bodies", "body_weights", "body_reward", "endeff_reward")},
+                                                ("body_reward", "endeff_reward"), _columns)) if o)
         self._forward_reward_weight = forward_reward_weight
         self._ctrl_cost_weight = ctrl_cost_weight
         self._healthy_reward = healthy_reward
@@ -557,21 +584,11 @@ class Rodent(PipelineEnv):
         self._reset_noise_scale = reset_noise_scale
         self._vision = vision
         self._bad_state_max = None if bad_state_max is None else float(bad_state_max)
-        self._ctor = dict(track_pos=track_pos, forward_reward_weight=forward_reward_weight, ctrl_cost_weight=ctrl_cost_weight,
-                          healthy_reward=healthy_reward, terminate_when_unhealthy=terminate_when_unhealthy,
-                          healthy_z_range=healthy_z_range, reset_noise_scale=reset_noise_scale, solver=solver,
-                          iterations=iterations, ls_iterations=ls_iterations, vision=vision, xml_path=xml_path,
-                          n_frames=kwargs["n_frames"], pipeline_outputs=kwargs.get("pipeline_outputs", False),
+        # what `with_num_envs` rebuilds a sibling from: every parameter of this constructor as it was given, and the keywords PipelineEnv takes
+        self._ctor = {name: given[name] for name in _CTOR_PARAMS}
+        self._ctor.update(n_frames=kwargs["n_frames"], pipeline_outputs=kwargs.get("pipeline_outputs", False),
                           contact_outputs=kwargs.get("contact_outputs", False), balance=kwargs.get("balance"),
-                          rebalance_every=kwargs.get("rebalance_every", 4), bad_state_max=bad_state_max,
-                          track_quat=track_quat, track_joints=track_joints, quat_reward_weight=quat_reward_weight,
-                          quat_reward_scale=quat_reward_scale, joint_reward_weight=joint_reward_weight,
-                          joint_reward_scale=joint_reward_scale, reset_to_reference=reset_to_reference,
-                          reference_obs_frames=reference_obs_frames, max_pos_error=max_pos_error, max_quat_error=max_quat_error,
-                          max_joint_error=max_joint_error, track_bodies=track_bodies, body_ids=body_ids, end_effector_ids=end_effector_ids,
-                          body_reward_weight=body_reward_weight, body_reward_scale=body_reward_scale,
-                          endeff_reward_weight=endeff_reward_weight, endeff_reward_scale=endeff_reward_scale,
-                          clip_restarts=clip_restarts, restart_frame_range=restart_frame_range, end_at_clip_end=end_at_clip_end)
+                          rebalance_every=kwargs.get("rebalance_every", 4))
 
     def with_num_envs(self, num_envs: int, device=None):
         """A sibling env with another batch size (ppo.train builds its per-rank and eval envs this way)."""
@@ -656,21 +673,20 @@ class Rodent(PipelineEnv):
             raise RuntimeError("pose tracking: no pose instance reads per-env parameters (randomize / set_env_params on a pose env)")
         return super().randomize(randomization_fn)
 
-    def _env_io(self, cur_frame, obs, reward=None, done=None, metrics=None, clip=None, pose_metrics=None, pose_fail=None, body_metrics=None, restart=None):
+    def _env_io(self, cur_frame, obs, reward=None, done=None, metrics=None, clip=None, restart=None, **buffers):
+        """The env-io dict of a launch.  `buffers`: the step options' output buffers by env-io key (`_launch_buffers`); each brings its
+        option's static entries along.  `restart`: the clip-restart block of a multi-step launch (single steps and resets pass none)."""
         io = dict(track_pos=self._track_pos, cur_frame=cur_frame, obs=obs, reward=reward, done=done, metrics=metrics, clip=clip,
                   healthy_reward=self._healthy_reward, ctrl_cost_weight=self._ctrl_cost_weight,
                   healthy_z_range=self._healthy_z_range, terminate_when_unhealthy=self._terminate_when_unhealthy,
                   bad_state_max=self._bad_state_max)
-        if pose_metrics is None and self._ref_frames:      # a reset that writes the reference blocks: it reads the pose rows too
-            pose_metrics = self._reset_pose_metrics
-        if pose_metrics is not None:         # a step of a pose env (a reset passes none: it has no reward)
-            io.update(track_pose=self._track_pose, pose_metrics=pose_metrics, quat_reward=self._quat_reward, joint_reward=self._joint_reward)
-        if pose_fail is not None:            # a step of an env with pose termination (a reset passes none: it has no done to raise)
-            io.update(pose_fail=pose_fail, pose_termination=self._pose_term)
-        if body_metrics is not None:         # a step of an env with body tracking (a reset passes none: it has no reward)
-            io.update(track_bodies=self._body["track_bodies"], body_weights=self._body["body_weights"], body_metrics=body_metrics,
-                      body_reward=self._body["body_reward"], endeff_reward=self._body["endeff_reward"])
-        if restart is not None:              # a multi-step launch of an env with clip restarts (single steps and resets pass none)
+        if "pose_metrics" not in buffers and self._ref_frames:      # a reset that writes the reference blocks: it reads the pose rows too,
+            buffers["pose_metrics"] = self._reset_pose_metrics     # so it hands the pose block -- and nothing else of the options
+        for o in self._options:
+            if o.key in buffers:
+                io[o.key] = buffers[o.key]
+                io.update(o.static)
+        if restart is not None:
             io["restart"] = restart
         return io
 
@@ -716,12 +732,8 @@ class Rodent(PipelineEnv):
             info["restart_slot"] = torch.zeros(N, dtype=torch.int32, device=dev)
         zero = torch.zeros(N, device=dev)
         metrics = {"pos_reward": zero, "reward_quadctrl": zero.clone(), "reward_alive": zero.clone()}
-        if self.pose_tracking:
-            metrics.update(quat_reward=zero.clone(), joint_reward=zero.clone())
-        if self._pose_term is not None:
-            metrics.update({k: zero.clone() for k in ("pose_fail", "pose_fail_pos", "pose_fail_quat", "pose_fail_joint")})
-        if self._body is not None:
-            metrics.update(body_reward=zero.clone(), endeff_reward=zero.clone())
+        for o in self._options:
+            metrics.update({k: zero.clone() for k in o.metrics})
         return State(PipelineState(**st, **out), obs, zero.clone(), zero.clone(), metrics, info)
 
     def _launch_buffers(self, state: State, episode_length: Optional[float] = None):
@@ -735,23 +747,17 @@ class Rodent(PipelineEnv):
         st = {k: torch.empty_like(v) for k, v in st_in.items()}
         io = dict(cur_frame=torch.empty_like(info["cur_frame"]), reward=torch.empty(N, device=dev), done=torch.empty(N, device=dev),
                   metrics=torch.empty(N, 3, device=dev), clip=info.get("clip"))      # clip: read only (None without a clip axis)
-        if self.pose_tracking:
-            io["pose_metrics"] = torch.empty(N, 2, device=dev)
-        if self._pose_term is not None:
-            io["pose_fail"] = torch.empty(N, device=dev)
-        if self._body is not None:
-            io["body_metrics"] = torch.empty(N, 2, device=dev)
+        for o in self._options:
+            io[o.key] = torch.empty((N,) + o.shape, device=dev)
         wrap = None
-        if episode_length is not None and self._clip_restarts:      # the restores draw from the bank, and frame and slot travel with the state
-            bank = info["restart_bank"]
+        if episode_length is not None:
+            bank = info["restart_bank"] if self._clip_restarts else dict(pipeline_state=info["first_pipeline_state"], obs=info["first_obs"])
             wrap = dict(first=fields(bank["pipeline_state"]), first_obs=bank["obs"], prev_done=state.done, steps_in=info["steps"],
-                        steps_out=torch.empty(N, device=dev), truncation_out=torch.empty(N, device=dev), episode_length=episode_length,
-                        slots=self._clip_restarts)
-            io["restart"] = dict(frames=bank["frame"], slot_in=info["restart_slot"], slot_out=torch.empty_like(info["restart_slot"]),
-                                 end_at_clip_end=self._end_at_clip_end)
-        elif episode_length is not None:
-            wrap = dict(first=fields(info["first_pipeline_state"]), first_obs=info["first_obs"], prev_done=state.done, steps_in=info["steps"],
                         steps_out=torch.empty(N, device=dev), truncation_out=torch.empty(N, device=dev), episode_length=episode_length)
+            if self._clip_restarts:      # the restores draw from the bank, and frame and slot travel with the state
+                wrap["slots"] = self._clip_restarts
+                io["restart"] = dict(frames=bank["frame"], slot_in=info["restart_slot"], slot_out=torch.empty_like(info["restart_slot"]),
+                                     end_at_clip_end=self._end_at_clip_end)
         return st_in, st, io, wrap
 
     def _next_state(self, state: State, st, io, obs, wrap=None, out=None) -> State:
@@ -764,14 +770,8 @@ class Rodent(PipelineEnv):
                 info["restart_slot"] = io["restart"]["slot_out"]
         m = dict(state.metrics)
         m.update(pos_reward=io["metrics"][:, 0], reward_quadctrl=io["metrics"][:, 1], reward_alive=io["metrics"][:, 2])
-        if self.pose_tracking:
-            m.update(quat_reward=io["pose_metrics"][:, 0], joint_reward=io["pose_metrics"][:, 1])
-        if self._pose_term is not None:      # the code of the (last) step, 0 .. 7, split into its bits
-            code = io["pose_fail"].to(torch.int32)
-            m.update(pose_fail=(code != 0).float(), pose_fail_pos=(code & 1).float(), pose_fail_quat=((code >> 1) & 1).float(),
-                     pose_fail_joint=((code >> 2) & 1).float())
-        if self._body is not None:
-            m.update(body_reward=io["body_metrics"][:, 0], endeff_reward=io["body_metrics"][:, 1])
+        for o in self._options:
+            m.update(zip(o.metrics, o.read(io[o.key])))
         return state.replace(pipeline_state=PipelineState(**st, **(out or {})), obs=obs, reward=io["reward"], done=io["done"], metrics=m, info=info)
 
     def unroll_wrapped(self, state: State, actions: torch.Tensor, episode_length: float) -> State:
@@ -811,6 +811,18 @@ class Rodent(PipelineEnv):
         evaluation runs the per-step loop, whose `EvalWrapper` sums the two pose metrics like the others."""
         return (not self.pose_tracking and self.device.type == "cuda" and not self._pipeline_outputs and not self._contact_outputs and self._batch.eval_supported())
 
+    def fused_actor_refusal(self) -> Optional[str]:
+        """None when the in-kernel actor of the instance this env's multi-step launches run reads the env's row width, else the
+        library's text.  The launches run the instance of the highest option in force -- clip restarts, then body tracking, then pose
+        termination, then the pose instance at the env's reference frames (0 without) -- so that one is asked."""
+        if self._clip_restarts:
+            return self._batch.clip_restarts_supported(with_actor=True)
+        if self._body is not None:
+            return self._batch.body_tracking_supported(with_actor=True)
+        if self._pose_term is not None:
+            return self._batch.pose_termination_supported(with_actor=True)
+        return self._batch.reference_obs_supported(self._ref_frames, with_actor=True)
+
     def unroll_eval(self, state: State, T: int, actor: dict, noise: Optional[torch.Tensor] = None, episode_length: Optional[float] = None,
                     eval_metrics: Optional[torch.Tensor] = None, actions_out: Optional[torch.Tensor] = None, qpos_out: Optional[torch.Tensor] = None) -> State:
         """T x [policy(obs) -> action -> step] in ONE launch without a trajectory (`rr_env_unroll_eval`): what an evaluation needs.
@@ -840,3 +852,6 @@ class Rodent(PipelineEnv):
         self._rebalance()
         self._batch.env_step_to(st_in, st, action, self._n_frames, self._env_io(obs=obs, **io), state.info["cur_frame"], out)
         return self._next_state(state, st, io, obs, out=out)
+
+
+_CTOR_PARAMS = tuple(p for p in inspect.signature(Rodent.__init__).parameters if p not in ("self", "num_envs", "device", "kwargs"))

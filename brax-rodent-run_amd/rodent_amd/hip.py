@@ -355,7 +355,7 @@ class Batch:
         return o
 
     def _env(self, env) -> RREnvIOClips:
-        d, N = self.dims, self.N
+        N = self.N
         tp = env["track_pos"]
         clip = env.get("clip")
         if (clip is not None) != (tp.dim() == 3):
@@ -376,33 +376,35 @@ class Batch:
         e.healthy_z_min, e.healthy_z_max = env.get("healthy_z_range", (0.03, 0.5))
         e.terminate_when_unhealthy = int(env.get("terminate_when_unhealthy", True))
         e.bad_state_max = float(env.get("bad_state_max") or 0.0)      # 0 = no bad-state check
-        # pose tracking rides on the batch, not in rr_env_io: the env-io dict decides what the launch about to be issued sees
-        fail = env.get("pose_fail")         # pose termination rides there too: the code array [N] and `pose_termination` = the three thresholds
-        if fail is None and self._pterm is not None:        # cleared BEFORE the pose block may go: the library keeps the pose block while it stands
-            self.set_pose_termination(None)
-        restart = env.get("restart")        # clip restarts likewise: dict(frames [K, N], slot_in [N], slot_out [N], end_at_clip_end), multi-step launches only
-        if restart is None and self._restart is not None:
-            self.set_clip_restarts(None)
-        bodies = env.get("track_bodies")    # body tracking likewise: [(C), T, nbody, 3] next to `body_weights` [2, nbody] and `body_metrics` [N, 2]
-        if bodies is None and self._body is not None:
-            self.set_body_tracking(None)
-        pose = env.get("track_pose")
-        if pose is not None:        # [T, nq - 3] rows (quaternion, joints), or [C, T, nq - 3] next to a [C, T, 3] track_pos
-            if tuple(pose.shape) != tuple(tp.shape[:-1]) + (d.nq - 3,):
-                raise ValueError(f"env io: track_pose has shape {tuple(pose.shape)}, expected {tuple(tp.shape[:-1]) + (d.nq - 3,)}")
-            self.set_pose(pose, env.get("pose_metrics"), env.get("quat_reward", (1.0, 2.0)), env.get("joint_reward", (1.0, 0.5)))
-        elif self._pose is not None:        # (refused while the batch carries reference frames: their launches all carry track_pose)
-            self.set_pose(None)
-        if fail is not None:
-            self.set_pose_termination(fail, env.get("pose_termination", (math.inf, math.inf, math.inf)))
-        if bodies is not None:
-            if tuple(bodies.shape) != tuple(tp.shape[:-1]) + (d.nbody, 3):
-                raise ValueError(f"env io: track_bodies has shape {tuple(bodies.shape)}, expected {tuple(tp.shape[:-1]) + (d.nbody, 3)}")
-            self.set_body_tracking(bodies, env.get("body_weights"), env.get("body_metrics"), env.get("body_reward", (1.0, 8.0)),
-                                   env.get("endeff_reward", (1.0, 100.0)))
-        if restart is not None:
-            self.set_clip_restarts(restart["frames"], restart["slot_in"], restart["slot_out"], restart.get("end_at_clip_end", False))
+        self._program_blocks(env)
         return e
+
+    def _program_blocks(self, env):
+        """The pose options ride on the batch, not in rr_env_io: the env-io dict decides what the launch about to be issued sees.  One row
+        per block -- the env-io key that decides its presence, the attribute that says whether it stands, its setter, the setter's
+        arguments out of the dict (the setters say what each entry is) -- in dependency order: termination, body tracking and clip
+        restarts each need the pose block, and the library keeps the pose block while one of them stands.  So the blocks absent from the
+        dict are cleared last to first, then the present ones are set first to last.  (Clearing the pose block is refused while the
+        batch carries reference frames: their launches all carry `track_pose`.)"""
+        lead, d, inf = tuple(env["track_pos"].shape[:-1]), self.dims, math.inf
+
+        def rows(key, tail):        # the clip's rows of a block: the same clips and frames as track_pos
+            if tuple(env[key].shape) != lead + tail:
+                raise ValueError(f"env io: {key} has shape {tuple(env[key].shape)}, expected {lead + tail}")
+            return env[key]
+        blocks = (("track_pose", "_pose", self.set_pose, lambda: (rows("track_pose", (d.nq - 3,)), env.get("pose_metrics"),
+                                                                 env.get("quat_reward", (1.0, 2.0)), env.get("joint_reward", (1.0, 0.5)))),
+                  ("pose_fail", "_pterm", self.set_pose_termination, lambda: (env["pose_fail"], env.get("pose_termination", (inf, inf, inf)))),
+                  ("track_bodies", "_body", self.set_body_tracking, lambda: (rows("track_bodies", (d.nbody, 3)), env.get("body_weights"), env.get("body_metrics"),
+                                                                             env.get("body_reward", (1.0, 8.0)), env.get("endeff_reward", (1.0, 100.0)))),
+                  ("restart", "_restart", self.set_clip_restarts, lambda: (env["restart"]["frames"], env["restart"]["slot_in"], env["restart"]["slot_out"],
+                                                                           env["restart"].get("end_at_clip_end", False))))
+        for key, attr, setter, _ in reversed(blocks):
+            if env.get(key) is None and getattr(self, attr) is not None:
+                setter(None)
+        for key, _, setter, args in blocks:
+            if env.get(key) is not None:
+                setter(*args())
 
     # ------------------------------------------------------------------ C-ABI calls
     def pipeline_init(self, st, out=None):
@@ -540,31 +542,27 @@ class Batch:
         self._sched = (env_map, cost)
         _check(lib().rr_batch_set_schedule(self.h, _ptr(env_map, torch.int32, self.N), _ptr(cost, torch.int32, self.N)))
 
+    def _set_block(self, attr: str, setter, block, tensors):
+        """The tail of the four block setters below: hand `block` (the block's struct; None clears it) to the library's `setter`, then
+        keep `tensors` alive in `attr` while the block stands, or drop them."""
+        _check(setter(self.h, None if block is None else C.byref(block)))
+        setattr(self, attr, None if block is None else tensors)
+
     def set_pose(self, track_pose: Optional[torch.Tensor], pose_metrics: Optional[torch.Tensor] = None, quat_reward=(1.0, 2.0), joint_reward=(1.0, 0.5)):
         """The pose-tracking block of this batch's later env steps (C ABI `rr_batch_set_pose`): `track_pose` [(C,) T, nq - 3] rows of
         quaternion then joints, `pose_metrics` [N, 2] out, `quat_reward` / `joint_reward` = (weight, scale); None clears it.  The env-io
         dict of a launch (`track_pose`, `pose_metrics`, `quat_reward`, `joint_reward` keys) sets or clears it by itself.  The batch keeps
         the tensors alive."""
-        if track_pose is None:
-            _check(lib().rr_batch_set_pose(self.h, None))
-            self._pose = None
-            return
-        p = RRPoseIO(_ptr(track_pose), _ptr(pose_metrics, numel=2 * self.N), *quat_reward, *joint_reward)
-        _check(lib().rr_batch_set_pose(self.h, C.byref(p)))
-        self._pose = (track_pose, pose_metrics)
+        p = None if track_pose is None else RRPoseIO(_ptr(track_pose), _ptr(pose_metrics, numel=2 * self.N), *quat_reward, *joint_reward)
+        self._set_block("_pose", lib().rr_batch_set_pose, p, (track_pose, pose_metrics))
 
     def set_pose_termination(self, fail: Optional[torch.Tensor], thresholds=(math.inf, math.inf, math.inf)):
         """The pose-termination block of this batch's later env steps (C ABI `rr_batch_set_pose_termination`): `fail` [N] out, the code
         of each env's step as a float 0 .. 7; `thresholds` = (max_pos, max_quat, max_joint), each > 0, inf = that criterion off; None
         clears it.  Needs the pose block (`set_pose`).  The env-io dict of a launch (`pose_fail`, `pose_termination` keys) sets or clears
         it by itself.  The batch keeps the tensor alive."""
-        if fail is None:
-            _check(lib().rr_batch_set_pose_termination(self.h, None))
-            self._pterm = None
-            return
-        t = RRPoseTermIO(_ptr(fail, numel=self.N), *(float(x) for x in thresholds), 0)
-        _check(lib().rr_batch_set_pose_termination(self.h, C.byref(t)))
-        self._pterm = fail
+        t = None if fail is None else RRPoseTermIO(_ptr(fail, numel=self.N), *(float(x) for x in thresholds), 0)
+        self._set_block("_pterm", lib().rr_batch_set_pose_termination, t, fail)
 
     def set_body_tracking(self, track_bodies: Optional[torch.Tensor], body_weights: Optional[torch.Tensor] = None,
                           body_metrics: Optional[torch.Tensor] = None, body_reward=(1.0, 8.0), endeff_reward=(1.0, 100.0)):
@@ -573,33 +571,26 @@ class Batch:
         `body_metrics` [N, 2] out (body_reward, endeff_reward); `body_reward` / `endeff_reward` = (weight, scale); None clears it.
         Needs the pose block (`set_pose`).  The env-io dict of a launch (`track_bodies`, `body_weights`, `body_metrics`, `body_reward`,
         `endeff_reward` keys) sets or clears it by itself.  The batch keeps the tensors alive."""
-        if track_bodies is None:
-            _check(lib().rr_batch_set_body_tracking(self.h, None))
-            self._body = None
-            return
-        nb = self.dims.nbody
-        if track_bodies.dim() < 3 or tuple(track_bodies.shape[-2:]) != (nb, 3):
-            raise ValueError(f"track_bodies has shape {tuple(track_bodies.shape)}, expected [(C), T, {nb}, 3]")
-        t = RRBodyIO(_ptr(track_bodies), _ptr(body_weights, numel=2 * nb), _ptr(body_metrics, numel=2 * self.N),
-                     float(body_reward[0]), float(body_reward[1]), float(endeff_reward[0]), float(endeff_reward[1]))
-        _check(lib().rr_batch_set_body_tracking(self.h, C.byref(t)))
-        self._body = (track_bodies, body_weights, body_metrics)
+        t, nb = None, self.dims.nbody
+        if track_bodies is not None:
+            if track_bodies.dim() < 3 or tuple(track_bodies.shape[-2:]) != (nb, 3):
+                raise ValueError(f"track_bodies has shape {tuple(track_bodies.shape)}, expected [(C), T, {nb}, 3]")
+            t = RRBodyIO(_ptr(track_bodies), _ptr(body_weights, numel=2 * nb), _ptr(body_metrics, numel=2 * self.N),
+                         float(body_reward[0]), float(body_reward[1]), float(endeff_reward[0]), float(endeff_reward[1]))
+        self._set_block("_body", lib().rr_batch_set_body_tracking, t, (track_bodies, body_weights, body_metrics))
 
     def set_clip_restarts(self, frames: Optional[torch.Tensor], slot_in: Optional[torch.Tensor] = None, slot_out: Optional[torch.Tensor] = None,
                           end_at_clip_end: bool = False):
         """The clip-restart block of this batch's later multi-step launches (C ABI `rr_batch_set_clip_restarts`): `frames` int32 [K, N]
         the start frame of each bank entry, `slot_in` / `slot_out` int32 [N]; None clears it.  Needs the pose block (`set_pose`).  The
         env-io dict of a launch (`restart` key) sets or clears it by itself.  The batch keeps the tensors alive."""
-        if frames is None:
-            _check(lib().rr_batch_set_clip_restarts(self.h, None))
-            self._restart = None
-            return
-        if frames.dim() != 2 or frames.shape[1] != self.N:
-            raise ValueError(f"clip restarts: frames has shape {tuple(frames.shape)}, expected [K, {self.N}]")
-        t = RRClipRestartIO(_ptr(frames, torch.int32), _ptr(slot_in, torch.int32, self.N), _ptr(slot_out, torch.int32, self.N),
-                            int(frames.shape[0]), int(bool(end_at_clip_end)))
-        _check(lib().rr_batch_set_clip_restarts(self.h, C.byref(t)))
-        self._restart = (frames, slot_in, slot_out)
+        t = None
+        if frames is not None:
+            if frames.dim() != 2 or frames.shape[1] != self.N:
+                raise ValueError(f"clip restarts: frames has shape {tuple(frames.shape)}, expected [K, {self.N}]")
+            t = RRClipRestartIO(_ptr(frames, torch.int32), _ptr(slot_in, torch.int32, self.N), _ptr(slot_out, torch.int32, self.N),
+                                int(frames.shape[0]), int(bool(end_at_clip_end)))
+        self._set_block("_restart", lib().rr_batch_set_clip_restarts, t, (frames, slot_in, slot_out))
 
     def _refusal(self, query, *args) -> Optional[str]:
         """None when the `rr_batch_*_supported` function `query` answers 1 for this batch, else the text it left in `rr_last_error`."""

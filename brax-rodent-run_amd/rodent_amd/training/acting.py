@@ -90,20 +90,14 @@ def actor_shape_supported(policy_net, action_size: int) -> bool:
 
 def fused_unroll_supported(wenv, policy_net, dist) -> bool:
     """The one-launch unroll needs the fused wrapper of a HIP rodent env (rollout configuration) whose model has a multi-step kernel
-    instance, and a policy the in-kernel actor evaluates (`actor_shape_supported`) on a row as wide as the env's -- the batch says
-    whether the actor of the instance it would launch reads that width (`reference_obs_supported(frames, with_actor=True)`: 1280 entries
-    without reference frames, 1664 with them); a wider row falls back to per-step collection."""
+    instance, and a policy the in-kernel actor evaluates (`actor_shape_supported`) on a row as wide as the env's -- the env says
+    whether the actor of the instance it would launch reads that width (`Rodent.fused_actor_refusal`: 1280 entries without reference
+    frames, 1664 with them or with a higher pose option); a wider row falls back to per-step collection."""
     base = wenv.unwrapped if hasattr(wenv, "unwrapped") else wenv
-    ask = getattr(getattr(base, "_batch", None), "reference_obs_supported", None)
-    if ask is not None and getattr(base, "clip_restarts", 0) >= 1:      # its multi-step launches run the clip-restart instances: the wide actor too
-        width_ok = base._batch.clip_restarts_supported(with_actor=True) is None
-    elif ask is not None and getattr(base, "body_tracking", None) is not None:      # its env steps run the wide actor at every frame count
-        width_ok = base._batch.body_tracking_supported(with_actor=True) is None
-    elif ask is not None and getattr(base, "pose_termination", None) is not None:      # likewise
-        width_ok = base._batch.pose_termination_supported(with_actor=True) is None
-    elif ask is not None:
-        width_ok = ask(getattr(base, "reference_obs_frames", 0), with_actor=True) is None
-    else:       # a batch that cannot say (not a `hip.Batch`): the 64 x 20 entries of the instances without reference frames
+    refusal = getattr(base, "fused_actor_refusal", None)
+    if refusal is not None:
+        width_ok = refusal() is None
+    else:       # an env that cannot say (not a `Rodent`): the 64 x 20 entries of the instances without reference frames
         width_ok = getattr(base, "observation_size", 0) <= 1280
     return (isinstance(wenv, wrappers.FusedEpisodeAutoResetWrapper) and hasattr(base, "unroll_policy_wrapped") and base.device.type == "cuda"
             and not base._pipeline_outputs and not base._contact_outputs and getattr(getattr(base, "sys", None), "solver", "cg") == "cg"

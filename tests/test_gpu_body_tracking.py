@@ -2,7 +2,7 @@
 rr_body_kernel instances): the reward's body-position and end-effector terms against a pose env of the same build -- bit for bit where
 nothing but the reward may move -- and against the float64 restatement `rodent.body_rewards` of the step's own returned xpos.
 
-Fixture: that of tests/test_gpu_pose.py, whose helpers are imported (12 envs on 3 clips, n_frames 2, CG 4/4, five steps; T = 104 and
+Fixture: that of tests/test_gpu_pose.py, from tests/pose_fixture.py (12 envs on 3 clips, n_frames 2, CG 4/4, five steps; T = 104 and
 T = 3), on rodent_optimized, rodent_new (nbody 67: three bodies on the lanes' second pass, under the root-slot map) and rodent_0 (the
 generic dims).  Reference bodies: `preprocessing.extract_features` of the pose (track position, qpos0[3:]) at every frame of every clip,
 plus AMP sin(0.9 b + 1.7 k + 0.05 t + c) per body b, axis k, frame t and clip c, so every entry differs.  B = all bodies, E = foot_L,
@@ -32,63 +32,35 @@ import numpy as np
 import pytest
 import torch
 
-from rodent_amd import jax_random, preprocessing
+from rodent_amd import jax_random
 from rodent_amd.envs import rodent
-from tests import test_gpu_pose as P
+from tests import pose_fixture as F
+from tests.pose_fixture import BW, C, DEV, EFF, EPS, IDS, N, SCALES, STEPS
 
 pytestmark = pytest.mark.gpu
-DEV = P.DEV
-N, C, STEPS, IDS, EPS = P.N, P.C, P.STEPS, P.IDS, P.EPS
 MODELS = ["rodent_optimized", "rodent_new", "rodent_0"]
 CASES = [(m, T) for m in MODELS for T in (104, 3)]
-EFF = {"rodent_optimized": (11, 15, 59, 64, 54), "rodent_0": (11, 15, 59, 64, 54), "rodent_new": (12, 16, 60, 65, 55)}
-AMP = 0.03
-BW = (0.6, 0.4)                                   # body_reward_weight, endeff_reward_weight
-SCALES = (8.0, 100.0)                             # body_reward_scale, endeff_reward_scale
-POSE_METRICS = P.OLD_METRICS + ("quat_reward", "joint_reward")
+POSE_METRICS = F.OLD_METRICS + ("quat_reward", "joint_reward")
 BODY_METRICS = ("body_reward", "endeff_reward")
 
 
 # ---------------------------------------------------------------------------------------------- the fixture
 @functools.lru_cache(maxsize=None)
-def _ref_bodies(model, T):
-    """Reference body positions [C, T, nbody, 3], float64: forward kinematics of (track position, qpos0[3:]) plus the sine term."""
-    q0, tr = P._qpos0(model), P._tracks(T)
-    qpos = np.concatenate([tr, np.broadcast_to(q0[3:], tr.shape[:-1] + (len(q0) - 3,))], axis=-1).reshape(C * T, len(q0))
-    base = preprocessing.extract_features(_pose_ref(model, T)[0], qpos).body_positions.astype(np.float64)
-    nbody = base.shape[1]
-    b, k, t, c = np.arange(nbody)[None, None, :, None], np.arange(3)[None, None, None, :], np.arange(T)[None, :, None, None], np.arange(C)[:, None, None, None]
-    return base.reshape(C, T, nbody, 3) + AMP * np.sin(0.9 * b + 1.7 * k + 0.05 * t + c)
-
-
-def _make(model, T, weights=BW, eff="fixture", **kw):
-    return P._make(model, T, track_bodies=_ref_bodies(model, T), end_effector_ids=EFF[model] if eff == "fixture" else eff,
-                   body_reward_weight=weights[0], body_reward_scale=SCALES[0], endeff_reward_weight=weights[1], endeff_reward_scale=SCALES[1], **kw)
-
-
-@functools.lru_cache(maxsize=None)
-def _pose_ref(model, T):
-    """Computed once per (model, T) and shared: (the pose env WITHOUT bodies, pipeline outputs on; its states of five bare steps)."""
-    env = P._make(model, T, pipeline_outputs=True)
-    return env, P._steps(env, P._draws(env, STEPS, 1)[0])
-
-
-@functools.lru_cache(maxsize=None)
 def _body_steps(model, T):
     """Computed once per (model, T) and shared: (the body env, pipeline outputs on; its states of five bare steps on the same keys, clips
-    and actions as `_pose_ref`)."""
-    env = _make(model, T, pipeline_outputs=True)
-    return env, P._steps(env, P._draws(env, STEPS, 1)[0])
+    and actions as `F.pose_ref`)."""
+    env = F.make_body(model, T, pipeline_outputs=True)
+    return env, F.steps(env, F.draws(env, STEPS, 1)[0])
 
 
 @functools.lru_cache(maxsize=None)
 def _forms(model, T):
     """Computed once per (model, T) and shared: the wrapped forms (tests/test_gpu_pose.py: seven steps, episodes of three) of the body env
     and of the pose env, same keys, clips, actions, noise and actor."""
-    env = _make(model, T)
+    env = F.make_body(model, T)
     assert env._batch.unroll_supported(False) and env._batch.unroll_supported(True)
-    acts, noise = P._draws(env, 7, 2)
-    return P._wrapped_forms(env, acts, noise, P._actor(env, 7)), P._forms(model, T)[0]
+    acts, noise = F.draws(env, 7, 2)
+    return F.wrapped_forms(env, acts, noise, F.actor(env, 7)), F.forms(model, T)[0]
 
 
 def _assert_same(got, want, what, metrics=POSE_METRICS, reward=False):
@@ -100,7 +72,7 @@ def _assert_same(got, want, what, metrics=POSE_METRICS, reward=False):
     if reward:
         pairs.append(("reward", got.reward, want.reward))
     for name, a, b in pairs:
-        la, lb = P._leaves(a), P._leaves(b)
+        la, lb = F.leaves(a), F.leaves(b)
         assert len(la) == len(lb) >= 1, (what, name)
         for i, (x, y) in enumerate(zip(la, lb)):
             assert x.shape == y.shape and x.dtype == y.dtype and torch.equal(x, y), (what, name, i, int((x != y).sum()))
@@ -108,14 +80,14 @@ def _assert_same(got, want, what, metrics=POSE_METRICS, reward=False):
 
 def _composed(pose_reward, state):
     """f32(f32(pose env's reward + body_reward) + endeff_reward) in numpy float32 arithmetic."""
-    return (P._f32(pose_reward) + P._f32(state.metrics["body_reward"])) + P._f32(state.metrics["endeff_reward"])
+    return (F.f32(pose_reward) + F.f32(state.metrics["body_reward"])) + F.f32(state.metrics["endeff_reward"])
 
 
 # ---------------------------------------------------------------------------------------------- 1. nothing else moves
 @pytest.mark.parametrize("model,T", CASES)
 def test_state_is_untouched_by_plain_steps(model, T):
     env, got = _body_steps(model, T)
-    _, want = _pose_ref(model, T)
+    _, want = F.pose_ref(model, T)
     bt = env.body_tracking
     assert bt is not None and bt["body_ids"] == tuple(range(1, env.sys.nbody)) and bt["end_effector_ids"] == EFF[model] and not env.eval_supported()
     assert bt["body_reward"] == (BW[0], SCALES[0]) and bt["endeff_reward"] == (BW[1], SCALES[1])
@@ -147,17 +119,17 @@ def test_reward_is_the_pose_reward_plus_body_plus_endeff(model, T):
     `unroll`; in the actor form (last step of the launch, whose metrics the state carries) within the one ulp tests/test_gpu_ppo.py
     allows that instance's reward."""
     _, got = _body_steps(model, T)
-    _, want = _pose_ref(model, T)
+    _, want = F.pose_ref(model, T)
     for t in range(1, STEPS + 1):
-        assert np.array_equal(P._f32(got[t].reward), _composed(want[t].reward, got[t])), (model, T, t)
+        assert np.array_equal(F.f32(got[t].reward), _composed(want[t].reward, got[t])), (model, T, t)
         assert float(got[t].metrics["body_reward"].min()) > 0 and float(got[t].metrics["endeff_reward"].min()) > 0
     fg, fw = _forms(model, T)
     for k in ("steps", "unroll"):
-        assert np.array_equal(P._f32(fg[k].reward), _composed(fw[k].reward, fg[k])), (model, T, k)
-    last = np.abs(P._f32(fg["buf"].reward[0, :, -1]).astype(np.float64) - _composed(fw["buf"].reward[0, :, -1], fg["policy"]).astype(np.float64))
+        assert np.array_equal(F.f32(fg[k].reward), _composed(fw[k].reward, fg[k])), (model, T, k)
+    last = np.abs(F.f32(fg["buf"].reward[0, :, -1]).astype(np.float64) - _composed(fw["buf"].reward[0, :, -1], fg["policy"]).astype(np.float64))
     print(f"{model} T={T}: actor form, last step: max |traj.reward - composed| = {last.max():.3g}")
-    assert last.max() <= P.ACTOR_REWARD_TOL
-    assert np.array_equal(P._f32(fg["policy"].reward), P._f32(fg["buf"].reward[0, :, -1]))       # t_reward receives the total the state carries
+    assert last.max() <= F.ACTOR_REWARD_TOL
+    assert np.array_equal(F.f32(fg["policy"].reward), F.f32(fg["buf"].reward[0, :, -1]))       # t_reward receives the total the state carries
 
 
 # ---------------------------------------------------------------------------------------------- 3. formula
@@ -179,7 +151,7 @@ def test_against_the_formula(model, T):
     env, states = _body_steps(model, T)
     nbody = env.sys.nbody
     rows = env._body["track_bodies"].cpu().numpy().astype(np.float64)
-    assert rows.shape == (C, T, nbody, 3) and np.array_equal(rows, _ref_bodies(model, T).astype(np.float32).astype(np.float64))
+    assert rows.shape == (C, T, nbody, 3) and np.array_equal(rows, F.ref_bodies(model, T).astype(np.float32).astype(np.float64))
     B, E = tuple(range(1, nbody)), EFF[model]
     assert nbody - 1 in E or nbody - 2 in E                 # an end effector on a lane's second body
     worst, alt = np.zeros(2), {k: np.zeros(2) for k in ("clip", "frame", "shift")}
@@ -219,7 +191,7 @@ def test_single_step_and_multi_step_agree(model, T):
     for k in BODY_METRICS:
         assert torch.equal(a.metrics[k], b.metrics[k]), (model, T, k)
     assert torch.equal(a.reward, b.reward)
-    la, lb = P._leaves(a), P._leaves(b)
+    la, lb = F.leaves(a), F.leaves(b)
     assert len(la) == len(lb) > 10
     for i, (x, y) in enumerate(zip(la, lb)):
         assert torch.equal(x, y), (model, T, i)
@@ -231,22 +203,21 @@ def test_with_reference_frames_and_a_termination_threshold(model):
     """H = 5 and `max_quat_error` (the data-derived threshold of tests/test_gpu_pose_termination.py, which fires in 25 % .. 75 % of the
     pairs): the whole state but the reward is that env's without bodies -- the observation's blocks, done and the failure code included --
     in bare steps and in the wrapped forms; the reward composes as everywhere."""
-    from tests import test_gpu_pose_termination as PT
     T = 104
-    thr = PT._reference(model, T)[3][1]
-    with_b, without = _make(model, T, reference_obs_frames=5, max_quat_error=thr), P._make(model, T, reference_obs_frames=5, max_quat_error=thr)
-    acts, _ = P._draws(with_b, STEPS, 1)
-    got, want = P._steps(with_b, acts), P._steps(without, acts)
+    thr = F.term_reference(model, T)[3][1]
+    with_b, without = F.make_body(model, T, reference_obs_frames=5, max_quat_error=thr), F.make(model, T, reference_obs_frames=5, max_quat_error=thr)
+    acts, _ = F.draws(with_b, STEPS, 1)
+    got, want = F.steps(with_b, acts), F.steps(without, acts)
     fails = 0
     for t in range(1, STEPS + 1):
-        _assert_same(got[t], want[t], (model, t), metrics=POSE_METRICS + PT.FAIL_METRICS)
-        assert np.array_equal(P._f32(got[t].reward), _composed(want[t].reward, got[t])), (model, t)
+        _assert_same(got[t], want[t], (model, t), metrics=POSE_METRICS + F.FAIL_METRICS)
+        assert np.array_equal(F.f32(got[t].reward), _composed(want[t].reward, got[t])), (model, t)
         fails += int(got[t].metrics["pose_fail"].sum())
     assert 15 <= fails <= 45 and got[1].obs.shape[1] == with_b.sys.obs_dim + 5 * with_b.sys.nq
-    acts, noise = P._draws(with_b, 7, 2)
-    fg, fw = P._wrapped_forms(with_b, acts, noise, P._actor(with_b, 7)), P._wrapped_forms(without, acts, noise, P._actor(without, 7))
+    acts, noise = F.draws(with_b, 7, 2)
+    fg, fw = F.wrapped_forms(with_b, acts, noise, F.actor(with_b, 7)), F.wrapped_forms(without, acts, noise, F.actor(without, 7))
     for k in ("steps", "unroll", "policy"):
-        _assert_same(fg[k], fw[k], (model, k), metrics=POSE_METRICS + PT.FAIL_METRICS)
+        _assert_same(fg[k], fw[k], (model, k), metrics=POSE_METRICS + F.FAIL_METRICS)
     for name in ("obs", "raw_action", "log_prob", "discount", "truncation"):
         assert torch.equal(getattr(fg["buf"], name), getattr(fw["buf"], name)), (model, name)
 
@@ -254,9 +225,9 @@ def test_with_reference_frames_and_a_termination_threshold(model):
 # ---------------------------------------------------------------------------------------------- 6. zero weights, no end effectors
 @pytest.mark.parametrize("model", MODELS)
 def test_zero_weights_give_the_pose_env(model):
-    _, want = _pose_ref(model, 104)
-    env = _make(model, 104, weights=(0.0, 0.0), pipeline_outputs=True)
-    got = P._steps(env, P._draws(env, STEPS, 1)[0])
+    _, want = F.pose_ref(model, 104)
+    env = F.make_body(model, 104, weights=(0.0, 0.0), pipeline_outputs=True)
+    got = F.steps(env, F.draws(env, STEPS, 1)[0])
     for t, (g, w) in enumerate(zip(got, want)):
         _assert_same(g, w, (model, t), reward=True)
         assert all(float(g.metrics[k].abs().max()) == 0.0 for k in BODY_METRICS)
@@ -264,16 +235,16 @@ def test_zero_weights_give_the_pose_env(model):
 
 @pytest.mark.parametrize("model", MODELS)
 def test_without_end_effectors_the_reward_has_the_body_term_alone(model):
-    _, want = _pose_ref(model, 104)
+    _, want = F.pose_ref(model, 104)
     _, full = _body_steps(model, 104)
-    env = _make(model, 104, eff=None, pipeline_outputs=True)
+    env = F.make_body(model, 104, eff=None, pipeline_outputs=True)
     assert env.body_tracking["end_effector_ids"] == () and env.body_tracking["endeff_reward"][0] == 0.0
-    got = P._steps(env, P._draws(env, STEPS, 1)[0])
+    got = F.steps(env, F.draws(env, STEPS, 1)[0])
     for t in range(1, STEPS + 1):
         _assert_same(got[t], want[t], (model, t))
         assert float(got[t].metrics["endeff_reward"].abs().max()) == 0.0
         assert torch.equal(got[t].metrics["body_reward"], full[t].metrics["body_reward"])
-        assert np.array_equal(P._f32(got[t].reward), P._f32(want[t].reward) + P._f32(got[t].metrics["body_reward"])), (model, t)
+        assert np.array_equal(F.f32(got[t].reward), F.f32(want[t].reward) + F.f32(got[t].metrics["body_reward"])), (model, t)
 
 
 # ---------------------------------------------------------------------------------------------- 7. bad state
@@ -281,18 +252,18 @@ def test_without_end_effectors_the_reward_has_the_body_term_alone(model):
 def test_a_bad_step_zeroes_the_body_terms(model):
     from rodent_amd.envs import wrappers
     from rodent_amd.training import acting
-    env = _make(model, 104, bad_state_max=1e10)
+    env = F.make_body(model, 104, bad_state_max=1e10)
     bad = 4
 
     def poison(state):       # NaN into a COPY of the incoming qvel (the stored first state shares the reset's tensors)
         qvel = state.pipeline_state.qvel.clone()
         qvel[bad, 3] = float("nan")
         return state.replace(pipeline_state=state.pipeline_state.replace(qvel=qvel))
-    acts, noise = P._draws(env, 1, 3)
+    acts, noise = F.draws(env, 1, 3)
     wenv = wrappers.wrap(env, episode_length=100, action_repeat=1)
     buf = acting.UnrollBuffer(1, N, 1, env.observation_size, env.action_size, torch.device(DEV))
-    res = dict(step=env.step(poison(env.reset(P._keys(), clip=IDS)), acts[0]), unroll=wenv.unroll(poison(wenv.reset(P._keys(), clip=IDS)), acts),
-               policy=wenv.unroll_policy(poison(wenv.reset(P._keys(), clip=IDS)), P._actor(env, 5), noise, P._traj(buf))[0])
+    res = dict(step=env.step(poison(env.reset(F.keys(), clip=IDS)), acts[0]), unroll=wenv.unroll(poison(wenv.reset(F.keys(), clip=IDS)), acts),
+               policy=wenv.unroll_policy(poison(wenv.reset(F.keys(), clip=IDS)), F.actor(env, 5), noise, F.traj(buf))[0])
     torch.cuda.synchronize()
     ok = [e for e in range(N) if e != bad]
     for k, s in res.items():
@@ -308,15 +279,15 @@ def test_a_bad_step_zeroes_the_body_terms(model):
 def test_refusals():
     from rodent_amd import envs
     T = 104
-    track = P._tracks(T)[0]
+    track = F.tracks(T)[0]
 
     def build(model, pose=True, **kw):
-        q0 = P._qpos0(model)
+        q0 = F.qpos0(model)
         if pose:
             kw.update(track_quat=np.tile([1.0, 0.0, 0.0, 0.0], (T, 1)), track_joints=np.tile(q0[7:], (T, 1)))
         return envs.get_environment("rodent", track_pos=track, num_envs=4, xml_path=f"{model}.xml", iterations=4, ls_iterations=4, n_frames=2,
                                     device=DEV, **kw)
-    bodies = _ref_bodies("rodent_optimized", T)[0]
+    bodies = F.ref_bodies("rodent_optimized", T)[0]
     with pytest.raises(ValueError, match="track_quat and track_joints"):
         build("rodent_optimized", pose=False, track_bodies=bodies)
     with pytest.raises(RuntimeError, match="Newton solver"):
@@ -351,7 +322,7 @@ def test_refusals():
     with pytest.raises(RuntimeError, match="null track_bodies, body_weights or body_metrics"):
         b.set_body_tracking(block[0], None, block[2])
     with pytest.raises(RuntimeError, match="no evaluation instance rewards the body positions"):
-        env.unroll_eval(env.reset(jax_random.split(jax_random.PRNGKey(1), 4)), 2, P._actor(env, 1))
+        env.unroll_eval(env.reset(jax_random.split(jax_random.PRNGKey(1), 4)), 2, F.actor(env, 1))
 
 
 # ---------------------------------------------------------------------------------------------- 9. training
@@ -360,7 +331,7 @@ def test_ppo_train_on_a_body_env(monkeypatch):
     by the per-step loop: finite losses and finite eval/episode_body_reward and eval/episode_endeff_reward next to the existing keys."""
     from rodent_amd.training import acting
     from rodent_amd.training.agents.ppo import train as ppo
-    env = _make("rodent_optimized", 104, n=64)
+    env = F.make_body("rodent_optimized", 104, n=64)
     calls, log = {"fused": 0}, []
     real_fused = acting.generate_unrolls_fused
     monkeypatch.setattr(acting, "generate_unrolls_fused", lambda *a, **k: (calls.__setitem__("fused", calls["fused"] + 1), real_fused(*a, **k))[1])

@@ -16,7 +16,7 @@ errors per criterion from the stepped qpos (taken before the restore), and each 
 ranks 70 % .. 80 % (each criterion alone fires in 20 % .. 30 % of those pairs: low enough for episodes to reach `episode_length` and
 the clip's end as well).  The failures of the run WITH the thresholds are then counted on the float64 restatement (`pose_fail_code` of
 the recorded stepped states) and must lie in 25 % .. 75 % of the pairs.  The device decides `error > threshold` in float32; its code is
-compared with the restatement wherever the error is further from the threshold than 100 float32 bounds (`test_gpu_pose_termination._bound`)."""
+compared with the restatement wherever the error is further from the threshold than 100 float32 bounds (`pose_fixture.term_bound`)."""
 import functools
 import math
 
@@ -26,12 +26,10 @@ import torch
 
 from rodent_amd import jax_random
 from rodent_amd.envs import rodent, wrappers
-from tests import test_gpu_body_tracking as B
-from tests import test_gpu_pose as P
-from tests import test_gpu_pose_termination as PT
+from tests import pose_fixture as F
+from tests.pose_fixture import DEV
 
 pytestmark = pytest.mark.gpu
-DEV = P.DEV
 N, C, T, L, STEPS = 32, 3, 104, 5, 14
 SEED, RANGE = 94, (90, 102)
 IDS = np.arange(N) % C
@@ -73,18 +71,18 @@ def _make(model, K, H=0, bodies=False, thr=None, end=None, **kw):
     if H:
         kw.update(reference_obs_frames=H)
     if bodies:
-        kw.update(track_bodies=B._ref_bodies(model, T), end_effector_ids=B.EFF[model], body_reward_weight=B.BW[0], body_reward_scale=B.SCALES[0],
-                  endeff_reward_weight=B.BW[1], endeff_reward_scale=B.SCALES[1])
+        kw.update(track_bodies=F.ref_bodies(model, T), end_effector_ids=F.EFF[model], body_reward_weight=F.BW[0], body_reward_scale=F.SCALES[0],
+                  endeff_reward_weight=F.BW[1], endeff_reward_scale=F.SCALES[1])
     if thr is not None:
         kw.update(max_pos_error=thr[0], max_quat_error=thr[1], max_joint_error=thr[2])
     frames = kw.pop("frames", T)
     if frames == T:
-        return P._make(model, T, n=N, **kw)
+        return F.make(model, T, n=N, **kw)
     from rodent_amd import envs          # the same fixture on a clip of another length (tests/test_gpu_pose.py has scales for T = 104 and 3 only)
-    quat, joints = P._reference(model, frames)
-    return envs.get_environment("rodent", track_pos=P._tracks(frames), num_envs=N, xml_path=f"{model}.xml", iterations=4, ls_iterations=4, n_frames=2,
-                                device=DEV, track_quat=quat, track_joints=joints, quat_reward_weight=P.W[0], quat_reward_scale=P.QUAT_SCALE[T],
-                                joint_reward_weight=P.W[1], joint_reward_scale=P.JOINT_SCALE, **kw)
+    quat, joints = F.reference(model, frames)
+    return envs.get_environment("rodent", track_pos=F.tracks(frames), num_envs=N, xml_path=f"{model}.xml", iterations=4, ls_iterations=4, n_frames=2,
+                                device=DEV, track_quat=quat, track_joints=joints, quat_reward_weight=F.W[0], quat_reward_scale=F.QUAT_SCALE[T],
+                                joint_reward_weight=F.W[1], joint_reward_scale=F.JOINT_SCALE, **kw)
 
 
 def _draws(env, steps, seed):
@@ -194,7 +192,7 @@ def _forms(case):
     out["unroll77"] = wenv.unroll(out["unroll7"], acts[7:])
     buf = acting.UnrollBuffer(2, N, 7, env.observation_size, env.action_size, torch.device(DEV))
     traj = dict(obs=buf.obs, raw_action=buf.raw_action, log_prob=buf.log_prob, reward=buf.reward, discount=buf.discount, truncation=buf.truncation)
-    out["policy"], out["policy_actions"] = wenv.unroll_policy(wenv.reset(_keys(), clip=IDS), P._actor(env, 7), noise, traj, segment=7)
+    out["policy"], out["policy_actions"] = wenv.unroll_policy(wenv.reset(_keys(), clip=IDS), F.actor(env, 7), noise, traj, segment=7)
     out["buf"] = buf
     torch.cuda.synchronize()
     return out
@@ -221,8 +219,8 @@ def test_pose_failures_fall_in_a_quarter_to_three_quarters_of_the_pairs(case):
         old, qpos = f["seen"][t - 1]
         e = _errors(env, qpos, old)
         code = rodent.pose_fail_code(e, thr)
-        clear = np.all(np.abs(e - np.asarray(thr)[:, None]) > 100 * PT._bound(e), axis=0)
-        got = PT._code_of(f["composed"][t])
+        clear = np.all(np.abs(e - np.asarray(thr)[:, None]) > 100 * F.term_bound(e), axis=0)
+        got = F.code_of(f["composed"][t])
         assert np.array_equal(got[clear], code[clear]), (case, t)
         fails, close = fails + int((code != 0).sum()), close + int((~clear).sum())
         s = f["composed"][t]
@@ -280,9 +278,9 @@ def test_unroll_policy_in_two_segments_replays_per_step(case):
         assert torch.equal(buf.discount[u, :, i], 1 - replay[t + 1].done) and torch.equal(buf.truncation[u, :, i], replay[t + 1].info["truncation"]), (case, t)
         worst = max(worst, float((buf.reward[u, :, i] - replay[t + 1].reward).abs().max()))
     assert torch.equal(buf.obs[0, :, 7], replay[7].obs) and torch.equal(buf.obs[1, :, 7], replay[STEPS].obs)
-    print(f"{case}: max |traj.reward - per-step reward| = {worst:.3g} (allowed {P.ACTOR_REWARD_TOL})")
-    assert worst <= P.ACTOR_REWARD_TOL
-    _assert_same(f["policy"], replay[STEPS], (case, "final"), reward_tol=P.ACTOR_REWARD_TOL)
+    print(f"{case}: max |traj.reward - per-step reward| = {worst:.3g} (allowed {F.ACTOR_REWARD_TOL})")
+    assert worst <= F.ACTOR_REWARD_TOL
+    _assert_same(f["policy"], replay[STEPS], (case, "final"), reward_tol=F.ACTOR_REWARD_TOL)
 
 
 # ---------------------------------------------------------------------------------------------- 4. no-restart equality
@@ -374,7 +372,7 @@ def test_a_nan_in_qvel_takes_the_next_bank_entry_in_all_three_forms():
     poisoned = s0.replace(pipeline_state=s0.pipeline_state.replace(qvel=qvel))
     buf = acting.UnrollBuffer(1, N, 1, env.observation_size, env.action_size, torch.device(DEV))
     outs = dict(step=wenv.step(poisoned, acts[0]), unroll=wenv.unroll(poisoned, acts[:1]),
-                policy=wenv.unroll_policy(poisoned, P._actor(env, 7), noise[:1], P._traj(buf))[0])
+                policy=wenv.unroll_policy(poisoned, F.actor(env, 7), noise[:1], F.traj(buf))[0])
     torch.cuda.synchronize()
     bank = s0.info["restart_bank"]
     for name, s in outs.items():
@@ -390,16 +388,16 @@ def test_a_nan_in_qvel_takes_the_next_bank_entry_in_all_three_forms():
 # ---------------------------------------------------------------------------------------------- 7. refusals
 def test_refusals():
     with pytest.raises(ValueError, match="need the reference pose"):
-        P._make("rodent_optimized", T, n=N, pose=False, clip_restarts=2)
+        F.make("rodent_optimized", T, n=N, pose=False, clip_restarts=2)
     with pytest.raises(ValueError, match="needs clip_restarts >= 1"):
         _make("rodent_optimized", 0, end_at_clip_end=True)
     with pytest.raises(RuntimeError, match="Newton"):
         _make("rodent_optimized", 2, solver="newton")
-    plain = P._make("rodent_optimized", T, n=N, pose=False)
-    newton = P._make("rodent_optimized", T, n=N, pose=False, solver="newton")
+    plain = F.make("rodent_optimized", T, n=N, pose=False)
+    newton = F.make("rodent_optimized", T, n=N, pose=False, solver="newton")
     assert "Newton" in newton._batch.clip_restarts_supported() and plain._batch.clip_restarts_supported() is None
     from rodent_amd import envs
-    cpu = envs.get_environment("rodent", track_pos=P._tracks(T)[0], num_envs=N, xml_path="rodent_cpu.xml", iterations=4, ls_iterations=4, n_frames=2, device=DEV)
+    cpu = envs.get_environment("rodent", track_pos=F.tracks(T)[0], num_envs=N, xml_path="rodent_cpu.xml", iterations=4, ls_iterations=4, n_frames=2, device=DEV)
     assert "candidate-pair" in cpu._batch.clip_restarts_supported() and "candidate-pair" in cpu._batch.clip_restarts_supported(with_actor=True)
     # the setter's own: no pose block, a slot count outside 1 .. 64, null pointers
     frames, slot = torch.zeros(2, N, dtype=torch.int32, device=DEV), torch.zeros(N, dtype=torch.int32, device=DEV)
@@ -422,7 +420,7 @@ def test_refusals():
         env.set_env_params(dof_f=torch.zeros(N, env.sys.nv, 16, device=DEV))
     # the evaluation form
     assert not env.eval_supported() and not wrappers.EvalWrapper(wenv).unroll_supported()
-    ring_actor = P._actor(env, 7)
+    ring_actor = F.actor(env, 7)
     with pytest.raises(RuntimeError, match="rr_env_unroll_eval"):
         env.unroll_eval(s, 2, ring_actor, None, episode_length=L, eval_metrics=torch.zeros(N, 6, device=DEV))
     # the per-step evaluator runs the fused wrapper and so gets the rule
@@ -439,7 +437,7 @@ def test_ppo_train_with_clip_restarts(monkeypatch):
     yes, the rollout runs as one launch, and the losses are finite."""
     from rodent_amd.training import acting
     from rodent_amd.training.agents.ppo import train as ppo
-    env = P._make("rodent_optimized", T, n=64, clip_restarts=3, restart_frame_range=RANGE, end_at_clip_end=True, reference_obs_frames=5,
+    env = F.make("rodent_optimized", T, n=64, clip_restarts=3, restart_frame_range=RANGE, end_at_clip_end=True, reference_obs_frames=5,
                   max_pos_error=0.05)
     calls, log, said = {"fused": 0}, [], []
     real_fused, real_supported = acting.generate_unrolls_fused, acting.fused_unroll_supported

@@ -9,103 +9,18 @@ qpos0[7:] + 0.02 sin(0.7 j + 0.05 t + c): every (clip, frame, joint) differs.  S
 lies in [0.10, 0.34] for T = 3 and in [0.12, 0.62] for T = 104, the summed squared joint error in [0.2, 2.5] (float64 CPU oracle on this
 fixture under uniform random actions), so quat_reward_scale 12 / 5 and joint_reward_scale 0.6 keep both exponents inside
 [-log 0.95, -log 0.05] = [0.051, 3.0]; the formula test asserts that.  Weights 0.75 / 0.5 (not the defaults)."""
-import functools
 import math
 
 import numpy as np
 import pytest
 import torch
 
-from rodent_amd import assets, jax_random, mjcf
+from rodent_amd import jax_random
 from rodent_amd.envs import rodent
+from tests.pose_fixture import (ACTOR_REWARD_TOL, C, DEV, EPS, IDS, JOINT_SCALE, MODELS, N, OLD_METRICS, QUAT_SCALE, STEPS, W, actor, draws, f32, forms,
+                                keys, leaves, make, plain_steps, qpos0, steps, tracks, traj)
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-N, C, STEPS = 12, 3, 5
-SEED = 78            # start frames [42, 99, 35, 32, 33, 99, 10, 46, 47, 47, 19, 51]
-IDS = np.arange(N) % C
-MODELS = ["rodent_optimized", "rodent_0"]
-EPS = 2.0 ** -24
-W = (0.75, 0.5)                                  # quat_reward_weight, joint_reward_weight
-QUAT_SCALE, JOINT_SCALE = {104: 5.0, 3: 12.0}, 0.6
-ACTOR_REWARD_TOL = 2.5e-7                        # tests/test_gpu_ppo.py::test_one_launch_unroll_with_the_actor_inside: the actor instance's reward, one ulp
-OLD_METRICS = ("pos_reward", "reward_quadctrl", "reward_alive")
-
-
-def _tracks(T):
-    t = np.arange(T, dtype=np.float64)
-    return np.stack([np.stack([0.004 * t, np.full(T, 0.1 * c), np.full(T, 0.0681 + 0.002 * c)], axis=1) for c in range(C)])
-
-
-@functools.lru_cache(maxsize=None)
-def _qpos0(model):
-    return mjcf.load_blob(assets.asset_path(model))["qpos0"].astype(np.float64)
-
-
-def _reference(model, T):
-    """(quat [C, T, 4], joints [C, T, nq - 7]) of the fixture, float64."""
-    q0 = _qpos0(model)
-    t, c, j = np.arange(T, dtype=np.float64), np.arange(C, dtype=np.float64), np.arange(len(q0) - 7, dtype=np.float64)
-    ang = 0.1 * (c[:, None] + 1) + 0.003 * t[None]
-    quat = np.stack([np.cos(ang / 2), np.zeros_like(ang), np.zeros_like(ang), np.sin(ang / 2)], axis=-1)
-    joints = q0[7:][None, None] + 0.02 * np.sin(0.7 * j[None, None] + 0.05 * t[None, :, None] + c[:, None, None])
-    return quat, joints
-
-
-def _make(model, T, n=N, pose=True, weights=W, **kw):
-    from rodent_amd import envs
-    if pose:
-        quat, joints = _reference(model, T)
-        kw.update(track_quat=quat, track_joints=joints, quat_reward_weight=weights[0], quat_reward_scale=QUAT_SCALE[T],
-                  joint_reward_weight=weights[1], joint_reward_scale=JOINT_SCALE)
-    kw.setdefault("iterations", 4)
-    return envs.get_environment("rodent", track_pos=_tracks(T), num_envs=n, xml_path=f"{model}.xml", ls_iterations=4, n_frames=2, device=DEV, **kw)
-
-
-def _keys():
-    return jax_random.split(jax_random.PRNGKey(SEED), N)
-
-
-def _draws(env, T, seed):
-    gen = torch.Generator(device=DEV).manual_seed(seed)
-    A = env.action_size
-    return torch.rand(T, N, A, device=DEV, generator=gen) * 2 - 1, torch.randn(T, N, A, device=DEV, generator=gen)
-
-
-def _actor(env, seed):
-    from rodent_amd.training import acting, networks, running_statistics
-    torch.manual_seed(seed)
-    nets = networks.make_ppo_networks(env.observation_size, env.action_size, device=DEV)
-    net, dist = nets.policy_network, nets.parametric_action_distribution
-    for l in net.layers:
-        l.bias.data.uniform_(-0.3, 0.3)
-    norm = running_statistics.init_state(env.observation_size, torch.device(DEV))
-    norm.mean.copy_(torch.randn(env.observation_size, device=DEV) * 0.05)
-    norm.std.copy_(torch.rand(env.observation_size, device=DEV) + 0.7)
-    return acting.actor_params(net, norm, dist.min_std)
-
-
-def _steps(env, acts):
-    """The reset state and the state after each plain `step`."""
-    out = [env.reset(_keys(), clip=IDS)]
-    for t in range(acts.shape[0]):
-        out.append(env.step(out[-1], acts[t]))
-    torch.cuda.synchronize()
-    return out
-
-
-@functools.lru_cache(maxsize=None)
-def _plain_steps(model, T):
-    """Computed once per (model, T) and shared: (pose env, its states, the plain env's states) of five plain steps on the same keys,
-    clips and actions."""
-    pose_env, plain_env = _make(model, T), _make(model, T, pose=False)
-    acts, _ = _draws(pose_env, STEPS, 1)
-    return pose_env, _steps(pose_env, acts), _steps(plain_env, acts)
-
-
-def _leaves(x):
-    from rodent_amd.envs import graphed
-    return graphed.tree_leaves(x)
 
 
 def _assert_same_but_reward(got, want, what):
@@ -115,51 +30,15 @@ def _assert_same_but_reward(got, want, what):
     pairs = [("pipeline_state", got.pipeline_state, want.pipeline_state), ("obs", got.obs, want.obs), ("done", got.done, want.done),
              ("info", got.info, want.info), ("metrics", {k: got.metrics[k] for k in OLD_METRICS}, {k: want.metrics[k] for k in OLD_METRICS})]
     for name, a, b in pairs:
-        la, lb = _leaves(a), _leaves(b)
+        la, lb = leaves(a), leaves(b)
         assert len(la) == len(lb) >= 1, (what, name)
         for i, (x, y) in enumerate(zip(la, lb)):
             assert x.shape == y.shape and x.dtype == y.dtype and torch.equal(x, y), (what, name, i, int((x != y).sum()))
 
 
-def _f32(x):
-    return x.detach().cpu().numpy().astype(np.float32)
-
-
 def _composed(plain_reward, state):
     """f32(f32(plain + quat_reward) + joint_reward) in numpy float32 arithmetic (each `+` of two float32 arrays rounds once)."""
-    return (_f32(plain_reward) + _f32(state.metrics["quat_reward"])) + _f32(state.metrics["joint_reward"])
-
-
-def _traj(buf):
-    return dict(obs=buf.obs[0], raw_action=buf.raw_action[0], log_prob=buf.log_prob[0], reward=buf.reward[0], discount=buf.discount[0],
-                truncation=buf.truncation[0])
-
-
-def _wrapped_forms(env, acts, noise, actor):
-    """Under Episode(3) + AutoReset: wrapped single steps, `unroll`, `unroll_policy` into trajectory buffers."""
-    from rodent_amd.envs import wrappers
-    from rodent_amd.training import acting
-    wenv = wrappers.wrap(env, episode_length=3, action_repeat=1)
-    s = wenv.reset(_keys(), clip=IDS)
-    for t in range(acts.shape[0]):
-        s = wenv.step(s, acts[t])
-    out = dict(steps=s, unroll=wenv.unroll(wenv.reset(_keys(), clip=IDS), acts))
-    buf = acting.UnrollBuffer(1, env.num_envs, acts.shape[0], env.observation_size, env.action_size, torch.device(DEV))
-    out["policy"], out["policy_actions"] = wenv.unroll_policy(wenv.reset(_keys(), clip=IDS), actor, noise, _traj(buf))
-    out["buf"] = buf
-    torch.cuda.synchronize()
-    return out
-
-
-@functools.lru_cache(maxsize=None)
-def _forms(model, T):
-    """Computed once per (model, T) and shared: the wrapped forms of the pose env and of the plain env, seven steps with episodes of
-    three (restores happen inside every launch)."""
-    pose_env, plain_env = _make(model, T), _make(model, T, pose=False)
-    assert pose_env._batch.unroll_supported(False) and pose_env._batch.unroll_supported(True)
-    actor = _actor(pose_env, 7)
-    acts, noise = _draws(pose_env, 7, 2)
-    return _wrapped_forms(pose_env, acts, noise, actor), _wrapped_forms(plain_env, acts, noise, actor)
+    return (f32(plain_reward) + f32(state.metrics["quat_reward"])) + f32(state.metrics["joint_reward"])
 
 
 CASES = [(m, T) for m in MODELS for T in (104, 3)]
@@ -168,7 +47,7 @@ CASES = [(m, T) for m in MODELS for T in (104, 3)]
 # ---------------------------------------------------------------------------------------------- 1. nothing else moves
 @pytest.mark.parametrize("model,T", CASES)
 def test_physics_and_old_outputs_are_untouched_by_plain_steps(model, T):
-    env, got, want = _plain_steps(model, T)
+    env, got, want = plain_steps(model, T)
     assert env.pose_tracking and not env.eval_supported()
     assert all(float(got[0].metrics[k].abs().max()) == 0.0 for k in ("quat_reward", "joint_reward"))       # zeros at reset
     assert torch.equal(got[0].reward, want[0].reward)
@@ -181,7 +60,7 @@ def test_physics_and_old_outputs_are_untouched_by_plain_steps(model, T):
 
 @pytest.mark.parametrize("model,T", CASES)
 def test_physics_and_old_outputs_are_untouched_by_the_multi_step_forms(model, T):
-    got, want = _forms(model, T)
+    got, want = forms(model, T)
     for k in ("steps", "unroll", "policy"):
         _assert_same_but_reward(got[k], want[k], (model, T, k))
     assert torch.equal(got["policy_actions"], want["policy_actions"])
@@ -197,17 +76,17 @@ def test_reward_is_plain_plus_quat_plus_joint(model, T):
     """reward == f32(f32(plain.reward + quat_reward) + joint_reward), the plain env's reward and the pose env's own metrics: bit for
     bit in `step` and `unroll`; in the actor form (last step of the launch, whose metrics the state carries) within the one ulp
     tests/test_gpu_ppo.py allows that instance's plain reward."""
-    _, got, want = _plain_steps(model, T)
+    _, got, want = plain_steps(model, T)
     for t in range(1, STEPS + 1):
-        assert np.array_equal(_f32(got[t].reward), _composed(want[t].reward, got[t])), (model, T, t)
+        assert np.array_equal(f32(got[t].reward), _composed(want[t].reward, got[t])), (model, T, t)
         assert float(got[t].metrics["quat_reward"].min()) > 0 and float(got[t].metrics["joint_reward"].min()) > 0
-    fg, fw = _forms(model, T)
+    fg, fw = forms(model, T)
     for k in ("steps", "unroll"):
-        assert np.array_equal(_f32(fg[k].reward), _composed(fw[k].reward, fg[k])), (model, T, k)
-    last = np.abs(_f32(fg["buf"].reward[0, :, -1]).astype(np.float64) - _composed(fw["buf"].reward[0, :, -1], fg["policy"]).astype(np.float64))
+        assert np.array_equal(f32(fg[k].reward), _composed(fw[k].reward, fg[k])), (model, T, k)
+    last = np.abs(f32(fg["buf"].reward[0, :, -1]).astype(np.float64) - _composed(fw["buf"].reward[0, :, -1], fg["policy"]).astype(np.float64))
     print(f"{model} T={T}: actor form, last step: max |traj.reward - composed| = {last.max():.3g}")
     assert last.max() <= ACTOR_REWARD_TOL
-    assert np.array_equal(_f32(fg["policy"].reward), _f32(fg["buf"].reward[0, :, -1]))       # t_reward receives the total the state carries
+    assert np.array_equal(f32(fg["policy"].reward), f32(fg["buf"].reward[0, :, -1]))       # t_reward receives the total the state carries
 
 
 # ---------------------------------------------------------------------------------------------- 3. formula
@@ -240,7 +119,7 @@ def test_against_the_formula(model, T):
     the neighbouring clip, for the neighbouring frame and (joints) with the joint row shifted by one index, the largest error-to-bound
     ratio over the samples -- the number this test holds below 1 for the right row -- is at least 100.  (Over the samples, not per
     sample: the joint term moves by -2 sum e_i dr_i + sum dr_i^2, which for a single env and step can cancel to nothing.)"""
-    env, states, _ = _plain_steps(model, T)
+    env, states, _ = plain_steps(model, T)
     kq, kj = QUAT_SCALE[T], JOINT_SCALE
     rows = env._pose_host.astype(np.float64)                 # float32 [C, T, nq - 3], what the device holds
     assert rows.shape == (C, T, env.sys.nq - 3) and torch.equal(env._track_pose.cpu(), torch.from_numpy(env._pose_host))
@@ -279,12 +158,12 @@ def test_against_the_formula(model, T):
 # ---------------------------------------------------------------------------------------------- 4. launch forms
 @pytest.mark.parametrize("model,T", CASES)
 def test_single_step_and_multi_step_agree(model, T):
-    got, _ = _forms(model, T)
+    got, _ = forms(model, T)
     a, b = got["steps"], got["unroll"]
     for k in ("quat_reward", "joint_reward"):
         assert torch.equal(a.metrics[k], b.metrics[k]), (model, T, k)
     assert torch.equal(a.reward, b.reward)
-    la, lb = _leaves(a), _leaves(b)
+    la, lb = leaves(a), leaves(b)
     assert len(la) == len(lb) > 10
     for i, (x, y) in enumerate(zip(la, lb)):
         assert torch.equal(x, y), (model, T, i)
@@ -295,18 +174,18 @@ def test_single_step_and_multi_step_agree(model, T):
 def test_a_bad_step_zeroes_the_pose_terms(model):
     from rodent_amd.envs import wrappers
     from rodent_amd.training import acting
-    env = _make(model, 104, bad_state_max=1e10)
+    env = make(model, 104, bad_state_max=1e10)
     bad = 4
 
     def poison(state):       # NaN into a COPY of the incoming qvel (the stored first state shares the reset's tensors)
         qvel = state.pipeline_state.qvel.clone()
         qvel[bad, 3] = float("nan")
         return state.replace(pipeline_state=state.pipeline_state.replace(qvel=qvel))
-    acts, noise = _draws(env, 1, 3)
+    acts, noise = draws(env, 1, 3)
     wenv = wrappers.wrap(env, episode_length=100, action_repeat=1)
     buf = acting.UnrollBuffer(1, N, 1, env.observation_size, env.action_size, torch.device(DEV))
-    res = dict(step=env.step(poison(env.reset(_keys(), clip=IDS)), acts[0]), unroll=wenv.unroll(poison(wenv.reset(_keys(), clip=IDS)), acts),
-               policy=wenv.unroll_policy(poison(wenv.reset(_keys(), clip=IDS)), _actor(env, 5), noise, _traj(buf))[0])
+    res = dict(step=env.step(poison(env.reset(keys(), clip=IDS)), acts[0]), unroll=wenv.unroll(poison(wenv.reset(keys(), clip=IDS)), acts),
+               policy=wenv.unroll_policy(poison(wenv.reset(keys(), clip=IDS)), actor(env, 5), noise, traj(buf))[0])
     torch.cuda.synchronize()
     ok = [e for e in range(N) if e != bad]
     for k, s in res.items():
@@ -321,10 +200,10 @@ def test_a_bad_step_zeroes_the_pose_terms(model):
 # ---------------------------------------------------------------------------------------------- 6. refusals
 def test_refusals():
     from rodent_amd import envs
-    track = _tracks(104)[0]
+    track = tracks(104)[0]
 
     def build(model, **kw):
-        q0 = _qpos0(model)
+        q0 = qpos0(model)
         quat = np.tile([1.0, 0.0, 0.0, 0.0], (104, 1))
         return envs.get_environment("rodent", track_pos=track, num_envs=4, xml_path=f"{model}.xml", iterations=4, ls_iterations=4, n_frames=2,
                                     device=DEV, track_quat=quat, track_joints=np.tile(q0[7:], (104, 1)), **kw)
@@ -341,7 +220,7 @@ def test_refusals():
     st = env.step(env.reset(jax_random.split(jax_random.PRNGKey(1), 4)), torch.zeros(4, env.action_size, device=DEV))      # still a working pose env
     assert float(st.metrics["quat_reward"].min()) > 0
     with pytest.raises(RuntimeError, match="no evaluation instance rewards the pose"):
-        env.unroll_eval(env.reset(jax_random.split(jax_random.PRNGKey(1), 4)), 2, _actor(env, 1))
+        env.unroll_eval(env.reset(jax_random.split(jax_random.PRNGKey(1), 4)), 2, actor(env, 1))
 
 
 # ---------------------------------------------------------------------------------------------- 7. training
@@ -350,7 +229,7 @@ def test_ppo_train_on_a_pose_env(monkeypatch):
     by the per-step loop: finite losses and finite eval/episode_quat_reward and eval/episode_joint_reward next to the existing keys."""
     from rodent_amd.training import acting
     from rodent_amd.training.agents.ppo import train as ppo
-    env = _make("rodent_optimized", 104, n=64)
+    env = make("rodent_optimized", 104, n=64)
     calls, log = {"fused": 0}, []
     real_fused = acting.generate_unrolls_fused
     monkeypatch.setattr(acting, "generate_unrolls_fused", lambda *a, **k: (calls.__setitem__("fused", calls["fused"] + 1), real_fused(*a, **k))[1])
@@ -372,10 +251,10 @@ def test_ppo_train_on_a_pose_env(monkeypatch):
 def test_zero_weights_give_the_plain_env(model):
     """Both weights 0: the pose instances run, the reward gains + 0 + 0, and the whole state -- reward included -- is the plain env's, apart
     from the two metrics, which are 0."""
-    _, _, want = _plain_steps(model, 104)
-    env = _make(model, 104, weights=(0.0, 0.0))
-    acts, _ = _draws(env, STEPS, 1)
-    got = _steps(env, acts)
+    _, _, want = plain_steps(model, 104)
+    env = make(model, 104, weights=(0.0, 0.0))
+    acts, _ = draws(env, STEPS, 1)
+    got = steps(env, acts)
     for t, (g, w) in enumerate(zip(got, want)):
         _assert_same_but_reward(g, w, (model, t))
         assert torch.equal(g.reward, w.reward), (model, t)

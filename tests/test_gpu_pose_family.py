@@ -3,7 +3,7 @@ body tracking in any combination, and an option a batch does not carry reaches i
 thresholds with a null pose_fail, a null track_bodies).  That rests on one property, pinned here: an option that is off, or on without
 effect, moves no bit of anything else.
 
-Fixture and helpers of tests/test_gpu_pose.py (12 envs on 3 clips, T = 104, n_frames 2, CG 4/4; rodent_optimized -- fixed dims -- and
+Fixture and helpers of tests/pose_fixture.py (12 envs on 3 clips, T = 104, n_frames 2, CG 4/4; rodent_optimized -- fixed dims -- and
 rodent_0 -- generic dims).  Per model the eight envs of the lattice H in {0, 5} x thresholds in {none, (1e30, 1e30, 1e30): every compare
 made, none fires} x bodies in {none, the fixture of tests/test_gpu_body_tracking.py}, all on the same keys, clips, actions and noise.
 Each runs (a) five bare steps, (b) the wrapped multi-step launch of seven steps with episodes of three and (c) the same with the actor
@@ -26,16 +26,14 @@ import itertools
 import pytest
 import torch
 
-from tests import test_gpu_body_tracking as B
-from tests import test_gpu_pose as P
+from tests import pose_fixture as F
+from tests.pose_fixture import FAIL_METRICS, MODELS
 
 pytestmark = pytest.mark.gpu
 T = 104
-MODELS = P.MODELS
 LATTICE = list(itertools.product((0, 5), (False, True), (False, True)))      # (H, thresholds, bodies)
 POSE_ENV = (0, False, False)
 FORMS = ("bare", "steps", "unroll", "policy")
-FAIL_METRICS = ("pose_fail", "pose_fail_pos", "pose_fail_quat", "pose_fail_joint")
 
 
 @functools.lru_cache(maxsize=None)
@@ -47,11 +45,11 @@ def _runs(model):
         kw = dict(reference_obs_frames=H) if H else {}
         if thr:
             kw.update(max_pos_error=1e30, max_quat_error=1e30, max_joint_error=1e30)
-        env = (B._make if bod else P._make)(model, T, **kw)
+        env = (F.make_body if bod else F.make)(model, T, **kw)
         assert env.observation_size == env.sys.obs_dim + H * env.sys.nq
-        acts, noise = P._draws(env, 7, 2)
-        r = P._wrapped_forms(env, acts, noise, P._actor(env, 7))
-        r.update(env=env, bare_all=P._steps(env, P._draws(env, P.STEPS, 1)[0]))
+        acts, noise = F.draws(env, 7, 2)
+        r = F.wrapped_forms(env, acts, noise, F.actor(env, 7))
+        r.update(env=env, bare_all=F.steps(env, F.draws(env, F.STEPS, 1)[0]))
         r["bare"] = r["bare_all"][-1]
         out[(H, thr, bod)] = r
     return out
@@ -72,7 +70,7 @@ def _assert_states_agree(a, b, D, what, reward):
     if reward:
         pairs.append(("reward", a.reward, b.reward))
     for name, u, v in pairs:
-        lu, lv = P._leaves(u), P._leaves(v)
+        lu, lv = F.leaves(u), F.leaves(v)
         assert len(lu) == len(lv) >= 1, (what, name)
         for i, (x, y) in enumerate(zip(lu, lv)):
             _same(x, y, D, (what, name, i))
@@ -130,3 +128,31 @@ def test_the_fixture_exercises_what_it_compares(model):
     a, b = runs[(5, True, False)], runs[(5, True, True)]
     for f in FORMS:
         assert not torch.equal(a[f].reward, b[f].reward), f
+
+
+def _launch_sequence():
+    """reset, step, reset, wrapped unroll of three (episodes of three: a restore from the bank inside), step -- on one fresh env with every
+    option: (which of the pose, termination, body and restart blocks stand on its batch after each launch, the final state)."""
+    from rodent_amd.envs import wrappers
+    env = F.make_body("rodent_optimized", T, reference_obs_frames=5, max_pos_error=1e30, max_quat_error=1e30, max_joint_error=1e30, clip_restarts=2)
+    wenv, b, acts, stand = wrappers.wrap(env, episode_length=3, action_repeat=1), env._batch, F.draws(env, 5, 4)[0], []
+
+    def seen(state):
+        stand.append(tuple(x is not None for x in (b._pose, b._pterm, b._body, b._restart)))
+        return state
+    s = seen(env.step(seen(env.reset(F.keys(), clip=F.IDS)), acts[0]))
+    s = seen(wenv.unroll(seen(wenv.reset(F.keys(), clip=F.IDS)), acts[1:4].contiguous()))
+    s = seen(env.step(s, acts[4]))
+    torch.cuda.synchronize()
+    return stand, s
+
+
+def test_each_launch_leaves_the_blocks_it_carries_and_the_sequence_replays():
+    """A reset of an env with reference frames hands the pose block alone, a step the pose, termination and body blocks, the multi-step
+    launch all four: every clear and set of `hip.Batch._program_blocks`, both ways; a second fresh env ends in the same state, bit for bit."""
+    (stand, got), (_, want) = _launch_sequence(), _launch_sequence()
+    reset, step, unroll = (True, False, False, False), (True, True, True, False), (True, True, True, True)
+    assert stand == [reset, step, reset, unroll, step]
+    lg, lw = F.leaves(got), F.leaves(want)
+    assert len(lg) == len(lw) > 10 and all(x.shape == y.shape and x.dtype == y.dtype and torch.equal(x, y) for x, y in zip(lg, lw))
+    assert int(got.info["restart_slot"].max()) == 1 and torch.isfinite(got.obs).all()       # the restore ran

@@ -3,7 +3,7 @@ rr_poseterm_kernel instances): the code against the float64 restatements `rodent
 else of the step against a pose env of the same build, bit for bit.
 
 Fixture: that of tests/test_gpu_pose.py (12 envs on 3 clips, n_frames 2, CG 4/4, five steps; rodent_optimized and rodent_0; T = 104 and
-T = 3), whose helpers are imported.
+T = 3), from tests/pose_fixture.py.
 
 THRESHOLDS come from the data, not from the code under test: the existing pose env (no termination) makes five bare steps, `pose_errors`
 gives the 60 (env, step) errors per criterion from the returned qpos, and each threshold stands in the middle of the widest gap between
@@ -17,7 +17,6 @@ Float32 bounds (eps = 2^-24, factor 2 for the slack of a first-order count, as t
   e_quat  = theta: (22 + 4 theta) eps absolute, derived in tests/test_gpu_pose.py::test_against_the_formula -> 2 x (22 + 4 theta) eps.
   e_joint = sqrt(S), S a sum of nq - 7 squares: a difference (eps), its square (3 eps), at most one addition inside a lane and the six of
             the wave sum (7 eps): 10 eps on S, halved by the root, plus sqrtf's 2 eps: 7 eps -> 2 x 7 eps x e_joint."""
-import functools
 import math
 
 import numpy as np
@@ -26,73 +25,32 @@ import torch
 
 from rodent_amd import jax_random
 from rodent_amd.envs import rodent
-from tests import test_gpu_pose as P
+from tests import pose_fixture as F
+from tests.pose_fixture import C, DEV, EPS, FAIL_METRICS, IDS, N, STEPS
 
 pytestmark = pytest.mark.gpu
-DEV = P.DEV
-N, C, STEPS, IDS, EPS = P.N, P.C, P.STEPS, P.IDS, P.EPS
-CASES = [(m, T) for m in P.MODELS for T in (104, 3)]
-POSE_METRICS = P.OLD_METRICS + ("quat_reward", "joint_reward")           # the five metrics a pose env has
-FAIL_METRICS = ("pose_fail", "pose_fail_pos", "pose_fail_quat", "pose_fail_joint")
+CASES = [(m, T) for m in F.MODELS for T in (104, 3)]
+POSE_METRICS = F.OLD_METRICS + ("quat_reward", "joint_reward")           # the five metrics a pose env has
 INF = math.inf
 
 
 # ---------------------------------------------------------------------------------------------- the reference side
-def _errors(env, T, qpos, old_frame):
-    """`pose_errors` (float64) of the returned float32 `qpos` [N, nq] against the float32 rows the device holds, at the clip and the
-    clamped frame the step's rewards read."""
-    fi = np.clip(old_frame.cpu().numpy(), 0, T - 1)
-    rows, tp = env._pose_host.astype(np.float64)[IDS, fi], env._track_host.astype(np.float64)[IDS, fi]
-    return np.stack(rodent.pose_errors(qpos.cpu().numpy().astype(np.float64), tp, rows[:, :4], rows[:, 4:]))       # [3, N]
-
-
-def _bound(e):
-    """Float32 error bounds of the three errors `e` [3, ...] (module docstring)."""
-    return np.stack([2 * 5 * EPS * e[0], 2 * (22 + 4 * e[1]) * EPS, 2 * 7 * EPS * e[2]])
-
-
 def _margin_ok(e, thr, which=(0, 1, 2)):
     """No error of the criteria `which` lies within 100 float32 bounds of its threshold."""
-    b = _bound(e)
+    b = F.term_bound(e)
     return all(bool((np.abs(e[k] - thr[k]) > 100 * b[k]).all()) for k in which if math.isfinite(thr[k]))
 
 
-def _mid_gap(e):
-    """The middle of the widest gap between sorted ranks 15 and 45 of the 60 errors `e`: 15 .. 45 of them lie above it."""
-    s = np.sort(np.asarray(e).ravel())
-    assert s.size == 60
-    i = 14 + int(np.argmax(np.diff(s)[14:45]))                # the gap s[i] .. s[i + 1], i = 14 .. 44: 59 - i = 15 .. 45 values above
-    return 0.5 * (s[i] + s[i + 1])
-
-
-@functools.lru_cache(maxsize=None)
-def _reference(model, T):
-    """Computed once per (model, T) and shared: (pose env, its states of five bare steps, the errors [STEPS, 3, N] of those steps, the
-    three thresholds)."""
-    env, states, _ = P._plain_steps(model, T)
-    errs = np.stack([_errors(env, T, states[t].pipeline_state.qpos, states[t - 1].info["cur_frame"]) for t in range(1, STEPS + 1)])
-    thr = tuple(float(_mid_gap(errs[:, k])) for k in range(3))
-    return env, states, errs, thr
-
-
 def _term_env(model, T, thr, **kw):
-    env = P._make(model, T, max_pos_error=None if math.isinf(thr[0]) else thr[0], max_quat_error=None if math.isinf(thr[1]) else thr[1],
+    env = F.make(model, T, max_pos_error=None if math.isinf(thr[0]) else thr[0], max_quat_error=None if math.isinf(thr[1]) else thr[1],
                   max_joint_error=None if math.isinf(thr[2]) else thr[2], **kw)
     got = env.pose_termination
     assert got is not None and all(a == float(np.float32(b)) for a, b in zip(got, thr))       # what the kernel compares with
     return env
 
 
-def _code_of(state):
-    m = {k: state.metrics[k].cpu().numpy() for k in FAIL_METRICS}
-    code = (m["pose_fail_pos"] + 2 * m["pose_fail_quat"] + 4 * m["pose_fail_joint"]).astype(np.int64)
-    assert np.array_equal(m["pose_fail"], (code != 0).astype(np.float32))
-    assert all(set(np.unique(v)) <= {0.0, 1.0} for v in m.values())
-    return code
-
-
 def _assert_equal_trees(a, b, what):
-    la, lb = P._leaves(a), P._leaves(b)
+    la, lb = F.leaves(a), F.leaves(b)
     assert len(la) == len(lb) >= 1, what
     for i, (x, y) in enumerate(zip(la, lb)):
         assert x.shape == y.shape and x.dtype == y.dtype and torch.equal(x, y), (what, i, int((x != y).sum()))
@@ -109,13 +67,13 @@ def _assert_same_but_done(got, want, what):
 # ---------------------------------------------------------------------------------------------- 0. the fixture's own condition
 @pytest.mark.parametrize("model,T", CASES)
 def test_the_thresholds_stand_clear_of_every_error(model, T):
-    _, _, errs, thr = _reference(model, T)
+    _, _, errs, thr = F.term_reference(model, T)
     e = errs.transpose(1, 0, 2).reshape(3, -1)
     for k, name in enumerate(("e_pos", "e_quat", "e_joint")):
         fires = int((e[k] > thr[k]).sum())
         nearest = float(np.abs(e[k] - thr[k]).min())
         print(f"{model} T={T}: {name} in [{e[k].min():.4g}, {e[k].max():.4g}], threshold {thr[k]:.6g}, fires in {fires} of 60, nearest error "
-              f"{nearest:.3g} away = {nearest / float(_bound(e)[k].max()):.0f} float32 bounds")
+              f"{nearest:.3g} away = {nearest / float(F.term_bound(e)[k].max()):.0f} float32 bounds")
         assert 15 <= fires <= 45
     assert _margin_ok(e, thr)
 
@@ -127,14 +85,14 @@ def test_bare_steps_raise_done_and_nothing_else(model, T, which):
     """Five bare steps with all three thresholds, and with each alone (the other two off: only its bit appears): the code is
     `pose_fail_code` of the float64 errors for all 60 pairs, done = max(the pose env's done, code != 0), and the rest of the state is
     the pose env's in every bit."""
-    _, want, errs, thr = _reference(model, T)
+    _, want, errs, thr = F.term_reference(model, T)
     assert _margin_ok(errs.transpose(1, 0, 2).reshape(3, -1), thr)
     on = {"all": (0, 1, 2), "pos": (0,), "quat": (1,), "joint": (2,)}[which]
     use = tuple(thr[k] if k in on else INF for k in range(3))
     env = _term_env(model, T, use)
     assert env.pose_tracking and not env.eval_supported()
-    acts, _ = P._draws(env, STEPS, 1)
-    got = P._steps(env, acts)
+    acts, _ = F.draws(env, STEPS, 1)
+    got = F.steps(env, acts)
     assert all(float(got[0].metrics[k].abs().max()) == 0.0 for k in FAIL_METRICS)       # zeros at reset
     _assert_same_but_done(got[0], want[0], (model, T, which, 0))
     assert torch.equal(got[0].done, want[0].done)
@@ -142,7 +100,7 @@ def test_bare_steps_raise_done_and_nothing_else(model, T, which):
     for t in range(1, STEPS + 1):
         _assert_same_but_done(got[t], want[t], (model, T, which, t))
         code = rodent.pose_fail_code(errs[t - 1], env.pose_termination)
-        assert np.array_equal(_code_of(got[t]), code), (model, T, which, t, _code_of(got[t]), code)
+        assert np.array_equal(F.code_of(got[t]), code), (model, T, which, t, F.code_of(got[t]), code)
         assert np.array_equal(got[t].done.cpu().numpy(), np.maximum(want[t].done.cpu().numpy(), (code != 0).astype(np.float32))), (model, T, which, t)
         seen |= set(code.tolist())
     allowed = set(range(8)) if which == "all" else {0, 1 << on[0]}
@@ -154,11 +112,11 @@ def test_bare_steps_raise_done_and_nothing_else(model, T, which):
 # ---------------------------------------------------------------------------------------------- 2. off / next to the reference observation
 @pytest.mark.parametrize("model,T", CASES)
 def test_all_thresholds_none_is_the_pose_env(model, T):
-    _, want, _, _ = _reference(model, T)
-    env = P._make(model, T, max_pos_error=None, max_quat_error=None, max_joint_error=INF)
+    _, want, _, _ = F.term_reference(model, T)
+    env = F.make(model, T, max_pos_error=None, max_quat_error=None, max_joint_error=INF)
     assert env.pose_termination is None
-    acts, _ = P._draws(env, STEPS, 1)
-    got = P._steps(env, acts)
+    acts, _ = F.draws(env, STEPS, 1)
+    got = F.steps(env, acts)
     assert env._batch._pterm is None and env._batch._pose is not None           # no termination block on the batch: its launches pick the pose instances
     for t, (g, w) in enumerate(zip(got, want)):
         assert set(g.metrics) == set(w.metrics)
@@ -169,17 +127,17 @@ def test_all_thresholds_none_is_the_pose_env(model, T):
 def test_one_threshold_next_to_five_reference_frames(model, T):
     """H = 5 with one finite threshold: the whole row, reference blocks included, is the reference-observation env's in every bit -- at
     reset (served by the instance a reset runs without the block) and after every step -- and the code is the restatement's."""
-    _, _, errs, thr = _reference(model, T)
-    ref_env = P._make(model, T, reference_obs_frames=5)
+    _, _, errs, thr = F.term_reference(model, T)
+    ref_env = F.make(model, T, reference_obs_frames=5)
     env = _term_env(model, T, (INF, INF, thr[2]), reference_obs_frames=5)
     assert env.observation_size == env.sys.obs_dim + 5 * env.sys.nq
-    acts, _ = P._draws(env, STEPS, 1)
-    got, want = P._steps(env, acts), P._steps(ref_env, acts)
+    acts, _ = F.draws(env, STEPS, 1)
+    got, want = F.steps(env, acts), F.steps(ref_env, acts)
     for t in range(STEPS + 1):
         _assert_same_but_done(got[t], want[t], (model, T, t))
         assert got[t].obs.shape == (N, env.observation_size)
         if t:
-            assert np.array_equal(_code_of(got[t]), rodent.pose_fail_code(errs[t - 1], env.pose_termination)), (model, T, t)
+            assert np.array_equal(F.code_of(got[t]), rodent.pose_fail_code(errs[t - 1], env.pose_termination)), (model, T, t)
 
 
 # ---------------------------------------------------------------------------------------------- 3. wrapped forms
@@ -208,13 +166,13 @@ def test_wrapped_forms_terminate_and_restore(model, T):
     the margin condition is asserted on this walk too).  The composed wrappers, driven step by step with the stepped qpos recorded before
     the restore, against the float64 code; the fused per-step wrapper and `unroll_wrapped` against the composition, bit for bit."""
     from rodent_amd.envs import wrappers
-    _, _, _, thr = _reference(model, T)
+    _, _, _, thr = F.term_reference(model, T)
     env = _term_env(model, T, (INF, thr[1], INF))
     use = env.pose_termination
-    acts, _ = P._draws(env, 6, 2)
+    acts, _ = F.draws(env, 6, 2)
     rec = _Recorder(wrappers.EpisodeWrapper(wrappers.VmapWrapper(env), 4, 1))
     comp = wrappers.AutoResetWrapper(rec)
-    s = comp.reset(P._keys(), clip=IDS)
+    s = comp.reset(F.keys(), clip=IDS)
     first = s
     walk = [s]
     steps = np.zeros(N, np.float32)
@@ -226,11 +184,11 @@ def test_wrapped_forms_terminate_and_restore(model, T):
         walk.append(s.replace(info=dict(s.info)))           # (AutoReset's next step edits the incoming info dict in place)
         torch.cuda.synchronize()
         before, qpos, done, trunc, nsteps = rec.seen[-1]
-        e = _errors(env, T, qpos, before)
+        e = F.term_errors(env, T, qpos, before)
         assert _margin_ok(e, use), (model, T, t, e[1], use[1])
         code = rodent.pose_fail_code(e, use)
         assert set(code.tolist()) <= {0, 2}
-        assert np.array_equal(_code_of(s), code), (model, T, t)
+        assert np.array_equal(F.code_of(s), code), (model, T, t)
         z = qpos[:, 2].cpu().numpy()
         own = ((z < z_min) | (z > z_max)).astype(np.float32)                          # the env's own done (terminate_when_unhealthy)
         done_env = np.maximum(own, (code != 0).astype(np.float32))
@@ -256,14 +214,14 @@ def test_wrapped_forms_terminate_and_restore(model, T):
     assert failed >= 1 and ran_out >= 1
     fused = wrappers.wrap(env, episode_length=4, action_repeat=1)
     assert isinstance(fused, wrappers.FusedEpisodeAutoResetWrapper)
-    f = fused.reset(P._keys(), clip=IDS)
+    f = fused.reset(F.keys(), clip=IDS)
     for t in range(6):
         f = fused.step(f, acts[t])
         for name in ("pipeline_state", "obs", "reward", "done", "metrics"):
             _assert_equal_trees(getattr(f, name), getattr(walk[t + 1], name), (model, T, "fused step", t, name))
         for k in ("cur_frame", "steps", "truncation"):
             assert torch.equal(f.info[k], walk[t + 1].info[k]), (model, T, "fused step", t, k)
-    u = fused.unroll(fused.reset(P._keys(), clip=IDS), acts)
+    u = fused.unroll(fused.reset(F.keys(), clip=IDS), acts)
     torch.cuda.synchronize()
     for name in ("pipeline_state", "obs", "reward", "done", "metrics"):
         _assert_equal_trees(getattr(u, name), getattr(walk[-1], name), (model, T, "unroll", name))
@@ -280,19 +238,19 @@ def test_the_actor_inside_terminates_like_the_replay(model, T):
     tests/test_gpu_ppo.py allows the actor instance."""
     from rodent_amd.envs import wrappers
     from rodent_amd.training import acting
-    _, _, _, thr = _reference(model, T)
+    _, _, _, thr = F.term_reference(model, T)
     env = _term_env(model, T, (INF, thr[1], INF), terminate_when_unhealthy=False)
     Wd, A = env.observation_size, env.action_size
-    actor = P._actor(env, 7)
+    actor = F.actor(env, 7)
     wenv = wrappers.wrap(env, episode_length=4, action_repeat=1)
     assert env._batch.pose_termination_supported(with_actor=True) is None
-    _, noise = P._draws(env, 6, 3)
+    _, noise = F.draws(env, 6, 3)
     buf = acting.UnrollBuffer(2, N, 3, Wd, A, torch.device(DEV))
     traj = dict(obs=buf.obs, raw_action=buf.raw_action, log_prob=buf.log_prob, reward=buf.reward, discount=buf.discount, truncation=buf.truncation)
-    got, actions = wenv.unroll_policy(wenv.reset(P._keys(), clip=IDS), actor, noise, traj, segment=3)
+    got, actions = wenv.unroll_policy(wenv.reset(F.keys(), clip=IDS), actor, noise, traj, segment=3)
     torch.cuda.synchronize()
     assert torch.isfinite(buf.obs).all() and torch.isfinite(buf.reward).all()
-    st = wenv.reset(P._keys(), clip=IDS)
+    st = wenv.reset(F.keys(), clip=IDS)
     by_clip = 0
     worst = 0.0
     for s in range(6):
@@ -308,7 +266,7 @@ def test_the_actor_inside_terminates_like_the_replay(model, T):
         assert torch.equal(st.metrics["pose_fail"], st.metrics["pose_fail_quat"])
         by_clip += int(ended.sum())
     print(f"{model} T={T}: {by_clip} (env, step) pairs ended by the clip inside the launch; max |traj.reward - replay| = {worst:.3g}")
-    assert worst <= P.ACTOR_REWARD_TOL
+    assert worst <= F.ACTOR_REWARD_TOL
     assert by_clip >= 1
     _assert_equal_trees(got.pipeline_state, st.pipeline_state, (model, T, "final state"))
     assert torch.equal(got.obs, st.obs) and torch.equal(got.done, st.done) and torch.equal(got.info["steps"], st.info["steps"])
@@ -317,11 +275,11 @@ def test_the_actor_inside_terminates_like_the_replay(model, T):
 
 
 # ---------------------------------------------------------------------------------------------- 5. bad state
-@pytest.mark.parametrize("model", P.MODELS)
+@pytest.mark.parametrize("model", F.MODELS)
 def test_a_bad_step_is_done_with_code_zero(model):
     from rodent_amd.envs import wrappers
     from rodent_amd.training import acting
-    _, _, _, thr = _reference(model, 104)
+    _, _, _, thr = F.term_reference(model, 104)
     env = _term_env(model, 104, thr, bad_state_max=1e10)
     bad = 4
 
@@ -329,17 +287,17 @@ def test_a_bad_step_is_done_with_code_zero(model):
         qvel = state.pipeline_state.qvel.clone()
         qvel[bad, 3] = float("nan")
         return state.replace(pipeline_state=state.pipeline_state.replace(qvel=qvel))
-    acts, noise = P._draws(env, 1, 3)
+    acts, noise = F.draws(env, 1, 3)
     wenv = wrappers.wrap(env, episode_length=100, action_repeat=1)
     buf = acting.UnrollBuffer(1, N, 1, env.observation_size, env.action_size, torch.device(DEV))
-    res = dict(step=env.step(poison(env.reset(P._keys(), clip=IDS)), acts[0]), unroll=wenv.unroll(poison(wenv.reset(P._keys(), clip=IDS)), acts),
-               policy=wenv.unroll_policy(poison(wenv.reset(P._keys(), clip=IDS)), P._actor(env, 5), noise, P._traj(buf))[0])
+    res = dict(step=env.step(poison(env.reset(F.keys(), clip=IDS)), acts[0]), unroll=wenv.unroll(poison(wenv.reset(F.keys(), clip=IDS)), acts),
+               policy=wenv.unroll_policy(poison(wenv.reset(F.keys(), clip=IDS)), F.actor(env, 5), noise, F.traj(buf))[0])
     torch.cuda.synchronize()
     for k, s in res.items():
         assert float(s.done[bad]) == 1.0 and float(s.reward[bad]) == 0.0, (model, k)
         for name in FAIL_METRICS:
             assert float(s.metrics[name][bad]) == 0.0, (model, k, name)
-        code = _code_of(s)
+        code = F.code_of(s)
         assert code[bad] == 0 and bool((s.done.cpu().numpy()[code != 0] == 1.0).all()), (model, k)          # the others: ended where their code says so
     assert float(buf.discount[0, bad, 0]) == 0.0 and float(buf.truncation[0, bad, 0]) == 0.0
     assert env.bad_states() == 3
@@ -348,10 +306,10 @@ def test_a_bad_step_is_done_with_code_zero(model):
 # ---------------------------------------------------------------------------------------------- 6. refusals
 def test_refusals():
     from rodent_amd import envs
-    track = P._tracks(104)[0]
+    track = F.tracks(104)[0]
 
     def build(model, pose=True, **kw):
-        q0 = P._qpos0(model)
+        q0 = F.qpos0(model)
         if pose:
             kw.update(track_quat=np.tile([1.0, 0.0, 0.0, 0.0], (104, 1)), track_joints=np.tile(q0[7:], (104, 1)))
         return envs.get_environment("rodent", track_pos=track, num_envs=4, xml_path=f"{model}.xml", iterations=4, ls_iterations=4, n_frames=2,
@@ -389,7 +347,7 @@ def test_refusals():
     st = env.step(env.reset(keys), torch.zeros(4, env.action_size, device=DEV))            # the env-io dict sets both blocks again
     assert float(st.metrics["pose_fail"].max()) == 0.0 and b._pterm is not None
     with pytest.raises(RuntimeError, match="no evaluation instance"):
-        env.unroll_eval(env.reset(keys), 2, P._actor(env, 1))
+        env.unroll_eval(env.reset(keys), 2, F.actor(env, 1))
 
 
 # ---------------------------------------------------------------------------------------------- 7. training
@@ -399,7 +357,7 @@ def test_ppo_train_with_pose_termination(monkeypatch):
     ended -- finite and in [0, 1]."""
     from rodent_amd.training import acting
     from rodent_amd.training.agents.ppo import train as ppo
-    _, _, _, thr = _reference("rodent_optimized", 104)
+    _, _, _, thr = F.term_reference("rodent_optimized", 104)
     env = _term_env("rodent_optimized", 104, (INF, thr[1], INF), n=64)
     calls, log = {"fused": 0}, []
     real_fused = acting.generate_unrolls_fused

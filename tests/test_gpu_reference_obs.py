@@ -2,7 +2,7 @@
 every observation row carries the clip's next H frames behind the model's obs_dim entries.  Held against a pose env with H = 0 of the same
 build -- bit for bit in everything but the new columns -- and against the float64 restatement `rodent.reference_obs`.
 
-Fixture (tests/test_gpu_pose.py's, rebuilt here): N = 12 envs, C = 3 clips, env e on clip e % 3 (explicit ids); n_frames = 2, solver
+Fixture (tests/pose_fixture.py's; the reference, env builder, actor and step loop are its own): N = 12 envs, C = 3 clips, env e on clip e % 3 (explicit ids); n_frames = 2, solver
 iterations 4 / 4, five steps.  T = 104 (start frames 0 .. 99: the two envs that start at frame 99 read past the clip's end) and T = 3
 (every read clamps); H = 1 and H = 5.  Reference pose: the quaternion of clip c at frame t is a rotation about z by 0.1 (c + 1) + 0.003 t,
 the joints are qpos0[7:] + 0.02 sin(0.7 j + 0.05 t + c); the quaternions of clip 1 are NEGATED, so the sign rule of q_h runs in both
@@ -14,32 +14,17 @@ import numpy as np
 import pytest
 import torch
 
-from rodent_amd import assets, jax_random, mjcf
+from rodent_amd import jax_random
 from rodent_amd.envs import rodent
+from tests.pose_fixture import C, DEV, EPS, IDS, MODELS, N, STEPS, draws, keys, leaves, qpos0, tracks
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-N, C, STEPS = 12, 3, 5
-SEED = 78            # start frames [42, 99, 35, 32, 33, 99, 10, 46, 47, 47, 19, 51]
-IDS = np.arange(N) % C
-MODELS = ["rodent_optimized", "rodent_0"]
-EPS = 2.0 ** -24
 CASES = [(m, T, H) for m in MODELS for T in (104, 3) for H in (1, 5)]
-
-
-def _tracks(T):
-    t = np.arange(T, dtype=np.float64)
-    return np.stack([np.stack([0.004 * t, np.full(T, 0.1 * c), np.full(T, 0.0681 + 0.002 * c)], axis=1) for c in range(C)])
-
-
-@functools.lru_cache(maxsize=None)
-def _qpos0(model):
-    return mjcf.load_blob(assets.asset_path(model))["qpos0"].astype(np.float64)
 
 
 def _reference(model, T):
     """(quat [C, T, 4], joints [C, T, nq - 7]) of the fixture, float64; clip 1's quaternions negated."""
-    q0 = _qpos0(model)
+    q0 = qpos0(model)
     t, c, j = np.arange(T, dtype=np.float64), np.arange(C, dtype=np.float64), np.arange(len(q0) - 7, dtype=np.float64)
     ang = 0.1 * (c[:, None] + 1) + 0.003 * t[None]
     quat = np.stack([np.cos(ang / 2), np.zeros_like(ang), np.zeros_like(ang), np.sin(ang / 2)], axis=-1)
@@ -55,18 +40,8 @@ def _make(model, T, H=0, n=N, pose=True, n_frames=2, **kw):
         kw.update(track_quat=quat, track_joints=joints, quat_reward_weight=0.75, quat_reward_scale=5.0, joint_reward_weight=0.5, joint_reward_scale=0.6)
     if H:
         kw["reference_obs_frames"] = H
-    return envs.get_environment("rodent", track_pos=_tracks(T), num_envs=n, xml_path=f"{model}.xml", iterations=4, ls_iterations=4, n_frames=n_frames,
+    return envs.get_environment("rodent", track_pos=tracks(T), num_envs=n, xml_path=f"{model}.xml", iterations=4, ls_iterations=4, n_frames=n_frames,
                                 device=DEV, **kw)
-
-
-def _keys():
-    return jax_random.split(jax_random.PRNGKey(SEED), N)
-
-
-def _draws(env, T, seed):
-    gen = torch.Generator(device=DEV).manual_seed(seed)
-    A = env.action_size
-    return torch.rand(T, N, A, device=DEV, generator=gen) * 2 - 1, torch.randn(T, N, A, device=DEV, generator=gen)
 
 
 def _actor(env, seed):
@@ -88,7 +63,7 @@ def _actor(env, seed):
 def _steps(env, acts, pre=None):
     """The reset state and the state after each plain `step`.  `pre` (an env of n_frames = 1): also the qpos after the FIRST substep of
     every step, which is what the last forward pass of the two-substep step sees (list aligned with the states; entry 0 is None)."""
-    out, first = [env.reset(_keys(), clip=IDS)], [None]
+    out, first = [env.reset(keys(), clip=IDS)], [None]
     for t in range(acts.shape[0]):
         if pre is not None:
             first.append(pre.step(out[-1], acts[t]).pipeline_state.qpos)
@@ -101,14 +76,14 @@ def _steps(env, acts, pre=None):
 def _base_steps(model, T):
     """Shared by the H cases of (model, T): the H = 0 pose env's states of five plain steps, and the qpos after the first substep of each."""
     env = _make(model, T)
-    acts, _ = _draws(env, STEPS, 1)
+    acts, _ = draws(env, STEPS, 1)
     return _steps(env, acts, _make(model, T, pose=False, n_frames=1))
 
 
 @functools.lru_cache(maxsize=None)
 def _ref_steps(model, T, H):
     env = _make(model, T, H)
-    acts, _ = _draws(env, STEPS, 1)
+    acts, _ = draws(env, STEPS, 1)
     return env, _steps(env, acts)[0]
 
 
@@ -116,11 +91,11 @@ def _wrapped(env, acts):
     """Under Episode(3) + AutoReset: the states of wrapped single steps, and the state `unroll` leaves."""
     from rodent_amd.envs import wrappers
     wenv = wrappers.wrap(env, episode_length=3, action_repeat=1)
-    steps = [wenv.reset(_keys(), clip=IDS)]
+    steps = [wenv.reset(keys(), clip=IDS)]
     for t in range(acts.shape[0]):
         steps.append(wenv.step(steps[-1], acts[t]))
-    unroll = wenv.unroll(wenv.reset(_keys(), clip=IDS), acts)
-    unroll3 = wenv.unroll(wenv.reset(_keys(), clip=IDS), acts[:3].contiguous())
+    unroll = wenv.unroll(wenv.reset(keys(), clip=IDS), acts)
+    unroll3 = wenv.unroll(wenv.reset(keys(), clip=IDS), acts[:3].contiguous())
     torch.cuda.synchronize()
     return dict(steps=steps, unroll=unroll, unroll3=unroll3)
 
@@ -128,24 +103,19 @@ def _wrapped(env, acts):
 @functools.lru_cache(maxsize=None)
 def _base_wrapped(model, T):
     env = _make(model, T)
-    return _wrapped(env, _draws(env, STEPS, 2)[0])
+    return _wrapped(env, draws(env, STEPS, 2)[0])
 
 
 @functools.lru_cache(maxsize=None)
 def _ref_wrapped(model, T, H):
     env = _make(model, T, H)
-    return env, _wrapped(env, _draws(env, STEPS, 2)[0])
-
-
-def _leaves(x):
-    from rodent_amd.envs import graphed
-    return graphed.tree_leaves(x)
+    return env, _wrapped(env, draws(env, STEPS, 2)[0])
 
 
 def _assert_same_but_the_blocks(got, want, K, Wd, what):
     """Every leaf of the two states bit for bit; a leaf that is an observation (last axis Wd wide in `got`, K in `want`: obs, first_obs)
     in its first K columns."""
-    la, lb = _leaves(got), _leaves(want)
+    la, lb = leaves(got), leaves(want)
     assert len(la) == len(lb) > 10, (what, len(la), len(lb))
     wide = 0
     for i, (x, y) in enumerate(zip(la, lb)):
@@ -257,7 +227,7 @@ def test_blocks_against_the_float64_restatement(model, T, H):
 def test_single_step_and_multi_step_agree_and_restores_are_verbatim(model, T, H):
     env, f = _ref_wrapped(model, T, H)
     a, b = f["steps"][-1], f["unroll"]
-    la, lb = _leaves(a), _leaves(b)
+    la, lb = leaves(a), leaves(b)
     assert len(la) == len(lb) > 10
     for i, (x, y) in enumerate(zip(la, lb)):
         assert x.shape == y.shape and torch.equal(x, y), (model, T, H, i)
@@ -290,18 +260,18 @@ def test_the_actor_inside_reads_the_whole_row(model, T, H):
     actor, net, norm, dist = _actor(env, 7)
     wenv = wrappers.wrap(env, episode_length=3, action_repeat=1)
     assert acting.fused_unroll_supported(wenv, net, dist) and env._batch.reference_obs_supported(H, with_actor=True) is None
-    _, noise = _draws(env, 6, 3)
+    _, noise = draws(env, 6, 3)
 
     def launch(act):
         buf = acting.UnrollBuffer(2, N, 3, Wd, A, torch.device(DEV))
         traj = dict(obs=buf.obs, raw_action=buf.raw_action, log_prob=buf.log_prob, reward=buf.reward, discount=buf.discount, truncation=buf.truncation)
-        st, actions = wenv.unroll_policy(wenv.reset(_keys(), clip=IDS), act, noise, traj, segment=3)
+        st, actions = wenv.unroll_policy(wenv.reset(keys(), clip=IDS), act, noise, traj, segment=3)
         torch.cuda.synchronize()
         return buf, st, actions
     buf, got, actions = launch(actor)
     assert torch.isfinite(buf.obs).all() and torch.isfinite(buf.log_prob).all() and buf.obs.shape == (2, N, 4, Wd)
     # (1)
-    st = wenv.reset(_keys(), clip=IDS)
+    st = wenv.reset(keys(), clip=IDS)
     for s in range(6):
         assert torch.equal(buf.obs[s // 3, :, s % 3], st.obs), (model, T, H, s)
         st = wenv.step(st, actions[s])
@@ -365,15 +335,15 @@ def test_refusals():
     actor, net, _, dist = _actor(env6, 2)
     wenv6 = wrappers.wrap(env6, episode_length=3, action_repeat=1)
     assert not acting.fused_unroll_supported(wenv6, net, dist)
-    acts, noise = _draws(env6, 2, 4)
-    s = wenv6.step(wenv6.reset(_keys(), clip=IDS), acts[0])                        # `step` works
+    acts, noise = draws(env6, 2, 4)
+    s = wenv6.step(wenv6.reset(keys(), clip=IDS), acts[0])                        # `step` works
     assert s.obs.shape == (N, W6) and torch.isfinite(s.obs).all()
-    u = wenv6.unroll(wenv6.reset(_keys(), clip=IDS), acts[:1].contiguous())
+    u = wenv6.unroll(wenv6.reset(keys(), clip=IDS), acts[:1].contiguous())
     assert torch.equal(u.obs, s.obs)
     buf = acting.UnrollBuffer(1, N, 2, W6, env6.action_size, torch.device(DEV))
     traj = dict(obs=buf.obs[0], raw_action=buf.raw_action[0], log_prob=buf.log_prob[0], reward=buf.reward[0], discount=buf.discount[0], truncation=buf.truncation[0])
     with pytest.raises(RuntimeError, match="wider than 1664"):
-        wenv6.unroll_policy(wenv6.reset(_keys(), clip=IDS), actor, noise, traj)
+        wenv6.unroll_policy(wenv6.reset(keys(), clip=IDS), actor, noise, traj)
     torch.cuda.synchronize()
 
 
@@ -420,10 +390,10 @@ def test_a_bad_step_ends_the_episode_and_the_restored_row_is_finite(model):
         qvel = state.pipeline_state.qvel.clone()
         qvel[bad, 3] = float("nan")
         return state.replace(pipeline_state=state.pipeline_state.replace(qvel=qvel))
-    acts, _ = _draws(env, 1, 3)
+    acts, _ = draws(env, 1, 3)
     wenv = wrappers.wrap(env, episode_length=100, action_repeat=1)
-    s = env.step(poison(env.reset(_keys(), clip=IDS)), acts[0])
-    w0 = wenv.reset(_keys(), clip=IDS)
+    s = env.step(poison(env.reset(keys(), clip=IDS)), acts[0])
+    w0 = wenv.reset(keys(), clip=IDS)
     u = wenv.unroll(poison(w0), acts)
     torch.cuda.synchronize()
     ok = [e for e in range(N) if e != bad]
