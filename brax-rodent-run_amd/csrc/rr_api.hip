@@ -409,12 +409,14 @@ struct rr_batch {
   rr_body_io body = {};                 // body tracking of the env steps (rr_batch_set_body_tracking); track_bodies null: off; set only with a pose block
   rr_clip_restart_io restart = {};      // clip restarts of the multi-step launches (rr_batch_set_clip_restarts); frames null: off; set only with a pose block
   bool solve_lds = false;               // rr_batch_set_solve_resident(b, 0): production single-step launches run rr_matlds_kernel
+  rr_vel_io vel = {};                   // velocity tracking of the env steps (rr_batch_set_velocity_tracking); track_vel null: off; set only with a pose block
   bool has_env_params() const { return env_dof_f || env_act_f || env_con_f; }
 };
 
 static const char* pose_eval_refusal(const rr_batch* b) {
   if (b && b->restart.frames) return "rr_env_unroll_eval: no evaluation instance restores from the bank of start states (rr_batch_set_clip_restarts is on); evaluate step by step";
   if (b && b->body.track_bodies) return "rr_env_unroll_eval: no evaluation instance rewards the body positions (rr_batch_set_body_tracking is on); evaluate step by step";
+  if (b && b->vel.track_vel) return "rr_env_unroll_eval: no evaluation instance rewards the velocities (rr_batch_set_velocity_tracking is on); evaluate step by step";
   if (b && b->pterm.fail) return "rr_env_unroll_eval: no evaluation instance ends episodes on the pose error (rr_batch_set_pose_termination is on); evaluate step by step";
   if (b && b->ref_frames > 0) return "rr_env_unroll_eval: no evaluation instance writes the reference observation (rr_batch_set_reference_obs is on); evaluate step by step";
   return "rr_env_unroll_eval: no evaluation instance rewards the pose (this env io carries track_pose); evaluate step by step";
@@ -694,18 +696,20 @@ static int launch(rr_batch* b, const Launch& L) {
   // pose tracking (rr_batch_set_pose): an env step's reward terms -- a reset has no reward and ignores the block -- served by the POSE
   // instance of the same launch form; shared tables, production instances only.  The options on top of the block:
   //   reference frames (rr_batch_set_reference_obs): env steps AND resets write the blocks, and every row is obs_width() wide;
-  //   pose termination (rr_batch_set_pose_termination) and body tracking (rr_batch_set_body_tracking): env steps only -- a reset has
-  //   neither done nor reward and stays on the variant it uses without them;
+  //   pose termination (rr_batch_set_pose_termination), body tracking (rr_batch_set_body_tracking) and velocity tracking
+  //   (rr_batch_set_velocity_tracking): env steps only -- a reset has neither done nor reward and stays on the variant it uses without them;
   //   clip restarts (rr_batch_set_clip_restarts): the multi-step launches of the training wrappers only -- single steps have no restore
   //   in the kernel, the evaluation form none from a bank.
-  // Any of the first three selects V_BODY, clip restarts V_RESTART (rr_kernel.h rr_body_kernel: one instance for every combination);
-  // an env step with a termination block and no body block runs V_POSETERM, the same computation without the body code.  An option the
-  // batch does not carry reaches the kernel as zero frames, thresholds that no error exceeds with a null pose_fail, a null track_bodies
+  // Any of the first four selects V_BODY, clip restarts V_RESTART (rr_kernel.h rr_body_kernel: one instance for every combination);
+  // an env step with a termination block and neither a body nor a velocity block runs V_POSETERM, the same computation without the
+  // `if (BODY)` code.  An option the batch does not carry reaches the kernel as zero frames, thresholds that no error exceeds with a
+  // null pose_fail, a null track_bodies, a null track_vel
   const bool pose_step = b->pose.track_pose && L.env && L.mode == 1;
   const bool refobs = b->ref_frames > 0 && b->pose.track_pose && L.env;
   const bool pose = pose_step || refobs;
   const bool pterm = b->pterm.fail && pose_step, body = b->body.track_bodies && pose_step, restart = b->restart.frames && pose_step && L.un && !L.ev;
-  const bool options = refobs || pterm || body || restart;
+  const bool vel = b->vel.track_vel && pose_step;
+  const bool options = refobs || pterm || body || restart || vel;
   if (options) io.pose_max_pos = io.pose_max_quat = io.pose_max_joint = INFINITY;
   if (refobs) io.ref_frames = b->ref_frames;
   if (restart) {
@@ -716,6 +720,11 @@ static int launch(rr_batch* b, const Launch& L) {
     io.track_bodies = b->body.track_bodies; io.body_weights = b->body.body_weights; io.body_metrics = b->body.body_metrics;
     io.body_w = b->body.body_reward_weight; io.body_k = b->body.body_reward_scale; io.endeff_w = b->body.endeff_reward_weight; io.endeff_k = b->body.endeff_reward_scale;
   }
+  if (vel) {
+    io.track_vel = b->vel.track_vel; io.vel_metrics = b->vel.vel_metrics;
+    io.vel_lin_w = b->vel.lin_weight; io.vel_lin_k = b->vel.lin_scale; io.vel_ang_w = b->vel.ang_weight; io.vel_ang_k = b->vel.ang_scale;
+    io.vel_joint_w = b->vel.joint_weight; io.vel_joint_k = b->vel.joint_scale;
+  }
   if (pterm) { io.pose_fail = b->pterm.fail; io.pose_max_pos = b->pterm.max_pos; io.pose_max_quat = b->pterm.max_quat; io.pose_max_joint = b->pterm.max_joint; }
   if (pose) {
     io.track_pose = b->pose.track_pose; io.pose_metrics = b->pose.pose_metrics;
@@ -724,7 +733,7 @@ static int launch(rr_batch* b, const Launch& L) {
   }
   if (pose && params) return fail(RR_EUNSUPPORTED, "launch: pose tracking: no pose instance reads per-env parameters (this batch carries some)");
   if (pose && (io.dbg || geom || b->prof)) return fail(RR_EUNSUPPORTED, "launch: pose tracking: no debug dump, contact-geometry outputs or profile build with track_pose (diagnostic instances have no pose form)");
-  Variant v = b->prof ? V_PROFILE : ((io.dbg || geom) ? V_DEBUG : (params ? V_RAND : (restart ? V_RESTART : (pterm && !body ? V_POSETERM : (options ? V_BODY : (pose ? V_POSE : V_PROD))))));
+  Variant v = b->prof ? V_PROFILE : ((io.dbg || geom) ? V_DEBUG : (params ? V_RAND : (restart ? V_RESTART : (pterm && !body && !vel ? V_POSETERM : (options ? V_BODY : (pose ? V_POSE : V_PROD))))));
   // two-tree model, physics only, no diagnostics: one wavefront per replica (rr_kernel.h PAIR)
   const bool pair = m->pair_ok && v == V_PROD && !L.env && !L.out && !L.un && !b->env_map && !b->cost && m->solver != 2;
   if (pair) v = V_PAIR;
@@ -812,7 +821,7 @@ extern "C" int rr_env_unroll_policy(rr_batch* b, const rr_state* in, const rr_st
 }
 extern "C" int rr_batch_eval_supported(const rr_batch* b) {
   if (!b) return fail(RR_EINVAL, "rr_batch_eval_supported: null batch");
-  const bool options = b->ref_frames > 0 || b->pterm.fail || b->body.track_bodies || b->restart.frames;      // of the pose family: none has an evaluation instance
+  const bool options = b->ref_frames > 0 || b->pterm.fail || b->body.track_bodies || b->restart.frames || b->vel.track_vel;      // of the pose family: none has an evaluation instance
   const Variant v = b->prof ? V_PROFILE : (b->has_env_params() ? V_RAND : (options ? V_BODY : V_PROD));
   return (select(b->m, F_EVAL, v, b).kern && !actor_limit(b->m, nullptr)) ? 1 : 0;
 }
@@ -1465,6 +1474,7 @@ extern "C" int rr_batch_set_pose(rr_batch* b, const rr_pose_io* p) {
   if (!p || (!p->track_pose && !p->pose_metrics)) {
     if (b->ref_frames > 0) return fail(RR_EINVAL, "rr_batch_set_pose: the batch carries reference frames (rr_batch_set_reference_obs), whose rows come from the pose block: set them to 0 first");
     if (b->restart.frames) return fail(RR_EINVAL, "rr_batch_set_pose: the batch carries a clip-restart block (rr_batch_set_clip_restarts), which serves pose envs only: clear it first");
+    if (b->vel.track_vel) return fail(RR_EINVAL, "rr_batch_set_pose: the batch carries a velocity-tracking block (rr_batch_set_velocity_tracking), whose rows are indexed like the pose block's: clear it first");
     if (b->body.track_bodies) return fail(RR_EINVAL, "rr_batch_set_pose: the batch carries a body-tracking block (rr_batch_set_body_tracking), whose rows are indexed like the pose block's: clear it first");
     if (b->pterm.fail) return fail(RR_EINVAL, "rr_batch_set_pose: the batch carries a pose-termination block (rr_batch_set_pose_termination), whose errors come from the pose block: clear it first");
     b->pose = rr_pose_io{};
@@ -1530,6 +1540,21 @@ extern "C" int rr_batch_set_body_tracking(rr_batch* b, const rr_body_io* t) {
   for (float x : {t->body_reward_weight, t->body_reward_scale, t->endeff_reward_weight, t->endeff_reward_scale})
     if (!(x >= 0.0f) || !std::isfinite(x)) return fail(RR_EINVAL, "rr_batch_set_body_tracking: weights and scales must be finite and >= 0");
   b->body = *t;
+  return RR_OK;
+}
+extern "C" int rr_batch_velocity_tracking_supported(const rr_batch* b, int32_t with_actor) {
+  if (!b) return fail(RR_EINVAL, "rr_batch_velocity_tracking_supported: null batch");
+  return supported("rr_batch_velocity_tracking_supported", pose_option_limit(b, F_STEP, b->ref_frames, with_actor != 0));
+}
+extern "C" int rr_batch_set_velocity_tracking(rr_batch* b, const rr_vel_io* t) {
+  if (!b) return fail(RR_EINVAL, "rr_batch_set_velocity_tracking: null batch");
+  if (!t) { b->vel = rr_vel_io{}; return RR_OK; }
+  if (const char* why = pose_option_limit(b, F_STEP, b->ref_frames, false)) return fail(RR_EUNSUPPORTED, std::string("rr_batch_set_velocity_tracking: ") + why);
+  if (!b->pose.track_pose) return fail(RR_EINVAL, "rr_batch_set_velocity_tracking: needs a pose block (rr_batch_set_pose) first: track_vel is indexed like track_pose");
+  if (!t->track_vel || !t->vel_metrics) return fail(RR_EINVAL, "rr_batch_set_velocity_tracking: null track_vel or vel_metrics");
+  for (float x : {t->lin_weight, t->lin_scale, t->ang_weight, t->ang_scale, t->joint_weight, t->joint_scale})
+    if (!(x >= 0.0f) || !std::isfinite(x)) return fail(RR_EINVAL, "rr_batch_set_velocity_tracking: weights and scales must be finite and >= 0");
+  b->vel = *t;
   return RR_OK;
 }
 extern "C" int rr_batch_clip_restarts_supported(const rr_batch* b, int32_t with_actor) {

@@ -324,6 +324,17 @@ struct RRIO {
   int* restart_slot_out;       // [N]
   int restart_K;               // 1 .. 64
   int restart_end;             // != 0: the clip's end (no next frame left to read without clamping) truncates the episode
+  // VELOCITY TRACKING (BODY instances, rr_body_kernel and rr_restart_kernel; no other instance reads these): the clip's velocities next
+  // to its pose.  track_vel is [T][nv] (with `clip` set [num_clips][T][nv]), a row in qvel layout, indexed by the clip and frame the
+  // position and pose rewards read.  With d = qvel - row on the stepped qvel:
+  //   S_lin = sum d[0:3]^2,  S_ang = sum d[3:6]^2,  S_joint = sum d[6:]^2      (every product and sum rounded on its own: per lane the
+  //                                                                              dofs in ascending order, then the wave sum)
+  //   lin = vel_lin_w exp(-vel_lin_k S_lin),  ang = vel_ang_w exp(-vel_ang_k S_ang),  joint = vel_joint_w exp(-vel_joint_k S_joint)
+  //   reward = ((reward so far + lin) + ang) + joint;  vel_metrics[env] = (lin, ang, joint), zeroed by a bad step.  Never at reset.
+  // A null track_vel: no such terms (one scalar load and a branch).  All fetched by narrow loads where they are used (load_io_member).
+  const float* track_vel;
+  float* vel_metrics;          // [N][3]
+  float vel_lin_w, vel_lin_k, vel_ang_w, vel_ang_k, vel_joint_w, vel_joint_k;
 };
 
 // ------------------------------------------------------------------------------------------ small math
@@ -2650,7 +2661,9 @@ static_assert(offsetof(RRIO, pterm_pad) + sizeof(int) == offsetof(RRIO, track_bo
 static_assert(offsetof(RRIO, track_bodies) + 3 * sizeof(float*) == offsetof(RRIO, body_w), "the weights and scales follow the three body-tracking pointers without padding");
 static_assert(offsetof(RRIO, endeff_k) + sizeof(float) == offsetof(RRIO, restart_frames) && offsetof(RRIO, restart_frames) % 8 == 0, "the clip-restart members follow the body-tracking members without padding");
 static_assert(offsetof(RRIO, restart_frames) + 3 * sizeof(int*) == offsetof(RRIO, restart_K), "the slot count follows the three clip-restart pointers without padding");
-static_assert(offsetof(RRIO, restart_end) + sizeof(int) == sizeof(RRIO), "the clip-restart members close RRIO without padding");
+static_assert(offsetof(RRIO, restart_end) + sizeof(int) == offsetof(RRIO, track_vel) && offsetof(RRIO, track_vel) % 8 == 0, "the velocity-tracking members follow the clip-restart members without padding");
+static_assert(offsetof(RRIO, track_vel) + 2 * sizeof(float*) == offsetof(RRIO, vel_lin_w), "the weights and scales follow the two velocity-tracking pointers without padding");
+static_assert(offsetof(RRIO, vel_joint_k) + sizeof(float) == sizeof(RRIO), "the velocity-tracking members close RRIO without padding");
 // ... and so are the model tables outside the solver's loops: RRTables is re-read at the head of each phase that indexes a table
 // (narrow scalar loads next to an existing hand-off; the unused members' loads are dead), so no table pointer is held across the
 // substep.  The loops' own tables are the exception (RRLoopTables, taken once from the parameter).
@@ -2897,8 +2910,9 @@ __global__ __launch_bounds__(RR_LANES, 2) void rr_poseterm_kernel(const RRDims D
 // (rr_batch_set_pose_termination; POSE TERMINATION) and body tracking (rr_batch_set_body_tracking; BODY TRACKING) -- in ONE set of
 // instances: POSE, REFOBS, PTERM and BODY are all on, and this entry serves every combination of the three on a batch.  What a batch
 // does not carry reaches the kernel switched off at run time: ref_frames = 0 is the same code with zero blocks (the row is rr_obs_width =
-// obs_dim wide), no termination block is +inf thresholds and a null pose_fail, no body block a null track_bodies.  Env steps of a batch
-// with any of the three run it; the single-step form also serves the RESETS of a batch with ref_frames > 0 (they write the blocks; the
+// obs_dim wide), no termination block is +inf thresholds and a null pose_fail, no body block a null track_bodies.  Velocity tracking
+// (rr_batch_set_velocity_tracking; VELOCITY TRACKING) rides here too, under `if (BODY)`: no such block is a null track_vel.  Env steps of
+// a batch with any of the four run it; the single-step form also serves the RESETS of a batch with ref_frames > 0 (they write the blocks; the
 // step-only code is not reached at reset).  A batch with the pose block alone stays on rr_pose_kernel, whose actor reads the narrower
 // row.  An entry of its own for the reason the others are: every `if (REFOBS)`, `if (PTERM)` and `if (BODY)` in the body folds away in
 // their instances.  The same nine forms as rr_pose_kernel; the actor inside reads RR_ACTOR_JM_REFOBS entries per lane whatever the frame
@@ -2915,7 +2929,7 @@ __global__ __launch_bounds__(RR_LANES, 2) void rr_body_kernel(const RRDims Dk, c
 // states, the restored frame and the clip-end truncation (RRIO, CLIP RESTARTS), served to the multi-step launches of a batch that carries
 // the block.  An entry of its own for the reason the others are: every `if (RESTART)` in the body folds away in their instances.  POSE,
 // REFOBS, PTERM and BODY are on -- a superset instance: ref_frames = 0 is that code with zero blocks, no termination block is +inf
-// thresholds and a null pose_fail, no body block a null track_bodies.  Multi-step forms only (a single step has no restore in the
+// thresholds and a null pose_fail, no body block a null track_bodies, no velocity block a null track_vel.  Multi-step forms only (a single step has no restore in the
 // kernel): without and with the actor, which reads RR_ACTOR_JM_REFOBS entries per lane whatever the frame count.
 template <class DT, bool ACTOR = false>
 __global__ __launch_bounds__(RR_LANES, 2) void rr_restart_kernel(const RRDims Dk, const RRTables Tk, const RRIO io_kernarg, const int num_envs, const int n_frames) {

@@ -491,6 +491,33 @@
           pe2 = wave_sum(pe2);
         }
       }
+      // ---- VELOCITY TRACKING, sums (BODY instances, RRIO::track_vel): the squared differences of the stepped qvel to the clip's row at
+      // the clip and frame of the other rewards, in three sums by dof range -- 0 .. 2 linear, 3 .. 5 angular, 6 .. nv - 1 joints.  The
+      // lanes read their dofs of both coalesced (nv = 73: dofs 64 .. 72 are a lane's second pass); every difference, square and sum is
+      // rounded on its own (contraction off), a dof outside a range adds +0 to that range's sum, which changes no bit of a sum of
+      // squares; one wave sum for the three.  Clip and frame are clamped before the offset is formed, so no row lies outside track_vel.
+      // A batch without the block pays the one scalar load and the branch.  ISOLATION: the lane id passes through an opaque copy and
+      // nothing here is shared with the pose sums above.
+      float vs[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+      if (BODY) {
+        const float* tvel = load_io_member<const float*>(offsetof(RRIO, track_vel));
+        if (tvel) {
+#pragma clang fp contract(off)
+          int vc = 0;
+          if (io.clip) { vc = io.clip[env]; vc = vc < 0 ? 0 : (vc > io.num_clips - 1 ? io.num_clips - 1 : vc); }
+          const int vf = old_frame < 0 ? 0 : (old_frame > io.track_len - 1 ? io.track_len - 1 : old_frame);
+          const float* vrow = tvel + ((size_t)vc * (size_t)io.track_len + (size_t)vf) * (size_t)D.nv;
+          const int vl = opaque(lane);
+          for (int i = vl; i < D.nv; i += RR_LANES) {
+            const float e = w.s_qvel[i] - vrow[i];
+            const float ee = e * e;
+            vs[0] = vs[0] + (i < 3 ? ee : 0.0f);
+            vs[1] = vs[1] + (i >= 3 && i < 6 ? ee : 0.0f);
+            vs[2] = vs[2] + (i >= 6 ? ee : 0.0f);
+          }
+          wave_sum_n<4>(vs);
+        }
+      }
       if (lane == 0) {
         int fi = old_frame < 0 ? 0 : (old_frame > io.track_len - 1 ? io.track_len - 1 : old_frame);
         const v3 dx = ld3(w.s_qpos) - ld3(track + 3 * fi);
@@ -555,6 +582,24 @@
             bm[0] = body_rew; bm[1] = endeff_rew;
           }
         }
+        // ---- VELOCITY TRACKING, terms (BODY instances): lane 0 forms the three terms from the wave sums above.  ISOLATION as for the
+        // body terms: the reward so far passes through an opaque copy, the terms stand under contraction off.
+        if (BODY) {
+          if (load_io_member<const float*>(offsetof(RRIO, track_vel))) {
+#pragma clang fp contract(off)
+            float* vm = load_io_member<float*>(offsetof(RRIO, vel_metrics)) + 3 * (size_t)env;
+            float rv = rew;
+            asm volatile("" : "+v"(rv));
+            const float xl = load_io_member<float>(offsetof(RRIO, vel_lin_k)) * vs[0];
+            const float lin_rew = load_io_member<float>(offsetof(RRIO, vel_lin_w)) * expf(-xl);
+            const float xa = load_io_member<float>(offsetof(RRIO, vel_ang_k)) * vs[1];
+            const float ang_rew = load_io_member<float>(offsetof(RRIO, vel_ang_w)) * expf(-xa);
+            const float xv = load_io_member<float>(offsetof(RRIO, vel_joint_k)) * vs[2];
+            const float jvel_rew = load_io_member<float>(offsetof(RRIO, vel_joint_w)) * expf(-xv);
+            rew = ((rv + lin_rew) + ang_rew) + jvel_rew;
+            vm[0] = lin_rew; vm[1] = ang_rew; vm[2] = jvel_rew;
+          }
+        }
         io.reward[env] = rew;
         if (ACTOR && !EVAL) io.t_reward[rr_traj_at(io, num_envs, env, ut)] = rew;
         io.done[env] = io.terminate_when_unhealthy ? 1.0f - healthy : 0.0f;
@@ -572,6 +617,7 @@
           }
           if (BODY) {
             if (load_io_member<const float*>(offsetof(RRIO, track_bodies))) { float* bm = load_io_member<float*>(offsetof(RRIO, body_metrics)) + 2 * (size_t)env; bm[0] = 0.0f; bm[1] = 0.0f; }
+            if (load_io_member<const float*>(offsetof(RRIO, track_vel))) { float* vm = load_io_member<float*>(offsetof(RRIO, vel_metrics)) + 3 * (size_t)env; vm[0] = 0.0f; vm[1] = 0.0f; vm[2] = 0.0f; }
           }
           if (PTERM) pterm_code = 0;      // a bad step: done = 1 from the check above, code 0
         }

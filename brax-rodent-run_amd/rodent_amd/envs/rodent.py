@@ -107,6 +107,15 @@ def reset_qpos(qpos0, track: np.ndarray, start_frame, qpos_noise, clip=None, pos
     return qpos + qpos_noise
 
 
+def reset_qvel(track_vel: np.ndarray, start_frame, qvel_noise, clip=None) -> np.ndarray:
+    """The qvel `Rodent.reset` starts from with the clip's velocities given and `reset_to_reference=True`, float32 [N, nv], out of the
+    draws of `reset_draws`: track_vel[(clip,) start_frame] (the env's [(C,) T, nv] rows, the frame clamped within the clip) plus the
+    noise, a float32 sum.  The draws are not touched."""
+    fi = np.clip(start_frame, 0, track_vel.shape[-2] - 1)
+    row = track_vel[fi] if clip is None else track_vel[clip, fi]
+    return np.asarray(row, dtype=np.float32) + np.asarray(qvel_noise, dtype=np.float32)
+
+
 def _check_track(track_pos) -> np.ndarray:
     """track_pos as float32 [T, 3] or [C, T, 3] (C >= 1, T >= 1), ValueError otherwise."""
     t = track_pos.detach().cpu().numpy() if torch.is_tensor(track_pos) else np.asarray(track_pos)
@@ -355,6 +364,58 @@ def _check_body_tracking(track: np.ndarray, track_bodies, body_ids, end_effector
     return np.ascontiguousarray(bodies, dtype=np.float32), masks, sets[0], sets[1]
 
 
+def velocity_rewards(qvel, ref_vel, weights=(1.0, 1.0, 1.0), scales=(10.0, 0.1, 0.01)):
+    """The three velocity terms the step kernel adds to the reward of an env with velocity tracking (`Rodent(track_velocity=...)`; C ABI
+    `rr_batch_set_velocity_tracking`) restated in numpy float64.  `qvel` [..., nv] the stepped state, `ref_vel` [..., nv] the clip's row
+    in qvel layout at the clip and frame the step's rewards read (`cur_frame` before the step, clamped); `weights` = (lin, ang, joint)
+    reward weights, `scales` likewise.  With d = qvel - ref_vel:
+
+        S_lin = sum d[0:3]**2,   S_ang = sum d[3:6]**2,   S_joint = sum d[6:]**2
+        lin_vel_reward = weights[0] * exp(-scales[0] * S_lin),  ang_vel_reward and joint_vel_reward likewise
+
+    Returns (lin_vel_reward, ang_vel_reward, joint_vel_reward), float64 [...]."""
+    d2 = (np.asarray(qvel, dtype=np.float64) - np.asarray(ref_vel, dtype=np.float64)) ** 2
+    sums = (d2[..., :3].sum(-1), d2[..., 3:6].sum(-1), d2[..., 6:].sum(-1))
+    return tuple(w * np.exp(-k * s) for w, k, s in zip(weights, scales, sums))
+
+
+def _check_velocity_tracking(track: np.ndarray, track_velocity, track_angular_velocity, track_joint_velocity, nv: int, weights_and_scales,
+                             have_pose: bool) -> Optional[np.ndarray]:
+    """The velocity-tracking arguments of `Rodent` against its (checked) `track` [(C,) T, 3]: None when none of the three arrays is given,
+    else the rows the device holds, float32 [(C,) T, nv] in qvel layout = [velocity | angular_velocity | joints_velocity].  ValueError for
+    some of the three without the others, the arrays without the pose arguments, a shape other than track.shape[:-1] + (3,) / + (3,) /
+    + (nv - 6,), a non-finite entry, and a negative or non-finite weight or scale."""
+    for x in weights_and_scales:
+        if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, float, np.integer, np.floating)):
+            raise ValueError(f"velocity reward weights and scales must be numbers, finite and >= 0, got {x!r}")
+        with np.errstate(over="ignore"):
+            x32 = np.float32(x)
+        if not (np.isfinite(x32) and x32 >= 0):
+            raise ValueError(f"velocity reward weights and scales must be finite and >= 0 (as float32), got {x!r}")
+    given = [a is not None for a in (track_velocity, track_angular_velocity, track_joint_velocity)]
+    if not any(given):
+        return None
+    if not all(given):
+        raise ValueError("track_velocity, track_angular_velocity and track_joint_velocity go together: pass all three (velocity tracking) or none")
+    if not have_pose:
+        raise ValueError("track_velocity / track_angular_velocity / track_joint_velocity need the reference pose: pass track_quat and track_joints")
+    arr = lambda a: (a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)).astype(np.float64)
+    lin, ang, joint = arr(track_velocity), arr(track_angular_velocity), arr(track_joint_velocity)
+    lead = track.shape[:-1]
+    if lin.shape != lead + (3,) or ang.shape != lead + (3,) or joint.shape != lead + (nv - 6,):
+        raise ValueError(f"track_velocity / track_angular_velocity / track_joint_velocity must have shapes {lead + (3,)} / {lead + (3,)} / "
+                         f"{lead + (nv - 6,)} next to a track_pos of shape {track.shape} (the same clips and frames), got {lin.shape} / "
+                         f"{ang.shape} / {joint.shape}")
+    rows = np.concatenate([lin, ang, joint], axis=-1)
+    if not np.isfinite(rows).all():
+        raise ValueError("track_velocity / track_angular_velocity / track_joint_velocity hold a non-finite entry")
+    with np.errstate(over="ignore"):
+        rows32 = np.ascontiguousarray(rows, dtype=np.float32)
+    if not np.isfinite(rows32).all():
+        raise ValueError("track_velocity / track_angular_velocity / track_joint_velocity hold an entry that is not finite as a float32")
+    return rows32
+
+
 class _StepOption(NamedTuple):
     """One option of the env step as `Rodent` hands it to its batch and reads it back: the output buffer a step launch gets under the
     env-io key `key` (float32 [N] + `shape`), the `static` env-io entries that go with it (the option's tensors and scalar tuples), the
@@ -366,7 +427,7 @@ class _StepOption(NamedTuple):
     read: Callable
 
 
-_columns = lambda buf: (buf[:, 0], buf[:, 1])      # the two columns of an [N, 2] metrics buffer, as views
+_columns = lambda buf: tuple(buf[:, j] for j in range(buf.shape[1]))      # the columns of an [N, 2] or [N, 3] metrics buffer, as views
 
 
 def _code_bits(buf):
@@ -415,6 +476,15 @@ class Rodent(PipelineEnv):
         clip_restarts: int = 0,
         restart_frame_range=None,
         end_at_clip_end: bool = False,
+        track_velocity=None,
+        track_angular_velocity=None,
+        track_joint_velocity=None,
+        lin_vel_reward_weight: float = 1.0,
+        lin_vel_reward_scale: float = 10.0,
+        ang_vel_reward_weight: float = 1.0,
+        ang_vel_reward_scale: float = 0.1,
+        joint_vel_reward_weight: float = 1.0,
+        joint_vel_reward_scale: float = 0.01,
         **kwargs,
     ):
         """`track_pos`: the reference positions to track, float [T, 3] -- one clip, followed by every env -- or [C, T, 3], C >= 1 clips of
@@ -498,7 +568,31 @@ class Rodent(PipelineEnv):
 
         The clip's end (`end_at_clip_end=True`, needs K >= 1) is a truncation like `episode_length`, so the value bootstraps; the step
         that ends the episode is untouched.  K = 1 restores the frame with the state.  The bare `step` and the raw evaluation rollout have
-        no wrappers and do not change."""
+        no wrappers and do not change.
+
+        Velocity tracking: `track_velocity` [T, 3], `track_angular_velocity` [T, 3] and `track_joint_velocity` [T, nv - 6] -- with a
+        [C, T, 3] track_pos each gains the clip axis -- are the clip's velocities (`preprocessing.ReferenceClip.velocity`,
+        `.angular_velocity`, `.joints_velocity`); all three or none, pose envs only, every entry finite.  They are kept as one device
+        array `track_vel` [(C,) T, nv] whose rows are in `qvel` layout, [velocity | angular_velocity | joints_velocity].  The frames
+        agree: qvel[0:3] is the world-frame linear velocity of the free joint and qvel[3:6] its angular velocity in the root's OWN frame,
+        and `preprocessing.compute_velocity_from_kinematics` forms the clip's angular velocity as the axis-angle of conj(q_t) q_{t+1}
+        over dt, which is that same frame -- so the rows are compared with qvel as they are.  A pose reward alone pays a policy that holds
+        the right pose at the wrong speed, or jitters around it, in full; these three terms score the speed.  Every env step (never a
+        reset) adds, at the clip and frame the other rewards read and with d = qvel - row on the stepped qvel (`velocity_rewards` is the
+        float64 restatement):
+
+            lin_vel_reward   = lin_vel_reward_weight   * exp(-lin_vel_reward_scale   * sum(d[0:3]**2))
+            ang_vel_reward   = ang_vel_reward_weight   * exp(-ang_vel_reward_scale   * sum(d[3:6]**2))
+            joint_vel_reward = joint_vel_reward_weight * exp(-joint_vel_reward_scale * sum(d[6:]**2))
+            reward           = ((reward with the pose and body terms + lin_vel_reward) + ang_vel_reward) + joint_vel_reward
+
+        `State.metrics` gains `lin_vel_reward`, `ang_vel_reward` and `joint_vel_reward`, after the body metrics (zeros at reset and after
+        a bad step); physics, done, the observation, cur_frame and the other metrics are what they are without the terms.  A weight of 0
+        switches its term off.  The six defaults (1, 10, 1, 0.1, 1, 0.01) are UNTUNED choices, not values from a reference.  Served where
+        body tracking is, in `step`, `unroll_wrapped` and `unroll_policy_wrapped`, with or without the other options.  With the arrays
+        given, `reset_to_reference=True` also starts the episode MOVING: qvel = track_vel[clip, start_frame] + noise instead of the bare
+        noise (`reset_qvel`), in the reset state and in every entry of the clip-restart bank; the random draws are the same.  Without the
+        arrays, or with `reset_to_reference=False`, `reset` is what it is without them in every bit."""
         given = locals()                  # the arguments as they came (first statement: nothing else is a local yet): `_ctor` below
         if bad_state_max is not None:
             with np.errstate(over="ignore", under="ignore"):
@@ -523,6 +617,9 @@ class Rodent(PipelineEnv):
         body_np = _check_body_tracking(track_np, track_bodies, body_ids, end_effector_ids, sys.nbody,
                                        (body_reward_weight, body_reward_scale, endeff_reward_weight, endeff_reward_scale), pose_np is not None)
         restarts = _check_clip_restarts(clip_restarts, restart_frame_range, end_at_clip_end, pose_np is not None, track_np.shape[-2])
+        vel_np = _check_velocity_tracking(track_np, track_velocity, track_angular_velocity, track_joint_velocity, sys.nv,
+                                          (lin_vel_reward_weight, lin_vel_reward_scale, ang_vel_reward_weight, ang_vel_reward_scale,
+                                           joint_vel_reward_weight, joint_vel_reward_scale), pose_np is not None)
         if reset_to_reference and pose_np is None:
             raise ValueError("reset_to_reference=True needs the reference pose: pass track_quat and track_joints")
         physics_steps_per_control_step = 10   # [REF Rodent_Env_Brax.py:53-57]
@@ -555,6 +652,7 @@ class Rodent(PipelineEnv):
                   (ref_frames > 0, f"reference_obs_frames={ref_frames}", reference_frames_supported),
                   (pose_term is not None, "max_pos_error / max_quat_error / max_joint_error", batch.pose_termination_supported),
                   (body_np is not None, "track_bodies=...", batch.body_tracking_supported),
+                  (vel_np is not None, "track_velocity=...", batch.velocity_tracking_supported),
                   (self._clip_restarts > 0, f"clip_restarts={self._clip_restarts}", batch.clip_restarts_supported))
         for wanted, label, query in probes:       # a model, solver or frame count without the option's instance: the library's reason
             why = query() if wanted else None
@@ -567,6 +665,11 @@ class Rodent(PipelineEnv):
             self._body = dict(track_bodies=torch.from_numpy(rows).to(self.device).contiguous(), body_weights=torch.from_numpy(masks).to(self.device).contiguous(),
                               body_reward=(float(body_reward_weight) if B else 0.0, float(body_reward_scale)),
                               endeff_reward=(float(endeff_reward_weight) if E else 0.0, float(endeff_reward_scale)), body_ids=B, end_effector_ids=E)
+        self._vel_host = vel_np           # None: no velocity tracking (no such members anywhere; reset starts at rest)
+        self._track_vel = None if vel_np is None else torch.from_numpy(vel_np).to(self.device).contiguous()
+        self._vel = None if vel_np is None else dict(lin_vel_reward=(float(lin_vel_reward_weight), float(lin_vel_reward_scale)),
+                                                     ang_vel_reward=(float(ang_vel_reward_weight), float(ang_vel_reward_scale)),
+                                                     joint_vel_reward=(float(joint_vel_reward_weight), float(joint_vel_reward_scale)))
         # the step options in force, in the order their metrics follow the three old ones; a reset hands none of them (it has no reward
         # and no done to raise) -- but see `_env_io` for an env with reference frames
         self._options = tuple(o for o in (
@@ -575,7 +678,10 @@ class Rodent(PipelineEnv):
             pose_term is not None and _StepOption("pose_fail", (), dict(pose_termination=pose_term),
                                                   ("pose_fail", "pose_fail_pos", "pose_fail_quat", "pose_fail_joint"), _code_bits),
             body_np is not None and _StepOption("body_metrics", (2,), {k: self._body[k] for k in ("track_bodies", "body_weights", "body_reward", "endeff_reward")},
-                                                ("body_reward", "endeff_reward"), _columns)) if o)
+                                                ("body_reward", "endeff_reward"), _columns),
+            vel_np is not None and _StepOption("vel_metrics", (3,), dict(track_vel=self._track_vel, lin_vel_reward=self._vel["lin_vel_reward"],
+                                                                       ang_vel_reward=self._vel["ang_vel_reward"], joint_vel_reward=self._vel["joint_vel_reward"]),
+                                               ("lin_vel_reward", "ang_vel_reward", "joint_vel_reward"), _columns)) if o)
         self._forward_reward_weight = forward_reward_weight
         self._ctrl_cost_weight = ctrl_cost_weight
         self._healthy_reward = healthy_reward
@@ -632,6 +738,12 @@ class Rodent(PipelineEnv):
         if self._body is None:
             return None
         return {k: self._body[k] for k in ("body_ids", "end_effector_ids", "body_reward", "endeff_reward")}
+
+    @property
+    def velocity_tracking(self) -> Optional[dict]:
+        """None without velocity tracking, else dict(lin_vel_reward=(weight, scale), ang_vel_reward=(weight, scale),
+        joint_vel_reward=(weight, scale)) as the kernel uses them."""
+        return None if self._vel is None else dict(self._vel)
 
     @property
     def clip_restarts(self) -> int:
@@ -713,7 +825,9 @@ class Rodent(PipelineEnv):
         for k in range(K):
             # float32 [T, 3] or [C, T, 3] (and the pose rows), what the device holds
             qpos = reset_qpos(s.qpos0, self._track_host, frames[k], noises[k], clip, self._pose_host if self._reset_to_reference else None)
-            st = dict(qpos=torch.from_numpy(qpos).to(dev), qvel=torch.from_numpy(qvels[k]).to(dev),
+            # with the clip's velocities the episode starts moving: the row of the start frame plus the (same) noise
+            qvel = reset_qvel(self._vel_host, frames[k], qvels[k], clip) if self._vel_host is not None and self._reset_to_reference else qvels[k]
+            st = dict(qpos=torch.from_numpy(qpos).to(dev), qvel=torch.from_numpy(qvel).to(dev),
                       act=torch.zeros(N, s.na, device=dev), qacc_warmstart=torch.zeros(N, s.nv, device=dev))
             out = self._alloc_outputs(full=False)
             cur_frame = torch.from_numpy(frames[k].astype(np.int32)).to(dev)
@@ -813,12 +927,14 @@ class Rodent(PipelineEnv):
 
     def fused_actor_refusal(self) -> Optional[str]:
         """None when the in-kernel actor of the instance this env's multi-step launches run reads the env's row width, else the
-        library's text.  The launches run the instance of the highest option in force -- clip restarts, then body tracking, then pose
+        library's text.  The launches run the instance of the highest option in force -- clip restarts, then body tracking, then velocity tracking, then pose
         termination, then the pose instance at the env's reference frames (0 without) -- so that one is asked."""
         if self._clip_restarts:
             return self._batch.clip_restarts_supported(with_actor=True)
         if self._body is not None:
             return self._batch.body_tracking_supported(with_actor=True)
+        if self._vel is not None:
+            return self._batch.velocity_tracking_supported(with_actor=True)
         if self._pose_term is not None:
             return self._batch.pose_termination_supported(with_actor=True)
         return self._batch.reference_obs_supported(self._ref_frames, with_actor=True)

@@ -72,6 +72,12 @@ class RRClipRestartIO(C.Structure):
     _fields_ = [("frames", C.c_void_p), ("slot_in", C.c_void_p), ("slot_out", C.c_void_p), ("num_slots", C.c_int32), ("end_at_clip_end", C.c_int32)]
 
 
+class RRVelIO(C.Structure):
+    """`rr_vel_io`, the velocity-tracking block a batch carries next to its pose block (`rr_batch_set_velocity_tracking`)."""
+    _fields_ = [("track_vel", C.c_void_p), ("vel_metrics", C.c_void_p), ("lin_weight", C.c_float), ("lin_scale", C.c_float),
+                ("ang_weight", C.c_float), ("ang_scale", C.c_float), ("joint_weight", C.c_float), ("joint_scale", C.c_float)]
+
+
 class RRUnrollIO(C.Structure):
     _fields_ = [("first", RRState), ("first_obs", C.c_void_p), ("prev_done", C.c_void_p), ("steps_in", C.c_void_p), ("steps_out", C.c_void_p),
                 ("truncation_out", C.c_void_p), ("episode_length", C.c_float)]
@@ -103,7 +109,7 @@ class RRPpoCfg(C.Structure):
 
 
 EXPORTS = ["rr_model_load", "rr_model_dims", "rr_model_set_solver", "rr_model_set_solver_type", "rr_model_destroy", "rr_model_table", "rr_kernarg_layout", "rr_batch_create",
-           "rr_batch_destroy", "rr_pipeline_init", "rr_pipeline_step", "rr_env_step", "rr_env_reset", "rr_pipeline_step_to", "rr_env_step_to", "rr_batch_contact_overflow", "rr_batch_bad_states", "rr_batch_unroll_supported", "rr_env_unroll", "rr_env_unroll_policy", "rr_batch_eval_supported", "rr_env_unroll_eval", "rr_batch_pose_supported", "rr_batch_set_pose", "rr_batch_set_reference_obs", "rr_batch_obs_width", "rr_batch_reference_obs_supported", "rr_batch_set_pose_termination", "rr_batch_pose_termination_supported", "rr_batch_set_body_tracking", "rr_batch_body_tracking_supported", "rr_batch_set_clip_restarts", "rr_batch_clip_restarts_supported", "rr_wrap_clip_restart",
+           "rr_batch_destroy", "rr_pipeline_init", "rr_pipeline_step", "rr_env_step", "rr_env_reset", "rr_pipeline_step_to", "rr_env_step_to", "rr_batch_contact_overflow", "rr_batch_bad_states", "rr_batch_unroll_supported", "rr_env_unroll", "rr_env_unroll_policy", "rr_batch_eval_supported", "rr_env_unroll_eval", "rr_batch_pose_supported", "rr_batch_set_pose", "rr_batch_set_reference_obs", "rr_batch_obs_width", "rr_batch_reference_obs_supported", "rr_batch_set_pose_termination", "rr_batch_pose_termination_supported", "rr_batch_set_body_tracking", "rr_batch_body_tracking_supported", "rr_batch_set_clip_restarts", "rr_batch_clip_restarts_supported", "rr_batch_set_velocity_tracking", "rr_batch_velocity_tracking_supported", "rr_wrap_clip_restart",
            "rr_compute_gae", "rr_mlp_forward", "rr_ppo_loss_workspace_bytes", "rr_ppo_loss", "rr_policy_act_workspace_bytes", "rr_policy_act", "rr_policy_sample", "rr_policy_backward_workspace_bytes", "rr_policy_backward", "rr_mlp_silu_backward_workspace_bytes", "rr_mlp_silu_backward", "rr_mlp_value_backward_workspace_bytes", "rr_mlp_policy_backward", "rr_mlp_policy_backward_workspace_bytes", "rr_mlp_value_backward", "rr_mlp_weight_grad_workspace_bytes", "rr_mlp_weight_grad", "rr_mlp_weight_grad_batch_workspace_bytes", "rr_mlp_weight_grad_batch", "rr_obs_moments_workspace_bytes", "rr_obs_moments", "rr_wrap_episode_autoreset", "rr_debug_layout", "rr_batch_set_schedule", "rr_batch_set_env_params", "rr_batch_env_params_supported", "rr_batch_set_profile", "rr_batch_set_ls_repeat_exit", "rr_batch_set_solver_trim", "rr_batch_set_solver_batch", "rr_batch_set_solve_resident", "rr_model_solve_resident_switch", "rr_batch_set_root_slot", "rr_model_root_slot_switch", "rr_batch_set_timing", "rr_batch_kernel_time", "rr_last_error"]
 
 _lib = None
@@ -201,6 +207,8 @@ def lib():
         L.rr_batch_body_tracking_supported.argtypes = [C.c_void_p, C.c_int32]
         L.rr_batch_set_clip_restarts.argtypes = [C.c_void_p, C.POINTER(RRClipRestartIO)]
         L.rr_batch_clip_restarts_supported.argtypes = [C.c_void_p, C.c_int32]
+        L.rr_batch_set_velocity_tracking.argtypes = [C.c_void_p, C.POINTER(RRVelIO)]
+        L.rr_batch_velocity_tracking_supported.argtypes = [C.c_void_p, C.c_int32]
         L.rr_wrap_clip_restart.argtypes = [C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int32)] + \
             [C.c_void_p] * 5 + [C.c_float, C.c_float] + [C.c_void_p] * 4 + [C.c_int32] * 3 + [C.c_void_p]
         L.rr_batch_set_ls_repeat_exit.argtypes = [C.c_void_p, C.c_int32]
@@ -318,6 +326,7 @@ class Batch:
         self._pterm = None          # the tensor of the pose-termination block in force (set_pose_termination)
         self._body = None           # the tensors of the body-tracking block in force (set_body_tracking)
         self._restart = None        # the tensors of the clip-restart block in force (set_clip_restarts)
+        self._vel = None            # the tensors of the velocity-tracking block in force (set_velocity_tracking)
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream().cuda_stream
         _check(lib().rr_batch_create(model.h, self.N, self.device.index or 0, C.c_void_p(stream), C.byref(self.h)))
@@ -382,8 +391,8 @@ class Batch:
     def _program_blocks(self, env):
         """The pose options ride on the batch, not in rr_env_io: the env-io dict decides what the launch about to be issued sees.  One row
         per block -- the env-io key that decides its presence, the attribute that says whether it stands, its setter, the setter's
-        arguments out of the dict (the setters say what each entry is) -- in dependency order: termination, body tracking and clip
-        restarts each need the pose block, and the library keeps the pose block while one of them stands.  So the blocks absent from the
+        arguments out of the dict (the setters say what each entry is) -- in dependency order: termination, body tracking, velocity tracking
+        and clip restarts each need the pose block, and the library keeps the pose block while one of them stands.  So the blocks absent from the
         dict are cleared last to first, then the present ones are set first to last.  (Clearing the pose block is refused while the
         batch carries reference frames: their launches all carry `track_pose`.)"""
         lead, d, inf = tuple(env["track_pos"].shape[:-1]), self.dims, math.inf
@@ -397,6 +406,8 @@ class Batch:
                   ("pose_fail", "_pterm", self.set_pose_termination, lambda: (env["pose_fail"], env.get("pose_termination", (inf, inf, inf)))),
                   ("track_bodies", "_body", self.set_body_tracking, lambda: (rows("track_bodies", (d.nbody, 3)), env.get("body_weights"), env.get("body_metrics"),
                                                                              env.get("body_reward", (1.0, 8.0)), env.get("endeff_reward", (1.0, 100.0)))),
+                  ("track_vel", "_vel", self.set_velocity_tracking, lambda: (rows("track_vel", (d.nv,)), env.get("vel_metrics"), env.get("lin_vel_reward", (1.0, 10.0)),
+                                                                           env.get("ang_vel_reward", (1.0, 0.1)), env.get("joint_vel_reward", (1.0, 0.01)))),
                   ("restart", "_restart", self.set_clip_restarts, lambda: (env["restart"]["frames"], env["restart"]["slot_in"], env["restart"]["slot_out"],
                                                                            env["restart"].get("end_at_clip_end", False))))
         for key, attr, setter, _ in reversed(blocks):
@@ -543,7 +554,7 @@ class Batch:
         _check(lib().rr_batch_set_schedule(self.h, _ptr(env_map, torch.int32, self.N), _ptr(cost, torch.int32, self.N)))
 
     def _set_block(self, attr: str, setter, block, tensors):
-        """The tail of the four block setters below: hand `block` (the block's struct; None clears it) to the library's `setter`, then
+        """The tail of the block setters below: hand `block` (the block's struct; None clears it) to the library's `setter`, then
         keep `tensors` alive in `attr` while the block stands, or drop them."""
         _check(setter(self.h, None if block is None else C.byref(block)))
         setattr(self, attr, None if block is None else tensors)
@@ -578,6 +589,25 @@ class Batch:
             t = RRBodyIO(_ptr(track_bodies), _ptr(body_weights, numel=2 * nb), _ptr(body_metrics, numel=2 * self.N),
                          float(body_reward[0]), float(body_reward[1]), float(endeff_reward[0]), float(endeff_reward[1]))
         self._set_block("_body", lib().rr_batch_set_body_tracking, t, (track_bodies, body_weights, body_metrics))
+
+    def set_velocity_tracking(self, track_vel: Optional[torch.Tensor], vel_metrics: Optional[torch.Tensor] = None, lin_vel_reward=(1.0, 10.0),
+                              ang_vel_reward=(1.0, 0.1), joint_vel_reward=(1.0, 0.01)):
+        """The velocity-tracking block of this batch's later env steps (C ABI `rr_batch_set_velocity_tracking`): `track_vel` [(C), T, nv]
+        the clip's velocities, rows in qvel layout, `vel_metrics` [N, 3] out (lin_vel_reward, ang_vel_reward, joint_vel_reward); the three
+        pairs = (weight, scale); None clears it.  Needs the pose block (`set_pose`).  The env-io dict of a launch (`track_vel`,
+        `vel_metrics`, `lin_vel_reward`, `ang_vel_reward`, `joint_vel_reward` keys) sets or clears it by itself.  The batch keeps the
+        tensors alive."""
+        t, nv = None, self.dims.nv
+        if track_vel is not None:
+            if track_vel.dim() < 2 or track_vel.shape[-1] != nv:
+                raise ValueError(f"track_vel has shape {tuple(track_vel.shape)}, expected [(C), T, {nv}]")
+            t = RRVelIO(_ptr(track_vel), _ptr(vel_metrics, numel=3 * self.N), *(float(x) for pair in (lin_vel_reward, ang_vel_reward, joint_vel_reward) for x in pair))
+        self._set_block("_vel", lib().rr_batch_set_velocity_tracking, t, (track_vel, vel_metrics))
+
+    def velocity_tracking_supported(self, with_actor: bool = False) -> Optional[str]:
+        """None when this batch serves velocity tracking at its frame count (C ABI `rr_batch_velocity_tracking_supported`) -- with
+        `with_actor` also in the one-launch rollout with the actor inside -- else the refusal's text."""
+        return self._refusal(lib().rr_batch_velocity_tracking_supported, int(with_actor))
 
     def set_clip_restarts(self, frames: Optional[torch.Tensor], slot_in: Optional[torch.Tensor] = None, slot_out: Optional[torch.Tensor] = None,
                           end_at_clip_end: bool = False):

@@ -82,11 +82,20 @@ def main():
                     "the K - 1 further start states are drawn in [LO, HI) (default 0 100, the reference's range)")
     ap.add_argument("--end-at-clip-end", action="store_true", help="with --clip-restarts: truncate an episode at the clip's last frame instead "
                     "of comparing it with the clamped last row (the clip must be longer than every start frame: the synthetic line has 250 frames)")
+    ap.add_argument("--track-velocity", action="store_true", help="with --track-pose: reward the clip's velocities too (Rodent(track_velocity=..., "
+                    "track_angular_velocity=..., track_joint_velocity=...), untuned default weights), and with them a reset to the reference starts "
+                    "moving: the clip file's velocity, angular_velocity and joints_velocity; the synthetic lines get "
+                    "preprocessing.compute_velocity_from_kinematics of their own poses")
+    ap.add_argument("--lin-vel-scale", type=float, default=10.0, metavar="K", help="with --track-velocity: Rodent(lin_vel_reward_scale=K)")
+    ap.add_argument("--ang-vel-scale", type=float, default=0.1, metavar="K", help="with --track-velocity: Rodent(ang_vel_reward_scale=K)")
+    ap.add_argument("--joint-vel-scale", type=float, default=0.01, metavar="K", help="with --track-velocity: Rodent(joint_vel_reward_scale=K)")
     ap.add_argument("--policy-width", type=int, choices=(32, 256), default=32, help="units per hidden layer of the policy network; both "
                     "widths run on the hand-written learner kernels (256: per-step rollouts, the in-kernel actor is 32-wide)")
     ap.add_argument("--policy-depth", type=int, default=4, help="hidden layers of the policy network (1 .. 7 for the hand-written kernels; "
                     "the one-launch rollout of the 32-wide policy takes 1 .. 4)")
     args = ap.parse_args()
+    if args.track_velocity and not args.track_pose:      # (before any device is touched)
+        ap.error("--track-velocity: the velocities are indexed like the reference pose; add --track-pose")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -156,6 +165,21 @@ def main():
             bodies = preprocessing.extract_features(probe, qpos).body_positions
             bodies = bodies.reshape(lead + bodies.shape[1:])
         pose.update(track_bodies=bodies, end_effector_ids=args.end_effector_ids)
+
+    if args.track_velocity:
+        single = track_pos.ndim == 2
+        if clips is not None and clips.velocity is not None:      # the clip's own velocities, the clip axis as track_pos has it
+            vel = [np.asarray(a) for a in (clips.velocity, clips.angular_velocity, clips.joints_velocity)]
+            vel = [a[0] if single else a for a in vel]
+        else:                                        # finite differences of the poses the env tracks, as preprocessing.process_clip forms them
+            lead = track_pos.shape[:-1]              # (the last frame is repeated, so the last row is zero); dt 0.02: the env's control step
+            qpos = np.concatenate([track_pos, np.broadcast_to(pose["track_quat"], lead + (4,)), pose["track_joints"]], axis=-1)
+            qpos = qpos[None] if single else qpos
+            qvel = np.stack([preprocessing.compute_velocity_from_kinematics(np.concatenate([q, q[-1:]], axis=0), 0.02) for q in qpos])
+            qvel = qvel[0] if single else qvel
+            vel = [qvel[..., :3], qvel[..., 3:6], qvel[..., 6:]]
+        pose.update(track_velocity=vel[0], track_angular_velocity=vel[1], track_joint_velocity=vel[2], lin_vel_reward_scale=args.lin_vel_scale,
+                    ang_vel_reward_scale=args.ang_vel_scale, joint_vel_reward_scale=args.joint_vel_scale)
 
     envs.register_environment("rodent", envs.Rodent)
     env = envs.get_environment(

@@ -394,6 +394,36 @@ typedef struct rr_clip_restart_io {
 int rr_batch_set_clip_restarts(rr_batch* b, const rr_clip_restart_io* restart);
 int rr_batch_clip_restarts_supported(const rr_batch* b, int32_t with_actor);
 
+/* Velocity tracking: the reward also scores the clip's velocities, so a policy that holds the right pose at the wrong speed no longer
+ * earns full reward.  The block is set on the BATCH, next to the pose block it needs (the structs above are closed), and read by every
+ * later env step of it -- rr_env_step(_to), rr_env_unroll and rr_env_unroll_policy -- until it is replaced or cleared (NULL; a batch
+ * starts without one); a launch takes the pointers as they are when it is issued.  track_vel is [T][nv] (with clip ids
+ * [num_clips][T][nv]), indexed like track_pose, a row in qvel layout: the world-frame linear velocity of the free joint [3], the angular
+ * velocity in the root's own frame [3], the joint velocities [nv - 6].  An env step (never a reset) forms, with d = qvel - r on the
+ * stepped qvel and r the row of the clip and frame its position and pose rewards read:
+ *   S_lin = sum d[0:3]^2,   S_ang = sum d[3:6]^2,   S_joint = sum d[6:]^2
+ *   lin_vel_reward   = lin_weight   exp(-lin_scale   S_lin)
+ *   ang_vel_reward   = ang_weight   exp(-ang_scale   S_ang)
+ *   joint_vel_reward = joint_weight exp(-joint_scale S_joint)
+ *   reward = ((r_0 + lin_vel_reward) + ang_vel_reward) + joint_vel_reward;   vel_metrics[e] = the three terms
+ * r_0 the reward with the pose terms (and the body terms where the batch carries that block); every product and sum rounded to float32
+ * on its own.  done, cur_frame, obs, the state, metrics, pose_metrics, pose_fail and body_metrics are what they are without the block; a
+ * bad step (bad_state_max) zeroes vel_metrics with the others.  rr_env_reset ignores the block.
+ * rr_batch_set_velocity_tracking: no pose block on the batch (rr_batch_set_pose first), a NULL pointer, or a weight or scale that is
+ * negative or not finite: RR_EINVAL; RR_EUNSUPPORTED with the reason wherever pose tracking is unsupported.  While the block is set,
+ * rr_batch_set_pose(b, NULL) is RR_EINVAL (clear this block first), and what refuses a pose block refuses here: rr_env_unroll_eval,
+ * per-env parameters, the debug dump, contact-geometry outputs and the profile build.  The env steps run the body-tracking instances
+ * whatever else the batch carries, so rr_env_unroll_policy serves rows of up to 1664 entries.
+ * rr_batch_velocity_tracking_supported(b, with_actor): 1 / 0 -- whether the batch serves the block with its current frame count
+ * (with_actor != 0: also in rr_env_unroll_policy); with 0 rr_last_error holds the reason.  It does not need the pose block to be set. */
+typedef struct rr_vel_io {
+  const float* track_vel;      /* [(C)][T][nv] */
+  float* vel_metrics;          /* [N][3] out: (lin_vel_reward, ang_vel_reward, joint_vel_reward) */
+  float lin_weight, lin_scale, ang_weight, ang_scale, joint_weight, joint_scale;
+} rr_vel_io;
+int rr_batch_set_velocity_tracking(rr_batch* b, const rr_vel_io* vel);
+int rr_batch_velocity_tracking_supported(const rr_batch* b, int32_t with_actor);
+
 /* Generalised advantage estimation of one PPO minibatch, the reverse scan of brax.training.agents.ppo.losses.compute_gae
  * [UP; SURVEY.md Appendix E], one thread per trajectory.  All arrays time-major [T][B] device float32; bootstrap [B];
  * outputs vs [T][B] and advantages [T][B].  `stream` is a hipStream_t (NULL = default stream). */

@@ -6,17 +6,20 @@ alternating in one process on one GPU.  No gate: it reports.
   --option poseterm  a pose env | the same with three thresholds of 1e30: every comparison made, no episode ended by it
   --option body      a pose env | the same with `track_bodies` (the forward kinematics of the reference pose at every frame,
                      `preprocessing.extract_features`), B = all bodies, E = foot_L, foot_R, hand_L, hand_R, skull
+  --option velocity  that body env | the same with the clip's velocities (`track_velocity`, `track_angular_velocity`,
+                     `track_joint_velocity`: `preprocessing.compute_velocity_from_kinematics` of the reference poses); both sides run
+                     the body instances, and the final states must be identical, with and without --actor
   --option restart   a pose env with max_pos_error 1e9 (the family its multi-step launches would otherwise run) | the same with
                      `clip_restarts` 1 | with 8
 
 All envs: rodent_optimized.xml, CG 8/8, n_frames 10, --num-envs envs through Episode(150) + AutoReset in multi-step launches, tracking a
 synthetic reference pose (identity quaternion, qpos0's joints) with the default weights and scales.  Default: random actions through
-`rr_env_unroll`, --unroll env steps per launch -- the workload of bench.py config 2.  --actor (poseterm, body, restart): the one-launch
+`rr_env_unroll`, --unroll env steps per launch -- the workload of bench.py config 2.  --actor (poseterm, body, velocity, restart): the one-launch
 rollout with the actor inside (`rr_env_unroll_policy`, a 4 x 32 policy, one segment of --unroll steps per launch).  After two warm-up
 launches per side, each repeat times --launches launches per side, in the order above, with a host clock around a device synchronise;
 the medians, the per-repeat values, the ranges and the ratios against the first side are printed as one JSON line.
 
-usage: python tools/bench_pose_options.py --option {pose,refobs,poseterm,body,restart} [--actor] [--frames 5] [--num-envs 2048]
+usage: python tools/bench_pose_options.py --option {pose,refobs,poseterm,body,velocity,restart} [--actor] [--frames 5] [--num-envs 2048]
                                           [--unroll 50] [--launches 4] [--repeats 7] [--out FILE]"""
 import argparse
 import json
@@ -44,15 +47,22 @@ class Option(NamedTuple):
     actor: bool
     check: Callable
     identical: Optional[tuple] = None
+    identical_with_actor: bool = False      # whether that claim is also checked under --actor
 
 
 def _alive(st):
     return float(st.metrics["quat_reward"].max()) > 0 and bool(torch.isfinite(st.obs).all())
 
 
-def options(frames: int, bodies: Callable) -> dict:
-    """The table.  `bodies`: first side's env -> track_bodies (a callable keyword is called with that env)."""
+def options(frames: int, bodies: Callable, velocity: dict) -> dict:
+    """The table.  `bodies`: an env of the model -> track_bodies (a callable keyword is called with the first side's env, or a one-env
+    probe while that side is being built); `velocity`: the three velocity keywords."""
+    body = dict(track_bodies=bodies, end_effector_ids=END_EFFECTORS)
     return {
+        "velocity": Option((("body", body), ("velocity", dict(body, **velocity))), True, True,
+                           lambda st: _alive(st) and all(bool(torch.isfinite(st.metrics[k]).all()) and float(st.metrics[k].max()) > 0
+                                                         for k in ("lin_vel_reward", "ang_vel_reward", "joint_vel_reward")),
+                           ("final_states_identical", "velocity"), True),
         "pose": Option((("plain", {}), ("pose", {})), False, False, lambda st: float(st.metrics["quat_reward"].max()) > 0),
         "refobs": Option((("pose", {}), ("refobs", dict(reference_obs_frames=frames))), True, False, _alive),
         "poseterm": Option((("pose", {}), ("poseterm", NEVER)), True, True, lambda st: float(st.metrics["pose_fail"].max()) == 0.0 and _alive(st),
@@ -66,7 +76,7 @@ def options(frames: int, bodies: Callable) -> dict:
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--option", required=True, choices=("pose", "refobs", "poseterm", "body", "restart"))
+    ap.add_argument("--option", required=True, choices=("pose", "refobs", "poseterm", "body", "velocity", "restart"))
     ap.add_argument("--actor", action="store_true")
     ap.add_argument("--frames", type=int, default=5)
     ap.add_argument("--num-envs", type=int, default=2048)
@@ -85,14 +95,21 @@ def main():
     q0 = np.asarray(mjcf.load_blob(assets.asset_path("rodent_optimized"))["qpos0"], np.float64)
     quat, joints = np.tile([1.0, 0.0, 0.0, 0.0], (T, 1)), np.tile(q0[7:], (T, 1))
     qpos = np.concatenate([np.asarray(track, np.float64), quat, joints], axis=1)
-    opt = options(args.frames, lambda env: preprocessing.extract_features(env, qpos).body_positions)[args.option]
+    qvel = preprocessing.compute_velocity_from_kinematics(np.concatenate([qpos, qpos[-1:]], axis=0), 0.02)      # [T, nv], the last row zero
+    velocity = dict(track_velocity=qvel[:, :3], track_angular_velocity=qvel[:, 3:6], track_joint_velocity=qvel[:, 6:])
+    opt = options(args.frames, lambda env: preprocessing.extract_features(env, qpos).body_positions, velocity)[args.option]
     if args.actor and not opt.actor:
-        ap.error(f"--actor: --option {args.option} has no such mode (poseterm, body and restart have)")
+        ap.error(f"--actor: --option {args.option} has no such mode (poseterm, body, velocity and restart have)")
     dev = torch.device("cuda:0")
     keys = jax_random.split(jax_random.PRNGKey(0), N)
     first, sides = opt.sides[0][0], {}
+
+    def model_env():      # an env to run forward kinematics on: the first side's, or a probe while that side is being built
+        if first in sides:
+            return sides[first]["env"]
+        return envs.get_environment("rodent", track_pos=track, num_envs=1, xml_path="rodent_optimized.xml", device=dev)
     for name, kw in opt.sides:
-        kw = {k: (v(sides[first]["env"]) if callable(v) else v) for k, v in kw.items()}
+        kw = {k: (v(model_env()) if callable(v) else v) for k, v in kw.items()}
         if opt.pose_base or name != first:
             kw.update(track_quat=quat, track_joints=joints)
         env = envs.get_environment("rodent", track_pos=track, num_envs=N, xml_path="rodent_optimized.xml", iterations=8, ls_iterations=8, device=dev, **kw)
@@ -146,7 +163,7 @@ def main():
         res["per_repeat_time_ratio" if len(others) == 1 else name + "_per_repeat_time_ratio"] = [
             round(float(a / b), 5) for a, b in zip(sides[name]["ms"], sides[first]["ms"])]
         assert opt.check(sides[name]["state"]), (args.option, name)
-    if opt.identical and not args.actor:
+    if opt.identical and (not args.actor or opt.identical_with_actor):
         key, name = opt.identical
         res[key] = bool(torch.equal(sides[name]["state"].pipeline_state.qpos, sides[first]["state"].pipeline_state.qpos))
     line = json.dumps(res)
