@@ -410,10 +410,13 @@ struct rr_batch {
   rr_clip_restart_io restart = {};      // clip restarts of the multi-step launches (rr_batch_set_clip_restarts); frames null: off; set only with a pose block
   bool solve_lds = false;               // rr_batch_set_solve_resident(b, 0): production single-step launches run rr_matlds_kernel
   rr_vel_io vel = {};                   // velocity tracking of the env steps (rr_batch_set_velocity_tracking); track_vel null: off; set only with a pose block
+  rr_clip_library_io lib = {};          // clip library of the env launches (rr_batch_set_clip_library); both pointers null: off; set only with a pose block
+  bool has_clip_library() const { return lib.clip_lengths || lib.bank_clips; }
   bool has_env_params() const { return env_dof_f || env_act_f || env_con_f; }
 };
 
 static const char* pose_eval_refusal(const rr_batch* b) {
+  if (b && b->has_clip_library()) return "rr_env_unroll_eval: no evaluation instance reads per-clip lengths or moves an env to another clip (rr_batch_set_clip_library is on); evaluate step by step";
   if (b && b->restart.frames) return "rr_env_unroll_eval: no evaluation instance restores from the bank of start states (rr_batch_set_clip_restarts is on); evaluate step by step";
   if (b && b->body.track_bodies) return "rr_env_unroll_eval: no evaluation instance rewards the body positions (rr_batch_set_body_tracking is on); evaluate step by step";
   if (b && b->vel.track_vel) return "rr_env_unroll_eval: no evaluation instance rewards the velocities (rr_batch_set_velocity_tracking is on); evaluate step by step";
@@ -703,13 +706,16 @@ static int launch(rr_batch* b, const Launch& L) {
   // Any of the first four selects V_BODY, clip restarts V_RESTART (rr_kernel.h rr_body_kernel: one instance for every combination);
   // an env step with a termination block and neither a body nor a velocity block runs V_POSETERM, the same computation without the
   // `if (BODY)` code.  An option the batch does not carry reaches the kernel as zero frames, thresholds that no error exceeds with a
-  // null pose_fail, a null track_bodies, a null track_vel
+  // null pose_fail, a null track_bodies, a null track_vel.  The clip library (rr_batch_set_clip_library) counts as an option of the env
+  // steps too: only the BODY instances read clip_len, bank_clips and clip_out, so such a batch never runs V_POSE or V_POSETERM.  The
+  // lengths also go to the resets that run V_BODY (reference frames); the other resets stay on their variant and read none
   const bool pose_step = b->pose.track_pose && L.env && L.mode == 1;
   const bool refobs = b->ref_frames > 0 && b->pose.track_pose && L.env;
   const bool pose = pose_step || refobs;
   const bool pterm = b->pterm.fail && pose_step, body = b->body.track_bodies && pose_step, restart = b->restart.frames && pose_step && L.un && !L.ev;
   const bool vel = b->vel.track_vel && pose_step;
-  const bool options = refobs || pterm || body || restart || vel;
+  const bool library = b->has_clip_library() && pose_step;
+  const bool options = refobs || pterm || body || restart || vel || library;
   if (options) io.pose_max_pos = io.pose_max_quat = io.pose_max_joint = INFINITY;
   if (refobs) io.ref_frames = b->ref_frames;
   if (restart) {
@@ -725,6 +731,12 @@ static int launch(rr_batch* b, const Launch& L) {
     io.vel_lin_w = b->vel.lin_weight; io.vel_lin_k = b->vel.lin_scale; io.vel_ang_w = b->vel.ang_weight; io.vel_ang_k = b->vel.ang_scale;
     io.vel_joint_w = b->vel.joint_weight; io.vel_joint_k = b->vel.joint_scale;
   }
+  if (b->has_clip_library() && (pose_step || refobs)) io.clip_len = b->lib.clip_lengths;
+  if (library && restart && b->lib.bank_clips) {
+    if (!io.clip) return fail(RR_EINVAL, "launch: clip library: bank_clips needs the env io's clip ids");
+    if (io.clip == b->lib.clip_out) return fail(RR_EINVAL, "launch: clip library: clip_out may not alias the env io's clip");
+    io.bank_clips = b->lib.bank_clips; io.clip_out = b->lib.clip_out;
+  }
   if (pterm) { io.pose_fail = b->pterm.fail; io.pose_max_pos = b->pterm.max_pos; io.pose_max_quat = b->pterm.max_quat; io.pose_max_joint = b->pterm.max_joint; }
   if (pose) {
     io.track_pose = b->pose.track_pose; io.pose_metrics = b->pose.pose_metrics;
@@ -733,7 +745,7 @@ static int launch(rr_batch* b, const Launch& L) {
   }
   if (pose && params) return fail(RR_EUNSUPPORTED, "launch: pose tracking: no pose instance reads per-env parameters (this batch carries some)");
   if (pose && (io.dbg || geom || b->prof)) return fail(RR_EUNSUPPORTED, "launch: pose tracking: no debug dump, contact-geometry outputs or profile build with track_pose (diagnostic instances have no pose form)");
-  Variant v = b->prof ? V_PROFILE : ((io.dbg || geom) ? V_DEBUG : (params ? V_RAND : (restart ? V_RESTART : (pterm && !body && !vel ? V_POSETERM : (options ? V_BODY : (pose ? V_POSE : V_PROD))))));
+  Variant v = b->prof ? V_PROFILE : ((io.dbg || geom) ? V_DEBUG : (params ? V_RAND : (restart ? V_RESTART : (pterm && !body && !vel && !library ? V_POSETERM : (options ? V_BODY : (pose ? V_POSE : V_PROD))))));
   // two-tree model, physics only, no diagnostics: one wavefront per replica (rr_kernel.h PAIR)
   const bool pair = m->pair_ok && v == V_PROD && !L.env && !L.out && !L.un && !b->env_map && !b->cost && m->solver != 2;
   if (pair) v = V_PAIR;
@@ -821,7 +833,7 @@ extern "C" int rr_env_unroll_policy(rr_batch* b, const rr_state* in, const rr_st
 }
 extern "C" int rr_batch_eval_supported(const rr_batch* b) {
   if (!b) return fail(RR_EINVAL, "rr_batch_eval_supported: null batch");
-  const bool options = b->ref_frames > 0 || b->pterm.fail || b->body.track_bodies || b->restart.frames || b->vel.track_vel;      // of the pose family: none has an evaluation instance
+  const bool options = b->ref_frames > 0 || b->pterm.fail || b->body.track_bodies || b->restart.frames || b->vel.track_vel || b->has_clip_library();      // of the pose family: none has an evaluation instance
   const Variant v = b->prof ? V_PROFILE : (b->has_env_params() ? V_RAND : (options ? V_BODY : V_PROD));
   return (select(b->m, F_EVAL, v, b).kern && !actor_limit(b->m, nullptr)) ? 1 : 0;
 }
@@ -1433,6 +1445,69 @@ extern "C" int rr_wrap_clip_restart(int32_t num_envs, int32_t narr, const float*
   return RR_OK;
 }
 
+// The same with the clip library (rr_clip_library_io's rule, one env step): the clip's end is taken at the length of the clip the step
+// was made on, and where done the bank entry's clip comes back with its frame.  clip is finished in place; null pointers switch the
+// two additions off one by one.
+__global__ void rr_wrap_library_kernel(const RRWrapArgs A, const float* __restrict__ prev_done, const float* __restrict__ prev_steps,
+                                       float* __restrict__ done, float* __restrict__ steps, float* __restrict__ truncation,
+                                       float episode_length, float action_repeat, int* __restrict__ cur_frame, const int* __restrict__ bank_frames,
+                                       const int* __restrict__ slot_in, int* __restrict__ slot_out, int num_slots, int track_len, int end_at_clip_end,
+                                       int* __restrict__ clip, const int* __restrict__ bank_clips, const int* __restrict__ clip_lengths) {
+  const int e = blockIdx.x, N = gridDim.x;
+  const float s0 = prev_done[e] != 0.0f ? 0.0f : prev_steps[e];
+  const float s1 = s0 + action_repeat;
+  const int new_frame = cur_frame[e];
+  int c = clip ? clip[e] : 0;
+  c = c < 0 ? 0 : c;
+  int len = track_len;
+  if (clip_lengths) { len = clip_lengths[c]; len = len < 1 ? 1 : (len > track_len ? track_len : len); }
+  const bool over = s1 >= episode_length || (end_at_clip_end && new_frame >= len - 1);
+  const float d_env = done[e];
+  const float d_out = over ? 1.0f : d_env;
+  int slot = slot_in[e];
+  slot = slot < 0 ? 0 : (slot > num_slots - 1 ? num_slots - 1 : slot);      // clamped into the bank
+  if (d_out != 0.0f) slot = slot + 1 >= num_slots ? 0 : slot + 1;
+  const size_t row = (size_t)slot * N + e;
+  const int frame = d_out != 0.0f ? bank_frames[row] : new_frame;
+  if (d_out != 0.0f && bank_clips) c = bank_clips[row];
+  __syncthreads();                       // every thread has read done[e], cur_frame[e] and clip[e] before thread 0 rewrites them
+  if (threadIdx.x == 0) {
+    steps[e] = s1; truncation[e] = over ? 1.0f - d_env : 0.0f; done[e] = d_out; cur_frame[e] = frame; slot_out[e] = slot;
+    if (clip) clip[e] = c;
+  }
+  if (d_out != 0.0f) {
+    for (int a = 0; a < A.narr; ++a) {
+      const int w = A.width[a];
+      const float* src = A.first[a] + row * w;
+      float* dst = A.cur[a] + (size_t)e * w;
+      for (int i = threadIdx.x; i < w; i += blockDim.x) dst[i] = src[i];
+    }
+  }
+}
+
+extern "C" int rr_wrap_clip_library(int32_t num_envs, int32_t narr, const float* const* first, float* const* cur, const int32_t* widths,
+                                    const float* prev_done, const float* prev_steps, float* done, float* steps, float* truncation,
+                                    float episode_length, float action_repeat, int32_t* cur_frame, const int32_t* bank_frames,
+                                    const int32_t* slot_in, int32_t* slot_out, int32_t num_slots, int32_t track_len, int32_t end_at_clip_end,
+                                    int32_t* clip, const int32_t* bank_clips, const int32_t* clip_lengths, void* stream) {
+  if (num_envs <= 0 || narr < 0 || narr > RR_WRAP_MAX || !prev_done || !prev_steps || !done || !steps || !truncation || !cur_frame || !bank_frames ||
+      !slot_in || !slot_out || track_len <= 0 || (bank_clips && !clip))
+    return fail(RR_EINVAL, "rr_wrap_clip_library: bad argument");
+  if (num_slots < 1 || num_slots > 64) return fail(RR_EINVAL, "rr_wrap_clip_library: num_slots must lie in 1 .. 64");
+  RRWrapArgs A;
+  memset(&A, 0, sizeof(A));
+  A.narr = narr;
+  for (int i = 0; i < narr; ++i) {
+    if (!first[i] || !cur[i] || widths[i] <= 0) return fail(RR_EINVAL, "rr_wrap_clip_library: null array");
+    A.first[i] = first[i]; A.cur[i] = cur[i]; A.width[i] = widths[i];
+  }
+  hipLaunchKernelGGL(rr_wrap_library_kernel, dim3(num_envs), dim3(256), 0, (hipStream_t)stream, A, prev_done, prev_steps, done, steps, truncation,
+                     episode_length, action_repeat, cur_frame, bank_frames, slot_in, slot_out, num_slots, track_len, end_at_clip_end,
+                     clip, bank_clips, clip_lengths);
+  HIPCHK(hipGetLastError());
+  return RR_OK;
+}
+
 extern "C" int rr_debug_layout(const rr_batch* b, const char*** names, const int32_t** offsets, const int32_t** sizes) {
   if (!b) return fail(RR_EINVAL, "rr_debug_layout: null batch");
   if (names) *names = const_cast<const char**>(b->m->dbg_cnames.data());
@@ -1473,6 +1548,7 @@ extern "C" int rr_batch_set_pose(rr_batch* b, const rr_pose_io* p) {
   if (!b) return fail(RR_EINVAL, "rr_batch_set_pose: null batch");
   if (!p || (!p->track_pose && !p->pose_metrics)) {
     if (b->ref_frames > 0) return fail(RR_EINVAL, "rr_batch_set_pose: the batch carries reference frames (rr_batch_set_reference_obs), whose rows come from the pose block: set them to 0 first");
+    if (b->has_clip_library()) return fail(RR_EINVAL, "rr_batch_set_pose: the batch carries a clip-library block (rr_batch_set_clip_library), which serves pose envs only: clear it first");
     if (b->restart.frames) return fail(RR_EINVAL, "rr_batch_set_pose: the batch carries a clip-restart block (rr_batch_set_clip_restarts), which serves pose envs only: clear it first");
     if (b->vel.track_vel) return fail(RR_EINVAL, "rr_batch_set_pose: the batch carries a velocity-tracking block (rr_batch_set_velocity_tracking), whose rows are indexed like the pose block's: clear it first");
     if (b->body.track_bodies) return fail(RR_EINVAL, "rr_batch_set_pose: the batch carries a body-tracking block (rr_batch_set_body_tracking), whose rows are indexed like the pose block's: clear it first");
@@ -1563,12 +1639,31 @@ extern "C" int rr_batch_clip_restarts_supported(const rr_batch* b, int32_t with_
 }
 extern "C" int rr_batch_set_clip_restarts(rr_batch* b, const rr_clip_restart_io* r) {
   if (!b) return fail(RR_EINVAL, "rr_batch_set_clip_restarts: null batch");
-  if (!r) { b->restart = rr_clip_restart_io{}; return RR_OK; }
+  if (!r) {
+    if (b->lib.bank_clips) return fail(RR_EINVAL, "rr_batch_set_clip_restarts: the batch carries a clip-library block with bank_clips (rr_batch_set_clip_library), the clips of this block's entries: clear it first");
+    b->restart = rr_clip_restart_io{};
+    return RR_OK;
+  }
   if (const char* why = pose_option_limit(b, F_UNROLL, b->ref_frames, false)) return fail(RR_EUNSUPPORTED, std::string("rr_batch_set_clip_restarts: ") + why);
   if (!b->pose.track_pose) return fail(RR_EINVAL, "rr_batch_set_clip_restarts: needs a pose block (rr_batch_set_pose) first: clip restarts serve pose envs only");
   if (!r->frames || !r->slot_in || !r->slot_out) return fail(RR_EINVAL, "rr_batch_set_clip_restarts: null frames, slot_in or slot_out");
   if (r->num_slots < 1 || r->num_slots > 64) return fail(RR_EINVAL, "rr_batch_set_clip_restarts: num_slots must lie in 1 .. 64");
   b->restart = *r;
+  return RR_OK;
+}
+extern "C" int rr_batch_clip_library_supported(const rr_batch* b, int32_t with_actor) {
+  if (!b) return fail(RR_EINVAL, "rr_batch_clip_library_supported: null batch");
+  return supported("rr_batch_clip_library_supported", pose_option_limit(b, F_STEP, b->ref_frames, with_actor != 0));
+}
+extern "C" int rr_batch_set_clip_library(rr_batch* b, const rr_clip_library_io* l) {
+  if (!b) return fail(RR_EINVAL, "rr_batch_set_clip_library: null batch");
+  if (!l) { b->lib = rr_clip_library_io{}; return RR_OK; }
+  if (const char* why = pose_option_limit(b, F_STEP, b->ref_frames, false)) return fail(RR_EUNSUPPORTED, std::string("rr_batch_set_clip_library: ") + why);
+  if (!b->pose.track_pose) return fail(RR_EINVAL, "rr_batch_set_clip_library: needs a pose block (rr_batch_set_pose) first: lengths and clip changes serve pose envs only");
+  if (!l->clip_lengths && !l->bank_clips) return fail(RR_EINVAL, "rr_batch_set_clip_library: null clip_lengths and bank_clips (NULL clears the block)");
+  if (l->bank_clips && !b->restart.frames) return fail(RR_EINVAL, "rr_batch_set_clip_library: bank_clips needs a clip-restart block (rr_batch_set_clip_restarts) first: they are the clips of its entries");
+  if (l->bank_clips && !l->clip_out) return fail(RR_EINVAL, "rr_batch_set_clip_library: bank_clips needs clip_out");
+  b->lib = *l;
   return RR_OK;
 }
 extern "C" int32_t rr_batch_obs_width(const rr_batch* b) {

@@ -335,6 +335,19 @@ struct RRIO {
   const float* track_vel;
   float* vel_metrics;          // [N][3]
   float vel_lin_w, vel_lin_k, vel_ang_w, vel_ang_k, vel_joint_w, vel_joint_k;
+  // CLIP LIBRARY (BODY instances, rr_body_kernel and rr_restart_kernel; no other instance reads these; rr_batch_set_clip_library).
+  // clip_len [num_clips] (one entry without `clip`): clip c consists of rows 0 .. clip_len[c] - 1 of every [num_clips][track_len][..]
+  // array, the rows behind them are padding that nothing reads.  Wherever an env on clip c clamps a frame into 0 .. track_len - 1 it
+  // clamps into 0 .. L - 1 instead, L = clip_len[c] clamped into 1 .. track_len (rr_clip_frames), and the clip's end of CLIP RESTARTS is
+  // new_frame >= L - 1.  The row stride stays track_len.  A null clip_len: every clip has track_len frames.
+  // bank_clips [K][N] (RESTART instances, next to restart_frames): the clip of each bank entry.  The rule gains one line,
+  //   done: clip <- bank_clips[slot'] (clamped into 0 .. num_clips - 1);  else the clip the env is on,
+  // the launch reads clip[env] once, carries the id wave-uniform through its steps and stores it to clip_out[env] after the last one
+  // (`clip` itself is read only).  A null bank_clips: every entry on the env's clip, nothing stored.
+  // Only integer bounds and row bases change: no reward expression gains a use.  Fetched by narrow loads where they are used.
+  const int* clip_len;
+  const int* bank_clips;
+  int* clip_out;               // [N]
 };
 
 // ------------------------------------------------------------------------------------------ small math
@@ -2663,7 +2676,8 @@ static_assert(offsetof(RRIO, endeff_k) + sizeof(float) == offsetof(RRIO, restart
 static_assert(offsetof(RRIO, restart_frames) + 3 * sizeof(int*) == offsetof(RRIO, restart_K), "the slot count follows the three clip-restart pointers without padding");
 static_assert(offsetof(RRIO, restart_end) + sizeof(int) == offsetof(RRIO, track_vel) && offsetof(RRIO, track_vel) % 8 == 0, "the velocity-tracking members follow the clip-restart members without padding");
 static_assert(offsetof(RRIO, track_vel) + 2 * sizeof(float*) == offsetof(RRIO, vel_lin_w), "the weights and scales follow the two velocity-tracking pointers without padding");
-static_assert(offsetof(RRIO, vel_joint_k) + sizeof(float) == sizeof(RRIO), "the velocity-tracking members close RRIO without padding");
+static_assert(offsetof(RRIO, vel_joint_k) + sizeof(float) == offsetof(RRIO, clip_len) && offsetof(RRIO, clip_len) % 8 == 0, "the clip-library members follow the velocity-tracking members without padding");
+static_assert(offsetof(RRIO, clip_len) + 3 * sizeof(int*) == sizeof(RRIO), "the three clip-library pointers close RRIO without padding");
 // ... and so are the model tables outside the solver's loops: RRTables is re-read at the head of each phase that indexes a table
 // (narrow scalar loads next to an existing hand-off; the unused members' loads are dead), so no table pointer is held across the
 // substep.  The loops' own tables are the exception (RRLoopTables, taken once from the parameter).
@@ -2713,6 +2727,22 @@ template <bool REFOBS, class DT>
 static __device__ __forceinline__ int rr_obs_width(const DT& D) {
   if constexpr (REFOBS) return D.obs_dim + load_io_member<int>(offsetof(RRIO, ref_frames)) * D.nq;
   else return D.obs_dim;
+}
+
+// Frames of clip `c` (already clamped into 0 .. num_clips - 1) = the exclusive upper bound of every frame clamp of an env on it.  BODY
+// instances (RRIO, CLIP LIBRARY): clip_len[c] clamped into 1 .. track_len, so no frame addresses outside a clip's rows; a null clip_len,
+// and every other instance: track_len itself, the expression those instances had before.  `c` is wave-uniform: a scalar load, read where
+// it is used.
+template <bool BODY>
+static __device__ __forceinline__ int rr_clip_frames(int c, int track_len) {
+  if constexpr (BODY) {
+    const int* cl = load_io_member<const int*>(offsetof(RRIO, clip_len));
+    if (!cl) return track_len;
+    const int n = __builtin_amdgcn_readfirstlane(cl[c]);
+    return n < 1 ? 1 : (n > track_len ? track_len : n);
+  } else {
+    return track_len;
+  }
 }
 
 // RAND instances: the tables with the three randomisable ones advanced to environment `env`'s rows.  `env` is wave-uniform, the

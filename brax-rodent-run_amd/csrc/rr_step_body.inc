@@ -43,6 +43,7 @@
   float u_steps = 0.0f, u_prev_done = 0.0f;
   int u_frame = 0;
   int u_slot = 0;                // RESTART: the bank entry the env's next restore follows (RRIO, CLIP RESTARTS)
+  int u_clip = 0;                // RESTART: the clip the env is on, clamped; a restore may move it (RRIO, CLIP LIBRARY); 0 without clip ids
   unsigned u_work = 0;
   int u_overflow = 0;            // DYN: some step of this launch dropped pairs (RRIO::cost bit 31 of a multi-step launch)
   if (UNROLL) {
@@ -55,6 +56,11 @@
       const int rk = load_io_member<int>(offsetof(RRIO, restart_K));
       u_slot = __builtin_amdgcn_readfirstlane(load_io_member<const int*>(offsetof(RRIO, restart_slot_in))[env]);
       u_slot = u_slot < 0 ? 0 : (u_slot > rk - 1 ? rk - 1 : u_slot);
+      if (const int* cp = load_io_member<const int*>(offsetof(RRIO, clip))) {      // read once: the epilogues below take the id from here
+        const int nc = load_io_member<int>(offsetof(RRIO, num_clips));
+        u_clip = __builtin_amdgcn_readfirstlane(cp[env]);
+        u_clip = u_clip < 0 ? 0 : (u_clip > nc - 1 ? nc - 1 : u_clip);
+      }
     }
   }
   int niter = 0;
@@ -185,11 +191,12 @@
           int bc = 0;
           if (const int* bclip = load_io_member<const int*>(offsetof(RRIO, clip))) {
             const int nc = load_io_member<int>(offsetof(RRIO, num_clips));
-            bc = bclip[env];
+            bc = RESTART ? u_clip : bclip[env];
             bc = bc < 0 ? 0 : (bc > nc - 1 ? nc - 1 : bc);
           }
+          const int bcl = rr_clip_frames<BODY>(bc, blen);      // the clip's own frames; the row stride below stays blen
           int bf = UNROLL ? u_frame : load_io_member<const int*>(offsetof(RRIO, cur_frame_in))[env];
-          bf = bf < 0 ? 0 : (bf > blen - 1 ? blen - 1 : bf);
+          bf = bf < 0 ? 0 : (bf > bcl - 1 ? bcl - 1 : bf);
           const float* brow = tbod + ((size_t)bc * (size_t)blen + (size_t)bf) * (size_t)(3 * D.nbody);
           float sb = 0.0f, se = 0.0f;
           for (int b = lane; b < D.nbody; b += RR_LANES) {
@@ -385,9 +392,19 @@
     // is clamped, so none addresses outside the array; the frame clamp below stays per clip.  Null clip: io.track_pos as it is.
     const float* track = io.track_pos;
     if (io.clip) {
-      int c = io.clip[env];
+      int c = RESTART ? u_clip : io.clip[env];
       c = c < 0 ? 0 : (c > io.num_clips - 1 ? io.num_clips - 1 : c);
       track += (size_t)3 * (size_t)io.track_len * (size_t)c;
+    }
+    // CLIP LIBRARY (BODY instances): frames of the env's clip, the bound of the two position clamps below and of the clip's end.  Every
+    // clamp of this epilogue keeps the expression it has in the other instances, and a BODY instance lowers the result to the clip's
+    // last frame behind it (L <= track_len, so the two clamps are one clamp into 0 .. L - 1): the code shared with the other
+    // instances is theirs token for token.
+    int tlen = io.track_len;
+    if (BODY) {
+      int tc = 0;
+      if (io.clip) { tc = RESTART ? u_clip : io.clip[env]; tc = tc < 0 ? 0 : (tc > io.num_clips - 1 ? io.num_clips - 1 : tc); }
+      tlen = rr_clip_frames<BODY>(tc, io.track_len);
     }
     const int ow = rr_obs_width<REFOBS>(D);      // row stride of obs / t_obs / first_obs (REFOBS: with the reference blocks)
     float* ob = EVAL ? io.t_obs + ((size_t)env * 2 + ((ut + 1) & 1)) * ow : ACTOR ? io.t_obs + rr_traj_obs(io, num_envs, env, rr_traj(io, ut).u, rr_traj(io, ut).t + 1) * ow : io.obs + (size_t)env * ow;
@@ -406,6 +423,7 @@
     if (lane < 3) {  // xmat[1] @ (track_pos[frame + 1] - qpos[:3]); JAX clamps the gather index
       int fi = new_frame + 1;
       fi = fi < 0 ? 0 : (fi > io.track_len - 1 ? io.track_len - 1 : fi);
+      if (BODY) fi = fi > tlen - 1 ? tlen - 1 : fi;
       const v3 v = ld3(track + 3 * fi) - ld3(w.s_qpos);
       float m1[9];
       quat_to_mat(m1, xq1);
@@ -432,7 +450,9 @@
         float* rob = ob;
         asm volatile("" : "+s"(rob) : : "memory");
         int rc = 0;
-        if (io.clip) { rc = io.clip[env]; rc = rc < 0 ? 0 : (rc > io.num_clips - 1 ? io.num_clips - 1 : rc); }
+        if (io.clip) { rc = RESTART ? u_clip : io.clip[env]; rc = rc < 0 ? 0 : (rc > io.num_clips - 1 ? io.num_clips - 1 : rc); }
+        int rcl = io.track_len;
+        if (BODY) rcl = rr_clip_frames<BODY>(rc, io.track_len);
         float xo[4], m1[9];
 #pragma unroll
         for (int k = 0; k < 4; ++k) { xo[k] = xq1[k]; asm volatile("" : "+v"(xo[k])); }
@@ -441,6 +461,7 @@
         for (int h = 1; h <= H; ++h) {
           int fh = new_frame + h;
           fh = fh < 0 ? 0 : (fh > io.track_len - 1 ? io.track_len - 1 : fh);
+          if (BODY) fh = fh > rcl - 1 ? rcl - 1 : fh;
           const float* rrow = tpose + ((size_t)rc * (size_t)io.track_len + (size_t)fh) * (size_t)(D.nq - 3);
           float* blk = rob + D.obs_dim + (h - 1) * D.nq;
           for (int i = rl; i < D.nq - 7; i += RR_LANES) blk[7 + i] = rrow[4 + i] - w.s_qpos[7 + i];
@@ -484,8 +505,9 @@
         if (tpose) {
 #pragma clang fp contract(off)
           int pc = 0;
-          if (io.clip) { pc = io.clip[env]; pc = pc < 0 ? 0 : (pc > io.num_clips - 1 ? io.num_clips - 1 : pc); }
-          const int pf = old_frame < 0 ? 0 : (old_frame > io.track_len - 1 ? io.track_len - 1 : old_frame);
+          if (io.clip) { pc = RESTART ? u_clip : io.clip[env]; pc = pc < 0 ? 0 : (pc > io.num_clips - 1 ? io.num_clips - 1 : pc); }
+          int pf = old_frame < 0 ? 0 : (old_frame > io.track_len - 1 ? io.track_len - 1 : old_frame);
+          if (BODY) { const int pcl = rr_clip_frames<BODY>(pc, io.track_len); pf = pf > pcl - 1 ? pcl - 1 : pf; }
           prow = tpose + ((size_t)pc * (size_t)io.track_len + (size_t)pf) * (size_t)(D.nq - 3);
           for (int i = lane; i < D.nq - 7; i += RR_LANES) { const float e = w.s_qpos[7 + i] - prow[4 + i]; const float ee = e * e; pe2 = pe2 + ee; }
           pe2 = wave_sum(pe2);
@@ -504,8 +526,9 @@
         if (tvel) {
 #pragma clang fp contract(off)
           int vc = 0;
-          if (io.clip) { vc = io.clip[env]; vc = vc < 0 ? 0 : (vc > io.num_clips - 1 ? io.num_clips - 1 : vc); }
-          const int vf = old_frame < 0 ? 0 : (old_frame > io.track_len - 1 ? io.track_len - 1 : old_frame);
+          if (io.clip) { vc = RESTART ? u_clip : io.clip[env]; vc = vc < 0 ? 0 : (vc > io.num_clips - 1 ? io.num_clips - 1 : vc); }
+          const int vcl = rr_clip_frames<BODY>(vc, io.track_len);
+          const int vf = old_frame < 0 ? 0 : (old_frame > vcl - 1 ? vcl - 1 : old_frame);
           const float* vrow = tvel + ((size_t)vc * (size_t)io.track_len + (size_t)vf) * (size_t)D.nv;
           const int vl = opaque(lane);
           for (int i = vl; i < D.nv; i += RR_LANES) {
@@ -520,6 +543,7 @@
       }
       if (lane == 0) {
         int fi = old_frame < 0 ? 0 : (old_frame > io.track_len - 1 ? io.track_len - 1 : old_frame);
+        if (BODY) fi = fi > tlen - 1 ? tlen - 1 : fi;
         const v3 dx = ld3(w.s_qpos) - ld3(track + 3 * fi);
         // explicit roundings (no fused multiply-add left to the optimiser), so that the instances of the kernel form the reward from the
         // same operations: single-step and multi-step instances agree bit for bit (tests/test_gpu_env.py); the actor-inside instance to
@@ -641,8 +665,8 @@
       const bool wrapped = !EVAL || !(io.a_pad & RR_EVAL_RAW);      // EVAL without the wrappers: the env's own done, no step count, no restore
       if (wrapped) u_steps = (u_prev_done != 0.0f ? 0.0f : u_steps) + 1.0f;
       bool over = wrapped && u_steps >= io.episode_length;
-      if (RESTART) {      // new_frame >= T - 1: the new state's observation has no next frame left to read without clamping
-        if (load_io_member<int>(offsetof(RRIO, restart_end)) != 0 && new_frame >= io.track_len - 1) over = true;
+      if (RESTART) {      // new_frame >= L - 1, L the frames of the clip the step was made on: the new state's observation has no next frame left to read without clamping
+        if (load_io_member<int>(offsetof(RRIO, restart_end)) != 0 && new_frame >= tlen - 1) over = true;
       }
       const float done2 = over ? 1.0f : done_env, trunc = over ? 1.0f - done_env : 0.0f;
       u_prev_done = done2;
@@ -670,6 +694,11 @@
           if (u_slot >= load_io_member<int>(offsetof(RRIO, restart_K))) u_slot = 0;
           const size_t re = (size_t)u_slot * (size_t)num_envs + (size_t)env;      // row of the bank entry in every [K][N][width] array
           u_frame = __builtin_amdgcn_readfirstlane(load_io_member<const int*>(offsetof(RRIO, restart_frames))[re]);
+          if (const int* bcl = load_io_member<const int*>(offsetof(RRIO, bank_clips))) {      // CLIP LIBRARY: the entry's clip, clamped
+            const int nc = load_io_member<int>(offsetof(RRIO, num_clips));
+            const int c = __builtin_amdgcn_readfirstlane(bcl[re]);
+            u_clip = c < 0 ? 0 : (c > nc - 1 ? nc - 1 : c);
+          }
           w.sync();
           for (int i = lane; i < D.nq; i += RR_LANES) w.s_qpos[i] = io.first_qpos[re * D.nq + i];
           for (int i = lane; i < D.nv; i += RR_LANES) { w.s_qvel[i] = io.first_qvel[re * D.nv + i]; w.s_warm[i] = io.first_warm[re * D.nv + i]; }
@@ -705,6 +734,7 @@
         if (lane == 0) { io.done[env] = done2; if (wrapped) { io.steps_out[env] = u_steps; io.trunc_out[env] = trunc; } }
         if (RESTART) {      // the frame and the slot the next launch goes on from (lane 0 stored new_frame above: program order)
           if (lane == 0) { io.cur_frame[env] = u_frame; load_io_member<int*>(offsetof(RRIO, restart_slot_out))[env] = u_slot; }
+          if (lane == 0) { if (int* co = load_io_member<int*>(offsetof(RRIO, clip_out))) co[env] = u_clip; }      // CLIP LIBRARY: the clip the next launch goes on from
         }
         for (int i = lane; i < D.nq; i += RR_LANES) io.qpos[(size_t)env * D.nq + i] = w.s_qpos[i];
         for (int i = lane; i < D.nv; i += RR_LANES) { io.qvel[(size_t)env * D.nv + i] = w.s_qvel[i]; io.warm[(size_t)env * D.nv + i] = w.s_warm[i]; }

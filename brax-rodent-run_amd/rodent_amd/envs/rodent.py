@@ -47,31 +47,88 @@ def reset_draws(keys, nq: int, nv: int, reset_noise_scale: float, num_clips: Opt
     return start_frame, qpos_noise, qvel, clip
 
 
-def restart_bank_draws(keys, num_entries: int, nq: int, nv: int, reset_noise_scale: float, frame_range=(0, 100), num_clips: Optional[int] = None):
+def restart_bank_draws(keys, num_entries: int, nq: int, nv: int, reset_noise_scale: float, frame_range=(0, 100), num_clips: Optional[int] = None,
+                       across_clips: bool = False):
     """The host draws of the start bank of `Rodent(clip_restarts=K)`, without a device: `keys` uint32 [N, 2] -> (start_frame int32
     [K, N], qpos noise float32 [K, N, nq], qvel float32 [K, N, nv], clip int32 [N] or None).  Entry 0 is `reset_draws(keys)` itself,
     whatever K is.  Entry k = 1 .. K - 1 is `reset_draws(fold_in(keys, k))` -- qpos noise and qvel -- except its start frame, which is
-    `randint(lo, hi)` of that key's first subkey, `frame_range` = (lo, hi).  The clip is the one of `keys`: every entry follows it."""
+    `randint(lo, hi)` of that key's first subkey, `frame_range` = (lo, hi).  The clip is the one of `keys`: every entry follows it.
+    `across_clips` (`Rodent(restart_across_clips=True)`, needs `num_clips`): the clip is int32 [K, N] instead, entry k the clip that
+    `reset_draws(fold_in(keys, k), num_clips=C)` returns and the default discards -- no new key is consumed, no other draw moves."""
     keys = np.asarray(keys, dtype=np.uint32).reshape(-1, 2)
     lo, hi = frame_range
-    frames, noises, qvels = [], [], []
-    clip = None
+    frames, noises, qvels, clips = [], [], [], []
     for k in range(int(num_entries)):
         kk = keys if k == 0 else jax_random.fold_in(keys, k)
         f, noise, qvel, drawn = reset_draws(kk, nq, nv, reset_noise_scale, num_clips)
-        if k == 0:
-            clip = drawn
-        else:
+        if k > 0:
             f = jax_random.randint(jax_random.split(kk, 4)[:, 0], int(lo), int(hi))
-        frames.append(np.asarray(f, dtype=np.int32)); noises.append(noise); qvels.append(qvel)
+        frames.append(np.asarray(f, dtype=np.int32)); noises.append(noise); qvels.append(qvel); clips.append(drawn)
+    clip = clips[0] if not across_clips or clips[0] is None else np.stack(clips)
     return np.stack(frames), np.stack(noises), np.stack(qvels), clip
 
 
-def _check_clip_restarts(clip_restarts, restart_frame_range, end_at_clip_end, have_pose: bool, track_len: int):
+def fold_start_frames(start_frame, lengths: Optional[np.ndarray], clip=None) -> np.ndarray:
+    """The start frames of an env with per-clip lengths (`Rodent(clip_lengths=...)`), int32 like `start_frame` ([N] or [K, N]): the
+    draws folded into their clip, start = draw mod (L_c - 1) with c the entry's clip (`clip` broadcast against `start_frame`; None:
+    clip 0).  The identity wherever draw < L_c - 1, and every start is <= L_c - 2, so the track entry of the reset observation (frame
+    + 1) lies within the clip.  `lengths` None: the draws as they are."""
+    start_frame = np.asarray(start_frame, dtype=np.int32)
+    if lengths is None:
+        return start_frame
+    L = np.asarray(lengths, dtype=np.int64)[0 if clip is None else np.asarray(clip, dtype=np.int64)]
+    return (start_frame.astype(np.int64) % (L - 1)).astype(np.int32)
+
+
+def reference_rows(rows: np.ndarray, frame, clip=None, lengths: Optional[np.ndarray] = None) -> np.ndarray:
+    """The rows of a clip array `rows` [(C,) T, ...] (track_pos, the pose rows, track_bodies, track_vel) that an env on clip `clip` at
+    frame `frame` reads: rows[(clip,) clamp(frame, 0, L_c - 1)], L_c = `lengths`[clip] (None: T for every clip; `clip` None: clip 0 of
+    a [T, ...] array).  The one place the host restatements clamp a frame: `pose_rewards`, `pose_errors`, `body_rewards` and
+    `velocity_rewards` take the rows it returns, `reference_obs`, `reset_qpos` and `reset_qvel` call it with their `lengths` argument.
+    No row at or behind L_c is touched."""
+    frame = np.asarray(frame, dtype=np.int64)
+    T = rows.shape[0] if clip is None else rows.shape[1]
+    if clip is None:
+        last = T - 1 if lengths is None else int(np.asarray(lengths).reshape(-1)[0]) - 1
+        return rows[np.clip(frame, 0, last)]
+    c = np.clip(np.asarray(clip, dtype=np.int64), 0, rows.shape[0] - 1)
+    last = T - 1 if lengths is None else np.asarray(lengths, dtype=np.int64)[c] - 1
+    return rows[c, np.clip(frame, 0, last)]
+
+
+def _check_clip_library(clip_lengths, restart_across_clips, track: np.ndarray, have_pose: bool, clip_restarts: int):
+    """`clip_lengths` and `restart_across_clips` of `Rodent` against its (checked) `track` [(C,) T, 3] as (lengths int32 [C] or None,
+    flag).  ValueError for either without the pose arguments, lengths that are not integers of shape [C] (an int or [1] next to a
+    [T, 3] track) with 2 <= L_c <= T, and `restart_across_clips` without `clip_restarts >= 1` or without a clip axis."""
+    across = bool(restart_across_clips)
+    if (clip_lengths is not None or across) and not have_pose:
+        raise ValueError("clip_lengths / restart_across_clips need the reference pose: pass track_quat and track_joints")
+    if across and clip_restarts < 1:
+        raise ValueError("restart_across_clips=True needs clip_restarts >= 1: the clips belong to the entries of the start bank")
+    if across and track.ndim != 3:
+        raise ValueError("restart_across_clips=True needs a [C, T, 3] track_pos: a single [T, 3] track has no other clip to move to")
+    if clip_lengths is None:
+        return None, across
+    C_, T = (track.shape[0] if track.ndim == 3 else 1), track.shape[-2]
+    L = clip_lengths.detach().cpu().numpy() if torch.is_tensor(clip_lengths) else np.asarray(clip_lengths)
+    if L.dtype.kind not in "iu":
+        raise ValueError(f"clip_lengths must be integers, got dtype {L.dtype}")
+    if L.ndim == 0 and track.ndim == 2:
+        L = L.reshape(1)
+    if L.shape != (C_,):
+        raise ValueError(f"clip_lengths must have shape ({C_},) next to a track_pos of shape {track.shape}"
+                         f"{' (or be an int)' if track.ndim == 2 else ''}, got {tuple(L.shape)}")
+    if L.min() < 2 or L.max() > T:
+        raise ValueError(f"clip_lengths must lie in 2 .. T = {T} (a clip needs a frame to start at and a next one), got {int(L.min())} .. {int(L.max())}")
+    return np.ascontiguousarray(L, dtype=np.int32), across
+
+
+def _check_clip_restarts(clip_restarts, restart_frame_range, end_at_clip_end, have_pose: bool, track_len: int, have_lengths: bool = False):
     """`clip_restarts`, `restart_frame_range` and `end_at_clip_end` of `Rodent` as (K, (lo, hi), flag); ValueError for K outside 0 .. 64,
     any of the three without the pose arguments, `end_at_clip_end` with K = 0, lo < 0 or hi <= lo, and -- with `end_at_clip_end` -- a
     clip so short that some entry can start at its end (T - 1 <= the largest frame an entry can draw; 99 for entry 0): such an env would
-    truncate on every step."""
+    truncate on every step.  With `have_lengths` (`clip_lengths` given) that last refusal does not apply: every start is folded into
+    its clip (`fold_start_frames`), which guarantees what it checked."""
     if isinstance(clip_restarts, (bool, np.bool_)) or not isinstance(clip_restarts, (int, np.integer)) or not 0 <= int(clip_restarts) <= 64:
         raise ValueError(f"clip_restarts must be an int in 0 .. 64 (0: the first state comes back, the frame does not), got {clip_restarts!r}")
     K, end = int(clip_restarts), bool(end_at_clip_end)
@@ -86,7 +143,7 @@ def _check_clip_restarts(clip_restarts, restart_frame_range, end_at_clip_end, ha
     lo, hi = int(lo), int(hi)
     if lo < 0 or hi <= lo:
         raise ValueError(f"restart_frame_range = (lo, hi) needs 0 <= lo < hi (frames are drawn in [lo, hi)), got {(lo, hi)!r}")
-    if end:
+    if end and not have_lengths:
         largest = max(99, hi - 1) if K > 1 else 99
         if track_len - 1 <= largest:
             raise ValueError(f"end_at_clip_end=True: the clip has {track_len} frames, but an entry of the start bank can start at frame {largest}; "
@@ -94,25 +151,34 @@ def _check_clip_restarts(clip_restarts, restart_frame_range, end_at_clip_end, ha
     return K, (lo, hi), end
 
 
-def reset_qpos(qpos0, track: np.ndarray, start_frame, qpos_noise, clip=None, pose: Optional[np.ndarray] = None) -> np.ndarray:
+def reset_qpos(qpos0, track: np.ndarray, start_frame, qpos_noise, clip=None, pose: Optional[np.ndarray] = None, lengths=None) -> np.ndarray:
     """The qpos `Rodent.reset` starts from, float32 [N, nq], out of the draws of `reset_draws`: qpos0 with the root position replaced by
     track[(clip,) start_frame] (the frame clamped within the clip), plus the noise.  `pose` (the env's [(C,) T, nq - 3] rows, given with
-    `reset_to_reference=True`): qpos[3:] starts from pose[(clip,) start_frame] instead of qpos0[3:].  The draws are not touched."""
+    `reset_to_reference=True`): qpos[3:] starts from pose[(clip,) start_frame] instead of qpos0[3:].  `lengths` (int [C], the env's
+    `clip_lengths`): the clamp is the clip's own, and no row at or behind L_c is read.  The draws are not touched."""
     N = len(start_frame)
     qpos = np.tile(np.asarray(qpos0, dtype=np.float32), (N, 1))
-    fi = np.clip(start_frame, 0, track.shape[-2] - 1)
-    qpos[:, :3] = track[fi] if clip is None else track[clip, fi]
-    if pose is not None:
-        qpos[:, 3:] = pose[fi] if clip is None else pose[clip, fi]
+    if lengths is None:
+        fi = np.clip(start_frame, 0, track.shape[-2] - 1)
+        qpos[:, :3] = track[fi] if clip is None else track[clip, fi]
+        if pose is not None:
+            qpos[:, 3:] = pose[fi] if clip is None else pose[clip, fi]
+    else:
+        qpos[:, :3] = reference_rows(track, start_frame, clip, lengths)
+        if pose is not None:
+            qpos[:, 3:] = reference_rows(pose, start_frame, clip, lengths)
     return qpos + qpos_noise
 
 
-def reset_qvel(track_vel: np.ndarray, start_frame, qvel_noise, clip=None) -> np.ndarray:
+def reset_qvel(track_vel: np.ndarray, start_frame, qvel_noise, clip=None, lengths=None) -> np.ndarray:
     """The qvel `Rodent.reset` starts from with the clip's velocities given and `reset_to_reference=True`, float32 [N, nv], out of the
     draws of `reset_draws`: track_vel[(clip,) start_frame] (the env's [(C,) T, nv] rows, the frame clamped within the clip) plus the
-    noise, a float32 sum.  The draws are not touched."""
-    fi = np.clip(start_frame, 0, track_vel.shape[-2] - 1)
-    row = track_vel[fi] if clip is None else track_vel[clip, fi]
+    noise, a float32 sum.  `lengths`: as in `reset_qpos`.  The draws are not touched."""
+    if lengths is None:
+        fi = np.clip(start_frame, 0, track_vel.shape[-2] - 1)
+        row = track_vel[fi] if clip is None else track_vel[clip, fi]
+    else:
+        row = reference_rows(track_vel, start_frame, clip, lengths)
     return np.asarray(row, dtype=np.float32) + np.asarray(qvel_noise, dtype=np.float32)
 
 
@@ -124,8 +190,9 @@ def _check_track(track_pos) -> np.ndarray:
     return np.ascontiguousarray(t, dtype=np.float32)
 
 
-def _check_clip(clip, num_clips: Optional[int], num_envs: int) -> np.ndarray:
-    """Explicit clip ids of `Rodent.reset` as int32 [N]; ValueError for an env without a clip axis, a wrong shape or an id outside [0, C)."""
+def _check_clip(clip, num_clips: Optional[int], num_envs: int, entries: Optional[int] = None) -> np.ndarray:
+    """Explicit clip ids of `Rodent.reset` as int32 [N]; ValueError for an env without a clip axis, a wrong shape or an id outside [0, C).
+    `entries` = K (an env with `restart_across_clips`): ids of shape [K, N], one row per bank entry, pass too and come back as they are."""
     if num_clips is None:
         raise ValueError("reset(clip=...) needs an env built with a [C, T, 3] track_pos; this one has a single [T, 3] track")
     c = clip.detach().cpu().numpy() if torch.is_tensor(clip) else np.asarray(clip)
@@ -133,8 +200,8 @@ def _check_clip(clip, num_clips: Optional[int], num_envs: int) -> np.ndarray:
         raise ValueError(f"clip ids must be integers, got dtype {c.dtype}")
     if c.ndim == 0:
         c = np.full(num_envs, c)
-    if c.shape != (num_envs,):
-        raise ValueError(f"clip must be an int or have shape ({num_envs},), got {tuple(c.shape)}")
+    if c.shape != (num_envs,) and (entries is None or c.shape != (entries, num_envs)):
+        raise ValueError(f"clip must be an int or have shape ({num_envs},){'' if entries is None else f' or ({entries}, {num_envs})'}, got {tuple(c.shape)}")
     if c.size and (c.min() < 0 or c.max() >= num_clips):
         raise ValueError(f"clip ids must lie in [0, {num_clips}), got {int(c.min())} .. {int(c.max())}")
     return c.astype(np.int32)
@@ -202,7 +269,7 @@ def _quat_to_mat(q: np.ndarray) -> np.ndarray:
                      np.stack([2 * (x * z - w * y), 2 * (y * z + w * x), w * w - x * x - y * y + z * z], -1)], -2)
 
 
-def reference_obs(qpos, track_pos, track_quat, track_joints, frame, frames: int, clip=None, xquat=None, xmat=None) -> np.ndarray:
+def reference_obs(qpos, track_pos, track_quat, track_joints, frame, frames: int, clip=None, xquat=None, xmat=None, lengths=None) -> np.ndarray:
     """The reference blocks the step kernel appends to the observation (`Rodent(reference_obs_frames=H)`; C ABI
     `rr_batch_set_reference_obs`) restated in numpy float64: [..., frames * nq], block h = 1 .. frames = (p_h[3], q_h[4], j_h[nq - 7]).
 
@@ -216,7 +283,9 @@ def reference_obs(qpos, track_pos, track_quat, track_joints, frame, frames: int,
         j_h = r_j - qpos[7:]
 
     Body 1 is the root body of the free joint, so x = qpos[3:7] and xmat[1] is its matrix; `xquat` [N, 4] / `xmat` [N, 3, 3] override
-    them (e.g. with the values of a forward pass).  r_q and -r_q give the same block; frames past the clip's end repeat its last row."""
+    them (e.g. with the values of a forward pass).  r_q and -r_q give the same block; frames past the clip's end repeat its last row.
+    `lengths` (int [C], the env's `clip_lengths`): the clip's end is its own, f_h = clamp(frame + h, 0, L_c - 1), and no row at or behind
+    L_c is read (`reference_rows`)."""
     qpos = np.asarray(qpos, dtype=np.float64)
     tp, tq, tj = (np.asarray(a, dtype=np.float64) for a in (track_pos, track_quat, track_joints))
     N, nq = qpos.shape
@@ -229,8 +298,11 @@ def reference_obs(qpos, track_pos, track_quat, track_joints, frame, frames: int,
     xw, xx, xy, xz = (x[:, i] for i in range(4))
     out = np.empty((N, int(frames), nq))
     for h in range(1, int(frames) + 1):
-        f = np.clip(frame + h, 0, T - 1)
-        row = (lambda a: a[f]) if clip is None else (lambda a: a[c, f])
+        if lengths is None:
+            f = np.clip(frame + h, 0, T - 1)
+            row = (lambda a: a[f]) if clip is None else (lambda a: a[c, f])
+        else:
+            row = lambda a, fh=frame + h: reference_rows(a, fh, None if clip is None else c, lengths)
         out[:, h - 1, :3] = np.einsum("nij,nj->ni", R, row(tp) - qpos[:, :3])
         rw, rx, ry, rz = (row(tq)[:, i] for i in range(4))
         d = np.stack([xw * rw + xx * rx + xy * ry + xz * rz, xw * rx - xx * rw - xy * rz + xz * ry,
@@ -485,6 +557,8 @@ class Rodent(PipelineEnv):
         ang_vel_reward_scale: float = 0.1,
         joint_vel_reward_weight: float = 1.0,
         joint_vel_reward_scale: float = 0.01,
+        clip_lengths=None,
+        restart_across_clips: bool = False,
         **kwargs,
     ):
         """`track_pos`: the reference positions to track, float [T, 3] -- one clip, followed by every env -- or [C, T, 3], C >= 1 clips of
@@ -592,7 +666,26 @@ class Rodent(PipelineEnv):
         body tracking is, in `step`, `unroll_wrapped` and `unroll_policy_wrapped`, with or without the other options.  With the arrays
         given, `reset_to_reference=True` also starts the episode MOVING: qvel = track_vel[clip, start_frame] + noise instead of the bare
         noise (`reset_qvel`), in the reset state and in every entry of the clip-restart bank; the random draws are the same.  Without the
-        arrays, or with `reset_to_reference=False`, `reset` is what it is without them in every bit."""
+        arrays, or with `reset_to_reference=False`, `reset` is what it is without them in every bit.
+
+        Clip library (pose envs only; both off by default, and off is today's path in every bit and every key).  `clip_lengths`: int
+        [C] next to a [C, T, 3] track (an int or [1] next to a [T, 3] one), 2 <= L_c <= T: clip c consists of rows 0 .. L_c - 1 of every
+        clip array, and the rows behind them are padding that nothing reads -- no launch, not `reset_qpos` / `reset_qvel`
+        (`preprocessing.load_reference_clips` pads unequal clips and returns the lengths).  Wherever an env on clip c clamps a frame into
+        [0, T - 1] it clamps into [0, L_c - 1] instead -- the position reward's row, the observation's track entry, the reference blocks,
+        the pose reward and pose-termination row, the body rows, the velocity rows -- and `end_at_clip_end` becomes new_frame >=
+        L_c - 1.  Start frames fold into the clip: start = draw mod (L_c - 1) for the reset state and for every bank entry
+        (`fold_start_frames`; the identity where draw < L_c - 1), so the clip-length refusal of `end_at_clip_end` does not apply.  The
+        float64 restatements take their rows from `reference_rows(..., lengths=)`; `reference_obs` has a `lengths` argument.
+        `restart_across_clips=True` (needs `clip_restarts` >= 1 and a clip axis): bank entry k >= 1 takes the clip that
+        `reset_draws(fold_in(key, k), num_clips=C)` returns (`restart_bank_draws(across_clips=True)`; no other draw moves), entry 0 the
+        reset's clip; `reset(rng, clip=ids)` takes [N] (entry 0, the others drawn) or [K, N].  Each entry's start state is formed on its
+        own clip, `info['restart_bank']` gains `clip` (int32 [K, N]), and the rule above gains one line,
+
+            done:  clip <- bank clip[slot']
+
+        so `info['clip']` changes at a restore in the wrapped forms (a fresh tensor; the input state's is left alone).  The bare `step`
+        does not change the clip."""
         given = locals()                  # the arguments as they came (first statement: nothing else is a local yet): `_ctor` below
         if bad_state_max is not None:
             with np.errstate(over="ignore", under="ignore"):
@@ -616,7 +709,8 @@ class Rodent(PipelineEnv):
         pose_term = _check_pose_termination(max_pos_error, max_quat_error, max_joint_error, pose_np is not None)
         body_np = _check_body_tracking(track_np, track_bodies, body_ids, end_effector_ids, sys.nbody,
                                        (body_reward_weight, body_reward_scale, endeff_reward_weight, endeff_reward_scale), pose_np is not None)
-        restarts = _check_clip_restarts(clip_restarts, restart_frame_range, end_at_clip_end, pose_np is not None, track_np.shape[-2])
+        restarts = _check_clip_restarts(clip_restarts, restart_frame_range, end_at_clip_end, pose_np is not None, track_np.shape[-2], clip_lengths is not None)
+        lengths_np, across = _check_clip_library(clip_lengths, restart_across_clips, track_np, pose_np is not None, restarts[0])
         vel_np = _check_velocity_tracking(track_np, track_velocity, track_angular_velocity, track_joint_velocity, sys.nv,
                                           (lin_vel_reward_weight, lin_vel_reward_scale, ang_vel_reward_weight, ang_vel_reward_scale,
                                            joint_vel_reward_weight, joint_vel_reward_scale), pose_np is not None)
@@ -637,6 +731,9 @@ class Rodent(PipelineEnv):
         self._ref_frames = ref_frames
         self._pose_term = pose_term       # None: no pose termination (no such members anywhere, the launches run the instances they ran)
         self._clip_restarts, self._restart_frame_range, self._end_at_clip_end = restarts
+        self._lengths_host = lengths_np       # None: every clip has T frames (no such members anywhere)
+        self._clip_lengths = None if lengths_np is None else torch.from_numpy(lengths_np).to(self.device).contiguous()
+        self._across_clips = across
         batch = self._batch
 
         def reference_frames_supported():
@@ -653,7 +750,8 @@ class Rodent(PipelineEnv):
                   (pose_term is not None, "max_pos_error / max_quat_error / max_joint_error", batch.pose_termination_supported),
                   (body_np is not None, "track_bodies=...", batch.body_tracking_supported),
                   (vel_np is not None, "track_velocity=...", batch.velocity_tracking_supported),
-                  (self._clip_restarts > 0, f"clip_restarts={self._clip_restarts}", batch.clip_restarts_supported))
+                  (self._clip_restarts > 0, f"clip_restarts={self._clip_restarts}", batch.clip_restarts_supported),
+                  (lengths_np is not None or across, "clip_lengths=... / restart_across_clips=True", batch.clip_library_supported))
         for wanted, label, query in probes:       # a model, solver or frame count without the option's instance: the library's reason
             why = query() if wanted else None
             if why is not None:
@@ -761,6 +859,16 @@ class Rodent(PipelineEnv):
         return self._restart_frame_range
 
     @property
+    def clip_lengths(self) -> Optional[torch.Tensor]:
+        """Frames of each clip, int32 [C] on the env's device (None: every clip has `track_len` frames)."""
+        return self._clip_lengths
+
+    @property
+    def restart_across_clips(self) -> bool:
+        """Whether the entries of the start bank have clips of their own, so that a restore may move the env to another clip."""
+        return self._across_clips
+
+    @property
     def track_len(self) -> int:
         """Frames T of a clip."""
         return int(self._track_host.shape[-2])
@@ -785,9 +893,11 @@ class Rodent(PipelineEnv):
             raise RuntimeError("pose tracking: no pose instance reads per-env parameters (randomize / set_env_params on a pose env)")
         return super().randomize(randomization_fn)
 
-    def _env_io(self, cur_frame, obs, reward=None, done=None, metrics=None, clip=None, restart=None, **buffers):
+    def _env_io(self, cur_frame, obs, reward=None, done=None, metrics=None, clip=None, restart=None, clip_library=None, **buffers):
         """The env-io dict of a launch.  `buffers`: the step options' output buffers by env-io key (`_launch_buffers`); each brings its
-        option's static entries along.  `restart`: the clip-restart block of a multi-step launch (single steps and resets pass none)."""
+        option's static entries along.  `restart`: the clip-restart block of a multi-step launch (single steps and resets pass none).
+        `clip_library`: the clip-library block (an env with `clip_lengths` or `restart_across_clips` only); it rides on the pose block,
+        so a reset that hands none (no reference frames: it reads no clamped frame) hands no library either."""
         io = dict(track_pos=self._track_pos, cur_frame=cur_frame, obs=obs, reward=reward, done=done, metrics=metrics, clip=clip,
                   healthy_reward=self._healthy_reward, ctrl_cost_weight=self._ctrl_cost_weight,
                   healthy_z_range=self._healthy_z_range, terminate_when_unhealthy=self._terminate_when_unhealthy,
@@ -800,6 +910,8 @@ class Rodent(PipelineEnv):
                 io.update(o.static)
         if restart is not None:
             io["restart"] = restart
+        if clip_library is not None and "pose_metrics" in buffers:
+            io["clip_library"] = clip_library
         return io
 
     def reset(self, rng, clip=None) -> State:
@@ -809,40 +921,55 @@ class Rodent(PipelineEnv):
         An env with a [C, T, 3] track gives each env a clip: `randint(rng_pos, 0, C)` from the fourth key of the reference's split (which
         the reference never uses, so start frame, qpos noise and qvel are what a single-clip env draws from the same key), or `clip`, an
         int or integer ids [N] in [0, C) (ValueError outside, and for an env without a clip axis).  The ids live in `info['clip']` (int32
-        [N], device) and stay for the life of the state: like `cur_frame` they are not restored by AutoReset, and never re-drawn."""
+        [N], device) and stay for the life of the state: like `cur_frame` they are not restored by AutoReset, and never re-drawn.  With
+        `restart_across_clips` every entry of the start bank has a clip of its own -- `clip` [N] sets entry 0 and the others are drawn,
+        [K, N] sets every entry -- kept in `info['restart_bank']['clip']`, and the wrapped forms move `info['clip']` at a restore."""
         N, dev, s = self.num_envs, self.device, self.sys
-        if clip is not None:
-            clip = _check_clip(clip, self._num_clips, N)
+        if clip is not None:      # (validated before anything else of the env is touched)
+            clip = _check_clip(clip, self._num_clips, N, self._clip_restarts if getattr(self, "_across_clips", False) else None)
+        K = max(self._clip_restarts, 1)      # entry 0 of the bank is the reset state itself: the same draws, whatever K is
         if isinstance(rng, (int, np.integer)):
             rng = jax_random.split(jax_random.PRNGKey(int(rng)), N)
         keys = np.asarray(rng, dtype=np.uint32).reshape(N, 2)
-        K = max(self._clip_restarts, 1)      # entry 0 of the bank is the reset state itself: the same draws, whatever K is
-        frames, noises, qvels, drawn = restart_bank_draws(keys, K, s.nq, s.nv, self._reset_noise_scale, self._restart_frame_range, self._num_clips)
+        frames, noises, qvels, drawn = restart_bank_draws(keys, K, s.nq, s.nv, self._reset_noise_scale, self._restart_frame_range, self._num_clips,
+                                                          self._across_clips)
         if clip is None:
             clip = drawn
-        clip_dev = None if clip is None else torch.from_numpy(np.ascontiguousarray(clip, dtype=np.int32)).to(dev)
+        elif self._across_clips and clip.ndim == 1:      # entry 0 given, the others as drawn
+            clip = np.concatenate([clip[None], drawn[1:]], axis=0)
+        # the clip of entry k: its row with `restart_across_clips`, else the env's one clip (None without a clip axis)
+        clips = [clip[k] if self._across_clips else clip for k in range(K)]
+        to_dev = lambda c: None if c is None else torch.from_numpy(np.ascontiguousarray(c, dtype=np.int32)).to(dev)
+        clip_dev = to_dev(clips[0])
+        L = self._lengths_host
+        library = None if L is None else dict(lengths=self._clip_lengths)
         entries = []
         for k in range(K):
+            clip = clips[k]
+            if L is not None:       # the draw folded into the entry's clip
+                frames[k] = fold_start_frames(frames[k], L, clip)
             # float32 [T, 3] or [C, T, 3] (and the pose rows), what the device holds
-            qpos = reset_qpos(s.qpos0, self._track_host, frames[k], noises[k], clip, self._pose_host if self._reset_to_reference else None)
+            qpos = reset_qpos(s.qpos0, self._track_host, frames[k], noises[k], clip, self._pose_host if self._reset_to_reference else None, L)
             # with the clip's velocities the episode starts moving: the row of the start frame plus the (same) noise
-            qvel = reset_qvel(self._vel_host, frames[k], qvels[k], clip) if self._vel_host is not None and self._reset_to_reference else qvels[k]
+            qvel = reset_qvel(self._vel_host, frames[k], qvels[k], clip, L) if self._vel_host is not None and self._reset_to_reference else qvels[k]
             st = dict(qpos=torch.from_numpy(qpos).to(dev), qvel=torch.from_numpy(qvel).to(dev),
                       act=torch.zeros(N, s.na, device=dev), qacc_warmstart=torch.zeros(N, s.nv, device=dev))
             out = self._alloc_outputs(full=False)
             cur_frame = torch.from_numpy(frames[k].astype(np.int32)).to(dev)
             obs = torch.empty(N, self.observation_size, device=dev)
-            self._batch.env_reset(st, self._env_io(cur_frame, obs, clip=clip_dev), out)
+            self._batch.env_reset(st, self._env_io(cur_frame, obs, clip=clip_dev if k == 0 else to_dev(clip), clip_library=library), out)
             entries.append((st, out, cur_frame, obs))
         st, out, cur_frame, obs = entries[0]
         info = {"cur_frame": cur_frame}
-        if clip is not None:
+        if clip_dev is not None:
             info["clip"] = clip_dev
         if self._clip_restarts:
             stack = lambda name, src: torch.stack([e[src][name] for e in entries]).contiguous()
             bank_ps = PipelineState(**{n: stack(n, 0) for n in st}, **{n: (stack(n, 1) if out[n] is not None else None) for n in out})
             info["restart_bank"] = dict(pipeline_state=bank_ps, obs=torch.stack([e[3] for e in entries]).contiguous(),
                                         frame=torch.stack([e[2] for e in entries]).contiguous())
+            if self._across_clips:
+                info["restart_bank"]["clip"] = to_dev(np.stack(clips))
             info["restart_slot"] = torch.zeros(N, dtype=torch.int32, device=dev)
         zero = torch.zeros(N, device=dev)
         metrics = {"pos_reward": zero, "reward_quadctrl": zero.clone(), "reward_alive": zero.clone()}
@@ -872,6 +999,12 @@ class Rodent(PipelineEnv):
                 wrap["slots"] = self._clip_restarts
                 io["restart"] = dict(frames=bank["frame"], slot_in=info["restart_slot"], slot_out=torch.empty_like(info["restart_slot"]),
                                      end_at_clip_end=self._end_at_clip_end)
+        if self._clip_lengths is not None or (self._across_clips and wrap is not None):
+            # the clip library: the lengths in every step launch; the entries' clips in the multi-step forms, which return the clip each
+            # env is on in a fresh tensor (the incoming state's ids are read only)
+            io["clip_library"] = dict(lengths=self._clip_lengths)
+            if self._across_clips and wrap is not None:
+                io["clip_library"].update(bank_clips=info["restart_bank"]["clip"], clip_out=torch.empty_like(info["clip"]))
         return st_in, st, io, wrap
 
     def _next_state(self, state: State, st, io, obs, wrap=None, out=None) -> State:
@@ -882,6 +1015,8 @@ class Rodent(PipelineEnv):
             info.update(steps=wrap["steps_out"], truncation=wrap["truncation_out"])
             if "restart" in io:
                 info["restart_slot"] = io["restart"]["slot_out"]
+            if io.get("clip_library", {}).get("clip_out") is not None:
+                info["clip"] = io["clip_library"]["clip_out"]
         m = dict(state.metrics)
         m.update(pos_reward=io["metrics"][:, 0], reward_quadctrl=io["metrics"][:, 1], reward_alive=io["metrics"][:, 2])
         for o in self._options:
@@ -935,6 +1070,8 @@ class Rodent(PipelineEnv):
             return self._batch.body_tracking_supported(with_actor=True)
         if self._vel is not None:
             return self._batch.velocity_tracking_supported(with_actor=True)
+        if self._clip_lengths is not None:      # per-clip lengths alone: the env steps run the body-tracking instance too
+            return self._batch.clip_library_supported(with_actor=True)
         if self._pose_term is not None:
             return self._batch.pose_termination_supported(with_actor=True)
         return self._batch.reference_obs_supported(self._ref_frames, with_actor=True)

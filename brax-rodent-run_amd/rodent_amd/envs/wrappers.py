@@ -8,6 +8,8 @@ its clip across restores.  `reset(rng, **kw)` hands keyword arguments (`clip=`) 
 
 An env with clip restarts (`Rodent(clip_restarts=K)`, K >= 1) is wrapped by `ClipEpisodeWrapper` and `ClipAutoResetWrapper` instead: the
 clip's end may truncate the episode, and a restore takes the next entry of the env's start bank -- state, observation AND frame.
+With the clip library (`Rodent(clip_lengths=..., restart_across_clips=True)`) the clip's end is that of the env's own clip, and the restore
+also takes the entry's clip: `info['clip']` then changes at a restore.
 """
 from __future__ import annotations
 
@@ -124,7 +126,8 @@ def _base(env):
 class ClipEpisodeWrapper(EpisodeWrapper):
     """`EpisodeWrapper` of an env with clip restarts: with `end_at_clip_end` the episode also ends -- a truncation, like
     `episode_length` -- when the stepped frame reaches the clip's last one, new_frame >= T - 1: the new state's observation has no next
-    frame left to read without clamping."""
+    frame left to read without clamping.  An env with `clip_lengths` (int [C], on the env's device) ends at its own clip's length:
+    new_frame >= L_c - 1, c = `info['clip']` after the step (clip 0 without ids)."""
 
     def step(self, state, action):
         total = None
@@ -138,7 +141,12 @@ class ClipEpisodeWrapper(EpisodeWrapper):
         over = steps >= self.episode_length
         base = _base(self.env)
         if base.end_at_clip_end:
-            over = over | (state.info["cur_frame"] >= base.track_len - 1)
+            lengths = getattr(base, "clip_lengths", None)
+            if lengths is None:
+                over = over | (state.info["cur_frame"] >= base.track_len - 1)
+            else:
+                own = lengths[state.info["clip"].long()] if "clip" in state.info else lengths[0]
+                over = over | (state.info["cur_frame"] >= own - 1)
         done = torch.where(over, one, state.done)
         state.info["truncation"] = torch.where(over, 1 - state.done, zero)
         state.info["steps"] = steps
@@ -149,7 +157,7 @@ class ClipAutoResetWrapper(Wrapper):
     """`AutoResetWrapper` of an env with clip restarts: where done, the env takes the NEXT entry of its start bank
     (`info['restart_bank']`, built by the env's `reset`) -- slot' = (slot + 1) mod K; pipeline state, observation and `cur_frame` come
     from entry slot' -- so the restarted episode rejoins its clip at the frame its state was formed at.  Bank and slot are info: never
-    re-drawn, never restored."""
+    re-drawn, never restored.  A bank with a `clip` leaf (`restart_across_clips`) also hands its entry's clip to `info['clip']`."""
 
     def step(self, state, action):
         if "steps" in state.info:
@@ -171,6 +179,8 @@ class ClipAutoResetWrapper(Wrapper):
         new_ps = _tree_map2(where_done, bank["pipeline_state"], state.pipeline_state)
         obs = where_done(bank["obs"], state.obs)
         state.info["cur_frame"] = where_done(bank["frame"], state.info["cur_frame"])
+        if "clip" in bank:
+            state.info["clip"] = where_done(bank["clip"], state.info["clip"])
         state.info["restart_slot"] = nslot
         return state.replace(pipeline_state=new_ps, obs=obs)
 
@@ -255,8 +265,17 @@ class FusedEpisodeAutoResetWrapper(Wrapper):
             cur = [getattr(ps, n) for n in names] + [nstate.obs]
             steps, trunc = torch.empty_like(nstate.done), torch.empty_like(nstate.done)
             slot = torch.empty_like(state.info["restart_slot"])
-            hip.wrap_clip_restart(first, cur, state.done, state.info["steps"], nstate.done, steps, trunc, self.episode_length, 1,
-                                  nstate.info["cur_frame"], bank["frame"], state.info["restart_slot"], slot, base.track_len, base.end_at_clip_end)
+            lengths = getattr(base, "clip_lengths", None)
+            if lengths is not None or "clip" in bank:      # the clip library: the env's own clip's end, the entry's clip with its frame
+                clip = state.info["clip"].clone() if "clip" in state.info else None      # the bare step leaves the ids alone: finished in a copy
+                hip.wrap_clip_library(first, cur, state.done, state.info["steps"], nstate.done, steps, trunc, self.episode_length, 1,
+                                      nstate.info["cur_frame"], bank["frame"], state.info["restart_slot"], slot, base.track_len, base.end_at_clip_end,
+                                      clip, bank.get("clip"), lengths)
+                if clip is not None:
+                    nstate.info["clip"] = clip
+            else:
+                hip.wrap_clip_restart(first, cur, state.done, state.info["steps"], nstate.done, steps, trunc, self.episode_length, 1,
+                                      nstate.info["cur_frame"], bank["frame"], state.info["restart_slot"], slot, base.track_len, base.end_at_clip_end)
             nstate.info.update(steps=steps, truncation=trunc, restart_slot=slot)
             return nstate
         fps, ps = nstate.info["first_pipeline_state"], nstate.pipeline_state

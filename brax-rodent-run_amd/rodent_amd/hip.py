@@ -78,6 +78,11 @@ class RRVelIO(C.Structure):
                 ("ang_weight", C.c_float), ("ang_scale", C.c_float), ("joint_weight", C.c_float), ("joint_scale", C.c_float)]
 
 
+class RRClipLibraryIO(C.Structure):
+    """`rr_clip_library_io`, the clip-library block a batch carries next to its pose block (`rr_batch_set_clip_library`)."""
+    _fields_ = [("clip_lengths", C.c_void_p), ("bank_clips", C.c_void_p), ("clip_out", C.c_void_p)]
+
+
 class RRUnrollIO(C.Structure):
     _fields_ = [("first", RRState), ("first_obs", C.c_void_p), ("prev_done", C.c_void_p), ("steps_in", C.c_void_p), ("steps_out", C.c_void_p),
                 ("truncation_out", C.c_void_p), ("episode_length", C.c_float)]
@@ -109,7 +114,7 @@ class RRPpoCfg(C.Structure):
 
 
 EXPORTS = ["rr_model_load", "rr_model_dims", "rr_model_set_solver", "rr_model_set_solver_type", "rr_model_destroy", "rr_model_table", "rr_kernarg_layout", "rr_batch_create",
-           "rr_batch_destroy", "rr_pipeline_init", "rr_pipeline_step", "rr_env_step", "rr_env_reset", "rr_pipeline_step_to", "rr_env_step_to", "rr_batch_contact_overflow", "rr_batch_bad_states", "rr_batch_unroll_supported", "rr_env_unroll", "rr_env_unroll_policy", "rr_batch_eval_supported", "rr_env_unroll_eval", "rr_batch_pose_supported", "rr_batch_set_pose", "rr_batch_set_reference_obs", "rr_batch_obs_width", "rr_batch_reference_obs_supported", "rr_batch_set_pose_termination", "rr_batch_pose_termination_supported", "rr_batch_set_body_tracking", "rr_batch_body_tracking_supported", "rr_batch_set_clip_restarts", "rr_batch_clip_restarts_supported", "rr_batch_set_velocity_tracking", "rr_batch_velocity_tracking_supported", "rr_wrap_clip_restart",
+           "rr_batch_destroy", "rr_pipeline_init", "rr_pipeline_step", "rr_env_step", "rr_env_reset", "rr_pipeline_step_to", "rr_env_step_to", "rr_batch_contact_overflow", "rr_batch_bad_states", "rr_batch_unroll_supported", "rr_env_unroll", "rr_env_unroll_policy", "rr_batch_eval_supported", "rr_env_unroll_eval", "rr_batch_pose_supported", "rr_batch_set_pose", "rr_batch_set_reference_obs", "rr_batch_obs_width", "rr_batch_reference_obs_supported", "rr_batch_set_pose_termination", "rr_batch_pose_termination_supported", "rr_batch_set_body_tracking", "rr_batch_body_tracking_supported", "rr_batch_set_clip_restarts", "rr_batch_clip_restarts_supported", "rr_batch_set_velocity_tracking", "rr_batch_velocity_tracking_supported", "rr_batch_set_clip_library", "rr_batch_clip_library_supported", "rr_wrap_clip_restart", "rr_wrap_clip_library",
            "rr_compute_gae", "rr_mlp_forward", "rr_ppo_loss_workspace_bytes", "rr_ppo_loss", "rr_policy_act_workspace_bytes", "rr_policy_act", "rr_policy_sample", "rr_policy_backward_workspace_bytes", "rr_policy_backward", "rr_mlp_silu_backward_workspace_bytes", "rr_mlp_silu_backward", "rr_mlp_value_backward_workspace_bytes", "rr_mlp_policy_backward", "rr_mlp_policy_backward_workspace_bytes", "rr_mlp_value_backward", "rr_mlp_weight_grad_workspace_bytes", "rr_mlp_weight_grad", "rr_mlp_weight_grad_batch_workspace_bytes", "rr_mlp_weight_grad_batch", "rr_obs_moments_workspace_bytes", "rr_obs_moments", "rr_wrap_episode_autoreset", "rr_debug_layout", "rr_batch_set_schedule", "rr_batch_set_env_params", "rr_batch_env_params_supported", "rr_batch_set_profile", "rr_batch_set_ls_repeat_exit", "rr_batch_set_solver_trim", "rr_batch_set_solver_batch", "rr_batch_set_solve_resident", "rr_model_solve_resident_switch", "rr_batch_set_root_slot", "rr_model_root_slot_switch", "rr_batch_set_timing", "rr_batch_kernel_time", "rr_last_error"]
 
 _lib = None
@@ -209,8 +214,11 @@ def lib():
         L.rr_batch_clip_restarts_supported.argtypes = [C.c_void_p, C.c_int32]
         L.rr_batch_set_velocity_tracking.argtypes = [C.c_void_p, C.POINTER(RRVelIO)]
         L.rr_batch_velocity_tracking_supported.argtypes = [C.c_void_p, C.c_int32]
+        L.rr_batch_set_clip_library.argtypes = [C.c_void_p, C.POINTER(RRClipLibraryIO)]
+        L.rr_batch_clip_library_supported.argtypes = [C.c_void_p, C.c_int32]
         L.rr_wrap_clip_restart.argtypes = [C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int32)] + \
             [C.c_void_p] * 5 + [C.c_float, C.c_float] + [C.c_void_p] * 4 + [C.c_int32] * 3 + [C.c_void_p]
+        L.rr_wrap_clip_library.argtypes = L.rr_wrap_clip_restart.argtypes[:-1] + [C.c_void_p] * 4      # ... clip, bank_clips, clip_lengths, stream
         L.rr_batch_set_ls_repeat_exit.argtypes = [C.c_void_p, C.c_int32]
         L.rr_batch_set_solver_trim.argtypes = [C.c_void_p, C.c_int32]
         L.rr_batch_set_solver_batch.argtypes = [C.c_void_p, C.c_int32]
@@ -327,6 +335,7 @@ class Batch:
         self._body = None           # the tensors of the body-tracking block in force (set_body_tracking)
         self._restart = None        # the tensors of the clip-restart block in force (set_clip_restarts)
         self._vel = None            # the tensors of the velocity-tracking block in force (set_velocity_tracking)
+        self._library = None        # the tensors of the clip-library block in force (set_clip_library)
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream().cuda_stream
         _check(lib().rr_batch_create(model.h, self.N, self.device.index or 0, C.c_void_p(stream), C.byref(self.h)))
@@ -392,7 +401,8 @@ class Batch:
         """The pose options ride on the batch, not in rr_env_io: the env-io dict decides what the launch about to be issued sees.  One row
         per block -- the env-io key that decides its presence, the attribute that says whether it stands, its setter, the setter's
         arguments out of the dict (the setters say what each entry is) -- in dependency order: termination, body tracking, velocity tracking
-        and clip restarts each need the pose block, and the library keeps the pose block while one of them stands.  So the blocks absent from the
+        and clip restarts each need the pose block, the clip library (`clip_library` key) the pose block and, for its bank clips, the
+        clip-restart block, and the library keeps a block while one that needs it stands.  So the blocks absent from the
         dict are cleared last to first, then the present ones are set first to last.  (Clearing the pose block is refused while the
         batch carries reference frames: their launches all carry `track_pose`.)"""
         lead, d, inf = tuple(env["track_pos"].shape[:-1]), self.dims, math.inf
@@ -409,9 +419,12 @@ class Batch:
                   ("track_vel", "_vel", self.set_velocity_tracking, lambda: (rows("track_vel", (d.nv,)), env.get("vel_metrics"), env.get("lin_vel_reward", (1.0, 10.0)),
                                                                            env.get("ang_vel_reward", (1.0, 0.1)), env.get("joint_vel_reward", (1.0, 0.01)))),
                   ("restart", "_restart", self.set_clip_restarts, lambda: (env["restart"]["frames"], env["restart"]["slot_in"], env["restart"]["slot_out"],
-                                                                           env["restart"].get("end_at_clip_end", False))))
+                                                                           env["restart"].get("end_at_clip_end", False))),
+                  ("clip_library", "_library", self.set_clip_library, lambda: (env["clip_library"].get("lengths"), env["clip_library"].get("bank_clips"),
+                                                                               env["clip_library"].get("clip_out"), 1 if len(lead) == 1 else lead[0])))
         for key, attr, setter, _ in reversed(blocks):
-            if env.get(key) is None and getattr(self, attr) is not None:
+            # (the clip library is always set afresh: the bank clips of an earlier launch would keep the restart block from being cleared)
+            if (env.get(key) is None or key == "clip_library") and getattr(self, attr) is not None:
                 setter(None)
         for key, _, setter, args in blocks:
             if env.get(key) is not None:
@@ -622,6 +635,28 @@ class Batch:
                                 int(frames.shape[0]), int(bool(end_at_clip_end)))
         self._set_block("_restart", lib().rr_batch_set_clip_restarts, t, (frames, slot_in, slot_out))
 
+    def set_clip_library(self, lengths: Optional[torch.Tensor], bank_clips: Optional[torch.Tensor] = None, clip_out: Optional[torch.Tensor] = None,
+                         num_clips: Optional[int] = None):
+        """The clip-library block of this batch's later env launches (C ABI `rr_batch_set_clip_library`): `lengths` int32 [C] the frames
+        of each clip (None: every clip has T), `bank_clips` int32 [K, N] the clip of each clip-restart bank entry (None: every entry on
+        the env's clip) with `clip_out` int32 [N], which a multi-step launch fills with the clip each env is on after it; all None clears
+        the block.  `num_clips` (given by the env-io path): the length `lengths` must have.  Needs the pose block, and for `bank_clips`
+        the clip-restart block.  The env-io dict of a launch (`clip_library` key) sets or clears it by itself.  The batch keeps the
+        tensors alive."""
+        t = None
+        if lengths is not None or bank_clips is not None:
+            if lengths is not None and (lengths.dim() != 1 or (num_clips is not None and lengths.shape[0] != num_clips)):
+                raise ValueError(f"clip library: lengths has shape {tuple(lengths.shape)}, expected [{'C' if num_clips is None else num_clips}]")
+            if bank_clips is not None and (bank_clips.dim() != 2 or bank_clips.shape[1] != self.N):
+                raise ValueError(f"clip library: bank_clips has shape {tuple(bank_clips.shape)}, expected [K, {self.N}]")
+            t = RRClipLibraryIO(_ptr(lengths, torch.int32), _ptr(bank_clips, torch.int32), _ptr(clip_out, torch.int32, self.N))
+        self._set_block("_library", lib().rr_batch_set_clip_library, t, (lengths, bank_clips, clip_out))
+
+    def clip_library_supported(self, with_actor: bool = False) -> Optional[str]:
+        """None when this batch serves the clip library at its frame count (C ABI `rr_batch_clip_library_supported`) -- with
+        `with_actor` also in the one-launch rollout with the actor inside -- else the refusal's text."""
+        return self._refusal(lib().rr_batch_clip_library_supported, int(with_actor))
+
     def _refusal(self, query, *args) -> Optional[str]:
         """None when the `rr_batch_*_supported` function `query` answers 1 for this batch, else the text it left in `rr_last_error`."""
         if _check(query(self.h, *args)) == 1:
@@ -766,6 +801,30 @@ def wrap_clip_restart(first, cur, prev_done, prev_steps, done, steps, truncation
                                       truncation.data_ptr(), float(episode_length), float(action_repeat), _ptr(cur_frame, torch.int32, N),
                                       _ptr(bank_frames, torch.int32, K * N), _ptr(slot_in, torch.int32, N), _ptr(slot_out, torch.int32, N),
                                       int(K), int(track_len), int(bool(end_at_clip_end)), C.c_void_p(stream)))
+
+
+def wrap_clip_library(first, cur, prev_done, prev_steps, done, steps, truncation, episode_length: float, action_repeat: float,
+                      cur_frame, bank_frames, slot_in, slot_out, track_len: int, end_at_clip_end: bool, clip=None, bank_clips=None, lengths=None):
+    """`wrap_clip_restart` with the clip library (C ABI `rr_wrap_clip_library`): `clip` int32 [N], the clip each env made the step on,
+    finished in place (the bank entry's clip where done); `bank_clips` int32 [K, N] or None; `lengths` int32 [C] or None -- the clip's
+    end is taken at the env's own clip's length."""
+    n = len(cur)
+    N = done.numel()
+    K = bank_frames.shape[0]
+    for t in list(first) + list(cur) + [prev_done, prev_steps, done, steps, truncation]:
+        _ptr(t)
+    for f, c in zip(first, cur):
+        if tuple(f.shape) != (K,) + tuple(c.shape):
+            raise ValueError("bank / current state shapes differ")
+    F = (C.c_void_p * n)(*[t.data_ptr() for t in first])
+    Cu = (C.c_void_p * n)(*[t.data_ptr() for t in cur])
+    W = (C.c_int32 * n)(*[t.numel() // N for t in cur])
+    stream = torch.cuda.current_stream(done.device).cuda_stream
+    _check(lib().rr_wrap_clip_library(N, n, F, Cu, W, prev_done.data_ptr(), prev_steps.data_ptr(), done.data_ptr(), steps.data_ptr(),
+                                      truncation.data_ptr(), float(episode_length), float(action_repeat), _ptr(cur_frame, torch.int32, N),
+                                      _ptr(bank_frames, torch.int32, K * N), _ptr(slot_in, torch.int32, N), _ptr(slot_out, torch.int32, N),
+                                      int(K), int(track_len), int(bool(end_at_clip_end)), _ptr(clip, torch.int32, N),
+                                      _ptr(bank_clips, torch.int32, K * N), _ptr(lengths, torch.int32), C.c_void_p(stream)))
 
 
 def _mlp_net(weights, biases, in_dim=None):

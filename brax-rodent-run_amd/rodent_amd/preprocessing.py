@@ -163,3 +163,30 @@ def load_reference_clip(filename: str, clip_names: Union[List[str], str]) -> Ref
         if vals:
             agg[a] = np.stack(vals)
     return ReferenceClip(**agg)
+
+
+def load_reference_clips(filename: str, clip_names: List[str]):
+    """The named clips of UNEQUAL length as one stacked clip: (ReferenceClip with every array [C, T, ...], lengths int32 [C]), T the
+    longest clip's frame count and lengths[c] the frames clip c has in the file.  A shorter clip is padded to T by repeating its last
+    row, so an env that is not told the lengths follows such a clip into a standing last frame instead of into garbage; hand the
+    lengths to `Rodent(clip_lengths=...)` and the padding is never read.  `load_reference_clip` (equal lengths, one stack) is
+    unchanged."""
+    if isinstance(clip_names, str):
+        clip_names = [clip_names]
+    clips = [load_reference_clip(filename, name) for name in clip_names]
+    lengths = []
+    for name, c in zip(clip_names, clips):
+        n = {np.asarray(getattr(c, a)).shape[1] for a in FIELDS if getattr(c, a) is not None}
+        if len(n) != 1:
+            raise ValueError(f"clip {name!r}: its arrays have different frame counts {sorted(n)}")
+        lengths.append(n.pop())
+    T, agg = max(lengths), {}
+    for a in FIELDS:
+        vals = [getattr(c, a) for c in clips]
+        if any(v is None for v in vals):
+            if not all(v is None for v in vals):
+                raise ValueError(f"attribute {a!r} is present in some of the clips {clip_names} only")
+            continue
+        rows = [np.asarray(v)[0] for v in vals]
+        agg[a] = np.stack([np.concatenate([r, np.repeat(r[-1:], T - len(r), axis=0)], axis=0) for r in rows])
+    return ReferenceClip(**agg), np.asarray(lengths, dtype=np.int32)

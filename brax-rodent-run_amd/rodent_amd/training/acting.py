@@ -227,6 +227,9 @@ class Evaluator:
         t = time.time()
         policy = self._policy_fn(policy_params)
         state = self._env.reset(jax_random.split(unroll_key, self._env.num_envs))
+        # the clips the episodes START on: `EvalWrapper` scores an env's first episode only, and an env with `restart_across_clips` may be
+        # on another clip by the end of the unroll (the tensor is the same one after the unroll where clips do not move)
+        clip = state.info.get("clip")
         if self.one_launch():
             T, N = self._unroll_length, self._env.num_envs
             noise = None if self._deterministic else torch.randn(T, N, self._env.action_size, device=state.obs.device)
@@ -243,7 +246,6 @@ class Evaluator:
         for name, value in em["episode_metrics"].items():
             metrics[f"eval/episode_{name}"] = float(value.mean()) if aggregate_episodes else value.cpu().numpy()
         # multi-clip eval env: the episode reward per clip, over the eval envs that follow it (a clip no eval env drew has no key)
-        clip = state.info.get("clip")
         if clip is not None and getattr(self._env, "num_clips", 1) > 1 and aggregate_episodes:
             reward, ids = em["episode_metrics"]["reward"].cpu(), clip.cpu()
             for c in torch.unique(ids).tolist():

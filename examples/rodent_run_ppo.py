@@ -82,6 +82,11 @@ def main():
                     "the K - 1 further start states are drawn in [LO, HI) (default 0 100, the reference's range)")
     ap.add_argument("--end-at-clip-end", action="store_true", help="with --clip-restarts: truncate an episode at the clip's last frame instead "
                     "of comparing it with the clamped last row (the clip must be longer than every start frame: the synthetic line has 250 frames)")
+    ap.add_argument("--restart-across-clips", action="store_true", help="with --clip-restarts and several clips: every start state of the bank has a "
+                    "clip of its own, so a restarted episode may move to another clip (Rodent(restart_across_clips=True))")
+    ap.add_argument("--clip-lengths", type=int, nargs="+", default=None, metavar="L", help="with --track-pose and --synthetic-clips K: the frames of each "
+                    "synthetic line, K ints in 2 .. 250 (Rodent(clip_lengths=...)): rewards, observation and --end-at-clip-end stop at the clip's own "
+                    "last frame.  Clips of unequal length in a --clip file get theirs from the file (preprocessing.load_reference_clips)")
     ap.add_argument("--track-velocity", action="store_true", help="with --track-pose: reward the clip's velocities too (Rodent(track_velocity=..., "
                     "track_angular_velocity=..., track_joint_velocity=...), untuned default weights), and with them a reset to the reference starts "
                     "moving: the clip file's velocity, angular_velocity and joints_velocity; the synthetic lines get "
@@ -130,9 +135,19 @@ def main():
         ap.error("--end-at-clip-end: needs --clip-restarts K >= 1")
     if not 0 <= args.reference_frames <= 16:
         ap.error("--reference-frames: 0 .. 16")
+    if (args.restart_across_clips or args.clip_lengths is not None) and not args.track_pose:
+        ap.error("--restart-across-clips / --clip-lengths: they serve envs that track the reference pose; add --track-pose")
+    if args.restart_across_clips and args.clip_restarts < 1:
+        ap.error("--restart-across-clips: needs --clip-restarts K >= 1")
+    clip_lengths = args.clip_lengths
     clips = None                                     # the loaded ReferenceClip(s), [C, T, ...] fields; None for a .npy track or the synthetic line
     if args.clip and os.path.exists(args.clip) and not args.clip.endswith(".npy"):
-        clips = preprocessing.load_reference_clip(args.clip, args.clip_name)
+        try:
+            clips = preprocessing.load_reference_clip(args.clip, args.clip_name)
+        except ValueError:                            # clips of unequal length: padded to the longest, each keeps its own length
+            if not args.track_pose:
+                raise
+            clips, clip_lengths = preprocessing.load_reference_clips(args.clip, args.clip_name)
         position = np.asarray(clips.position)         # reference_clip.position [REF :84], [C, T, 3]
         track_pos = position[0] if len(args.clip_name) == 1 else position
     elif args.clip and os.path.exists(args.clip):
@@ -189,6 +204,7 @@ def main():
         bad_state_max=args.bad_state_max, reference_obs_frames=args.reference_frames, max_pos_error=args.max_pos_error,
         max_quat_error=args.max_quat_error, max_joint_error=args.max_joint_error, clip_restarts=args.clip_restarts,
         restart_frame_range=None if args.restart_frames is None else tuple(args.restart_frames), end_at_clip_end=args.end_at_clip_end,
+        clip_lengths=None if clip_lengths is None else np.asarray(clip_lengths, dtype=np.int32), restart_across_clips=args.restart_across_clips,
         **pose)     # a clip too short for --end-at-clip-end is refused here with the reason (ValueError)
 
     train_fn = functools.partial(

@@ -424,6 +424,41 @@ typedef struct rr_vel_io {
 int rr_batch_set_velocity_tracking(rr_batch* b, const rr_vel_io* vel);
 int rr_batch_velocity_tracking_supported(const rr_batch* b, int32_t with_actor);
 
+/* Clip library: clips keep their own length, and a restarted episode may move to another clip.  The block is set on the BATCH, next to
+ * the pose block it needs (the structs above are closed), and read by every later env launch of it until it is replaced or cleared
+ * (NULL; a batch starts without one); a launch takes the pointers as they are when it is issued.
+ * clip_lengths [num_clips] (one entry for an env io without clip ids): clip c consists of rows 0 .. L_c - 1 of track_pos, track_pose,
+ * track_bodies and track_vel, L_c = clip_lengths[c] clamped into 1 .. track_len; the rows behind them are padding that no launch reads
+ * (the row stride stays track_len).  Wherever an env on clip c clamps a frame into 0 .. track_len - 1 without the block -- the position
+ * reward's row, the observation's track entry (frame + 1), the reference blocks (frame + h), the pose reward and pose-termination row,
+ * the body rows, the velocity rows -- it clamps into 0 .. L_c - 1, and end_at_clip_end of rr_clip_restart_io becomes new_frame >=
+ * L_c - 1.  Env steps read it, and the resets of a batch with reference frames; a reset without them reads frame + 1 unclamped by the
+ * clip, so the caller starts every env at a frame <= L_c - 2.  NULL: every clip has track_len frames.
+ * bank_clips [num_slots][N] (needs a clip-restart block and env io clip ids): the clip of each bank entry.  rr_clip_restart_io's rule
+ * gains one line,
+ *   done:  clip <- bank_clips[slot'] (clamped into 0 .. num_clips - 1);   else the clip the env is on,
+ * in rr_env_unroll and rr_env_unroll_policy: the launch reads the env io's clip [N] once, every step reads the rows of the clip the
+ * env is on, and clip_out [N] receives the clip each env is on after the last step (the env io's clip is left alone; the two may not
+ * alias).  Single steps (rr_env_step(_to)) have no restore in the kernel: rr_wrap_clip_library below.  NULL: every entry on the env's
+ * clip.
+ * Nothing else of a step changes: with lengths equal to track_len and every bank entry on the env's clip the results are those without
+ * the block, bit for bit.
+ * rr_batch_set_clip_library: no pose block on the batch, both pointers NULL, bank_clips without a clip-restart block or without
+ * clip_out: RR_EINVAL; RR_EUNSUPPORTED with the reason wherever pose tracking is unsupported.  While the block is set,
+ * rr_batch_set_pose(b, NULL) is RR_EINVAL, and with bank_clips so is rr_batch_set_clip_restarts(b, NULL): clear this block first.  What
+ * refuses a pose block refuses here: rr_env_unroll_eval, per-env parameters, the debug dump, contact-geometry outputs and the profile
+ * build.  The env steps of a batch with the block run the body-tracking instances (the restart instances in the multi-step forms with a
+ * clip-restart block) whatever else the batch carries.
+ * rr_batch_clip_library_supported(b, with_actor): 1 / 0 -- whether the batch serves the block with its current frame count (with_actor
+ * != 0: also in rr_env_unroll_policy); with 0 rr_last_error holds the reason.  It does not need the pose block to be set. */
+typedef struct rr_clip_library_io {
+  const int32_t* clip_lengths;  /* [C] or NULL: every clip has T frames */
+  const int32_t* bank_clips;    /* [K][N] or NULL: every bank entry on the env's clip */
+  int32_t* clip_out;            /* [N] out; required with bank_clips: the clip each env is on after a multi-step launch */
+} rr_clip_library_io;
+int rr_batch_set_clip_library(rr_batch* b, const rr_clip_library_io* lib);
+int rr_batch_clip_library_supported(const rr_batch* b, int32_t with_actor);
+
 /* Generalised advantage estimation of one PPO minibatch, the reverse scan of brax.training.agents.ppo.losses.compute_gae
  * [UP; SURVEY.md Appendix E], one thread per trajectory.  All arrays time-major [T][B] device float32; bootstrap [B];
  * outputs vs [T][B] and advantages [T][B].  `stream` is a hipStream_t (NULL = default stream). */
@@ -591,6 +626,16 @@ int rr_wrap_clip_restart(int32_t num_envs, int32_t narr, const float* const* fir
                          float episode_length, float action_repeat, int32_t* cur_frame, const int32_t* bank_frames,
                          const int32_t* slot_in, int32_t* slot_out, int32_t num_slots, int32_t track_len, int32_t end_at_clip_end,
                          void* stream);
+/* The same with the clip library (rr_clip_library_io's rule on one env step; the entry above is unchanged): rr_wrap_clip_restart's
+ * arguments, then clip [N], the clip each env made the step on, finished in place (the bank entry's clip where done; NULL with a NULL
+ * bank_clips and at most one clip), bank_clips [num_slots][N] or NULL (every entry on the env's clip), clip_lengths [num_clips] or NULL
+ * (every clip has track_len frames): the clip's end is new_frame >= L - 1, L = clip_lengths[clip] clamped into 1 .. track_len.  The
+ * ids in clip and bank_clips must lie in 0 .. num_clips - 1 (this entry does not know num_clips). */
+int rr_wrap_clip_library(int32_t num_envs, int32_t narr, const float* const* first, float* const* cur, const int32_t* widths,
+                         const float* prev_done, const float* prev_steps, float* done, float* steps, float* truncation,
+                         float episode_length, float action_repeat, int32_t* cur_frame, const int32_t* bank_frames,
+                         const int32_t* slot_in, int32_t* slot_out, int32_t num_slots, int32_t track_len, int32_t end_at_clip_end,
+                         int32_t* clip, const int32_t* bank_clips, const int32_t* clip_lengths, void* stream);
 
 /* Scheduling of the environments on the GPU (results are unaffected: environments are independent).  `env_map` (device,
  * [N] int32, a permutation of 0..N-1, or NULL = identity): workgroup w steps environment env_map[w]; `cost_cycles` (device,

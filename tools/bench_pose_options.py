@@ -11,15 +11,17 @@ alternating in one process on one GPU.  No gate: it reports.
                      the body instances, and the final states must be identical, with and without --actor
   --option restart   a pose env with max_pos_error 1e9 (the family its multi-step launches would otherwise run) | the same with
                      `clip_restarts` 1 | with 8
+  --option library   that `clip_restarts` 8 env on three copies of the clip ([3, T, ...] arrays) | the same with `clip_lengths`
+                     (T, 2T/3, T/3) and `restart_across_clips`
 
 All envs: rodent_optimized.xml, CG 8/8, n_frames 10, --num-envs envs through Episode(150) + AutoReset in multi-step launches, tracking a
 synthetic reference pose (identity quaternion, qpos0's joints) with the default weights and scales.  Default: random actions through
-`rr_env_unroll`, --unroll env steps per launch -- the workload of bench.py config 2.  --actor (poseterm, body, velocity, restart): the one-launch
+`rr_env_unroll`, --unroll env steps per launch -- the workload of bench.py config 2.  --actor (poseterm, body, velocity, restart, library): the one-launch
 rollout with the actor inside (`rr_env_unroll_policy`, a 4 x 32 policy, one segment of --unroll steps per launch).  After two warm-up
 launches per side, each repeat times --launches launches per side, in the order above, with a host clock around a device synchronise;
 the medians, the per-repeat values, the ranges and the ratios against the first side are printed as one JSON line.
 
-usage: python tools/bench_pose_options.py --option {pose,refobs,poseterm,body,velocity,restart} [--actor] [--frames 5] [--num-envs 2048]
+usage: python tools/bench_pose_options.py --option {pose,refobs,poseterm,body,velocity,restart,library} [--actor] [--frames 5] [--num-envs 2048]
                                           [--unroll 50] [--launches 4] [--repeats 7] [--out FILE]"""
 import argparse
 import json
@@ -48,17 +50,22 @@ class Option(NamedTuple):
     check: Callable
     identical: Optional[tuple] = None
     identical_with_actor: bool = False      # whether that claim is also checked under --actor
+    clips: int = 0                          # > 0: every side tracks that many copies of the clip, [clips, T, ...] arrays
 
 
 def _alive(st):
     return float(st.metrics["quat_reward"].max()) > 0 and bool(torch.isfinite(st.obs).all())
 
 
-def options(frames: int, bodies: Callable, velocity: dict) -> dict:
+def options(frames: int, bodies: Callable, velocity: dict, T: int = 250) -> dict:
     """The table.  `bodies`: an env of the model -> track_bodies (a callable keyword is called with the first side's env, or a one-env
-    probe while that side is being built); `velocity`: the three velocity keywords."""
+    probe while that side is being built); `velocity`: the three velocity keywords; `T`: the clip's frames."""
     body = dict(track_bodies=bodies, end_effector_ids=END_EFFECTORS)
+    k8 = dict(max_pos_error=1e9, clip_restarts=8)
     return {
+        "library": Option((("k8", k8), ("library", dict(k8, clip_lengths=(T, 2 * T // 3, T // 3), restart_across_clips=True))), True, True,
+                          lambda st: _alive(st) and int(st.info["restart_slot"].max()) <= 7 and 0 <= int(st.info["clip"].min()) and int(st.info["clip"].max()) <= 2,
+                          clips=3),
         "velocity": Option((("body", body), ("velocity", dict(body, **velocity))), True, True,
                            lambda st: _alive(st) and all(bool(torch.isfinite(st.metrics[k]).all()) and float(st.metrics[k].max()) > 0
                                                          for k in ("lin_vel_reward", "ang_vel_reward", "joint_vel_reward")),
@@ -76,7 +83,7 @@ def options(frames: int, bodies: Callable, velocity: dict) -> dict:
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--option", required=True, choices=("pose", "refobs", "poseterm", "body", "velocity", "restart"))
+    ap.add_argument("--option", required=True, choices=("pose", "refobs", "poseterm", "body", "velocity", "restart", "library"))
     ap.add_argument("--actor", action="store_true")
     ap.add_argument("--frames", type=int, default=5)
     ap.add_argument("--num-envs", type=int, default=2048)
@@ -97,9 +104,11 @@ def main():
     qpos = np.concatenate([np.asarray(track, np.float64), quat, joints], axis=1)
     qvel = preprocessing.compute_velocity_from_kinematics(np.concatenate([qpos, qpos[-1:]], axis=0), 0.02)      # [T, nv], the last row zero
     velocity = dict(track_velocity=qvel[:, :3], track_angular_velocity=qvel[:, 3:6], track_joint_velocity=qvel[:, 6:])
-    opt = options(args.frames, lambda env: preprocessing.extract_features(env, qpos).body_positions, velocity)[args.option]
+    opt = options(args.frames, lambda env: preprocessing.extract_features(env, qpos).body_positions, velocity, T)[args.option]
     if args.actor and not opt.actor:
-        ap.error(f"--actor: --option {args.option} has no such mode (poseterm, body, velocity and restart have)")
+        ap.error(f"--actor: --option {args.option} has no such mode (poseterm, body, velocity, restart and library have)")
+    if opt.clips:      # the same clip `clips` times over
+        track, quat, joints = (np.stack([np.asarray(a)] * opt.clips) for a in (track, quat, joints))
     dev = torch.device("cuda:0")
     keys = jax_random.split(jax_random.PRNGKey(0), N)
     first, sides = opt.sides[0][0], {}
