@@ -412,6 +412,8 @@ struct rr_batch {
   rr_vel_io vel = {};                   // velocity tracking of the env steps (rr_batch_set_velocity_tracking); track_vel null: off; set only with a pose block
   rr_clip_library_io lib = {};          // clip library of the env launches (rr_batch_set_clip_library); both pointers null: off; set only with a pose block
   bool has_clip_library() const { return lib.clip_lengths || lib.bank_clips; }
+  rr_clip_sampling_io samp = {};        // clip sampling of the multi-step launches (rr_batch_set_clip_sampling); clip_weights and outcomes null: off; set only with a clip-restart block
+  bool has_clip_sampling() const { return samp.clip_weights || samp.outcomes; }
   bool has_env_params() const { return env_dof_f || env_act_f || env_con_f; }
 };
 
@@ -736,6 +738,15 @@ static int launch(rr_batch* b, const Launch& L) {
     if (!io.clip) return fail(RR_EINVAL, "launch: clip library: bank_clips needs the env io's clip ids");
     if (io.clip == b->lib.clip_out) return fail(RR_EINVAL, "launch: clip library: clip_out may not alias the env io's clip");
     io.bank_clips = b->lib.bank_clips; io.clip_out = b->lib.clip_out;
+  }
+  if (restart && b->has_clip_sampling()) {      // only the RESTART instances read these; single steps ignore the block (rr_wrap_clip_sampling)
+    io.outcomes = (long long*)b->samp.outcomes; io.sample_seed = b->samp.seed;
+    if (b->samp.clip_weights) {
+      if (!io.bank_clips) return fail(RR_EINVAL, "launch: clip sampling: clip_weights needs the clip library's bank_clips");
+      io.clip_weights = b->samp.clip_weights;
+    }
+    io.draws_in = b->samp.draws_in; io.draws_out = b->samp.draws_out;
+    if (io.draws_in && io.draws_in == io.draws_out) return fail(RR_EINVAL, "launch: clip sampling: draws_out may not alias draws_in");
   }
   if (pterm) { io.pose_fail = b->pterm.fail; io.pose_max_pos = b->pterm.max_pos; io.pose_max_quat = b->pterm.max_quat; io.pose_max_joint = b->pterm.max_joint; }
   if (pose) {
@@ -1508,6 +1519,112 @@ extern "C" int rr_wrap_clip_library(int32_t num_envs, int32_t narr, const float*
   return RR_OK;
 }
 
+// The same with clip sampling (rr_clip_sampling_io's rule, one env step): the outcome counters of the step -- on the clip it was made
+// on, flushed every step -- and, where done, the slot drawn by the env's bank weights instead of the next one.  pose_fail: the step's
+// pose-termination codes (null: none).  Null outcomes / clip_weights switch the two additions off one by one.
+__global__ void rr_wrap_sampling_kernel(const RRWrapArgs A, const float* __restrict__ prev_done, const float* __restrict__ prev_steps,
+                                        float* __restrict__ done, float* __restrict__ steps, float* __restrict__ truncation,
+                                        float episode_length, float action_repeat, int* __restrict__ cur_frame, const int* __restrict__ bank_frames,
+                                        const int* __restrict__ slot_in, int* __restrict__ slot_out, int num_slots, int track_len, int end_at_clip_end,
+                                        int* __restrict__ clip, const int* __restrict__ bank_clips, const int* __restrict__ clip_lengths, int num_clips,
+                                        const float* __restrict__ pose_fail, const int* __restrict__ clip_weights, const int* __restrict__ draws_in,
+                                        int* __restrict__ draws_out, long long* __restrict__ outcomes, unsigned seed) {
+  const int e = blockIdx.x, N = gridDim.x;
+  const float s0 = prev_done[e] != 0.0f ? 0.0f : prev_steps[e];
+  const float s1 = s0 + action_repeat;
+  const int new_frame = cur_frame[e];
+  int c = clip ? clip[e] : 0;
+  c = c < 0 ? 0 : (c > num_clips - 1 ? num_clips - 1 : c);
+  const int c_step = c;                  // the clip the step was made on
+  int len = track_len;
+  if (clip_lengths) { len = clip_lengths[c]; len = len < 1 ? 1 : (len > track_len ? track_len : len); }
+  const bool over = s1 >= episode_length || (end_at_clip_end && new_frame >= len - 1);
+  const float d_env = done[e];
+  const float d_out = over ? 1.0f : d_env;
+  const bool failed = pose_fail && pose_fail[e] != 0.0f;
+  unsigned n = draws_in ? (unsigned)draws_in[e] : 0u;
+  int slot = slot_in[e];
+  slot = slot < 0 ? 0 : (slot > num_slots - 1 ? num_slots - 1 : slot);      // clamped into the bank
+  if (d_out != 0.0f) {
+    int drawn = -1;
+    if (clip_weights && bank_clips) {      // the K entries one after the other: every thread of the block forms the same slot
+      unsigned S = 0;
+      for (int k = 0; k < num_slots; ++k) {
+        int ck = bank_clips[(size_t)k * N + e];
+        ck = ck < 0 ? 0 : (ck > num_clips - 1 ? num_clips - 1 : ck);
+        S += (unsigned)clip_weights[ck] & 0xFFFFu;
+      }
+      if (S != 0) {
+        const unsigned h = rr_fmix32(rr_fmix32(seed ^ ((unsigned)e * 0x9E3779B1u)) + n);
+        const unsigned r = (unsigned)(((unsigned long long)h * (unsigned long long)S) >> 32);
+        unsigned p = 0;
+        drawn = num_slots - 1;
+        for (int k = 0; k < num_slots; ++k) {
+          int ck = bank_clips[(size_t)k * N + e];
+          ck = ck < 0 ? 0 : (ck > num_clips - 1 ? num_clips - 1 : ck);
+          p += (unsigned)clip_weights[ck] & 0xFFFFu;
+          if (p > r) { drawn = k; break; }
+        }
+      }
+    }
+    n = n + 1u;
+    slot = drawn >= 0 ? drawn : (slot + 1 >= num_slots ? 0 : slot + 1);
+  }
+  const size_t row = (size_t)slot * N + e;
+  const int frame = d_out != 0.0f ? bank_frames[row] : new_frame;
+  if (d_out != 0.0f && bank_clips) { c = bank_clips[row]; c = c < 0 ? 0 : (c > num_clips - 1 ? num_clips - 1 : c); }
+  __syncthreads();                       // every thread has read done[e], cur_frame[e] and clip[e] before thread 0 rewrites them
+  if (threadIdx.x == 0) {
+    steps[e] = s1; truncation[e] = over ? 1.0f - d_env : 0.0f; done[e] = d_out; cur_frame[e] = frame; slot_out[e] = slot;
+    if (clip) clip[e] = c;
+    if (draws_out) draws_out[e] = (int)n;
+    if (outcomes) {
+      long long* orow = outcomes + 5 * (size_t)c_step;
+      __hip_atomic_fetch_add(orow + 4, 1ll, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (d_out != 0.0f) {
+        __hip_atomic_fetch_add(orow, 1ll, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_fetch_add(orow + (failed ? 1 : (d_env != 0.0f ? 2 : 3)), 1ll, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+    }
+  }
+  if (d_out != 0.0f) {
+    for (int a = 0; a < A.narr; ++a) {
+      const int w = A.width[a];
+      const float* src = A.first[a] + row * w;
+      float* dst = A.cur[a] + (size_t)e * w;
+      for (int i = threadIdx.x; i < w; i += blockDim.x) dst[i] = src[i];
+    }
+  }
+}
+
+extern "C" int rr_wrap_clip_sampling(int32_t num_envs, int32_t narr, const float* const* first, float* const* cur, const int32_t* widths,
+                                     const float* prev_done, const float* prev_steps, float* done, float* steps, float* truncation,
+                                     float episode_length, float action_repeat, int32_t* cur_frame, const int32_t* bank_frames,
+                                     const int32_t* slot_in, int32_t* slot_out, int32_t num_slots, int32_t track_len, int32_t end_at_clip_end,
+                                     int32_t* clip, const int32_t* bank_clips, const int32_t* clip_lengths, int32_t num_clips,
+                                     const float* pose_fail, const rr_clip_sampling_io* sampling, void* stream) {
+  if (num_envs <= 0 || narr < 0 || narr > RR_WRAP_MAX || !prev_done || !prev_steps || !done || !steps || !truncation || !cur_frame || !bank_frames ||
+      !slot_in || !slot_out || track_len <= 0 || num_clips < 1 || (bank_clips && !clip) || !sampling)
+    return fail(RR_EINVAL, "rr_wrap_clip_sampling: bad argument");
+  if (num_slots < 1 || num_slots > 64) return fail(RR_EINVAL, "rr_wrap_clip_sampling: num_slots must lie in 1 .. 64");
+  if (!sampling->clip_weights && !sampling->outcomes) return fail(RR_EINVAL, "rr_wrap_clip_sampling: null clip_weights and outcomes");
+  if (sampling->clip_weights && (!bank_clips || !sampling->draws_in || !sampling->draws_out)) return fail(RR_EINVAL, "rr_wrap_clip_sampling: clip_weights needs bank_clips, draws_in and draws_out");
+  if (sampling->outcomes && num_clips > 1 && !clip) return fail(RR_EINVAL, "rr_wrap_clip_sampling: outcomes of several clips need clip");
+  RRWrapArgs A;
+  memset(&A, 0, sizeof(A));
+  A.narr = narr;
+  for (int i = 0; i < narr; ++i) {
+    if (!first[i] || !cur[i] || widths[i] <= 0) return fail(RR_EINVAL, "rr_wrap_clip_sampling: null array");
+    A.first[i] = first[i]; A.cur[i] = cur[i]; A.width[i] = widths[i];
+  }
+  hipLaunchKernelGGL(rr_wrap_sampling_kernel, dim3(num_envs), dim3(256), 0, (hipStream_t)stream, A, prev_done, prev_steps, done, steps, truncation,
+                     episode_length, action_repeat, cur_frame, bank_frames, slot_in, slot_out, num_slots, track_len, end_at_clip_end,
+                     clip, bank_clips, clip_lengths, num_clips, pose_fail, sampling->clip_weights, sampling->draws_in, sampling->draws_out,
+                     (long long*)sampling->outcomes, sampling->seed);
+  HIPCHK(hipGetLastError());
+  return RR_OK;
+}
+
 extern "C" int rr_debug_layout(const rr_batch* b, const char*** names, const int32_t** offsets, const int32_t** sizes) {
   if (!b) return fail(RR_EINVAL, "rr_debug_layout: null batch");
   if (names) *names = const_cast<const char**>(b->m->dbg_cnames.data());
@@ -1640,6 +1757,7 @@ extern "C" int rr_batch_clip_restarts_supported(const rr_batch* b, int32_t with_
 extern "C" int rr_batch_set_clip_restarts(rr_batch* b, const rr_clip_restart_io* r) {
   if (!b) return fail(RR_EINVAL, "rr_batch_set_clip_restarts: null batch");
   if (!r) {
+    if (b->has_clip_sampling()) return fail(RR_EINVAL, "rr_batch_set_clip_restarts: the batch carries a clip-sampling block (rr_batch_set_clip_sampling), which counts and draws this block's restores: clear it first");
     if (b->lib.bank_clips) return fail(RR_EINVAL, "rr_batch_set_clip_restarts: the batch carries a clip-library block with bank_clips (rr_batch_set_clip_library), the clips of this block's entries: clear it first");
     b->restart = rr_clip_restart_io{};
     return RR_OK;
@@ -1657,6 +1775,9 @@ extern "C" int rr_batch_clip_library_supported(const rr_batch* b, int32_t with_a
 }
 extern "C" int rr_batch_set_clip_library(rr_batch* b, const rr_clip_library_io* l) {
   if (!b) return fail(RR_EINVAL, "rr_batch_set_clip_library: null batch");
+  if (!l || !l->bank_clips) {
+    if (b->samp.clip_weights) return fail(RR_EINVAL, "rr_batch_set_clip_library: the batch carries a clip-sampling block with clip_weights (rr_batch_set_clip_sampling), which weighs this block's bank_clips: clear it first");
+  }
   if (!l) { b->lib = rr_clip_library_io{}; return RR_OK; }
   if (const char* why = pose_option_limit(b, F_STEP, b->ref_frames, false)) return fail(RR_EUNSUPPORTED, std::string("rr_batch_set_clip_library: ") + why);
   if (!b->pose.track_pose) return fail(RR_EINVAL, "rr_batch_set_clip_library: needs a pose block (rr_batch_set_pose) first: lengths and clip changes serve pose envs only");
@@ -1664,6 +1785,22 @@ extern "C" int rr_batch_set_clip_library(rr_batch* b, const rr_clip_library_io* 
   if (l->bank_clips && !b->restart.frames) return fail(RR_EINVAL, "rr_batch_set_clip_library: bank_clips needs a clip-restart block (rr_batch_set_clip_restarts) first: they are the clips of its entries");
   if (l->bank_clips && !l->clip_out) return fail(RR_EINVAL, "rr_batch_set_clip_library: bank_clips needs clip_out");
   b->lib = *l;
+  return RR_OK;
+}
+extern "C" int rr_batch_clip_sampling_supported(const rr_batch* b, int32_t with_actor) {
+  if (!b) return fail(RR_EINVAL, "rr_batch_clip_sampling_supported: null batch");
+  return supported("rr_batch_clip_sampling_supported", pose_option_limit(b, F_UNROLL, b->ref_frames, with_actor != 0));
+}
+extern "C" int rr_batch_set_clip_sampling(rr_batch* b, const rr_clip_sampling_io* s) {
+  if (!b) return fail(RR_EINVAL, "rr_batch_set_clip_sampling: null batch");
+  if (!s) { b->samp = rr_clip_sampling_io{}; return RR_OK; }
+  if (const char* why = pose_option_limit(b, F_UNROLL, b->ref_frames, false)) return fail(RR_EUNSUPPORTED, std::string("rr_batch_set_clip_sampling: ") + why);
+  if (!b->restart.frames) return fail(RR_EINVAL, "rr_batch_set_clip_sampling: needs a clip-restart block (rr_batch_set_clip_restarts) first: it counts and draws that block's restores");
+  if (!s->clip_weights && !s->outcomes) return fail(RR_EINVAL, "rr_batch_set_clip_sampling: null clip_weights and outcomes (NULL clears the block)");
+  if (s->clip_weights && !b->lib.bank_clips) return fail(RR_EINVAL, "rr_batch_set_clip_sampling: clip_weights needs a clip-library block with bank_clips (rr_batch_set_clip_library) first: the weights are those of the entries' clips");
+  if (s->clip_weights && (!s->draws_in || !s->draws_out)) return fail(RR_EINVAL, "rr_batch_set_clip_sampling: clip_weights needs draws_in and draws_out");
+  if (s->draws_in && s->draws_in == s->draws_out) return fail(RR_EINVAL, "rr_batch_set_clip_sampling: draws_out may not alias draws_in");
+  b->samp = *s;
   return RR_OK;
 }
 extern "C" int32_t rr_batch_obs_width(const rr_batch* b) {

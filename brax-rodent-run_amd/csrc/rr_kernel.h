@@ -348,6 +348,24 @@ struct RRIO {
   const int* clip_len;
   const int* bank_clips;
   int* clip_out;               // [N]
+  // CLIP SAMPLING (RESTART instances, rr_restart_kernel; no other instance reads these; rr_batch_set_clip_sampling).  Integers only.
+  // outcomes [num_clips][5] int64, added to and never cleared by a launch.  With c the clip a wrapped step was made on (before any
+  // restore): col 4 += 1; where done: col 0 += 1 and exactly one of col 1 (the step's pose-termination code is nonzero), col 2 (else the
+  // env's own done: unhealthy, bad state), col 3 (else: `over` alone, a truncation by episode_length or the clip's end).  The launch
+  // counts the steps of the running episode segment in a wave-uniform register and flushes it with the episode's end and with the
+  // launch's last step: one 64-bit atomic add per flush (lane 0, agent scope, relaxed, like `progress`).  Null: no counting.
+  // clip_weights [num_clips] int32, entries 0 .. 65535 (needs bank_clips): a restore draws its slot instead of taking the next one,
+  //   q_k = clip_weights[clamp(bank_clips[k][env])], k = 0 .. K - 1;  S = sum q_k;
+  //   h = fmix32(fmix32(sample_seed ^ (uint32(env) * 0x9E3779B1)) + uint32(n)), n = the env's restore count;  r = (uint64(h) * S) >> 32;
+  //   slot' = the smallest k with q_0 + .. + q_k > r;   S == 0: slot' = (slot + 1) mod K.
+  // Lane k < K loads q_k, an inclusive wave scan of six steps, a ballot of prefix > r and its lowest set bit: wave-uniform, and run only
+  // at a restore.  n is read from draws_in[env] once, grows by one at every restore either way and goes to draws_out[env] after the
+  // launch's last step (null draws_in: n starts at 0 and is not stored).  Null clip_weights: the cyclic rule.
+  const int* clip_weights;
+  const int* draws_in;
+  int* draws_out;              // [N]
+  long long* outcomes;         // [num_clips][5]
+  unsigned sample_seed;
 };
 
 // ------------------------------------------------------------------------------------------ small math
@@ -2677,7 +2695,9 @@ static_assert(offsetof(RRIO, restart_frames) + 3 * sizeof(int*) == offsetof(RRIO
 static_assert(offsetof(RRIO, restart_end) + sizeof(int) == offsetof(RRIO, track_vel) && offsetof(RRIO, track_vel) % 8 == 0, "the velocity-tracking members follow the clip-restart members without padding");
 static_assert(offsetof(RRIO, track_vel) + 2 * sizeof(float*) == offsetof(RRIO, vel_lin_w), "the weights and scales follow the two velocity-tracking pointers without padding");
 static_assert(offsetof(RRIO, vel_joint_k) + sizeof(float) == offsetof(RRIO, clip_len) && offsetof(RRIO, clip_len) % 8 == 0, "the clip-library members follow the velocity-tracking members without padding");
-static_assert(offsetof(RRIO, clip_len) + 3 * sizeof(int*) == sizeof(RRIO), "the three clip-library pointers close RRIO without padding");
+static_assert(offsetof(RRIO, clip_len) + 3 * sizeof(int*) == offsetof(RRIO, clip_weights), "the clip-sampling members follow the three clip-library pointers without padding");
+static_assert(offsetof(RRIO, clip_weights) + 4 * sizeof(int*) == offsetof(RRIO, sample_seed), "the seed follows the four clip-sampling pointers without padding");
+static_assert(offsetof(RRIO, sample_seed) + 2 * sizeof(unsigned) == sizeof(RRIO), "the seed closes RRIO (one word of tail padding: the struct is 8-byte aligned)");
 // ... and so are the model tables outside the solver's loops: RRTables is re-read at the head of each phase that indexes a table
 // (narrow scalar loads next to an existing hand-off; the unused members' loads are dead), so no table pointer is held across the
 // substep.  The loops' own tables are the exception (RRLoopTables, taken once from the parameter).
@@ -2743,6 +2763,33 @@ static __device__ __forceinline__ int rr_clip_frames(int c, int track_len) {
   } else {
     return track_len;
   }
+}
+
+// MurmurHash3's 32-bit finaliser, the hash of the weighted restore (RRIO, CLIP SAMPLING)
+static __device__ __host__ __forceinline__ unsigned rr_fmix32(unsigned h) {
+  h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;
+  return h;
+}
+
+// The slot a weighted restore of `env` draws (RRIO, CLIP SAMPLING), or -1 where every entry of the env's bank has weight 0.  Called by
+// the whole wave with wave-uniform arguments; K <= 64 = one lane per entry.  Lanes >= K carry the total, so the ballot's lowest set bit
+// is a slot of the bank whenever S > r, which r's definition guarantees.
+static __device__ __forceinline__ int rr_weighted_slot(const int* cw, const int* bcl, int K, int nc, int env, int num_envs, unsigned seed, unsigned n, int lane) {
+  unsigned p = 0;
+  if (lane < K) {
+    int c = bcl[(size_t)lane * (size_t)num_envs + (size_t)env];
+    c = c < 0 ? 0 : (c > nc - 1 ? nc - 1 : c);
+    p = (unsigned)cw[c] & 0xFFFFu;      // entries are 0 .. 65535 by contract: the mask keeps S within 32 bits whatever the table holds
+  }
+#pragma unroll
+  for (int d = 1; d < RR_LANES; d <<= 1) { const unsigned t = __shfl_up(p, d, RR_LANES); if (lane >= d) p += t; }
+  const unsigned S = (unsigned)__builtin_amdgcn_readlane((int)p, RR_LANES - 1);
+  if (S == 0) return -1;
+  const unsigned h = rr_fmix32(rr_fmix32(seed ^ ((unsigned)env * 0x9E3779B1u)) + n);
+  const unsigned r = (unsigned)(((unsigned long long)h * (unsigned long long)S) >> 32);
+  const unsigned long long m = __ballot(p > r);
+  const int k = (int)__builtin_ctzll(m | (1ull << (K - 1)));      // (the guard bit is never the lowest: slot K - 1 has prefix S > r)
+  return __builtin_amdgcn_readfirstlane(k);
 }
 
 // RAND instances: the tables with the three randomisable ones advanced to environment `env`'s rows.  `env` is wave-uniform, the

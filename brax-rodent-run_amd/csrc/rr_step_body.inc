@@ -44,6 +44,8 @@
   int u_frame = 0;
   int u_slot = 0;                // RESTART: the bank entry the env's next restore follows (RRIO, CLIP RESTARTS)
   int u_clip = 0;                // RESTART: the clip the env is on, clamped; a restore may move it (RRIO, CLIP LIBRARY); 0 without clip ids
+  unsigned u_draws = 0;          // RESTART: restores of the env so far, the counter of the weighted draw's hash (RRIO, CLIP SAMPLING)
+  int u_seg = 0;                 // RESTART: wrapped steps of the running episode segment not yet added to the outcome table
   unsigned u_work = 0;
   int u_overflow = 0;            // DYN: some step of this launch dropped pairs (RRIO::cost bit 31 of a multi-step launch)
   if (UNROLL) {
@@ -61,6 +63,7 @@
         u_clip = __builtin_amdgcn_readfirstlane(cp[env]);
         u_clip = u_clip < 0 ? 0 : (u_clip > nc - 1 ? nc - 1 : u_clip);
       }
+      if (const int* di = load_io_member<const int*>(offsetof(RRIO, draws_in))) u_draws = (unsigned)__builtin_amdgcn_readfirstlane(di[env]);
     }
   }
   int niter = 0;
@@ -689,9 +692,36 @@
         if (io.e_qpos_out) for (int i = lane; i < D.nq; i += RR_LANES) io.e_qpos_out[((size_t)(ut + 1) * num_envs + env) * D.nq + i] = w.s_qpos[i];
       }
       if (RESTART) {
-        if (__builtin_amdgcn_readfirstlane(__float_as_int(done2)) != 0) {
+        const bool ended = __builtin_amdgcn_readfirstlane(__float_as_int(done2)) != 0;
+        // CLIP SAMPLING, outcome counters: on the clip the step was made on (u_clip moves below).  The segment's steps are flushed with the
+        // episode's end and with the launch's last step
+        if (long long* oc = load_io_member<long long*>(offsetof(RRIO, outcomes))) {
+          u_seg = u_seg + 1;
+          if (ended || ut == nsteps - 1) {
+            if (lane == 0) {
+              long long* row = oc + 5 * (size_t)u_clip;
+              __hip_atomic_fetch_add(row + 4, (long long)u_seg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+              if (ended) {
+                const int col = (PTERM && pterm_code != 0) ? 1 : (done_env != 0.0f ? 2 : 3);
+                __hip_atomic_fetch_add(row, 1ll, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_fetch_add(row + col, 1ll, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+              }
+            }
+            u_seg = 0;
+          }
+        }
+        if (ended) {
+          // CLIP SAMPLING, weighted restore: the slot drawn by the env's bank weights; the next slot without a table or with S == 0
+          int drawn = -1;
+          if (const int* cw = load_io_member<const int*>(offsetof(RRIO, clip_weights))) {
+            if (const int* wbc = load_io_member<const int*>(offsetof(RRIO, bank_clips)))
+              drawn = rr_weighted_slot(cw, wbc, load_io_member<int>(offsetof(RRIO, restart_K)), load_io_member<int>(offsetof(RRIO, num_clips)), env, num_envs,
+                                       load_io_member<unsigned>(offsetof(RRIO, sample_seed)), u_draws, lane);
+          }
+          u_draws = u_draws + 1u;
           u_slot = u_slot + 1;
           if (u_slot >= load_io_member<int>(offsetof(RRIO, restart_K))) u_slot = 0;
+          if (drawn >= 0) u_slot = drawn;
           const size_t re = (size_t)u_slot * (size_t)num_envs + (size_t)env;      // row of the bank entry in every [K][N][width] array
           u_frame = __builtin_amdgcn_readfirstlane(load_io_member<const int*>(offsetof(RRIO, restart_frames))[re]);
           if (const int* bcl = load_io_member<const int*>(offsetof(RRIO, bank_clips))) {      // CLIP LIBRARY: the entry's clip, clamped
@@ -735,6 +765,7 @@
         if (RESTART) {      // the frame and the slot the next launch goes on from (lane 0 stored new_frame above: program order)
           if (lane == 0) { io.cur_frame[env] = u_frame; load_io_member<int*>(offsetof(RRIO, restart_slot_out))[env] = u_slot; }
           if (lane == 0) { if (int* co = load_io_member<int*>(offsetof(RRIO, clip_out))) co[env] = u_clip; }      // CLIP LIBRARY: the clip the next launch goes on from
+          if (lane == 0) { if (int* dro = load_io_member<int*>(offsetof(RRIO, draws_out))) dro[env] = (int)u_draws; }      // CLIP SAMPLING: the restore count likewise
         }
         for (int i = lane; i < D.nq; i += RR_LANES) io.qpos[(size_t)env * D.nq + i] = w.s_qpos[i];
         for (int i = lane; i < D.nv; i += RR_LANES) { io.qvel[(size_t)env * D.nv + i] = w.s_qvel[i]; io.warm[(size_t)env * D.nv + i] = w.s_warm[i]; }

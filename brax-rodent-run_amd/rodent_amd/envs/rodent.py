@@ -123,6 +123,124 @@ def _check_clip_library(clip_lengths, restart_across_clips, track: np.ndarray, h
     return np.ascontiguousarray(L, dtype=np.int32), across
 
 
+_M32 = np.uint64(0xFFFFFFFF)
+MAX_CLIP_WEIGHT = 65535      # the largest entry of the device's weight table; K <= 64 entries then sum within 32 bits
+OUTCOME_COLUMNS = ("episodes", "pose_fail", "env_done", "truncated", "steps")      # the columns of the [C, 5] outcome table
+
+
+def _fmix32(h):
+    """MurmurHash3's 32-bit finaliser on uint64 arrays holding 32-bit values."""
+    h = np.asarray(h, dtype=np.uint64) & _M32
+    h = h ^ (h >> np.uint64(16))
+    h = (h * np.uint64(0x85EBCA6B)) & _M32
+    h = h ^ (h >> np.uint64(13))
+    h = (h * np.uint64(0xC2B2AE35)) & _M32
+    return h ^ (h >> np.uint64(16))
+
+
+def restart_hash(seed, env, n) -> np.ndarray:
+    """The 32-bit hash a weighted restore draws with (`Rodent(restart_sampling="weighted")`; C ABI `rr_clip_sampling_io`), uint64 holding
+    32-bit values, broadcast over `env` and `n`: fmix32((fmix32(seed ^ (env * 0x9E3779B1)) + n)), every operation mod 2**32, fmix32
+    MurmurHash3's finaliser.  `env` the env's index, `n` its restore count (`info['restart_draws']`) before the restore."""
+    env = np.asarray(env).astype(np.uint64) & _M32
+    n = np.asarray(n).astype(np.uint64) & _M32
+    first = _fmix32((np.uint64(int(seed) & 0xFFFFFFFF) ^ ((env * np.uint64(0x9E3779B1)) & _M32)))
+    return _fmix32((first + n) & _M32)
+
+
+def weighted_slot(h, slot_weights, slot: int = 0) -> int:
+    """The bank entry a weighted restore takes: `h` the 32-bit hash (`restart_hash`), `slot_weights` the K integer weights q_k of the
+    env's bank entries (`clip_weights()[bank clip[k]]`, 0 .. 65535), S their sum.  r = (h * S) >> 32 and the result is the smallest k
+    with q_0 + .. + q_k > r: an entry of weight 0 is never drawn.  S == 0: the cyclic rule's (`slot` + 1) mod K."""
+    q = [int(x) for x in np.asarray(slot_weights).reshape(-1)]
+    S = sum(q)
+    if S == 0:
+        return (int(slot) + 1) % len(q)
+    r = (int(h) * S) >> 32
+    acc = 0
+    for k, qk in enumerate(q):
+        acc += qk
+        if acc > r:
+            return k
+    raise AssertionError("unreachable: r < S")
+
+
+def quantise_clip_weights(w) -> np.ndarray:
+    """Float weights [C], finite, >= 0 and not all zero, as the int32 table the device reads: 0 -> 0, otherwise
+    max(1, round(65535 * w / max w)) (round half to even), so the largest weight is 65535 and no positive weight is lost."""
+    w = np.asarray(w, dtype=np.float64)
+    if w.ndim != 1 or not np.isfinite(w).all() or (w < 0).any() or not (w > 0).any():
+        raise ValueError(f"clip weights must be a float [C] array, finite, >= 0 and not all zero, got {w!r}")
+    q = np.maximum(1, np.rint(MAX_CLIP_WEIGHT * (w / w.max()))).astype(np.int32)
+    return np.where(w > 0, q, 0).astype(np.int32)
+
+
+def clip_outcome_update(outcomes: np.ndarray, clip, code, done_env, done) -> np.ndarray:
+    """One wrapped env step of the outcome counters (`Rodent(clip_outcomes=True)`; C ABI `rr_clip_sampling_io`), added to `outcomes`
+    int64 [C, 5] in place (and returned): `clip` int [N] the clip each step was made on (before any restore), `code` [N] the step's
+    pose-termination code (0 without pose termination), `done_env` [N] the env's own done, `done` [N] the wrapped done.  Col 4 counts
+    the steps, col 0 the ended episodes, and each of those falls into exactly one of col 1 (code != 0), col 2 (else done_env), col 3
+    (else: a truncation)."""
+    clip = np.asarray(clip, dtype=np.int64).reshape(-1)
+    N = clip.shape[0]
+    as_flag = lambda a: np.broadcast_to(np.asarray(a).reshape(-1) != 0, (N,))
+    failed, own, ended = as_flag(code), as_flag(done_env), as_flag(done)
+    col = np.where(failed, 1, np.where(own, 2, 3))
+    np.add.at(outcomes, (clip, 4), 1)
+    np.add.at(outcomes, (clip[ended], 0), 1)
+    np.add.at(outcomes, (clip[ended], col[ended]), 1)
+    return outcomes
+
+
+class FailureWeights:
+    """A `clip_weight_fn` for `ppo.train`: restart weights from an exponentially decayed failure rate per clip.  Called with a training
+    step's outcome table [C, 5] it updates fails_c <- decay * fails_c + (col 1 + col 2) and episodes_c <- decay * episodes_c + col 0,
+    and returns w_c = floor + (1 - floor) * fails_c / episodes_c, with weight 1 for a clip that has not finished an episode yet (so an
+    unseen clip is tried).  None -- keep the weights -- while every weight would be 0 (`floor` 0 and no failure so far).  `floor` and
+    `decay` are untuned defaults."""
+
+    def __init__(self, floor: float = 0.1, decay: float = 0.9):
+        if not 0.0 <= floor <= 1.0 or not 0.0 <= decay < 1.0:
+            raise ValueError(f"FailureWeights needs 0 <= floor <= 1 and 0 <= decay < 1, got floor={floor!r}, decay={decay!r}")
+        self.floor, self.decay = float(floor), float(decay)
+        self.fails = self.episodes = None
+
+    def rates(self) -> Optional[np.ndarray]:
+        """The decayed failure rate per clip, NaN for a clip without a finished episode; None before the first call."""
+        if self.fails is None:
+            return None
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(self.episodes > 0, self.fails / self.episodes, np.nan)
+
+    def __call__(self, outcomes) -> Optional[np.ndarray]:
+        o = np.asarray(outcomes, dtype=np.float64)
+        if self.fails is None:
+            self.fails, self.episodes = np.zeros(o.shape[0]), np.zeros(o.shape[0])
+        self.fails = self.decay * self.fails + (o[:, 1] + o[:, 2])
+        self.episodes = self.decay * self.episodes + o[:, 0]
+        rate = self.rates()
+        w = np.where(np.isnan(rate), 1.0, self.floor + (1.0 - self.floor) * np.nan_to_num(rate))
+        return w if (w > 0).any() else None
+
+
+def _check_clip_sampling(restart_sampling, clip_outcomes, restart_sampling_seed, across: bool, clip_restarts: int, num_clips: Optional[int]):
+    """`restart_sampling`, `clip_outcomes` and `restart_sampling_seed` of `Rodent` as (weighted, counting, seed); ValueError for a
+    sampling other than None / "weighted", "weighted" without `restart_across_clips=True`, `clip_outcomes=True` without
+    `clip_restarts >= 1` or without a clip axis, and a seed outside 0 .. 2**32 - 1."""
+    if restart_sampling not in (None, "weighted"):
+        raise ValueError(f"restart_sampling must be None (the next entry of the bank) or 'weighted', got {restart_sampling!r}")
+    weighted, counting = restart_sampling == "weighted", bool(clip_outcomes)
+    if weighted and not across:
+        raise ValueError("restart_sampling='weighted' needs restart_across_clips=True: the weights are those of the bank entries' clips")
+    if counting and clip_restarts < 1:
+        raise ValueError("clip_outcomes=True needs clip_restarts >= 1: the counters sit in the clip-restart rule")
+    if counting and num_clips is None:
+        raise ValueError("clip_outcomes=True needs a [C, T, 3] track_pos: a single [T, 3] track has no clip axis to count by")
+    if isinstance(restart_sampling_seed, (bool, np.bool_)) or not isinstance(restart_sampling_seed, (int, np.integer)) or not 0 <= int(restart_sampling_seed) < 2 ** 32:
+        raise ValueError(f"restart_sampling_seed must be an int in 0 .. 2**32 - 1, got {restart_sampling_seed!r}")
+    return weighted, counting, int(restart_sampling_seed)
+
+
 def _check_clip_restarts(clip_restarts, restart_frame_range, end_at_clip_end, have_pose: bool, track_len: int, have_lengths: bool = False):
     """`clip_restarts`, `restart_frame_range` and `end_at_clip_end` of `Rodent` as (K, (lo, hi), flag); ValueError for K outside 0 .. 64,
     any of the three without the pose arguments, `end_at_clip_end` with K = 0, lo < 0 or hi <= lo, and -- with `end_at_clip_end` -- a
@@ -559,6 +677,9 @@ class Rodent(PipelineEnv):
         joint_vel_reward_scale: float = 0.01,
         clip_lengths=None,
         restart_across_clips: bool = False,
+        restart_sampling: Optional[str] = None,
+        clip_outcomes: bool = False,
+        restart_sampling_seed: int = 0,
         **kwargs,
     ):
         """`track_pos`: the reference positions to track, float [T, 3] -- one clip, followed by every env -- or [C, T, 3], C >= 1 clips of
@@ -685,7 +806,22 @@ class Rodent(PipelineEnv):
             done:  clip <- bank clip[slot']
 
         so `info['clip']` changes at a restore in the wrapped forms (a fresh tensor; the input state's is left alone).  The bare `step`
-        does not change the clip."""
+        does not change the clip.
+
+        Clip sampling (both off by default, and off is today's path in every bit and every key; integers only, so the composed
+        wrappers, the fused per-step wrapper and both one-launch rollouts agree bit for bit).  `clip_outcomes=True` (needs
+        `clip_restarts` >= 1 and a clip axis): the wrapped forms count, per clip the step was made on, the wrapped steps (col 4), the
+        ended episodes (col 0) and why each ended -- pose failure (col 1), else the env's own done: unhealthy or a bad state (col 2),
+        else a truncation by `episode_length` or the clip's end (col 3) -- in an int64 [C, 5] device table that `clip_outcomes()` reads
+        (`clip_outcome_update` restates a step).  `restart_sampling="weighted"` (needs `restart_across_clips=True`): a restore draws its
+        bank entry instead of taking the next one, with probability proportional to the weight of the entry's clip,
+
+            q_k = clip_weights()[bank clip[k]];  S = sum q_k;  h = restart_hash(restart_sampling_seed, env, n);  r = (h * S) >> 32
+            done:  slot' = the smallest k with q_0 + .. + q_k > r        (`weighted_slot`; S == 0: the cyclic rule)
+
+        n = `info['restart_draws']` (int32 [N], zeros at `reset`), the env's restore count, which grows by one at every restore.  The
+        weights start uniform (all 65535) and are set with `set_clip_weights` -- in place, so later launches and replayed graphs see
+        them; a clip of weight 0 is never drawn while another entry of the env's bank has a positive one."""
         given = locals()                  # the arguments as they came (first statement: nothing else is a local yet): `_ctor` below
         if bad_state_max is not None:
             with np.errstate(over="ignore", under="ignore"):
@@ -711,6 +847,8 @@ class Rodent(PipelineEnv):
                                        (body_reward_weight, body_reward_scale, endeff_reward_weight, endeff_reward_scale), pose_np is not None)
         restarts = _check_clip_restarts(clip_restarts, restart_frame_range, end_at_clip_end, pose_np is not None, track_np.shape[-2], clip_lengths is not None)
         lengths_np, across = _check_clip_library(clip_lengths, restart_across_clips, track_np, pose_np is not None, restarts[0])
+        weighted, counting, sample_seed = _check_clip_sampling(restart_sampling, clip_outcomes, restart_sampling_seed, across, restarts[0],
+                                                               track_np.shape[0] if track_np.ndim == 3 else None)
         vel_np = _check_velocity_tracking(track_np, track_velocity, track_angular_velocity, track_joint_velocity, sys.nv,
                                           (lin_vel_reward_weight, lin_vel_reward_scale, ang_vel_reward_weight, ang_vel_reward_scale,
                                            joint_vel_reward_weight, joint_vel_reward_scale), pose_np is not None)
@@ -734,6 +872,13 @@ class Rodent(PipelineEnv):
         self._lengths_host = lengths_np       # None: every clip has T frames (no such members anywhere)
         self._clip_lengths = None if lengths_np is None else torch.from_numpy(lengths_np).to(self.device).contiguous()
         self._across_clips = across
+        # clip sampling: None without either option (no such members anywhere); the two tables live for the env's life and are rewritten
+        # in place, so a captured launch keeps reading them
+        self._sampling = None
+        if weighted or counting:
+            C_ = track_np.shape[0]
+            self._sampling = dict(weights=torch.full((C_,), MAX_CLIP_WEIGHT, dtype=torch.int32, device=self.device) if weighted else None,
+                                  outcomes=torch.zeros(C_, 5, dtype=torch.int64, device=self.device) if counting else None, seed=sample_seed)
         batch = self._batch
 
         def reference_frames_supported():
@@ -751,7 +896,8 @@ class Rodent(PipelineEnv):
                   (body_np is not None, "track_bodies=...", batch.body_tracking_supported),
                   (vel_np is not None, "track_velocity=...", batch.velocity_tracking_supported),
                   (self._clip_restarts > 0, f"clip_restarts={self._clip_restarts}", batch.clip_restarts_supported),
-                  (lengths_np is not None or across, "clip_lengths=... / restart_across_clips=True", batch.clip_library_supported))
+                  (lengths_np is not None or across, "clip_lengths=... / restart_across_clips=True", batch.clip_library_supported),
+                  (weighted or counting, "restart_sampling=... / clip_outcomes=True", batch.clip_sampling_supported))
         for wanted, label, query in probes:       # a model, solver or frame count without the option's instance: the library's reason
             why = query() if wanted else None
             if why is not None:
@@ -869,6 +1015,38 @@ class Rodent(PipelineEnv):
         return self._across_clips
 
     @property
+    def clip_sampling(self) -> Optional[dict]:
+        """None without `restart_sampling` / `clip_outcomes`, else dict(weights=int32 [C] device table or None, outcomes=int64 [C, 5]
+        device table or None, seed): the tables themselves, which the wrapped forms read and add to."""
+        return self._sampling
+
+    def set_clip_weights(self, w):
+        """The weights a weighted restore draws by (`restart_sampling="weighted"`): float [C], finite, >= 0, not all zero, quantised by
+        `quantise_clip_weights`.  Written into the device table IN PLACE: every later launch sees them, a replayed graph included."""
+        if self._sampling is None or self._sampling["weights"] is None:
+            raise ValueError("set_clip_weights needs an env built with restart_sampling='weighted'")
+        w = w.detach().cpu().numpy() if torch.is_tensor(w) else np.asarray(w)
+        if w.shape != (self.num_clips,):
+            raise ValueError(f"clip weights must have shape ({self.num_clips},), got {tuple(w.shape)}")
+        self._sampling["weights"].copy_(torch.from_numpy(quantise_clip_weights(w)))
+
+    def clip_weights(self) -> Optional[np.ndarray]:
+        """The weight table as the device holds it, int32 numpy [C] (None without `restart_sampling="weighted"`)."""
+        if self._sampling is None or self._sampling["weights"] is None:
+            return None
+        return self._sampling["weights"].cpu().numpy().copy()
+
+    def clip_outcomes(self, clear: bool = False) -> np.ndarray:
+        """The outcome counters so far, int64 numpy [C, 5] with the columns `OUTCOME_COLUMNS` (`clip_outcomes=True`, else ValueError);
+        `clear` zeroes the device table after the read (in place).  Synchronises the env's stream."""
+        if self._sampling is None or self._sampling["outcomes"] is None:
+            raise ValueError("clip_outcomes() needs an env built with clip_outcomes=True")
+        out = self._sampling["outcomes"].cpu().numpy().copy()      # (a copy: a CPU tensor shares its memory with the array)
+        if clear:
+            self._sampling["outcomes"].zero_()
+        return out
+
+    @property
     def track_len(self) -> int:
         """Frames T of a clip."""
         return int(self._track_host.shape[-2])
@@ -893,11 +1071,12 @@ class Rodent(PipelineEnv):
             raise RuntimeError("pose tracking: no pose instance reads per-env parameters (randomize / set_env_params on a pose env)")
         return super().randomize(randomization_fn)
 
-    def _env_io(self, cur_frame, obs, reward=None, done=None, metrics=None, clip=None, restart=None, clip_library=None, **buffers):
+    def _env_io(self, cur_frame, obs, reward=None, done=None, metrics=None, clip=None, restart=None, clip_library=None, clip_sampling=None, **buffers):
         """The env-io dict of a launch.  `buffers`: the step options' output buffers by env-io key (`_launch_buffers`); each brings its
         option's static entries along.  `restart`: the clip-restart block of a multi-step launch (single steps and resets pass none).
         `clip_library`: the clip-library block (an env with `clip_lengths` or `restart_across_clips` only); it rides on the pose block,
-        so a reset that hands none (no reference frames: it reads no clamped frame) hands no library either."""
+        so a reset that hands none (no reference frames: it reads no clamped frame) hands no library either.  `clip_sampling`: the
+        clip-sampling block, which rides on the clip-restart block."""
         io = dict(track_pos=self._track_pos, cur_frame=cur_frame, obs=obs, reward=reward, done=done, metrics=metrics, clip=clip,
                   healthy_reward=self._healthy_reward, ctrl_cost_weight=self._ctrl_cost_weight,
                   healthy_z_range=self._healthy_z_range, terminate_when_unhealthy=self._terminate_when_unhealthy,
@@ -912,6 +1091,8 @@ class Rodent(PipelineEnv):
             io["restart"] = restart
         if clip_library is not None and "pose_metrics" in buffers:
             io["clip_library"] = clip_library
+        if clip_sampling is not None and restart is not None:
+            io["clip_sampling"] = clip_sampling
         return io
 
     def reset(self, rng, clip=None) -> State:
@@ -971,6 +1152,8 @@ class Rodent(PipelineEnv):
             if self._across_clips:
                 info["restart_bank"]["clip"] = to_dev(np.stack(clips))
             info["restart_slot"] = torch.zeros(N, dtype=torch.int32, device=dev)
+            if self._sampling is not None and self._sampling["weights"] is not None:      # the restore count the weighted draw hashes
+                info["restart_draws"] = torch.zeros(N, dtype=torch.int32, device=dev)
         zero = torch.zeros(N, device=dev)
         metrics = {"pos_reward": zero, "reward_quadctrl": zero.clone(), "reward_alive": zero.clone()}
         for o in self._options:
@@ -1005,6 +1188,10 @@ class Rodent(PipelineEnv):
             io["clip_library"] = dict(lengths=self._clip_lengths)
             if self._across_clips and wrap is not None:
                 io["clip_library"].update(bank_clips=info["restart_bank"]["clip"], clip_out=torch.empty_like(info["clip"]))
+        if self._sampling is not None and wrap is not None:      # clip sampling: the multi-step forms count and draw in the kernel
+            io["clip_sampling"] = dict(self._sampling)
+            if self._sampling["weights"] is not None:
+                io["clip_sampling"].update(draws_in=info["restart_draws"], draws_out=torch.empty_like(info["restart_draws"]))
         return st_in, st, io, wrap
 
     def _next_state(self, state: State, st, io, obs, wrap=None, out=None) -> State:
@@ -1017,6 +1204,8 @@ class Rodent(PipelineEnv):
                 info["restart_slot"] = io["restart"]["slot_out"]
             if io.get("clip_library", {}).get("clip_out") is not None:
                 info["clip"] = io["clip_library"]["clip_out"]
+            if io.get("clip_sampling", {}).get("draws_out") is not None:
+                info["restart_draws"] = io["clip_sampling"]["draws_out"]
         m = dict(state.metrics)
         m.update(pos_reward=io["metrics"][:, 0], reward_quadctrl=io["metrics"][:, 1], reward_alive=io["metrics"][:, 2])
         for o in self._options:

@@ -9,7 +9,8 @@ its clip across restores.  `reset(rng, **kw)` hands keyword arguments (`clip=`) 
 An env with clip restarts (`Rodent(clip_restarts=K)`, K >= 1) is wrapped by `ClipEpisodeWrapper` and `ClipAutoResetWrapper` instead: the
 clip's end may truncate the episode, and a restore takes the next entry of the env's start bank -- state, observation AND frame.
 With the clip library (`Rodent(clip_lengths=..., restart_across_clips=True)`) the clip's end is that of the env's own clip, and the restore
-also takes the entry's clip: `info['clip']` then changes at a restore.
+also takes the entry's clip: `info['clip']` then changes at a restore.  With clip sampling (`Rodent(restart_sampling="weighted",
+clip_outcomes=True)`) the restore draws its entry by the clips' weights and every wrapped step is counted per clip, in integers.
 """
 from __future__ import annotations
 
@@ -153,11 +154,48 @@ class ClipEpisodeWrapper(EpisodeWrapper):
         return state.replace(done=done)
 
 
+_M32 = 0xFFFFFFFF
+
+
+def _fmix32(h):
+    """MurmurHash3's 32-bit finaliser on int64 tensors holding 32-bit values (a product's low 32 bits survive the int64 wrap-around)."""
+    h = h ^ (h >> 16)
+    h = (h * 0x85EBCA6B) & _M32
+    h = h ^ (h >> 13)
+    h = (h * 0xC2B2AE35) & _M32
+    return h ^ (h >> 16)
+
+
+def weighted_slots(weights, bank_clips, seed: int, draws):
+    """`rodent.weighted_slot` for every env at once, in torch integers: `weights` int32 [C], `bank_clips` int32 [K, N], `draws` int32 [N]
+    -> int64 [N], the drawn slot, -1 where every entry of the env's bank has weight 0."""
+    q = (weights.long() & 0xFFFF)[bank_clips.long().clamp(0, weights.shape[0] - 1)]      # [K, N]
+    prefix = q.cumsum(0)
+    S = prefix[-1]
+    env = torch.arange(bank_clips.shape[1], device=bank_clips.device)
+    h = _fmix32((_fmix32((int(seed) & _M32) ^ ((env * 0x9E3779B1) & _M32)) + (draws.long() & _M32)) & _M32)
+    r = (h * S) >> 32
+    k = (prefix <= r).sum(0)            # prefixes never decrease: the count of those <= r is the first index with prefix > r
+    return torch.where(S > 0, k, torch.full_like(k, -1))
+
+
+def count_outcomes(outcomes, clip, failed, done_env, done):
+    """`rodent.clip_outcome_update` in torch integers, added to the int64 [C, 5] device table `outcomes` in place: `clip` int64 [N],
+    `failed` / `done_env` / `done` bool [N]."""
+    flat, d = outcomes.view(-1), done.long()
+    col = torch.where(failed, 1, torch.where(done_env, 2, 3))
+    flat.index_add_(0, clip * 5 + 4, torch.ones_like(d))
+    flat.index_add_(0, clip * 5, d)
+    flat.index_add_(0, clip * 5 + col, d)
+
+
 class ClipAutoResetWrapper(Wrapper):
     """`AutoResetWrapper` of an env with clip restarts: where done, the env takes the NEXT entry of its start bank
     (`info['restart_bank']`, built by the env's `reset`) -- slot' = (slot + 1) mod K; pipeline state, observation and `cur_frame` come
     from entry slot' -- so the restarted episode rejoins its clip at the frame its state was formed at.  Bank and slot are info: never
-    re-drawn, never restored.  A bank with a `clip` leaf (`restart_across_clips`) also hands its entry's clip to `info['clip']`."""
+    re-drawn, never restored.  A bank with a `clip` leaf (`restart_across_clips`) also hands its entry's clip to `info['clip']`.  An env
+    with `clip_sampling` tables (`Rodent(restart_sampling=..., clip_outcomes=...)`) has its steps counted on the clip they were made on,
+    and its restores drawn by the clips' weights (`weighted_slots`; `info['restart_draws']` grows by one at every restore)."""
 
     def step(self, state, action):
         if "steps" in state.info:
@@ -170,6 +208,19 @@ class ClipAutoResetWrapper(Wrapper):
         bank, slot = state.info["restart_bank"], state.info["restart_slot"]
         K = bank["frame"].shape[0]
         nslot = torch.where(done, (slot + 1) % K, slot)
+        sampling = getattr(_base(self.env), "clip_sampling", None)
+        if sampling is not None:
+            if sampling["outcomes"] is not None:
+                # the env's own done back out of the wrapped one: truncation = over ? 1 - done_env : 0, so done_env = done and no truncation
+                own = done & (state.info["truncation"] == 0)
+                failed = state.metrics["pose_fail"] != 0 if "pose_fail" in state.metrics else torch.zeros_like(done)
+                on = state.info["clip"].long() if "clip" in state.info else torch.zeros_like(slot, dtype=torch.long)
+                count_outcomes(sampling["outcomes"], on.clamp(0, sampling["outcomes"].shape[0] - 1), failed, own, done)
+            if sampling["weights"] is not None:
+                draws = state.info["restart_draws"]
+                drawn = weighted_slots(sampling["weights"], bank["clip"], sampling["seed"], draws)
+                nslot = torch.where(done & (drawn >= 0), drawn.to(slot.dtype), nslot)
+                state.info["restart_draws"] = draws + done.to(draws.dtype)
         row, env = nslot.long(), torch.arange(done.shape[0], device=done.device)
 
         def where_done(x, y):      # x: the bank's leaf [K, N, ...]
@@ -266,7 +317,20 @@ class FusedEpisodeAutoResetWrapper(Wrapper):
             steps, trunc = torch.empty_like(nstate.done), torch.empty_like(nstate.done)
             slot = torch.empty_like(state.info["restart_slot"])
             lengths = getattr(base, "clip_lengths", None)
-            if lengths is not None or "clip" in bank:      # the clip library: the env's own clip's end, the entry's clip with its frame
+            sampling = getattr(base, "clip_sampling", None)
+            if sampling is not None:      # clip sampling: the library's rule plus the counters and the weighted draw
+                clip = state.info["clip"].clone() if "clip" in state.info else None
+                draws = state.info.get("restart_draws")
+                ndraws = None if draws is None else torch.empty_like(draws)
+                hip.wrap_clip_sampling(first, cur, state.done, state.info["steps"], nstate.done, steps, trunc, self.episode_length, 1,
+                                       nstate.info["cur_frame"], bank["frame"], state.info["restart_slot"], slot, base.track_len, base.end_at_clip_end,
+                                       base.num_clips, clip, bank.get("clip"), lengths, nstate.metrics.get("pose_fail"), sampling["weights"],
+                                       draws, ndraws, sampling["outcomes"], sampling["seed"])
+                if clip is not None:
+                    nstate.info["clip"] = clip
+                if ndraws is not None:
+                    nstate.info["restart_draws"] = ndraws
+            elif lengths is not None or "clip" in bank:      # the clip library: the env's own clip's end, the entry's clip with its frame
                 clip = state.info["clip"].clone() if "clip" in state.info else None      # the bare step leaves the ids alone: finished in a copy
                 hip.wrap_clip_library(first, cur, state.done, state.info["steps"], nstate.done, steps, trunc, self.episode_length, 1,
                                       nstate.info["cur_frame"], bank["frame"], state.info["restart_slot"], slot, base.track_len, base.end_at_clip_end,

@@ -83,6 +83,11 @@ class RRClipLibraryIO(C.Structure):
     _fields_ = [("clip_lengths", C.c_void_p), ("bank_clips", C.c_void_p), ("clip_out", C.c_void_p)]
 
 
+class RRClipSamplingIO(C.Structure):
+    """`rr_clip_sampling_io`, the clip-sampling block a batch carries next to its clip-restart block (`rr_batch_set_clip_sampling`)."""
+    _fields_ = [("clip_weights", C.c_void_p), ("draws_in", C.c_void_p), ("draws_out", C.c_void_p), ("outcomes", C.c_void_p), ("seed", C.c_uint32)]
+
+
 class RRUnrollIO(C.Structure):
     _fields_ = [("first", RRState), ("first_obs", C.c_void_p), ("prev_done", C.c_void_p), ("steps_in", C.c_void_p), ("steps_out", C.c_void_p),
                 ("truncation_out", C.c_void_p), ("episode_length", C.c_float)]
@@ -114,7 +119,7 @@ class RRPpoCfg(C.Structure):
 
 
 EXPORTS = ["rr_model_load", "rr_model_dims", "rr_model_set_solver", "rr_model_set_solver_type", "rr_model_destroy", "rr_model_table", "rr_kernarg_layout", "rr_batch_create",
-           "rr_batch_destroy", "rr_pipeline_init", "rr_pipeline_step", "rr_env_step", "rr_env_reset", "rr_pipeline_step_to", "rr_env_step_to", "rr_batch_contact_overflow", "rr_batch_bad_states", "rr_batch_unroll_supported", "rr_env_unroll", "rr_env_unroll_policy", "rr_batch_eval_supported", "rr_env_unroll_eval", "rr_batch_pose_supported", "rr_batch_set_pose", "rr_batch_set_reference_obs", "rr_batch_obs_width", "rr_batch_reference_obs_supported", "rr_batch_set_pose_termination", "rr_batch_pose_termination_supported", "rr_batch_set_body_tracking", "rr_batch_body_tracking_supported", "rr_batch_set_clip_restarts", "rr_batch_clip_restarts_supported", "rr_batch_set_velocity_tracking", "rr_batch_velocity_tracking_supported", "rr_batch_set_clip_library", "rr_batch_clip_library_supported", "rr_wrap_clip_restart", "rr_wrap_clip_library",
+           "rr_batch_destroy", "rr_pipeline_init", "rr_pipeline_step", "rr_env_step", "rr_env_reset", "rr_pipeline_step_to", "rr_env_step_to", "rr_batch_contact_overflow", "rr_batch_bad_states", "rr_batch_unroll_supported", "rr_env_unroll", "rr_env_unroll_policy", "rr_batch_eval_supported", "rr_env_unroll_eval", "rr_batch_pose_supported", "rr_batch_set_pose", "rr_batch_set_reference_obs", "rr_batch_obs_width", "rr_batch_reference_obs_supported", "rr_batch_set_pose_termination", "rr_batch_pose_termination_supported", "rr_batch_set_body_tracking", "rr_batch_body_tracking_supported", "rr_batch_set_clip_restarts", "rr_batch_clip_restarts_supported", "rr_batch_set_velocity_tracking", "rr_batch_velocity_tracking_supported", "rr_batch_set_clip_library", "rr_batch_clip_library_supported", "rr_batch_set_clip_sampling", "rr_batch_clip_sampling_supported", "rr_wrap_clip_restart", "rr_wrap_clip_library", "rr_wrap_clip_sampling",
            "rr_compute_gae", "rr_mlp_forward", "rr_ppo_loss_workspace_bytes", "rr_ppo_loss", "rr_policy_act_workspace_bytes", "rr_policy_act", "rr_policy_sample", "rr_policy_backward_workspace_bytes", "rr_policy_backward", "rr_mlp_silu_backward_workspace_bytes", "rr_mlp_silu_backward", "rr_mlp_value_backward_workspace_bytes", "rr_mlp_policy_backward", "rr_mlp_policy_backward_workspace_bytes", "rr_mlp_value_backward", "rr_mlp_weight_grad_workspace_bytes", "rr_mlp_weight_grad", "rr_mlp_weight_grad_batch_workspace_bytes", "rr_mlp_weight_grad_batch", "rr_obs_moments_workspace_bytes", "rr_obs_moments", "rr_wrap_episode_autoreset", "rr_debug_layout", "rr_batch_set_schedule", "rr_batch_set_env_params", "rr_batch_env_params_supported", "rr_batch_set_profile", "rr_batch_set_ls_repeat_exit", "rr_batch_set_solver_trim", "rr_batch_set_solver_batch", "rr_batch_set_solve_resident", "rr_model_solve_resident_switch", "rr_batch_set_root_slot", "rr_model_root_slot_switch", "rr_batch_set_timing", "rr_batch_kernel_time", "rr_last_error"]
 
 _lib = None
@@ -219,6 +224,10 @@ def lib():
         L.rr_wrap_clip_restart.argtypes = [C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int32)] + \
             [C.c_void_p] * 5 + [C.c_float, C.c_float] + [C.c_void_p] * 4 + [C.c_int32] * 3 + [C.c_void_p]
         L.rr_wrap_clip_library.argtypes = L.rr_wrap_clip_restart.argtypes[:-1] + [C.c_void_p] * 4      # ... clip, bank_clips, clip_lengths, stream
+        L.rr_batch_set_clip_sampling.argtypes = [C.c_void_p, C.POINTER(RRClipSamplingIO)]
+        L.rr_batch_clip_sampling_supported.argtypes = [C.c_void_p, C.c_int32]
+        # ... clip, bank_clips, clip_lengths, num_clips, pose_fail, sampling, stream
+        L.rr_wrap_clip_sampling.argtypes = L.rr_wrap_clip_restart.argtypes[:-1] + [C.c_void_p] * 3 + [C.c_int32, C.c_void_p, C.POINTER(RRClipSamplingIO), C.c_void_p]
         L.rr_batch_set_ls_repeat_exit.argtypes = [C.c_void_p, C.c_int32]
         L.rr_batch_set_solver_trim.argtypes = [C.c_void_p, C.c_int32]
         L.rr_batch_set_solver_batch.argtypes = [C.c_void_p, C.c_int32]
@@ -336,6 +345,7 @@ class Batch:
         self._restart = None        # the tensors of the clip-restart block in force (set_clip_restarts)
         self._vel = None            # the tensors of the velocity-tracking block in force (set_velocity_tracking)
         self._library = None        # the tensors of the clip-library block in force (set_clip_library)
+        self._sampling = None       # the tensors of the clip-sampling block in force (set_clip_sampling)
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream().cuda_stream
         _check(lib().rr_batch_create(model.h, self.N, self.device.index or 0, C.c_void_p(stream), C.byref(self.h)))
@@ -402,7 +412,8 @@ class Batch:
         per block -- the env-io key that decides its presence, the attribute that says whether it stands, its setter, the setter's
         arguments out of the dict (the setters say what each entry is) -- in dependency order: termination, body tracking, velocity tracking
         and clip restarts each need the pose block, the clip library (`clip_library` key) the pose block and, for its bank clips, the
-        clip-restart block, and the library keeps a block while one that needs it stands.  So the blocks absent from the
+        clip-restart block, clip sampling (`clip_sampling` key) the clip-restart block and, for its weights, the library's bank clips,
+        and the library keeps a block while one that needs it stands.  So the blocks absent from the
         dict are cleared last to first, then the present ones are set first to last.  (Clearing the pose block is refused while the
         batch carries reference frames: their launches all carry `track_pose`.)"""
         lead, d, inf = tuple(env["track_pos"].shape[:-1]), self.dims, math.inf
@@ -421,10 +432,14 @@ class Batch:
                   ("restart", "_restart", self.set_clip_restarts, lambda: (env["restart"]["frames"], env["restart"]["slot_in"], env["restart"]["slot_out"],
                                                                            env["restart"].get("end_at_clip_end", False))),
                   ("clip_library", "_library", self.set_clip_library, lambda: (env["clip_library"].get("lengths"), env["clip_library"].get("bank_clips"),
-                                                                               env["clip_library"].get("clip_out"), 1 if len(lead) == 1 else lead[0])))
+                                                                               env["clip_library"].get("clip_out"), 1 if len(lead) == 1 else lead[0])),
+                  ("clip_sampling", "_sampling", self.set_clip_sampling, lambda: (env["clip_sampling"].get("weights"), env["clip_sampling"].get("draws_in"),
+                                                                                 env["clip_sampling"].get("draws_out"), env["clip_sampling"].get("outcomes"),
+                                                                                 env["clip_sampling"].get("seed", 0), 1 if len(lead) == 1 else lead[0])))
         for key, attr, setter, _ in reversed(blocks):
-            # (the clip library is always set afresh: the bank clips of an earlier launch would keep the restart block from being cleared)
-            if (env.get(key) is None or key == "clip_library") and getattr(self, attr) is not None:
+            # (the clip library and clip sampling are always set afresh: the bank clips of an earlier launch would keep the restart block
+            # from being cleared, the weights the bank clips)
+            if (env.get(key) is None or key in ("clip_library", "clip_sampling")) and getattr(self, attr) is not None:
                 setter(None)
         for key, _, setter, args in blocks:
             if env.get(key) is not None:
@@ -657,6 +672,29 @@ class Batch:
         `with_actor` also in the one-launch rollout with the actor inside -- else the refusal's text."""
         return self._refusal(lib().rr_batch_clip_library_supported, int(with_actor))
 
+    def set_clip_sampling(self, weights: Optional[torch.Tensor], draws_in: Optional[torch.Tensor] = None, draws_out: Optional[torch.Tensor] = None,
+                          outcomes: Optional[torch.Tensor] = None, seed: int = 0, num_clips: Optional[int] = None):
+        """The clip-sampling block of this batch's later multi-step launches (C ABI `rr_batch_set_clip_sampling`): `weights` int32 [C],
+        entries 0 .. 65535, the weights a restore draws its bank entry by (None: the next entry), with `draws_in` / `draws_out` int32 [N],
+        each env's restore count before and after the launch; `outcomes` int64 [C, 5], the per-clip outcome counters the launches add to
+        (None: no counting); `seed` the draw's seed; `weights` and `outcomes` both None clears the block.  `num_clips` (given by the
+        env-io path): the length both tables must have.  Needs the clip-restart block, and for `weights` the clip library's bank clips.
+        The launches read the tables' content when they run: rewrite them in place.  The env-io dict of a launch (`clip_sampling` key)
+        sets or clears it by itself.  The batch keeps the tensors alive."""
+        t = None
+        if weights is not None or outcomes is not None:
+            for name, a, tail in (("weights", weights, ()), ("outcomes", outcomes, (5,))):
+                if a is not None and (a.dim() != 1 + len(tail) or tuple(a.shape[1:]) != tail or (num_clips is not None and a.shape[0] != num_clips)):
+                    raise ValueError(f"clip sampling: {name} has shape {tuple(a.shape)}, expected {(('C' if num_clips is None else num_clips),) + tail}")
+            t = RRClipSamplingIO(_ptr(weights, torch.int32), _ptr(draws_in, torch.int32, self.N), _ptr(draws_out, torch.int32, self.N),
+                                 _ptr(outcomes, torch.int64), int(seed) & 0xFFFFFFFF)
+        self._set_block("_sampling", lib().rr_batch_set_clip_sampling, t, (weights, draws_in, draws_out, outcomes))
+
+    def clip_sampling_supported(self, with_actor: bool = False) -> Optional[str]:
+        """None when this batch serves clip sampling at its frame count (C ABI `rr_batch_clip_sampling_supported`) -- with `with_actor`
+        also in the one-launch rollout with the actor inside -- else the refusal's text."""
+        return self._refusal(lib().rr_batch_clip_sampling_supported, int(with_actor))
+
     def _refusal(self, query, *args) -> Optional[str]:
         """None when the `rr_batch_*_supported` function `query` answers 1 for this batch, else the text it left in `rr_last_error`."""
         if _check(query(self.h, *args)) == 1:
@@ -825,6 +863,34 @@ def wrap_clip_library(first, cur, prev_done, prev_steps, done, steps, truncation
                                       _ptr(bank_frames, torch.int32, K * N), _ptr(slot_in, torch.int32, N), _ptr(slot_out, torch.int32, N),
                                       int(K), int(track_len), int(bool(end_at_clip_end)), _ptr(clip, torch.int32, N),
                                       _ptr(bank_clips, torch.int32, K * N), _ptr(lengths, torch.int32), C.c_void_p(stream)))
+
+
+def wrap_clip_sampling(first, cur, prev_done, prev_steps, done, steps, truncation, episode_length: float, action_repeat: float,
+                       cur_frame, bank_frames, slot_in, slot_out, track_len: int, end_at_clip_end: bool, num_clips: int, clip=None, bank_clips=None,
+                       lengths=None, pose_fail=None, weights=None, draws_in=None, draws_out=None, outcomes=None, seed: int = 0):
+    """`wrap_clip_library` with clip sampling (C ABI `rr_wrap_clip_sampling`): `num_clips` C; `pose_fail` float [N] or None, the step's
+    pose-termination codes; `weights` int32 [C] or None with `draws_in` / `draws_out` int32 [N]; `outcomes` int64 [C, 5] or None, added
+    to in place; `seed` the draw's seed."""
+    n = len(cur)
+    N = done.numel()
+    K = bank_frames.shape[0]
+    for t in list(first) + list(cur) + [prev_done, prev_steps, done, steps, truncation]:
+        _ptr(t)
+    for f, c in zip(first, cur):
+        if tuple(f.shape) != (K,) + tuple(c.shape):
+            raise ValueError("bank / current state shapes differ")
+    F = (C.c_void_p * n)(*[t.data_ptr() for t in first])
+    Cu = (C.c_void_p * n)(*[t.data_ptr() for t in cur])
+    W = (C.c_int32 * n)(*[t.numel() // N for t in cur])
+    stream = torch.cuda.current_stream(done.device).cuda_stream
+    block = RRClipSamplingIO(_ptr(weights, torch.int32, int(num_clips)), _ptr(draws_in, torch.int32, N), _ptr(draws_out, torch.int32, N),
+                             _ptr(outcomes, torch.int64, 5 * int(num_clips)), int(seed) & 0xFFFFFFFF)
+    _check(lib().rr_wrap_clip_sampling(N, n, F, Cu, W, prev_done.data_ptr(), prev_steps.data_ptr(), done.data_ptr(), steps.data_ptr(),
+                                       truncation.data_ptr(), float(episode_length), float(action_repeat), _ptr(cur_frame, torch.int32, N),
+                                       _ptr(bank_frames, torch.int32, K * N), _ptr(slot_in, torch.int32, N), _ptr(slot_out, torch.int32, N),
+                                       int(K), int(track_len), int(bool(end_at_clip_end)), _ptr(clip, torch.int32, N),
+                                       _ptr(bank_clips, torch.int32, K * N), _ptr(lengths, torch.int32), int(num_clips),
+                                       _ptr(pose_fail, numel=N), C.byref(block), C.c_void_p(stream)))
 
 
 def _mlp_net(weights, biases, in_dim=None):

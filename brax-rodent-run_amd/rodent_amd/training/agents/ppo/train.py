@@ -78,6 +78,7 @@ def train(
     max_training_steps: Optional[int] = None,
     timing_fn: Optional[Callable] = None,
     return_training_state: bool = False,
+    clip_weight_fn: Optional[Callable] = None,
 ):
     """PPO training.  Returns (make_policy, params=(normalizer_params, policy_params), metrics).
 
@@ -86,6 +87,12 @@ def train(
     `global_advantage_normalization` (extension, default off = the reference's behaviour: advantages are normalised over
     the rank-local minibatch): normalise with the mean / variance of the GLOBAL minibatch instead, one
     3-float all-reduce {n, sum a, sum a^2} per minibatch (the north star's "advantage-normalisation all-reduce").
+    `clip_weight_fn` (extension; an env built with `clip_outcomes=True`): after every training step the training envs' per-clip outcome
+    counters are read and cleared, summed over the sub-batches and over the ranks (one int64 all-reduce), and reported as
+    `training/clip_fail_rate` ((pose failures + env dones) / ended episodes), `training/clip_truncated_share` and, with at most 16
+    clips, `training/clip_fail_rate_clip{c}`.  The function is called with that step's int64 [C, 5] table on every rank; a result
+    other than None goes to `set_clip_weights` of every training batch (`envs.rodent.FailureWeights` is one such function).  The eval
+    env keeps its uniform weights.
     """
     assert batch_size * num_minibatches % num_envs == 0
     xt = time.time()
@@ -307,6 +314,31 @@ def train(
     if getattr(env, "bad_state_max", None) and hasattr(env, "bad_states"):
         bad_envs = [sub["env"] for sub in sub_rollout.subs] if sub_rollout is not None else [env]
     bad = {"total": 0, "reported": 0, "warned": False}
+    # Envs built with the outcome counters (Rodent(clip_outcomes=True)): read and cleared after the closing synchronisation, like the two
+    # counters above.  The env carries the setting; off: no metric, and `clip_weight_fn` has nothing to be called with.
+    outcome_envs = []
+    if (getattr(env, "clip_sampling", None) or {}).get("outcomes") is not None:
+        outcome_envs = [sub["env"] for sub in sub_rollout.subs] if sub_rollout is not None else [env]
+    elif clip_weight_fn is not None:
+        raise ValueError("ppo.train: clip_weight_fn needs an environment built with clip_outcomes=True (it is called with the outcome table)")
+
+    def clip_outcome_metrics(out):
+        table = sum(e.clip_outcomes(clear=True) for e in outcome_envs)      # int64 [C, 5]
+        if process_count > 1:
+            t = torch.from_numpy(np.ascontiguousarray(table)).to(device)
+            table = D.all_reduce_sum_(t).cpu().numpy()
+        ended = table[:, 0]
+        rate = lambda num, den: float(num) / float(den) if den else 0.0
+        out["training/clip_fail_rate"] = rate(table[:, 1].sum() + table[:, 2].sum(), ended.sum())
+        out["training/clip_truncated_share"] = rate(table[:, 3].sum(), ended.sum())
+        if table.shape[0] <= 16:
+            for c in range(table.shape[0]):
+                out[f"training/clip_fail_rate_clip{c}"] = rate(table[c, 1] + table[c, 2], ended[c])
+        if clip_weight_fn is not None:
+            w = clip_weight_fn(table)
+            if w is not None:
+                for e in outcome_envs:
+                    e.set_clip_weights(w)
 
     def training_step():
         nonlocal env_state, normalizer_params
@@ -371,6 +403,8 @@ def train(
                 warnings.warn(f"ppo.train: {bad['total']} (env, step) events so far in which an env's qpos / qvel was non-finite or beyond "
                               f"bad_state_max = {env.bad_state_max:g}; those episodes were ended and restored "
                               "(training/bad_state_resets counts them)", RuntimeWarning, stacklevel=2)
+        if outcome_envs:
+            clip_outcome_metrics(out)
         return out
 
     metrics = {}

@@ -84,6 +84,16 @@ def main():
                     "of comparing it with the clamped last row (the clip must be longer than every start frame: the synthetic line has 250 frames)")
     ap.add_argument("--restart-across-clips", action="store_true", help="with --clip-restarts and several clips: every start state of the bank has a "
                     "clip of its own, so a restarted episode may move to another clip (Rodent(restart_across_clips=True))")
+    ap.add_argument("--clip-outcomes", action="store_true", help="with --clip-restarts and several clips: count per clip the wrapped steps, the ended "
+                    "episodes and why they ended (Rodent(clip_outcomes=True)); reported as training/clip_fail_rate, training/clip_truncated_share "
+                    "and, up to 16 clips, training/clip_fail_rate_clip{c}")
+    ap.add_argument("--weighted-restarts", action="store_true", help="with --restart-across-clips: a restarted episode draws its start state with "
+                    "probability proportional to its clip's weight, and the weights follow the clips' failure rates "
+                    "(Rodent(restart_sampling='weighted'), ppo.train(clip_weight_fn=FailureWeights(...)); implies --clip-outcomes)")
+    ap.add_argument("--weight-floor", type=float, default=0.1, metavar="F", help="with --weighted-restarts: the weight of a clip that never fails, "
+                    "relative to one that always does (FailureWeights(floor=F); untuned default)")
+    ap.add_argument("--weight-decay", type=float, default=0.9, metavar="D", help="with --weighted-restarts: the decay per training step of the "
+                    "failure and episode counts the rates are formed from (FailureWeights(decay=D); untuned default)")
     ap.add_argument("--clip-lengths", type=int, nargs="+", default=None, metavar="L", help="with --track-pose and --synthetic-clips K: the frames of each "
                     "synthetic line, K ints in 2 .. 250 (Rodent(clip_lengths=...)): rewards, observation and --end-at-clip-end stop at the clip's own "
                     "last frame.  Clips of unequal length in a --clip file get theirs from the file (preprocessing.load_reference_clips)")
@@ -139,6 +149,10 @@ def main():
         ap.error("--restart-across-clips / --clip-lengths: they serve envs that track the reference pose; add --track-pose")
     if args.restart_across_clips and args.clip_restarts < 1:
         ap.error("--restart-across-clips: needs --clip-restarts K >= 1")
+    if args.weighted_restarts and not args.restart_across_clips:
+        ap.error("--weighted-restarts: needs --restart-across-clips (the weights are those of the bank entries' clips)")
+    if args.clip_outcomes and args.clip_restarts < 1:
+        ap.error("--clip-outcomes: needs --clip-restarts K >= 1")
     clip_lengths = args.clip_lengths
     clips = None                                     # the loaded ReferenceClip(s), [C, T, ...] fields; None for a .npy track or the synthetic line
     if args.clip and os.path.exists(args.clip) and not args.clip.endswith(".npy"):
@@ -205,6 +219,7 @@ def main():
         max_quat_error=args.max_quat_error, max_joint_error=args.max_joint_error, clip_restarts=args.clip_restarts,
         restart_frame_range=None if args.restart_frames is None else tuple(args.restart_frames), end_at_clip_end=args.end_at_clip_end,
         clip_lengths=None if clip_lengths is None else np.asarray(clip_lengths, dtype=np.int32), restart_across_clips=args.restart_across_clips,
+        restart_sampling="weighted" if args.weighted_restarts else None, clip_outcomes=args.clip_outcomes or args.weighted_restarts,
         **pose)     # a clip too short for --end-at-clip-end is refused here with the reason (ValueError)
 
     train_fn = functools.partial(
@@ -214,6 +229,7 @@ def main():
         learning_rate=config["learning_rate"], entropy_cost=1e-3, num_envs=config["num_envs"],
         batch_size=config["batch_size"], seed=0, max_training_steps=args.max_training_steps,
         randomization_fn=domain_randomize if args.randomize else None,
+        clip_weight_fn=envs.rodent.FailureWeights(floor=args.weight_floor, decay=args.weight_decay) if args.weighted_restarts else None,
         network_factory=functools.partial(networks.make_ppo_networks, policy_hidden_layer_sizes=(args.policy_width,) * args.policy_depth))
 
     run_id = uuid.uuid4()

@@ -459,6 +459,44 @@ typedef struct rr_clip_library_io {
 int rr_batch_set_clip_library(rr_batch* b, const rr_clip_library_io* lib);
 int rr_batch_clip_library_supported(const rr_batch* b, int32_t with_actor);
 
+/* Clip sampling: per-clip outcome counters, and restores that draw their bank entry by per-clip weights.  The block is set on the BATCH,
+ * next to the clip-restart block it needs, and read by every later rr_env_unroll / rr_env_unroll_policy of it until it is replaced or
+ * cleared (NULL; a batch starts without one); a launch takes the pointers as they are when it is issued, and reads the tables' CONTENT
+ * when it runs, so weights rewritten in place reach the next launch (and a replayed graph).  Integers only: the composed wrappers, the
+ * per-step wrapper below and the multi-step launches agree bit for bit.  With done_env, over, done as in rr_clip_restart_io's rule and c
+ * the clip the step was made on (before any restore; 0 without clip ids):
+ * outcomes [num_clips][5] int64, added to and never cleared by a launch:
+ *   col 4 += 1 for every wrapped step made on c;
+ *   done:  col 0 += 1, and exactly one of
+ *          col 1 += 1   the step's pose-termination code is nonzero,
+ *          col 2 += 1   else done_env (unhealthy, bad state),
+ *          col 3 += 1   else (over alone: a truncation by episode_length or the clip's end),
+ * so columns 1 + 2 + 3 = column 0.  A launch adds an episode segment's steps in one atomic add at the segment's end (the episode's end
+ * or the launch's last step); totals after whole launches do not depend on how the steps were split into launches.  NULL: no counting.
+ * clip_weights [num_clips] int32, entries 0 .. 65535 (the low 16 bits are read), needs a clip-library block with bank_clips:
+ *   q_k = clip_weights[clamp(bank_clips[k][env], 0, num_clips - 1)], k = 0 .. num_slots - 1;   S = sum q_k;
+ *   h = fmix32(fmix32(seed ^ (uint32(env) * 0x9E3779B1)) + uint32(n)), fmix32 = MurmurHash3's finaliser (h ^= h >> 16; h *= 0x85EBCA6B;
+ *       h ^= h >> 13; h *= 0xC2B2AE35; h ^= h >> 16, mod 2^32), n = the env's restore count;
+ *   r = (uint64(h) * S) >> 32;   done:  slot' = the smallest k with q_0 + .. + q_k > r;   S == 0:  slot' = (slot + 1) mod num_slots.
+ * A slot whose clip has weight 0 is never drawn while S > 0; slot' == slot is allowed.  State, observation, frame and clip then come
+ * from entry slot' as before.  n = draws_in[env] at the launch's first step, grows by one at every restore (drawn or cyclic) and goes to
+ * draws_out[env] after the last step, as slot_out does (the two may not alias).  NULL: the cyclic rule.
+ * rr_batch_set_clip_sampling: no clip-restart block on the batch, clip_weights and outcomes both NULL, clip_weights without a
+ * clip-library block with bank_clips or without draws_in / draws_out: RR_EINVAL; RR_EUNSUPPORTED with the reason wherever pose tracking
+ * is unsupported.  While the block is set, rr_batch_set_clip_restarts(b, NULL) is RR_EINVAL, and with clip_weights so is clearing
+ * bank_clips (rr_batch_set_clip_library): clear this block first.  No new instance: the launches run the restart instances they ran;
+ * single steps (rr_env_step(_to)) ignore the block: rr_wrap_clip_sampling below.
+ * rr_batch_clip_sampling_supported(b, with_actor): 1 / 0 as for the other blocks; with 0 rr_last_error holds the reason. */
+typedef struct rr_clip_sampling_io {
+  const int32_t* clip_weights;  /* [C], 0 .. 65535, or NULL: the cyclic rule */
+  const int32_t* draws_in;      /* [N] restores of each env so far; required with clip_weights */
+  int32_t* draws_out;           /* [N] out; required with clip_weights */
+  int64_t* outcomes;            /* [C][5] or NULL: no counting */
+  uint32_t seed;
+} rr_clip_sampling_io;
+int rr_batch_set_clip_sampling(rr_batch* b, const rr_clip_sampling_io* sampling);
+int rr_batch_clip_sampling_supported(const rr_batch* b, int32_t with_actor);
+
 /* Generalised advantage estimation of one PPO minibatch, the reverse scan of brax.training.agents.ppo.losses.compute_gae
  * [UP; SURVEY.md Appendix E], one thread per trajectory.  All arrays time-major [T][B] device float32; bootstrap [B];
  * outputs vs [T][B] and advantages [T][B].  `stream` is a hipStream_t (NULL = default stream). */
@@ -636,6 +674,16 @@ int rr_wrap_clip_library(int32_t num_envs, int32_t narr, const float* const* fir
                          float episode_length, float action_repeat, int32_t* cur_frame, const int32_t* bank_frames,
                          const int32_t* slot_in, int32_t* slot_out, int32_t num_slots, int32_t track_len, int32_t end_at_clip_end,
                          int32_t* clip, const int32_t* bank_clips, const int32_t* clip_lengths, void* stream);
+/* The same with clip sampling (rr_clip_sampling_io's rule on one env step; the entries above are unchanged): rr_wrap_clip_library's
+ * arguments, then num_clips (ids in clip and bank_clips are clamped into 0 .. num_clips - 1), pose_fail [N] or NULL, the
+ * pose-termination codes of the step (what rr_pose_term_io's fail received), and the block: the step's outcomes are added at once, and
+ * where done the slot is drawn with n = draws_in[env]; draws_out[env] receives n, or n + 1 where done. */
+int rr_wrap_clip_sampling(int32_t num_envs, int32_t narr, const float* const* first, float* const* cur, const int32_t* widths,
+                          const float* prev_done, const float* prev_steps, float* done, float* steps, float* truncation,
+                          float episode_length, float action_repeat, int32_t* cur_frame, const int32_t* bank_frames,
+                          const int32_t* slot_in, int32_t* slot_out, int32_t num_slots, int32_t track_len, int32_t end_at_clip_end,
+                          int32_t* clip, const int32_t* bank_clips, const int32_t* clip_lengths, int32_t num_clips,
+                          const float* pose_fail, const rr_clip_sampling_io* sampling, void* stream);
 
 /* Scheduling of the environments on the GPU (results are unaffected: environments are independent).  `env_map` (device,
  * [N] int32, a permutation of 0..N-1, or NULL = identity): workgroup w steps environment env_map[w]; `cost_cycles` (device,

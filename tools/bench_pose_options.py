@@ -13,15 +13,17 @@ alternating in one process on one GPU.  No gate: it reports.
                      `clip_restarts` 1 | with 8
   --option library   that `clip_restarts` 8 env on three copies of the clip ([3, T, ...] arrays) | the same with `clip_lengths`
                      (T, 2T/3, T/3) and `restart_across_clips`
+  --option sampling  that `clip_restarts` 8 env on three copies of the clip with `restart_across_clips` | the same with
+                     `restart_sampling="weighted"` (weights 1, 2, 5) and `clip_outcomes`
 
 All envs: rodent_optimized.xml, CG 8/8, n_frames 10, --num-envs envs through Episode(150) + AutoReset in multi-step launches, tracking a
 synthetic reference pose (identity quaternion, qpos0's joints) with the default weights and scales.  Default: random actions through
-`rr_env_unroll`, --unroll env steps per launch -- the workload of bench.py config 2.  --actor (poseterm, body, velocity, restart, library): the one-launch
+`rr_env_unroll`, --unroll env steps per launch -- the workload of bench.py config 2.  --actor (poseterm, body, velocity, restart, library, sampling): the one-launch
 rollout with the actor inside (`rr_env_unroll_policy`, a 4 x 32 policy, one segment of --unroll steps per launch).  After two warm-up
 launches per side, each repeat times --launches launches per side, in the order above, with a host clock around a device synchronise;
 the medians, the per-repeat values, the ranges and the ratios against the first side are printed as one JSON line.
 
-usage: python tools/bench_pose_options.py --option {pose,refobs,poseterm,body,velocity,restart,library} [--actor] [--frames 5] [--num-envs 2048]
+usage: python tools/bench_pose_options.py --option {pose,refobs,poseterm,body,velocity,restart,library,sampling} [--actor] [--frames 5] [--num-envs 2048]
                                           [--unroll 50] [--launches 4] [--repeats 7] [--out FILE]"""
 import argparse
 import json
@@ -62,7 +64,11 @@ def options(frames: int, bodies: Callable, velocity: dict, T: int = 250) -> dict
     probe while that side is being built); `velocity`: the three velocity keywords; `T`: the clip's frames."""
     body = dict(track_bodies=bodies, end_effector_ids=END_EFFECTORS)
     k8 = dict(max_pos_error=1e9, clip_restarts=8)
+    across = dict(k8, restart_across_clips=True)
     return {
+        "sampling": Option((("across", across), ("sampling", dict(across, restart_sampling="weighted", clip_outcomes=True))), True, True,
+                           lambda st: _alive(st) and int(st.info["restart_slot"].max()) <= 7 and int(st.info["restart_draws"].max()) >= 1,
+                           clips=3),
         "library": Option((("k8", k8), ("library", dict(k8, clip_lengths=(T, 2 * T // 3, T // 3), restart_across_clips=True))), True, True,
                           lambda st: _alive(st) and int(st.info["restart_slot"].max()) <= 7 and 0 <= int(st.info["clip"].min()) and int(st.info["clip"].max()) <= 2,
                           clips=3),
@@ -83,7 +89,7 @@ def options(frames: int, bodies: Callable, velocity: dict, T: int = 250) -> dict
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--option", required=True, choices=("pose", "refobs", "poseterm", "body", "velocity", "restart", "library"))
+    ap.add_argument("--option", required=True, choices=("pose", "refobs", "poseterm", "body", "velocity", "restart", "library", "sampling"))
     ap.add_argument("--actor", action="store_true")
     ap.add_argument("--frames", type=int, default=5)
     ap.add_argument("--num-envs", type=int, default=2048)
@@ -106,7 +112,7 @@ def main():
     velocity = dict(track_velocity=qvel[:, :3], track_angular_velocity=qvel[:, 3:6], track_joint_velocity=qvel[:, 6:])
     opt = options(args.frames, lambda env: preprocessing.extract_features(env, qpos).body_positions, velocity, T)[args.option]
     if args.actor and not opt.actor:
-        ap.error(f"--actor: --option {args.option} has no such mode (poseterm, body, velocity, restart and library have)")
+        ap.error(f"--actor: --option {args.option} has no such mode (poseterm, body, velocity, restart, library and sampling have)")
     if opt.clips:      # the same clip `clips` times over
         track, quat, joints = (np.stack([np.asarray(a)] * opt.clips) for a in (track, quat, joints))
     dev = torch.device("cuda:0")
@@ -122,6 +128,8 @@ def main():
         if opt.pose_base or name != first:
             kw.update(track_quat=quat, track_joints=joints)
         env = envs.get_environment("rodent", track_pos=track, num_envs=N, xml_path="rodent_optimized.xml", iterations=8, ls_iterations=8, device=dev, **kw)
+        if env.clip_weights() is not None:      # unequal weights, so the draw's scan and search do work
+            env.set_clip_weights([1, 2, 5])
         wenv = wrappers.wrap(env, episode_length=150, action_repeat=1)
         gen = torch.Generator(device=dev)
         gen.manual_seed(1234)
@@ -172,6 +180,10 @@ def main():
         res["per_repeat_time_ratio" if len(others) == 1 else name + "_per_repeat_time_ratio"] = [
             round(float(a / b), 5) for a, b in zip(sides[name]["ms"], sides[first]["ms"])]
         assert opt.check(sides[name]["state"]), (args.option, name)
+    if args.option == "sampling":      # the counters of the timed side: every wrapped step of every launch, and each end by exactly one cause
+        table = sides["sampling"]["env"].clip_outcomes()
+        assert table[:, 4].sum() == N * U * (2 + args.repeats * args.launches) and (table[:, 1:4].sum(1) == table[:, 0]).all(), table
+        res["outcomes"] = table.tolist()
     if opt.identical and (not args.actor or opt.identical_with_actor):
         key, name = opt.identical
         res[key] = bool(torch.equal(sides[name]["state"].pipeline_state.qpos, sides[first]["state"].pipeline_state.qpos))
