@@ -414,6 +414,7 @@ struct rr_batch {
   bool has_clip_library() const { return lib.clip_lengths || lib.bank_clips; }
   rr_clip_sampling_io samp = {};        // clip sampling of the multi-step launches (rr_batch_set_clip_sampling); clip_weights and outcomes null: off; set only with a clip-restart block
   bool has_clip_sampling() const { return samp.clip_weights || samp.outcomes; }
+  rr_reference_restart_io refr = {};    // reference restarts of the multi-step launches (rr_batch_set_reference_restart); draws_in null: off; set only with a clip-restart block
   bool has_env_params() const { return env_dof_f || env_act_f || env_con_f; }
 };
 
@@ -747,6 +748,13 @@ static int launch(rr_batch* b, const Launch& L) {
     }
     io.draws_in = b->samp.draws_in; io.draws_out = b->samp.draws_out;
     if (io.draws_in && io.draws_in == io.draws_out) return fail(RR_EINVAL, "launch: clip sampling: draws_out may not alias draws_in");
+  }
+  if (restart && b->refr.draws_in) {      // only the RESTART instances read these; single steps ignore the block
+    if (b->refr.across_clips && io.clip && !io.clip_out) return fail(RR_EINVAL, "launch: reference restarts: across_clips needs the clip library's bank_clips and clip_out (the clip an env moves to goes out there)");
+    if (io.clip && io.num_clips > 65536) return fail(RR_EINVAL, "launch: reference restarts: num_clips must be <= 65536 (the weights' sum stays within 32 bits)");
+    io.rref_on = 1; io.rref_seed = b->refr.seed; io.rref_lo = b->refr.frame_lo; io.rref_hi = b->refr.frame_hi;
+    io.rref_across = b->refr.across_clips ? 1 : 0; io.rref_noise = b->refr.noise_scale;
+    io.clip_weights = b->refr.clip_weights; io.draws_in = b->refr.draws_in; io.draws_out = b->refr.draws_out;
   }
   if (pterm) { io.pose_fail = b->pterm.fail; io.pose_max_pos = b->pterm.max_pos; io.pose_max_quat = b->pterm.max_quat; io.pose_max_joint = b->pterm.max_joint; }
   if (pose) {
@@ -1757,6 +1765,7 @@ extern "C" int rr_batch_clip_restarts_supported(const rr_batch* b, int32_t with_
 extern "C" int rr_batch_set_clip_restarts(rr_batch* b, const rr_clip_restart_io* r) {
   if (!b) return fail(RR_EINVAL, "rr_batch_set_clip_restarts: null batch");
   if (!r) {
+    if (b->refr.draws_in) return fail(RR_EINVAL, "rr_batch_set_clip_restarts: the batch carries a reference-restart block (rr_batch_set_reference_restart), which replaces this block's restores: clear it first");
     if (b->has_clip_sampling()) return fail(RR_EINVAL, "rr_batch_set_clip_restarts: the batch carries a clip-sampling block (rr_batch_set_clip_sampling), which counts and draws this block's restores: clear it first");
     if (b->lib.bank_clips) return fail(RR_EINVAL, "rr_batch_set_clip_restarts: the batch carries a clip-library block with bank_clips (rr_batch_set_clip_library), the clips of this block's entries: clear it first");
     b->restart = rr_clip_restart_io{};
@@ -1801,6 +1810,23 @@ extern "C" int rr_batch_set_clip_sampling(rr_batch* b, const rr_clip_sampling_io
   if (s->clip_weights && (!s->draws_in || !s->draws_out)) return fail(RR_EINVAL, "rr_batch_set_clip_sampling: clip_weights needs draws_in and draws_out");
   if (s->draws_in && s->draws_in == s->draws_out) return fail(RR_EINVAL, "rr_batch_set_clip_sampling: draws_out may not alias draws_in");
   b->samp = *s;
+  return RR_OK;
+}
+extern "C" int rr_batch_reference_restart_supported(const rr_batch* b, int32_t with_actor) {
+  if (!b) return fail(RR_EINVAL, "rr_batch_reference_restart_supported: null batch");
+  return supported("rr_batch_reference_restart_supported", pose_option_limit(b, F_UNROLL, b->ref_frames, with_actor != 0));
+}
+extern "C" int rr_batch_set_reference_restart(rr_batch* b, const rr_reference_restart_io* r) {
+  if (!b) return fail(RR_EINVAL, "rr_batch_set_reference_restart: null batch");
+  if (!r) { b->refr = rr_reference_restart_io{}; return RR_OK; }
+  if (const char* why = pose_option_limit(b, F_UNROLL, b->ref_frames, false)) return fail(RR_EUNSUPPORTED, std::string("rr_batch_set_reference_restart: ") + why);
+  if (!b->pose.track_pose) return fail(RR_EINVAL, "rr_batch_set_reference_restart: needs a pose block (rr_batch_set_pose) first: the start state is built from the clip's pose rows");
+  if (!b->restart.frames) return fail(RR_EINVAL, "rr_batch_set_reference_restart: needs a clip-restart block (rr_batch_set_clip_restarts) first: it replaces that block's restores");
+  if (!r->draws_in || !r->draws_out) return fail(RR_EINVAL, "rr_batch_set_reference_restart: null draws_in or draws_out");
+  if (r->draws_in == r->draws_out) return fail(RR_EINVAL, "rr_batch_set_reference_restart: draws_out may not alias draws_in");
+  if (r->frame_lo < 0 || r->frame_hi <= r->frame_lo) return fail(RR_EINVAL, "rr_batch_set_reference_restart: needs 0 <= frame_lo < frame_hi");
+  if (!(r->noise_scale >= 0.0f) || !std::isfinite(r->noise_scale)) return fail(RR_EINVAL, "rr_batch_set_reference_restart: noise_scale must be finite and >= 0");
+  b->refr = *r;
   return RR_OK;
 }
 extern "C" int32_t rr_batch_obs_width(const rr_batch* b) {

@@ -366,6 +366,22 @@ struct RRIO {
   int* draws_out;              // [N]
   long long* outcomes;         // [num_clips][5]
   unsigned sample_seed;
+  // REFERENCE RESTARTS (RESTART instances, rr_restart_kernel; no other instance reads these; rr_batch_set_reference_restart).  rref_on
+  // != 0: a restore reads no bank entry.  With n the env's restore count before the restore (draws_in / draws_out as above) and
+  //   base = fmix32(fmix32(rref_seed ^ (uint32(env) * 0x9E3779B1)) + n);  h(p, i) = fmix32(base ^ (((p << 16) | i) * 0x9E3779B1))
+  // it draws, wave-uniform and in integers,
+  //   clip  c = rref_across ? (clip_weights with S > 0 ? the smallest c with q_0 + .. + q_c > (h(1, 0) * S) >> 32, the scan in chunks of 64
+  //             : (h(1, 0) * num_clips) >> 32) : the clip the env is on
+  //   frame d = rref_lo + ((h(2, 0) * (rref_hi - rref_lo)) >> 32);  f = clip_len ? d mod (L_c - 1) : d;  rows at clamp(f, 0, L_c - 1)
+  // builds qpos = [track_pos[c][f], track_pose[c][f]] + rref_noise * s(h(3, i)), qvel = (track_vel ? track_vel[c][f] : 0) + rref_noise *
+  // s(h(4, i)), s(h) = (h >> 8) * 2^-23 - 1 (exact; then one rounded product and one rounded sum), zeroes act and the warm start, sets
+  // cur_frame = f and clip = c, and the launch runs ONE forward-only pass of the loop body on that state (mode 2: no substep, the reset
+  // epilogue) before the next step, which writes the observation where the ended step's stood.  The bank's arrays are not read; the
+  // slot advances cyclically and means nothing.  Fetched by narrow loads where they are used.
+  unsigned rref_seed;
+  int rref_on, rref_lo, rref_hi, rref_across;
+  float rref_noise;
+  int rref_pad;
 };
 
 // ------------------------------------------------------------------------------------------ small math
@@ -2697,7 +2713,8 @@ static_assert(offsetof(RRIO, track_vel) + 2 * sizeof(float*) == offsetof(RRIO, v
 static_assert(offsetof(RRIO, vel_joint_k) + sizeof(float) == offsetof(RRIO, clip_len) && offsetof(RRIO, clip_len) % 8 == 0, "the clip-library members follow the velocity-tracking members without padding");
 static_assert(offsetof(RRIO, clip_len) + 3 * sizeof(int*) == offsetof(RRIO, clip_weights), "the clip-sampling members follow the three clip-library pointers without padding");
 static_assert(offsetof(RRIO, clip_weights) + 4 * sizeof(int*) == offsetof(RRIO, sample_seed), "the seed follows the four clip-sampling pointers without padding");
-static_assert(offsetof(RRIO, sample_seed) + 2 * sizeof(unsigned) == sizeof(RRIO), "the seed closes RRIO (one word of tail padding: the struct is 8-byte aligned)");
+static_assert(offsetof(RRIO, sample_seed) + sizeof(unsigned) == offsetof(RRIO, rref_seed), "the reference-restart members follow the seed without padding (rref_seed takes the word that was tail padding)");
+static_assert(offsetof(RRIO, rref_pad) + sizeof(int) == sizeof(RRIO) && offsetof(RRIO, rref_seed) + 7 * sizeof(int) == sizeof(RRIO), "the reference-restart members close RRIO without padding");
 // ... and so are the model tables outside the solver's loops: RRTables is re-read at the head of each phase that indexes a table
 // (narrow scalar loads next to an existing hand-off; the unused members' loads are dead), so no table pointer is held across the
 // substep.  The loops' own tables are the exception (RRLoopTables, taken once from the parameter).
@@ -2790,6 +2807,46 @@ static __device__ __forceinline__ int rr_weighted_slot(const int* cw, const int*
   const unsigned long long m = __ballot(p > r);
   const int k = (int)__builtin_ctzll(m | (1ull << (K - 1)));      // (the guard bit is never the lowest: slot K - 1 has prefix S > r)
   return __builtin_amdgcn_readfirstlane(k);
+}
+
+// The hashes of a reference restart (RRIO, REFERENCE RESTARTS): `base` per (seed, env, restore count), one hash per purpose p and element i
+static __device__ __host__ __forceinline__ unsigned rr_ref_base(unsigned seed, int env, unsigned n) { return rr_fmix32(rr_fmix32(seed ^ ((unsigned)env * 0x9E3779B1u)) + n); }
+static __device__ __host__ __forceinline__ unsigned rr_ref_hash(unsigned base, unsigned p, unsigned i) { return rr_fmix32(base ^ (((p << 16) | i) * 0x9E3779B1u)); }
+// s(h) = (h >> 8) * 2^-23 - 1 in [-1, 1): both operations exact in float32
+static __device__ __host__ __forceinline__ float rr_ref_unit(unsigned h) { return (float)(h >> 8) * 0x1p-23f - 1.0f; }
+
+// The clip a reference restart draws over all `nc` clips with the hash `h` (RRIO, REFERENCE RESTARTS).  Called by the whole wave with
+// wave-uniform arguments.  With a weight table `cw` of sum S > 0: the smallest c with q_0 + .. + q_c > r = (h * S) >> 32, found chunk of
+// 64 clips by chunk -- lane l holds q_(c0 + l), an inclusive wave scan on top of the chunks before, a ballot of prefix > r.  r < S, so
+// some chunk has a set bit; a clip of weight 0 repeats its predecessor's prefix and is never the lowest one.  Otherwise uniform.
+// The host keeps nc <= 65536, so S stays within 32 bits.
+static __device__ __forceinline__ int rr_ref_clip(const int* cw, int nc, unsigned h, int lane) {
+  if (cw) {
+    unsigned S = 0;
+    for (int c0 = 0; c0 < nc; c0 += RR_LANES) {
+      unsigned p = c0 + lane < nc ? ((unsigned)cw[c0 + lane] & 0xFFFFu) : 0u;
+#pragma unroll
+      for (int d = 1; d < RR_LANES; d <<= 1) { const unsigned t = __shfl_up(p, d, RR_LANES); if (lane >= d) p += t; }
+      S += (unsigned)__builtin_amdgcn_readlane((int)p, RR_LANES - 1);
+    }
+    if (S != 0) {
+      const unsigned r = (unsigned)(((unsigned long long)h * (unsigned long long)S) >> 32);
+      unsigned before = 0;
+      for (int c0 = 0; c0 < nc; c0 += RR_LANES) {
+        unsigned p = c0 + lane < nc ? ((unsigned)cw[c0 + lane] & 0xFFFFu) : 0u;
+#pragma unroll
+        for (int d = 1; d < RR_LANES; d <<= 1) { const unsigned t = __shfl_up(p, d, RR_LANES); if (lane >= d) p += t; }
+        const unsigned long long m = __ballot(before + p > r);
+        if (m != 0) {
+          const int c = c0 + (int)__builtin_ctzll(m);
+          return __builtin_amdgcn_readfirstlane(c > nc - 1 ? nc - 1 : c);
+        }
+        before += (unsigned)__builtin_amdgcn_readlane((int)p, RR_LANES - 1);
+      }
+      return nc - 1;      // not reached (r < S)
+    }
+  }
+  return (int)(((unsigned long long)h * (unsigned long long)(unsigned)nc) >> 32);
 }
 
 // RAND instances: the tables with the three randomisable ones advanced to environment `env`'s rows.  `env` is wave-uniform, the

@@ -46,6 +46,7 @@
   int u_clip = 0;                // RESTART: the clip the env is on, clamped; a restore may move it (RRIO, CLIP LIBRARY); 0 without clip ids
   unsigned u_draws = 0;          // RESTART: restores of the env so far, the counter of the weighted draw's hash (RRIO, CLIP SAMPLING)
   int u_seg = 0;                 // RESTART: wrapped steps of the running episode segment not yet added to the outcome table
+  int u_ref = 0;                 // RESTART: a reference restart has staged its start state in LDS, and the next trip of the loop is its forward pass (RRIO, REFERENCE RESTARTS)
   unsigned u_work = 0;
   int u_overflow = 0;            // DYN: some step of this launch dropped pairs (RRIO::cost bit 31 of a multi-step launch)
   if (UNROLL) {
@@ -68,12 +69,22 @@
   }
   int niter = 0;
   float xq1[4] = {1, 0, 0, 0};   // xquat of body 1 at the last forward pass (obs: xmat[1])
+ // A TRIP OF THIS LOOP MAY REPEAT AT THE SAME `ut` (RESTART instances only; RRIO, REFERENCE RESTARTS): a step whose episode ends with a
+ // reference restart sets u_ref and takes `ut` back by one at its end, and the next trip (`refpass` below) is the restore's forward pass at
+ // that step's index -- mode 2, no actor, no state load, no bad-state check, no wrappers.  Whatever a trip does ONCE PER ENV STEP (counters,
+ // pacing, trajectory rows, step bookkeeping) must therefore stand where `refpass` does not reach, i.e. in the wrapper block's `else` arm
+ // or behind `!refpass`; today only u_work (the cost report, which counts the pass as the work it is) and the harmless rewrite of the
+ // segment's opening row and of the final state see both trips.
  for (int ut = 0; ut < nsteps; ++ut) {
   if (UNROLL) { lane = opaque(lane); w.lane = lane; asm volatile("" : "+s"(env)); if (RAND) w.renv = env; io = load_io(); }
+  // REFERENCE RESTARTS: this trip is the forward pass of a restore -- the loop body in mode 2 (no substep, no actor, no wrappers, the
+  // reset epilogue) on the state the ended step left in LDS, at the step's own index `ut`, so the observation lands where the step's stood
+  const bool refpass = RESTART && u_ref != 0;
+  if (RESTART) mode = refpass ? 2 : load_io_member<int>(offsetof(RRIO, mode));
   const RRTables T = w.tables();
   const int senv = PAIR ? 2 * env + wrep : env;      // row of this wave's replica in the state arrays (from the step's own copy of env: see RR_FRAME_LOCAL)
   const size_t ctrl_at = UNROLL ? ((size_t)((EVAL && !(io.a_pad & RR_EVAL_ACTIONS)) ? 0 : ut) * num_envs + env) * D.nu : (size_t)senv * D.nu;
-  if (ACTOR) {
+  if (ACTOR && !refpass) {
     if (ut == 0) {       // the observation the rollout starts from is row 0 of the env's trajectory (EVAL: of its two-row ring)
       const int ow = rr_obs_width<REFOBS>(D);      // row stride (REFOBS: with the reference blocks)
       for (int i = lane; i < ow; i += RR_LANES) io.t_obs[(EVAL ? (size_t)env * 2 : rr_traj_obs(io, num_envs, env, 0, 0)) * ow + i] = io.a_obs_in[(size_t)env * ow + i];
@@ -88,16 +99,16 @@
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
   }
   // ---- load state (a multi-step rollout keeps it in LDS after its first step)
-  if (!UNROLL || ut == 0) {
+  if (!UNROLL || (ut == 0 && !refpass)) {
     for (int i = lane; i < D.nq; i += RR_LANES) w.s_qpos[i] = io.qpos_in[(size_t)senv * D.nq + i];
     for (int i = lane; i < D.nv; i += RR_LANES) w.s_qvel[i] = io.qvel_in[(size_t)senv * D.nv + i];
     for (int i = lane; i < D.nu; i += RR_LANES) w.s_act[i] = io.act_in[(size_t)senv * D.nu + i];
   }
-  for (int i = lane; i < D.nu; i += RR_LANES) w.s_ctrl[i] = io.ctrl ? io.ctrl[ctrl_at + i] : 0.0f;
+  for (int i = lane; i < D.nu; i += RR_LANES) w.s_ctrl[i] = (io.ctrl && !refpass) ? io.ctrl[ctrl_at + i] : 0.0f;
 #pragma unroll
   for (int s = 0; s < NVS; ++s) {
     const int d = lane + RR_LANES * s;
-    if ((!UNROLL || ut == 0) && d < D.nv) w.s_warm[d] = io.warm_in[(size_t)senv * D.nv + d];
+    if ((!UNROLL || (ut == 0 && !refpass)) && d < D.nv) w.s_warm[d] = io.warm_in[(size_t)senv * D.nv + d];
     if (d < D.nv) {
       auto di = row_at(T.dof_i, RR_DOFI, d);
       w.dofc0[s] = (di[3] & 255) | ((di[2] & 15) << 8) | ((di[9] & 15) << 12) | ((di[0] & 255) << 16) | ((row_at(T.body_i, RR_BODYI, di[0])[0] & 255) << 24);
@@ -656,7 +667,23 @@
       }
       if (PTERM) pterm_code = __builtin_amdgcn_readfirstlane(pterm_code);      // lane 0's value in every lane: done_env below is formed by all of them
     }
-    if (UNROLL) {
+    if (RESTART && refpass) {
+      // REFERENCE RESTARTS: the pass has written the restored state's observation over the ended step's; what that step left to it
+      // follows -- the row that opens the next segment, and the state of the launch's last step (after the pass, as a reset stores it)
+      u_ref = 0;
+      if (ACTOR && !EVAL) {
+        const RRTraj tr = rr_traj(io, ut);
+        if (tr.t + 1 == io.a_seg && ut + 1 < nsteps) {
+          float* nx = io.t_obs + rr_traj_obs(io, num_envs, env, tr.u + 1, 0) * ow;
+          for (int i = lane; i < ow; i += RR_LANES) nx[i] = ob[i];
+        }
+      }
+      if (ut == nsteps - 1) {
+        for (int i = lane; i < D.nq; i += RR_LANES) io.qpos[(size_t)env * D.nq + i] = w.s_qpos[i];
+        for (int i = lane; i < D.nv; i += RR_LANES) { io.qvel[(size_t)env * D.nv + i] = w.s_qvel[i]; io.warm[(size_t)env * D.nv + i] = w.s_warm[i]; }
+        for (int i = lane; i < D.nu; i += RR_LANES) io.act[(size_t)env * D.nu + i] = w.s_act[i];
+      }
+    } else if (UNROLL) {
       // EpisodeWrapper + AutoResetWrapper on the step just made (action_repeat 1), as rr_wrap_kernel applies them:
       // steps' = (prev_done ? 0 : steps) + 1; over = steps' >= episode_length; done <- over ? 1 : done; truncation = over ? 1 - done_env : 0;
       // where done, the stored first state and first observation come back (info -- cur_frame, steps -- is not restored)
@@ -712,29 +739,78 @@
         }
         if (ended) {
           // CLIP SAMPLING, weighted restore: the slot drawn by the env's bank weights; the next slot without a table or with S == 0
+          const bool refr = load_io_member<int>(offsetof(RRIO, rref_on)) != 0;      // REFERENCE RESTARTS: no bank entry is read
+          const unsigned rn = u_draws;
           int drawn = -1;
-          if (const int* cw = load_io_member<const int*>(offsetof(RRIO, clip_weights))) {
-            if (const int* wbc = load_io_member<const int*>(offsetof(RRIO, bank_clips)))
-              drawn = rr_weighted_slot(cw, wbc, load_io_member<int>(offsetof(RRIO, restart_K)), load_io_member<int>(offsetof(RRIO, num_clips)), env, num_envs,
-                                       load_io_member<unsigned>(offsetof(RRIO, sample_seed)), u_draws, lane);
+          if (!refr) {      // (a reference restart draws a clip, not a slot: the weights are read below)
+            if (const int* cw = load_io_member<const int*>(offsetof(RRIO, clip_weights))) {
+              if (const int* wbc = load_io_member<const int*>(offsetof(RRIO, bank_clips)))
+                drawn = rr_weighted_slot(cw, wbc, load_io_member<int>(offsetof(RRIO, restart_K)), load_io_member<int>(offsetof(RRIO, num_clips)), env, num_envs,
+                                         load_io_member<unsigned>(offsetof(RRIO, sample_seed)), u_draws, lane);
+            }
           }
           u_draws = u_draws + 1u;
           u_slot = u_slot + 1;
           if (u_slot >= load_io_member<int>(offsetof(RRIO, restart_K))) u_slot = 0;
           if (drawn >= 0) u_slot = drawn;
-          const size_t re = (size_t)u_slot * (size_t)num_envs + (size_t)env;      // row of the bank entry in every [K][N][width] array
-          u_frame = __builtin_amdgcn_readfirstlane(load_io_member<const int*>(offsetof(RRIO, restart_frames))[re]);
-          if (const int* bcl = load_io_member<const int*>(offsetof(RRIO, bank_clips))) {      // CLIP LIBRARY: the entry's clip, clamped
+          if (refr) {
+            // REFERENCE RESTARTS (RRIO): clip and frame drawn here, wave-uniform and in integers; the start state built in LDS from the
+            // clip's rows plus noise; the forward pass and the observation are the next trip of the loop (refpass).  Clip and frame are
+            // clamped before a row offset is formed, so no row lies outside the arrays or at or behind the clip's own end.
+            const unsigned base = rr_ref_base(load_io_member<unsigned>(offsetof(RRIO, rref_seed)), env, rn);
             const int nc = load_io_member<int>(offsetof(RRIO, num_clips));
-            const int c = __builtin_amdgcn_readfirstlane(bcl[re]);
-            u_clip = c < 0 ? 0 : (c > nc - 1 ? nc - 1 : c);
+            int c = u_clip;
+            if (load_io_member<int>(offsetof(RRIO, rref_across)) != 0 && load_io_member<const int*>(offsetof(RRIO, clip)) && nc >= 1)
+              c = rr_ref_clip(load_io_member<const int*>(offsetof(RRIO, clip_weights)), nc, rr_ref_hash(base, 1u, 0u), opaque(lane));
+            const int flo = load_io_member<int>(offsetof(RRIO, rref_lo)), fhi = load_io_member<int>(offsetof(RRIO, rref_hi));
+            int f = flo + (int)(((unsigned long long)rr_ref_hash(base, 2u, 0u) * (unsigned long long)(unsigned)(fhi - flo)) >> 32);
+            const int tl = load_io_member<int>(offsetof(RRIO, track_len));
+            const int cl = rr_clip_frames<BODY>(c, tl);
+            if (load_io_member<const int*>(offsetof(RRIO, clip_len))) f = cl > 1 ? (int)((unsigned)f % (unsigned)(cl - 1)) : 0;
+            const int fr = f < 0 ? 0 : (f > cl - 1 ? cl - 1 : f);
+            u_clip = c; u_frame = f;
+            const size_t rrow = (size_t)c * (size_t)tl + (size_t)fr;
+            const float* rp = load_io_member<const float*>(offsetof(RRIO, track_pos)) + rrow * 3;
+            const float* rq = load_io_member<const float*>(offsetof(RRIO, track_pose)) + rrow * (size_t)(D.nq - 3);
+            const float* rv = load_io_member<const float*>(offsetof(RRIO, track_vel));
+            const float ns = load_io_member<float>(offsetof(RRIO, rref_noise));
+            const int rl = opaque(lane);
+            w.sync();
+            {      // one rounded product and one rounded sum per element: contraction off and the plain operators (__fmul_rn / __fadd_rn carry the
+                   // translation unit's contraction licence, see POSE TRACKING above), and the product passes through an opaque copy
+#pragma clang fp contract(off)
+              for (int i = rl; i < D.nq; i += RR_LANES) {
+                const float row = i < 3 ? rp[i] : rq[i - 3];
+                float nz = ns * rr_ref_unit(rr_ref_hash(base, 3u, (unsigned)i));
+                asm volatile("" : "+v"(nz));
+                w.s_qpos[i] = row + nz;
+              }
+              for (int i = rl; i < D.nv; i += RR_LANES) {
+                const float row = rv ? rv[rrow * (size_t)D.nv + i] : 0.0f;
+                float nz = ns * rr_ref_unit(rr_ref_hash(base, 4u, (unsigned)i));
+                asm volatile("" : "+v"(nz));
+                w.s_qvel[i] = row + nz;
+                w.s_warm[i] = 0.0f;
+              }
+            }
+            for (int i = rl; i < D.nu; i += RR_LANES) w.s_act[i] = 0.0f;
+            w.sync();
+            u_ref = 1;
+          } else {      // the bank restore: state, observation, frame and clip of entry u_slot
+            const size_t re = (size_t)u_slot * (size_t)num_envs + (size_t)env;      // row of the bank entry in every [K][N][width] array
+            u_frame = __builtin_amdgcn_readfirstlane(load_io_member<const int*>(offsetof(RRIO, restart_frames))[re]);
+            if (const int* bcl = load_io_member<const int*>(offsetof(RRIO, bank_clips))) {      // CLIP LIBRARY: the entry's clip, clamped
+              const int nc = load_io_member<int>(offsetof(RRIO, num_clips));
+              const int c = __builtin_amdgcn_readfirstlane(bcl[re]);
+              u_clip = c < 0 ? 0 : (c > nc - 1 ? nc - 1 : c);
+            }
+            w.sync();
+            for (int i = lane; i < D.nq; i += RR_LANES) w.s_qpos[i] = io.first_qpos[re * D.nq + i];
+            for (int i = lane; i < D.nv; i += RR_LANES) { w.s_qvel[i] = io.first_qvel[re * D.nv + i]; w.s_warm[i] = io.first_warm[re * D.nv + i]; }
+            for (int i = lane; i < D.nu; i += RR_LANES) w.s_act[i] = io.first_act[re * D.nu + i];
+            for (int i = lane; i < ow; i += RR_LANES) ob[i] = io.first_obs[re * ow + i];
+            w.sync();
           }
-          w.sync();
-          for (int i = lane; i < D.nq; i += RR_LANES) w.s_qpos[i] = io.first_qpos[re * D.nq + i];
-          for (int i = lane; i < D.nv; i += RR_LANES) { w.s_qvel[i] = io.first_qvel[re * D.nv + i]; w.s_warm[i] = io.first_warm[re * D.nv + i]; }
-          for (int i = lane; i < D.nu; i += RR_LANES) w.s_act[i] = io.first_act[re * D.nu + i];
-          for (int i = lane; i < ow; i += RR_LANES) ob[i] = io.first_obs[re * ow + i];
-          w.sync();
         }
       } else if (wrapped && __builtin_amdgcn_readfirstlane(__float_as_int(done2)) != 0) {
         w.sync();
@@ -771,6 +847,9 @@
         for (int i = lane; i < D.nv; i += RR_LANES) { io.qvel[(size_t)env * D.nv + i] = w.s_qvel[i]; io.warm[(size_t)env * D.nv + i] = w.s_warm[i]; }
         for (int i = lane; i < D.nu; i += RR_LANES) io.act[(size_t)env * D.nu + i] = w.s_act[i];
       }
+      // REFERENCE RESTARTS: the restore's forward pass is the next trip, at this step's index (what the three blocks above wrote of the
+      // ended step's state and observation, the pass writes again)
+      if (RESTART) { if (u_ref != 0) ut = ut - 1; }
     }
   }
  }     // ut

@@ -165,6 +165,103 @@ def weighted_slot(h, slot_weights, slot: int = 0) -> int:
     raise AssertionError("unreachable: r < S")
 
 
+MAX_REFERENCE_CLIPS = 32768      # clips a reference restart draws over: the weights' sum times a 32-bit hash stays within 63 bits
+
+
+def reference_restart_hash(seed, env, n, purpose: int, element=0) -> np.ndarray:
+    """The 32-bit hashes a reference restart draws with (`Rodent(restart_from_reference=True)`; C ABI `rr_reference_restart_io`), uint64
+    holding 32-bit values: fmix32(restart_hash(seed, env, n) ^ (((purpose << 16) | element) * 0x9E3779B1)), mod 2**32.  `purpose`: 1 the
+    clip, 2 the frame, 3 the qpos noise, 4 the qvel noise; `element` the index within qpos / qvel (broadcast against `env` and `n`)."""
+    tag = (np.uint64(int(purpose) << 16) | (np.asarray(element).astype(np.uint64) & np.uint64(0xFFFF))) * np.uint64(0x9E3779B1)
+    return _fmix32(restart_hash(seed, env, n) ^ (tag & _M32))
+
+
+def reference_restart_draws(seed, env, n, frame_range, clip=None, num_clips: Optional[int] = None, across_clips: bool = False, weights=None,
+                            lengths=None):
+    """The clip and start frame a reference restart of env `env` at restore count `n` (`info['restart_draws']` before the restore) takes,
+    in integers: (clip int32 [N] or None, draw int32 [N], frame int32 [N]).
+
+    clip:  with `across_clips` and `num_clips` = C, over all C clips with h = reference_restart_hash(seed, env, n, 1): by `weights` (the
+           int table of `clip_weights()`, sum S > 0) the smallest c with q_0 + .. + q_c > (h * S) >> 32 -- `weighted_slot`'s prefix rule
+           on the C clip weights, a clip of weight 0 is never drawn --, without a table or with S == 0 uniformly, (h * C) >> 32.
+           Otherwise `clip` itself (None without a clip axis).
+    draw:  lo + ((h' * (hi - lo)) >> 32), h' = reference_restart_hash(seed, env, n, 2), `frame_range` = (lo, hi): in [lo, hi).
+    frame: the draw folded into the drawn clip as every start frame is (`fold_start_frames`: draw mod (L_c - 1) with `lengths`, else the
+           draw itself; the rows are then read at the clamped frame, `reference_rows`)."""
+    env, n = np.broadcast_arrays(np.asarray(env, dtype=np.int64), np.asarray(n, dtype=np.int64))
+    lo, hi = (int(x) for x in frame_range)
+    if across_clips and num_clips is not None:
+        h = reference_restart_hash(seed, env, n, 1)
+        q = None if weights is None else (np.asarray(weights).astype(np.uint64) & np.uint64(0xFFFF))
+        if q is not None and int(q.sum()) > 0:
+            prefix = np.cumsum(q)
+            r = (h * prefix[-1]) >> np.uint64(32)
+            clip = np.searchsorted(prefix, r, side="right").astype(np.int32)       # the first index whose prefix exceeds r
+        else:
+            clip = ((h * np.uint64(int(num_clips))) >> np.uint64(32)).astype(np.int32)
+    elif clip is not None:
+        clip = np.broadcast_to(np.asarray(clip, dtype=np.int32), env.shape).copy()
+    draw = (lo + ((reference_restart_hash(seed, env, n, 2) * np.uint64(hi - lo)) >> np.uint64(32)).astype(np.int64)).astype(np.int32)
+    return clip, draw, fold_start_frames(draw, lengths, clip)
+
+
+def reference_restart_noise(seed, env, n, purpose: int, width: int, noise_scale: float) -> np.ndarray:
+    """The noise of a reference restart, float32 [N, width]: noise_scale * s with s = (h_i >> 8) * 2**-23 - 1 in [-1, 1) -- exact in
+    float32 -- and h_i = reference_restart_hash(seed, env, n, purpose, i); one rounded float32 product.  Uniform like the noise of
+    `reset_draws`, from another generator."""
+    env, n = np.broadcast_arrays(np.asarray(env, dtype=np.int64), np.asarray(n, dtype=np.int64))
+    h = reference_restart_hash(seed, env[:, None], n[:, None], purpose, np.arange(int(width))[None, :])
+    s = (h >> np.uint64(8)).astype(np.float32) * np.float32(2.0 ** -23) - np.float32(1.0)
+    return np.float32(noise_scale) * s
+
+
+def reference_restart_state(seed, env, n, clip, frame, track: np.ndarray, pose: np.ndarray, track_vel: Optional[np.ndarray], noise_scale: float,
+                            lengths=None):
+    """The state a reference restart starts from, (qpos float32 [N, nq], qvel float32 [N, nv]), for the clip and frame of
+    `reference_restart_draws`: qpos = [track[(clip,) frame], pose[(clip,) frame]] and qvel = track_vel[(clip,) frame] (zeros for
+    `track_vel` an int: that many dofs, an env without a velocity block), the frame clamped within the clip (`reference_rows`: no row at
+    or behind L_c is read), each plus `reference_restart_noise` (purpose 3 / 4) in one rounded float32 sum."""
+    rows = lambda a: np.asarray(reference_rows(a, frame, clip, lengths), dtype=np.float32)
+    qpos = np.concatenate([rows(track), rows(pose)], axis=-1)
+    qvel = np.zeros((qpos.shape[0], int(track_vel)), dtype=np.float32) if isinstance(track_vel, (int, np.integer)) else rows(track_vel)
+    return (qpos + reference_restart_noise(seed, env, n, 3, qpos.shape[1], noise_scale),
+            qvel + reference_restart_noise(seed, env, n, 4, qvel.shape[1], noise_scale))
+
+
+def _fmix32_t(h: torch.Tensor) -> torch.Tensor:
+    """`_fmix32` on int64 tensors holding 32-bit values (a product's low 32 bits survive the int64 wrap-around)."""
+    h = h ^ (h >> 16)
+    h = (h * 0x85EBCA6B) & 0xFFFFFFFF
+    h = h ^ (h >> 13)
+    h = (h * 0xC2B2AE35) & 0xFFFFFFFF
+    return h ^ (h >> 16)
+
+
+def _reference_restart_hash_t(seed: int, env: torch.Tensor, n: torch.Tensor, purpose: int, element=0) -> torch.Tensor:
+    """`reference_restart_hash` in torch integers (the device form the per-step wrappers draw with)."""
+    base = _fmix32_t((_fmix32_t((int(seed) & 0xFFFFFFFF) ^ ((env * 0x9E3779B1) & 0xFFFFFFFF)) + (n & 0xFFFFFFFF)) & 0xFFFFFFFF)
+    return _fmix32_t(base ^ ((((int(purpose) << 16) | element) * 0x9E3779B1) & 0xFFFFFFFF))
+
+
+def _check_reference_restart(restart_from_reference, restart_noise_seed, reset_to_reference: bool, clip_restarts: int, have_pose: bool,
+                             num_clips: Optional[int]):
+    """`restart_from_reference` and `restart_noise_seed` of `Rodent` as (flag, seed); ValueError for the flag on a position-only env,
+    without `reset_to_reference=True` or without `clip_restarts >= 1`, for more than `MAX_REFERENCE_CLIPS` clips, and for a seed outside
+    0 .. 2**32 - 1."""
+    on = bool(restart_from_reference)
+    if isinstance(restart_noise_seed, (bool, np.bool_)) or not isinstance(restart_noise_seed, (int, np.integer)) or not 0 <= int(restart_noise_seed) < 2 ** 32:
+        raise ValueError(f"restart_noise_seed must be an int in 0 .. 2**32 - 1, got {restart_noise_seed!r}")
+    if on and not have_pose:
+        raise ValueError("restart_from_reference=True needs the reference pose: pass track_quat and track_joints (a position-only env has no pose rows to start from)")
+    if on and not reset_to_reference:
+        raise ValueError("restart_from_reference=True needs reset_to_reference=True: a restore starts from the clip's pose as the reset does")
+    if on and clip_restarts < 1:
+        raise ValueError("restart_from_reference=True needs clip_restarts >= 1: it replaces the restore of the clip-restart rule")
+    if on and num_clips is not None and num_clips > MAX_REFERENCE_CLIPS:
+        raise ValueError(f"restart_from_reference=True serves at most {MAX_REFERENCE_CLIPS} clips, got {num_clips}")
+    return on, int(restart_noise_seed)
+
+
 def quantise_clip_weights(w) -> np.ndarray:
     """Float weights [C], finite, >= 0 and not all zero, as the int32 table the device reads: 0 -> 0, otherwise
     max(1, round(65535 * w / max w)) (round half to even), so the largest weight is 65535 and no positive weight is lost."""
@@ -680,6 +777,8 @@ class Rodent(PipelineEnv):
         restart_sampling: Optional[str] = None,
         clip_outcomes: bool = False,
         restart_sampling_seed: int = 0,
+        restart_from_reference: bool = False,
+        restart_noise_seed: int = 0,
         **kwargs,
     ):
         """`track_pos`: the reference positions to track, float [T, 3] -- one clip, followed by every env -- or [C, T, 3], C >= 1 clips of
@@ -821,7 +920,25 @@ class Rodent(PipelineEnv):
 
         n = `info['restart_draws']` (int32 [N], zeros at `reset`), the env's restore count, which grows by one at every restore.  The
         weights start uniform (all 65535) and are set with `set_clip_weights` -- in place, so later launches and replayed graphs see
-        them; a clip of weight 0 is never drawn while another entry of the env's bank has a positive one."""
+        them; a clip of weight 0 is never drawn while another entry of the env's bank has a positive one.
+
+        Reference restarts (`restart_from_reference=True`; off by default, and off is today's path in every bit and every key; needs
+        `reset_to_reference=True` and `clip_restarts` >= 1, K = 1 suffices).  A restore of the wrapped forms takes NO bank entry: it
+        draws a clip and a start frame, builds the start state from the clip's rows plus noise and forms the observation the reset
+        launch gives for that state -- inside the one-launch rollouts, by a forward-only pass of the step kernel that is not counted as
+        a step; in the per-step wrappers by a reset launch and a select.  So the start states of a run are not the K per env that
+        `reset` drew, but any frame of any clip.  With n = `info['restart_draws']` (now present whatever the sampling; it grows by one
+        per restore) every draw is an integer hash of (`restart_noise_seed`, env, n, purpose, element) (`reference_restart_hash`):
+
+            clip:   with `restart_across_clips`, over all C clips -- by `clip_weights()` when `restart_sampling="weighted"` (a clip of
+                    weight 0 is never drawn), else uniformly; otherwise the env stays on its clip       (`reference_restart_draws`)
+            frame:  lo + ((h * (hi - lo)) >> 32) in `restart_frame_range`, folded into the clip like every start frame
+            state:  qpos = [track_pos, pose][clip, frame], qvel = track_vel[clip, frame] (0 without the velocity arrays), each element
+                    plus reset_noise_scale * ((h_i >> 8) * 2**-23 - 1); act and warm start 0                (`reference_restart_state`)
+
+        `info['cur_frame']` and `info['clip']` move to the draw; `reset`, the bank it builds (entry 0 still is the reset state) and
+        `info['restart_slot']` (which advances cyclically and selects nothing) stay, as do the outcome counters, `end_at_clip_end`, pose
+        termination, the bad-state check and truncation.  `restart_sampling_seed` is not used by these restores."""
         given = locals()                  # the arguments as they came (first statement: nothing else is a local yet): `_ctor` below
         if bad_state_max is not None:
             with np.errstate(over="ignore", under="ignore"):
@@ -849,6 +966,8 @@ class Rodent(PipelineEnv):
         lengths_np, across = _check_clip_library(clip_lengths, restart_across_clips, track_np, pose_np is not None, restarts[0])
         weighted, counting, sample_seed = _check_clip_sampling(restart_sampling, clip_outcomes, restart_sampling_seed, across, restarts[0],
                                                                track_np.shape[0] if track_np.ndim == 3 else None)
+        ref_restart, noise_seed = _check_reference_restart(restart_from_reference, restart_noise_seed, bool(reset_to_reference), restarts[0], pose_np is not None,
+                                                           track_np.shape[0] if track_np.ndim == 3 else None)
         vel_np = _check_velocity_tracking(track_np, track_velocity, track_angular_velocity, track_joint_velocity, sys.nv,
                                           (lin_vel_reward_weight, lin_vel_reward_scale, ang_vel_reward_weight, ang_vel_reward_scale,
                                            joint_vel_reward_weight, joint_vel_reward_scale), pose_np is not None)
@@ -872,6 +991,7 @@ class Rodent(PipelineEnv):
         self._lengths_host = lengths_np       # None: every clip has T frames (no such members anywhere)
         self._clip_lengths = None if lengths_np is None else torch.from_numpy(lengths_np).to(self.device).contiguous()
         self._across_clips = across
+        self._ref_restart, self._noise_seed = ref_restart, noise_seed
         # clip sampling: None without either option (no such members anywhere); the two tables live for the env's life and are rewritten
         # in place, so a captured launch keeps reading them
         self._sampling = None
@@ -897,7 +1017,8 @@ class Rodent(PipelineEnv):
                   (vel_np is not None, "track_velocity=...", batch.velocity_tracking_supported),
                   (self._clip_restarts > 0, f"clip_restarts={self._clip_restarts}", batch.clip_restarts_supported),
                   (lengths_np is not None or across, "clip_lengths=... / restart_across_clips=True", batch.clip_library_supported),
-                  (weighted or counting, "restart_sampling=... / clip_outcomes=True", batch.clip_sampling_supported))
+                  (weighted or counting, "restart_sampling=... / clip_outcomes=True", batch.clip_sampling_supported),
+                  (ref_restart, "restart_from_reference=True", batch.reference_restart_supported))
         for wanted, label, query in probes:       # a model, solver or frame count without the option's instance: the library's reason
             why = query() if wanted else None
             if why is not None:
@@ -1015,6 +1136,53 @@ class Rodent(PipelineEnv):
         return self._across_clips
 
     @property
+    def restart_from_reference(self) -> bool:
+        """Whether a restore of the wrapped forms starts from a freshly drawn clip frame instead of a bank entry."""
+        return self._ref_restart
+
+    def reference_restart(self, clip: Optional[torch.Tensor], draws: torch.Tensor):
+        """The reference restart of EVERY env at restore counts `draws` (int32 [N]), from the clips `clip` (int32 [N]; None without a clip
+        axis), as the per-step wrappers apply it where an episode ended: the draws of `reference_restart_draws` and the state of
+        `reference_restart_state` in torch on the device, then the reset launch on that state.  Returns (pipeline state, obs, cur_frame
+        int32 [N], clip int32 [N] or None)."""
+        N, dev, s, seed = self.num_envs, self.device, self.sys, self._noise_seed
+        env, n = torch.arange(N, device=dev), draws.long()
+        lo, hi = self._restart_frame_range
+        c = None if clip is None else clip.long()
+        if self._across_clips:
+            h = _reference_restart_hash_t(seed, env, n, 1)
+            uniform = (h * self.num_clips) >> 32
+            w = None if self._sampling is None else self._sampling["weights"]
+            if w is not None:
+                prefix = (w.long() & 0xFFFF).cumsum(0)
+                c = torch.where(prefix[-1] > 0, torch.searchsorted(prefix, (h * prefix[-1]) >> 32, right=True).clamp(max=self.num_clips - 1), uniform)
+            else:
+                c = uniform
+        f = lo + ((_reference_restart_hash_t(seed, env, n, 2) * (hi - lo)) >> 32)
+        if self._clip_lengths is not None:
+            L = self._clip_lengths.long()[c if c is not None else torch.zeros_like(env)]
+            f = f % (L - 1)
+            fr = torch.minimum(f.clamp(min=0), L - 1)
+        else:
+            fr = f.clamp(0, self.track_len - 1)
+        rows = lambda a: a[fr] if c is None else a[c, fr]
+        scale = torch.tensor(self._reset_noise_scale, dtype=torch.float32, device=dev)
+
+        def noise(purpose, width):
+            h = _reference_restart_hash_t(seed, env[:, None], n[:, None], purpose, torch.arange(width, device=dev)[None, :])
+            return scale * ((h >> 8).to(torch.float32) * (2.0 ** -23) - 1.0)
+        qpos = torch.cat([rows(self._track_pos), rows(self._track_pose)], dim=-1) + noise(3, s.nq)
+        qvel = (rows(self._track_vel) if self._track_vel is not None else torch.zeros(N, s.nv, device=dev)) + noise(4, s.nv)
+        st = dict(qpos=qpos.contiguous(), qvel=qvel.contiguous(), act=torch.zeros(N, s.na, device=dev), qacc_warmstart=torch.zeros(N, s.nv, device=dev))
+        out = self._alloc_outputs(full=False)
+        cur_frame = f.to(torch.int32)
+        clip_dev = None if c is None else c.to(torch.int32)
+        obs = torch.empty(N, self.observation_size, device=dev)
+        library = None if self._clip_lengths is None else dict(lengths=self._clip_lengths)
+        self._batch.env_reset(st, self._env_io(cur_frame, obs, clip=clip_dev, clip_library=library), out)
+        return PipelineState(**st, **out), obs, cur_frame, clip_dev
+
+    @property
     def clip_sampling(self) -> Optional[dict]:
         """None without `restart_sampling` / `clip_outcomes`, else dict(weights=int32 [C] device table or None, outcomes=int64 [C, 5]
         device table or None, seed): the tables themselves, which the wrapped forms read and add to."""
@@ -1071,7 +1239,8 @@ class Rodent(PipelineEnv):
             raise RuntimeError("pose tracking: no pose instance reads per-env parameters (randomize / set_env_params on a pose env)")
         return super().randomize(randomization_fn)
 
-    def _env_io(self, cur_frame, obs, reward=None, done=None, metrics=None, clip=None, restart=None, clip_library=None, clip_sampling=None, **buffers):
+    def _env_io(self, cur_frame, obs, reward=None, done=None, metrics=None, clip=None, restart=None, clip_library=None, clip_sampling=None,
+                reference_restart=None, **buffers):
         """The env-io dict of a launch.  `buffers`: the step options' output buffers by env-io key (`_launch_buffers`); each brings its
         option's static entries along.  `restart`: the clip-restart block of a multi-step launch (single steps and resets pass none).
         `clip_library`: the clip-library block (an env with `clip_lengths` or `restart_across_clips` only); it rides on the pose block,
@@ -1093,6 +1262,8 @@ class Rodent(PipelineEnv):
             io["clip_library"] = clip_library
         if clip_sampling is not None and restart is not None:
             io["clip_sampling"] = clip_sampling
+        if reference_restart is not None and restart is not None:      # reference restarts ride on the clip-restart block too
+            io["reference_restart"] = reference_restart
         return io
 
     def reset(self, rng, clip=None) -> State:
@@ -1152,7 +1323,7 @@ class Rodent(PipelineEnv):
             if self._across_clips:
                 info["restart_bank"]["clip"] = to_dev(np.stack(clips))
             info["restart_slot"] = torch.zeros(N, dtype=torch.int32, device=dev)
-            if self._sampling is not None and self._sampling["weights"] is not None:      # the restore count the weighted draw hashes
+            if (self._sampling is not None and self._sampling["weights"] is not None) or self._ref_restart:      # the restore count the draws hash
                 info["restart_draws"] = torch.zeros(N, dtype=torch.int32, device=dev)
         zero = torch.zeros(N, device=dev)
         metrics = {"pos_reward": zero, "reward_quadctrl": zero.clone(), "reward_alive": zero.clone()}
@@ -1189,9 +1360,17 @@ class Rodent(PipelineEnv):
             if self._across_clips and wrap is not None:
                 io["clip_library"].update(bank_clips=info["restart_bank"]["clip"], clip_out=torch.empty_like(info["clip"]))
         if self._sampling is not None and wrap is not None:      # clip sampling: the multi-step forms count and draw in the kernel
-            io["clip_sampling"] = dict(self._sampling)
-            if self._sampling["weights"] is not None:
-                io["clip_sampling"].update(draws_in=info["restart_draws"], draws_out=torch.empty_like(info["restart_draws"]))
+            if not self._ref_restart:
+                io["clip_sampling"] = dict(self._sampling)
+                if self._sampling["weights"] is not None:
+                    io["clip_sampling"].update(draws_in=info["restart_draws"], draws_out=torch.empty_like(info["restart_draws"]))
+            elif self._sampling["outcomes"] is not None:
+                # reference restarts draw a clip, not a slot: weights and restore counts travel in that block (below), the counters stay here
+                io["clip_sampling"] = dict(weights=None, outcomes=self._sampling["outcomes"], seed=self._sampling["seed"])
+        if self._ref_restart and wrap is not None:      # reference restarts: the multi-step forms draw and build the start state in the kernel
+            io["reference_restart"] = dict(draws_in=info["restart_draws"], draws_out=torch.empty_like(info["restart_draws"]),
+                                           weights=None if self._sampling is None else self._sampling["weights"], seed=self._noise_seed,
+                                           frame_range=self._restart_frame_range, across_clips=self._across_clips, noise_scale=self._reset_noise_scale)
         return st_in, st, io, wrap
 
     def _next_state(self, state: State, st, io, obs, wrap=None, out=None) -> State:
@@ -1206,6 +1385,8 @@ class Rodent(PipelineEnv):
                 info["clip"] = io["clip_library"]["clip_out"]
             if io.get("clip_sampling", {}).get("draws_out") is not None:
                 info["restart_draws"] = io["clip_sampling"]["draws_out"]
+            if "reference_restart" in io:
+                info["restart_draws"] = io["reference_restart"]["draws_out"]
         m = dict(state.metrics)
         m.update(pos_reward=io["metrics"][:, 0], reward_quadctrl=io["metrics"][:, 1], reward_alive=io["metrics"][:, 2])
         for o in self._options:

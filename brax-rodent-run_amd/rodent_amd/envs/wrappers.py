@@ -189,13 +189,35 @@ def count_outcomes(outcomes, clip, failed, done_env, done):
     flat.index_add_(0, clip * 5 + col, d)
 
 
+def _reference_restore(base, state, done, nslot):
+    """The restore of an env with `restart_from_reference`: where `done`, state, observation, `cur_frame` and `info['clip']` come from
+    `base.reference_restart` at the env's restore count (no bank entry is read), and `info['restart_draws']` grows by one; the slot
+    advances cyclically (`nslot`) and selects nothing.  Cost: the per-step forms pay ONE forward-only launch (a reset of all N envs)
+    per wrapped step, whether or not an env is done -- no host synchronisation, and a captured graph replays it -- and that launch
+    clears the restart, library and sampling blocks of the batch, which the next step launch sets again.  The one-launch rollouts
+    (`unroll`, `unroll_policy`) pay a forward pass per ended episode only."""
+    draws = state.info["restart_draws"]
+    ps, obs, frame, clip = base.reference_restart(state.info.get("clip"), draws)
+
+    def where_done(x, y):
+        return torch.where(done.reshape((-1,) + (1,) * (y.dim() - 1)), x, y)
+
+    state.info["cur_frame"] = where_done(frame, state.info["cur_frame"])
+    if clip is not None:
+        state.info["clip"] = where_done(clip, state.info["clip"])
+    state.info["restart_draws"] = draws + done.to(draws.dtype)
+    state.info["restart_slot"] = nslot
+    return state.replace(pipeline_state=_tree_map2(where_done, ps, state.pipeline_state), obs=where_done(obs, state.obs))
+
+
 class ClipAutoResetWrapper(Wrapper):
     """`AutoResetWrapper` of an env with clip restarts: where done, the env takes the NEXT entry of its start bank
     (`info['restart_bank']`, built by the env's `reset`) -- slot' = (slot + 1) mod K; pipeline state, observation and `cur_frame` come
     from entry slot' -- so the restarted episode rejoins its clip at the frame its state was formed at.  Bank and slot are info: never
     re-drawn, never restored.  A bank with a `clip` leaf (`restart_across_clips`) also hands its entry's clip to `info['clip']`.  An env
     with `clip_sampling` tables (`Rodent(restart_sampling=..., clip_outcomes=...)`) has its steps counted on the clip they were made on,
-    and its restores drawn by the clips' weights (`weighted_slots`; `info['restart_draws']` grows by one at every restore)."""
+    and its restores drawn by the clips' weights (`weighted_slots`; `info['restart_draws']` grows by one at every restore).  An env with
+    `restart_from_reference` takes no bank entry: `_reference_restore`."""
 
     def step(self, state, action):
         if "steps" in state.info:
@@ -216,11 +238,13 @@ class ClipAutoResetWrapper(Wrapper):
                 failed = state.metrics["pose_fail"] != 0 if "pose_fail" in state.metrics else torch.zeros_like(done)
                 on = state.info["clip"].long() if "clip" in state.info else torch.zeros_like(slot, dtype=torch.long)
                 count_outcomes(sampling["outcomes"], on.clamp(0, sampling["outcomes"].shape[0] - 1), failed, own, done)
-            if sampling["weights"] is not None:
+            if sampling["weights"] is not None and not getattr(_base(self.env), "restart_from_reference", False):
                 draws = state.info["restart_draws"]
                 drawn = weighted_slots(sampling["weights"], bank["clip"], sampling["seed"], draws)
                 nslot = torch.where(done & (drawn >= 0), drawn.to(slot.dtype), nslot)
                 state.info["restart_draws"] = draws + done.to(draws.dtype)
+        if getattr(_base(self.env), "restart_from_reference", False):
+            return _reference_restore(_base(self.env), state, done, nslot)
         row, env = nslot.long(), torch.arange(done.shape[0], device=done.device)
 
         def where_done(x, y):      # x: the bank's leaf [K, N, ...]
@@ -318,6 +342,9 @@ class FusedEpisodeAutoResetWrapper(Wrapper):
             slot = torch.empty_like(state.info["restart_slot"])
             lengths = getattr(base, "clip_lengths", None)
             sampling = getattr(base, "clip_sampling", None)
+            ref = getattr(base, "restart_from_reference", False)
+            if ref:      # reference restarts: the rule below with the cyclic slot (its restore is replaced after it), the counters as they are
+                sampling = None if sampling is None or sampling["outcomes"] is None else dict(sampling, weights=None)
             if sampling is not None:      # clip sampling: the library's rule plus the counters and the weighted draw
                 clip = state.info["clip"].clone() if "clip" in state.info else None
                 draws = state.info.get("restart_draws")
@@ -341,6 +368,11 @@ class FusedEpisodeAutoResetWrapper(Wrapper):
                 hip.wrap_clip_restart(first, cur, state.done, state.info["steps"], nstate.done, steps, trunc, self.episode_length, 1,
                                       nstate.info["cur_frame"], bank["frame"], state.info["restart_slot"], slot, base.track_len, base.end_at_clip_end)
             nstate.info.update(steps=steps, truncation=trunc, restart_slot=slot)
+            if ref:      # where done, the bank entry the launch above restored gives way to the freshly drawn start state
+                for k in ("clip", "restart_draws"):
+                    if k in state.info:
+                        nstate.info[k] = state.info[k]
+                return _reference_restore(base, nstate, nstate.done.bool(), slot)
             return nstate
         fps, ps = nstate.info["first_pipeline_state"], nstate.pipeline_state
         names = [f.name for f in dataclasses.fields(ps) if torch.is_tensor(getattr(ps, f.name))]

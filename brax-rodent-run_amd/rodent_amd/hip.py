@@ -88,6 +88,12 @@ class RRClipSamplingIO(C.Structure):
     _fields_ = [("clip_weights", C.c_void_p), ("draws_in", C.c_void_p), ("draws_out", C.c_void_p), ("outcomes", C.c_void_p), ("seed", C.c_uint32)]
 
 
+class RRReferenceRestartIO(C.Structure):
+    """`rr_reference_restart_io`, the reference-restart block a batch carries next to its clip-restart block (`rr_batch_set_reference_restart`)."""
+    _fields_ = [("clip_weights", C.c_void_p), ("draws_in", C.c_void_p), ("draws_out", C.c_void_p), ("seed", C.c_uint32), ("frame_lo", C.c_int32),
+                ("frame_hi", C.c_int32), ("across_clips", C.c_int32), ("noise_scale", C.c_float), ("pad", C.c_int32)]
+
+
 class RRUnrollIO(C.Structure):
     _fields_ = [("first", RRState), ("first_obs", C.c_void_p), ("prev_done", C.c_void_p), ("steps_in", C.c_void_p), ("steps_out", C.c_void_p),
                 ("truncation_out", C.c_void_p), ("episode_length", C.c_float)]
@@ -119,7 +125,7 @@ class RRPpoCfg(C.Structure):
 
 
 EXPORTS = ["rr_model_load", "rr_model_dims", "rr_model_set_solver", "rr_model_set_solver_type", "rr_model_destroy", "rr_model_table", "rr_kernarg_layout", "rr_batch_create",
-           "rr_batch_destroy", "rr_pipeline_init", "rr_pipeline_step", "rr_env_step", "rr_env_reset", "rr_pipeline_step_to", "rr_env_step_to", "rr_batch_contact_overflow", "rr_batch_bad_states", "rr_batch_unroll_supported", "rr_env_unroll", "rr_env_unroll_policy", "rr_batch_eval_supported", "rr_env_unroll_eval", "rr_batch_pose_supported", "rr_batch_set_pose", "rr_batch_set_reference_obs", "rr_batch_obs_width", "rr_batch_reference_obs_supported", "rr_batch_set_pose_termination", "rr_batch_pose_termination_supported", "rr_batch_set_body_tracking", "rr_batch_body_tracking_supported", "rr_batch_set_clip_restarts", "rr_batch_clip_restarts_supported", "rr_batch_set_velocity_tracking", "rr_batch_velocity_tracking_supported", "rr_batch_set_clip_library", "rr_batch_clip_library_supported", "rr_batch_set_clip_sampling", "rr_batch_clip_sampling_supported", "rr_wrap_clip_restart", "rr_wrap_clip_library", "rr_wrap_clip_sampling",
+           "rr_batch_destroy", "rr_pipeline_init", "rr_pipeline_step", "rr_env_step", "rr_env_reset", "rr_pipeline_step_to", "rr_env_step_to", "rr_batch_contact_overflow", "rr_batch_bad_states", "rr_batch_unroll_supported", "rr_env_unroll", "rr_env_unroll_policy", "rr_batch_eval_supported", "rr_env_unroll_eval", "rr_batch_pose_supported", "rr_batch_set_pose", "rr_batch_set_reference_obs", "rr_batch_obs_width", "rr_batch_reference_obs_supported", "rr_batch_set_pose_termination", "rr_batch_pose_termination_supported", "rr_batch_set_body_tracking", "rr_batch_body_tracking_supported", "rr_batch_set_clip_restarts", "rr_batch_clip_restarts_supported", "rr_batch_set_velocity_tracking", "rr_batch_velocity_tracking_supported", "rr_batch_set_clip_library", "rr_batch_clip_library_supported", "rr_batch_set_clip_sampling", "rr_batch_clip_sampling_supported", "rr_batch_set_reference_restart", "rr_batch_reference_restart_supported", "rr_wrap_clip_restart", "rr_wrap_clip_library", "rr_wrap_clip_sampling",
            "rr_compute_gae", "rr_mlp_forward", "rr_ppo_loss_workspace_bytes", "rr_ppo_loss", "rr_policy_act_workspace_bytes", "rr_policy_act", "rr_policy_sample", "rr_policy_backward_workspace_bytes", "rr_policy_backward", "rr_mlp_silu_backward_workspace_bytes", "rr_mlp_silu_backward", "rr_mlp_value_backward_workspace_bytes", "rr_mlp_policy_backward", "rr_mlp_policy_backward_workspace_bytes", "rr_mlp_value_backward", "rr_mlp_weight_grad_workspace_bytes", "rr_mlp_weight_grad", "rr_mlp_weight_grad_batch_workspace_bytes", "rr_mlp_weight_grad_batch", "rr_obs_moments_workspace_bytes", "rr_obs_moments", "rr_wrap_episode_autoreset", "rr_debug_layout", "rr_batch_set_schedule", "rr_batch_set_env_params", "rr_batch_env_params_supported", "rr_batch_set_profile", "rr_batch_set_ls_repeat_exit", "rr_batch_set_solver_trim", "rr_batch_set_solver_batch", "rr_batch_set_solve_resident", "rr_model_solve_resident_switch", "rr_batch_set_root_slot", "rr_model_root_slot_switch", "rr_batch_set_timing", "rr_batch_kernel_time", "rr_last_error"]
 
 _lib = None
@@ -226,6 +232,8 @@ def lib():
         L.rr_wrap_clip_library.argtypes = L.rr_wrap_clip_restart.argtypes[:-1] + [C.c_void_p] * 4      # ... clip, bank_clips, clip_lengths, stream
         L.rr_batch_set_clip_sampling.argtypes = [C.c_void_p, C.POINTER(RRClipSamplingIO)]
         L.rr_batch_clip_sampling_supported.argtypes = [C.c_void_p, C.c_int32]
+        L.rr_batch_set_reference_restart.argtypes = [C.c_void_p, C.POINTER(RRReferenceRestartIO)]
+        L.rr_batch_reference_restart_supported.argtypes = [C.c_void_p, C.c_int32]
         # ... clip, bank_clips, clip_lengths, num_clips, pose_fail, sampling, stream
         L.rr_wrap_clip_sampling.argtypes = L.rr_wrap_clip_restart.argtypes[:-1] + [C.c_void_p] * 3 + [C.c_int32, C.c_void_p, C.POINTER(RRClipSamplingIO), C.c_void_p]
         L.rr_batch_set_ls_repeat_exit.argtypes = [C.c_void_p, C.c_int32]
@@ -346,6 +354,7 @@ class Batch:
         self._vel = None            # the tensors of the velocity-tracking block in force (set_velocity_tracking)
         self._library = None        # the tensors of the clip-library block in force (set_clip_library)
         self._sampling = None       # the tensors of the clip-sampling block in force (set_clip_sampling)
+        self._refrestart = None     # the tensors of the reference-restart block in force (set_reference_restart)
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream().cuda_stream
         _check(lib().rr_batch_create(model.h, self.N, self.device.index or 0, C.c_void_p(stream), C.byref(self.h)))
@@ -413,6 +422,7 @@ class Batch:
         arguments out of the dict (the setters say what each entry is) -- in dependency order: termination, body tracking, velocity tracking
         and clip restarts each need the pose block, the clip library (`clip_library` key) the pose block and, for its bank clips, the
         clip-restart block, clip sampling (`clip_sampling` key) the clip-restart block and, for its weights, the library's bank clips,
+        reference restarts (`reference_restart` key) the pose and clip-restart blocks,
         and the library keeps a block while one that needs it stands.  So the blocks absent from the
         dict are cleared last to first, then the present ones are set first to last.  (Clearing the pose block is refused while the
         batch carries reference frames: their launches all carry `track_pose`.)"""
@@ -435,11 +445,16 @@ class Batch:
                                                                                env["clip_library"].get("clip_out"), 1 if len(lead) == 1 else lead[0])),
                   ("clip_sampling", "_sampling", self.set_clip_sampling, lambda: (env["clip_sampling"].get("weights"), env["clip_sampling"].get("draws_in"),
                                                                                  env["clip_sampling"].get("draws_out"), env["clip_sampling"].get("outcomes"),
-                                                                                 env["clip_sampling"].get("seed", 0), 1 if len(lead) == 1 else lead[0])))
+                                                                                 env["clip_sampling"].get("seed", 0), 1 if len(lead) == 1 else lead[0])),
+                  ("reference_restart", "_refrestart", self.set_reference_restart, lambda: (env["reference_restart"]["draws_in"], env["reference_restart"]["draws_out"],
+                                                                                           env["reference_restart"].get("weights"), env["reference_restart"].get("seed", 0),
+                                                                                           env["reference_restart"].get("frame_range", (0, 100)),
+                                                                                           env["reference_restart"].get("across_clips", False),
+                                                                                           env["reference_restart"].get("noise_scale", 0.0), 1 if len(lead) == 1 else lead[0])))
         for key, attr, setter, _ in reversed(blocks):
             # (the clip library and clip sampling are always set afresh: the bank clips of an earlier launch would keep the restart block
             # from being cleared, the weights the bank clips)
-            if (env.get(key) is None or key in ("clip_library", "clip_sampling")) and getattr(self, attr) is not None:
+            if (env.get(key) is None or key in ("clip_library", "clip_sampling", "reference_restart")) and getattr(self, attr) is not None:
                 setter(None)
         for key, _, setter, args in blocks:
             if env.get(key) is not None:
@@ -689,6 +704,27 @@ class Batch:
             t = RRClipSamplingIO(_ptr(weights, torch.int32), _ptr(draws_in, torch.int32, self.N), _ptr(draws_out, torch.int32, self.N),
                                  _ptr(outcomes, torch.int64), int(seed) & 0xFFFFFFFF)
         self._set_block("_sampling", lib().rr_batch_set_clip_sampling, t, (weights, draws_in, draws_out, outcomes))
+
+    def set_reference_restart(self, draws_in: Optional[torch.Tensor], draws_out: Optional[torch.Tensor] = None, weights: Optional[torch.Tensor] = None,
+                              seed: int = 0, frame_range=(0, 100), across_clips: bool = False, noise_scale: float = 0.0, num_clips: Optional[int] = None):
+        """The reference-restart block of this batch's later multi-step launches (C ABI `rr_batch_set_reference_restart`): a restore reads
+        no bank entry but draws a clip (`across_clips`; by `weights` int32 [C] or, None, uniformly) and a start frame in `frame_range`,
+        builds the start state from the clip's rows plus `noise_scale` noise and forms its observation in the launch (`seed` the draws'
+        seed).  `draws_in` / `draws_out` int32 [N]: each env's restore count before and after the launch; `draws_in` None clears the
+        block.  Needs the pose and clip-restart blocks.  The env-io dict of a launch (`reference_restart` key) sets or clears it by
+        itself.  The batch keeps the tensors alive."""
+        t = None
+        if draws_in is not None:
+            if weights is not None and (weights.dim() != 1 or (num_clips is not None and weights.shape[0] != num_clips)):
+                raise ValueError(f"reference restarts: weights has shape {tuple(weights.shape)}, expected [{'C' if num_clips is None else num_clips}]")
+            t = RRReferenceRestartIO(_ptr(weights, torch.int32), _ptr(draws_in, torch.int32, self.N), _ptr(draws_out, torch.int32, self.N),
+                                     int(seed) & 0xFFFFFFFF, int(frame_range[0]), int(frame_range[1]), int(bool(across_clips)), float(noise_scale), 0)
+        self._set_block("_refrestart", lib().rr_batch_set_reference_restart, t, (weights, draws_in, draws_out))
+
+    def reference_restart_supported(self, with_actor: bool = False) -> Optional[str]:
+        """None when this batch's multi-step launches serve reference restarts at its frame count (C ABI
+        `rr_batch_reference_restart_supported`) -- with `with_actor` the one-launch rollout with the actor inside -- else the refusal's text."""
+        return self._refusal(lib().rr_batch_reference_restart_supported, int(with_actor))
 
     def clip_sampling_supported(self, with_actor: bool = False) -> Optional[str]:
         """None when this batch serves clip sampling at its frame count (C ABI `rr_batch_clip_sampling_supported`) -- with `with_actor`

@@ -84,6 +84,10 @@ def main():
                     "of comparing it with the clamped last row (the clip must be longer than every start frame: the synthetic line has 250 frames)")
     ap.add_argument("--restart-across-clips", action="store_true", help="with --clip-restarts and several clips: every start state of the bank has a "
                     "clip of its own, so a restarted episode may move to another clip (Rodent(restart_across_clips=True))")
+    ap.add_argument("--restart-from-reference", action="store_true", help="with --clip-restarts K >= 1 (1 suffices): a restarted episode starts from a "
+                    "freshly drawn clip and frame -- the clip's pose (and velocities) plus noise -- instead of one of its K stored start states, "
+                    "so a run starts episodes all over the library (Rodent(reset_to_reference=True, restart_from_reference=True))")
+    ap.add_argument("--restart-noise-seed", type=int, default=0, metavar="S", help="with --restart-from-reference: the seed of its draws")
     ap.add_argument("--clip-outcomes", action="store_true", help="with --clip-restarts and several clips: count per clip the wrapped steps, the ended "
                     "episodes and why they ended (Rodent(clip_outcomes=True)); reported as training/clip_fail_rate, training/clip_truncated_share "
                     "and, up to 16 clips, training/clip_fail_rate_clip{c}")
@@ -153,6 +157,8 @@ def main():
         ap.error("--weighted-restarts: needs --restart-across-clips (the weights are those of the bank entries' clips)")
     if args.clip_outcomes and args.clip_restarts < 1:
         ap.error("--clip-outcomes: needs --clip-restarts K >= 1")
+    if args.restart_from_reference and args.clip_restarts < 1:
+        ap.error("--restart-from-reference: needs --clip-restarts K >= 1 (and with it --track-pose)")
     clip_lengths = args.clip_lengths
     clips = None                                     # the loaded ReferenceClip(s), [C, T, ...] fields; None for a .npy track or the synthetic line
     if args.clip and os.path.exists(args.clip) and not args.clip.endswith(".npy"):
@@ -220,6 +226,7 @@ def main():
         restart_frame_range=None if args.restart_frames is None else tuple(args.restart_frames), end_at_clip_end=args.end_at_clip_end,
         clip_lengths=None if clip_lengths is None else np.asarray(clip_lengths, dtype=np.int32), restart_across_clips=args.restart_across_clips,
         restart_sampling="weighted" if args.weighted_restarts else None, clip_outcomes=args.clip_outcomes or args.weighted_restarts,
+        reset_to_reference=args.restart_from_reference, restart_from_reference=args.restart_from_reference, restart_noise_seed=args.restart_noise_seed,
         **pose)     # a clip too short for --end-at-clip-end is refused here with the reason (ValueError)
 
     train_fn = functools.partial(

@@ -497,6 +497,38 @@ typedef struct rr_clip_sampling_io {
 int rr_batch_set_clip_sampling(rr_batch* b, const rr_clip_sampling_io* sampling);
 int rr_batch_clip_sampling_supported(const rr_batch* b, int32_t with_actor);
 
+/* Reference restarts: a restore of rr_env_unroll / rr_env_unroll_policy that reads NO bank entry but draws a clip and a start frame,
+ * builds the start state from the clip's rows plus noise and forms its observation by a forward-only pass inside the launch (what
+ * rr_env_reset computes for that state, not counted as a step).  Set on the BATCH next to the pose and clip-restart blocks it needs,
+ * like the blocks above; NULL clears it.  Integer hashing only, no float transcendental.  With n = draws_in[env] before the restore
+ * (it grows by one per restore and goes to draws_out[env] after the launch's last step; these replace the clip-sampling block's pair),
+ *   base = fmix32(fmix32(seed ^ (uint32(env) * 0x9E3779B1)) + n);   h(p, i) = fmix32(base ^ (((p << 16) | i) * 0x9E3779B1))   (mod 2^32)
+ *   clip:   across_clips and clip ids given: over all num_clips clips -- with clip_weights of sum S > 0 the smallest c with
+ *           q_0 + .. + q_c > (uint64(h(1, 0)) * S) >> 32 (a clip of weight 0 is never drawn), else (uint64(h(1, 0)) * num_clips) >> 32;
+ *           otherwise the clip the env is on.  num_clips <= 65536.
+ *   frame:  d = frame_lo + ((uint64(h(2, 0)) * (frame_hi - frame_lo)) >> 32);  f = d mod (L_c - 1) with per-clip lengths (clip library),
+ *           else d;  the rows are read at clamp(f, 0, L_c - 1): none at or behind the clip's end.
+ *   state:  qpos = [track_pos[c][f], track_pose[c][f]], qvel = track_vel[c][f] with a velocity block, else 0; to element i of qpos is added
+ *           noise_scale * s(h(3, i)), to element i of qvel noise_scale * s(h(4, i)), s(h) = (h >> 8) * 2^-23 - 1 (exact in float32), one
+ *           rounded product and one rounded sum.  act = 0, qacc_warmstart = 0 going into the pass.  cur_frame <- f, clip <- c (clip_out
+ *           of the clip library).  The slot advances cyclically and selects nothing; the bank's arrays are not read.
+ * rr_batch_set_reference_restart: no pose block or no clip-restart block on the batch, NULL draws_in / draws_out or the two aliased,
+ * frame_lo < 0 or frame_hi <= frame_lo, a noise_scale that is negative or not finite: RR_EINVAL; RR_EUNSUPPORTED with the reason where
+ * there is no restart instance (as rr_batch_set_clip_restarts).  The launches run the restart instances; single steps ignore the block
+ * (the per-step wrappers restore through rr_env_reset).  rr_batch_reference_restart_supported(b, with_actor): 1 / 0 as for the others. */
+typedef struct rr_reference_restart_io {
+  const int32_t* clip_weights;  /* [C], 0 .. 65535, or NULL: the uniform draw */
+  const int32_t* draws_in;      /* [N] restores of each env so far */
+  int32_t* draws_out;           /* [N] out */
+  uint32_t seed;
+  int32_t frame_lo, frame_hi;   /* frames are drawn in [frame_lo, frame_hi) */
+  int32_t across_clips;         /* != 0: a restore draws its clip over the whole library */
+  float noise_scale;
+  int32_t pad;
+} rr_reference_restart_io;
+int rr_batch_set_reference_restart(rr_batch* b, const rr_reference_restart_io* r);
+int rr_batch_reference_restart_supported(const rr_batch* b, int32_t with_actor);
+
 /* Generalised advantage estimation of one PPO minibatch, the reverse scan of brax.training.agents.ppo.losses.compute_gae
  * [UP; SURVEY.md Appendix E], one thread per trajectory.  All arrays time-major [T][B] device float32; bootstrap [B];
  * outputs vs [T][B] and advantages [T][B].  `stream` is a hipStream_t (NULL = default stream). */

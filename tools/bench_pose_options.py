@@ -15,15 +15,18 @@ alternating in one process on one GPU.  No gate: it reports.
                      (T, 2T/3, T/3) and `restart_across_clips`
   --option sampling  that `clip_restarts` 8 env on three copies of the clip with `restart_across_clips` | the same with
                      `restart_sampling="weighted"` (weights 1, 2, 5) and `clip_outcomes`
+  --option reference_restart  that `clip_restarts` 8, `restart_across_clips` env with `reset_to_reference` on three copies of the clip |
+                     the same with `clip_restarts` 1 and `restart_from_reference`: every restore draws a clip and a frame, builds its
+                     state and runs the reset's forward pass in the launch; the episode-end rate of the timed side is reported
 
 All envs: rodent_optimized.xml, CG 8/8, n_frames 10, --num-envs envs through Episode(150) + AutoReset in multi-step launches, tracking a
 synthetic reference pose (identity quaternion, qpos0's joints) with the default weights and scales.  Default: random actions through
-`rr_env_unroll`, --unroll env steps per launch -- the workload of bench.py config 2.  --actor (poseterm, body, velocity, restart, library, sampling): the one-launch
+`rr_env_unroll`, --unroll env steps per launch -- the workload of bench.py config 2.  --actor (poseterm, body, velocity, restart, library, sampling, reference_restart): the one-launch
 rollout with the actor inside (`rr_env_unroll_policy`, a 4 x 32 policy, one segment of --unroll steps per launch).  After two warm-up
 launches per side, each repeat times --launches launches per side, in the order above, with a host clock around a device synchronise;
 the medians, the per-repeat values, the ranges and the ratios against the first side are printed as one JSON line.
 
-usage: python tools/bench_pose_options.py --option {pose,refobs,poseterm,body,velocity,restart,library,sampling} [--actor] [--frames 5] [--num-envs 2048]
+usage: python tools/bench_pose_options.py --option {pose,refobs,poseterm,body,velocity,restart,library,sampling,reference_restart} [--actor] [--frames 5] [--num-envs 2048]
                                           [--unroll 50] [--launches 4] [--repeats 7] [--out FILE]"""
 import argparse
 import json
@@ -65,7 +68,11 @@ def options(frames: int, bodies: Callable, velocity: dict, T: int = 250) -> dict
     body = dict(track_bodies=bodies, end_effector_ids=END_EFFECTORS)
     k8 = dict(max_pos_error=1e9, clip_restarts=8)
     across = dict(k8, restart_across_clips=True)
+    ref8 = dict(across, reset_to_reference=True)
     return {
+        "reference_restart": Option((("across", ref8), ("reference", dict(ref8, clip_restarts=1, restart_from_reference=True))), True, True,
+                                    lambda st: _alive(st) and int(st.info["restart_draws"].max()) >= 1 and 0 <= int(st.info["clip"].min())
+                                    and int(st.info["clip"].max()) <= 2, clips=3),
         "sampling": Option((("across", across), ("sampling", dict(across, restart_sampling="weighted", clip_outcomes=True))), True, True,
                            lambda st: _alive(st) and int(st.info["restart_slot"].max()) <= 7 and int(st.info["restart_draws"].max()) >= 1,
                            clips=3),
@@ -89,7 +96,7 @@ def options(frames: int, bodies: Callable, velocity: dict, T: int = 250) -> dict
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--option", required=True, choices=("pose", "refobs", "poseterm", "body", "velocity", "restart", "library", "sampling"))
+    ap.add_argument("--option", required=True, choices=("pose", "refobs", "poseterm", "body", "velocity", "restart", "library", "sampling", "reference_restart"))
     ap.add_argument("--actor", action="store_true")
     ap.add_argument("--frames", type=int, default=5)
     ap.add_argument("--num-envs", type=int, default=2048)
@@ -112,7 +119,7 @@ def main():
     velocity = dict(track_velocity=qvel[:, :3], track_angular_velocity=qvel[:, 3:6], track_joint_velocity=qvel[:, 6:])
     opt = options(args.frames, lambda env: preprocessing.extract_features(env, qpos).body_positions, velocity, T)[args.option]
     if args.actor and not opt.actor:
-        ap.error(f"--actor: --option {args.option} has no such mode (poseterm, body, velocity, restart, library and sampling have)")
+        ap.error(f"--actor: --option {args.option} has no such mode (poseterm, body, velocity, restart, library, sampling and reference_restart have)")
     if opt.clips:      # the same clip `clips` times over
         track, quat, joints = (np.stack([np.asarray(a)] * opt.clips) for a in (track, quat, joints))
     dev = torch.device("cuda:0")
@@ -184,6 +191,9 @@ def main():
         table = sides["sampling"]["env"].clip_outcomes()
         assert table[:, 4].sum() == N * U * (2 + args.repeats * args.launches) and (table[:, 1:4].sum(1) == table[:, 0]).all(), table
         res["outcomes"] = table.tolist()
+    if args.option == "reference_restart":      # restores of the timed side per wrapped env step, warm-up launches included
+        steps = N * U * (2 + args.repeats * args.launches)
+        res["episode_ends_per_env_step"] = round(float(sides["reference"]["state"].info["restart_draws"].sum()) / steps, 6)
     if opt.identical and (not args.actor or opt.identical_with_actor):
         key, name = opt.identical
         res[key] = bool(torch.equal(sides[name]["state"].pipeline_state.qpos, sides[first]["state"].pipeline_state.qpos))
