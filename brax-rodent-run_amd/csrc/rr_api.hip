@@ -1365,6 +1365,51 @@ extern "C" int rr_obs_moments(const float* obs, int64_t nseq, int32_t Tp1, int32
   return RR_OK;
 }
 
+// ------------------------------------------------------------------------------------------ Adam behind a global-norm clip
+extern "C" int32_t rr_clipped_adam_partials(int64_t n) {
+  if (n <= 0) return 0;
+  const int64_t k = (n + RR_ADAM_PART_ELEMS - 1) / RR_ADAM_PART_ELEMS;
+  return (int32_t)(k < RR_ADAM_MAX_PARTIALS ? k : RR_ADAM_MAX_PARTIALS);
+}
+extern "C" size_t rr_clipped_adam_workspace_bytes(int64_t n) { return (size_t)rr_clipped_adam_partials(n) * sizeof(double); }
+extern "C" int rr_clipped_adam_step(const rr_adam_tensor* table, int32_t ntensors, const float* grad_flat, float* m_flat, float* v_flat, int64_t n,
+                                    const double* cfg_dev, double* state_dev, void* workspace, void* stream) {
+  if (ntensors > RR_ADAM_MAX_TENSORS) return fail(RR_EINVAL, "rr_clipped_adam_step: more than 64 tensors");
+  if (!table || ntensors <= 0 || !grad_flat || !m_flat || !v_flat || !cfg_dev || !state_dev || !workspace || n <= 0)
+    return fail(RR_EINVAL, "rr_clipped_adam_step: bad argument");
+  if ((((uintptr_t)grad_flat | (uintptr_t)m_flat | (uintptr_t)v_flat) & 15) || (((uintptr_t)cfg_dev | (uintptr_t)state_dev | (uintptr_t)workspace) & 7))
+    return fail(RR_EINVAL, "rr_clipped_adam_step: the flat buffers must be 16-byte aligned, cfg / state / workspace 8-byte aligned");
+  RRAdamTable T;
+  memset(&T, 0, sizeof(T));
+  int64_t sum = 0, blocks = 0;
+  for (int k = 0; k < ntensors; ++k) {           // the segments tile [0, n) in table order: every access of the flat buffers is in range
+    const rr_adam_tensor& e = table[k];
+    if (!e.param || ((uintptr_t)e.param & 3)) return fail(RR_EINVAL, "rr_clipped_adam_step: null or misaligned parameter pointer in the table");
+    if (e.numel <= 0 || e.offset != sum || e.numel > n - sum)
+      return fail(RR_EINVAL, "rr_clipped_adam_step: the table's segments must follow each other from offset 0 and sum to n");
+    T.t[k].p = e.param; T.t[k].off = e.offset; T.t[k].numel = e.numel;
+    int64_t head = (4 - (e.offset & 3)) & 3;
+    if (head > e.numel) head = e.numel;
+    const int64_t nb = (e.numel - head) >> 2, nblk = nb ? (nb + 255) / 256 : 1;
+    T.first_block[k] = (int)blocks;
+    blocks += nblk;
+    if (blocks > INT_MAX) return fail(RR_EINVAL, "rr_clipped_adam_step: too many elements");
+    sum += e.numel;
+  }
+  if (sum != n) return fail(RR_EINVAL, "rr_clipped_adam_step: n differs from the sum of the table's element counts");
+  for (int k = ntensors; k <= RR_ADAM_MAX_TENSORS; ++k) T.first_block[k] = (int)blocks;
+  T.ntensors = ntensors;
+  const int nparts = rr_clipped_adam_partials(n);
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(rr_adam_sumsq_kernel, dim3(nparts), dim3(256), 0, st, grad_flat, (long long)n, (double*)workspace);
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(rr_adam_finalize_kernel, dim3(1), dim3(64), 0, st, (const double*)workspace, nparts, cfg_dev, state_dev);
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(rr_adam_apply_kernel, dim3((unsigned)blocks), dim3(256), 0, st, T, grad_flat, m_flat, v_flat, cfg_dev, (const double*)state_dev);
+  HIPCHK(hipGetLastError());
+  return RR_OK;
+}
+
 // ------------------------------------------------------------------------------------------ training wrappers, fused
 // brax.envs.wrappers.training: EpisodeWrapper (step count, truncation, done at episode end) followed by AutoResetWrapper
 // (restore the stored first state where done) -- ~15 elementwise launches per env step when composed from tensor ops;

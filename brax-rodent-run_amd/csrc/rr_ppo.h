@@ -458,3 +458,129 @@ __global__ __launch_bounds__(256) void rr_obs_moments_reduce_kernel(const RRMomA
   for (int b = 0; b < A.nblk; ++b) s += A.part[(size_t)b * 2 * A.K + e];
   A.out[e] = s;
 }
+
+// ------------------------------------------------------------------------------------------ Adam behind a global-norm clip
+// optax.chain(clip_by_global_norm(max_grad_norm), adam(lr)) [UP brax.training.agents.ppo.train, max_grad_norm] on the flat gradient buffer,
+// with an update whose norm is not finite SKIPPED (an extension: optax would carry the NaN into the moments).  Three launches:
+//   A1 rr_adam_sumsq_kernel     per-block partial sums of g^2 in double (grid-stride over float4, wave shuffles, LDS across the four waves);
+//                               the block count is a function of n alone (rr_adam_partials), every thread's elements and the order of
+//                               every addition are fixed by n: no atomics, nothing depends on timing
+//   A2 rr_adam_finalize_kernel  one wave adds the partials (lane l takes partials l, l + 64, ... in index order, then the shuffle tree),
+//                               lane 0 forms norm, s, the skip flag, t + 1, 1 - b^t (double) and updates the statistics with plain stores
+//   A3 rr_adam_apply_kernel     the update, one block per 1024-element chunk of a tensor
+// Three, not two: A3's blocks all READ t, s and the skip flag, so the one thread that WRITES them has to have finished before any of them
+// starts -- a launch boundary is the only ordering between blocks that costs no atomic and no spinning.  Folding A2 into A1 (last block
+// done) would need a ticket counter and a fence for the sake of ~2 us per update.
+// t, the hyper-parameters and the statistics live in device memory (doubles), so a captured graph replays the step as it stands; the tensor
+// table never changes and travels in the kernel arguments (read with scalar loads, block-uniform index).
+#define RR_ADAM_MAX_TENSORS 64
+#define RR_ADAM_MAX_PARTIALS 1024
+#define RR_ADAM_PART_ELEMS 4096          // elements per partial until the cap: 256 threads x 4 float4
+#define RR_ADAM_CHUNK 1024               // elements per block of A3: 256 threads x 1 float4
+// cfg [8] doubles: lr, b1, b2, eps, max_grad_norm.   state [16] doubles (include/rodent_rr.h):
+enum { RR_ADAM_T = 0, RR_ADAM_NORM = 1, RR_ADAM_SCALE = 2, RR_ADAM_SKIP = 3, RR_ADAM_BC1 = 4, RR_ADAM_BC2 = 5,
+       RR_ADAM_NORM_SUM = 8, RR_ADAM_NORM_MAX = 9, RR_ADAM_APPLIED = 10, RR_ADAM_CLIPPED = 11, RR_ADAM_SKIPPED = 12 };
+
+struct RRAdamTensor { float* p; long long off; long long numel; };
+struct RRAdamTable {
+  RRAdamTensor t[RR_ADAM_MAX_TENSORS];
+  int first_block[RR_ADAM_MAX_TENSORS + 1];      // A3: tensor k owns blocks first_block[k] .. first_block[k + 1] - 1
+  int ntensors;
+};
+
+// g: 16-byte aligned; n4 = n / 4 float4 groups, the n % 4 last elements go to the first threads of block 0
+__global__ __launch_bounds__(256) void rr_adam_sumsq_kernel(const float* __restrict__ g, long long n, double* __restrict__ part) {
+  __shared__ double sh[4];
+  const long long n4 = n >> 2;
+  const float4* g4 = (const float4*)g;
+  double s[1] = {0.0};
+  for (long long j = (long long)blockIdx.x * 256 + threadIdx.x; j < n4; j += (long long)gridDim.x * 256) {
+    const float4 x = g4[j];
+    s[0] += ((double)x.x * (double)x.x + (double)x.y * (double)x.y) + ((double)x.z * (double)x.z + (double)x.w * (double)x.w);
+  }
+  if (blockIdx.x == 0 && (long long)threadIdx.x < n - 4 * n4) { const double x = (double)g[4 * n4 + threadIdx.x]; s[0] += x * x; }
+  rr_block_sum<1>(s, sh, part + blockIdx.x, 0);
+}
+
+__global__ __launch_bounds__(64) void rr_adam_finalize_kernel(const double* __restrict__ part, int nparts, const double* __restrict__ cfg,
+                                                              double* state) {
+  double s = 0.0;
+  for (int k = threadIdx.x; k < nparts; k += 64) s += part[k];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  if (threadIdx.x != 0) return;
+  const float norm = (float)sqrt(s);                      // rounded to float32 once
+  state[RR_ADAM_NORM] = (double)norm;
+  if (!(fabsf(norm) <= 3.402823466e38f)) {                // NaN or inf: some element is not finite.  Nothing else moves
+    state[RR_ADAM_SKIP] = 1.0;
+    state[RR_ADAM_SKIPPED] += 1.0;
+    return;
+  }
+  const float mx = (float)cfg[4];
+  const float sc = norm > mx ? mx / norm : 1.0f;
+  const double t = state[RR_ADAM_T] + 1.0;
+  state[RR_ADAM_T] = t;
+  state[RR_ADAM_SCALE] = (double)sc;
+  state[RR_ADAM_SKIP] = 0.0;
+  state[RR_ADAM_BC1] = (double)(float)(1.0 - pow(cfg[1], t));
+  state[RR_ADAM_BC2] = (double)(float)(1.0 - pow(cfg[2], t));
+  state[RR_ADAM_NORM_SUM] += (double)norm;
+  state[RR_ADAM_NORM_MAX] = fmax(state[RR_ADAM_NORM_MAX], (double)norm);
+  state[RR_ADAM_APPLIED] += 1.0;
+  if (sc < 1.0f) state[RR_ADAM_CLIPPED] += 1.0;
+}
+
+struct RRAdamCoef { float sc, b1, omb1, b2, omb2, bc1, bc2, lr, eps; bool clip; };
+static __device__ __forceinline__ void rr_adam_elem(const RRAdamCoef& c, float g, float& m, float& v, float& p) {
+  const float gh = c.clip ? c.sc * g : g;                 // at or below the threshold: the gradient itself
+  m = c.b1 * m + c.omb1 * gh;
+  v = c.b2 * v + c.omb2 * (gh * gh);
+  p -= c.lr * (m / c.bc1) / (sqrtf(v / c.bc2) + c.eps);
+}
+
+// One block per RR_ADAM_CHUNK elements of a tensor's BODY.  A tensor's segment of the flat buffers starts at element `off`: its first
+// (4 - off % 4) % 4 elements (head) and what is left behind the last whole float4 (tail) are scalar work of the tensor's first block; the
+// body between them is float4 work on g, m, v -- and on p where the parameter's address is congruent (p + head 16-byte aligned: always for
+// separately allocated tensors whose offset is a multiple of 4), else four scalar accesses to p.
+__global__ __launch_bounds__(256) void rr_adam_apply_kernel(const RRAdamTable T, const float* __restrict__ g, float* __restrict__ mf,
+                                                            float* __restrict__ vf, const double* __restrict__ cfg,
+                                                            const double* __restrict__ state) {
+  if (state[RR_ADAM_SKIP] != 0.0) return;
+  int k = 0;
+  while (k + 1 < T.ntensors && (int)blockIdx.x >= T.first_block[k + 1]) ++k;       // block-uniform: scalar loads of the kernel arguments
+  const int chunk = blockIdx.x - T.first_block[k];
+  float* p = T.t[k].p;
+  const long long off = T.t[k].off, numel = T.t[k].numel;
+  RRAdamCoef c;
+  c.sc = (float)state[RR_ADAM_SCALE]; c.clip = c.sc < 1.0f;
+  c.b1 = (float)cfg[1]; c.omb1 = (float)(1.0 - cfg[1]); c.b2 = (float)cfg[2]; c.omb2 = (float)(1.0 - cfg[2]);
+  c.bc1 = (float)state[RR_ADAM_BC1]; c.bc2 = (float)state[RR_ADAM_BC2]; c.lr = (float)cfg[0]; c.eps = (float)cfg[3];
+  long long head = (4 - (off & 3)) & 3;
+  if (head > numel) head = numel;
+  const long long nb = (numel - head) >> 2, tail = numel - head - 4 * nb;
+  if (chunk == 0) {                                        // head: threads 0 .. head-1, tail: threads 4 .. 4 + tail-1
+    long long e = -1;
+    if ((long long)threadIdx.x < head) e = threadIdx.x;
+    else if (threadIdx.x >= 4 && (long long)threadIdx.x - 4 < tail) e = head + 4 * nb + (threadIdx.x - 4);
+    if (e >= 0) {
+      float m = mf[off + e], v = vf[off + e], pp = p[e];
+      rr_adam_elem(c, g[off + e], m, v, pp);
+      mf[off + e] = m; vf[off + e] = v; p[e] = pp;
+    }
+  }
+  const long long j = (long long)chunk * 256 + threadIdx.x;         // float4 group of the body
+  if (j >= nb) return;
+  const long long f = off + head + 4 * j, e = head + 4 * j;           // f % 4 == 0
+  const float4 g4 = *(const float4*)(g + f);
+  float4 m4 = *(float4*)(mf + f), v4 = *(float4*)(vf + f), p4;
+  const bool pal = (((uintptr_t)(p + head)) & 15) == 0;               // block-uniform
+  if (pal) p4 = *(float4*)(p + e);
+  else { p4.x = p[e]; p4.y = p[e + 1]; p4.z = p[e + 2]; p4.w = p[e + 3]; }
+  rr_adam_elem(c, g4.x, m4.x, v4.x, p4.x);
+  rr_adam_elem(c, g4.y, m4.y, v4.y, p4.y);
+  rr_adam_elem(c, g4.z, m4.z, v4.z, p4.z);
+  rr_adam_elem(c, g4.w, m4.w, v4.w, p4.w);
+  *(float4*)(mf + f) = m4; *(float4*)(vf + f) = v4;
+  if (pal) *(float4*)(p + e) = p4;
+  else { p[e] = p4.x; p[e + 1] = p4.y; p[e + 2] = p4.z; p[e + 3] = p4.w; }
+}

@@ -119,6 +119,10 @@ class RRDwItem(C.Structure):
         [("M", C.c_int32), ("O", C.c_int32), ("I", C.c_int32), ("grad", C.c_void_p)]
 
 
+class RRAdamTensor(C.Structure):
+    _fields_ = [("param", C.c_void_p), ("offset", C.c_int64), ("numel", C.c_int64)]
+
+
 class RRPpoCfg(C.Structure):
     _fields_ = [(n, C.c_float) for n in ("entropy_cost", "discounting", "reward_scaling", "gae_lambda", "clipping_epsilon", "min_std")] + \
         [("normalize_advantage", C.c_int32)]
@@ -126,7 +130,7 @@ class RRPpoCfg(C.Structure):
 
 EXPORTS = ["rr_model_load", "rr_model_dims", "rr_model_set_solver", "rr_model_set_solver_type", "rr_model_destroy", "rr_model_table", "rr_kernarg_layout", "rr_batch_create",
            "rr_batch_destroy", "rr_pipeline_init", "rr_pipeline_step", "rr_env_step", "rr_env_reset", "rr_pipeline_step_to", "rr_env_step_to", "rr_batch_contact_overflow", "rr_batch_bad_states", "rr_batch_unroll_supported", "rr_env_unroll", "rr_env_unroll_policy", "rr_batch_eval_supported", "rr_env_unroll_eval", "rr_batch_pose_supported", "rr_batch_set_pose", "rr_batch_set_reference_obs", "rr_batch_obs_width", "rr_batch_reference_obs_supported", "rr_batch_set_pose_termination", "rr_batch_pose_termination_supported", "rr_batch_set_body_tracking", "rr_batch_body_tracking_supported", "rr_batch_set_clip_restarts", "rr_batch_clip_restarts_supported", "rr_batch_set_velocity_tracking", "rr_batch_velocity_tracking_supported", "rr_batch_set_clip_library", "rr_batch_clip_library_supported", "rr_batch_set_clip_sampling", "rr_batch_clip_sampling_supported", "rr_batch_set_reference_restart", "rr_batch_reference_restart_supported", "rr_wrap_clip_restart", "rr_wrap_clip_library", "rr_wrap_clip_sampling",
-           "rr_compute_gae", "rr_mlp_forward", "rr_ppo_loss_workspace_bytes", "rr_ppo_loss", "rr_policy_act_workspace_bytes", "rr_policy_act", "rr_policy_sample", "rr_policy_backward_workspace_bytes", "rr_policy_backward", "rr_mlp_silu_backward_workspace_bytes", "rr_mlp_silu_backward", "rr_mlp_value_backward_workspace_bytes", "rr_mlp_policy_backward", "rr_mlp_policy_backward_workspace_bytes", "rr_mlp_value_backward", "rr_mlp_weight_grad_workspace_bytes", "rr_mlp_weight_grad", "rr_mlp_weight_grad_batch_workspace_bytes", "rr_mlp_weight_grad_batch", "rr_obs_moments_workspace_bytes", "rr_obs_moments", "rr_wrap_episode_autoreset", "rr_debug_layout", "rr_batch_set_schedule", "rr_batch_set_env_params", "rr_batch_env_params_supported", "rr_batch_set_profile", "rr_batch_set_ls_repeat_exit", "rr_batch_set_solver_trim", "rr_batch_set_solver_batch", "rr_batch_set_solve_resident", "rr_model_solve_resident_switch", "rr_batch_set_root_slot", "rr_model_root_slot_switch", "rr_batch_set_timing", "rr_batch_kernel_time", "rr_last_error"]
+           "rr_compute_gae", "rr_mlp_forward", "rr_ppo_loss_workspace_bytes", "rr_ppo_loss", "rr_policy_act_workspace_bytes", "rr_policy_act", "rr_policy_sample", "rr_policy_backward_workspace_bytes", "rr_policy_backward", "rr_mlp_silu_backward_workspace_bytes", "rr_mlp_silu_backward", "rr_mlp_value_backward_workspace_bytes", "rr_mlp_policy_backward", "rr_mlp_policy_backward_workspace_bytes", "rr_mlp_value_backward", "rr_mlp_weight_grad_workspace_bytes", "rr_mlp_weight_grad", "rr_mlp_weight_grad_batch_workspace_bytes", "rr_mlp_weight_grad_batch", "rr_obs_moments_workspace_bytes", "rr_obs_moments", "rr_clipped_adam_workspace_bytes", "rr_clipped_adam_partials", "rr_clipped_adam_step", "rr_wrap_episode_autoreset", "rr_debug_layout", "rr_batch_set_schedule", "rr_batch_set_env_params", "rr_batch_env_params_supported", "rr_batch_set_profile", "rr_batch_set_ls_repeat_exit", "rr_batch_set_solver_trim", "rr_batch_set_solver_batch", "rr_batch_set_solve_resident", "rr_model_solve_resident_switch", "rr_batch_set_root_slot", "rr_model_root_slot_switch", "rr_batch_set_timing", "rr_batch_kernel_time", "rr_last_error"]
 
 _lib = None
 
@@ -207,6 +211,11 @@ def lib():
         L.rr_obs_moments_workspace_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int32]
         L.rr_obs_moments_workspace_bytes.restype = C.c_size_t
         L.rr_obs_moments.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.rr_clipped_adam_workspace_bytes.argtypes = [C.c_int64]
+        L.rr_clipped_adam_workspace_bytes.restype = C.c_size_t
+        L.rr_clipped_adam_partials.argtypes = [C.c_int64]
+        L.rr_clipped_adam_step.argtypes = [C.POINTER(RRAdamTensor), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p]
         L.rr_batch_set_profile.argtypes = [C.c_void_p, C.c_void_p]
         L.rr_batch_set_schedule.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.rr_batch_set_env_params.argtypes = [C.c_void_p, C.POINTER(RREnvParams)]
@@ -1105,6 +1114,39 @@ def obs_moments(obs, T: int, mean, bufs=None):
     _check(lib().rr_obs_moments(obs.data_ptr(), nseq, Tp1, T, K, mean.data_ptr(), sums.data_ptr(), ws.data_ptr(), ws.numel() * 8,
                                 C.c_void_p(torch.cuda.current_stream(obs.device).cuda_stream)))
     return sums
+
+
+def clipped_adam_partials(n: int) -> int:
+    """Partial sums the norm of an n-element gradient is formed from (C ABI `rr_clipped_adam_partials`): a function of n alone."""
+    return _check(lib().rr_clipped_adam_partials(int(n)))
+
+
+class ClippedAdamBuffers:
+    """Everything one `rr_clipped_adam_step` reads besides the tensors, kept by the caller so that a captured HIP graph sees the same
+    addresses for the life of the object: `cfg` (device float64 [8]: lr, b1, b2, eps, max_grad_norm), `state` (device float64 [16]: t, the
+    last norm / scale / skip flag / bias corrections and the counters; `training.optim` names the slots), the workspace of the partial sums
+    and the tensor table.  `params`: contiguous float32 device tensors in the order of their segments of `grad_flat`; `m_flat` / `v_flat`:
+    the moments, laid out as the gradient is.  `step()` launches on the current stream."""
+
+    def __init__(self, params, grad_flat, m_flat, v_flat, *, lr, b1, b2, eps, max_grad_norm, n=None):
+        self.params, self.grad, self.m, self.v = list(params), grad_flat, m_flat, v_flat
+        dev = grad_flat.device
+        self.n = int(grad_flat.numel() if n is None else n)
+        for t in (grad_flat, m_flat, v_flat):
+            _ptr(t)
+        self.table = (RRAdamTensor * max(len(self.params), 1))()
+        off = 0
+        for k, p in enumerate(self.params):
+            self.table[k] = RRAdamTensor(_ptr(p), off, p.numel())
+            off += p.numel()
+        self.cfg = torch.tensor([lr, b1, b2, eps, max_grad_norm, 0.0, 0.0, 0.0], dtype=torch.float64, device=dev)
+        self.state = torch.zeros(16, dtype=torch.float64, device=dev)
+        self.workspace = torch.empty(max(lib().rr_clipped_adam_workspace_bytes(self.n) // 8, 1), dtype=torch.float64, device=dev)
+
+    def step(self):
+        _check(lib().rr_clipped_adam_step(self.table, len(self.params), self.grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.n,
+                                          self.cfg.data_ptr(), self.state.data_ptr(), self.workspace.data_ptr(),
+                                          C.c_void_p(torch.cuda.current_stream(self.grad.device).cuda_stream)))
 
 
 def policy_sample(logits, noise, min_std: float):

@@ -22,7 +22,7 @@ import torch
 
 from .... import jax_random
 from ....envs import wrappers
-from ... import acting, distributed as D, fused_mlp, networks as ppo_networks_mod, running_statistics
+from ... import acting, distributed as D, fused_mlp, networks as ppo_networks_mod, optim, running_statistics
 from ...types import PPONetworkParams, TrainingState
 from . import losses as ppo_losses
 
@@ -79,6 +79,7 @@ def train(
     timing_fn: Optional[Callable] = None,
     return_training_state: bool = False,
     clip_weight_fn: Optional[Callable] = None,
+    max_grad_norm: Optional[float] = None,
 ):
     """PPO training.  Returns (make_policy, params=(normalizer_params, policy_params), metrics).
 
@@ -93,7 +94,18 @@ def train(
     clips, `training/clip_fail_rate_clip{c}`.  The function is called with that step's int64 [C, 5] table on every rank; a result
     other than None goes to `set_clip_weights` of every training batch (`envs.rodent.FailureWeights` is one such function).  The eval
     env keeps its uniform weights.
+    `max_grad_norm` (upstream's argument of that name; default None = no clipping, the optimiser and the captured graphs of a build
+    without the option): a number > 0 (`inf` allowed, anything else raises ValueError) puts `optax.clip_by_global_norm` in front of Adam
+    (`training.optim.ClippedAdam`, three HIP launches per minibatch update): the all-reduced gradient of BOTH networks is scaled by
+    max_grad_norm / norm where its global norm (squares summed in float64, rounded to float32 once) exceeds max_grad_norm, and used as
+    it is otherwise.  EXTENSION over optax: an update whose norm is not finite (some gradient element is NaN or +-inf) is skipped --
+    parameters, both moments and Adam's step count keep their bits -- instead of turning every parameter into NaN for the rest of the
+    run; the learner's counterpart of the env's `bad_state_max`.  Reported per training step, read and cleared after its closing
+    synchronisation: `training/grad_norm` (mean pre-clip norm over the applied updates), `training/grad_norm_max`,
+    `training/grad_clip_share` (applied updates that were scaled), `training/skipped_updates` (one warning the first time it is not 0).
     """
+    if max_grad_norm is not None:
+        max_grad_norm = optim.check_max_grad_norm(max_grad_norm)
     assert batch_size * num_minibatches % num_envs == 0
     xt = time.time()
     process_count, process_id = D.world_size(), D.rank()
@@ -163,8 +175,12 @@ def train(
     # puts a collective inside the loss: that mode runs eagerly.)
     use_graph = (device.type == "cuda" and os.environ.get("RR_PPO_GRAPH", "1") == "1"
                  and not (global_advantage_normalization and process_count > 1))
-    optimizer = torch.optim.Adam(params, lr=learning_rate, betas=(0.9, 0.999), eps=1e-8, fused=(device.type == "cuda"),
-                                 capturable=use_graph)
+    if max_grad_norm is None:
+        optimizer = torch.optim.Adam(params, lr=learning_rate, betas=(0.9, 0.999), eps=1e-8, fused=(device.type == "cuda"),
+                                     capturable=use_graph)
+    else:                                                # clip_by_global_norm -> adam, non-finite updates skipped: rr_clipped_adam_step
+        optimizer = optim.ClippedAdam(params, flat, lr=learning_rate, max_grad_norm=max_grad_norm, betas=(0.9, 0.999), eps=1e-8)
+    clip_stats = {"warned": False}
     normalizer_params = running_statistics.init_state(env.observation_size, device)
     normalize = running_statistics.normalize if normalize_observations else (lambda x, y: x)
     make_policy = ppo_networks_mod.make_inference_fn(ppo_network)
@@ -405,6 +421,15 @@ def train(
                               "(training/bad_state_resets counts them)", RuntimeWarning, stacklevel=2)
         if outcome_envs:
             clip_outcome_metrics(out)
+        if max_grad_norm is not None:                    # the optimiser's device block: read and cleared here, after the closing synchronisation
+            st = optimizer.stats(clear=True)
+            for k in ("grad_norm", "grad_norm_max", "grad_clip_share", "skipped_updates"):
+                out[f"training/{k}"] = float(st[k])
+            if st["skipped_updates"] and not clip_stats["warned"]:
+                clip_stats["warned"] = True
+                warnings.warn(f"ppo.train: {st['skipped_updates']} of {st['skipped_updates'] + st['applied_updates']} minibatch updates of this "
+                              "training step had a gradient with a non-finite element and were skipped: parameters and optimiser state kept "
+                              "(training/skipped_updates counts them)", RuntimeWarning, stacklevel=2)
         return out
 
     metrics = {}

@@ -16,7 +16,8 @@ class PPONetworkParams:
 @dataclasses.dataclass
 class TrainingState:
     """Contains training state for the learner."""
-    optimizer_state: Any             # torch.optim.Adam (optax.adam(lr): b1 .9, b2 .999, eps 1e-8)
+    optimizer_state: Any             # torch.optim.Adam (optax.adam(lr): b1 .9, b2 .999, eps 1e-8); with ppo.train(max_grad_norm=...)
+                                     # training.optim.ClippedAdam (clip_by_global_norm in front of it); both have a non-empty .state
     params: PPONetworkParams
     normalizer_params: Any           # running_statistics.RunningStatisticsState
     env_steps: torch.Tensor          # int64 scalar, += env_steps_per_training_step per training step (upstream: int32)

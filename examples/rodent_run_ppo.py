@@ -112,7 +112,11 @@ def main():
                     "widths run on the hand-written learner kernels (256: per-step rollouts, the in-kernel actor is 32-wide)")
     ap.add_argument("--policy-depth", type=int, default=4, help="hidden layers of the policy network (1 .. 7 for the hand-written kernels; "
                     "the one-launch rollout of the 32-wide policy takes 1 .. 4)")
+    ap.add_argument("--max-grad-norm", type=float, default=None, metavar="X", help="clip every minibatch gradient to global norm X before Adam and "
+                    "skip updates whose gradient is not finite (ppo.train(max_grad_norm=X); inf: only the skip); default: no clipping")
     args = ap.parse_args()
+    if args.max_grad_norm is not None and not args.max_grad_norm > 0:
+        ap.error("--max-grad-norm: a number > 0 (inf allowed)")
     if args.track_velocity and not args.track_pose:      # (before any device is touched)
         ap.error("--track-velocity: the velocities are indexed like the reference pose; add --track-pose")
 
@@ -236,6 +240,7 @@ def main():
         learning_rate=config["learning_rate"], entropy_cost=1e-3, num_envs=config["num_envs"],
         batch_size=config["batch_size"], seed=0, max_training_steps=args.max_training_steps,
         randomization_fn=domain_randomize if args.randomize else None,
+        max_grad_norm=args.max_grad_norm,
         clip_weight_fn=envs.rodent.FailureWeights(floor=args.weight_floor, decay=args.weight_decay) if args.weighted_restarts else None,
         network_factory=functools.partial(networks.make_ppo_networks, policy_hidden_layer_sizes=(args.policy_width,) * args.policy_depth))
 

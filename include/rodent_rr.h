@@ -680,6 +680,34 @@ size_t rr_obs_moments_workspace_bytes(int64_t nseq, int32_t T, int32_t K);
 int rr_obs_moments(const float* obs, int64_t nseq, int32_t Tp1, int32_t T, int32_t K, const float* mean, double* sums, void* workspace,
                    size_t workspace_bytes, void* stream);
 
+/* One optimiser step of optax.chain(optax.clip_by_global_norm(max_grad_norm), optax.adam(lr)) [UP brax.training.agents.ppo.train,
+ * `max_grad_norm`] on a flat gradient buffer, three launches, with an update whose norm is not finite skipped (an extension over optax):
+ *   norm = float32(sqrt(sum_i g_i^2)), the squares summed in double in an order that depends on n alone (no atomics);
+ *   norm not finite: nothing but state[1], state[3] = 1 and state[12] += 1 is written;
+ *   s = norm <= max_grad_norm ? 1 : max_grad_norm / norm;  g^ = g where s = 1, else s * g;  t += 1;
+ *   m = b1 m + (1 - b1) g^;  v = b2 v + (1 - b2) g^^2;  p -= lr (m / (1 - b1^t)) / (sqrt(v / (1 - b2^t)) + eps).
+ * table: HOST array of `ntensors` (<= 64) entries, the parameter tensors (device float32) in the order of their segments of the flat
+ *   buffers: offset[0] = 0, offset[k + 1] = offset[k] + numel[k], sum of numel = n.  It is checked on the host and travels in the kernel
+ *   arguments, so a captured graph keeps it; the parameters stay where they are.
+ * grad_flat / m_flat / v_flat: device float32 [n], 16-byte aligned; the moments are laid out as the gradient is.
+ * cfg_dev: device double [8]: lr, b1, b2, eps, max_grad_norm (inf: never clip), 3 unused.
+ * state_dev: device double [16], zero before the first step: [0] t, [1] norm of the last step (pre-clip, float32 value), [2] its s,
+ *   [3] 1 if it was skipped, [4] 1 - b1^t, [5] 1 - b2^t (float32 values); statistics since the caller last cleared them: [8] sum of the
+ *   applied updates' norms, [9] their largest, [10] applied updates, [11] those with s < 1, [12] skipped updates.  Everything a replay
+ *   of a captured graph must see lives here and in cfg_dev, not in the call's arguments.
+ * workspace: rr_clipped_adam_workspace_bytes(n) bytes of device memory, 8-byte aligned (the partial sums).
+ * rr_clipped_adam_partials(n): how many partial sums the norm of n elements is formed from (a function of n alone; 0 for n <= 0).
+ * RR_EINVAL: more than 64 tensors, a null pointer, misaligned buffers, segments that do not follow each other, n different from their sum. */
+typedef struct {
+  float* param;
+  int64_t offset;      /* of the tensor's segment in the flat buffers, in elements */
+  int64_t numel;
+} rr_adam_tensor;
+size_t rr_clipped_adam_workspace_bytes(int64_t n);
+int32_t rr_clipped_adam_partials(int64_t n);
+int rr_clipped_adam_step(const rr_adam_tensor* table, int32_t ntensors, const float* grad_flat, float* m_flat, float* v_flat, int64_t n,
+                         const double* cfg_dev, double* state_dev, void* workspace, void* stream);
+
 /* brax.envs.wrappers.training.EpisodeWrapper + AutoResetWrapper [UP; SURVEY.md 3.4] after an env step, in one launch:
  * steps' = (prev_done ? 0 : prev_steps) + action_repeat; over = steps' >= episode_length; done <- over ? 1 : done;
  * truncation = over ? 1 - done_env : 0; and for every env with done != 0 the rows of the `narr` (<= 12) arrays `cur[i]`
