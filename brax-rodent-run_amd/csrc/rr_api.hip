@@ -928,15 +928,25 @@ extern "C" size_t rr_ppo_loss_workspace_bytes(int32_t T, int32_t B) {
   ppo_blocks(T, B, &n1, &n2);
   return rr_align_up((size_t)2 * T * B * sizeof(float), 8) + ((size_t)2 * n1 + (size_t)3 * n2) * sizeof(double);
 }
-extern "C" int rr_ppo_loss(const float* policy_logits, const float* values, const float* raw_action, const float* log_prob, const float* reward,
+extern "C" size_t rr_ppo_loss_diag_workspace_bytes(int32_t T, int32_t B) {
+  if (T <= 0 || B <= 0) return 0;
+  int n1, n2;
+  ppo_blocks(T, B, &n1, &n2);
+  return rr_ppo_loss_workspace_bytes(T, B) + (size_t)5 * n2 * sizeof(double);
+}
+// diag != NULL: the DIAG instances of the loss and metrics kernels (rr_ppo_loss_diag)
+static int ppo_loss_launch(const float* policy_logits, const float* values, const float* raw_action, const float* log_prob, const float* reward,
                            const float* discount, const float* truncation, const int64_t* idx, const float* noise, int32_t T, int32_t B, int32_t A,
-                           const rr_ppo_cfg* cfg, float* grad_logits, float* grad_values, float* metrics, void* workspace, size_t workspace_bytes,
-                           void* stream) {
+                           const rr_ppo_cfg* cfg, float* grad_logits, float* grad_values, float* metrics, double* diag, float* kl_out,
+                           void* workspace, size_t workspace_bytes, void* stream) {
+  const std::string who = diag ? "rr_ppo_loss_diag" : "rr_ppo_loss";                         // the entry the caller used, for its error text
   if (!policy_logits || !values || !raw_action || !log_prob || !reward || !discount || !truncation || !noise || !cfg || !grad_logits ||
       !grad_values || !metrics || !workspace || T <= 0 || B <= 0 || A <= 0)
-    return fail(RR_EINVAL, "rr_ppo_loss: bad argument");
-  if (workspace_bytes < rr_ppo_loss_workspace_bytes(T, B) || ((uintptr_t)workspace & 7))
-    return fail(RR_EINVAL, "rr_ppo_loss: workspace too small (rr_ppo_loss_workspace_bytes) or not 8-byte aligned");
+    return fail(RR_EINVAL, who + ": bad argument");
+  if (workspace_bytes < (diag ? rr_ppo_loss_diag_workspace_bytes(T, B) : rr_ppo_loss_workspace_bytes(T, B)) || ((uintptr_t)workspace & 7))
+    return fail(RR_EINVAL, who + ": workspace too small (rr_ppo_loss_workspace_bytes / rr_ppo_loss_diag_workspace_bytes) or not 8-byte aligned");
+  if (diag && (((uintptr_t)diag & 7) || ((uintptr_t)kl_out & 3)))
+    return fail(RR_EINVAL, "rr_ppo_loss_diag: diag must be 8-byte aligned, kl_out 4-byte aligned");
   RRPpoArgs P;
   memset(&P, 0, sizeof(P));
   P.logits = policy_logits; P.values = values; P.raw_action = raw_action; P.log_prob = log_prob; P.reward = reward; P.discount = discount;
@@ -949,12 +959,33 @@ extern "C" int rr_ppo_loss(const float* policy_logits, const float* values, cons
   P.vs = (float*)w; P.adv = P.vs + (size_t)T * B;
   P.part_adv = (double*)(w + rr_align_up((size_t)2 * T * B * sizeof(float), 8));
   P.part_loss = P.part_adv + 2 * P.nblk1;
+  if (diag) { P.part_diag = P.part_loss + 3 * P.nblk2; P.diag = diag; P.kl_out = kl_out; }
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(rr_ppo_gae_kernel, dim3(P.nblk1), dim3(256), 0, st, P);
-  hipLaunchKernelGGL(rr_ppo_loss_kernel, dim3(P.nblk2), dim3(256), 0, st, P);
-  hipLaunchKernelGGL(rr_ppo_metrics_kernel, dim3(1), dim3(64), 0, st, P);
+  if (diag) {
+    hipLaunchKernelGGL(rr_ppo_loss_kernel<true>, dim3(P.nblk2), dim3(256), 0, st, P);
+    hipLaunchKernelGGL(rr_ppo_metrics_kernel<true>, dim3(1), dim3(64), 0, st, P);
+  } else {
+    hipLaunchKernelGGL(rr_ppo_loss_kernel<false>, dim3(P.nblk2), dim3(256), 0, st, P);
+    hipLaunchKernelGGL(rr_ppo_metrics_kernel<false>, dim3(1), dim3(64), 0, st, P);
+  }
   HIPCHK(hipGetLastError());
   return RR_OK;
+}
+extern "C" int rr_ppo_loss(const float* policy_logits, const float* values, const float* raw_action, const float* log_prob, const float* reward,
+                           const float* discount, const float* truncation, const int64_t* idx, const float* noise, int32_t T, int32_t B, int32_t A,
+                           const rr_ppo_cfg* cfg, float* grad_logits, float* grad_values, float* metrics, void* workspace, size_t workspace_bytes,
+                           void* stream) {
+  return ppo_loss_launch(policy_logits, values, raw_action, log_prob, reward, discount, truncation, idx, noise, T, B, A, cfg, grad_logits,
+                         grad_values, metrics, nullptr, nullptr, workspace, workspace_bytes, stream);
+}
+extern "C" int rr_ppo_loss_diag(const float* policy_logits, const float* values, const float* raw_action, const float* log_prob,
+                                const float* reward, const float* discount, const float* truncation, const int64_t* idx, const float* noise,
+                                int32_t T, int32_t B, int32_t A, const rr_ppo_cfg* cfg, float* grad_logits, float* grad_values, float* metrics,
+                                double* diag, float* kl_out, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!diag) return fail(RR_EINVAL, "rr_ppo_loss_diag: diag is NULL");
+  return ppo_loss_launch(policy_logits, values, raw_action, log_prob, reward, discount, truncation, idx, noise, T, B, A, cfg, grad_logits,
+                         grad_values, metrics, diag, kl_out, workspace, workspace_bytes, stream);
 }
 
 extern "C" int rr_policy_sample(const float* logits, const float* noise, int32_t N, int32_t A, float min_std, float* action, float* raw_action,
@@ -1372,42 +1403,61 @@ extern "C" int32_t rr_clipped_adam_partials(int64_t n) {
   return (int32_t)(k < RR_ADAM_MAX_PARTIALS ? k : RR_ADAM_MAX_PARTIALS);
 }
 extern "C" size_t rr_clipped_adam_workspace_bytes(int64_t n) { return (size_t)rr_clipped_adam_partials(n) * sizeof(double); }
-extern "C" int rr_clipped_adam_step(const rr_adam_tensor* table, int32_t ntensors, const float* grad_flat, float* m_flat, float* v_flat, int64_t n,
-                                    const double* cfg_dev, double* state_dev, void* workspace, void* stream) {
-  if (ntensors > RR_ADAM_MAX_TENSORS) return fail(RR_EINVAL, "rr_clipped_adam_step: more than 64 tensors");
+// kl_dev != NULL: the KL instance of the finalisation (rr_clipped_adam_step_kl), which writes cfg_dev[0]
+static int clipped_adam_launch(const rr_adam_tensor* table, int32_t ntensors, const float* grad_flat, float* m_flat, float* v_flat, int64_t n,
+                               double* cfg_dev, double* state_dev, const float* kl_dev, const double* klcfg_dev, void* workspace, void* stream) {
+  const std::string who = kl_dev ? "rr_clipped_adam_step_kl" : "rr_clipped_adam_step";       // the entry the caller used, for its error text
+  if (ntensors > RR_ADAM_MAX_TENSORS) return fail(RR_EINVAL, who + ": more than 64 tensors");
   if (!table || ntensors <= 0 || !grad_flat || !m_flat || !v_flat || !cfg_dev || !state_dev || !workspace || n <= 0)
-    return fail(RR_EINVAL, "rr_clipped_adam_step: bad argument");
+    return fail(RR_EINVAL, who + ": bad argument");
   if ((((uintptr_t)grad_flat | (uintptr_t)m_flat | (uintptr_t)v_flat) & 15) || (((uintptr_t)cfg_dev | (uintptr_t)state_dev | (uintptr_t)workspace) & 7))
-    return fail(RR_EINVAL, "rr_clipped_adam_step: the flat buffers must be 16-byte aligned, cfg / state / workspace 8-byte aligned");
+    return fail(RR_EINVAL, who + ": the flat buffers must be 16-byte aligned, cfg / state / workspace 8-byte aligned");
   RRAdamTable T;
   memset(&T, 0, sizeof(T));
   int64_t sum = 0, blocks = 0;
   for (int k = 0; k < ntensors; ++k) {           // the segments tile [0, n) in table order: every access of the flat buffers is in range
     const rr_adam_tensor& e = table[k];
-    if (!e.param || ((uintptr_t)e.param & 3)) return fail(RR_EINVAL, "rr_clipped_adam_step: null or misaligned parameter pointer in the table");
+    if (!e.param || ((uintptr_t)e.param & 3)) return fail(RR_EINVAL, who + ": null or misaligned parameter pointer in the table");
     if (e.numel <= 0 || e.offset != sum || e.numel > n - sum)
-      return fail(RR_EINVAL, "rr_clipped_adam_step: the table's segments must follow each other from offset 0 and sum to n");
+      return fail(RR_EINVAL, who + ": the table's segments must follow each other from offset 0 and sum to n");
     T.t[k].p = e.param; T.t[k].off = e.offset; T.t[k].numel = e.numel;
     int64_t head = (4 - (e.offset & 3)) & 3;
     if (head > e.numel) head = e.numel;
     const int64_t nb = (e.numel - head) >> 2, nblk = nb ? (nb + 255) / 256 : 1;
     T.first_block[k] = (int)blocks;
     blocks += nblk;
-    if (blocks > INT_MAX) return fail(RR_EINVAL, "rr_clipped_adam_step: too many elements");
+    if (blocks > INT_MAX) return fail(RR_EINVAL, who + ": too many elements");
     sum += e.numel;
   }
-  if (sum != n) return fail(RR_EINVAL, "rr_clipped_adam_step: n differs from the sum of the table's element counts");
+  if (sum != n) return fail(RR_EINVAL, who + ": n differs from the sum of the table's element counts");
   for (int k = ntensors; k <= RR_ADAM_MAX_TENSORS; ++k) T.first_block[k] = (int)blocks;
   T.ntensors = ntensors;
   const int nparts = rr_clipped_adam_partials(n);
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(rr_adam_sumsq_kernel, dim3(nparts), dim3(256), 0, st, grad_flat, (long long)n, (double*)workspace);
   HIPCHK(hipGetLastError());
-  hipLaunchKernelGGL(rr_adam_finalize_kernel, dim3(1), dim3(64), 0, st, (const double*)workspace, nparts, cfg_dev, state_dev);
+  if (kl_dev)
+    hipLaunchKernelGGL(rr_adam_finalize_kernel<true>, dim3(1), dim3(64), 0, st, (const double*)workspace, nparts, cfg_dev, state_dev, kl_dev, klcfg_dev);
+  else
+    hipLaunchKernelGGL(rr_adam_finalize_kernel<false>, dim3(1), dim3(64), 0, st, (const double*)workspace, nparts, (const double*)cfg_dev, state_dev,
+                       (const float*)nullptr, (const double*)nullptr);
   HIPCHK(hipGetLastError());
-  hipLaunchKernelGGL(rr_adam_apply_kernel, dim3((unsigned)blocks), dim3(256), 0, st, T, grad_flat, m_flat, v_flat, cfg_dev, (const double*)state_dev);
+  hipLaunchKernelGGL(rr_adam_apply_kernel, dim3((unsigned)blocks), dim3(256), 0, st, T, grad_flat, m_flat, v_flat, (const double*)cfg_dev,
+                     (const double*)state_dev);
   HIPCHK(hipGetLastError());
   return RR_OK;
+}
+extern "C" int rr_clipped_adam_step(const rr_adam_tensor* table, int32_t ntensors, const float* grad_flat, float* m_flat, float* v_flat, int64_t n,
+                                    const double* cfg_dev, double* state_dev, void* workspace, void* stream) {
+  return clipped_adam_launch(table, ntensors, grad_flat, m_flat, v_flat, n, const_cast<double*>(cfg_dev), state_dev, nullptr, nullptr, workspace,
+                             stream);
+}
+extern "C" int rr_clipped_adam_step_kl(const rr_adam_tensor* table, int32_t ntensors, const float* grad_flat, float* m_flat, float* v_flat,
+                                       int64_t n, double* cfg_dev, double* state_dev, const float* kl_dev, const double* klcfg_dev,
+                                       void* workspace, void* stream) {
+  if (!kl_dev || !klcfg_dev || ((uintptr_t)kl_dev & 3) || ((uintptr_t)klcfg_dev & 7))
+    return fail(RR_EINVAL, "rr_clipped_adam_step_kl: kl_dev (4-byte aligned) and klcfg_dev (8-byte aligned) must be given");
+  return clipped_adam_launch(table, ntensors, grad_flat, m_flat, v_flat, n, cfg_dev, state_dev, kl_dev, klcfg_dev, workspace, stream);
 }
 
 // ------------------------------------------------------------------------------------------ training wrappers, fused

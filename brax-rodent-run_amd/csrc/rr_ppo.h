@@ -9,6 +9,10 @@
 //   K2 rr_ppo_loss_kernel   32 lanes per sample (one action dimension per lane, coalesced rows): log-prob, entropy, the three
 //                           loss terms (block sums, double) and the gradient rows
 //   K3 rr_ppo_metrics_kernel  the four scalars of the metrics dict
+// K2 and K3 are templates on DIAG.  The DIAG instances (rr_ppo_loss_diag) add five block sums of their own -- the k3 KL term, the clipped
+// samples, vs, vs^2, vs - v -- and K3 turns them into approx_kl, clip_fraction, explained_variance and entropy of the minibatch, adds them
+// to the training step's accumulators (one thread, plain stores) and writes the KL as float32 where the optimiser step reads it.  Gradients
+// and the four metrics are formed by the same instructions in both instances.
 // No atomics: every reduction is a fixed tree over per-block partial sums, so a replayed HIP graph reproduces the eager result
 // bit for bit.  The minibatch is addressed THROUGH the permutation (`idx`), so the five gathered copies of the batch leaves
 // (raw_action, log_prob, reward, discount, truncation) are never made.
@@ -36,7 +40,13 @@ struct RRPpoArgs {
   double* part_adv;              // [2 * nblk1]
   double* part_loss;             // [3 * nblk2]
   int nblk1, nblk2;
+  // DIAG instances only (include/rodent_rr.h, rr_ppo_loss_diag)
+  double* part_diag;             // [5 * nblk2]: sum of expm1(d) - d, clipped samples, sum vs, sum vs^2, sum (vs - v)
+  double* diag;                  // [16]: the minibatch's four figures and the training step's accumulators
+  float* kl_out;                 // the minibatch's approx_kl rounded to float32 once (nullable)
 };
+enum { RR_DIAG_KL = 0, RR_DIAG_CLIP = 1, RR_DIAG_EV = 2, RR_DIAG_ENT = 3,
+       RR_DIAG_COUNT = 8, RR_DIAG_KL_SUM = 9, RR_DIAG_KL_MAX = 10, RR_DIAG_CLIP_SUM = 11, RR_DIAG_EV_SUM = 12, RR_DIAG_ENT_SUM = 13 };
 
 template <int N>
 static __device__ __forceinline__ void rr_block_sum(double (&v)[N], double* sh /* [N * 4] */, double* out, int stride) {
@@ -85,6 +95,7 @@ __global__ __launch_bounds__(256) void rr_ppo_gae_kernel(const RRPpoArgs P) {
   rr_block_sum<2>(s, sh, P.part_adv + blockIdx.x, P.nblk1);
 }
 
+template <bool DIAG>
 __global__ __launch_bounds__(256) void rr_ppo_loss_kernel(const RRPpoArgs P) {
   __shared__ double sh[12];
   __shared__ float s_stat[2];
@@ -107,6 +118,7 @@ __global__ __launch_bounds__(256) void rr_ppo_loss_kernel(const RRPpoArgs P) {
   const int P2 = 2 * A;
   const float invn = 1.0f / (float)n;
   double acc[3] = {0.0, 0.0, 0.0};
+  double dg[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
   // bootstrap rows: no gradient
   for (int i = blockIdx.x * 256 + threadIdx.x; i < B * P2; i += gridDim.x * 256) P.grad_logits[(size_t)n * P2 + i] = 0.0f;
   for (int i = blockIdx.x * 256 + threadIdx.x; i < B; i += gridDim.x * 256) P.grad_values[n + i] = 0.0f;
@@ -137,6 +149,12 @@ __global__ __launch_bounds__(256) void rr_ppo_loss_kernel(const RRPpoArgs P) {
     if (lane == 0) {
       acc[0] += (double)fminf(s1, s2); acc[1] += (double)ve * (double)ve; acc[2] += (double)ent;
       P.grad_values[smp] = -0.5f * invn * ve;              // d (0.25 mean(ve^2)) / d v
+      if constexpr (DIAG) {
+        // k3 estimator of KL(behaviour || current): the term in double from the float32 d -- in float32 (rho - 1) - d keeps no digit
+        // at the d ~ 1e-3 of early training
+        const double d = (double)(lp - P.log_prob[row]), vsd = (double)P.vs[smp];
+        dg[0] += expm1(d) - d; dg[1] += (double)(1.0f - inr); dg[2] += vsd; dg[3] += vsd * vsd; dg[4] += (double)ve;
+      }
     }
     // pass 2: gradient rows
     for (int a = lane; a < A; a += 32) {
@@ -151,10 +169,25 @@ __global__ __launch_bounds__(256) void rr_ppo_loss_kernel(const RRPpoArgs P) {
     }
   }
   rr_block_sum<3>(acc, sh, P.part_loss + blockIdx.x, P.nblk2);
+  if constexpr (DIAG) {
+    __shared__ double shd[20];
+    rr_block_sum<5>(dg, shd, P.part_diag + blockIdx.x, P.nblk2);
+  }
 }
 
+template <bool DIAG>
 __global__ __launch_bounds__(64) void rr_ppo_metrics_kernel(const RRPpoArgs P) {
   double s[3] = {0.0, 0.0, 0.0};
+  double g[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+  if constexpr (DIAG) {
+    for (int k = threadIdx.x; k < P.nblk2; k += 64)
+#pragma unroll
+      for (int j = 0; j < 5; ++j) g[j] += P.part_diag[j * P.nblk2 + k];
+#pragma unroll
+    for (int j = 0; j < 5; ++j)
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) g[j] += __shfl_xor(g[j], o, 64);
+  }
   for (int k = threadIdx.x; k < P.nblk2; k += 64)
 #pragma unroll
     for (int j = 0; j < 3; ++j) s[j] += P.part_loss[j * P.nblk2 + k];
@@ -166,6 +199,17 @@ __global__ __launch_bounds__(64) void rr_ppo_metrics_kernel(const RRPpoArgs P) {
     const double n = (double)P.T * P.B;
     const float pl = (float)(-s[0] / n), vl = (float)(0.25 * s[1] / n), el = (float)(-(double)P.entropy_cost * s[2] / n);
     P.metrics[0] = pl + vl + el; P.metrics[1] = pl; P.metrics[2] = vl; P.metrics[3] = el;
+    if constexpr (DIAG) {
+      // population variances from the double sums; explained variance is 0 where the returns do not vary
+      const double kl = g[0] / n, cf = g[1] / n, ent = s[2] / n;
+      const double mvs = g[2] / n, vvs = fmax(g[3] / n - mvs * mvs, 0.0), mve = g[4] / n, vve = fmax(s[1] / n - mve * mve, 0.0);
+      const double ev = vvs > 0.0 ? 1.0 - vve / vvs : 0.0;
+      double* D = P.diag;
+      D[RR_DIAG_KL] = kl; D[RR_DIAG_CLIP] = cf; D[RR_DIAG_EV] = ev; D[RR_DIAG_ENT] = ent;
+      D[RR_DIAG_COUNT] += 1.0; D[RR_DIAG_KL_SUM] += kl; D[RR_DIAG_KL_MAX] = fmax(D[RR_DIAG_KL_MAX], kl);
+      D[RR_DIAG_CLIP_SUM] += cf; D[RR_DIAG_EV_SUM] += ev; D[RR_DIAG_ENT_SUM] += ent;
+      if (P.kl_out) *P.kl_out = (float)kl;                 // the optimiser step's input, rounded to float32 once
+    }
   }
 }
 
@@ -468,6 +512,10 @@ __global__ __launch_bounds__(256) void rr_obs_moments_reduce_kernel(const RRMomA
 //   A2 rr_adam_finalize_kernel  one wave adds the partials (lane l takes partials l, l + 64, ... in index order, then the shuffle tree),
 //                               lane 0 forms norm, s, the skip flag, t + 1, 1 - b^t (double) and updates the statistics with plain stores
 //   A3 rr_adam_apply_kernel     the update, one block per 1024-element chunk of a tensor
+// The KL instance of A2 (rr_clipped_adam_step_kl) decides two more things before the norm, from the minibatch's approx_kl (a float32 in
+// device memory, identical on every rank after the all-reduce) and a block of four settings, restating training/optim.py kl_control_rule:
+// the sticky stop of target_kl (flag set: nothing but the stop counter moves; A3's blocks return on the skip flag, which a stop sets too)
+// and the KL-adaptive learning rate, written in double to cfg[0] before A3 reads it.
 // Three, not two: A3's blocks all READ t, s and the skip flag, so the one thread that WRITES them has to have finished before any of them
 // starts -- a launch boundary is the only ordering between blocks that costs no atomic and no spinning.  Folding A2 into A1 (last block
 // done) would need a ticket counter and a fence for the sake of ~2 us per update.
@@ -479,6 +527,7 @@ __global__ __launch_bounds__(256) void rr_obs_moments_reduce_kernel(const RRMomA
 #define RR_ADAM_CHUNK 1024               // elements per block of A3: 256 threads x 1 float4
 // cfg [8] doubles: lr, b1, b2, eps, max_grad_norm.   state [16] doubles (include/rodent_rr.h):
 enum { RR_ADAM_T = 0, RR_ADAM_NORM = 1, RR_ADAM_SCALE = 2, RR_ADAM_SKIP = 3, RR_ADAM_BC1 = 4, RR_ADAM_BC2 = 5,
+       RR_ADAM_STOP = 6, RR_ADAM_KL = 7, RR_ADAM_STOPPED = 13,      // the KL instance's: sticky stop flag, last KL, stopped updates
        RR_ADAM_NORM_SUM = 8, RR_ADAM_NORM_MAX = 9, RR_ADAM_APPLIED = 10, RR_ADAM_CLIPPED = 11, RR_ADAM_SKIPPED = 12 };
 
 struct RRAdamTensor { float* p; long long off; long long numel; };
@@ -502,19 +551,46 @@ __global__ __launch_bounds__(256) void rr_adam_sumsq_kernel(const float* __restr
   rr_block_sum<1>(s, sh, part + blockIdx.x, 0);
 }
 
-__global__ __launch_bounds__(64) void rr_adam_finalize_kernel(const double* __restrict__ part, int nparts, const double* __restrict__ cfg,
-                                                              double* state) {
+// klcfg [4] doubles: stop threshold (1.5 target_kl), desired_kl, lr_lo, lr_hi; 0 = that control is off
+// the plain instance only reads cfg, so it may assume that nothing it writes aliases it; the KL instance writes cfg[0]
+template <bool KL> struct RRAdamCfgPtr { typedef const double* __restrict__ type; };
+template <> struct RRAdamCfgPtr<true> { typedef double* type; };
+template <bool KL>
+__global__ __launch_bounds__(64) void rr_adam_finalize_kernel(const double* __restrict__ part, int nparts, typename RRAdamCfgPtr<KL>::type cfg,
+                                                              double* state, const float* klp, const double* klcfg) {
+  if constexpr (KL) {
+    if (state[RR_ADAM_STOP] != 0.0) {                       // stopped earlier in this training step: before anything else
+      if (threadIdx.x == 0) { state[RR_ADAM_STOPPED] += 1.0; state[RR_ADAM_SKIP] = 1.0; }
+      return;
+    }
+  }
   double s = 0.0;
   for (int k = threadIdx.x; k < nparts; k += 64) s += part[k];
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
   if (threadIdx.x != 0) return;
+  double kl = 0.0;
+  if constexpr (KL) {
+    kl = (double)*klp;
+    state[RR_ADAM_KL] = kl;
+    if (klcfg[0] > 0.0 && !(kl <= klcfg[0])) {              // also a NaN KL: a stop, not a non-finite skip
+      state[RR_ADAM_STOP] = 1.0; state[RR_ADAM_SKIP] = 1.0; state[RR_ADAM_STOPPED] += 1.0;
+      return;
+    }
+  }
   const float norm = (float)sqrt(s);                      // rounded to float32 once
   state[RR_ADAM_NORM] = (double)norm;
   if (!(fabsf(norm) <= 3.402823466e38f)) {                // NaN or inf: some element is not finite.  Nothing else moves
     state[RR_ADAM_SKIP] = 1.0;
     state[RR_ADAM_SKIPPED] += 1.0;
     return;
+  }
+  if constexpr (KL) {
+    const double desired = klcfg[1], lr = cfg[0];
+    if (desired > 0.0) {                                    // rsl_rl's rule, before this minibatch's update
+      if (kl > 2.0 * desired) cfg[0] = fmax(klcfg[2], lr / 1.5);
+      else if (kl > 0.0 && kl < 0.5 * desired) cfg[0] = fmin(klcfg[3], lr * 1.5);
+    }
   }
   const float mx = (float)cfg[4];
   const float sc = norm > mx ? mx / norm : 1.0f;

@@ -130,7 +130,7 @@ class RRPpoCfg(C.Structure):
 
 EXPORTS = ["rr_model_load", "rr_model_dims", "rr_model_set_solver", "rr_model_set_solver_type", "rr_model_destroy", "rr_model_table", "rr_kernarg_layout", "rr_batch_create",
            "rr_batch_destroy", "rr_pipeline_init", "rr_pipeline_step", "rr_env_step", "rr_env_reset", "rr_pipeline_step_to", "rr_env_step_to", "rr_batch_contact_overflow", "rr_batch_bad_states", "rr_batch_unroll_supported", "rr_env_unroll", "rr_env_unroll_policy", "rr_batch_eval_supported", "rr_env_unroll_eval", "rr_batch_pose_supported", "rr_batch_set_pose", "rr_batch_set_reference_obs", "rr_batch_obs_width", "rr_batch_reference_obs_supported", "rr_batch_set_pose_termination", "rr_batch_pose_termination_supported", "rr_batch_set_body_tracking", "rr_batch_body_tracking_supported", "rr_batch_set_clip_restarts", "rr_batch_clip_restarts_supported", "rr_batch_set_velocity_tracking", "rr_batch_velocity_tracking_supported", "rr_batch_set_clip_library", "rr_batch_clip_library_supported", "rr_batch_set_clip_sampling", "rr_batch_clip_sampling_supported", "rr_batch_set_reference_restart", "rr_batch_reference_restart_supported", "rr_wrap_clip_restart", "rr_wrap_clip_library", "rr_wrap_clip_sampling",
-           "rr_compute_gae", "rr_mlp_forward", "rr_ppo_loss_workspace_bytes", "rr_ppo_loss", "rr_policy_act_workspace_bytes", "rr_policy_act", "rr_policy_sample", "rr_policy_backward_workspace_bytes", "rr_policy_backward", "rr_mlp_silu_backward_workspace_bytes", "rr_mlp_silu_backward", "rr_mlp_value_backward_workspace_bytes", "rr_mlp_policy_backward", "rr_mlp_policy_backward_workspace_bytes", "rr_mlp_value_backward", "rr_mlp_weight_grad_workspace_bytes", "rr_mlp_weight_grad", "rr_mlp_weight_grad_batch_workspace_bytes", "rr_mlp_weight_grad_batch", "rr_obs_moments_workspace_bytes", "rr_obs_moments", "rr_clipped_adam_workspace_bytes", "rr_clipped_adam_partials", "rr_clipped_adam_step", "rr_wrap_episode_autoreset", "rr_debug_layout", "rr_batch_set_schedule", "rr_batch_set_env_params", "rr_batch_env_params_supported", "rr_batch_set_profile", "rr_batch_set_ls_repeat_exit", "rr_batch_set_solver_trim", "rr_batch_set_solver_batch", "rr_batch_set_solve_resident", "rr_model_solve_resident_switch", "rr_batch_set_root_slot", "rr_model_root_slot_switch", "rr_batch_set_timing", "rr_batch_kernel_time", "rr_last_error"]
+           "rr_compute_gae", "rr_mlp_forward", "rr_ppo_loss_workspace_bytes", "rr_ppo_loss", "rr_ppo_loss_diag_workspace_bytes", "rr_ppo_loss_diag", "rr_policy_act_workspace_bytes", "rr_policy_act", "rr_policy_sample", "rr_policy_backward_workspace_bytes", "rr_policy_backward", "rr_mlp_silu_backward_workspace_bytes", "rr_mlp_silu_backward", "rr_mlp_value_backward_workspace_bytes", "rr_mlp_policy_backward", "rr_mlp_policy_backward_workspace_bytes", "rr_mlp_value_backward", "rr_mlp_weight_grad_workspace_bytes", "rr_mlp_weight_grad", "rr_mlp_weight_grad_batch_workspace_bytes", "rr_mlp_weight_grad_batch", "rr_obs_moments_workspace_bytes", "rr_obs_moments", "rr_clipped_adam_workspace_bytes", "rr_clipped_adam_partials", "rr_clipped_adam_step", "rr_clipped_adam_step_kl", "rr_wrap_episode_autoreset", "rr_debug_layout", "rr_batch_set_schedule", "rr_batch_set_env_params", "rr_batch_env_params_supported", "rr_batch_set_profile", "rr_batch_set_ls_repeat_exit", "rr_batch_set_solver_trim", "rr_batch_set_solver_batch", "rr_batch_set_solve_resident", "rr_model_solve_resident_switch", "rr_batch_set_root_slot", "rr_model_root_slot_switch", "rr_batch_set_timing", "rr_batch_kernel_time", "rr_last_error"]
 
 _lib = None
 
@@ -180,6 +180,9 @@ def lib():
         L.rr_ppo_loss_workspace_bytes.argtypes = [C.c_int32, C.c_int32]
         L.rr_ppo_loss_workspace_bytes.restype = C.c_size_t
         L.rr_ppo_loss.argtypes = [C.c_void_p] * 9 + [C.c_int32] * 3 + [C.POINTER(RRPpoCfg)] + [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p]
+        L.rr_ppo_loss_diag_workspace_bytes.argtypes = [C.c_int32, C.c_int32]
+        L.rr_ppo_loss_diag_workspace_bytes.restype = C.c_size_t
+        L.rr_ppo_loss_diag.argtypes = [C.c_void_p] * 9 + [C.c_int32] * 3 + [C.POINTER(RRPpoCfg)] + [C.c_void_p] * 6 + [C.c_size_t, C.c_void_p]
         L.rr_policy_act_workspace_bytes.argtypes = [C.c_int32]
         L.rr_policy_act_workspace_bytes.restype = C.c_size_t
         L.rr_policy_act.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(RRMlpNet), C.c_void_p, C.c_float,
@@ -216,6 +219,7 @@ def lib():
         L.rr_clipped_adam_partials.argtypes = [C.c_int64]
         L.rr_clipped_adam_step.argtypes = [C.POINTER(RRAdamTensor), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_void_p]
+        L.rr_clipped_adam_step_kl.argtypes = [C.POINTER(RRAdamTensor), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 6
         L.rr_batch_set_profile.argtypes = [C.c_void_p, C.c_void_p]
         L.rr_batch_set_schedule.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.rr_batch_set_env_params.argtypes = [C.c_void_p, C.POINTER(RREnvParams)]
@@ -985,8 +989,11 @@ def mlp_forward(obs, mean=None, std=None, policy=None, value=None, want_pre=Fals
 
 
 def ppo_loss(policy_logits, values, data, idx, noise, T: int, *, entropy_cost, discounting, reward_scaling, gae_lambda, clipping_epsilon,
-             normalize_advantage=True, min_std=0.001, out=None):
+             normalize_advantage=True, min_std=0.001, out=None, diag=None, kl_out=None):
     """Loss half of a PPO minibatch update and its gradient w.r.t. the network outputs (C ABI `rr_ppo_loss`, 3 launches).
+    `diag` (device float64 [16]): the same through `rr_ppo_loss_diag`, which also writes the minibatch's approx_kl, clip_fraction,
+    explained_variance and entropy to diag[0:4], adds them to the accumulators diag[8:14] (`DIAG_*`) and, with `kl_out` (one float32
+    element), stores the KL there; gradients and metrics are bitwise those of the plain call.
 
     policy_logits [(T+1)*B, 2A] / values [(T+1)*B]: the networks' outputs on the gathered minibatch, time-major; `data`: the
     collected batch, batch-major (`raw_action` [R, T, A]; `log_prob`, `reward`, `discount`, `truncation` [R, T]); idx [B] int64
@@ -1005,7 +1012,7 @@ def ppo_loss(policy_logits, values, data, idx, noise, T: int, *, entropy_cost, d
     elif data["log_prob"].shape[0] < B:
         raise ValueError("rr_ppo_loss: fewer batch rows than the minibatch")
     out = out if out is not None else {}
-    wb = lib().rr_ppo_loss_workspace_bytes(T, B)
+    wb = lib().rr_ppo_loss_workspace_bytes(T, B) if diag is None else lib().rr_ppo_loss_diag_workspace_bytes(T, B)
     if "workspace" not in out or out["workspace"].numel() * 8 < wb or out["grad_logits"].shape != policy_logits.shape:
         out["workspace"] = torch.empty((wb + 7) // 8, dtype=torch.float64, device=dev)
         out["grad_logits"] = torch.empty_like(policy_logits)
@@ -1013,12 +1020,25 @@ def ppo_loss(policy_logits, values, data, idx, noise, T: int, *, entropy_cost, d
         out["metrics"] = torch.empty(4, device=dev)
     cfg = RRPpoCfg(entropy_cost, discounting, reward_scaling, gae_lambda, clipping_epsilon, min_std, 1 if normalize_advantage else 0)
     stream = torch.cuda.current_stream(dev).cuda_stream
-    _check(lib().rr_ppo_loss(policy_logits.data_ptr(), values.data_ptr(), data["raw_action"].data_ptr(), data["log_prob"].data_ptr(),
-                             data["reward"].data_ptr(), data["discount"].data_ptr(), data["truncation"].data_ptr(),
-                             _dp(idx), noise.data_ptr(), T, B, A, C.byref(cfg),
-                             out["grad_logits"].data_ptr(), out["grad_values"].data_ptr(), out["metrics"].data_ptr(),
-                             out["workspace"].data_ptr(), out["workspace"].numel() * 8, C.c_void_p(stream)))
+    head = (policy_logits.data_ptr(), values.data_ptr(), data["raw_action"].data_ptr(), data["log_prob"].data_ptr(),
+            data["reward"].data_ptr(), data["discount"].data_ptr(), data["truncation"].data_ptr(),
+            _dp(idx), noise.data_ptr(), T, B, A, C.byref(cfg),
+            out["grad_logits"].data_ptr(), out["grad_values"].data_ptr(), out["metrics"].data_ptr())
+    tail = (out["workspace"].data_ptr(), out["workspace"].numel() * 8, C.c_void_p(stream))
+    if diag is None:
+        if kl_out is not None:
+            raise ValueError("rr_ppo_loss: kl_out needs diag (rr_ppo_loss_diag)")
+        _check(lib().rr_ppo_loss(*head, *tail))
+    else:
+        _ptr(diag, torch.float64, DIAG_DOUBLES)
+        _check(lib().rr_ppo_loss_diag(*head, diag.data_ptr(), None if kl_out is None else _ptr(kl_out, numel=1), *tail))
     return out["grad_logits"], out["grad_values"], out["metrics"]
+
+
+# the diagnostics block of `rr_ppo_loss_diag` (device float64; include/rodent_rr.h)
+DIAG_DOUBLES = 16
+DIAG_KL, DIAG_CLIP, DIAG_EV, DIAG_ENT = 0, 1, 2, 3
+DIAG_COUNT, DIAG_KL_SUM, DIAG_KL_MAX, DIAG_CLIP_SUM, DIAG_EV_SUM, DIAG_ENT_SUM = 8, 9, 10, 11, 12, 13
 
 
 def mlp_silu_backward(g, z, bias_grad):
@@ -1128,7 +1148,7 @@ class ClippedAdamBuffers:
     and the tensor table.  `params`: contiguous float32 device tensors in the order of their segments of `grad_flat`; `m_flat` / `v_flat`:
     the moments, laid out as the gradient is.  `step()` launches on the current stream."""
 
-    def __init__(self, params, grad_flat, m_flat, v_flat, *, lr, b1, b2, eps, max_grad_norm, n=None):
+    def __init__(self, params, grad_flat, m_flat, v_flat, *, lr, b1, b2, eps, max_grad_norm, n=None, kl=None, kl_cfg=None):
         self.params, self.grad, self.m, self.v = list(params), grad_flat, m_flat, v_flat
         dev = grad_flat.device
         self.n = int(grad_flat.numel() if n is None else n)
@@ -1142,8 +1162,21 @@ class ClippedAdamBuffers:
         self.cfg = torch.tensor([lr, b1, b2, eps, max_grad_norm, 0.0, 0.0, 0.0], dtype=torch.float64, device=dev)
         self.state = torch.zeros(16, dtype=torch.float64, device=dev)
         self.workspace = torch.empty(max(lib().rr_clipped_adam_workspace_bytes(self.n) // 8, 1), dtype=torch.float64, device=dev)
+        # `kl` (one float32 element on the device: the minibatch's approx_kl) and `kl_cfg` (stop threshold, desired_kl, lr_lo, lr_hi; 0 = off):
+        # the step goes through `rr_clipped_adam_step_kl`, which decides the target-KL stop and the KL-adaptive learning rate on the device
+        self.kl, self.kl_cfg = kl, None
+        if kl is not None:
+            _ptr(kl, numel=1)
+            self.kl_cfg = torch.tensor([float(x) for x in kl_cfg], dtype=torch.float64, device=dev)
+            if self.kl_cfg.numel() != 4:
+                raise ValueError("ClippedAdamBuffers: kl_cfg is (stop threshold, desired_kl, lr_lo, lr_hi)")
 
     def step(self):
+        if self.kl is not None:
+            _check(lib().rr_clipped_adam_step_kl(self.table, len(self.params), self.grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.n,
+                                                 self.cfg.data_ptr(), self.state.data_ptr(), self.kl.data_ptr(), self.kl_cfg.data_ptr(),
+                                                 self.workspace.data_ptr(), C.c_void_p(torch.cuda.current_stream(self.grad.device).cuda_stream)))
+            return
         _check(lib().rr_clipped_adam_step(self.table, len(self.params), self.grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.n,
                                           self.cfg.data_ptr(), self.state.data_ptr(), self.workspace.data_ptr(),
                                           C.c_void_p(torch.cuda.current_stream(self.grad.device).cuda_stream)))

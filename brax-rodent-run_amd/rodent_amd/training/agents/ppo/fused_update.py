@@ -21,13 +21,18 @@ from ... import fused_mlp
 
 class FusedUpdate:
     def __init__(self, policy_net, value_net, dist, unroll_length: int, *, entropy_cost, discounting, reward_scaling, gae_lambda,
-                 clipping_epsilon, normalize_advantage):
+                 clipping_epsilon, normalize_advantage, diagnostics: bool = False, kl_out=None):
         self.policy_net, self.value_net, self.dist, self.T = policy_net, value_net, dist, unroll_length
         self.cfg = dict(entropy_cost=entropy_cost, discounting=discounting, reward_scaling=reward_scaling, gae_lambda=gae_lambda,
                         clipping_epsilon=clipping_epsilon, normalize_advantage=normalize_advantage, min_std=dist.min_std)
         dev = policy_net.layers[0].weight.device
         self.trange = torch.arange(unroll_length + 1, device=dev)
         self.bufs = {}
+        # learner diagnostics: the loss goes through `rr_ppo_loss_diag`, which adds every evaluated minibatch's approx_kl, clip fraction,
+        # explained variance and entropy to this device block (`hip.DIAG_*`; the caller reads and clears it after a synchronisation) and
+        # writes the KL to `kl_out` (the flat gradient buffer's first extra slot) for the optimiser step
+        self.diag = torch.zeros(hip.DIAG_DOUBLES, dtype=torch.float64, device=dev) if diagnostics else None
+        self.kl_out = kl_out
         # the policy network's backward (35 us chain, small products) runs on a second stream next to the value network's (the
         # matrix-core kernels that fill the GPU): fork / join through events, inside a HIP-graph capture as well.  RR_LEARNER_STREAMS=0: one stream
         import os
@@ -83,7 +88,7 @@ class FusedUpdate:
         pol, val, ppre, vpre = hip.mlp_forward(obs, mean, std, fused_mlp.net_params(self.policy_net), fused_mlp.net_params(self.value_net),
                                                want_pre=True, rows=rows)
         noise = torch.randn(T * B, A, device=obs.device, dtype=obs.dtype, generator=generator)     # the draw of dist.entropy
-        g_pol, g_val, metrics = hip.ppo_loss(pol, val, data, idx, noise, T, out=self.bufs, **self.cfg)
+        g_pol, g_val, metrics = hip.ppo_loss(pol, val, data, idx, noise, T, out=self.bufs, diag=self.diag, kl_out=self.kl_out, **self.cfg)
         n = T * B                                                                           # the bootstrap rows carry no policy gradient
         if self.side is None:
             items = self._policy_backward(ppre, g_pol[:n], obs, rows[:n], mean, std) + self._value_backward(vpre, g_val, obs, rows, mean, std)

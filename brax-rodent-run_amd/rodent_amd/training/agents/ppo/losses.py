@@ -30,8 +30,15 @@ def compute_gae(truncation, termination, rewards, values, bootstrap_value, lambd
 
 def compute_ppo_loss(policy_logits, baseline, bootstrap_value, data: Dict[str, torch.Tensor], dist, entropy_cost=1e-4,
                      discounting=0.9, reward_scaling=1.0, gae_lambda=0.95, clipping_epsilon=0.3,
-                     normalize_advantage=True, generator=None, advantage_stats_fn=None) -> Tuple[torch.Tensor, Dict[str, torch.Tensor]]:
-    """`data` leaves are time-major [T, B(, ...)]: reward, discount, truncation, raw_action, log_prob."""
+                     normalize_advantage=True, generator=None, advantage_stats_fn=None,
+                     diagnostics: bool = False) -> Tuple[torch.Tensor, Dict[str, torch.Tensor]]:
+    """`data` leaves are time-major [T, B(, ...)]: reward, discount, truncation, raw_action, log_prob.
+
+    `diagnostics=True` adds four float64 scalars of the minibatch to the metrics (the restatement of what the DIAG instances of the loss
+    kernels, csrc/rr_ppo.h, report): `approx_kl` = mean(expm1(d) - d), d = log_prob_new - log_prob_behaviour (the k3 estimator, >= 0; the
+    term is formed in double from d as the inputs' dtype gives it -- in float32 (rho - 1) - d keeps no digit at early training's KL);
+    `clip_fraction`, the share of samples with rho outside [1 - eps, 1 + eps]; `explained_variance` = 1 - Var(vs - v) / Var(vs) with
+    population variances, 0 where Var(vs) == 0; `entropy`, the mean sampled entropy."""
     rewards = data["reward"] * reward_scaling
     truncation = data["truncation"]
     termination = (1 - data["discount"]) * (1 - truncation)
@@ -54,5 +61,16 @@ def compute_ppo_loss(policy_logits, baseline, bootstrap_value, data: Dict[str, t
     entropy = torch.mean(dist.entropy(policy_logits, generator))
     entropy_loss = entropy_cost * -entropy
     total_loss = policy_loss + v_loss + entropy_loss
-    return total_loss, {"total_loss": total_loss.detach(), "policy_loss": policy_loss.detach(),
-                        "v_loss": v_loss.detach(), "entropy_loss": entropy_loss.detach()}
+    metrics = {"total_loss": total_loss.detach(), "policy_loss": policy_loss.detach(),
+               "v_loss": v_loss.detach(), "entropy_loss": entropy_loss.detach()}
+    if diagnostics:
+        with torch.no_grad():
+            d = (target_action_log_probs - behaviour_action_log_probs).double()
+            rho = rho_s.detach()
+            var_vs, var_ve = vs.double().var(unbiased=False), v_error.detach().double().var(unbiased=False)
+            metrics["approx_kl"] = (torch.expm1(d) - d).mean()
+            metrics["clip_fraction"] = (~((rho >= 1 - clipping_epsilon) & (rho <= 1 + clipping_epsilon))).double().mean()
+            metrics["explained_variance"] = torch.where(var_vs > 0, 1.0 - var_ve / torch.where(var_vs > 0, var_vs, torch.ones_like(var_vs)),
+                                                        torch.zeros_like(var_vs))
+            metrics["entropy"] = entropy.detach().double()
+    return total_loss, metrics

@@ -20,7 +20,7 @@ from typing import Callable, Optional, Tuple
 import numpy as np
 import torch
 
-from .... import jax_random
+from .... import hip, jax_random
 from ....envs import wrappers
 from ... import acting, distributed as D, fused_mlp, networks as ppo_networks_mod, optim, running_statistics
 from ...types import PPONetworkParams, TrainingState
@@ -80,6 +80,11 @@ def train(
     return_training_state: bool = False,
     clip_weight_fn: Optional[Callable] = None,
     max_grad_norm: Optional[float] = None,
+    learner_diagnostics: bool = False,
+    target_kl: Optional[float] = None,
+    learning_rate_schedule: Optional[str] = None,
+    desired_kl: float = optim.DESIRED_KL_DEFAULT,
+    learning_rate_bounds: Tuple[float, float] = optim.LR_BOUNDS_DEFAULT,
 ):
     """PPO training.  Returns (make_policy, params=(normalizer_params, policy_params), metrics).
 
@@ -103,9 +108,35 @@ def train(
     run; the learner's counterpart of the env's `bad_state_max`.  Reported per training step, read and cleared after its closing
     synchronisation: `training/grad_norm` (mean pre-clip norm over the applied updates), `training/grad_norm_max`,
     `training/grad_clip_share` (applied updates that were scaled), `training/skipped_updates` (one warning the first time it is not 0).
+    `learner_diagnostics` (extension, default off; also on with either option below): every evaluated minibatch contributes approx_kl
+    (mean of expm1(d) - d, d = new - behaviour log-prob: the k3 estimator, >= 0), the clip fraction of the surrogate, the explained
+    variance 1 - Var(vs - v) / Var(vs) and the sampled entropy.  Reported per training step as `training/approx_kl`,
+    `training/clip_fraction`, `training/explained_variance`, `training/entropy` (means over ALL minibatches evaluated in the step) and
+    `training/approx_kl_max`; the four loss keys keep their last-minibatch meaning.  The sums live in device memory (the loss kernels'
+    DIAG instances on the fused path, persistent tensors elsewhere) and are read and cleared after the closing synchronisation.
+    `target_kl` (default None; a finite number > 0, anything else raises ValueError): the early stop of Spinning Up and Stable-Baselines3.
+    Once a minibatch's approx_kl, measured before its own update, is not <= 1.5 * target_kl (that convention's factor; a NaN KL too), that
+    update and every later one of the training step is not applied; the host reads the flag once per pass over the batch and leaves
+    the loops.  `training/stopped_updates` counts the evaluated updates that were not applied.
+    `learning_rate_schedule="adaptive_kl"` (default None = constant) with `desired_kl` and `learning_rate_bounds`: rsl_rl's rule, before
+    the update of the minibatch whose KL was measured: kl > 2 desired_kl: lr = max(lo, lr / 1.5); 0 < kl < desired_kl / 2: lr = min(hi,
+    lr * 1.5).  `learning_rate` must lie inside the bounds.  The three defaults (0.01, (1e-5, 1e-2)) are rsl_rl's and untuned here.
+    `training/learning_rate` is the value after the step's last update.  Both controls decide on the device, inside the clipped Adam
+    step, from a KL that travels behind the gradients through their all-reduce, so every rank takes the same decision; with
+    `max_grad_norm=None` they therefore REPLACE torch.optim.Adam by `training.optim.ClippedAdam(max_grad_norm=inf)` on that path (the
+    `training/grad_*` keys are reported too).  Whether either control trains the rodent better has not been measured.
     """
     if max_grad_norm is not None:
         max_grad_norm = optim.check_max_grad_norm(max_grad_norm)
+    if learning_rate_schedule not in (None, "adaptive_kl"):
+        raise ValueError(f"learning_rate_schedule must be None or 'adaptive_kl', got {learning_rate_schedule!r}")
+    if target_kl is not None:
+        target_kl = optim.check_target_kl(target_kl)
+    adaptive_lr = learning_rate_schedule == "adaptive_kl"
+    if adaptive_lr:
+        desired_kl, *learning_rate_bounds = optim.check_adaptive_kl(learning_rate, desired_kl, learning_rate_bounds)
+    kl_control = target_kl is not None or adaptive_lr
+    diagnostics = bool(learner_diagnostics) or kl_control
     assert batch_size * num_minibatches % num_envs == 0
     xt = time.time()
     process_count, process_id = D.world_size(), D.rank()
@@ -163,7 +194,8 @@ def train(
     if process_count > 1:                                # replicate (rank 0's init), like device_put_replicated
         for p in params:
             torch.distributed.broadcast(p.data, src=0)
-    flat = D.FlatGrads(params)
+    # the KL controls read the minibatch's approx_kl from the first of four slots behind the gradients (four: what follows stays float4-aligned)
+    flat = D.FlatGrads(params, extra=4) if kl_control else D.FlatGrads(params)
     # optax.adam(lr): b1=.9, b2=.999, eps=1e-8, eps outside the sqrt -- torch.optim.Adam's update; one fused
     # multi-tensor launch per step on the GPU
     # One process on a GPU: the minibatch update (gather, normalise, both MLPs forward + backward, GAE kernel, fused Adam) is
@@ -175,11 +207,14 @@ def train(
     # puts a collective inside the loss: that mode runs eagerly.)
     use_graph = (device.type == "cuda" and os.environ.get("RR_PPO_GRAPH", "1") == "1"
                  and not (global_advantage_normalization and process_count > 1))
-    if max_grad_norm is None:
+    if max_grad_norm is None and not kl_control:
         optimizer = torch.optim.Adam(params, lr=learning_rate, betas=(0.9, 0.999), eps=1e-8, fused=(device.type == "cuda"),
                                      capturable=use_graph)
     else:                                                # clip_by_global_norm -> adam, non-finite updates skipped: rr_clipped_adam_step
-        optimizer = optim.ClippedAdam(params, flat, lr=learning_rate, max_grad_norm=max_grad_norm, betas=(0.9, 0.999), eps=1e-8)
+        optimizer = optim.ClippedAdam(params, flat, lr=learning_rate, max_grad_norm=float("inf") if max_grad_norm is None else max_grad_norm,
+                                      betas=(0.9, 0.999), eps=1e-8, target_kl=target_kl, desired_kl=desired_kl if adaptive_lr else None,
+                                      learning_rate_bounds=tuple(learning_rate_bounds) if adaptive_lr else None)
+    clipped_adam = isinstance(optimizer, optim.ClippedAdam)
     clip_stats = {"warned": False}
     normalizer_params = running_statistics.init_state(env.observation_size, device)
     normalize = running_statistics.normalize if normalize_observations else (lambda x, y: x)
@@ -243,7 +278,13 @@ def train(
         from . import fused_update
         fused_update_fn = fused_update.FusedUpdate(policy_net, value_net, dist, T, entropy_cost=entropy_cost, discounting=discounting,
                                                    reward_scaling=reward_scaling, gae_lambda=gae_lambda, clipping_epsilon=clipping_epsilon,
-                                                   normalize_advantage=normalize_advantage)
+                                                   normalize_advantage=normalize_advantage, diagnostics=diagnostics,
+                                                   kl_out=flat.tail[:1] if kl_control else None)
+    # diagnostics of the autograd and CPU paths: a persistent float64 tensor laid out as the fused path's block and updated in place, so a
+    # captured graph replays the additions
+    diag_acc = None
+    if diagnostics and fused_update_fn is None:
+        diag_acc = torch.zeros(hip.DIAG_DOUBLES, dtype=torch.float64, device=device)
 
     def fwd_bwd(data, idx, nparams):
         if fused_update_fn is not None:
@@ -265,9 +306,19 @@ def train(
             policy_logits, values[:T], values[T], mbd, dist, entropy_cost=entropy_cost, discounting=discounting,
             reward_scaling=reward_scaling, gae_lambda=gae_lambda, clipping_epsilon=clipping_epsilon,
             normalize_advantage=normalize_advantage, generator=gen,
-            advantage_stats_fn=adv_stats if (global_advantage_normalization and process_count > 1) else None)
+            advantage_stats_fn=adv_stats if (global_advantage_normalization and process_count > 1) else None, diagnostics=diagnostics)
         flat.zero_()
         loss.backward()
+        if diagnostics:
+            kl, cf, ev, ent = (m.pop(k) for k in ("approx_kl", "clip_fraction", "explained_variance", "entropy"))
+            diag_acc[hip.DIAG_COUNT] += 1.0
+            diag_acc[hip.DIAG_KL_SUM] += kl
+            diag_acc[hip.DIAG_KL_MAX] = torch.fmax(diag_acc[hip.DIAG_KL_MAX], kl)       # fmax: a NaN KL does not erase the maximum (the kernel's fmax)
+            diag_acc[hip.DIAG_CLIP_SUM] += cf
+            diag_acc[hip.DIAG_EV_SUM] += ev
+            diag_acc[hip.DIAG_ENT_SUM] += ent
+            if kl_control:
+                flat.tail[0] = kl.float()                    # rounded to float32 once; averaged over the ranks with the gradients
         return m
 
     def eager_update(data, idx, nparams):
@@ -389,11 +440,17 @@ def train(
         if normalize_observations and gstate["norm"] is not None:     # the graph reads the normaliser from fixed buffers
             for f in ("count", "mean", "summed_variance", "std"):
                 getattr(gstate["norm"], f).copy_(getattr(normalizer_params, f))
+        if kl_control:
+            optimizer.begin_training_step()              # clears the sticky stop flag of target_kl
         for _ in range(num_updates_per_batch):
             perm = torch.randperm(U * N, generator=perm_gen).to(device)
             for mb in range(num_minibatches):
                 idx = perm[mb * local_batch:(mb + 1) * local_batch]
                 metrics = minibatch_update(data, idx)
+            # target_kl: one 8-byte read per pass, so that no pass is spent on updates that can change nothing.  The flag derives from the
+            # all-reduced KL: every rank reads the same value and leaves together
+            if target_kl is not None and optimizer.stopped:
+                break
         sync()
         t2 = time.time()
         training_state.normalizer_params = normalizer_params
@@ -421,8 +478,20 @@ def train(
                               "(training/bad_state_resets counts them)", RuntimeWarning, stacklevel=2)
         if outcome_envs:
             clip_outcome_metrics(out)
-        if max_grad_norm is not None:                    # the optimiser's device block: read and cleared here, after the closing synchronisation
+        if diagnostics:                                  # read and cleared next to the optimiser's block below
+            blk = fused_update_fn.diag if fused_update_fn is not None else diag_acc
+            dg = blk.tolist()                            # a copy: the block is cleared next
+            blk[hip.DIAG_COUNT:hip.DIAG_ENT_SUM + 1].zero_()
+            cnt = max(float(dg[hip.DIAG_COUNT]), 1.0)
+            out.update({"training/approx_kl": float(dg[hip.DIAG_KL_SUM]) / cnt, "training/approx_kl_max": float(dg[hip.DIAG_KL_MAX]),
+                        "training/clip_fraction": float(dg[hip.DIAG_CLIP_SUM]) / cnt, "training/explained_variance": float(dg[hip.DIAG_EV_SUM]) / cnt,
+                        "training/entropy": float(dg[hip.DIAG_ENT_SUM]) / cnt})
+        if clipped_adam:                                 # the optimiser's device block: read and cleared here, after the closing synchronisation
             st = optimizer.stats(clear=True)
+            if target_kl is not None:
+                out["training/stopped_updates"] = float(st["stopped_updates"])
+            if adaptive_lr:
+                out["training/learning_rate"] = float(st["learning_rate"])
             for k in ("grad_norm", "grad_norm_max", "grad_clip_share", "skipped_updates"):
                 out[f"training/{k}"] = float(st[k])
             if st["skipped_updates"] and not clip_stats["warned"]:

@@ -68,13 +68,17 @@ def all_reduce_mean_(t: torch.Tensor) -> torch.Tensor:
 class FlatGrads:
     """All parameters' gradients live in ONE flat buffer so the per-minibatch `pmean(grads)`
     [UP brax.training.gradients.gradient_update_fn] is a single all-reduce (2.5 MB, latency-bound
-    on xGMI: one collective per minibatch instead of one per tensor)."""
+    on xGMI: one collective per minibatch instead of one per tensor).  `extra=k` appends k slots behind the parameters' `n` elements
+    (`tail`): scalars that must be identical on every rank after the update's all-reduce -- the minibatch's approx_kl of the KL controls
+    (`training.optim`) -- travel in the same collective.  Use a multiple of 4, so that what follows the buffer keeps float4 alignment."""
 
-    def __init__(self, params):
+    def __init__(self, params, extra: int = 0):
         self.params = [p for p in params]
         n = sum(p.numel() for p in self.params)
         p0 = self.params[0]
-        self.flat = torch.zeros(n, dtype=p0.dtype, device=p0.device)
+        self.n, self.extra = n, int(extra)
+        self.flat = torch.zeros(n + self.extra, dtype=p0.dtype, device=p0.device)
+        self.tail = self.flat[n:]
         o = 0
         for p in self.params:
             p.grad = self.flat[o:o + p.numel()].view_as(p)

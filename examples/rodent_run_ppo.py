@@ -24,7 +24,7 @@ import torch
 
 from rodent_amd import assets, envs, jax_random, mjcf, preprocessing, rollout
 from rodent_amd.io import model
-from rodent_amd.training import acting, networks
+from rodent_amd.training import acting, networks, optim
 from rodent_amd.training.agents.ppo import train as ppo
 
 
@@ -114,9 +114,23 @@ def main():
                     "the one-launch rollout of the 32-wide policy takes 1 .. 4)")
     ap.add_argument("--max-grad-norm", type=float, default=None, metavar="X", help="clip every minibatch gradient to global norm X before Adam and "
                     "skip updates whose gradient is not finite (ppo.train(max_grad_norm=X); inf: only the skip); default: no clipping")
+    ap.add_argument("--learner-diagnostics", action="store_true", help="report training/approx_kl, approx_kl_max, clip_fraction, "
+                    "explained_variance and entropy, means over all minibatches of a training step (ppo.train(learner_diagnostics=True))")
+    ap.add_argument("--target-kl", type=float, default=None, metavar="X", help="stop a training step's updates once a minibatch's approx_kl "
+                    "exceeds 1.5 X, the rule of Spinning Up / Stable-Baselines3 (ppo.train(target_kl=X)); default: no stop")
+    ap.add_argument("--lr-schedule", choices=("adaptive_kl",), default=None, help="adaptive_kl: rsl_rl's KL-adaptive learning rate "
+                    "(ppo.train(learning_rate_schedule='adaptive_kl')); default: constant")
+    ap.add_argument("--desired-kl", type=float, default=None, metavar="X", help="with --lr-schedule adaptive_kl: the KL the schedule steers "
+                    f"to (default {optim.DESIRED_KL_DEFAULT:g}: rsl_rl's, untuned here)")
+    ap.add_argument("--lr-bounds", type=float, nargs=2, default=None, metavar=("LO", "HI"), help="with --lr-schedule adaptive_kl: the learning "
+                    "rate stays inside [LO, HI] (default %g %g: rsl_rl's, untuned here)" % optim.LR_BOUNDS_DEFAULT)
     args = ap.parse_args()
     if args.max_grad_norm is not None and not args.max_grad_norm > 0:
         ap.error("--max-grad-norm: a number > 0 (inf allowed)")
+    if args.target_kl is not None and not 0 < args.target_kl < float("inf"):
+        ap.error("--target-kl: a finite number > 0")
+    if args.lr_schedule is None and (args.desired_kl is not None or args.lr_bounds is not None):
+        ap.error("--desired-kl / --lr-bounds: only with --lr-schedule adaptive_kl")
     if args.track_velocity and not args.track_pose:      # (before any device is touched)
         ap.error("--track-velocity: the velocities are indexed like the reference pose; add --track-pose")
 
@@ -241,6 +255,9 @@ def main():
         batch_size=config["batch_size"], seed=0, max_training_steps=args.max_training_steps,
         randomization_fn=domain_randomize if args.randomize else None,
         max_grad_norm=args.max_grad_norm,
+        learner_diagnostics=args.learner_diagnostics, target_kl=args.target_kl, learning_rate_schedule=args.lr_schedule,
+        desired_kl=optim.DESIRED_KL_DEFAULT if args.desired_kl is None else args.desired_kl,
+        learning_rate_bounds=optim.LR_BOUNDS_DEFAULT if args.lr_bounds is None else tuple(args.lr_bounds),
         clip_weight_fn=envs.rodent.FailureWeights(floor=args.weight_floor, decay=args.weight_decay) if args.weighted_restarts else None,
         network_factory=functools.partial(networks.make_ppo_networks, policy_hidden_layer_sizes=(args.policy_width,) * args.policy_depth))
 

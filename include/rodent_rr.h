@@ -581,6 +581,23 @@ int rr_ppo_loss(const float* policy_logits, const float* values, const float* ra
                 const float* discount, const float* truncation, const int64_t* idx, const float* noise, int32_t T, int32_t B, int32_t A,
                 const rr_ppo_cfg* cfg, float* grad_logits, float* grad_values, float* metrics, void* workspace, size_t workspace_bytes,
                 void* stream);
+/* rr_ppo_loss with the learner's diagnostics (the DIAG instances of the loss and metrics kernels; gradients and metrics[4] are bitwise
+ * rr_ppo_loss's).  Five more block sums, fixed order, no atomics, give per minibatch
+ *   approx_kl          = mean(expm1(d) - d), d = log_prob_new - log_prob_behaviour in float32, the term in double (k3 estimator, >= 0)
+ *   clip_fraction      = share of samples with rho outside [1 - eps, 1 + eps]
+ *   explained_variance = 1 - Var(vs - v) / Var(vs), population variances from double sums; 0 where Var(vs) == 0
+ *   entropy            = mean sampled entropy
+ * diag: device double [16], 8-byte aligned, written by one thread with plain stores: [0..3] the four figures of this minibatch in that
+ *   order; accumulators since the caller last cleared them: [8] minibatches, [9] sum of approx_kl, [10] largest approx_kl, [11] sum of
+ *   clip_fraction, [12] sum of explained_variance, [13] sum of entropy.  A replayed graph keeps adding to them.
+ * kl_out: device float, nullable: approx_kl rounded to float32 once -- the input of rr_clipped_adam_step_kl (the first slot behind the
+ *   parameters in the flat gradient buffer, so that the ranks' all-reduce averages it with the gradients).
+ * workspace: rr_ppo_loss_diag_workspace_bytes(T, B) bytes, 8-byte aligned. */
+size_t rr_ppo_loss_diag_workspace_bytes(int32_t T, int32_t B);
+int rr_ppo_loss_diag(const float* policy_logits, const float* values, const float* raw_action, const float* log_prob, const float* reward,
+                     const float* discount, const float* truncation, const int64_t* idx, const float* noise, int32_t T, int32_t B, int32_t A,
+                     const rr_ppo_cfg* cfg, float* grad_logits, float* grad_values, float* metrics, double* diag, float* kl_out,
+                     void* workspace, size_t workspace_bytes, void* stream);
 
 /* The rollout's actor step, acting.actor_step -> make_inference_fn [UP; SURVEY.md a22], in two launches: observations (optionally
  * through obs_rows, optionally normalised by mean / std) -> policy network (as rr_mlp_forward takes it: 32-wide hidden layers,
@@ -707,6 +724,21 @@ size_t rr_clipped_adam_workspace_bytes(int64_t n);
 int32_t rr_clipped_adam_partials(int64_t n);
 int rr_clipped_adam_step(const rr_adam_tensor* table, int32_t ntensors, const float* grad_flat, float* m_flat, float* v_flat, int64_t n,
                          const double* cfg_dev, double* state_dev, void* workspace, void* stream);
+/* rr_clipped_adam_step behind two controls driven by the minibatch's approx_kl, decided on the device by the finalisation kernel so that
+ * a captured graph replays the decision (the rule: training/optim.py kl_control_rule).  kl_dev: device float, the KL measured before this
+ * update.  klcfg_dev: device double [4]: stop threshold (1.5 x target_kl, the factor of Spinning Up and Stable-Baselines3), desired_kl,
+ * lr_lo, lr_hi; 0 switches the stop (slot 0) or the schedule (slot 1) off.  In this order:
+ *   state[6] != 0 (sticky stop flag; the caller clears it at the start of a training step's learner phase): state[13] += 1, state[3] = 1,
+ *     nothing else moves -- not the norm statistics either;
+ *   state[7] = kl;  threshold > 0 and not kl <= threshold (a NaN KL too): state[6] = 1, state[3] = 1, state[13] += 1, return;
+ *   norm not finite: skipped as in rr_clipped_adam_step, the learning rate is left alone;
+ *   desired_kl > 0 (rsl_rl's schedule, in double on cfg_dev[0], before this update): kl > 2 desired: lr = max(lr_lo, lr / 1.5);
+ *     0 < kl < desired / 2: lr = min(lr_hi, lr * 1.5);
+ *   then the step of rr_clipped_adam_step.
+ * The update kernel's blocks return on state[3], which a stop sets as a skip does; parameters, both moments and t keep their bits.
+ * cfg_dev is written (slot 0); the layouts of cfg_dev and state_dev are rr_clipped_adam_step's, with state slots 6, 7 and 13 in use. */
+int rr_clipped_adam_step_kl(const rr_adam_tensor* table, int32_t ntensors, const float* grad_flat, float* m_flat, float* v_flat, int64_t n,
+                            double* cfg_dev, double* state_dev, const float* kl_dev, const double* klcfg_dev, void* workspace, void* stream);
 
 /* brax.envs.wrappers.training.EpisodeWrapper + AutoResetWrapper [UP; SURVEY.md 3.4] after an env step, in one launch:
  * steps' = (prev_done ? 0 : prev_steps) + action_repeat; over = steps' >= episode_length; done <- over ? 1 : done;
