@@ -1466,67 +1466,108 @@ extern "C" int rr_clipped_adam_step_kl(const rr_adam_tensor* table, int32_t nten
 // here one launch, one 256-thread block per env.  Arrays are row-major [N][width]; `cur` is overwritten in place.
 #define RR_WRAP_MAX 12
 struct RRWrapArgs { const float* first[RR_WRAP_MAX]; float* cur[RR_WRAP_MAX]; int width[RR_WRAP_MAX]; int narr; };
-__global__ void rr_wrap_kernel(const RRWrapArgs A, const float* __restrict__ prev_done, const float* __restrict__ prev_steps,
+// What the rule gains level by level; each level has the ones below it, and its own members of RRWrapClip (by value, like RRWrapArgs):
+//   RESTART  (rr_clip_restart_io's rule, one env step): `first[i]` are banks [num_slots][N][widths[i]], the clip's end joins `over`, and
+//            where done the next bank entry and its frame come back.  cur_frame holds the stepped frame and is finished in place.
+//   LIBRARY  (rr_clip_library_io's): the clip's end is taken at the length of the clip the step was made on, and where done the bank
+//            entry's clip comes back with its frame.  clip is finished in place; null pointers switch the two additions off one by one.
+//   SAMPLING (rr_clip_sampling_io's): the outcome counters of the step -- on the clip it was made on, flushed every step -- and, where
+//            done, the slot drawn by the env's bank weights instead of the next one.  pose_fail: the step's pose-termination codes (null:
+//            none).  Null outcomes / clip_weights switch the two additions off one by one.  This level knows num_clips and clamps every
+//            clip id into 0 .. num_clips - 1; LIBRARY clamps the id it indexes clip_lengths with below only and hands a bank entry's on.
+enum { RR_WRAP_PLAIN, RR_WRAP_RESTART, RR_WRAP_LIBRARY, RR_WRAP_SAMPLING };
+struct RRWrapClip {
+  int* cur_frame; const int* bank_frames; const int* slot_in; int* slot_out; int num_slots, track_len, end_at_clip_end;      // RESTART
+  int* clip; const int* bank_clips; const int* clip_lengths;                                                                 // LIBRARY
+  int num_clips; const float* pose_fail; const int* clip_weights; const int* draws_in; int* draws_out; long long* outcomes;  // SAMPLING
+  unsigned seed;
+};
+template <int LEVEL>
+__global__ void rr_wrap_kernel(const RRWrapArgs A, const RRWrapClip K, const float* __restrict__ prev_done, const float* __restrict__ prev_steps,
                                float* __restrict__ done, float* __restrict__ steps, float* __restrict__ truncation,
                                float episode_length, float action_repeat) {
-  const int e = blockIdx.x;
+  const int e = blockIdx.x, N = gridDim.x;
+  auto clip_id = [&](int c) {            // a clip id as the level takes it
+    c = c < 0 ? 0 : c;
+    if constexpr (LEVEL >= RR_WRAP_SAMPLING) c = c > K.num_clips - 1 ? K.num_clips - 1 : c;
+    return c;
+  };
   // AutoReset (before the step): steps <- 0 where the incoming state was done;  Episode: steps += action_repeat, done at the
   // episode end, truncation = over & !terminated;  AutoReset (after): first state where done
   const float s0 = prev_done[e] != 0.0f ? 0.0f : prev_steps[e];
   const float s1 = s0 + action_repeat;
-  const bool over = s1 >= episode_length;
+  bool over = s1 >= episode_length;
+  int new_frame = 0, c = 0;
+  if constexpr (LEVEL >= RR_WRAP_RESTART) {
+    new_frame = K.cur_frame[e];
+    int len = K.track_len;
+    if constexpr (LEVEL >= RR_WRAP_LIBRARY) {
+      c = clip_id(K.clip ? K.clip[e] : 0);
+      if (K.clip_lengths) { len = K.clip_lengths[c]; len = len < 1 ? 1 : (len > K.track_len ? K.track_len : len); }
+    }
+    over = over || (K.end_at_clip_end && new_frame >= len - 1);
+  }
+  const int c_step = c;                  // the clip the step was made on
   const float d_env = done[e];
   const float d_out = over ? 1.0f : d_env;
-  __syncthreads();                       // every thread has read done[e] before thread 0 rewrites it
-  if (threadIdx.x == 0) { steps[e] = s1; truncation[e] = over ? 1.0f - d_env : 0.0f; done[e] = d_out; }
-  if (d_out != 0.0f) {
-    for (int a = 0; a < A.narr; ++a) {
-      const int w = A.width[a];
-      const float* src = A.first[a] + (size_t)e * w;
-      float* dst = A.cur[a] + (size_t)e * w;
-      for (int i = threadIdx.x; i < w; i += blockDim.x) dst[i] = src[i];
+  size_t row = e;                        // the row of `first` that comes back where done
+  int frame = 0, slot = 0;
+  bool failed = false;
+  unsigned n = 0;
+  if constexpr (LEVEL >= RR_WRAP_RESTART) {
+    if constexpr (LEVEL >= RR_WRAP_SAMPLING) {
+      failed = K.pose_fail && K.pose_fail[e] != 0.0f;
+      n = K.draws_in ? (unsigned)K.draws_in[e] : 0u;
+    }
+    slot = K.slot_in[e];
+    slot = slot < 0 ? 0 : (slot > K.num_slots - 1 ? K.num_slots - 1 : slot);      // clamped into the bank
+    if (d_out != 0.0f) {
+      int drawn = -1;
+      if constexpr (LEVEL >= RR_WRAP_SAMPLING) {
+        if (K.clip_weights && K.bank_clips) {      // the K entries one after the other: every thread of the block forms the same slot
+          auto weight = [&](int k) { return (unsigned)K.clip_weights[clip_id(K.bank_clips[(size_t)k * N + e])] & 0xFFFFu; };
+          unsigned S = 0;
+          for (int k = 0; k < K.num_slots; ++k) S += weight(k);
+          if (S != 0) {
+            const unsigned h = rr_fmix32(rr_fmix32(K.seed ^ ((unsigned)e * 0x9E3779B1u)) + n);
+            const unsigned r = (unsigned)(((unsigned long long)h * (unsigned long long)S) >> 32);
+            unsigned p = 0;
+            drawn = K.num_slots - 1;
+            for (int k = 0; k < K.num_slots; ++k) {
+              p += weight(k);
+              if (p > r) { drawn = k; break; }
+            }
+          }
+        }
+        n = n + 1u;
+      }
+      slot = drawn >= 0 ? drawn : (slot + 1 >= K.num_slots ? 0 : slot + 1);
+    }
+    row = (size_t)slot * N + e;
+    frame = d_out != 0.0f ? K.bank_frames[row] : new_frame;
+    if constexpr (LEVEL >= RR_WRAP_LIBRARY) {
+      if (d_out != 0.0f && K.bank_clips) c = LEVEL >= RR_WRAP_SAMPLING ? clip_id(K.bank_clips[row]) : K.bank_clips[row];
     }
   }
-}
-
-extern "C" int rr_wrap_episode_autoreset(int32_t num_envs, int32_t narr, const float* const* first, float* const* cur, const int32_t* widths,
-                                         const float* prev_done, const float* prev_steps, float* done, float* steps, float* truncation,
-                                         float episode_length, float action_repeat, void* stream) {
-  if (num_envs <= 0 || narr < 0 || narr > RR_WRAP_MAX || !prev_done || !prev_steps || !done || !steps || !truncation)
-    return fail(RR_EINVAL, "rr_wrap_episode_autoreset: bad argument");
-  RRWrapArgs A;
-  memset(&A, 0, sizeof(A));
-  A.narr = narr;
-  for (int i = 0; i < narr; ++i) {
-    if (!first[i] || !cur[i] || widths[i] <= 0) return fail(RR_EINVAL, "rr_wrap_episode_autoreset: null array");
-    A.first[i] = first[i]; A.cur[i] = cur[i]; A.width[i] = widths[i];
+  __syncthreads();                       // every thread has read done[e], cur_frame[e] and clip[e] before thread 0 rewrites them
+  if (threadIdx.x == 0) {
+    steps[e] = s1; truncation[e] = over ? 1.0f - d_env : 0.0f; done[e] = d_out;
+    if constexpr (LEVEL >= RR_WRAP_RESTART) { K.cur_frame[e] = frame; K.slot_out[e] = slot; }
+    if constexpr (LEVEL >= RR_WRAP_LIBRARY) {
+      if (K.clip) K.clip[e] = c;
+    }
+    if constexpr (LEVEL >= RR_WRAP_SAMPLING) {
+      if (K.draws_out) K.draws_out[e] = (int)n;
+      if (K.outcomes) {
+        long long* orow = K.outcomes + 5 * (size_t)c_step;
+        __hip_atomic_fetch_add(orow + 4, 1ll, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (d_out != 0.0f) {
+          __hip_atomic_fetch_add(orow, 1ll, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          __hip_atomic_fetch_add(orow + (failed ? 1 : (d_env != 0.0f ? 2 : 3)), 1ll, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+      }
+    }
   }
-  hipLaunchKernelGGL(rr_wrap_kernel, dim3(num_envs), dim3(256), 0, (hipStream_t)stream, A, prev_done, prev_steps, done, steps, truncation,
-                     episode_length, action_repeat);
-  HIPCHK(hipGetLastError());
-  return RR_OK;
-}
-
-// The same with clip restarts (rr_clip_restart_io's rule, one env step): `first[i]` are banks [num_slots][N][widths[i]], the clip's end joins
-// `over`, and where done the next bank entry and its frame come back.  cur_frame holds the stepped frame and is finished in place.
-__global__ void rr_wrap_restart_kernel(const RRWrapArgs A, const float* __restrict__ prev_done, const float* __restrict__ prev_steps,
-                                       float* __restrict__ done, float* __restrict__ steps, float* __restrict__ truncation,
-                                       float episode_length, float action_repeat, int* __restrict__ cur_frame, const int* __restrict__ bank_frames,
-                                       const int* __restrict__ slot_in, int* __restrict__ slot_out, int num_slots, int track_len, int end_at_clip_end) {
-  const int e = blockIdx.x, N = gridDim.x;
-  const float s0 = prev_done[e] != 0.0f ? 0.0f : prev_steps[e];
-  const float s1 = s0 + action_repeat;
-  const int new_frame = cur_frame[e];
-  const bool over = s1 >= episode_length || (end_at_clip_end && new_frame >= track_len - 1);
-  const float d_env = done[e];
-  const float d_out = over ? 1.0f : d_env;
-  int slot = slot_in[e];
-  slot = slot < 0 ? 0 : (slot > num_slots - 1 ? num_slots - 1 : slot);      // clamped into the bank
-  if (d_out != 0.0f) slot = slot + 1 >= num_slots ? 0 : slot + 1;
-  const size_t row = (size_t)slot * N + e;
-  const int frame = d_out != 0.0f ? bank_frames[row] : new_frame;
-  __syncthreads();                       // every thread has read done[e] and cur_frame[e] before thread 0 rewrites them
-  if (threadIdx.x == 0) { steps[e] = s1; truncation[e] = over ? 1.0f - d_env : 0.0f; done[e] = d_out; cur_frame[e] = frame; slot_out[e] = slot; }
   if (d_out != 0.0f) {
     for (int a = 0; a < A.narr; ++a) {
       const int w = A.width[a];
@@ -1535,6 +1576,39 @@ __global__ void rr_wrap_restart_kernel(const RRWrapArgs A, const float* __restri
       for (int i = threadIdx.x; i < w; i += blockDim.x) dst[i] = src[i];
     }
   }
+}
+
+// The checks of every entry `who` in their one order -- the scalar arguments and required pointers, num_slots, the entry's own refusal
+// `why` (null: none), the arrays -- and the launch.
+template <int LEVEL>
+static int wrap_launch(const char* who, int32_t num_envs, int32_t narr, const float* const* first, float* const* cur, const int32_t* widths,
+                       const float* prev_done, const float* prev_steps, float* done, float* steps, float* truncation,
+                       float episode_length, float action_repeat, const RRWrapClip& K, const char* why, void* stream) {
+  const std::string name = std::string(who) + ": ";
+  if (num_envs <= 0 || narr < 0 || narr > RR_WRAP_MAX || !prev_done || !prev_steps || !done || !steps || !truncation ||
+      (LEVEL >= RR_WRAP_RESTART && (!K.cur_frame || !K.bank_frames || !K.slot_in || !K.slot_out || K.track_len <= 0)) ||
+      (LEVEL >= RR_WRAP_SAMPLING && K.num_clips < 1) || (LEVEL >= RR_WRAP_LIBRARY && K.bank_clips && !K.clip))
+    return fail(RR_EINVAL, name + "bad argument");
+  if (LEVEL >= RR_WRAP_RESTART && (K.num_slots < 1 || K.num_slots > 64)) return fail(RR_EINVAL, name + "num_slots must lie in 1 .. 64");
+  if (why) return fail(RR_EINVAL, name + why);
+  RRWrapArgs A;
+  memset(&A, 0, sizeof(A));
+  A.narr = narr;
+  for (int i = 0; i < narr; ++i) {
+    if (!first[i] || !cur[i] || widths[i] <= 0) return fail(RR_EINVAL, name + "null array");
+    A.first[i] = first[i]; A.cur[i] = cur[i]; A.width[i] = widths[i];
+  }
+  hipLaunchKernelGGL(rr_wrap_kernel<LEVEL>, dim3(num_envs), dim3(256), 0, (hipStream_t)stream, A, K, prev_done, prev_steps, done, steps, truncation,
+                     episode_length, action_repeat);
+  HIPCHK(hipGetLastError());
+  return RR_OK;
+}
+
+extern "C" int rr_wrap_episode_autoreset(int32_t num_envs, int32_t narr, const float* const* first, float* const* cur, const int32_t* widths,
+                                         const float* prev_done, const float* prev_steps, float* done, float* steps, float* truncation,
+                                         float episode_length, float action_repeat, void* stream) {
+  return wrap_launch<RR_WRAP_PLAIN>("rr_wrap_episode_autoreset", num_envs, narr, first, cur, widths, prev_done, prev_steps, done, steps, truncation,
+                                    episode_length, action_repeat, RRWrapClip{}, nullptr, stream);
 }
 
 extern "C" int rr_wrap_clip_restart(int32_t num_envs, int32_t narr, const float* const* first, float* const* cur, const int32_t* widths,
@@ -1542,61 +1616,9 @@ extern "C" int rr_wrap_clip_restart(int32_t num_envs, int32_t narr, const float*
                                     float episode_length, float action_repeat, int32_t* cur_frame, const int32_t* bank_frames,
                                     const int32_t* slot_in, int32_t* slot_out, int32_t num_slots, int32_t track_len, int32_t end_at_clip_end,
                                     void* stream) {
-  if (num_envs <= 0 || narr < 0 || narr > RR_WRAP_MAX || !prev_done || !prev_steps || !done || !steps || !truncation || !cur_frame || !bank_frames ||
-      !slot_in || !slot_out || track_len <= 0)
-    return fail(RR_EINVAL, "rr_wrap_clip_restart: bad argument");
-  if (num_slots < 1 || num_slots > 64) return fail(RR_EINVAL, "rr_wrap_clip_restart: num_slots must lie in 1 .. 64");
-  RRWrapArgs A;
-  memset(&A, 0, sizeof(A));
-  A.narr = narr;
-  for (int i = 0; i < narr; ++i) {
-    if (!first[i] || !cur[i] || widths[i] <= 0) return fail(RR_EINVAL, "rr_wrap_clip_restart: null array");
-    A.first[i] = first[i]; A.cur[i] = cur[i]; A.width[i] = widths[i];
-  }
-  hipLaunchKernelGGL(rr_wrap_restart_kernel, dim3(num_envs), dim3(256), 0, (hipStream_t)stream, A, prev_done, prev_steps, done, steps, truncation,
-                     episode_length, action_repeat, cur_frame, bank_frames, slot_in, slot_out, num_slots, track_len, end_at_clip_end);
-  HIPCHK(hipGetLastError());
-  return RR_OK;
-}
-
-// The same with the clip library (rr_clip_library_io's rule, one env step): the clip's end is taken at the length of the clip the step
-// was made on, and where done the bank entry's clip comes back with its frame.  clip is finished in place; null pointers switch the
-// two additions off one by one.
-__global__ void rr_wrap_library_kernel(const RRWrapArgs A, const float* __restrict__ prev_done, const float* __restrict__ prev_steps,
-                                       float* __restrict__ done, float* __restrict__ steps, float* __restrict__ truncation,
-                                       float episode_length, float action_repeat, int* __restrict__ cur_frame, const int* __restrict__ bank_frames,
-                                       const int* __restrict__ slot_in, int* __restrict__ slot_out, int num_slots, int track_len, int end_at_clip_end,
-                                       int* __restrict__ clip, const int* __restrict__ bank_clips, const int* __restrict__ clip_lengths) {
-  const int e = blockIdx.x, N = gridDim.x;
-  const float s0 = prev_done[e] != 0.0f ? 0.0f : prev_steps[e];
-  const float s1 = s0 + action_repeat;
-  const int new_frame = cur_frame[e];
-  int c = clip ? clip[e] : 0;
-  c = c < 0 ? 0 : c;
-  int len = track_len;
-  if (clip_lengths) { len = clip_lengths[c]; len = len < 1 ? 1 : (len > track_len ? track_len : len); }
-  const bool over = s1 >= episode_length || (end_at_clip_end && new_frame >= len - 1);
-  const float d_env = done[e];
-  const float d_out = over ? 1.0f : d_env;
-  int slot = slot_in[e];
-  slot = slot < 0 ? 0 : (slot > num_slots - 1 ? num_slots - 1 : slot);      // clamped into the bank
-  if (d_out != 0.0f) slot = slot + 1 >= num_slots ? 0 : slot + 1;
-  const size_t row = (size_t)slot * N + e;
-  const int frame = d_out != 0.0f ? bank_frames[row] : new_frame;
-  if (d_out != 0.0f && bank_clips) c = bank_clips[row];
-  __syncthreads();                       // every thread has read done[e], cur_frame[e] and clip[e] before thread 0 rewrites them
-  if (threadIdx.x == 0) {
-    steps[e] = s1; truncation[e] = over ? 1.0f - d_env : 0.0f; done[e] = d_out; cur_frame[e] = frame; slot_out[e] = slot;
-    if (clip) clip[e] = c;
-  }
-  if (d_out != 0.0f) {
-    for (int a = 0; a < A.narr; ++a) {
-      const int w = A.width[a];
-      const float* src = A.first[a] + row * w;
-      float* dst = A.cur[a] + (size_t)e * w;
-      for (int i = threadIdx.x; i < w; i += blockDim.x) dst[i] = src[i];
-    }
-  }
+  const RRWrapClip K = {cur_frame, bank_frames, slot_in, slot_out, num_slots, track_len, end_at_clip_end};
+  return wrap_launch<RR_WRAP_RESTART>("rr_wrap_clip_restart", num_envs, narr, first, cur, widths, prev_done, prev_steps, done, steps, truncation,
+                                      episode_length, action_repeat, K, nullptr, stream);
 }
 
 extern "C" int rr_wrap_clip_library(int32_t num_envs, int32_t narr, const float* const* first, float* const* cur, const int32_t* widths,
@@ -1604,100 +1626,9 @@ extern "C" int rr_wrap_clip_library(int32_t num_envs, int32_t narr, const float*
                                     float episode_length, float action_repeat, int32_t* cur_frame, const int32_t* bank_frames,
                                     const int32_t* slot_in, int32_t* slot_out, int32_t num_slots, int32_t track_len, int32_t end_at_clip_end,
                                     int32_t* clip, const int32_t* bank_clips, const int32_t* clip_lengths, void* stream) {
-  if (num_envs <= 0 || narr < 0 || narr > RR_WRAP_MAX || !prev_done || !prev_steps || !done || !steps || !truncation || !cur_frame || !bank_frames ||
-      !slot_in || !slot_out || track_len <= 0 || (bank_clips && !clip))
-    return fail(RR_EINVAL, "rr_wrap_clip_library: bad argument");
-  if (num_slots < 1 || num_slots > 64) return fail(RR_EINVAL, "rr_wrap_clip_library: num_slots must lie in 1 .. 64");
-  RRWrapArgs A;
-  memset(&A, 0, sizeof(A));
-  A.narr = narr;
-  for (int i = 0; i < narr; ++i) {
-    if (!first[i] || !cur[i] || widths[i] <= 0) return fail(RR_EINVAL, "rr_wrap_clip_library: null array");
-    A.first[i] = first[i]; A.cur[i] = cur[i]; A.width[i] = widths[i];
-  }
-  hipLaunchKernelGGL(rr_wrap_library_kernel, dim3(num_envs), dim3(256), 0, (hipStream_t)stream, A, prev_done, prev_steps, done, steps, truncation,
-                     episode_length, action_repeat, cur_frame, bank_frames, slot_in, slot_out, num_slots, track_len, end_at_clip_end,
-                     clip, bank_clips, clip_lengths);
-  HIPCHK(hipGetLastError());
-  return RR_OK;
-}
-
-// The same with clip sampling (rr_clip_sampling_io's rule, one env step): the outcome counters of the step -- on the clip it was made
-// on, flushed every step -- and, where done, the slot drawn by the env's bank weights instead of the next one.  pose_fail: the step's
-// pose-termination codes (null: none).  Null outcomes / clip_weights switch the two additions off one by one.
-__global__ void rr_wrap_sampling_kernel(const RRWrapArgs A, const float* __restrict__ prev_done, const float* __restrict__ prev_steps,
-                                        float* __restrict__ done, float* __restrict__ steps, float* __restrict__ truncation,
-                                        float episode_length, float action_repeat, int* __restrict__ cur_frame, const int* __restrict__ bank_frames,
-                                        const int* __restrict__ slot_in, int* __restrict__ slot_out, int num_slots, int track_len, int end_at_clip_end,
-                                        int* __restrict__ clip, const int* __restrict__ bank_clips, const int* __restrict__ clip_lengths, int num_clips,
-                                        const float* __restrict__ pose_fail, const int* __restrict__ clip_weights, const int* __restrict__ draws_in,
-                                        int* __restrict__ draws_out, long long* __restrict__ outcomes, unsigned seed) {
-  const int e = blockIdx.x, N = gridDim.x;
-  const float s0 = prev_done[e] != 0.0f ? 0.0f : prev_steps[e];
-  const float s1 = s0 + action_repeat;
-  const int new_frame = cur_frame[e];
-  int c = clip ? clip[e] : 0;
-  c = c < 0 ? 0 : (c > num_clips - 1 ? num_clips - 1 : c);
-  const int c_step = c;                  // the clip the step was made on
-  int len = track_len;
-  if (clip_lengths) { len = clip_lengths[c]; len = len < 1 ? 1 : (len > track_len ? track_len : len); }
-  const bool over = s1 >= episode_length || (end_at_clip_end && new_frame >= len - 1);
-  const float d_env = done[e];
-  const float d_out = over ? 1.0f : d_env;
-  const bool failed = pose_fail && pose_fail[e] != 0.0f;
-  unsigned n = draws_in ? (unsigned)draws_in[e] : 0u;
-  int slot = slot_in[e];
-  slot = slot < 0 ? 0 : (slot > num_slots - 1 ? num_slots - 1 : slot);      // clamped into the bank
-  if (d_out != 0.0f) {
-    int drawn = -1;
-    if (clip_weights && bank_clips) {      // the K entries one after the other: every thread of the block forms the same slot
-      unsigned S = 0;
-      for (int k = 0; k < num_slots; ++k) {
-        int ck = bank_clips[(size_t)k * N + e];
-        ck = ck < 0 ? 0 : (ck > num_clips - 1 ? num_clips - 1 : ck);
-        S += (unsigned)clip_weights[ck] & 0xFFFFu;
-      }
-      if (S != 0) {
-        const unsigned h = rr_fmix32(rr_fmix32(seed ^ ((unsigned)e * 0x9E3779B1u)) + n);
-        const unsigned r = (unsigned)(((unsigned long long)h * (unsigned long long)S) >> 32);
-        unsigned p = 0;
-        drawn = num_slots - 1;
-        for (int k = 0; k < num_slots; ++k) {
-          int ck = bank_clips[(size_t)k * N + e];
-          ck = ck < 0 ? 0 : (ck > num_clips - 1 ? num_clips - 1 : ck);
-          p += (unsigned)clip_weights[ck] & 0xFFFFu;
-          if (p > r) { drawn = k; break; }
-        }
-      }
-    }
-    n = n + 1u;
-    slot = drawn >= 0 ? drawn : (slot + 1 >= num_slots ? 0 : slot + 1);
-  }
-  const size_t row = (size_t)slot * N + e;
-  const int frame = d_out != 0.0f ? bank_frames[row] : new_frame;
-  if (d_out != 0.0f && bank_clips) { c = bank_clips[row]; c = c < 0 ? 0 : (c > num_clips - 1 ? num_clips - 1 : c); }
-  __syncthreads();                       // every thread has read done[e], cur_frame[e] and clip[e] before thread 0 rewrites them
-  if (threadIdx.x == 0) {
-    steps[e] = s1; truncation[e] = over ? 1.0f - d_env : 0.0f; done[e] = d_out; cur_frame[e] = frame; slot_out[e] = slot;
-    if (clip) clip[e] = c;
-    if (draws_out) draws_out[e] = (int)n;
-    if (outcomes) {
-      long long* orow = outcomes + 5 * (size_t)c_step;
-      __hip_atomic_fetch_add(orow + 4, 1ll, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (d_out != 0.0f) {
-        __hip_atomic_fetch_add(orow, 1ll, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_fetch_add(orow + (failed ? 1 : (d_env != 0.0f ? 2 : 3)), 1ll, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-    }
-  }
-  if (d_out != 0.0f) {
-    for (int a = 0; a < A.narr; ++a) {
-      const int w = A.width[a];
-      const float* src = A.first[a] + row * w;
-      float* dst = A.cur[a] + (size_t)e * w;
-      for (int i = threadIdx.x; i < w; i += blockDim.x) dst[i] = src[i];
-    }
-  }
+  const RRWrapClip K = {cur_frame, bank_frames, slot_in, slot_out, num_slots, track_len, end_at_clip_end, clip, bank_clips, clip_lengths};
+  return wrap_launch<RR_WRAP_LIBRARY>("rr_wrap_clip_library", num_envs, narr, first, cur, widths, prev_done, prev_steps, done, steps, truncation,
+                                      episode_length, action_repeat, K, nullptr, stream);
 }
 
 extern "C" int rr_wrap_clip_sampling(int32_t num_envs, int32_t narr, const float* const* first, float* const* cur, const int32_t* widths,
@@ -1706,26 +1637,15 @@ extern "C" int rr_wrap_clip_sampling(int32_t num_envs, int32_t narr, const float
                                      const int32_t* slot_in, int32_t* slot_out, int32_t num_slots, int32_t track_len, int32_t end_at_clip_end,
                                      int32_t* clip, const int32_t* bank_clips, const int32_t* clip_lengths, int32_t num_clips,
                                      const float* pose_fail, const rr_clip_sampling_io* sampling, void* stream) {
-  if (num_envs <= 0 || narr < 0 || narr > RR_WRAP_MAX || !prev_done || !prev_steps || !done || !steps || !truncation || !cur_frame || !bank_frames ||
-      !slot_in || !slot_out || track_len <= 0 || num_clips < 1 || (bank_clips && !clip) || !sampling)
-    return fail(RR_EINVAL, "rr_wrap_clip_sampling: bad argument");
-  if (num_slots < 1 || num_slots > 64) return fail(RR_EINVAL, "rr_wrap_clip_sampling: num_slots must lie in 1 .. 64");
-  if (!sampling->clip_weights && !sampling->outcomes) return fail(RR_EINVAL, "rr_wrap_clip_sampling: null clip_weights and outcomes");
-  if (sampling->clip_weights && (!bank_clips || !sampling->draws_in || !sampling->draws_out)) return fail(RR_EINVAL, "rr_wrap_clip_sampling: clip_weights needs bank_clips, draws_in and draws_out");
-  if (sampling->outcomes && num_clips > 1 && !clip) return fail(RR_EINVAL, "rr_wrap_clip_sampling: outcomes of several clips need clip");
-  RRWrapArgs A;
-  memset(&A, 0, sizeof(A));
-  A.narr = narr;
-  for (int i = 0; i < narr; ++i) {
-    if (!first[i] || !cur[i] || widths[i] <= 0) return fail(RR_EINVAL, "rr_wrap_clip_sampling: null array");
-    A.first[i] = first[i]; A.cur[i] = cur[i]; A.width[i] = widths[i];
-  }
-  hipLaunchKernelGGL(rr_wrap_sampling_kernel, dim3(num_envs), dim3(256), 0, (hipStream_t)stream, A, prev_done, prev_steps, done, steps, truncation,
-                     episode_length, action_repeat, cur_frame, bank_frames, slot_in, slot_out, num_slots, track_len, end_at_clip_end,
-                     clip, bank_clips, clip_lengths, num_clips, pose_fail, sampling->clip_weights, sampling->draws_in, sampling->draws_out,
-                     (long long*)sampling->outcomes, sampling->seed);
-  HIPCHK(hipGetLastError());
-  return RR_OK;
+  if (!sampling) return fail(RR_EINVAL, "rr_wrap_clip_sampling: bad argument");      // (the first check's answer, whatever else is wrong)
+  const rr_clip_sampling_io& s = *sampling;
+  const char* why = !s.clip_weights && !s.outcomes ? "null clip_weights and outcomes"
+                    : s.clip_weights && (!bank_clips || !s.draws_in || !s.draws_out) ? "clip_weights needs bank_clips, draws_in and draws_out"
+                    : s.outcomes && num_clips > 1 && !clip ? "outcomes of several clips need clip" : nullptr;
+  const RRWrapClip K = {cur_frame, bank_frames, slot_in, slot_out, num_slots, track_len, end_at_clip_end, clip, bank_clips, clip_lengths,
+                        num_clips, pose_fail, s.clip_weights, s.draws_in, s.draws_out, (long long*)s.outcomes, s.seed};
+  return wrap_launch<RR_WRAP_SAMPLING>("rr_wrap_clip_sampling", num_envs, narr, first, cur, widths, prev_done, prev_steps, done, steps, truncation,
+                                       episode_length, action_repeat, K, why, stream);
 }
 
 extern "C" int rr_debug_layout(const rr_batch* b, const char*** names, const int32_t** offsets, const int32_t** sizes) {

@@ -333,56 +333,47 @@ class FusedEpisodeAutoResetWrapper(Wrapper):
         from .. import hip
         nstate = self.env.step(state, action)              # fresh tensors: safe to finish in place
         base = _base(self.env)
-        if getattr(base, "clip_restarts", 0) >= 1:         # clip restarts: the rule of the two Clip wrappers in one launch
-            bank, ps = nstate.info["restart_bank"], nstate.pipeline_state
-            names = [f.name for f in dataclasses.fields(ps) if torch.is_tensor(getattr(ps, f.name))]
-            first = [getattr(bank["pipeline_state"], n) for n in names] + [bank["obs"]]
-            cur = [getattr(ps, n) for n in names] + [nstate.obs]
-            steps, trunc = torch.empty_like(nstate.done), torch.empty_like(nstate.done)
-            slot = torch.empty_like(state.info["restart_slot"])
-            lengths = getattr(base, "clip_lengths", None)
-            sampling = getattr(base, "clip_sampling", None)
-            ref = getattr(base, "restart_from_reference", False)
-            if ref:      # reference restarts: the rule below with the cyclic slot (its restore is replaced after it), the counters as they are
-                sampling = None if sampling is None or sampling["outcomes"] is None else dict(sampling, weights=None)
-            if sampling is not None:      # clip sampling: the library's rule plus the counters and the weighted draw
-                clip = state.info["clip"].clone() if "clip" in state.info else None
-                draws = state.info.get("restart_draws")
-                ndraws = None if draws is None else torch.empty_like(draws)
-                hip.wrap_clip_sampling(first, cur, state.done, state.info["steps"], nstate.done, steps, trunc, self.episode_length, 1,
-                                       nstate.info["cur_frame"], bank["frame"], state.info["restart_slot"], slot, base.track_len, base.end_at_clip_end,
-                                       base.num_clips, clip, bank.get("clip"), lengths, nstate.metrics.get("pose_fail"), sampling["weights"],
-                                       draws, ndraws, sampling["outcomes"], sampling["seed"])
-                if clip is not None:
-                    nstate.info["clip"] = clip
-                if ndraws is not None:
-                    nstate.info["restart_draws"] = ndraws
-            elif lengths is not None or "clip" in bank:      # the clip library: the env's own clip's end, the entry's clip with its frame
-                clip = state.info["clip"].clone() if "clip" in state.info else None      # the bare step leaves the ids alone: finished in a copy
-                hip.wrap_clip_library(first, cur, state.done, state.info["steps"], nstate.done, steps, trunc, self.episode_length, 1,
-                                      nstate.info["cur_frame"], bank["frame"], state.info["restart_slot"], slot, base.track_len, base.end_at_clip_end,
-                                      clip, bank.get("clip"), lengths)
-                if clip is not None:
-                    nstate.info["clip"] = clip
-            else:
-                hip.wrap_clip_restart(first, cur, state.done, state.info["steps"], nstate.done, steps, trunc, self.episode_length, 1,
-                                      nstate.info["cur_frame"], bank["frame"], state.info["restart_slot"], slot, base.track_len, base.end_at_clip_end)
-            nstate.info.update(steps=steps, truncation=trunc, restart_slot=slot)
-            if ref:      # where done, the bank entry the launch above restored gives way to the freshly drawn start state
-                for k in ("clip", "restart_draws"):
-                    if k in state.info:
-                        nstate.info[k] = state.info[k]
-                return _reference_restore(base, nstate, nstate.done.bool(), slot)
-            return nstate
-        fps, ps = nstate.info["first_pipeline_state"], nstate.pipeline_state
+        restarts = getattr(base, "clip_restarts", 0) >= 1  # clip restarts: the rule of the two Clip wrappers, the stored states a bank
+        if restarts:
+            bank = nstate.info["restart_bank"]
+            fps, fobs = bank["pipeline_state"], bank["obs"]
+        else:
+            fps, fobs = nstate.info["first_pipeline_state"], nstate.info["first_obs"]
+        ps = nstate.pipeline_state
         names = [f.name for f in dataclasses.fields(ps) if torch.is_tensor(getattr(ps, f.name))]
-        first = [getattr(fps, n) for n in names] + [nstate.info["first_obs"]]
+        first = [getattr(fps, n) for n in names] + [fobs]
         cur = [getattr(ps, n) for n in names] + [nstate.obs]
         steps, trunc = torch.empty_like(nstate.done), torch.empty_like(nstate.done)
-        hip.wrap_episode_autoreset(first, cur, state.done, state.info["steps"], nstate.done, steps, trunc,
-                                   self.episode_length, 1)
-        nstate.info["steps"] = steps
-        nstate.info["truncation"] = trunc
+        common = (first, cur, state.done, state.info["steps"], nstate.done, steps, trunc, self.episode_length, 1)
+        nstate.info.update(steps=steps, truncation=trunc)
+        if not restarts:
+            hip.wrap_episode_autoreset(*common)
+            return nstate
+        slot = torch.empty_like(state.info["restart_slot"])
+        lengths = getattr(base, "clip_lengths", None)
+        sampling = getattr(base, "clip_sampling", None)
+        ref = getattr(base, "restart_from_reference", False)
+        if ref:      # reference restarts: the rule below with the cyclic slot (its restore is replaced after it), the counters as they are
+            sampling = None if sampling is None or sampling["outcomes"] is None else dict(sampling, weights=None)
+        # the clip library (the env's own clip's end, the entry's clip with its frame) and clip sampling (the counters and the weighted draw on
+        # top of it) finish the clip ids, in a copy: the bare step leaves them alone
+        library = lengths is not None or "clip" in bank or sampling is not None
+        clip = state.info["clip"].clone() if library and "clip" in state.info else None
+        draws = state.info.get("restart_draws") if sampling is not None else None
+        ndraws = None if draws is None else torch.empty_like(draws)
+        weights, outcomes, seed = (sampling["weights"], sampling["outcomes"], sampling["seed"]) if sampling is not None else (None, None, 0)
+        hip.wrap_clip(*common, nstate.info["cur_frame"], bank["frame"], state.info["restart_slot"], slot, base.track_len, base.end_at_clip_end,
+                      clip, bank.get("clip"), lengths, base.num_clips, nstate.metrics.get("pose_fail"), weights, draws, ndraws, outcomes, seed)
+        nstate.info["restart_slot"] = slot
+        if clip is not None:
+            nstate.info["clip"] = clip
+        if ndraws is not None:
+            nstate.info["restart_draws"] = ndraws
+        if ref:      # where done, the bank entry the launch above restored gives way to the freshly drawn start state
+            for k in ("clip", "restart_draws"):
+                if k in state.info:
+                    nstate.info[k] = state.info[k]
+            return _reference_restore(base, nstate, nstate.done.bool(), slot)
         return nstate
 
 

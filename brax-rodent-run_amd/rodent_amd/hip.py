@@ -850,96 +850,60 @@ def compute_gae(truncation, termination, rewards, values, bootstrap_value, lambd
     return vs, adv
 
 
+def _wrap_common(first, cur, prev_done, prev_steps, done, steps, truncation, K=None):
+    """The head every per-step wrapper entry takes: (N, narr, first[], cur[], widths[]) and the current stream.  `first` holds states
+    [N, ...] like `cur` (K None) or banks [K, N, ...]."""
+    n = len(cur)
+    N = done.numel()
+    for t in list(first) + list(cur) + [prev_done, prev_steps, done, steps, truncation]:
+        _ptr(t)
+    for f, c in zip(first, cur):
+        if K is None and f.shape != c.shape:
+            raise ValueError("first / current state shapes differ")
+        if K is not None and tuple(f.shape) != (K,) + tuple(c.shape):
+            raise ValueError("bank / current state shapes differ")
+    F = (C.c_void_p * n)(*[t.data_ptr() for t in first])
+    Cu = (C.c_void_p * n)(*[t.data_ptr() for t in cur])
+    W = (C.c_int32 * n)(*[t.numel() // N for t in cur])
+    return (N, n, F, Cu, W), C.c_void_p(torch.cuda.current_stream(done.device).cuda_stream)
+
+
 def wrap_episode_autoreset(first, cur, prev_done, prev_steps, done, steps, truncation, episode_length: float, action_repeat: float):
     """Fused EpisodeWrapper + AutoResetWrapper bookkeeping (C ABI `rr_wrap_episode_autoreset`): `first` / `cur` are equally
     long lists of contiguous float32 device tensors with a leading env axis; `cur`, `done`, `steps`, `truncation` are written."""
-    n = len(cur)
-    N = done.numel()
-    for t in list(first) + list(cur) + [prev_done, prev_steps, done, steps, truncation]:
-        _ptr(t)
-    F = (C.c_void_p * n)(*[t.data_ptr() for t in first])
-    Cu = (C.c_void_p * n)(*[t.data_ptr() for t in cur])
-    W = (C.c_int32 * n)(*[t.numel() // N for t in cur])
-    for f, c in zip(first, cur):
-        if f.shape != c.shape:
-            raise ValueError("first / current state shapes differ")
-    stream = torch.cuda.current_stream(done.device).cuda_stream
-    _check(lib().rr_wrap_episode_autoreset(N, n, F, Cu, W, prev_done.data_ptr(), prev_steps.data_ptr(), done.data_ptr(), steps.data_ptr(),
-                                           truncation.data_ptr(), float(episode_length), float(action_repeat), C.c_void_p(stream)))
+    head, stream = _wrap_common(first, cur, prev_done, prev_steps, done, steps, truncation)
+    _check(lib().rr_wrap_episode_autoreset(*head, prev_done.data_ptr(), prev_steps.data_ptr(), done.data_ptr(), steps.data_ptr(),
+                                           truncation.data_ptr(), float(episode_length), float(action_repeat), stream))
 
 
-def wrap_clip_restart(first, cur, prev_done, prev_steps, done, steps, truncation, episode_length: float, action_repeat: float,
-                      cur_frame, bank_frames, slot_in, slot_out, track_len: int, end_at_clip_end: bool):
-    """`wrap_episode_autoreset` for an env with clip restarts (C ABI `rr_wrap_clip_restart`): `first` are banks [K, N, ...], `cur_frame`
-    int32 [N] holds the stepped frame and is finished in place, `bank_frames` int32 [K, N], `slot_in` / `slot_out` int32 [N]."""
-    n = len(cur)
-    N = done.numel()
+def wrap_clip(first, cur, prev_done, prev_steps, done, steps, truncation, episode_length: float, action_repeat: float,
+              cur_frame, bank_frames, slot_in, slot_out, track_len: int, end_at_clip_end: bool, clip=None, bank_clips=None, lengths=None,
+              num_clips=None, pose_fail=None, weights=None, draws_in=None, draws_out=None, outcomes=None, seed: int = 0):
+    """`wrap_episode_autoreset` for an env with clip restarts: `first` are banks [K, N, ...], `cur_frame` int32 [N] holds the stepped
+    frame and is finished in place, `bank_frames` int32 [K, N], `slot_in` / `slot_out` int32 [N].
+    The clip library: `clip` int32 [N], the clip each env made the step on, finished in place (the bank entry's clip where done);
+    `bank_clips` int32 [K, N] or None; `lengths` int32 [C] or None -- the clip's end is taken at the env's own clip's length.
+    Clip sampling (needs `num_clips` C): `weights` int32 [C] or None with `draws_in` / `draws_out` int32 [N]; `outcomes` int64 [C, 5] or
+    None, added to in place; `pose_fail` float [N] or None, the step's pose-termination codes; `seed` the draw's seed.
+    The call goes to the narrowest C entry that serves what was passed -- `rr_wrap_clip_restart`, with `bank_clips` or `lengths`
+    `rr_wrap_clip_library`, with `weights` or `outcomes` `rr_wrap_clip_sampling` -- and arguments of a wider entry are not read."""
     K = bank_frames.shape[0]
-    for t in list(first) + list(cur) + [prev_done, prev_steps, done, steps, truncation]:
-        _ptr(t)
-    for f, c in zip(first, cur):
-        if tuple(f.shape) != (K,) + tuple(c.shape):
-            raise ValueError("bank / current state shapes differ")
-    F = (C.c_void_p * n)(*[t.data_ptr() for t in first])
-    Cu = (C.c_void_p * n)(*[t.data_ptr() for t in cur])
-    W = (C.c_int32 * n)(*[t.numel() // N for t in cur])
-    stream = torch.cuda.current_stream(done.device).cuda_stream
-    _check(lib().rr_wrap_clip_restart(N, n, F, Cu, W, prev_done.data_ptr(), prev_steps.data_ptr(), done.data_ptr(), steps.data_ptr(),
-                                      truncation.data_ptr(), float(episode_length), float(action_repeat), _ptr(cur_frame, torch.int32, N),
-                                      _ptr(bank_frames, torch.int32, K * N), _ptr(slot_in, torch.int32, N), _ptr(slot_out, torch.int32, N),
-                                      int(K), int(track_len), int(bool(end_at_clip_end)), C.c_void_p(stream)))
-
-
-def wrap_clip_library(first, cur, prev_done, prev_steps, done, steps, truncation, episode_length: float, action_repeat: float,
-                      cur_frame, bank_frames, slot_in, slot_out, track_len: int, end_at_clip_end: bool, clip=None, bank_clips=None, lengths=None):
-    """`wrap_clip_restart` with the clip library (C ABI `rr_wrap_clip_library`): `clip` int32 [N], the clip each env made the step on,
-    finished in place (the bank entry's clip where done); `bank_clips` int32 [K, N] or None; `lengths` int32 [C] or None -- the clip's
-    end is taken at the env's own clip's length."""
-    n = len(cur)
-    N = done.numel()
-    K = bank_frames.shape[0]
-    for t in list(first) + list(cur) + [prev_done, prev_steps, done, steps, truncation]:
-        _ptr(t)
-    for f, c in zip(first, cur):
-        if tuple(f.shape) != (K,) + tuple(c.shape):
-            raise ValueError("bank / current state shapes differ")
-    F = (C.c_void_p * n)(*[t.data_ptr() for t in first])
-    Cu = (C.c_void_p * n)(*[t.data_ptr() for t in cur])
-    W = (C.c_int32 * n)(*[t.numel() // N for t in cur])
-    stream = torch.cuda.current_stream(done.device).cuda_stream
-    _check(lib().rr_wrap_clip_library(N, n, F, Cu, W, prev_done.data_ptr(), prev_steps.data_ptr(), done.data_ptr(), steps.data_ptr(),
-                                      truncation.data_ptr(), float(episode_length), float(action_repeat), _ptr(cur_frame, torch.int32, N),
-                                      _ptr(bank_frames, torch.int32, K * N), _ptr(slot_in, torch.int32, N), _ptr(slot_out, torch.int32, N),
-                                      int(K), int(track_len), int(bool(end_at_clip_end)), _ptr(clip, torch.int32, N),
-                                      _ptr(bank_clips, torch.int32, K * N), _ptr(lengths, torch.int32), C.c_void_p(stream)))
-
-
-def wrap_clip_sampling(first, cur, prev_done, prev_steps, done, steps, truncation, episode_length: float, action_repeat: float,
-                       cur_frame, bank_frames, slot_in, slot_out, track_len: int, end_at_clip_end: bool, num_clips: int, clip=None, bank_clips=None,
-                       lengths=None, pose_fail=None, weights=None, draws_in=None, draws_out=None, outcomes=None, seed: int = 0):
-    """`wrap_clip_library` with clip sampling (C ABI `rr_wrap_clip_sampling`): `num_clips` C; `pose_fail` float [N] or None, the step's
-    pose-termination codes; `weights` int32 [C] or None with `draws_in` / `draws_out` int32 [N]; `outcomes` int64 [C, 5] or None, added
-    to in place; `seed` the draw's seed."""
-    n = len(cur)
-    N = done.numel()
-    K = bank_frames.shape[0]
-    for t in list(first) + list(cur) + [prev_done, prev_steps, done, steps, truncation]:
-        _ptr(t)
-    for f, c in zip(first, cur):
-        if tuple(f.shape) != (K,) + tuple(c.shape):
-            raise ValueError("bank / current state shapes differ")
-    F = (C.c_void_p * n)(*[t.data_ptr() for t in first])
-    Cu = (C.c_void_p * n)(*[t.data_ptr() for t in cur])
-    W = (C.c_int32 * n)(*[t.numel() // N for t in cur])
-    stream = torch.cuda.current_stream(done.device).cuda_stream
+    head, stream = _wrap_common(first, cur, prev_done, prev_steps, done, steps, truncation, K)
+    N = head[0]
+    args = head + (prev_done.data_ptr(), prev_steps.data_ptr(), done.data_ptr(), steps.data_ptr(), truncation.data_ptr(), float(episode_length),
+                   float(action_repeat), _ptr(cur_frame, torch.int32, N), _ptr(bank_frames, torch.int32, K * N), _ptr(slot_in, torch.int32, N),
+                   _ptr(slot_out, torch.int32, N), int(K), int(track_len), int(bool(end_at_clip_end)))
+    sampling, library = weights is not None or outcomes is not None, bank_clips is not None or lengths is not None
+    if not sampling and not library:
+        _check(lib().rr_wrap_clip_restart(*args, stream))
+        return
+    args += (_ptr(clip, torch.int32, N), _ptr(bank_clips, torch.int32, K * N), _ptr(lengths, torch.int32))
+    if not sampling:
+        _check(lib().rr_wrap_clip_library(*args, stream))
+        return
     block = RRClipSamplingIO(_ptr(weights, torch.int32, int(num_clips)), _ptr(draws_in, torch.int32, N), _ptr(draws_out, torch.int32, N),
                              _ptr(outcomes, torch.int64, 5 * int(num_clips)), int(seed) & 0xFFFFFFFF)
-    _check(lib().rr_wrap_clip_sampling(N, n, F, Cu, W, prev_done.data_ptr(), prev_steps.data_ptr(), done.data_ptr(), steps.data_ptr(),
-                                       truncation.data_ptr(), float(episode_length), float(action_repeat), _ptr(cur_frame, torch.int32, N),
-                                       _ptr(bank_frames, torch.int32, K * N), _ptr(slot_in, torch.int32, N), _ptr(slot_out, torch.int32, N),
-                                       int(K), int(track_len), int(bool(end_at_clip_end)), _ptr(clip, torch.int32, N),
-                                       _ptr(bank_clips, torch.int32, K * N), _ptr(lengths, torch.int32), int(num_clips),
-                                       _ptr(pose_fail, numel=N), C.byref(block), C.c_void_p(stream)))
+    _check(lib().rr_wrap_clip_sampling(*args, int(num_clips), _ptr(pose_fail, numel=N), C.byref(block), stream))
 
 
 def _mlp_net(weights, biases, in_dim=None):

@@ -516,5 +516,5 @@ def test_no_new_instance_and_the_restart_kernel_keeps_its_budget(all_kernels):
     for k in restart:
         print(k["name"], "vgpr", k["vgpr"], "sgpr_spill", k["sgpr_spill"])
         assert k["vgpr"] <= 256 and k["scratch"] == 0 and k["vgpr_spill"] == 0 and k["lds"] == 0, k
-    wrap = [k for k in all_kernels if "rr_wrap_sampling_kernel" in k["name"]]
+    wrap = [k for k in all_kernels if "rr_wrap_kernelILi3EE" in k["name"]]      # the sampling level of the per-step wrapper's template
     assert len(wrap) == 1 and wrap[0]["scratch"] == 0 and wrap[0]["lds"] == 0
