@@ -136,9 +136,10 @@ static Instance select(const rr_model* m, Form form, Variant v, const rr_batch* 
     if (!s221) return no("only the (2,2,1) slot counts have instances with per-env parameters");
   } else if (unroll && (newton || !s221))
     return no("rr_env_unroll: no multi-step kernel instance for this model / solver");
-  if (m->dyn) {      // candidate-pair contacts: the production instances (generic dimensions); no debug dump, no profile build
-    if (v != V_PROD) return no(no_diag);
+  if (m->dyn) {      // candidate-pair contacts: the production instances and the single-step debug dump (generic dimensions); no profile build
+    if (v != V_PROD && (v != V_DEBUG || newton || !s221)) return no(no_diag);
     if (newton || !s221) return no(no_slots);
+    if (v == V_DEBUG) return Instance{rr_step_kernel<2, 2, 1, false, true, RRDims, false, false, false, false, true>};      // multi-step forms: refused above
     if (eval) return Instance{rr_eval_kernel<RRDims, true>};
     return Instance{actor ? rr_step_kernel<2, 2, 1, false, false, RRDims, false, true, true, false, true>
                     : (unroll ? rr_step_kernel<2, 2, 1, false, false, RRDims, false, true, false, false, true> : rr_step_kernel<2, 2, 1, false, false, RRDims, false, false, false, false, true>)};
@@ -215,6 +216,10 @@ static void layout(rr_model* m) {
   // 1 = iteration cap, 2 = improvement below the tolerance, 4 = gradient below the tolerance
   k.g_solver_end = dbg("solver_end", 2);
   k.g_kaok = dbg("kernarg_ok", 1);
+  // candidate-pair models: the scan's count before the clamp to the slots, and the pair id held by each slot (-1 beyond the count); the
+  // kernel finds both behind kernarg_ok (contact_geometry_dyn), so RRDims carries no offset for them
+  static_assert(RR_DBG_PEN_COUNT == 1 && RR_DBG_SLOT_PAIR == RR_DBG_PEN_COUNT + 1, "pen_count (1 float) and slot_pair follow kernarg_ok (1 float) in this order");
+  if (m->dyn) { dbg("pen_count", 1); dbg("slot_pair", m->NCS * RR_LANES); }
   k.dbg_floats = g;
   for (auto& s : m->dbg_names) m->dbg_cnames.push_back(s.c_str());
   m->dims.lds_bytes = L.lds_floats * (int)sizeof(float);

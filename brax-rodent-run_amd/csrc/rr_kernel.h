@@ -19,6 +19,9 @@
 #include "rr_tanh_normal.h"
 
 #define RR_LANES 64
+// debug dump of the candidate-pair models: where pen_count and slot_pair lie, in floats behind kernarg_ok (RRDims carries no offset for
+// them; layout() in rr_api.hip appends the two sections in this order and asserts it)
+constexpr int RR_DBG_PEN_COUNT = 1, RR_DBG_SLOT_PAIR = 2;
 #define RR_DOFI 12   // ints per dof in k_dof_i
 #define RR_BODYI 12  // ints per body in k_body_i
 #ifndef RR_WIDE
@@ -615,8 +618,9 @@ template <class A> struct rr_same<A, A> { static constexpr bool value = true; };
 // substep the wave scans it, keeps the pairs in penetration in its 64 * NCS contact slots (in list order, by ballot), and works on those:
 // J = jac(body2) - jac(body1) through SIGNED dof chains (the dofs on exactly one of the two ancestor chains; J x) and a two-interval
 // membership test (J' f); contacts of condim 1 carry one row (rows 1..3 of the slot get D = 0); transmissions with several joints (fixed
-// tendons) go through per-actuator sums.  Production physics + env epilogue only: single-step, multi-step (UNROLL) and multi-step with the
+// tendons) go through per-actuator sums.  Production physics + env epilogue: single-step, multi-step (UNROLL) and multi-step with the
 // actor inside (UNROLL + ACTOR); everything DYN-specific is re-derived per substep, so the multi-step loop carries nothing extra for it.
+// One diagnostic instance, DBG x DYN, single-step: the dump with the contact sections per candidate pair (contact_geometry_dyn).
 // JRES: this instance may hold the solve-job descriptors in registers for the substep (RR_JOBS_RESIDENT; not the debug-dump instances, whose
 // dump paths leave no room for them)
 // MRES: how much of the inverse factor this instance may hold in registers next to them (RR_SOLVE_MAT_RESIDENT; Wave::MAT_RES): 0 nothing,
@@ -1837,24 +1841,55 @@ struct Wave {
     pos = pa + n * (rad[0] + 0.5f * dist);
     return dist;
   }
-  __device__ __forceinline__ void contact_geometry_dyn() {
+  // dbg / o_dist / o_pos / o_frame: the debug-dump instance only (compile-time null in every other one).  The dump's contact sections
+  // are per CANDIDATE PAIR: dist / pos / frame of every pair come from the scan's own pair_geometry() call, the one whose sign selects the
+  // pair; con_D / con_aref of a pair that holds a slot are its slot's (written below and in constraint_rows), of every other pair 0.
+  // Behind kernarg_ok: pen_count (pairs in penetration before the clamp to the slots) and slot_pair[WC] (pair id by slot, -1 beyond).
+  __device__ __forceinline__ void contact_geometry_dyn(float* dbg = nullptr, float* o_dist = nullptr, float* o_pos = nullptr, float* o_frame = nullptr) {
     const RRTables T = tables();
     const DT D = phase_dims();   // the run-time scalars this phase reads (dt, gravity, schedule lengths): local to it, like T
     int count = 0;
     for (int p0 = 0; p0 < D.ncon; p0 += RR_LANES) {          // scan: which candidate pairs are in penetration
       const int p = p0 + lane;
       bool pen = false;
-      if (p < D.ncon) { v3 pos_, n_; pen = pair_geometry(T, p, pos_, n_) < 0.0f; }
+      if (p < D.ncon) {
+        v3 pos_, n_;
+        const float dist_ = pair_geometry(T, p, pos_, n_);
+        pen = dist_ < 0.0f;
+        if (dbg || o_dist || o_pos || o_frame) {
+          const v3 yb = (n_.y > -0.5f && n_.y < 0.5f) ? mk3(0, 1, 0) : mk3(0, 0, 1);       // make_frame(n), as the slots form it below
+          v3 fb = yb - n_ * dot(n_, yb);
+          fb = fb * (1.0f / sqrtf(dot(fb, fb)));
+          const v3 fc = cross(n_, fb);
+          if (dbg) {
+            dbg[D.g_con_dist + p] = dist_;
+            st3(dbg + D.g_con_pos + 3 * p, pos_);
+            st3(dbg + D.g_con_frame + 9 * p, n_); st3(dbg + D.g_con_frame + 9 * p + 3, fb); st3(dbg + D.g_con_frame + 9 * p + 6, fc);
+          }
+          if (o_dist) o_dist[p] = dist_;
+          if (o_pos) st3(o_pos + 3 * p, pos_);
+          if (o_frame) { st3(o_frame + 9 * p, n_); st3(o_frame + 9 * p + 3, fb); st3(o_frame + 9 * p + 6, fc); }
+        }
+      }
       const unsigned long long mk = __ballot(pen);
+      bool slotted = false;
       if (pen) {
         const int slot = count + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mk >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mk, 0u));
         if (slot < WC) s_jlist[slot] = p;
+        slotted = slot < WC;
+      }
+      if (dbg && p < D.ncon && !slotted) {      // no cell is written twice: a slotted pair's cells are its slot's to write
+        dbg[D.g_con_D + p] = 0.0f;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) dbg[D.g_con_aref + 4 * p + k] = 0.0f;
       }
       count += __popcll(mk);
     }
+    if (dbg && lane == 0) dbg[D.g_kaok + RR_DBG_PEN_COUNT] = (float)count;
     dyn_overflow |= count > WC ? 1 : 0;
     if (count > WC) count = WC;
     sync();
+    if (dbg) for (int slot = lane; slot < WC; slot += RR_LANES) dbg[D.g_kaok + RR_DBG_SLOT_PAIR + slot] = slot < count ? (float)s_jlist[slot] : -1.0f;
 #pragma unroll
     for (int cs = 0; cs < NCS; ++cs) {
       const int slot = lane + RR_LANES * cs;
@@ -1883,6 +1918,7 @@ struct Wave {
         const float rr = fmaxf(cf[21] * (1.0f - imp) / imp, RR_MINVAL);
         con_mu[cs] = con_nrow[cs] == 1 ? 0.0f : cf[20]; con_D[cs] = 1.0f / rr;
         con_kk[cs] = k * imp * dist; con_b[cs] = bcoef;
+        if (dbg) dbg[D.g_con_D + p] = con_D[cs];
         const v3 off = pos - get_com(ci[3]);
         con_off[cs][0] = off.x; con_off[cs][1] = off.y; con_off[cs][2] = off.z;
         con_fr[cs][0] = n.x; con_fr[cs][1] = n.y; con_fr[cs][2] = n.z;
@@ -1929,10 +1965,10 @@ struct Wave {
 #pragma unroll
         for (int k = 0; k < 4; ++k) con_aref[cs][k] = -con_b[cs] * jq[cs][k] - con_kk[cs];
       }
-      const int c = lane + RR_LANES * cs;
-      if (dbg && c < D.ncon) {
+      const int c = DYN ? con_pid[cs] : lane + RR_LANES * cs;      // DYN: the dump is per candidate pair; the pairs without a slot hold 0 (contact_geometry_dyn)
+      if (dbg && (DYN ? con_act[cs] : c < D.ncon)) {
 #pragma unroll
-        for (int k = 0; k < 4; ++k) dbg[D.g_con_aref + 4 * c + k] = con_aref[cs][k];
+        for (int k = 0; k < 4; ++k) dbg[D.g_con_aref + 4 * c + k] = (!DYN || k < con_nrow[cs]) ? con_aref[cs][k] : 0.0f;
       }
     }
   }

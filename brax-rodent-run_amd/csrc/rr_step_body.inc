@@ -3,7 +3,7 @@
 // compile-time switches NBS, NVS, NCS, PROF, DBG, DT, NEWTON, UNROLL, ACTOR, PAIR, DYN, RAND, EVAL, POSE, REFOBS, PTERM, BODY, RESTART, MRES, ROOTSLOT.
 // Why text and not a function: see the note above rr_step_kernel.
   static_assert(!PAIR || (!PROF && !DBG && !NEWTON && !UNROLL && !ACTOR), "PAIR: production physics instance only");
-  static_assert(!DYN || (!PROF && !DBG && !NEWTON && !PAIR), "DYN: production instances only (single-step, multi-step, multi-step with the actor)");
+  static_assert(!DYN || (!PROF && !NEWTON && !PAIR && (!DBG || (!UNROLL && !ACTOR))), "DYN: production instances (single-step, multi-step, multi-step with the actor) and the single-step debug dump");
   static_assert(!ACTOR || UNROLL, "the actor lives in the multi-step instances");
   static_assert(!POSE || (!RAND && !EVAL && !PROF && !DBG && !NEWTON && !PAIR && !DYN), "POSE: production CG instances of the floor-contact models only");
   static_assert(!REFOBS || POSE, "REFOBS: a form of the pose instances (the blocks are rows of track_pose)");
@@ -242,7 +242,7 @@
         op = io.o_cpos ? io.o_cpos + (size_t)env * 3 * D.ncon : nullptr;
         of = io.o_cframe ? io.o_cframe + (size_t)env * 9 * D.ncon : nullptr;
       }
-      if (DYN) w.contact_geometry_dyn();
+      if (DYN) w.contact_geometry_dyn(dg, od, op, of);
       else w.contact_geometry(dg, od, op, of);
     }
     w.velocity_sweep();

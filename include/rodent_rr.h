@@ -63,7 +63,11 @@ typedef struct rr_outputs {
   float* subtree_com;   /* [N][3]  (root 0) */
   float* debug;         /* [N][dims.dbg_floats], see rr_debug_layout; NULL in production */
   /* contact geometry of the last forward pass (mjx.Data.contact.{dist,pos,frame}; brax State.contact
-   * [NB mjcf.ipynb:917-921]); the integer fields geom1 / geom2 / link_idx are static: rr_model_table */
+   * [NB mjcf.ipynb:917-921]); the integer fields geom1 / geom2 / link_idx are static: rr_model_table.
+   * Models with candidate-pair contacts (rodent_cpu.xml): ncon is the number of candidate pairs and every pair has its entry, in
+   * penetration or not, as in MJX -- the values of the very pair_geometry evaluation whose sign selects the pairs that take a slot.
+   * `debug` and these three are served by the debug-dump instance, single-step launches only (rr_pipeline_step, rr_env_step,
+   * rr_env_reset); the multi-step forms, the profile build and the Newton solver refuse them. */
   float* contact_dist;  /* [N][ncon]   */
   float* contact_pos;   /* [N][ncon*3] */
   float* contact_frame; /* [N][ncon*9]: rows normal, tangent 1, tangent 2 */
@@ -806,7 +810,12 @@ int rr_batch_set_env_params(rr_batch* b, const rr_env_params* p);
 /* 1 when rr_batch_set_env_params can serve this batch's model / solver, 0 otherwise */
 int rr_batch_env_params_supported(const rr_batch* b);
 
-/* Debug dump layout: names[i] begins at float offsets[i] of each env's debug row; returns the field count. */
+/* Debug dump layout: names[i] begins at float offsets[i] of each env's debug row; returns the field count.
+ * Models with candidate-pair contacts keep the shared layout, with the contact sections per CANDIDATE PAIR (ncon pairs): con_dist, con_pos
+ * and con_frame of every pair, bit for bit what rr_outputs.contact_* receive; con_D and con_aref (4 rows; a condim-1 pair has one, its
+ * other three cells hold 0) of the pairs that hold a contact slot, 0 for every other pair.  Two sections follow kernarg_ok for these models
+ * only: pen_count (1: the pairs in penetration BEFORE the clamp to the 64 slots) and slot_pair (64: the pair id held by each slot, -1
+ * beyond the count).  Integers are stored as floats (exact: ids are below 2^24). */
 int rr_debug_layout(const rr_batch* b, const char*** names, const int32_t** offsets, const int32_t** sizes);
 
 /* Diagnostic, debug-dump launches only (rr_outputs.debug or the contact-geometry outputs): the line search leaves its bracketing loop

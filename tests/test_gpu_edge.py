@@ -211,7 +211,7 @@ LAUNCH_FORMS = {
     ("rodent_0", "cg"): _ALL,                     # (2,2,1) slot counts, generic dimensions
     ("rodent_new", "cg"): _ALL,                   # fixed-dimension instances
     ("rodent_optimized", "cg"): _ALL,
-    ("rodent_cpu", "cg"): dict(debug=NO_DIAG, profile=NO_DIAG, unroll=None, eval=None, params=SKIP),          # candidate-pair contacts
+    ("rodent_cpu", "cg"): dict(debug=None, profile=NO_DIAG, unroll=None, eval=None, params=SKIP),             # candidate-pair contacts
     ("rodent_pair", "cg"): dict(debug=None, profile=NO_DIAG, unroll="multi-step", eval=SKIP, params=SKIP),    # (3,3,2) + the two-wave pair instance
     ("rodent_0", "newton"): _NEWTON,
     ("rodent_new", "newton"): _NEWTON,

@@ -88,6 +88,100 @@ def test_forward_stages_match_oracle(model_name, oracle_built):
     assert not bad, bad
 
 
+def test_forward_stages_match_oracle_candidate_pairs(oracle_built):
+    """rodent_cpu, the model with candidate-pair contacts, through the debug-dump instance of the DYN kernel: a sibling of the test above,
+    because the model has no floor and no free joint (no settled states) and its contact sections are per candidate pair.  Colliding
+    poses inside the joint limits (tests/pair_contact_cases.py); the STAGES bounds unchanged on every stage up to con_dist -- the
+    hinge-root kinematics and the tendon transmission (qfrc_actuator) among them, and on con_pos of the pairs with a sphere and con_frame
+    of the sphere-sphere pairs.  The rest of con_pos / con_frame, and the slots: tests/test_gpu_pair_contacts.py, under a criterion that
+    knows the ill-conditioned capsule pairs (the float32 oracle itself is 7e-4 off on their normals).  The sections STAGES does not name are held to 3x the worse of the oracle's two float32 builds + 2^-22
+    of the field's scale (the form of tests/smooth_regime.py); the limit rows and the solver's sections as in the tests around."""
+    from rodent_amd import assets, hip
+    from tests import pair_contact_cases as pc
+    N = pc.N
+    st, ctrl = pc.inputs("shipped", pc.MODEL, seed=5)
+    st = pc.beyond_limits(st, seed=6)                           # three hinges per env past an end of their range: limit rows
+    dev = torch.device("cuda:0")
+    batch = hip.Batch(hip.Model(assets.asset_path(pc.MODEL), iterations=8, ls_iterations=8), N, dev)
+    ds = _to_dev(st, dev)
+    dbg = torch.zeros(N, batch.dims.dbg_floats, device=dev)
+    batch.pipeline_step(ds, torch.tensor(ctrl, dtype=torch.float32, device=dev), 1, out=dict(debug=dbg))
+    torch.cuda.synchronize()
+    lay = batch.debug_layout()
+    dbg = dbg.cpu().numpy().astype(np.float64)
+    sec = lambda name: dbg[:, lay[name][0]:lay[name][0] + lay[name][1]]
+    O = {p: pc.PairOracle(pc.MODEL, N, p).forward(st, ctrl) for p in ("f64", "f32", "f32fma")}
+    A = O["f64"]
+    m = pc.shipped()
+    nb, nlimit = int(m["nbody"]), A.M.nlimit
+    assert int((A.get("con_dist") < 0).sum()) > N               # the scenario exercises contacts
+    worst = {}
+    for name, oname, tol in STAGES:
+        if name not in ("con_pos", "con_frame"):                # by kind, below
+            worst[name] = max(_rel(sec(name)[e], A.get(oname)[e]) for e in range(N))
+    tol = {n: t for n, _, t in STAGES}
+    # con_pos / con_frame under their STAGES bounds where an independent float32 evaluation can meet them: the position of the pairs with a
+    # sphere (kinds 4, 5), the frame of the sphere-sphere pairs (the float32 oracle: 1.4e-7 m, 6.2e-7; sphere-capsule frames 3.2e-6)
+    kind, P = np.asarray(m["con_kind"]), A.M.ncon
+    for name, width, kinds in (("con_pos", 3, (4, 5)), ("con_frame", 9, (4,))):
+        g, w = sec(name).reshape(N, P, width)[:, np.isin(kind, kinds)], A.get(name).reshape(N, P, width)[:, np.isin(kind, kinds)]
+        worst[name] = max(_rel(g[e], w[e]) for e in range(N))
+    # rows of the pairs in penetration in both evaluations, by pair (condim 1: one row)
+    wD, wa = A.rows(m)
+    both = (A.get("con_dist") < -2e-6) & (sec("con_dist") < 0)
+    assert both.sum() > N
+    worst["con_D"], worst["con_aref"] = _rel(sec("con_D")[both], wD[both]), _rel(sec("con_aref").reshape(N, P, 4)[both], wa[both])
+    tol.update(con_D=2e-4, con_aref=4e-5)
+    # limit rows (every hinge is limited): activity exact away from the switching point, D / aref of the active rows
+    lim_dof = m["jnt_dofadr"][m["limit_jnt"]]
+    lim = sec("limit_pos_D_aref").reshape(N, -1, 3)[:, lim_dof]
+    lpos = A.get("efc_pos")[:, :nlimit]
+    assert np.array_equal((lim[:, :, 0] < 0)[np.abs(lpos) > 2e-6], (lpos < 0)[np.abs(lpos) > 2e-6])
+    la = lpos < -2e-6
+    assert la.sum() > N                                         # ... and joint limits (corner poses)
+    worst["lim_D"] = _rel(lim[:, :, 1][la], A.get("efc_D")[:, :nlimit][la])
+    worst["lim_aref"] = _rel(lim[:, :, 2][la], A.get("efc_aref")[:, :nlimit][la])
+    tol.update(lim_D=2e-4, lim_aref=4e-5)
+    # sections without a STAGES bound: the yardstick of the run
+    root = A.get("subtree_com").reshape(N, nb, 3)[:, 1]
+    extra = {"subtree_com": (sec("subtree_com")[:, :3], lambda o: o.get("subtree_com").reshape(N, nb, 3)[:, 1]),
+             "cfrc": (sec("cfrc"), lambda o: np.concatenate([np.zeros((N, 6)), o.get("cfrc")[:, 6:]], 1)),
+             "qLDiagInv": (sec("qLDiagInv"), lambda o: o.get("qLDiagInv"))}
+    assert np.abs(root).max() > 0 and (sec("subtree_com")[:, 3:] == 0).all()      # one tree: the second tree's cells hold 0
+    for name, (got, f) in extra.items():
+        want = f(A)
+        scale = np.abs(want).max()
+        worst[name] = np.abs(got - want).max() / scale
+        tol[name] = 3.0 * max(np.abs(f(O[p]) - want).max() / scale for p in ("f32", "f32fma")) + 2.0 ** -22
+    # the solver's sections: qacc is what the launch hands on, bit for bit; bounds of test_solver_and_substep_match_oracle below
+    assert np.array_equal(sec("qacc").astype(np.float32), ds["qacc_warmstart"].cpu().numpy())
+    # ... and, like qfrc_constraint, the result of a truncated CG run with rows active: heavy-tailed against float64 whoever computes it
+    # (tests/parity.py), so by C3 -- the median and the 90th percentile of the per-env error within 3x the worse float32 build's + floor
+    from tests import parity
+    niter, rows = sec("niter_cost")[:, 0], []
+    # floors as parity.SUBSTEP_FLOORS["qacc"]: a few float32 ulps of a quantity scaled to 1 (each of these errors is divided by its env's scale)
+    floors = dict(qacc=parity.SUBSTEP_FLOORS["qacc"], qfrc_constraint=2e-6, solver_cost=2e-6)
+    dumped = dict(qacc=sec("qacc"), qfrc_constraint=sec("qfrc_constraint"), solver_cost=sec("niter_cost")[:, 1:2])
+    for name, floor_scale in (("qacc", 1.0), ("qfrc_constraint", 1e-3), ("solver_cost", 1.0)):
+        want = A.get(name).reshape(N, -1)
+        sc = np.maximum(np.abs(want).max(1), floor_scale)
+        gaps = [np.abs(O[p].get(name).reshape(N, -1) - want).max(1) / sc for p in ("f32", "f32fma")]
+        for q in (0.5, 0.9):
+            rows.append((name, q, float(np.quantile(np.abs(dumped[name] - want).max(1) / sc, q)), max(float(np.quantile(g, q)) for g in gaps)))
+    print("worst relative error per stage:", {k: f"{v:.2e} ({tol[k]:.1e})" for k, v in worst.items()}, "| (section, q, err, float32 oracle)", rows)
+    parity.check_quantiles(rows, floors)
+    print("iteration count against the float32 oracle's where float64 iterates: equal, within one",
+          pc.assert_iteration_counts(niter, A.get("solver_niter")[:, 0], O["f32"].get("solver_niter")[:, 0]))      # C2 on this model
+    assert (sec("kernarg_ok") == 1).all()
+    ls, end = sec("ls_iters"), sec("solver_end").astype(int)
+    assert (ls >= 0).all() and (ls == np.round(ls)).all()
+    # solver_end: [0] which start was chosen; [1] how the loop ended, a sum of 1 (iteration cap), 2 (improvement), 4 (gradient): never 0
+    assert np.isin(end[:, 0], (0, 1)).all() and (end[:, 1] >= 1).all() and (end[:, 1] <= 7).all()
+    assert np.array_equal(end[:, 1] & 1, (niter >= 8).astype(int))
+    bad = {k: v for k, v in worst.items() if not v <= tol[k]}
+    assert not bad, bad
+
+
 @pytest.mark.parametrize("model,instance", [("rodent_optimized", "debug_dump"), ("rodent_optimized", "production"),
                                             ("rodent_new", "production"), ("rodent_pair", "production")])
 def test_solver_and_substep_match_oracle(oracle_built, model, instance):

@@ -8,8 +8,9 @@ import pytest
 import torch
 
 from rodent_amd import assets, mjcf
+from tests import pair_contact_cases as pc
 from tests import parity, util
-from tests.hip_impl import HipImpl, NoDiscrete
+from tests.hip_impl import HipImpl
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -41,26 +42,48 @@ def _colliding_inputs(ref, n_envs, steps, seed):
 
 
 def test_teacher_forced_substeps_with_self_collisions(oracle_built):
+    """Through the debug-dump instance: con_dist, the limit rows and the iteration count the criteria judge are the kernel's own."""
     N = 8
     seq, tab = _colliding_inputs(oracle_built, N, 40, seed=11)
     A = parity.OracleImpl("rodent_cpu", N, "f64", (8, 8))
     B = parity.OracleImpl("rodent_cpu", N, "f32", (8, 8))
     nact = sum(int((A.substep(st, c)["con_dist"] < 0).sum()) for st, c in seq[:10])
     assert nact >= 20                                       # the sample does exercise the contacts
-    impl = HipImpl("rodent_cpu", N, (8, 8), False)
-    out = parity.substep_ladder(NoDiscrete(impl, A), seq, A, B)
-    print(out["quantiles"])
-    parity.check_quantiles(out["quantiles"], parity.SUBSTEP_FLOORS)
-    assert impl.batch.contact_overflow() == 0                # never more than 64 pairs in penetration: nothing was dropped
+    hip_impl = HipImpl("rodent_cpu", N, (8, 8), True)
+    impl, A, B = pc.Recording(hip_impl), pc.Recording(A), pc.Recording(B)
+    out = parity.substep_ladder(impl, seq, A, B)
+    print(out["quantiles"], "niter equal", out["niter_equal"], "(float32 oracle: %g)" % out["niter_equal_f32_oracle"], "limit rows", out["limit_rows"])
+    print("iteration count against the float32 oracle's where float64 iterates: equal, within one", pc.assert_substep_criteria(out, impl, A, B))
+    assert hip_impl.batch.contact_overflow() == 0            # never more than 64 pairs in penetration: nothing was dropped
 
 
-def test_contact_slot_overflow_is_counted(oracle_built):
+def test_teacher_forced_substeps_with_sphere_sphere_contacts(oracle_built, tmp_path):
+    """The same ladder on the `spheres` variant (tests/pair_contact_cases.py): 10 x 8 substeps with sphere-sphere pairs among the contacts."""
+    N = 8
+    stem = pc.blob("spheres", tmp_path)
+    seq = [pc.inputs("spheres", stem, n=N, seed=30 + t) for t in range(10)]
+    A = parity.OracleImpl(stem, N, "f64", (8, 8))
+    B = parity.OracleImpl(stem, N, "f32", (8, 8))
+    k4 = mjcf.load_blob(assets.asset_path("rodent_cpu"))["con_kind"] == 4
+    assert sum(int((A.substep(st, c)["con_dist"][:, k4] < 0).sum()) for st, c in seq) >= 10
+    hip_impl = HipImpl(stem, N, (8, 8), True)
+    impl, A, B = pc.Recording(hip_impl), pc.Recording(A), pc.Recording(B)
+    out = parity.substep_ladder(impl, seq, A, B)
+    print(out["quantiles"], "niter equal", out["niter_equal"], "(float32 oracle: %g)" % out["niter_equal_f32_oracle"], "limit rows", out["limit_rows"])
+    print("iteration count against the float32 oracle's where float64 iterates: equal, within one", pc.assert_substep_criteria(out, impl, A, B))
+    assert hip_impl.batch.contact_overflow() == 0
+
+
+@pytest.mark.parametrize("variant", ["shipped", "overflow"])
+def test_contact_slot_overflow_is_counted(oracle_built, tmp_path, variant):
     """A pose with every joint at the same end of its range folds the animal into itself: if more than 64 pairs penetrate, the surplus is
-    dropped for that substep and the batch's overflow counter says so (the state stays finite either way)."""
+    dropped for that substep and the batch's overflow counter says so (the state stays finite either way).  The shipped model stays
+    below 64 within its limits; the `overflow` variant (every radius x 3, tests/pair_contact_cases.py) is far above."""
     N = 4
     tab = mjcf.load_blob(assets.asset_path("rodent_cpu"))
-    impl = HipImpl("rodent_cpu", N, (8, 8), False)
-    M = oracle_built.RefModel(assets.asset_path("rodent_cpu"), "f64")
+    stem = pc.blob(variant, tmp_path)
+    impl = HipImpl(stem, N, (8, 8), False)
+    M = oracle_built.RefModel(assets.asset_path(stem), "f64")
     d = oracle_built.RefData(M)
     worst, q_worst = 0, None
     for sgn in (0, 1):
@@ -69,12 +92,14 @@ def test_contact_slot_overflow_is_counted(oracle_built):
         n = int((d.get("con_dist") < 0).sum())
         if n > worst:
             worst, q_worst = n, q
+    assert (worst > 64) == (variant == "overflow"), worst
     st = dict(qpos=np.tile(q_worst, (N, 1)), qvel=np.zeros((N, 67)), act=np.zeros((N, 38)), qacc_warmstart=np.zeros((N, 67)))
     ds = impl._dev(st)
     impl.batch.pipeline_step(ds, torch.zeros(N, 38, device=DEV), 1)
     torch.cuda.synchronize()
     assert all(torch.isfinite(v).all() for v in ds.values())
     assert (impl.batch.contact_overflow() > 0) == (worst > 64), (worst, impl.batch.contact_overflow())
+    assert impl.batch.contact_overflow() == (N if worst > 64 else 0)
 
 
 def test_contacts_act_and_results_are_deterministic(oracle_built):
